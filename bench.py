@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Benchmark of the ComMU Transformer-XL training hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the headline; --dump-outputs DIR writes the last timed step's
+loss and updated parameters (float32 .npy, seeded inputs: the same arguments give the same inputs); --full adds the
+per-kernel rooflines, the extra shape rows, the decode rows and the CPU baselines.
 N > 1 without a torch.distributed environment: this process starts the N ranks ITSELF (`python -m torch.distributed.run
 --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` as a child, before touching the GPU), relays rank 0's line
 and exits with the child's status; under `torch.distributed.run` (WORLD_SIZE set) it is one rank.  One rank per GPU over
@@ -338,11 +341,40 @@ def auto_graph(args):
 
 
 LAST_COMM = {}          # rank-local GradReducer.comm_stats() of the last train_bench (N > 1 only)
+DUMP_BYTES = 64_000_000          # --dump-outputs: bytes of all .npy files together, headers included
 
 
-def train_bench(args, dev, world, rank, steps, warmup, reset_prob=0.0):
+def step_outputs(loss, model):
+    """What one optimiser step hands its caller, copied to the host in fp32: the step's loss (Trainer.step's return value)
+    and every parameter after the update (the fp32 master weights, in named_parameters order)."""
+    out = {"loss": loss.detach().float().reshape(1).cpu().numpy()}
+    for name, p in model.named_parameters():
+        out["param." + name] = p.detach().float().cpu().numpy()
+    return out
+
+
+def write_outputs(dirname, arrays, limit=DUMP_BYTES, seed=0):
+    """--dump-outputs: each array as DIR/<name>.npy in float32.  Arrays that together exceed `limit` are all cut to the
+    same share of their elements, at flat indices drawn from a generator seeded with `seed` (sorted; the same shapes give
+    the same indices), so that two builds can still be compared file for file."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(a.size for a in arrays.values())
+    room = limit - 256 * len(arrays)          # (.npy header and the at-least-one element of a sampled array)
+    share = min(1.0, room / (4.0 * max(total, 1)))
+    rng = np.random.default_rng(seed)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float32)
+        if share < 1.0:
+            idx = np.sort(rng.choice(a.size, size=max(1, int(a.size * share)), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def train_bench(args, dev, world, rank, steps, warmup, reset_prob=0.0, profile=True, outputs=None):
     """W untimed + K timed optimiser steps of the shape in `args`; returns (elapsed seconds (max over ranks),
-    tokens per step per rank, per-entry-point HIP-event times) -- None on ranks other than 0."""
+    tokens per step per rank, per-entry-point HIP-event times (None unless `profile`), their scale to the timed steps).
+    outputs: a dict that receives what the LAST timed step handed its caller, on the host (see step_outputs)."""
     from commu_amd import _lib
     from commu_amd.ddp import GradReducer
     from commu_amd.model.config_helper import get_cfg
@@ -382,12 +414,14 @@ def train_bench(args, dev, world, rank, steps, warmup, reset_prob=0.0):
                 gc_log.append((len(step_log), info["generation"], round(1e3 * (time.perf_counter() - _t[0]), 2)))
         gc.callbacks.append(_gc_cb)
 
+    last_loss = [None]
+
     def run(nsteps, base, sample_events=False):
         for i in range(nsteps):
             d, t, r, n = batches[(base + i) % len(batches)]
             if step_log is not None:
                 th = time.perf_counter()
-            trainer.step(d, t, r, n)
+            last_loss[0] = trainer.step(d, t, r, n)
             if step_log is not None:
                 step_log.append(round(1e3 * (time.perf_counter() - th), 2))
 
@@ -415,6 +449,8 @@ def train_bench(args, dev, world, rank, steps, warmup, reset_prob=0.0):
               f"host ms per step() {step_log}; gc (step, generation, ms) {[g for g in gc_log if g[2] >= 1.0]}; reserved {ms['reserved_bytes.all.current'] >> 20} MiB, segments "
               f"{ms['segment.all.allocated']}, retries {ms['num_alloc_retries']}", file=sys.stderr, flush=True)
         gc.callbacks.remove(_gc_cb)
+    if outputs is not None:
+        outputs.update(step_outputs(last_loss[0], trainer.model))
     LAST_COMM.clear()
     if reducer is not None:
         # attribution for the scaling curve: wire bytes per rank and step, and the time the main stream sat in
@@ -424,16 +460,18 @@ def train_bench(args, dev, world, rank, steps, warmup, reset_prob=0.0):
     # streams): an event pair around each of the ~130 profiled calls costs ~4 % of a step, which used to sit inside the
     # number the driver reports (every fourth step).  hipGraph mode: a replay has no per-call hooks, so these steps run
     # eagerly -- same kernels, same streams.
-    prof_names = ["commu_relattn_bwd_kv", "commu_relattn_bwd_q", "commu_relattn_fwd", "commu_relattn_fwd_save", "commu_gemm_nt_bf16",
-                  "commu_gemm_tn_bf16", "commu_gemm_tn_bf16_grouped", "commu_relattn_bwd_band"]
-    nprof = max(2, (steps + 3) // 4)
-    _lib.profile_start(prof_names, shape_args={"commu_gemm_nt_bf16": (6, 7, 8)})          # (M, N, K) of every NT GEMM
-    _lib.profile_enable(True)
-    trainer.graph_mode = False
-    run(nprof, warmup + steps)
-    torch.cuda.synchronize()
-    trainer.graph_mode = use_graph
-    prof = _lib.profile_stop()
+    prof, nprof = None, steps
+    if profile:
+        prof_names = ["commu_relattn_bwd_kv", "commu_relattn_bwd_q", "commu_relattn_fwd", "commu_relattn_fwd_save",
+                      "commu_gemm_nt_bf16", "commu_gemm_tn_bf16", "commu_gemm_tn_bf16_grouped", "commu_relattn_bwd_band"]
+        nprof = max(2, (steps + 3) // 4)
+        _lib.profile_start(prof_names, shape_args={"commu_gemm_nt_bf16": (6, 7, 8)})          # (M, N, K) of every NT GEMM
+        _lib.profile_enable(True)
+        trainer.graph_mode = False
+        run(nprof, warmup + steps)
+        torch.cuda.synchronize()
+        trainer.graph_mode = use_graph
+        prof = _lib.profile_stop()
     if world > 1:
         tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -722,7 +760,17 @@ def main():
                          "on the wire with fp32 summation (all-to-all + all-gather, half the bytes)")
     ap.add_argument("--no-side-stream", action="store_true",
                     help="weight-gradient work on the main stream (default: a side stream)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel HIP-event steps and the rooflines, the step's HBM traffic from the "
+                         "committed profiles, the exchange statistics of an N > 1 job, the iterator-fed step, the extra shape "
+                         "rows, the decode rows and the CPU baselines (each still subject to its --no-* switch); "
+                         "default: set up, warm up, time the steps, print the headline line")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one handed its caller (loss, updated parameters) as "
+                         f"DIR/<name>.npy in float32, at most {DUMP_BYTES // 10 ** 6} MB in all (a fixed, seeded sample beyond)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -744,17 +792,22 @@ def main():
             raise SystemExit(f"--global-batch {args.global_batch} is not divisible by {world} ranks (train.py:396)")
         args.batch_per_gpu, scaling = args.global_batch // world, "strong"
     B = args.batch_per_gpu
-    elapsed, tokens_per_step, prof, pscale = train_bench(args, dev, world, rank, args.steps, args.warmup)
+    outputs = {} if args.dump_outputs and rank == 0 else None
+    elapsed, tokens_per_step, prof, pscale = train_bench(args, dev, world, rank, args.steps, args.warmup,
+                                                         profile=args.full, outputs=outputs)
     if rank != 0:
         if world > 1:
             dist.destroy_process_group()
         return
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs)
 
     ms_per_step = 1e3 * elapsed / args.steps
     value = tokens_per_step * world * args.steps / elapsed
     L, D, DI, T, M, H = args.layers, args.d_model, args.d_inner, args.tgt_len, args.mem_len, args.heads
     f_fwd = fwd_flops_per_token(L, D, DI, T, M)
     step_flops = 3.0 * f_fwd * tokens_per_step
+    use_graph = args.graph if args.graph is not None else auto_graph(args)
     out = {
         "metric": "training tokens/sec at d_model=512 tgt_len=1024",
         "value": round(value, 1), "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -764,14 +817,27 @@ def main():
                    "global_batch": B * world, "batch_per_gpu": B, "batch_chunk": args.batch_chunk,
                    "passes_per_step": passes_of(args), "seq_len": T,
                    "dropout": args.dropout, "parallelism": f"dp{world}", "optimizer": "clip1.0+Adam+invsqrt-LR",
-                   "launch": ("hipGraph replay (the per-kernel events come from eager steps after the timed region)"
-                              if (args.graph if args.graph is not None else auto_graph(args)) else "eager"),
+                   "launch": ("eager" if not use_graph else "hipGraph replay (the per-kernel events come from eager steps "
+                              "after the timed region)" if args.full else "hipGraph replay"),
                    "weights": "random init (train.py:291-342)"},
         "step_tflops_algorithmic": round(step_flops / 1e12, 3),
         "step_mfma_frac": round(step_flops / (elapsed / args.steps) / (BF16_MFMA_PEAK_TFLOPS * 1e12), 4),
-        "roofline": attention_roofline(args, prof, tokens_per_step, elapsed, pscale),
-        "roofline_gemm": gemm_roofline(prof, elapsed, pscale),
     }
+    if args.full:
+        # (a plain run stops at the headline: these figures take runs of their own and are measured with --full only)
+        full_rows(args, dev, world, out, elapsed, tokens_per_step, prof, pscale)
+    elif world == 1 and args.from_iterator:
+        out["iterator_fed"] = iterator_bench(args, dev, args.steps, args.warmup, ms_per_step)
+    print(json.dumps(out), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_rows(args, dev, world, out, elapsed, tokens_per_step, prof, pscale):
+    """Everything --full adds to the line `out`, in place."""
+    ms_per_step = 1e3 * elapsed / args.steps
+    out["roofline"] = attention_roofline(args, prof, tokens_per_step, elapsed, pscale)
+    out["roofline_gemm"] = gemm_roofline(prof, elapsed, pscale)
     # the step's SECOND roofline: measured HBM bytes per step (PMC, committed profile) / this run's step time against the
     # 8 TB/s peak -- the K = 512 GEMMs, LayerNorms and the attention scratch are memory-side work the MFMA fraction hides
     st = step_traffic(args) if world == 1 else None
@@ -803,9 +869,6 @@ def main():
             out["decode"]["cpu_baseline"] = decode_cpu_baseline(args)
     if world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args)
-    print(json.dumps(out), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

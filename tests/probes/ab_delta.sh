@@ -6,7 +6,7 @@ import os,sys,json,io,contextlib
 sys.path.insert(0,"commu-code_amd")
 from commu_amd import ops
 ops.DELTA_KERNEL = os.environ["COMMU_DELTA_KERNEL"]=="1"
-sys.argv=["bench.py","--steps","20","--warmup","5","--no-cpu-baseline","--no-decode","--no-extra"]
+sys.argv=["bench.py","--full","--steps","20","--warmup","5","--no-cpu-baseline","--no-decode","--no-extra"]
 buf=io.StringIO()
 with contextlib.redirect_stdout(buf):
     import runpy; runpy.run_path("bench.py", run_name="__main__")

@@ -33,7 +33,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, os.path.join(ROOT, "commu-code_amd"))
 from commu_amd import source_stamp          # the same stamp bench.py computes: a stale profile is refused
 out = {"shape": [6, 512, 8, 1024, 0, 64], "source_sha256": source_stamp.kernel_source_hash(), "switches": source_stamp.traffic_switches(), "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) on "
-       "`python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-decode --no-extra`; bytes = (2*FETCH_SIZE + WRITE_SIZE) KiB",
+       "`python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-decode --no-extra`; bytes = (2*FETCH_SIZE + WRITE_SIZE) KiB",
        "fetch_kib_raw": {KERNELS[k]: fetch[k] for k in fetch}, "write_kib_raw": {KERNELS[k]: write[k] for k in write},
        "bytes_per_launch": {KERNELS[k]: (2.0 * fetch.get(k, 0.0) + write.get(k, 0.0)) * 1024.0 for k in fetch}}
 json.dump(out, open(sys.argv[3], "w"), indent=1)

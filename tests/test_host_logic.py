@@ -390,6 +390,29 @@ def test_profile_stamp_covers_every_kernel_source_and_the_traffic_switches(tmp_p
         assert bench.step_traffic(args) is None
 
 
+def test_bench_dump_outputs_fit_the_limit_and_repeat(tmp_path):
+    """bench.py --dump-outputs: float32 files, whole arrays while they fit; past the limit every array is cut to the same
+    seeded sample, identical from run to run, and the files stay under the limit."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(3)
+    arrays = {"loss": np.array([6.5], dtype=np.float32), "param.w": rng.standard_normal((300, 200)),
+              "param.b": rng.standard_normal(7).astype(np.float32)}
+    bench.write_outputs(str(tmp_path / "whole"), arrays)
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "whole" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, a.astype(np.float32))
+    limit = 40_000
+    for run in ("a", "b"):
+        bench.write_outputs(str(tmp_path / run), arrays, limit=limit)
+        assert sum(f.stat().st_size for f in (tmp_path / run).iterdir()) <= limit
+    for name, a in arrays.items():
+        sa, sb = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert sa.dtype == np.float32 and np.array_equal(sa, sb) and 1 <= sa.size <= a.size
+        assert np.isin(sa, a.astype(np.float32)).all()
+    assert np.load(tmp_path / "a" / "param.w.npy").size < 300 * 200
+
+
 def test_strong_scaling_projection_arithmetic():
     """extra_rows.strong_b8...projection_8gpu_NOT_MEASURED: exchange = 2 (n-1)/n payload / (7 links x 153 GB/s x 0.7)."""
     import argparse
