@@ -155,6 +155,17 @@ PROTOTYPES = {
     "commu_relattn_f32": [c_p, c_i, c_p, c_p, C.c_longlong, C.c_longlong, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i,
                           c_i, c_i, c_i, c_i, c_i, c_f, c_p],
     "commu_decode_kv_append_f32": [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p],
+    "commu_gemm_f32": [c_i, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_f, C.c_uint, c_p, c_i, c_i, c_p, c_i,
+                       c_p],
+    "commu_relattn_fwd_f32": [c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
+                              c_f, c_f, C.c_uint, c_p],
+    "commu_relattn_bwd_f32": [c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p,
+                              c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_f, C.c_uint, c_p],
+    "commu_layernorm_fwd_f32": [c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_f, c_p],
+    "commu_layernorm_bwd_f32": [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_i, c_p],
+    "commu_ce_bwd_f32": [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p],
+    "commu_embed_bwd_f32": [c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_f, c_f, C.c_uint, c_p],
+    "commu_dropout_f32": [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_f, C.c_uint, c_p],
     "commu_hip_version": [],
 }
 _RESTYPE = {"commu_decode_tail_pack_bytes": C.c_longlong, "commu_attn_pf_bytes": C.c_longlong, "commu_hip_version": C.c_char_p, "commu_attn_p_scratch_elems": C.c_longlong,

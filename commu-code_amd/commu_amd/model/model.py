@@ -122,6 +122,12 @@ class _Saved:
                  "p", "patt", "seed")
 
 
+class _SavedF32:
+    """Activations of one fp32 training forward (_run_train_f32) kept for _run_backward_f32."""
+    __slots__ = ("T", "M", "B", "tokens", "target", "reset", "pd", "p", "patt", "seed", "same_length", "mem_len", "h", "cat",
+                 "qkv", "rd", "vec", "lse", "z1", "mu1", "rs1", "a", "hid", "z2", "mu2", "rs2", "hL", "logits", "ce_lse")
+
+
 class _XLLoss(torch.autograd.Function):
     """loss[T,B] = NLL of the whole network; backward runs the hand-written backward schedule."""
 
@@ -146,6 +152,31 @@ class _XLLoss(torch.autograd.Function):
         if dloss is None:          # (only new_mems was used downstream: nothing to differentiate)
             return (None,) * (5 + len(model._flat["params"]))
         grads = model._run_backward(saved, dloss.contiguous())
+        return (None, None, None, None, None) + grads
+
+
+class _XLLossF32(torch.autograd.Function):
+    """fp32 training mode (model.fp32_training): loss[T,B] of the fp32 forward; backward runs _run_backward_f32."""
+
+    @staticmethod
+    def forward(ctx, model, data, target, reset, mems, *params):
+        loss, new_mems, saved = model._run_train_f32(data, target, reset, mems)
+        ctx.model, ctx.saved = model, saved
+        ctx.set_materialize_grads(False)
+        if new_mems is None:
+            new_mems = torch.empty(0, device=data.device)
+        ctx.mark_non_differentiable(new_mems)
+        return loss, new_mems
+
+    @staticmethod
+    def backward(ctx, dloss, _dmems):
+        model, saved = ctx.model, ctx.saved
+        ctx.saved = None
+        if saved is None:
+            raise CommuHipError("backward called twice on the same forward")
+        if dloss is None:
+            return (None,) * (5 + len(model._flat["params"]))
+        grads = model._run_backward_f32(saved, dloss.contiguous())
         return (None, None, None, None, None) + grads
 
 
@@ -198,6 +229,9 @@ class MemTransformerLM(nn.Module):
         # "autograd" returns the gradients to autograd (compatible with torch DDP hooks).
         self.grad_mode = "direct"
         self._flat = None
+        # fp32 training (opt-in): a gradient-enabled forward and its backward in the reference's arithmetic -- fp32 master
+        # weights (no shadows, no padding), activations, memory and every backward contraction (csrc/train_f32.hip)
+        self.fp32_training = False
 
     # ------------------------------------------------------------------ reference API
     def reset_length(self, tgt_len, mem_len):                            # model.py:494-496
@@ -213,18 +247,26 @@ class MemTransformerLM(nn.Module):
     def forward(self, data, target, reset_mems, mems):                   # model.py:678-693
         if mems is None:
             mems = self.init_mems(self.n_layer)
+        grad = torch.is_grad_enabled() and any(p.requires_grad for p in self._param_list())
+        if grad and getattr(self, "fp32_training", False):
+            # the reference's training arithmetic (train.py:48 `amp = None`, :139-169): fp32 forward with dropout, fp32 backward
+            self._ensure_flat()
+            loss, new_mems = _XLLossF32.apply(self, data, target, reset_mems, mems, *self._flat["params"])
+            if mems is None:
+                new_mems = None
+            return loss, new_mems
         if getattr(self, "parity_fp32", False):
             # the reference's arithmetic (fp32 end to end, train.py:48 `amp = None`) for the LOSS of a forward pass --
-            # evaluate (train.py:74-110) and any no-grad forward; there is no fp32 backward pass
-            if torch.is_grad_enabled() and any(p.requires_grad for p in self._param_list()):
+            # evaluate (train.py:74-110) and any no-grad forward; the fp32 backward pass is model.fp32_training
+            if grad:
                 raise CommuHipError("parity_fp32 is a forward-only mode: call forward under torch.no_grad() (evaluate does), "
-                                    "or switch it off for training")
+                                    "or set model.fp32_training = True for an fp32 training pass")
             if self.training and (float(self.drop.p) > 0 or (self.n_layer > 0 and float(self.layers[0].dec_attn.dropatt.p) > 0)):
                 raise CommuHipError("parity_fp32 has eval-mode semantics (no dropout): call model.eval() first")
             with torch.no_grad():
                 nll, new_mems, _ = self._run_forward_f32(data, mems, reset=reset_mems, target=target)
             return nll, new_mems
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self._param_list()):
+        if grad:
             self._ensure_flat()
             loss, new_mems = _XLLoss.apply(self, data, target, reset_mems, mems, *self._flat["params"])
             if mems is None:
@@ -307,6 +349,186 @@ class MemTransformerLM(nn.Module):
             nll, _ = ops.ce_fwd(logits, target.contiguous().view(-1).to(dev), V)
             return nll.view(T, B), new_mems, (kv_out if want_kv else None)
         return logits.view(T, B, V), new_mems, (kv_out if want_kv else None)
+
+    # ------------------------------------------------------------------ fp32 training mode
+    def _run_train_f32(self, data, target, reset, mems):
+        """Gradient-enabled forward (model.py:540-604, 678-693) in the reference's arithmetic (model.fp32_training): fp32
+        master weights (no shadows, no padding), fp32 activations and memory, fp32 MFMA products, accurate transcendentals,
+        dropout in train() mode with the bf16 path's masks (same base seed, same site ids, same element indices).  Returns
+        (nll [T, B], new_mems fp32 [L+1, n, B, d_model] or None, saved activations for _run_backward_f32)."""
+        fl = self._ensure_flat()
+        dev = fl["dev"]
+        if not data.is_cuda:
+            raise CommuHipError("inputs must be GPU tensors (no CPU fallback)")
+        T, B = data.shape
+        D, H, DH, L, V = self.d_model, self.n_head, self.d_head, self.n_layer, self.n_token
+        HD = H * DH
+        M = 0 if mems is None or mems.numel() == 0 else mems.shape[1]
+        if M > 0 and (mems.dtype != F32 or not mems.is_contiguous()):
+            mems = mems.to(F32).contiguous()
+        K, TB = T + M, T * B
+        tokens = data.contiguous().view(-1)
+        rst = None
+        if reset is not None and M > 0:
+            rst = reset.to(device=dev, dtype=torch.uint8).contiguous()
+        # K16 dropout: the draw of _run_forward (one base seed per forward call, `fixed_drop_seed` included)
+        p = float(self.drop.p) if self.training else 0.0
+        patt = float(self.layers[0].dec_attn.dropatt.p) if (self.training and L > 0) else 0.0
+        seed = 0
+        if p > 0 or patt > 0:
+            fixed = getattr(self, "fixed_drop_seed", None)
+            seed = int(fixed) if fixed is not None else int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+
+        def ss(site):
+            return ops.site_seed(seed, site)
+        sv = _SavedF32()
+        E = self.word_emb.emb_layers[0].weight
+        h = ops.embed_f32(tokens, E)                                                        # model.py:585
+        if p > 0:
+            ops.dropout_f32(h, p, ss(0), out=h)
+        pd = ops.posemb_f32(self.pos_emb.inv_freq, K, D, clamp_len=int(self.clamp_len))    # :578-584 (by distance)
+        if p > 0:
+            ops.dropout_f32(pd, p, ss(1), out=pd)
+        u, vb = self.r_w_bias, self.r_r_bias
+        sv.T, sv.M, sv.B, sv.tokens, sv.reset, sv.pd, sv.p, sv.patt, sv.seed = T, M, B, tokens, rst, pd, p, patt, seed
+        sv.same_length, sv.mem_len = bool(self.same_length), int(self.mem_len)
+        for k in ("h", "cat", "qkv", "rd", "vec", "lse", "z1", "mu1", "rs1", "a", "hid", "z2", "mu2", "rs2"):
+            setattr(sv, k, [])
+        hids = [h]
+        for i in range(L):
+            att, ff = self.layers[i].dec_attn, self.layers[i].pos_ff
+            s0 = 16 + 4 * i
+            Wqkv = att.qkv_net.weight
+            qkv = torch.empty(K * B, 3 * HD, device=dev, dtype=F32)
+            cat = None
+            if M > 0:                                       # memory rows: k | v only (their q third is never used, :306)
+                cat = mems[i].reshape(M * B, D)
+                ops.gemm_f32(cat, Wqkv[HD:], out=qkv[:M * B, HD:])
+            ops.gemm_f32(h, Wqkv, out=qkv[M * B:])
+            rd = ops.gemm_f32(pd, att.r_net.weight)                                        # :308-310
+            vec, lse = ops.relattn_fwd_f32(qkv[M * B:, :HD], qkv[:, HD:2 * HD], qkv[:, 2 * HD:], rd, u, vb, rst, T, M, B, H, DH,
+                                           sv.same_length, sv.mem_len, self.attn_scale, drop_p=patt, drop_seed=ss(s0))
+            z1 = ops.gemm_f32(vec, att.o_net.weight, resid=h, drop_p=p, drop_seed=ss(s0 + 1))          # :344-349
+            a, mu1, rs1 = ops.layernorm_fwd_f32(z1, att.layer_norm.weight, att.layer_norm.bias, att.layer_norm.eps)
+            hid = ops.gemm_f32(a, ff.CoreNet[0].weight, bias=ff.CoreNet[0].bias, relu=True, drop_p=p, drop_seed=ss(s0 + 2))
+            z2 = ops.gemm_f32(hid, ff.CoreNet[3].weight, bias=ff.CoreNet[3].bias, resid=a, drop_p=p, drop_seed=ss(s0 + 3))
+            y, mu2, rs2 = ops.layernorm_fwd_f32(z2, ff.layer_norm.weight, ff.layer_norm.bias, ff.layer_norm.eps)   # :163-181
+            for k, x in (("h", h), ("cat", cat), ("qkv", qkv), ("rd", rd), ("vec", vec), ("lse", lse), ("z1", z1), ("mu1", mu1),
+                         ("rs1", rs1), ("a", a), ("hid", hid), ("z2", z2), ("mu2", mu2), ("rs2", rs2)):
+                getattr(sv, k).append(x)
+            h = y
+            hids.append(h)
+        h_out = ops.dropout_f32(h, p, ss(2)) if p > 0 else h                              # :601
+        new_mems = None                                                                    # K9 (:507-538)
+        if mems is not None:
+            hs = torch.stack([x.view(T, B, D) for x in hids])
+            allm = hs if M == 0 else torch.cat([mems, hs], dim=1)
+            end = M + T
+            beg = max(0, end - self.mem_len)
+            new_mems = allm[:, beg:end].contiguous()
+        logits = ops.gemm_f32(h_out, E, bias=self.crit.out_layers[0].bias)                 # :46 (tied weight)
+        tgt = target.contiguous().view(-1)
+        nll, ce_lse = ops.ce_fwd(logits, tgt, V)                                           # :689-691
+        sv.hL, sv.logits, sv.ce_lse, sv.target = h_out, logits, ce_lse, tgt
+        return nll.view(T, B), new_mems, sv
+
+    def _run_backward_f32(self, sv, dloss):
+        """Backward of _run_train_f32, every contraction in fp32 (csrc/train_f32.hip), all on the current stream in a fixed
+        order: two identical calls give identical gradients.  Delivery as _run_backward: into the flat gradient buffer
+        (grad_mode "direct", accumulating) or as return values; grad_ready_hook per layer, top-down, same slices."""
+        fl = self._ensure_flat()
+        dev = fl["dev"]
+        params = fl["params"]
+        direct = self.grad_mode == "direct"
+        if direct:
+            fresh = all(p.grad is None for p in params)
+            aliased = all(p.grad is not None and p.grad.data_ptr() == fl["g"].data_ptr() + 4 * off
+                          for p, off in zip(params, fl["offs"]))
+            if fresh:
+                fl["g"].zero_()
+                for p, off in zip(params, fl["offs"]):
+                    p.grad = fl["g"][off:off + p.numel()].view(p.shape)
+            elif not aliased:
+                direct = False
+        G = fl["g"] if direct else torch.zeros_like(fl["g"])
+        gname = self._name_off
+
+        def gv(name, shape):
+            n = 1
+            for s_ in shape:
+                n *= s_
+            return G[gname[name]:gname[name] + n].view(shape)
+        T, M, B = sv.T, sv.M, sv.B
+        D, H, DH, L, V = self.d_model, self.n_head, self.d_head, self.n_layer, self.n_token
+        HD, K, TB = H * DH, T + M, T * B
+        p, patt = sv.p, sv.patt
+
+        def ss(site):
+            return ops.site_seed(sv.seed, site)
+        ones = fl.get("ones_f32")
+        if ones is None or ones.numel() < max(TB, K * B):
+            ones = fl["ones_f32"] = torch.ones(max(TB, K * B), device=dev, dtype=F32)
+        E = self.word_emb.emb_layers[0].weight
+        gE = gv("word_emb.emb_layers.0.weight", (V, D))
+        dlogits = ops.ce_bwd_f32(sv.logits, sv.target, sv.ce_lse, dloss.reshape(-1).to(F32).contiguous(), V)
+        ops.gemm_f32(dlogits, sv.hL, out=gE, ta=True, tb=False, accumulate=True)           # output layer (tied weight)
+        ops.colsum_f32(dlogits, gv("crit.out_layers.0.bias", (V,)), ones)
+        dy = ops.gemm_f32(dlogits, E, tb=False)
+        if p > 0:
+            ops.dropout_f32(dy, p, ss(2), out=dy)                                          # final dropout (:601)
+        gu, gvb = gv("r_w_bias", (HD,)), gv("r_r_bias", (HD,))
+        u, vb = self.r_w_bias, self.r_r_bias
+        hook = getattr(self, "grad_ready_hook", None)
+        for i in range(L - 1, -1, -1):
+            pre = f"layers.{i}."
+            att, ff = self.layers[i].dec_attn, self.layers[i].pos_ff
+            s0 = 16 + 4 * i
+            dz2 = ops.layernorm_bwd_f32(dy, sv.z2[i], sv.mu2[i], sv.rs2[i], ff.layer_norm.weight,
+                                        dgamma=gv(pre + "pos_ff.layer_norm.weight", (D,)), dbeta=gv(pre + "pos_ff.layer_norm.bias", (D,)))
+            dl2 = ops.dropout_f32(dz2, p, ss(s0 + 3)) if p > 0 else dz2
+            ops.gemm_f32(dl2, sv.hid[i], out=gv(pre + "pos_ff.CoreNet.3.weight", (D, self.d_inner)), ta=True, tb=False,
+                         accumulate=True)
+            ops.colsum_f32(dl2, gv(pre + "pos_ff.CoreNet.3.bias", (D,)), ones)
+            dhid = ops.gemm_f32(dl2, ff.CoreNet[3].weight, tb=False)
+            ops.dropout_f32(dhid, p, ss(s0 + 2), gate=sv.hid[i], out=dhid)               # dropout + ReLU backward
+            ops.gemm_f32(dhid, sv.a[i], out=gv(pre + "pos_ff.CoreNet.0.weight", (self.d_inner, D)), ta=True, tb=False,
+                         accumulate=True)
+            ops.colsum_f32(dhid, gv(pre + "pos_ff.CoreNet.0.bias", (self.d_inner,)), ones)
+            da = ops.gemm_f32(dhid, ff.CoreNet[0].weight, tb=False)
+            dz1 = ops.layernorm_bwd_f32(da, sv.z1[i], sv.mu1[i], sv.rs1[i], att.layer_norm.weight,
+                                        dgamma=gv(pre + "dec_attn.layer_norm.weight", (D,)),
+                                        dbeta=gv(pre + "dec_attn.layer_norm.bias", (D,)), add=dz2)      # (+ the residual branch)
+            dl1 = ops.dropout_f32(dz1, p, ss(s0 + 1)) if p > 0 else dz1
+            ops.gemm_f32(dl1, sv.vec[i], out=gv(pre + "dec_attn.o_net.weight", (D, HD)), ta=True, tb=False, accumulate=True)
+            dvec = ops.gemm_f32(dl1, att.o_net.weight, tb=False)
+            qkv = sv.qkv[i]
+            dqkv = torch.empty(K * B, 3 * HD, device=dev, dtype=F32)          # (the q third of the memory rows stays unused)
+            drd = torch.empty(K, HD, device=dev, dtype=F32)
+            dq_ac, dq_bd = ops.relattn_bwd_f32(qkv[M * B:, :HD], qkv[:, HD:2 * HD], qkv[:, 2 * HD:], sv.rd[i], u, vb, sv.reset,
+                                               sv.vec[i], dvec, sv.lse[i], T, M, B, H, DH, sv.same_length, sv.mem_len,
+                                               self.attn_scale, dqkv[M * B:, :HD], dqkv[:, HD:2 * HD], dqkv[:, 2 * HD:], drd,
+                                               drop_p=patt, drop_seed=ss(s0))
+            ops.colsum_f32(dq_ac, gu, ones)
+            ops.colsum_f32(dq_bd, gvb, ones)
+            ops.gemm_f32(drd, sv.pd, out=gv(pre + "dec_attn.r_net.weight", (HD, D)), ta=True, tb=False, accumulate=True)
+            gW = gv(pre + "dec_attn.qkv_net.weight", (3 * HD, D))
+            ops.gemm_f32(dqkv[M * B:], sv.h[i], out=gW, ta=True, tb=False, accumulate=True)
+            if M > 0:                       # memory rows feed the k | v weight gradient (model.py:303-306; memory detached)
+                ops.gemm_f32(dqkv[:M * B, HD:], sv.cat[i], out=gW[HD:], ta=True, tb=False, accumulate=True)
+            dy = ops.gemm_f32(dqkv[M * B:], att.qkv_net.weight, tb=False, resid=dz1)
+            if hook is not None and direct:          # every gradient of layer i is final: its slice may be exchanged
+                lo = gname[pre + "dec_attn.qkv_net.weight"]
+                hi = gname[f"layers.{i + 1}.dec_attn.qkv_net.weight"] if i + 1 < L else gname["crit.out_layers.0.bias"]
+                if getattr(hook, "wants_events", False):
+                    ev = torch.cuda.Event()
+                    ev.record(torch.cuda.current_stream())
+                    hook(G, lo, hi, [ev])
+                else:
+                    hook(G, lo, hi)
+        ops.embed_bwd_f32(sv.tokens, dy, gE, math.sqrt(D), drop_p=p, drop_seed=ss(0))   # :585 (+ its dropout)
+        if direct:
+            return tuple(None for _ in params)
+        return tuple(G[off:off + p_.numel()].view(p_.shape) for p_, off in zip(params, fl["offs"]))
 
     def zero_grad(self, set_to_none: bool = True):                      # nn.Module.zero_grad without the module-tree walk
         for p in self._param_list():

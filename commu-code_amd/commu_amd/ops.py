@@ -998,3 +998,139 @@ def relattn_f32(q, k, v, stride_key, stride_seq, rd, u, vb, T, M, B, H, DH, same
 def decode_kv_append_f32(qkv, kc, vc, klen, active, HD, Lmax):
     call("commu_decode_kv_append_f32", _p(qkv), _f32_2d(qkv, "qkv"), _p(kc), _p(vc), _p(klen), _p(active), qkv.shape[0], HD,
          Lmax, _s())
+
+
+# ---------------------------------------------------------------------------------------------- fp32 training mode
+# (csrc/train_f32.hip: model.fp32_training -- the backward pass and the dropout forward in the reference's arithmetic)
+def f32_slabs(M, N, K):
+    """Row split of a long contraction (commu_gemm_f32 nslabs): a function of the shape only, so the summation order and
+    the result are the same on every call.  Slabs of >= 1024 rows until the grid has ~1024 workgroups."""
+    tiles = ((M + 63) // 64) * ((N + 63) // 64)
+    if K < 4096 or tiles >= 1024:
+        return 1
+    return max(1, min(K // 1024, 1024 // tiles, 128))
+
+
+def gemm_f32(A, B, out=None, *, ta=False, tb=True, bias=None, relu=False, drop_p=0.0, drop_seed=0, resid=None,
+             accumulate=False, slabs=None):
+    """out [M, N] (+)= op(A) . op(B) in fp32 (commu_gemm_f32): ta -> A is stored [K, M]; tb -> B is stored [N, K] (nn.Linear).
+    NT (ta=False, tb=True) = Linear forward, NN (tb=False) = dX, TN (ta=True, tb=False) = dW.  slabs: None = f32_slabs."""
+    lda, ldb = _f32_2d(A, "A"), _f32_2d(B, "B")
+    M, K = (A.shape[1], A.shape[0]) if ta else A.shape
+    N, Kb = B.shape if tb else (B.shape[1], B.shape[0])
+    assert Kb == K, (A.shape, B.shape, ta, tb)
+    if out is None:
+        assert not accumulate
+        out = torch.empty(M, N, device=A.device, dtype=F32)
+    ldc = _f32_2d(out, "out")
+    assert tuple(out.shape) == (M, N)
+    if bias is not None:
+        assert bias.dtype == F32 and bias.is_contiguous() and bias.numel() >= N
+    ldr = 0 if resid is None else _f32_2d(resid, "resid")
+    epi = bias is not None or relu or drop_p > 0 or resid is not None
+    ns = 1 if epi or ldc != N else (f32_slabs(M, N, K) if slabs is None else int(slabs))
+    ws = torch.empty(ns * M * N, device=A.device, dtype=F32) if ns > 1 else None
+    call("commu_gemm_f32", 1 if ta else 0, 1 if tb else 0, _p(A), lda, _p(B), ldb, _p(out), ldc, M, N, K, _p(bias),
+         1 if relu else 0, float(drop_p), int(drop_seed) & 0xFFFFFFFF, _p(resid), ldr, 1 if accumulate else 0, _p(ws), ns, _s())
+    return out
+
+
+def colsum_f32(X, out, ones):
+    """out [N] += column sums of X [rows, N] (a bias gradient), deterministic: the TN GEMM of a ones vector (row split in order)."""
+    gemm_f32(ones[:X.shape[0]].view(-1, 1), X, out.view(1, -1), ta=True, tb=False, accumulate=True)
+    return out
+
+
+def relattn_fwd_f32(q, k, v, rd, u, vb, reset, T, M, B, H, DH, same_length, mem_len, scale, drop_p=0.0, drop_seed=0,
+                    out=None):
+    """model.py:283-345 in train mode (commu_relattn_fwd_f32): q [T*B, >= H*DH] view, k / v [K*B, >= H*DH] views with a common
+    leading dimension, rd [K, >= H*DH].  Returns (out [T*B, H*DH], lse [B, H, T])."""
+    ld_q, ld_kv, ld_rd = _f32_2d(q, "q"), _f32_2d(k, "k"), _f32_2d(rd, "rd")
+    assert _f32_2d(v, "v") == ld_kv and k.shape[0] == v.shape[0] == (T + M) * B and rd.shape[0] >= T + M
+    assert u.dtype == F32 and vb.dtype == F32 and u.numel() >= H * DH and vb.numel() >= H * DH
+    if out is None:
+        out = torch.empty(T * B, H * DH, device=q.device, dtype=F32)
+    lse = torch.empty(B, H, T, device=q.device, dtype=F32)
+    call("commu_relattn_fwd_f32", _p(q), ld_q, _p(k), _p(v), ld_kv, _p(rd), ld_rd, _p(u), _p(vb), _p(reset), _p(out),
+         _f32_2d(out, "out"), _p(lse), T, M, B, H, DH, 1 if same_length else 0, int(mem_len), float(scale), float(drop_p),
+         int(drop_seed) & 0xFFFFFFFF, _s())
+    return out, lse
+
+
+def relattn_bwd_f32(q, k, v, rd, u, vb, reset, o, dout, lse, T, M, B, H, DH, same_length, mem_len, scale, dq, dk, dv, drd,
+                    drop_p=0.0, drop_seed=0):
+    """Backward of relattn_fwd_f32 (commu_relattn_bwd_f32): writes dq [T*B, >= H*DH], dk / dv [K*B, >= H*DH] (common leading
+    dimension), drd [K, >= H*DH]; returns (dq_ac, dq_bd) [T*B, H*DH] -- their column sums are the r_w_bias / r_r_bias
+    gradients."""
+    ld_q, ld_kv, ld_rd = _f32_2d(q, "q"), _f32_2d(k, "k"), _f32_2d(rd, "rd")
+    assert _f32_2d(v, "v") == ld_kv and _f32_2d(dv, "dv") == _f32_2d(dk, "dk")
+    assert dk.shape[0] == (T + M) * B and drd.shape[0] >= T + M and lse.numel() == B * H * T
+    dev = q.device
+    delta = torch.empty(B * H * T, device=dev, dtype=F32)
+    dq_ac = torch.empty(T * B, H * DH, device=dev, dtype=F32)
+    dq_bd = torch.empty(T * B, H * DH, device=dev, dtype=F32)
+    call("commu_relattn_bwd_f32", _p(q), ld_q, _p(k), _p(v), ld_kv, _p(rd), ld_rd, _p(u), _p(vb), _p(reset), _p(o),
+         _f32_2d(o, "o"), _p(dout), _f32_2d(dout, "dout"), _p(lse), _p(delta), _p(dq), _f32_2d(dq, "dq"), _p(dq_ac), _p(dq_bd),
+         _p(dk), _p(dv), _f32_2d(dk, "dk"), _p(drd), _f32_2d(drd, "drd"), T, M, B, H, DH, 1 if same_length else 0, int(mem_len),
+         float(scale), float(drop_p), int(drop_seed) & 0xFFFFFFFF, _s())
+    return dq_ac, dq_bd
+
+
+def layernorm_fwd_f32(x, gamma, beta, eps=1e-5, out=None):
+    """nn.LayerNorm in fp32 saving (mean, rstd) for the backward."""
+    ldx = _f32_2d(x, "x")
+    rows, D = x.shape
+    if out is None:
+        out = torch.empty(rows, D, device=x.device, dtype=F32)
+    mean = torch.empty(rows, device=x.device, dtype=F32)
+    rstd = torch.empty(rows, device=x.device, dtype=F32)
+    assert gamma.dtype == F32 and beta.dtype == F32 and gamma.numel() == D
+    call("commu_layernorm_fwd_f32", _p(x), ldx, _p(gamma), _p(beta), _p(out), _f32_2d(out, "out"), _p(mean), _p(rstd), rows, D,
+         float(eps), _s())
+    return out, mean, rstd
+
+
+def ln_f32_blocks(rows):
+    """Blocks of the LayerNorm backward's partial parameter sums (a function of the row count only: fixed summation order)."""
+    return max(1, min(512, (rows + 31) // 32))
+
+
+def layernorm_bwd_f32(dy, x, mean, rstd, gamma, dgamma=None, dbeta=None, add=None, dx=None):
+    """dx of nn.LayerNorm from dy (+ add, the residual branch's gradient); dgamma / dbeta (optional) += their gradients."""
+    rows, D = x.shape
+    if dx is None:
+        dx = torch.empty(rows, D, device=x.device, dtype=F32)
+    nblk = ln_f32_blocks(rows)
+    part = torch.empty(2 * nblk * D, device=x.device, dtype=F32)
+    call("commu_layernorm_bwd_f32", _p(dy), _f32_2d(dy, "dy"), _p(add), 0 if add is None else _f32_2d(add, "add"), _p(x),
+         _f32_2d(x, "x"), _p(mean), _p(rstd), _p(gamma), _p(dx), _f32_2d(dx, "dx"), _p(part), nblk, _p(dgamma), _p(dbeta), rows,
+         D, _s())
+    return dx
+
+
+def ce_bwd_f32(logits, target, lse, g, V):
+    """fp32 dlogits [rows, V] of the per-token NLL (ce_fwd's lse), weighted by g [rows]."""
+    rows = logits.shape[0]
+    dl = torch.empty(rows, V, device=logits.device, dtype=F32)
+    call("commu_ce_bwd_f32", _p(logits), _f32_2d(logits, "logits"), _p(target), _p(lse), _p(g), _p(dl), V, rows, V, _s())
+    return dl
+
+
+def embed_bwd_f32(tok, dx, gE, scale, drop_p=0.0, drop_seed=0, order=None):
+    """gE [V, D] += scale * (dropout-backward of dx) scattered by token, deterministic (token-sorted rows)."""
+    V, D = gE.shape
+    perm, offs = token_order(tok, V) if order is None else order
+    assert gE.is_contiguous() and dx.shape[1] == D
+    call("commu_embed_bwd_f32", _p(perm), _p(offs), _p(dx), _f32_2d(dx, "dx"), _p(gE), V, D, float(scale), float(drop_p),
+         int(drop_seed) & 0xFFFFFFFF, _s())
+    return gE
+
+
+def dropout_f32(x, drop_p=0.0, drop_seed=0, gate=None, out=None):
+    """x * keep / (1 - p) with the element-wise site mask (index over x's [rows, cols]), 0 where gate <= 0; out may be x."""
+    rows, cols = x.shape
+    if out is None:
+        out = torch.empty(rows, cols, device=x.device, dtype=F32)
+    call("commu_dropout_f32", _p(x), _f32_2d(x, "x"), _p(gate), 0 if gate is None else _f32_2d(gate, "gate"), _p(out),
+         _f32_2d(out, "out"), rows, cols, float(drop_p), int(drop_seed) & 0xFFFFFFFF, _s())
+    return out

@@ -189,6 +189,10 @@ class Trainer:
         """Capture / replay only at steady shapes: every micro-batch's XL memory at its full length (or no memory), the
         optimiser state allocated (one eager step done), and the batch shape of the captured graph."""
         cfg, model = self.cfg, self.model
+        if getattr(model, "fp32_training", False):
+            # the captured step is the bf16 schedule (_device_forward_backward): never capture it for an fp32 model
+            self.graph_failed = "fp32_training: the hipGraph step is the bf16 schedule; fp32 training steps run eagerly"
+            return False
         if self.train_step < 2:
             return False
         if cfg.TRAIN.mem_length > 0:
@@ -386,7 +390,7 @@ def evaluate(model, cfg, eval_iter, pad_id=0):
     return total_tok, total_nll
 
 
-def evaluate_best_checkpoint(path, cfg, vocab, device, eval_iter, reducer=None, pad_id=0):
+def evaluate_best_checkpoint(path, cfg, vocab, device, eval_iter, reducer=None, pad_id=0, parity=False):
     """train.py:486-513, the script's last block: a FRESH model with `MODEL.same_length = True`, the weights of
     `checkpoint_best.pt`, the test split through evaluate(), token count and NLL summed over the ranks (one packed
     collective instead of the reference's two); returns (test nll per token, tokens of all ranks)."""
@@ -397,6 +401,7 @@ def evaluate_best_checkpoint(path, cfg, vocab, device, eval_iter, reducer=None, 
     model = MemTransformerLM(cfg, vocab)
     model.load_state_dict(read_checkpoint(path)["model"])
     model = model.to(device)
+    model.parity_fp32 = bool(parity)          # (parity: the evaluation in the reference's fp32 arithmetic)
     tok, nll = evaluate(model, cfg, eval_iter, pad_id)
     if reducer is not None:
         tok, nll = reducer.sum_scalars([tok, nll / 10000.0], device=device)

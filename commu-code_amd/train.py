@@ -40,6 +40,9 @@ def parse_args(argv=None):
     p.add_argument("--graph", action="store_true",
                    help="replay the optimiser step from hipGraphs once its shapes are steady (not in the reference; pays "
                         "when a micro-batch is small enough for the host's launch rate to bound the step)")
+    p.add_argument("--parity", action="store_true",
+                   help="(not in the reference) train in the reference's fp32 arithmetic: fp32 forward with dropout, fp32 "
+                        "backward, eager steps (model.fp32_training + model.parity_fp32; evaluation in fp32 too)")
     p.add_argument("--max_step", type=int, default=None)
     p.add_argument("--log_interval", type=int, default=None)
     p.add_argument("--eval_interval", type=int, default=None)
@@ -103,6 +106,9 @@ def main(argv=None):
                                       local_rank=rank, world_size=num_gpus)
     assert cfg.MODEL.units % cfg.MODEL.num_heads == 0
     model = build_model(cfg, dataset.vocab, device)
+    if getattr(args, "parity", False):
+        model.fp32_training = True
+        model.parity_fp32 = True
     log(f"#total params = {sum(p.nelement() for p in model.parameters())}")
     reducer = GradReducer() if world > 1 else None
     if reducer is not None:
@@ -155,7 +161,8 @@ def main(argv=None):
     if reducer is not None:
         reducer.barrier()
     if os.path.exists(best):
-        test_nll, _ = evaluate_best_checkpoint(best, cfg, dataset.vocab, device, test_iter, reducer=reducer)
+        test_nll, _ = evaluate_best_checkpoint(best, cfg, dataset.vocab, device, test_iter, reducer=reducer,
+                                               parity=bool(getattr(args, "parity", False)))
         log("=" * 100)
         log("| End of training | test nll {:5.2f} | test ppl {:9.3f}".format(test_nll, math.exp(min(test_nll, 50.0))))
         log("=" * 100)

@@ -545,6 +545,63 @@ int commu_relattn_f32(const float* q, int ld_q, const float* k, const float* v, 
 int commu_decode_kv_append_f32(const float* qkv, int ld, float* kc, float* vc, const int* klen,
                                const unsigned char* active, int B, int HD, int Lmax, hipStream_t stream);
 
+/* ---- fp32 TRAINING MODE (csrc/train_f32.hip; model.fp32_training / train.py --parity).
+ * The reference trains in fp32 (train.py:48 `amp = None`, train.py:139-169): these entry points add the backward pass
+ * and the training-mode (dropout) forward to the fp32 parity forward above.  Exact fp32 products with fp32 accumulation,
+ * accurate expf / logf, no floating-point atomics: every output element is written by one thread in a fixed order, so two
+ * identical passes give bitwise-identical results.  Dropout sites use the bf16 path's counter-based masks
+ * (commu_gemm_nt_bf16 / commu_relattn_fwd): same seed, same keep decisions, kept values scaled by 1 / (1 - thr / 65536). */
+/* C[M,N] (+)= op(A)[M,K] . op(B)[K,N]; ta = 0: A stored [M][lda], ta = 1: A stored [K][lda] (op(A) = A^T); tb = 1: B
+ * stored [N][ldb] (op(B) = B^T, the nn.Linear form, model.py:46,164,167,205,212,278), tb = 0: B stored [K][ldb].
+ * Epilogue in order: + bias[n], ReLU, dropout (drop_p > 0; element index m * N + n), + resid[m][ldr], + C (accumulate).
+ * nslabs > 1 (a long contraction, e.g. a weight gradient over T*B rows): k is split into nslabs ranges written to
+ * ws [nslabs][M][N] and summed in slab order into C by commu_reduce_slabs_f32 -- needs ldc == N and no epilogue but
+ * accumulate. */
+int commu_gemm_f32(int ta, int tb, const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K,
+                   const float* bias, int relu, float drop_p, unsigned drop_seed, const float* resid, int ldr,
+                   int accumulate, float* ws, int nslabs, hipStream_t stream);
+/* model.py:283-345 in train mode: q [T*B rows][ld_q], k / v [K*B rows][ld_kv] (row j*B+b, head h at column h*DH; rows
+ * j < M are the memory), rd [distance][ld_rd] (distance i + M - j), out [T*B][ld_o], lse [B][H][T] = log-sum-exp of the
+ * undropped scaled scores.  Masks of model.py:549-574 (causal, same_length with mem_len, reset[b] hides the memory);
+ * attention dropout (model.py:327) on the probabilities with the commu_relattn_fwd mask.  DH <= 64, any DH. */
+int commu_relattn_fwd_f32(const float* q, int ld_q, const float* k, const float* v, int ld_kv, const float* rd, int ld_rd,
+                          const float* r_w_bias, const float* r_r_bias, const unsigned char* reset, float* out, int ld_o,
+                          float* lse, int T, int M, int B, int H, int DH, int same_length, int mem_len, float scale,
+                          float drop_p, unsigned drop_seed, hipStream_t stream);
+/* Backward of commu_relattn_fwd_f32 (operands as there; o = its output, dout = dO, lse = its lse), recomputing S and P:
+ * delta [B][H][T] = dO . O (written), then three passes with one writer per output:
+ *   query-stationary: dq_ac / dq_bd [T*B][H*DH] = the AC / BD parts of dq (their column sums are the r_w_bias / r_r_bias
+ *   gradients, model.py:292-297), dq [T*B][ld_dq] = their sum;
+ *   key-stationary: dk, dv [K*B][ld_dkv] for all K keys, memory rows included (model.py:303-306);
+ *   distance-stationary: drd [K][ld_drd], drd[d] = sum_{b,i} dS[i, i+M-d] (q_i + r_r_bias). */
+int commu_relattn_bwd_f32(const float* q, int ld_q, const float* k, const float* v, int ld_kv, const float* rd, int ld_rd,
+                          const float* r_w_bias, const float* r_r_bias, const unsigned char* reset, const float* o,
+                          int ld_o, const float* dout, int ld_do, const float* lse, float* delta, float* dq, int ld_dq,
+                          float* dq_ac, float* dq_bd, float* dk, float* dv, int ld_dkv, float* drd, int ld_drd, int T,
+                          int M, int B, int H, int DH, int same_length, int mem_len, float scale, float drop_p,
+                          unsigned drop_seed, hipStream_t stream);
+/* nn.LayerNorm (model.py:179,352) saving mean / rstd [rows]; D <= 1024 */
+int commu_layernorm_fwd_f32(const float* x, int ldx, const float* gamma, const float* beta, float* y, int ldy, float* mean,
+                            float* rstd, int rows, int D, float eps, hipStream_t stream);
+/* LayerNorm backward: dx = rstd (g dy - mean(g dy) - xhat mean(g dy xhat)) with dy = dy + add (add: optional second
+ * incoming gradient, the residual branch).  part [2][nblk][D]: per-block partial dgamma / dbeta (block k takes rows
+ * [k r, (k+1) r), r = ceil(rows / nblk)), then dgamma / dbeta (optional) += their in-order sums. */
+int commu_layernorm_bwd_f32(const float* dy, int lddy, const float* add, int ldadd, const float* x, int ldx,
+                            const float* mean, const float* rstd, const float* gamma, float* dx, int lddx, float* part,
+                            int nblk, float* dgamma, float* dbeta, int rows, int D, hipStream_t stream);
+/* model.py:64-73 backward in fp32: dlogits[r][c] = g[r] (exp(logits[r][c] - lse[r]) - [c == target[r]]), c < V */
+int commu_ce_bwd_f32(const float* logits, int ldl, const long long* target, const float* lse, const float* g,
+                     float* dlogits, int ldd, int rows, int V, hipStream_t stream);
+/* model.py:409-420 + 585-586 backward: gE[v] += scale * sum over the rows of token v, in the order perm / offs of
+ * commu_token_order, of dropout(dx[row]) (the embedding site: element index row * D + c) */
+int commu_embed_bwd_f32(const long long* perm, const long long* offs, const float* dx, int ldx, float* gE, int V, int D,
+                        float scale, float drop_p, unsigned drop_seed, hipStream_t stream);
+/* y = x * keep / (1 - p) (element index r * cols + c; drop_p 0: no mask), and 0 where gate (optional) <= 0 -- a dropout
+ * site's forward and backward (model.py:166,168,211,585-586,601), and the ReLU backward from the saved activation; y may
+ * alias x */
+int commu_dropout_f32(const float* x, int ldx, const float* gate, int ldg, float* y, int ldy, int rows, int cols,
+                      float drop_p, unsigned drop_seed, hipStream_t stream);
+
 /* library identification */
 const char* commu_hip_version(void);
 
