@@ -132,6 +132,9 @@ PROTOTYPES = {
     "commu_decode_attn_split": [c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_i,
                                 c_i, c_p, c_p, c_p],
     "commu_decode_advance": [c_p, c_p, c_i, c_i, c_p],
+    "commu_decode_kv_append_ring": [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
+    "commu_decode_attn_ring": [c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i,
+                               c_i, c_p, c_p, c_p],
     "commu_decode_tail_supported": [c_i, c_i, c_i, c_i],
     "commu_decode_tail_sync_words": [],
     "commu_decode_tail_trace": [c_p],
@@ -155,6 +158,8 @@ PROTOTYPES = {
     "commu_relattn_f32": [c_p, c_i, c_p, c_p, C.c_longlong, C.c_longlong, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i,
                           c_i, c_i, c_i, c_i, c_i, c_f, c_p],
     "commu_decode_kv_append_f32": [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p],
+    "commu_decode_kv_append_ring_f32": [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p],
+    "commu_decode_attn_ring_f32": [c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p],
     "commu_gemm_f32": [c_i, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_f, C.c_uint, c_p, c_i, c_i, c_p, c_i,
                        c_p],
     "commu_relattn_fwd_f32": [c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i,

@@ -38,11 +38,25 @@ def _s():
 
 
 class DecodeState:
-    """K/V caches + distance-indexed R tables for B sequences of up to Lmax positions."""
+    """K/V caches + distance-indexed R tables for B sequences of up to Lmax positions.
+
+    window=M selects the reference's SLIDING memory (model.py:507-538): the cache of a sequence is a ring of M + 1 rows
+    (Lmax is then derived), position p lives in row p mod (M + 1), and klen[b] -- "positions kept so far" in both modes --
+    keeps counting beyond the ring (the kernels derive the row from it).  Without a window the cache is linear and klen
+    saturates at its last row."""
 
     MAX_POSITIONS = 4224          # cache rows the decode attention kernel supports (commu_decode_attn)
+    KLEN_UNBOUNDED = 1 << 30      # the length bound handed to the book-keeping kernels in window mode
 
-    def __init__(self, model, B: int, Lmax: int):
+    def __init__(self, model, B: int, Lmax: int, window: Optional[int] = None):
+        if window is not None:
+            window = int(window)
+            if window < 1:
+                raise CommuHipError(f"a sliding decode memory needs at least one position, got {window}")
+            Lmax = window + 1
+        self.window = window
+        # what klen saturates at (commu_decode_advance, commu_forcing_post, commu_decode_sample_post_pre)
+        self.klen_cap = Lmax if window is None else self.KLEN_UNBOUNDED
         if Lmax > self.MAX_POSITIONS:
             raise CommuHipError(f"decode cache of {Lmax} positions requested; this build supports {self.MAX_POSITIONS} "
                                 "(the reference's 1 + 4146 fits)")
@@ -112,9 +126,19 @@ class DecodeState:
         HD = m.n_head * m.d_head
         for i, qkv in enumerate(qkvs):
             kv = qkv.view(T0, B, 3, HD)
+            if self.window is not None:
+                first, rows = self._ring_rows(T0)
+                self.kc[i].index_copy_(1, rows, kv[first:, :, 1].permute(1, 0, 2))
+                self.vc[i].index_copy_(1, rows, kv[first:, :, 2].permute(1, 0, 2))
+                continue
             self.kc[i, :, :T0].copy_(kv[:, :, 1].permute(1, 0, 2))
             self.vc[i, :, :T0].copy_(kv[:, :, 2].permute(1, 0, 2))
         self.klen.fill_(T0)
+
+    def _ring_rows(self, T0):
+        """Window mode: (first kept position, ring rows) of the last min(T0, window) positions of a T0-token context."""
+        first = max(0, T0 - self.window)
+        return first, (torch.arange(first, T0, device=self.klen.device) % self.Lmax)
 
     def _step_f32(self, tokens, active, keep, want_logits):
         """step() on fp32 operands: per layer [qkv_net, K/V append, cached attention over the ragged memories, o_net +
@@ -130,16 +154,21 @@ class DecodeState:
             lay = m.layers[i]
             att, ff = lay.dec_attn, lay.pos_ff
             ops.gemm_nt_f32(h, att.qkv_net.weight, out=f["qkv"])
-            ops.decode_kv_append_f32(f["qkv"], self.kc[i], self.vc[i], self.klen, active, HD, self.Lmax)
-            ops.relattn_f32(f["qkv"][:, :HD], self.kc[i], self.vc[i], HD, self.Lmax * HD, self.rd[i], u, vb, 1, 0, B, H, DH,
-                            bool(m.same_length), int(m.mem_len), m.attn_scale, klen=self.klen, out=f["vec"])
+            if self.window is not None:
+                ops.decode_kv_append_ring_f32(f["qkv"], self.kc[i], self.vc[i], self.klen, active, HD, self.Lmax)
+                ops.decode_attn_ring_f32(f["qkv"][:, :HD], self.kc[i], self.vc[i], self.rd[i], u, vb, self.klen, H, DH,
+                                         self.Lmax, bool(m.same_length), m.attn_scale, out=f["vec"])
+            else:
+                ops.decode_kv_append_f32(f["qkv"], self.kc[i], self.vc[i], self.klen, active, HD, self.Lmax)
+                ops.relattn_f32(f["qkv"][:, :HD], self.kc[i], self.vc[i], HD, self.Lmax * HD, self.rd[i], u, vb, 1, 0, B, H,
+                                DH, bool(m.same_length), int(m.mem_len), m.attn_scale, klen=self.klen, out=f["vec"])
             ops.gemm_nt_f32(f["vec"], att.o_net.weight, resid=h, out=f["z1"])
             ops.layernorm_f32(f["z1"], att.layer_norm.weight, att.layer_norm.bias, att.layer_norm.eps, out=f["a"])
             ops.gemm_nt_f32(f["a"], ff.CoreNet[0].weight, bias=ff.CoreNet[0].bias, relu=True, out=f["hid"])
             ops.gemm_nt_f32(f["hid"], ff.CoreNet[3].weight, bias=ff.CoreNet[3].bias, resid=f["a"], out=f["z2"])
             h = ops.layernorm_f32(f["z2"], ff.layer_norm.weight, ff.layer_norm.bias, ff.layer_norm.eps, out=f["h"][i])
         if keep is not None:
-            call("commu_decode_advance", _p(self.klen), _p(keep), B, self.Lmax, _s())
+            call("commu_decode_advance", _p(self.klen), _p(keep), B, self.klen_cap, _s())
         if want_logits:
             dst = self.logits if active is None else self.logits_new
             ops.gemm_nt_f32(h, E, bias=m.crit.out_layers[0].bias, out=dst[:, :V])
@@ -149,11 +178,12 @@ class DecodeState:
 
     def prefill(self, ctx: torch.Tensor):
         """ctx: int64 [T0, B] context tokens (midi_inferrer.py:186-197): fills the caches with their K/V
-        (same kernels as training, memory-less forward) and sets klen = T0."""
+        (same kernels as training, memory-less forward) and sets klen = T0.  Window mode: the context may be longer than
+        the window; the K/V of its last min(T0, window) positions go to their ring rows."""
         m = self.model
         T0, B = ctx.shape
         assert B == self.B
-        if T0 >= self.Lmax:
+        if self.window is None and T0 >= self.Lmax:
             raise CommuHipError(f"context of {T0} tokens does not fit a decode cache of {self.Lmax} positions")
         if self.parity:
             return self._prefill_f32(ctx)
@@ -161,17 +191,27 @@ class DecodeState:
         H, DH = m.n_head, m._DHp
         for i, qkv in enumerate(qkvs):
             kv = qkv.view(T0, B, 3, H, DH)
+            if self.window is not None:
+                first, rows = self._ring_rows(T0)
+                self.kc[i].index_copy_(2, rows, kv[first:, :, 1].permute(1, 2, 0, 3))
+                self.vc[i].index_copy_(2, rows, kv[first:, :, 2].permute(1, 2, 0, 3))
+                continue
             self.kc[i, :, :, :T0].copy_(kv[:, :, 1].permute(1, 2, 0, 3))
             self.vc[i, :, :, :T0].copy_(kv[:, :, 2].permute(1, 2, 0, 3))
         self.klen.fill_(T0)
 
     def _attn(self, i, u, vb, active, B, H, DH, scale):
         """Cached attention of layer i (K/V append fused in).  attn_splits > 1: the keys of a (sequence, head) pair over
-        several workgroups (long memories, few live sequences); pairs with fewer than 512 keys run unsplit either way."""
-        if self.attn_splits > 1:
-            if self.split_ws is None:
-                self.split_ws = torch.empty(B * H * 16 * (DH + 2), device=self.qkv.device, dtype=torch.float32)
-                self.split_cnt = torch.zeros(B * H, device=self.qkv.device, dtype=torch.int32)
+        several workgroups (long memories, few live sequences); pairs with fewer than 512 keys run unsplit either way.
+        Window mode: the ring variant of the same kernel (commu_decode_attn_ring)."""
+        if self.attn_splits > 1 and self.split_ws is None:
+            self.split_ws = torch.empty(B * H * 16 * (DH + 2), device=self.qkv.device, dtype=torch.float32)
+            self.split_cnt = torch.zeros(B * H, device=self.qkv.device, dtype=torch.int32)
+        if self.window is not None:
+            ops.decode_attn_ring(self.qkv, self.kc[i], self.vc[i], self.rd[i], u, vb, self.klen, active, self.vec, self.Lmax,
+                                 scale, append=True, same_length=bool(self.model.same_length), nsplit=int(self.attn_splits),
+                                 split_ws=self.split_ws, split_cnt=self.split_cnt)
+        elif self.attn_splits > 1:
             call("commu_decode_attn_split", _p(self.qkv), self.qkv.stride(0), _p(self.kc[i]), _p(self.vc[i]),
                  _p(self.rd[i]), self.rd[i].stride(0), _p(u), _p(vb), _p(self.klen), _p(active),
                  _p(self.vec), self.vec.stride(0), B, H, DH, self.Lmax, scale, 1, int(self.attn_splits),
@@ -217,7 +257,7 @@ class DecodeState:
             z2 = ops.gemm_nt(hid, w["w2"], bias=w["b2"], resid=a)
             ln2 = lay.pos_ff.layer_norm
         if keep is not None:
-            call("commu_decode_advance", _p(self.klen), _p(keep), B, self.Lmax, _s())
+            call("commu_decode_advance", _p(self.klen), _p(keep), B, self.klen_cap, _s())
         if want_logits:
             V = m.n_token
             dst = self.logits if active is None else self.logits_new
@@ -292,7 +332,7 @@ class DecodeState:
                  _p(out_n), ld_on, B, D, DI, HD, _p(self.t_sync[i]), _p(self.t_err), _s())
             h = h_out
         if keep is not None:
-            call("commu_decode_advance", _p(self.klen), _p(keep), B, self.Lmax, _s())
+            call("commu_decode_advance", _p(self.klen), _p(keep), B, self.klen_cap, _s())
         return self.logits
 
     def check(self):
@@ -311,8 +351,11 @@ class ForcedDecoder:
     POLL = 16          # iterations between two looks at the `done` flags (one D2H of B ints)
 
     def __init__(self, model, B: int, generation_length: int, memory_length: int, temperature: float, top_k: int,
-                 max_chords: int = 64, record_trace: bool = False, top_p: float = 1.0):
+                 max_chords: int = 64, record_trace: bool = False, top_p: float = 1.0, sliding: bool = False):
+        """sliding: the reference's sliding memory window (DecodeState window mode) -- generation_length is then bounded by
+        the token buffers only, not by memory_length."""
         self.model, self.B = model, B
+        self.sliding = bool(sliding)
         self.generation_length, self.temperature, self.top_k = int(generation_length), float(temperature), int(top_k)
         self.top_p = float(top_p)          # nucleus filter after top-k (extra mode; 1.0 = the reference's behaviour)
         dev = next(model.parameters()).device
@@ -320,12 +363,24 @@ class ForcedDecoder:
         self.NF = call("commu_forcing_state_ints")
         self.n_ctx_max = 16
         # a sequence grows by at most one token per iteration; its cache by at most one row per iteration
-        lmax = min(int(memory_length) + 1, DecodeState.MAX_POSITIONS)
-        if self.n_ctx_max + self.generation_length + 1 > lmax:
-            raise CommuHipError(
-                f"context + generation_length ({self.generation_length}) exceeds the decode memory of {lmax} positions; the "
-                "reference would start sliding its memory window here, which the K/V-cache step does not implement")
-        self.state = DecodeState(model, B, lmax)
+        if self.sliding:
+            M = int(memory_length)
+            if M + 1 > DecodeState.MAX_POSITIONS:
+                raise CommuHipError(f"a sliding memory of {M} positions needs {M + 1} cache rows; this build supports "
+                                    f"{DecodeState.MAX_POSITIONS}")
+            if M < self.n_ctx_max:
+                raise CommuHipError(f"a sliding memory of {M} positions cannot hold the conditioning context (up to "
+                                    f"{self.n_ctx_max} tokens)")
+            self.state = DecodeState(model, B, M + 1, window=M)
+        else:
+            lmax = min(int(memory_length) + 1, DecodeState.MAX_POSITIONS)
+            if self.n_ctx_max + self.generation_length + 1 > lmax:
+                raise CommuHipError(
+                    f"context + generation_length ({self.generation_length}) exceeds the decode memory of {lmax} positions; "
+                    "the reference would start sliding its memory window here, which the K/V-cache step does not implement "
+                    "unless it is asked to (sliding=True, --sliding_memory)")
+            self.state = DecodeState(model, B, lmax)
+        self._ctx_kv = None          # sliding: the context rows of every slot's K/V cache as load() left them (rearm)
         self.ld_seq = self.n_ctx_max + self.generation_length + 2
         self.ld_chord = max_chords
         self.ld_u = self.generation_length + 1
@@ -367,8 +422,8 @@ class ForcedDecoder:
                         active=self.draw, token=self.token, probs_out=self.probs if want_probs else None,
                         top_p=self.top_p)
         call("commu_forcing_post", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_pos), self.ld_chord,
-             _p(self.wrong), _p(self.draw), _p(self.token), None, _p(self.state.klen), _p(self.keep), self.state.Lmax,
-             B, _s())
+             _p(self.wrong), _p(self.draw), _p(self.token), None, _p(self.state.klen), _p(self.keep),
+             self.state.klen_cap, B, _s())
 
     def body_pre(self):
         """body() followed by pre() with the three per-sequence stages (sampling step, post, pre) as one launch: what
@@ -379,7 +434,7 @@ class ForcedDecoder:
              self.temperature, self.top_k, self.top_p, _p(self.token), None, 0, _p(self.fsm), _p(self.seq), self.ld_seq,
              _p(self.chord_tok), _p(self.chord_pos), self.ld_chord, _p(self.utable), self.ld_u, self.generation_length,
              _p(self.tok), _p(self.active), _p(self.keep), _p(self.draw), _p(self.uni), _p(self.trace), self.ld_trace,
-             _p(st.klen), st.Lmax, self.B, _s())
+             _p(st.klen), st.klen_cap, self.B, _s())
 
     def iteration(self, want_probs: bool = False):
         """One complete iteration, eagerly (tests inspect the draws between iterations)."""
@@ -443,6 +498,14 @@ class ForcedDecoder:
         self.state.vc.zero_()
         self.state.repack()          # (the model may have been trained since the decoder was built)
         self.state.prefill(ctx.to(self.dev))
+        if self.sliding:
+            # once a slot's ring has wrapped its context rows are gone: keep them for rearm() (rows = positions here, the
+            # context is shorter than the ring)
+            n = n_cond
+            if self.state.parity:
+                self._ctx_kv = (self.state.kc[:, :, :n].clone(), self.state.vc[:, :, :n].clone())
+            else:
+                self._ctx_kv = (self.state.kc[:, :, :, :n].clone(), self.state.vc[:, :, :, :n].clone())
         fsm = np.zeros((B, self.NF), dtype=np.int32)
         seq = np.zeros((B, self.ld_seq), dtype=np.int32)
         ctok = np.zeros((B, self.ld_chord), dtype=np.int32)
@@ -480,6 +543,8 @@ class ForcedDecoder:
     # tokens and chords) without touching the other slots: the context rows of its K/V cache are what they were, so only
     # the state record, the lengths, the rejected-token map and the variates are reset.  The re-armed slot sits out the
     # iteration in flight (its decision was taken from the finished record) and starts with the next one.
+    # Sliding memory: the slot's ring may have wrapped over its context rows, so they are restored from the copy load()
+    # took -- device-side copies on the decode stream, ordered between two graph replays, no synchronisation.
     def rearm(self, b: int, uniforms_row: Optional[np.ndarray] = None):
         rep0 = self.reports[b]
         rep = ForcingReport(rep0.n_chords, rep0.num_measures)
@@ -488,6 +553,15 @@ class ForcedDecoder:
                int(rep.length_fit), 0, 0]
         self.fsm[b].copy_(torch.tensor(rec, dtype=torch.int32))
         self.wrong[b].zero_()
+        if self.sliding:
+            st, n = self.state, self.n_cond
+            ck, cv = self._ctx_kv
+            if st.parity:
+                st.kc[:, b, :n].copy_(ck[:, b])
+                st.vc[:, b, :n].copy_(cv[:, b])
+            else:
+                st.kc[:, b, :, :n].copy_(ck[:, b])
+                st.vc[:, b, :, :n].copy_(cv[:, b])
         self.state.klen[b] = self.n_cond
         if uniforms_row is not None:
             u = np.full(self.ld_u, 0.5, dtype=np.float32)
@@ -524,6 +598,8 @@ class ForcedDecoder:
         """n iterations.  klen_bound: an upper bound of the memory lengths during them (0: unknown / short), live_rows: the
         number of sequences still decoding (None: unknown = all): beyond LONG_KLEN with at most LONG_ROWS live sequences
         the split-key iteration graph runs (built on first use)."""
+        if self.sliding:          # a ring never holds more keys than it has rows
+            klen_bound = min(klen_bound, self.state.Lmax)
         long = klen_bound > self.LONG_KLEN and live_rows is not None and live_rows <= self.LONG_ROWS
         if use_graph and long and getattr(self, "graph_long", None) is None:
             self.build_graph(long=True)
@@ -573,7 +649,7 @@ class ForcedDecoder:
 
     def sequences(self):
         """Token lists (None where nothing could be drawn, Q12) and, per sequence, the model-step trace
-        [(fed token, memory length before, after)] when it was recorded."""
+        [(fed token, memory length before, after)] when it was recorded (the lengths of the reference's memory tensor)."""
         fsm = self.fsm.cpu().numpy()
         seq = self.seq.cpu().numpy()
         out, traces = [], []
@@ -583,8 +659,10 @@ class ForcedDecoder:
             out.append(None if fsm[b, 6] else seq[b, :fsm[b, 0]].tolist())
             if tr is not None:
                 klen, t = self.n_cond, []
+                # (sliding: the memory the reference would report holds at most `window` positions, model.py:524-536)
+                cap = self.state.window if self.sliding else klen + self.ld_trace
                 for k in range(min(int(fsm[b, 13]), self.ld_trace // 2)):
-                    t.append((int(tr[b, 2 * k]), klen, klen + 1))
+                    t.append((int(tr[b, 2 * k]), min(klen, cap), min(klen + 1, cap)))
                     klen += int(tr[b, 2 * k + 1])
                 traces.append(t)
         return out, traces
@@ -594,20 +672,22 @@ class BatchedGenerator:
     """Generates `len(input_datas)` sequences in parallel (temperature / top_k shared by the batch, per-sequence
     `num_measures` / `chord_token_components`).  Decoders (caches + captured graph) are kept per batch size."""
 
-    def __init__(self, model, device, generation_length=4096, memory_length=4146):
+    def __init__(self, model, device, generation_length=4096, memory_length=4146, sliding=False):
         self.model, self.device = model, device
         self.generation_length, self.memory_length = generation_length, memory_length
+        self.sliding = bool(sliding)     # the reference's sliding memory window: generation_length may exceed memory_length
         self.uniform_sources = None      # optional list of callables, one per sequence (tests inject fixture variates)
         self.trace = None                # set to a list to receive per-sequence model-step traces
         self.use_graph = True
         self._decoders = {}
 
     def decoder(self, B, temperature, top_k, max_chords, top_p=1.0):
-        key = (B, float(temperature), int(top_k), float(top_p), self.trace is not None)
+        key = (B, float(temperature), int(top_k), float(top_p), self.trace is not None, self.sliding)
         dec = self._decoders.get(key)
         if dec is None or dec.ld_chord < max_chords:
             dec = ForcedDecoder(self.model, B, self.generation_length, self.memory_length, temperature, top_k,
-                                max_chords=max(64, max_chords), record_trace=self.trace is not None, top_p=top_p)
+                                max_chords=max(64, max_chords), record_trace=self.trace is not None, top_p=top_p,
+                                sliding=self.sliding)
             self._decoders[key] = dec
         return dec
 

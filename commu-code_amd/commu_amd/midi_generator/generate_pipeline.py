@@ -20,9 +20,13 @@ from .midi_inferrer import InferenceTask
 
 
 class TokenGenerationPipeline:
-    def __init__(self, model, device: torch.device, generation_length: int = 4096, memory_length: int = 4146):
+    def __init__(self, model, device: torch.device, generation_length: int = 4096, memory_length: int = 4146,
+                 sliding: bool = False):
+        """sliding: decode with the reference's sliding memory window (model.py:507-538), so that generation_length may
+        exceed memory_length."""
         self.model, self.device = model, device
         self.generation_length, self.memory_length = generation_length, memory_length
+        self.sliding = bool(sliding)
         self.preprocess_task = PreprocessTask()
         self.attempts = 0
         self.rejected = []          # (reason, sequence) of every attempt that did not pass: "sampling" | "forcing" | "no_note"
@@ -37,7 +41,7 @@ class TokenGenerationPipeline:
         encoded_meta = self.preprocess_task.execute(dict(input_args))
         data = self.preprocess_task.input_data
         checker = InferenceTask(self.device)                            # only its validator is used here
-        gen = BatchedGenerator(self.model, self.device, self.generation_length, self.memory_length)
+        gen = BatchedGenerator(self.model, self.device, self.generation_length, self.memory_length, sliding=self.sliding)
 
         def accept(seq, teacher) -> bool:
             self.attempts += 1

@@ -93,7 +93,9 @@ class InferenceTask:
         data = self.input_data
         glen = self.inference_cfg.GENERATION.generation_length
         mlen = getattr(self.inference_cfg.MODEL, "memory_length", 4146) if hasattr(self.inference_cfg, "MODEL") else 4146
-        gen = BatchedGenerator(self.model, self.device, glen, mlen)
+        # (not a key of the reference's configuration: set by generate.py --sliding_memory)
+        sliding = bool(getattr(self.inference_cfg.GENERATION, "sliding_memory", False))
+        gen = BatchedGenerator(self.model, self.device, glen, mlen, sliding=sliding)
 
         def accept(seq, rep) -> bool:
             self.attempts += 1

@@ -35,6 +35,16 @@ class ModelInitializeTask:
 
     def initialize_inference_config(self):
         cfg = get_default_cfg_inference()
+        # generate.py --memory_length / --generation_length / --sliding_memory (not in the reference, whose inference
+        # configuration is fixed at 4146 / 4096 and whose memory always slides)
+        mlen, glen = getattr(self.model_args, "memory_length", None), getattr(self.model_args, "generation_length", None)
+        cfg.defrost()
+        if mlen is not None:
+            cfg.MODEL.memory_length = int(mlen)
+        if glen is not None:
+            cfg.GENERATION.generation_length = int(glen)
+        if getattr(self.model_args, "sliding_memory", False):
+            cfg.GENERATION.sliding_memory = True
         cfg.freeze()
         return cfg
 

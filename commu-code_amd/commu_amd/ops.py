@@ -1000,6 +1000,125 @@ def decode_kv_append_f32(qkv, kc, vc, klen, active, HD, Lmax):
          Lmax, _s())
 
 
+# ---------------------------------------------------------------------------------------------- sliding decode memory
+# (the cached decode step on a ring of W = memory_length + 1 rows: include/commu_hip.h, commu_decode_attn_ring)
+RING_MAX_ROWS = 4224          # DEC_MAXK of csrc/decode.hip: the score row of a (sequence, head) pair lives in LDS
+
+
+def _ring_args(cache_k, cache_v, klen, active, B, dtype, shape):
+    for t, name in ((cache_k, "kc"), (cache_v, "vc"), (klen, "klen")) + (() if active is None else ((active, "active"),)):
+        if not t.is_cuda:
+            raise CommuHipError(f"{name}: commu_amd kernels need GPU tensors (no CPU fallback)")
+    for t, name in ((cache_k, "kc"), (cache_v, "vc")):
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise CommuHipError(f"{name}: contiguous {dtype} ring cache of shape {shape} expected, got {t.dtype} "
+                                f"{tuple(t.shape)}")
+    if klen.dtype != torch.int32 or klen.numel() != B or not klen.is_contiguous():
+        raise CommuHipError(f"klen: contiguous int32 [{B}] expected")
+    if active is not None and (active.dtype != torch.uint8 or active.numel() != B or not active.is_contiguous()):
+        raise CommuHipError(f"active: contiguous uint8 [{B}] expected")
+
+
+def _ring_rows(W):
+    W = int(W)
+    if W < 2 or W > RING_MAX_ROWS:
+        raise CommuHipError(f"ring of {W} rows requested; the decode attention supports 2 .. {RING_MAX_ROWS} "
+                            "(memory_length + 1)")
+    return W
+
+
+def decode_kv_append_ring(qkv, kc, vc, klen, active, W):
+    """K and V of the new tokens (columns [HD, 3 HD) of qkv, bf16 [B, 3 HD]) into ring row klen[b] mod W of the caches
+    kc / vc bf16 [B, H, W, DH], sequences with active[b] != 0 (None: all)."""
+    W = _ring_rows(W)
+    if kc.dim() != 4:
+        raise CommuHipError("kc: [B, H, W, DH] expected")
+    B, H, _, DH = kc.shape
+    _ring_args(kc, vc, klen, active, B, BF16, (B, H, W, DH))
+    if not qkv.is_cuda:
+        raise CommuHipError("qkv: commu_amd kernels need GPU tensors (no CPU fallback)")
+    if qkv.dtype != BF16 or qkv.dim() != 2 or qkv.shape != (B, 3 * H * DH) or qkv.stride(1) != 1 or qkv.stride(0) % 8:
+        raise CommuHipError(f"qkv: bf16 [{B}, {3 * H * DH}] with a row stride that is a multiple of 8 expected")
+    call("commu_decode_kv_append_ring", _p(qkv), qkv.stride(0), _p(kc), _p(vc), _p(klen), _p(active), B, W, H, H * DH, _s())
+
+
+def decode_attn_ring(qkv, kc, vc, rd, u, vb, klen, active, out, W, scale, append=True, same_length=False, nsplit=1,
+                     split_ws=None, split_cnt=None):
+    """Cached single-token attention over the ring caches kc / vc bf16 [B, H, W, DH] (commu_decode_attn_ring): klen int32
+    [B] counts absolute positions, rd bf16 [>= W, >= H DH] is the distance table, out bf16 [B, H DH].  append: the new
+    token's K/V are written to row klen[b] mod W by the kernel itself.  nsplit > 1: split_ws fp32 [>= B H nsplit (DH + 2)],
+    split_cnt int32 [>= B H] zeroed once."""
+    W = _ring_rows(W)
+    if kc.dim() != 4:
+        raise CommuHipError("kc: [B, H, W, DH] expected")
+    B, H, _, DH = kc.shape
+    if DH not in (32, 64):
+        raise CommuHipError(f"d_head {DH}: the decode attention is built for 32 and 64 (pad the model's head)")
+    _ring_args(kc, vc, klen, active, B, BF16, (B, H, W, DH))
+    HD = H * DH
+    for t, name in ((qkv, "qkv"), (rd, "rd"), (out, "out"), (u, "r_w_bias"), (vb, "r_r_bias")):
+        if not t.is_cuda:
+            raise CommuHipError(f"{name}: commu_amd kernels need GPU tensors (no CPU fallback)")
+    if qkv.dtype != BF16 or qkv.dim() != 2 or qkv.shape != (B, 3 * HD) or qkv.stride(1) != 1 or qkv.stride(0) % 8:
+        raise CommuHipError(f"qkv: bf16 [{B}, {3 * HD}] with a row stride that is a multiple of 8 expected")
+    if rd.dtype != BF16 or rd.dim() != 2 or rd.shape[0] < W or rd.shape[1] < HD or rd.stride(1) != 1 or rd.stride(0) % 8:
+        raise CommuHipError(f"rd: bf16 [>= {W}, >= {HD}] with a row stride that is a multiple of 8 expected")
+    if out.dtype != BF16 or out.dim() != 2 or out.shape != (B, HD) or out.stride(1) != 1:
+        raise CommuHipError(f"out: bf16 [{B}, {HD}] expected")
+    for t, name in ((u, "r_w_bias"), (vb, "r_r_bias")):
+        if t.dtype != F32 or t.numel() < HD or not t.is_contiguous():
+            raise CommuHipError(f"{name}: contiguous fp32 [>= {HD}] expected")
+    nsplit = int(nsplit)
+    if nsplit < 1 or nsplit > 16:
+        raise CommuHipError("nsplit: 1 .. 16")
+    if nsplit > 1:
+        if split_ws is None or split_cnt is None or not split_ws.is_cuda or not split_cnt.is_cuda:
+            raise CommuHipError("nsplit > 1 needs split_ws and split_cnt on the GPU")
+        if split_ws.dtype != F32 or split_ws.numel() < B * H * nsplit * (DH + 2) or split_cnt.dtype != torch.int32 \
+                or split_cnt.numel() < B * H:
+            raise CommuHipError("split_ws: fp32 [>= B H nsplit (DH + 2)], split_cnt: int32 [>= B H]")
+    call("commu_decode_attn_ring", _p(qkv), qkv.stride(0), _p(kc), _p(vc), _p(rd), rd.stride(0), _p(u), _p(vb), _p(klen),
+         _p(active), _p(out), out.stride(0), B, H, DH, W, float(scale), 1 if append else 0, 1 if same_length else 0, nsplit,
+         _p(split_ws) if nsplit > 1 else None, _p(split_cnt) if nsplit > 1 else None, _s())
+    return out
+
+
+def decode_kv_append_ring_f32(qkv, kc, vc, klen, active, HD, W):
+    """fp32 parity mode: the new tokens' K / V into ring row klen[b] mod W of kc / vc fp32 [B, W, HD]."""
+    W = _ring_rows(W)
+    ld = _f32_2d(qkv, "qkv")
+    B = qkv.shape[0]
+    if qkv.shape[1] != 3 * HD:
+        raise CommuHipError(f"qkv: fp32 [{B}, {3 * HD}] expected")
+    _ring_args(kc, vc, klen, active, B, F32, (B, W, HD))
+    call("commu_decode_kv_append_ring_f32", _p(qkv), ld, _p(kc), _p(vc), _p(klen), _p(active), B, HD, W, _s())
+
+
+def decode_attn_ring_f32(q, kc, vc, rd, u, vb, klen, H, DH, W, same_length, scale, out=None):
+    """fp32 parity mode: the cached single-token attention over the ring caches kc / vc fp32 [B, W, H DH]
+    (commu_decode_attn_ring_f32).  q: 2-D view [B, >= H DH] of the new tokens' projections; rd fp32 [>= W, >= H DH]."""
+    W = _ring_rows(W)
+    ld_q = _f32_2d(q, "q")
+    ld_rd = _f32_2d(rd, "rd")
+    B, HD = q.shape[0], H * DH
+    if DH < 1 or DH > 64 or q.shape[1] < HD:
+        raise CommuHipError(f"q: fp32 [{B}, >= {HD}] with d_head <= 64 expected")
+    _ring_args(kc, vc, klen, None, B, F32, (B, W, HD))
+    if rd.shape[0] < W or rd.shape[1] < HD:
+        raise CommuHipError(f"rd: fp32 [>= {W}, >= {HD}] expected")
+    for t, name in ((u, "r_w_bias"), (vb, "r_r_bias")):
+        if not t.is_cuda or t.dtype != F32 or t.numel() < HD or not t.is_contiguous():
+            raise CommuHipError(f"{name}: contiguous fp32 [>= {HD}] on the GPU expected")
+    if out is None:
+        out = torch.empty(B, HD, device=q.device, dtype=F32)
+    ld_o = _f32_2d(out, "out")
+    if out.shape != (B, HD):
+        raise CommuHipError(f"out: fp32 [{B}, {HD}] expected")
+    call("commu_decode_attn_ring_f32", _p(q), ld_q, _p(kc), _p(vc), _p(rd), ld_rd, _p(u), _p(vb), _p(klen), _p(out), ld_o, B, H,
+         DH, W, 1 if same_length else 0, float(scale), _s())
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- fp32 training mode
 # (csrc/train_f32.hip: model.fp32_training -- the backward pass and the dropout forward in the reference's arithmetic)
 def f32_slabs(M, N, K):

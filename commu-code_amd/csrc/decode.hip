@@ -12,6 +12,14 @@
 //
 //  kv_append : cache[b][klen[b]] = (k, v) of the new token (active sequences only)
 //  decode_attn: one workgroup per (b, h): scores lane-per-key, softmax in LDS, P.V lane-per-feature
+//
+// RING mode (the reference's SLIDING memory, model.py:507-538 with the same_length mask of model.py:549-568 at qlen 1,
+// mlen = M): the cache of a (sequence, head) pair is a ring of W = M + 1 rows (W, not M, rows also with same_length: the
+// new token's row and the M memory rows never alias, so a discarded step, quirk Q3, cannot damage a live row).  klen[b]
+// keeps counting ABSOLUTE positions; position p lives in row p mod W.  The new token (position pos, row cur = pos mod W)
+// sees the min(pos + 1, W) rows that have been written; row j is at distance (cur - j) mod W; with same_length and
+// pos >= M the row at distance M (row cur + 1 mod W) is hidden, which leaves exactly M keys.  K and V are still streamed
+// as physical rows 0 .. nvalid - 1 in order; only the distance-table row and the hidden row depend on the wrap.
 #include "common.h"
 #include "commu_hip.h"
 
@@ -20,11 +28,12 @@ namespace {
 // caches are head-major: [B][H][Lmax][DH], so the rows one workgroup streams are contiguous
 __global__ void kv_append_kernel(const bf16* __restrict__ qkv, int ld_qkv, bf16* __restrict__ kc,
                                  bf16* __restrict__ vc, const int* __restrict__ klen,
-                                 const unsigned char* __restrict__ active, int B, int Lmax, int H, int DH) {
+                                 const unsigned char* __restrict__ active, int B, int Lmax, int H, int DH, int ring) {
     const int b = blockIdx.x;
     if (active != nullptr && !active[b]) return;
-    const int pos = klen[b];
-    if (pos >= Lmax) return;
+    int pos = klen[b];
+    if (ring) pos %= Lmax;
+    else if (pos >= Lmax) return;
     const int HD = H * DH;
     const bf16* src = qkv + (size_t)b * ld_qkv;
     for (int c = threadIdx.x * 8; c < HD; c += blockDim.x * 8) {
@@ -49,12 +58,13 @@ __device__ __forceinline__ float oct_sum(float v) {
 // 64/LPR consecutive cache rows (LPR = DH/8 lanes per row), fully coalesced.
 // UNR row-instructions per batch (measured at 1000 keys: 2 -> 33.5 us, 4 -> 28.5, 8 -> 28.8; the streaming part then runs at
 // 5.9 TB/s and the remaining 6 us are launch + the dependent first loads)
-template <int DH, int UNR = 4>
+// RING: see the file header (mask_oldest = the model's same_length; the linear instantiation ignores it)
+template <int DH, bool RING, int UNR = 4>
 __global__ __launch_bounds__(256) void decode_attn_kernel(
     const bf16* __restrict__ qkv, int ld_qkv, const bf16* kc, const bf16* vc,
     const bf16* __restrict__ rd, int ld_rd, const float* __restrict__ u, const float* __restrict__ vb,
     const int* __restrict__ klen, const unsigned char* __restrict__ active, bf16* __restrict__ out, int ld_o,
-    int H, int Lmax, float scale, int append, int nsplit, float* split_ws, unsigned* split_cnt) {
+    int H, int Lmax, float scale, int append, int nsplit, float* split_ws, unsigned* split_cnt, int mask_oldest) {
     constexpr int LPR = DH / 8;            // lanes per row (8 for DH 64, 4 for DH 32)
     constexpr int RPW = 64 / LPR;          // rows per wave instruction
     __shared__ float sS[DEC_MAXK];
@@ -72,7 +82,8 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
     const int sub = lane % LPR, rowl = lane / LPR;
     // one round trip for everything the step needs before the cache: length, active flag, q, the biases, and the new
     // token's K and V (every lane: the 8 features of its chunk)
-    const int pos = klen[b];
+    const int apos = klen[b];
+    const int pos = RING ? apos % Lmax : apos;          // the new token's cache row
     const unsigned char act = active != nullptr ? active[b] : (unsigned char)1;
     const bf16* qrow = qkv + (size_t)b * ld_qkv + h * DH + 8 * sub;
     const bf16x8 q8 = ld_bf16x8(qrow);
@@ -83,12 +94,14 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
     if (!act) return;
     // fused kv_append: this head's K and V of the new token go to cache row klen[b]; the step itself takes them from
     // registers (row `self`), so nothing waits for the store
-    const int self = (append && pos < Lmax) ? pos : -1;
+    const int self = (append && (RING || pos < Lmax)) ? pos : -1;
     if (self >= 0 && tid < 2 * LPR && split == 0) {
         bf16* dst = (bf16*)(tid < LPR ? kc : vc) + (((size_t)b * H + h) * Lmax + pos) * DH + 8 * sub;
         st_bf16x8(dst, tid < LPR ? knew : vnew);
     }
-    const int nall = min(pos + 1, Lmax);           // keys 0..klen[b] (the new token included)
+    const int nall = min(apos + 1, Lmax);          // keys 0..klen[b] (the new token included); ring: the rows written so far
+    // ring with same_length, memory full: the row at distance Lmax - 1 is the one after the new token's
+    const int jmask = (RING && mask_oldest && apos >= Lmax - 1) ? (pos + 1 == Lmax ? 0 : pos + 1) : -1;
     // this workgroup's keys [jlo, n): chunks of >= 512 keys, a multiple of 64 (all of them without a split)
     int jlo = 0, n = nall, neff = 1;
     if (nsplit > 1) {
@@ -122,7 +135,9 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
             for (int u = 0; u < UNR; ++u) {
                 const int jc = min(j0 + 4 * RPW * u + rowl, n - 1);
                 kd[u] = ld_bf16x8(kb + (size_t)jc * DH);
-                rdst[u] = ld_bf16x8(rb + (size_t)((nall - 1) - jc) * ld_rd);
+                int d = RING ? pos - jc : (nall - 1) - jc;
+                if (RING && d < 0) d += Lmax;          // rows after the new token's hold the OLDEST positions
+                rdst[u] = ld_bf16x8(rb + (size_t)d * ld_rd);
             }
         };
         auto consume = [&](const bf16x8 (&kd)[UNR], const bf16x8 (&rdst)[UNR], int j0) {
@@ -134,6 +149,7 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
 #pragma unroll
                 for (int e = 0; e < 8; ++e) s += qu[e] * bf2f(kx[e]) + qv[e] * bf2f(rdst[u][e]);
                 s = (LPR == 8) ? oct_sum(s) : (s + dpp_f<0xB1>(s)) + dpp_f<0x4E>(s + dpp_f<0xB1>(s));
+                if (RING && j == jmask) s = -3.0e38f;          // hidden: its probability becomes exactly 0
                 if (j < n) {
                     if (sub == 0) sS[j - jlo] = s;
                     mx = fmaxf(mx, s);
@@ -243,33 +259,54 @@ __global__ void klen_advance_kernel(int* __restrict__ klen, const unsigned char*
 
 }  // namespace
 
+static int launch_kv_append(const void* qkv, int ld_qkv, void* kcache, void* vcache, const int* klen,
+                            const unsigned char* active, int B, int Lmax, int H, int HD, int ring, hipStream_t stream) {
+    if (B <= 0) return 0;
+    if ((HD % 8) || (ld_qkv % 8) || H <= 0 || (HD % H) || ((HD / H) % 8) || Lmax <= 0) return -22;
+    COMMU_LAUNCH(kv_append_kernel, dim3(B), dim3(64), 0, stream, (const bf16*)qkv, ld_qkv, (bf16*)kcache,
+                 (bf16*)vcache, klen, active, B, Lmax, H, HD / H, ring);
+    COMMU_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int commu_decode_kv_append(const void* qkv, int ld_qkv, void* kcache, void* vcache, const int* klen,
                                       const unsigned char* active, int B, int Lmax, int H, int HD,
                                       hipStream_t stream) {
-    if (B <= 0) return 0;
-    if ((HD % 8) || (ld_qkv % 8) || H <= 0 || (HD % H) || ((HD / H) % 8)) return -22;
-    COMMU_LAUNCH(kv_append_kernel, dim3(B), dim3(64), 0, stream, (const bf16*)qkv, ld_qkv, (bf16*)kcache,
-                 (bf16*)vcache, klen, active, B, Lmax, H, HD / H);
-    COMMU_LAUNCH_CHECK();
-    return 0;
+    return launch_kv_append(qkv, ld_qkv, kcache, vcache, klen, active, B, Lmax, H, HD, 0, stream);
+}
+
+extern "C" int commu_decode_kv_append_ring(const void* qkv, int ld_qkv, void* kcache, void* vcache, const int* klen,
+                                           const unsigned char* active, int B, int W, int H, int HD,
+                                           hipStream_t stream) {
+    return launch_kv_append(qkv, ld_qkv, kcache, vcache, klen, active, B, W, H, HD, 1, stream);
 }
 
 static int launch_decode_attn(const void* qkv, int ld_qkv, void* kcache, void* vcache, const void* rd, int ld_rd,
                               const float* r_w_bias, const float* r_r_bias, const int* klen, const unsigned char* active,
                               void* out, int ld_o, int B, int H, int DH, int Lmax, float scale, int append, int nsplit,
-                              float* split_ws, unsigned* split_cnt, hipStream_t stream) {
+                              float* split_ws, unsigned* split_cnt, hipStream_t stream, int ring = 0,
+                              int mask_oldest = 0) {
     if (B <= 0) return 0;
     if (Lmax > DEC_MAXK || (ld_qkv % 8) || (ld_rd % 8)) return -22;
+    if (ring && Lmax < 2) return -22;
     if (nsplit < 1 || nsplit > 16 || (nsplit > 1 && (split_ws == nullptr || split_cnt == nullptr))) return -22;
     dim3 grid(B * H * nsplit);
-    if (DH == 64)
-        COMMU_LAUNCH(decode_attn_kernel<64>, grid, dim3(256), 0, stream, (const bf16*)qkv, ld_qkv,
+    if (DH == 64 && !ring)
+        COMMU_LAUNCH((decode_attn_kernel<64, false>), grid, dim3(256), 0, stream, (const bf16*)qkv, ld_qkv,
                      (const bf16*)kcache, (const bf16*)vcache, (const bf16*)rd, ld_rd, r_w_bias, r_r_bias, klen,
-                     active, (bf16*)out, ld_o, H, Lmax, scale, append, nsplit, split_ws, split_cnt);
-    else if (DH == 32)
-        COMMU_LAUNCH(decode_attn_kernel<32>, grid, dim3(256), 0, stream, (const bf16*)qkv, ld_qkv,
+                     active, (bf16*)out, ld_o, H, Lmax, scale, append, nsplit, split_ws, split_cnt, mask_oldest);
+    else if (DH == 64 && ring)
+        COMMU_LAUNCH((decode_attn_kernel<64, true>), grid, dim3(256), 0, stream, (const bf16*)qkv, ld_qkv,
                      (const bf16*)kcache, (const bf16*)vcache, (const bf16*)rd, ld_rd, r_w_bias, r_r_bias, klen,
-                     active, (bf16*)out, ld_o, H, Lmax, scale, append, nsplit, split_ws, split_cnt);
+                     active, (bf16*)out, ld_o, H, Lmax, scale, append, nsplit, split_ws, split_cnt, mask_oldest);
+    else if (DH == 32 && !ring)
+        COMMU_LAUNCH((decode_attn_kernel<32, false>), grid, dim3(256), 0, stream, (const bf16*)qkv, ld_qkv,
+                     (const bf16*)kcache, (const bf16*)vcache, (const bf16*)rd, ld_rd, r_w_bias, r_r_bias, klen,
+                     active, (bf16*)out, ld_o, H, Lmax, scale, append, nsplit, split_ws, split_cnt, mask_oldest);
+    else if (DH == 32 && ring)
+        COMMU_LAUNCH((decode_attn_kernel<32, true>), grid, dim3(256), 0, stream, (const bf16*)qkv, ld_qkv,
+                     (const bf16*)kcache, (const bf16*)vcache, (const bf16*)rd, ld_rd, r_w_bias, r_r_bias, klen,
+                     active, (bf16*)out, ld_o, H, Lmax, scale, append, nsplit, split_ws, split_cnt, mask_oldest);
     else
         return -22;
     COMMU_LAUNCH_CHECK();
@@ -298,4 +335,15 @@ extern "C" int commu_decode_advance(int* klen, const unsigned char* advance, int
     COMMU_LAUNCH(klen_advance_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, klen, advance, B, Lmax);
     COMMU_LAUNCH_CHECK();
     return 0;
+}
+
+// ring mode (file header): W = memory_length + 1 cache rows, klen counts absolute positions; nsplit = 1: unsplit (split_ws /
+// split_cnt may be null)
+extern "C" int commu_decode_attn_ring(const void* qkv, int ld_qkv, void* kcache, void* vcache, const void* rd, int ld_rd,
+                                      const float* r_w_bias, const float* r_r_bias, const int* klen,
+                                      const unsigned char* active, void* out, int ld_o, int B, int H, int DH, int W,
+                                      float scale, int append, int same_length, int nsplit, float* split_ws,
+                                      unsigned* split_cnt, hipStream_t stream) {
+    return launch_decode_attn(qkv, ld_qkv, kcache, vcache, rd, ld_rd, r_w_bias, r_r_bias, klen, active, out, ld_o, B, H, DH, W,
+                              scale, append, nsplit, split_ws, split_cnt, stream, 1, same_length ? 1 : 0);
 }

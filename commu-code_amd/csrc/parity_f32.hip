@@ -372,3 +372,120 @@ extern "C" int commu_decode_kv_append_f32(const float* qkv, int ld, float* kc, f
     COMMU_LAUNCH_CHECK();
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------------ sliding decode memory
+// The cached decode step on a RING of W = mem_len + 1 rows per sequence ([B][W][H DH]): the reference's sliding memory
+// (model.py:507-538) with the same_length mask of model.py:549-568 at qlen 1.  klen[b] counts ABSOLUTE positions; position
+// p lives in row p mod W.  The new token (position pos = klen[b], already appended) sees positions
+// max(0, pos - (W - 1)) .. pos, without the oldest of them when same_length is on and the memory is full; distance
+// pos - p.  Keys are visited in CHRONOLOGICAL order, in the same chunks and with the same arithmetic as
+// relattn_f32_kernel at T = 1: before the first wrap the result equals the linear cache's bit for bit.
+template <int VW>
+__global__ __launch_bounds__(64) void decode_attn_ring_f32_kernel(const float* __restrict__ q, int ld_q,
+                                                                  const float* __restrict__ kbase,
+                                                                  const float* __restrict__ vbase,
+                                                                  const float* __restrict__ rd, int ld_rd,
+                                                                  const float* __restrict__ u,
+                                                                  const float* __restrict__ vbias,
+                                                                  const int* __restrict__ klen, float* __restrict__ out,
+                                                                  int ld_o, int H, int DH, int W, int same_length,
+                                                                  float scale) {
+    __shared__ float qu[64], qv[64];
+    const int h = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
+    const int pos = klen[b];
+    const float* qr = q + (size_t)b * ld_q + (size_t)h * DH;
+    if (lane < DH) {
+        const float x = qr[lane];
+        qu[lane] = x + u[h * DH + lane];
+        qv[lane] = x + vbias[h * DH + lane];
+    }
+    __syncthreads();
+    const int M = W - 1;
+    int lo = pos > M ? pos - M : 0;
+    if (same_length && pos >= M) lo += 1;
+    const int hi = pos;
+    const int wrap = (pos / W) * W;          // positions >= wrap are in row p - wrap, older ones in row p - wrap + W
+    const size_t sj = (size_t)H * DH;
+    const float* kb = kbase + (size_t)b * W * sj + (size_t)h * DH;
+    const float* vb_ = vbase + (size_t)b * W * sj + (size_t)h * DH;
+    const float* rdh = rd + (size_t)h * DH;
+    float mrun = -INFINITY, lrun = 0.f, acc = 0.f;
+    for (int j0 = lo; j0 <= hi; j0 += 64) {
+        const int j = j0 + lane;
+        float s = -INFINITY;
+        if (j <= hi) {
+            const float* kr = kb + (size_t)(j >= wrap ? j - wrap : j - wrap + W) * sj;
+            const float* rr = rdh + (size_t)(pos - j) * ld_rd;
+            float ac = 0.f, bd = 0.f;
+            if (VW == 4) {
+                for (int d = 0; d < DH; d += 4) {
+                    const f4 kx = *(const f4*)(kr + d), rx = *(const f4*)(rr + d);
+                    ac = fmaf(qu[d], kx.x, ac); ac = fmaf(qu[d + 1], kx.y, ac); ac = fmaf(qu[d + 2], kx.z, ac); ac = fmaf(qu[d + 3], kx.w, ac);
+                    bd = fmaf(qv[d], rx.x, bd); bd = fmaf(qv[d + 1], rx.y, bd); bd = fmaf(qv[d + 2], rx.z, bd); bd = fmaf(qv[d + 3], rx.w, bd);
+                }
+            } else {
+                for (int d = 0; d < DH; ++d) {
+                    ac = fmaf(qu[d], kr[d], ac);
+                    bd = fmaf(qv[d], rr[d], bd);
+                }
+            }
+            s = (ac + bd) * scale;
+        }
+        const float mnew = fmaxf(mrun, wave_max(s));
+        const float p = (j <= hi) ? expf(s - mnew) : 0.f;
+        const float corr = (mrun == -INFINITY) ? 0.f : expf(mrun - mnew);
+        lrun = lrun * corr + wave_sum(p);
+        acc *= corr;
+        const int n = min(64, hi - j0 + 1);
+        const int pbits = __builtin_bit_cast(int, p);          // (v_readlane: see relattn_f32_kernel)
+        if (lane < DH) {
+            int r = j0 >= wrap ? j0 - wrap : j0 - wrap + W;
+            for (int jj = 0; jj < n; ++jj) {
+                acc = fmaf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(pbits, jj)), vb_[(size_t)r * sj + lane], acc);
+                r = r + 1 == W ? 0 : r + 1;
+            }
+        }
+        mrun = mnew;
+    }
+    if (lane < DH) out[(size_t)b * ld_o + (size_t)h * DH + lane] = (hi >= lo) ? acc / lrun : 0.f;
+}
+
+extern "C" int commu_decode_attn_ring_f32(const float* q, int ld_q, const float* kc, const float* vc, const float* rd,
+                                          int ld_rd, const float* r_w_bias, const float* r_r_bias, const int* klen,
+                                          float* out, int ld_o, int B, int H, int DH, int W, int same_length, float scale,
+                                          hipStream_t stream) {
+    if (B <= 0 || H <= 0 || DH <= 0 || DH > 64 || B > 65535 || W < 2 || klen == nullptr) return -22;
+    const dim3 grid(H, B);
+    const bool v4 = DH % 4 == 0 && ld_rd % 4 == 0 && (((uintptr_t)kc | (uintptr_t)rd) % 16 == 0);
+    if (v4)
+        COMMU_LAUNCH(decode_attn_ring_f32_kernel<4>, grid, dim3(64), 0, stream, q, ld_q, kc, vc, rd, ld_rd, r_w_bias, r_r_bias,
+                     klen, out, ld_o, H, DH, W, same_length, scale);
+    else
+        COMMU_LAUNCH(decode_attn_ring_f32_kernel<1>, grid, dim3(64), 0, stream, q, ld_q, kc, vc, rd, ld_rd, r_w_bias, r_r_bias,
+                     klen, out, ld_o, H, DH, W, same_length, scale);
+    COMMU_LAUNCH_CHECK();
+    return 0;
+}
+
+// the new token's key / value rows into ring row klen[b] mod W of the caches [B][W][HD]
+__global__ void kv_append_ring_f32_kernel(const float* __restrict__ qkv, int ld, float* __restrict__ kc, float* __restrict__ vc,
+                                          const int* __restrict__ klen, const unsigned char* __restrict__ active, int HD, int W) {
+    const int b = blockIdx.x;
+    if (active && !active[b]) return;
+    const int row = klen[b] % W;
+    const float* src = qkv + (size_t)b * ld;
+    float* kd = kc + ((size_t)b * W + row) * HD;
+    float* vd = vc + ((size_t)b * W + row) * HD;
+    for (int c = threadIdx.x; c < HD; c += blockDim.x) {
+        kd[c] = src[HD + c];
+        vd[c] = src[2 * HD + c];
+    }
+}
+
+extern "C" int commu_decode_kv_append_ring_f32(const float* qkv, int ld, float* kc, float* vc, const int* klen,
+                                               const unsigned char* active, int B, int HD, int W, hipStream_t stream) {
+    if (B <= 0 || W < 1 || klen == nullptr) return -22;
+    COMMU_LAUNCH(kv_append_ring_f32_kernel, dim3(B), dim3(128), 0, stream, qkv, ld, kc, vc, klen, active, HD, W);
+    COMMU_LAUNCH_CHECK();
+    return 0;
+}

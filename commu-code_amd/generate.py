@@ -30,6 +30,14 @@ def parse_args():
     # decoding (--temperature 0) reproduces the reference's tokens wherever the top-1 / top-2 logit gap exceeds fp32
     # summation-order noise (~1e-6 of the logit range; the bf16 path needs a gap above its ~1e-2 logit error).
     model_arg_parser.add_argument("--parity", action="store_true")
+    # not in the reference (its inference configuration fixes them, config_helper.py:61-80): the length of the
+    # Transformer-XL memory and the number of loop iterations.  Without --sliding_memory the K/V cache is linear and
+    # context + generation_length must fit into memory_length + 1 positions; with it the cache is a ring of
+    # memory_length + 1 rows that slides like the reference's memory (model.py:507-538), so generation_length is free.
+    # (not given: the inference configuration's values, the reference's 4146 / 4096)
+    model_arg_parser.add_argument("--memory_length", type=int, default=None)
+    model_arg_parser.add_argument("--generation_length", type=int, default=None)
+    model_arg_parser.add_argument("--sliding_memory", action="store_true")
     input_arg_parser.add_argument("--output_dir", type=str, required=True)
     input_arg_parser.add_argument("--bpm", type=int)
     input_arg_parser.add_argument("--audio_key", type=str, choices=list(meta.KEY_MAP.keys()))

@@ -441,6 +441,22 @@ int commu_decode_attn_split(const void* qkv, int ld_qkv, void* kcache, void* vca
                             float* split_ws, unsigned* split_cnt, hipStream_t stream);
 /* klen[b] += advance[b]  (a step whose memory the reference discards does not advance: quirk Q3) */
 int commu_decode_advance(int* klen, const unsigned char* advance, int B, int Lmax, hipStream_t stream);
+/* ---- the same step with the reference's SLIDING memory (forward_generate keeps the last mem_len hidden states per layer,
+ * commu/model/model.py:507-538; with same_length the oldest key is hidden once the memory is full, model.py:549-568 at
+ * qlen 1, mlen = mem_len).  The cache of a (sequence, head) pair is a RING of W = mem_len + 1 rows ([B][H][W][DH],
+ * 2 <= W <= 4224); klen[b] counts the ABSOLUTE positions kept so far and is not bounded by W (pass a large Lmax to
+ * commu_decode_advance / commu_forcing_post / commu_decode_sample_post_pre); position p lives in row p mod W.  The new
+ * token (row klen[b] mod W) attends the min(klen[b] + 1, W) rows written so far, row j at distance (klen[b] - j) mod W
+ * (rd: [>= W][ld_rd]); same_length != 0 and klen[b] >= W - 1: the row at distance W - 1 is hidden.  No row is ever moved:
+ * a step reads each live row once and writes one.
+ * commu_decode_attn_ring: nsplit = 1 is the unsplit kernel (split_ws / split_cnt may be null), nsplit > 1 as
+ * commu_decode_attn_split. */
+int commu_decode_kv_append_ring(const void* qkv, int ld_qkv, void* kcache, void* vcache, const int* klen,
+                                const unsigned char* active, int B, int W, int H, int HD, hipStream_t stream);
+int commu_decode_attn_ring(const void* qkv, int ld_qkv, void* kcache, void* vcache, const void* rd, int ld_rd,
+                           const float* r_w_bias, const float* r_r_bias, const int* klen, const unsigned char* active,
+                           void* out, int ld_o, int B, int H, int DH, int W, float scale, int append, int same_length,
+                           int nsplit, float* split_ws, unsigned* split_cnt, hipStream_t stream);
 /* Everything of a decode-step layer that follows its attention, as ONE launch (csrc/decode_tail.hip):
  *   z1 = vec . Wo^T + h;  a = LN1(z1);  hid = relu(a . W1^T + b1);  z2 = hid . W2^T + b2 + a;  h_out = LN2(z2)
  *   (o_net + residual + LayerNorm model.py:344-352, PositionwiseFF model.py:163-179)
@@ -544,6 +560,18 @@ int commu_relattn_f32(const float* q, int ld_q, const float* k, const float* v, 
  * kc / vc [B][Lmax][HD], for the sequences with active[b] != 0 (null: all) */
 int commu_decode_kv_append_f32(const float* qkv, int ld, float* kc, float* vc, const int* klen,
                                const unsigned char* active, int B, int HD, int Lmax, hipStream_t stream);
+/* the decode step of the parity mode with the reference's SLIDING memory (commu/model/model.py:507-538, same_length mask
+ * model.py:549-568 at qlen 1): fp32 ring caches kc / vc [B][W][H DH], W = mem_len + 1 >= 2; klen[b] = absolute positions
+ * kept so far, position p in row p mod W.  commu_decode_kv_append_ring_f32 writes row klen[b] mod W;
+ * commu_decode_attn_ring_f32 (q: row b of the new tokens' projections, already appended) attends positions
+ * max(0, klen[b] - (W - 1)) .. klen[b] in chronological order at distance klen[b] - p (rd: [>= W][ld_rd]), the oldest
+ * hidden when same_length != 0 and klen[b] >= W - 1.  Before the first wrap the result equals commu_relattn_f32's on
+ * the linear cache bit for bit. */
+int commu_decode_kv_append_ring_f32(const float* qkv, int ld, float* kc, float* vc, const int* klen,
+                                    const unsigned char* active, int B, int HD, int W, hipStream_t stream);
+int commu_decode_attn_ring_f32(const float* q, int ld_q, const float* kc, const float* vc, const float* rd, int ld_rd,
+                               const float* r_w_bias, const float* r_r_bias, const int* klen, float* out, int ld_o, int B,
+                               int H, int DH, int W, int same_length, float scale, hipStream_t stream);
 
 /* ---- fp32 TRAINING MODE (csrc/train_f32.hip; model.fp32_training / train.py --parity).
  * The reference trains in fp32 (train.py:48 `amp = None`, train.py:139-169): these entry points add the backward pass
