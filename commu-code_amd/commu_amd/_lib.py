@@ -154,7 +154,6 @@ PROTOTYPES = {
     "commu_gemm_nt_f32": [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p],
     "commu_embed_f32": [c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_p],
     "commu_posemb_f32": [c_p, c_p, c_i, c_i, c_i, c_i, c_p],
-    "commu_layernorm_f32": [c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_p],
     "commu_relattn_f32": [c_p, c_i, c_p, c_p, C.c_longlong, C.c_longlong, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i,
                           c_i, c_i, c_i, c_i, c_i, c_f, c_p],
     "commu_decode_kv_append_f32": [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p],

@@ -163,10 +163,11 @@ class DecodeState:
                 ops.relattn_f32(f["qkv"][:, :HD], self.kc[i], self.vc[i], HD, self.Lmax * HD, self.rd[i], u, vb, 1, 0, B, H,
                                 DH, bool(m.same_length), int(m.mem_len), m.attn_scale, klen=self.klen, out=f["vec"])
             ops.gemm_nt_f32(f["vec"], att.o_net.weight, resid=h, out=f["z1"])
-            ops.layernorm_f32(f["z1"], att.layer_norm.weight, att.layer_norm.bias, att.layer_norm.eps, out=f["a"])
+            ops.layernorm_fwd_f32(f["z1"], att.layer_norm.weight, att.layer_norm.bias, att.layer_norm.eps, out=f["a"], stats=False)
             ops.gemm_nt_f32(f["a"], ff.CoreNet[0].weight, bias=ff.CoreNet[0].bias, relu=True, out=f["hid"])
             ops.gemm_nt_f32(f["hid"], ff.CoreNet[3].weight, bias=ff.CoreNet[3].bias, resid=f["a"], out=f["z2"])
-            h = ops.layernorm_f32(f["z2"], ff.layer_norm.weight, ff.layer_norm.bias, ff.layer_norm.eps, out=f["h"][i])
+            h = ops.layernorm_fwd_f32(f["z2"], ff.layer_norm.weight, ff.layer_norm.bias, ff.layer_norm.eps, out=f["h"][i],
+                                      stats=False)[0]
         if keep is not None:
             call("commu_decode_advance", _p(self.klen), _p(keep), B, self.klen_cap, _s())
         if want_logits:

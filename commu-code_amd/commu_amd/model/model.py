@@ -116,24 +116,24 @@ def _low_priority_stream(dev):
 
 
 class _Saved:
-    """Activations of one forward call kept for its backward."""
+    """Activations of one forward call kept for its backward (the fp32 training mode leaves qs / hbits / zff unset)."""
     __slots__ = ("T", "M", "B", "tokens", "target", "reset", "h", "cat", "qkv", "rd", "vec", "lse", "qs", "z1", "mu1",
                  "rs1", "a", "hid", "hbits", "zff", "z2", "mu2", "rs2", "pd", "hL", "logits", "ce_lse", "same_length", "mem_len",
                  "p", "patt", "seed")
 
 
-class _SavedF32:
-    """Activations of one fp32 training forward (_run_train_f32) kept for _run_backward_f32."""
-    __slots__ = ("T", "M", "B", "tokens", "target", "reset", "pd", "p", "patt", "seed", "same_length", "mem_len", "h", "cat",
-                 "qkv", "rd", "vec", "lse", "z1", "mu1", "rs1", "a", "hid", "z2", "mu2", "rs2", "hL", "logits", "ce_lse")
-
-
 class _XLLoss(torch.autograd.Function):
-    """loss[T,B] = NLL of the whole network; backward runs the hand-written backward schedule."""
+    """loss[T,B] = NLL of the whole network; backward runs the hand-written backward schedule.  model.fp32_training picks
+    the pair: _run_forward_f32 / _run_backward_f32 (the reference's arithmetic) instead of _run_forward / _run_backward."""
 
     @staticmethod
     def forward(ctx, model, data, target, reset, mems, *params):
-        loss, new_mems, saved = model._run_forward(data, target, reset, mems, need_grad=True)
+        if getattr(model, "fp32_training", False):
+            loss, new_mems, saved = model._run_forward_f32(data, mems, reset=reset, target=target, save=True)
+            ctx.run_backward = model._run_backward_f32
+        else:
+            loss, new_mems, saved = model._run_forward(data, target, reset, mems, need_grad=True)
+            ctx.run_backward = model._run_backward
         ctx.model, ctx.saved = model, saved
         # (without this autograd hands backward() a ZERO tensor of new_mems' shape -- [L+1, M, B, D]: a 0.47-GB fill per step
         #  at the bench shape with mem_len 1024 -- for an output that is marked non-differentiable)
@@ -151,32 +151,7 @@ class _XLLoss(torch.autograd.Function):
             raise CommuHipError("backward called twice on the same forward")
         if dloss is None:          # (only new_mems was used downstream: nothing to differentiate)
             return (None,) * (5 + len(model._flat["params"]))
-        grads = model._run_backward(saved, dloss.contiguous())
-        return (None, None, None, None, None) + grads
-
-
-class _XLLossF32(torch.autograd.Function):
-    """fp32 training mode (model.fp32_training): loss[T,B] of the fp32 forward; backward runs _run_backward_f32."""
-
-    @staticmethod
-    def forward(ctx, model, data, target, reset, mems, *params):
-        loss, new_mems, saved = model._run_train_f32(data, target, reset, mems)
-        ctx.model, ctx.saved = model, saved
-        ctx.set_materialize_grads(False)
-        if new_mems is None:
-            new_mems = torch.empty(0, device=data.device)
-        ctx.mark_non_differentiable(new_mems)
-        return loss, new_mems
-
-    @staticmethod
-    def backward(ctx, dloss, _dmems):
-        model, saved = ctx.model, ctx.saved
-        ctx.saved = None
-        if saved is None:
-            raise CommuHipError("backward called twice on the same forward")
-        if dloss is None:
-            return (None,) * (5 + len(model._flat["params"]))
-        grads = model._run_backward_f32(saved, dloss.contiguous())
+        grads = ctx.run_backward(saved, dloss.contiguous())
         return (None, None, None, None, None) + grads
 
 
@@ -248,14 +223,10 @@ class MemTransformerLM(nn.Module):
         if mems is None:
             mems = self.init_mems(self.n_layer)
         grad = torch.is_grad_enabled() and any(p.requires_grad for p in self._param_list())
-        if grad and getattr(self, "fp32_training", False):
-            # the reference's training arithmetic (train.py:48 `amp = None`, :139-169): fp32 forward with dropout, fp32 backward
-            self._ensure_flat()
-            loss, new_mems = _XLLossF32.apply(self, data, target, reset_mems, mems, *self._flat["params"])
-            if mems is None:
-                new_mems = None
-            return loss, new_mems
-        if getattr(self, "parity_fp32", False):
+        # (fp32_training: the reference's training arithmetic -- train.py:48 `amp = None`, :139-169 -- fp32 forward with dropout,
+        #  fp32 backward; it takes the gradient-enabled passes, also of a model in parity mode)
+        f32_grad = grad and getattr(self, "fp32_training", False)
+        if getattr(self, "parity_fp32", False) and not f32_grad:
             # the reference's arithmetic (fp32 end to end, train.py:48 `amp = None`) for the LOSS of a forward pass --
             # evaluate (train.py:74-110) and any no-grad forward; the fp32 backward pass is model.fp32_training
             if grad:
@@ -287,170 +258,133 @@ class MemTransformerLM(nn.Module):
             logits, new_mems, _ = self._run_forward(data, None, None, mems, need_grad=False, want_logits=True)
         return logits, new_mems
 
-    def _run_forward_f32(self, data, mems, want_kv=False, reset=None, target=None):
-        """forward_generate (model.py:606-628 -> _forward :576-604) in the reference's own arithmetic: fp32 master weights
-        (no bf16 shadows, no padding), fp32 activations and memory, fp32 MFMA Linears, accurate transcendentals
-        (csrc/parity_f32.hip).  The mode behind the "bit-exact greedy tokens" claim: `model.parity_fp32 = True` /
-        `generate.py --parity`; what differs from the reference is summation order only.  Eval-mode semantics (no dropout),
-        memory as the reference keeps it: a fp32 [L+1, M, B, d_model] tensor.
+    def _run_forward_f32(self, data, mems, want_kv=False, reset=None, target=None, save=False):
+        """The forward (model.py:540-604, 606-628, 678-693) in the reference's own arithmetic: fp32 master weights (no bf16
+        shadows, no padding), fp32 activations and memory, fp32 MFMA Linears, accurate transcendentals (csrc/parity_f32.hip,
+        csrc/train_f32.hip); what differs from the reference is summation order only.  ONE schedule for
+          * the parity mode behind the "bit-exact greedy tokens" claim (`model.parity_fp32 = True` / `generate.py --parity`):
+            forward_generate, the no-grad forward and the decode prefill (want_kv: also the layers' qkv buffers) -- eval-mode
+            semantics (no dropout);
+          * save=True: the gradient pass of model.fp32_training -- dropout in train() mode with the bf16 path's masks (same
+            base seed, same site ids, same element indices), activations kept for _run_backward_f32.
+        Memory as the reference keeps it: a fp32 [L+1, M, B, d_model] tensor.
         reset (optional bool [B]): `reset_mems` of forward (model.py:558-574: that sequence does not see the memory).
-        target (optional [T, B]): return the per-token NLL [T, B] (model.py:689-691, fp32 log-softmax) instead of the logits."""
-        params = self._param_list()
-        dev = params[0].device
+        target (optional [T, B]): return the per-token NLL [T, B] (model.py:689-691, fp32 log-softmax) instead of the logits.
+        Returns (logits [T, B, V] or nll, new_mems or None, the saved activations / the qkv buffers / None)."""
+        dev = self._param_list()[0].device
         if dev.type != "cuda" or not data.is_cuda:
             raise CommuHipError("MemTransformerLM runs on an MI355X only (no CPU fallback)")
         T, B = data.shape
         D, H, DH, L, V = self.d_model, self.n_head, self.d_head, self.n_layer, self.n_token
         HD = H * DH
         M = 0 if mems is None or mems.numel() == 0 else mems.shape[1]
-        if M > 0 and mems.dtype != F32:
-            mems = mems.to(F32)
-        if M > 0 and not mems.is_contiguous():
-            mems = mems.contiguous()
-        K = T + M
-        E = self.word_emb.emb_layers[0].weight
-        h = ops.embed_f32(data.contiguous().view(-1), E)                                   # model.py:585
-        pd = ops.posemb_f32(self.pos_emb.inv_freq, K, D, clamp_len=int(self.clamp_len))    # :578-584 (by distance)
-        u, vb = self.r_w_bias.contiguous(), self.r_r_bias.contiguous()
-        rst = None
-        if reset is not None and M > 0:
-            rst = reset.to(device=dev, dtype=torch.uint8).contiguous()
-        hids = [h]
-        kv_out = []
-        for i in range(L):
-            lay = self.layers[i]
-            att, ff = lay.dec_attn, lay.pos_ff
-            Wqkv = att.qkv_net.weight
-            qkv = torch.empty(K * B, 3 * HD, device=dev, dtype=F32)
-            if M > 0:                                       # memory rows: k | v only (their q third is never used, :306)
-                ops.gemm_nt_f32(mems[i].reshape(M * B, D), Wqkv[HD:], out=qkv[:M * B, HD:])
-            ops.gemm_nt_f32(h, Wqkv, out=qkv[M * B:])
-            rd = ops.gemm_nt_f32(pd, att.r_net.weight)                                     # :308-310
-            vec = ops.relattn_f32(qkv[M * B:, :HD], qkv[:, HD:2 * HD], qkv[:, 2 * HD:], B * 3 * HD, 3 * HD, rd, u, vb,
-                                  T, M, B, H, DH, bool(self.same_length), int(self.mem_len), self.attn_scale, reset=rst)
-            z1 = ops.gemm_nt_f32(vec, att.o_net.weight, resid=h)                           # :344-349
-            a = ops.layernorm_f32(z1, att.layer_norm.weight, att.layer_norm.bias, att.layer_norm.eps)
-            hid = ops.gemm_nt_f32(a, ff.CoreNet[0].weight, bias=ff.CoreNet[0].bias, relu=True)     # :163-181
-            z2 = ops.gemm_nt_f32(hid, ff.CoreNet[3].weight, bias=ff.CoreNet[3].bias, resid=a)
-            h = ops.layernorm_f32(z2, ff.layer_norm.weight, ff.layer_norm.bias, ff.layer_norm.eps)
-            hids.append(h)
-            if want_kv:
-                kv_out.append(qkv)
-        # K9 (model.py:507-538): cat(mems, hids)[max(0, M + T - mem_len) : M + T]
-        new_mems = None
-        if mems is not None:
-            hs = torch.stack([x.view(T, B, D) for x in hids])
-            allm = hs if M == 0 else torch.cat([mems, hs], dim=1)
-            end = M + T
-            beg = max(0, end - self.mem_len)
-            new_mems = allm[:, beg:end].contiguous()
-        logits = ops.gemm_nt_f32(h, E, bias=self.crit.out_layers[0].bias)                  # :46,620-626 (tied weight)
-        if target is not None:                                                             # :689-691 (fp32 log-softmax + gather)
-            nll, _ = ops.ce_fwd(logits, target.contiguous().view(-1).to(dev), V)
-            return nll.view(T, B), new_mems, (kv_out if want_kv else None)
-        return logits.view(T, B, V), new_mems, (kv_out if want_kv else None)
-
-    # ------------------------------------------------------------------ fp32 training mode
-    def _run_train_f32(self, data, target, reset, mems):
-        """Gradient-enabled forward (model.py:540-604, 678-693) in the reference's arithmetic (model.fp32_training): fp32
-        master weights (no shadows, no padding), fp32 activations and memory, fp32 MFMA products, accurate transcendentals,
-        dropout in train() mode with the bf16 path's masks (same base seed, same site ids, same element indices).  Returns
-        (nll [T, B], new_mems fp32 [L+1, n, B, d_model] or None, saved activations for _run_backward_f32)."""
-        fl = self._ensure_flat()
-        dev = fl["dev"]
-        if not data.is_cuda:
-            raise CommuHipError("inputs must be GPU tensors (no CPU fallback)")
-        T, B = data.shape
-        D, H, DH, L, V = self.d_model, self.n_head, self.d_head, self.n_layer, self.n_token
-        HD = H * DH
-        M = 0 if mems is None or mems.numel() == 0 else mems.shape[1]
         if M > 0 and (mems.dtype != F32 or not mems.is_contiguous()):
             mems = mems.to(F32).contiguous()
-        K, TB = T + M, T * B
+        K = T + M
         tokens = data.contiguous().view(-1)
         rst = None
         if reset is not None and M > 0:
             rst = reset.to(device=dev, dtype=torch.uint8).contiguous()
-        # K16 dropout: the draw of _run_forward (one base seed per forward call, `fixed_drop_seed` included)
-        p = float(self.drop.p) if self.training else 0.0
-        patt = float(self.layers[0].dec_attn.dropatt.p) if (self.training and L > 0) else 0.0
-        seed = 0
-        if p > 0 or patt > 0:
-            fixed = getattr(self, "fixed_drop_seed", None)
-            seed = int(fixed) if fixed is not None else int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+        p, patt, seed = self._drop_draw() if save else (0.0, 0.0, 0)
+        same_length, mem_len = bool(self.same_length), int(self.mem_len)
 
         def ss(site):
             return ops.site_seed(seed, site)
-        sv = _SavedF32()
+
+        def lin(x, W, site=None, **kw):
+            # nn.Linear, by the kernel each mode has always run: the gradient pass through the general GEMM (its dropout
+            # epilogue at `site`; never the skinny kernel), the no-grad passes through gemm_nt_f32 (skinny kernel at <= 64 rows)
+            if save:
+                return ops.gemm_f32(x, W, drop_p=0.0 if site is None else p, drop_seed=0 if site is None else ss(site), **kw)
+            return ops.gemm_nt_f32(x, W, **kw)
         E = self.word_emb.emb_layers[0].weight
         h = ops.embed_f32(tokens, E)                                                        # model.py:585
-        if p > 0:
-            ops.dropout_f32(h, p, ss(0), out=h)
         pd = ops.posemb_f32(self.pos_emb.inv_freq, K, D, clamp_len=int(self.clamp_len))    # :578-584 (by distance)
         if p > 0:
+            ops.dropout_f32(h, p, ss(0), out=h)
             ops.dropout_f32(pd, p, ss(1), out=pd)
-        u, vb = self.r_w_bias, self.r_r_bias
-        sv.T, sv.M, sv.B, sv.tokens, sv.reset, sv.pd, sv.p, sv.patt, sv.seed = T, M, B, tokens, rst, pd, p, patt, seed
-        sv.same_length, sv.mem_len = bool(self.same_length), int(self.mem_len)
-        for k in ("h", "cat", "qkv", "rd", "vec", "lse", "z1", "mu1", "rs1", "a", "hid", "z2", "mu2", "rs2"):
-            setattr(sv, k, [])
+        u, vb = self.r_w_bias.contiguous(), self.r_r_bias.contiguous()
+        sv = None
+        per_layer = ("h", "cat", "qkv", "rd", "vec", "lse", "z1", "mu1", "rs1", "a", "hid", "z2", "mu2", "rs2")
+        if save:
+            sv = _Saved()
+            sv.T, sv.M, sv.B, sv.tokens, sv.reset, sv.pd, sv.p, sv.patt, sv.seed = T, M, B, tokens, rst, pd, p, patt, seed
+            sv.same_length, sv.mem_len = same_length, mem_len
+            for k in per_layer:
+                setattr(sv, k, [])
         hids = [h]
+        kv_out = []
         for i in range(L):
             att, ff = self.layers[i].dec_attn, self.layers[i].pos_ff
             s0 = 16 + 4 * i
             Wqkv = att.qkv_net.weight
             qkv = torch.empty(K * B, 3 * HD, device=dev, dtype=F32)
-            cat = None
+            cat = lse = None
             if M > 0:                                       # memory rows: k | v only (their q third is never used, :306)
                 cat = mems[i].reshape(M * B, D)
-                ops.gemm_f32(cat, Wqkv[HD:], out=qkv[:M * B, HD:])
-            ops.gemm_f32(h, Wqkv, out=qkv[M * B:])
-            rd = ops.gemm_f32(pd, att.r_net.weight)                                        # :308-310
-            vec, lse = ops.relattn_fwd_f32(qkv[M * B:, :HD], qkv[:, HD:2 * HD], qkv[:, 2 * HD:], rd, u, vb, rst, T, M, B, H, DH,
-                                           sv.same_length, sv.mem_len, self.attn_scale, drop_p=patt, drop_seed=ss(s0))
-            z1 = ops.gemm_f32(vec, att.o_net.weight, resid=h, drop_p=p, drop_seed=ss(s0 + 1))          # :344-349
-            a, mu1, rs1 = ops.layernorm_fwd_f32(z1, att.layer_norm.weight, att.layer_norm.bias, att.layer_norm.eps)
-            hid = ops.gemm_f32(a, ff.CoreNet[0].weight, bias=ff.CoreNet[0].bias, relu=True, drop_p=p, drop_seed=ss(s0 + 2))
-            z2 = ops.gemm_f32(hid, ff.CoreNet[3].weight, bias=ff.CoreNet[3].bias, resid=a, drop_p=p, drop_seed=ss(s0 + 3))
-            y, mu2, rs2 = ops.layernorm_fwd_f32(z2, ff.layer_norm.weight, ff.layer_norm.bias, ff.layer_norm.eps)   # :163-181
-            for k, x in (("h", h), ("cat", cat), ("qkv", qkv), ("rd", rd), ("vec", vec), ("lse", lse), ("z1", z1), ("mu1", mu1),
-                         ("rs1", rs1), ("a", a), ("hid", hid), ("z2", z2), ("mu2", mu2), ("rs2", rs2)):
-                getattr(sv, k).append(x)
+                lin(cat, Wqkv[HD:], out=qkv[:M * B, HD:])
+            lin(h, Wqkv, out=qkv[M * B:])
+            rd = lin(pd, att.r_net.weight)                                                 # :308-310
+            q, k, v = qkv[M * B:, :HD], qkv[:, HD:2 * HD], qkv[:, 2 * HD:]
+            if save:
+                vec, lse = ops.relattn_fwd_f32(q, k, v, rd, u, vb, rst, T, M, B, H, DH, same_length, mem_len, self.attn_scale,
+                                               drop_p=patt, drop_seed=ss(s0))
+            else:
+                vec = ops.relattn_f32(q, k, v, B * 3 * HD, 3 * HD, rd, u, vb, T, M, B, H, DH, same_length, mem_len,
+                                      self.attn_scale, reset=rst)
+            z1 = lin(vec, att.o_net.weight, s0 + 1, resid=h)                               # :344-349
+            a, mu1, rs1 = ops.layernorm_fwd_f32(z1, att.layer_norm.weight, att.layer_norm.bias, att.layer_norm.eps, stats=save)
+            hid = lin(a, ff.CoreNet[0].weight, s0 + 2, bias=ff.CoreNet[0].bias, relu=True)  # :163-181
+            z2 = lin(hid, ff.CoreNet[3].weight, s0 + 3, bias=ff.CoreNet[3].bias, resid=a)
+            y, mu2, rs2 = ops.layernorm_fwd_f32(z2, ff.layer_norm.weight, ff.layer_norm.bias, ff.layer_norm.eps, stats=save)
+            if save:
+                for k_, x in zip(per_layer, (h, cat, qkv, rd, vec, lse, z1, mu1, rs1, a, hid, z2, mu2, rs2)):
+                    getattr(sv, k_).append(x)
             h = y
             hids.append(h)
+            if want_kv:
+                kv_out.append(qkv)
+        extra = sv if save else (kv_out if want_kv else None)
+        new_mems = self._update_mems_f32(hids, mems, M, T, B)
         h_out = ops.dropout_f32(h, p, ss(2)) if p > 0 else h                              # :601
-        new_mems = None                                                                    # K9 (:507-538)
-        if mems is not None:
-            hs = torch.stack([x.view(T, B, D) for x in hids])
-            allm = hs if M == 0 else torch.cat([mems, hs], dim=1)
-            end = M + T
-            beg = max(0, end - self.mem_len)
-            new_mems = allm[:, beg:end].contiguous()
-        logits = ops.gemm_f32(h_out, E, bias=self.crit.out_layers[0].bias)                 # :46 (tied weight)
-        tgt = target.contiguous().view(-1)
-        nll, ce_lse = ops.ce_fwd(logits, tgt, V)                                           # :689-691
-        sv.hL, sv.logits, sv.ce_lse, sv.target = h_out, logits, ce_lse, tgt
-        return nll.view(T, B), new_mems, sv
+        logits = lin(h_out, E, bias=self.crit.out_layers[0].bias)                          # :46,620-626 (tied weight)
+        if target is None:
+            return logits.view(T, B, V), new_mems, extra
+        tgt = target.contiguous().view(-1).to(dev)
+        nll, ce_lse = ops.ce_fwd(logits, tgt, V)                                           # :689-691 (fp32 log-softmax + gather)
+        if save:
+            sv.hL, sv.logits, sv.ce_lse, sv.target = h_out, logits, ce_lse, tgt
+        return nll.view(T, B), new_mems, extra
 
+    def _update_mems_f32(self, hids, mems, M, T, B):
+        """K9 in fp32 (model.py:507-538): cat(mems, hids)[max(0, M + T - mem_len) : M + T]; hids: L+1 tensors [T*B, d_model]."""
+        if mems is None:
+            return None
+        hs = torch.stack([x.view(T, B, self.d_model) for x in hids])
+        allm = hs if M == 0 else torch.cat([mems, hs], dim=1)
+        end = M + T
+        return allm[:, max(0, end - self.mem_len):end].contiguous()
+
+    def _drop_draw(self):
+        """K16 dropout of one forward call: (p, attention p, base seed).  Active in train() mode; ONE draw per call
+        (`fixed_drop_seed`: tests pin the base seed; default: torch's CPU generator), one derived seed per site (ops.site_seed)."""
+        p = float(self.drop.p) if self.training else 0.0
+        patt = float(self.layers[0].dec_attn.dropatt.p) if (self.training and self.n_layer > 0) else 0.0
+        seed = 0
+        if p > 0 or patt > 0:
+            fixed = getattr(self, "fixed_drop_seed", None)
+            seed = int(fixed) if fixed is not None else int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+        return p, patt, seed
+
+    # ------------------------------------------------------------------ fp32 training mode: the backward schedule
     def _run_backward_f32(self, sv, dloss):
-        """Backward of _run_train_f32, every contraction in fp32 (csrc/train_f32.hip), all on the current stream in a fixed
+        """Backward of _run_forward_f32(save=True), every contraction in fp32 (csrc/train_f32.hip), all on the current stream in a fixed
         order: two identical calls give identical gradients.  Delivery as _run_backward: into the flat gradient buffer
         (grad_mode "direct", accumulating) or as return values; grad_ready_hook per layer, top-down, same slices."""
         fl = self._ensure_flat()
         dev = fl["dev"]
         params = fl["params"]
-        direct = self.grad_mode == "direct"
-        if direct:
-            fresh = all(p.grad is None for p in params)
-            aliased = all(p.grad is not None and p.grad.data_ptr() == fl["g"].data_ptr() + 4 * off
-                          for p, off in zip(params, fl["offs"]))
-            if fresh:
-                fl["g"].zero_()
-                for p, off in zip(params, fl["offs"]):
-                    p.grad = fl["g"][off:off + p.numel()].view(p.shape)
-            elif not aliased:
-                direct = False
-        G = fl["g"] if direct else torch.zeros_like(fl["g"])
+        G, direct = self._grad_target()
         gname = self._name_off
 
         def gv(name, shape):
@@ -517,8 +451,7 @@ class MemTransformerLM(nn.Module):
                 ops.gemm_f32(dqkv[:M * B, HD:], sv.cat[i], out=gW[HD:], ta=True, tb=False, accumulate=True)
             dy = ops.gemm_f32(dqkv[M * B:], att.qkv_net.weight, tb=False, resid=dz1)
             if hook is not None and direct:          # every gradient of layer i is final: its slice may be exchanged
-                lo = gname[pre + "dec_attn.qkv_net.weight"]
-                hi = gname[f"layers.{i + 1}.dec_attn.qkv_net.weight"] if i + 1 < L else gname["crit.out_layers.0.bias"]
+                lo, hi = self._layer_grad_range(i)
                 if getattr(hook, "wants_events", False):
                     ev = torch.cuda.Event()
                     ev.record(torch.cuda.current_stream())
@@ -529,6 +462,31 @@ class MemTransformerLM(nn.Module):
         if direct:
             return tuple(None for _ in params)
         return tuple(G[off:off + p_.numel()].view(p_.shape) for p_, off in zip(params, fl["offs"]))
+
+    def _grad_target(self):
+        """(G, direct) of a backward pass.  grad_mode "direct": G is the flat gradient buffer, which every p.grad aliases -- a
+        fresh step (every p.grad None) zeroes it and installs the aliases; gradients that live elsewhere turn direct off.
+        Not direct: G is a zeroed buffer of the same layout whose slices the pass returns to autograd."""
+        fl = self._flat
+        params = fl["params"]
+        direct = self.grad_mode == "direct"
+        if direct:
+            fresh = all(p.grad is None for p in params)
+            aliased = all(p.grad is not None and p.grad.data_ptr() == fl["g"].data_ptr() + 4 * off
+                          for p, off in zip(params, fl["offs"]))
+            if fresh:
+                fl["g"].zero_()
+                for p, off in zip(params, fl["offs"]):
+                    p.grad = fl["g"][off:off + p.numel()].view(p.shape)
+            elif not aliased:
+                direct = False
+        return (fl["g"] if direct else torch.zeros_like(fl["g"])), direct
+
+    def _layer_grad_range(self, i):
+        """(lo, hi) of layer i's slice of the flat gradient buffer: what grad_ready_hook may exchange once the layer is done."""
+        off = self._name_off
+        nxt = f"layers.{i + 1}.dec_attn.qkv_net.weight" if i + 1 < self.n_layer else "crit.out_layers.0.bias"
+        return off[f"layers.{i}.dec_attn.qkv_net.weight"], off[nxt]
 
     def zero_grad(self, set_to_none: bool = True):                      # nn.Module.zero_grad without the module-tree walk
         for p in self._param_list():
@@ -777,13 +735,7 @@ class MemTransformerLM(nn.Module):
         lay = [self.layers[i] for i in range(L)]
         sv = _Saved() if need_grad else None
 
-        # K16 dropout: active in train() mode; one base seed per forward call, one derived seed per site
-        p = float(self.drop.p) if self.training else 0.0
-        patt = float(lay[0].dec_attn.dropatt.p) if (self.training and L > 0) else 0.0
-        seed = 0
-        if p > 0 or patt > 0:          # (`fixed_drop_seed`: tests pin the base seed; default: torch's CPU generator)
-            fixed = getattr(self, "fixed_drop_seed", None)
-            seed = int(fixed) if fixed is not None else int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+        p, patt, seed = self._drop_draw()          # K16 dropout
 
         def ss(site):
             return ops.site_seed(seed, site)
@@ -918,20 +870,7 @@ class MemTransformerLM(nn.Module):
         fl = self._ensure_flat()
         dev = fl["dev"]
         params = fl["params"]
-        direct = self.grad_mode == "direct"
-        if direct:
-            fresh = all(p.grad is None for p in params)
-            aliased = all(p.grad is not None and p.grad.data_ptr() == fl["g"].data_ptr() + 4 * off
-                          for p, off in zip(params, fl["offs"]))
-            if fresh:
-                fl["g"].zero_()
-                for p, off in zip(params, fl["offs"]):
-                    p.grad = fl["g"][off:off + p.numel()].view(p.shape)
-            elif not aliased:
-                direct = False
-        G = fl["g"]
-        if not direct:
-            G = torch.zeros_like(fl["g"])
+        G, direct = self._grad_target()
         gname = {n: o for n, o in self._name_off.items()}
 
         def gv(name, shape):
@@ -1183,8 +1122,7 @@ class MemTransformerLM(nn.Module):
                 # slice of the flat buffer may be exchanged.  The main stream is NOT joined with the side stream
                 # here (that would serialise exactly the work the side stream hides); a hook that can order itself
                 # after events (`wants_events`) gets one per stream, others get the old blocking join.
-                lo = gname[pre + "dec_attn.qkv_net.weight"]
-                hi = gname[f"layers.{i + 1}.dec_attn.qkv_net.weight"] if i + 1 < L else gname["crit.out_layers.0.bias"]
+                lo, hi = self._layer_grad_range(i)
                 if getattr(hook, "wants_events", False):
                     evs = [torch.cuda.Event()]
                     evs[0].record(main)

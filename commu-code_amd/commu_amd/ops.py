@@ -923,7 +923,8 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
 
 
 # ---------------------------------------------------------------------------------------------- fp32 parity mode
-# (csrc/parity_f32.hip: the generation path on fp32 operands end to end -- the reference's arithmetic, train.py:48)
+# (csrc/parity_f32.hip: the generation path on fp32 operands end to end -- the reference's arithmetic, train.py:48; its
+#  LayerNorm is layernorm_fwd_f32(stats=False) below)
 def _f32_2d(t, name):
     if not t.is_cuda:
         raise CommuHipError("commu_amd kernels need GPU tensors (no CPU fallback)")
@@ -967,16 +968,6 @@ def posemb_f32(inv_freq, n, D, out=None, clamp_len=-1):
         out = torch.empty(n, D, device=inv_freq.device, dtype=F32)
     assert inv_freq.dtype == F32 and inv_freq.numel() == D // 2
     call("commu_posemb_f32", _p(inv_freq), _p(out), _f32_2d(out, "out"), n, D, int(clamp_len), _s())
-    return out
-
-
-def layernorm_f32(x, gamma, beta, eps=1e-5, out=None):
-    ldx = _f32_2d(x, "x")
-    rows, D = x.shape
-    if out is None:
-        out = torch.empty(rows, D, device=x.device, dtype=F32)
-    assert gamma.dtype == F32 and beta.dtype == F32 and gamma.numel() == D
-    call("commu_layernorm_f32", _p(x), ldx, _p(gamma), _p(beta), _p(out), _f32_2d(out, "out"), rows, D, float(eps), _s())
     return out
 
 
@@ -1195,14 +1186,15 @@ def relattn_bwd_f32(q, k, v, rd, u, vb, reset, o, dout, lse, T, M, B, H, DH, sam
     return dq_ac, dq_bd
 
 
-def layernorm_fwd_f32(x, gamma, beta, eps=1e-5, out=None):
-    """nn.LayerNorm in fp32 saving (mean, rstd) for the backward."""
+def layernorm_fwd_f32(x, gamma, beta, eps=1e-5, out=None, stats=True):
+    """nn.LayerNorm in fp32: (out, mean, rstd), the statistics saved for the backward; stats=False: (out, None, None), nothing
+    allocated beside out (the forward-only callers; the decode step passes static buffers under graph capture)."""
     ldx = _f32_2d(x, "x")
     rows, D = x.shape
     if out is None:
         out = torch.empty(rows, D, device=x.device, dtype=F32)
-    mean = torch.empty(rows, device=x.device, dtype=F32)
-    rstd = torch.empty(rows, device=x.device, dtype=F32)
+    mean = torch.empty(rows, device=x.device, dtype=F32) if stats else None
+    rstd = torch.empty(rows, device=x.device, dtype=F32) if stats else None
     assert gamma.dtype == F32 and beta.dtype == F32 and gamma.numel() == D
     call("commu_layernorm_fwd_f32", _p(x), ldx, _p(gamma), _p(beta), _p(out), _f32_2d(out, "out"), _p(mean), _p(rstd), rows, D,
          float(eps), _s())

@@ -1,31 +1,29 @@
-// fp32 TRAINING MODE (model.fp32_training): the backward pass and the dropout forward of the reference's arithmetic.
+// fp32 TRAINING MODE (model.fp32_training) and the kernels every fp32 forward shares with it.
 //
-// The reference trains in fp32 (train.py:48 `amp = None`; train.py:139-169).  parity_f32.hip holds the fp32 forward of the
-// generation / evaluation path; this translation unit adds what a gradient-enabled fp32 pass needs on top of it: a general
-// fp32 GEMM (NT / NN / TN, epilogues, deterministic row split), the relative attention's training forward (log-sum-exp out,
-// attention dropout) and its backward in three passes, LayerNorm forward / backward, the cross-entropy backward, the
-// embedding backward and an element-wise dropout / ReLU-gate kernel.
+// The reference trains in fp32 (train.py:48 `amp = None`; train.py:139-169).  This translation unit holds the general fp32
+// GEMM (NT / NN / TN, epilogues, deterministic row split: the 64 x 64 tile behind every fp32 Linear, commu_gemm_nt_f32 of
+// parity_f32.hip included), LayerNorm forward (statistics optional: the parity forward and the decode step call it without)
+// and backward, the relative attention's training forward (attn_row_f32.h with attention dropout on, log-sum-exp out) and
+// its backward in three passes, the cross-entropy backward, the embedding backward and an element-wise dropout /
+// ReLU-gate kernel.  parity_f32.hip holds what only the generation path needs.
 // Rules of every product here: exact fp32 products with fp32 accumulation (v_mfma_f32_16x16x4_f32 or fmaf chains), accurate
 // expf / logf, and NO floating-point atomics -- every output element has one writer that sums in a fixed order, so two
 // identical passes give bitwise-identical gradients.  Dropout masks are the build's counter-based ones (common.h drop_word,
 // attn_drop.h DropLane): the same keep decisions as the bf16 path for the same seeds.
 #include "common.h"
 #include "commu_hip.h"
-#include "attn_drop.h"
-#include <math.h>
-
-typedef __attribute__((ext_vector_type(4))) float f4;
+#include "attn_row_f32.h"
 
 namespace {
 
 // ------------------------------------------------------------------------------------------------ GEMM
 // C[M,N] (+)= op(A)[M,K] . op(B)[K,N] with op(A) = A ([M][K], TA 0) or A^T (A stored [K][M], TA 1) and op(B) = B^T (B stored
 // [N][K], TB 1: the nn.Linear form) or B (stored [K][N], TB 0).  NT = Linear forward, NN = dX, TN = dW.
-// The 64 x 64 tile of gemm_nt_f32_kernel (parity_f32.hip): 4 waves of 2 x 2 v_mfma_f32_16x16x4_f32 tiles, K step 16.
+// 64 x 64 tile, 4 waves (each 32 x 32 = 2 x 2 v_mfma_f32_16x16x4_f32 tiles of 16 x 16), K step 16.
 #define TG_BM 64
 #define TG_BN 64
 #define TG_BK 16
-#define TG_LD 80
+#define TG_LD 80          // LDS row pitch in floats: k rows 0 / 1 of a 32-lane read land in banks 0-15 / 16-31
 
 struct GemmEpi {
     const float* bias;          // [N] or null
@@ -37,36 +35,60 @@ struct GemmEpi {
     int accumulate;             // C += result
 };
 
-// one 64-row x 16-k tile of an operand into S[k][row]: stored [row][k] (T 0: a thread takes 4 consecutive k of one row) or
-// [k][row] (T 1: 4 consecutive rows of one k), zero outside [rows) x [kend)
-template <int T>
-__device__ __forceinline__ void stage_tile(const float* __restrict__ X, int ldx, int r0, int rows, int k0, int kend, int tid,
-                                           float (*S)[TG_LD]) {
-    if (T == 0) {
-        const int r = tid >> 2, kk = (tid & 3) * 4;
-        const bool rok = r0 + r < rows;
-        const float* p = X + (size_t)(rok ? r0 + r : 0) * ldx;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int k = k0 + kk + e;
-            S[kk + e][r] = (rok && k < kend) ? p[k] : 0.f;
+// One 64-row x 16-k tile of an operand into S[k][row], zero outside [rows) x [kend).
+// Stored [row][k] (row-major): thread (tid >> 2, 4 (tid & 3)) takes 4 consecutive k of one row -- into registers BEFORE the
+// barrier that frees the LDS tile (load_rows: the global latency overlaps the previous step's MFMAs), one 16-byte load when
+// VEC (leading dimension % 4 == 0 and a 16-byte aligned base: the launcher checks) --, then store_rows.  load_rows takes
+// both operands (RA / RB: which of them are row-major) under ONE branch, so that their loads are in flight together.
+template <bool RA, bool RB, bool VEC>
+__device__ __forceinline__ void load_rows(const float* __restrict__ ap, bool aok, const float* __restrict__ bp, bool bok, int k0,
+                                          int kend, int tid, float (&av)[4], float (&bv)[4]) {
+    const int kk = k0 + (tid & 3) * 4;
+    if (VEC && kk + 3 < kend) {
+        if (RA) {
+            const f4 x = *(const f4*)(ap + kk);
+            av[0] = x.x; av[1] = x.y; av[2] = x.z; av[3] = x.w;
+        }
+        if (RB) {
+            const f4 y = *(const f4*)(bp + kk);
+            bv[0] = y.x; bv[1] = y.y; bv[2] = y.z; bv[3] = y.w;
         }
     } else {
-        const int kk = tid >> 4, r = (tid & 15) * 4;
-        const int k = k0 + kk;
-        const bool kok = k < kend;
-        const float* p = X + (size_t)(kok ? k : 0) * ldx;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const int rr = r0 + r + e;
-            S[kk][r + e] = (kok && rr < rows) ? p[rr] : 0.f;
+            if (RA) av[e] = (kk + e < kend) ? ap[kk + e] : 0.f;
+            if (RB) bv[e] = (kk + e < kend) ? bp[kk + e] : 0.f;
         }
+    }
+    if (RA && !aok) av[0] = av[1] = av[2] = av[3] = 0.f;
+    if (RB && !bok) bv[0] = bv[1] = bv[2] = bv[3] = 0.f;
+}
+
+__device__ __forceinline__ void store_rows(const float (&x)[4], int tid, float (*S)[TG_LD]) {
+    const int r = tid >> 2, kk = (tid & 3) * 4;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) S[kk + e][r] = x[e];
+}
+
+// Stored [k][row] (transposed): 4 consecutive rows of one k, straight into LDS.
+__device__ __forceinline__ void stage_cols(const float* __restrict__ X, int ldx, int r0, int rows, int k0, int kend, int tid,
+                                           float (*S)[TG_LD]) {
+    const int kk = tid >> 4, r = (tid & 15) * 4;
+    const int k = k0 + kk;
+    const bool kok = k < kend;
+    const float* p = X + (size_t)(kok ? k : 0) * ldx;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int rr = r0 + r + e;
+        S[kk][r + e] = (kok && rr < rows) ? p[rr] : 0.f;
     }
 }
 
 // gridDim.z > 1: slab z sums k in [z * kchunk, (z + 1) * kchunk) into C + z * slab_stride, no epilogue (the caller reduces
 // the slabs in order)
-template <int TA, int TB>
+// EPI: the training epilogue (dropout, accumulate, slabs) is compiled in; the plain Linear (bias, ReLU, residual) runs without
+// and ignores kchunk / slab_stride (one slab: k in [0, K), C itself)
+template <int TA, int TB, bool VEC, bool EPI = true>
 __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb,
                                                        float* __restrict__ C, int ldc, long long slab_stride, int M, int N, int K,
                                                        int kchunk, GemmEpi e) {
@@ -74,17 +96,23 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
     __shared__ float Bs[TG_BK][TG_LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int m0 = blockIdx.y * TG_BM, n0 = blockIdx.x * TG_BN;
-    const int kbeg = blockIdx.z * kchunk, kend = min(K, kbeg + kchunk);
+    const int kbeg = EPI ? blockIdx.z * kchunk : 0, kend = EPI ? min(K, kbeg + kchunk) : K;
     const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
     f32x4 acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
         for (int b = 0; b < 2; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // the row of each row-major operand that this thread stages (row 0 where the tile ends: read, then zeroed)
+    const int am = m0 + (tid >> 2), bn = n0 + (tid >> 2);
+    const float* ap = A + (size_t)(TA == 0 && am < M ? am : 0) * lda;
+    const float* bp = B + (size_t)(TB == 1 && bn < N ? bn : 0) * ldb;
     for (int k0 = kbeg; k0 < kend; k0 += TG_BK) {
+        float av[4], bv[4];
+        load_rows<TA == 0, TB == 1, VEC>(ap, am < M, bp, bn < N, k0, kend, tid, av, bv);
         __syncthreads();          // the previous step's fragment reads are done
-        stage_tile<TA>(A, lda, m0, M, k0, kend, tid, As);
-        stage_tile<TB ? 0 : 1>(B, ldb, n0, N, k0, kend, tid, Bs);
+        if (TA == 0) store_rows(av, tid, As); else stage_cols(A, lda, m0, M, k0, kend, tid, As);
+        if (TB == 1) store_rows(bv, tid, Bs); else stage_cols(B, ldb, n0, N, k0, kend, tid, Bs);
         __syncthreads();
 #pragma unroll
         for (int ks = 0; ks < TG_BK; ks += 4) {
@@ -97,10 +125,10 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
             acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
         }
     }
-    const bool slab = gridDim.z > 1;
-    float* Cz = C + (size_t)blockIdx.z * slab_stride;
+    const bool slab = EPI && gridDim.z > 1;
+    float* Cz = EPI ? C + (size_t)blockIdx.z * slab_stride : C;
     DropKey dk{0u, 0u};
-    if (e.drop_thr) dk = drop_key(e.drop_seed);
+    if (EPI && e.drop_thr) dk = drop_key(e.drop_seed);
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -117,9 +145,9 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
                 if (!slab) {
                     v += bs;
                     if (e.relu) v = fmaxf(v, 0.f);
-                    if (e.drop_thr) v = drop_keep(dk, (unsigned)row * (unsigned)N + (unsigned)col, e.drop_thr) ? v * e.drop_scale : 0.f;
+                    if (EPI && e.drop_thr) v = drop_keep(dk, (unsigned)row * (unsigned)N + (unsigned)col, e.drop_thr) ? v * e.drop_scale : 0.f;
                     if (e.resid) v += e.resid[(size_t)row * e.ldr + col];
-                    if (e.accumulate) v += *dst;
+                    if (EPI && e.accumulate) v += *dst;
                 }
                 *dst = v;
             }
@@ -142,28 +170,27 @@ struct AttF32 {
     float drop_scale;
 };
 
-// first visible key of query i (model.py:549-574: causal; same_length hides keys j <= i - s; reset hides the memory)
-__device__ __forceinline__ int vis_lo(const AttF32& a, int i, bool rst) {
-    int lo = 0;
-    if (a.same_length) {
-        const int mask_len = a.M + a.T - a.mem_len;
-        const int s = mask_len > 0 ? a.T - mask_len : a.T;
-        lo = max(0, i - s + 1);
-    }
-    if (rst && lo < a.M) lo = a.M;
-    return lo;
+// first visible key of query i (attn_row_f32.h: one definition for forward and backward)
+__device__ __forceinline__ int vis_lo(const AttF32& a, int i, bool rst) { return vis_lo(a.same_length, a.T, a.M, a.mem_len, i, rst); }
+
+// forward: one wave per (h, b, i) runs attn_row_f32 over the projection buffer with the attention dropout on.  Writes out
+// and lse[(b H + h) T + i] = log-sum-exp of the UNDROPPED scores.
+// (5 waves per SIMD: the register budget the kernel has always had; the mask's hash state sits on top of the row's registers)
+template <int VW>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void relattn_fwd_f32_kernel(const AttF32 a) {
+    const int h = blockIdx.x, b = blockIdx.y, i = blockIdx.z, lane = threadIdx.x, DH = a.DH, B = a.B;
+    const size_t hd = (size_t)h * DH;
+    float lse;
+    const float o = attn_row_f32<VW, true>(a.q + ((size_t)i * B + b) * a.ld_q + hd, a.u + hd, a.vb + hd, a.k + (size_t)b * a.ld_kv + hd,
+                                           a.v + (size_t)b * a.ld_kv + hd, (size_t)B * a.ld_kv, RowsLinear{}, a.rd + hd, a.ld_rd,
+                                           vis_lo(a, i, a.reset && a.reset[b]), i + a.M, DH, a.scale, a.drop_seed, a.drop_thr_hi,
+                                           a.H, b, h, i, lse);
+    if (lane < DH) a.out[((size_t)i * B + b) * a.ld_o + hd + lane] = o * a.drop_scale;
+    if (lane == 0) a.lse[((size_t)b * a.H + h) * a.T + i] = lse;
 }
 
-// keep decision of element (i, j) of (b, h): the DropLane word of that element (lane r16 = j & 15, row 4 g + reg = i & 15)
-__device__ __forceinline__ bool att_keep(const AttF32& a, int b, int h, int i, int j) {
-    DropLane dl;
-    dl.init(a.drop_seed, b, h, a.H, (i & 15) >> 2, j & 15);
-    unsigned hw[4];
-    dl.words(i >> 4, j >> 4, hw);
-    return hw[i & 3] >= a.drop_thr_hi;
-}
-
-// sum_d (x[d] (+ xb[d])) * y[d], d in order (every pass computes a score with the same sequence of fmaf)
+// sum_d (x[d] (+ xb[d])) * y[d], d in order (the sequence of fmaf of the forward, attn_row_f32.h: every pass
+// recomputes the same score)
 template <int VW>
 __device__ __forceinline__ float dotp(const float* __restrict__ x, const float* __restrict__ xb, const float* __restrict__ y, int DH) {
     float s = 0.f;
@@ -180,52 +207,6 @@ __device__ __forceinline__ float dotp(const float* __restrict__ x, const float* 
     return s;
 }
 
-__device__ __forceinline__ float rl(float x, int l) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), l));
-}
-
-// forward: one wave per (h, b, i); a lane owns a key of each 64-key chunk, online softmax across chunks, a lane per feature
-// for P . V.  Writes out and lse[(b H + h) T + i] = log-sum-exp of the UNDROPPED scores.
-template <int VW>
-__global__ __launch_bounds__(64) void relattn_fwd_f32_kernel(const AttF32 a) {
-    __shared__ __attribute__((aligned(16))) float qu[64], qv[64];
-    const int h = blockIdx.x, b = blockIdx.y, i = blockIdx.z, lane = threadIdx.x, DH = a.DH, B = a.B;
-    const float* qr = a.q + ((size_t)i * B + b) * a.ld_q + (size_t)h * DH;
-    if (lane < DH) {
-        const float x = qr[lane];
-        qu[lane] = x + a.u[h * DH + lane];
-        qv[lane] = x + a.vb[h * DH + lane];
-    }
-    __syncthreads();
-    const int lo = vis_lo(a, i, a.reset && a.reset[b]), hi = i + a.M;
-    const size_t sj = (size_t)B * a.ld_kv;
-    const float* kb = a.k + (size_t)b * a.ld_kv + (size_t)h * DH;
-    const float* vb_ = a.v + (size_t)b * a.ld_kv + (size_t)h * DH;
-    const float* rdh = a.rd + (size_t)h * DH;
-    float mrun = -INFINITY, lrun = 0.f, acc = 0.f;
-    for (int j0 = lo; j0 <= hi; j0 += 64) {
-        const int j = j0 + lane;
-        float s = -INFINITY;
-        if (j <= hi)
-            s = (dotp<VW>(qu, nullptr, kb + j * sj, DH) + dotp<VW>(qv, nullptr, rdh + (size_t)(i + a.M - j) * a.ld_rd, DH)) * a.scale;
-        const float mnew = fmaxf(mrun, wave_max(s));
-        float p = (j <= hi) ? expf(s - mnew) : 0.f;
-        const float corr = (mrun == -INFINITY) ? 0.f : expf(mrun - mnew);
-        lrun = lrun * corr + wave_sum(p);          // the normaliser: undropped
-        if (a.drop_thr_hi && j <= hi && !att_keep(a, b, h, i, j)) p = 0.f;
-        acc *= corr;
-        const int n = min(64, hi - j0 + 1);
-        if (lane < DH) {
-            const float* vr = vb_ + (size_t)j0 * sj + lane;
-            for (int jj = 0; jj < n; ++jj) acc = fmaf(rl(p, jj), vr[(size_t)jj * sj], acc);
-        }
-        mrun = mnew;
-    }
-    const bool any = hi >= lo;
-    if (lane < DH) a.out[((size_t)i * B + b) * a.ld_o + (size_t)h * DH + lane] = any ? acc / lrun * a.drop_scale : 0.f;
-    if (lane == 0) a.lse[((size_t)b * a.H + h) * a.T + i] = any ? mrun + logf(lrun) : 0.f;
-}
-
 // dS_ij * scale of a visible (i, j) from the recomputed score: P = exp(s - lse_i), dP = keep / (1 - p) dO_i . v_j,
 // dS = P (dP - delta_i) with delta_i = dO_i . O_i (that holds with dropout too).  pdrop = the dropped probability.
 template <int VW>
@@ -238,7 +219,7 @@ __device__ __forceinline__ float att_ds(const AttF32& a, int b, int h, int i, in
     float dp = dotp<VW>(dorow, nullptr, vrow, DH);
     pdrop = p;
     if (a.drop_thr_hi) {
-        const bool keep = att_keep(a, b, h, i, j);
+        const bool keep = att_keep(a.drop_seed, a.drop_thr_hi, a.H, b, h, i, j);
         dp = keep ? dp * a.drop_scale : 0.f;
         pdrop = keep ? p * a.drop_scale : 0.f;
     }
@@ -361,7 +342,9 @@ __global__ __launch_bounds__(64) void relattn_bwd_rd_f32_kernel(const AttF32 a) 
 }
 
 // ------------------------------------------------------------------------------------------------ LayerNorm
-// nn.LayerNorm (model.py:179,352) saving mean / rstd: one wave per row (D <= 1024)
+// nn.LayerNorm (model.py:179,352): biased variance, eps inside the root; one wave per row (D <= 1024), two passes over
+// registers; STATS: mean / rstd saved for the backward
+template <bool STATS>
 __global__ __launch_bounds__(256) void layernorm_fwd_f32_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ g,
                                                                 const float* __restrict__ bt, float* __restrict__ y, int ldy,
                                                                 float* __restrict__ mean_out, float* __restrict__ rstd_out,
@@ -369,7 +352,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_f32_kernel(const float* __r
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= rows) return;
     const float* xr = x + (size_t)row * ldx;
-    float v[16];
+    float v[16];          // D <= 1024
     float s = 0.f;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
@@ -391,7 +374,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_f32_kernel(const float* __r
         const int c = lane + 64 * e;
         if (c < D) y[(size_t)row * ldy + c] = (v[e] - mean) * rstd * g[c] + bt[c];
     }
-    if (lane == 0) {
+    if (STATS && lane == 0) {
         mean_out[row] = mean;
         rstd_out[row] = rstd;
     }
@@ -546,14 +529,27 @@ extern "C" int commu_gemm_f32(int ta, int tb, const float* A, int lda, const flo
     }
     const dim3 grid((N + TG_BN - 1) / TG_BN, (M + TG_BM - 1) / TG_BM, nslabs);
     const long long ss = (long long)M * N;
-    if (ta == 0 && tb == 1)
-        COMMU_LAUNCH((gemm_f32_kernel<0, 1>), grid, dim3(256), 0, stream, A, lda, B, ldb, out, ldo, ss, M, N, K, kchunk, e);
-    else if (ta == 0 && tb == 0)
-        COMMU_LAUNCH((gemm_f32_kernel<0, 0>), grid, dim3(256), 0, stream, A, lda, B, ldb, out, ldo, ss, M, N, K, kchunk, e);
-    else if (ta == 1 && tb == 0)
-        COMMU_LAUNCH((gemm_f32_kernel<1, 0>), grid, dim3(256), 0, stream, A, lda, B, ldb, out, ldo, ss, M, N, K, kchunk, e);
+    // 16-byte staging loads (load_rows) when every row-major operand allows them
+    const bool vec = (ta || (lda % 4 == 0 && (uintptr_t)A % 16 == 0)) && (!tb || (ldb % 4 == 0 && (uintptr_t)B % 16 == 0));
+#define GEMM_F32_LAUNCH(TA, TB, VEC) \
+    COMMU_LAUNCH((gemm_f32_kernel<TA, TB, VEC>), grid, dim3(256), 0, stream, A, lda, B, ldb, out, ldo, ss, M, N, K, kchunk, e)
+    if (ta == 1 && tb == 0)
+        GEMM_F32_LAUNCH(1, 0, false);          // (no row-major operand)
+    else if (ta == 0 && tb == 1 && vec && !e.drop_thr && !accumulate && nslabs == 1)
+        COMMU_LAUNCH((gemm_f32_kernel<0, 1, true, false>), grid, dim3(256), 0, stream, A, lda, B, ldb, out, ldo, ss, M, N, K, kchunk, e);
+    else if (ta == 0 && tb == 1 && vec)
+        GEMM_F32_LAUNCH(0, 1, true);
+    else if (ta == 0 && tb == 1)
+        GEMM_F32_LAUNCH(0, 1, false);
+    else if (ta == 0 && vec)
+        GEMM_F32_LAUNCH(0, 0, true);
+    else if (ta == 0)
+        GEMM_F32_LAUNCH(0, 0, false);
+    else if (vec)
+        GEMM_F32_LAUNCH(1, 1, true);
     else
-        COMMU_LAUNCH((gemm_f32_kernel<1, 1>), grid, dim3(256), 0, stream, A, lda, B, ldb, out, ldo, ss, M, N, K, kchunk, e);
+        GEMM_F32_LAUNCH(1, 1, false);
+#undef GEMM_F32_LAUNCH
     COMMU_LAUNCH_CHECK();
     if (nslabs > 1) return commu_reduce_slabs_f32(C, ws, (size_t)M * N, nslabs, (size_t)M * N, accumulate, 1.f, stream);
     return 0;
@@ -608,8 +604,13 @@ extern "C" int commu_relattn_bwd_f32(const float* q, int ld_q, const float* k, c
 extern "C" int commu_layernorm_fwd_f32(const float* x, int ldx, const float* gamma, const float* beta, float* y, int ldy, float* mean,
                                        float* rstd, int rows, int D, float eps, hipStream_t stream) {
     if (rows <= 0 || D <= 0 || D > 1024) return -22;
-    COMMU_LAUNCH(layernorm_fwd_f32_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, x, ldx, gamma, beta, y, ldy, mean, rstd, rows,
-                 D, eps);
+    if ((mean == nullptr) != (rstd == nullptr)) return -22;
+    if (mean)
+        COMMU_LAUNCH(layernorm_fwd_f32_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, stream, x, ldx, gamma, beta, y, ldy, mean,
+                     rstd, rows, D, eps);
+    else          // (the forward-only callers: parity forward, decode step)
+        COMMU_LAUNCH(layernorm_fwd_f32_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, stream, x, ldx, gamma, beta, y, ldy, mean,
+                     rstd, rows, D, eps);
     COMMU_LAUNCH_CHECK();
     return 0;
 }

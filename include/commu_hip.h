@@ -535,7 +535,8 @@ int commu_copy_rows_masked_f32(float* dst, int ldd, const float* src, int lds, c
  * MFMA products, accurate expf / sinf / cosf -- so that greedy decoding (midi_inferrer.py:199-237, temperature 0) picks
  * the reference's tokens wherever the top-1 / top-2 logit gap exceeds fp32 summation-order noise (~1e-6 of the range). */
 /* nn.Linear (model.py:46,164,167,205,212,278): C[M,N] = A[M,K] . B[N,K]^T (+ bias[n]) (ReLU if relu) (+ resid[m,n]); all
- * fp32 row-major; any M, N, K. */
+ * fp32 row-major; any M, N, K.  M <= 64 with 16-byte aligned operands (the decode step): a skinny kernel of its own;
+ * otherwise commu_gemm_f32 (ta 0, tb 1, one slab).  LayerNorm of this mode: commu_layernorm_fwd_f32 with null mean / rstd. */
 int commu_gemm_nt_f32(const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K,
                       const float* bias, const float* resid, int ldr, int relu, hipStream_t stream);
 /* model.py:409-420: out[row][0:D] = E[tok[row]][0:D] * scale (scale = sqrt(d_model)) */
@@ -544,9 +545,6 @@ int commu_embed_f32(const long long* tok, const float* E, float* out, int ld, in
 /* model.py:142-147 indexed by DISTANCE: out[d] = [sin(p * inv_freq) | cos(p * inv_freq)], d = 0 .. n-1, p = d or
  * min(d, clamp_len) when clamp_len > 0 (model.py:581-582) */
 int commu_posemb_f32(const float* inv_freq, float* out, int ld, int n, int D, int clamp_len, hipStream_t stream);
-/* nn.LayerNorm (model.py:179,352), D <= 1024 */
-int commu_layernorm_f32(const float* x, int ldx, const float* gamma, const float* beta, float* y, int ldy, int rows,
-                        int D, float eps, hipStream_t stream);
 /* model.py:283-345 (RelPartialLearnableMultiHeadAttn.forward without the projections), eval mode: q [T*B rows][ld_q]
  * (row i*B+b, head h at column h*DH), element (key j, sequence b, head h, d) of k / v at base + j*stride_key +
  * b*stride_seq + h*DH + d, rd [distance][ld_rd], out [T*B][ld_o].  klen (optional, int32 [B]): memory length of each
@@ -566,7 +564,7 @@ int commu_decode_kv_append_f32(const float* qkv, int ld, float* kc, float* vc, c
  * commu_decode_attn_ring_f32 (q: row b of the new tokens' projections, already appended) attends positions
  * max(0, klen[b] - (W - 1)) .. klen[b] in chronological order at distance klen[b] - p (rd: [>= W][ld_rd]), the oldest
  * hidden when same_length != 0 and klen[b] >= W - 1.  Before the first wrap the result equals commu_relattn_f32's on
- * the linear cache bit for bit. */
+ * the linear cache bit for bit (one row function, csrc/attn_row_f32.h, behind both and behind commu_relattn_fwd_f32). */
 int commu_decode_kv_append_ring_f32(const float* qkv, int ld, float* kc, float* vc, const int* klen,
                                     const unsigned char* active, int B, int HD, int W, hipStream_t stream);
 int commu_decode_attn_ring_f32(const float* q, int ld_q, const float* kc, const float* vc, const float* rd, int ld_rd,
@@ -608,7 +606,7 @@ int commu_relattn_bwd_f32(const float* q, int ld_q, const float* k, const float*
                           float* dq_ac, float* dq_bd, float* dk, float* dv, int ld_dkv, float* drd, int ld_drd, int T,
                           int M, int B, int H, int DH, int same_length, int mem_len, float scale, float drop_p,
                           unsigned drop_seed, hipStream_t stream);
-/* nn.LayerNorm (model.py:179,352) saving mean / rstd [rows]; D <= 1024 */
+/* nn.LayerNorm (model.py:179,352), D <= 1024; mean / rstd [rows] (both or neither; null: not saved) for the backward */
 int commu_layernorm_fwd_f32(const float* x, int ldx, const float* gamma, const float* beta, float* y, int ldy, float* mean,
                             float* rstd, int rows, int D, float eps, hipStream_t stream);
 /* LayerNorm backward: dx = rstd (g dy - mean(g dy) - xhat mean(g dy xhat)) with dy = dy + add (add: optional second

@@ -178,6 +178,31 @@ def test_attention_f32_fwd_bwd_vs_float64(case):
     assert rel(dq_ac + dq_bd, dqkv[M * B:, :HD]) == 0.0
 
 
+@pytest.mark.parametrize("DH", [36, 50])          # 36: the 16-byte vector path, 50: the scalar path
+def test_attention_f32_forward_two_entries_agree_bitwise(DH):
+    """commu_relattn_fwd_f32 without dropout and commu_relattn_f32 run ONE row function (csrc/attn_row_f32.h): the same bits
+    from the same projections; the training entry's lse against float64 at the bound of the test above."""
+    from commu_amd import ops
+    T, M, B, H, sl, mem_len = 5, 3, 2, 2, True, 3
+    K, HD = T + M, H * DH
+    qkv, rd, u, vb, _, reset = _attn_case(T, M, B, H, DH, sl, 1, 0, 0.0)
+    scale = 1.0 / math.sqrt(DH)
+    q64 = qkv[M * B:, :HD].double().reshape(T, B, H, DH)
+    k64 = qkv[:, HD:2 * HD].double().reshape(K, B, H, DH)
+    S = X.rel_attention_scores(q64, k64, rd.double().flip(0).reshape(K, H, DH), u.double().view(H, DH),
+                               vb.double().view(H, DH)) * scale
+    S = S.masked_fill(X.attn_mask(T, M, B, reset, sl, mem_len)[:, None], float("-inf"))
+    lse_ref = torch.logsumexp(S, 3)
+    qkv_d, rd_d, u_d, vb_d, rst = qkv.to(DEV), rd.to(DEV), u.to(DEV), vb.to(DEV), reset.to(DEV, torch.uint8)
+    q, k, v = qkv_d[M * B:, :HD], qkv_d[:, HD:2 * HD], qkv_d[:, 2 * HD:]
+    out_t, lse = ops.relattn_fwd_f32(q, k, v, rd_d, u_d, vb_d, rst, T, M, B, H, DH, sl, mem_len, scale, drop_p=0.0)
+    out_p = ops.relattn_f32(q, k, v, B * 3 * HD, 3 * HD, rd_d, u_d, vb_d, T, M, B, H, DH, sl, mem_len, scale, reset=rst)
+    torch.cuda.synchronize()
+    assert torch.isfinite(out_p).all()
+    assert torch.equal(out_t, out_p)
+    assert rel(lse, lse_ref) <= 1e-5
+
+
 @pytest.mark.parametrize("with_add", [False, True])
 def test_layernorm_f32_bwd_vs_float64(with_add):
     from commu_amd import ops
@@ -418,6 +443,43 @@ def test_parity_fp32_alone_still_raises_on_a_gradient_pass(golden_dir):
     data, target = torch.from_numpy(z["data0"]).to(DEV), torch.from_numpy(z["target0"]).to(DEV)
     with pytest.raises(CommuHipError, match="fp32_training"):
         model(data, target, None, None)
+
+
+def test_fp32_training_forward_equals_parity_forward_bitwise():
+    """ONE fp32 forward schedule and one set of kernels behind both modes: the gradient-enabled fp32_training pass in eval()
+    mode and the no-grad parity_fp32 pass give the same bits -- loss and new_mems of two consecutive segments, the second
+    with memory and one reset sequence.  Every Linear has more than 64 rows (T * B = M * B = 130, T = 65 distances), so
+    neither mode takes the decode step's skinny kernel."""
+    from commu_amd.model.config_helper import get_cfg
+    from commu_amd.model.dataset import BaseVocab
+    from commu_amd.train import build_model
+    T, B = 65, 2
+    cfg = get_cfg(num_layers=2, num_heads=2, units=72, inner_size=100, tgt_length=T, mem_length=65, batch_size=B,
+                  batch_chunk=1, dropout=0.1, attention_dropout=0.1)
+    model = build_model(cfg, BaseVocab(), torch.device(DEV), seed=11)
+    model.eval()
+    assert (model.n_layer, model.n_head, model.d_model, model.d_head, model.d_inner, model.mem_len) == (2, 2, 72, 36, 100, 65)
+    g = torch.Generator().manual_seed(3)
+    segs = [(torch.randint(0, model.n_token, (T, B), generator=g).to(DEV),
+             torch.randint(0, model.n_token, (T, B), generator=g).to(DEV),
+             torch.tensor(r, dtype=torch.bool, device=DEV)) for r in ([False, False], [False, True])]
+
+    def run():
+        mems, outs = None, []
+        for data, target, reset in segs:
+            loss, mems = model(data, target, reset, mems)
+            outs.append((loss.detach(), mems))
+        return outs
+    model.fp32_training = True
+    train = run()
+    assert train[0][0].dtype == torch.float32 and train[1][1].shape == (3, 65, B, 72)
+    model.fp32_training, model.parity_fp32 = False, True
+    with torch.no_grad():
+        parity = run()
+    for (loss_t, mems_t), (loss_p, mems_p) in zip(train, parity):
+        assert torch.isfinite(loss_p).all()
+        assert torch.equal(loss_t, loss_p)
+        assert torch.equal(mems_t, mems_p)
 
 
 # ------------------------------------------------------------------------------------------------ Trainer / CLI
