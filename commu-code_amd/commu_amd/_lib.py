@@ -127,6 +127,8 @@ PROTOTYPES = {
     "commu_transpose_heads": [c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
     "commu_sample_topk": [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_f, c_i, c_p, c_p, c_i, c_p],
     "commu_sample_topk_topp": [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_f, c_i, c_f, c_p, c_p, c_i, c_p],
+    "commu_sample_topk_topp_rows": [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_f, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_i, c_p,
+                                    c_p],
     "commu_decode_kv_append": [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
     "commu_decode_attn": [c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_p],
     "commu_decode_attn_split": [c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_i,
@@ -149,6 +151,12 @@ PROTOTYPES = {
     "commu_forcing_post": [c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p],
     "commu_decode_sample_post_pre": [c_p, c_i, c_i, c_p, c_f, c_i, c_f, c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_i,
                                      c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_p],
+    "commu_forcing_pre_rows": [c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i,
+                               c_p],
+    "commu_forcing_post_rows": [c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_p],
+    "commu_decode_sample_post_pre_rows": [c_p, c_i, c_i, c_p, c_f, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p,
+                                          c_i, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i,
+                                          c_p],
     "commu_copy_rows_masked_f32": [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_p],
     "commu_pack_batch": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, C.c_longlong, c_p, c_p],
     "commu_gemm_nt_f32": [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p],

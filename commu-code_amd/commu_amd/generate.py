@@ -37,6 +37,44 @@ def _s():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _per_row(x, B: int, name: str):
+    """x broadcast to B float64 values: a number, or a sequence of exactly B numbers."""
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    if np.ndim(x) == 0:
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating, np.ndarray)):
+            raise CommuHipError(f"{name}: a number or a sequence of {B} numbers expected, got {x!r}")
+        return np.full(B, x, dtype=np.float64)
+    try:
+        a = np.asarray(x, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise CommuHipError(f"{name}: a number or a sequence of {B} numbers expected, got {x!r}") from None
+    if a.ndim != 1 or a.shape[0] != B:
+        raise CommuHipError(f"{name}: {B} values expected (one per sequence), got shape {a.shape}")
+    return a
+
+
+def sampling_rows(B: int, temperature, top_k, top_p=1.0):
+    """The sampling controls of B sequences as three numpy arrays (float32 temperature, int32 top_k, float32 top_p): each
+    argument is a number for all sequences or a sequence of B numbers.  Pure host code; raises CommuHipError on a
+    negative or non-finite temperature, a top_k outside [1, 729] (or not an integer), a top_p outside (0, 1] and on a wrong
+    length -- the kernels do not validate what the arrays hold."""
+    B = int(B)
+    t = _per_row(temperature, B, "temperature")
+    k = _per_row(top_k, B, "top_k")
+    p = _per_row(top_p, B, "top_p")
+    V = TOKEN_OFFSET.VOCAB_SIZE
+    if not bool(np.all(np.isfinite(t) & (t >= 0))):
+        raise CommuHipError(f"temperature: finite values >= 0 expected (0 = greedy), got {t[~(np.isfinite(t) & (t >= 0))][0]}")
+    ok = np.isfinite(k) & (k == np.floor(k)) & (k >= 1) & (k <= V)
+    if not bool(np.all(ok)):
+        raise CommuHipError(f"top_k: integers in [1, {V}] expected, got {k[~ok][0]}")
+    ok = (p > 0) & (p <= 1)          # (NaN fails both comparisons)
+    if not bool(np.all(ok)):
+        raise CommuHipError(f"top_p: values in (0, 1] expected (1 = off), got {p[~ok][0]}")
+    return t.astype(np.float32), k.astype(np.int32), p.astype(np.float32)
+
+
 class DecodeState:
     """K/V caches + distance-indexed R tables for B sequences of up to Lmax positions.
 
@@ -398,6 +436,22 @@ class ForcedDecoder:
         self.draw = torch.zeros(B, dtype=u8, device=dev)
         self.uni = torch.zeros(B, dtype=F32, device=dev)
         self.token = torch.zeros(B, dtype=i32, device=dev)
+        # The sampling controls are per-slot device state the kernels read (a captured graph follows them: set_sampling
+        # rewrites them in place); the constructor's triple is every slot's initial value.  TWO MODES: while every slot has
+        # the same triple, that triple is what the captured launches hold, and no log-probabilities were asked for, the
+        # launches get the scalars and null arrays (the measured cost of the arrays: docs/EXPERIMENTS.md 8i).  Slots that
+        # differ, a new triple for launches already captured (a graph holds its scalars), or record_logprobs() switch the
+        # decoder to the arrays for good: the captured graphs are dropped once, and from then on settings change in place.
+        self.rows_on = False
+        self._sampling = sampling_rows(B, self.temperature, self.top_k, self.top_p)          # host mirror
+        self.temperature, self.top_p = float(self._sampling[0][0]), float(self._sampling[2][0])      # (as fp32 holds them)
+        self.temperature_rows = torch.from_numpy(self._sampling[0]).to(dev)
+        self.top_k_rows = torch.from_numpy(self._sampling[1]).to(dev)
+        self.top_p_rows = torch.from_numpy(self._sampling[2]).to(dev)
+        # log-probability pairs (full, kept) of the tokens in seq, NaN where a token was not drawn (context, forced), and
+        # the pair of the current draw beside `token` (the hand-over of the separate launches)
+        self.seq_logp = torch.full((B, self.ld_seq, 2), float("nan"), dtype=F32, device=dev)
+        self.logp = torch.full((B, 2), float("nan"), dtype=F32, device=dev)
         self.probs = None
         self.ld_trace = 2 * (self.generation_length + 2) if record_trace else 0
         self.trace = torch.zeros(B, self.ld_trace, dtype=i32, device=dev) if record_trace else None
@@ -409,30 +463,88 @@ class ForcedDecoder:
     # on the current stream.  The captured graph holds [step, {sample, post, pre of the NEXT iteration} as one launch]
     # (body_pre): run() issues the very first `pre` on its own and the kernel sequence is the same captured or not.
     # pre() / body() are the separate launches (iteration(): tests look at the draws between the stages).
+    def _rows_mode(self):
+        if not self.rows_on:
+            self.rows_on = True
+            self.graph = self.graph_long = None          # (they hold the launches without the arrays)
+            for dst, src in zip((self.temperature_rows, self.top_k_rows, self.top_p_rows), self._sampling):
+                dst.copy_(torch.from_numpy(src))         # (scalar mode kept the host mirror only)
+
+    def record_logprobs(self):
+        """Keep the log-probability pair of every token from now on (logprobs(), harvest_logprobs()).  Call it before
+        load(): tokens appended earlier have no entry.  Switches the decoder to the array launches (see __init__)."""
+        self._rows_mode()
+
+    def _rows_args(self):
+        """(temperature_rows, top_k_rows, top_p_rows, logp, seq_logp) as the launches get them."""
+        if not self.rows_on:
+            return None, None, None, None, None
+        return self.temperature_rows, self.top_k_rows, self.top_p_rows, self.logp, self.seq_logp
+
+    def set_sampling(self, temperature=None, top_k=None, top_p=None, rows: Optional[Sequence[int]] = None):
+        """New sampling controls for all slots (rows=None) or the listed ones: each of temperature / top_k / top_p is None
+        (unchanged), a number, or one value per addressed slot.  With the array launches (see __init__) the device arrays
+        are rewritten IN PLACE, ordered on the current stream like any launch: a captured graph keeps pointing at them and
+        needs no re-capture.  A few slots (rearm) are written by device-side fills -- no host copy, no synchronisation --,
+        a whole batch by one copy per array that changed."""
+        idx = np.arange(self.B) if rows is None else np.asarray(list(rows), dtype=np.int64)
+        if idx.ndim != 1 or (idx.size and (idx.min() < 0 or idx.max() >= self.B)):
+            raise CommuHipError(f"rows: slot numbers in [0, {self.B}) expected, got {rows!r}")
+        cur = self._sampling
+        new = sampling_rows(len(idx), *(cur[i][idx] if v is None else v for i, v in enumerate((temperature, top_k, top_p))))
+        changed = [not np.array_equal(cur[i][idx], new[i]) for i in range(3)]
+        for i in range(3):
+            cur[i][idx] = new[i]
+        if not self.rows_on:
+            if any(bool((c != c[0]).any()) for c in cur):
+                return self._rows_mode()                 # slots differ (uploads the mirror)
+            triple = (float(cur[0][0]), int(cur[1][0]), float(cur[2][0]))
+            if triple == (self.temperature, self.top_k, self.top_p):
+                return
+            if self.graph is not None or self.graph_long is not None:
+                return self._rows_mode()                 # the captured launches hold the old scalars
+            self.temperature, self.top_k, self.top_p = triple
+            return
+        for i, dst in enumerate((self.temperature_rows, self.top_k_rows, self.top_p_rows)):
+            if not changed[i]:
+                continue
+            if len(idx) <= 4:
+                for j in idx:
+                    dst[int(j)].fill_(cur[i][j].item())
+            elif bool((cur[i] == cur[i][0]).all()):
+                dst.fill_(cur[i][0].item())
+            else:
+                dst.copy_(torch.from_numpy(cur[i]))
+
     def pre(self):
-        call("commu_forcing_pre", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_tok), _p(self.chord_pos),
+        call("commu_forcing_pre_rows", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_tok), _p(self.chord_pos),
              self.ld_chord, _p(self.wrong), _p(self.utable), self.ld_u, self.generation_length, _p(self.tok),
-             _p(self.active), _p(self.keep), _p(self.draw), _p(self.uni), _p(self.trace), self.ld_trace, self.B, _s())
+             _p(self.active), _p(self.keep), _p(self.draw), _p(self.uni), _p(self.trace), self.ld_trace,
+             _p(self._rows_args()[4]), self.B, _s())
 
     def body(self, want_probs: bool = False):
         B = self.B
         self.state.step(self.tok, self.active, None)
         if want_probs and self.probs is None:
             self.probs = torch.zeros(B, TOKEN_OFFSET.VOCAB_SIZE, device=self.dev)
-        ops.sample_topk(self.state.logits, self.temperature, self.top_k, wrong=self.wrong, uniforms=self.uni,
-                        active=self.draw, token=self.token, probs_out=self.probs if want_probs else None,
-                        top_p=self.top_p)
-        call("commu_forcing_post", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_pos), self.ld_chord,
+        t_r, k_r, p_r, logp, seq_logp = self._rows_args()
+        ops.sample_topk(self.state.logits, self.temperature if t_r is None else t_r, self.top_k if k_r is None else k_r,
+                        wrong=self.wrong, uniforms=self.uni, active=self.draw, token=self.token,
+                        probs_out=self.probs if want_probs else None, top_p=self.top_p if p_r is None else p_r,
+                        logp_out=logp)
+        call("commu_forcing_post_rows", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_pos), self.ld_chord,
              _p(self.wrong), _p(self.draw), _p(self.token), None, _p(self.state.klen), _p(self.keep),
-             self.state.klen_cap, B, _s())
+             self.state.klen_cap, _p(logp), _p(seq_logp), B, _s())
 
     def body_pre(self):
         """body() followed by pre() with the three per-sequence stages (sampling step, post, pre) as one launch: what
         run() issues per iteration, captured or not."""
         st = self.state
         st.step(self.tok, self.active, None)
-        call("commu_decode_sample_post_pre", _p(st.logits), st.logits.stride(0), TOKEN_OFFSET.VOCAB_SIZE, _p(self.wrong),
-             self.temperature, self.top_k, self.top_p, _p(self.token), None, 0, _p(self.fsm), _p(self.seq), self.ld_seq,
+        t_r, k_r, p_r, _, seq_logp = self._rows_args()          # (fused: the pair reaches post in registers, no hand-over)
+        call("commu_decode_sample_post_pre_rows", _p(st.logits), st.logits.stride(0), TOKEN_OFFSET.VOCAB_SIZE,
+             _p(self.wrong), self.temperature, self.top_k, self.top_p, _p(t_r), _p(k_r), _p(p_r), _p(self.token), None, 0,
+             None, _p(seq_logp), _p(self.fsm), _p(self.seq), self.ld_seq,
              _p(self.chord_tok), _p(self.chord_pos), self.ld_chord, _p(self.utable), self.ld_u, self.generation_length,
              _p(self.tok), _p(self.active), _p(self.keep), _p(self.draw), _p(self.uni), _p(self.trace), self.ld_trace,
              _p(st.klen), st.klen_cap, self.B, _s())
@@ -457,7 +569,8 @@ class ForcedDecoder:
         long memories (commu_decode_attn_split: up to LONG_SPLITS workgroups per (sequence, head) pair)."""
         st = self.state
         # (the K/V rows the warm-up appends at klen are rewritten by the real run: the caches need no copy)
-        bufs = (self.fsm, self.seq, self.wrong, st.klen, st.logits, self.tok, self.active, self.keep, self.draw, self.uni)
+        bufs = (self.fsm, self.seq, self.wrong, st.klen, st.logits, self.tok, self.active, self.keep, self.draw, self.uni,
+                self.seq_logp, self.logp)
         saved = [t.clone() for t in bufs]
         tr = None if self.trace is None else self.trace.clone()
         keep_splits, st.attn_splits = st.attn_splits, (self.LONG_SPLITS if long else 1)
@@ -529,6 +642,8 @@ class ForcedDecoder:
             fsm[b] = [1 + n_cond, -1, 0, 1, int(nm % 4 == 0), 0, 0, 0, 0, len(ct), 0, int(rep.length_fit), 0, 0]
         self.fsm.copy_(torch.from_numpy(fsm))
         self.seq.copy_(torch.from_numpy(seq))
+        self.seq_logp.fill_(float("nan"))          # (the context was not drawn)
+        self.logp.fill_(float("nan"))
         self.chord_tok.copy_(torch.from_numpy(ctok))
         self.chord_pos.copy_(torch.from_numpy(cpos))
         self.wrong.zero_()
@@ -545,8 +660,12 @@ class ForcedDecoder:
     # the state record, the lengths, the rejected-token map and the variates are reset.  The re-armed slot sits out the
     # iteration in flight (its decision was taken from the finished record) and starts with the next one.
     # Sliding memory: the slot's ring may have wrapped over its context rows, so they are restored from the copy load()
-    # took -- device-side copies on the decode stream, ordered between two graph replays, no synchronisation.
-    def rearm(self, b: int, uniforms_row: Optional[np.ndarray] = None):
+    # took -- device-side copies on the decode stream, ordered between two graph replays, no synchronisation (the small
+    # host-to-device copies of the state record and the variates are the ones a re-arm always made).
+    # sampling: a (temperature, top_k, top_p) triple for the slot's next attempt (None: the slot keeps its controls).
+    def rearm(self, b: int, uniforms_row: Optional[np.ndarray] = None, sampling=None):
+        if sampling is not None:
+            self.set_sampling(*sampling, rows=[b])
         rep0 = self.reports[b]
         rep = ForcingReport(rep0.n_chords, rep0.num_measures)
         self.reports[b] = rep
@@ -554,6 +673,7 @@ class ForcedDecoder:
                int(rep.length_fit), 0, 0]
         self.fsm[b].copy_(torch.tensor(rec, dtype=torch.int32))
         self.wrong[b].zero_()
+        self.seq_logp[b].fill_(float("nan"))
         if self.sliding:
             st, n = self.state, self.n_cond
             ck, cv = self._ctx_kv
@@ -578,6 +698,18 @@ class ForcedDecoder:
         if fsm_row[6]:
             return None
         return self.seq[b, :int(fsm_row[0])].cpu().tolist()
+
+    def _need_logprobs(self):
+        if not self.rows_on:
+            raise CommuHipError("no log-probabilities were recorded: call record_logprobs() (or set_sampling()) before load()")
+
+    def harvest_logprobs(self, b: int, fsm_row):
+        """harvest()'s companion: the log-probability pairs (full, kept) of slot b's tokens, numpy [len, 2] with NaN rows
+        where a token was not drawn (context, forced); None where the sequence failed."""
+        self._need_logprobs()
+        if fsm_row[6]:
+            return None
+        return self.seq_logp[b, :int(fsm_row[0])].cpu().numpy()
 
     # ---- done flags without stalling the GPU: the flags of window k are copied to pinned memory behind window k and
     # looked at after window k + 1 has been queued, so the device never waits for the host between windows (a
@@ -604,6 +736,8 @@ class ForcedDecoder:
         long = klen_bound > self.LONG_KLEN and live_rows is not None and live_rows <= self.LONG_ROWS
         if use_graph and long and getattr(self, "graph_long", None) is None:
             self.build_graph(long=True)
+        if use_graph and not long and self.graph is None:          # (dropped by a set_sampling / record_logprobs since)
+            self.build_graph()
         g = self.graph_long if (use_graph and long) else self.graph
         if not use_graph:
             keep_splits, self.state.attn_splits = self.state.attn_splits, (self.LONG_SPLITS if long else 1)
@@ -668,10 +802,21 @@ class ForcedDecoder:
                 traces.append(t)
         return out, traces
 
+    def logprobs(self):
+        """Per sequence the [len, 2] float32 array of (full, kept) log-probabilities of its tokens -- full: log-softmax
+        over ids 1 .. 728 of the row the draw used (logits / temperature) at the token; kept: log of the token's probability
+        in the distribution it was drawn from (0 for greedy); NaN rows for the context and forced tokens -- or None where
+        the sequence failed (Q12)."""
+        self._need_logprobs()
+        fsm = self.fsm.cpu().numpy()
+        lp = self.seq_logp.cpu().numpy()
+        return [None if fsm[b, 6] else lp[b, :fsm[b, 0]].copy() for b in range(self.B)]
+
 
 class BatchedGenerator:
-    """Generates `len(input_datas)` sequences in parallel (temperature / top_k shared by the batch, per-sequence
-    `num_measures` / `chord_token_components`).  Decoders (caches + captured graph) are kept per batch size."""
+    """Generates `len(input_datas)` sequences in parallel (per-sequence temperature / top_k / top_p, `num_measures` and
+    `chord_token_components`).  Decoders (caches + captured graph) are kept per batch size: the sampling controls are
+    device state of the decoder, so a new setting reuses the cache and the capture."""
 
     def __init__(self, model, device, generation_length=4096, memory_length=4146, sliding=False):
         self.model, self.device = model, device
@@ -682,24 +827,34 @@ class BatchedGenerator:
         self.use_graph = True
         self._decoders = {}
 
-    def decoder(self, B, temperature, top_k, max_chords, top_p=1.0):
-        key = (B, float(temperature), int(top_k), float(top_p), self.trace is not None, self.sliding)
+    def decoder(self, B, temperature, top_k, max_chords, top_p=1.0, per_slot: bool = False):
+        """The decoder for B slots, its slots set to the given controls (numbers or one value per slot).  per_slot: the
+        caller will read log-probabilities or give slots their own controls later (rearm): the array launches from the
+        start.  Otherwise one triple for all slots runs the scalar launches, until a second setting arrives for launches
+        that are already captured (ForcedDecoder.__init__)."""
+        rows = sampling_rows(B, temperature, top_k, top_p)          # (validated before anything is built)
+        key = (B, self.trace is not None, self.sliding)
         dec = self._decoders.get(key)
         if dec is None or dec.ld_chord < max_chords:
-            dec = ForcedDecoder(self.model, B, self.generation_length, self.memory_length, temperature, top_k,
-                                max_chords=max(64, max_chords), record_trace=self.trace is not None, top_p=top_p,
-                                sliding=self.sliding)
+            dec = ForcedDecoder(self.model, B, self.generation_length, self.memory_length, float(rows[0][0]), int(rows[1][0]),
+                                max_chords=max(64, max_chords), record_trace=self.trace is not None,
+                                top_p=float(rows[2][0]), sliding=self.sliding)
             self._decoders[key] = dec
+        if per_slot:
+            dec.record_logprobs()
+        dec.set_sampling(*rows)
         return dec
 
     @torch.no_grad()
-    def generate(self, encoded_metas: Sequence[Sequence[int]], input_datas, temperature: float, top_k: int,
-                 top_p: float = 1.0):
+    def generate(self, encoded_metas: Sequence[Sequence[int]], input_datas, temperature, top_k, top_p=1.0,
+                 return_logprobs: bool = False):
+        """temperature / top_k / top_p: a number for the batch or one value per sequence.  return_logprobs: a third return
+        value, ForcedDecoder.logprobs() of the batch."""
         B = len(input_datas)
         max_chords = max(len(d.chord_token_components["chord_token"]) for d in input_datas)
-        dec = self.decoder(B, temperature, top_k, max_chords, top_p)
+        dec = self.decoder(B, temperature, top_k, max_chords, top_p, per_slot=return_logprobs)
         uniforms = None
-        if temperature != 0:
+        if bool((dec._sampling[0] != 0).any()):
             srcs = self.uniform_sources or [np.random.RandomState(1000 + b).random_sample for b in range(B)]
             uniforms = np.array([[float(srcs[b]()) for _ in range(dec.ld_u)] for b in range(B)], dtype=np.float32)
         dec.load(encoded_metas, input_datas, uniforms)
@@ -707,6 +862,8 @@ class BatchedGenerator:
         seqs, traces = dec.sequences()
         if self.trace is not None:
             self.trace[:] = traces
+        if return_logprobs:
+            return seqs, dec.reports, dec.logprobs()
         return seqs, dec.reports
 
     @staticmethod
@@ -716,26 +873,42 @@ class BatchedGenerator:
         return np.random.RandomState((seed + 7919 * attempt) % (2 ** 32)).random_sample(n).astype(np.float32)
 
     @torch.no_grad()
-    def generate_stream(self, encoded_meta: Sequence[int], input_data, temperature: float, top_k: int, need: int,
-                        accept, top_p: float = 1.0, slots: int = 64, seed: int = 0, max_attempts: Optional[int] = None):
+    def generate_stream(self, encoded_meta: Sequence[int], input_data, temperature, top_k, need: int,
+                        accept, top_p=1.0, slots: int = 64, seed: int = 0, max_attempts: Optional[int] = None,
+                        return_logprobs: bool = False):
         """Attempts of ONE request (the reference's `while idx != num_generate` loop, midi_inferrer.py:338-354, which tries
         one sequence after the other) decoded in up to `slots` parallel slots, CONTINUOUSLY: a slot whose sequence has
         ended is handed to `accept(sequence, report) -> bool` and re-armed with the next attempt while the other slots keep
         decoding -- the batch does not thin out towards the end of a round.  Returns (the first `need` accepted attempts IN
         ATTEMPT ORDER -- exactly what the reference's sequential loop would return for the same per-attempt variates,
         whatever the number of slots --, attempts started); fewer when `max_attempts` attempts did not yield `need`.
-        Attempt a draws from attempt_uniforms(seed, a, .) whichever slot decodes it."""
+        Attempt a draws from attempt_uniforms(seed, a, .) whichever slot decodes it.
+        temperature / top_k / top_p: a number, or a sequence indexed by ATTEMPT NUMBER modulo its length -- like its
+        variates, the controls of attempt a do not depend on the slot that decodes it.  return_logprobs: a third return
+        value, the log-probability arrays (ForcedDecoder.logprobs) of the returned attempts in the same order."""
         B = max(1, min(int(slots), int(need)))
         max_chords = len(input_data.chord_token_components["chord_token"])
-        dec = self.decoder(B, temperature, top_k, max_chords, top_p)
+        # each control's schedule, validated on its own (the three may have different lengths)
+        n_of = lambda x: 1 if np.ndim(x) == 0 else len(x)
+        sched = (sampling_rows(n_of(temperature), temperature, 1, 1.0)[0], sampling_rows(n_of(top_k), 0.0, top_k, 1.0)[1],
+                 sampling_rows(n_of(top_p), 0.0, 1, top_p)[2])
+
+        def triple(a):
+            return tuple(c[a % len(c)].item() for c in sched)
+        first = [triple(a) for a in range(B)]
+        varying = any(bool((c != c[0]).any()) for c in sched)          # (one triple for every attempt: nothing to re-arm)
+        dec = self.decoder(B, [t[0] for t in first], [t[1] for t in first], max_chords, [t[2] for t in first],
+                           per_slot=return_logprobs or varying)
         started = B
-        uni = np.stack([self.attempt_uniforms(seed, a, dec.ld_u) for a in range(B)]) if temperature != 0 else None
+        sampled = bool((sched[0] != 0).any())          # (a greedy attempt reads no variate)
+        uni = np.stack([self.attempt_uniforms(seed, a, dec.ld_u) for a in range(B)]) if sampled else None
         dec.load([list(encoded_meta)] * B, [input_data] * B, uni)
         if self.use_graph and dec.graph is None:
             dec.build_graph()
         dec.pre()
         slot_attempt = list(range(B))          # attempt number decoded in each slot; -1: slot retired
         results = {}                           # attempt -> its sequence if accepted, False if rejected
+        logps = {}                             # (return_logprobs) accepted attempt -> its log-probability array
         n_ok, out = 0, None
         dec.run_iterations(dec.POLL, self.use_graph)
         kb, nlive = 0, None                    # bound of the memory lengths, live slots (from the polled records)
@@ -752,12 +925,15 @@ class BatchedGenerator:
                 seq = dec.harvest(b, fsm[b])
                 ok = bool(accept(seq, dec.reports[b]))
                 results[a] = seq if ok else False
+                if ok and return_logprobs:
+                    logps[a] = dec.harvest_logprobs(b, fsm[b])
                 n_ok += ok
                 # no further attempts once enough were accepted: only the lower-numbered ones still in flight can matter
                 if n_ok >= need or (max_attempts is not None and started >= max_attempts):
                     slot_attempt[b] = -1
                     continue
-                dec.rearm(b, self.attempt_uniforms(seed, started, dec.ld_u) if temperature != 0 else None)
+                dec.rearm(b, self.attempt_uniforms(seed, started, dec.ld_u) if sampled else None,
+                          sampling=triple(started) if varying else None)
                 slot_attempt[b] = started
                 started += 1
             # the answer: the first `need` accepted attempts IN ATTEMPT ORDER, known once every attempt before the last of
@@ -765,16 +941,19 @@ class BatchedGenerator:
             got, a = [], 0
             while a in results and len(got) < need:
                 if results[a] is not False:
-                    got.append(results[a])
+                    got.append(a)
                 a += 1
             if len(got) >= need:
                 out = got
         if out is None:                        # max_attempts exhausted: whatever was accepted, in attempt order
-            out = [results[a] for a in sorted(results) if results[a] is not False][:need]
+            out = [a for a in sorted(results) if results[a] is not False][:need]
+        out, out_lp = [results[a] for a in out], [logps.get(a) for a in out]
         try:
             dec.state.check()
         except CommuHipError:
             dec.state.tail_ok, dec.graph, dec.graph_long = False, None, None          # later requests on this decoder: per-Linear launches
             dec.state.t_err.zero_()
             raise
+        if return_logprobs:
+            return out, started, out_lp
         return out, started

@@ -88,7 +88,8 @@ class InferenceTask:
     def validate_generated_sequence(self, seq: List[int]) -> bool:                           # :322-336
         return count_notes(seq) > 0
 
-    def execute(self, encoded_meta, max_rounds: Optional[int] = None) -> List[List[int]]:    # :338-354
+    def execute(self, encoded_meta, max_rounds: Optional[int] = None, return_logprobs: bool = False):    # :338-354
+        """return_logprobs (not in the reference): (sequences, their log-probability arrays -- ForcedDecoder.logprobs)."""
         from ..generate import BatchedGenerator
         data = self.input_data
         glen = self.inference_cfg.GENERATION.generation_length
@@ -108,7 +109,8 @@ class InferenceTask:
             return self.validate_generated_sequence(seq)
         # attempts decoded in up to 64 slots, a finished slot re-armed with the next attempt (the reference tries one
         # sequence after the other until num_generate passed; `max_rounds` bounds the attempts at max_rounds x num_generate)
-        out, _ = gen.generate_stream(list(encoded_meta), data, data.temperature, data.top_k, data.num_generate, accept,
-                                     top_p=getattr(data, "top_p", 1.0), seed=self.uniform_seed,
-                                     max_attempts=None if max_rounds is None else max_rounds * data.num_generate)
-        return out
+        res = gen.generate_stream(list(encoded_meta), data, data.temperature, data.top_k, data.num_generate, accept,
+                                  top_p=getattr(data, "top_p", 1.0), seed=self.uniform_seed,
+                                  max_attempts=None if max_rounds is None else max_rounds * data.num_generate,
+                                  return_logprobs=return_logprobs)
+        return (res[0], res[2]) if return_logprobs else res[0]

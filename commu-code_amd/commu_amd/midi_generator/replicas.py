@@ -11,8 +11,18 @@ def split_num_generate(num_generate, n_replicas):
     return [base + (1 if r < rem else 0) for r in range(n_replicas)]
 
 
-def generate_on_device(model_args, in_args, device_index, num_generate, uniform_seed, max_rounds, training_cfg=None):
-    """One replica: checkpoint -> model on cuda:<device_index>, `num_generate` validated sequences."""
+def logprobs_to_lists(logprobs):
+    """Log-probability arrays ([len, 2] float32, NaN rows where a token was not drawn) as JSON-ready lists: one list of
+    [full, kept] pairs per sequence, None for the entries that were not drawn."""
+    import math
+    return [None if lp is None else [None if math.isnan(f) or math.isnan(k) else [f, k] for f, k in lp.tolist()]
+            for lp in logprobs]
+
+
+def generate_on_device(model_args, in_args, device_index, num_generate, uniform_seed, max_rounds, training_cfg=None,
+                       logprobs=False):
+    """One replica: checkpoint -> model on cuda:<device_index>, `num_generate` validated sequences (logprobs: and their
+    log-probabilities as logprobs_to_lists gives them, a third value)."""
     import copy
 
     import torch
@@ -30,14 +40,17 @@ def generate_on_device(model_args, in_args, device_index, num_generate, uniform_
     task = InferenceTask(device)
     task.uniform_seed = uniform_seed
     task(model=model, input_data=pre.input_data, inference_cfg=init.inference_cfg)
+    if logprobs:
+        seqs, lps = task.execute(encoded_meta, max_rounds=max_rounds, return_logprobs=True)
+        return encoded_meta, seqs, logprobs_to_lists(lps)
     return encoded_meta, task.execute(encoded_meta, max_rounds=max_rounds)
 
 
-def replica_worker(rank, device_index, model_args, in_args, share, max_rounds, training_cfg, q):
+def replica_worker(rank, device_index, model_args, in_args, share, max_rounds, training_cfg, q, logprobs=False):
     try:
         # distinct variates per replica: 1_000_003 apart (a replica's rounds / sequences use seed + 7919 r + b)
         q.put((rank, generate_on_device(model_args, in_args, device_index, share, 1_000_003 * rank, max_rounds,
-                                        training_cfg)))
+                                        training_cfg, logprobs)))
     except Exception:
         import traceback
         q.put((rank, traceback.format_exc()))

@@ -906,19 +906,48 @@ def _bias_grads(dq, du_part, du, dvb, HD, dev, defer, group=None):
         defer(bias_part)
 
 
+def _sampling_control(x, name, dtype, nseq, device):
+    """A sampling control of sample_topk as (scalar, device array or None): a number applies to every sequence, a tensor
+    [nseq] gives each sequence its own value."""
+    if not isinstance(x, torch.Tensor):
+        return x, None
+    if not x.is_cuda or x.device != device:
+        raise CommuHipError(f"{name}: a per-sequence control lives on the device of the logits (no CPU fallback)")
+    if x.dtype != dtype or x.dim() != 1 or x.numel() != nseq or not x.is_contiguous():
+        raise CommuHipError(f"{name}: contiguous {str(dtype).replace('torch.', '')} [{nseq}] expected, got "
+                            f"{str(x.dtype).replace('torch.', '')} {tuple(x.shape)}")
+    return None, x
+
+
 def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=None, token=None, probs_out=None,
-                top_p=1.0):
+                top_p=1.0, logp_out=None):
     """In-place temperature + softmax + top-k + wrong-token mask + inverse-CDF draw per sequence.
     logits: fp32 [nseq, >=V] (row stride = ld), modified in place (logits[:, 1:V] /= temperature).
-    top_p < 1: nucleus filter after the top-k / rejected-token step (an extra mode; the reference has top-k only)."""
+    top_p < 1: nucleus filter after the top-k / rejected-token step (an extra mode; the reference has top-k only).
+    temperature / top_k / top_p: a number for all sequences, or a device tensor [nseq] (fp32 / int32 / fp32) with one
+    value per sequence -- sequence b's result is that of the scalar call with b's values.  The values of a tensor are not
+    checked here (generate.sampling_rows does that on the host); the kernel clamps top_k to [1, V].
+    logp_out: fp32 [nseq, 2], receives per drawn token (full, kept) -- the log-softmax over ids 1 .. V-1 of the row the
+    draw used at the drawn id, and the log of the token's probability in the distribution it was drawn from (0 for
+    temperature 0); NaN, NaN where nothing could be drawn; untouched where active[b] == 0."""
     nseq = logits.shape[0]
     V = 729
     assert logits.dtype == F32 and logits.stride(1) == 1
+    t_s, t_r = _sampling_control(temperature, "temperature", F32, nseq, logits.device)
+    k_s, k_r = _sampling_control(top_k, "top_k", torch.int32, nseq, logits.device)
+    p_s, p_r = _sampling_control(top_p, "top_p", F32, nseq, logits.device)
+    if logp_out is not None:
+        if not isinstance(logp_out, torch.Tensor) or not logp_out.is_cuda or logp_out.device != logits.device:
+            raise CommuHipError("logp_out: a tensor on the device of the logits expected (no CPU fallback)")
+        if logp_out.dtype != F32 or tuple(logp_out.shape) != (nseq, 2) or not logp_out.is_contiguous():
+            raise CommuHipError(f"logp_out: contiguous float32 [{nseq}, 2] expected, got "
+                                f"{str(logp_out.dtype).replace('torch.', '')} {tuple(logp_out.shape)}")
     if token is None:
         token = torch.empty(nseq, device=logits.device, dtype=torch.int32)
-    call("commu_sample_topk_topp", _p(logits), logits.stride(0), nseq, V, _p(wrong),
-         0 if wrong is None else wrong.stride(0), _p(uniforms), _p(active), float(temperature), int(top_k), float(top_p),
-         _p(token), _p(probs_out), 0 if probs_out is None else probs_out.stride(0), _s())
+    call("commu_sample_topk_topp_rows", _p(logits), logits.stride(0), nseq, V, _p(wrong),
+         0 if wrong is None else wrong.stride(0), _p(uniforms), _p(active), 0.0 if t_s is None else float(t_s),
+         1 if k_s is None else int(k_s), 1.0 if p_s is None else float(p_s), _p(t_r), _p(k_r), _p(p_r), _p(token),
+         _p(probs_out), 0 if probs_out is None else probs_out.stride(0), _p(logp_out), _s())
     return token
 
 

@@ -47,15 +47,41 @@ __device__ __forceinline__ int wscan_i(int v, int lane) {
 // ------------------------------------------------------------------------------------------------ sampling step (K15)
 constexpr int PER_LANE = 12;      // 64 * 12 = 768 >= 729: lane l owns ids [12 l, 12 l + 12)
 
+// The sampling controls of one sequence: scalars for the whole launch, or per-sequence device arrays ([B] each, null: the
+// scalar applies) -- the slots of one batch may sample at different settings, and a captured graph follows the arrays.
+struct SamplingRows {
+    const float* temperature;
+    const int* top_k;
+    const float* top_p;
+};
+
+// the pair of log-probabilities of a drawn token (see sample_topk_body); NaN, NaN: nothing was drawn
+struct TokenLogp {
+    float full, kept;
+};
+
 // one wave per sequence b (lane = threadIdx.x of a 64-thread workgroup)
+// want_logp: also compute `lp`, uniform over the wave, for the drawn token (left alone for inactive sequences) --
+//   full: log-softmax over ids 1 .. V-1 of the row as this draw used it (logits / temperature as written back, the
+//         compounded row on a Q5 re-draw; the raw row for temperature == 0) at the drawn id, as x[id] - max - log(sum);
+//   kept: log of the probability the token had in the distribution it was drawn from (after top-k, rejected-token mask,
+//         top-p and renormalisation; exactly 0 for greedy);
+// and store it to logp_out[b][0:2] when that is not null.
 __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restrict__ logits, int ld, int V,
                                                  const unsigned char* __restrict__ wrong, int ldw,
                                                  const float* __restrict__ uni,
                                                  const unsigned char* __restrict__ active, float temperature,
                                                  int top_k, int* __restrict__ token, float* __restrict__ probs_out,
-                                                 int ldp, float top_p = 1.f) {
-    const unsigned char act = active != nullptr ? active[b] : (unsigned char)1;          // (tested after the loads below are
-    float* lg = logits + (size_t)b * ld;                                                  //  issued: one round trip, not two)
+                                                 int ldp, float top_p, SamplingRows rows, bool want_logp,
+                                                 float* __restrict__ logp_out, TokenLogp& lp) {
+    float* lg = logits + (size_t)b * ld;
+    // The optional per-sequence inputs -- the active flag and this sequence's controls -- are loaded unconditionally: a null
+    // array reads a valid word of this sequence instead (token[b], logits[b][0]), which is then ignored.  So they are in
+    // flight together with the loads below; behind a branch per array each was a memory round trip of its own.
+    const unsigned char act_row = *(active != nullptr ? active + b : reinterpret_cast<const unsigned char*>(token + b));
+    const float t_row = *(rows.temperature != nullptr ? rows.temperature + b : lg);
+    const int k_row = *(rows.top_k != nullptr ? rows.top_k + b : token + b);
+    const float p_row = *(rows.top_p != nullptr ? rows.top_p + b : lg);
     float p[PER_LANE];
     const int base = lane * PER_LANE;
     // every load of the step up front and unconditional (clamped index): one memory round trip, not one per element
@@ -72,8 +98,17 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
             if (base + e < V && wb[e] != 0) wmask |= 1u << e;
     }
     const float u = uni != nullptr ? uni[b] : 0.5f;
-    if (!act) return -2;
+    // one value per wave, kept in scalar registers so that the mode branches below stay scalar branches
+    if (rows.temperature != nullptr)
+        temperature = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, t_row)));
+    if (rows.top_k != nullptr) top_k = __builtin_amdgcn_readfirstlane(k_row);
+    if (rows.top_p != nullptr) top_p = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p_row)));
+    // the radix select below needs 1 <= top_k <= V (exactly one lane owns the threshold bin); the host validates the
+    // values, the clamp keeps the kernel in bounds whatever an array holds
+    top_k = min(max(top_k, 1), V);
+    if (active != nullptr && act_row == 0) return -2;
     // ---- calc_probs
+    float lmx = 0.f, lsum = 1.f;          // (want_logp) max and sum of exp(x - max) over ids 1 .. V-1 of the row drawn from
     if (temperature == 0.f) {
         float best = -INFINITY;
         int bi = V;
@@ -86,6 +121,16 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
         bi = wmin_i(best == wbest ? bi : V);
 #pragma unroll
         for (int e = 0; e < PER_LANE; ++e) p[e] = (base + e == bi) ? 1.f : 0.f;
+        if (want_logp) {                                       // greedy has no softmax: its own max / sum pass
+            float sg = 0.f;
+#pragma unroll
+            for (int e = 0; e < PER_LANE; ++e) {
+                const int id = base + e;
+                sg += (id >= 1 && id < V) ? expf(raw[e] - wbest) : 0.f;
+            }
+            lmx = wbest;
+            lsum = wsum_f(sg);
+        }
     } else {
         float mx = -INFINITY;
 #pragma unroll
@@ -105,6 +150,8 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
             s += p[e];
         }
         s = wsum_f(s);
+        lmx = mx;
+        lsum = s;
         const float inv = 1.f / s;
 #pragma unroll
         for (int e = 0; e < PER_LANE; ++e) p[e] *= inv;
@@ -186,6 +233,10 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
         if (probs_out != nullptr)
             for (int e = 0; e < PER_LANE; ++e)
                 if (base + e < V) probs_out[(size_t)b * ldp + base + e] = NAN;
+        if (want_logp) {
+            lp.full = lp.kept = NAN;
+            if (logp_out != nullptr && lane == 0) logp_out[2 * b] = logp_out[2 * b + 1] = NAN;
+        }
         return -1;
     }
     const float inv = 1.f / tot;
@@ -256,6 +307,21 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
     last = wmax_i(last);
     const int drawn = (cand == (1 << 30)) ? last : cand;
     if (lane == 0) token[b] = drawn;
+    if (want_logp) {
+        // the drawn id's logit and its entry of the distribution, from the lane that owns the id; the row's entry is the
+        // division repeated (the value written back above)
+        float xd = 0.f, pd = 0.f;
+#pragma unroll
+        for (int e = 0; e < PER_LANE; ++e)
+            if (base + e == drawn) { xd = raw[e]; pd = p[e]; }
+        const int owner = max(drawn, 0) / PER_LANE;
+        xd = lane_f(xd, owner);
+        pd = lane_f(pd, owner);
+        if (temperature != 0.f) xd = xd / temperature;
+        lp.full = drawn < 0 ? NAN : (xd - lmx) - logf(lsum);
+        lp.kept = drawn < 0 ? NAN : (temperature == 0.f ? 0.f : logf(pd));
+        if (logp_out != nullptr && lane == 0) { logp_out[2 * b] = lp.full; logp_out[2 * b + 1] = lp.kept; }
+    }
     return drawn;
 }
 
@@ -299,7 +365,7 @@ __device__ __forceinline__ void forcing_pre_body(int b, int lane, int (&s)[F_COU
                                                  int ld_chord, unsigned char* wrong, const float* __restrict__ utable,
                                                  int ld_u, int max_iters, long long* tok, unsigned char* active,
                                                  unsigned char* keep, unsigned char* draw, float* uni, int* trace,
-                                                 int ld_trace) {
+                                                 int ld_trace, float* seq_logp) {
     int* sq = seq + (size_t)b * ld_seq;
     int clear = 0;
     if (lane == 0) {
@@ -314,6 +380,10 @@ __device__ __forceinline__ void forcing_pre_body(int b, int lane, int (&s)[F_COU
                 const int f = s[F_FORCED];
                 s[F_FORCED] = -1;
                 sq[len] = f;
+                if (seq_logp != nullptr) {                              // a forced token was not drawn
+                    float* q = seq_logp + 2 * ((size_t)b * ld_seq + len);
+                    q[0] = q[1] = NAN;
+                }
                 s[F_LEN] = len + 1;
                 if (f == TOK_BAR) s[F_NBAR] += 1;
                 t = f; act = 1; kp = 1;
@@ -371,15 +441,29 @@ __device__ __forceinline__ void forcing_pre_body(int b, int lane, int (&s)[F_COU
 }
 
 // token_val: the token drawn this iteration when the caller has it in a register (>= -1), else (-3) it is read from token[b]
+// seq_logp (optional, fp32 [B][ld_seq][2] parallel to seq): an appended draw's log-probability pair goes to the token's
+// index -- `lp` with a register token, else logp[b][0:2] (null: NaN); a draw that is not appended leaves no entry
+// flags (optional): draw[b], keep[b] and klen[b] as the caller loaded them ahead of the stage (the fused launch has them in
+// flight under the sampling step; read here they are three dependent memory round trips)
+struct StepFlags {
+    int draw, keep, klen;
+};
 __device__ __forceinline__ void forcing_post_body(int b, int lane, int (&s)[F_COUNT], int* seq, int ld_seq,
                                                   const int* __restrict__ chord_pos, int ld_chord, unsigned char* wrong,
                                                   const unsigned char* draw, const int* token, int* live, int* klen,
-                                                  const unsigned char* keep, int lmax, int token_val = -3) {
+                                                  const unsigned char* keep, int lmax, int token_val, TokenLogp lp,
+                                                  const float* logp, float* seq_logp, const StepFlags* flags = nullptr) {
     int clear = 0;
     if (lane == 0) {
         // memory length of the step that just ran: it grows unless the step's memory is discarded (quirk Q3)
-        if (klen != nullptr && keep[b] && klen[b] < lmax - 1) klen[b] += 1;
-        if (draw[b]) {
+        if (klen != nullptr) {
+            const int kp = flags != nullptr ? flags->keep : (int)keep[b];
+            if (kp) {
+                const int kl = flags != nullptr ? flags->klen : klen[b];
+                if (kl < lmax - 1) klen[b] = kl + 1;
+            }
+        }
+        if (flags != nullptr ? flags->draw : (int)draw[b]) {
             const int t = token_val >= -1 ? token_val : token[b];
             const int cur = s[F_CUR];
             const bool remnant = cur < s[F_NCHORD];
@@ -402,6 +486,12 @@ __device__ __forceinline__ void forcing_post_body(int b, int lane, int (&s)[F_CO
                 const int len = s[F_LEN];
                 if (len < ld_seq) {
                     seq[(size_t)b * ld_seq + len] = t;
+                    if (seq_logp != nullptr) {
+                        float* q = seq_logp + 2 * ((size_t)b * ld_seq + len);
+                        if (token_val >= -1) { q[0] = lp.full; q[1] = lp.kept; }
+                        else if (logp != nullptr) { q[0] = logp[2 * b]; q[1] = logp[2 * b + 1]; }
+                        else q[0] = q[1] = NAN;
+                    }
                     s[F_LEN] = len + 1;
                 }
                 if (t == TOK_BAR) s[F_NBAR] += 1;

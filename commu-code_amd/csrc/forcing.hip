@@ -23,22 +23,22 @@ __global__ __launch_bounds__(64) void forcing_pre_kernel(int* st, int* seq, int 
                                                          unsigned char* wrong, const float* __restrict__ utable, int ld_u,
                                                          int max_iters, long long* tok, unsigned char* active,
                                                          unsigned char* keep, unsigned char* draw, float* uni, int* trace,
-                                                         int ld_trace) {
+                                                         int ld_trace, float* seq_logp) {
     int rec[F_COUNT];
     if (threadIdx.x == 0) record_load(rec, st, blockIdx.x);
     forcing_pre_body(blockIdx.x, threadIdx.x, rec, seq, ld_seq, chord_tok, chord_pos, ld_chord, wrong, utable, ld_u, max_iters,
-                     tok, active, keep, draw, uni, trace, ld_trace);
+                     tok, active, keep, draw, uni, trace, ld_trace, seq_logp);
     if (threadIdx.x == 0) record_store(rec, st, blockIdx.x);
 }
 
 __global__ __launch_bounds__(64) void forcing_post_kernel(int* st, int* seq, int ld_seq, const int* __restrict__ chord_pos,
                                                           int ld_chord, unsigned char* wrong, const unsigned char* draw,
                                                           const int* token, int* live, int* klen, const unsigned char* keep,
-                                                          int lmax) {
+                                                          int lmax, const float* logp, float* seq_logp) {
     int rec[F_COUNT];
     if (threadIdx.x == 0) record_load(rec, st, blockIdx.x);
     forcing_post_body(blockIdx.x, threadIdx.x, rec, seq, ld_seq, chord_pos, ld_chord, wrong, draw, token, live, klen, keep,
-                      lmax);
+                      lmax, -3, TokenLogp{NAN, NAN}, logp, seq_logp);
     if (threadIdx.x == 0) record_store(rec, st, blockIdx.x);
 }
 
@@ -49,7 +49,9 @@ struct LoopStageArgs {
     float* logits; int ld, V;
     unsigned char* wrong;
     float temperature; int top_k; float top_p;
+    SamplingRows rows;              // per-sequence controls (null members: the scalars above)
     int* token; float* probs_out; int ldp;
+    float *logp, *seq_logp;         // (optional) the draw's log-probability pair [B][2]; the pairs of the tokens in seq
     int *st, *seq; int ld_seq;
     const int *chord_tok, *chord_pos; int ld_chord;
     const float* utable; int ld_u, max_iters;
@@ -64,17 +66,22 @@ __global__ __launch_bounds__(64) void sample_post_pre_kernel(LoopStageArgs a) {
     const int b = blockIdx.x, lane = threadIdx.x;
     if (a.trace != nullptr && lane == 0) a.trace[b * 4 + 0] = wall_clock64();
     int rec[F_COUNT];                                  // the record travels through the three stages in lane 0's registers;
-    if (lane == 0) record_load(rec, a.st, b);          // its loads are in flight under the sampling step
+    record_load(rec, a.st, b);                         // its loads are in flight under the sampling step (every lane loads the
+                                                       // same words: behind `if (lane == 0)` the wave waited for them here)
+    // what post reads of this iteration's decision, loaded here for the same reason (a null klen reads token[b] instead)
+    const StepFlags flags{a.draw[b], a.keep[b], *(a.klen != nullptr ? a.klen + b : a.token + b)};
+    TokenLogp lp{NAN, NAN};                            // like `drawn`, the pair reaches post in registers
     const int drawn = sample_topk_body(b, lane, a.logits, a.ld, a.V, a.wrong, VOCAB, a.uni, a.draw, a.temperature, a.top_k,
-                                       a.token, a.probs_out, a.ldp, a.top_p);
+                                       a.token, a.probs_out, a.ldp, a.top_p, a.rows,
+                                       a.logp != nullptr || a.seq_logp != nullptr, a.logp, lp);
     __syncthreads();
     if (a.trace != nullptr && lane == 0) a.trace[b * 4 + 1] = wall_clock64();
     forcing_post_body(b, lane, rec, a.seq, a.ld_seq, a.chord_pos, a.ld_chord, a.wrong, a.draw, a.token, nullptr, a.klen,
-                      a.keep, a.lmax, drawn >= -1 ? drawn : -3);
+                      a.keep, a.lmax, drawn >= -1 ? drawn : -3, lp, a.logp, a.seq_logp, &flags);
     __syncthreads();
     if (a.trace != nullptr && lane == 0) a.trace[b * 4 + 2] = wall_clock64();
     forcing_pre_body(b, lane, rec, a.seq, a.ld_seq, a.chord_tok, a.chord_pos, a.ld_chord, a.wrong, a.utable, a.ld_u,
-                     a.max_iters, a.tok, a.active, a.keep, a.draw, a.uni, a.step_trace, a.ld_trace);
+                     a.max_iters, a.tok, a.active, a.keep, a.draw, a.uni, a.step_trace, a.ld_trace, a.seq_logp);
     if (lane == 0) record_store(rec, a.st, b);
     if (a.trace != nullptr && lane == 0) a.trace[b * 4 + 3] = wall_clock64();
 }
@@ -92,14 +99,33 @@ __global__ void copy_rows_masked_kernel(float* __restrict__ dst, int ldd, const 
 
 extern "C" int commu_forcing_state_ints(void) { return F_COUNT; }
 
+extern "C" int commu_forcing_pre_rows(int* state, int* seq, int ld_seq, const int* chord_tok, const int* chord_pos,
+                                      int ld_chord, unsigned char* wrong, const float* utable, int ld_u, int max_iters,
+                                      long long* tok, unsigned char* active, unsigned char* keep, unsigned char* draw,
+                                      float* uni, int* trace, int ld_trace, float* seq_logp, int B, hipStream_t stream) {
+    if (B <= 0) return 0;
+    if (ld_seq < 2 || ld_chord < 1 || ld_u < 1) return -22;
+    COMMU_LAUNCH(forcing_pre_kernel, dim3(B), dim3(64), 0, stream, state, seq, ld_seq, chord_tok, chord_pos, ld_chord,
+                 wrong, utable, ld_u, max_iters, tok, active, keep, draw, uni, trace, ld_trace, seq_logp);
+    COMMU_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int commu_forcing_pre(int* state, int* seq, int ld_seq, const int* chord_tok, const int* chord_pos,
                                  int ld_chord, unsigned char* wrong, const float* utable, int ld_u, int max_iters,
                                  long long* tok, unsigned char* active, unsigned char* keep, unsigned char* draw,
                                  float* uni, int* trace, int ld_trace, int B, hipStream_t stream) {
+    return commu_forcing_pre_rows(state, seq, ld_seq, chord_tok, chord_pos, ld_chord, wrong, utable, ld_u, max_iters, tok,
+                                  active, keep, draw, uni, trace, ld_trace, nullptr, B, stream);
+}
+
+extern "C" int commu_forcing_post_rows(int* state, int* seq, int ld_seq, const int* chord_pos, int ld_chord,
+                                       unsigned char* wrong, const unsigned char* draw, const int* token, int* live,
+                                       int* klen, const unsigned char* keep, int lmax, const float* logp, float* seq_logp,
+                                       int B, hipStream_t stream) {
     if (B <= 0) return 0;
-    if (ld_seq < 2 || ld_chord < 1 || ld_u < 1) return -22;
-    COMMU_LAUNCH(forcing_pre_kernel, dim3(B), dim3(64), 0, stream, state, seq, ld_seq, chord_tok, chord_pos, ld_chord,
-                 wrong, utable, ld_u, max_iters, tok, active, keep, draw, uni, trace, ld_trace);
+    COMMU_LAUNCH(forcing_post_kernel, dim3(B), dim3(64), 0, stream, state, seq, ld_seq, chord_pos, ld_chord, wrong,
+                 draw, token, live, klen, keep, lmax, logp, seq_logp);
     COMMU_LAUNCH_CHECK();
     return 0;
 }
@@ -107,11 +133,8 @@ extern "C" int commu_forcing_pre(int* state, int* seq, int ld_seq, const int* ch
 extern "C" int commu_forcing_post(int* state, int* seq, int ld_seq, const int* chord_pos, int ld_chord,
                                   unsigned char* wrong, const unsigned char* draw, const int* token, int* live,
                                   int* klen, const unsigned char* keep, int lmax, int B, hipStream_t stream) {
-    if (B <= 0) return 0;
-    COMMU_LAUNCH(forcing_post_kernel, dim3(B), dim3(64), 0, stream, state, seq, ld_seq, chord_pos, ld_chord, wrong,
-                 draw, token, live, klen, keep, lmax);
-    COMMU_LAUNCH_CHECK();
-    return 0;
+    return commu_forcing_post_rows(state, seq, ld_seq, chord_pos, ld_chord, wrong, draw, token, live, klen, keep, lmax,
+                                   nullptr, nullptr, B, stream);
 }
 
 extern "C" int commu_copy_rows_masked_f32(float* dst, int ldd, const float* src, int lds_, const unsigned char* mask,
@@ -129,17 +152,34 @@ extern "C" int commu_decode_loop_trace(unsigned long long* buf) {
     return 0;
 }
 
+extern "C" int commu_decode_sample_post_pre_rows(float* logits, int ld, int V, unsigned char* wrong, float temperature,
+                                                 int top_k, float top_p, const float* temperature_rows,
+                                                 const int* top_k_rows, const float* top_p_rows, int* token,
+                                                 float* probs_out, int ldp, float* logp, float* seq_logp, int* state,
+                                                 int* seq, int ld_seq, const int* chord_tok, const int* chord_pos,
+                                                 int ld_chord, const float* utable, int ld_u, int max_iters, long long* tok,
+                                                 unsigned char* active, unsigned char* keep, unsigned char* draw, float* uni,
+                                                 int* trace, int ld_trace, int* klen, int lmax, int B, hipStream_t stream) {
+    if (B <= 0) return 0;
+    if (V != VOCAB || V > 64 * PER_LANE || ld_seq < 2 || ld_chord < 1 || ld_u < 1) return -22;
+    // (a scalar that an array replaces is not looked at; the kernel clamps what the arrays hold)
+    if ((top_k_rows == nullptr && (top_k < 1 || top_k > V)) || (top_p_rows == nullptr && !(top_p > 0.f))) return -22;
+    LoopStageArgs a{logits, ld, V, wrong, temperature, top_k, top_p, SamplingRows{temperature_rows, top_k_rows, top_p_rows},
+                    token, probs_out, ldp, logp, seq_logp, state, seq, ld_seq, chord_tok, chord_pos, ld_chord, utable, ld_u,
+                    max_iters, tok, active, keep, draw, uni, trace, ld_trace, klen, lmax, g_loop_trace};
+    COMMU_LAUNCH(sample_post_pre_kernel, dim3(B), dim3(64), 0, stream, a);
+    COMMU_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int commu_decode_sample_post_pre(float* logits, int ld, int V, unsigned char* wrong, float temperature, int top_k,
                                             float top_p, int* token, float* probs_out, int ldp, int* state, int* seq, int ld_seq,
                                             const int* chord_tok, const int* chord_pos, int ld_chord, const float* utable,
                                             int ld_u, int max_iters, long long* tok, unsigned char* active,
                                             unsigned char* keep, unsigned char* draw, float* uni, int* trace, int ld_trace,
                                             int* klen, int lmax, int B, hipStream_t stream) {
-    if (B <= 0) return 0;
-    if (V != VOCAB || V > 64 * PER_LANE || top_k < 1 || top_k > V || ld_seq < 2 || ld_chord < 1 || ld_u < 1 || !(top_p > 0.f)) return -22;
-    LoopStageArgs a{logits, ld, V, wrong, temperature, top_k, top_p, token, probs_out, ldp, state, seq, ld_seq, chord_tok, chord_pos,
-                    ld_chord, utable, ld_u, max_iters, tok, active, keep, draw, uni, trace, ld_trace, klen, lmax, g_loop_trace};
-    COMMU_LAUNCH(sample_post_pre_kernel, dim3(B), dim3(64), 0, stream, a);
-    COMMU_LAUNCH_CHECK();
-    return 0;
+    return commu_decode_sample_post_pre_rows(logits, ld, V, wrong, temperature, top_k, top_p, nullptr, nullptr, nullptr, token,
+                                             probs_out, ldp, nullptr, nullptr, state, seq, ld_seq, chord_tok, chord_pos,
+                                             ld_chord, utable, ld_u, max_iters, tok, active, keep, draw, uni, trace, ld_trace,
+                                             klen, lmax, B, stream);
 }

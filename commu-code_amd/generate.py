@@ -58,6 +58,10 @@ def parse_args():
     input_arg_parser.add_argument("--top_p", type=float, default=1.0)
     # not in the reference (which retries rejected sequences forever, midi_inferrer.py:342-353): bound the retries
     input_arg_parser.add_argument("--max_rounds", type=int, default=None)
+    # not in the reference (which returns token ids only): also write "logprobs" to sequences.json -- per sequence one
+    # [full, kept] pair per token (log-softmax of logits / temperature at the token; log of its probability after top-k /
+    # top-p and renormalisation), null for the tokens that were not drawn (context, forced bars / positions / chords)
+    input_arg_parser.add_argument("--logprobs", action="store_true")
     # not in the reference: replicas of the generator, one per GPU (default: every visible GPU, at most num_generate)
     input_arg_parser.add_argument("--gpus", type=int, default=None)
     return {"model_args": model_arg_parser, "input_args": input_arg_parser}
@@ -76,19 +80,21 @@ def main(model_args, input_args, training_cfg=None, device_indices=None):
     in_args = dict(vars(input_args))
     max_rounds = in_args.pop("max_rounds", None)
     gpus = in_args.pop("gpus", None)
+    want_lp = bool(in_args.pop("logprobs", False))
     if device_indices is None:
         n_vis = torch.cuda.device_count()
         device_indices = list(range(max(1, n_vis if gpus is None else min(gpus, n_vis))))
     shares = split_num_generate(in_args["num_generate"], len(device_indices))
     if len(shares) == 1:
-        encoded_meta, sequences = generate_on_device(model_args, in_args, device_indices[0], shares[0], 0, max_rounds,
-                                                     training_cfg)
+        encoded_meta, sequences, *lps = generate_on_device(model_args, in_args, device_indices[0], shares[0], 0, max_rounds,
+                                                           training_cfg, want_lp)
+        logprobs = lps[0] if want_lp else None
     else:
         import torch.multiprocessing as mp
         ctx = mp.get_context("spawn")          # (never fork / exec a process that has initialised the GPU)
         q = ctx.Queue()
         procs = [ctx.Process(target=replica_worker, args=(r, device_indices[r], model_args, in_args, share, max_rounds,
-                                                    training_cfg, q)) for r, share in enumerate(shares)]
+                                                    training_cfg, q, want_lp)) for r, share in enumerate(shares)]
         for p_ in procs:
             p_.start()
         # a replica that dies natively (GPU fault, OOM kill) never reports: poll the queue and the processes
@@ -113,9 +119,13 @@ def main(model_args, input_args, training_cfg=None, device_indices=None):
             raise RuntimeError("generation replica failed:\n" + bad[0])
         encoded_meta = results[0][0]
         sequences = [seq for r in range(len(shares)) for seq in results[r][1]]
+        logprobs = [lp for r in range(len(shares)) for lp in results[r][2]] if want_lp else None
     os.makedirs(input_args.output_dir, exist_ok=True)
     with open(os.path.join(input_args.output_dir, "sequences.json"), "w") as f:
-        json.dump({"encoded_meta": encoded_meta, "sequences": sequences}, f)
+        doc = {"encoded_meta": encoded_meta, "sequences": sequences}
+        if want_lp:
+            doc["logprobs"] = logprobs
+        json.dump(doc, f)
     return sequences
 
 

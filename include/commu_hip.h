@@ -418,6 +418,26 @@ int commu_sample_topk(float* logits, int ld, int nseq, int V, const unsigned cha
 int commu_sample_topk_topp(float* logits, int ld, int nseq, int V, const unsigned char* wrong, int ldw,
                            const float* uniforms, const unsigned char* active, float temperature, int top_k,
                            float top_p, int* token, float* probs_out, int ldp, hipStream_t stream);
+/* the same with PER-SEQUENCE controls and the log-probabilities of the drawn token (the reference samples one sequence
+ * at a time with the request's one temperature / top_k, midi_inferrer.py:209-237, generate.py:43-44; it reports no
+ * probabilities): temperature_rows / top_k_rows / top_p_rows, device arrays [nseq], each optional -- null: the scalar
+ * argument applies to every sequence.  Sequence b's result is bit for bit that of commu_sample_topk_topp with b's triple.
+ * top_k values are clamped to [1, V] in the kernel; validating the arrays is the caller's job.
+ * logp_out (optional, fp32 [nseq][2]), for the token just drawn:
+ *   [0] full: log-softmax over ids 1 .. V-1 of the row as this draw used it -- logits / temperature as written back (the
+ *       compounded row on a re-draw, Q5, like calc_probs), the raw row for temperature == 0 -- at the drawn id;
+ *   [1] kept: log of the token's probability in the distribution it was drawn from (after top-k, rejected tokens, top-p
+ *       and renormalisation: apply_sampling, :221-230); exactly 0 for temperature == 0.
+ *   Both NaN when nothing could be drawn (token -1, Q12); sequences with active[b] == 0 keep their entries.
+ * Required pointers (all sampling entry points, this one and the two above, which forward here): logits and token must be
+ * valid, readable device arrays -- token [nseq] always receives the result, and the kernel issues every optional load
+ * unconditionally: where `active` or a control array is null it reads token[b] or logits[b][0] instead and ignores the
+ * value, so that these loads share one memory round trip with the logits. */
+int commu_sample_topk_topp_rows(float* logits, int ld, int nseq, int V, const unsigned char* wrong, int ldw,
+                                const float* uniforms, const unsigned char* active, float temperature, int top_k,
+                                float top_p, const float* temperature_rows, const int* top_k_rows,
+                                const float* top_p_rows, int* token, float* probs_out, int ldp, float* logp_out,
+                                hipStream_t stream);
 
 /* ---- single-token decode step with a K/V cache (forward_generate with qlen 1, model.py:606-628, as
  * called by midi_inferrer.py:199-207).  Caches are bf16 [B][H][Lmax][DH] per layer; klen[b] = valid rows
@@ -508,11 +528,26 @@ int commu_forcing_pre(int* state, int* seq, int ld_seq, const int* chord_tok, co
                       unsigned char* wrong, const float* utable, int ld_u, int max_iters, long long* tok,
                       unsigned char* active, unsigned char* keep, unsigned char* draw, float* uni, int* trace,
                       int ld_trace, int B, hipStream_t stream);
+/* commu_forcing_pre that also keeps seq_logp (optional, fp32 [B][ld_seq][2], parallel to seq: the log-probability pair
+ * of every token, see commu_sample_topk_topp_rows): a FORCED token appended here (midi_inferrer.py:247-251) was not
+ * drawn and gets NaN, NaN */
+int commu_forcing_pre_rows(int* state, int* seq, int ld_seq, const int* chord_tok, const int* chord_pos, int ld_chord,
+                           unsigned char* wrong, const float* utable, int ld_u, int max_iters, long long* tok,
+                           unsigned char* active, unsigned char* keep, unsigned char* draw, float* uni, int* trace,
+                           int ld_trace, float* seq_logp, int B, hipStream_t stream);
 /* klen / keep (optional): the cache lengths of the decode step advance here (klen[b] += keep[b], capped at lmax - 1),
  * which saves the separate commu_decode_advance launch */
 int commu_forcing_post(int* state, int* seq, int ld_seq, const int* chord_pos, int ld_chord, unsigned char* wrong,
                        const unsigned char* draw, const int* token, int* live, int* klen, const unsigned char* keep,
                        int lmax, int B, hipStream_t stream);
+/* commu_forcing_post that also keeps seq_logp: where the drawn token is appended (midi_inferrer.py:313-317) its pair
+ * logp[b][0:2] (fp32 [B][2], what commu_sample_topk_topp_rows wrote beside token) is stored at the token's index; a draw
+ * that is not appended -- rejected chord, position past a pending chord, replaced EOS / bar (:294-311), Q12 -- leaves
+ * no entry.  logp / seq_logp null: commu_forcing_post. */
+int commu_forcing_post_rows(int* state, int* seq, int ld_seq, const int* chord_pos, int ld_chord, unsigned char* wrong,
+                            const unsigned char* draw, const int* token, int* live, int* klen,
+                            const unsigned char* keep, int lmax, const float* logp, float* seq_logp, int B,
+                            hipStream_t stream);
 /* The three per-sequence stages that follow the model step as ONE launch, in this order and with the meaning of the
  * separate entry points: commu_sample_topk_topp (active = draw, wrong [B][729]) -> commu_forcing_post (live = null) ->
  * commu_forcing_pre (the decision of the NEXT iteration). */
@@ -525,6 +560,20 @@ int commu_decode_sample_post_pre(float* logits, int ld, int V, unsigned char* wr
                                  int max_iters, long long* tok, unsigned char* active, unsigned char* keep,
                                  unsigned char* draw, float* uni, int* trace, int ld_trace, int* klen, int lmax, int B,
                                  hipStream_t stream);
+/* The same launch from the _rows stages: commu_sample_topk_topp_rows (per-sequence controls, each array optional; logp
+ * optional) -> commu_forcing_post_rows -> commu_forcing_pre_rows (seq_logp optional).  The pair reaches the book-keeping
+ * stage in registers; logp[b] is written as well when given.  With every added pointer null this is
+ * commu_decode_sample_post_pre (generate_sequence, midi_inferrer.py:239-320, one iteration).
+ * Required pointers, here and in commu_decode_sample_post_pre: token, state, draw and keep (read at the top of the launch,
+ * under the sampling stage, and handed to the book-keeping stage in registers; a null klen reads token[b] instead). */
+int commu_decode_sample_post_pre_rows(float* logits, int ld, int V, unsigned char* wrong, float temperature, int top_k,
+                                      float top_p, const float* temperature_rows, const int* top_k_rows,
+                                      const float* top_p_rows, int* token, float* probs_out, int ldp, float* logp,
+                                      float* seq_logp, int* state, int* seq, int ld_seq, const int* chord_tok,
+                                      const int* chord_pos, int ld_chord, const float* utable, int ld_u, int max_iters,
+                                      long long* tok, unsigned char* active, unsigned char* keep, unsigned char* draw,
+                                      float* uni, int* trace, int ld_trace, int* klen, int lmax, int B,
+                                      hipStream_t stream);
 /* dst[b][0:n] = src[b][0:n] where mask[b] != 0 */
 int commu_copy_rows_masked_f32(float* dst, int ldd, const float* src, int lds, const unsigned char* mask, int rows,
                                int n, hipStream_t stream);
