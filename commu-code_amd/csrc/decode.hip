@@ -198,7 +198,9 @@ __global__ __launch_bounds__(256) void decode_attn_kernel(
         }
 #pragma unroll
         for (int u = 0; u < UNR; ++u) {
-            const bf16x8 vx = (j0 + 4 * RPW * u + rowl == self) ? vnew : vd[u];
+            // (the CLAMPED row: a tail lane past n re-reads row n - 1 with p = 0; where that is the new token's row, whose
+            //  store may not have landed -- another workgroup's, with a split -- 0 x stale bits must not reach acc)
+            const bf16x8 vx = (min(j0 + 4 * RPW * u + rowl, n - 1) == self) ? vnew : vd[u];
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc[e] += p[u] * bf2f(vx[e]);
         }

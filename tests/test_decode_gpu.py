@@ -437,7 +437,9 @@ def test_split_key_decode_attention_matches_the_unsplit_kernel(loaded):
     partial (max, sum, P.V) records inside the launch) against commu_decode_attn on the same caches: ragged memories from 3
     to 4100 keys (pairs with <= 512 keys take the unsplit path inside the split launch), inactive sequences, repeated
     launches (the counters must come back to zero), and -- `loaded` -- a second stream keeping the GPU busy so that the
-    workgroups of a pair start unevenly (a stale or missing record would be an O(1) error)."""
+    workgroups of a pair start unevenly (a stale or missing record would be an O(1) error).  Both kernels are also held,
+    element by element, to the float64 contract: |got - want| <= 2^-8 |want| + c A (tests/decode_contract.py)."""
+    import decode_contract as DC
     from commu_amd._lib import call
     from commu_amd.ops import _p, _s
     B, H, DH, Lmax = 12, 8, 64, 4200
@@ -455,6 +457,14 @@ def test_split_key_decode_attention_matches_the_unsplit_kernel(loaded):
     ref = torch.zeros(B, H * DH, device=DEV, dtype=torch.bfloat16)
     call("commu_decode_attn", _p(qkv), qkv.stride(0), _p(kc), _p(vc), _p(rd), rd.stride(0), _p(u), _p(vb), _p(klen),
          _p(active), _p(ref), ref.stride(0), B, H, DH, Lmax, 0.125, 0, _s())
+    live = [b for b in range(B) if b != 10]
+    want, A = DC.contract_batch(qkv[:, :H * DH].view(B, H, DH), kc, vc, rd.view(Lmax, H, DH), u.view(H, DH), vb.view(H, DH),
+                                [(list(range(n + 1)), list(range(n, -1, -1))) if b != 10 else None
+                                 for b, n in enumerate(klen.tolist())], 0.125)
+    want, A = want.view(B, H * DH)[live], A.view(B, H * DH)[live]
+    r_ref = float(DC.ratio(ref.cpu()[live], want, A).nan_to_num(nan=float("inf")).max())
+    print(f"unsplit kernel vs float64 contract: {r_ref:.3f} of the per-element bound")
+    assert r_ref <= 1.0, ("unsplit kernel vs float64 contract", r_ref)
     side = torch.cuda.Stream()
     a_ = torch.randn(4096, 4096, device=DEV)
     for nsplit in (8, 3, 16):
@@ -471,6 +481,10 @@ def test_split_key_decode_attention_matches_the_unsplit_kernel(loaded):
             assert int(cnt.abs().sum()) == 0, (nsplit, rep)
             d = (out.float() - ref.float()).abs().max()
             assert float(d) < 2e-2 * float(ref.float().abs().max()), (nsplit, rep, float(d))
+            r = float(DC.ratio(out.cpu()[live], want, A).nan_to_num(nan=float("inf")).max())
+            if rep == 0:
+                print(f"split kernel nsplit {nsplit} vs float64 contract: {r:.3f} of the per-element bound")
+            assert r <= 1.0, (nsplit, rep, "split kernel vs float64 contract", r)
             assert float(out[10].float().abs().max()) == 0          # the inactive sequence is not touched
 
 

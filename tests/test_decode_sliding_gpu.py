@@ -16,6 +16,8 @@ pytestmark = pytest.mark.gpu
 
 from oracle import decode_ref as Dz  # noqa: E402
 from oracle import xl_ref as X  # noqa: E402
+import decode_contract as DC  # noqa: E402
+from decode_contract import visible as _visible  # noqa: E402
 
 DEV = "cuda"
 
@@ -25,29 +27,11 @@ def load(golden_dir, name):
 
 
 # ------------------------------------------------------------------------------------------------ 1. kernels
-def _visible(pos, M, same_length):
-    lo = max(0, pos - M)
-    if same_length and pos >= M:
-        lo += 1
-    return list(range(lo, pos + 1))
-
-
 def _contract_f64(q, kc, vc, rd, u, vb, pos_list, M, same_length, scale, head_major):
-    """float64 evaluation of the contract on the ring caches (the new token's K/V already in row pos mod W).
-    q [B, H, DH]; kc / vc [B, H, W, DH] (head_major) or [B, W, H, DH]; rd [>= W, H, DH]; returns [B, H, DH]."""
-    W = M + 1
-    B, H, DH = q.shape
-    out = torch.zeros(B, H, DH, dtype=torch.float64)
-    q, kc, vc, rd, u, vb = (t.double().cpu() for t in (q, kc, vc, rd, u, vb))
-    for b, pos in enumerate(pos_list):
-        ps = torch.tensor(_visible(pos, M, same_length))
-        rows, dist = ps % W, pos - ps
-        for h in range(H):
-            k = kc[b, h, rows] if head_major else kc[b, rows, h]
-            v = vc[b, h, rows] if head_major else vc[b, rows, h]
-            s = ((q[b, h] + u[h]) @ k.T + (q[b, h] + vb[h]) @ rd[dist, h].T) * scale
-            out[b, h] = torch.softmax(s, -1) @ v
-    return out
+    """float64 evaluation of the contract on the ring caches (the new token's K/V already in row pos mod W):
+    decode_contract.contract_f64 over the batch.  q [B, H, DH]; kc / vc [B, H, W, DH] (head_major) or [B, W, H, DH];
+    rd [>= W, H, DH]; returns (want, A) [B, H, DH]: the output and the magnitude its accumulation error scales with."""
+    return DC.contract_batch(q, kc, vc, rd, u, vb, DC.ring_rows_dist(pos_list, M, same_length), scale, head_major)
 
 
 def _positions(M):
@@ -64,8 +48,8 @@ def test_ring_attention_kernel_bf16_vs_linear_kernel(DH, M, same_length):
     linear kernel commu_decode_attn on a DE-ROTATED copy of the same cache: rows back in chronological order, the hidden
     oldest row dropped, klen set accordingly -- the same mathematics in a different summation order with one bf16 output
     rounding, which is what test_split_key_decode_attention_matches_the_unsplit_kernel bounds at 2e-2 of the output's
-    max.  With append the new K/V must land in row pos mod W and nowhere else.  Both kernels' error against a float64
-    evaluation of the contract is printed for the record."""
+    max.  With append the new K/V must land in row pos mod W and nowhere else.  Both kernels are also held, element by
+    element, to the float64 contract: |got - want| <= 2^-8 |want| + c A (tests/decode_contract.py)."""
     from commu_amd import ops
     from commu_amd._lib import call
     from commu_amd.ops import _p, _s
@@ -103,11 +87,13 @@ def test_ring_attention_kernel_bf16_vs_linear_kernel(DH, M, same_length):
     lin = torch.zeros(B, HD, device=DEV, dtype=torch.bfloat16)
     call("commu_decode_attn", _p(qkv), qkv.stride(0), _p(kl), _p(vl), _p(rd), rd.stride(0), _p(u), _p(vb), _p(klen_lin),
          _p(active), _p(lin), lin.stride(0), B, H, DH, W, scale, 0, _s())
-    want = _contract_f64(qkv[:, :HD].view(B, H, DH), kc1, vc1, rd.view(W, H, DH), u.view(H, DH), vb.view(H, DH), pos_list, M,
-                         same_length, scale, True).view(B, HD)
+    want, A = (t.view(B, HD) for t in _contract_f64(qkv[:, :HD].view(B, H, DH), kc1, vc1, rd.view(W, H, DH), u.view(H, DH),
+                                                    vb.view(H, DH), pos_list, M, same_length, scale, True))
     want[B - 1] = 0
     top = float(lin.float().abs().max())
     err_lin = float((lin.double().cpu() - want).abs().max()) / top
+    r_lin = float(DC.ratio(lin.cpu()[:B - 1], want[:B - 1], A[:B - 1]).nan_to_num(nan=float("inf")).max())
+    assert r_lin <= 1.0, ("linear kernel vs float64 contract", r_lin)
     ws = torch.full((B * H * 16 * (DH + 2),), float("nan"), device=DEV, dtype=torch.float32)
     cnt = torch.zeros(B * H, device=DEV, dtype=torch.int32)
     for nsplit in ((1, 4) if W >= 2048 else (1,)):
@@ -122,9 +108,12 @@ def test_ring_attention_kernel_bf16_vs_linear_kernel(DH, M, same_length):
                 assert torch.equal(kc, kc1) and torch.equal(vc, vc1), (nsplit, append, "cache rows")
                 d = float((out.float() - lin.float()).abs().max())
                 err = float((out.double().cpu() - want).abs().max()) / top
+                r = float(DC.ratio(out.cpu()[:B - 1], want[:B - 1], A[:B - 1]).nan_to_num(nan=float("inf")).max())
                 if rep == 0:
                     print(f"ring decode attention DH {DH} W {W} same_length {same_length} nsplit {nsplit} append {append}: "
-                          f"vs linear kernel {d / top:.2e} of max; vs float64 contract: ring {err:.2e}, linear {err_lin:.2e}")
+                          f"vs linear kernel {d / top:.2e} of max; vs float64 contract: ring {err:.2e}, linear {err_lin:.2e} "
+                          f"of max; of the per-element bound: ring {r:.3f}, linear {r_lin:.3f}")
+                assert r <= 1.0, (nsplit, append, rep, "ring kernel vs float64 contract", r)
                 assert d < 2e-2 * top, (nsplit, append, rep, d, top)
                 assert float(out[B - 1].float().abs().max()) == 0          # the inactive sequence is not touched
 
@@ -159,7 +148,7 @@ def test_ring_attention_kernel_f32_vs_float64(DH, M, same_length):
     out = ops.decode_attn_ring_f32(qkv[:, :HD], kc, vc, rd, u, vb, klen, H, DH, W, same_length, scale)
     assert torch.equal(kc, kc1) and torch.equal(vc, vc1)
     want = _contract_f64(qkv[:, :HD].view(B, H, DH), kc1.view(B, W, H, DH), vc1.view(B, W, H, DH), rd.view(W, H, DH),
-                         u.view(H, DH), vb.view(H, DH), pos_list, M, same_length, scale, False).view(B, HD)
+                         u.view(H, DH), vb.view(H, DH), pos_list, M, same_length, scale, False)[0].view(B, HD)
     err = float((out.double().cpu() - want).abs().max()) / float(want.abs().max())
     print(f"fp32 ring decode attention DH {DH} W {W} same_length {same_length}: {err:.2e} of range")
     assert err <= 2e-6
