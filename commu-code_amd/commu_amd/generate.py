@@ -124,7 +124,8 @@ class DecodeState:
         self.vec = torch.zeros(B, HD, device=dev, dtype=BF16)
         # layer-tail launches: hand-off buffers per layer, arrival counters per launch, give-up flag
         DI = model._DIp
-        self.tail_ok = bool(call("commu_decode_tail_supported", B, D, DI, HD)) and L > 0
+        # (the logits launch takes 512 < V <= 1024 only: other vocabularies use the per-Linear launches)
+        self.tail_ok = bool(call("commu_decode_tail_supported", B, D, DI, HD)) and L > 0 and 512 < model.n_token <= 1024
         if self.tail_ok:
             nw = call("commu_decode_tail_sync_words")
             self.t_z1 = torch.zeros(L, B, D, device=dev, dtype=BF16)

@@ -654,7 +654,9 @@ extern "C" int commu_decode_layer_tail(const void* vec, int ld_vec, const void* 
     if (d_ln < 4 || d_ln > D || (d_ln % 4) || (ld_vec % 8) || (ld_h % 4) || (ld_ho % 8) || (ld_on % 4) || sync == nullptr ||
         err == nullptr)
         return -22;
-    if (logits ? (Nn < 1 || Nn > 1024 || bn == nullptr) : (Nn != 3 * HD)) return -22;
+    // (the LOGITS kernels walk 2 column tiles per workgroup, and commu_decode_tail_pack lays out ceil(ceil(Nn / 16) / 32) of
+    //  them: for Nn <= 512 that is 1, and workgroups ng >= 16 would read past the packed copy)
+    if (logits ? (Nn <= 512 || Nn > 1024 || bn == nullptr) : (Nn != 3 * HD)) return -22;
     TailArgs a = tail_args_zero();
     a.vec = (const bf16*)vec; a.ld_vec = ld_vec;
     a.h = (const bf16*)h; a.ld_h = ld_h;

@@ -482,7 +482,8 @@ int commu_decode_attn_ring(const void* qkv, int ld_qkv, void* kcache, void* vcac
  *   (o_net + residual + LayerNorm model.py:344-352, PositionwiseFF model.py:163-179)
  * and then out_n = h_out . Wn^T: the NEXT layer's qkv_net (logits == 0: Nn = 3 HD, bf16, model.py:297-299) or the
  * tied-embedding logits (logits != 0: + bn, fp32, columns < Nn, model.py:64-73; rows with active[row] == 0 are not
- * written -- active may be null).  vec [B][HD], h / h_out [B][D] bf16;
+ * written -- active may be null).  The logits launch takes 512 < Nn <= 1024 only (others: -22): its kernels walk two
+ * column tiles per workgroup, and the packed copy of a weight with Nn <= 512 rows has one.  vec [B][HD], h / h_out [B][D] bf16;
  * z1 / z2 [B][D] and hid [B][DI] are dense bf16 hand-off buffers that belong to THIS layer; sync:
  * commu_decode_tail_sync_words() arrival counters that must be ZERO on entry (one set per launch of a step); *err
  * becomes non-zero when a workgroup gave up waiting (the results of that launch are then invalid).
