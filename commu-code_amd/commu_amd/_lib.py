@@ -157,6 +157,10 @@ PROTOTYPES = {
     "commu_decode_sample_post_pre_rows": [c_p, c_i, c_i, c_p, c_f, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p,
                                           c_i, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i,
                                           c_p],
+    "commu_forcing_replay": [c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p,
+                             c_p, c_p, c_i, c_p, c_i, c_p],
+    "commu_decode_prefill_scatter": [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p],
+    "commu_decode_prefill_scatter_f32": [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
     "commu_copy_rows_masked_f32": [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_p],
     "commu_pack_batch": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, C.c_longlong, c_p, c_p],
     "commu_gemm_nt_f32": [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p],

@@ -240,6 +240,48 @@ class DecodeState:
             self.vc[i, :, :, :T0].copy_(kv[:, :, 2].permute(1, 2, 0, 3))
         self.klen.fill_(T0)
 
+    def prefill_ragged(self, ctx: torch.Tensor, lens, slots=None):
+        """prefill() for contexts of different lengths: ctx int64 [Tmax, Bc] holds context b in ctx[:lens[b], b] (what
+        stands beyond is padding: the memory-less forward is causal, no valid row depends on it), lens int32 [Bc] (device
+        tensor or a sequence), slots (optional, int32 [Bc]) names the decode slot of each context (default: b).  One
+        forward over the padded batch, then ONE launch per layer (commu_decode_prefill_scatter) that moves the K/V of the
+        valid positions -- window mode: the last min(lens[b], window) of them, to their ring rows -- and sets
+        klen[slot] = lens[b].  Rows of other slots and rows beyond a context are not touched."""
+        m = self.model
+        Tmax, Bc = ctx.shape
+        dev = self.klen.device
+        if Tmax < 1 or Bc < 1:
+            raise CommuHipError(f"ctx: at least one position and one context expected, got shape {tuple(ctx.shape)}")
+
+        def rows(x, name):
+            if x is None:
+                return None, None
+            host = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(list(x))
+            if host.shape != (Bc,):
+                raise CommuHipError(f"{name}: {Bc} values expected (one per context), got shape {host.shape}")
+            t = x if isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.int32 and x.is_contiguous() \
+                else torch.from_numpy(host.astype(np.int32)).to(dev)
+            return t, host
+        lens_t, lens_h = rows(lens, "lens")
+        slots_t, slots_h = rows(slots, "slots")
+        if lens_t is None:
+            raise CommuHipError("lens: the length of every context is needed")
+        if lens_h.min() < 0 or lens_h.max() > Tmax:
+            raise CommuHipError(f"lens: values in [0, {Tmax}] expected, got {int(lens_h.min())} .. {int(lens_h.max())}")
+        if slots_h is None and Bc != self.B:
+            raise CommuHipError(f"{Bc} contexts for {self.B} slots: name the slots")
+        if slots_h is not None and (slots_h.min() < 0 or slots_h.max() >= self.B or len(set(slots_h.tolist())) != Bc):
+            raise CommuHipError(f"slots: {Bc} different slot numbers in [0, {self.B}) expected, got {slots_h.tolist()}")
+        if self.window is None and int(lens_h.max()) >= self.Lmax:
+            raise CommuHipError(f"context of {int(lens_h.max())} tokens does not fit a decode cache of {self.Lmax} positions")
+        if self.parity:
+            _, _, qkvs = m._run_forward_f32(ctx, None, want_kv=True)
+        else:
+            _, _, qkvs = m._run_forward(ctx, None, None, None, need_grad=False, want_logits=True, want_kv=True)
+        for i, qkv in enumerate(qkvs):
+            ops.decode_prefill_scatter(qkv.view(Tmax * Bc, -1), Tmax, self.kc[i], self.vc[i], self.klen, lens_t, slots_t,
+                                       window=self.window or 0)
+
     def _attn(self, i, u, vb, active, B, H, DH, scale):
         """Cached attention of layer i (K/V append fused in).  attn_splits > 1: the keys of a (sequence, head) pair over
         several workgroups (long memories, few live sequences); pairs with fewer than 512 keys run unsplit either way.
@@ -391,10 +433,17 @@ class ForcedDecoder:
     POLL = 16          # iterations between two looks at the `done` flags (one D2H of B ints)
 
     def __init__(self, model, B: int, generation_length: int, memory_length: int, temperature: float, top_k: int,
-                 max_chords: int = 64, record_trace: bool = False, top_p: float = 1.0, sliding: bool = False):
+                 max_chords: int = 64, record_trace: bool = False, top_p: float = 1.0, sliding: bool = False,
+                 max_prompt: int = 0):
         """sliding: the reference's sliding memory window (DecodeState window mode) -- generation_length is then bounded by
-        the token buffers only, not by memory_length."""
+        the token buffers only, not by memory_length.
+        max_prompt: the longest token prefix load(prompts=) may prime a slot with (0: the loop starts from the conditioning
+        context only; no buffer changes size and no launch is added).  generation_length counts the iterations AFTER the
+        prompt."""
         self.model, self.B = model, B
+        self.max_prompt = int(max_prompt)
+        if self.max_prompt < 0:
+            raise CommuHipError(f"max_prompt: a length >= 0 expected, got {max_prompt}")
         self.sliding = bool(sliding)
         self.generation_length, self.temperature, self.top_k = int(generation_length), float(temperature), int(top_k)
         self.top_p = float(top_p)          # nucleus filter after top-k (extra mode; 1.0 = the reference's behaviour)
@@ -421,7 +470,7 @@ class ForcedDecoder:
                     "unless it is asked to (sliding=True, --sliding_memory)")
             self.state = DecodeState(model, B, lmax)
         self._ctx_kv = None          # sliding: the context rows of every slot's K/V cache as load() left them (rearm)
-        self.ld_seq = self.n_ctx_max + self.generation_length + 2
+        self.ld_seq = self.n_ctx_max + self.generation_length + 2 + self.max_prompt
         self.ld_chord = max_chords
         self.ld_u = self.generation_length + 1
         i32, u8 = torch.int32, torch.uint8
@@ -454,11 +503,22 @@ class ForcedDecoder:
         self.seq_logp = torch.full((B, self.ld_seq, 2), float("nan"), dtype=F32, device=dev)
         self.logp = torch.full((B, 2), float("nan"), dtype=F32, device=dev)
         self.probs = None
-        self.ld_trace = 2 * (self.generation_length + 2) if record_trace else 0
+        # (the replay of a prompt token takes at most two iterations: the decision to force it, then its append)
+        self.ld_trace = 2 * (self.generation_length + 2 + 2 * self.max_prompt) if record_trace else 0
         self.trace = torch.zeros(B, self.ld_trace, dtype=i32, device=dev) if record_trace else None
         self.graph = None
         self.graph_long = None
         self.n_cond = 0
+        # primed generation (load(prompts=)): the prompts, what the replay would have fed the model (kept steps only) and
+        # where a prompt leaves the rules; the primed records / lengths / trace as load() left them (rearm)
+        self.ld_fed = self.n_ctx_max + 2 * self.max_prompt
+        self.klen0 = 0               # the longest memory any slot starts with
+        self._primed = None
+        if self.max_prompt > 0:
+            self.prompt = torch.zeros(B, self.max_prompt, dtype=i32, device=dev)
+            self.prompt_len = torch.zeros(B, dtype=i32, device=dev)
+            self.fed = torch.zeros(B, self.ld_fed, dtype=i32, device=dev)
+            self.diverged = torch.full((B, 2), -1, dtype=i32, device=dev)
 
     # ---- one loop iteration = decide (pre) -> model step -> sampling step -> book-keeping (post), as kernel launches
     # on the current stream.  The captured graph holds [step, {sample, post, pre of the NEXT iteration} as one launch]
@@ -596,31 +656,111 @@ class ForcedDecoder:
             self.graph = g
         return g
 
-    def load(self, encoded_metas: Sequence[Sequence[int]], input_datas, uniforms: Optional[np.ndarray] = None):
+    REPLAY_REASONS = {1: "the forcing rules put another token there",
+                      2: "the rules would not have appended it (a chord token where a draw is expected, a position past a "
+                         "pending chord, or an EOS / BAR that the rules replace)",
+                      3: "EOS ends a sequence: nothing can follow it",
+                      4: "the slot's record was finished before the prompt was"}
+
+    def _check_prompts(self, prompts):
+        """prompts as B lists of ints, validated on the host (None: no prompts)."""
+        if prompts is None:
+            return None
+        if len(prompts) != self.B:
+            raise CommuHipError(f"prompts: one token list per slot expected ({self.B}), got {len(prompts)}")
+        out = []
+        V = TOKEN_OFFSET.VOCAB_SIZE
+        for b, p in enumerate(prompts):
+            p = [] if p is None else [int(t) for t in p]
+            if len(p) > self.max_prompt:
+                raise CommuHipError(f"prompt of slot {b} has {len(p)} tokens; this decoder was built with max_prompt="
+                                    f"{self.max_prompt}")
+            bad = next((i for i, t in enumerate(p) if t < 0 or t >= V), None)
+            if bad is not None:
+                raise CommuHipError(f"prompt of slot {b}: token {p[bad]} at index {bad} is outside [0, {V})")
+            out.append(p)
+        return out
+
+    def _prime(self, ctx, prompts):
+        """Second half of load(prompts=): replay the prompts through the device state machine (commu_forcing_replay, no
+        model step), download records / lengths / divergences once, then fill the caches with the K/V of
+        [0] + meta[:n-1] + the kept tokens of the replayed stream in one ragged forward.
+        What the replay cannot reconstruct: draws the loop rejected leave no mark in a sequence (a sampled continuation
+        consumes its variates from the start of the table), and where the loop replaced a draw by a forced mid-bar chord
+        position it fed that position twice -- the replay feeds it once, so the cache is one row shorter there."""
+        B, n_cond, st = self.B, self.n_cond, self.state
+        pr = np.zeros((B, self.max_prompt), dtype=np.int32)
+        for b, p in enumerate(prompts):
+            pr[b, :len(p)] = p
+        self.prompt.copy_(torch.from_numpy(pr))
+        self.prompt_len.copy_(torch.tensor([len(p) for p in prompts], dtype=torch.int32))
+        self.fed.zero_()
+        st.klen.fill_(n_cond)
+        call("commu_forcing_replay", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.prompt), self.max_prompt,
+             _p(self.prompt_len), _p(self.chord_tok), _p(self.chord_pos), self.ld_chord, _p(self.wrong), _p(self.utable),
+             self.ld_u, _p(self.tok), _p(self.active), _p(self.keep), _p(self.draw), _p(self.uni), _p(self.trace),
+             self.ld_trace, _p(self.seq_logp), _p(st.klen), _p(self.fed), self.ld_fed, _p(self.diverged), B, _s())
+        got = torch.cat([self.fsm, st.klen[:, None], self.diverged], 1).cpu().numpy()          # the one download
+        klen, div = got[:, self.NF], got[:, self.NF + 1:]
+        for b in range(B):
+            if div[b, 0] >= 0:
+                i, why = int(div[b, 0]), int(div[b, 1])
+                raise CommuHipError(f"prompt of slot {b} cannot be continued: token {prompts[b][i]} at index {i} of "
+                                    f"{len(prompts[b])}: {self.REPLAY_REASONS.get(why, why)} (reason {why})")
+        klen0 = int(klen.max())
+        if klen0 - n_cond > self.ld_fed:
+            raise CommuHipError(f"the replayed stream of {klen0 - n_cond} kept tokens exceeds the buffer of {self.ld_fed}")
+        if not self.sliding and klen0 + self.generation_length + 1 > st.Lmax:
+            b = int(klen.argmax())
+            raise CommuHipError(
+                f"slot {b} starts with {klen0} cached positions (context {n_cond} + {klen0 - n_cond} replayed model steps); "
+                f"with generation_length {self.generation_length} that needs {klen0 + self.generation_length + 1} "
+                f"positions and the decode memory has {st.Lmax} (shorten the prompt or generation_length, or use "
+                "sliding=True)")
+        full = torch.zeros(klen0, B, dtype=torch.long, device=self.dev)
+        full[:n_cond] = ctx.to(self.dev)
+        if klen0 > n_cond:
+            full[n_cond:] = self.fed[:, :klen0 - n_cond].t()
+        st.prefill_ragged(full, klen.astype(np.int32))
+        self.klen0 = klen0
+        self._primed = (self.fsm.clone(), st.klen.clone(), None if self.trace is None else self.trace.clone())
+
+    def _keep_ring_rows(self, n):
+        """Sliding: once a slot's ring has wrapped its first rows are gone: keep physical rows 0 .. n - 1 for rearm()."""
+        n = min(int(n), self.state.Lmax)
+        self._ctx_rows = n
+        if self.state.parity:
+            self._ctx_kv = (self.state.kc[:, :, :n].clone(), self.state.vc[:, :, :n].clone())
+        else:
+            self._ctx_kv = (self.state.kc[:, :, :, :n].clone(), self.state.vc[:, :, :, :n].clone())
+
+    def load(self, encoded_metas: Sequence[Sequence[int]], input_datas, uniforms: Optional[np.ndarray] = None,
+             prompts: Optional[Sequence[Sequence[int]]] = None):
         """Conditioning of all B sequences: context [0] + meta[:n-1] into the caches (the n-th meta token is fed by
-        the first loop iteration, its memory discarded: quirk Q3), chord progressions, variates."""
+        the first loop iteration, its memory discarded: quirk Q3), chord progressions, variates.
+        prompts (needs max_prompt > 0): one token list per slot (lengths may differ, lists may be empty), the tokens that
+        FOLLOW the conditioning tokens.  A primed slot starts in the state the free-running loop would be in after
+        producing its prompt itself (_prime); a prompt the rules could not have produced raises CommuHipError."""
         B = self.B
         assert len(encoded_metas) == B and len(input_datas) == B
+        prompts = self._check_prompts(prompts)
         n_cond = len(encoded_metas[0])
         if n_cond + 1 > self.n_ctx_max or any(len(m) != n_cond for m in encoded_metas):
             raise CommuHipError("encoded_meta: every sequence needs the same number (<= 15) of conditioning tokens")
         self.n_cond = n_cond
-        self._last_load = (encoded_metas, input_datas, uniforms)
+        self._last_load = (encoded_metas, input_datas, uniforms, prompts)
+        self._primed, self.klen0 = None, n_cond
         if getattr(self.state, "t_err", None) is not None:
             self.state.t_err.zero_()          # (a hand-off timeout of an earlier request must not fail this one)
         ctx = torch.tensor([[0] + list(m[:n_cond - 1]) for m in encoded_metas], dtype=torch.long).t().contiguous()
         self.state.kc.zero_()
         self.state.vc.zero_()
         self.state.repack()          # (the model may have been trained since the decoder was built)
-        self.state.prefill(ctx.to(self.dev))
-        if self.sliding:
-            # once a slot's ring has wrapped its context rows are gone: keep them for rearm() (rows = positions here, the
-            # context is shorter than the ring)
-            n = n_cond
-            if self.state.parity:
-                self._ctx_kv = (self.state.kc[:, :, :n].clone(), self.state.vc[:, :, :n].clone())
-            else:
-                self._ctx_kv = (self.state.kc[:, :, :, :n].clone(), self.state.vc[:, :, :, :n].clone())
+        if prompts is None:
+            self.state.prefill(ctx.to(self.dev))
+            if self.sliding:
+                # keep the context rows for rearm() (rows = positions here, the context is shorter than the ring)
+                self._keep_ring_rows(n_cond)
         fsm = np.zeros((B, self.NF), dtype=np.int32)
         seq = np.zeros((B, self.ld_seq), dtype=np.int32)
         ctok = np.zeros((B, self.ld_chord), dtype=np.int32)
@@ -655,6 +795,10 @@ class ForcedDecoder:
             n = min(uniforms.shape[1], self.ld_u)
             u[:, :n] = uniforms[:, :n]
             self.utable.copy_(torch.from_numpy(u))
+        if prompts is not None:
+            self._prime(ctx, prompts)
+            if self.sliding:
+                self._keep_ring_rows(self.klen0)
 
     # ---- slots: a finished sequence's slot can be re-armed for another attempt of the SAME request (same conditioning
     # tokens and chords) without touching the other slots: the context rows of its K/V cache are what they were, so only
@@ -663,6 +807,8 @@ class ForcedDecoder:
     # Sliding memory: the slot's ring may have wrapped over its context rows, so they are restored from the copy load()
     # took -- device-side copies on the decode stream, ordered between two graph replays, no synchronisation (the small
     # host-to-device copies of the state record and the variates are the ones a re-arm always made).
+    # Primed slots (load(prompts=)) return to their PRIMED state: record, klen and trace from the device copies load() took;
+    # sliding: the physical rows 0 .. min(longest primed memory, ring rows) - 1.
     # sampling: a (temperature, top_k, top_p) triple for the slot's next attempt (None: the slot keeps its controls).
     def rearm(self, b: int, uniforms_row: Optional[np.ndarray] = None, sampling=None):
         if sampling is not None:
@@ -670,13 +816,16 @@ class ForcedDecoder:
         rep0 = self.reports[b]
         rep = ForcingReport(rep0.n_chords, rep0.num_measures)
         self.reports[b] = rep
-        rec = [1 + self.n_cond, -1, 0, 1, int(rep.num_measures % 4 == 0), 0, 0, 0, 0, rep.n_chords, 0,
-               int(rep.length_fit), 0, 0]
-        self.fsm[b].copy_(torch.tensor(rec, dtype=torch.int32))
+        if self._primed is not None:          # back to the primed state: the record as the replay left it (device copy)
+            self.fsm[b].copy_(self._primed[0][b])
+        else:
+            rec = [1 + self.n_cond, -1, 0, 1, int(rep.num_measures % 4 == 0), 0, 0, 0, 0, rep.n_chords, 0,
+                   int(rep.length_fit), 0, 0]
+            self.fsm[b].copy_(torch.tensor(rec, dtype=torch.int32))
         self.wrong[b].zero_()
         self.seq_logp[b].fill_(float("nan"))
         if self.sliding:
-            st, n = self.state, self.n_cond
+            st, n = self.state, self._ctx_rows
             ck, cv = self._ctx_kv
             if st.parity:
                 st.kc[:, b, :n].copy_(ck[:, b])
@@ -684,14 +833,20 @@ class ForcedDecoder:
             else:
                 st.kc[:, b, :, :n].copy_(ck[:, b])
                 st.vc[:, b, :, :n].copy_(cv[:, b])
-        self.state.klen[b] = self.n_cond
+        if self._primed is not None:
+            self.state.klen[b].copy_(self._primed[1][b])
+        else:
+            self.state.klen[b] = self.n_cond
         if uniforms_row is not None:
             u = np.full(self.ld_u, 0.5, dtype=np.float32)
             n = min(len(uniforms_row), self.ld_u)
             u[:n] = uniforms_row[:n]
             self.utable[b].copy_(torch.from_numpy(u))
         if self.trace is not None:
-            self.trace[b].zero_()
+            if self._primed is not None:      # (the recorded trace covers the replayed stream too)
+                self.trace[b].copy_(self._primed[2][b])
+            else:
+                self.trace[b].zero_()
 
     def harvest(self, b: int, fsm_row):
         """Token list of slot b (None where nothing could be drawn, Q12) from its downloaded state record."""
@@ -771,7 +926,7 @@ class ForcedDecoder:
         self.pre()                                          # decision of the first iteration
         it, pending, live = 0, False, None
         while it < self.generation_length + 1:
-            self.run_iterations(self.POLL, use_graph, klen_bound=self.n_cond + it + self.POLL, live_rows=live)
+            self.run_iterations(self.POLL, use_graph, klen_bound=self.klen0 + it + self.POLL, live_rows=live)
             it += self.POLL
             if pending:
                 rec = self.poll_result()                                  # the records one window back: no stall
@@ -828,7 +983,7 @@ class BatchedGenerator:
         self.use_graph = True
         self._decoders = {}
 
-    def decoder(self, B, temperature, top_k, max_chords, top_p=1.0, per_slot: bool = False):
+    def decoder(self, B, temperature, top_k, max_chords, top_p=1.0, per_slot: bool = False, max_prompt: int = 0):
         """The decoder for B slots, its slots set to the given controls (numbers or one value per slot).  per_slot: the
         caller will read log-probabilities or give slots their own controls later (rearm): the array launches from the
         start.  Otherwise one triple for all slots runs the scalar launches, until a second setting arrives for launches
@@ -836,10 +991,12 @@ class BatchedGenerator:
         rows = sampling_rows(B, temperature, top_k, top_p)          # (validated before anything is built)
         key = (B, self.trace is not None, self.sliding)
         dec = self._decoders.get(key)
-        if dec is None or dec.ld_chord < max_chords:
+        if dec is None or dec.ld_chord < max_chords or dec.max_prompt < max_prompt:
+            # (a decoder built for prompts serves requests without one: its buffers are only longer)
             dec = ForcedDecoder(self.model, B, self.generation_length, self.memory_length, float(rows[0][0]), int(rows[1][0]),
                                 max_chords=max(64, max_chords), record_trace=self.trace is not None,
-                                top_p=float(rows[2][0]), sliding=self.sliding)
+                                top_p=float(rows[2][0]), sliding=self.sliding,
+                                max_prompt=max(max_prompt, 0 if dec is None else dec.max_prompt))
             self._decoders[key] = dec
         if per_slot:
             dec.record_logprobs()
@@ -848,17 +1005,22 @@ class BatchedGenerator:
 
     @torch.no_grad()
     def generate(self, encoded_metas: Sequence[Sequence[int]], input_datas, temperature, top_k, top_p=1.0,
-                 return_logprobs: bool = False):
+                 return_logprobs: bool = False, prompts: Optional[Sequence[Sequence[int]]] = None):
         """temperature / top_k / top_p: a number for the batch or one value per sequence.  return_logprobs: a third return
-        value, ForcedDecoder.logprobs() of the batch."""
+        value, ForcedDecoder.logprobs() of the batch.  prompts: one token list per sequence (may be empty) that the
+        sequence continues (ForcedDecoder.load): every returned sequence is [0] + meta + prompt + what was generated, and
+        generation_length counts the iterations after the prompt."""
         B = len(input_datas)
         max_chords = max(len(d.chord_token_components["chord_token"]) for d in input_datas)
-        dec = self.decoder(B, temperature, top_k, max_chords, top_p, per_slot=return_logprobs)
+        if prompts is not None and len(prompts) != B:
+            raise CommuHipError(f"prompts: one token list per sequence expected ({B}), got {len(prompts)}")
+        max_prompt = 0 if prompts is None else max(len(p) for p in prompts)
+        dec = self.decoder(B, temperature, top_k, max_chords, top_p, per_slot=return_logprobs, max_prompt=max_prompt)
         uniforms = None
         if bool((dec._sampling[0] != 0).any()):
             srcs = self.uniform_sources or [np.random.RandomState(1000 + b).random_sample for b in range(B)]
             uniforms = np.array([[float(srcs[b]()) for _ in range(dec.ld_u)] for b in range(B)], dtype=np.float32)
-        dec.load(encoded_metas, input_datas, uniforms)
+        dec.load(encoded_metas, input_datas, uniforms, prompts=prompts)
         dec.run(use_graph=self.use_graph)
         seqs, traces = dec.sequences()
         if self.trace is not None:
@@ -876,7 +1038,7 @@ class BatchedGenerator:
     @torch.no_grad()
     def generate_stream(self, encoded_meta: Sequence[int], input_data, temperature, top_k, need: int,
                         accept, top_p=1.0, slots: int = 64, seed: int = 0, max_attempts: Optional[int] = None,
-                        return_logprobs: bool = False):
+                        return_logprobs: bool = False, prompt: Optional[Sequence[int]] = None):
         """Attempts of ONE request (the reference's `while idx != num_generate` loop, midi_inferrer.py:338-354, which tries
         one sequence after the other) decoded in up to `slots` parallel slots, CONTINUOUSLY: a slot whose sequence has
         ended is handed to `accept(sequence, report) -> bool` and re-armed with the next attempt while the other slots keep
@@ -886,7 +1048,9 @@ class BatchedGenerator:
         Attempt a draws from attempt_uniforms(seed, a, .) whichever slot decodes it.
         temperature / top_k / top_p: a number, or a sequence indexed by ATTEMPT NUMBER modulo its length -- like its
         variates, the controls of attempt a do not depend on the slot that decodes it.  return_logprobs: a third return
-        value, the log-probability arrays (ForcedDecoder.logprobs) of the returned attempts in the same order."""
+        value, the log-probability arrays (ForcedDecoder.logprobs) of the returned attempts in the same order.
+        prompt: a token list every attempt of the request continues (primed slots, ForcedDecoder.load; a re-armed slot
+        returns to the primed state)."""
         B = max(1, min(int(slots), int(need)))
         max_chords = len(input_data.chord_token_components["chord_token"])
         # each control's schedule, validated on its own (the three may have different lengths)
@@ -899,11 +1063,12 @@ class BatchedGenerator:
         first = [triple(a) for a in range(B)]
         varying = any(bool((c != c[0]).any()) for c in sched)          # (one triple for every attempt: nothing to re-arm)
         dec = self.decoder(B, [t[0] for t in first], [t[1] for t in first], max_chords, [t[2] for t in first],
-                           per_slot=return_logprobs or varying)
+                           per_slot=return_logprobs or varying, max_prompt=0 if prompt is None else len(prompt))
         started = B
         sampled = bool((sched[0] != 0).any())          # (a greedy attempt reads no variate)
         uni = np.stack([self.attempt_uniforms(seed, a, dec.ld_u) for a in range(B)]) if sampled else None
-        dec.load([list(encoded_meta)] * B, [input_data] * B, uni)
+        dec.load([list(encoded_meta)] * B, [input_data] * B, uni,
+                 prompts=None if prompt is None else [list(prompt)] * B)
         if self.use_graph and dec.graph is None:
             dec.build_graph()
         dec.pre()

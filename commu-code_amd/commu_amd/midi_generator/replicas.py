@@ -20,9 +20,9 @@ def logprobs_to_lists(logprobs):
 
 
 def generate_on_device(model_args, in_args, device_index, num_generate, uniform_seed, max_rounds, training_cfg=None,
-                       logprobs=False):
+                       logprobs=False, prompt=None):
     """One replica: checkpoint -> model on cuda:<device_index>, `num_generate` validated sequences (logprobs: and their
-    log-probabilities as logprobs_to_lists gives them, a third value)."""
+    log-probabilities as logprobs_to_lists gives them, a third value).  prompt: token ids every sequence continues."""
     import copy
 
     import torch
@@ -41,16 +41,17 @@ def generate_on_device(model_args, in_args, device_index, num_generate, uniform_
     task.uniform_seed = uniform_seed
     task(model=model, input_data=pre.input_data, inference_cfg=init.inference_cfg)
     if logprobs:
-        seqs, lps = task.execute(encoded_meta, max_rounds=max_rounds, return_logprobs=True)
+        seqs, lps = task.execute(encoded_meta, max_rounds=max_rounds, return_logprobs=True, prompt=prompt)
         return encoded_meta, seqs, logprobs_to_lists(lps)
-    return encoded_meta, task.execute(encoded_meta, max_rounds=max_rounds)
+    return encoded_meta, task.execute(encoded_meta, max_rounds=max_rounds, prompt=prompt)
 
 
-def replica_worker(rank, device_index, model_args, in_args, share, max_rounds, training_cfg, q, logprobs=False):
+def replica_worker(rank, device_index, model_args, in_args, share, max_rounds, training_cfg, q, logprobs=False,
+                   prompt=None):
     try:
         # distinct variates per replica: 1_000_003 apart (a replica's rounds / sequences use seed + 7919 r + b)
         q.put((rank, generate_on_device(model_args, in_args, device_index, share, 1_000_003 * rank, max_rounds,
-                                        training_cfg, logprobs)))
+                                        training_cfg, logprobs, prompt)))
     except Exception:
         import traceback
         q.put((rank, traceback.format_exc()))

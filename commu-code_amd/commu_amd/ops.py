@@ -1274,3 +1274,54 @@ def dropout_f32(x, drop_p=0.0, drop_seed=0, gate=None, out=None):
     call("commu_dropout_f32", _p(x), _f32_2d(x, "x"), _p(gate), 0 if gate is None else _f32_2d(gate, "gate"), _p(out),
          _f32_2d(out, "out"), rows, cols, float(drop_p), int(drop_seed) & 0xFFFFFFFF, _s())
     return out
+
+
+def _i32_rows(t, n, name):
+    if t is not None and (not t.is_cuda or t.dtype != torch.int32 or t.dim() != 1 or t.numel() != n or not t.is_contiguous()):
+        raise CommuHipError(f"{name}: contiguous int32 [{n}] on the GPU expected")
+
+
+def decode_prefill_scatter(qkv, T, kc, vc, klen, lens, slots=None, window=0):
+    """Ragged prefill of one layer's K/V caches (commu_decode_prefill_scatter / _f32): qkv is the layer's time-major
+    projection buffer [T * B, >= 3 H DH] (row t * B + b) of a memory-less forward over B padded contexts; positions
+    max(0, lens[b] - window) <= t < lens[b] go to the rows of slot slots[b] (None: b) of kc / vc -- bf16 [Bc, H, Lmax, DH]
+    with DH 32 or 64, or the fp32 parity layout [Bc, Lmax, H DH] -- linear (window 0) or ring (Lmax = window + 1) --,
+    and klen[slots[b]] = lens[b].  lens / slots / klen: int32 device arrays.  Host-side checks only of what is known on
+    the host: the kernel clamps lens to [0, T] and skips slots outside the cache."""
+    for t, name in ((qkv, "qkv"), (kc, "kc"), (vc, "vc"), (klen, "klen"), (lens, "lens")):
+        if not t.is_cuda:
+            raise CommuHipError(f"{name}: commu_amd kernels need GPU tensors (no CPU fallback)")
+    T, window = int(T), int(window)
+    if qkv.dim() != 2 or T < 1 or qkv.shape[0] % T or qkv.stride(1) != 1:
+        raise CommuHipError(f"qkv: 2-D [T * B, >= 3 H DH] with T = {T} expected, got {tuple(qkv.shape)}")
+    B = qkv.shape[0] // T
+    if kc.shape != vc.shape or kc.dtype != vc.dtype or not kc.is_contiguous() or not vc.is_contiguous():
+        raise CommuHipError("kc / vc: two contiguous caches of one shape and dtype expected")
+    Bc = kc.shape[0]
+    _i32_rows(lens, B, "lens")
+    _i32_rows(slots, B, "slots")
+    _i32_rows(klen, Bc, "klen")
+    if slots is None and B > Bc:
+        raise CommuHipError(f"{B} contexts for a cache of {Bc} slots")
+    if qkv.dtype == BF16 and kc.dtype == BF16 and kc.dim() == 4:
+        _, H, Lmax, DH = kc.shape
+        if DH not in (32, 64):
+            raise CommuHipError(f"d_head {DH}: the decode caches are built for 32 and 64 (pad the model's head)")
+        HD = H * DH
+    elif qkv.dtype == F32 and kc.dtype == F32 and kc.dim() == 3:
+        _, Lmax, HD = kc.shape
+        H = DH = None
+    else:
+        raise CommuHipError("qkv / caches: bf16 with [Bc, H, Lmax, DH] caches, or fp32 with [Bc, Lmax, H DH] caches expected")
+    if qkv.shape[1] < 3 * HD:
+        raise CommuHipError(f"qkv: at least {3 * HD} columns expected, got {qkv.shape[1]}")
+    if window < 0 or (window > 0 and Lmax != window + 1):
+        raise CommuHipError(f"a ring of window {window} has {window + 1} rows; the caches have {Lmax}")
+    if H is not None:
+        if qkv.stride(0) % 8:
+            raise CommuHipError("qkv: a row stride that is a multiple of 8 expected")
+        call("commu_decode_prefill_scatter", _p(qkv), qkv.stride(0), T, B, _p(kc), _p(vc), _p(klen), _p(lens), _p(slots), Bc,
+             H, DH, Lmax, window, _s())
+    else:
+        call("commu_decode_prefill_scatter_f32", _p(qkv), qkv.stride(0), T, B, _p(kc), _p(vc), _p(klen), _p(lens), _p(slots),
+             Bc, HD, Lmax, window, _s())

@@ -259,7 +259,64 @@ __global__ void klen_advance_kernel(int* __restrict__ klen, const unsigned char*
     if (b < B && advance[b] && klen[b] < Lmax - 1) klen[b] += 1;
 }
 
+// Ragged prefill: the K and V columns of one layer's time-major projection buffer (row t * B + b) into the caches of
+// the slots, positions lo <= t < len[b] of sequence b only (lo = max(0, len[b] - window) in ring mode, else 0), and
+// klen[slot[b]] = len[b].  A lane moves 16 bytes; the 8 lanes of a position read one 128-byte line of the source (one
+// head at DH 64, two at DH 32), and the wave's 8 positions are consecutive rows of the destination.  Workgroup =
+// 32 positions; blockIdx.z walks the kept range in pieces of 256 positions.
+template <int DH>
+__global__ __launch_bounds__(256) void prefill_scatter_kernel(const bf16* __restrict__ qkv, int ld, int T, int B,
+                                                              bf16* __restrict__ kc, bf16* __restrict__ vc,
+                                                              int* __restrict__ klen, const int* __restrict__ len,
+                                                              const int* __restrict__ slot, int Bc, int H, int Lmax,
+                                                              int window) {
+    constexpr int HPL = 64 / DH;                      // heads per 128-byte line
+    const int b = blockIdx.y;
+    const int s = slot != nullptr ? slot[b] : b;
+    if (s < 0 || s >= Bc) return;
+    const int n = min(max(len[b], 0), T);
+    if (blockIdx.x == 0 && blockIdx.z == 0 && threadIdx.x == 0) klen[s] = n;
+    const int lo = window > 0 ? max(0, n - window) : 0;
+    const int hi = window > 0 ? n : min(n, Lmax);
+    const int c = threadIdx.x & 7;
+    const int head = blockIdx.x * HPL + (c * 8) / DH, col = (c * 8) % DH;
+    if (head >= H) return;
+    const size_t HD = (size_t)H * DH;
+    const bf16* src = qkv + (size_t)b * ld + HD + (size_t)head * DH + col;
+    const size_t dst0 = ((size_t)s * H + head) * Lmax;
+    for (int t = lo + blockIdx.z * 256 + (threadIdx.x >> 3), e = 0; e < 8 && t < hi; ++e, t += 32) {
+        const bf16* p = src + (size_t)t * B * ld;
+        const uint4 kq = *reinterpret_cast<const uint4*>(p);
+        const uint4 vq = *reinterpret_cast<const uint4*>(p + HD);
+        const size_t d = (dst0 + (window > 0 ? t % Lmax : t)) * DH + col;
+        *reinterpret_cast<uint4*>(kc + d) = kq;
+        *reinterpret_cast<uint4*>(vc + d) = vq;
+    }
+}
+
 }  // namespace
+
+extern "C" int commu_decode_prefill_scatter(const void* qkv, int ld_qkv, int T, int B, void* kcache, void* vcache,
+                                            int* klen, const int* len, const int* slot, int Bcache, int H, int DH,
+                                            int Lmax, int window, hipStream_t stream) {
+    if (B <= 0 || T <= 0) return 0;
+    if (H <= 0 || Bcache <= 0 || Lmax <= 0 || window < 0 || (window > 0 && Lmax != window + 1) || B > 65535) return -22;
+    if (ld_qkv < 3 * H * DH || (ld_qkv % 8) || (((uintptr_t)qkv | (uintptr_t)kcache | (uintptr_t)vcache) % 16)) return -22;
+    if (klen == nullptr || len == nullptr) return -22;
+    const int cap = window > 0 ? window : Lmax;          // positions a sequence can keep
+    const int span = T < cap ? T : cap;
+    if (DH == 64) {
+        COMMU_LAUNCH(prefill_scatter_kernel<64>, dim3(H, B, (span + 255) / 256), dim3(256), 0, stream, (const bf16*)qkv,
+                     ld_qkv, T, B, (bf16*)kcache, (bf16*)vcache, klen, len, slot, Bcache, H, Lmax, window);
+    } else if (DH == 32) {
+        COMMU_LAUNCH(prefill_scatter_kernel<32>, dim3((H + 1) / 2, B, (span + 255) / 256), dim3(256), 0, stream,
+                     (const bf16*)qkv, ld_qkv, T, B, (bf16*)kcache, (bf16*)vcache, klen, len, slot, Bcache, H, Lmax, window);
+    } else {
+        return -22;
+    }
+    COMMU_LAUNCH_CHECK();
+    return 0;
+}
 
 static int launch_kv_append(const void* qkv, int ld_qkv, void* kcache, void* vcache, const int* klen,
                             const unsigned char* active, int B, int Lmax, int H, int HD, int ring, hipStream_t stream) {

@@ -86,6 +86,86 @@ __global__ __launch_bounds__(64) void sample_post_pre_kernel(LoopStageArgs a) {
     if (a.trace != nullptr && lane == 0) a.trace[b * 4 + 3] = wall_clock64();
 }
 
+// Primed generation: the two transitions replayed over a given token prefix with NO model step, so that a slot enters the
+// loop in the state the free-running loop would be in after producing the prefix itself.  Wherever `pre` decides to
+// draw, the next prompt token is handed to `post` as the drawn token; wherever `pre` feeds a forced token, that token
+// must be the next prompt token.  The replay stops at the first prompt index the rules would not have produced.
+// One wave per slot; lane 0 walks the prompt, the wave clears the rejected-token map where the transitions ask for it
+// (every loop decision is broadcast, so the wave stays converged through the bodies).
+enum { REPLAY_FORCED = 1,        // the rules force another token at this index
+       REPLAY_NOT_APPENDED = 2,  // `post` does not append the token (chord where a draw is expected, position past a
+                                 // pending chord, EOS / BAR that the rules replace, no room in seq)
+       REPLAY_EOS = 3,           // the prompt holds EOS: nothing follows it
+       REPLAY_INVALID = 4 };     // token outside [0, 729), or the record was finished before the prompt was
+__global__ __launch_bounds__(64) void forcing_replay_kernel(int* st, int* seq, int ld_seq, const int* __restrict__ prompt,
+                                                            int ld_prompt, const int* __restrict__ prompt_len,
+                                                            const int* __restrict__ chord_tok,
+                                                            const int* __restrict__ chord_pos, int ld_chord,
+                                                            unsigned char* wrong, const float* __restrict__ utable,
+                                                            int ld_u, long long* tok, unsigned char* active,
+                                                            unsigned char* keep, unsigned char* draw, float* uni,
+                                                            int* trace, int ld_trace, float* seq_logp, int* klen, int* fed,
+                                                            int ld_fed, int* diverged) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int n = min(max(prompt_len[b], 0), ld_prompt);
+    if (lane == 0) diverged[2 * b] = diverged[2 * b + 1] = -1;
+    if (n == 0) return;                                // the record stays exactly as load() wrote it
+    const int* pr = prompt + (size_t)b * ld_prompt;
+    int rec[F_COUNT] = {};
+    if (lane == 0) record_load(rec, st, b);
+    int i = 0, nfed = 0, at = -1, why = -1;            // (lane 0) prompt index, kept tokens fed, divergence
+    // a prompt token takes at most two iterations (the decision to force it, then its append)
+#pragma unroll 1
+    for (int it = 0; it < 2 * n + 2; ++it) {
+        int stop = 0;
+        if (lane == 0) {
+            if (i >= n) stop = 1;
+            else if (pr[i] < 0 || pr[i] >= VOCAB) { at = i; why = REPLAY_INVALID; stop = 1; }
+            else if (rec[F_FORCED] >= 0 && rec[F_FORCED] != pr[i]) { at = i; why = REPLAY_FORCED; stop = 1; }
+        }
+        if (__builtin_amdgcn_readfirstlane(stop)) break;
+        const int len0 = rec[F_LEN];
+        forcing_pre_body(b, lane, rec, seq, ld_seq, chord_tok, chord_pos, ld_chord, wrong, utable, ld_u, 0x7fffffff, tok,
+                         active, keep, draw, uni, trace, ld_trace, seq_logp);
+        int tv = -1, drew = 0;
+        if (lane == 0) {
+            if (rec[F_DONE]) { at = i; why = REPLAY_INVALID; stop = 1; }
+            else {
+                if (active[b] && keep[b]) {            // what the loop would have given the model and kept
+                    if (nfed < ld_fed) fed[(size_t)b * ld_fed + nfed] = (int)tok[b];
+                    ++nfed;
+                }
+                if (rec[F_LEN] > len0) {               // the forced token pr[i] was appended
+                    if (pr[i] == TOK_EOS) { at = i; why = REPLAY_EOS; stop = 1; }
+                    ++i;
+                }
+                drew = draw[b];
+                if (drew) tv = pr[i];                  // (a draw and a forced append exclude each other: i < n here)
+            }
+        }
+        if (__builtin_amdgcn_readfirstlane(stop)) break;
+        const int len1 = rec[F_LEN];
+        forcing_post_body(b, lane, rec, seq, ld_seq, chord_pos, ld_chord, wrong, draw, nullptr, nullptr, klen, keep,
+                          1 << 30, tv, TokenLogp{NAN, NAN}, nullptr, seq_logp);
+        if (lane == 0 && drew) {
+            if (rec[F_LEN] == len1) { at = i; why = REPLAY_NOT_APPENDED; stop = 1; }
+            else {
+                if (tv == TOK_EOS) { at = i; why = REPLAY_EOS; stop = 1; }
+                ++i;
+            }
+        }
+        if (__builtin_amdgcn_readfirstlane(stop)) break;
+    }
+    if (lane == 0) {
+        if (at < 0 && i < n) { at = i; why = REPLAY_INVALID; }
+        rec[F_ITERS] = 0;                              // generation_length and the variate table count what follows
+        rec[F_NDRAW] = 0;
+        record_store(rec, st, b);
+        diverged[2 * b] = at;
+        diverged[2 * b + 1] = why;
+    }
+}
+
 // dst[b][0:n] = src[b][0:n] for rows with mask[b] != 0 (the logits of the sequences that stepped: the others keep
 // theirs for a possible re-draw, quirk Q5)
 __global__ void copy_rows_masked_kernel(float* __restrict__ dst, int ldd, const float* __restrict__ src, int lds_,
@@ -135,6 +215,25 @@ extern "C" int commu_forcing_post(int* state, int* seq, int ld_seq, const int* c
                                   int* klen, const unsigned char* keep, int lmax, int B, hipStream_t stream) {
     return commu_forcing_post_rows(state, seq, ld_seq, chord_pos, ld_chord, wrong, draw, token, live, klen, keep, lmax,
                                    nullptr, nullptr, B, stream);
+}
+
+extern "C" int commu_forcing_replay(int* state, int* seq, int ld_seq, const int* prompt, int ld_prompt,
+                                    const int* prompt_len, const int* chord_tok, const int* chord_pos, int ld_chord,
+                                    unsigned char* wrong, const float* utable, int ld_u, long long* tok,
+                                    unsigned char* active, unsigned char* keep, unsigned char* draw, float* uni, int* trace,
+                                    int ld_trace, float* seq_logp, int* klen, int* fed, int ld_fed, int* diverged, int B,
+                                    hipStream_t stream) {
+    if (B <= 0) return 0;
+    if (ld_seq < 2 || ld_chord < 1 || ld_u < 1 || ld_prompt < 1 || ld_fed < 1) return -22;
+    if (state == nullptr || seq == nullptr || prompt == nullptr || prompt_len == nullptr || wrong == nullptr ||
+        utable == nullptr || tok == nullptr || active == nullptr || keep == nullptr || draw == nullptr || uni == nullptr ||
+        klen == nullptr || fed == nullptr || diverged == nullptr)
+        return -22;
+    COMMU_LAUNCH(forcing_replay_kernel, dim3(B), dim3(64), 0, stream, state, seq, ld_seq, prompt, ld_prompt, prompt_len,
+                 chord_tok, chord_pos, ld_chord, wrong, utable, ld_u, tok, active, keep, draw, uni, trace, ld_trace, seq_logp,
+                 klen, fed, ld_fed, diverged);
+    COMMU_LAUNCH_CHECK();
+    return 0;
 }
 
 extern "C" int commu_copy_rows_masked_f32(float* dst, int ldd, const float* src, int lds_, const unsigned char* mask,

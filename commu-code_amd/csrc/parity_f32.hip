@@ -267,3 +267,59 @@ extern "C" int commu_decode_kv_append_ring_f32(const float* qkv, int ld, float* 
     COMMU_LAUNCH_CHECK();
     return 0;
 }
+
+// Ragged prefill of the fp32 caches [B][Lmax][HD]: key / value columns of the time-major projection rows t * B + b,
+// positions lo <= t < len[b] (lo = max(0, len[b] - window) on a ring, else 0), into the rows of slot[b]; klen[slot[b]] =
+// len[b].  VW floats per lane (4: 16 bytes); a row's HD floats are consecutive on both sides.  blockIdx.y walks the
+// kept range in pieces of 32 positions.
+template <int VW>
+__global__ __launch_bounds__(256) void prefill_scatter_f32_kernel(const float* __restrict__ qkv, int ld, int T, int B,
+                                                                  float* __restrict__ kc, float* __restrict__ vc,
+                                                                  int* __restrict__ klen, const int* __restrict__ len,
+                                                                  const int* __restrict__ slot, int Bc, int HD, int Lmax,
+                                                                  int window) {
+    const int b = blockIdx.x;
+    const int s = slot != nullptr ? slot[b] : b;
+    if (s < 0 || s >= Bc) return;
+    const int n = min(max(len[b], 0), T);
+    if (blockIdx.y == 0 && threadIdx.x == 0) klen[s] = n;
+    const int lo = window > 0 ? max(0, n - window) : 0;
+    const int hi = window > 0 ? n : min(n, Lmax);
+    const int t0 = lo + blockIdx.y * 32, t1 = min(t0 + 32, hi);
+    const int per = HD / VW;
+    for (int i = threadIdx.x; i < (t1 - t0) * per; i += blockDim.x) {
+        const int t = t0 + i / per, c = (i % per) * VW;
+        const float* p = qkv + ((size_t)t * B + b) * ld + HD + c;
+        const size_t d = ((size_t)s * Lmax + (window > 0 ? t % Lmax : t)) * HD + c;
+        if constexpr (VW == 4) {
+            const float4 kq = *reinterpret_cast<const float4*>(p);
+            const float4 vq = *reinterpret_cast<const float4*>(p + HD);
+            *reinterpret_cast<float4*>(kc + d) = kq;
+            *reinterpret_cast<float4*>(vc + d) = vq;
+        } else {
+            kc[d] = p[0];
+            vc[d] = p[HD];
+        }
+    }
+}
+
+extern "C" int commu_decode_prefill_scatter_f32(const float* qkv, int ld, int T, int B, float* kc, float* vc, int* klen,
+                                                const int* len, const int* slot, int Bcache, int HD, int Lmax, int window,
+                                                hipStream_t stream) {
+    if (B <= 0 || T <= 0) return 0;
+    if (HD <= 0 || Bcache <= 0 || Lmax <= 0 || window < 0 || (window > 0 && Lmax != window + 1) || ld < 3 * HD) return -22;
+    if (klen == nullptr || len == nullptr) return -22;
+    const int cap = window > 0 ? window : Lmax;
+    const int span = T < cap ? T : cap;
+    const dim3 grid(B, (span + 31) / 32);
+    if (grid.y > 65535) return -22;
+    const bool v4 = HD % 4 == 0 && ld % 4 == 0 && (((uintptr_t)qkv | (uintptr_t)kc | (uintptr_t)vc) % 16 == 0);
+    if (v4)
+        COMMU_LAUNCH(prefill_scatter_f32_kernel<4>, grid, dim3(256), 0, stream, qkv, ld, T, B, kc, vc, klen, len, slot,
+                     Bcache, HD, Lmax, window);
+    else
+        COMMU_LAUNCH(prefill_scatter_f32_kernel<1>, grid, dim3(256), 0, stream, qkv, ld, T, B, kc, vc, klen, len, slot,
+                     Bcache, HD, Lmax, window);
+    COMMU_LAUNCH_CHECK();
+    return 0;
+}

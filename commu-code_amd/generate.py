@@ -62,9 +62,23 @@ def parse_args():
     # [full, kept] pair per token (log-softmax of logits / temperature at the token; log of its probability after top-k /
     # top-p and renormalisation), null for the tokens that were not drawn (context, forced bars / positions / chords)
     input_arg_parser.add_argument("--logprobs", action="store_true")
+    # not in the reference (which starts every sequence from the meta tokens): a JSON list of token ids that FOLLOW the
+    # meta tokens; every generated sequence continues it (primed generation: the loop enters in the state it would be in
+    # after producing these tokens itself; a prompt the chord / bar rules could not have produced is refused).
+    # --generation_length counts the iterations after the prompt.
+    input_arg_parser.add_argument("--prompt_tokens", type=str, default=None, metavar="FILE")
     # not in the reference: replicas of the generator, one per GPU (default: every visible GPU, at most num_generate)
     input_arg_parser.add_argument("--gpus", type=int, default=None)
     return {"model_args": model_arg_parser, "input_args": input_arg_parser}
+
+
+def read_prompt_tokens(path):
+    """The token ids of a --prompt_tokens file: a JSON list of integers."""
+    with open(path) as f:
+        doc = json.load(f)
+    if not isinstance(doc, list) or not all(isinstance(t, int) and not isinstance(t, bool) for t in doc):
+        raise ValueError(f"{path}: a JSON list of token ids expected")
+    return doc
 
 
 from commu_amd.midi_generator.replicas import generate_on_device, replica_worker, split_num_generate  # noqa: E402
@@ -81,20 +95,22 @@ def main(model_args, input_args, training_cfg=None, device_indices=None):
     max_rounds = in_args.pop("max_rounds", None)
     gpus = in_args.pop("gpus", None)
     want_lp = bool(in_args.pop("logprobs", False))
+    prompt_file = in_args.pop("prompt_tokens", None)
+    prompt = read_prompt_tokens(prompt_file) if prompt_file else None
     if device_indices is None:
         n_vis = torch.cuda.device_count()
         device_indices = list(range(max(1, n_vis if gpus is None else min(gpus, n_vis))))
     shares = split_num_generate(in_args["num_generate"], len(device_indices))
     if len(shares) == 1:
         encoded_meta, sequences, *lps = generate_on_device(model_args, in_args, device_indices[0], shares[0], 0, max_rounds,
-                                                           training_cfg, want_lp)
+                                                           training_cfg, want_lp, prompt)
         logprobs = lps[0] if want_lp else None
     else:
         import torch.multiprocessing as mp
         ctx = mp.get_context("spawn")          # (never fork / exec a process that has initialised the GPU)
         q = ctx.Queue()
         procs = [ctx.Process(target=replica_worker, args=(r, device_indices[r], model_args, in_args, share, max_rounds,
-                                                    training_cfg, q, want_lp)) for r, share in enumerate(shares)]
+                                                    training_cfg, q, want_lp, prompt)) for r, share in enumerate(shares)]
         for p_ in procs:
             p_.start()
         # a replica that dies natively (GPU fault, OOM kill) never reports: poll the queue and the processes

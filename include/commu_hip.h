@@ -575,6 +575,32 @@ int commu_decode_sample_post_pre_rows(float* logits, int ld, int V, unsigned cha
                                       long long* tok, unsigned char* active, unsigned char* keep, unsigned char* draw,
                                       float* uni, int* trace, int ld_trace, int* klen, int lmax, int B,
                                       hipStream_t stream);
+/* ---- primed generation: enter the loop at an arbitrary point of a sequence (continue a given token prefix).
+ * commu_forcing_replay runs the two transitions above over prompt[b][0 .. prompt_len[b]) WITHOUT a model step, starting
+ * from the record, seq and klen as a load of the conditioning context leaves them (midi_inferrer.py:186-197): wherever
+ * commu_forcing_pre decides to draw, the next prompt token is handed to commu_forcing_post as the drawn token; wherever
+ * it feeds a forced token (midi_inferrer.py:239-320), that token must be the next prompt token.  One wave per slot.
+ * Results: the record (iters and ndraw reset to 0; ntrace and the optional trace continue), seq, klen[b] (+ 1 per kept
+ * model step the loop would have made), fed[b][0 ..] = the tokens of those kept steps in order (int32 [B][ld_fed]; with
+ * the discarded first step left out and forced tokens doubled, quirks Q3 / Q4), and diverged[b] = {prompt index,
+ * reason} or {-1, -1}: 1 the rules force another token there, 2 the book-keeping does not append the token (a chord
+ * token where a draw is expected, a position past a pending chord, an EOS / bar the rules replace), 3 the prompt
+ * holds EOS, 4 a token outside [0, 729) or a record that was already finished.  A slot with prompt_len 0 keeps its record
+ * bit for bit.  tok / active / keep / draw / uni are the loop's scratch arrays (overwritten); seq_logp optional. */
+int commu_forcing_replay(int* state, int* seq, int ld_seq, const int* prompt, int ld_prompt, const int* prompt_len,
+                         const int* chord_tok, const int* chord_pos, int ld_chord, unsigned char* wrong,
+                         const float* utable, int ld_u, long long* tok, unsigned char* active, unsigned char* keep,
+                         unsigned char* draw, float* uni, int* trace, int ld_trace, float* seq_logp, int* klen, int* fed,
+                         int ld_fed, int* diverged, int B, hipStream_t stream);
+/* Ragged prefill of the K/V caches from ONE layer's time-major projection buffer of a memory-less forward over the
+ * padded contexts (midi_inferrer.py:186-197 for B contexts of different lengths): qkv bf16, row t * B + b, row pitch
+ * ld_qkv >= 3 H DH, DH 32 or 64.  The K and V of positions max(0, len[b] - window) <= t < len[b] go to cache rows
+ * [slot[b]][h][t][DH] (window 0: linear cache, every position below len[b]) or [..][t mod (window + 1)][DH] (ring of
+ * Lmax = window + 1 rows), and klen[slot[b]] = len[b].  len / slot: int32 [B] device arrays (slot null: b; slots outside
+ * [0, Bcache) are skipped, len is clamped to [0, T]); rows outside the range are not touched. */
+int commu_decode_prefill_scatter(const void* qkv, int ld_qkv, int T, int B, void* kcache, void* vcache, int* klen,
+                                 const int* len, const int* slot, int Bcache, int H, int DH, int Lmax, int window,
+                                 hipStream_t stream);
 /* dst[b][0:n] = src[b][0:n] where mask[b] != 0 */
 int commu_copy_rows_masked_f32(float* dst, int ldd, const float* src, int lds, const unsigned char* mask, int rows,
                                int n, hipStream_t stream);
@@ -620,6 +646,10 @@ int commu_decode_kv_append_ring_f32(const float* qkv, int ld, float* kc, float* 
 int commu_decode_attn_ring_f32(const float* q, int ld_q, const float* kc, const float* vc, const float* rd, int ld_rd,
                                const float* r_w_bias, const float* r_r_bias, const int* klen, float* out, int ld_o, int B,
                                int H, int DH, int W, int same_length, float scale, hipStream_t stream);
+/* commu_decode_prefill_scatter on the fp32 caches of this mode, kc / vc [Bcache][Lmax][HD] (midi_inferrer.py:186-197) */
+int commu_decode_prefill_scatter_f32(const float* qkv, int ld, int T, int B, float* kc, float* vc, int* klen,
+                                     const int* len, const int* slot, int Bcache, int HD, int Lmax, int window,
+                                     hipStream_t stream);
 
 /* ---- fp32 TRAINING MODE (csrc/train_f32.hip; model.fp32_training / train.py --parity).
  * The reference trains in fp32 (train.py:48 `amp = None`, train.py:139-169): these entry points add the backward pass
