@@ -640,7 +640,7 @@ static int launch_gemm_nt(const void* A, int lda, const void* B, int ldb, void* 
             return -22;
         G8Args g8{(const bf16*)A, (const bf16*)B, C, lda, ldb, ldc, M, N, K, (M + 255) / 256, (N + 255) / 256,
                   bias, nullptr, 0, (const bf16*)relu_mask, 0, flags, drop_seed,
-                  drop_threshold16(drop_p), drop_keep_scale16(drop_threshold16(drop_p)), mask_scale, 0, 0};
+                  drop_threshold16(drop_p), drop_keep_scale16(drop_threshold16(drop_p)), mask_scale, 0, nullptr};
         return launch_gemm8_nt(g8, stream);
     }
     const bool skinny = M <= 64 && batch == 1 && bs.tri_B == 0 && (K % 128) == 0 && K <= 1024 && N >= 32 &&
@@ -691,7 +691,7 @@ static int launch_gemm_nt(const void* A, int lda, const void* B, int ldb, void* 
         // large-M Linear shapes: persistent 256 x 256 x 64 eight-phase kernel (gemm8.hip)
         G8Args g8{(const bf16*)A, (const bf16*)B, C, lda, ldb, ldc, M, N, K, (M + 255) / 256, (N + 255) / 256,
                   bias, (const bf16*)resid, ldr, (const bf16*)relu_mask, ldm, flags, drop_seed,
-                  drop_threshold16(drop_p), drop_keep_scale16(drop_threshold16(drop_p)), mask_scale, 0, 0};
+                  drop_threshold16(drop_p), drop_keep_scale16(drop_threshold16(drop_p)), mask_scale, 0, nullptr};
         return launch_gemm8_nt(g8, stream);
     }
     const bool narrow = (N <= 64);

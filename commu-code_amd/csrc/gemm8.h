@@ -14,9 +14,27 @@ struct G8Args {
     int ldm, flags;
     unsigned drop_seed, drop_thr;
     float drop_scale, mask_scale;
-    int store_mode;           // (experiment) 0 plain, 1 nt, 2 sc1, 3 sc0 sc1
     int skew_cycles;          // start-up skew between the workgroups of an XCD (0: none)
+    unsigned* stamps;         // (profiling build ABL 4) [workgroup][32 K-tiles][8 barriers] shader-clock stamps of wave 0
 };
+
+// Output tiles of workgroup `bid` in a persistent grid of G: tile i (0 <= i < my_n) has id xbase + idx + i * cpx.  XCD x (the
+// workgroups with bid % 8 == x) owns a contiguous range of tile ids (tile columns fastest, so the workgroups of an XCD share
+// activation row blocks in that XCD's L2) and its workgroups stride through the range; a grid that is not a multiple of 8
+// (tests, tiny problems) strides through the tile ids directly.
+struct G8Tiles {
+    int xbase, idx, cpx, my_n;
+};
+__host__ __device__ inline G8Tiles g8_tiles(int ntiles, int G, int bid) {
+    const bool xcdmap = (G & 7) == 0;
+    const int xcd = bid & 7, idx = xcdmap ? bid >> 3 : bid;
+    const int q8 = ntiles >> 3, r8 = ntiles & 7;
+    const int xbase = !xcdmap ? 0 : (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8);
+    const int xcount = !xcdmap ? ntiles : q8 + (xcd < r8 ? 1 : 0);
+    const int cpx = xcdmap ? G >> 3 : G;
+    const int my_n = idx < xcount ? (xcount - idx + cpx - 1) / cpx : 0;
+    return G8Tiles{xbase, idx, cpx, my_n};
+}
 
 // true when the 8-phase NT kernel takes this problem (large M, K % 64 == 0, 32-bit buffer offsets)
 bool gemm8_nt_eligible(int M, int N, int K, int lda, int ldb, int batch, int tri_B, int flags);

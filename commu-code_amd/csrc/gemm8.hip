@@ -69,14 +69,28 @@ struct Cur {          // position of a K-tile in this workgroup's flattened (out
     } while (0)
 #define G8_WAIT_LGKM() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 
+// (profiling build ABL 4) wave 0 stamps the shader clock after barrier k (0..7) of K-tile sidx of its workgroup's stream into its
+// own edge scratch: G8_STAMP_KT K-tiles x 8 barriers x 4 bytes = 1 KB of LDS, copied out once at the end of the kernel -- no
+// vector-memory instruction joins the counted waits of the loop
+constexpr int G8_STAMP_KT = 32;
+__device__ __forceinline__ void g8_stamp(LDS_AS unsigned* slots, int w, int sidx, int k) {
+    __builtin_amdgcn_sched_barrier(0);
+    if (w == 0 && sidx < G8_STAMP_KT) {
+        unsigned long long t;
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+        slots[sidx * 8 + k] = (unsigned)t;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+}
+
 // One output element through the fused epilogue (bias -> relu -> dropout -> resid -> relu-mask), then stored.
 template <bool OUT_F32>
-__device__ __forceinline__ void g8_store_one(const G8Args& a, float v, int m, int n) {
+__device__ __forceinline__ void g8_store_one(const G8Args& a, const DropKey dk, float v, int m, int n) {
     const int flags = a.flags;
     if (flags & COMMU_EPI_BIAS) v += a.bias[n];
     if (flags & COMMU_EPI_RELU) v = fmaxf(v, 0.f);
     if (flags & COMMU_EPI_DROPOUT)
-        v = drop_keep(salted(a.drop_seed), (unsigned)m * (unsigned)a.N + (unsigned)n, a.drop_thr) ? v * a.drop_scale : 0.f;
+        v = drop_keep(dk, (unsigned)m * (unsigned)a.N + (unsigned)n, a.drop_thr) ? v * a.drop_scale : 0.f;
     if (flags & COMMU_EPI_RESID) v += bf2f(a.resid[(size_t)m * a.ldr + n]);
     if (flags & COMMU_EPI_RELUMASK) v = (bf2f(a.rmask[(size_t)m * a.ldm + n]) > 0.f) ? v * a.mask_scale : 0.f;
     if (OUT_F32) ((float*)a.C)[(size_t)m * a.ldc + n] = v;
@@ -88,7 +102,7 @@ __device__ __forceinline__ void g8_store_one(const G8Args& a, float v, int m, in
 // accumulators go through a wave-private 4-KB LDS scratch, 16 rows at a time, and are stored one element per lane
 // (compact code; only the last row / column of tiles takes this path).
 template <bool OUT_F32>
-__device__ __forceinline__ void g8_store(const G8Args& a, f32x4 (&acc)[4][8], int mbase, int nbase, int r16, int g,
+__device__ __forceinline__ void g8_store(const G8Args& a, const DropKey dk, f32x4 (&acc)[4][8], int mbase, int nbase, int r16, int g,
                                          LDS_AS float* scratch, int lane) {
     const int flags = a.flags, N = a.N;
     const bool interior = (mbase + 128 <= a.M) && (nbase + 64 <= N) && (a.ldc % 8) == 0 &&
@@ -107,18 +121,24 @@ __device__ __forceinline__ void g8_store(const G8Args& a, f32x4 (&acc)[4][8], in
                 for (int e = 0; e < 4; ++e) { bv[j][e] = b0[e]; bv[j][4 + e] = b1[e]; }
             }
         }
+        // The residual (or ReLU-mask: never both, see gemm8_nt_eligible) vectors travel eight pieces ahead of their use in a ring
+        // of eight registers: the first row half's are requested before the first is used, and each piece of the second half is
+        // requested into the slot its predecessor has just left, BEHIND that piece's store.  (Requested per row half after the
+        // half's stores, the second half's first use waited -- one in-order counter -- for all eight stores of the first half to
+        // be acknowledged and then for a fresh load round trip.)
+        const bool has_aux = (flags & (COMMU_EPI_RESID | COMMU_EPI_RELUMASK)) != 0;
+        const bf16* ap = (flags & COMMU_EPI_RESID) ? a.resid : a.rmask;
+        const int lda_ = (flags & COMMU_EPI_RESID) ? a.ldr : a.ldm;
+        auto aux_ld = [&](int h, int q) {
+            return ld_bf16x8(ap + (size_t)(mbase + 16 * (4 * h + (q >> 1)) + r16) * lda_ + nbase + 32 * (q & 1) + 8 * g);
+        };
+        bf16x8 aux[8];
+        if (has_aux) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) aux[q] = aux_ld(0, q);
+        }
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            // all of this row half's residual (or ReLU-mask: never both, see gemm8_nt_eligible) vectors are requested
-            // before the first is used
-            bf16x8 aux[8];
-            if (flags & (COMMU_EPI_RESID | COMMU_EPI_RELUMASK)) {
-                const bf16* ap = (flags & COMMU_EPI_RESID) ? a.resid : a.rmask;
-                const int lda_ = (flags & COMMU_EPI_RESID) ? a.ldr : a.ldm;
-#pragma unroll
-                for (int q = 0; q < 8; ++q)
-                    aux[q] = ld_bf16x8(ap + (size_t)(mbase + 16 * (4 * h + (q >> 1)) + r16) * lda_ + nbase + 32 * (q & 1) + 8 * g);
-            }
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 const int mi = 4 * h + (q >> 1), j = q & 1;
@@ -135,7 +155,6 @@ __device__ __forceinline__ void g8_store(const G8Args& a, f32x4 (&acc)[4][8], in
                     for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
                 }
                 if (flags & COMMU_EPI_DROPOUT) {          // (N even, n a multiple of 8: one word per two columns)
-                    const DropKey dk = drop_key(salted(a.drop_seed));
                     const unsigned q0 = ((unsigned)m * (unsigned)N + (unsigned)n) >> 1, thr_hi = a.drop_thr << 16;
 #pragma unroll
                     for (int e2 = 0; e2 < 4; ++e2) {
@@ -161,13 +180,9 @@ __device__ __forceinline__ void g8_store(const G8Args& a, f32x4 (&acc)[4][8], in
 #pragma unroll
                     for (int e = 0; e < 8; ++e) o[e] = f2bf(v[e]);
                     bf16* cp = (bf16*)a.C + (size_t)m * a.ldc + n;
-                    if (a.store_mode == 1) __builtin_nontemporal_store(o, (bf16x8*)cp);
-                    else if (a.store_mode == 2)
-                        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(cp), "v"(o) : "memory");
-                    else if (a.store_mode == 3)
-                        asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1\n\ts_nop 1" :: "v"(cp), "v"(o) : "memory");
-                    else st_bf16x8(cp, o);
+                    st_bf16x8(cp, o);
                 }
+                if (has_aux && h == 0) aux[q] = aux_ld(1, q);
             }
         }
         return;
@@ -182,7 +197,7 @@ __device__ __forceinline__ void g8_store(const G8Args& a, f32x4 (&acc)[4][8], in
         for (int it = 0; it < 16; ++it) {
             const float v = scratch[it * 64 + lane];
             const int m = mbase + 16 * mi + it;
-            if (m < a.M && n < N) g8_store_one<OUT_F32>(a, v, m, n);
+            if (m < a.M && n < N) g8_store_one<OUT_F32>(a, dk, v, m, n);
         }
     }
 }
@@ -198,7 +213,7 @@ __device__ __forceinline__ bool g8_interior(const G8Args& a, int mbase, int nbas
 
 // (one 16-row block m4 of the quadrant)
 template <bool OUT_F32, int J, int XH, int BITS>
-__device__ __forceinline__ void g8_drain_piece(const G8Args& a, int flags, f32x4 (&acc)[4][8], const float (&bv)[8], int mbase,
+__device__ __forceinline__ void g8_drain_piece(const G8Args& a, const DropKey dk, int flags, f32x4 (&acc)[4][8], const float (&bv)[8], int mbase,
                                                int nbase, int r16, int g, int m4, unsigned& word, unsigned bits_in) {
     const int N = a.N;
     const int n = nbase + 32 * J + 8 * g;
@@ -219,7 +234,6 @@ __device__ __forceinline__ void g8_drain_piece(const G8Args& a, int flags, f32x4
         if (flags & COMMU_EPI_DROPOUT) {
             // one hash word per TWO elements (common.h drop_word): the lane's 8 columns start at an even flat index (n is a
             // multiple of 8 and the launcher only takes an even N with COMMU_EPI_DROPOUT): four words for eight elements
-            const DropKey dk = drop_key(salted(a.drop_seed));
             const unsigned q0 = ((unsigned)m * (unsigned)N + (unsigned)n) >> 1;
             const unsigned thr_hi = a.drop_thr << 16;          // (high half: whole-word compare; low half: 16-bit compare)
 #pragma unroll
@@ -259,13 +273,13 @@ __device__ __forceinline__ void g8_drain_piece(const G8Args& a, int flags, f32x4
 // consecutive store instructions (halves that arrive a phase apart are written back twice for 11-20 % of the lines,
 // tests/probes/write_amp.sh).  Quadrant numbers (phase order of the MFMAs): (J0,XH0) 0, (J1,XH0) 1, (J1,XH1) 2, (J0,XH1) 3.
 template <bool OUT_F32, int XH, int BITS = 0>
-__device__ __forceinline__ void g8_drain_rows(const G8Args& a, int flags, f32x4 (&acc)[4][8], const float (&bv)[2][8], int mbase,
+__device__ __forceinline__ void g8_drain_rows(const G8Args& a, const DropKey dk, int flags, f32x4 (&acc)[4][8], const float (&bv)[2][8], int mbase,
                                               int nbase, int r16, int g, unsigned* bits_out, unsigned bits_in0, unsigned bits_in1) {
     unsigned word0 = 0u, word1 = 0u;
 #pragma unroll
     for (int m4 = 0; m4 < 4; ++m4) {
-        g8_drain_piece<OUT_F32, 0, XH, BITS>(a, flags, acc, bv[0], mbase, nbase, r16, g, m4, word0, bits_in0);
-        g8_drain_piece<OUT_F32, 1, XH, BITS>(a, flags, acc, bv[1], mbase, nbase, r16, g, m4, word1, bits_in1);
+        g8_drain_piece<OUT_F32, 0, XH, BITS>(a, dk, flags, acc, bv[0], mbase, nbase, r16, g, m4, word0, bits_in0);
+        g8_drain_piece<OUT_F32, 1, XH, BITS>(a, dk, flags, acc, bv[1], mbase, nbase, r16, g, m4, word1, bits_in1);
     }
     if (BITS == 1) {
         bits_out[64 * (XH ? 3 : 0)] = word0;
@@ -285,19 +299,20 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(const G8Args a) {
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = w >> 2, wc = w & 3, r16 = lane & 15, g = lane >> 4;
     const int nk = a.K >> 6;
+    // The dropout key, once per kernel and BEFORE the first LDS-DMA is issued: the seed salt is a load from device memory, and
+    // read inside an epilogue (as it was, for every drain and whether or not the launch has dropout) it made the compiler wait
+    // vmcnt(0) there -- which on the hardware's one in-order counter drains the whole staging queue: a full memory round trip
+    // exposed twice per wave row and output tile (tests/probes/gemm_tile_probe.hip, profiles/gemm_tile_boundary.txt).
+    DropKey dk = drop_key(salted(a.drop_seed));
+    dk.key = __builtin_amdgcn_readfirstlane(dk.key);
+    dk.k2 = __builtin_amdgcn_readfirstlane(dk.k2);
+    asm volatile("" : "+s"(dk.key), "+s"(dk.k2));
 
-    // ---- this workgroup's output tiles: XCD x owns a contiguous range of tile ids (tile columns fastest, so the
-    // workgroups of an XCD share activation row blocks in that XCD's L2); its workgroups stride through the range
+    // ---- this workgroup's output tiles (g8_tiles, gemm8.h)
     const int ntiles = a.tiles_m * a.tiles_n;
-    const int G = (int)gridDim.x, bid = (int)blockIdx.x;
-    // (a grid that is not a multiple of 8 -- tests, tiny problems -- strides through the tile ids directly)
-    const bool xcdmap = (G & 7) == 0;
-    const int xcd = bid & 7, idx = xcdmap ? bid >> 3 : bid;
-    const int q8 = ntiles >> 3, r8 = ntiles & 7;
-    const int xbase = !xcdmap ? 0 : (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8);
-    const int xcount = !xcdmap ? ntiles : q8 + (xcd < r8 ? 1 : 0);
-    const int cpx = xcdmap ? G >> 3 : G;
-    const int my_n = idx < xcount ? (xcount - idx + cpx - 1) / cpx : 0;
+    const int bid = (int)blockIdx.x;
+    const G8Tiles tl = g8_tiles(ntiles, (int)gridDim.x, bid);
+    const int xbase = tl.xbase, idx = tl.idx, cpx = tl.cpx, my_n = tl.my_n;
     if (my_n == 0) return;
 
     auto settile = [&](Cur& c) {
@@ -354,6 +369,15 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(const G8Args a) {
     const int wo0 = laneoff + ch0 + wc * 4096, wo1 = laneoff + (ch0 ^ 64) + wc * 4096;
 #define G8_FRAG(off) (*(const LDS_AS bf16x8*)(lds + (off)))
 #define G8_MFMA(wa, xb, c) (ABL == 1 ? g8_fake(wa, xb, c) : mfma16(wa, xb, c))
+#define G8_STAMP(k)                                          \
+    do {                                                     \
+        if (ABL == 4) g8_stamp(stamp_slots, w, sidx, k);     \
+    } while (0)
+    LDS_AS unsigned* stamp_slots = (LDS_AS unsigned*)(smem + 2 * BUF_BYTES);          // (wave 0's edge scratch)
+    if (ABL == 4 && w == 0) {
+#pragma unroll
+        for (int i = 0; i < G8_STAMP_KT * 8 / 64; ++i) stamp_slots[64 * i + lane] = 0u;
+    }
 
     f32x4 acc[4][8];
 #pragma unroll
@@ -425,8 +449,16 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(const G8Args a) {
 
     bf16x8 xf[4][2], wf[2][2];
     int pb = 0;
+    auto burst_store = [&](int mb, int nb) {
+        g8_store<OUT_F32>(a, dk, acc, mb, nb, r16, g, (LDS_AS float*)(smem + 2 * BUF_BYTES + w * 4096), lane);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    };
     while (c0.i < my_n) {
         const int pbo = pb * BUF_BYTES;
+        const int sidx = c0.i * nk + c0.kt;          // (ABL 4 only)
         const bool v1 = c1.i < my_n, v2 = c2.i < my_n;
         // ---------------- phase 1: (Xlo, Wlo); stage Wlo of the NEXT K-tile
 #pragma unroll
@@ -444,9 +476,10 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(const G8Args a) {
             if (v1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        if (PIPE && pend) g8_drain_rows<OUT_F32, 0, BITS>(a, pflags, acc, bvl, pmb, pnb, r16, g, pbits, PIPE == 3 ? rbl[0] : 0u, PIPE == 3 ? rbl[64] : 0u);
+        if (PIPE && pend) g8_drain_rows<OUT_F32, 0, BITS>(a, dk, pflags, acc, bvl, pmb, pnb, r16, g, pbits, PIPE == 3 ? rbl[0] : 0u, PIPE == 3 ? rbl[64] : 0u);
         G8_WAIT_LGKM();
         G8_BAR();
+        G8_STAMP(0);
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)
@@ -456,6 +489,7 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(const G8Args a) {
                 for (int mi = 0; mi < 4; ++mi) acc[ni][mi] = G8_MFMA(wf[ni][kk], xf[mi][kk], acc[ni][mi]);
         __builtin_amdgcn_s_setprio(0);
         G8_BAR();
+        G8_STAMP(1);
         // ---------------- phase 2: (Xlo, Whi); Xlo of this buffer is dead -> stage Xlo two K-tiles ahead
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni) {
@@ -465,6 +499,7 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(const G8Args a) {
         if (v2) stage(Q_XLO, c2, pb);
         G8_WAIT_LGKM();
         G8_BAR();
+        G8_STAMP(2);
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)
@@ -474,6 +509,7 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(const G8Args a) {
                 for (int mi = 0; mi < 4; ++mi) acc[2 + ni][mi] = G8_MFMA(wf[ni][kk], xf[mi][kk], acc[2 + ni][mi]);
         __builtin_amdgcn_s_setprio(0);
         G8_BAR();
+        G8_STAMP(3);
         // ---------------- phase 3: (Xhi, Whi); Whi is dead -> stage Whi two ahead
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi) {
@@ -481,9 +517,10 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(const G8Args a) {
             xf[mi][1] = G8_FRAG(pbo + Q_XHI * HT_BYTES + xo1 + mi * 2048);
         }
         if (v2) stage(Q_WHI, c2, pb);
-        if (PIPE && pend) g8_drain_rows<OUT_F32, 1, BITS>(a, pflags, acc, bvl, pmb, pnb, r16, g, pbits, PIPE == 3 ? rbl[192] : 0u, PIPE == 3 ? rbl[128] : 0u);
+        if (PIPE && pend) g8_drain_rows<OUT_F32, 1, BITS>(a, dk, pflags, acc, bvl, pmb, pnb, r16, g, pbits, PIPE == 3 ? rbl[192] : 0u, PIPE == 3 ? rbl[128] : 0u);
         G8_WAIT_LGKM();
         G8_BAR();
+        G8_STAMP(4);
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)
@@ -494,6 +531,7 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(const G8Args a) {
                     acc[2 + ni][4 + mi] = G8_MFMA(wf[ni][kk], xf[mi][kk], acc[2 + ni][4 + mi]);
         __builtin_amdgcn_s_setprio(0);
         G8_BAR();
+        G8_STAMP(5);
         // ---------------- phase 4: (Xhi, Wlo); Xhi is dead -> stage Xhi two ahead; the next K-tile must have landed
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni) {
@@ -517,6 +555,7 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(const G8Args a) {
         }
         G8_WAIT_LGKM();
         G8_BAR();
+        G8_STAMP(6);
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)
@@ -526,6 +565,7 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(const G8Args a) {
                 for (int mi = 0; mi < 4; ++mi) acc[ni][4 + mi] = G8_MFMA(wf[ni][kk], xf[mi][kk], acc[ni][4 + mi]);
         __builtin_amdgcn_s_setprio(0);
         G8_BAR();
+        G8_STAMP(7);
         // ---------------- end of an output tile: write it out (the next tile's loads are already in flight)
         if (c0.kt == nk - 1 && (ABL != 3 || acc[0][0][0] == 1234.5f)) {
             const int mb = c0.m0 + wr * 128, nb = c0.n0 + wc * 64;
@@ -545,11 +585,7 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(const G8Args a) {
                     }
                 }
             } else {
-                g8_store<OUT_F32>(a, acc, mb, nb, r16, g, (LDS_AS float*)(smem + 2 * BUF_BYTES + w * 4096), lane);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+                burst_store(mb, nb);
             }
         }
         c0 = c1;
@@ -559,12 +595,19 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(const G8Args a) {
     }
     if (PIPE && pend) {          // the last tile of this workgroup
         if (PIPE == 3) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        g8_drain_rows<OUT_F32, 0, BITS>(a, pflags, acc, bvl, pmb, pnb, r16, g, pbits, PIPE == 3 ? rbl[0] : 0u, PIPE == 3 ? rbl[64] : 0u);
-        g8_drain_rows<OUT_F32, 1, BITS>(a, pflags, acc, bvl, pmb, pnb, r16, g, pbits, PIPE == 3 ? rbl[192] : 0u, PIPE == 3 ? rbl[128] : 0u);
+        g8_drain_rows<OUT_F32, 0, BITS>(a, dk, pflags, acc, bvl, pmb, pnb, r16, g, pbits, PIPE == 3 ? rbl[0] : 0u, PIPE == 3 ? rbl[64] : 0u);
+        g8_drain_rows<OUT_F32, 1, BITS>(a, dk, pflags, acc, bvl, pmb, pnb, r16, g, pbits, PIPE == 3 ? rbl[192] : 0u, PIPE == 3 ? rbl[128] : 0u);
     }
     if (wr == 0) G8_BAR();          // pairs with the stagger barrier of the second wave row
+    if (ABL == 4 && w == 0 && a.stamps != nullptr) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int i = 0; i < G8_STAMP_KT * 8 / 64; ++i)
+            a.stamps[(size_t)bid * (G8_STAMP_KT * 8) + 64 * i + lane] = stamp_slots[64 * i + lane];
+    }
 #undef G8_FRAG
 #undef G8_MFMA
+#undef G8_STAMP
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -841,6 +884,38 @@ bool gemm8_nt_bits_eligible(int M, int N, int K, int lda, int ldb, int ldc, int 
     return gemm8_nt_eligible(M, N, K, lda, ldb, 1, 0, flags);
 }
 
+// Profiling switch of tests/probes/gemm_tile_probe.hip (not in commu_hip.h; nothing in the product calls it): abl 2 / 3 / 4
+// selects the no-staging / no-epilogue / phase-stamp build of the two plain bf16 kernels for the launches that follow, 0 restores
+// the product path; stamps: device buffer of 256 unsigned per workgroup for abl 4.
+static int g8_probe_abl = 0;
+static unsigned* g8_probe_stamps = nullptr;
+extern "C" void commu_gemm8_probe(int abl, void* stamps) {
+    g8_probe_abl = abl;
+    g8_probe_stamps = (unsigned*)stamps;
+}
+
+// (tests/test_gemm_tile_map_host.py; not in commu_hip.h) 0 when for every tile count 1..max_tiles the workgroups of a grid of
+// `grid` take every tile exactly once, else the first tile count at which they do not
+extern "C" int commu_gemm8_tile_cover(int grid, int max_tiles) {
+    if (grid <= 0 || max_tiles <= 0) return -1;
+    unsigned char* seen = (unsigned char*)malloc((size_t)max_tiles);
+    int bad = 0;
+    for (int nt = 1; nt <= max_tiles && !bad; ++nt) {
+        for (int t = 0; t < nt; ++t) seen[t] = 0;
+        for (int bid = 0; bid < grid && !bad; ++bid) {
+            const G8Tiles tl = g8_tiles(nt, grid, bid);
+            for (int i = 0; i < tl.my_n; ++i) {
+                const int lid = tl.xbase + tl.idx + i * tl.cpx;
+                if (lid < 0 || lid >= nt || seen[lid]++) { bad = nt; break; }
+            }
+        }
+        for (int t = 0; t < nt && !bad; ++t)
+            if (!seen[t]) bad = nt;
+    }
+    free(seen);
+    return bad;
+}
+
 int launch_gemm8_nt(const G8Args& a_in, hipStream_t stream) {
     const G8Args& a0 = a_in;
     const int ntiles = a0.tiles_m * a0.tiles_n;
@@ -852,11 +927,20 @@ int launch_gemm8_nt(const G8Args& a_in, hipStream_t stream) {
     G8Args a = a_in;
     a.skew_cycles = 0;
     if (const char* e = getenv("COMMU_GEMM8_SKEW")) a.skew_cycles = atoi(e);
-    a.store_mode = 0;
-    if (const char* e = getenv("COMMU_GEMM8_ST")) a.store_mode = atoi(e);
 #define G8_LAUNCH(F32, AB) COMMU_LAUNCH((gemm_nt8_kernel<F32, AB>), dim3(grid), dim3(512), 0, stream, a)
     const bool pipe = getenv("COMMU_GEMM8_NOPIPE") == nullptr;
-    if (a.flags & COMMU_EPI_OUT_F32) {
+    a.stamps = g8_probe_stamps;
+    if (g8_probe_abl >= 2 && g8_probe_abl <= 4 &&
+        !(a.flags & (COMMU_EPI_OUT_F32 | COMMU_EPI_SIGNBITS_OUT | COMMU_EPI_RELUBITS))) {
+        const bool p1 = pipe && !(a.flags & (COMMU_EPI_RESID | COMMU_EPI_RELUMASK));
+#define G8_PROBE(AB)                                                                                    \
+    if (p1) COMMU_LAUNCH((gemm_nt8_kernel<false, AB, 1>), dim3(grid), dim3(512), 0, stream, a);         \
+    else COMMU_LAUNCH((gemm_nt8_kernel<false, AB, 0>), dim3(grid), dim3(512), 0, stream, a)
+        if (g8_probe_abl == 2) { G8_PROBE(2); }
+        else if (g8_probe_abl == 3) { G8_PROBE(3); }
+        else { G8_PROBE(4); }
+#undef G8_PROBE
+    } else if (a.flags & COMMU_EPI_OUT_F32) {
         G8_LAUNCH(true, 0);
     } else if (a.flags & COMMU_EPI_SIGNBITS_OUT) {
         COMMU_LAUNCH((gemm_nt8_kernel<false, 0, 2>), dim3(grid), dim3(512), 0, stream, a);
