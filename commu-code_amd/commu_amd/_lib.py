@@ -137,6 +137,9 @@ PROTOTYPES = {
     "commu_decode_kv_append_ring": [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
     "commu_decode_attn_ring": [c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_i,
                                c_i, c_p, c_p, c_p],
+    "commu_decode_attn_kv8": [c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_i,
+                              c_i, c_i, c_i, c_p, c_p, c_p],
+    "commu_decode_prefill_scatter_kv8": [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p],
     "commu_decode_tail_supported": [c_i, c_i, c_i, c_i],
     "commu_decode_tail_sync_words": [],
     "commu_decode_tail_trace": [c_p],

@@ -81,12 +81,24 @@ class DecodeState:
     window=M selects the reference's SLIDING memory (model.py:507-538): the cache of a sequence is a ring of M + 1 rows
     (Lmax is then derived), position p lives in row p mod (M + 1), and klen[b] -- "positions kept so far" in both modes --
     keeps counting beyond the ring (the kernels derive the row from it).  Without a window the cache is linear and klen
-    saturates at its last row."""
+    saturates at its last row.
+
+    kv_dtype="fp8" (opt-in; csrc/decode_kv8.hip) stores K and V as e4m3 bytes with one power-of-two scale byte per 32
+    features: kc8 / vc8 uint8 [L, B, H, Lmax, DH] and ks / vs uint8 [L, B, H, Lmax, DH / 32] instead of kc / vc, 0.516 of the
+    bf16 cache's bytes.  The mode rounds the stored K and V and nothing else (a position has one K and one V, whatever
+    step reads it); it carries no parity claim and is refused together with model.parity_fp32."""
 
     MAX_POSITIONS = 4224          # cache rows the decode attention kernel supports (commu_decode_attn)
     KLEN_UNBOUNDED = 1 << 30      # the length bound handed to the book-keeping kernels in window mode
+    KV_DTYPES = ("bf16", "fp8")
 
-    def __init__(self, model, B: int, Lmax: int, window: Optional[int] = None):
+    def __init__(self, model, B: int, Lmax: int, window: Optional[int] = None, kv_dtype: str = "bf16"):
+        if kv_dtype not in self.KV_DTYPES:
+            raise CommuHipError(f"kv_dtype: one of {self.KV_DTYPES} expected, got {kv_dtype!r}")
+        if kv_dtype == "fp8" and bool(getattr(model, "parity_fp32", False)):
+            raise CommuHipError("kv_dtype='fp8' rounds the cached K and V; the fp32 parity mode (model.parity_fp32) exists to be "
+                                "exact: choose one")
+        self.kv_dtype = kv_dtype
         if window is not None:
             window = int(window)
             if window < 1:
@@ -113,8 +125,13 @@ class DecodeState:
         L, D = model.n_layer, model._Dp
         H, DH = model.n_head, model._DHp
         HD = H * DH
-        self.kc = torch.zeros(L, B, H, Lmax, DH, device=dev, dtype=BF16)      # head-major: contiguous per (b, h)
-        self.vc = torch.zeros(L, B, H, Lmax, DH, device=dev, dtype=BF16)
+        if kv_dtype == "fp8":
+            u8 = torch.uint8          # e4m3 bytes + one E8M0 scale byte per 32 features (include/commu_hip.h)
+            self.kc8, self.vc8 = (torch.zeros(L, B, H, Lmax, DH, device=dev, dtype=u8) for _ in range(2))
+            self.ks, self.vs = (torch.zeros(L, B, H, Lmax, DH // 32, device=dev, dtype=u8) for _ in range(2))
+        else:
+            self.kc = torch.zeros(L, B, H, Lmax, DH, device=dev, dtype=BF16)      # head-major: contiguous per (b, h)
+            self.vc = torch.zeros(L, B, H, Lmax, DH, device=dev, dtype=BF16)
         self.klen = torch.zeros(B, device=dev, dtype=torch.int32)
         self._pd = ops.posemb(model.pos_emb.inv_freq, Lmax, model.d_model, ld=D, clamp_len=int(model.clamp_len))
         self.rd = [ops.gemm_nt(self._pd, model._weights(i)["r"]) for i in range(L)]
@@ -137,6 +154,15 @@ class DecodeState:
             self.t_err = torch.zeros(1, device=dev, dtype=torch.int32)
             self.t_packs = None
             self.repack()
+
+    def cache_tensors(self):
+        """The tensors that make up the K/V cache: (kc, vc), or (kc8, vc8, ks, vs) with kv_dtype="fp8".  Position rows are
+        dimension 3 ([L, B, H, Lmax, .]); fp32 parity mode: dimension 2 ([L, B, Lmax, H DH])."""
+        return (self.kc8, self.vc8, self.ks, self.vs) if self.kv_dtype == "fp8" else (self.kc, self.vc)
+
+    def cache_bytes(self) -> int:
+        """Bytes held by the K/V cache (all layers, slots and rows)."""
+        return sum(t.numel() * t.element_size() for t in self.cache_tensors())
 
     # ---- fp32 parity mode ------------------------------------------------------------------------------------------
     def _init_f32(self):
@@ -227,6 +253,8 @@ class DecodeState:
             raise CommuHipError(f"context of {T0} tokens does not fit a decode cache of {self.Lmax} positions")
         if self.parity:
             return self._prefill_f32(ctx)
+        if self.kv_dtype == "fp8":          # (equal lengths, default slots: the quantising scatter is the only way in)
+            return self.prefill_ragged(ctx, [T0] * B)
         _, _, qkvs = m._run_forward(ctx, None, None, None, need_grad=False, want_logits=True, want_kv=True)
         H, DH = m.n_head, m._DHp
         for i, qkv in enumerate(qkvs):
@@ -279,6 +307,10 @@ class DecodeState:
         else:
             _, _, qkvs = m._run_forward(ctx, None, None, None, need_grad=False, want_logits=True, want_kv=True)
         for i, qkv in enumerate(qkvs):
+            if self.kv_dtype == "fp8":
+                ops.decode_prefill_scatter_kv8(qkv.view(Tmax * Bc, -1), Tmax, self.kc8[i], self.vc8[i], self.ks[i], self.vs[i],
+                                               self.klen, lens_t, slots_t, window=self.window or 0)
+                continue
             ops.decode_prefill_scatter(qkv.view(Tmax * Bc, -1), Tmax, self.kc[i], self.vc[i], self.klen, lens_t, slots_t,
                                        window=self.window or 0)
 
@@ -289,7 +321,12 @@ class DecodeState:
         if self.attn_splits > 1 and self.split_ws is None:
             self.split_ws = torch.empty(B * H * 16 * (DH + 2), device=self.qkv.device, dtype=torch.float32)
             self.split_cnt = torch.zeros(B * H, device=self.qkv.device, dtype=torch.int32)
-        if self.window is not None:
+        if self.kv_dtype == "fp8":          # one entry point: linear / ring, unsplit / split-key
+            ops.decode_attn_kv8(self.qkv, self.kc8[i], self.vc8[i], self.ks[i], self.vs[i], self.rd[i], u, vb, self.klen,
+                                active, self.vec, scale, append=True, ring=self.window is not None,
+                                same_length=bool(self.model.same_length), nsplit=int(self.attn_splits),
+                                split_ws=self.split_ws, split_cnt=self.split_cnt)
+        elif self.window is not None:
             ops.decode_attn_ring(self.qkv, self.kc[i], self.vc[i], self.rd[i], u, vb, self.klen, active, self.vec, self.Lmax,
                                  scale, append=True, same_length=bool(self.model.same_length), nsplit=int(self.attn_splits),
                                  split_ws=self.split_ws, split_cnt=self.split_cnt)
@@ -434,8 +471,9 @@ class ForcedDecoder:
 
     def __init__(self, model, B: int, generation_length: int, memory_length: int, temperature: float, top_k: int,
                  max_chords: int = 64, record_trace: bool = False, top_p: float = 1.0, sliding: bool = False,
-                 max_prompt: int = 0):
-        """sliding: the reference's sliding memory window (DecodeState window mode) -- generation_length is then bounded by
+                 max_prompt: int = 0, kv_dtype: str = "bf16"):
+        """kv_dtype: "bf16", or "fp8" for the opt-in e4m3 K/V cache (DecodeState).
+        sliding: the reference's sliding memory window (DecodeState window mode) -- generation_length is then bounded by
         the token buffers only, not by memory_length.
         max_prompt: the longest token prefix load(prompts=) may prime a slot with (0: the loop starts from the conditioning
         context only; no buffer changes size and no launch is added).  generation_length counts the iterations AFTER the
@@ -452,6 +490,7 @@ class ForcedDecoder:
         self.NF = call("commu_forcing_state_ints")
         self.n_ctx_max = 16
         # a sequence grows by at most one token per iteration; its cache by at most one row per iteration
+        kv = {} if kv_dtype == "bf16" else {"kv_dtype": kv_dtype}          # (the default builds its state as it always did)
         if self.sliding:
             M = int(memory_length)
             if M + 1 > DecodeState.MAX_POSITIONS:
@@ -460,7 +499,7 @@ class ForcedDecoder:
             if M < self.n_ctx_max:
                 raise CommuHipError(f"a sliding memory of {M} positions cannot hold the conditioning context (up to "
                                     f"{self.n_ctx_max} tokens)")
-            self.state = DecodeState(model, B, M + 1, window=M)
+            self.state = DecodeState(model, B, M + 1, window=M, **kv)
         else:
             lmax = min(int(memory_length) + 1, DecodeState.MAX_POSITIONS)
             if self.n_ctx_max + self.generation_length + 1 > lmax:
@@ -468,7 +507,7 @@ class ForcedDecoder:
                     f"context + generation_length ({self.generation_length}) exceeds the decode memory of {lmax} positions; "
                     "the reference would start sliding its memory window here, which the K/V-cache step does not implement "
                     "unless it is asked to (sliding=True, --sliding_memory)")
-            self.state = DecodeState(model, B, lmax)
+            self.state = DecodeState(model, B, lmax, **kv)
         self._ctx_kv = None          # sliding: the context rows of every slot's K/V cache as load() left them (rearm)
         self.ld_seq = self.n_ctx_max + self.generation_length + 2 + self.max_prompt
         self.ld_chord = max_chords
@@ -732,7 +771,7 @@ class ForcedDecoder:
         if self.state.parity:
             self._ctx_kv = (self.state.kc[:, :, :n].clone(), self.state.vc[:, :, :n].clone())
         else:
-            self._ctx_kv = (self.state.kc[:, :, :, :n].clone(), self.state.vc[:, :, :, :n].clone())
+            self._ctx_kv = tuple(t[:, :, :, :n].clone() for t in self.state.cache_tensors())
 
     def load(self, encoded_metas: Sequence[Sequence[int]], input_datas, uniforms: Optional[np.ndarray] = None,
              prompts: Optional[Sequence[Sequence[int]]] = None):
@@ -753,8 +792,8 @@ class ForcedDecoder:
         if getattr(self.state, "t_err", None) is not None:
             self.state.t_err.zero_()          # (a hand-off timeout of an earlier request must not fail this one)
         ctx = torch.tensor([[0] + list(m[:n_cond - 1]) for m in encoded_metas], dtype=torch.long).t().contiguous()
-        self.state.kc.zero_()
-        self.state.vc.zero_()
+        for t in self.state.cache_tensors():
+            t.zero_()
         self.state.repack()          # (the model may have been trained since the decoder was built)
         if prompts is None:
             self.state.prefill(ctx.to(self.dev))
@@ -826,13 +865,13 @@ class ForcedDecoder:
         self.seq_logp[b].fill_(float("nan"))
         if self.sliding:
             st, n = self.state, self._ctx_rows
-            ck, cv = self._ctx_kv
             if st.parity:
+                ck, cv = self._ctx_kv
                 st.kc[:, b, :n].copy_(ck[:, b])
                 st.vc[:, b, :n].copy_(cv[:, b])
             else:
-                st.kc[:, b, :, :n].copy_(ck[:, b])
-                st.vc[:, b, :, :n].copy_(cv[:, b])
+                for t, c in zip(st.cache_tensors(), self._ctx_kv):
+                    t[:, b, :, :n].copy_(c[:, b])
         if self._primed is not None:
             self.state.klen[b].copy_(self._primed[1][b])
         else:
@@ -974,7 +1013,10 @@ class BatchedGenerator:
     `chord_token_components`).  Decoders (caches + captured graph) are kept per batch size: the sampling controls are
     device state of the decoder, so a new setting reuses the cache and the capture."""
 
-    def __init__(self, model, device, generation_length=4096, memory_length=4146, sliding=False):
+    def __init__(self, model, device, generation_length=4096, memory_length=4146, sliding=False, kv_dtype="bf16"):
+        if kv_dtype not in DecodeState.KV_DTYPES:
+            raise CommuHipError(f"kv_dtype: one of {DecodeState.KV_DTYPES} expected, got {kv_dtype!r}")
+        self.kv_dtype = kv_dtype         # "fp8": the opt-in e4m3 K/V cache of the decode step (DecodeState)
         self.model, self.device = model, device
         self.generation_length, self.memory_length = generation_length, memory_length
         self.sliding = bool(sliding)     # the reference's sliding memory window: generation_length may exceed memory_length
@@ -995,7 +1037,7 @@ class BatchedGenerator:
             # (a decoder built for prompts serves requests without one: its buffers are only longer)
             dec = ForcedDecoder(self.model, B, self.generation_length, self.memory_length, float(rows[0][0]), int(rows[1][0]),
                                 max_chords=max(64, max_chords), record_trace=self.trace is not None,
-                                top_p=float(rows[2][0]), sliding=self.sliding,
+                                top_p=float(rows[2][0]), sliding=self.sliding, kv_dtype=self.kv_dtype,
                                 max_prompt=max(max_prompt, 0 if dec is None else dec.max_prompt))
             self._decoders[key] = dec
         if per_slot:

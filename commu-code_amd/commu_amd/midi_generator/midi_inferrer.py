@@ -99,7 +99,9 @@ class InferenceTask:
         mlen = getattr(self.inference_cfg.MODEL, "memory_length", 4146) if hasattr(self.inference_cfg, "MODEL") else 4146
         # (not a key of the reference's configuration: set by generate.py --sliding_memory)
         sliding = bool(getattr(self.inference_cfg.GENERATION, "sliding_memory", False))
-        gen = BatchedGenerator(self.model, self.device, glen, mlen, sliding=sliding)
+        # (likewise: generate.py --kv_cache)
+        kv_dtype = str(getattr(self.inference_cfg.GENERATION, "kv_cache", "bf16"))
+        gen = BatchedGenerator(self.model, self.device, glen, mlen, sliding=sliding, kv_dtype=kv_dtype)
 
         def accept(seq, rep) -> bool:
             self.attempts += 1

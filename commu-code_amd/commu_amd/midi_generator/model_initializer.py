@@ -45,6 +45,9 @@ class ModelInitializeTask:
             cfg.GENERATION.generation_length = int(glen)
         if getattr(self.model_args, "sliding_memory", False):
             cfg.GENERATION.sliding_memory = True
+        # generate.py --kv_cache (not in the reference): storage of the decode step's K/V cache, "bf16" or "fp8"
+        if getattr(self.model_args, "kv_cache", None) not in (None, "bf16"):
+            cfg.GENERATION.kv_cache = str(self.model_args.kv_cache)
         cfg.freeze()
         return cfg
 

@@ -22,7 +22,9 @@ def logprobs_to_lists(logprobs):
 def generate_on_device(model_args, in_args, device_index, num_generate, uniform_seed, max_rounds, training_cfg=None,
                        logprobs=False, prompt=None):
     """One replica: checkpoint -> model on cuda:<device_index>, `num_generate` validated sequences (logprobs: and their
-    log-probabilities as logprobs_to_lists gives them, a third value).  prompt: token ids every sequence continues."""
+    log-probabilities as logprobs_to_lists gives them, a third value).  prompt: token ids every sequence continues.
+    model_args carries the decode options of every replica (--parity, --sliding_memory, --kv_cache, ...): they reach
+    the generator through the inference configuration that ModelInitializeTask builds."""
     import copy
 
     import torch

@@ -1325,3 +1325,98 @@ def decode_prefill_scatter(qkv, T, kc, vc, klen, lens, slots=None, window=0):
     else:
         call("commu_decode_prefill_scatter_f32", _p(qkv), qkv.stride(0), T, B, _p(kc), _p(vc), _p(klen), _p(lens), _p(slots),
              Bc, HD, Lmax, window, _s())
+
+
+# ---------------------------------------------------------------------------------------------- fp8 K/V cache (opt-in)
+# (include/commu_hip.h, commu_decode_attn_kv8: e4m3 bytes [B, H, Lmax, DH] + one E8M0 scale byte per 32 features)
+def _kv8_caches(kc8, vc8, ks, vs):
+    """(B, H, Lmax, DH) of the four byte tensors of one layer's fp8 K/V cache, checked."""
+    for t, name in ((kc8, "kc8"), (vc8, "vc8"), (ks, "ks"), (vs, "vs")):
+        if not t.is_cuda:
+            raise CommuHipError(f"{name}: commu_amd kernels need GPU tensors (no CPU fallback)")
+        if t.dtype != torch.uint8 or t.dim() != 4 or not t.is_contiguous():
+            raise CommuHipError(f"{name}: contiguous uint8 [B, H, Lmax, ...] expected, got {t.dtype} {tuple(t.shape)}")
+    B, H, Lmax, DH = kc8.shape
+    if DH not in (32, 64):
+        raise CommuHipError(f"d_head {DH}: the decode caches are built for 32 and 64 (pad the model's head)")
+    if vc8.shape != kc8.shape:
+        raise CommuHipError(f"vc8: {tuple(kc8.shape)} like kc8 expected, got {tuple(vc8.shape)}")
+    for t, name in ((ks, "ks"), (vs, "vs")):
+        if tuple(t.shape) != (B, H, Lmax, DH // 32):
+            raise CommuHipError(f"{name}: scale bytes [{B}, {H}, {Lmax}, {DH // 32}] expected, got {tuple(t.shape)}")
+    return B, H, Lmax, DH
+
+
+def decode_attn_kv8(qkv, kc8, vc8, ks, vs, rd, u, vb, klen, active, out, scale, append=True, ring=False, same_length=False,
+                    nsplit=1, split_ws=None, split_cnt=None):
+    """Cached single-token attention over an fp8 K/V cache (commu_decode_attn_kv8): kc8 / vc8 uint8 [B, H, Lmax, DH] (e4m3
+    bytes), ks / vs uint8 [B, H, Lmax, DH / 32] (E8M0 scale bytes); qkv bf16 [B, 3 H DH], rd bf16 [>= Lmax, >= H DH], out
+    bf16 [B, H DH], klen int32 [B].  ring: the caches are rings of Lmax = memory_length + 1 rows and klen counts absolute
+    positions (same_length hides the oldest row of a full ring); otherwise linear.  append: the kernel quantises the new
+    token's K/V into its row and attends to that image.  nsplit > 1: split_ws fp32 [>= B H nsplit (DH + 2)], split_cnt
+    int32 [>= B H] zeroed once."""
+    B, H, Lmax, DH = _kv8_caches(kc8, vc8, ks, vs)
+    if ring:
+        _ring_rows(Lmax)
+    elif Lmax < 1 or Lmax > RING_MAX_ROWS:
+        raise CommuHipError(f"decode cache of {Lmax} positions; the decode attention supports 1 .. {RING_MAX_ROWS}")
+    HD = H * DH
+    for t, name in ((qkv, "qkv"), (rd, "rd"), (out, "out"), (u, "r_w_bias"), (vb, "r_r_bias"), (klen, "klen")) \
+            + (() if active is None else ((active, "active"),)):
+        if not t.is_cuda:
+            raise CommuHipError(f"{name}: commu_amd kernels need GPU tensors (no CPU fallback)")
+    if klen.dtype != torch.int32 or klen.numel() != B or not klen.is_contiguous():
+        raise CommuHipError(f"klen: contiguous int32 [{B}] expected")
+    if active is not None and (active.dtype != torch.uint8 or active.numel() != B or not active.is_contiguous()):
+        raise CommuHipError(f"active: contiguous uint8 [{B}] expected")
+    if qkv.dtype != BF16 or qkv.dim() != 2 or qkv.shape != (B, 3 * HD) or qkv.stride(1) != 1 or qkv.stride(0) % 8:
+        raise CommuHipError(f"qkv: bf16 [{B}, {3 * HD}] with a row stride that is a multiple of 8 expected")
+    if rd.dtype != BF16 or rd.dim() != 2 or rd.shape[0] < Lmax or rd.shape[1] < HD or rd.stride(1) != 1 or rd.stride(0) % 8:
+        raise CommuHipError(f"rd: bf16 [>= {Lmax}, >= {HD}] with a row stride that is a multiple of 8 expected")
+    if out.dtype != BF16 or out.dim() != 2 or out.shape != (B, HD) or out.stride(1) != 1:
+        raise CommuHipError(f"out: bf16 [{B}, {HD}] expected")
+    for t, name in ((u, "r_w_bias"), (vb, "r_r_bias")):
+        if t.dtype != F32 or t.numel() < HD or not t.is_contiguous():
+            raise CommuHipError(f"{name}: contiguous fp32 [>= {HD}] expected")
+    nsplit = int(nsplit)
+    if nsplit < 1 or nsplit > 16:
+        raise CommuHipError("nsplit: 1 .. 16")
+    if nsplit > 1:
+        if split_ws is None or split_cnt is None or not split_ws.is_cuda or not split_cnt.is_cuda:
+            raise CommuHipError("nsplit > 1 needs split_ws and split_cnt on the GPU")
+        if split_ws.dtype != F32 or split_ws.numel() < B * H * nsplit * (DH + 2) or split_cnt.dtype != torch.int32 \
+                or split_cnt.numel() < B * H:
+            raise CommuHipError("split_ws: fp32 [>= B H nsplit (DH + 2)], split_cnt: int32 [>= B H]")
+    call("commu_decode_attn_kv8", _p(qkv), qkv.stride(0), _p(kc8), _p(vc8), _p(ks), _p(vs), _p(rd), rd.stride(0), _p(u),
+         _p(vb), _p(klen), _p(active), _p(out), out.stride(0), B, H, DH, Lmax, float(scale), 1 if append else 0,
+         1 if ring else 0, 1 if same_length else 0, nsplit, _p(split_ws) if nsplit > 1 else None,
+         _p(split_cnt) if nsplit > 1 else None, _s())
+    return out
+
+
+def decode_prefill_scatter_kv8(qkv, T, kc8, vc8, ks, vs, klen, lens, slots=None, window=0):
+    """decode_prefill_scatter into an fp8 K/V cache (commu_decode_prefill_scatter_kv8): qkv bf16 [T * B, >= 3 H DH] (row
+    t * B + b); the K and V of positions max(0, lens[b] - window) <= t < lens[b] are quantised (decode_attn_kv8's recipe)
+    into the rows of slot slots[b] (None: b) of kc8 / vc8 uint8 [Bc, H, Lmax, DH] and ks / vs uint8 [Bc, H, Lmax, DH / 32]
+    -- linear (window 0) or ring (Lmax = window + 1) --, and klen[slots[b]] = lens[b]."""
+    Bc, H, Lmax, DH = _kv8_caches(kc8, vc8, ks, vs)
+    for t, name in ((qkv, "qkv"), (klen, "klen"), (lens, "lens")):
+        if not t.is_cuda:
+            raise CommuHipError(f"{name}: commu_amd kernels need GPU tensors (no CPU fallback)")
+    T, window = int(T), int(window)
+    if qkv.dtype != BF16 or qkv.dim() != 2 or T < 1 or qkv.shape[0] % T or qkv.stride(1) != 1:
+        raise CommuHipError(f"qkv: bf16 2-D [T * B, >= 3 H DH] with T = {T} expected, got {qkv.dtype} {tuple(qkv.shape)}")
+    B = qkv.shape[0] // T
+    _i32_rows(lens, B, "lens")
+    _i32_rows(slots, B, "slots")
+    _i32_rows(klen, Bc, "klen")
+    if slots is None and B > Bc:
+        raise CommuHipError(f"{B} contexts for a cache of {Bc} slots")
+    if qkv.shape[1] < 3 * H * DH:
+        raise CommuHipError(f"qkv: at least {3 * H * DH} columns expected, got {qkv.shape[1]}")
+    if window < 0 or (window > 0 and Lmax != window + 1):
+        raise CommuHipError(f"a ring of window {window} has {window + 1} rows; the caches have {Lmax}")
+    if qkv.stride(0) % 8:
+        raise CommuHipError("qkv: a row stride that is a multiple of 8 expected")
+    call("commu_decode_prefill_scatter_kv8", _p(qkv), qkv.stride(0), T, B, _p(kc8), _p(vc8), _p(ks), _p(vs), _p(klen),
+         _p(lens), _p(slots), Bc, H, DH, Lmax, window, _s())

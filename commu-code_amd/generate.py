@@ -38,6 +38,10 @@ def parse_args():
     model_arg_parser.add_argument("--memory_length", type=int, default=None)
     model_arg_parser.add_argument("--generation_length", type=int, default=None)
     model_arg_parser.add_argument("--sliding_memory", action="store_true")
+    # not in the reference: the storage of the decode step's K/V cache.  fp8 = e4m3 bytes with one power-of-two scale byte
+    # per 32 features, 0.516 of the bf16 cache's bytes; it rounds the cached K and V (accuracy-bounded, no parity claim:
+    # INTEGRATION.md) and is refused together with --parity.
+    model_arg_parser.add_argument("--kv_cache", type=str, choices=["bf16", "fp8"], default="bf16")
     input_arg_parser.add_argument("--output_dir", type=str, required=True)
     input_arg_parser.add_argument("--bpm", type=int)
     input_arg_parser.add_argument("--audio_key", type=str, choices=list(meta.KEY_MAP.keys()))

@@ -477,6 +477,25 @@ int commu_decode_attn_ring(const void* qkv, int ld_qkv, void* kcache, void* vcac
                            const float* r_w_bias, const float* r_r_bias, const int* klen, const unsigned char* active,
                            void* out, int ld_o, int B, int H, int DH, int W, float scale, int append, int same_length,
                            int nsplit, float* split_ws, unsigned* split_cnt, hipStream_t stream);
+/* The cached decode step over an fp8 K/V cache (csrc/decode_kv8.hip; opt-in, no parity claim).  Per layer:
+ *   kc8 / vc8: uint8 [B][H][Lmax][DH], OCP e4m3 bytes, head-major like the bf16 caches;
+ *   ks / vs:   uint8 [B][H][Lmax][DH/32], one E8M0 byte per 32 consecutive features of a row: scale 2^(byte - 127).
+ * The quantiser is commu_quant_mxfp8's: sb = clamp(biased exponent of the block's amax - 8, 0, 254); the elements are
+ * multiplied by 2^(127 - sb), clamped to +-448 and rounded to nearest even.  DH 64 or 32.
+ * RULE: a position has one K and one V, whatever step reads it -- the step that appends a token attends to the
+ * quantise -> dequantise image of its K and V, so every step computes the attention of commu_decode_attn /
+ * commu_decode_attn_ring over the DEQUANTISED cache as it stands after the append.
+ * commu_decode_attn_kv8: one entry point for the linear cache (ring 0; mask_oldest ignored) and the ring of Lmax = W rows
+ * (ring 1; mask_oldest = the model's same_length), unsplit (nsplit 1; split_ws / split_cnt may be null) or split-key as
+ * commu_decode_attn_split.  append 1 also writes the new token's bytes and scale bytes to its row.  qkv, rd, out: bf16.
+ * commu_decode_prefill_scatter_kv8: commu_decode_prefill_scatter with the quantiser on the way (one launch per layer). */
+int commu_decode_attn_kv8(const void* qkv, int ld_qkv, void* kc8, void* vc8, void* ks, void* vs, const void* rd, int ld_rd,
+                          const float* r_w_bias, const float* r_r_bias, const int* klen, const unsigned char* active,
+                          void* out, int ld_o, int B, int H, int DH, int Lmax, float scale, int append, int ring,
+                          int mask_oldest, int nsplit, float* split_ws, unsigned* split_cnt, hipStream_t stream);
+int commu_decode_prefill_scatter_kv8(const void* qkv, int ld_qkv, int T, int B, void* kc8, void* vc8, void* ks, void* vs,
+                                     int* klen, const int* len, const int* slot, int Bcache, int H, int DH, int Lmax,
+                                     int window, hipStream_t stream);
 /* Everything of a decode-step layer that follows its attention, as ONE launch (csrc/decode_tail.hip):
  *   z1 = vec . Wo^T + h;  a = LN1(z1);  hid = relu(a . W1^T + b1);  z2 = hid . W2^T + b2 + a;  h_out = LN2(z2)
  *   (o_net + residual + LayerNorm model.py:344-352, PositionwiseFF model.py:163-179)
