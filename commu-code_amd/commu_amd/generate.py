@@ -75,6 +75,122 @@ def sampling_rows(B: int, temperature, top_k, top_p=1.0):
     return t.astype(np.float32), k.astype(np.int32), p.astype(np.float32)
 
 
+# ---- constraints on what a slot may draw: one additive fp32 row per slot, applied by the sampling step to the row its
+# softmax sees (logits / temperature + bias, before top-k; commu_sample_topk_topp_bias).  A finite entry re-weights an id,
+# -inf bans it.  Rows are VPAD wide like the logits rows; ids 0 and >= 729 are never drawn and their entries are ignored.
+N_VELOCITY = TOKEN_OFFSET.CHORD_START - TOKEN_OFFSET.NOTE_VELOCITY          # 64 velocity tokens, one per bin of 2
+N_PITCH = TOKEN_OFFSET.NOTE_VELOCITY - TOKEN_OFFSET.PITCH                   # 128 pitch tokens, MIDI note numbers
+
+
+def _check_bias_row(row, what="logit bias"):
+    """A constraint row as float32 [VPAD]: [729] or [768] values, no NaN, no +inf, and something left to draw."""
+    V = TOKEN_OFFSET.VOCAB_SIZE
+    try:
+        a = np.asarray(row, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise CommuHipError(f"{what}: a row of {V} (or {VPAD}) numbers expected, got {type(row).__name__}") from None
+    if a.ndim != 1 or a.shape[0] not in (V, VPAD):
+        raise CommuHipError(f"{what}: a row of {V} (or {VPAD}) numbers expected, got shape {a.shape}")
+    bad = np.isnan(a[:V]) | (a[:V] == np.inf)
+    if bool(bad.any()):
+        i = int(np.flatnonzero(bad)[0])
+        raise CommuHipError(f"{what}: entry {i} is {a[i]}; finite values or -inf (a ban) expected")
+    if not bool(np.isfinite(a[1:V]).any()):
+        raise CommuHipError(f"{what}: all of ids 1 .. {V - 1} are banned, nothing could be drawn")
+    out = np.zeros(VPAD, dtype=np.float32)
+    out[:V] = a[:V]
+    return out
+
+
+def token_constraints(ban=(), bias=None, pitch_range=None, velocity_range=None):
+    """A constraint row for ForcedDecoder.set_logit_bias / generate(logit_bias=): float32 [768], 0 where an id is left
+    alone, a finite re-weighting where `bias` names one, -inf where it is banned.  Pure host code.
+    ban: token ids that must not be drawn.  bias: {id: number} (or (id, number) pairs), added to the id's logit on the
+    scale the softmax sees (after the division by the temperature); -inf is a ban.
+    pitch_range=(lo, hi): MIDI note numbers; the pitch tokens TOKEN_OFFSET.PITCH + p with p outside [lo, hi] are banned.
+    velocity_range=(lo, hi): MIDI velocities; of the 64 velocity tokens TOKEN_OFFSET.NOTE_VELOCITY + bin the bins outside
+    [floor(lo / 2), ceil(hi / 2)] are banned -- the mapping of the min_velocity / max_velocity meta tokens (meta.encode_meta).
+    Raises CommuHipError on an id outside [1, 729), NaN or +inf, an empty range, and a row that bans everything."""
+    V = TOKEN_OFFSET.VOCAB_SIZE
+    row = np.zeros(VPAD, dtype=np.float32)
+
+    def tid(t, what):
+        if isinstance(t, (bool, np.bool_)) or not isinstance(t, (int, np.integer, str)):
+            raise CommuHipError(f"{what}: a token id in [1, {V}) expected, got {t!r}")
+        try:
+            i = int(t)          # (JSON object keys arrive as strings)
+        except ValueError:
+            raise CommuHipError(f"{what}: a token id in [1, {V}) expected, got {t!r}") from None
+        if not 1 <= i < V:
+            raise CommuHipError(f"{what}: token id {i} is outside [1, {V})")
+        return i
+
+    def span(r, what, n, lo_of, hi_of):
+        try:
+            lo, hi = r
+            lo, hi = float(lo), float(hi)
+        except (TypeError, ValueError):
+            raise CommuHipError(f"{what}: a pair (lo, hi) of numbers expected, got {r!r}") from None
+        if not (math.isfinite(lo) and math.isfinite(hi)) or lo > hi:
+            raise CommuHipError(f"{what}: ({lo:g}, {hi:g}) is empty")
+        a, b = max(lo_of(lo), 0), min(hi_of(hi), n - 1)
+        if a > b or hi < 0 or lo > 127:
+            raise CommuHipError(f"{what}: ({lo:g}, {hi:g}) leaves none of the {n} tokens (values 0 .. 127)")
+        return a, b
+
+    if pitch_range is not None:
+        a, b = span(pitch_range, "pitch_range", N_PITCH, math.ceil, math.floor)
+        row[TOKEN_OFFSET.PITCH:TOKEN_OFFSET.PITCH + a] = -np.inf
+        row[TOKEN_OFFSET.PITCH + b + 1:TOKEN_OFFSET.NOTE_VELOCITY] = -np.inf
+    if velocity_range is not None:
+        a, b = span(velocity_range, "velocity_range", N_VELOCITY, lambda v: math.floor(v / 2), lambda v: math.ceil(v / 2))
+        row[TOKEN_OFFSET.NOTE_VELOCITY:TOKEN_OFFSET.NOTE_VELOCITY + a] = -np.inf
+        row[TOKEN_OFFSET.NOTE_VELOCITY + b + 1:TOKEN_OFFSET.CHORD_START] = -np.inf
+    if bias is not None:
+        for t, v in (bias.items() if hasattr(bias, "items") else bias):
+            i = tid(t, "bias")
+            if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise CommuHipError(f"bias: a number expected for token {i}, got {v!r}")
+            v = float(v)
+            if math.isnan(v) or v == math.inf:
+                raise CommuHipError(f"bias: token {i} has {v}; a finite value or -inf (a ban) expected")
+            if row[i] != -np.inf:          # (a ban stays a ban)
+                row[i] = np.float32(v)
+    for t in ban:
+        row[tid(t, "ban")] = -np.inf
+    return _check_bias_row(row, "token_constraints")
+
+
+def read_logit_bias(doc):
+    """The {"ban": [ids], "bias": {"id": number}} document of generate.py --logit_bias as token_constraints arguments
+    (ban, bias); either key may be missing.  Raises CommuHipError on anything else."""
+    if not isinstance(doc, dict) or not set(doc) <= {"ban", "bias"}:
+        raise CommuHipError('logit bias: a JSON object {"ban": [ids], "bias": {"id": number}} expected, got '
+                            + (f"keys {sorted(doc)}" if isinstance(doc, dict) else type(doc).__name__))
+    ban, bias = doc.get("ban", []), doc.get("bias", {})
+    if not isinstance(ban, list):
+        raise CommuHipError(f'logit bias: "ban" is a list of token ids, got {type(ban).__name__}')
+    if not isinstance(bias, dict):
+        raise CommuHipError(f'logit bias: "bias" is an object of id: number, got {type(bias).__name__}')
+    return ban, bias
+
+
+def logit_bias_rows(x, n: int):
+    """x as float32 [n, VPAD] validated constraint rows: one row ([729] or [768] values) for all n, or n rows."""
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    if not isinstance(x, np.ndarray):
+        try:
+            x = np.asarray(x, dtype=np.float32)
+        except (TypeError, ValueError):
+            raise CommuHipError(f"logit bias: one row or {n} rows of numbers expected") from None
+    if x.ndim == 1:
+        return np.tile(_check_bias_row(x), (n, 1))
+    if x.ndim != 2 or x.shape[0] != n:
+        raise CommuHipError(f"logit bias: one row or {n} rows expected (one per slot addressed), got shape {x.shape}")
+    return np.stack([_check_bias_row(r, f"logit bias, row {i}") for i, r in enumerate(x)])
+
+
 class DecodeState:
     """K/V caches + distance-indexed R tables for B sequences of up to Lmax positions.
 
@@ -542,6 +658,9 @@ class ForcedDecoder:
         self.seq_logp = torch.full((B, self.ld_seq, 2), float("nan"), dtype=F32, device=dev)
         self.logp = torch.full((B, 2), float("nan"), dtype=F32, device=dev)
         self.probs = None
+        # constraint rows (set_logit_bias): fp32 [B][VPAD], allocated by the first constraint; None: the launches get a null
+        # pointer and are the ones a decoder without constraints always made
+        self.bias = None
         # (the replay of a prompt token takes at most two iterations: the decision to force it, then its append)
         self.ld_trace = 2 * (self.generation_length + 2 + 2 * self.max_prompt) if record_trace else 0
         self.trace = torch.zeros(B, self.ld_trace, dtype=i32, device=dev) if record_trace else None
@@ -616,6 +735,36 @@ class ForcedDecoder:
             else:
                 dst.copy_(torch.from_numpy(cur[i]))
 
+    def set_logit_bias(self, bias, rows: Optional[Sequence[int]] = None):
+        """Constraint rows (token_constraints) for all slots (rows=None) or the listed ones: None (clear), one row for all
+        of them, or one row per addressed slot.  The sampling step adds slot b's row to the row its softmax sees, before
+        top-k: a finite entry re-weights an id, -inf bans it.  Only DRAWS are constrained: forced tokens (bars, positions,
+        chords) are placed by the rules whatever the row says, and a prompt (load(prompts=)) is not checked against it.
+        The first constraint allocates the zeroed [B][768] device buffer and drops the captured graphs once (they hold the
+        launch without it), the way the per-slot sampling controls do; from then on rows are rewritten IN PLACE, ordered on
+        the current stream like any launch, and a captured graph follows them.  A cleared row is zeros: x + 0 is x, so the
+        slot draws bit for bit what it draws without a constraint.  A decoder that never got one allocates nothing."""
+        idx = np.arange(self.B) if rows is None else np.asarray(list(rows), dtype=np.int64)
+        if idx.ndim != 1 or (idx.size and (idx.min() < 0 or idx.max() >= self.B)):
+            raise CommuHipError(f"rows: slot numbers in [0, {self.B}) expected, got {rows!r}")
+        new = None if bias is None else logit_bias_rows(bias, len(idx))          # (validated before anything changes)
+        if self.bias is None:
+            if new is None:
+                return
+            self.bias = torch.zeros(self.B, VPAD, dtype=F32, device=self.dev)
+            self.graph = self.graph_long = None
+        if new is None:
+            if rows is None:
+                self.bias.zero_()
+            else:
+                for j in idx:
+                    self.bias[int(j)].zero_()
+        elif rows is None:
+            self.bias.copy_(torch.from_numpy(new))
+        else:
+            for j, r in zip(idx, new):
+                self.bias[int(j)].copy_(torch.from_numpy(r))
+
     def pre(self):
         call("commu_forcing_pre_rows", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_tok), _p(self.chord_pos),
              self.ld_chord, _p(self.wrong), _p(self.utable), self.ld_u, self.generation_length, _p(self.tok),
@@ -631,7 +780,7 @@ class ForcedDecoder:
         ops.sample_topk(self.state.logits, self.temperature if t_r is None else t_r, self.top_k if k_r is None else k_r,
                         wrong=self.wrong, uniforms=self.uni, active=self.draw, token=self.token,
                         probs_out=self.probs if want_probs else None, top_p=self.top_p if p_r is None else p_r,
-                        logp_out=logp)
+                        logp_out=logp, bias=self.bias)
         call("commu_forcing_post_rows", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_pos), self.ld_chord,
              _p(self.wrong), _p(self.draw), _p(self.token), None, _p(self.state.klen), _p(self.keep),
              self.state.klen_cap, _p(logp), _p(seq_logp), B, _s())
@@ -642,12 +791,16 @@ class ForcedDecoder:
         st = self.state
         st.step(self.tok, self.active, None)
         t_r, k_r, p_r, _, seq_logp = self._rows_args()          # (fused: the pair reaches post in registers, no hand-over)
-        call("commu_decode_sample_post_pre_rows", _p(st.logits), st.logits.stride(0), TOKEN_OFFSET.VOCAB_SIZE,
-             _p(self.wrong), self.temperature, self.top_k, self.top_p, _p(t_r), _p(k_r), _p(p_r), _p(self.token), None, 0,
-             None, _p(seq_logp), _p(self.fsm), _p(self.seq), self.ld_seq,
-             _p(self.chord_tok), _p(self.chord_pos), self.ld_chord, _p(self.utable), self.ld_u, self.generation_length,
-             _p(self.tok), _p(self.active), _p(self.keep), _p(self.draw), _p(self.uni), _p(self.trace), self.ld_trace,
-             _p(st.klen), st.klen_cap, self.B, _s())
+        args = (_p(st.logits), st.logits.stride(0), TOKEN_OFFSET.VOCAB_SIZE,
+                _p(self.wrong), self.temperature, self.top_k, self.top_p, _p(t_r), _p(k_r), _p(p_r), _p(self.token), None, 0,
+                None, _p(seq_logp), _p(self.fsm), _p(self.seq), self.ld_seq,
+                _p(self.chord_tok), _p(self.chord_pos), self.ld_chord, _p(self.utable), self.ld_u, self.generation_length,
+                _p(self.tok), _p(self.active), _p(self.keep), _p(self.draw), _p(self.uni), _p(self.trace), self.ld_trace,
+                _p(st.klen), st.klen_cap, self.B)
+        if self.bias is None:
+            call("commu_decode_sample_post_pre_rows", *args, _s())
+        else:
+            call("commu_decode_sample_post_pre_bias", *args, _p(self.bias), self.bias.stride(0), _s())
 
     def iteration(self, want_probs: bool = False):
         """One complete iteration, eagerly (tests inspect the draws between iterations)."""
@@ -849,9 +1002,12 @@ class ForcedDecoder:
     # Primed slots (load(prompts=)) return to their PRIMED state: record, klen and trace from the device copies load() took;
     # sliding: the physical rows 0 .. min(longest primed memory, ring rows) - 1.
     # sampling: a (temperature, top_k, top_p) triple for the slot's next attempt (None: the slot keeps its controls).
-    def rearm(self, b: int, uniforms_row: Optional[np.ndarray] = None, sampling=None):
+    # logit_bias: a constraint row for the slot's next attempt (None: the slot keeps its row; set_logit_bias clears one).
+    def rearm(self, b: int, uniforms_row: Optional[np.ndarray] = None, sampling=None, logit_bias=None):
         if sampling is not None:
             self.set_sampling(*sampling, rows=[b])
+        if logit_bias is not None:
+            self.set_logit_bias(logit_bias, rows=[b])
         rep0 = self.reports[b]
         rep = ForcingReport(rep0.n_chords, rep0.num_measures)
         self.reports[b] = rep
@@ -1025,12 +1181,16 @@ class BatchedGenerator:
         self.use_graph = True
         self._decoders = {}
 
-    def decoder(self, B, temperature, top_k, max_chords, top_p=1.0, per_slot: bool = False, max_prompt: int = 0):
+    def decoder(self, B, temperature, top_k, max_chords, top_p=1.0, per_slot: bool = False, max_prompt: int = 0,
+                logit_bias=None):
         """The decoder for B slots, its slots set to the given controls (numbers or one value per slot).  per_slot: the
         caller will read log-probabilities or give slots their own controls later (rearm): the array launches from the
         start.  Otherwise one triple for all slots runs the scalar launches, until a second setting arrives for launches
-        that are already captured (ForcedDecoder.__init__)."""
+        that are already captured (ForcedDecoder.__init__).  logit_bias: the request's constraint rows (one for all slots
+        or one per slot; None clears what an earlier request left on this decoder)."""
         rows = sampling_rows(B, temperature, top_k, top_p)          # (validated before anything is built)
+        if logit_bias is not None:
+            logit_bias = logit_bias_rows(logit_bias, B)
         key = (B, self.trace is not None, self.sliding)
         dec = self._decoders.get(key)
         if dec is None or dec.ld_chord < max_chords or dec.max_prompt < max_prompt:
@@ -1043,12 +1203,15 @@ class BatchedGenerator:
         if per_slot:
             dec.record_logprobs()
         dec.set_sampling(*rows)
+        dec.set_logit_bias(logit_bias)
         return dec
 
     @torch.no_grad()
     def generate(self, encoded_metas: Sequence[Sequence[int]], input_datas, temperature, top_k, top_p=1.0,
-                 return_logprobs: bool = False, prompts: Optional[Sequence[Sequence[int]]] = None):
-        """temperature / top_k / top_p: a number for the batch or one value per sequence.  return_logprobs: a third return
+                 return_logprobs: bool = False, prompts: Optional[Sequence[Sequence[int]]] = None, logit_bias=None):
+        """temperature / top_k / top_p: a number for the batch or one value per sequence.  logit_bias: a constraint row
+        (token_constraints) for the request or one per sequence -- what a sequence may DRAW; forced tokens and prompts are
+        not affected (ForcedDecoder.set_logit_bias).  return_logprobs: a third return
         value, ForcedDecoder.logprobs() of the batch.  prompts: one token list per sequence (may be empty) that the
         sequence continues (ForcedDecoder.load): every returned sequence is [0] + meta + prompt + what was generated, and
         generation_length counts the iterations after the prompt."""
@@ -1057,7 +1220,8 @@ class BatchedGenerator:
         if prompts is not None and len(prompts) != B:
             raise CommuHipError(f"prompts: one token list per sequence expected ({B}), got {len(prompts)}")
         max_prompt = 0 if prompts is None else max(len(p) for p in prompts)
-        dec = self.decoder(B, temperature, top_k, max_chords, top_p, per_slot=return_logprobs, max_prompt=max_prompt)
+        dec = self.decoder(B, temperature, top_k, max_chords, top_p, per_slot=return_logprobs, max_prompt=max_prompt,
+                           logit_bias=logit_bias)
         uniforms = None
         if bool((dec._sampling[0] != 0).any()):
             srcs = self.uniform_sources or [np.random.RandomState(1000 + b).random_sample for b in range(B)]
@@ -1080,7 +1244,7 @@ class BatchedGenerator:
     @torch.no_grad()
     def generate_stream(self, encoded_meta: Sequence[int], input_data, temperature, top_k, need: int,
                         accept, top_p=1.0, slots: int = 64, seed: int = 0, max_attempts: Optional[int] = None,
-                        return_logprobs: bool = False, prompt: Optional[Sequence[int]] = None):
+                        return_logprobs: bool = False, prompt: Optional[Sequence[int]] = None, logit_bias=None):
         """Attempts of ONE request (the reference's `while idx != num_generate` loop, midi_inferrer.py:338-354, which tries
         one sequence after the other) decoded in up to `slots` parallel slots, CONTINUOUSLY: a slot whose sequence has
         ended is handed to `accept(sequence, report) -> bool` and re-armed with the next attempt while the other slots keep
@@ -1092,8 +1256,11 @@ class BatchedGenerator:
         variates, the controls of attempt a do not depend on the slot that decodes it.  return_logprobs: a third return
         value, the log-probability arrays (ForcedDecoder.logprobs) of the returned attempts in the same order.
         prompt: a token list every attempt of the request continues (primed slots, ForcedDecoder.load; a re-armed slot
-        returns to the primed state)."""
+        returns to the primed state).
+        logit_bias: one constraint row (token_constraints) for every attempt of the request."""
         B = max(1, min(int(slots), int(need)))
+        if logit_bias is not None and np.ndim(logit_bias) != 1:
+            raise CommuHipError(f"logit_bias: one row for the request expected, got shape {np.shape(logit_bias)}")
         max_chords = len(input_data.chord_token_components["chord_token"])
         # each control's schedule, validated on its own (the three may have different lengths)
         n_of = lambda x: 1 if np.ndim(x) == 0 else len(x)
@@ -1105,7 +1272,8 @@ class BatchedGenerator:
         first = [triple(a) for a in range(B)]
         varying = any(bool((c != c[0]).any()) for c in sched)          # (one triple for every attempt: nothing to re-arm)
         dec = self.decoder(B, [t[0] for t in first], [t[1] for t in first], max_chords, [t[2] for t in first],
-                           per_slot=return_logprobs or varying, max_prompt=0 if prompt is None else len(prompt))
+                           per_slot=return_logprobs or varying, max_prompt=0 if prompt is None else len(prompt),
+                           logit_bias=logit_bias)
         started = B
         sampled = bool((sched[0] != 0).any())          # (a greedy attempt reads no variate)
         uni = np.stack([self.attempt_uniforms(seed, a, dec.ld_u) for a in range(B)]) if sampled else None

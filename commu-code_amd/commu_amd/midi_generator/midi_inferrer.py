@@ -89,10 +89,11 @@ class InferenceTask:
         return count_notes(seq) > 0
 
     def execute(self, encoded_meta, max_rounds: Optional[int] = None, return_logprobs: bool = False,
-                prompt: Optional[List[int]] = None):                                          # :338-354
+                prompt: Optional[List[int]] = None, logit_bias=None):                         # :338-354
         """return_logprobs (not in the reference): (sequences, their log-probability arrays -- ForcedDecoder.logprobs).
         prompt (not in the reference): token ids that follow the meta tokens; every attempt continues them (primed
-        generation, BatchedGenerator.generate_stream) and every returned sequence starts with [0] + meta + prompt."""
+        generation, BatchedGenerator.generate_stream) and every returned sequence starts with [0] + meta + prompt.
+        logit_bias (not in the reference): a constraint row (generate.token_constraints) on what every attempt may draw."""
         from ..generate import BatchedGenerator
         data = self.input_data
         glen = self.inference_cfg.GENERATION.generation_length
@@ -117,5 +118,6 @@ class InferenceTask:
         res = gen.generate_stream(list(encoded_meta), data, data.temperature, data.top_k, data.num_generate, accept,
                                   top_p=getattr(data, "top_p", 1.0), seed=self.uniform_seed,
                                   max_attempts=None if max_rounds is None else max_rounds * data.num_generate,
-                                  return_logprobs=return_logprobs, prompt=None if not prompt else list(prompt))
+                                  return_logprobs=return_logprobs, prompt=None if not prompt else list(prompt),
+                                  logit_bias=logit_bias)
         return (res[0], res[2]) if return_logprobs else res[0]

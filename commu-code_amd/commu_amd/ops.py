@@ -920,7 +920,7 @@ def _sampling_control(x, name, dtype, nseq, device):
 
 
 def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=None, token=None, probs_out=None,
-                top_p=1.0, logp_out=None):
+                top_p=1.0, logp_out=None, bias=None, V=729):
     """In-place temperature + softmax + top-k + wrong-token mask + inverse-CDF draw per sequence.
     logits: fp32 [nseq, >=V] (row stride = ld), modified in place (logits[:, 1:V] /= temperature).
     top_p < 1: nucleus filter after the top-k / rejected-token step (an extra mode; the reference has top-k only).
@@ -929,10 +929,24 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
     checked here (generate.sampling_rows does that on the host); the kernel clamps top_k to [1, V].
     logp_out: fp32 [nseq, 2], receives per drawn token (full, kept) -- the log-softmax over ids 1 .. V-1 of the row the
     draw used at the drawn id, and the log of the token's probability in the distribution it was drawn from (0 for
-    temperature 0); NaN, NaN where nothing could be drawn; untouched where active[b] == 0."""
+    temperature 0); NaN, NaN where nothing could be drawn; untouched where active[b] == 0.
+    bias: fp32 [nseq, >=V] on the device of the logits (row stride = ld_bias), a constraint per sequence: the distribution
+    is built from logits / temperature + bias (the raw row + bias for temperature 0) -- a finite entry re-weights an id,
+    -inf bans it, before top-k.  It is never written back: the logits are left as the call without it leaves them
+    (commu_sample_topk_topp_bias; generate.token_constraints builds and validates such rows).
+    V: the ids drawn from are 1 .. V-1 (2 <= V <= 768; the decode loop's vocabulary by default)."""
     nseq = logits.shape[0]
-    V = 729
+    V = int(V)
     assert logits.dtype == F32 and logits.stride(1) == 1
+    if bias is not None:
+        if not isinstance(bias, torch.Tensor) or not bias.is_cuda or bias.device != logits.device:
+            raise CommuHipError("bias: a tensor on the device of the logits expected (no CPU fallback)")
+        if bias.dtype != F32 or bias.dim() != 2 or bias.shape[0] != nseq or bias.shape[1] < V:
+            raise CommuHipError(f"bias: float32 [{nseq}, >= {V}] expected, got "
+                                f"{str(bias.dtype).replace('torch.', '')} {tuple(bias.shape)}")
+        if bias.stride(1) != 1 or (nseq > 1 and bias.stride(0) < V):
+            raise CommuHipError(f"bias: rows of unit stride, at least {V} elements apart, expected; got strides "
+                                f"{tuple(bias.stride())}")
     t_s, t_r = _sampling_control(temperature, "temperature", F32, nseq, logits.device)
     k_s, k_r = _sampling_control(top_k, "top_k", torch.int32, nseq, logits.device)
     p_s, p_r = _sampling_control(top_p, "top_p", F32, nseq, logits.device)
@@ -944,10 +958,11 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
                                 f"{str(logp_out.dtype).replace('torch.', '')} {tuple(logp_out.shape)}")
     if token is None:
         token = torch.empty(nseq, device=logits.device, dtype=torch.int32)
-    call("commu_sample_topk_topp_rows", _p(logits), logits.stride(0), nseq, V, _p(wrong),
+    call("commu_sample_topk_topp_bias", _p(logits), logits.stride(0), nseq, V, _p(wrong),
          0 if wrong is None else wrong.stride(0), _p(uniforms), _p(active), 0.0 if t_s is None else float(t_s),
          1 if k_s is None else int(k_s), 1.0 if p_s is None else float(p_s), _p(t_r), _p(k_r), _p(p_r), _p(token),
-         _p(probs_out), 0 if probs_out is None else probs_out.stride(0), _p(logp_out), _s())
+         _p(probs_out), 0 if probs_out is None else probs_out.stride(0), _p(logp_out), _p(bias),
+         0 if bias is None else max(int(bias.stride(0)), V), _s())
     return token
 
 

@@ -67,13 +67,21 @@ struct TokenLogp {
 //   kept: log of the probability the token had in the distribution it was drawn from (after top-k, rejected-token mask,
 //         top-p and renormalisation; exactly 0 for greedy);
 // and store it to logp_out[b][0:2] when that is not null.
+// BIAS (bias fp32 [B][ld_bias], ld_bias >= V): a constraint of the caller's on what sequence b may draw.  With x the
+//   value above (logits / temperature, the raw row for greedy) the distribution is built from y[id] = x[id] + bias[b][id],
+//   one fp32 add: a finite entry re-weights an id, -inf bans it (its probability is exactly 0 and it takes none of the k
+//   places: bias, then top-k, then the rejected-token mask, then top-p).  What is written back is x, never y, so a Q5
+//   re-draw adds the bias once to the compounded row; `full` is the log-softmax of y.  A row banned entirely has no
+//   mass: the Q12 exit below.  Without BIAS the pointer is not looked at and the code is what it was.
+template <bool BIAS>
 __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restrict__ logits, int ld, int V,
                                                  const unsigned char* __restrict__ wrong, int ldw,
                                                  const float* __restrict__ uni,
                                                  const unsigned char* __restrict__ active, float temperature,
                                                  int top_k, int* __restrict__ token, float* __restrict__ probs_out,
                                                  int ldp, float top_p, SamplingRows rows, bool want_logp,
-                                                 float* __restrict__ logp_out, TokenLogp& lp) {
+                                                 float* __restrict__ logp_out, TokenLogp& lp,
+                                                 const float* __restrict__ bias = nullptr, int ld_bias = 0) {
     float* lg = logits + (size_t)b * ld;
     // The optional per-sequence inputs -- the active flag and this sequence's controls -- are loaded unconditionally: a null
     // array reads a valid word of this sequence instead (token[b], logits[b][0]), which is then ignored.  So they are in
@@ -88,6 +96,11 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
     float raw[PER_LANE];
 #pragma unroll
     for (int e = 0; e < PER_LANE; ++e) raw[e] = lg[min(base + e, V - 1)];
+    float bv[PER_LANE];           // (BIAS) this lane's entries of the bias row, in the same batch of loads
+    if constexpr (BIAS) {
+#pragma unroll
+        for (int e = 0; e < PER_LANE; ++e) bv[e] = bias[(size_t)b * ld_bias + min(base + e, V - 1)];
+    }
     unsigned wmask = 0u;          // the rejected ("wrong") tokens of this lane
     if (wrong != nullptr) {
         unsigned char wb[PER_LANE];
@@ -115,6 +128,7 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
 #pragma unroll
         for (int e = 0; e < PER_LANE; ++e) {
             const int id = base + e;
+            if constexpr (BIAS) raw[e] += bv[e];               // greedy writes nothing back: the row drawn from is y
             if (id >= 1 && id < V && raw[e] > best) { best = raw[e]; bi = id; }
         }
         const float wbest = wmax_f(best);                      // ties: the lowest id
@@ -139,8 +153,10 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
             const bool in = id >= 1 && id < V;
             const float x = in ? raw[e] / temperature : -INFINITY;
             if (in) lg[id] = x;                 // in-place division: compounds on a redo (Q5)
-            p[e] = x;
-            mx = fmaxf(mx, x);
+            float y = x;
+            if constexpr (BIAS) y = in ? x + bv[e] : -INFINITY;          // (the bias is not written back)
+            p[e] = y;
+            mx = fmaxf(mx, y);
         }
         mx = wmax_f(mx);
         float s = 0.f;
@@ -317,7 +333,16 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
         const int owner = max(drawn, 0) / PER_LANE;
         xd = lane_f(xd, owner);
         pd = lane_f(pd, owner);
-        if (temperature != 0.f) xd = xd / temperature;
+        if (temperature != 0.f) {
+            xd = xd / temperature;
+            if constexpr (BIAS) {                  // y at the drawn id, as the softmax above saw it
+                float bd = 0.f;
+#pragma unroll
+                for (int e = 0; e < PER_LANE; ++e)
+                    if (base + e == drawn) bd = bv[e];
+                xd += lane_f(bd, owner);
+            }
+        }
         lp.full = drawn < 0 ? NAN : (xd - lmx) - logf(lsum);
         lp.kept = drawn < 0 ? NAN : (temperature == 0.f ? 0.f : logf(pd));
         if (logp_out != nullptr && lane == 0) { logp_out[2 * b] = lp.full; logp_out[2 * b + 1] = lp.kept; }

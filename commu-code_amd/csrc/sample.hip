@@ -7,12 +7,14 @@
 //                   uniform variate u[b] (torch.multinomial's stream is not reproducible).
 // A sequence whose kept mass is 0 (Q12: greedy argmax is a rejected token) gets token -1.
 // The controls may be per-sequence device arrays, and the step can report the log-probabilities of the token it drew
-// (decode_loop.h: SamplingRows, TokenLogp).
+// (decode_loop.h: SamplingRows, TokenLogp).  An optional additive row per sequence constrains what may be drawn (bias, then
+// top-k: sample_topk_body<BIAS>); without one the launch is the kernel that never heard of it.
 #include "decode_loop.h"
 #include "commu_hip.h"
 
 namespace {
 
+template <bool BIAS>
 __global__ __launch_bounds__(64) void sample_topk_kernel(float* __restrict__ logits, int ld, int V,
                                                          const unsigned char* __restrict__ wrong, int ldw,
                                                          const float* __restrict__ uni,
@@ -20,29 +22,47 @@ __global__ __launch_bounds__(64) void sample_topk_kernel(float* __restrict__ log
                                                          float temperature, int top_k,
                                                          int* __restrict__ token, float* __restrict__ probs_out,
                                                          int ldp, float top_p, SamplingRows rows,
-                                                         float* __restrict__ logp_out) {
+                                                         float* __restrict__ logp_out,
+                                                         const float* __restrict__ bias, int ld_bias) {
     TokenLogp lp;
-    sample_topk_body(blockIdx.x, threadIdx.x, logits, ld, V, wrong, ldw, uni, active, temperature, top_k, token, probs_out,
-                     ldp, top_p, rows, logp_out != nullptr, logp_out, lp);
+    sample_topk_body<BIAS>(blockIdx.x, threadIdx.x, logits, ld, V, wrong, ldw, uni, active, temperature, top_k, token,
+                           probs_out, ldp, top_p, rows, logp_out != nullptr, logp_out, lp, bias, ld_bias);
 }
 
 }  // namespace
+
+extern "C" int commu_sample_topk_topp_bias(float* logits, int ld, int nseq, int V, const unsigned char* wrong, int ldw,
+                                           const float* uniforms, const unsigned char* active, float temperature,
+                                           int top_k, float top_p, const float* temperature_rows, const int* top_k_rows,
+                                           const float* top_p_rows, int* token, float* probs_out, int ldp,
+                                           float* logp_out, const float* bias, int ld_bias, hipStream_t stream) {
+    if (nseq <= 0) return 0;
+    if (bias != nullptr && ld_bias < V) return -22;          // (the kernel reads bias[b][0 .. V-1])
+    // (a scalar that an array replaces is not looked at; the kernel clamps what the arrays hold)
+    if (V > 64 * PER_LANE || V < 2 || (top_k_rows == nullptr && (top_k < 1 || top_k > V)) ||
+        (top_p_rows == nullptr && !(top_p > 0.f)))
+        return -22;
+    const SamplingRows rows{temperature_rows, top_k_rows, top_p_rows};
+    // two kernels: without a bias the launch is the one it always was (no added load, no added register)
+    if (bias != nullptr) {
+        COMMU_LAUNCH(sample_topk_kernel<true>, dim3(nseq), dim3(64), 0, stream, logits, ld, V, wrong, ldw, uniforms, active,
+                     temperature, top_k, token, probs_out, ldp, top_p, rows, logp_out, bias, ld_bias);
+    } else {
+        COMMU_LAUNCH(sample_topk_kernel<false>, dim3(nseq), dim3(64), 0, stream, logits, ld, V, wrong, ldw, uniforms, active,
+                     temperature, top_k, token, probs_out, ldp, top_p, rows, logp_out, nullptr, 0);
+    }
+    COMMU_LAUNCH_CHECK();
+    return 0;
+}
 
 extern "C" int commu_sample_topk_topp_rows(float* logits, int ld, int nseq, int V, const unsigned char* wrong, int ldw,
                                            const float* uniforms, const unsigned char* active, float temperature,
                                            int top_k, float top_p, const float* temperature_rows, const int* top_k_rows,
                                            const float* top_p_rows, int* token, float* probs_out, int ldp,
                                            float* logp_out, hipStream_t stream) {
-    if (nseq <= 0) return 0;
-    // (a scalar that an array replaces is not looked at; the kernel clamps what the arrays hold)
-    if (V > 64 * PER_LANE || V < 2 || (top_k_rows == nullptr && (top_k < 1 || top_k > V)) ||
-        (top_p_rows == nullptr && !(top_p > 0.f)))
-        return -22;
-    COMMU_LAUNCH(sample_topk_kernel, dim3(nseq), dim3(64), 0, stream, logits, ld, V, wrong, ldw, uniforms, active,
-                 temperature, top_k, token, probs_out, ldp, top_p, SamplingRows{temperature_rows, top_k_rows, top_p_rows},
-                 logp_out);
-    COMMU_LAUNCH_CHECK();
-    return 0;
+    return commu_sample_topk_topp_bias(logits, ld, nseq, V, wrong, ldw, uniforms, active, temperature, top_k, top_p,
+                                       temperature_rows, top_k_rows, top_p_rows, token, probs_out, ldp, logp_out, nullptr, 0,
+                                       stream);
 }
 
 extern "C" int commu_sample_topk_topp(float* logits, int ld, int nseq, int V, const unsigned char* wrong, int ldw,

@@ -71,6 +71,14 @@ def parse_args():
     # after producing these tokens itself; a prompt the chord / bar rules could not have produced is refused).
     # --generation_length counts the iterations after the prompt.
     input_arg_parser.add_argument("--prompt_tokens", type=str, default=None, metavar="FILE")
+    # not in the reference (where pitch_range / min_velocity / max_velocity / inst are conditioning hints only): constrain
+    # what the sequences may DRAW.  --logit_bias: a JSON file {"ban": [ids], "bias": {"id": number}} -- banned ids are never
+    # drawn, a number is added to the id's logit on the scale the softmax sees (after the division by the temperature),
+    # before top-k.  --pitch_min / --pitch_max: MIDI note numbers, pitch tokens outside them are banned.  Forced tokens
+    # (bars, positions, the chord progression) and --prompt_tokens are not affected.
+    input_arg_parser.add_argument("--logit_bias", type=str, default=None, metavar="FILE")
+    input_arg_parser.add_argument("--pitch_min", type=int, default=None)
+    input_arg_parser.add_argument("--pitch_max", type=int, default=None)
     # not in the reference: replicas of the generator, one per GPU (default: every visible GPU, at most num_generate)
     input_arg_parser.add_argument("--gpus", type=int, default=None)
     return {"model_args": model_arg_parser, "input_args": input_arg_parser}
@@ -83,6 +91,26 @@ def read_prompt_tokens(path):
     if not isinstance(doc, list) or not all(isinstance(t, int) and not isinstance(t, bool) for t in doc):
         raise ValueError(f"{path}: a JSON list of token ids expected")
     return doc
+
+
+def read_constraints(path=None, pitch_min=None, pitch_max=None):
+    """The constraint row of --logit_bias / --pitch_min / --pitch_max (None when none of them is given); host code only,
+    raises (commu_amd.generate.CommuHipError, ValueError) on a malformed file or an empty range."""
+    if path is None and pitch_min is None and pitch_max is None:
+        return None
+    from commu_amd.generate import read_logit_bias, token_constraints
+    ban, bias = [], {}
+    if path is not None:
+        with open(path) as f:
+            try:
+                doc = json.load(f)
+            except json.JSONDecodeError as e:
+                raise ValueError(f"{path}: not JSON ({e})") from None
+        ban, bias = read_logit_bias(doc)
+    pitch = None
+    if pitch_min is not None or pitch_max is not None:
+        pitch = (0 if pitch_min is None else pitch_min, 127 if pitch_max is None else pitch_max)
+    return token_constraints(ban=ban, bias=bias, pitch_range=pitch)
 
 
 from commu_amd.midi_generator.replicas import generate_on_device, replica_worker, split_num_generate  # noqa: E402
@@ -101,20 +129,23 @@ def main(model_args, input_args, training_cfg=None, device_indices=None):
     want_lp = bool(in_args.pop("logprobs", False))
     prompt_file = in_args.pop("prompt_tokens", None)
     prompt = read_prompt_tokens(prompt_file) if prompt_file else None
+    # (refused here when malformed: before a model is loaded or a replica started)
+    logit_bias = read_constraints(in_args.pop("logit_bias", None), in_args.pop("pitch_min", None),
+                                  in_args.pop("pitch_max", None))
     if device_indices is None:
         n_vis = torch.cuda.device_count()
         device_indices = list(range(max(1, n_vis if gpus is None else min(gpus, n_vis))))
     shares = split_num_generate(in_args["num_generate"], len(device_indices))
     if len(shares) == 1:
         encoded_meta, sequences, *lps = generate_on_device(model_args, in_args, device_indices[0], shares[0], 0, max_rounds,
-                                                           training_cfg, want_lp, prompt)
+                                                           training_cfg, want_lp, prompt, logit_bias)
         logprobs = lps[0] if want_lp else None
     else:
         import torch.multiprocessing as mp
         ctx = mp.get_context("spawn")          # (never fork / exec a process that has initialised the GPU)
         q = ctx.Queue()
         procs = [ctx.Process(target=replica_worker, args=(r, device_indices[r], model_args, in_args, share, max_rounds,
-                                                    training_cfg, q, want_lp, prompt)) for r, share in enumerate(shares)]
+                                                    training_cfg, q, want_lp, prompt, logit_bias)) for r, share in enumerate(shares)]
         for p_ in procs:
             p_.start()
         # a replica that dies natively (GPU fault, OOM kill) never reports: poll the queue and the processes

@@ -438,6 +438,29 @@ int commu_sample_topk_topp_rows(float* logits, int ld, int nseq, int V, const un
                                 float top_p, const float* temperature_rows, const int* top_k_rows,
                                 const float* top_p_rows, int* token, float* probs_out, int ldp, float* logp_out,
                                 hipStream_t stream);
+/* the same with a CONSTRAINT on what each sequence may draw (the reference has none: a ComMU request's pitch_range,
+ * min/max_velocity and inst are conditioning hints only): bias, fp32 [nseq][ld_bias] with ld_bias >= V, optional.
+ * With x the value the step computes without it -- logits / temperature, which is still what is written back; the raw row
+ * for temperature == 0 -- the distribution is built from y[id] = x[id] + bias[b][id] for 1 <= id < V, one fp32 add: on the
+ * scale of the row the softmax sees, so it is defined on a Q5 re-draw (the stored row is already divided), never
+ * compounded, and a ban is exact either way.  A finite entry re-weights an id, -inf bans it; NaN and +inf are the
+ * caller's to refuse (generate.token_constraints).
+ *   Order: bias, then top-k, then the rejected-token mask `wrong`, then top-p -- a banned id takes none of the k places
+ *   (`wrong`, quirk Q5 of the reference, does).  Max, sum, top-k, top-p and the draw all work on y; temperature == 0
+ *   takes the argmax of y, ties to the lowest id.
+ *   The bias is NEVER written back: after the call the logits are bit for bit what the call without it leaves, and a
+ *   re-draw from them adds the bias once to the compounded row.
+ *   probs_out is the constrained distribution, exactly 0 at banned ids.  logp_out[0] (full) is the log-softmax of y over
+ *   ids 1 .. V-1 at the drawn id, "the row as this draw used it"; [1] (kept) as above; full <= kept still holds.
+ *   A row whose every id is banned, or whose remaining ids `wrong` removes, takes the Q12 exit: token -1, NaN pair.
+ *   The 12 bias loads of a lane are issued with its logits loads (same index clamp, lanes past V contribute nothing).
+ * bias == null: commu_sample_topk_topp_rows bit for bit -- a kernel of its own, without the loads (the three entry
+ * points above forward here with null).  ld_bias < V: -22. */
+int commu_sample_topk_topp_bias(float* logits, int ld, int nseq, int V, const unsigned char* wrong, int ldw,
+                                const float* uniforms, const unsigned char* active, float temperature, int top_k,
+                                float top_p, const float* temperature_rows, const int* top_k_rows,
+                                const float* top_p_rows, int* token, float* probs_out, int ldp, float* logp_out,
+                                const float* bias, int ld_bias, hipStream_t stream);
 
 /* ---- single-token decode step with a K/V cache (forward_generate with qlen 1, model.py:606-628, as
  * called by midi_inferrer.py:199-207).  Caches are bf16 [B][H][Lmax][DH] per layer; klen[b] = valid rows
@@ -594,6 +617,18 @@ int commu_decode_sample_post_pre_rows(float* logits, int ld, int V, unsigned cha
                                       long long* tok, unsigned char* active, unsigned char* keep, unsigned char* draw,
                                       float* uni, int* trace, int ld_trace, int* klen, int lmax, int B,
                                       hipStream_t stream);
+/* The same launch with the sampling stage of commu_sample_topk_topp_bias: bias fp32 [B][ld_bias] (ld_bias >= 729),
+ * sequence b's constraint row -- read by the sampling stage only.  Forced tokens are not draws and are not affected; the
+ * rejected-token map stays the forcing rules' own.  bias == null: commu_decode_sample_post_pre_rows, which forwards here,
+ * bit for bit and with the kernel it always launched. */
+int commu_decode_sample_post_pre_bias(float* logits, int ld, int V, unsigned char* wrong, float temperature, int top_k,
+                                      float top_p, const float* temperature_rows, const int* top_k_rows,
+                                      const float* top_p_rows, int* token, float* probs_out, int ldp, float* logp,
+                                      float* seq_logp, int* state, int* seq, int ld_seq, const int* chord_tok,
+                                      const int* chord_pos, int ld_chord, const float* utable, int ld_u, int max_iters,
+                                      long long* tok, unsigned char* active, unsigned char* keep, unsigned char* draw,
+                                      float* uni, int* trace, int ld_trace, int* klen, int lmax, int B,
+                                      const float* bias, int ld_bias, hipStream_t stream);
 /* ---- primed generation: enter the loop at an arbitrary point of a sequence (continue a given token prefix).
  * commu_forcing_replay runs the two transitions above over prompt[b][0 .. prompt_len[b]) WITHOUT a model step, starting
  * from the record, seq and klen as a load of the conditioning context leaves them (midi_inferrer.py:186-197): wherever
