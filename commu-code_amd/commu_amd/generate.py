@@ -202,15 +202,40 @@ class DecodeState:
     kv_dtype="fp8" (opt-in; csrc/decode_kv8.hip) stores K and V as e4m3 bytes with one power-of-two scale byte per 32
     features: kc8 / vc8 uint8 [L, B, H, Lmax, DH] and ks / vs uint8 [L, B, H, Lmax, DH / 32] instead of kc / vc, 0.516 of the
     bf16 cache's bytes.  The mode rounds the stored K and V and nothing else (a position has one K and one V, whatever
-    step reads it); it carries no parity claim and is refused together with model.parity_fp32."""
+    step reads it); it carries no parity claim and is refused together with model.parity_fp32.
+
+    shared_prefix=Pcap (opt-in; csrc/decode_prefix.hip) holds the positions that ALL slots have in common once: pk / pv bf16
+    [L, H, Pcap, DH] with prefix_len (one int32 word on the device) valid rows, filled by prefill_shared().  The cache
+    kc / vc [L, B, H, Lmax, DH] then holds the PRIVATE rows only: row r of slot b is absolute position prefix_len + r, klen[b]
+    counts private rows and starts at 0.  Every step computes what the unshared state computes over a cache that holds the
+    prefix in every slot (relative scores depend on the distance only).  bf16 linear cache only: refused together with
+    window, kv_dtype="fp8" and model.parity_fp32."""
 
     MAX_POSITIONS = 4224          # cache rows the decode attention kernel supports (commu_decode_attn)
     KLEN_UNBOUNDED = 1 << 30      # the length bound handed to the book-keeping kernels in window mode
     KV_DTYPES = ("bf16", "fp8")
 
-    def __init__(self, model, B: int, Lmax: int, window: Optional[int] = None, kv_dtype: str = "bf16"):
+    def __init__(self, model, B: int, Lmax: int, window: Optional[int] = None, kv_dtype: str = "bf16",
+                 shared_prefix: Optional[int] = None):
         if kv_dtype not in self.KV_DTYPES:
             raise CommuHipError(f"kv_dtype: one of {self.KV_DTYPES} expected, got {kv_dtype!r}")
+        if shared_prefix is not None:          # (refused before anything is allocated; each of the three is a follow-up)
+            shared_prefix = int(shared_prefix)
+            if window is not None:
+                raise CommuHipError("shared_prefix with a sliding window: a ring would wrap over the shared rows; the shared "
+                                    "prompt prefix is built for the linear cache only")
+            if kv_dtype == "fp8":
+                raise CommuHipError("shared_prefix with kv_dtype='fp8': the shared prompt prefix is built for the bf16 cache "
+                                    "only")
+            if bool(getattr(model, "parity_fp32", False)):
+                raise CommuHipError("shared_prefix with the fp32 parity mode (model.parity_fp32): the shared prompt prefix is "
+                                    "built for the bf16 cache only")
+            if shared_prefix < 1:
+                raise CommuHipError(f"shared_prefix: a capacity of at least one position expected, got {shared_prefix}")
+            if shared_prefix + Lmax > self.MAX_POSITIONS:
+                raise CommuHipError(f"a shared prefix of up to {shared_prefix} positions and {Lmax} private rows need "
+                                    f"{shared_prefix + Lmax} positions; this build supports {self.MAX_POSITIONS}")
+        self.shared_prefix = shared_prefix
         if kv_dtype == "fp8" and bool(getattr(model, "parity_fp32", False)):
             raise CommuHipError("kv_dtype='fp8' rounds the cached K and V; the fp32 parity mode (model.parity_fp32) exists to be "
                                 "exact: choose one")
@@ -249,7 +274,14 @@ class DecodeState:
             self.kc = torch.zeros(L, B, H, Lmax, DH, device=dev, dtype=BF16)      # head-major: contiguous per (b, h)
             self.vc = torch.zeros(L, B, H, Lmax, DH, device=dev, dtype=BF16)
         self.klen = torch.zeros(B, device=dev, dtype=torch.int32)
-        self._pd = ops.posemb(model.pos_emb.inv_freq, Lmax, model.d_model, ld=D, clamp_len=int(model.clamp_len))
+        n_dist = Lmax          # rows of the distance tables
+        if shared_prefix is not None:
+            self.pk = torch.zeros(L, H, shared_prefix, DH, device=dev, dtype=BF16)      # head-major like the cache
+            self.pv = torch.zeros(L, H, shared_prefix, DH, device=dev, dtype=BF16)
+            self.prefix_len = torch.zeros(1, device=dev, dtype=torch.int32)             # P: read by the kernels
+            self.prefix_ws, self.prefix_cnt = None, None
+            n_dist = shared_prefix + Lmax          # (a key of the prefix is up to P + Lmax - 1 away)
+        self._pd = ops.posemb(model.pos_emb.inv_freq, n_dist, model.d_model, ld=D, clamp_len=int(model.clamp_len))
         self.rd = [ops.gemm_nt(self._pd, model._weights(i)["r"]) for i in range(L)]
         self.logits = torch.zeros(B, VPAD, device=dev, dtype=F32)          # persistent: re-draws read them again (Q5)
         self.logits_new = torch.zeros(B, VPAD, device=dev, dtype=F32)      # this step's logits before the row select
@@ -273,7 +305,10 @@ class DecodeState:
 
     def cache_tensors(self):
         """The tensors that make up the K/V cache: (kc, vc), or (kc8, vc8, ks, vs) with kv_dtype="fp8".  Position rows are
-        dimension 3 ([L, B, H, Lmax, .]); fp32 parity mode: dimension 2 ([L, B, Lmax, H DH])."""
+        dimension 3 ([L, B, H, Lmax, .]); fp32 parity mode: dimension 2 ([L, B, Lmax, H DH]).  shared_prefix: the private
+        caches and the prefix, (kc, vc, pk, pv)."""
+        if self.shared_prefix is not None:
+            return (self.kc, self.vc, self.pk, self.pv)
         return (self.kc8, self.vc8, self.ks, self.vs) if self.kv_dtype == "fp8" else (self.kc, self.vc)
 
     def cache_bytes(self) -> int:
@@ -430,10 +465,41 @@ class DecodeState:
             ops.decode_prefill_scatter(qkv.view(Tmax * Bc, -1), Tmax, self.kc[i], self.vc[i], self.klen, lens_t, slots_t,
                                        window=self.window or 0)
 
+    def prefill_shared(self, ctx_column: torch.Tensor):
+        """shared_prefix: the K/V of the positions every slot has in common.  ctx_column: int64 [P] (or [P, 1]) tokens; ONE
+        memory-less forward over that single column, then one commu_decode_prefill_scatter launch per layer (one context,
+        one slot: source and destination layouts are the prefill's) moves them into pk / pv and sets prefix_len = P.  Every
+        slot then starts with no private rows (klen = 0)."""
+        if self.shared_prefix is None:
+            raise CommuHipError("prefill_shared: this decode state was built without shared_prefix")
+        col = ctx_column.reshape(-1, 1).to(self.klen.device)
+        P = col.shape[0]
+        if P < 1 or P > self.shared_prefix:
+            raise CommuHipError(f"a shared prefix of {P} positions was given; this state holds 1 .. {self.shared_prefix}")
+        _, _, qkvs = self.model._run_forward(col, None, None, None, need_grad=False, want_logits=True, want_kv=True)
+        lens = torch.full((1,), P, device=self.klen.device, dtype=torch.int32)
+        for i, qkv in enumerate(qkvs):
+            ops.decode_prefill_scatter(qkv.view(P, -1), P, self.pk[i].unsqueeze(0), self.pv[i].unsqueeze(0), self.prefix_len,
+                                       lens)
+        self.klen.zero_()
+
+    def _attn_prefix(self, i, u, vb, active, B, H, DH, scale):
+        """_attn with a shared prefix (commu_decode_attn_prefix): one launch does the prefix part once per group of slots,
+        the private part per slot and the merge.  attn_splits splits the PRIVATE keys."""
+        if self.prefix_ws is None:
+            n = ops.decode_prefix_ws_floats(B, H, DH, self.shared_prefix, 16)          # (any nsplit the policy may choose)
+            self.prefix_ws = torch.empty(n, device=self.qkv.device, dtype=torch.float32)
+            self.prefix_cnt = torch.zeros(B * H, device=self.qkv.device, dtype=torch.int32)
+        ops.decode_attn_prefix(self.qkv, self.pk[i], self.pv[i], self.prefix_len, self.kc[i], self.vc[i], self.rd[i], u, vb,
+                               self.klen, active, self.vec, scale, self.prefix_ws, self.prefix_cnt, append=True,
+                               nsplit=int(self.attn_splits))
+
     def _attn(self, i, u, vb, active, B, H, DH, scale):
         """Cached attention of layer i (K/V append fused in).  attn_splits > 1: the keys of a (sequence, head) pair over
         several workgroups (long memories, few live sequences); pairs with fewer than 512 keys run unsplit either way.
         Window mode: the ring variant of the same kernel (commu_decode_attn_ring)."""
+        if self.shared_prefix is not None:
+            return self._attn_prefix(i, u, vb, active, B, H, DH, scale)
         if self.attn_splits > 1 and self.split_ws is None:
             self.split_ws = torch.empty(B * H * 16 * (DH + 2), device=self.qkv.device, dtype=torch.float32)
             self.split_cnt = torch.zeros(B * H, device=self.qkv.device, dtype=torch.int32)
@@ -587,8 +653,11 @@ class ForcedDecoder:
 
     def __init__(self, model, B: int, generation_length: int, memory_length: int, temperature: float, top_k: int,
                  max_chords: int = 64, record_trace: bool = False, top_p: float = 1.0, sliding: bool = False,
-                 max_prompt: int = 0, kv_dtype: str = "bf16"):
+                 max_prompt: int = 0, kv_dtype: str = "bf16", shared_prompt: bool = False):
         """kv_dtype: "bf16", or "fp8" for the opt-in e4m3 K/V cache (DecodeState).
+        shared_prompt (opt-in, needs max_prompt > 0): every load() gives all slots the same conditioning tokens, chords and
+        prompt; their K/V are computed and held ONCE (DecodeState(shared_prefix=)) and a slot's cache holds only what it
+        generates itself: generation_length + 2 private rows.
         sliding: the reference's sliding memory window (DecodeState window mode) -- generation_length is then bounded by
         the token buffers only, not by memory_length.
         max_prompt: the longest token prefix load(prompts=) may prime a slot with (0: the loop starts from the conditioning
@@ -607,7 +676,19 @@ class ForcedDecoder:
         self.n_ctx_max = 16
         # a sequence grows by at most one token per iteration; its cache by at most one row per iteration
         kv = {} if kv_dtype == "bf16" else {"kv_dtype": kv_dtype}          # (the default builds its state as it always did)
-        if self.sliding:
+        self.shared_prompt = bool(shared_prompt)
+        self.prefix_P = 0            # shared_prompt: the positions all slots have in common (set by load)
+        if self.shared_prompt:
+            if self.max_prompt < 1:
+                raise CommuHipError("shared_prompt: a decoder that shares a prompt needs max_prompt > 0")
+            # what a replay can produce for this max_prompt: the context and the kept tokens of the replayed stream
+            pcap = self.n_ctx_max + (self.n_ctx_max + 2 * self.max_prompt)
+            lp = self.generation_length + 2
+            self._mem_rows = min(int(memory_length) + 1, DecodeState.MAX_POSITIONS)      # shared + private positions
+            # (window / fp8 / parity are refused by the state, before it allocates, with the reason)
+            self.state = DecodeState(model, B, lp, window=int(memory_length) if self.sliding else None, shared_prefix=pcap,
+                                     **kv)
+        elif self.sliding:
             M = int(memory_length)
             if M + 1 > DecodeState.MAX_POSITIONS:
                 raise CommuHipError(f"a sliding memory of {M} positions needs {M + 1} cache rows; this build supports "
@@ -902,6 +983,13 @@ class ForcedDecoder:
         klen0 = int(klen.max())
         if klen0 - n_cond > self.ld_fed:
             raise CommuHipError(f"the replayed stream of {klen0 - n_cond} kept tokens exceeds the buffer of {self.ld_fed}")
+        if self.shared_prompt:
+            # equal conditioning, chords and prompts were checked on the host: the replays cannot have diverged
+            if int(klen.min()) != klen0:
+                raise CommuHipError(f"internal error: equal prompts replayed to different memory lengths {klen.tolist()}")
+            self._share(klen0, torch.cat([ctx[:, 0].to(self.dev), self.fed[0, :klen0 - n_cond].long()]))
+            self._primed = (self.fsm.clone(), st.klen.clone(), None if self.trace is None else self.trace.clone())
+            return
         if not self.sliding and klen0 + self.generation_length + 1 > st.Lmax:
             b = int(klen.argmax())
             raise CommuHipError(
@@ -916,6 +1004,45 @@ class ForcedDecoder:
         st.prefill_ragged(full, klen.astype(np.int32))
         self.klen0 = klen0
         self._primed = (self.fsm.clone(), st.klen.clone(), None if self.trace is None else self.trace.clone())
+
+    def _check_shared(self, encoded_metas, input_datas, prompts):
+        """shared_prompt: every slot must carry what slot 0 carries."""
+        def chords(d):
+            c = d.chord_token_components
+            return [int(t) for t in c["chord_token"]], [int(t) for t in c["chord_position"]]
+        m0, c0 = [int(t) for t in encoded_metas[0]], chords(input_datas[0])
+        for b in range(1, self.B):
+            what = None
+            if [int(t) for t in encoded_metas[b]] != m0:
+                what = "encoded_meta"
+            elif chords(input_datas[b])[0] != c0[0]:
+                what = "chord tokens"
+            elif chords(input_datas[b])[1] != c0[1]:
+                what = "chord positions"
+            elif float(input_datas[b].num_measures) != float(input_datas[0].num_measures):
+                what = "num_measures"
+            elif prompts is not None and prompts[b] != prompts[0]:
+                what = "prompt"
+            if what is not None:
+                raise CommuHipError(f"shared_prompt: slot {b} differs from slot 0 in its {what}; a decoder that shares the "
+                                    "prompt needs the same conditioning, chords and prompt in every slot")
+
+    def _share(self, P, column):
+        """shared_prompt: the P common positions (tokens `column`) become the shared prefix, every slot starts with no
+        private rows."""
+        st = self.state
+        need = P + self.generation_length + 1
+        if need > self._mem_rows:
+            raise CommuHipError(
+                f"every slot starts with {P} shared positions (context {self.n_cond} + {P - self.n_cond} replayed model "
+                f"steps); with generation_length {self.generation_length} that needs {need} positions and the decode memory "
+                f"has {self._mem_rows} (shorten the prompt or generation_length)")
+        if self.generation_length + 1 > st.Lmax:
+            raise CommuHipError(f"generation_length {self.generation_length} needs {self.generation_length + 1} private rows; "
+                                f"the decode state has {st.Lmax}")
+        st.prefill_shared(column)          # (sets prefix_len = P and klen = 0)
+        self.prefix_P = P
+        self.klen0 = 0                     # the split-key policy looks at the private rows
 
     def _keep_ring_rows(self, n):
         """Sliding: once a slot's ring has wrapped its first rows are gone: keep physical rows 0 .. n - 1 for rearm()."""
@@ -939,6 +1066,8 @@ class ForcedDecoder:
         n_cond = len(encoded_metas[0])
         if n_cond + 1 > self.n_ctx_max or any(len(m) != n_cond for m in encoded_metas):
             raise CommuHipError("encoded_meta: every sequence needs the same number (<= 15) of conditioning tokens")
+        if self.shared_prompt:
+            self._check_shared(encoded_metas, input_datas, prompts)
         self.n_cond = n_cond
         self._last_load = (encoded_metas, input_datas, uniforms, prompts)
         self._primed, self.klen0 = None, n_cond
@@ -948,7 +1077,9 @@ class ForcedDecoder:
         for t in self.state.cache_tensors():
             t.zero_()
         self.state.repack()          # (the model may have been trained since the decoder was built)
-        if prompts is None:
+        if prompts is None and self.shared_prompt:          # the conditioning context is what the slots share
+            self._share(n_cond, ctx[:, 0].to(self.dev))
+        elif prompts is None:
             self.state.prefill(ctx.to(self.dev))
             if self.sliding:
                 # keep the context rows for rearm() (rows = positions here, the context is shorter than the ring)
@@ -1001,6 +1132,8 @@ class ForcedDecoder:
     # host-to-device copies of the state record and the variates are the ones a re-arm always made).
     # Primed slots (load(prompts=)) return to their PRIMED state: record, klen and trace from the device copies load() took;
     # sliding: the physical rows 0 .. min(longest primed memory, ring rows) - 1.
+    # shared_prompt: the prefix belongs to no slot and is never written by a step; the slot's private rows are abandoned
+    # (klen = 0), nothing is copied.
     # sampling: a (temperature, top_k, top_p) triple for the slot's next attempt (None: the slot keeps its controls).
     # logit_bias: a constraint row for the slot's next attempt (None: the slot keeps its row; set_logit_bias clears one).
     def rearm(self, b: int, uniforms_row: Optional[np.ndarray] = None, sampling=None, logit_bias=None):
@@ -1028,7 +1161,9 @@ class ForcedDecoder:
             else:
                 for t, c in zip(st.cache_tensors(), self._ctx_kv):
                     t[:, b, :, :n].copy_(c[:, b])
-        if self._primed is not None:
+        if self.shared_prompt:               # no rows to restore: the slot's private rows are simply abandoned
+            self.state.klen[b] = 0
+        elif self._primed is not None:
             self.state.klen[b].copy_(self._primed[1][b])
         else:
             self.state.klen[b] = self.n_cond
@@ -1169,9 +1304,12 @@ class BatchedGenerator:
     `chord_token_components`).  Decoders (caches + captured graph) are kept per batch size: the sampling controls are
     device state of the decoder, so a new setting reuses the cache and the capture."""
 
-    def __init__(self, model, device, generation_length=4096, memory_length=4146, sliding=False, kv_dtype="bf16"):
+    def __init__(self, model, device, generation_length=4096, memory_length=4146, sliding=False, kv_dtype="bf16",
+                 shared_prompt=False):
         if kv_dtype not in DecodeState.KV_DTYPES:
             raise CommuHipError(f"kv_dtype: one of {DecodeState.KV_DTYPES} expected, got {kv_dtype!r}")
+        # opt-in: requests whose sequences all continue ONE prompt hold its K/V once (ForcedDecoder(shared_prompt=True))
+        self.shared_prompt = bool(shared_prompt)
         self.kv_dtype = kv_dtype         # "fp8": the opt-in e4m3 K/V cache of the decode step (DecodeState)
         self.model, self.device = model, device
         self.generation_length, self.memory_length = generation_length, memory_length
@@ -1182,23 +1320,25 @@ class BatchedGenerator:
         self._decoders = {}
 
     def decoder(self, B, temperature, top_k, max_chords, top_p=1.0, per_slot: bool = False, max_prompt: int = 0,
-                logit_bias=None):
+                logit_bias=None, shared: bool = False):
         """The decoder for B slots, its slots set to the given controls (numbers or one value per slot).  per_slot: the
         caller will read log-probabilities or give slots their own controls later (rearm): the array launches from the
         start.  Otherwise one triple for all slots runs the scalar launches, until a second setting arrives for launches
         that are already captured (ForcedDecoder.__init__).  logit_bias: the request's constraint rows (one for all slots
-        or one per slot; None clears what an earlier request left on this decoder)."""
+        or one per slot; None clears what an earlier request left on this decoder).  shared: the decoder that holds the
+        request's common prompt once (its own cache layout: kept beside the unshared decoder of the same size)."""
         rows = sampling_rows(B, temperature, top_k, top_p)          # (validated before anything is built)
         if logit_bias is not None:
             logit_bias = logit_bias_rows(logit_bias, B)
-        key = (B, self.trace is not None, self.sliding)
+        key = (B, self.trace is not None, self.sliding) + (("shared",) if shared else ())
         dec = self._decoders.get(key)
         if dec is None or dec.ld_chord < max_chords or dec.max_prompt < max_prompt:
             # (a decoder built for prompts serves requests without one: its buffers are only longer)
             dec = ForcedDecoder(self.model, B, self.generation_length, self.memory_length, float(rows[0][0]), int(rows[1][0]),
                                 max_chords=max(64, max_chords), record_trace=self.trace is not None,
                                 top_p=float(rows[2][0]), sliding=self.sliding, kv_dtype=self.kv_dtype,
-                                max_prompt=max(max_prompt, 0 if dec is None else dec.max_prompt))
+                                max_prompt=max(max_prompt, 0 if dec is None else dec.max_prompt),
+                                **({"shared_prompt": True} if shared else {}))
             self._decoders[key] = dec
         if per_slot:
             dec.record_logprobs()
@@ -1220,8 +1360,9 @@ class BatchedGenerator:
         if prompts is not None and len(prompts) != B:
             raise CommuHipError(f"prompts: one token list per sequence expected ({B}), got {len(prompts)}")
         max_prompt = 0 if prompts is None else max(len(p) for p in prompts)
+        # (shared_prompt: requests with a prompt only -- without one there is nothing but the short context to share)
         dec = self.decoder(B, temperature, top_k, max_chords, top_p, per_slot=return_logprobs, max_prompt=max_prompt,
-                           logit_bias=logit_bias)
+                           logit_bias=logit_bias, shared=self.shared_prompt and max_prompt > 0)
         uniforms = None
         if bool((dec._sampling[0] != 0).any()):
             srcs = self.uniform_sources or [np.random.RandomState(1000 + b).random_sample for b in range(B)]
@@ -1244,7 +1385,8 @@ class BatchedGenerator:
     @torch.no_grad()
     def generate_stream(self, encoded_meta: Sequence[int], input_data, temperature, top_k, need: int,
                         accept, top_p=1.0, slots: int = 64, seed: int = 0, max_attempts: Optional[int] = None,
-                        return_logprobs: bool = False, prompt: Optional[Sequence[int]] = None, logit_bias=None):
+                        return_logprobs: bool = False, prompt: Optional[Sequence[int]] = None, logit_bias=None,
+                        share_prompt: bool = False):
         """Attempts of ONE request (the reference's `while idx != num_generate` loop, midi_inferrer.py:338-354, which tries
         one sequence after the other) decoded in up to `slots` parallel slots, CONTINUOUSLY: a slot whose sequence has
         ended is handed to `accept(sequence, report) -> bool` and re-armed with the next attempt while the other slots keep
@@ -1257,8 +1399,14 @@ class BatchedGenerator:
         value, the log-probability arrays (ForcedDecoder.logprobs) of the returned attempts in the same order.
         prompt: a token list every attempt of the request continues (primed slots, ForcedDecoder.load; a re-armed slot
         returns to the primed state).
-        logit_bias: one constraint row (token_constraints) for every attempt of the request."""
+        logit_bias: one constraint row (token_constraints) for every attempt of the request.
+        share_prompt (opt-in; also on with BatchedGenerator(shared_prompt=True) when a prompt is given): the K/V of the
+        context and the prompt are computed and held once for all slots (ForcedDecoder(shared_prompt=True)); the attempts
+        returned are the ones the unshared decoder defines, up to the summation order of the attention."""
         B = max(1, min(int(slots), int(need)))
+        if share_prompt and not prompt:
+            raise CommuHipError("share_prompt: there is no prompt to share (prompt= is empty)")
+        share = bool(prompt) and (bool(share_prompt) or self.shared_prompt)
         if logit_bias is not None and np.ndim(logit_bias) != 1:
             raise CommuHipError(f"logit_bias: one row for the request expected, got shape {np.shape(logit_bias)}")
         max_chords = len(input_data.chord_token_components["chord_token"])
@@ -1273,7 +1421,7 @@ class BatchedGenerator:
         varying = any(bool((c != c[0]).any()) for c in sched)          # (one triple for every attempt: nothing to re-arm)
         dec = self.decoder(B, [t[0] for t in first], [t[1] for t in first], max_chords, [t[2] for t in first],
                            per_slot=return_logprobs or varying, max_prompt=0 if prompt is None else len(prompt),
-                           logit_bias=logit_bias)
+                           logit_bias=logit_bias, shared=share)
         started = B
         sampled = bool((sched[0] != 0).any())          # (a greedy attempt reads no variate)
         uni = np.stack([self.attempt_uniforms(seed, a, dec.ld_u) for a in range(B)]) if sampled else None
@@ -1292,7 +1440,7 @@ class BatchedGenerator:
             dec.poll_submit()                  # the records after the window just queued ...
             dec.run_iterations(dec.POLL, self.use_graph, klen_bound=kb, live_rows=nlive)      # ... are read while the next window runs
             fsm = dec.poll_result()
-            kb = int(fsm[:, 0].max()) + 3 * dec.POLL
+            kb = int(fsm[:, 0].max()) + 3 * dec.POLL - (dec.prefix_P if dec.shared_prompt else 0)      # (private rows)
             nlive = sum(1 for b_ in range(B) if slot_attempt[b_] >= 0 and not fsm[b_, 5]) + 1
             for b in range(B):
                 a = slot_attempt[b]

@@ -21,10 +21,12 @@ from .midi_inferrer import InferenceTask
 
 class TokenGenerationPipeline:
     def __init__(self, model, device: torch.device, generation_length: int = 4096, memory_length: int = 4146,
-                 sliding: bool = False, kv_dtype: str = "bf16"):
+                 sliding: bool = False, kv_dtype: str = "bf16", shared_prompt: bool = False):
         """sliding: decode with the reference's sliding memory window (model.py:507-538), so that generation_length may
-        exceed memory_length.  kv_dtype: "bf16", or "fp8" for the opt-in e4m3 K/V cache (generate.DecodeState)."""
+        exceed memory_length.  kv_dtype: "bf16", or "fp8" for the opt-in e4m3 K/V cache (generate.DecodeState).
+        shared_prompt: requests with a prompt hold its K/V once for all slots (generate.ForcedDecoder(shared_prompt=True))."""
         self.kv_dtype = kv_dtype
+        self.shared_prompt = bool(shared_prompt)
         self.model, self.device = model, device
         self.generation_length, self.memory_length = generation_length, memory_length
         self.sliding = bool(sliding)
@@ -45,7 +47,7 @@ class TokenGenerationPipeline:
         data = self.preprocess_task.input_data
         checker = InferenceTask(self.device)                            # only its validator is used here
         gen = BatchedGenerator(self.model, self.device, self.generation_length, self.memory_length, sliding=self.sliding,
-                               kv_dtype=self.kv_dtype)
+                               kv_dtype=self.kv_dtype, **({"shared_prompt": True} if self.shared_prompt else {}))
 
         def accept(seq, teacher) -> bool:
             self.attempts += 1

@@ -102,7 +102,10 @@ class InferenceTask:
         sliding = bool(getattr(self.inference_cfg.GENERATION, "sliding_memory", False))
         # (likewise: generate.py --kv_cache)
         kv_dtype = str(getattr(self.inference_cfg.GENERATION, "kv_cache", "bf16"))
-        gen = BatchedGenerator(self.model, self.device, glen, mlen, sliding=sliding, kv_dtype=kv_dtype)
+        # (likewise: generate.py --share_prompt; it takes effect for requests with a prompt)
+        share = bool(getattr(self.inference_cfg.GENERATION, "share_prompt", False))
+        gen = BatchedGenerator(self.model, self.device, glen, mlen, sliding=sliding, kv_dtype=kv_dtype,
+                               **({"shared_prompt": True} if share else {}))
 
         def accept(seq, rep) -> bool:
             self.attempts += 1

@@ -48,6 +48,9 @@ class ModelInitializeTask:
         # generate.py --kv_cache (not in the reference): storage of the decode step's K/V cache, "bf16" or "fp8"
         if getattr(self.model_args, "kv_cache", None) not in (None, "bf16"):
             cfg.GENERATION.kv_cache = str(self.model_args.kv_cache)
+        # generate.py --share_prompt (not in the reference): one K/V copy of the prompt for all decode slots
+        if getattr(self.model_args, "share_prompt", False):
+            cfg.GENERATION.share_prompt = True
         cfg.freeze()
         return cfg
 

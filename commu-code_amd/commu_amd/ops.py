@@ -1435,3 +1435,74 @@ def decode_prefill_scatter_kv8(qkv, T, kc8, vc8, ks, vs, klen, lens, slots=None,
         raise CommuHipError("qkv: a row stride that is a multiple of 8 expected")
     call("commu_decode_prefill_scatter_kv8", _p(qkv), qkv.stride(0), T, B, _p(kc8), _p(vc8), _p(ks), _p(vs), _p(klen),
          _p(lens), _p(slots), Bc, H, DH, Lmax, window, _s())
+
+
+# ---------------------------------------------------------------------------------------------- shared prompt prefix (opt-in)
+# (include/commu_hip.h, commu_decode_attn_prefix: the K/V of the positions all slots have in common, held once)
+def decode_prefix_chunk() -> int:
+    """Prefix rows per chunk (one record per (pair, chunk)) of commu_decode_attn_prefix."""
+    return int(call("commu_decode_prefix_chunk"))
+
+
+def decode_prefix_group() -> int:
+    """Slots that one prefix workgroup of commu_decode_attn_prefix serves from its staged chunk."""
+    return int(call("commu_decode_prefix_group"))
+
+
+def decode_prefix_ws_floats(B, H, DH, Pcap, nsplit=1) -> int:
+    """fp32 words of the record workspace of decode_attn_prefix: B H (nsplit + ceil(Pcap / chunk)) (DH + 2)."""
+    return B * H * (int(nsplit) + -(-int(Pcap) // decode_prefix_chunk())) * (DH + 2)
+
+
+def decode_attn_prefix(qkv, pk, pv, prefix_len, kc, vc, rd, u, vb, klen, active, out, scale, ws, cnt, append=True, nsplit=1):
+    """Cached single-token attention over a shared prefix and private rows (commu_decode_attn_prefix): pk / pv bf16
+    [H, Pcap, DH] with prefix_len (int32 [1], on the GPU) valid rows; kc / vc bf16 [B, H, Lp, DH] private rows (row r =
+    absolute position prefix_len + r), klen int32 [B] private rows per slot; qkv bf16 [B, >= 3 H DH], rd bf16
+    [>= Pcap + Lp, >= H DH], out bf16 [B, >= H DH]; ws fp32 [>= decode_prefix_ws_floats(...)], cnt int32 [>= B H] zeroed
+    once (every launch leaves it zero).  nsplit > 1 splits the PRIVATE keys as decode_attn's split-key launch does."""
+    for t, name in ((qkv, "qkv"), (pk, "pk"), (pv, "pv"), (prefix_len, "prefix_len"), (kc, "kc"), (vc, "vc"), (rd, "rd"),
+                    (out, "out"), (u, "r_w_bias"), (vb, "r_r_bias"), (klen, "klen"), (ws, "ws"), (cnt, "cnt")) \
+            + (() if active is None else ((active, "active"),)):
+        if not t.is_cuda:
+            raise CommuHipError(f"{name}: commu_amd kernels need GPU tensors (no CPU fallback)")
+    if kc.dtype != BF16 or kc.dim() != 4 or not kc.is_contiguous() or vc.dtype != BF16 or vc.shape != kc.shape \
+            or not vc.is_contiguous():
+        raise CommuHipError("kc / vc: two contiguous bf16 caches [B, H, Lp, DH] expected")
+    B, H, Lp, DH = kc.shape
+    if DH not in (32, 64):
+        raise CommuHipError(f"d_head {DH}: the decode caches are built for 32 and 64 (pad the model's head)")
+    if pk.dtype != BF16 or pk.dim() != 3 or pk.shape[0] != H or pk.shape[2] != DH or not pk.is_contiguous() \
+            or pv.dtype != BF16 or pv.shape != pk.shape or not pv.is_contiguous():
+        raise CommuHipError(f"pk / pv: two contiguous bf16 prefixes [{H}, Pcap, {DH}] expected")
+    Pcap = pk.shape[1]
+    if Lp < 1 or Pcap < 1 or Pcap + Lp > RING_MAX_ROWS:
+        raise CommuHipError(f"prefix of {Pcap} and private cache of {Lp} positions; together the decode attention supports "
+                            f"{RING_MAX_ROWS}")
+    HD = H * DH
+    if prefix_len.dtype != torch.int32 or prefix_len.numel() != 1:
+        raise CommuHipError("prefix_len: int32 [1] expected")
+    if klen.dtype != torch.int32 or klen.numel() != B or not klen.is_contiguous():
+        raise CommuHipError(f"klen: contiguous int32 [{B}] expected")
+    if active is not None and (active.dtype != torch.uint8 or active.numel() != B or not active.is_contiguous()):
+        raise CommuHipError(f"active: contiguous uint8 [{B}] expected")
+    if qkv.dtype != BF16 or qkv.dim() != 2 or qkv.shape[0] != B or qkv.shape[1] < 3 * HD or qkv.stride(1) != 1 \
+            or qkv.stride(0) % 8:
+        raise CommuHipError(f"qkv: bf16 [{B}, >= {3 * HD}] with a row stride that is a multiple of 8 expected")
+    if rd.dtype != BF16 or rd.dim() != 2 or rd.shape[0] < Pcap + Lp or rd.shape[1] < HD or rd.stride(1) != 1 \
+            or rd.stride(0) % 8:
+        raise CommuHipError(f"rd: bf16 [>= {Pcap + Lp}, >= {HD}] with a row stride that is a multiple of 8 expected")
+    if out.dtype != BF16 or out.dim() != 2 or out.shape[0] != B or out.shape[1] < HD or out.stride(1) != 1:
+        raise CommuHipError(f"out: bf16 [{B}, >= {HD}] expected")
+    for t, name in ((u, "r_w_bias"), (vb, "r_r_bias")):
+        if t.dtype != F32 or t.numel() < HD or not t.is_contiguous():
+            raise CommuHipError(f"{name}: contiguous fp32 [>= {HD}] expected")
+    nsplit = int(nsplit)
+    if nsplit < 1 or nsplit > 16:
+        raise CommuHipError("nsplit: 1 .. 16")
+    if ws.dtype != F32 or ws.numel() < decode_prefix_ws_floats(B, H, DH, Pcap, nsplit) or not ws.is_contiguous() \
+            or cnt.dtype != torch.int32 or cnt.numel() < B * H or not cnt.is_contiguous():
+        raise CommuHipError("ws: fp32 [>= B H (nsplit + ceil(Pcap / chunk)) (DH + 2)], cnt: int32 [>= B H]")
+    call("commu_decode_attn_prefix", _p(qkv), qkv.stride(0), _p(pk), _p(pv), _p(prefix_len), Pcap, _p(kc), _p(vc), _p(rd),
+         rd.stride(0), _p(u), _p(vb), _p(klen), _p(active), _p(out), out.stride(0), B, H, DH, Lp, float(scale),
+         1 if append else 0, nsplit, _p(ws), _p(cnt), _s())
+    return out

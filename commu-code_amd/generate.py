@@ -42,6 +42,10 @@ def parse_args():
     # per 32 features, 0.516 of the bf16 cache's bytes; it rounds the cached K and V (accuracy-bounded, no parity claim:
     # INTEGRATION.md) and is refused together with --parity.
     model_arg_parser.add_argument("--kv_cache", type=str, choices=["bf16", "fp8"], default="bf16")
+    # not in the reference: with --prompt_tokens every attempt continues the same opening; hold the K/V of the meta tokens
+    # and the prompt ONCE for all decode slots instead of once per slot (the same attention, another summation order).
+    # bf16 linear cache only: refused without --prompt_tokens and with --sliding_memory, --kv_cache fp8 or --parity.
+    model_arg_parser.add_argument("--share_prompt", action="store_true")
     input_arg_parser.add_argument("--output_dir", type=str, required=True)
     input_arg_parser.add_argument("--bpm", type=int)
     input_arg_parser.add_argument("--audio_key", type=str, choices=list(meta.KEY_MAP.keys()))
@@ -93,6 +97,20 @@ def read_prompt_tokens(path):
     return doc
 
 
+def check_share_prompt(model_args, input_args):
+    """--share_prompt against the options it cannot be combined with (host code only; ValueError with the reason)."""
+    if not getattr(model_args, "share_prompt", False):
+        return
+    if not getattr(input_args, "prompt_tokens", None):
+        raise ValueError("--share_prompt needs --prompt_tokens: without a prompt there is nothing to share")
+    for flag, on in (("--sliding_memory", bool(getattr(model_args, "sliding_memory", False))),
+                     ("--kv_cache fp8", getattr(model_args, "kv_cache", "bf16") == "fp8"),
+                     ("--parity", bool(getattr(model_args, "parity", False)))):
+        if on:
+            raise ValueError(f"--share_prompt cannot be combined with {flag}: the shared prompt prefix is built for the "
+                             "bf16 linear K/V cache only")
+
+
 def read_constraints(path=None, pitch_min=None, pitch_max=None):
     """The constraint row of --logit_bias / --pitch_min / --pitch_max (None when none of them is given); host code only,
     raises (commu_amd.generate.CommuHipError, ValueError) on a malformed file or an empty range."""
@@ -123,6 +141,7 @@ def main(model_args, input_args, training_cfg=None, device_indices=None):
     device order.  --gpus 1 (or one visible device) keeps everything in this process.  `device_indices` (tests):
     explicit device of every replica, e.g. [0, 0] = two replica processes on the one GPU of a test box."""
     import torch
+    check_share_prompt(model_args, input_args)          # (refused before a model is loaded or a replica started)
     in_args = dict(vars(input_args))
     max_rounds = in_args.pop("max_rounds", None)
     gpus = in_args.pop("gpus", None)

@@ -519,6 +519,24 @@ int commu_decode_attn_kv8(const void* qkv, int ld_qkv, void* kc8, void* vc8, voi
 int commu_decode_prefill_scatter_kv8(const void* qkv, int ld_qkv, int T, int B, void* kc8, void* vc8, void* ks, void* vs,
                                      int* klen, const int* len, const int* slot, int Bcache, int H, int DH, int Lmax,
                                      int window, hipStream_t stream);
+/* The cached decode attention with a SHARED PROMPT PREFIX (csrc/decode_prefix.hip; opt-in, bf16 linear cache only).
+ *   pk / pv:    bf16 [H][Pcap][DH], the K / V of the positions every slot has in common, held once; *prefix_len = P of
+ *               them are valid (a device word the kernel reads: nothing of P is baked into a launch);
+ *   kc / vc:    bf16 [B][H][Lp][DH], the private rows: row r of slot b is absolute position P + r; klen[b] counts
+ *               private rows only, the new token is appended to private row klen[b] (append 1);
+ *   rd:         the distance table, at least Pcap + Lp rows (Pcap + Lp <= 4224).
+ * An active pair (b, h) attends to prefix rows 0 .. P-1 of head h and private rows 0 .. klen[b] of (b, h), the key of
+ * absolute position p at distance P + klen[b] - p: commu_decode_attn over a cache that holds the prefix in every slot.
+ * ws: fp32 [B H (nsplit + ceil(Pcap / chunk)) (DH + 2)] records, cnt: [B H] arrival counters, ZERO on entry (the launch
+ * leaves them zero); nsplit 1 .. 16 splits the private keys as commu_decode_attn_split does.  Rows of inactive slots are
+ * not written.  DH 64 or 32.  commu_decode_prefix_chunk / _group: prefix rows per chunk, slots per prefix workgroup. */
+int commu_decode_prefix_chunk(void);
+int commu_decode_prefix_group(void);
+int commu_decode_attn_prefix(const void* qkv, int ld_qkv, const void* pk, const void* pv, const int* prefix_len, int Pcap,
+                             void* kcache, void* vcache, const void* rd, int ld_rd, const float* r_w_bias,
+                             const float* r_r_bias, const int* klen, const unsigned char* active, void* out, int ld_o,
+                             int B, int H, int DH, int Lp, float scale, int append, int nsplit, float* ws, unsigned* cnt,
+                             hipStream_t stream);
 /* Everything of a decode-step layer that follows its attention, as ONE launch (csrc/decode_tail.hip):
  *   z1 = vec . Wo^T + h;  a = LN1(z1);  hid = relu(a . W1^T + b1);  z2 = hid . W2^T + b2 + a;  h_out = LN2(z2)
  *   (o_net + residual + LayerNorm model.py:344-352, PositionwiseFF model.py:163-179)
