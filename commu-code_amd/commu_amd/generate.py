@@ -292,7 +292,7 @@ class DecodeState:
         # (the logits launch takes 512 < V <= 1024 only: other vocabularies use the per-Linear launches)
         self.tail_ok = bool(call("commu_decode_tail_supported", B, D, DI, HD)) and L > 0 and 512 < model.n_token <= 1024
         if self.tail_ok:
-            nw = call("commu_decode_tail_sync_words")
+            nw = call("commu_decode_tail_sync_words_for", B)          # (B <= 64: commu_decode_tail_sync_words())
             self.t_z1 = torch.zeros(L, B, D, device=dev, dtype=BF16)
             self.t_hid = torch.zeros(L, B, DI, device=dev, dtype=BF16)
             self.t_z2 = torch.zeros(L, B, D, device=dev, dtype=BF16)

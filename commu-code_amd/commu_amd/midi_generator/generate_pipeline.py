@@ -21,10 +21,13 @@ from .midi_inferrer import InferenceTask
 
 class TokenGenerationPipeline:
     def __init__(self, model, device: torch.device, generation_length: int = 4096, memory_length: int = 4146,
-                 sliding: bool = False, kv_dtype: str = "bf16", shared_prompt: bool = False):
+                 sliding: bool = False, kv_dtype: str = "bf16", shared_prompt: bool = False, decode_slots: int = 64):
         """sliding: decode with the reference's sliding memory window (model.py:507-538), so that generation_length may
         exceed memory_length.  kv_dtype: "bf16", or "fp8" for the opt-in e4m3 K/V cache (generate.DecodeState).
-        shared_prompt: requests with a prompt hold its K/V once for all slots (generate.ForcedDecoder(shared_prompt=True))."""
+        shared_prompt: requests with a prompt hold its K/V once for all slots (generate.ForcedDecoder(shared_prompt=True)).
+        decode_slots: attempts decoded side by side (BatchedGenerator.generate_stream(slots=)); the sequences returned do not
+        depend on it."""
+        self.decode_slots = int(decode_slots)
         self.kv_dtype = kv_dtype
         self.shared_prompt = bool(shared_prompt)
         self.model, self.device = model, device
@@ -66,5 +69,6 @@ class TokenGenerationPipeline:
         out, _ = gen.generate_stream(encoded_meta, data, data.temperature, data.top_k, data.num_generate, accept,
                                      top_p=getattr(data, "top_p", 1.0), seed=uniform_seed,
                                      max_attempts=None if max_rounds is None else max_rounds * data.num_generate,
-                                     prompt=None if not prompt else list(prompt), logit_bias=logit_bias)
+                                     prompt=None if not prompt else list(prompt), logit_bias=logit_bias,
+                                     **({} if self.decode_slots == 64 else {"slots": self.decode_slots}))
         return out

@@ -104,6 +104,8 @@ class InferenceTask:
         kv_dtype = str(getattr(self.inference_cfg.GENERATION, "kv_cache", "bf16"))
         # (likewise: generate.py --share_prompt; it takes effect for requests with a prompt)
         share = bool(getattr(self.inference_cfg.GENERATION, "share_prompt", False))
+        # (likewise: generate.py --decode_slots)
+        slots = int(getattr(self.inference_cfg.GENERATION, "decode_slots", 64))
         gen = BatchedGenerator(self.model, self.device, glen, mlen, sliding=sliding, kv_dtype=kv_dtype,
                                **({"shared_prompt": True} if share else {}))
 
@@ -116,11 +118,11 @@ class InferenceTask:
             except Exception:
                 return False
             return self.validate_generated_sequence(seq)
-        # attempts decoded in up to 64 slots, a finished slot re-armed with the next attempt (the reference tries one
+        # attempts decoded in up to `slots` (64) slots, a finished slot re-armed with the next attempt (the reference tries one
         # sequence after the other until num_generate passed; `max_rounds` bounds the attempts at max_rounds x num_generate)
         res = gen.generate_stream(list(encoded_meta), data, data.temperature, data.top_k, data.num_generate, accept,
                                   top_p=getattr(data, "top_p", 1.0), seed=self.uniform_seed,
                                   max_attempts=None if max_rounds is None else max_rounds * data.num_generate,
                                   return_logprobs=return_logprobs, prompt=None if not prompt else list(prompt),
-                                  logit_bias=logit_bias)
+                                  logit_bias=logit_bias, **({} if slots == 64 else {"slots": slots}))
         return (res[0], res[2]) if return_logprobs else res[0]

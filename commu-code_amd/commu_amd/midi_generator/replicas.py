@@ -24,7 +24,8 @@ def generate_on_device(model_args, in_args, device_index, num_generate, uniform_
     """One replica: checkpoint -> model on cuda:<device_index>, `num_generate` validated sequences (logprobs: and their
     log-probabilities as logprobs_to_lists gives them, a third value).  prompt: token ids every sequence continues.
     logit_bias: a constraint row (generate.token_constraints, a numpy array) on what every sequence may draw.
-    model_args carries the decode options of every replica (--parity, --sliding_memory, --kv_cache, --share_prompt, ...): they reach
+    model_args carries the decode options of every replica (--parity, --sliding_memory, --kv_cache, --share_prompt,
+    --decode_slots, ...): they reach
     the generator through the inference configuration that ModelInitializeTask builds."""
     import copy
 

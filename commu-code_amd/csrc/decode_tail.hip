@@ -42,6 +42,29 @@ constexpr int NGRP = 32;             // column groups (= workgroups) per row gro
 constexpr unsigned SPIN_LIMIT = 1u << 17;
 constexpr int CNT_STRIDE = 64;       // words between two arrival counters
 
+// ---- how many sequences one launch takes.  A row group (16 sequences) is NGRP workgroups that wait for each other, so a
+// launch whose workgroups are all resident at once completes whatever order they were dispatched in.  The compiler's
+// resource report for this file (hipcc -O3 -Rpass-analysis=kernel-resource-usage, gfx950):
+//   decode_tail_kernel<512, 1024, 512 | 640, QKV | LOGITS>   235-237 VGPRs (no AGPRs), 106 SGPRs, 17152 B LDS, occupancy 2 waves / SIMD
+//   decode_tail_wide_kernel<1024, 2048, 1024, QKV | LOGITS>  178 VGPRs (no AGPRs),     106 SGPRs,  9472 B LDS, occupancy 2 waves / SIMD
+// A 256-thread workgroup puts one wave on each of a CU's 4 SIMDs: 2 waves / SIMD = 2 workgroups per CU (the unified register
+// file holds 512 per lane and SIMD; 106 SGPRs admit 6 workgroups and 2 x 17 KB of LDS fit 160 KB, so the registers decide).
+// 256 CUs x 2 = 512 resident workgroups = 16 row groups of 32 = 256 sequences.  __launch_bounds__(256, 2) holds the
+// kernels that take more than 64 sequences (G = 16) to that budget: an edit that needs more than 256 registers fails to
+// compile instead of halving the residency (which would strand row groups at B > 128).  Up to 64 sequences a launch is
+// 128 workgroups, which fit at one per CU: those kernels (G = 4) keep their bound and the instruction streams they had.
+// Other work on the chip (a side stream) can still delay workgroups; the bounded spins + *err cover that at any B.
+constexpr int TAIL_CUS = 256;                    // CUs of an MI355X
+constexpr int TAIL_WAVES_PER_SIMD = 2;           // the report's occupancy = 256-thread workgroups per CU
+constexpr int TAIL_ROWS = 16;                    // sequences per row group
+constexpr int TAIL_MAX_B = TAIL_ROWS * (TAIL_CUS * TAIL_WAVES_PER_SIMD) / NGRP;
+static_assert(TAIL_MAX_B == 256, "16 rows x (256 CUs x 2 workgroups per CU) / 32 column groups");
+// arrival counters [3 phases][G row groups][CNT_STRIDE]: G = 4 up to 64 sequences (the layout callers of
+// commu_decode_tail_sync_words() know), 16 beyond.  G is a template argument of the kernels, chosen per launch from B:
+// as a run-time argument it re-scheduled the B <= 64 kernels (same memory and MFMA instructions, other scalar code) and
+// the 64-slot iteration measured 0.5 % slower than before, outside the spread; as a constant those kernels are unchanged.
+__host__ __device__ constexpr int tail_groups(int B) { return B <= 64 ? 4 : TAIL_MAX_B / TAIL_ROWS; }
+
 struct TailArgs {
     const bf16* vec;  int ld_vec;           // [B][HD] attention output
     const bf16* h;    int ld_h;             // [B][D] layer input (residual of o_net)
@@ -55,7 +78,7 @@ struct TailArgs {
     bf16* h_out;      int ld_ho;            // [B][D] layer output
     void* out_n;      int ld_on;            // [B][Nn]: bf16 (qkv) or fp32 (logits)
     int B;
-    unsigned* sync;                         // [3][4][CNT_STRIDE] arrival counters of this launch, zero on entry
+    unsigned* sync;                         // [3][G][CNT_STRIDE] arrival counters of this launch, zero on entry
     unsigned* err;
     const unsigned char* active;            // (logits) rows with active[row] == 0 keep their previous logits; null: all
     // head launch (MODE_HEAD): x = E32[tok[row]] * emb_scale instead of LN2(z2); zero_words[0 .. n_zero) are cleared
@@ -213,8 +236,12 @@ __device__ __forceinline__ void store4_sc1(srd_t srd, unsigned off, f32x4 v) {
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o), srd, (int)off, 0, AUX_SC1);
 }
 
-template <int D, int DI, int HD, int MODE>
-__global__ __launch_bounds__(256) void decode_tail_kernel(TailArgs a) {
+// G: counter groups of the sync block (tail_groups(B): 4 up to 64 sequences, 16 beyond; the head launch has no counters and
+// runs the G = 4 instantiation at any B).  The G = 16 kernels are the ones that need 512 workgroups resident, so they
+// carry the register budget (see TAIL_MAX_B); the G = 4 kernels are bounded as they always were.
+template <int D, int DI, int HD, int MODE, int G>
+__global__ __launch_bounds__(256, G > 4 ? TAIL_WAVES_PER_SIMD : 1) void decode_tail_kernel(TailArgs a) {
+    constexpr int PSTRIDE = G * CNT_STRIDE;          // words between two phases' counters
     constexpr bool LOGITS = MODE == MODE_LOGITS, HEAD = MODE == MODE_HEAD;
     constexpr int KS_D = D / 128, KS_DI = DI / 128, KS_HD = HD / 128;        // 32-wide MFMA steps per wave (4 waves split K)
     constexpr int NT1 = D / 512, NT2 = DI / 512, NT3 = D / 512, NT4 = LOGITS ? 2 : (3 * HD + 511) / 512;
@@ -307,14 +334,14 @@ __global__ __launch_bounds__(256) void decode_tail_kernel(TailArgs a) {
             for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e] + bias1[e], 0.f);
             store4_sc1(make_srd(a.hid, (size_t)B * DI * 2), ((unsigned)row * DI + col) * 2u, v);
         }
-        arrive(cnt + 4 * CNT_STRIDE, w < NT2);
+        arrive(cnt + PSTRIDE, w < NT2);
         if (w < NT2) load_p3();
         stamp();
     }
     // ---------------------------------------------------------------- phase 3: z2 = hid . W2^T + b2 + a
     if (!HEAD) {
         bf16x8 xf[KS_DI];
-        wait_arrivals(cnt + 4 * CNT_STRIDE, a.err, 2u);
+        wait_arrivals(cnt + PSTRIDE, a.err, 2u);
         stamp();
         load_x<KS_DI>(xf, make_srd(a.hid, (size_t)B * DI * 2), ((unsigned)row * DI + k0i) * 2u, true);
         if (w >= NT3) load_p4();
@@ -326,7 +353,7 @@ __global__ __launch_bounds__(256) void decode_tail_kernel(TailArgs a) {
             for (int e = 0; e < 4; ++e) v[e] += bias2[e] + bf2f(ra[e]);
             store4_sc1(make_srd(a.z2, (size_t)B * D * 2), ((unsigned)row * D + col) * 2u, v);
         }
-        arrive(cnt + 8 * CNT_STRIDE, w < NT3);
+        arrive(cnt + 2 * PSTRIDE, w < NT3);
         if (w < NT3) load_p4();
         stamp();
     }
@@ -352,7 +379,7 @@ __global__ __launch_bounds__(256) void decode_tail_kernel(TailArgs a) {
                 }
             }
         } else {
-            wait_arrivals(cnt + 8 * CNT_STRIDE, a.err, 3u);
+            wait_arrivals(cnt + 2 * PSTRIDE, a.err, 3u);
             stamp();
             load_x<KS_D>(xf, make_srd(a.z2, (size_t)B * D * 2), ((unsigned)row * D + k0d) * 2u, true);
             layer_norm<KS_D>(xf, gm2, bt2, a.d_ln, a.eps2, st, w, r16, g, k0d);
@@ -463,8 +490,9 @@ __device__ __forceinline__ void wide_phase(const bf16* __restrict__ Wp, const bf
     }
 }
 
-template <int D, int DI, int HD, int MODE>
-__global__ __launch_bounds__(256) void decode_tail_wide_kernel(TailArgs a) {
+template <int D, int DI, int HD, int MODE, int G>
+__global__ __launch_bounds__(256, G > 4 ? TAIL_WAVES_PER_SIMD : 1) void decode_tail_wide_kernel(TailArgs a) {
+    constexpr int PSTRIDE = G * CNT_STRIDE;
     constexpr bool LOGITS = MODE == MODE_LOGITS, HEAD = MODE == MODE_HEAD;
     constexpr int KS_D = D / 128, KS_DI = DI / 128, KS_HD = HD / 128;
     constexpr int NT1 = D / 512, NT2 = DI / 512, NT3 = D / 512, NT4 = LOGITS ? 2 : (3 * HD + 511) / 512;
@@ -528,12 +556,12 @@ __global__ __launch_bounds__(256) void decode_tail_wide_kernel(TailArgs a) {
                 store4_sc1(shid, ((unsigned)row * DI + col) * 2u, v);
             }
         });
-        arrive(cnt + 4 * CNT_STRIDE, w < 2);
+        arrive(cnt + PSTRIDE, w < 2);
     }
     // ---------------------------------------------------------------- phase 3: z2 = hid . W2^T + b2 + a
     if (!HEAD) {
         bf16x8 xf[KS_DI];
-        wait_arrivals(cnt + 4 * CNT_STRIDE, a.err, 2u);
+        wait_arrivals(cnt + PSTRIDE, a.err, 2u);
         load_x<KS_DI>(xf, make_srd(a.hid, (size_t)B * DI * 2), ((unsigned)row * DI + k0i) * 2u, true);
         const srd_t sz2 = make_srd(a.z2, (size_t)B * D * 2);
         wide_phase<KS_DI, NT3>(a.W2, xf, red, ng, w, lane, [&](int t, f32x4 v) {
@@ -546,7 +574,7 @@ __global__ __launch_bounds__(256) void decode_tail_wide_kernel(TailArgs a) {
                 store4_sc1(sz2, ((unsigned)row * D + col) * 2u, v);
             }
         });
-        arrive(cnt + 8 * CNT_STRIDE, w < 2);
+        arrive(cnt + 2 * PSTRIDE, w < 2);
     }
     // ---------------------------------------------------------------- phase 4: h' = LN2(z2); out = h' . Wn^T (+ bn)
     {
@@ -568,7 +596,7 @@ __global__ __launch_bounds__(256) void decode_tail_wide_kernel(TailArgs a) {
                 }
             }
         } else {
-            wait_arrivals(cnt + 8 * CNT_STRIDE, a.err, 3u);
+            wait_arrivals(cnt + 2 * PSTRIDE, a.err, 3u);
             load_x<KS_D>(xf, make_srd(a.z2, (size_t)B * D * 2), ((unsigned)row * D + k0d) * 2u, true);
             layer_norm_wide<KS_D>(xf, a.g2, a.be2, a.d_ln, a.eps2, st, w, r16, g, k0d);
         }
@@ -603,19 +631,24 @@ __global__ __launch_bounds__(256) void decode_tail_wide_kernel(TailArgs a) {
 }  // namespace
 
 extern "C" int commu_decode_tail_supported(int B, int D, int DI, int HD) {
-    if (B < 1 || B > 64) return 0;
+    if (B < 1 || B > TAIL_MAX_B) return 0;
     if (D == 512 && DI == 1024 && (HD == 512 || HD == 640)) return 1;
     if (D == 1024 && DI == 2048 && HD == 1024) return 1;          // decode_tail_wide_kernel
     return 0;
 }
 
-extern "C" int commu_decode_tail_sync_words(void) { return 12 * CNT_STRIDE; }
+extern "C" int commu_decode_tail_sync_words(void) { return 3 * tail_groups(64) * CNT_STRIDE; }
+
+extern "C" int commu_decode_tail_sync_words_for(int B) {
+    if (B < 1 || B > TAIL_MAX_B) return 0;
+    return 3 * tail_groups(B) * CNT_STRIDE;
+}
 
 static unsigned long long* g_tail_trace = nullptr;
-static TailArgs tail_args_zero() {
+static TailArgs tail_args_zero(int B) {
     TailArgs a;
     memset(&a, 0, sizeof(a));
-    a.trace = g_tail_trace;
+    a.trace = B <= 64 ? g_tail_trace : nullptr;          // (the trace buffer has 128 workgroups' rows)
     return a;
 }
 /* diagnostics: every following layer-tail / head launch writes the 100 MHz timestamps of its phase boundaries to
@@ -657,7 +690,7 @@ extern "C" int commu_decode_layer_tail(const void* vec, int ld_vec, const void* 
     // (the LOGITS kernels walk 2 column tiles per workgroup, and commu_decode_tail_pack lays out ceil(ceil(Nn / 16) / 32) of
     //  them: for Nn <= 512 that is 1, and workgroups ng >= 16 would read past the packed copy)
     if (logits ? (Nn <= 512 || Nn > 1024 || bn == nullptr) : (Nn != 3 * HD)) return -22;
-    TailArgs a = tail_args_zero();
+    TailArgs a = tail_args_zero(B);
     a.vec = (const bf16*)vec; a.ld_vec = ld_vec;
     a.h = (const bf16*)h; a.ld_h = ld_h;
     a.Wo = (const bf16*)Wo_packed; a.W1 = (const bf16*)W1_packed; a.W2 = (const bf16*)W2_packed;
@@ -670,15 +703,26 @@ extern "C" int commu_decode_layer_tail(const void* vec, int ld_vec, const void* 
     a.out_n = out_n; a.ld_on = ld_on;
     a.B = B; a.sync = sync; a.err = err; a.active = active;
     const dim3 grid(NGRP * ((B + 15) / 16));
-    if (D == 1024) {
-        if (logits) COMMU_LAUNCH((decode_tail_wide_kernel<1024, 2048, 1024, MODE_LOGITS>), grid, dim3(256), 0, stream, a);
-        else COMMU_LAUNCH((decode_tail_wide_kernel<1024, 2048, 1024, MODE_QKV>), grid, dim3(256), 0, stream, a);
+    if (B > 64) {          // sixteen counter groups (tail_groups)
+        if (D == 1024) {
+            if (logits) COMMU_LAUNCH((decode_tail_wide_kernel<1024, 2048, 1024, MODE_LOGITS, 16>), grid, dim3(256), 0, stream, a);
+            else COMMU_LAUNCH((decode_tail_wide_kernel<1024, 2048, 1024, MODE_QKV, 16>), grid, dim3(256), 0, stream, a);
+        } else if (HD == 512) {
+            if (logits) COMMU_LAUNCH((decode_tail_kernel<512, 1024, 512, MODE_LOGITS, 16>), grid, dim3(256), 0, stream, a);
+            else COMMU_LAUNCH((decode_tail_kernel<512, 1024, 512, MODE_QKV, 16>), grid, dim3(256), 0, stream, a);
+        } else {
+            if (logits) COMMU_LAUNCH((decode_tail_kernel<512, 1024, 640, MODE_LOGITS, 16>), grid, dim3(256), 0, stream, a);
+            else COMMU_LAUNCH((decode_tail_kernel<512, 1024, 640, MODE_QKV, 16>), grid, dim3(256), 0, stream, a);
+        }
+    } else if (D == 1024) {
+        if (logits) COMMU_LAUNCH((decode_tail_wide_kernel<1024, 2048, 1024, MODE_LOGITS, 4>), grid, dim3(256), 0, stream, a);
+        else COMMU_LAUNCH((decode_tail_wide_kernel<1024, 2048, 1024, MODE_QKV, 4>), grid, dim3(256), 0, stream, a);
     } else if (HD == 512) {
-        if (logits) COMMU_LAUNCH((decode_tail_kernel<512, 1024, 512, MODE_LOGITS>), grid, dim3(256), 0, stream, a);
-        else COMMU_LAUNCH((decode_tail_kernel<512, 1024, 512, MODE_QKV>), grid, dim3(256), 0, stream, a);
+        if (logits) COMMU_LAUNCH((decode_tail_kernel<512, 1024, 512, MODE_LOGITS, 4>), grid, dim3(256), 0, stream, a);
+        else COMMU_LAUNCH((decode_tail_kernel<512, 1024, 512, MODE_QKV, 4>), grid, dim3(256), 0, stream, a);
     } else {          // 10 heads x 64: the released default config (d_model 500, 10 x 50) after zero padding
-        if (logits) COMMU_LAUNCH((decode_tail_kernel<512, 1024, 640, MODE_LOGITS>), grid, dim3(256), 0, stream, a);
-        else COMMU_LAUNCH((decode_tail_kernel<512, 1024, 640, MODE_QKV>), grid, dim3(256), 0, stream, a);
+        if (logits) COMMU_LAUNCH((decode_tail_kernel<512, 1024, 640, MODE_LOGITS, 4>), grid, dim3(256), 0, stream, a);
+        else COMMU_LAUNCH((decode_tail_kernel<512, 1024, 640, MODE_QKV, 4>), grid, dim3(256), 0, stream, a);
     }
     COMMU_LAUNCH_CHECK();
     return 0;
@@ -689,16 +733,16 @@ extern "C" int commu_decode_head(const int64_t* tok, const float* E, int d_true,
                                  int DI, int HD, unsigned* zero_words, int n_zero, hipStream_t stream) {
     if (!commu_decode_tail_supported(B, D, DI, HD)) return -22;
     if (d_true <= 0 || d_true > D || (d_true % 4) || (ld_ho % 8) || (ld_qkv % 4) || h_out == nullptr) return -22;
-    TailArgs a = tail_args_zero();
+    TailArgs a = tail_args_zero(B);
     a.tok = tok; a.E32 = E; a.d_true = d_true; a.V = V; a.emb_scale = scale;
     a.Wn = (const bf16*)Wqkv_packed; a.Nn = 3 * HD;
     a.h_out = (bf16*)h_out; a.ld_ho = ld_ho;
     a.out_n = qkv; a.ld_on = ld_qkv;
     a.B = B; a.zero_words = zero_words; a.n_zero = zero_words != nullptr ? n_zero : 0;
     const dim3 grid(NGRP * ((B + 15) / 16));
-    if (D == 1024) COMMU_LAUNCH((decode_tail_wide_kernel<1024, 2048, 1024, MODE_HEAD>), grid, dim3(256), 0, stream, a);
-    else if (HD == 512) COMMU_LAUNCH((decode_tail_kernel<512, 1024, 512, MODE_HEAD>), grid, dim3(256), 0, stream, a);
-    else COMMU_LAUNCH((decode_tail_kernel<512, 1024, 640, MODE_HEAD>), grid, dim3(256), 0, stream, a);
+    if (D == 1024) COMMU_LAUNCH((decode_tail_wide_kernel<1024, 2048, 1024, MODE_HEAD, 4>), grid, dim3(256), 0, stream, a);
+    else if (HD == 512) COMMU_LAUNCH((decode_tail_kernel<512, 1024, 512, MODE_HEAD, 4>), grid, dim3(256), 0, stream, a);
+    else COMMU_LAUNCH((decode_tail_kernel<512, 1024, 640, MODE_HEAD, 4>), grid, dim3(256), 0, stream, a);
     COMMU_LAUNCH_CHECK();
     return 0;
 }

@@ -19,6 +19,8 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+DECODE_SLOTS_MIN, DECODE_SLOTS_MAX, DECODE_SLOTS_DEFAULT = 1, 256, 64          # --decode_slots
+
 
 def parse_args():
     from commu_amd.midi_generator import meta
@@ -46,6 +48,11 @@ def parse_args():
     # and the prompt ONCE for all decode slots instead of once per slot (the same attention, another summation order).
     # bf16 linear cache only: refused without --prompt_tokens and with --sliding_memory, --kv_cache fp8 or --parity.
     model_arg_parser.add_argument("--share_prompt", action="store_true")
+    # not in the reference (which decodes one sequence at a time): how many attempts are decoded side by side.  1 .. 256;
+    # up to 256 slots run the fused layer-tail launches ("Supported shapes").  The sequences returned do
+    # not depend on it.  (checked by check_decode_slots: the range is named in its message)
+    model_arg_parser.add_argument("--decode_slots", default=DECODE_SLOTS_DEFAULT,
+                                  help=f"parallel decode slots, {DECODE_SLOTS_MIN} .. {DECODE_SLOTS_MAX} (default: %(default)s)")
     input_arg_parser.add_argument("--output_dir", type=str, required=True)
     input_arg_parser.add_argument("--bpm", type=int)
     input_arg_parser.add_argument("--audio_key", type=str, choices=list(meta.KEY_MAP.keys()))
@@ -111,6 +118,20 @@ def check_share_prompt(model_args, input_args):
                              "bf16 linear K/V cache only")
 
 
+def check_decode_slots(model_args):
+    """--decode_slots as an int in [1, 256] (host code only; ValueError that names the range).  Also written back to
+    model_args, so that what travels to the replicas is the checked number."""
+    v = getattr(model_args, "decode_slots", DECODE_SLOTS_DEFAULT)
+    try:
+        n = int(v) if not isinstance(v, (bool, float)) else None
+    except (TypeError, ValueError):
+        n = None
+    if n is None or not DECODE_SLOTS_MIN <= n <= DECODE_SLOTS_MAX:
+        raise ValueError(f"--decode_slots: an integer in [{DECODE_SLOTS_MIN}, {DECODE_SLOTS_MAX}] expected, got {v!r}")
+    model_args.decode_slots = n
+    return n
+
+
 def read_constraints(path=None, pitch_min=None, pitch_max=None):
     """The constraint row of --logit_bias / --pitch_min / --pitch_max (None when none of them is given); host code only,
     raises (commu_amd.generate.CommuHipError, ValueError) on a malformed file or an empty range."""
@@ -142,6 +163,7 @@ def main(model_args, input_args, training_cfg=None, device_indices=None):
     explicit device of every replica, e.g. [0, 0] = two replica processes on the one GPU of a test box."""
     import torch
     check_share_prompt(model_args, input_args)          # (refused before a model is loaded or a replica started)
+    check_decode_slots(model_args)                      # (likewise)
     in_args = dict(vars(input_args))
     max_rounds = in_args.pop("max_rounds", None)
     gpus = in_args.pop("gpus", None)

@@ -545,15 +545,20 @@ int commu_decode_attn_prefix(const void* qkv, int ld_qkv, const void* pk, const 
  * written -- active may be null).  The logits launch takes 512 < Nn <= 1024 only (others: -22): its kernels walk two
  * column tiles per workgroup, and the packed copy of a weight with Nn <= 512 rows has one.  vec [B][HD], h / h_out [B][D] bf16;
  * z1 / z2 [B][D] and hid [B][DI] are dense bf16 hand-off buffers that belong to THIS layer; sync:
- * commu_decode_tail_sync_words() arrival counters that must be ZERO on entry (one set per launch of a step); *err
- * becomes non-zero when a workgroup gave up waiting (the results of that launch are then invalid).
+ * commu_decode_tail_sync_words_for(B) words that must be ZERO on entry (one set per launch of a step): the arrival counter
+ * of phase p and row group mg (16 sequences) is word (p G + mg) 64 with G = 4 for B <= 64 and 16 beyond; the launch leaves
+ * 32 in the counters of the row groups in use and touches no other word.  commu_decode_tail_sync_words() is the B <= 64
+ * value (768).  *err becomes non-zero when a workgroup gave up waiting (the results of that launch are then invalid).
  * commu_decode_tail_supported(B, D, DI, HD) names the shapes this build takes -- (512, 1024, 8 or 10 heads x 64) and the
- * wide (1024, 2048, 16 x 64), up to 64 sequences -- (others: -22; callers use the per-Linear launches).  d_ln: LayerNorm width (<= D; zero-padded models). */
+ * wide (1024, 2048, 16 x 64), 1 .. 256 sequences -- (others: -22; callers use the per-Linear launches).  256 is what
+ * stays resident at once: 32 workgroups per 16 sequences, 2 workgroups per CU, 256 CUs (csrc/decode_tail.hip has the
+ * derivation).  d_ln: LayerNorm width (<= D; zero-padded models). */
 int commu_decode_tail_supported(int B, int D, int DI, int HD);
-/* diagnostics: following layer-tail / head launches write 100 MHz timestamps of their phase boundaries to
- * buf[workgroup][16] (device memory, 128 x 16 words; null: off) */
+/* diagnostics: following layer-tail / head launches of up to 64 sequences write 100 MHz timestamps of their phase
+ * boundaries to buf[workgroup][16] (device memory, 128 x 16 words; null: off) */
 int commu_decode_tail_trace(unsigned long long* buf);
 int commu_decode_tail_sync_words(void);
+int commu_decode_tail_sync_words_for(int B);
 int commu_decode_layer_tail(const void* vec, int ld_vec, const void* h, int ld_h, const void* Wo_packed,
                             const void* W1_packed, const float* b1, const void* W2_packed, const float* b2,
                             const float* g1, const float* be1, float eps1, const float* g2, const float* be2, float eps2,
