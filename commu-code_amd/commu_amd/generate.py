@@ -20,7 +20,7 @@ import torch
 
 from . import ops
 from ._lib import CommuHipError, call
-from .midi_generator.midi_inferrer import TOKEN_OFFSET, ForcingReport
+from .midi_generator.midi_inferrer import TOKEN_OFFSET, ForcingReport, token_class  # noqa: F401
 
 BF16, F32 = torch.bfloat16, torch.float32
 VPAD = 768
@@ -189,6 +189,78 @@ def logit_bias_rows(x, n: int):
     if x.ndim != 2 or x.shape[0] != n:
         raise CommuHipError(f"logit bias: one row or {n} rows expected (one per slot addressed), got shape {x.shape}")
     return np.stack([_check_bias_row(r, f"logit bias, row {i}") for i, r in enumerate(x)])
+
+
+# ---- the event grammar: a constraint chosen per draw by the slot's own state.  A table is fp32 [8][VPAD]; row c is the
+# additive row for a draw whose previous token has class c (midi_inferrer.token_class: OTHER, BAR, PITCH, VELOCITY, CHORD,
+# DURATION, POSITION), row 7 is zeros: the row of a slot whose grammar is off (commu_sample_topk_topp_gram).
+N_CLASSES = 7
+
+
+def event_grammar():
+    """The default table, entries 0 or -inf: after OTHER, BAR, CHORD or DURATION a draw is a position, BAR or EOS (a group
+    boundary); after a POSITION a velocity; after a VELOCITY a pitch; after a PITCH a duration.  Chord tokens are never
+    drawn (the forcing rules place them).  With it every drawn token continues a group the reference's token-to-MIDI
+    step keeps (midi_inferrer.parse_events).  Not enforced: positions increasing inside a bar, duplicate notes, and the
+    contents of a prompt."""
+    T = TOKEN_OFFSET
+    g = np.full((8, VPAD), -np.inf, dtype=np.float32)
+    g[7] = 0.0
+    g[:7, 0] = 0.0                     # (ids 0 and >= 729 are never drawn: their entries are ignored)
+    g[:7, T.VOCAB_SIZE:] = 0.0
+    for c in (0, 1, 4, 5):             # OTHER, BAR, CHORD, DURATION: a group boundary
+        g[c, T.POSITION:T.BPM] = 0.0
+        g[c, T.BAR] = 0.0
+        g[c, T.EOS] = 0.0
+    g[6, T.NOTE_VELOCITY:T.CHORD_START] = 0.0        # POSITION -> VELOCITY
+    g[3, T.PITCH:T.NOTE_VELOCITY] = 0.0              # VELOCITY -> PITCH
+    g[2, T.NOTE_DURATION:T.POSITION] = 0.0           # PITCH -> DURATION
+    return g
+
+
+def grammar_table(x):
+    """x as a validated grammar table, float32 [8][VPAD] with a zero row 7: [7 or 8] rows of at least 729 entries, finite
+    or -inf (a ban).  Raises CommuHipError on another shape, NaN or +inf, and a class row that bans every id in 1 .. 728
+    (a draw after such a token could only fail).  Row 7 of an 8-row table is replaced by zeros: it is the `off` row."""
+    V = TOKEN_OFFSET.VOCAB_SIZE
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    try:
+        a = np.asarray(x, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise CommuHipError(f"grammar: a table of 7 or 8 rows of at least {V} numbers expected, got "
+                            f"{type(x).__name__}") from None
+    if a.ndim != 2 or a.shape[0] not in (N_CLASSES, N_CLASSES + 1) or a.shape[1] < V:
+        raise CommuHipError(f"grammar: a table of 7 or 8 rows of at least {V} numbers expected, got shape {a.shape}")
+    a = a[:N_CLASSES, :V]
+    bad = np.isnan(a) | (a == np.inf)
+    if bool(bad.any()):
+        c, i = (int(v[0]) for v in np.nonzero(bad))
+        raise CommuHipError(f"grammar: row {c}, entry {i} is {a[c, i]}; finite values or -inf (a ban) expected")
+    for c in range(N_CLASSES):
+        if not bool(np.isfinite(a[c, 1:]).any()):
+            raise CommuHipError(f"grammar: row {c} bans all of ids 1 .. {V - 1}, nothing could be drawn after a token of "
+                                f"class {c}")
+    out = np.zeros((N_CLASSES + 1, VPAD), dtype=np.float32)
+    out[:N_CLASSES, :V] = a
+    return out
+
+
+def _grammar_request(grammar, B: int):
+    """A request's grammar= as (table or None, slots that are on): None / False, True (the default table), a table
+    (grammar_table) for every sequence, or one bool per sequence (the default table where True)."""
+    if grammar is None or grammar is False:
+        return None, []
+    if grammar is True:
+        return event_grammar(), list(range(B))
+    if isinstance(grammar, torch.Tensor):
+        grammar = grammar.detach().cpu().numpy()
+    if np.ndim(grammar) == 1 and all(isinstance(v, (bool, np.bool_)) for v in grammar):
+        if len(grammar) != B:
+            raise CommuHipError(f"grammar: one bool per sequence expected ({B}), got {len(grammar)}")
+        on = [b for b, v in enumerate(grammar) if v]
+        return (event_grammar() if on else None), on
+    return grammar_table(grammar), list(range(B))
 
 
 class DecodeState:
@@ -742,6 +814,11 @@ class ForcedDecoder:
         # constraint rows (set_logit_bias): fp32 [B][VPAD], allocated by the first constraint; None: the launches get a null
         # pointer and are the ones a decoder without constraints always made
         self.bias = None
+        # event grammar (set_grammar): the table fp32 [8][VPAD] and the slots' switches [B], allocated by the first grammar;
+        # None: null pointers, the launches a decoder without a grammar always made
+        self.gram = None
+        self.gram_on = None
+        self._gram_host = None          # host mirror of the table (a re-arm that changes nothing uploads nothing)
         # (the replay of a prompt token takes at most two iterations: the decision to force it, then its append)
         self.ld_trace = 2 * (self.generation_length + 2 + 2 * self.max_prompt) if record_trace else 0
         self.trace = torch.zeros(B, self.ld_trace, dtype=i32, device=dev) if record_trace else None
@@ -846,6 +923,41 @@ class ForcedDecoder:
             for j, r in zip(idx, new):
                 self.bias[int(j)].copy_(torch.from_numpy(r))
 
+    def set_grammar(self, table=True, rows: Optional[Sequence[int]] = None):
+        """The event grammar for all slots (rows=None) or the listed ones: True (event_grammar(), the default table), a
+        table (grammar_table) or None (off).  A slot that is on draws from (x + bias) + table[c], c the class of the last
+        token in its seq when the sampling stage runs -- the last prompt token for the first draw of a primed slot --, so
+        every token it draws continues a group of midi_inferrer.parse_events.  Only DRAWS are constrained: forced tokens
+        are placed by the rules and a prompt is not checked.  The decoder holds ONE table; a table given here replaces it
+        for every slot that is on.  The first grammar allocates the table and the [B] switches and drops the captured
+        graphs once (they hold the launch without them), exactly as set_logit_bias does; later calls rewrite in place,
+        ordered on the current stream.  A slot that is off reads the zero row 7: it draws bit for bit what it drew
+        without the feature.  A decoder that never got a grammar allocates nothing."""
+        idx = np.arange(self.B) if rows is None else np.asarray(list(rows), dtype=np.int64)
+        if idx.ndim != 1 or (idx.size and (idx.min() < 0 or idx.max() >= self.B)):
+            raise CommuHipError(f"rows: slot numbers in [0, {self.B}) expected, got {rows!r}")
+        if table is False:
+            table = None
+        new = None if table is None else (event_grammar() if table is True else grammar_table(table))
+        if self.gram is None:
+            if new is None:
+                return
+            self.gram = torch.zeros(N_CLASSES + 1, VPAD, dtype=F32, device=self.dev)
+            self.gram_on = torch.zeros(self.B, dtype=torch.uint8, device=self.dev)
+            self.graph = self.graph_long = None
+        if new is not None and (self._gram_host is None or not np.array_equal(new, self._gram_host)):
+            self.gram.copy_(torch.from_numpy(new))
+            self._gram_host = new
+        val = 0 if new is None else 1
+        if rows is None:
+            self.gram_on.fill_(val)
+        else:
+            for j in idx:
+                self.gram_on[int(j)].fill_(val)
+
+    def _gram_args(self):
+        return None if self.gram is None else (self.gram, self.gram_on, self.fsm, self.seq)
+
     def pre(self):
         call("commu_forcing_pre_rows", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_tok), _p(self.chord_pos),
              self.ld_chord, _p(self.wrong), _p(self.utable), self.ld_u, self.generation_length, _p(self.tok),
@@ -861,7 +973,7 @@ class ForcedDecoder:
         ops.sample_topk(self.state.logits, self.temperature if t_r is None else t_r, self.top_k if k_r is None else k_r,
                         wrong=self.wrong, uniforms=self.uni, active=self.draw, token=self.token,
                         probs_out=self.probs if want_probs else None, top_p=self.top_p if p_r is None else p_r,
-                        logp_out=logp, bias=self.bias)
+                        logp_out=logp, bias=self.bias, **({} if self.gram is None else {"grammar": self._gram_args()}))
         call("commu_forcing_post_rows", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_pos), self.ld_chord,
              _p(self.wrong), _p(self.draw), _p(self.token), None, _p(self.state.klen), _p(self.keep),
              self.state.klen_cap, _p(logp), _p(seq_logp), B, _s())
@@ -878,7 +990,10 @@ class ForcedDecoder:
                 _p(self.chord_tok), _p(self.chord_pos), self.ld_chord, _p(self.utable), self.ld_u, self.generation_length,
                 _p(self.tok), _p(self.active), _p(self.keep), _p(self.draw), _p(self.uni), _p(self.trace), self.ld_trace,
                 _p(st.klen), st.klen_cap, self.B)
-        if self.bias is None:
+        if self.gram is not None:
+            call("commu_decode_sample_post_pre_gram", *args, _p(self.bias), 0 if self.bias is None else self.bias.stride(0),
+                 _p(self.gram), self.gram.stride(0), _p(self.gram_on), _s())
+        elif self.bias is None:
             call("commu_decode_sample_post_pre_rows", *args, _s())
         else:
             call("commu_decode_sample_post_pre_bias", *args, _p(self.bias), self.bias.stride(0), _s())
@@ -1136,11 +1251,17 @@ class ForcedDecoder:
     # (klen = 0), nothing is copied.
     # sampling: a (temperature, top_k, top_p) triple for the slot's next attempt (None: the slot keeps its controls).
     # logit_bias: a constraint row for the slot's next attempt (None: the slot keeps its row; set_logit_bias clears one).
-    def rearm(self, b: int, uniforms_row: Optional[np.ndarray] = None, sampling=None, logit_bias=None):
+    # grammar: True / False switches the slot's event grammar for its next attempt (None: the slot keeps its switch).
+    def rearm(self, b: int, uniforms_row: Optional[np.ndarray] = None, sampling=None, logit_bias=None, grammar=None):
         if sampling is not None:
             self.set_sampling(*sampling, rows=[b])
         if logit_bias is not None:
             self.set_logit_bias(logit_bias, rows=[b])
+        if grammar is not None:
+            if self.gram is None:
+                self.set_grammar(True if grammar else None, rows=[b])
+            else:                              # (the table stays: one byte changes)
+                self.gram_on[int(b)].fill_(1 if grammar else 0)
         rep0 = self.reports[b]
         rep = ForcingReport(rep0.n_chords, rep0.num_measures)
         self.reports[b] = rep
@@ -1320,7 +1441,7 @@ class BatchedGenerator:
         self._decoders = {}
 
     def decoder(self, B, temperature, top_k, max_chords, top_p=1.0, per_slot: bool = False, max_prompt: int = 0,
-                logit_bias=None, shared: bool = False):
+                logit_bias=None, shared: bool = False, grammar=None):
         """The decoder for B slots, its slots set to the given controls (numbers or one value per slot).  per_slot: the
         caller will read log-probabilities or give slots their own controls later (rearm): the array launches from the
         start.  Otherwise one triple for all slots runs the scalar launches, until a second setting arrives for launches
@@ -1330,6 +1451,7 @@ class BatchedGenerator:
         rows = sampling_rows(B, temperature, top_k, top_p)          # (validated before anything is built)
         if logit_bias is not None:
             logit_bias = logit_bias_rows(logit_bias, B)
+        gram_table, gram_rows = _grammar_request(grammar, B)
         key = (B, self.trace is not None, self.sliding) + (("shared",) if shared else ())
         dec = self._decoders.get(key)
         if dec is None or dec.ld_chord < max_chords or dec.max_prompt < max_prompt:
@@ -1344,12 +1466,19 @@ class BatchedGenerator:
             dec.record_logprobs()
         dec.set_sampling(*rows)
         dec.set_logit_bias(logit_bias)
+        # (grammar: the request's event grammar; a request without one switches off what an earlier one left)
+        dec.set_grammar(None)
+        if gram_rows:
+            dec.set_grammar(gram_table, rows=None if len(gram_rows) == B else gram_rows)
         return dec
 
     @torch.no_grad()
     def generate(self, encoded_metas: Sequence[Sequence[int]], input_datas, temperature, top_k, top_p=1.0,
-                 return_logprobs: bool = False, prompts: Optional[Sequence[Sequence[int]]] = None, logit_bias=None):
-        """temperature / top_k / top_p: a number for the batch or one value per sequence.  logit_bias: a constraint row
+                 return_logprobs: bool = False, prompts: Optional[Sequence[Sequence[int]]] = None, logit_bias=None,
+                 grammar=None):
+        """temperature / top_k / top_p: a number for the batch or one value per sequence.  grammar: None, True (the default
+        event grammar), a table (grammar_table) or one bool per sequence -- every token such a sequence DRAWS continues a
+        group the token-to-MIDI step keeps (ForcedDecoder.set_grammar).  logit_bias: a constraint row
         (token_constraints) for the request or one per sequence -- what a sequence may DRAW; forced tokens and prompts are
         not affected (ForcedDecoder.set_logit_bias).  return_logprobs: a third return
         value, ForcedDecoder.logprobs() of the batch.  prompts: one token list per sequence (may be empty) that the
@@ -1362,7 +1491,7 @@ class BatchedGenerator:
         max_prompt = 0 if prompts is None else max(len(p) for p in prompts)
         # (shared_prompt: requests with a prompt only -- without one there is nothing but the short context to share)
         dec = self.decoder(B, temperature, top_k, max_chords, top_p, per_slot=return_logprobs, max_prompt=max_prompt,
-                           logit_bias=logit_bias, shared=self.shared_prompt and max_prompt > 0)
+                           logit_bias=logit_bias, shared=self.shared_prompt and max_prompt > 0, grammar=grammar)
         uniforms = None
         if bool((dec._sampling[0] != 0).any()):
             srcs = self.uniform_sources or [np.random.RandomState(1000 + b).random_sample for b in range(B)]
@@ -1386,7 +1515,7 @@ class BatchedGenerator:
     def generate_stream(self, encoded_meta: Sequence[int], input_data, temperature, top_k, need: int,
                         accept, top_p=1.0, slots: int = 64, seed: int = 0, max_attempts: Optional[int] = None,
                         return_logprobs: bool = False, prompt: Optional[Sequence[int]] = None, logit_bias=None,
-                        share_prompt: bool = False):
+                        share_prompt: bool = False, grammar=None):
         """Attempts of ONE request (the reference's `while idx != num_generate` loop, midi_inferrer.py:338-354, which tries
         one sequence after the other) decoded in up to `slots` parallel slots, CONTINUOUSLY: a slot whose sequence has
         ended is handed to `accept(sequence, report) -> bool` and re-armed with the next attempt while the other slots keep
@@ -1400,6 +1529,7 @@ class BatchedGenerator:
         prompt: a token list every attempt of the request continues (primed slots, ForcedDecoder.load; a re-armed slot
         returns to the primed state).
         logit_bias: one constraint row (token_constraints) for every attempt of the request.
+        grammar: None, True (the default event grammar) or a table (grammar_table): one setting for the request.
         share_prompt (opt-in; also on with BatchedGenerator(shared_prompt=True) when a prompt is given): the K/V of the
         context and the prompt are computed and held once for all slots (ForcedDecoder(shared_prompt=True)); the attempts
         returned are the ones the unshared decoder defines, up to the summation order of the attention."""
@@ -1409,6 +1539,9 @@ class BatchedGenerator:
         share = bool(prompt) and (bool(share_prompt) or self.shared_prompt)
         if logit_bias is not None and np.ndim(logit_bias) != 1:
             raise CommuHipError(f"logit_bias: one row for the request expected, got shape {np.shape(logit_bias)}")
+        if grammar is not None and not isinstance(grammar, (bool, np.bool_)) and np.ndim(grammar) != 2:
+            raise CommuHipError(f"grammar: one setting for the request expected (True or a table), got shape "
+                                f"{np.shape(grammar)}")
         max_chords = len(input_data.chord_token_components["chord_token"])
         # each control's schedule, validated on its own (the three may have different lengths)
         n_of = lambda x: 1 if np.ndim(x) == 0 else len(x)
@@ -1421,7 +1554,7 @@ class BatchedGenerator:
         varying = any(bool((c != c[0]).any()) for c in sched)          # (one triple for every attempt: nothing to re-arm)
         dec = self.decoder(B, [t[0] for t in first], [t[1] for t in first], max_chords, [t[2] for t in first],
                            per_slot=return_logprobs or varying, max_prompt=0 if prompt is None else len(prompt),
-                           logit_bias=logit_bias, shared=share)
+                           logit_bias=logit_bias, shared=share, grammar=grammar)
         started = B
         sampled = bool((sched[0] != 0).any())          # (a greedy attempt reads no variate)
         uni = np.stack([self.attempt_uniforms(seed, a, dec.ld_u) for a in range(B)]) if sampled else None

@@ -52,6 +52,66 @@ def count_notes(seq: List[int]) -> int:
     return n
 
 
+# ---- the event grammar (generate.event_grammar, csrc/decode_loop.h: token_class): token classes by id
+CLASS_OTHER, CLASS_BAR, CLASS_PITCH, CLASS_VELOCITY, CLASS_CHORD, CLASS_DURATION, CLASS_POSITION = range(7)
+
+
+def token_class(t: int) -> int:
+    """The class of a token id: OTHER (pad 0, EOS 1, ids >= 560: meta, bpm, ...; anything outside the vocabulary), BAR,
+    PITCH, VELOCITY, CHORD, DURATION, POSITION."""
+    t = int(t)
+    if t < TOKEN_OFFSET.BAR or t >= TOKEN_OFFSET.BPM:
+        return CLASS_OTHER
+    if t < TOKEN_OFFSET.PITCH:
+        return CLASS_BAR
+    if t < TOKEN_OFFSET.NOTE_VELOCITY:
+        return CLASS_PITCH
+    if t < TOKEN_OFFSET.CHORD_START:
+        return CLASS_VELOCITY
+    if t < TOKEN_OFFSET.NOTE_DURATION:
+        return CLASS_CHORD
+    if t < TOKEN_OFFSET.POSITION:
+        return CLASS_DURATION
+    return CLASS_POSITION
+
+
+def parse_events(seq: List[int], start: int) -> Optional[int]:
+    """Whether seq[start:] is a chain of the groups the reference's token-to-MIDI step keeps
+    (commu/preprocessor/encoder/encoder_utils.py:385-419; everything else it drops silently): BAR | EOS (the last token) |
+    POSITION, CHORD | POSITION, VELOCITY, PITCH, DURATION.  Returns the index of the first token that does not continue a
+    group, None when there is none.  A note group cut short by the end of the sequence (the iteration cap) is well formed;
+    a sequence that ends in EOS has no such group, since EOS does not continue one."""
+    state = 0          # 0: at a group boundary; 1 / 2 / 3: after a position / velocity / pitch; 4: after EOS
+    for i in range(max(int(start), 0), len(seq)):
+        t = int(seq[i])
+        c = token_class(t)
+        if state == 4:
+            return i                                    # nothing follows EOS
+        if state == 0:
+            if c == CLASS_POSITION:
+                state = 1
+            elif t == TOKEN_OFFSET.EOS:
+                state = 4
+            elif c != CLASS_BAR:
+                return i
+        elif state == 1:
+            if c == CLASS_CHORD:
+                state = 0
+            elif c == CLASS_VELOCITY:
+                state = 2
+            else:
+                return i
+        elif state == 2:
+            if c != CLASS_PITCH:
+                return i
+            state = 3
+        else:
+            if c != CLASS_DURATION:
+                return i
+            state = 0
+    return None
+
+
 class ForcingReport:
     """What the forcing state machine was asked to place in one sequence and how far it got."""
 
@@ -89,11 +149,13 @@ class InferenceTask:
         return count_notes(seq) > 0
 
     def execute(self, encoded_meta, max_rounds: Optional[int] = None, return_logprobs: bool = False,
-                prompt: Optional[List[int]] = None, logit_bias=None):                         # :338-354
+                prompt: Optional[List[int]] = None, logit_bias=None, grammar=None):           # :338-354
         """return_logprobs (not in the reference): (sequences, their log-probability arrays -- ForcedDecoder.logprobs).
         prompt (not in the reference): token ids that follow the meta tokens; every attempt continues them (primed
         generation, BatchedGenerator.generate_stream) and every returned sequence starts with [0] + meta + prompt.
-        logit_bias (not in the reference): a constraint row (generate.token_constraints) on what every attempt may draw."""
+        logit_bias (not in the reference): a constraint row (generate.token_constraints) on what every attempt may draw.
+        grammar (not in the reference): True or a table (generate.grammar_table) -- every drawn token continues a group the
+        token-to-MIDI step keeps (generate.event_grammar, BatchedGenerator.generate_stream)."""
         from ..generate import BatchedGenerator
         data = self.input_data
         glen = self.inference_cfg.GENERATION.generation_length
@@ -106,6 +168,9 @@ class InferenceTask:
         share = bool(getattr(self.inference_cfg.GENERATION, "share_prompt", False))
         # (likewise: generate.py --decode_slots)
         slots = int(getattr(self.inference_cfg.GENERATION, "decode_slots", 64))
+        # (likewise: generate.py --grammar; an argument given here wins)
+        if grammar is None and bool(getattr(self.inference_cfg.GENERATION, "grammar", False)):
+            grammar = True
         gen = BatchedGenerator(self.model, self.device, glen, mlen, sliding=sliding, kv_dtype=kv_dtype,
                                **({"shared_prompt": True} if share else {}))
 
@@ -124,5 +189,6 @@ class InferenceTask:
                                   top_p=getattr(data, "top_p", 1.0), seed=self.uniform_seed,
                                   max_attempts=None if max_rounds is None else max_rounds * data.num_generate,
                                   return_logprobs=return_logprobs, prompt=None if not prompt else list(prompt),
-                                  logit_bias=logit_bias, **({} if slots == 64 else {"slots": slots}))
+                                  logit_bias=logit_bias, **({} if slots == 64 else {"slots": slots}),
+                                  **({} if grammar is None else {"grammar": grammar}))
         return (res[0], res[2]) if return_logprobs else res[0]

@@ -51,6 +51,9 @@ class ModelInitializeTask:
         # generate.py --share_prompt (not in the reference): one K/V copy of the prompt for all decode slots
         if getattr(self.model_args, "share_prompt", False):
             cfg.GENERATION.share_prompt = True
+        # generate.py --grammar (not in the reference): the default event grammar on every draw
+        if getattr(self.model_args, "grammar", False):
+            cfg.GENERATION.grammar = True
         # generate.py --decode_slots (not in the reference): attempts decoded side by side (64 unless the key is set)
         if getattr(self.model_args, "decode_slots", None) not in (None, 64):
             cfg.GENERATION.decode_slots = int(self.model_args.decode_slots)

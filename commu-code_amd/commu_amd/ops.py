@@ -920,7 +920,7 @@ def _sampling_control(x, name, dtype, nseq, device):
 
 
 def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=None, token=None, probs_out=None,
-                top_p=1.0, logp_out=None, bias=None, V=729):
+                top_p=1.0, logp_out=None, bias=None, V=729, grammar=None):
     """In-place temperature + softmax + top-k + wrong-token mask + inverse-CDF draw per sequence.
     logits: fp32 [nseq, >=V] (row stride = ld), modified in place (logits[:, 1:V] /= temperature).
     top_p < 1: nucleus filter after the top-k / rejected-token step (an extra mode; the reference has top-k only).
@@ -934,7 +934,12 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
     is built from logits / temperature + bias (the raw row + bias for temperature 0) -- a finite entry re-weights an id,
     -inf bans it, before top-k.  It is never written back: the logits are left as the call without it leaves them
     (commu_sample_topk_topp_bias; generate.token_constraints builds and validates such rows).
-    V: the ids drawn from are 1 .. V-1 (2 <= V <= 768; the decode loop's vocabulary by default)."""
+    V: the ids drawn from are 1 .. V-1 (2 <= V <= 768; the decode loop's vocabulary by default).
+    grammar: (table, on, state, seq) on the device of the logits -- table fp32 [8, >=V] (generate.grammar_table), on uint8
+    [nseq] or None (all on), state the int32 forcing records [nseq, commu_forcing_state_ints()], seq int32 [nseq, ld_seq].
+    Row c of the table is added after the bias for a sequence whose previous token seq[b][state[b][0] - 1] has class c
+    (generate.token_class), row 7 for a sequence that is off; like the bias it is never written back
+    (commu_sample_topk_topp_gram)."""
     nseq = logits.shape[0]
     V = int(V)
     assert logits.dtype == F32 and logits.stride(1) == 1
@@ -958,11 +963,32 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
                                 f"{str(logp_out.dtype).replace('torch.', '')} {tuple(logp_out.shape)}")
     if token is None:
         token = torch.empty(nseq, device=logits.device, dtype=torch.int32)
-    call("commu_sample_topk_topp_bias", _p(logits), logits.stride(0), nseq, V, _p(wrong),
-         0 if wrong is None else wrong.stride(0), _p(uniforms), _p(active), 0.0 if t_s is None else float(t_s),
-         1 if k_s is None else int(k_s), 1.0 if p_s is None else float(p_s), _p(t_r), _p(k_r), _p(p_r), _p(token),
-         _p(probs_out), 0 if probs_out is None else probs_out.stride(0), _p(logp_out), _p(bias),
-         0 if bias is None else max(int(bias.stride(0)), V), _s())
+    args = (_p(logits), logits.stride(0), nseq, V, _p(wrong),
+            0 if wrong is None else wrong.stride(0), _p(uniforms), _p(active), 0.0 if t_s is None else float(t_s),
+            1 if k_s is None else int(k_s), 1.0 if p_s is None else float(p_s), _p(t_r), _p(k_r), _p(p_r), _p(token),
+            _p(probs_out), 0 if probs_out is None else probs_out.stride(0), _p(logp_out), _p(bias),
+            0 if bias is None else max(int(bias.stride(0)), V))
+    if grammar is None:
+        call("commu_sample_topk_topp_bias", *args, _s())
+        return token
+    table, on, state, seq = grammar
+    nrec = call("commu_forcing_state_ints")
+    for t, name, dtype, shape in ((table, "table", F32, "[8, >= %d]" % V), (on, "on", torch.uint8, "[%d]" % nseq),
+                                  (state, "state", torch.int32, "[%d, %d]" % (nseq, nrec)),
+                                  (seq, "seq", torch.int32, "[%d, ld_seq]" % nseq)):
+        if t is None and name == "on":
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != logits.device:
+            raise CommuHipError(f"grammar {name}: a tensor on the device of the logits expected (no CPU fallback)")
+        ok = t.dtype == dtype and t.is_contiguous() and {
+            "table": t.dim() == 2 and t.shape[0] == 8 and t.shape[1] >= V,
+            "on": tuple(t.shape) == (nseq,),
+            "state": tuple(t.shape) == (nseq, nrec),
+            "seq": t.dim() == 2 and t.shape[0] == nseq and t.shape[1] >= 1}[name]
+        if not ok:
+            raise CommuHipError(f"grammar {name}: contiguous {str(dtype).replace('torch.', '')} {shape} expected, got "
+                                f"{str(t.dtype).replace('torch.', '')} {tuple(t.shape)}")
+    call("commu_sample_topk_topp_gram", *args, _p(table), table.stride(0), _p(on), _p(state), _p(seq), seq.stride(0), _s())
     return token
 
 

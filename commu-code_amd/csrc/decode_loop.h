@@ -73,7 +73,36 @@ struct TokenLogp {
 //   places: bias, then top-k, then the rejected-token mask, then top-p).  What is written back is x, never y, so a Q5
 //   re-draw adds the bias once to the compounded row; `full` is the log-softmax of y.  A row banned entirely has no
 //   mass: the Q12 exit below.  Without BIAS the pointer is not looked at and the code is what it was.
-template <bool BIAS>
+// GRAM (Grammar: table fp32 [8][ld], ld >= V): a constraint chosen by the sequence's own state -- row c of the table is
+//   added for a draw whose PREVIOUS token (the last token of seq when the stage runs; the same one on a Q5 re-draw) has
+//   class c (token_class), row 7 (zeros by convention) for a sequence whose grammar is off: y[id] = (x[id] + bias[b][id]) +
+//   table[c][id], in that fp32 order.  All that is said of the bias holds: before top-k, never written back, -inf bans.
+//   The row index is uniform over the wave (scalar), there is no branch on it.  Without GRAM nothing of `g` is looked at.
+//   The previous token is a load that depends on the record's length, and the table row one that depends on it: the body
+//   issues the first right behind its logits loads, so that the logits, the bias and the rejected-token map travel under
+//   the chain record -> previous token -> table row instead of behind it (the caller passes `len` and `on` as it loaded
+//   them, without waiting for them).
+struct Grammar {
+    const float* table;
+    int ld;
+    const int* seq_row;     // the sequence's row of seq
+    int len, ld_seq;        // tokens in it (the record's F_LEN; clamped into the row whatever it holds)
+    int on;                 // the sequence's switch
+};
+// token classes of the event grammar by id ranges (TOKEN_OFFSET): 0 OTHER (pad, EOS, ids >= 560), 1 BAR, 2 PITCH, 3 VELOCITY,
+// 4 CHORD, 5 DURATION, 6 POSITION -- range compares, no table in memory; any int is classified (negative: OTHER)
+__device__ __forceinline__ int token_class(int t) {
+    int c = 0;
+    c = t >= 2 ? 1 : c;
+    c = t >= 3 ? 2 : c;
+    c = t >= 131 ? 3 : c;
+    c = t >= 195 ? 4 : c;
+    c = t >= 304 ? 5 : c;
+    c = t >= 432 ? 6 : c;
+    c = t >= 560 ? 0 : c;
+    return c;
+}
+template <bool BIAS, bool GRAM = false>
 __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restrict__ logits, int ld, int V,
                                                  const unsigned char* __restrict__ wrong, int ldw,
                                                  const float* __restrict__ uni,
@@ -81,7 +110,8 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
                                                  int top_k, int* __restrict__ token, float* __restrict__ probs_out,
                                                  int ldp, float top_p, SamplingRows rows, bool want_logp,
                                                  float* __restrict__ logp_out, TokenLogp& lp,
-                                                 const float* __restrict__ bias = nullptr, int ld_bias = 0) {
+                                                 const float* __restrict__ bias = nullptr, int ld_bias = 0,
+                                                 Grammar g = Grammar{nullptr, 0, nullptr, 0, 0, 0}) {
     float* lg = logits + (size_t)b * ld;
     // The optional per-sequence inputs -- the active flag and this sequence's controls -- are loaded unconditionally: a null
     // array reads a valid word of this sequence instead (token[b], logits[b][0]), which is then ignored.  So they are in
@@ -96,10 +126,20 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
     float raw[PER_LANE];
 #pragma unroll
     for (int e = 0; e < PER_LANE; ++e) raw[e] = lg[min(base + e, V - 1)];
+    int prev = 0;                 // (GRAM) the last token of seq: every lane loads the same word
+    if constexpr (GRAM) prev = g.seq_row[min(max(g.len, 1), g.ld_seq) - 1];
     float bv[PER_LANE];           // (BIAS) this lane's entries of the bias row, in the same batch of loads
     if constexpr (BIAS) {
 #pragma unroll
         for (int e = 0; e < PER_LANE; ++e) bv[e] = bias[(size_t)b * ld_bias + min(base + e, V - 1)];
+    }
+    // (GRAM) this lane's entries of the grammar row of the previous token's class: issued as soon as the token is here, so
+    // that the rejected-token map and the variate below travel under them
+    float gv[PER_LANE];
+    if constexpr (GRAM) {
+        const int row = __builtin_amdgcn_readfirstlane(g.on != 0 ? token_class(prev) : 7);
+#pragma unroll
+        for (int e = 0; e < PER_LANE; ++e) gv[e] = g.table[(size_t)row * g.ld + min(base + e, V - 1)];
     }
     unsigned wmask = 0u;          // the rejected ("wrong") tokens of this lane
     if (wrong != nullptr) {
@@ -129,6 +169,7 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
         for (int e = 0; e < PER_LANE; ++e) {
             const int id = base + e;
             if constexpr (BIAS) raw[e] += bv[e];               // greedy writes nothing back: the row drawn from is y
+            if constexpr (GRAM) raw[e] += gv[e];
             if (id >= 1 && id < V && raw[e] > best) { best = raw[e]; bi = id; }
         }
         const float wbest = wmax_f(best);                      // ties: the lowest id
@@ -155,6 +196,7 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
             if (in) lg[id] = x;                 // in-place division: compounds on a redo (Q5)
             float y = x;
             if constexpr (BIAS) y = in ? x + bv[e] : -INFINITY;          // (the bias is not written back)
+            if constexpr (GRAM) y = in ? y + gv[e] : -INFINITY;          // (nor the grammar row)
             p[e] = y;
             mx = fmaxf(mx, y);
         }
@@ -341,6 +383,13 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
                 for (int e = 0; e < PER_LANE; ++e)
                     if (base + e == drawn) bd = bv[e];
                 xd += lane_f(bd, owner);
+            }
+            if constexpr (GRAM) {
+                float gd = 0.f;
+#pragma unroll
+                for (int e = 0; e < PER_LANE; ++e)
+                    if (base + e == drawn) gd = gv[e];
+                xd += lane_f(gd, owner);
             }
         }
         lp.full = drawn < 0 ? NAN : (xd - lmx) - logf(lsum);

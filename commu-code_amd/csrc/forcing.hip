@@ -63,8 +63,19 @@ struct LoopStageArgs {
     unsigned long long* trace;      // (diagnostics) [sequence][4] 100 MHz timestamps: start, sampled, post done, pre done
     const float* bias; int ld_bias; // (BIAS) the caller's constraint rows for the sampling step (sample_topk_body)
 };
-template <bool BIAS>
-__global__ __launch_bounds__(64) void sample_post_pre_kernel(LoopStageArgs a) {
+// (GRAM) the grammar table [8][ld_gram] and the slots' switches [B]: arguments of the grammar kernels only, so that the
+// launch without a grammar keeps its instructions AND its argument block (the kernel body is written on its parameter: moved
+// into a device function that takes the arguments by reference, the kernels without a grammar came out different)
+struct LoopStageArgsGram : LoopStageArgs {
+    const float* gram; int ld_gram;
+    const unsigned char* gram_on;
+};
+template <bool GRAM>
+struct LoopArgsOf { using type = LoopStageArgs; };
+template <>
+struct LoopArgsOf<true> { using type = LoopStageArgsGram; };
+template <bool BIAS, bool GRAM>
+__global__ __launch_bounds__(64) void sample_post_pre_kernel(typename LoopArgsOf<GRAM>::type a) {
     const int b = blockIdx.x, lane = threadIdx.x;
     if (a.trace != nullptr && lane == 0) a.trace[b * 4 + 0] = wall_clock64();
     int rec[F_COUNT];                                  // the record travels through the three stages in lane 0's registers;
@@ -73,9 +84,19 @@ __global__ __launch_bounds__(64) void sample_post_pre_kernel(LoopStageArgs a) {
     // what post reads of this iteration's decision, loaded here for the same reason (a null klen reads token[b] instead)
     const StepFlags flags{a.draw[b], a.keep[b], *(a.klen != nullptr ? a.klen + b : a.token + b)};
     TokenLogp lp{NAN, NAN};                            // like `drawn`, the pair reaches post in registers
-    const int drawn = sample_topk_body<BIAS>(b, lane, a.logits, a.ld, a.V, a.wrong, VOCAB, a.uni, a.draw, a.temperature,
-                                             a.top_k, a.token, a.probs_out, a.ldp, a.top_p, a.rows,
-                                             a.logp != nullptr || a.seq_logp != nullptr, a.logp, lp, a.bias, a.ld_bias);
+    Grammar g{nullptr, 0, nullptr, 0, 0, 0};
+    if constexpr (GRAM) {
+        // the slot's switch is loaded with the flags above (a null gram_on reads draw[b], which is then ignored).  The
+        // previous token is one dependent load behind the record: the sampling body issues it right behind its logits
+        // loads -- issued here, the wait for the record came BEFORE the logits loads and they sat behind it
+        const unsigned char on_b = *(a.gram_on != nullptr ? a.gram_on + b : a.draw + b);
+        g = Grammar{a.gram, a.ld_gram, a.seq + (size_t)b * a.ld_seq, rec[F_LEN], a.ld_seq,
+                    a.gram_on != nullptr ? (int)on_b : 1};
+    }
+    const int drawn = sample_topk_body<BIAS, GRAM>(b, lane, a.logits, a.ld, a.V, a.wrong, VOCAB, a.uni, a.draw,
+                                                   a.temperature, a.top_k, a.token, a.probs_out, a.ldp, a.top_p, a.rows,
+                                                   a.logp != nullptr || a.seq_logp != nullptr, a.logp, lp, a.bias,
+                                                   a.ld_bias, g);
     __syncthreads();
     if (a.trace != nullptr && lane == 0) a.trace[b * 4 + 1] = wall_clock64();
     forcing_post_body(b, lane, rec, a.seq, a.ld_seq, a.chord_pos, a.ld_chord, a.wrong, a.draw, a.token, nullptr, a.klen,
@@ -253,6 +274,43 @@ extern "C" int commu_decode_loop_trace(unsigned long long* buf) {
     return 0;
 }
 
+extern "C" int commu_decode_sample_post_pre_gram(float* logits, int ld, int V, unsigned char* wrong, float temperature,
+                                                 int top_k, float top_p, const float* temperature_rows,
+                                                 const int* top_k_rows, const float* top_p_rows, int* token,
+                                                 float* probs_out, int ldp, float* logp, float* seq_logp, int* state,
+                                                 int* seq, int ld_seq, const int* chord_tok, const int* chord_pos,
+                                                 int ld_chord, const float* utable, int ld_u, int max_iters, long long* tok,
+                                                 unsigned char* active, unsigned char* keep, unsigned char* draw, float* uni,
+                                                 int* trace, int ld_trace, int* klen, int lmax, int B, const float* bias,
+                                                 int ld_bias, const float* gram, int ld_gram, const unsigned char* gram_on,
+                                                 hipStream_t stream) {
+    if (B <= 0) return 0;
+    if (V != VOCAB || V > 64 * PER_LANE || ld_seq < 2 || ld_chord < 1 || ld_u < 1) return -22;
+    if (bias != nullptr && ld_bias < V) return -22;          // (the kernel reads bias[b][0 .. V-1])
+    // (the kernel reads gram[0 .. 7][0 .. V-1] and finds the previous token through the record)
+    if (gram != nullptr && (ld_gram < V || state == nullptr || seq == nullptr)) return -22;
+    // (a scalar that an array replaces is not looked at; the kernel clamps what the arrays hold)
+    if ((top_k_rows == nullptr && (top_k < 1 || top_k > V)) || (top_p_rows == nullptr && !(top_p > 0.f))) return -22;
+    LoopStageArgs a{logits, ld, V, wrong, temperature, top_k, top_p, SamplingRows{temperature_rows, top_k_rows, top_p_rows},
+                    token, probs_out, ldp, logp, seq_logp, state, seq, ld_seq, chord_tok, chord_pos, ld_chord, utable, ld_u,
+                    max_iters, tok, active, keep, draw, uni, trace, ld_trace, klen, lmax, g_loop_trace, bias, ld_bias};
+    // four kernels: without a bias / a grammar the launch is the one it always was (no added load, no added register, no
+    // added argument)
+    if (gram != nullptr) {
+        LoopStageArgsGram ag;
+        static_cast<LoopStageArgs&>(ag) = a;
+        ag.gram = gram; ag.ld_gram = ld_gram; ag.gram_on = gram_on;
+        if (bias != nullptr) COMMU_LAUNCH((sample_post_pre_kernel<true, true>), dim3(B), dim3(64), 0, stream, ag);
+        else COMMU_LAUNCH((sample_post_pre_kernel<false, true>), dim3(B), dim3(64), 0, stream, ag);
+    } else if (bias != nullptr) {
+        COMMU_LAUNCH((sample_post_pre_kernel<true, false>), dim3(B), dim3(64), 0, stream, a);
+    } else {
+        COMMU_LAUNCH((sample_post_pre_kernel<false, false>), dim3(B), dim3(64), 0, stream, a);
+    }
+    COMMU_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int commu_decode_sample_post_pre_bias(float* logits, int ld, int V, unsigned char* wrong, float temperature,
                                                  int top_k, float top_p, const float* temperature_rows,
                                                  const int* top_k_rows, const float* top_p_rows, int* token,
@@ -262,22 +320,10 @@ extern "C" int commu_decode_sample_post_pre_bias(float* logits, int ld, int V, u
                                                  unsigned char* active, unsigned char* keep, unsigned char* draw, float* uni,
                                                  int* trace, int ld_trace, int* klen, int lmax, int B, const float* bias,
                                                  int ld_bias, hipStream_t stream) {
-    if (B <= 0) return 0;
-    if (V != VOCAB || V > 64 * PER_LANE || ld_seq < 2 || ld_chord < 1 || ld_u < 1) return -22;
-    if (bias != nullptr && ld_bias < V) return -22;          // (the kernel reads bias[b][0 .. V-1])
-    // (a scalar that an array replaces is not looked at; the kernel clamps what the arrays hold)
-    if ((top_k_rows == nullptr && (top_k < 1 || top_k > V)) || (top_p_rows == nullptr && !(top_p > 0.f))) return -22;
-    LoopStageArgs a{logits, ld, V, wrong, temperature, top_k, top_p, SamplingRows{temperature_rows, top_k_rows, top_p_rows},
-                    token, probs_out, ldp, logp, seq_logp, state, seq, ld_seq, chord_tok, chord_pos, ld_chord, utable, ld_u,
-                    max_iters, tok, active, keep, draw, uni, trace, ld_trace, klen, lmax, g_loop_trace, bias, ld_bias};
-    // two kernels: without a bias the launch is the one it always was (no added load, no added register)
-    if (bias != nullptr) {
-        COMMU_LAUNCH(sample_post_pre_kernel<true>, dim3(B), dim3(64), 0, stream, a);
-    } else {
-        COMMU_LAUNCH(sample_post_pre_kernel<false>, dim3(B), dim3(64), 0, stream, a);
-    }
-    COMMU_LAUNCH_CHECK();
-    return 0;
+    return commu_decode_sample_post_pre_gram(logits, ld, V, wrong, temperature, top_k, top_p, temperature_rows, top_k_rows,
+                                             top_p_rows, token, probs_out, ldp, logp, seq_logp, state, seq, ld_seq, chord_tok,
+                                             chord_pos, ld_chord, utable, ld_u, max_iters, tok, active, keep, draw, uni, trace,
+                                             ld_trace, klen, lmax, B, bias, ld_bias, nullptr, 0, nullptr, stream);
 }
 
 extern "C" int commu_decode_sample_post_pre_rows(float* logits, int ld, int V, unsigned char* wrong, float temperature,

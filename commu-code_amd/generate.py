@@ -48,6 +48,11 @@ def parse_args():
     # and the prompt ONCE for all decode slots instead of once per slot (the same attention, another summation order).
     # bf16 linear cache only: refused without --prompt_tokens and with --sliding_memory, --kv_cache fp8 or --parity.
     model_arg_parser.add_argument("--share_prompt", action="store_true")
+    # not in the reference (whose token-to-MIDI step silently drops every token outside an exact Position, Note Velocity,
+    # Note On, Note Duration or Position, Chord group, encoder_utils.py:385-419): the default event grammar -- every DRAWN
+    # token continues such a group (commu_amd.generate.event_grammar).  Forced tokens and --prompt_tokens are not affected.
+    model_arg_parser.add_argument("--grammar", action="store_true",
+                                  help="event grammar: every drawn token continues a note or chord group")
     # not in the reference (which decodes one sequence at a time): how many attempts are decoded side by side.  1 .. 256;
     # up to 256 slots run the fused layer-tail launches ("Supported shapes").  The sequences returned do
     # not depend on it.  (checked by check_decode_slots: the range is named in its message)

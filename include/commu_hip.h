@@ -461,6 +461,27 @@ int commu_sample_topk_topp_bias(float* logits, int ld, int nseq, int V, const un
                                 float top_p, const float* temperature_rows, const int* top_k_rows,
                                 const float* top_p_rows, int* token, float* probs_out, int ldp, float* logp_out,
                                 const float* bias, int ld_bias, hipStream_t stream);
+/* the same with an EVENT GRAMMAR: a constraint chosen per draw by the sequence's own state, so that what is drawn
+ * survives the reference's token-to-MIDI step, which keeps only the exact groups Position, Note Velocity, Note On,
+ * Note Duration and Position, Chord and silently drops everything else (commu/preprocessor/encoder/encoder_utils.py:385-419).
+ * gram: fp32 [8][ld_gram], ld_gram >= V, optional.  Row c is the additive row for a draw whose PREVIOUS token has class c;
+ * classes by id: 0 OTHER (pad 0, EOS 1, ids >= 560), 1 BAR (2), 2 PITCH (3 .. 130), 3 VELOCITY (131 .. 194), 4 CHORD
+ * (195 .. 303), 5 DURATION (304 .. 431), 6 POSITION (432 .. 559), found by range compares.  Row 7, zeros by convention,
+ * is the row of a sequence whose switch gram_on[b] is 0 (gram_on == null: every sequence is on).  The previous token is
+ * seq[b][state[b][F_LEN] - 1] (state: the forcing records, commu_forcing_state_ints() ints each; seq int32
+ * [nseq][ld_seq]) at the moment the stage runs; a Q5 re-draw sees the same one.
+ *   y[id] = (x[id] + bias[b][id]) + gram[c][id], in this fp32 order.  All that is said of the bias above holds for the
+ *   grammar row: before top-k, never written back, probs_out exactly 0 at banned ids, full the log-softmax of y, a row
+ *   with nothing left takes the Q12 exit.  The 12 grammar loads of a lane use the index clamp of its logits loads.
+ * gram == null: commu_sample_topk_topp_bias bit for bit, with the kernel it always launched (it forwards here).
+ * ld_gram < V, or a grammar without state / seq: -22. */
+int commu_sample_topk_topp_gram(float* logits, int ld, int nseq, int V, const unsigned char* wrong, int ldw,
+                                const float* uniforms, const unsigned char* active, float temperature, int top_k,
+                                float top_p, const float* temperature_rows, const int* top_k_rows,
+                                const float* top_p_rows, int* token, float* probs_out, int ldp, float* logp_out,
+                                const float* bias, int ld_bias, const float* gram, int ld_gram,
+                                const unsigned char* gram_on, const int* state, const int* seq, int ld_seq,
+                                hipStream_t stream);
 
 /* ---- single-token decode step with a K/V cache (forward_generate with qlen 1, model.py:606-628, as
  * called by midi_inferrer.py:199-207).  Caches are bf16 [B][H][Lmax][DH] per layer; klen[b] = valid rows
@@ -652,6 +673,20 @@ int commu_decode_sample_post_pre_bias(float* logits, int ld, int V, unsigned cha
                                       long long* tok, unsigned char* active, unsigned char* keep, unsigned char* draw,
                                       float* uni, int* trace, int ld_trace, int* klen, int lmax, int B,
                                       const float* bias, int ld_bias, hipStream_t stream);
+/* The same launch with the sampling stage of commu_sample_topk_topp_gram (the event grammar that keeps every drawn token
+ * inside a group encoder_utils.py:385-419 turns into a note or a chord): gram fp32 [8][ld_gram] (ld_gram >= 729), gram_on
+ * [B] bytes (null: all on).  The previous token is read through the record the launch holds anyway; the sampling stage issues
+ * that load right behind its logits loads.  Forced tokens (midi_inferrer.py:239-320) and prompts are not draws: not affected, not checked.  gram == null:
+ * commu_decode_sample_post_pre_bias, which forwards here, bit for bit and with the kernel it always launched. */
+int commu_decode_sample_post_pre_gram(float* logits, int ld, int V, unsigned char* wrong, float temperature, int top_k,
+                                      float top_p, const float* temperature_rows, const int* top_k_rows,
+                                      const float* top_p_rows, int* token, float* probs_out, int ldp, float* logp,
+                                      float* seq_logp, int* state, int* seq, int ld_seq, const int* chord_tok,
+                                      const int* chord_pos, int ld_chord, const float* utable, int ld_u, int max_iters,
+                                      long long* tok, unsigned char* active, unsigned char* keep, unsigned char* draw,
+                                      float* uni, int* trace, int ld_trace, int* klen, int lmax, int B,
+                                      const float* bias, int ld_bias, const float* gram, int ld_gram,
+                                      const unsigned char* gram_on, hipStream_t stream);
 /* ---- primed generation: enter the loop at an arbitrary point of a sequence (continue a given token prefix).
  * commu_forcing_replay runs the two transitions above over prompt[b][0 .. prompt_len[b]) WITHOUT a model step, starting
  * from the record, seq and klen as a load of the conditioning context leaves them (midi_inferrer.py:186-197): wherever
