@@ -133,6 +133,8 @@ PROTOTYPES = {
                                     c_p, c_i, c_p],
     "commu_sample_topk_topp_gram": [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_f, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_i, c_p,
                                     c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_p],
+    "commu_sample_topk_topp_harm": [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_f, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_i, c_p,
+                                    c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_p],
     "commu_decode_kv_append": [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
     "commu_decode_attn": [c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_p],
     "commu_decode_attn_split": [c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_i,
@@ -175,6 +177,9 @@ PROTOTYPES = {
     "commu_decode_sample_post_pre_gram": [c_p, c_i, c_i, c_p, c_f, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p,
                                           c_i, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i,
                                           c_p, c_i, c_p, c_i, c_p, c_p],
+    "commu_decode_sample_post_pre_harm": [c_p, c_i, c_i, c_p, c_f, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p,
+                                          c_i, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i,
+                                          c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_p],
     "commu_forcing_replay": [c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p,
                              c_p, c_p, c_i, c_p, c_i, c_p],
     "commu_decode_prefill_scatter": [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p],

@@ -263,6 +263,83 @@ def _grammar_request(grammar, B: int):
     return grammar_table(grammar), list(range(B))
 
 
+# ---- the harmony constraint: a third additive term chosen per draw by the chord the slot is in.  A table is fp32
+# [111][16]: row t - 195 for the chord tokens 195 .. 303 (rows 0 .. 107 the 12 roots x 9 qualities, row 108 Chord_NN), row 109
+# for a slot whose seq holds no chord yet, row 110 zeros: the row of a slot whose switch is off.  Column pc is MIDI pitch class
+# pc (C = 0); columns 12 .. 15 are zero padding, so a row is one 64-byte line (commu_sample_topk_topp_harm).
+HARM_ROWS, HARM_COLS, HARM_NN, HARM_NO_CHORD, HARM_OFF = 111, 16, 108, 109, 110
+
+
+def harmony_table(outside=-np.inf, extra=()):
+    """The default table: in a chord's row its chord tones (meta.chord_pitch_classes) get 0 and every other pitch class
+    gets `outside` -- -inf (strict: only chord tones are drawn) or a finite value <= 0 (soft: the others are discouraged).
+    extra: intervals in semitones above the root that are allowed as well (e.g. (2, 9) admits the ninth and the sixth).
+    Rows 108 (Chord_NN), 109 (no chord yet) and 110 (off) are zeros: no statement."""
+    from .midi_generator.meta import chord_pitch_classes, chord_root
+    if isinstance(outside, (bool, np.bool_)) or not isinstance(outside, (int, float, np.integer, np.floating)):
+        raise CommuHipError(f"harmony: outside is -inf or a finite number <= 0, got {outside!r}")
+    outside = float(outside)
+    if math.isnan(outside) or outside > 0:
+        raise CommuHipError(f"harmony: outside is -inf or a finite number <= 0, got {outside}")
+    given = extra
+    try:
+        given = list(extra)
+        extra = [int(i) for i in given]
+        if any(isinstance(i, (bool, np.bool_)) or e != i for e, i in zip(extra, given)):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise CommuHipError(f"harmony: extra is a collection of whole semitone intervals, got {given!r}") from None
+    t = np.zeros((HARM_ROWS, HARM_COLS), dtype=np.float32)
+    for r in range(HARM_NN):
+        allowed = set(chord_pitch_classes(195 + r)) | {(chord_root(195 + r) + i) % 12 for i in extra}
+        for pc in range(12):
+            t[r, pc] = 0.0 if pc in allowed else outside
+    return t
+
+
+def harmony_rows(x):
+    """x as a validated harmony table, float32 [111][16]: [110][12] (chord rows 0 .. 108 and the no-chord row 109) or the
+    full [111][16], entries finite or -inf (a ban).  Raises CommuHipError on another shape, NaN or +inf, a row 110 or pad
+    columns that are not zero, and a row whose 12 entries are all -inf (after a velocity the slot would have nothing to
+    draw)."""
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    what = f"a table of {HARM_OFF} rows of 12 numbers or {HARM_ROWS} rows of {HARM_COLS}"
+    try:
+        a = np.asarray(x, dtype=np.float32)
+    except (TypeError, ValueError):
+        raise CommuHipError(f"harmony: {what} expected, got {type(x).__name__}") from None
+    if a.shape not in ((HARM_OFF, 12), (HARM_ROWS, HARM_COLS)):
+        raise CommuHipError(f"harmony: {what} expected, got shape {a.shape}")
+    bad = np.isnan(a) | (a == np.inf)
+    if bool(bad.any()):
+        r, c = (int(v[0]) for v in np.nonzero(bad))
+        raise CommuHipError(f"harmony: row {r}, entry {c} is {a[r, c]}; finite values or -inf (a ban) expected")
+    if a.shape[0] == HARM_ROWS:
+        for c in np.flatnonzero(a[HARM_OFF]):
+            raise CommuHipError(f"harmony: row {HARM_OFF} is the row of a slot that is off and holds zeros, entry {int(c)} is "
+                                f"{a[HARM_OFF, c]}")
+        for r, c in zip(*np.nonzero(a[:, 12:])):
+            raise CommuHipError(f"harmony: columns 12 .. 15 are padding and hold zeros, row {int(r)}, entry {int(c) + 12} is "
+                                f"{a[r, c + 12]}")
+    for r in range(HARM_OFF):
+        if bool((a[r, :12] == -np.inf).all()):
+            raise CommuHipError(f"harmony: row {r} bans all 12 pitch classes (every entry is -inf), no pitch could be drawn "
+                                f"in that chord")
+    out = np.zeros((HARM_ROWS, HARM_COLS), dtype=np.float32)
+    out[:HARM_OFF, :12] = a[:HARM_OFF, :12]
+    return out
+
+
+def _harmony_request(harmony):
+    """A request's harmony= as a table or None: None / False, True (harmony_table(), strict) or a table (harmony_rows)."""
+    if harmony is None or harmony is False:
+        return None
+    if harmony is True:
+        return harmony_table()
+    return harmony_rows(harmony)
+
+
 class DecodeState:
     """K/V caches + distance-indexed R tables for B sequences of up to Lmax positions.
 
@@ -819,6 +896,11 @@ class ForcedDecoder:
         self.gram = None
         self.gram_on = None
         self._gram_host = None          # host mirror of the table (a re-arm that changes nothing uploads nothing)
+        # harmony (set_harmony): the table fp32 [111][16] and the slots' switches [B], allocated by the first table; None:
+        # the launches a decoder without harmony always made
+        self.harm = None
+        self.harm_on = None
+        self._harm_host = None
         # (the replay of a prompt token takes at most two iterations: the decision to force it, then its append)
         self.ld_trace = 2 * (self.generation_length + 2 + 2 * self.max_prompt) if record_trace else 0
         self.trace = torch.zeros(B, self.ld_trace, dtype=i32, device=dev) if record_trace else None
@@ -958,6 +1040,49 @@ class ForcedDecoder:
     def _gram_args(self):
         return None if self.gram is None else (self.gram, self.gram_on, self.fsm, self.seq)
 
+    def set_harmony(self, table=True, rows: Optional[Sequence[int]] = None):
+        """The harmony constraint for all slots (rows=None) or the listed ones: True (harmony_table(), strict: only chord
+        tones), a table (harmony_rows) or None / False (off).  A slot that is on draws its pitches (ids 3 .. 130, MIDI
+        pitch id - 3) from ((x + bias) + grammar row) + table[r][(id - 3) mod 12], r the row of the last chord token in
+        its seq when the sampling stage runs (109 while there is none) -- the last chord of the prompt for the first draw
+        of a primed slot; no other id is touched.  Only DRAWS are constrained: forced tokens are placed by the rules and a
+        prompt is not checked.  The decoder holds ONE table; a table given here replaces it for every slot that is on.
+        The first table allocates it and the [B] switches -- and a zero bias buffer and an all-off grammar where the decoder
+        has none: the one harmony kernel reads both, and x + 0 and the zero row 7 change no bit -- and drops the captured
+        graphs once, exactly as set_grammar does; later calls rewrite in place, ordered on the current stream.  A slot
+        that is off reads the zero row 110: it draws bit for bit what it drew without the feature.  A decoder that never
+        got a table allocates nothing.  Not enforced: a logit_bias (or a pitch range built from one) that leaves no pitch
+        of an allowed class makes the slot fail its draw after a velocity (Q12) when the grammar is on as well."""
+        idx = np.arange(self.B) if rows is None else np.asarray(list(rows), dtype=np.int64)
+        if idx.ndim != 1 or (idx.size and (idx.min() < 0 or idx.max() >= self.B)):
+            raise CommuHipError(f"rows: slot numbers in [0, {self.B}) expected, got {rows!r}")
+        if table is False:
+            table = None
+        new = None if table is None else (harmony_table() if table is True else harmony_rows(table))
+        if self.harm is None:
+            if new is None:
+                return
+            self.harm = torch.zeros(HARM_ROWS, HARM_COLS, dtype=F32, device=self.dev)
+            self.harm_on = torch.zeros(self.B, dtype=torch.uint8, device=self.dev)
+            if self.bias is None:
+                self.bias = torch.zeros(self.B, VPAD, dtype=F32, device=self.dev)
+            if self.gram is None:
+                self.gram = torch.zeros(N_CLASSES + 1, VPAD, dtype=F32, device=self.dev)
+                self.gram_on = torch.zeros(self.B, dtype=torch.uint8, device=self.dev)
+            self.graph = self.graph_long = None
+        if new is not None and (self._harm_host is None or not np.array_equal(new, self._harm_host)):
+            self.harm.copy_(torch.from_numpy(new))
+            self._harm_host = new
+        val = 0 if new is None else 1
+        if rows is None:
+            self.harm_on.fill_(val)
+        else:
+            for j in idx:
+                self.harm_on[int(j)].fill_(val)
+
+    def _harm_args(self):
+        return None if self.harm is None else (self.harm, self.harm_on, self.fsm, self.chord_tok)
+
     def pre(self):
         call("commu_forcing_pre_rows", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_tok), _p(self.chord_pos),
              self.ld_chord, _p(self.wrong), _p(self.utable), self.ld_u, self.generation_length, _p(self.tok),
@@ -973,7 +1098,8 @@ class ForcedDecoder:
         ops.sample_topk(self.state.logits, self.temperature if t_r is None else t_r, self.top_k if k_r is None else k_r,
                         wrong=self.wrong, uniforms=self.uni, active=self.draw, token=self.token,
                         probs_out=self.probs if want_probs else None, top_p=self.top_p if p_r is None else p_r,
-                        logp_out=logp, bias=self.bias, **({} if self.gram is None else {"grammar": self._gram_args()}))
+                        logp_out=logp, bias=self.bias, **({} if self.gram is None else {"grammar": self._gram_args()}),
+                        **({} if self.harm is None else {"harmony": self._harm_args()}))
         call("commu_forcing_post_rows", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_pos), self.ld_chord,
              _p(self.wrong), _p(self.draw), _p(self.token), None, _p(self.state.klen), _p(self.keep),
              self.state.klen_cap, _p(logp), _p(seq_logp), B, _s())
@@ -990,7 +1116,10 @@ class ForcedDecoder:
                 _p(self.chord_tok), _p(self.chord_pos), self.ld_chord, _p(self.utable), self.ld_u, self.generation_length,
                 _p(self.tok), _p(self.active), _p(self.keep), _p(self.draw), _p(self.uni), _p(self.trace), self.ld_trace,
                 _p(st.klen), st.klen_cap, self.B)
-        if self.gram is not None:
+        if self.harm is not None:          # (set_harmony allocated the bias and the grammar the kernel reads)
+            call("commu_decode_sample_post_pre_harm", *args, _p(self.bias), self.bias.stride(0), _p(self.gram),
+                 self.gram.stride(0), _p(self.gram_on), _p(self.harm), self.harm.stride(0), _p(self.harm_on), _s())
+        elif self.gram is not None:
             call("commu_decode_sample_post_pre_gram", *args, _p(self.bias), 0 if self.bias is None else self.bias.stride(0),
                  _p(self.gram), self.gram.stride(0), _p(self.gram_on), _s())
         elif self.bias is None:
@@ -1252,16 +1381,23 @@ class ForcedDecoder:
     # sampling: a (temperature, top_k, top_p) triple for the slot's next attempt (None: the slot keeps its controls).
     # logit_bias: a constraint row for the slot's next attempt (None: the slot keeps its row; set_logit_bias clears one).
     # grammar: True / False switches the slot's event grammar for its next attempt (None: the slot keeps its switch).
-    def rearm(self, b: int, uniforms_row: Optional[np.ndarray] = None, sampling=None, logit_bias=None, grammar=None):
+    # harmony: True / False switches the slot's harmony constraint for its next attempt (None: the slot keeps its switch).
+    def rearm(self, b: int, uniforms_row: Optional[np.ndarray] = None, sampling=None, logit_bias=None, grammar=None,
+              harmony=None):
         if sampling is not None:
             self.set_sampling(*sampling, rows=[b])
         if logit_bias is not None:
             self.set_logit_bias(logit_bias, rows=[b])
         if grammar is not None:
-            if self.gram is None:
+            if self.gram is None or self._gram_host is None:      # (no table yet: set_harmony's all-off grammar holds zeros)
                 self.set_grammar(True if grammar else None, rows=[b])
             else:                              # (the table stays: one byte changes)
                 self.gram_on[int(b)].fill_(1 if grammar else 0)
+        if harmony is not None:
+            if self.harm is None or self._harm_host is None:
+                self.set_harmony(True if harmony else None, rows=[b])
+            else:
+                self.harm_on[int(b)].fill_(1 if harmony else 0)
         rep0 = self.reports[b]
         rep = ForcingReport(rep0.n_chords, rep0.num_measures)
         self.reports[b] = rep
@@ -1441,17 +1577,19 @@ class BatchedGenerator:
         self._decoders = {}
 
     def decoder(self, B, temperature, top_k, max_chords, top_p=1.0, per_slot: bool = False, max_prompt: int = 0,
-                logit_bias=None, shared: bool = False, grammar=None):
+                logit_bias=None, shared: bool = False, grammar=None, harmony=None):
         """The decoder for B slots, its slots set to the given controls (numbers or one value per slot).  per_slot: the
         caller will read log-probabilities or give slots their own controls later (rearm): the array launches from the
         start.  Otherwise one triple for all slots runs the scalar launches, until a second setting arrives for launches
         that are already captured (ForcedDecoder.__init__).  logit_bias: the request's constraint rows (one for all slots
-        or one per slot; None clears what an earlier request left on this decoder).  shared: the decoder that holds the
+        or one per slot; None clears what an earlier request left on this decoder).  grammar / harmony: the request's event
+        grammar and harmony table (None switches off what an earlier request left).  shared: the decoder that holds the
         request's common prompt once (its own cache layout: kept beside the unshared decoder of the same size)."""
         rows = sampling_rows(B, temperature, top_k, top_p)          # (validated before anything is built)
         if logit_bias is not None:
             logit_bias = logit_bias_rows(logit_bias, B)
         gram_table, gram_rows = _grammar_request(grammar, B)
+        harm_table = _harmony_request(harmony)
         key = (B, self.trace is not None, self.sliding) + (("shared",) if shared else ())
         dec = self._decoders.get(key)
         if dec is None or dec.ld_chord < max_chords or dec.max_prompt < max_prompt:
@@ -1470,13 +1608,24 @@ class BatchedGenerator:
         dec.set_grammar(None)
         if gram_rows:
             dec.set_grammar(gram_table, rows=None if len(gram_rows) == B else gram_rows)
+        # (harmony: likewise; None on a decoder that never had a table allocates nothing)
+        dec.set_harmony(harm_table)
         return dec
+
+    @staticmethod
+    def _one_harmony(harmony):
+        if harmony is not None and not isinstance(harmony, (bool, np.bool_)) and np.ndim(harmony) != 2:
+            raise CommuHipError(f"harmony: one setting for the request expected (True or a table), got shape "
+                                f"{np.shape(harmony)}")
+        return harmony
 
     @torch.no_grad()
     def generate(self, encoded_metas: Sequence[Sequence[int]], input_datas, temperature, top_k, top_p=1.0,
                  return_logprobs: bool = False, prompts: Optional[Sequence[Sequence[int]]] = None, logit_bias=None,
-                 grammar=None):
-        """temperature / top_k / top_p: a number for the batch or one value per sequence.  grammar: None, True (the default
+                 grammar=None, harmony=None):
+        """temperature / top_k / top_p: a number for the batch or one value per sequence.  harmony: None, True (the strict
+        default table: only chord tones) or a table (harmony_rows), one setting for the request -- every pitch a sequence
+        DRAWS is weighed by the chord it is in (ForcedDecoder.set_harmony).  grammar: None, True (the default
         event grammar), a table (grammar_table) or one bool per sequence -- every token such a sequence DRAWS continues a
         group the token-to-MIDI step keeps (ForcedDecoder.set_grammar).  logit_bias: a constraint row
         (token_constraints) for the request or one per sequence -- what a sequence may DRAW; forced tokens and prompts are
@@ -1491,7 +1640,8 @@ class BatchedGenerator:
         max_prompt = 0 if prompts is None else max(len(p) for p in prompts)
         # (shared_prompt: requests with a prompt only -- without one there is nothing but the short context to share)
         dec = self.decoder(B, temperature, top_k, max_chords, top_p, per_slot=return_logprobs, max_prompt=max_prompt,
-                           logit_bias=logit_bias, shared=self.shared_prompt and max_prompt > 0, grammar=grammar)
+                           logit_bias=logit_bias, shared=self.shared_prompt and max_prompt > 0, grammar=grammar,
+                           harmony=self._one_harmony(harmony))
         uniforms = None
         if bool((dec._sampling[0] != 0).any()):
             srcs = self.uniform_sources or [np.random.RandomState(1000 + b).random_sample for b in range(B)]
@@ -1515,7 +1665,7 @@ class BatchedGenerator:
     def generate_stream(self, encoded_meta: Sequence[int], input_data, temperature, top_k, need: int,
                         accept, top_p=1.0, slots: int = 64, seed: int = 0, max_attempts: Optional[int] = None,
                         return_logprobs: bool = False, prompt: Optional[Sequence[int]] = None, logit_bias=None,
-                        share_prompt: bool = False, grammar=None):
+                        share_prompt: bool = False, grammar=None, harmony=None):
         """Attempts of ONE request (the reference's `while idx != num_generate` loop, midi_inferrer.py:338-354, which tries
         one sequence after the other) decoded in up to `slots` parallel slots, CONTINUOUSLY: a slot whose sequence has
         ended is handed to `accept(sequence, report) -> bool` and re-armed with the next attempt while the other slots keep
@@ -1530,6 +1680,7 @@ class BatchedGenerator:
         returns to the primed state).
         logit_bias: one constraint row (token_constraints) for every attempt of the request.
         grammar: None, True (the default event grammar) or a table (grammar_table): one setting for the request.
+        harmony: None, True (harmony_table(), strict) or a table (harmony_rows): one setting for the request.
         share_prompt (opt-in; also on with BatchedGenerator(shared_prompt=True) when a prompt is given): the K/V of the
         context and the prompt are computed and held once for all slots (ForcedDecoder(shared_prompt=True)); the attempts
         returned are the ones the unshared decoder defines, up to the summation order of the attention."""
@@ -1542,6 +1693,7 @@ class BatchedGenerator:
         if grammar is not None and not isinstance(grammar, (bool, np.bool_)) and np.ndim(grammar) != 2:
             raise CommuHipError(f"grammar: one setting for the request expected (True or a table), got shape "
                                 f"{np.shape(grammar)}")
+        harmony = self._one_harmony(harmony)
         max_chords = len(input_data.chord_token_components["chord_token"])
         # each control's schedule, validated on its own (the three may have different lengths)
         n_of = lambda x: 1 if np.ndim(x) == 0 else len(x)
@@ -1554,7 +1706,7 @@ class BatchedGenerator:
         varying = any(bool((c != c[0]).any()) for c in sched)          # (one triple for every attempt: nothing to re-arm)
         dec = self.decoder(B, [t[0] for t in first], [t[1] for t in first], max_chords, [t[2] for t in first],
                            per_slot=return_logprobs or varying, max_prompt=0 if prompt is None else len(prompt),
-                           logit_bias=logit_bias, shared=share, grammar=grammar)
+                           logit_bias=logit_bias, shared=share, grammar=grammar, harmony=harmony)
         started = B
         sampled = bool((sched[0] != 0).any())          # (a greedy attempt reads no variate)
         uni = np.stack([self.attempt_uniforms(seed, a, dec.ld_u) for a in range(B)]) if sampled else None

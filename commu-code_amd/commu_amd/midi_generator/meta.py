@@ -123,6 +123,30 @@ def _chord_vocab() -> Dict[str, int]:
 CHORD_VOCAB = _chord_vocab()
 POSITION_BASE, POSITION_RESOLUTION = 432, 128
 
+# semitones above the root of the nine vocabulary qualities (_QUALS), and the pitch class of the first root: _ROOTS runs
+# a, a#, b, c, ... and MIDI pitch classes count from C = 0, so a = 9, a# = 10, b = 11, c = 0, ..., g# = 8
+_QUAL_INTERVALS = {"": (0, 4, 7), "7": (0, 4, 7, 10), "+": (0, 4, 8), "dim": (0, 3, 6), "m": (0, 3, 7), "m7": (0, 3, 7, 10),
+                   "m7b5": (0, 3, 6, 10), "maj7": (0, 4, 7, 11), "sus4": (0, 5, 7)}
+_ROOT0_PITCH_CLASS = 9
+
+
+def chord_root(token: int) -> int:
+    """MIDI pitch class (C = 0) of the root of chord token 195 .. 302."""
+    if isinstance(token, bool) or int(token) != token or not 195 <= int(token) <= 302:
+        raise ValueError(f"chord_root: a chord token with a root in [195, 302] expected, got {token!r}")
+    return (_ROOT0_PITCH_CLASS + (int(token) - 195) // len(_QUALS)) % 12
+
+
+def chord_pitch_classes(token: int) -> frozenset:
+    """The MIDI pitch classes (C = 0 ... B = 11) of chord token 195 .. 303: root + the quality's intervals; the empty set
+    for Chord_NN (303), which makes no statement.  A pitch token id sounds MIDI pitch id - 3, class (id - 3) mod 12."""
+    if isinstance(token, bool) or int(token) != token or not 195 <= int(token) <= 303:
+        raise ValueError(f"chord_pitch_classes: a chord token in [195, 303] expected, got {token!r}")
+    if int(token) == 303:
+        return frozenset()
+    root = chord_root(token)
+    return frozenset((root + i) % 12 for i in _QUAL_INTERVALS[_QUALS[(int(token) - 195) % len(_QUALS)]])
+
 
 def chord_token_components(chord_progression: Sequence[str], time_signature: str) -> Dict[str, List[int]]:
     """container.py:37-61: one (token, position) per chord CHANGE (and per bar start).  The position of a change

@@ -149,13 +149,15 @@ class InferenceTask:
         return count_notes(seq) > 0
 
     def execute(self, encoded_meta, max_rounds: Optional[int] = None, return_logprobs: bool = False,
-                prompt: Optional[List[int]] = None, logit_bias=None, grammar=None):           # :338-354
+                prompt: Optional[List[int]] = None, logit_bias=None, grammar=None, harmony=None):           # :338-354
         """return_logprobs (not in the reference): (sequences, their log-probability arrays -- ForcedDecoder.logprobs).
         prompt (not in the reference): token ids that follow the meta tokens; every attempt continues them (primed
         generation, BatchedGenerator.generate_stream) and every returned sequence starts with [0] + meta + prompt.
         logit_bias (not in the reference): a constraint row (generate.token_constraints) on what every attempt may draw.
         grammar (not in the reference): True or a table (generate.grammar_table) -- every drawn token continues a group the
-        token-to-MIDI step keeps (generate.event_grammar, BatchedGenerator.generate_stream)."""
+        token-to-MIDI step keeps (generate.event_grammar, BatchedGenerator.generate_stream).
+        harmony (not in the reference): True (only chord tones) or a table (generate.harmony_rows) -- every drawn pitch is
+        weighed by the chord that is sounding (generate.harmony_table, ForcedDecoder.set_harmony)."""
         from ..generate import BatchedGenerator
         data = self.input_data
         glen = self.inference_cfg.GENERATION.generation_length
@@ -190,5 +192,6 @@ class InferenceTask:
                                   max_attempts=None if max_rounds is None else max_rounds * data.num_generate,
                                   return_logprobs=return_logprobs, prompt=None if not prompt else list(prompt),
                                   logit_bias=logit_bias, **({} if slots == 64 else {"slots": slots}),
-                                  **({} if grammar is None else {"grammar": grammar}))
+                                  **({} if grammar is None else {"grammar": grammar}),
+                                  **({} if harmony is None else {"harmony": harmony}))
         return (res[0], res[2]) if return_logprobs else res[0]

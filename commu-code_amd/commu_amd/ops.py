@@ -919,8 +919,21 @@ def _sampling_control(x, name, dtype, nseq, device):
     return None, x
 
 
+def _check_draw_state(kind, device, specs):
+    """The device tensors of sample_topk's grammar= / harmony=: specs of (tensor, name, dtype, shape as text, shape test); a
+    missing `on` means every sequence is on."""
+    for t, name, dtype, shape, fits in specs:
+        if t is None and name == "on":
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != device:
+            raise CommuHipError(f"{kind} {name}: a tensor on the device of the logits expected (no CPU fallback)")
+        if not (t.dtype == dtype and t.is_contiguous() and fits(t)):
+            raise CommuHipError(f"{kind} {name}: contiguous {str(dtype).replace('torch.', '')} {shape} expected, got "
+                                f"{str(t.dtype).replace('torch.', '')} {tuple(t.shape)}")
+
+
 def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=None, token=None, probs_out=None,
-                top_p=1.0, logp_out=None, bias=None, V=729, grammar=None):
+                top_p=1.0, logp_out=None, bias=None, V=729, grammar=None, harmony=None):
     """In-place temperature + softmax + top-k + wrong-token mask + inverse-CDF draw per sequence.
     logits: fp32 [nseq, >=V] (row stride = ld), modified in place (logits[:, 1:V] /= temperature).
     top_p < 1: nucleus filter after the top-k / rejected-token step (an extra mode; the reference has top-k only).
@@ -939,7 +952,13 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
     [nseq] or None (all on), state the int32 forcing records [nseq, commu_forcing_state_ints()], seq int32 [nseq, ld_seq].
     Row c of the table is added after the bias for a sequence whose previous token seq[b][state[b][0] - 1] has class c
     (generate.token_class), row 7 for a sequence that is off; like the bias it is never written back
-    (commu_sample_topk_topp_gram)."""
+    (commu_sample_topk_topp_gram).
+    harmony: (table, on, state, chord_tok) on the device of the logits -- table fp32 [111, >= 12] (generate.harmony_rows), on
+    uint8 [nseq] or None (all on), state as above, chord_tok int32 [nseq, ld_chord]: the chords the forcing rules place.
+    For the pitch ids 3 .. 130 table[r][(id - 3) mod 12] is added after the grammar row, r = chord_tok[b][state[b][F_CUR] - 1]
+    - 195 (109 while F_CUR is 0, 110 for a sequence that is off); no other id is touched and nothing is written back.  One
+    kernel serves it, with a bias and a grammar: where the call has none, a zero bias and an all-off grammar are made
+    here (x + 0 and the zero row 7 change no bit) (commu_sample_topk_topp_harm)."""
     nseq = logits.shape[0]
     V = int(V)
     assert logits.dtype == F32 and logits.stride(1) == 1
@@ -968,26 +987,40 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
             1 if k_s is None else int(k_s), 1.0 if p_s is None else float(p_s), _p(t_r), _p(k_r), _p(p_r), _p(token),
             _p(probs_out), 0 if probs_out is None else probs_out.stride(0), _p(logp_out), _p(bias),
             0 if bias is None else max(int(bias.stride(0)), V))
-    if grammar is None:
+    if grammar is None and harmony is None:
         call("commu_sample_topk_topp_bias", *args, _s())
         return token
-    table, on, state, seq = grammar
     nrec = call("commu_forcing_state_ints")
-    for t, name, dtype, shape in ((table, "table", F32, "[8, >= %d]" % V), (on, "on", torch.uint8, "[%d]" % nseq),
-                                  (state, "state", torch.int32, "[%d, %d]" % (nseq, nrec)),
-                                  (seq, "seq", torch.int32, "[%d, ld_seq]" % nseq)):
-        if t is None and name == "on":
-            continue
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != logits.device:
-            raise CommuHipError(f"grammar {name}: a tensor on the device of the logits expected (no CPU fallback)")
-        ok = t.dtype == dtype and t.is_contiguous() and {
-            "table": t.dim() == 2 and t.shape[0] == 8 and t.shape[1] >= V,
-            "on": tuple(t.shape) == (nseq,),
-            "state": tuple(t.shape) == (nseq, nrec),
-            "seq": t.dim() == 2 and t.shape[0] == nseq and t.shape[1] >= 1}[name]
-        if not ok:
-            raise CommuHipError(f"grammar {name}: contiguous {str(dtype).replace('torch.', '')} {shape} expected, got "
-                                f"{str(t.dtype).replace('torch.', '')} {tuple(t.shape)}")
+    if harmony is not None:
+        htable, hon, hstate, chord_tok = harmony
+        _check_draw_state("harmony", logits.device, (
+            (htable, "table", F32, "[111, >= 12]", lambda t: t.dim() == 2 and t.shape[0] == 111 and t.shape[1] >= 12),
+            (hon, "on", torch.uint8, "[%d]" % nseq, lambda t: tuple(t.shape) == (nseq,)),
+            (hstate, "state", torch.int32, "[%d, %d]" % (nseq, nrec), lambda t: tuple(t.shape) == (nseq, nrec)),
+            (chord_tok, "chord_tok", torch.int32, "[%d, ld_chord]" % nseq,
+             lambda t: t.dim() == 2 and t.shape[0] == nseq and t.shape[1] >= 1)))
+        if grammar is not None and (not isinstance(grammar[2], torch.Tensor) or grammar[2].data_ptr() != hstate.data_ptr()):
+            raise CommuHipError("harmony state: the records the grammar reads expected (one state per sequence)")
+        # The one harmony kernel reads a bias and a grammar: a call without them gets a zero bias and an all-off grammar,
+        # allocated per call.  That serves the stand-alone sampler (tests, probes); ForcedDecoder never takes these two
+        # branches -- set_harmony allocates its buffers once and body() passes them.
+        if grammar is None:
+            grammar = (torch.zeros(8, V, dtype=F32, device=logits.device),
+                       torch.zeros(nseq, dtype=torch.uint8, device=logits.device), hstate,
+                       torch.zeros(nseq, 1, dtype=torch.int32, device=logits.device))
+        if bias is None:
+            bias = torch.zeros(nseq, V, dtype=F32, device=logits.device)
+            args = args[:-2] + (_p(bias), V)
+    table, on, state, seq = grammar
+    _check_draw_state("grammar", logits.device, (
+        (table, "table", F32, "[8, >= %d]" % V, lambda t: t.dim() == 2 and t.shape[0] == 8 and t.shape[1] >= V),
+        (on, "on", torch.uint8, "[%d]" % nseq, lambda t: tuple(t.shape) == (nseq,)),
+        (state, "state", torch.int32, "[%d, %d]" % (nseq, nrec), lambda t: tuple(t.shape) == (nseq, nrec)),
+        (seq, "seq", torch.int32, "[%d, ld_seq]" % nseq, lambda t: t.dim() == 2 and t.shape[0] == nseq and t.shape[1] >= 1)))
+    if harmony is not None:
+        call("commu_sample_topk_topp_harm", *args, _p(table), table.stride(0), _p(on), _p(state), _p(seq), seq.stride(0),
+             _p(htable), htable.stride(0), _p(hon), _p(chord_tok), chord_tok.stride(0), _s())
+        return token
     call("commu_sample_topk_topp_gram", *args, _p(table), table.stride(0), _p(on), _p(state), _p(seq), seq.stride(0), _s())
     return token
 

@@ -46,6 +46,8 @@ __device__ __forceinline__ int wscan_i(int v, int lane) {
 
 // ------------------------------------------------------------------------------------------------ sampling step (K15)
 constexpr int PER_LANE = 12;      // 64 * 12 = 768 >= 729: lane l owns ids [12 l, 12 l + 12)
+constexpr int TOK_EOS = 1, TOK_BAR = 2, TOK_CHORD_LO = 195, TOK_CHORD_HI = 303, TOK_POS0 = 432, POS_RES = 128;
+constexpr int VOCAB = 729;
 
 // The sampling controls of one sequence: scalars for the whole launch, or per-sequence device arrays ([B] each, null: the
 // scalar applies) -- the slots of one batch may sample at different settings, and a captured graph follows the arrays.
@@ -102,7 +104,33 @@ __device__ __forceinline__ int token_class(int t) {
     c = t >= 560 ? 0 : c;
     return c;
 }
-template <bool BIAS, bool GRAM = false>
+// HARM (Harmony: table fp32 [111][ld], ld >= 12): a third additive term, chosen by the chord the sequence is in.  Row r of
+//   the table is 12 values by MIDI pitch class (column 0: C) and is added at the pitch ids only -- token id is MIDI pitch
+//   id - 3 (TOK_PITCH_LO .. TOK_PITCH_HI): y[id] = ((x[id] + bias[b][id]) + table[c][id]) + harm[r][(id - 3) mod 12] for
+//   3 <= id <= 130, in that fp32 order; every other id gets NO third add.  r = t - 195 for the last chord token t
+//   (195 .. 303) of seq when the stage runs, 109 while seq holds none, 110 (zeros by convention) for a sequence whose
+//   switch is off.  A chord enters seq only as a forced token, taken from chord_tok[b][F_CUR] when F_CUR is incremented
+//   and appended by the next iteration with no draw in between, and a drawn chord is never appended (forcing_pre_body /
+//   forcing_post_body; the prompt replay runs the same bodies): at every draw the last chord of seq is
+//   chord_tok[b][F_CUR - 1], and there is none while F_CUR == 0 (tests/test_harmony_host.py walks the rules to show it).
+//   So the row is record -> chord token -> 12 floats, as many dependent loads as the grammar's record -> previous token ->
+//   row.  The chord token load is issued beside the grammar's previous-token load; the row's loads are NOT beside the
+//   grammar's: as compiled they go out after the grammar row's, once the switch byte (a vector load queued behind the
+//   logits and bias loads) and the chord token are both here, one scalar round trip behind the grammar's chain (measured:
+//   docs/EXPERIMENTS.md 8s).
+//   The row index is uniform over the wave (scalar, no branch on it), and since a lane owns PER_LANE = 12 consecutive ids
+//   the pitch class of its element e is (e + 9) mod 12 for every lane: the 12 values are wave-uniform too, only the range
+//   test is per lane.  All that is said of the bias holds: before top-k, never written back, -inf bans.  Without HARM
+//   nothing of `h` is looked at.
+struct Harmony {
+    const float* table;
+    int ld;
+    const int* chord_row;   // the sequence's row of chord_tok
+    int cur, ld_chord;      // chords consumed so far (the record's F_CUR; clamped into the row whatever it holds)
+    int on;                 // the sequence's switch
+};
+constexpr int TOK_PITCH_LO = 3, TOK_PITCH_HI = 130, HARM_NO_CHORD = 109, HARM_OFF = 110;
+template <bool BIAS, bool GRAM = false, bool HARM = false>
 __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restrict__ logits, int ld, int V,
                                                  const unsigned char* __restrict__ wrong, int ldw,
                                                  const float* __restrict__ uni,
@@ -111,7 +139,8 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
                                                  int ldp, float top_p, SamplingRows rows, bool want_logp,
                                                  float* __restrict__ logp_out, TokenLogp& lp,
                                                  const float* __restrict__ bias = nullptr, int ld_bias = 0,
-                                                 Grammar g = Grammar{nullptr, 0, nullptr, 0, 0, 0}) {
+                                                 Grammar g = Grammar{nullptr, 0, nullptr, 0, 0, 0},
+                                                 Harmony h = Harmony{nullptr, 0, nullptr, 0, 0, 0}) {
     float* lg = logits + (size_t)b * ld;
     // The optional per-sequence inputs -- the active flag and this sequence's controls -- are loaded unconditionally: a null
     // array reads a valid word of this sequence instead (token[b], logits[b][0]), which is then ignored.  So they are in
@@ -128,6 +157,8 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
     for (int e = 0; e < PER_LANE; ++e) raw[e] = lg[min(base + e, V - 1)];
     int prev = 0;                 // (GRAM) the last token of seq: every lane loads the same word
     if constexpr (GRAM) prev = g.seq_row[min(max(g.len, 1), g.ld_seq) - 1];
+    int chord = 0;                // (HARM) the last chord placed, chord_tok[b][F_CUR - 1]: likewise one word for all lanes
+    if constexpr (HARM) chord = h.chord_row[min(max(h.cur, 1), h.ld_chord) - 1];
     float bv[PER_LANE];           // (BIAS) this lane's entries of the bias row, in the same batch of loads
     if constexpr (BIAS) {
 #pragma unroll
@@ -140,6 +171,16 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
         const int row = __builtin_amdgcn_readfirstlane(g.on != 0 ? token_class(prev) : 7);
 #pragma unroll
         for (int e = 0; e < PER_LANE; ++e) gv[e] = g.table[(size_t)row * g.ld + min(base + e, V - 1)];
+    }
+    // (HARM) the 12 pitch-class values of the chord's row, the same for every lane: element e of a lane is id 12 l + e,
+    // MIDI pitch 12 l + e - 3, pitch class (e + 9) mod 12
+    float hv[PER_LANE];
+    if constexpr (HARM) {
+        static_assert(PER_LANE == 12, "a lane's element e has pitch class (e + 9) mod 12 only while it owns 12 consecutive ids");
+        const bool is_chord = h.cur >= 1 && chord >= TOK_CHORD_LO && chord <= TOK_CHORD_HI;
+        const int row = __builtin_amdgcn_readfirstlane(h.on != 0 ? (is_chord ? chord - TOK_CHORD_LO : HARM_NO_CHORD) : HARM_OFF);
+#pragma unroll
+        for (int e = 0; e < PER_LANE; ++e) hv[e] = h.table[(size_t)row * h.ld + (e + 9) % 12];
     }
     unsigned wmask = 0u;          // the rejected ("wrong") tokens of this lane
     if (wrong != nullptr) {
@@ -170,6 +211,7 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
             const int id = base + e;
             if constexpr (BIAS) raw[e] += bv[e];               // greedy writes nothing back: the row drawn from is y
             if constexpr (GRAM) raw[e] += gv[e];
+            if constexpr (HARM) raw[e] = (id >= TOK_PITCH_LO && id <= TOK_PITCH_HI) ? raw[e] + hv[e] : raw[e];
             if (id >= 1 && id < V && raw[e] > best) { best = raw[e]; bi = id; }
         }
         const float wbest = wmax_f(best);                      // ties: the lowest id
@@ -197,6 +239,7 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
             float y = x;
             if constexpr (BIAS) y = in ? x + bv[e] : -INFINITY;          // (the bias is not written back)
             if constexpr (GRAM) y = in ? y + gv[e] : -INFINITY;          // (nor the grammar row)
+            if constexpr (HARM) y = (id >= TOK_PITCH_LO && id <= TOK_PITCH_HI) ? y + hv[e] : y;      // (nor the chord's)
             p[e] = y;
             mx = fmaxf(mx, y);
         }
@@ -391,6 +434,14 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
                     if (base + e == drawn) gd = gv[e];
                 xd += lane_f(gd, owner);
             }
+            if constexpr (HARM) {
+                float hd = 0.f;
+#pragma unroll
+                for (int e = 0; e < PER_LANE; ++e)
+                    if (base + e == drawn) hd = hv[e];
+                hd = lane_f(hd, owner);
+                xd = (drawn >= TOK_PITCH_LO && drawn <= TOK_PITCH_HI) ? xd + hd : xd;
+            }
         }
         lp.full = drawn < 0 ? NAN : (xd - lmx) - logf(lsum);
         lp.kept = drawn < 0 ? NAN : (temperature == 0.f ? 0.f : logf(pd));
@@ -401,8 +452,6 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
 
 
 // ------------------------------------------------------------------------------------------------ forcing rules
-constexpr int TOK_EOS = 1, TOK_BAR = 2, TOK_CHORD_LO = 195, TOK_CHORD_HI = 303, TOK_POS0 = 432, POS_RES = 128;
-constexpr int VOCAB = 729;
 
 // field indices of the int32 state record (commu_forcing_state_ints() ints per sequence)
 enum {

@@ -70,12 +70,19 @@ struct LoopStageArgsGram : LoopStageArgs {
     const float* gram; int ld_gram;
     const unsigned char* gram_on;
 };
-template <bool GRAM>
+// (HARM) the harmony table [111][ld_harm] and the slots' switches [B]: likewise arguments of the harmony kernel only
+struct LoopStageArgsHarm : LoopStageArgsGram {
+    const float* harm; int ld_harm;
+    const unsigned char* harm_on;
+};
+template <bool GRAM, bool HARM = false>
 struct LoopArgsOf { using type = LoopStageArgs; };
 template <>
-struct LoopArgsOf<true> { using type = LoopStageArgsGram; };
-template <bool BIAS, bool GRAM>
-__global__ __launch_bounds__(64) void sample_post_pre_kernel(typename LoopArgsOf<GRAM>::type a) {
+struct LoopArgsOf<true, false> { using type = LoopStageArgsGram; };
+template <>
+struct LoopArgsOf<true, true> { using type = LoopStageArgsHarm; };
+template <bool BIAS, bool GRAM, bool HARM = false>
+__global__ __launch_bounds__(64) void sample_post_pre_kernel(typename LoopArgsOf<GRAM, HARM>::type a) {
     const int b = blockIdx.x, lane = threadIdx.x;
     if (a.trace != nullptr && lane == 0) a.trace[b * 4 + 0] = wall_clock64();
     int rec[F_COUNT];                                  // the record travels through the three stages in lane 0's registers;
@@ -93,10 +100,18 @@ __global__ __launch_bounds__(64) void sample_post_pre_kernel(typename LoopArgsOf
         g = Grammar{a.gram, a.ld_gram, a.seq + (size_t)b * a.ld_seq, rec[F_LEN], a.ld_seq,
                     a.gram_on != nullptr ? (int)on_b : 1};
     }
-    const int drawn = sample_topk_body<BIAS, GRAM>(b, lane, a.logits, a.ld, a.V, a.wrong, VOCAB, a.uni, a.draw,
-                                                   a.temperature, a.top_k, a.token, a.probs_out, a.ldp, a.top_p, a.rows,
-                                                   a.logp != nullptr || a.seq_logp != nullptr, a.logp, lp, a.bias,
-                                                   a.ld_bias, g);
+    Harmony h{nullptr, 0, nullptr, 0, 0, 0};
+    if constexpr (HARM) {
+        // the same for the chord: the switch with the flags, the record's chord count as it was loaded; the chord token
+        // chord_tok[b][F_CUR - 1] is the body's load, beside the previous token
+        const unsigned char on_b = *(a.harm_on != nullptr ? a.harm_on + b : a.draw + b);
+        h = Harmony{a.harm, a.ld_harm, a.chord_tok + (size_t)b * a.ld_chord, rec[F_CUR], a.ld_chord,
+                    a.harm_on != nullptr ? (int)on_b : 1};
+    }
+    const int drawn = sample_topk_body<BIAS, GRAM, HARM>(b, lane, a.logits, a.ld, a.V, a.wrong, VOCAB, a.uni, a.draw,
+                                                         a.temperature, a.top_k, a.token, a.probs_out, a.ldp, a.top_p,
+                                                         a.rows, a.logp != nullptr || a.seq_logp != nullptr, a.logp, lp,
+                                                         a.bias, a.ld_bias, g, h);
     __syncthreads();
     if (a.trace != nullptr && lane == 0) a.trace[b * 4 + 1] = wall_clock64();
     forcing_post_body(b, lane, rec, a.seq, a.ld_seq, a.chord_pos, a.ld_chord, a.wrong, a.draw, a.token, nullptr, a.klen,
@@ -271,6 +286,42 @@ static unsigned long long* g_loop_trace = nullptr;
 /* diagnostics: following commu_decode_sample_post_pre launches write buf[sequence][4] timestamps (null: off) */
 extern "C" int commu_decode_loop_trace(unsigned long long* buf) {
     g_loop_trace = buf;
+    return 0;
+}
+
+extern "C" int commu_decode_sample_post_pre_harm(float* logits, int ld, int V, unsigned char* wrong, float temperature,
+                                                 int top_k, float top_p, const float* temperature_rows,
+                                                 const int* top_k_rows, const float* top_p_rows, int* token,
+                                                 float* probs_out, int ldp, float* logp, float* seq_logp, int* state,
+                                                 int* seq, int ld_seq, const int* chord_tok, const int* chord_pos,
+                                                 int ld_chord, const float* utable, int ld_u, int max_iters, long long* tok,
+                                                 unsigned char* active, unsigned char* keep, unsigned char* draw, float* uni,
+                                                 int* trace, int ld_trace, int* klen, int lmax, int B, const float* bias,
+                                                 int ld_bias, const float* gram, int ld_gram, const unsigned char* gram_on,
+                                                 const float* harm, int ld_harm, const unsigned char* harm_on,
+                                                 hipStream_t stream) {
+    if (harm == nullptr)
+        return commu_decode_sample_post_pre_gram(logits, ld, V, wrong, temperature, top_k, top_p, temperature_rows,
+                                                 top_k_rows, top_p_rows, token, probs_out, ldp, logp, seq_logp, state, seq,
+                                                 ld_seq, chord_tok, chord_pos, ld_chord, utable, ld_u, max_iters, tok, active,
+                                                 keep, draw, uni, trace, ld_trace, klen, lmax, B, bias, ld_bias, gram, ld_gram,
+                                                 gram_on, stream);
+    if (B <= 0) return 0;
+    if (V != VOCAB || V > 64 * PER_LANE || ld_seq < 2 || ld_chord < 1 || ld_u < 1) return -22;
+    // (the kernel reads harm[0 .. 110][0 .. 11] and finds the chord through the record: chord_tok[b][F_CUR - 1])
+    if (ld_harm < 12 || state == nullptr || chord_tok == nullptr) return -22;
+    // (one instantiation: the caller passes a zero bias and an all-off grammar where it has none)
+    if (bias == nullptr || ld_bias < V || gram == nullptr || ld_gram < V || seq == nullptr) return -22;
+    if ((top_k_rows == nullptr && (top_k < 1 || top_k > V)) || (top_p_rows == nullptr && !(top_p > 0.f))) return -22;
+    LoopStageArgsHarm a;
+    static_cast<LoopStageArgs&>(a) =
+        LoopStageArgs{logits, ld, V, wrong, temperature, top_k, top_p, SamplingRows{temperature_rows, top_k_rows, top_p_rows},
+                      token, probs_out, ldp, logp, seq_logp, state, seq, ld_seq, chord_tok, chord_pos, ld_chord, utable, ld_u,
+                      max_iters, tok, active, keep, draw, uni, trace, ld_trace, klen, lmax, g_loop_trace, bias, ld_bias};
+    a.gram = gram; a.ld_gram = ld_gram; a.gram_on = gram_on;
+    a.harm = harm; a.ld_harm = ld_harm; a.harm_on = harm_on;
+    COMMU_LAUNCH((sample_post_pre_kernel<true, true, true>), dim3(B), dim3(64), 0, stream, a);
+    COMMU_LAUNCH_CHECK();
     return 0;
 }
 

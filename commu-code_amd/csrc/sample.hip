@@ -9,7 +9,9 @@
 // The controls may be per-sequence device arrays, and the step can report the log-probabilities of the token it drew
 // (decode_loop.h: SamplingRows, TokenLogp).  An optional additive row per sequence constrains what may be drawn (bias, then
 // top-k: sample_topk_body<BIAS>); a table of such rows, picked by the class of the sequence's previous token, makes an event
-// grammar (<GRAM>, kernels of their own); without either the launch is the kernel that never heard of them.
+// grammar (<GRAM>, kernels of their own); a table of pitch-class rows, picked by the last chord the forcing rules placed, keeps
+// the drawn pitches in the sounding chord (<HARM>, one more kernel); without any of them the launch is the kernel that never
+// heard of them.
 #include "decode_loop.h"
 #include "commu_hip.h"
 
@@ -56,7 +58,66 @@ __global__ __launch_bounds__(64) void sample_topk_gram_kernel(float* __restrict_
                                  probs_out, ldp, top_p, rows, logp_out != nullptr, logp_out, lp, bias, ld_bias, g);
 }
 
+// the same with a harmony table: one instantiation (a bias and a grammar that change nothing are a zero row and an
+// all-off switch array), again a kernel of its own with its own arguments
+__global__ __launch_bounds__(64) void sample_topk_harm_kernel(float* __restrict__ logits, int ld, int V,
+                                                              const unsigned char* __restrict__ wrong, int ldw,
+                                                              const float* __restrict__ uni,
+                                                              const unsigned char* __restrict__ active,
+                                                              float temperature, int top_k,
+                                                              int* __restrict__ token, float* __restrict__ probs_out,
+                                                              int ldp, float top_p, SamplingRows rows,
+                                                              float* __restrict__ logp_out,
+                                                              const float* __restrict__ bias, int ld_bias,
+                                                              const float* __restrict__ gram, int ld_gram,
+                                                              const unsigned char* __restrict__ gram_on,
+                                                              const int* __restrict__ state, const int* __restrict__ seq,
+                                                              int ld_seq, const float* __restrict__ harm, int ld_harm,
+                                                              const unsigned char* __restrict__ harm_on,
+                                                              const int* __restrict__ chord_tok, int ld_chord) {
+    TokenLogp lp;
+    // the record's length and chord count and the two switches are loaded here (a null switch array reads a valid byte
+    // of this sequence, which is then ignored); the previous token and the chord token are the body's loads
+    const int b = blockIdx.x;
+    const unsigned char gon_b = *(gram_on != nullptr ? gram_on + b : reinterpret_cast<const unsigned char*>(token + b));
+    const unsigned char hon_b = *(harm_on != nullptr ? harm_on + b : reinterpret_cast<const unsigned char*>(token + b));
+    const Grammar g{gram, ld_gram, seq + (size_t)b * ld_seq, state[(size_t)b * F_COUNT + F_LEN], ld_seq,
+                    gram_on != nullptr ? (int)gon_b : 1};
+    const Harmony h{harm, ld_harm, chord_tok + (size_t)b * ld_chord, state[(size_t)b * F_COUNT + F_CUR], ld_chord,
+                    harm_on != nullptr ? (int)hon_b : 1};
+    sample_topk_body<true, true, true>(b, threadIdx.x, logits, ld, V, wrong, ldw, uni, active, temperature, top_k, token,
+                                       probs_out, ldp, top_p, rows, logp_out != nullptr, logp_out, lp, bias, ld_bias, g, h);
+}
+
 }  // namespace
+
+extern "C" int commu_sample_topk_topp_harm(float* logits, int ld, int nseq, int V, const unsigned char* wrong, int ldw,
+                                           const float* uniforms, const unsigned char* active, float temperature,
+                                           int top_k, float top_p, const float* temperature_rows, const int* top_k_rows,
+                                           const float* top_p_rows, int* token, float* probs_out, int ldp,
+                                           float* logp_out, const float* bias, int ld_bias, const float* gram, int ld_gram,
+                                           const unsigned char* gram_on, const int* state, const int* seq, int ld_seq,
+                                           const float* harm, int ld_harm, const unsigned char* harm_on,
+                                           const int* chord_tok, int ld_chord, hipStream_t stream) {
+    if (harm == nullptr)
+        return commu_sample_topk_topp_gram(logits, ld, nseq, V, wrong, ldw, uniforms, active, temperature, top_k, top_p,
+                                           temperature_rows, top_k_rows, top_p_rows, token, probs_out, ldp, logp_out, bias,
+                                           ld_bias, gram, ld_gram, gram_on, state, seq, ld_seq, stream);
+    if (nseq <= 0) return 0;
+    // (the kernel reads harm[0 .. 110][0 .. 11] and finds the chord through the record: chord_tok[b][F_CUR - 1])
+    if (ld_harm < 12 || state == nullptr || chord_tok == nullptr || ld_chord < 1) return -22;
+    // (one instantiation: the caller passes a zero bias and an all-off grammar where it has none)
+    if (bias == nullptr || ld_bias < V || gram == nullptr || ld_gram < V || seq == nullptr || ld_seq < 1) return -22;
+    if (V > 64 * PER_LANE || V < 2 || (top_k_rows == nullptr && (top_k < 1 || top_k > V)) ||
+        (top_p_rows == nullptr && !(top_p > 0.f)))
+        return -22;
+    const SamplingRows rows{temperature_rows, top_k_rows, top_p_rows};
+    COMMU_LAUNCH(sample_topk_harm_kernel, dim3(nseq), dim3(64), 0, stream, logits, ld, V, wrong, ldw, uniforms, active,
+                 temperature, top_k, token, probs_out, ldp, top_p, rows, logp_out, bias, ld_bias, gram, ld_gram, gram_on,
+                 state, seq, ld_seq, harm, ld_harm, harm_on, chord_tok, ld_chord);
+    COMMU_LAUNCH_CHECK();
+    return 0;
+}
 
 extern "C" int commu_sample_topk_topp_gram(float* logits, int ld, int nseq, int V, const unsigned char* wrong, int ldw,
                                            const float* uniforms, const unsigned char* active, float temperature,

@@ -53,6 +53,16 @@ def parse_args():
     # token continues such a group (commu_amd.generate.event_grammar).  Forced tokens and --prompt_tokens are not affected.
     model_arg_parser.add_argument("--grammar", action="store_true",
                                   help="event grammar: every drawn token continues a note or chord group")
+    # not in the reference (whose notes are free to leave the chord chart): weigh every DRAWN pitch by the chord that is
+    # sounding (commu_amd.generate.harmony_table).  chord: only chord tones are drawn; soft: the other pitch classes get
+    # -X on the scale the softmax sees (--harmony_penalty X); FILE.json: a table of 110 rows (the chord tokens 195 .. 303,
+    # then "no chord yet") of 12 numbers by pitch class (C first), null = banned.  Forced tokens and --prompt_tokens are not
+    # affected.  Combines with every other option.
+    model_arg_parser.add_argument("--harmony", type=str, default=None, metavar="{chord,soft,FILE.json}",
+                                  help="harmony constraint: drawn pitches follow the sounding chord (chord: strictly, "
+                                       "soft: by --harmony_penalty, or a JSON table of 110 rows of 12 numbers, null = banned)")
+    model_arg_parser.add_argument("--harmony_penalty", type=float, default=4.0,
+                                  help="what --harmony soft subtracts from the pitches outside the chord (default: %(default)s)")
     # not in the reference (which decodes one sequence at a time): how many attempts are decoded side by side.  1 .. 256;
     # up to 256 slots run the fused layer-tail launches ("Supported shapes").  The sequences returned do
     # not depend on it.  (checked by check_decode_slots: the range is named in its message)
@@ -157,6 +167,32 @@ def read_constraints(path=None, pitch_min=None, pitch_max=None):
     return token_constraints(ban=ban, bias=bias, pitch_range=pitch)
 
 
+def read_harmony(setting=None, penalty=4.0):
+    """The harmony table of --harmony / --harmony_penalty (None when the flag is not given); host code only, raises
+    (commu_amd.generate.CommuHipError, ValueError) on an unreadable or ill-shaped file or a penalty that is no penalty."""
+    if setting is None:
+        return None
+    from commu_amd.generate import harmony_rows, harmony_table
+    if setting == "chord":
+        return harmony_table()
+    if setting == "soft":
+        if isinstance(penalty, bool) or not isinstance(penalty, (int, float)) or not 0 <= penalty < float("inf"):
+            raise ValueError(f"--harmony_penalty: a finite number >= 0 expected, got {penalty!r}")
+        return harmony_table(outside=-float(penalty))
+    try:
+        with open(setting) as f:
+            doc = json.load(f)
+    except OSError as e:
+        raise ValueError(f"--harmony: chord, soft or a readable JSON file expected, got {setting!r} ({e.strerror})") from None
+    except json.JSONDecodeError as e:
+        raise ValueError(f"--harmony: {setting}: not JSON ({e})") from None
+    if not isinstance(doc, list) or len(doc) != 110 or not all(isinstance(r, list) and len(r) == 12 for r in doc):
+        raise ValueError(f"--harmony: {setting}: a list of 110 rows of 12 numbers (null: banned) expected")
+    if not all(v is None or (isinstance(v, (int, float)) and not isinstance(v, bool)) for r in doc for v in r):
+        raise ValueError(f"--harmony: {setting}: a list of 110 rows of 12 numbers (null: banned) expected")
+    return harmony_rows([[float("-inf") if v is None else float(v) for v in r] for r in doc])
+
+
 from commu_amd.midi_generator.replicas import generate_on_device, replica_worker, split_num_generate  # noqa: E402
 
 
@@ -178,20 +214,22 @@ def main(model_args, input_args, training_cfg=None, device_indices=None):
     # (refused here when malformed: before a model is loaded or a replica started)
     logit_bias = read_constraints(in_args.pop("logit_bias", None), in_args.pop("pitch_min", None),
                                   in_args.pop("pitch_max", None))
+    harmony = read_harmony(getattr(model_args, "harmony", None), getattr(model_args, "harmony_penalty", 4.0))      # (likewise)
     if device_indices is None:
         n_vis = torch.cuda.device_count()
         device_indices = list(range(max(1, n_vis if gpus is None else min(gpus, n_vis))))
     shares = split_num_generate(in_args["num_generate"], len(device_indices))
     if len(shares) == 1:
         encoded_meta, sequences, *lps = generate_on_device(model_args, in_args, device_indices[0], shares[0], 0, max_rounds,
-                                                           training_cfg, want_lp, prompt, logit_bias)
+                                                           training_cfg, want_lp, prompt, logit_bias, harmony)
         logprobs = lps[0] if want_lp else None
     else:
         import torch.multiprocessing as mp
         ctx = mp.get_context("spawn")          # (never fork / exec a process that has initialised the GPU)
         q = ctx.Queue()
         procs = [ctx.Process(target=replica_worker, args=(r, device_indices[r], model_args, in_args, share, max_rounds,
-                                                    training_cfg, q, want_lp, prompt, logit_bias)) for r, share in enumerate(shares)]
+                                                    training_cfg, q, want_lp, prompt, logit_bias, harmony))
+                 for r, share in enumerate(shares)]
         for p_ in procs:
             p_.start()
         # a replica that dies natively (GPU fault, OOM kill) never reports: poll the queue and the processes

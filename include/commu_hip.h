@@ -482,6 +482,29 @@ int commu_sample_topk_topp_gram(float* logits, int ld, int nseq, int V, const un
                                 const float* bias, int ld_bias, const float* gram, int ld_gram,
                                 const unsigned char* gram_on, const int* state, const int* seq, int ld_seq,
                                 hipStream_t stream);
+/* the same with a HARMONY table: a third additive term chosen by the chord the sequence is in, so that the pitches drawn
+ * fit the chord that is sounding.  harm: fp32 [111][ld_harm], ld_harm >= 12 (16: a row is one 64-byte line), optional.
+ * Row r holds 12 values by MIDI pitch class (column 0: C); token id is MIDI pitch id - 3.  r = t - 195 for the last
+ * chord token t (195 .. 303: 12 roots x 9 qualities, then Chord_NN) of seq[b][0 .. F_LEN) when the stage runs, 109 while
+ * seq holds none, 110 (zeros by convention) for a sequence whose switch harm_on[b] is 0 (harm_on == null: every sequence
+ * is on).  A chord enters seq only as a forced token that the rules take from chord_tok[b][F_CUR] (int32
+ * [nseq][ld_chord]) while they increment F_CUR, with no draw before it is appended, so the kernel reads
+ * chord_tok[b][state[b][F_CUR] - 1] (none while F_CUR is 0); a Q5 re-draw sees the same row.
+ *   y[id] = ((x[id] + bias[b][id]) + gram[c][id]) + harm[r][(id - 3) mod 12] for 3 <= id <= 130, in this fp32 order; every
+ *   other id gets no third add.  All that is said of the bias and the grammar row holds: before top-k, never written
+ *   back, probs_out exactly 0 at banned ids, full the log-softmax of y, a row with nothing left takes the Q12 exit.
+ * One kernel serves it, with a bias and a grammar: a caller that has none passes a zero bias row and gram_on zeros (x + 0
+ * is x and row 7 is zeros: bit for bit the draw without them).
+ * harm == null: commu_sample_topk_topp_gram bit for bit, with the kernel it always launched.
+ * ld_harm < 12, ld_chord < 1, a table without state / chord_tok, or without bias / gram / seq: -22. */
+int commu_sample_topk_topp_harm(float* logits, int ld, int nseq, int V, const unsigned char* wrong, int ldw,
+                                const float* uniforms, const unsigned char* active, float temperature, int top_k,
+                                float top_p, const float* temperature_rows, const int* top_k_rows,
+                                const float* top_p_rows, int* token, float* probs_out, int ldp, float* logp_out,
+                                const float* bias, int ld_bias, const float* gram, int ld_gram,
+                                const unsigned char* gram_on, const int* state, const int* seq, int ld_seq,
+                                const float* harm, int ld_harm, const unsigned char* harm_on, const int* chord_tok,
+                                int ld_chord, hipStream_t stream);
 
 /* ---- single-token decode step with a K/V cache (forward_generate with qlen 1, model.py:606-628, as
  * called by midi_inferrer.py:199-207).  Caches are bf16 [B][H][Lmax][DH] per layer; klen[b] = valid rows
@@ -687,6 +710,22 @@ int commu_decode_sample_post_pre_gram(float* logits, int ld, int V, unsigned cha
                                       float* uni, int* trace, int ld_trace, int* klen, int lmax, int B,
                                       const float* bias, int ld_bias, const float* gram, int ld_gram,
                                       const unsigned char* gram_on, hipStream_t stream);
+/* The same launch with the sampling stage of commu_sample_topk_topp_harm: harm fp32 [111][ld_harm] (ld_harm >= 12),
+ * harm_on [B] bytes (null: all on).  The chord is chord_tok[b][F_CUR - 1] of the record the launch holds anyway; the
+ * sampling stage issues that load beside the grammar's previous-token load.  One kernel, with a bias and a grammar (pass a
+ * zero bias and gram_on zeros where there is none).  Forced tokens and prompts are not draws: not affected, not checked.
+ * harm == null: commu_decode_sample_post_pre_gram bit for bit, with the kernel it always launched.  ld_harm < 12, or a
+ * table without bias / gram: -22. */
+int commu_decode_sample_post_pre_harm(float* logits, int ld, int V, unsigned char* wrong, float temperature, int top_k,
+                                      float top_p, const float* temperature_rows, const int* top_k_rows,
+                                      const float* top_p_rows, int* token, float* probs_out, int ldp, float* logp,
+                                      float* seq_logp, int* state, int* seq, int ld_seq, const int* chord_tok,
+                                      const int* chord_pos, int ld_chord, const float* utable, int ld_u, int max_iters,
+                                      long long* tok, unsigned char* active, unsigned char* keep, unsigned char* draw,
+                                      float* uni, int* trace, int ld_trace, int* klen, int lmax, int B,
+                                      const float* bias, int ld_bias, const float* gram, int ld_gram,
+                                      const unsigned char* gram_on, const float* harm, int ld_harm,
+                                      const unsigned char* harm_on, hipStream_t stream);
 /* ---- primed generation: enter the loop at an arbitrary point of a sequence (continue a given token prefix).
  * commu_forcing_replay runs the two transitions above over prompt[b][0 .. prompt_len[b]) WITHOUT a model step, starting
  * from the record, seq and klen as a load of the conditioning context leaves them (midi_inferrer.py:186-197): wherever
