@@ -53,6 +53,39 @@ class TnProblem(C.Structure):
                 ("colsum_off", C.c_longlong)]
 
 
+class SampleArgs(C.Structure):
+    """commu_sample_args (the header documents every field)."""
+    _fields_ = [("struct_bytes", C.c_uint),
+                ("logits", c_p), ("wrong", c_p), ("uniforms", c_p), ("active", c_p),
+                ("ld", c_i), ("nseq", c_i), ("V", c_i), ("ldw", c_i),
+                ("temperature_rows", c_p), ("top_k_rows", c_p), ("top_p_rows", c_p),
+                ("temperature", c_f), ("top_k", c_i), ("top_p", c_f),
+                ("token", c_p), ("probs_out", c_p), ("logp_out", c_p), ("ldp", c_i),
+                ("bias", c_p), ("gram", c_p), ("gram_on", c_p), ("harm", c_p), ("harm_on", c_p),
+                ("ld_bias", c_i), ("ld_gram", c_i), ("ld_harm", c_i),
+                ("state", c_p), ("seq", c_p), ("chord_tok", c_p), ("ld_seq", c_i), ("ld_chord", c_i)]
+
+
+class DecodeLoopArgs(C.Structure):
+    """commu_decode_loop_args (the header documents every field)."""
+    _fields_ = [("struct_bytes", C.c_uint),
+                ("logits", c_p), ("wrong", c_p), ("ld", c_i), ("V", c_i), ("B", c_i),
+                ("temperature_rows", c_p), ("top_k_rows", c_p), ("top_p_rows", c_p),
+                ("temperature", c_f), ("top_k", c_i), ("top_p", c_f),
+                ("token", c_p), ("probs_out", c_p), ("logp", c_p), ("seq_logp", c_p), ("ldp", c_i),
+                ("state", c_p), ("seq", c_p), ("chord_tok", c_p), ("chord_pos", c_p), ("utable", c_p),
+                ("ld_seq", c_i), ("ld_chord", c_i), ("ld_u", c_i), ("max_iters", c_i),
+                ("tok", c_p), ("active", c_p), ("keep", c_p), ("draw", c_p), ("uni", c_p), ("trace", c_p), ("ld_trace", c_i),
+                ("klen", c_p), ("lmax", c_i),
+                ("bias", c_p), ("gram", c_p), ("gram_on", c_p), ("harm", c_p), ("harm_on", c_p),
+                ("ld_bias", c_i), ("ld_gram", c_i), ("ld_harm", c_i)]
+
+
+def struct_args(cls, **fields):
+    """An argument struct with struct_bytes set; fields not named stay zero / null."""
+    return cls(struct_bytes=C.sizeof(cls), **fields)
+
+
 # name -> argtypes (all return int unless listed in _RESTYPE); stream is always the last c_void_p
 PROTOTYPES = {
     "commu_gemm_nt_bf16": [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_i, c_i, C.c_uint, c_f, c_f, c_p],
@@ -125,16 +158,8 @@ PROTOTYPES = {
     "commu_relattn_bwd_band": [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
     "commu_attn_delta": [c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p],
     "commu_transpose_heads": [c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
-    "commu_sample_topk": [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_f, c_i, c_p, c_p, c_i, c_p],
-    "commu_sample_topk_topp": [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_f, c_i, c_f, c_p, c_p, c_i, c_p],
-    "commu_sample_topk_topp_rows": [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_f, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_i, c_p,
-                                    c_p],
-    "commu_sample_topk_topp_bias": [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_f, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_i, c_p,
-                                    c_p, c_i, c_p],
-    "commu_sample_topk_topp_gram": [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_f, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_i, c_p,
-                                    c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_p],
-    "commu_sample_topk_topp_harm": [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_f, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_i, c_p,
-                                    c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_p],
+    "commu_sample_args_bytes": [],
+    "commu_sample_topk": [C.POINTER(SampleArgs), c_p],
     "commu_decode_kv_append": [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
     "commu_decode_attn": [c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_p],
     "commu_decode_attn_split": [c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_i,
@@ -161,25 +186,10 @@ PROTOTYPES = {
     "commu_decode_tail_pack_bytes": [c_i, c_i],
     "commu_decode_tail_pack": [c_p, c_i, c_i, c_i, c_p, c_p],
     "commu_forcing_state_ints": [],
-    "commu_forcing_pre": [c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p],
-    "commu_forcing_post": [c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p],
-    "commu_decode_sample_post_pre": [c_p, c_i, c_i, c_p, c_f, c_i, c_f, c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_i,
-                                     c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_p],
-    "commu_forcing_pre_rows": [c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i,
-                               c_p],
-    "commu_forcing_post_rows": [c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_p],
-    "commu_decode_sample_post_pre_rows": [c_p, c_i, c_i, c_p, c_f, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p,
-                                          c_i, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i,
-                                          c_p],
-    "commu_decode_sample_post_pre_bias": [c_p, c_i, c_i, c_p, c_f, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p,
-                                          c_i, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i,
-                                          c_p, c_i, c_p],
-    "commu_decode_sample_post_pre_gram": [c_p, c_i, c_i, c_p, c_f, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p,
-                                          c_i, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i,
-                                          c_p, c_i, c_p, c_i, c_p, c_p],
-    "commu_decode_sample_post_pre_harm": [c_p, c_i, c_i, c_p, c_f, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p,
-                                          c_i, c_p, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i,
-                                          c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_p],
+    "commu_forcing_pre": [c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p],
+    "commu_forcing_post": [c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_p],
+    "commu_decode_loop_args_bytes": [],
+    "commu_decode_sample_post_pre": [C.POINTER(DecodeLoopArgs), c_p],
     "commu_forcing_replay": [c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p,
                              c_p, c_p, c_i, c_p, c_i, c_p],
     "commu_decode_prefill_scatter": [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p],
@@ -211,7 +221,7 @@ _RESTYPE = {"commu_decode_tail_pack_bytes": C.c_longlong, "commu_attn_pf_bytes":
             "commu_gemm_nt_signbits_words": C.c_longlong, "commu_pack_batch": C.c_longlong}
 _NOCHECK = {"commu_layernorm_bwd_nblocks", "commu_colsum_slabs", "commu_embed_bwd_ws_rows", "commu_hip_version", "commu_attn_bwd_qrows", "commu_attn_fwd_generation", "commu_attn_bwd_kv_generation", "commu_colsum_slab_pass", "commu_gemm_tn_grouped_slices", "commu_gemm_tn_grouped_slices_budget", "commu_attn_band_slabs", "commu_attn_band_pairs",
             "commu_forcing_state_ints", "commu_decode_tail_supported", "commu_decode_tail_sync_words", "commu_decode_tail_sync_words_for", "commu_decode_tail_pack_bytes", "commu_attn_p_scratch_elems", "commu_gemm_nt_signbits_words", "commu_pack_batch", "commu_attn_pf_bytes",
-            "commu_decode_prefix_chunk", "commu_decode_prefix_group"}
+            "commu_decode_prefix_chunk", "commu_decode_prefix_group", "commu_sample_args_bytes", "commu_decode_loop_args_bytes"}
 
 _lib = None
 
@@ -238,6 +248,11 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = _RESTYPE.get(name, c_i)
+    # the argument structs as this table lays them out against the library's own sizeof
+    for cls, sizer in ((SampleArgs, lib.commu_sample_args_bytes), (DecodeLoopArgs, lib.commu_decode_loop_args_bytes)):
+        if C.sizeof(cls) != sizer():
+            raise CommuHipError(f"{cls.__name__}: {C.sizeof(cls)} bytes here, {sizer()} in {LIB_PATH} (include/commu_hip.h "
+                                "and _lib.py disagree)")
     _lib = lib
     return lib
 

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import CommuHipError, call
+from ._lib import CommuHipError, DecodeLoopArgs, call, struct_args
 from .midi_generator.midi_inferrer import TOKEN_OFFSET, ForcingReport, token_class  # noqa: F401
 
 BF16, F32 = torch.bfloat16, torch.float32
@@ -76,7 +76,7 @@ def sampling_rows(B: int, temperature, top_k, top_p=1.0):
 
 
 # ---- constraints on what a slot may draw: one additive fp32 row per slot, applied by the sampling step to the row its
-# softmax sees (logits / temperature + bias, before top-k; commu_sample_topk_topp_bias).  A finite entry re-weights an id,
+# softmax sees (logits / temperature + bias, before top-k; commu_sample_args.bias).  A finite entry re-weights an id,
 # -inf bans it.  Rows are VPAD wide like the logits rows; ids 0 and >= 729 are never drawn and their entries are ignored.
 N_VELOCITY = TOKEN_OFFSET.CHORD_START - TOKEN_OFFSET.NOTE_VELOCITY          # 64 velocity tokens, one per bin of 2
 N_PITCH = TOKEN_OFFSET.NOTE_VELOCITY - TOKEN_OFFSET.PITCH                   # 128 pitch tokens, MIDI note numbers
@@ -193,7 +193,7 @@ def logit_bias_rows(x, n: int):
 
 # ---- the event grammar: a constraint chosen per draw by the slot's own state.  A table is fp32 [8][VPAD]; row c is the
 # additive row for a draw whose previous token has class c (midi_inferrer.token_class: OTHER, BAR, PITCH, VELOCITY, CHORD,
-# DURATION, POSITION), row 7 is zeros: the row of a slot whose grammar is off (commu_sample_topk_topp_gram).
+# DURATION, POSITION), row 7 is zeros: the row of a slot whose grammar is off (commu_sample_args.gram).
 N_CLASSES = 7
 
 
@@ -266,7 +266,7 @@ def _grammar_request(grammar, B: int):
 # ---- the harmony constraint: a third additive term chosen per draw by the chord the slot is in.  A table is fp32
 # [111][16]: row t - 195 for the chord tokens 195 .. 303 (rows 0 .. 107 the 12 roots x 9 qualities, row 108 Chord_NN), row 109
 # for a slot whose seq holds no chord yet, row 110 zeros: the row of a slot whose switch is off.  Column pc is MIDI pitch class
-# pc (C = 0); columns 12 .. 15 are zero padding, so a row is one 64-byte line (commu_sample_topk_topp_harm).
+# pc (C = 0); columns 12 .. 15 are zero padding, so a row is one 64-byte line (commu_sample_args.harm).
 HARM_ROWS, HARM_COLS, HARM_NN, HARM_NO_CHORD, HARM_OFF = 111, 16, 108, 109, 110
 
 
@@ -922,17 +922,50 @@ class ForcedDecoder:
     # on the current stream.  The captured graph holds [step, {sample, post, pre of the NEXT iteration} as one launch]
     # (body_pre): run() issues the very first `pre` on its own and the kernel sequence is the same captured or not.
     # pre() / body() are the separate launches (iteration(): tests look at the draws between the stages).
-    def _rows_mode(self):
-        if not self.rows_on:
-            self.rows_on = True
-            self.graph = self.graph_long = None          # (they hold the launches without the arrays)
+    def _slots(self, rows):
+        """The slot numbers a setter addresses (rows=None: all of them), validated."""
+        idx = np.arange(self.B) if rows is None else np.asarray(list(rows), dtype=np.int64)
+        if idx.ndim != 1 or (idx.size and (idx.min() < 0 or idx.max() >= self.B)):
+            raise CommuHipError(f"rows: slot numbers in [0, {self.B}) expected, got {rows!r}")
+        return idx
+
+    def _first_use(self, rows=False, bias=False, gram=False, harm=False):
+        """What the first use of a per-slot launch input does, for each one asked for that the decoder does not have yet:
+        rows uploads the host mirror of the sampling controls (scalar mode kept the mirror only); bias / gram / harm
+        allocate their zeroed device buffers (gram and harm: the table and the [B] switches).  When anything was missing the
+        captured graphs are dropped, once: they hold the launches without it."""
+        new = False
+        if rows and not self.rows_on:
+            new = self.rows_on = True
             for dst, src in zip((self.temperature_rows, self.top_k_rows, self.top_p_rows), self._sampling):
-                dst.copy_(torch.from_numpy(src))         # (scalar mode kept the host mirror only)
+                dst.copy_(torch.from_numpy(src))
+        if bias and self.bias is None:
+            new = True
+            self.bias = torch.zeros(self.B, VPAD, dtype=F32, device=self.dev)
+        if gram and self.gram is None:
+            new = True
+            self.gram = torch.zeros(N_CLASSES + 1, VPAD, dtype=F32, device=self.dev)
+            self.gram_on = torch.zeros(self.B, dtype=torch.uint8, device=self.dev)
+        if harm and self.harm is None:
+            new = True
+            self.harm = torch.zeros(HARM_ROWS, HARM_COLS, dtype=F32, device=self.dev)
+            self.harm_on = torch.zeros(self.B, dtype=torch.uint8, device=self.dev)
+        if new:
+            self.graph = self.graph_long = None
+
+    @staticmethod
+    def _switch(on, val, rows, idx):
+        """The [B] switches `on` of the addressed slots (rows=None: all) set to val, in place."""
+        if rows is None:
+            on.fill_(val)
+        else:
+            for j in idx:
+                on[int(j)].fill_(val)
 
     def record_logprobs(self):
         """Keep the log-probability pair of every token from now on (logprobs(), harvest_logprobs()).  Call it before
         load(): tokens appended earlier have no entry.  Switches the decoder to the array launches (see __init__)."""
-        self._rows_mode()
+        self._first_use(rows=True)
 
     def _rows_args(self):
         """(temperature_rows, top_k_rows, top_p_rows, logp, seq_logp) as the launches get them."""
@@ -946,9 +979,7 @@ class ForcedDecoder:
         are rewritten IN PLACE, ordered on the current stream like any launch: a captured graph keeps pointing at them and
         needs no re-capture.  A few slots (rearm) are written by device-side fills -- no host copy, no synchronisation --,
         a whole batch by one copy per array that changed."""
-        idx = np.arange(self.B) if rows is None else np.asarray(list(rows), dtype=np.int64)
-        if idx.ndim != 1 or (idx.size and (idx.min() < 0 or idx.max() >= self.B)):
-            raise CommuHipError(f"rows: slot numbers in [0, {self.B}) expected, got {rows!r}")
+        idx = self._slots(rows)
         cur = self._sampling
         new = sampling_rows(len(idx), *(cur[i][idx] if v is None else v for i, v in enumerate((temperature, top_k, top_p))))
         changed = [not np.array_equal(cur[i][idx], new[i]) for i in range(3)]
@@ -956,12 +987,12 @@ class ForcedDecoder:
             cur[i][idx] = new[i]
         if not self.rows_on:
             if any(bool((c != c[0]).any()) for c in cur):
-                return self._rows_mode()                 # slots differ (uploads the mirror)
+                return self._first_use(rows=True)       # slots differ (uploads the mirror)
             triple = (float(cur[0][0]), int(cur[1][0]), float(cur[2][0]))
             if triple == (self.temperature, self.top_k, self.top_p):
                 return
             if self.graph is not None or self.graph_long is not None:
-                return self._rows_mode()                 # the captured launches hold the old scalars
+                return self._first_use(rows=True)       # the captured launches hold the old scalars
             self.temperature, self.top_k, self.top_p = triple
             return
         for i, dst in enumerate((self.temperature_rows, self.top_k_rows, self.top_p_rows)):
@@ -984,15 +1015,11 @@ class ForcedDecoder:
         launch without it), the way the per-slot sampling controls do; from then on rows are rewritten IN PLACE, ordered on
         the current stream like any launch, and a captured graph follows them.  A cleared row is zeros: x + 0 is x, so the
         slot draws bit for bit what it draws without a constraint.  A decoder that never got one allocates nothing."""
-        idx = np.arange(self.B) if rows is None else np.asarray(list(rows), dtype=np.int64)
-        if idx.ndim != 1 or (idx.size and (idx.min() < 0 or idx.max() >= self.B)):
-            raise CommuHipError(f"rows: slot numbers in [0, {self.B}) expected, got {rows!r}")
+        idx = self._slots(rows)
         new = None if bias is None else logit_bias_rows(bias, len(idx))          # (validated before anything changes)
-        if self.bias is None:
-            if new is None:
-                return
-            self.bias = torch.zeros(self.B, VPAD, dtype=F32, device=self.dev)
-            self.graph = self.graph_long = None
+        if self.bias is None and new is None:
+            return
+        self._first_use(bias=True)
         if new is None:
             if rows is None:
                 self.bias.zero_()
@@ -1015,27 +1042,17 @@ class ForcedDecoder:
         graphs once (they hold the launch without them), exactly as set_logit_bias does; later calls rewrite in place,
         ordered on the current stream.  A slot that is off reads the zero row 7: it draws bit for bit what it drew
         without the feature.  A decoder that never got a grammar allocates nothing."""
-        idx = np.arange(self.B) if rows is None else np.asarray(list(rows), dtype=np.int64)
-        if idx.ndim != 1 or (idx.size and (idx.min() < 0 or idx.max() >= self.B)):
-            raise CommuHipError(f"rows: slot numbers in [0, {self.B}) expected, got {rows!r}")
+        idx = self._slots(rows)
         if table is False:
             table = None
         new = None if table is None else (event_grammar() if table is True else grammar_table(table))
-        if self.gram is None:
-            if new is None:
-                return
-            self.gram = torch.zeros(N_CLASSES + 1, VPAD, dtype=F32, device=self.dev)
-            self.gram_on = torch.zeros(self.B, dtype=torch.uint8, device=self.dev)
-            self.graph = self.graph_long = None
+        if self.gram is None and new is None:
+            return
+        self._first_use(gram=True)
         if new is not None and (self._gram_host is None or not np.array_equal(new, self._gram_host)):
             self.gram.copy_(torch.from_numpy(new))
             self._gram_host = new
-        val = 0 if new is None else 1
-        if rows is None:
-            self.gram_on.fill_(val)
-        else:
-            for j in idx:
-                self.gram_on[int(j)].fill_(val)
+        self._switch(self.gram_on, 0 if new is None else 1, rows, idx)
 
     def _gram_args(self):
         return None if self.gram is None else (self.gram, self.gram_on, self.fsm, self.seq)
@@ -1053,38 +1070,23 @@ class ForcedDecoder:
         that is off reads the zero row 110: it draws bit for bit what it drew without the feature.  A decoder that never
         got a table allocates nothing.  Not enforced: a logit_bias (or a pitch range built from one) that leaves no pitch
         of an allowed class makes the slot fail its draw after a velocity (Q12) when the grammar is on as well."""
-        idx = np.arange(self.B) if rows is None else np.asarray(list(rows), dtype=np.int64)
-        if idx.ndim != 1 or (idx.size and (idx.min() < 0 or idx.max() >= self.B)):
-            raise CommuHipError(f"rows: slot numbers in [0, {self.B}) expected, got {rows!r}")
+        idx = self._slots(rows)
         if table is False:
             table = None
         new = None if table is None else (harmony_table() if table is True else harmony_rows(table))
-        if self.harm is None:
-            if new is None:
-                return
-            self.harm = torch.zeros(HARM_ROWS, HARM_COLS, dtype=F32, device=self.dev)
-            self.harm_on = torch.zeros(self.B, dtype=torch.uint8, device=self.dev)
-            if self.bias is None:
-                self.bias = torch.zeros(self.B, VPAD, dtype=F32, device=self.dev)
-            if self.gram is None:
-                self.gram = torch.zeros(N_CLASSES + 1, VPAD, dtype=F32, device=self.dev)
-                self.gram_on = torch.zeros(self.B, dtype=torch.uint8, device=self.dev)
-            self.graph = self.graph_long = None
+        if self.harm is None and new is None:
+            return
+        self._first_use(harm=True, bias=True, gram=True)      # (the one harmony kernel reads a bias and a grammar)
         if new is not None and (self._harm_host is None or not np.array_equal(new, self._harm_host)):
             self.harm.copy_(torch.from_numpy(new))
             self._harm_host = new
-        val = 0 if new is None else 1
-        if rows is None:
-            self.harm_on.fill_(val)
-        else:
-            for j in idx:
-                self.harm_on[int(j)].fill_(val)
+        self._switch(self.harm_on, 0 if new is None else 1, rows, idx)
 
     def _harm_args(self):
         return None if self.harm is None else (self.harm, self.harm_on, self.fsm, self.chord_tok)
 
     def pre(self):
-        call("commu_forcing_pre_rows", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_tok), _p(self.chord_pos),
+        call("commu_forcing_pre", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_tok), _p(self.chord_pos),
              self.ld_chord, _p(self.wrong), _p(self.utable), self.ld_u, self.generation_length, _p(self.tok),
              _p(self.active), _p(self.keep), _p(self.draw), _p(self.uni), _p(self.trace), self.ld_trace,
              _p(self._rows_args()[4]), self.B, _s())
@@ -1100,7 +1102,7 @@ class ForcedDecoder:
                         probs_out=self.probs if want_probs else None, top_p=self.top_p if p_r is None else p_r,
                         logp_out=logp, bias=self.bias, **({} if self.gram is None else {"grammar": self._gram_args()}),
                         **({} if self.harm is None else {"harmony": self._harm_args()}))
-        call("commu_forcing_post_rows", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_pos), self.ld_chord,
+        call("commu_forcing_post", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_pos), self.ld_chord,
              _p(self.wrong), _p(self.draw), _p(self.token), None, _p(self.state.klen), _p(self.keep),
              self.state.klen_cap, _p(logp), _p(seq_logp), B, _s())
 
@@ -1110,22 +1112,20 @@ class ForcedDecoder:
         st = self.state
         st.step(self.tok, self.active, None)
         t_r, k_r, p_r, _, seq_logp = self._rows_args()          # (fused: the pair reaches post in registers, no hand-over)
-        args = (_p(st.logits), st.logits.stride(0), TOKEN_OFFSET.VOCAB_SIZE,
-                _p(self.wrong), self.temperature, self.top_k, self.top_p, _p(t_r), _p(k_r), _p(p_r), _p(self.token), None, 0,
-                None, _p(seq_logp), _p(self.fsm), _p(self.seq), self.ld_seq,
-                _p(self.chord_tok), _p(self.chord_pos), self.ld_chord, _p(self.utable), self.ld_u, self.generation_length,
-                _p(self.tok), _p(self.active), _p(self.keep), _p(self.draw), _p(self.uni), _p(self.trace), self.ld_trace,
-                _p(st.klen), st.klen_cap, self.B)
-        if self.harm is not None:          # (set_harmony allocated the bias and the grammar the kernel reads)
-            call("commu_decode_sample_post_pre_harm", *args, _p(self.bias), self.bias.stride(0), _p(self.gram),
-                 self.gram.stride(0), _p(self.gram_on), _p(self.harm), self.harm.stride(0), _p(self.harm_on), _s())
-        elif self.gram is not None:
-            call("commu_decode_sample_post_pre_gram", *args, _p(self.bias), 0 if self.bias is None else self.bias.stride(0),
-                 _p(self.gram), self.gram.stride(0), _p(self.gram_on), _s())
-        elif self.bias is None:
-            call("commu_decode_sample_post_pre_rows", *args, _s())
-        else:
-            call("commu_decode_sample_post_pre_bias", *args, _p(self.bias), self.bias.stride(0), _s())
+        ld = lambda t: 0 if t is None else t.stride(0)
+        # (a constraint the decoder never got is a null pointer: the launch that never heard of it; set_harmony allocated
+        # the bias and the grammar its kernel reads)
+        a = struct_args(
+            DecodeLoopArgs, logits=_p(st.logits), ld=st.logits.stride(0), V=TOKEN_OFFSET.VOCAB_SIZE, B=self.B,
+            wrong=_p(self.wrong), temperature=self.temperature, top_k=self.top_k, top_p=self.top_p, temperature_rows=_p(t_r),
+            top_k_rows=_p(k_r), top_p_rows=_p(p_r), token=_p(self.token), seq_logp=_p(seq_logp), state=_p(self.fsm),
+            seq=_p(self.seq), ld_seq=self.ld_seq, chord_tok=_p(self.chord_tok), chord_pos=_p(self.chord_pos),
+            ld_chord=self.ld_chord, utable=_p(self.utable), ld_u=self.ld_u, max_iters=self.generation_length,
+            tok=_p(self.tok), active=_p(self.active), keep=_p(self.keep), draw=_p(self.draw), uni=_p(self.uni),
+            trace=_p(self.trace), ld_trace=self.ld_trace, klen=_p(st.klen), lmax=st.klen_cap,
+            bias=_p(self.bias), ld_bias=ld(self.bias), gram=_p(self.gram), ld_gram=ld(self.gram), gram_on=_p(self.gram_on),
+            harm=_p(self.harm), ld_harm=ld(self.harm), harm_on=_p(self.harm_on))
+        call("commu_decode_sample_post_pre", C.byref(a), _s())
 
     def iteration(self, want_probs: bool = False):
         """One complete iteration, eagerly (tests inspect the draws between iterations)."""

@@ -946,19 +946,19 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
     bias: fp32 [nseq, >=V] on the device of the logits (row stride = ld_bias), a constraint per sequence: the distribution
     is built from logits / temperature + bias (the raw row + bias for temperature 0) -- a finite entry re-weights an id,
     -inf bans it, before top-k.  It is never written back: the logits are left as the call without it leaves them
-    (commu_sample_topk_topp_bias; generate.token_constraints builds and validates such rows).
+    (commu_sample_args.bias; generate.token_constraints builds and validates such rows).
     V: the ids drawn from are 1 .. V-1 (2 <= V <= 768; the decode loop's vocabulary by default).
     grammar: (table, on, state, seq) on the device of the logits -- table fp32 [8, >=V] (generate.grammar_table), on uint8
     [nseq] or None (all on), state the int32 forcing records [nseq, commu_forcing_state_ints()], seq int32 [nseq, ld_seq].
     Row c of the table is added after the bias for a sequence whose previous token seq[b][state[b][0] - 1] has class c
     (generate.token_class), row 7 for a sequence that is off; like the bias it is never written back
-    (commu_sample_topk_topp_gram).
+    (commu_sample_args.gram).
     harmony: (table, on, state, chord_tok) on the device of the logits -- table fp32 [111, >= 12] (generate.harmony_rows), on
     uint8 [nseq] or None (all on), state as above, chord_tok int32 [nseq, ld_chord]: the chords the forcing rules place.
     For the pitch ids 3 .. 130 table[r][(id - 3) mod 12] is added after the grammar row, r = chord_tok[b][state[b][F_CUR] - 1]
     - 195 (109 while F_CUR is 0, 110 for a sequence that is off); no other id is touched and nothing is written back.  One
     kernel serves it, with a bias and a grammar: where the call has none, a zero bias and an all-off grammar are made
-    here (x + 0 and the zero row 7 change no bit) (commu_sample_topk_topp_harm)."""
+    here (x + 0 and the zero row 7 change no bit) (commu_sample_args.harm)."""
     nseq = logits.shape[0]
     V = int(V)
     assert logits.dtype == F32 and logits.stride(1) == 1
@@ -982,15 +982,13 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
                                 f"{str(logp_out.dtype).replace('torch.', '')} {tuple(logp_out.shape)}")
     if token is None:
         token = torch.empty(nseq, device=logits.device, dtype=torch.int32)
-    args = (_p(logits), logits.stride(0), nseq, V, _p(wrong),
-            0 if wrong is None else wrong.stride(0), _p(uniforms), _p(active), 0.0 if t_s is None else float(t_s),
-            1 if k_s is None else int(k_s), 1.0 if p_s is None else float(p_s), _p(t_r), _p(k_r), _p(p_r), _p(token),
-            _p(probs_out), 0 if probs_out is None else probs_out.stride(0), _p(logp_out), _p(bias),
-            0 if bias is None else max(int(bias.stride(0)), V))
-    if grammar is None and harmony is None:
-        call("commu_sample_topk_topp_bias", *args, _s())
-        return token
-    nrec = call("commu_forcing_state_ints")
+    a = _lib.struct_args(
+        _lib.SampleArgs, logits=_p(logits), ld=logits.stride(0), nseq=nseq, V=V, wrong=_p(wrong),
+        ldw=0 if wrong is None else wrong.stride(0), uniforms=_p(uniforms), active=_p(active),
+        temperature=0.0 if t_s is None else float(t_s), top_k=1 if k_s is None else int(k_s),
+        top_p=1.0 if p_s is None else float(p_s), temperature_rows=_p(t_r), top_k_rows=_p(k_r), top_p_rows=_p(p_r),
+        token=_p(token), probs_out=_p(probs_out), ldp=0 if probs_out is None else probs_out.stride(0), logp_out=_p(logp_out))
+    nrec = call("commu_forcing_state_ints") if grammar is not None or harmony is not None else 0
     if harmony is not None:
         htable, hon, hstate, chord_tok = harmony
         _check_draw_state("harmony", logits.device, (
@@ -1010,18 +1008,21 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
                        torch.zeros(nseq, 1, dtype=torch.int32, device=logits.device))
         if bias is None:
             bias = torch.zeros(nseq, V, dtype=F32, device=logits.device)
-            args = args[:-2] + (_p(bias), V)
-    table, on, state, seq = grammar
-    _check_draw_state("grammar", logits.device, (
-        (table, "table", F32, "[8, >= %d]" % V, lambda t: t.dim() == 2 and t.shape[0] == 8 and t.shape[1] >= V),
-        (on, "on", torch.uint8, "[%d]" % nseq, lambda t: tuple(t.shape) == (nseq,)),
-        (state, "state", torch.int32, "[%d, %d]" % (nseq, nrec), lambda t: tuple(t.shape) == (nseq, nrec)),
-        (seq, "seq", torch.int32, "[%d, ld_seq]" % nseq, lambda t: t.dim() == 2 and t.shape[0] == nseq and t.shape[1] >= 1)))
-    if harmony is not None:
-        call("commu_sample_topk_topp_harm", *args, _p(table), table.stride(0), _p(on), _p(state), _p(seq), seq.stride(0),
-             _p(htable), htable.stride(0), _p(hon), _p(chord_tok), chord_tok.stride(0), _s())
-        return token
-    call("commu_sample_topk_topp_gram", *args, _p(table), table.stride(0), _p(on), _p(state), _p(seq), seq.stride(0), _s())
+        a.harm, a.ld_harm, a.harm_on = _p(htable), htable.stride(0), _p(hon)
+        a.chord_tok, a.ld_chord = _p(chord_tok), chord_tok.stride(0)
+    if grammar is not None:
+        table, on, state, seq = grammar
+        _check_draw_state("grammar", logits.device, (
+            (table, "table", F32, "[8, >= %d]" % V, lambda t: t.dim() == 2 and t.shape[0] == 8 and t.shape[1] >= V),
+            (on, "on", torch.uint8, "[%d]" % nseq, lambda t: tuple(t.shape) == (nseq,)),
+            (state, "state", torch.int32, "[%d, %d]" % (nseq, nrec), lambda t: tuple(t.shape) == (nseq, nrec)),
+            (seq, "seq", torch.int32, "[%d, ld_seq]" % nseq,
+             lambda t: t.dim() == 2 and t.shape[0] == nseq and t.shape[1] >= 1)))
+        a.gram, a.ld_gram, a.gram_on = _p(table), table.stride(0), _p(on)
+        a.state, a.seq, a.ld_seq = _p(state), _p(seq), seq.stride(0)
+    if bias is not None:
+        a.bias, a.ld_bias = _p(bias), max(int(bias.stride(0)), V)
+    call("commu_sample_topk", C.byref(a), _s())
     return token
 
 

@@ -217,10 +217,10 @@ __global__ void copy_rows_masked_kernel(float* __restrict__ dst, int ldd, const 
 
 extern "C" int commu_forcing_state_ints(void) { return F_COUNT; }
 
-extern "C" int commu_forcing_pre_rows(int* state, int* seq, int ld_seq, const int* chord_tok, const int* chord_pos,
-                                      int ld_chord, unsigned char* wrong, const float* utable, int ld_u, int max_iters,
-                                      long long* tok, unsigned char* active, unsigned char* keep, unsigned char* draw,
-                                      float* uni, int* trace, int ld_trace, float* seq_logp, int B, hipStream_t stream) {
+extern "C" int commu_forcing_pre(int* state, int* seq, int ld_seq, const int* chord_tok, const int* chord_pos,
+                                 int ld_chord, unsigned char* wrong, const float* utable, int ld_u, int max_iters,
+                                 long long* tok, unsigned char* active, unsigned char* keep, unsigned char* draw,
+                                 float* uni, int* trace, int ld_trace, float* seq_logp, int B, hipStream_t stream) {
     if (B <= 0) return 0;
     if (ld_seq < 2 || ld_chord < 1 || ld_u < 1) return -22;
     COMMU_LAUNCH(forcing_pre_kernel, dim3(B), dim3(64), 0, stream, state, seq, ld_seq, chord_tok, chord_pos, ld_chord,
@@ -229,30 +229,15 @@ extern "C" int commu_forcing_pre_rows(int* state, int* seq, int ld_seq, const in
     return 0;
 }
 
-extern "C" int commu_forcing_pre(int* state, int* seq, int ld_seq, const int* chord_tok, const int* chord_pos,
-                                 int ld_chord, unsigned char* wrong, const float* utable, int ld_u, int max_iters,
-                                 long long* tok, unsigned char* active, unsigned char* keep, unsigned char* draw,
-                                 float* uni, int* trace, int ld_trace, int B, hipStream_t stream) {
-    return commu_forcing_pre_rows(state, seq, ld_seq, chord_tok, chord_pos, ld_chord, wrong, utable, ld_u, max_iters, tok,
-                                  active, keep, draw, uni, trace, ld_trace, nullptr, B, stream);
-}
-
-extern "C" int commu_forcing_post_rows(int* state, int* seq, int ld_seq, const int* chord_pos, int ld_chord,
-                                       unsigned char* wrong, const unsigned char* draw, const int* token, int* live,
-                                       int* klen, const unsigned char* keep, int lmax, const float* logp, float* seq_logp,
-                                       int B, hipStream_t stream) {
+extern "C" int commu_forcing_post(int* state, int* seq, int ld_seq, const int* chord_pos, int ld_chord,
+                                  unsigned char* wrong, const unsigned char* draw, const int* token, int* live,
+                                  int* klen, const unsigned char* keep, int lmax, const float* logp, float* seq_logp,
+                                  int B, hipStream_t stream) {
     if (B <= 0) return 0;
     COMMU_LAUNCH(forcing_post_kernel, dim3(B), dim3(64), 0, stream, state, seq, ld_seq, chord_pos, ld_chord, wrong,
                  draw, token, live, klen, keep, lmax, logp, seq_logp);
     COMMU_LAUNCH_CHECK();
     return 0;
-}
-
-extern "C" int commu_forcing_post(int* state, int* seq, int ld_seq, const int* chord_pos, int ld_chord,
-                                  unsigned char* wrong, const unsigned char* draw, const int* token, int* live,
-                                  int* klen, const unsigned char* keep, int lmax, int B, hipStream_t stream) {
-    return commu_forcing_post_rows(state, seq, ld_seq, chord_pos, ld_chord, wrong, draw, token, live, klen, keep, lmax,
-                                   nullptr, nullptr, B, stream);
 }
 
 extern "C" int commu_forcing_replay(int* state, int* seq, int ld_seq, const int* prompt, int ld_prompt,
@@ -289,116 +274,47 @@ extern "C" int commu_decode_loop_trace(unsigned long long* buf) {
     return 0;
 }
 
-extern "C" int commu_decode_sample_post_pre_harm(float* logits, int ld, int V, unsigned char* wrong, float temperature,
-                                                 int top_k, float top_p, const float* temperature_rows,
-                                                 const int* top_k_rows, const float* top_p_rows, int* token,
-                                                 float* probs_out, int ldp, float* logp, float* seq_logp, int* state,
-                                                 int* seq, int ld_seq, const int* chord_tok, const int* chord_pos,
-                                                 int ld_chord, const float* utable, int ld_u, int max_iters, long long* tok,
-                                                 unsigned char* active, unsigned char* keep, unsigned char* draw, float* uni,
-                                                 int* trace, int ld_trace, int* klen, int lmax, int B, const float* bias,
-                                                 int ld_bias, const float* gram, int ld_gram, const unsigned char* gram_on,
-                                                 const float* harm, int ld_harm, const unsigned char* harm_on,
-                                                 hipStream_t stream) {
-    if (harm == nullptr)
-        return commu_decode_sample_post_pre_gram(logits, ld, V, wrong, temperature, top_k, top_p, temperature_rows,
-                                                 top_k_rows, top_p_rows, token, probs_out, ldp, logp, seq_logp, state, seq,
-                                                 ld_seq, chord_tok, chord_pos, ld_chord, utable, ld_u, max_iters, tok, active,
-                                                 keep, draw, uni, trace, ld_trace, klen, lmax, B, bias, ld_bias, gram, ld_gram,
-                                                 gram_on, stream);
-    if (B <= 0) return 0;
-    if (V != VOCAB || V > 64 * PER_LANE || ld_seq < 2 || ld_chord < 1 || ld_u < 1) return -22;
-    // (the kernel reads harm[0 .. 110][0 .. 11] and finds the chord through the record: chord_tok[b][F_CUR - 1])
-    if (ld_harm < 12 || state == nullptr || chord_tok == nullptr) return -22;
-    // (one instantiation: the caller passes a zero bias and an all-off grammar where it has none)
-    if (bias == nullptr || ld_bias < V || gram == nullptr || ld_gram < V || seq == nullptr) return -22;
-    if ((top_k_rows == nullptr && (top_k < 1 || top_k > V)) || (top_p_rows == nullptr && !(top_p > 0.f))) return -22;
-    LoopStageArgsHarm a;
-    static_cast<LoopStageArgs&>(a) =
-        LoopStageArgs{logits, ld, V, wrong, temperature, top_k, top_p, SamplingRows{temperature_rows, top_k_rows, top_p_rows},
-                      token, probs_out, ldp, logp, seq_logp, state, seq, ld_seq, chord_tok, chord_pos, ld_chord, utable, ld_u,
-                      max_iters, tok, active, keep, draw, uni, trace, ld_trace, klen, lmax, g_loop_trace, bias, ld_bias};
-    a.gram = gram; a.ld_gram = ld_gram; a.gram_on = gram_on;
-    a.harm = harm; a.ld_harm = ld_harm; a.harm_on = harm_on;
-    COMMU_LAUNCH((sample_post_pre_kernel<true, true, true>), dim3(B), dim3(64), 0, stream, a);
-    COMMU_LAUNCH_CHECK();
-    return 0;
-}
+extern "C" int commu_decode_loop_args_bytes(void) { return (int)sizeof(commu_decode_loop_args); }
 
-extern "C" int commu_decode_sample_post_pre_gram(float* logits, int ld, int V, unsigned char* wrong, float temperature,
-                                                 int top_k, float top_p, const float* temperature_rows,
-                                                 const int* top_k_rows, const float* top_p_rows, int* token,
-                                                 float* probs_out, int ldp, float* logp, float* seq_logp, int* state,
-                                                 int* seq, int ld_seq, const int* chord_tok, const int* chord_pos,
-                                                 int ld_chord, const float* utable, int ld_u, int max_iters, long long* tok,
-                                                 unsigned char* active, unsigned char* keep, unsigned char* draw, float* uni,
-                                                 int* trace, int ld_trace, int* klen, int lmax, int B, const float* bias,
-                                                 int ld_bias, const float* gram, int ld_gram, const unsigned char* gram_on,
-                                                 hipStream_t stream) {
-    if (B <= 0) return 0;
-    if (V != VOCAB || V > 64 * PER_LANE || ld_seq < 2 || ld_chord < 1 || ld_u < 1) return -22;
-    if (bias != nullptr && ld_bias < V) return -22;          // (the kernel reads bias[b][0 .. V-1])
-    // (the kernel reads gram[0 .. 7][0 .. V-1] and finds the previous token through the record)
-    if (gram != nullptr && (ld_gram < V || state == nullptr || seq == nullptr)) return -22;
+// The one host entry point of the fused launch: validate once, then pick the kernel by which constraint pointers are given.
+extern "C" int commu_decode_sample_post_pre(const commu_decode_loop_args* p, hipStream_t stream) {
+    if (p == nullptr || p->struct_bytes != sizeof(commu_decode_loop_args)) return -22;
+    if (p->B <= 0) return 0;
+    const int V = p->V;
+    if (V != VOCAB || V > 64 * PER_LANE || p->ld_seq < 2 || p->ld_chord < 1 || p->ld_u < 1) return -22;
     // (a scalar that an array replaces is not looked at; the kernel clamps what the arrays hold)
-    if ((top_k_rows == nullptr && (top_k < 1 || top_k > V)) || (top_p_rows == nullptr && !(top_p > 0.f))) return -22;
-    LoopStageArgs a{logits, ld, V, wrong, temperature, top_k, top_p, SamplingRows{temperature_rows, top_k_rows, top_p_rows},
-                    token, probs_out, ldp, logp, seq_logp, state, seq, ld_seq, chord_tok, chord_pos, ld_chord, utable, ld_u,
-                    max_iters, tok, active, keep, draw, uni, trace, ld_trace, klen, lmax, g_loop_trace, bias, ld_bias};
-    // four kernels: without a bias / a grammar the launch is the one it always was (no added load, no added register, no
-    // added argument)
-    if (gram != nullptr) {
-        LoopStageArgsGram ag;
-        static_cast<LoopStageArgs&>(ag) = a;
-        ag.gram = gram; ag.ld_gram = ld_gram; ag.gram_on = gram_on;
-        if (bias != nullptr) COMMU_LAUNCH((sample_post_pre_kernel<true, true>), dim3(B), dim3(64), 0, stream, ag);
-        else COMMU_LAUNCH((sample_post_pre_kernel<false, true>), dim3(B), dim3(64), 0, stream, ag);
-    } else if (bias != nullptr) {
-        COMMU_LAUNCH((sample_post_pre_kernel<true, false>), dim3(B), dim3(64), 0, stream, a);
+    if ((p->top_k_rows == nullptr && (p->top_k < 1 || p->top_k > V)) || (p->top_p_rows == nullptr && !(p->top_p > 0.f)))
+        return -22;
+    if (p->bias != nullptr && p->ld_bias < V) return -22;    // (the kernel reads bias[b][0 .. V-1])
+    // (the kernel reads gram[0 .. 7][0 .. V-1] and finds the previous token through the record)
+    if (p->gram != nullptr && (p->ld_gram < V || p->state == nullptr || p->seq == nullptr)) return -22;
+    // (the kernel reads harm[0 .. 110][0 .. 11] and finds the chord through the record: chord_tok[b][F_CUR - 1]; one
+    // instantiation: the caller passes a zero bias and an all-off grammar where it has none)
+    if (p->harm != nullptr && (p->ld_harm < 12 || p->chord_tok == nullptr || p->bias == nullptr || p->gram == nullptr))
+        return -22;
+    LoopStageArgsHarm a;
+    static_cast<LoopStageArgs&>(a) = LoopStageArgs{
+        p->logits, p->ld, V, p->wrong, p->temperature, p->top_k, p->top_p,
+        SamplingRows{p->temperature_rows, p->top_k_rows, p->top_p_rows}, p->token, p->probs_out, p->ldp, p->logp, p->seq_logp,
+        p->state, p->seq, p->ld_seq, p->chord_tok, p->chord_pos, p->ld_chord, p->utable, p->ld_u, p->max_iters, p->tok,
+        p->active, p->keep, p->draw, p->uni, p->trace, p->ld_trace, p->klen, p->lmax, g_loop_trace, p->bias, p->ld_bias};
+    a.gram = p->gram; a.ld_gram = p->ld_gram; a.gram_on = p->gram_on;
+    a.harm = p->harm; a.ld_harm = p->ld_harm; a.harm_on = p->harm_on;
+    const LoopStageArgsGram& ag = a;          // (each kernel gets the argument block of its own kind, by value)
+    const LoopStageArgs& a0 = a;
+    const dim3 grid(p->B), block(64);
+    // five kernels: without a bias / a grammar / a harmony table the launch is the one it always was (no added load, no
+    // added register, no added argument)
+    if (p->harm != nullptr) {
+        COMMU_LAUNCH((sample_post_pre_kernel<true, true, true>), grid, block, 0, stream, a);
+    } else if (p->gram != nullptr) {
+        if (p->bias != nullptr) COMMU_LAUNCH((sample_post_pre_kernel<true, true>), grid, block, 0, stream, ag);
+        else COMMU_LAUNCH((sample_post_pre_kernel<false, true>), grid, block, 0, stream, ag);
+    } else if (p->bias != nullptr) {
+        COMMU_LAUNCH((sample_post_pre_kernel<true, false>), grid, block, 0, stream, a0);
     } else {
-        COMMU_LAUNCH((sample_post_pre_kernel<false, false>), dim3(B), dim3(64), 0, stream, a);
+        COMMU_LAUNCH((sample_post_pre_kernel<false, false>), grid, block, 0, stream, a0);
     }
     COMMU_LAUNCH_CHECK();
     return 0;
-}
-
-extern "C" int commu_decode_sample_post_pre_bias(float* logits, int ld, int V, unsigned char* wrong, float temperature,
-                                                 int top_k, float top_p, const float* temperature_rows,
-                                                 const int* top_k_rows, const float* top_p_rows, int* token,
-                                                 float* probs_out, int ldp, float* logp, float* seq_logp, int* state,
-                                                 int* seq, int ld_seq, const int* chord_tok, const int* chord_pos,
-                                                 int ld_chord, const float* utable, int ld_u, int max_iters, long long* tok,
-                                                 unsigned char* active, unsigned char* keep, unsigned char* draw, float* uni,
-                                                 int* trace, int ld_trace, int* klen, int lmax, int B, const float* bias,
-                                                 int ld_bias, hipStream_t stream) {
-    return commu_decode_sample_post_pre_gram(logits, ld, V, wrong, temperature, top_k, top_p, temperature_rows, top_k_rows,
-                                             top_p_rows, token, probs_out, ldp, logp, seq_logp, state, seq, ld_seq, chord_tok,
-                                             chord_pos, ld_chord, utable, ld_u, max_iters, tok, active, keep, draw, uni, trace,
-                                             ld_trace, klen, lmax, B, bias, ld_bias, nullptr, 0, nullptr, stream);
-}
-
-extern "C" int commu_decode_sample_post_pre_rows(float* logits, int ld, int V, unsigned char* wrong, float temperature,
-                                                 int top_k, float top_p, const float* temperature_rows,
-                                                 const int* top_k_rows, const float* top_p_rows, int* token,
-                                                 float* probs_out, int ldp, float* logp, float* seq_logp, int* state,
-                                                 int* seq, int ld_seq, const int* chord_tok, const int* chord_pos,
-                                                 int ld_chord, const float* utable, int ld_u, int max_iters, long long* tok,
-                                                 unsigned char* active, unsigned char* keep, unsigned char* draw, float* uni,
-                                                 int* trace, int ld_trace, int* klen, int lmax, int B, hipStream_t stream) {
-    return commu_decode_sample_post_pre_bias(logits, ld, V, wrong, temperature, top_k, top_p, temperature_rows, top_k_rows,
-                                             top_p_rows, token, probs_out, ldp, logp, seq_logp, state, seq, ld_seq, chord_tok,
-                                             chord_pos, ld_chord, utable, ld_u, max_iters, tok, active, keep, draw, uni, trace,
-                                             ld_trace, klen, lmax, B, nullptr, 0, stream);
-}
-
-extern "C" int commu_decode_sample_post_pre(float* logits, int ld, int V, unsigned char* wrong, float temperature, int top_k,
-                                            float top_p, int* token, float* probs_out, int ldp, int* state, int* seq, int ld_seq,
-                                            const int* chord_tok, const int* chord_pos, int ld_chord, const float* utable,
-                                            int ld_u, int max_iters, long long* tok, unsigned char* active,
-                                            unsigned char* keep, unsigned char* draw, float* uni, int* trace, int ld_trace,
-                                            int* klen, int lmax, int B, hipStream_t stream) {
-    return commu_decode_sample_post_pre_rows(logits, ld, V, wrong, temperature, top_k, top_p, nullptr, nullptr, nullptr, token,
-                                             probs_out, ldp, nullptr, nullptr, state, seq, ld_seq, chord_tok, chord_pos,
-                                             ld_chord, utable, ld_u, max_iters, tok, active, keep, draw, uni, trace, ld_trace,
-                                             klen, lmax, B, stream);
 }

@@ -91,104 +91,50 @@ __global__ __launch_bounds__(64) void sample_topk_harm_kernel(float* __restrict_
 
 }  // namespace
 
-extern "C" int commu_sample_topk_topp_harm(float* logits, int ld, int nseq, int V, const unsigned char* wrong, int ldw,
-                                           const float* uniforms, const unsigned char* active, float temperature,
-                                           int top_k, float top_p, const float* temperature_rows, const int* top_k_rows,
-                                           const float* top_p_rows, int* token, float* probs_out, int ldp,
-                                           float* logp_out, const float* bias, int ld_bias, const float* gram, int ld_gram,
-                                           const unsigned char* gram_on, const int* state, const int* seq, int ld_seq,
-                                           const float* harm, int ld_harm, const unsigned char* harm_on,
-                                           const int* chord_tok, int ld_chord, hipStream_t stream) {
-    if (harm == nullptr)
-        return commu_sample_topk_topp_gram(logits, ld, nseq, V, wrong, ldw, uniforms, active, temperature, top_k, top_p,
-                                           temperature_rows, top_k_rows, top_p_rows, token, probs_out, ldp, logp_out, bias,
-                                           ld_bias, gram, ld_gram, gram_on, state, seq, ld_seq, stream);
-    if (nseq <= 0) return 0;
-    // (the kernel reads harm[0 .. 110][0 .. 11] and finds the chord through the record: chord_tok[b][F_CUR - 1])
-    if (ld_harm < 12 || state == nullptr || chord_tok == nullptr || ld_chord < 1) return -22;
-    // (one instantiation: the caller passes a zero bias and an all-off grammar where it has none)
-    if (bias == nullptr || ld_bias < V || gram == nullptr || ld_gram < V || seq == nullptr || ld_seq < 1) return -22;
-    if (V > 64 * PER_LANE || V < 2 || (top_k_rows == nullptr && (top_k < 1 || top_k > V)) ||
-        (top_p_rows == nullptr && !(top_p > 0.f)))
-        return -22;
-    const SamplingRows rows{temperature_rows, top_k_rows, top_p_rows};
-    COMMU_LAUNCH(sample_topk_harm_kernel, dim3(nseq), dim3(64), 0, stream, logits, ld, V, wrong, ldw, uniforms, active,
-                 temperature, top_k, token, probs_out, ldp, top_p, rows, logp_out, bias, ld_bias, gram, ld_gram, gram_on,
-                 state, seq, ld_seq, harm, ld_harm, harm_on, chord_tok, ld_chord);
-    COMMU_LAUNCH_CHECK();
-    return 0;
-}
+extern "C" int commu_sample_args_bytes(void) { return (int)sizeof(commu_sample_args); }
 
-extern "C" int commu_sample_topk_topp_gram(float* logits, int ld, int nseq, int V, const unsigned char* wrong, int ldw,
-                                           const float* uniforms, const unsigned char* active, float temperature,
-                                           int top_k, float top_p, const float* temperature_rows, const int* top_k_rows,
-                                           const float* top_p_rows, int* token, float* probs_out, int ldp,
-                                           float* logp_out, const float* bias, int ld_bias, const float* gram, int ld_gram,
-                                           const unsigned char* gram_on, const int* state, const int* seq, int ld_seq,
-                                           hipStream_t stream) {
-    if (nseq <= 0) return 0;
-    if (bias != nullptr && ld_bias < V) return -22;          // (the kernel reads bias[b][0 .. V-1])
-    // (the kernel reads gram[0 .. 7][0 .. V-1] and finds the previous token through the record)
-    if (gram != nullptr && (ld_gram < V || state == nullptr || seq == nullptr || ld_seq < 1)) return -22;
+// The one host entry point: validate once, then pick the kernel by which constraint pointers are given.
+extern "C" int commu_sample_topk(const commu_sample_args* a, hipStream_t stream) {
+    if (a == nullptr || a->struct_bytes != sizeof(commu_sample_args)) return -22;
+    if (a->nseq <= 0) return 0;
+    const int V = a->V;
     // (a scalar that an array replaces is not looked at; the kernel clamps what the arrays hold)
-    if (V > 64 * PER_LANE || V < 2 || (top_k_rows == nullptr && (top_k < 1 || top_k > V)) ||
-        (top_p_rows == nullptr && !(top_p > 0.f)))
+    if (V > 64 * PER_LANE || V < 2 || (a->top_k_rows == nullptr && (a->top_k < 1 || a->top_k > V)) ||
+        (a->top_p_rows == nullptr && !(a->top_p > 0.f)))
         return -22;
-    const SamplingRows rows{temperature_rows, top_k_rows, top_p_rows};
-    // four kernels: without a bias / a grammar the launch is the one it always was (no added load, no added register, no
-    // added argument)
-    if (gram != nullptr) {
-        if (bias != nullptr) {
-            COMMU_LAUNCH(sample_topk_gram_kernel<true>, dim3(nseq), dim3(64), 0, stream, logits, ld, V, wrong, ldw, uniforms,
-                         active, temperature, top_k, token, probs_out, ldp, top_p, rows, logp_out, bias, ld_bias, gram, ld_gram,
-                         gram_on, state, seq, ld_seq);
+    if (a->bias != nullptr && a->ld_bias < V) return -22;    // (the kernel reads bias[b][0 .. V-1])
+    // (the kernel reads gram[0 .. 7][0 .. V-1] and finds the previous token through the record)
+    if (a->gram != nullptr && (a->ld_gram < V || a->state == nullptr || a->seq == nullptr || a->ld_seq < 1)) return -22;
+    // (the kernel reads harm[0 .. 110][0 .. 11] and finds the chord through the record: chord_tok[b][F_CUR - 1]; one
+    // instantiation: the caller passes a zero bias and an all-off grammar where it has none)
+    if (a->harm != nullptr && (a->ld_harm < 12 || a->chord_tok == nullptr || a->ld_chord < 1 || a->bias == nullptr ||
+                               a->gram == nullptr))
+        return -22;
+    const SamplingRows rows{a->temperature_rows, a->top_k_rows, a->top_p_rows};
+    const dim3 grid(a->nseq), block(64);
+    // every kernel's parameters begin with the same fifteen, then (bias, ld_bias), then what its constraints add
+    auto launch = [&](auto kernel, const float* bias, int ld_bias, auto... more) {
+        COMMU_LAUNCH(kernel, grid, block, 0, stream, a->logits, a->ld, V, a->wrong, a->ldw, a->uniforms, a->active,
+                     a->temperature, a->top_k, a->token, a->probs_out, a->ldp, a->top_p, rows, a->logp_out, bias, ld_bias,
+                     more...);
+    };
+    // five kernels: without a bias / a grammar / a harmony table the launch is the one it always was (no added load, no
+    // added register, no added argument)
+    if (a->harm != nullptr) {
+        launch(sample_topk_harm_kernel, a->bias, a->ld_bias, a->gram, a->ld_gram, a->gram_on, a->state, a->seq, a->ld_seq,
+               a->harm, a->ld_harm, a->harm_on, a->chord_tok, a->ld_chord);
+    } else if (a->gram != nullptr) {
+        if (a->bias != nullptr) {
+            launch(sample_topk_gram_kernel<true>, a->bias, a->ld_bias, a->gram, a->ld_gram, a->gram_on, a->state, a->seq,
+                   a->ld_seq);
         } else {
-            COMMU_LAUNCH(sample_topk_gram_kernel<false>, dim3(nseq), dim3(64), 0, stream, logits, ld, V, wrong, ldw, uniforms,
-                         active, temperature, top_k, token, probs_out, ldp, top_p, rows, logp_out, nullptr, 0, gram, ld_gram,
-                         gram_on, state, seq, ld_seq);
+            launch(sample_topk_gram_kernel<false>, nullptr, 0, a->gram, a->ld_gram, a->gram_on, a->state, a->seq, a->ld_seq);
         }
-    } else if (bias != nullptr) {
-        COMMU_LAUNCH(sample_topk_kernel<true>, dim3(nseq), dim3(64), 0, stream, logits, ld, V, wrong, ldw, uniforms, active,
-                     temperature, top_k, token, probs_out, ldp, top_p, rows, logp_out, bias, ld_bias);
+    } else if (a->bias != nullptr) {
+        launch(sample_topk_kernel<true>, a->bias, a->ld_bias);
     } else {
-        COMMU_LAUNCH(sample_topk_kernel<false>, dim3(nseq), dim3(64), 0, stream, logits, ld, V, wrong, ldw, uniforms, active,
-                     temperature, top_k, token, probs_out, ldp, top_p, rows, logp_out, nullptr, 0);
+        launch(sample_topk_kernel<false>, nullptr, 0);
     }
     COMMU_LAUNCH_CHECK();
     return 0;
-}
-
-extern "C" int commu_sample_topk_topp_bias(float* logits, int ld, int nseq, int V, const unsigned char* wrong, int ldw,
-                                           const float* uniforms, const unsigned char* active, float temperature,
-                                           int top_k, float top_p, const float* temperature_rows, const int* top_k_rows,
-                                           const float* top_p_rows, int* token, float* probs_out, int ldp,
-                                           float* logp_out, const float* bias, int ld_bias, hipStream_t stream) {
-    return commu_sample_topk_topp_gram(logits, ld, nseq, V, wrong, ldw, uniforms, active, temperature, top_k, top_p,
-                                       temperature_rows, top_k_rows, top_p_rows, token, probs_out, ldp, logp_out, bias,
-                                       ld_bias, nullptr, 0, nullptr, nullptr, nullptr, 0, stream);
-}
-
-extern "C" int commu_sample_topk_topp_rows(float* logits, int ld, int nseq, int V, const unsigned char* wrong, int ldw,
-                                           const float* uniforms, const unsigned char* active, float temperature,
-                                           int top_k, float top_p, const float* temperature_rows, const int* top_k_rows,
-                                           const float* top_p_rows, int* token, float* probs_out, int ldp,
-                                           float* logp_out, hipStream_t stream) {
-    return commu_sample_topk_topp_bias(logits, ld, nseq, V, wrong, ldw, uniforms, active, temperature, top_k, top_p,
-                                       temperature_rows, top_k_rows, top_p_rows, token, probs_out, ldp, logp_out, nullptr, 0,
-                                       stream);
-}
-
-extern "C" int commu_sample_topk_topp(float* logits, int ld, int nseq, int V, const unsigned char* wrong, int ldw,
-                                      const float* uniforms, const unsigned char* active, float temperature,
-                                      int top_k, float top_p, int* token, float* probs_out, int ldp,
-                                      hipStream_t stream) {
-    return commu_sample_topk_topp_rows(logits, ld, nseq, V, wrong, ldw, uniforms, active, temperature, top_k, top_p, nullptr,
-                                       nullptr, nullptr, token, probs_out, ldp, nullptr, stream);
-}
-
-extern "C" int commu_sample_topk(float* logits, int ld, int nseq, int V, const unsigned char* wrong, int ldw,
-                                 const float* uniforms, const unsigned char* active, float temperature,
-                                 int top_k, int* token, float* probs_out, int ldp, hipStream_t stream) {
-    return commu_sample_topk_topp(logits, ld, nseq, V, wrong, ldw, uniforms, active, temperature, top_k, 1.f, token,
-                                  probs_out, ldp, stream);
 }

@@ -403,108 +403,111 @@ int commu_transpose_heads(const void* src, int ld, const float* bias, void* dst,
                           int DH, int W, int off, hipStream_t stream);
 
 /* ---- sampling step of the decode loop (InferenceTask.calc_probs / apply_sampling / infer_token,
- * commu/midi_generator/midi_inferrer.py:209-237), one wave per sequence:
- *   logits[b][1:V] /= temperature IN PLACE (quirk Q5), softmax, pad column 0 -> 0 (Q6), keep the
- *   top_k, zero wrong[b][id] != 0, renormalise, draw by inverse CDF with uniforms[b].
- *   temperature == 0: one-hot argmax.  token[b] = -1 when nothing can be drawn (Q12).
- *   active (optional): only sequences with active[b] != 0 are processed.
- *   probs_out (optional): the [nseq][ldp] distribution that was drawn from. */
-int commu_sample_topk(float* logits, int ld, int nseq, int V, const unsigned char* wrong, int ldw,
-                      const float* uniforms, const unsigned char* active, float temperature, int top_k,
-                      int* token, float* probs_out, int ldp, hipStream_t stream);
-/* the same with a nucleus ("top-p") filter after the top-k / rejected-token step -- an extra mode, the reference has none
- * (generate.py:43-44 offers top_k and temperature only): in order of decreasing probability (ties: lowest id first) a
- * token is kept while the probability mass before it is < top_p; survivors renormalised.  top_p >= 1: off. */
-int commu_sample_topk_topp(float* logits, int ld, int nseq, int V, const unsigned char* wrong, int ldw,
-                           const float* uniforms, const unsigned char* active, float temperature, int top_k,
-                           float top_p, int* token, float* probs_out, int ldp, hipStream_t stream);
-/* the same with PER-SEQUENCE controls and the log-probabilities of the drawn token (the reference samples one sequence
- * at a time with the request's one temperature / top_k, midi_inferrer.py:209-237, generate.py:43-44; it reports no
- * probabilities): temperature_rows / top_k_rows / top_p_rows, device arrays [nseq], each optional -- null: the scalar
- * argument applies to every sequence.  Sequence b's result is bit for bit that of commu_sample_topk_topp with b's triple.
- * top_k values are clamped to [1, V] in the kernel; validating the arrays is the caller's job.
- * logp_out (optional, fp32 [nseq][2]), for the token just drawn:
+ * commu/midi_generator/midi_inferrer.py:209-237), one wave per sequence.  ONE entry point; its arguments are a struct,
+ * documented here field by field.  Without a constraint the step is the reference's:
+ *   logits[b][1:V] /= temperature IN PLACE (quirk Q5), softmax, pad column 0 -> 0 (Q6), keep the top_k, zero
+ *   wrong[b][id] != 0, renormalise, draw by inverse CDF with uniforms[b].  temperature == 0: one-hot argmax.
+ *   token[b] = -1 when nothing can be drawn (Q12).
+ * struct_bytes: sizeof(commu_sample_args) as the caller compiled it; a value that differs from the library's
+ *   (commu_sample_args_bytes()) is refused with -22 before anything else is looked at.
+ * WHAT IS DRAWN FROM
+ *   logits fp32 [nseq][ld], the ids drawn from are 1 .. V-1 (2 <= V <= 768); wrong (optional) uint8 [nseq][ldw], the
+ *   rejected tokens; uniforms fp32 [nseq]; active (optional) uint8 [nseq]: only sequences with active[b] != 0 are processed.
+ * CONTROLS
+ *   temperature, top_k (1 .. V), top_p: one value for every sequence.  top_p is a nucleus filter after the top-k /
+ *   rejected-token step -- an extra mode, the reference has none (generate.py:43-44 offers top_k and temperature only): in
+ *   order of decreasing probability (ties: lowest id first) a token is kept while the probability mass before it is
+ *   < top_p; survivors renormalised.  top_p >= 1: off; top_p <= 0: -22.
+ *   temperature_rows / top_k_rows / top_p_rows: device arrays [nseq], each optional -- null: the scalar applies to every
+ *   sequence; given: the scalar is not looked at (the reference samples one sequence at a time with the request's one
+ *   temperature / top_k, midi_inferrer.py:209-237).  Sequence b's result is bit for bit that of the scalar call with b's
+ *   triple.  top_k values are clamped to [1, V] in the kernel; validating the arrays is the caller's job.
+ * RESULTS
+ *   token int32 [nseq]; probs_out (optional) fp32 [nseq][ldp], the distribution that was drawn from; logp_out (optional)
+ *   fp32 [nseq][2], for the token just drawn (the reference reports no probabilities):
  *   [0] full: log-softmax over ids 1 .. V-1 of the row as this draw used it -- logits / temperature as written back (the
  *       compounded row on a re-draw, Q5, like calc_probs), the raw row for temperature == 0 -- at the drawn id;
  *   [1] kept: log of the token's probability in the distribution it was drawn from (after top-k, rejected tokens, top-p
  *       and renormalisation: apply_sampling, :221-230); exactly 0 for temperature == 0.
  *   Both NaN when nothing could be drawn (token -1, Q12); sequences with active[b] == 0 keep their entries.
- * Required pointers (all sampling entry points, this one and the two above, which forward here): logits and token must be
- * valid, readable device arrays -- token [nseq] always receives the result, and the kernel issues every optional load
- * unconditionally: where `active` or a control array is null it reads token[b] or logits[b][0] instead and ignores the
- * value, so that these loads share one memory round trip with the logits. */
-int commu_sample_topk_topp_rows(float* logits, int ld, int nseq, int V, const unsigned char* wrong, int ldw,
-                                const float* uniforms, const unsigned char* active, float temperature, int top_k,
-                                float top_p, const float* temperature_rows, const int* top_k_rows,
-                                const float* top_p_rows, int* token, float* probs_out, int ldp, float* logp_out,
-                                hipStream_t stream);
-/* the same with a CONSTRAINT on what each sequence may draw (the reference has none: a ComMU request's pitch_range,
- * min/max_velocity and inst are conditioning hints only): bias, fp32 [nseq][ld_bias] with ld_bias >= V, optional.
- * With x the value the step computes without it -- logits / temperature, which is still what is written back; the raw row
- * for temperature == 0 -- the distribution is built from y[id] = x[id] + bias[b][id] for 1 <= id < V, one fp32 add: on the
- * scale of the row the softmax sees, so it is defined on a Q5 re-draw (the stored row is already divided), never
- * compounded, and a ban is exact either way.  A finite entry re-weights an id, -inf bans it; NaN and +inf are the
- * caller's to refuse (generate.token_constraints).
- *   Order: bias, then top-k, then the rejected-token mask `wrong`, then top-p -- a banned id takes none of the k places
- *   (`wrong`, quirk Q5 of the reference, does).  Max, sum, top-k, top-p and the draw all work on y; temperature == 0
- *   takes the argmax of y, ties to the lowest id.
- *   The bias is NEVER written back: after the call the logits are bit for bit what the call without it leaves, and a
- *   re-draw from them adds the bias once to the compounded row.
+ * CONSTRAINTS on what a sequence may draw (the reference has none: a ComMU request's pitch_range, min/max_velocity and
+ * inst are conditioning hints only).  Each is optional and each has kernels of its own: with a null pointer the launch
+ * is the kernel that never heard of the constraint, with the instructions and the argument block it always had.  With x
+ * the value the step computes without them -- logits / temperature, the raw row for temperature == 0 -- the
+ * distribution is built from
+ *   y[id] = ((x[id] + bias[b][id]) + gram[c][id]) + harm[r][(id - 3) mod 12]      for 1 <= id < V, in this fp32 order
+ *   (the third add at the pitch ids 3 <= id <= 130 only; a term whose pointer is null is not added).
+ *   ORDER: bias, then grammar row, then harmony row, then top-k, then the rejected-token mask `wrong`, then top-p -- a
+ *   banned id takes none of the k places (`wrong`, quirk Q5 of the reference, does).  Max, sum, top-k, top-p and the draw
+ *   all work on y; temperature == 0 takes the argmax of y, ties to the lowest id.  A finite entry re-weights an id, -inf
+ *   bans it; NaN and +inf are the caller's to refuse (generate.token_constraints).
+ *   NOTHING BUT x IS WRITTEN BACK: after the call the logits are bit for bit what the call without constraints leaves,
+ *   and a Q5 re-draw from them adds every term once to the compounded row (it sees the same rows c and r).
  *   probs_out is the constrained distribution, exactly 0 at banned ids.  logp_out[0] (full) is the log-softmax of y over
- *   ids 1 .. V-1 at the drawn id, "the row as this draw used it"; [1] (kept) as above; full <= kept still holds.
- *   A row whose every id is banned, or whose remaining ids `wrong` removes, takes the Q12 exit: token -1, NaN pair.
- *   The 12 bias loads of a lane are issued with its logits loads (same index clamp, lanes past V contribute nothing).
- * bias == null: commu_sample_topk_topp_rows bit for bit -- a kernel of its own, without the loads (the three entry
- * points above forward here with null).  ld_bias < V: -22. */
-int commu_sample_topk_topp_bias(float* logits, int ld, int nseq, int V, const unsigned char* wrong, int ldw,
-                                const float* uniforms, const unsigned char* active, float temperature, int top_k,
-                                float top_p, const float* temperature_rows, const int* top_k_rows,
-                                const float* top_p_rows, int* token, float* probs_out, int ldp, float* logp_out,
-                                const float* bias, int ld_bias, hipStream_t stream);
-/* the same with an EVENT GRAMMAR: a constraint chosen per draw by the sequence's own state, so that what is drawn
- * survives the reference's token-to-MIDI step, which keeps only the exact groups Position, Note Velocity, Note On,
- * Note Duration and Position, Chord and silently drops everything else (commu/preprocessor/encoder/encoder_utils.py:385-419).
- * gram: fp32 [8][ld_gram], ld_gram >= V, optional.  Row c is the additive row for a draw whose PREVIOUS token has class c;
- * classes by id: 0 OTHER (pad 0, EOS 1, ids >= 560), 1 BAR (2), 2 PITCH (3 .. 130), 3 VELOCITY (131 .. 194), 4 CHORD
- * (195 .. 303), 5 DURATION (304 .. 431), 6 POSITION (432 .. 559), found by range compares.  Row 7, zeros by convention,
- * is the row of a sequence whose switch gram_on[b] is 0 (gram_on == null: every sequence is on).  The previous token is
- * seq[b][state[b][F_LEN] - 1] (state: the forcing records, commu_forcing_state_ints() ints each; seq int32
- * [nseq][ld_seq]) at the moment the stage runs; a Q5 re-draw sees the same one.
- *   y[id] = (x[id] + bias[b][id]) + gram[c][id], in this fp32 order.  All that is said of the bias above holds for the
- *   grammar row: before top-k, never written back, probs_out exactly 0 at banned ids, full the log-softmax of y, a row
- *   with nothing left takes the Q12 exit.  The 12 grammar loads of a lane use the index clamp of its logits loads.
- * gram == null: commu_sample_topk_topp_bias bit for bit, with the kernel it always launched (it forwards here).
- * ld_gram < V, or a grammar without state / seq: -22. */
-int commu_sample_topk_topp_gram(float* logits, int ld, int nseq, int V, const unsigned char* wrong, int ldw,
-                                const float* uniforms, const unsigned char* active, float temperature, int top_k,
-                                float top_p, const float* temperature_rows, const int* top_k_rows,
-                                const float* top_p_rows, int* token, float* probs_out, int ldp, float* logp_out,
-                                const float* bias, int ld_bias, const float* gram, int ld_gram,
-                                const unsigned char* gram_on, const int* state, const int* seq, int ld_seq,
-                                hipStream_t stream);
-/* the same with a HARMONY table: a third additive term chosen by the chord the sequence is in, so that the pitches drawn
- * fit the chord that is sounding.  harm: fp32 [111][ld_harm], ld_harm >= 12 (16: a row is one 64-byte line), optional.
- * Row r holds 12 values by MIDI pitch class (column 0: C); token id is MIDI pitch id - 3.  r = t - 195 for the last
- * chord token t (195 .. 303: 12 roots x 9 qualities, then Chord_NN) of seq[b][0 .. F_LEN) when the stage runs, 109 while
- * seq holds none, 110 (zeros by convention) for a sequence whose switch harm_on[b] is 0 (harm_on == null: every sequence
- * is on).  A chord enters seq only as a forced token that the rules take from chord_tok[b][F_CUR] (int32
- * [nseq][ld_chord]) while they increment F_CUR, with no draw before it is appended, so the kernel reads
- * chord_tok[b][state[b][F_CUR] - 1] (none while F_CUR is 0); a Q5 re-draw sees the same row.
- *   y[id] = ((x[id] + bias[b][id]) + gram[c][id]) + harm[r][(id - 3) mod 12] for 3 <= id <= 130, in this fp32 order; every
- *   other id gets no third add.  All that is said of the bias and the grammar row holds: before top-k, never written
- *   back, probs_out exactly 0 at banned ids, full the log-softmax of y, a row with nothing left takes the Q12 exit.
- * One kernel serves it, with a bias and a grammar: a caller that has none passes a zero bias row and gram_on zeros (x + 0
- * is x and row 7 is zeros: bit for bit the draw without them).
- * harm == null: commu_sample_topk_topp_gram bit for bit, with the kernel it always launched.
- * ld_harm < 12, ld_chord < 1, a table without state / chord_tok, or without bias / gram / seq: -22. */
-int commu_sample_topk_topp_harm(float* logits, int ld, int nseq, int V, const unsigned char* wrong, int ldw,
-                                const float* uniforms, const unsigned char* active, float temperature, int top_k,
-                                float top_p, const float* temperature_rows, const int* top_k_rows,
-                                const float* top_p_rows, int* token, float* probs_out, int ldp, float* logp_out,
-                                const float* bias, int ld_bias, const float* gram, int ld_gram,
-                                const unsigned char* gram_on, const int* state, const int* seq, int ld_seq,
-                                const float* harm, int ld_harm, const unsigned char* harm_on, const int* chord_tok,
-                                int ld_chord, hipStream_t stream);
+ *   ids 1 .. V-1 at the drawn id; [1] (kept) as above; full <= kept still holds.  A row whose every id is banned, or
+ *   whose remaining ids `wrong` removes, takes the Q12 exit: token -1, NaN pair.  The 12 loads per lane of each term use
+ *   the index clamp of the lane's logits loads (lanes past V contribute nothing).
+ *   bias: fp32 [nseq][ld_bias], ld_bias >= V (else -22): sequence b's additive row.
+ *   gram: the EVENT GRAMMAR, fp32 [8][ld_gram], ld_gram >= V (else -22): a row chosen per draw by the sequence's own
+ *     state, so that what is drawn survives the reference's token-to-MIDI step, which keeps only the exact groups
+ *     Position, Note Velocity, Note On, Note Duration and Position, Chord and silently drops everything else
+ *     (commu/preprocessor/encoder/encoder_utils.py:385-419).  Row c is the row for a draw whose PREVIOUS token
+ *     seq[b][state[b][F_LEN] - 1] has class c; classes by id: 0 OTHER (pad 0, EOS 1, ids >= 560), 1 BAR (2), 2 PITCH
+ *     (3 .. 130), 3 VELOCITY (131 .. 194), 4 CHORD (195 .. 303), 5 DURATION (304 .. 431), 6 POSITION (432 .. 559), found
+ *     by range compares.  ROW 7, zeros by convention, is the OFF ROW: the row of a sequence whose switch gram_on[b] is 0.
+ *     gram_on: uint8 [nseq]; null: every sequence is on.  Needs state and seq (ld_seq >= 1), else -22.
+ *   harm: the HARMONY table, fp32 [111][ld_harm], ld_harm >= 12 (else -22; 16: a row is one 64-byte line): a row chosen
+ *     by the chord the sequence is in, so that the pitches drawn fit the chord that is sounding.  Row r holds 12 values by
+ *     MIDI pitch class (column 0: C); token id is MIDI pitch id - 3.  r = t - 195 for the last chord token t (195 .. 303:
+ *     12 roots x 9 qualities, then Chord_NN) of seq[b][0 .. F_LEN) when the stage runs, 109 while seq holds none.  ROW 110,
+ *     zeros by convention, is the OFF ROW: the row of a sequence whose switch harm_on[b] is 0.  harm_on: uint8 [nseq];
+ *     null: every sequence is on.  A chord enters seq only as a forced token that the rules take from
+ *     chord_tok[b][F_CUR] while they increment F_CUR, with no draw before it is appended, so the kernel reads
+ *     chord_tok[b][state[b][F_CUR] - 1] (none while F_CUR is 0).  ONE kernel serves it, with a bias and a grammar: harm
+ *     requires bias, gram, seq, state and chord_tok (ld_chord >= 1), else -22; a caller that has no bias or grammar
+ *     passes a zero bias row and gram_on zeros (x + 0 is x and row 7 is zeros: bit for bit the draw without them).
+ * WHAT gram / harm READ
+ *   state: the forcing records, int32 [nseq][commu_forcing_state_ints()]; seq int32 [nseq][ld_seq]; chord_tok int32
+ *   [nseq][ld_chord].  Not looked at, and may be null, in a call without gram and harm.
+ * REQUIRED POINTERS: logits and token must be valid, readable device arrays -- token [nseq] always receives the result,
+ * and the kernel issues every optional load unconditionally: where `active`, a control array or a switch array is null it
+ * reads token[b] or logits[b][0] instead and ignores the value, so that these loads share one memory round trip with the
+ * logits.  nseq <= 0: nothing is launched, 0. */
+typedef struct commu_sample_args {
+    unsigned struct_bytes;
+    /* what is drawn from */
+    float* logits;
+    const unsigned char* wrong;
+    const float* uniforms;
+    const unsigned char* active;
+    int ld, nseq, V, ldw;
+    /* controls */
+    const float* temperature_rows;
+    const int* top_k_rows;
+    const float* top_p_rows;
+    float temperature;
+    int top_k;
+    float top_p;
+    /* results */
+    int* token;
+    float* probs_out;
+    float* logp_out;
+    int ldp;
+    /* constraints */
+    const float* bias;
+    const float* gram;
+    const unsigned char* gram_on;
+    const float* harm;
+    const unsigned char* harm_on;
+    int ld_bias, ld_gram, ld_harm;
+    /* what gram / harm read */
+    const int* state;
+    const int* seq;
+    const int* chord_tok;
+    int ld_seq, ld_chord;
+} commu_sample_args;
+int commu_sample_args_bytes(void);
+int commu_sample_topk(const commu_sample_args* a, hipStream_t stream);
 
 /* ---- single-token decode step with a K/V cache (forward_generate with qlen 1, model.py:606-628, as
  * called by midi_inferrer.py:199-207).  Caches are bf16 [B][H][Lmax][DH] per layer; klen[b] = valid rows
@@ -634,98 +637,94 @@ int commu_decode_head(const int64_t* tok, const float* E, int d_true, int V, flo
  * int32 [B][ld_trace]) records (token, keep) of every model step.  commu_forcing_post applies the drawn token
  * (token[b] < 0: nothing could be drawn, Q12).  live (optional): += number of unfinished sequences. */
 int commu_forcing_state_ints(void);
+/* seq_logp (optional, fp32 [B][ld_seq][2], parallel to seq: the log-probability pair of every token, see
+ * commu_sample_args.logp_out): a FORCED token appended here (midi_inferrer.py:247-251) was not drawn and gets NaN, NaN;
+ * null: no pairs are kept */
 int commu_forcing_pre(int* state, int* seq, int ld_seq, const int* chord_tok, const int* chord_pos, int ld_chord,
                       unsigned char* wrong, const float* utable, int ld_u, int max_iters, long long* tok,
                       unsigned char* active, unsigned char* keep, unsigned char* draw, float* uni, int* trace,
-                      int ld_trace, int B, hipStream_t stream);
-/* commu_forcing_pre that also keeps seq_logp (optional, fp32 [B][ld_seq][2], parallel to seq: the log-probability pair
- * of every token, see commu_sample_topk_topp_rows): a FORCED token appended here (midi_inferrer.py:247-251) was not
- * drawn and gets NaN, NaN */
-int commu_forcing_pre_rows(int* state, int* seq, int ld_seq, const int* chord_tok, const int* chord_pos, int ld_chord,
-                           unsigned char* wrong, const float* utable, int ld_u, int max_iters, long long* tok,
-                           unsigned char* active, unsigned char* keep, unsigned char* draw, float* uni, int* trace,
-                           int ld_trace, float* seq_logp, int B, hipStream_t stream);
+                      int ld_trace, float* seq_logp, int B, hipStream_t stream);
 /* klen / keep (optional): the cache lengths of the decode step advance here (klen[b] += keep[b], capped at lmax - 1),
- * which saves the separate commu_decode_advance launch */
+ * which saves the separate commu_decode_advance launch.
+ * logp / seq_logp (optional): where the drawn token is appended (midi_inferrer.py:313-317) its pair logp[b][0:2] (fp32
+ * [B][2], what commu_sample_topk wrote beside token) is stored at the token's index; a draw that is not appended --
+ * rejected chord, position past a pending chord, replaced EOS / bar (:294-311), Q12 -- leaves no entry.  Null: no pairs
+ * are kept. */
 int commu_forcing_post(int* state, int* seq, int ld_seq, const int* chord_pos, int ld_chord, unsigned char* wrong,
                        const unsigned char* draw, const int* token, int* live, int* klen, const unsigned char* keep,
-                       int lmax, int B, hipStream_t stream);
-/* commu_forcing_post that also keeps seq_logp: where the drawn token is appended (midi_inferrer.py:313-317) its pair
- * logp[b][0:2] (fp32 [B][2], what commu_sample_topk_topp_rows wrote beside token) is stored at the token's index; a draw
- * that is not appended -- rejected chord, position past a pending chord, replaced EOS / bar (:294-311), Q12 -- leaves
- * no entry.  logp / seq_logp null: commu_forcing_post. */
-int commu_forcing_post_rows(int* state, int* seq, int ld_seq, const int* chord_pos, int ld_chord, unsigned char* wrong,
-                            const unsigned char* draw, const int* token, int* live, int* klen,
-                            const unsigned char* keep, int lmax, const float* logp, float* seq_logp, int B,
-                            hipStream_t stream);
-/* The three per-sequence stages that follow the model step as ONE launch, in this order and with the meaning of the
- * separate entry points: commu_sample_topk_topp (active = draw, wrong [B][729]) -> commu_forcing_post (live = null) ->
- * commu_forcing_pre (the decision of the NEXT iteration). */
+                       int lmax, const float* logp, float* seq_logp, int B, hipStream_t stream);
 /* diagnostics: following commu_decode_sample_post_pre launches write 100 MHz timestamps buf[sequence][4] = kernel start,
  * after the sampling step, after post, after pre (device memory; null: off) */
 int commu_decode_loop_trace(unsigned long long* buf);
-int commu_decode_sample_post_pre(float* logits, int ld, int V, unsigned char* wrong, float temperature, int top_k,
-                                 float top_p, int* token, float* probs_out, int ldp, int* state, int* seq, int ld_seq,
-                                 const int* chord_tok, const int* chord_pos, int ld_chord, const float* utable, int ld_u,
-                                 int max_iters, long long* tok, unsigned char* active, unsigned char* keep,
-                                 unsigned char* draw, float* uni, int* trace, int ld_trace, int* klen, int lmax, int B,
-                                 hipStream_t stream);
-/* The same launch from the _rows stages: commu_sample_topk_topp_rows (per-sequence controls, each array optional; logp
- * optional) -> commu_forcing_post_rows -> commu_forcing_pre_rows (seq_logp optional).  The pair reaches the book-keeping
- * stage in registers; logp[b] is written as well when given.  With every added pointer null this is
- * commu_decode_sample_post_pre (generate_sequence, midi_inferrer.py:239-320, one iteration).
- * Required pointers, here and in commu_decode_sample_post_pre: token, state, draw and keep (read at the top of the launch,
- * under the sampling stage, and handed to the book-keeping stage in registers; a null klen reads token[b] instead). */
-int commu_decode_sample_post_pre_rows(float* logits, int ld, int V, unsigned char* wrong, float temperature, int top_k,
-                                      float top_p, const float* temperature_rows, const int* top_k_rows,
-                                      const float* top_p_rows, int* token, float* probs_out, int ldp, float* logp,
-                                      float* seq_logp, int* state, int* seq, int ld_seq, const int* chord_tok,
-                                      const int* chord_pos, int ld_chord, const float* utable, int ld_u, int max_iters,
-                                      long long* tok, unsigned char* active, unsigned char* keep, unsigned char* draw,
-                                      float* uni, int* trace, int ld_trace, int* klen, int lmax, int B,
-                                      hipStream_t stream);
-/* The same launch with the sampling stage of commu_sample_topk_topp_bias: bias fp32 [B][ld_bias] (ld_bias >= 729),
- * sequence b's constraint row -- read by the sampling stage only.  Forced tokens are not draws and are not affected; the
- * rejected-token map stays the forcing rules' own.  bias == null: commu_decode_sample_post_pre_rows, which forwards here,
- * bit for bit and with the kernel it always launched. */
-int commu_decode_sample_post_pre_bias(float* logits, int ld, int V, unsigned char* wrong, float temperature, int top_k,
-                                      float top_p, const float* temperature_rows, const int* top_k_rows,
-                                      const float* top_p_rows, int* token, float* probs_out, int ldp, float* logp,
-                                      float* seq_logp, int* state, int* seq, int ld_seq, const int* chord_tok,
-                                      const int* chord_pos, int ld_chord, const float* utable, int ld_u, int max_iters,
-                                      long long* tok, unsigned char* active, unsigned char* keep, unsigned char* draw,
-                                      float* uni, int* trace, int ld_trace, int* klen, int lmax, int B,
-                                      const float* bias, int ld_bias, hipStream_t stream);
-/* The same launch with the sampling stage of commu_sample_topk_topp_gram (the event grammar that keeps every drawn token
- * inside a group encoder_utils.py:385-419 turns into a note or a chord): gram fp32 [8][ld_gram] (ld_gram >= 729), gram_on
- * [B] bytes (null: all on).  The previous token is read through the record the launch holds anyway; the sampling stage issues
- * that load right behind its logits loads.  Forced tokens (midi_inferrer.py:239-320) and prompts are not draws: not affected, not checked.  gram == null:
- * commu_decode_sample_post_pre_bias, which forwards here, bit for bit and with the kernel it always launched. */
-int commu_decode_sample_post_pre_gram(float* logits, int ld, int V, unsigned char* wrong, float temperature, int top_k,
-                                      float top_p, const float* temperature_rows, const int* top_k_rows,
-                                      const float* top_p_rows, int* token, float* probs_out, int ldp, float* logp,
-                                      float* seq_logp, int* state, int* seq, int ld_seq, const int* chord_tok,
-                                      const int* chord_pos, int ld_chord, const float* utable, int ld_u, int max_iters,
-                                      long long* tok, unsigned char* active, unsigned char* keep, unsigned char* draw,
-                                      float* uni, int* trace, int ld_trace, int* klen, int lmax, int B,
-                                      const float* bias, int ld_bias, const float* gram, int ld_gram,
-                                      const unsigned char* gram_on, hipStream_t stream);
-/* The same launch with the sampling stage of commu_sample_topk_topp_harm: harm fp32 [111][ld_harm] (ld_harm >= 12),
- * harm_on [B] bytes (null: all on).  The chord is chord_tok[b][F_CUR - 1] of the record the launch holds anyway; the
- * sampling stage issues that load beside the grammar's previous-token load.  One kernel, with a bias and a grammar (pass a
- * zero bias and gram_on zeros where there is none).  Forced tokens and prompts are not draws: not affected, not checked.
- * harm == null: commu_decode_sample_post_pre_gram bit for bit, with the kernel it always launched.  ld_harm < 12, or a
- * table without bias / gram: -22. */
-int commu_decode_sample_post_pre_harm(float* logits, int ld, int V, unsigned char* wrong, float temperature, int top_k,
-                                      float top_p, const float* temperature_rows, const int* top_k_rows,
-                                      const float* top_p_rows, int* token, float* probs_out, int ldp, float* logp,
-                                      float* seq_logp, int* state, int* seq, int ld_seq, const int* chord_tok,
-                                      const int* chord_pos, int ld_chord, const float* utable, int ld_u, int max_iters,
-                                      long long* tok, unsigned char* active, unsigned char* keep, unsigned char* draw,
-                                      float* uni, int* trace, int ld_trace, int* klen, int lmax, int B,
-                                      const float* bias, int ld_bias, const float* gram, int ld_gram,
-                                      const unsigned char* gram_on, const float* harm, int ld_harm,
-                                      const unsigned char* harm_on, hipStream_t stream);
+/* The three per-sequence stages that follow the model step as ONE launch (generate_sequence, midi_inferrer.py:239-320,
+ * one iteration), in this order and with the meaning of the separate entry points:
+ *   commu_sample_topk (active = draw, uniforms = uni, ldw = 729, nseq = B) -> commu_forcing_post (live = null) ->
+ *   commu_forcing_pre (the decision of the NEXT iteration).
+ * The fields are those arguments under their names there; what differs:
+ *   struct_bytes: sizeof(commu_decode_loop_args) as the caller compiled it; a value that differs from the library's
+ *     (commu_decode_loop_args_bytes()) is refused with -22 before anything else is looked at.
+ *   V must be 729 (wrong is uint8 [B][729]); ld_seq >= 2, ld_chord >= 1, ld_u >= 1 (else -22).
+ *   logp (optional): the pair of the draw reaches the book-keeping stage in registers; logp[b] is written as well when
+ *     given.  seq_logp optional, as in the separate stages.
+ *   klen / lmax: as commu_forcing_post (a sliding memory passes a large lmax).
+ *   bias / gram / gram_on / harm / harm_on: the constraints of commu_sample_args with the same order, the same off rows
+ *     7 and 110, the same "nothing but x is written back" and the same kernel selection: a null pointer launches the
+ *     kernel that never heard of the constraint (instructions and argument block); harm requires bias and gram (pass a
+ *     zero bias and gram_on zeros where there is none), else -22; ld_bias / ld_gram < 729 or ld_harm < 12: -22; a null
+ *     switch array: every sequence is on.  The grammar's previous token and the harmony's chord chord_tok[b][F_CUR - 1]
+ *     are read through the record the launch holds anyway; the sampling stage issues those two loads right behind its
+ *     logits loads.  gram and harm need state and seq, harm chord_tok (else -22).  Forced tokens (midi_inferrer.py:239-320)
+ *     and prompts are not draws: not affected, not checked; the rejected-token map stays the forcing rules' own.
+ * REQUIRED POINTERS beside those of the stages: token, state, draw and keep (read at the top of the launch, under the
+ * sampling stage, and handed to the book-keeping stage in registers; a null klen reads token[b] instead, a null switch
+ * array draw[b]).  B <= 0: nothing is launched, 0. */
+typedef struct commu_decode_loop_args {
+    unsigned struct_bytes;
+    /* what is drawn from */
+    float* logits;
+    unsigned char* wrong;
+    int ld, V, B;
+    /* controls */
+    const float* temperature_rows;
+    const int* top_k_rows;
+    const float* top_p_rows;
+    float temperature;
+    int top_k;
+    float top_p;
+    /* results */
+    int* token;
+    float* probs_out;
+    float* logp;
+    float* seq_logp;
+    int ldp;
+    /* the forcing records and what the rules read */
+    int* state;
+    int* seq;
+    const int* chord_tok;
+    const int* chord_pos;
+    const float* utable;
+    int ld_seq, ld_chord, ld_u, max_iters;
+    /* the decision of the next iteration */
+    long long* tok;
+    unsigned char* active;
+    unsigned char* keep;
+    unsigned char* draw;
+    float* uni;
+    int* trace;
+    int ld_trace;
+    /* cache lengths */
+    int* klen;
+    int lmax;
+    /* constraints */
+    const float* bias;
+    const float* gram;
+    const unsigned char* gram_on;
+    const float* harm;
+    const unsigned char* harm_on;
+    int ld_bias, ld_gram, ld_harm;
+} commu_decode_loop_args;
+int commu_decode_loop_args_bytes(void);
+int commu_decode_sample_post_pre(const commu_decode_loop_args* a, hipStream_t stream);
 /* ---- primed generation: enter the loop at an arbitrary point of a sequence (continue a given token prefix).
  * commu_forcing_replay runs the two transitions above over prompt[b][0 .. prompt_len[b]) WITHOUT a model step, starting
  * from the record, seq and klen as a load of the conditioning context leaves them (midi_inferrer.py:186-197): wherever

@@ -1,5 +1,5 @@
 """The sampling step with a constraint row, restated in plain numpy (no GPU, no package code): what
-commu_sample_topk_topp_bias computes for ONE sequence, in the documented order
+commu_sample_topk computes for ONE sequence with a bias row, in the documented order
 
     x = raw / temperature (fp32, written back; the raw row for temperature 0)
     y = x + bias                       (fp32, ids 1 .. V-1; never written back)

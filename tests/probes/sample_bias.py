@@ -1,4 +1,4 @@
-"""What a constraint row per slot (ForcedDecoder.set_logit_bias, commu_decode_sample_post_pre_bias) costs per decode
+"""What a constraint row per slot (ForcedDecoder.set_logit_bias, commu_decode_loop_args.bias) costs per decode
 iteration: the bench model (L6 D512 H8), 64 slots at ~11 keys -- where the sampling stage is the largest share of the
 iteration --, graph replay, three decoders INTERLEAVED, REPS repeats of ITERS iterations each:
 
@@ -6,8 +6,8 @@ iteration --, graph replay, three decoders INTERLEAVED, REPS repeats of ITERS it
   * zeros  -- the bias buffer allocated and all zeros: the 3 KB per slot are loaded, nothing changes;
   * rows   -- a pitch range, banned chord tokens and a finite re-weighting in every slot.
 
-Also the stand-alone sampling kernel (commu_sample_topk_topp_bias, 64 rows) with and without the rows, by HIP events.
-JSON lines: ms per iteration / us per launch, median and spread.
+Also the stand-alone sampling kernel (commu_sample_topk with commu_sample_args.bias, 64 rows) with and without the rows, by
+HIP events.  JSON lines: ms per iteration / us per launch, median and spread.
 
     python tests/probes/sample_bias.py [--out FILE]
 """

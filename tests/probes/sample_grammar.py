@@ -1,4 +1,4 @@
-"""What the event grammar (ForcedDecoder.set_grammar, commu_decode_sample_post_pre_gram) costs per decode iteration and what
+"""What the event grammar (ForcedDecoder.set_grammar, commu_decode_loop_args.gram) costs per decode iteration and what
 it buys: the bench model (L6 D512 H8), 64 slots, graph replay.
 
   --rows iter     ms per iteration at about 11 keys and at 1000 keys, decoders INTERLEAVED, REPS windows of SUB iterations
@@ -11,9 +11,9 @@ it buys: the bench model (L6 D512 H8), 64 slots, graph replay.
                   library built; --tag names the rows; --modes null: this tree with the one decoder the parent's process
                   has -- three decoders interleaved evict each other's caches, one alone does not), e.g. new, parent, new,
                   parent: the two runs of one tree give the A/A spread.
-  --rows kernel   the stand-alone sampling kernel (commu_sample_topk_topp_gram, 64 rows), 200 launches back to back by HIP
-                  events, as a graph replay (the device's time) and from Python (bound by the host): no grammar, every row
-                  off, the default table.
+  --rows kernel   the stand-alone sampling kernel (commu_sample_topk with commu_sample_args.gram, 64 rows), 200 launches
+                  back to back by HIP events, as a graph replay (the device's time) and from Python (bound by the host):
+                  no grammar, every row off, the default table.
   --rows waste    the decode fixture's small UNTRAINED model (tests/golden/g6_decode.npz), 64 slots, generation_length 512,
                   with and without the grammar: notes per sequence (count_notes) and draws per sequence that were not
                   appended (F_NDRAW minus the appended draws).

@@ -1,4 +1,4 @@
-"""What the harmony constraint (ForcedDecoder.set_harmony, commu_decode_sample_post_pre_harm) costs per decode iteration:
+"""What the harmony constraint (ForcedDecoder.set_harmony, commu_decode_loop_args.harm) costs per decode iteration:
 the bench model (L6 D512 H8), 64 slots, graph replay.  Every slot is primed behind its first forced chord (bar, position 0,
 Chord_am), so the strict table has a chord row to apply; the model's bias keeps bars, EOS and chord tokens away afterwards,
 so every iteration is a model step and a draw.  A slot starts at 15 keys (12 of the context, 3 of the prompt); the WARM = 32

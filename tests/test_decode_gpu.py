@@ -73,7 +73,7 @@ def test_sampling_topk_selection_matches_torch_topk():
 
 @pytest.mark.parametrize("top_p", [0.3, 0.6, 0.9, 0.999])
 def test_sampling_nucleus_filter_vs_oracle(top_p):
-    """The extra top-p mode (commu_sample_topk_topp; the reference has top-k only): the kept set and the renormalised
+    """The extra top-p mode (commu_sample_args.top_p; the reference has top-k only): the kept set and the renormalised
     probabilities against oracle.decode_ref.apply_top_p applied to the oracle's top-k / rejected-token distribution, with
     and without rejected tokens, including rows with exact ties at the nucleus boundary; the draw is the inverse CDF of
     that distribution.  Rows whose cumulative mass passes within 1e-5 of top_p are checked up to that one token."""

@@ -1,8 +1,7 @@
-"""The event grammar on the GPU: the sampling kernel with a grammar table (commu_sample_topk_topp_gram) against the numpy
-restatement (grammar_contract.restate_with_grammar: (x + bias) + gram[class of the previous token]) and against the entry
-points without one, bit for bit; then through the decode loop (fused launch, captured graph, separate launches, fp32
+"""The event grammar on the GPU: the sampling kernel with a grammar table (commu_sample_args.gram) against the numpy
+restatement (grammar_contract.restate_with_grammar: (x + bias) + gram[class of the previous token]) and against the
+launches without one, bit for bit; then through the decode loop (fused launch, captured graph, separate launches, fp32
 parity), in-place switching, primed slots, the single-request API, one cache combination and the CLI's --help."""
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -17,6 +16,7 @@ import grammar_contract as GC  # noqa: E402
 import test_decode_gpu as TD  # noqa: E402
 import test_logit_bias_gpu as LBG  # noqa: E402
 import test_sampling_rows_gpu as SR  # noqa: E402
+from sample_launch import sample_launch  # noqa: E402
 
 DEV = "cuda"
 V = 729
@@ -27,14 +27,6 @@ N = 16
 # previous tokens of the 16 kernel rows: every class and both ends of every id range
 PREV = [0, 1, 2, 3, 130, 131, 194, 195, 303, 304, 431, 432, 559, 560, 728, 60]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _s():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def records(prev):
@@ -51,30 +43,12 @@ def records(prev):
     return st, seq
 
 
-def launch(r, entry="gram", bias=None, gram=None, on=None, wrong=None, ld_gram=None, state=True):
-    """One launch on fresh device copies of the 16 rows; entry "gram" / "bias"."""
-    from commu_amd._lib import call
-    lg = r["logits"].clone().to(DEV)
-    pr = torch.full((N, V), -3.0, device=DEV)
-    tok = torch.full((N,), -7, dtype=torch.int32, device=DEV)
-    lp = torch.full((N, 2), 7.0, device=DEV)
-    w = (r["wrong"] if wrong is None else wrong).to(DEV)
-    u, td, kd, pd = r["us"].to(DEV), r["t"].to(DEV), r["k"].to(DEV), r["p"].to(DEV)
-    bd = None if bias is None else bias.to(DEV)
-    args = [_p(lg), lg.stride(0), N, V, _p(w), w.stride(0), _p(u), None, 0.0, 1, 1.0, _p(td), _p(kd), _p(pd), _p(tok), _p(pr),
-            pr.stride(0), _p(lp), _p(bd), 0 if bd is None else bd.stride(0)]
-    keep = []
-    if entry == "gram":
-        gd = None if gram is None else torch.as_tensor(gram).to(DEV)
-        od = None if on is None else on.to(DEV)
-        st, sq = r["state"].to(DEV), r["seq"].to(DEV)
-        keep = [gd, od, st, sq]
-        args += [_p(gd), 0 if gd is None else (gd.stride(0) if ld_gram is None else ld_gram), _p(od),
-                 _p(st) if state else None, _p(sq) if state else None, sq.stride(0)]
-    call("commu_sample_topk_topp_" + entry, *args, _s())
-    torch.cuda.synchronize()
-    del keep
-    return lg.cpu(), tok.cpu(), pr.cpu(), lp.cpu()
+def launch(r, bias=None, gram=None, on=None, wrong=None, ld_gram=None, state=True):
+    """One launch on fresh device copies of the 16 rows (sample_launch); state=False: null record and seq pointers (the
+    row stride of seq is still passed)."""
+    return sample_launch(r["logits"], r["wrong"] if wrong is None else wrong, r["us"], r["t"], r["k"], r["p"], bias=bias,
+                         gram=gram, ld_gram=ld_gram, gram_on=on, state=r["state"] if state else None,
+                         seq=r["seq"] if state else None, ld_seq=r["seq"].stride(0))
 
 
 @pytest.fixture(scope="module")
@@ -133,7 +107,7 @@ def check(r, out, bias, gram, on=None, wrong=None):
 def test_separate_sampler_against_the_restatement(rows):
     from commu_amd.generate import event_grammar
     default = torch.from_numpy(event_grammar())
-    free = launch(rows, "bias")
+    free = launch(rows, state=False)
     for bias in (None, rows["bias"]):
         out = launch(rows, bias=bias, gram=default)
         refs = check(rows, out, bias, default)
@@ -172,10 +146,11 @@ def test_grammar_off_is_the_bias_entry_point_bit_for_bit(rows):
     default = torch.from_numpy(event_grammar())
     off = torch.zeros(N, dtype=torch.uint8)
     for bias in (None, rows["bias"]):
-        old = launch(rows, "bias", bias=bias)
+        # (`old`, no grammar and no record / seq pointers, is what the entry point without a grammar argument and the one
+        # with gram == null and no state were: one call now)
+        old = launch(rows, bias=bias, state=False)
         assert same(old, launch(rows, bias=bias, gram=default, on=off))
         assert same(old, launch(rows, bias=bias, gram=None))
-        assert same(old, launch(rows, bias=bias, gram=None, state=False))
     assert int((old[1] >= 1).sum()) >= 8
     # refusals of the C entry point: a short row stride, a grammar without the record / seq
     for kw in (dict(ld_gram=700), dict(state=False)):

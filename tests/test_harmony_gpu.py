@@ -1,9 +1,8 @@
-"""The harmony constraint on the GPU: the sampling kernel with a harmony table (commu_sample_topk_topp_harm) against the
+"""The harmony constraint on the GPU: the sampling kernel with a harmony table (commu_sample_args.harm) against the
 numpy restatement (harmony_contract.restate_with_harmony: ((x + bias) + gram[c]) + harm[r][(id - 3) mod 12] at the pitch
-ids, r from the last chord of seq) and against the entry point without one, bit for bit; then through the decode loop
+ids, r from the last chord of seq) and against the launch without one, bit for bit; then through the decode loop
 (fused launch, captured graph, fp32 parity), a mid-bar chord change, primed slots, in-place switching, the single-request
 API, the fp8 sliding cache and the CLI."""
-import ctypes as C
 import json
 import os
 import subprocess
@@ -21,6 +20,7 @@ import harmony_contract as HC  # noqa: E402
 import test_decode_gpu as TD  # noqa: E402
 import test_logit_bias_gpu as LBG  # noqa: E402
 import test_sampling_rows_gpu as SR  # noqa: E402
+from sample_launch import sample_launch  # noqa: E402
 
 DEV = "cuda"
 V = 729
@@ -37,14 +37,6 @@ EDGE_IDS = [2, 3, 14, 15, 130, 131]
 TOP32 = [16, 19]                # top_k 32 rows under chord rows 0 / 107 whose 32 most likely ids the chord bans
 # previous token of row b (the grammar's key): mostly a velocity, after which the grammar admits pitches only
 PREV = [140 if b % 4 else (432, 2, 310, 60, 559, 600)[b // 4] for b in range(N)]
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _s():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def case_of(b):
@@ -107,34 +99,14 @@ def rows():
                 toks=toks, on=on, strict=torch.from_numpy(strict))
 
 
-def launch(r, entry="harm", bias=None, gram=None, gram_on=None, harm=None, harm_on=None, wrong=None, ld_harm=None,
-           state=True, chords=True, ld_chord=None):
-    """One launch on fresh device copies of the 24 rows; entry "harm" / "gram"."""
-    from commu_amd._lib import call
-    lg = r["logits"].clone().to(DEV)
-    pr = torch.full((N, V), -3.0, device=DEV)
-    tok = torch.full((N,), -7, dtype=torch.int32, device=DEV)
-    lp = torch.full((N, 2), 7.0, device=DEV)
-    w = (r["wrong"] if wrong is None else wrong).to(DEV)
-    u, td, kd, pd = r["us"].to(DEV), r["t"].to(DEV), r["k"].to(DEV), r["p"].to(DEV)
-    bd = None if bias is None else bias.to(DEV)
-    gd = None if gram is None else torch.as_tensor(gram).to(DEV)
-    god = None if gram_on is None else gram_on.to(DEV)
-    st, sq, ct = r["state"].to(DEV), r["seq"].to(DEV), r["chord_tok"].to(DEV)
-    args = [_p(lg), lg.stride(0), N, V, _p(w), w.stride(0), _p(u), None, 0.0, 1, 1.0, _p(td), _p(kd), _p(pd), _p(tok), _p(pr),
-            pr.stride(0), _p(lp), _p(bd), 0 if bd is None else bd.stride(0), _p(gd), 0 if gd is None else gd.stride(0), _p(god),
-            _p(st) if state else None, _p(sq), sq.stride(0)]
-    keep = [bd, gd, god, st, sq, ct]
-    if entry == "harm":
-        hd = None if harm is None else torch.as_tensor(harm).to(DEV).contiguous()
-        hod = None if harm_on is None else harm_on.to(DEV)
-        keep += [hd, hod]
-        args += [_p(hd), 0 if hd is None else (hd.stride(0) if ld_harm is None else ld_harm), _p(hod),
-                 _p(ct) if chords else None, ct.stride(0) if ld_chord is None else ld_chord]
-    call("commu_sample_topk_topp_" + entry, *args, _s())
-    torch.cuda.synchronize()
-    del keep
-    return lg.cpu(), tok.cpu(), pr.cpu(), lp.cpu()
+def launch(r, bias=None, gram=None, gram_on=None, harm=None, harm_on=None, wrong=None, ld_harm=None, state=True,
+           chords=True, ld_chord=None):
+    """One launch on fresh device copies of the 24 rows (sample_launch); state=False / chords=False: a null record /
+    chord_tok pointer (the row stride of chord_tok is still passed)."""
+    return sample_launch(r["logits"], r["wrong"] if wrong is None else wrong, r["us"], r["t"], r["k"], r["p"], bias=bias,
+                         gram=gram, gram_on=gram_on, harm=harm, ld_harm=ld_harm, harm_on=harm_on,
+                         state=r["state"] if state else None, seq=r["seq"], chord_tok=r["chord_tok"] if chords else None,
+                         ld_chord=r["chord_tok"].stride(0) if ld_chord is None else ld_chord)
 
 
 def zero_bias():
@@ -204,7 +176,7 @@ def test_separate_sampler_against_the_restatement(rows):
     from commu_amd.generate import event_grammar
     default = torch.from_numpy(event_grammar())
     zg, zon = off_grammar()
-    free = launch(rows, "gram")
+    free = launch(rows, chords=False)
     strict = rows["strict"]
     for bias, gram in ((None, None), (rows["bias"], None), (None, default), (rows["bias"], default)):
         kw = dict(bias=zero_bias() if bias is None else bias, gram=zg if gram is None else gram,
@@ -235,7 +207,7 @@ def test_separate_sampler_against_the_restatement(rows):
     # ids 2 and 131 are untouched by a table whose every entry is -5: their ratio to each other is the free call's, their
     # ratio to a pitch id is e^5 times the free call's
     flat = launch(rows, bias=zero_bias(), gram=zg, gram_on=zon, harm=flat_table(), harm_on=rows["on"])
-    fr = launch(rows, "gram", bias=zero_bias(), gram=zg, gram_on=zon)
+    fr = launch(rows, bias=zero_bias(), gram=zg, gram_on=zon, chords=False)
     checked = 0
     for b in range(N):
         a, f = flat[2][b].double(), fr[2][b].double()
@@ -275,11 +247,11 @@ def test_off_slots_and_a_zero_table_are_the_gram_entry_point_bit_for_bit(rows):
     default = torch.from_numpy(event_grammar())
     all_off = torch.zeros(N, dtype=torch.uint8)
     for bias in (zero_bias(), rows["bias"]):
-        old = launch(rows, "gram", bias=bias, gram=default)
+        old = launch(rows, bias=bias, gram=default, chords=False)
         assert same(old, launch(rows, bias=bias, gram=default, harm=rows["strict"], harm_on=all_off))
         assert same(old, launch(rows, bias=bias, gram=default, harm=np.zeros((111, 16), np.float32), harm_on=rows["on"]))
-        assert same(old, launch(rows, bias=bias, gram=default, harm=None))          # (forwards to the gram entry point)
-    assert same(launch(rows, "gram"), launch(rows, bias=zero_bias(), gram=off_grammar()[0], gram_on=off_grammar()[1],
+        assert same(old, launch(rows, bias=bias, gram=default, harm=None))          # (same kernel, given a chord_tok)
+    assert same(launch(rows, chords=False), launch(rows, bias=zero_bias(), gram=off_grammar()[0], gram_on=off_grammar()[1],
                                              harm=rows["strict"], harm_on=all_off))
     assert int((old[1] >= 1).sum()) >= 12
     assert not same(old, launch(rows, bias=rows["bias"], gram=default, harm=rows["strict"], harm_on=rows["on"]))

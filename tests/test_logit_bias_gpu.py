@@ -1,9 +1,7 @@
-"""Constrained sampling on the GPU: the sampling kernel with a per-slot additive bias row (commu_sample_topk_topp_bias)
-against the entry points without one (bit for bit), against the numpy restatement of the documented order
+"""Constrained sampling on the GPU: the sampling kernel with a per-slot additive bias row (commu_sample_args.bias)
+against the launch without one (bit for bit), against the numpy restatement of the documented order
 (logit_bias_contract.restate: bias, top-k, rejected tokens, top-p), its write-back and edge rows; then the same rows
 through the decode loop (fused launch, captured graph, in-place updates, primed slots) and the single-request API."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
@@ -13,20 +11,13 @@ pytestmark = pytest.mark.gpu
 import logit_bias_contract as LB  # noqa: E402
 import test_decode_gpu as TD  # noqa: E402
 import test_sampling_rows_gpu as SR  # noqa: E402
+from sample_launch import sample_launch  # noqa: E402
 
 DEV = "cuda"
 V = 729
 NEG = float("-inf")
 LOGP_TOL = SR.LOGP_TOL          # (the reference is fed y as fp32 rounds it: the added operation brings no new error)
 bits = SR.bits
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _s():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def bias_rows(logits):
@@ -45,28 +36,10 @@ def bias_rows(logits):
     return bias, kind
 
 
-def launch(entry, logits, wrong, us, t, k, p, active=None, bias=None, ld_bias=None, v=V, logp=True, uniform=None):
-    """One launch of `entry` ("bias" / "rows") on fresh device copies; t / k / p: per-row tensors."""
-    from commu_amd._lib import call
-    n = logits.shape[0]
-    lg = logits.clone().to(DEV)
-    pr = torch.full((n, V), -3.0, device=DEV)
-    tok = torch.full((n,), -7, dtype=torch.int32, device=DEV)
-    lp = torch.full((n, 2), 7.0, device=DEV) if logp else None
-    w = None if wrong is None else wrong.to(DEV)
-    u = (us if uniform is None else torch.full((n,), uniform, dtype=torch.float32)).to(DEV)
-    a = None if active is None else active.to(DEV)
-    td, kd, pd = t.to(DEV), k.to(DEV), p.to(DEV)
-    bd = None if bias is None else bias.to(DEV)
-    args = [_p(lg), lg.stride(0), n, v, _p(w), 0 if w is None else w.stride(0), _p(u), _p(a), 0.0, 1, 1.0, _p(td), _p(kd),
-            _p(pd), _p(tok), _p(pr), pr.stride(0), _p(lp)]
-    if entry == "bias":
-        args += [_p(bd), 0 if bd is None else (bd.stride(0) if ld_bias is None else ld_bias)]
-    else:
-        assert bias is None
-    call("commu_sample_topk_topp_" + entry, *args, _s())
-    torch.cuda.synchronize()
-    return lg.cpu(), tok.cpu(), pr.cpu(), None if lp is None else lp.cpu()
+def launch(logits, wrong, us, t, k, p, active=None, bias=None, ld_bias=None, v=V, logp=True, uniform=None):
+    """One launch on fresh device copies (sample_launch); t / k / p: per-row tensors; bias None: a null pointer."""
+    u = us if uniform is None else torch.full((logits.shape[0],), uniform, dtype=torch.float32)
+    return sample_launch(logits, wrong, u, t, k, p, v=v, active=active, logp=logp, bias=bias, ld_bias=ld_bias)
 
 
 @pytest.fixture(scope="module")
@@ -88,14 +61,14 @@ def same(a, b):
 
 # ------------------------------------------------------------------------------------------------ 1. nothing changes
 def test_null_bias_zero_bias_and_the_rows_entry_point_agree_bit_for_bit(rows):
-    """Tokens, probs_out, the log-probability pair and the written-back logits, with and without an active mask."""
+    """Tokens, probs_out, the log-probability pair and the written-back logits, with and without an active mask.  (The
+    former entry point without a bias argument and the one with a null bias are one call of commu_sample_topk now: `old`.)"""
     for active in (None, rows["active"]):
-        old = launch("rows", *_args(rows), active=active)
-        null = launch("bias", *_args(rows), active=active)
-        zero = launch("bias", *_args(rows), active=active, bias=torch.zeros(64, 768))
-        assert same(old, null) and same(old, zero)
+        old = launch(*_args(rows), active=active)
+        zero = launch(*_args(rows), active=active, bias=torch.zeros(64, 768))
+        assert same(old, zero)
         assert int((old[1] == -1).sum()) >= 1 and int((old[1] > 0).sum()) >= 40
-    # and through ops.sample_topk, which now takes the new entry point
+    # and through ops.sample_topk, which fills the same struct
     lg, tok, pr, lp = SR.run_rows(rows["logits"], rows["wrong"], rows["us"], rows["t"], rows["k"], rows["p"],
                                   rows["active"], logp=True)
     assert same(old, (lg.cpu(), tok.cpu(), pr.cpu(), lp.cpu()))
@@ -107,7 +80,7 @@ def test_bans_are_exact_zeros_and_never_drawn(rows):
     banned = bias[:, :V] == NEG
     assert int(banned[kind == 1].sum()) > 1000
     for u in (0.0, 1.0 - 2.0 ** -24, 0.1, 0.37, 0.5, 0.9, 0.999):
-        lg, tok, pr, lp = launch("bias", *_args(rows), active=rows["active"], bias=bias, uniform=u)
+        lg, tok, pr, lp = launch(*_args(rows), active=rows["active"], bias=bias, uniform=u)
         drew = on & (tok >= 0)
         assert int(drew.sum()) >= 40
         assert bool((pr[drew][banned[drew]] == 0.0).all())               # exactly 0, not merely small
@@ -125,7 +98,7 @@ def test_a_ban_takes_none_of_the_k_places(rows):
     bias = torch.zeros(64, 768)
     for b in range(64):
         bias[b, order[b, :int(k[b])]] = NEG
-    lg, tok, pr, lp = launch("bias", *_args(rows), bias=bias)
+    lg, tok, pr, lp = launch(*_args(rows), bias=bias)
     plain = 0
     for b in range(64):
         kb = int(k[b])
@@ -191,16 +164,16 @@ def test_finite_bias_against_the_float64_restatement(rows):
     inactive rows) within LOGP_TOL of the restatement, which is fed y as fp32 rounds it.  Then +4 on the id a greedy row
     drew without a bias: it is drawn again and its `full` has moved."""
     bias = rows["bias"]
-    out = launch("bias", *_args(rows), active=rows["active"], bias=bias)
+    out = launch(*_args(rows), active=rows["active"], bias=bias)
     refs = check_against_restatement(rows, out, rows["logits"].numpy(), bias)
     assert sum(1 for r in refs if r is not None and r.token < 0) >= 1
-    free = launch("bias", *_args(rows), active=rows["active"])
+    free = launch(*_args(rows), active=rows["active"])
     greedy = [b for b in range(64) if float(rows["t"][b]) == 0 and int(free[1][b]) >= 1]
     assert len(greedy) >= 4
     plus = torch.zeros(64, 768)
     for b in greedy:
         plus[b, int(free[1][b])] = 4.0
-    moved = launch("bias", *_args(rows), active=rows["active"], bias=plus)
+    moved = launch(*_args(rows), active=rows["active"], bias=plus)
     for b in greedy:
         assert int(moved[1][b]) == int(free[1][b])
         assert abs(float(moved[3][b, 0]) - float(free[3][b, 0])) > 1e-3, b
@@ -211,13 +184,13 @@ def test_tail_lanes_and_the_row_stride(rows):
     """V = 600: lanes whose ids lie past V load a clamped index and contribute nothing (the bias holds NaN there, the
     logits +inf); ld_bias = 729: a bias of another row stride gives the same bits."""
     bias = rows["bias"].clone()
-    out768 = launch("bias", *_args(rows), active=rows["active"], bias=bias)
-    out729 = launch("bias", *_args(rows), active=rows["active"], bias=bias[:, :V].contiguous())
+    out768 = launch(*_args(rows), active=rows["active"], bias=bias)
+    out729 = launch(*_args(rows), active=rows["active"], bias=bias[:, :V].contiguous())
     assert same(out768, out729)
     bias[:, 600:] = float("nan")
     logits = rows["logits"].clone()
     logits[:, 600:] = float("inf")
-    out = launch("bias", logits, rows["wrong"], rows["us"], rows["t"], rows["k"], rows["p"], active=rows["active"], bias=bias,
+    out = launch(logits, rows["wrong"], rows["us"], rows["t"], rows["k"], rows["p"], active=rows["active"], bias=bias,
                  v=600)
     check_against_restatement(rows, out, logits.numpy(), bias, v=600)
     assert bool((out[1][rows["active"].bool()] < 600).all())
@@ -228,11 +201,11 @@ def test_the_bias_is_never_written_back(rows):
     """After a biased call the logits are the unbiased call's, bit for bit; a second draw from them (Q5) reports the
     twice-divided row plus the bias ONCE."""
     bias = rows["bias"]
-    first = launch("bias", *_args(rows), active=rows["active"], bias=bias)
-    free = launch("bias", *_args(rows), active=rows["active"])
+    first = launch(*_args(rows), active=rows["active"], bias=bias)
+    free = launch(*_args(rows), active=rows["active"])
     assert torch.equal(bits(first[0]), bits(free[0]))
     assert not torch.equal(first[1], free[1])                            # (the draws did differ)
-    second = launch("bias", first[0], rows["wrong"], rows["us"], rows["t"], rows["k"], rows["p"], active=rows["active"],
+    second = launch(first[0], rows["wrong"], rows["us"], rows["t"], rows["k"], rows["p"], active=rows["active"],
                     bias=bias)
     check_against_restatement(rows, second, first[0].numpy(), bias)
     hot = (rows["which"] == 4) & rows["active"].bool() & (first[1] >= 0) & (second[1] >= 0)
@@ -262,7 +235,7 @@ def test_edge_rows():
     bias[7, 1:V] = NEG                                                    # row 7: the two smallest ids allowed
     bias[7, 1], bias[7, 2] = 0.0, 0.0
     us = torch.full((8,), 0.5)
-    lg, tok, pr, lp = launch("bias", logits, wrong, us, t, k, p, active=active, bias=bias)
+    lg, tok, pr, lp = launch(logits, wrong, us, t, k, p, active=active, bias=bias)
     for b in (0, 1, 2, 3):
         assert int(tok[b]) == -1 and bool(torch.isnan(lp[b]).all()) and bool(torch.isnan(pr[b]).all()), b
     assert int(tok[4]) == 77 and float(pr[4, 77]) == 1.0 and int((pr[4] > 0).sum()) == 1
@@ -279,7 +252,7 @@ def test_edge_rows():
 # ------------------------------------------------------------------------------------------------ 6. refusals
 def test_sample_topk_refuses_mismatched_bias_tensors():
     from commu_amd import ops
-    from commu_amd._lib import CommuHipError, call
+    from commu_amd._lib import CommuHipError
     lg = torch.zeros(4, V, device=DEV)
     for bad in (torch.zeros(4, 768), torch.zeros(4, 768, device=DEV, dtype=torch.float64),
                 torch.zeros(4, 768, device=DEV, dtype=torch.bfloat16), torch.zeros(3, 768, device=DEV),
@@ -291,10 +264,8 @@ def test_sample_topk_refuses_mismatched_bias_tensors():
     tok = ops.sample_topk(lg, 0.95, 32, bias=torch.zeros(8, 768, device=DEV)[::2])      # rows further apart are fine
     assert tok.shape == (4,)
     # the C entry point refuses a row stride shorter than the ids it reads
-    b = torch.zeros(4, 768, device=DEV)
     with pytest.raises(CommuHipError, match="-22"):
-        call("commu_sample_topk_topp_bias", _p(lg), V, 4, V, None, 0, None, None, 0.95, 32, 1.0, None, None, None, _p(tok),
-             None, 0, None, _p(b), 700, _s())
+        sample_launch(torch.zeros(4, V), None, None, 0.95, 32, 1.0, logp=False, bias=torch.zeros(4, 768), ld_bias=700)
 
 
 # ------------------------------------------------------------------------------------------------ through the loop
