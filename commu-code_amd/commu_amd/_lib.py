@@ -63,7 +63,8 @@ class SampleArgs(C.Structure):
                 ("token", c_p), ("probs_out", c_p), ("logp_out", c_p), ("ldp", c_i),
                 ("bias", c_p), ("gram", c_p), ("gram_on", c_p), ("harm", c_p), ("harm_on", c_p),
                 ("ld_bias", c_i), ("ld_gram", c_i), ("ld_harm", c_i),
-                ("state", c_p), ("seq", c_p), ("chord_tok", c_p), ("ld_seq", c_i), ("ld_chord", c_i)]
+                ("state", c_p), ("seq", c_p), ("chord_tok", c_p), ("ld_seq", c_i), ("ld_chord", c_i),
+                ("cls_ctl", c_p)]
 
 
 class DecodeLoopArgs(C.Structure):
@@ -78,7 +79,8 @@ class DecodeLoopArgs(C.Structure):
                 ("tok", c_p), ("active", c_p), ("keep", c_p), ("draw", c_p), ("uni", c_p), ("trace", c_p), ("ld_trace", c_i),
                 ("klen", c_p), ("lmax", c_i),
                 ("bias", c_p), ("gram", c_p), ("gram_on", c_p), ("harm", c_p), ("harm_on", c_p),
-                ("ld_bias", c_i), ("ld_gram", c_i), ("ld_harm", c_i)]
+                ("ld_bias", c_i), ("ld_gram", c_i), ("ld_harm", c_i),
+                ("cls_ctl", c_p)]
 
 
 def struct_args(cls, **fields):

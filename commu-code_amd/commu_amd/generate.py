@@ -340,6 +340,132 @@ def _harmony_request(harmony):
     return harmony_rows(harmony)
 
 
+# ---- class-keyed sampling: a (temperature, top_k, top_p) triple per token class instead of one per slot.  On the host a
+# table is float64 [8][3] (columns temperature, top_k, top_p) in which NaN means "inherit the slot's base value"; row c is
+# the triple of a draw whose PREVIOUS token has class c (the grammar's key, midi_inferrer.token_class), row 7 is never
+# selected.  On the device a slot's table is 8 records of 16 bytes {float temperature; int top_k; float top_p; int 0}, the
+# inherited entries filled in from the slot's base triple and row 7 holding the base triple (commu_sample_args.cls_ctl).
+CLASS_NAMES = ("other", "bar", "pitch", "velocity", "chord", "duration", "position")
+# what is drawn next UNDER THE DEFAULT EVENT GRAMMAR (event_grammar) -> the classes of the previous token it follows
+DRAWN_AFTER = {"velocity": ("position",), "pitch": ("velocity",), "duration": ("pitch",),
+               "boundary": ("other", "bar", "chord", "duration")}
+CLASS_CTL_DTYPE = np.dtype([("temperature", np.float32), ("top_k", np.int32), ("top_p", np.float32), ("reserved", np.int32)])
+
+
+def _class_entry(entry, what):
+    """One entry of class_sampling() as a row (temperature, top_k, top_p), NaN where the entry does not say."""
+    V = TOKEN_OFFSET.VOCAB_SIZE
+    if not isinstance(entry, dict):
+        raise CommuHipError(f"class_sampling: {what}: a dict with any of temperature, top_k, top_p expected, got {entry!r}")
+    row = np.full(3, np.nan)
+    for key, v in entry.items():
+        if key not in ("temperature", "top_k", "top_p"):
+            raise CommuHipError(f"class_sampling: {what}: unknown control {key!r} (temperature, top_k, top_p)")
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise CommuHipError(f"class_sampling: {what}: {key} is a number, got {v!r}")
+        v = float(v)
+        if key == "temperature" and not (np.isfinite(v) and v >= 0):
+            raise CommuHipError(f"class_sampling: {what}: temperature: a finite value >= 0 expected (0 = greedy), got {v}")
+        if key == "top_k" and not (np.isfinite(v) and v == np.floor(v) and 1 <= v < V):
+            raise CommuHipError(f"class_sampling: {what}: top_k: an integer in [1, {V}) expected, got {v}")
+        if key == "top_p" and not (0 < v <= 1):
+            raise CommuHipError(f"class_sampling: {what}: top_p: a value in (0, 1] expected (1 = off), got {v}")
+        row[("temperature", "top_k", "top_p").index(key)] = v
+    return row
+
+
+def class_sampling(drawn=None, after=None):
+    """A class-control table, float64 [8][3] with NaN for "inherit the slot's base value" (ForcedDecoder.set_class_sampling,
+    generate(class_sampling=)).  after: {class name: {temperature / top_k / top_p: value}} keyed by the class of the
+    PREVIOUS token (CLASS_NAMES) -- what the kernel keys on.  drawn: the same keyed by what is drawn next under the default
+    event grammar (DRAWN_AFTER): velocity (after a position), pitch (after a velocity), duration (after a pitch), boundary
+    (after other, bar, chord, duration: a position, a bar or EOS).  Without the grammar the `drawn` names only say which
+    previous classes are meant.  Raises CommuHipError on an unknown name, a class named through both routes, and values
+    outside temperature >= 0, top_k in [1, 729), top_p in (0, 1]."""
+    table = np.full((N_CLASSES + 1, 3), np.nan)
+    named = {}
+    for route, entries, names in (("after", after, CLASS_NAMES), ("drawn", drawn, tuple(DRAWN_AFTER))):
+        if entries is None:
+            continue
+        if not isinstance(entries, dict):
+            raise CommuHipError(f"class_sampling: {route}: a dict keyed by {', '.join(names)} expected, got {entries!r}")
+        for name, entry in entries.items():
+            if name not in names:
+                raise CommuHipError(f"class_sampling: {route}: unknown name {name!r} (one of {', '.join(names)})")
+            row = _class_entry(entry, f"{route} {name!r}")
+            for cname in ((name,) if route == "after" else DRAWN_AFTER[name]):
+                c = CLASS_NAMES.index(cname)
+                if c in named:
+                    raise CommuHipError(f"class_sampling: class {c} ({cname}) is named twice: through {named[c]} and through "
+                                        f"{route} {name!r}")
+                named[c] = f"{route} {name!r}"
+                table[c] = row
+    return table
+
+
+def class_sampling_table(x):
+    """x as a validated class-control table float64 [8][3] (class_sampling() builds one): 7 or 8 rows of (temperature,
+    top_k, top_p), NaN: inherit.  Row 7 is never selected and comes back as NaN."""
+    V = TOKEN_OFFSET.VOCAB_SIZE
+    try:
+        a = np.array(x, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise CommuHipError(f"class_sampling: a table of 7 or 8 rows of (temperature, top_k, top_p) expected, got "
+                            f"{type(x).__name__}") from None
+    if a.ndim != 2 or a.shape[0] not in (N_CLASSES, N_CLASSES + 1) or a.shape[1] != 3:
+        raise CommuHipError(f"class_sampling: a table of 7 or 8 rows of (temperature, top_k, top_p) expected, got shape "
+                            f"{a.shape}")
+    out = np.full((N_CLASSES + 1, 3), np.nan)
+    out[:N_CLASSES] = a[:N_CLASSES]
+    t, k, p = out[:N_CLASSES].T
+    for c in range(N_CLASSES):
+        if not np.isnan(t[c]) and not (np.isfinite(t[c]) and t[c] >= 0):
+            raise CommuHipError(f"class_sampling: row {c}: temperature: a finite value >= 0 expected, got {t[c]}")
+        if not np.isnan(k[c]) and not (np.isfinite(k[c]) and k[c] == np.floor(k[c]) and 1 <= k[c] < V):
+            raise CommuHipError(f"class_sampling: row {c}: top_k: an integer in [1, {V}) expected, got {k[c]}")
+        if not np.isnan(p[c]) and not (0 < p[c] <= 1):
+            raise CommuHipError(f"class_sampling: row {c}: top_p: a value in (0, 1] expected, got {p[c]}")
+    return out
+
+
+def class_ctl_records(tables, sampling):
+    """The device records of n slots: tables float64 [n][8][3] (NaN: inherit), sampling the slots' base triples as
+    sampling_rows returns them ([n] each).  Returns CLASS_CTL_DTYPE [n][8]: entry (c, i) is the table's where it is not NaN
+    and the slot's base value elsewhere; row 7 is the base triple; reserved 0."""
+    tables = np.asarray(tables, dtype=np.float64)
+    n = tables.shape[0]
+    base = np.stack([np.asarray(s, dtype=np.float64) for s in sampling], axis=1)          # [n][3]
+    full = np.where(np.isnan(tables), base[:, None, :], tables)
+    full[:, N_CLASSES] = base
+    rec = np.zeros((n, N_CLASSES + 1), dtype=CLASS_CTL_DTYPE)
+    rec["temperature"], rec["top_k"], rec["top_p"] = full[..., 0], full[..., 1], full[..., 2]
+    return rec
+
+
+def read_class_sampling(doc):
+    """The CLI's --class_sampling document as (table, uses_drawn_names): {"pitch": {...}, "duration": {...}, ...} names
+    what is DRAWN (DRAWN_AFTER; meaningful under the default grammar only), {"after": {"velocity": {...}, ...}} the class of
+    the previous token; both may stand in one document."""
+    if not isinstance(doc, dict):
+        raise CommuHipError(f"class_sampling: a JSON object expected, got {type(doc).__name__}")
+    after = doc.get("after")
+    drawn = {k: v for k, v in doc.items() if k != "after"}
+    return class_sampling(drawn=drawn or None, after=after), bool(drawn)
+
+
+def _class_request(cs):
+    """A request's class_sampling= as a table or None: None / False, a table (class_sampling_table) or a dict
+    {"drawn": {...}, "after": {...}} (the arguments of class_sampling())."""
+    if cs is None or cs is False:
+        return None
+    if isinstance(cs, dict):
+        extra = set(cs) - {"drawn", "after"}
+        if extra:
+            raise CommuHipError(f"class_sampling: a dict with the keys drawn / after expected, got {sorted(extra)!r}")
+        return class_sampling(drawn=cs.get("drawn"), after=cs.get("after"))
+    return class_sampling_table(cs)
+
+
 class DecodeState:
     """K/V caches + distance-indexed R tables for B sequences of up to Lmax positions.
 
@@ -901,6 +1027,11 @@ class ForcedDecoder:
         self.harm = None
         self.harm_on = None
         self._harm_host = None
+        # class-keyed sampling (set_class_sampling): the slots' control records int32 [B][8][4] (the bit patterns of
+        # CLASS_CTL_DTYPE), allocated by the first table, and the host's NaN-tables float64 [B][8][3] they are composed
+        # from; None: the launches a decoder without class controls always made
+        self.cls_ctl = None
+        self._cls_host = None
         # (the replay of a prompt token takes at most two iterations: the decision to force it, then its append)
         self.ld_trace = 2 * (self.generation_length + 2 + 2 * self.max_prompt) if record_trace else 0
         self.trace = torch.zeros(B, self.ld_trace, dtype=i32, device=dev) if record_trace else None
@@ -929,11 +1060,12 @@ class ForcedDecoder:
             raise CommuHipError(f"rows: slot numbers in [0, {self.B}) expected, got {rows!r}")
         return idx
 
-    def _first_use(self, rows=False, bias=False, gram=False, harm=False):
+    def _first_use(self, rows=False, bias=False, gram=False, harm=False, cls=False):
         """What the first use of a per-slot launch input does, for each one asked for that the decoder does not have yet:
         rows uploads the host mirror of the sampling controls (scalar mode kept the mirror only); bias / gram / harm
-        allocate their zeroed device buffers (gram and harm: the table and the [B] switches).  When anything was missing the
-        captured graphs are dropped, once: they hold the launches without it."""
+        allocate their zeroed device buffers (gram and harm: the table and the [B] switches); cls allocates the slots'
+        class-control records (set_class_sampling fills them).  When anything was missing the captured graphs are dropped,
+        once: they hold the launches without it."""
         new = False
         if rows and not self.rows_on:
             new = self.rows_on = True
@@ -950,6 +1082,10 @@ class ForcedDecoder:
             new = True
             self.harm = torch.zeros(HARM_ROWS, HARM_COLS, dtype=F32, device=self.dev)
             self.harm_on = torch.zeros(self.B, dtype=torch.uint8, device=self.dev)
+        if cls and self.cls_ctl is None:
+            new = True
+            self.cls_ctl = torch.zeros(self.B, N_CLASSES + 1, 4, dtype=torch.int32, device=self.dev)
+            self._cls_host = np.full((self.B, N_CLASSES + 1, 3), np.nan)
         if new:
             self.graph = self.graph_long = None
 
@@ -1005,6 +1141,8 @@ class ForcedDecoder:
                 dst.fill_(cur[i][0].item())
             else:
                 dst.copy_(torch.from_numpy(cur[i]))
+        if self.cls_ctl is not None and any(changed):          # (the inherited entries and row 7 follow the base triple)
+            self._write_class_ctl(rows, idx)
 
     def set_logit_bias(self, bias, rows: Optional[Sequence[int]] = None):
         """Constraint rows (token_constraints) for all slots (rows=None) or the listed ones: None (clear), one row for all
@@ -1085,6 +1223,47 @@ class ForcedDecoder:
     def _harm_args(self):
         return None if self.harm is None else (self.harm, self.harm_on, self.fsm, self.chord_tok)
 
+    def set_class_sampling(self, table=None, rows: Optional[Sequence[int]] = None):
+        """Class-keyed sampling controls for all slots (rows=None) or the listed ones: a table float64 [8][3]
+        (class_sampling(), NaN: inherit) or None (no override).  A slot with a table draws with the triple of record
+        c = token_class(previous token) -- the last token of its seq when the sampling stage runs, the grammar's key; the
+        last prompt token for the first draw of a primed slot -- and every entry the table leaves NaN is the slot's base
+        value (set_sampling, rearm(sampling=)); forced tokens and prompts are not draws.  Under the default event grammar
+        the previous token's class fixes what is drawn next (class_sampling(drawn=)); without it the key is still the
+        previous token's class.  The first table allocates the slots' records -- and what the one kernel reads besides: the
+        array launches (record_logprobs), a zero bias, an all-off grammar and an all-off harmony table -- and drops the
+        captured graphs once; later calls rewrite the records IN PLACE, ordered on the current stream, and a captured graph
+        follows them.  None writes the slot's base triple into all 8 records: bit for bit what the array launches decode
+        without the feature.  set_sampling() and rearm(sampling=) recompose the inherited entries of the slots they touch
+        (the NaN-tables stay on the host).  A decoder that never got a table allocates nothing."""
+        idx = self._slots(rows)
+        new = None if table is None else class_sampling_table(table)          # (validated before anything changes)
+        if self.cls_ctl is None and new is None:
+            return
+        fresh = self.cls_ctl is None
+        self._first_use(rows=True, bias=True, gram=True, harm=True, cls=True)
+        self._cls_host[idx] = np.nan if new is None else new
+        if fresh:          # (the slots not addressed get their base triple in every record)
+            rows, idx = None, np.arange(self.B)
+        self._write_class_ctl(rows, idx)
+
+    def _write_class_ctl(self, rows, idx):
+        """The records of the addressed slots composed from their NaN-tables and base triples, written in place."""
+        rec = class_ctl_records(self._cls_host[idx], [c[idx] for c in self._sampling])
+        words = torch.from_numpy(rec.view(np.int32).reshape(len(idx), N_CLASSES + 1, 4))
+        if rows is None:
+            self.cls_ctl.copy_(words)
+        else:
+            for j, w in zip(idx, words):
+                self.cls_ctl[int(j)].copy_(w)
+
+    def class_samples(self):
+        """Whether a class record of any slot holds a temperature other than 0 (such a draw reads a variate)."""
+        return self._cls_host is not None and bool((np.nan_to_num(self._cls_host[..., 0], nan=0.0) != 0).any())
+
+    def _cls_args(self):
+        return None if self.cls_ctl is None else (self.cls_ctl, self.fsm, self.seq)
+
     def pre(self):
         call("commu_forcing_pre", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_tok), _p(self.chord_pos),
              self.ld_chord, _p(self.wrong), _p(self.utable), self.ld_u, self.generation_length, _p(self.tok),
@@ -1101,7 +1280,8 @@ class ForcedDecoder:
                         wrong=self.wrong, uniforms=self.uni, active=self.draw, token=self.token,
                         probs_out=self.probs if want_probs else None, top_p=self.top_p if p_r is None else p_r,
                         logp_out=logp, bias=self.bias, **({} if self.gram is None else {"grammar": self._gram_args()}),
-                        **({} if self.harm is None else {"harmony": self._harm_args()}))
+                        **({} if self.harm is None else {"harmony": self._harm_args()}),
+                        **({} if self.cls_ctl is None else {"class_ctl": self._cls_args()}))
         call("commu_forcing_post", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_pos), self.ld_chord,
              _p(self.wrong), _p(self.draw), _p(self.token), None, _p(self.state.klen), _p(self.keep),
              self.state.klen_cap, _p(logp), _p(seq_logp), B, _s())
@@ -1124,7 +1304,7 @@ class ForcedDecoder:
             tok=_p(self.tok), active=_p(self.active), keep=_p(self.keep), draw=_p(self.draw), uni=_p(self.uni),
             trace=_p(self.trace), ld_trace=self.ld_trace, klen=_p(st.klen), lmax=st.klen_cap,
             bias=_p(self.bias), ld_bias=ld(self.bias), gram=_p(self.gram), ld_gram=ld(self.gram), gram_on=_p(self.gram_on),
-            harm=_p(self.harm), ld_harm=ld(self.harm), harm_on=_p(self.harm_on))
+            harm=_p(self.harm), ld_harm=ld(self.harm), harm_on=_p(self.harm_on), cls_ctl=_p(self.cls_ctl))
         call("commu_decode_sample_post_pre", C.byref(a), _s())
 
     def iteration(self, want_probs: bool = False):
@@ -1577,19 +1757,22 @@ class BatchedGenerator:
         self._decoders = {}
 
     def decoder(self, B, temperature, top_k, max_chords, top_p=1.0, per_slot: bool = False, max_prompt: int = 0,
-                logit_bias=None, shared: bool = False, grammar=None, harmony=None):
+                logit_bias=None, shared: bool = False, grammar=None, harmony=None, class_sampling=None):
         """The decoder for B slots, its slots set to the given controls (numbers or one value per slot).  per_slot: the
         caller will read log-probabilities or give slots their own controls later (rearm): the array launches from the
         start.  Otherwise one triple for all slots runs the scalar launches, until a second setting arrives for launches
         that are already captured (ForcedDecoder.__init__).  logit_bias: the request's constraint rows (one for all slots
         or one per slot; None clears what an earlier request left on this decoder).  grammar / harmony: the request's event
-        grammar and harmony table (None switches off what an earlier request left).  shared: the decoder that holds the
+        grammar and harmony table (None switches off what an earlier request left).  class_sampling: the request's
+        class-control table (None resets every slot to its base triple where an earlier request left one; a decoder that
+        never had a table allocates nothing).  shared: the decoder that holds the
         request's common prompt once (its own cache layout: kept beside the unshared decoder of the same size)."""
         rows = sampling_rows(B, temperature, top_k, top_p)          # (validated before anything is built)
         if logit_bias is not None:
             logit_bias = logit_bias_rows(logit_bias, B)
         gram_table, gram_rows = _grammar_request(grammar, B)
         harm_table = _harmony_request(harmony)
+        cls_table = _class_request(class_sampling)
         key = (B, self.trace is not None, self.sliding) + (("shared",) if shared else ())
         dec = self._decoders.get(key)
         if dec is None or dec.ld_chord < max_chords or dec.max_prompt < max_prompt:
@@ -1610,6 +1793,8 @@ class BatchedGenerator:
             dec.set_grammar(gram_table, rows=None if len(gram_rows) == B else gram_rows)
         # (harmony: likewise; None on a decoder that never had a table allocates nothing)
         dec.set_harmony(harm_table)
+        # (class-keyed controls: likewise, after set_sampling -- the inherited entries are the slots' base triples)
+        dec.set_class_sampling(cls_table)
         return dec
 
     @staticmethod
@@ -1622,8 +1807,10 @@ class BatchedGenerator:
     @torch.no_grad()
     def generate(self, encoded_metas: Sequence[Sequence[int]], input_datas, temperature, top_k, top_p=1.0,
                  return_logprobs: bool = False, prompts: Optional[Sequence[Sequence[int]]] = None, logit_bias=None,
-                 grammar=None, harmony=None):
-        """temperature / top_k / top_p: a number for the batch or one value per sequence.  harmony: None, True (the strict
+                 grammar=None, harmony=None, class_sampling=None):
+        """temperature / top_k / top_p: a number for the batch or one value per sequence.  class_sampling: None, a table
+        (class_sampling()) or its arguments as a dict {"drawn": ..., "after": ...}, one setting for the request -- a triple
+        per token class that replaces the sequence's own where the table says so (ForcedDecoder.set_class_sampling).  harmony: None, True (the strict
         default table: only chord tones) or a table (harmony_rows), one setting for the request -- every pitch a sequence
         DRAWS is weighed by the chord it is in (ForcedDecoder.set_harmony).  grammar: None, True (the default
         event grammar), a table (grammar_table) or one bool per sequence -- every token such a sequence DRAWS continues a
@@ -1641,9 +1828,9 @@ class BatchedGenerator:
         # (shared_prompt: requests with a prompt only -- without one there is nothing but the short context to share)
         dec = self.decoder(B, temperature, top_k, max_chords, top_p, per_slot=return_logprobs, max_prompt=max_prompt,
                            logit_bias=logit_bias, shared=self.shared_prompt and max_prompt > 0, grammar=grammar,
-                           harmony=self._one_harmony(harmony))
+                           harmony=self._one_harmony(harmony), class_sampling=class_sampling)
         uniforms = None
-        if bool((dec._sampling[0] != 0).any()):
+        if bool((dec._sampling[0] != 0).any()) or dec.class_samples():
             srcs = self.uniform_sources or [np.random.RandomState(1000 + b).random_sample for b in range(B)]
             uniforms = np.array([[float(srcs[b]()) for _ in range(dec.ld_u)] for b in range(B)], dtype=np.float32)
         dec.load(encoded_metas, input_datas, uniforms, prompts=prompts)
@@ -1665,7 +1852,7 @@ class BatchedGenerator:
     def generate_stream(self, encoded_meta: Sequence[int], input_data, temperature, top_k, need: int,
                         accept, top_p=1.0, slots: int = 64, seed: int = 0, max_attempts: Optional[int] = None,
                         return_logprobs: bool = False, prompt: Optional[Sequence[int]] = None, logit_bias=None,
-                        share_prompt: bool = False, grammar=None, harmony=None):
+                        share_prompt: bool = False, grammar=None, harmony=None, class_sampling=None):
         """Attempts of ONE request (the reference's `while idx != num_generate` loop, midi_inferrer.py:338-354, which tries
         one sequence after the other) decoded in up to `slots` parallel slots, CONTINUOUSLY: a slot whose sequence has
         ended is handed to `accept(sequence, report) -> bool` and re-armed with the next attempt while the other slots keep
@@ -1681,6 +1868,8 @@ class BatchedGenerator:
         logit_bias: one constraint row (token_constraints) for every attempt of the request.
         grammar: None, True (the default event grammar) or a table (grammar_table): one setting for the request.
         harmony: None, True (harmony_table(), strict) or a table (harmony_rows): one setting for the request.
+        class_sampling: None, a table (class_sampling()) or {"drawn": ..., "after": ...}: one setting for the request; the
+        entries it leaves open inherit the ATTEMPT's own triple (a re-armed slot recomposes them).
         share_prompt (opt-in; also on with BatchedGenerator(shared_prompt=True) when a prompt is given): the K/V of the
         context and the prompt are computed and held once for all slots (ForcedDecoder(shared_prompt=True)); the attempts
         returned are the ones the unshared decoder defines, up to the summation order of the attention."""
@@ -1706,9 +1895,10 @@ class BatchedGenerator:
         varying = any(bool((c != c[0]).any()) for c in sched)          # (one triple for every attempt: nothing to re-arm)
         dec = self.decoder(B, [t[0] for t in first], [t[1] for t in first], max_chords, [t[2] for t in first],
                            per_slot=return_logprobs or varying, max_prompt=0 if prompt is None else len(prompt),
-                           logit_bias=logit_bias, shared=share, grammar=grammar, harmony=harmony)
+                           logit_bias=logit_bias, shared=share, grammar=grammar, harmony=harmony,
+                           class_sampling=class_sampling)
         started = B
-        sampled = bool((sched[0] != 0).any())          # (a greedy attempt reads no variate)
+        sampled = bool((sched[0] != 0).any()) or dec.class_samples()          # (a greedy attempt reads no variate)
         uni = np.stack([self.attempt_uniforms(seed, a, dec.ld_u) for a in range(B)]) if sampled else None
         dec.load([list(encoded_meta)] * B, [input_data] * B, uni,
                  prompts=None if prompt is None else [list(prompt)] * B)

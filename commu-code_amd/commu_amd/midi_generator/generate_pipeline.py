@@ -38,12 +38,14 @@ class TokenGenerationPipeline:
         self.rejected = []          # (reason, sequence) of every attempt that did not pass: "sampling" | "forcing" | "no_note"
 
     def execute(self, input_args: dict, max_rounds: Optional[int] = None, uniform_seed: int = 0,
-                prompt: Optional[List[int]] = None, logit_bias=None, harmony=None) -> List[List[int]]:
+                prompt: Optional[List[int]] = None, logit_bias=None, harmony=None,
+                class_sampling=None) -> List[List[int]]:
         """input_args: the reference's input dictionary (generate.py:17-44).  Runs rounds of parallel decoding until
         `num_generate` sequences passed both validators (the reference retries one sequence at a time forever;
         `max_rounds` bounds it).  prompt: token ids that follow the meta tokens; every attempt continues them.
         logit_bias: a constraint row (generate.token_constraints) on what every attempt may draw.
-        harmony: True (only chord tones) or a table (generate.harmony_rows): drawn pitches follow the sounding chord."""
+        harmony: True (only chord tones) or a table (generate.harmony_rows): drawn pitches follow the sounding chord.
+        class_sampling: a table (generate.class_sampling) or its arguments as a dict: a sampling triple per token class."""
         self.model.eval()
         self.model.same_length = True                                   # model_initializer.py:49-50
         self.model.reset_length(1, self.memory_length)
@@ -72,5 +74,6 @@ class TokenGenerationPipeline:
                                      max_attempts=None if max_rounds is None else max_rounds * data.num_generate,
                                      prompt=None if not prompt else list(prompt), logit_bias=logit_bias,
                                      **({} if self.decode_slots == 64 else {"slots": self.decode_slots}),
-                                     **({} if harmony is None else {"harmony": harmony}))
+                                     **({} if harmony is None else {"harmony": harmony}),
+                                     **({} if class_sampling is None else {"class_sampling": class_sampling}))
         return out

@@ -149,7 +149,8 @@ class InferenceTask:
         return count_notes(seq) > 0
 
     def execute(self, encoded_meta, max_rounds: Optional[int] = None, return_logprobs: bool = False,
-                prompt: Optional[List[int]] = None, logit_bias=None, grammar=None, harmony=None):           # :338-354
+                prompt: Optional[List[int]] = None, logit_bias=None, grammar=None, harmony=None,
+                class_sampling=None):                                                                      # :338-354
         """return_logprobs (not in the reference): (sequences, their log-probability arrays -- ForcedDecoder.logprobs).
         prompt (not in the reference): token ids that follow the meta tokens; every attempt continues them (primed
         generation, BatchedGenerator.generate_stream) and every returned sequence starts with [0] + meta + prompt.
@@ -157,7 +158,9 @@ class InferenceTask:
         grammar (not in the reference): True or a table (generate.grammar_table) -- every drawn token continues a group the
         token-to-MIDI step keeps (generate.event_grammar, BatchedGenerator.generate_stream).
         harmony (not in the reference): True (only chord tones) or a table (generate.harmony_rows) -- every drawn pitch is
-        weighed by the chord that is sounding (generate.harmony_table, ForcedDecoder.set_harmony)."""
+        weighed by the chord that is sounding (generate.harmony_table, ForcedDecoder.set_harmony).
+        class_sampling (not in the reference): a table (generate.class_sampling) or its arguments as a dict -- a
+        temperature / top_k / top_p per token class (ForcedDecoder.set_class_sampling)."""
         from ..generate import BatchedGenerator
         data = self.input_data
         glen = self.inference_cfg.GENERATION.generation_length
@@ -173,6 +176,12 @@ class InferenceTask:
         # (likewise: generate.py --grammar; an argument given here wins)
         if grammar is None and bool(getattr(self.inference_cfg.GENERATION, "grammar", False)):
             grammar = True
+        # (likewise: generate.py --class_sampling, the JSON text of its document; an argument given here wins)
+        if class_sampling is None and getattr(self.inference_cfg.GENERATION, "class_sampling", None):
+            import json
+
+            from ..generate import read_class_sampling
+            class_sampling = read_class_sampling(json.loads(self.inference_cfg.GENERATION.class_sampling))[0]
         gen = BatchedGenerator(self.model, self.device, glen, mlen, sliding=sliding, kv_dtype=kv_dtype,
                                **({"shared_prompt": True} if share else {}))
 
@@ -193,5 +202,6 @@ class InferenceTask:
                                   return_logprobs=return_logprobs, prompt=None if not prompt else list(prompt),
                                   logit_bias=logit_bias, **({} if slots == 64 else {"slots": slots}),
                                   **({} if grammar is None else {"grammar": grammar}),
-                                  **({} if harmony is None else {"harmony": harmony}))
+                                  **({} if harmony is None else {"harmony": harmony}),
+                                  **({} if class_sampling is None else {"class_sampling": class_sampling}))
         return (res[0], res[2]) if return_logprobs else res[0]

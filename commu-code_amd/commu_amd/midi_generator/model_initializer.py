@@ -54,6 +54,10 @@ class ModelInitializeTask:
         # generate.py --grammar (not in the reference): the default event grammar on every draw
         if getattr(self.model_args, "grammar", False):
             cfg.GENERATION.grammar = True
+        # generate.py --class_sampling (not in the reference): sampling controls per token class, the JSON text of the
+        # document (generate.read_class_sampling)
+        if getattr(self.model_args, "class_sampling", None):
+            cfg.GENERATION.class_sampling = str(self.model_args.class_sampling)
         # generate.py --decode_slots (not in the reference): attempts decoded side by side (64 unless the key is set)
         if getattr(self.model_args, "decode_slots", None) not in (None, 64):
             cfg.GENERATION.decode_slots = int(self.model_args.decode_slots)

@@ -20,13 +20,15 @@ def logprobs_to_lists(logprobs):
 
 
 def generate_on_device(model_args, in_args, device_index, num_generate, uniform_seed, max_rounds, training_cfg=None,
-                       logprobs=False, prompt=None, logit_bias=None, harmony=None):
+                       logprobs=False, prompt=None, logit_bias=None, harmony=None, class_sampling=None):
     """One replica: checkpoint -> model on cuda:<device_index>, `num_generate` validated sequences (logprobs: and their
     log-probabilities as logprobs_to_lists gives them, a third value).  prompt: token ids every sequence continues.
     logit_bias: a constraint row (generate.token_constraints, a numpy array) on what every sequence may draw.
     harmony: a harmony table (generate.harmony_rows, a numpy array) -- drawn pitches are weighed by the sounding chord.
+    class_sampling: a class-control table (generate.class_sampling, a numpy array); the command line's --class_sampling
+    travels in model_args instead.
     model_args carries the decode options of every replica (--parity, --sliding_memory, --kv_cache, --share_prompt,
-    --decode_slots, ...): they reach
+    --decode_slots, --class_sampling, ...): they reach
     the generator through the inference configuration that ModelInitializeTask builds."""
     import copy
 
@@ -47,18 +49,18 @@ def generate_on_device(model_args, in_args, device_index, num_generate, uniform_
     task(model=model, input_data=pre.input_data, inference_cfg=init.inference_cfg)
     if logprobs:
         seqs, lps = task.execute(encoded_meta, max_rounds=max_rounds, return_logprobs=True, prompt=prompt,
-                                 logit_bias=logit_bias, harmony=harmony)
+                                 logit_bias=logit_bias, harmony=harmony, class_sampling=class_sampling)
         return encoded_meta, seqs, logprobs_to_lists(lps)
     return encoded_meta, task.execute(encoded_meta, max_rounds=max_rounds, prompt=prompt, logit_bias=logit_bias,
-                                      harmony=harmony)
+                                      harmony=harmony, class_sampling=class_sampling)
 
 
 def replica_worker(rank, device_index, model_args, in_args, share, max_rounds, training_cfg, q, logprobs=False,
-                   prompt=None, logit_bias=None, harmony=None):
+                   prompt=None, logit_bias=None, harmony=None, class_sampling=None):
     try:
         # distinct variates per replica: 1_000_003 apart (a replica's rounds / sequences use seed + 7919 r + b)
         q.put((rank, generate_on_device(model_args, in_args, device_index, share, 1_000_003 * rank, max_rounds,
-                                        training_cfg, logprobs, prompt, logit_bias, harmony)))
+                                        training_cfg, logprobs, prompt, logit_bias, harmony, class_sampling)))
     except Exception:
         import traceback
         q.put((rank, traceback.format_exc()))

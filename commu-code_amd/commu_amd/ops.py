@@ -933,7 +933,7 @@ def _check_draw_state(kind, device, specs):
 
 
 def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=None, token=None, probs_out=None,
-                top_p=1.0, logp_out=None, bias=None, V=729, grammar=None, harmony=None):
+                top_p=1.0, logp_out=None, bias=None, V=729, grammar=None, harmony=None, class_ctl=None):
     """In-place temperature + softmax + top-k + wrong-token mask + inverse-CDF draw per sequence.
     logits: fp32 [nseq, >=V] (row stride = ld), modified in place (logits[:, 1:V] /= temperature).
     top_p < 1: nucleus filter after the top-k / rejected-token step (an extra mode; the reference has top-k only).
@@ -958,7 +958,12 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
     For the pitch ids 3 .. 130 table[r][(id - 3) mod 12] is added after the grammar row, r = chord_tok[b][state[b][F_CUR] - 1]
     - 195 (109 while F_CUR is 0, 110 for a sequence that is off); no other id is touched and nothing is written back.  One
     kernel serves it, with a bias and a grammar: where the call has none, a zero bias and an all-off grammar are made
-    here (x + 0 and the zero row 7 change no bit) (commu_sample_args.harm)."""
+    here (x + 0 and the zero row 7 change no bit) (commu_sample_args.harm).
+    class_ctl: (records, state, seq) on the device of the logits -- records int32 [nseq, 8, 4], the bit patterns of
+    {float temperature; int top_k; float top_p; int 0} per class (generate.class_ctl_records), state and seq as the grammar's.
+    Sequence b draws with the triple of record token_class(seq[b][state[b][0] - 1]); temperature / top_k / top_p given
+    here are not looked at.  One kernel serves it, the harmony kernel's with the records: where the call has no bias,
+    grammar or harmony, a zero bias and all-off tables are made here (commu_sample_args.cls_ctl)."""
     nseq = logits.shape[0]
     V = int(V)
     assert logits.dtype == F32 and logits.stride(1) == 1
@@ -988,7 +993,26 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
         temperature=0.0 if t_s is None else float(t_s), top_k=1 if k_s is None else int(k_s),
         top_p=1.0 if p_s is None else float(p_s), temperature_rows=_p(t_r), top_k_rows=_p(k_r), top_p_rows=_p(p_r),
         token=_p(token), probs_out=_p(probs_out), ldp=0 if probs_out is None else probs_out.stride(0), logp_out=_p(logp_out))
-    nrec = call("commu_forcing_state_ints") if grammar is not None or harmony is not None else 0
+    nrec = call("commu_forcing_state_ints") if grammar is not None or harmony is not None or class_ctl is not None else 0
+    if class_ctl is not None:
+        ctl, cstate, cseq = class_ctl
+        _check_draw_state("class_ctl", logits.device, (
+            (ctl, "records", torch.int32, "[%d, 8, 4]" % nseq, lambda t: tuple(t.shape) == (nseq, 8, 4)),
+            (cstate, "state", torch.int32, "[%d, %d]" % (nseq, nrec), lambda t: tuple(t.shape) == (nseq, nrec)),
+            (cseq, "seq", torch.int32, "[%d, ld_seq]" % nseq,
+             lambda t: t.dim() == 2 and t.shape[0] == nseq and t.shape[1] >= 1)))
+        for other, what in ((grammar, "grammar"), (harmony, "harmony")):
+            if other is not None and (not isinstance(other[2], torch.Tensor) or other[2].data_ptr() != cstate.data_ptr()):
+                raise CommuHipError(f"class_ctl state: the records the {what} reads expected (one state per sequence)")
+        # (as for harmony below: the stand-alone sampler's convenience; ForcedDecoder passes its own buffers)
+        if grammar is None:
+            grammar = (torch.zeros(8, V, dtype=F32, device=logits.device),
+                       torch.zeros(nseq, dtype=torch.uint8, device=logits.device), cstate, cseq)
+        if harmony is None:
+            harmony = (torch.zeros(111, 16, dtype=F32, device=logits.device),
+                       torch.zeros(nseq, dtype=torch.uint8, device=logits.device), cstate,
+                       torch.zeros(nseq, 1, dtype=torch.int32, device=logits.device))
+        a.cls_ctl = _p(ctl)
     if harmony is not None:
         htable, hon, hstate, chord_tok = harmony
         _check_draw_state("harmony", logits.device, (

@@ -130,7 +130,29 @@ struct Harmony {
     int on;                 // the sequence's switch
 };
 constexpr int TOK_PITCH_LO = 3, TOK_PITCH_HI = 130, HARM_NO_CHORD = 109, HARM_OFF = 110;
-template <bool BIAS, bool GRAM = false, bool HARM = false>
+// CLS (ClassControls: records {float temperature; int top_k; float top_p; int reserved} [8] per sequence, 16 bytes each,
+//   one sequence's table one 128-byte line): the sampling triple of a draw is chosen by the class of the sequence's
+//   PREVIOUS token -- the grammar's key, the same load with the same clamp, but NOT gated by the grammar's switch: record
+//   c = token_class(prev) of the sequence's table, so rows 0 .. 6 are selected and row 7 never is (the host keeps the slot's
+//   base triple there).  With CLS the triple comes from that record ONLY: neither the scalars nor `rows` are looked at (their
+//   loads are not issued).  Everything after the selection is the code below as it stands -- the clamp of top_k, greedy for
+//   temperature == 0, the in-place division by the SELECTED temperature (a Q5 re-draw sees the same previous token, selects
+//   the same record and compounds by the same temperature) -- so a draw with record (t, k, p) is bit for bit the draw of
+//   the array-mode kernel for a sequence whose rows hold (t, k, p).
+//   PLACEMENT: ONE load of record c, issued when the class is known.  Its address is wave-uniform, so it is a scalar
+//   load (s_load_dwordx4) that lands in scalar registers and never enters the vector queue; it goes out right behind the
+//   grammar row's 12 vector loads, which the first arithmetic waits for anyway, so the extra dependent step of the chain
+//   record -> previous token -> class -> control record travels under them.  The other placement -- the slot's whole
+//   128-byte table loaded UP FRONT beside the logits (lane l takes record l & 7 as one 16-byte vector load) and the record
+//   picked with v_readlane at the scalar index c, so that no load depends on the class -- was built and measured: 0.07 us
+//   SLOWER on the kernel alone (8.38 against 8.31 .. 8.32 us; its vector load queues behind the logits and bias loads and
+//   the pick waits for it), no difference per iteration (docs/EXPERIMENTS.md 8u).  The three values are wave-uniform and
+//   held in scalar registers, so the greedy / radix / nucleus branches stay scalar branches, as with SamplingRows.
+//   CLS needs GRAM (the previous token is the grammar's load); callers without a grammar pass the all-off switch array.
+struct ClassControls {
+    const int4* table;      // the sequence's 8 records
+};
+template <bool BIAS, bool GRAM = false, bool HARM = false, bool CLS = false>
 __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restrict__ logits, int ld, int V,
                                                  const unsigned char* __restrict__ wrong, int ldw,
                                                  const float* __restrict__ uni,
@@ -140,15 +162,21 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
                                                  float* __restrict__ logp_out, TokenLogp& lp,
                                                  const float* __restrict__ bias = nullptr, int ld_bias = 0,
                                                  Grammar g = Grammar{nullptr, 0, nullptr, 0, 0, 0},
-                                                 Harmony h = Harmony{nullptr, 0, nullptr, 0, 0, 0}) {
+                                                 Harmony h = Harmony{nullptr, 0, nullptr, 0, 0, 0},
+                                                 ClassControls cc = ClassControls{nullptr}) {
+    static_assert(!CLS || GRAM, "the class key is the grammar's previous token");
     float* lg = logits + (size_t)b * ld;
     // The optional per-sequence inputs -- the active flag and this sequence's controls -- are loaded unconditionally: a null
     // array reads a valid word of this sequence instead (token[b], logits[b][0]), which is then ignored.  So they are in
     // flight together with the loads below; behind a branch per array each was a memory round trip of its own.
     const unsigned char act_row = *(active != nullptr ? active + b : reinterpret_cast<const unsigned char*>(token + b));
-    const float t_row = *(rows.temperature != nullptr ? rows.temperature + b : lg);
-    const int k_row = *(rows.top_k != nullptr ? rows.top_k + b : token + b);
-    const float p_row = *(rows.top_p != nullptr ? rows.top_p + b : lg);
+    float t_row = 0.f, p_row = 0.f;
+    int k_row = 0;
+    if constexpr (!CLS) {         // (CLS: the triple is the class record's, loaded below; none of these loads is issued)
+        t_row = *(rows.temperature != nullptr ? rows.temperature + b : lg);
+        k_row = *(rows.top_k != nullptr ? rows.top_k + b : token + b);
+        p_row = *(rows.top_p != nullptr ? rows.top_p + b : lg);
+    }
     float p[PER_LANE];
     const int base = lane * PER_LANE;
     // every load of the step up front and unconditional (clamped index): one memory round trip, not one per element
@@ -193,10 +221,19 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
     }
     const float u = uni != nullptr ? uni[b] : 0.5f;
     // one value per wave, kept in scalar registers so that the mode branches below stay scalar branches
-    if (rows.temperature != nullptr)
-        temperature = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, t_row)));
-    if (rows.top_k != nullptr) top_k = __builtin_amdgcn_readfirstlane(k_row);
-    if (rows.top_p != nullptr) top_p = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p_row)));
+    if constexpr (CLS) {
+        // the record of the previous token's class (0 <= c <= 6: row 7 is never picked): a uniform address, one scalar load
+        const int c = __builtin_amdgcn_readfirstlane(token_class(prev));
+        const int4 crec = cc.table[c];
+        temperature = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(crec.x));
+        top_k = __builtin_amdgcn_readfirstlane(crec.y);
+        top_p = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(crec.z));
+    } else {
+        if (rows.temperature != nullptr)
+            temperature = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, t_row)));
+        if (rows.top_k != nullptr) top_k = __builtin_amdgcn_readfirstlane(k_row);
+        if (rows.top_p != nullptr) top_p = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p_row)));
+    }
     // the radix select below needs 1 <= top_k <= V (exactly one lane owns the threshold bin); the host validates the
     // values, the clamp keeps the kernel in bounds whatever an array holds
     top_k = min(max(top_k, 1), V);

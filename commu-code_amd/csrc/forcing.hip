@@ -75,14 +75,20 @@ struct LoopStageArgsHarm : LoopStageArgsGram {
     const float* harm; int ld_harm;
     const unsigned char* harm_on;
 };
-template <bool GRAM, bool HARM = false>
+// (CLS) the class-control records [B][8] (decode_loop.h: ClassControls): an argument of the class kernel only
+struct LoopStageArgsCls : LoopStageArgsHarm {
+    const int4* cls_ctl;
+};
+template <bool GRAM, bool HARM = false, bool CLS = false>
 struct LoopArgsOf { using type = LoopStageArgs; };
 template <>
-struct LoopArgsOf<true, false> { using type = LoopStageArgsGram; };
+struct LoopArgsOf<true, false, false> { using type = LoopStageArgsGram; };
 template <>
-struct LoopArgsOf<true, true> { using type = LoopStageArgsHarm; };
-template <bool BIAS, bool GRAM, bool HARM = false>
-__global__ __launch_bounds__(64) void sample_post_pre_kernel(typename LoopArgsOf<GRAM, HARM>::type a) {
+struct LoopArgsOf<true, true, false> { using type = LoopStageArgsHarm; };
+template <>
+struct LoopArgsOf<true, true, true> { using type = LoopStageArgsCls; };
+template <bool BIAS, bool GRAM, bool HARM = false, bool CLS = false>
+__global__ __launch_bounds__(64) void sample_post_pre_kernel(typename LoopArgsOf<GRAM, HARM, CLS>::type a) {
     const int b = blockIdx.x, lane = threadIdx.x;
     if (a.trace != nullptr && lane == 0) a.trace[b * 4 + 0] = wall_clock64();
     int rec[F_COUNT];                                  // the record travels through the three stages in lane 0's registers;
@@ -108,10 +114,12 @@ __global__ __launch_bounds__(64) void sample_post_pre_kernel(typename LoopArgsOf
         h = Harmony{a.harm, a.ld_harm, a.chord_tok + (size_t)b * a.ld_chord, rec[F_CUR], a.ld_chord,
                     a.harm_on != nullptr ? (int)on_b : 1};
     }
-    const int drawn = sample_topk_body<BIAS, GRAM, HARM>(b, lane, a.logits, a.ld, a.V, a.wrong, VOCAB, a.uni, a.draw,
-                                                         a.temperature, a.top_k, a.token, a.probs_out, a.ldp, a.top_p,
-                                                         a.rows, a.logp != nullptr || a.seq_logp != nullptr, a.logp, lp,
-                                                         a.bias, a.ld_bias, g, h);
+    ClassControls cc{nullptr};
+    if constexpr (CLS) cc = ClassControls{a.cls_ctl + (size_t)b * 8};      // (the body loads the record it selects)
+    const int drawn = sample_topk_body<BIAS, GRAM, HARM, CLS>(b, lane, a.logits, a.ld, a.V, a.wrong, VOCAB, a.uni, a.draw,
+                                                              a.temperature, a.top_k, a.token, a.probs_out, a.ldp, a.top_p,
+                                                              a.rows, a.logp != nullptr || a.seq_logp != nullptr, a.logp,
+                                                              lp, a.bias, a.ld_bias, g, h, cc);
     __syncthreads();
     if (a.trace != nullptr && lane == 0) a.trace[b * 4 + 1] = wall_clock64();
     forcing_post_body(b, lane, rec, a.seq, a.ld_seq, a.chord_pos, a.ld_chord, a.wrong, a.draw, a.token, nullptr, a.klen,
@@ -283,7 +291,9 @@ extern "C" int commu_decode_sample_post_pre(const commu_decode_loop_args* p, hip
     const int V = p->V;
     if (V != VOCAB || V > 64 * PER_LANE || p->ld_seq < 2 || p->ld_chord < 1 || p->ld_u < 1) return -22;
     // (a scalar that an array replaces is not looked at; the kernel clamps what the arrays hold)
-    if ((p->top_k_rows == nullptr && (p->top_k < 1 || p->top_k > V)) || (p->top_p_rows == nullptr && !(p->top_p > 0.f)))
+    // (with cls_ctl neither the scalars nor the arrays are looked at)
+    if (p->cls_ctl == nullptr &&
+        ((p->top_k_rows == nullptr && (p->top_k < 1 || p->top_k > V)) || (p->top_p_rows == nullptr && !(p->top_p > 0.f))))
         return -22;
     if (p->bias != nullptr && p->ld_bias < V) return -22;    // (the kernel reads bias[b][0 .. V-1])
     // (the kernel reads gram[0 .. 7][0 .. V-1] and finds the previous token through the record)
@@ -292,7 +302,12 @@ extern "C" int commu_decode_sample_post_pre(const commu_decode_loop_args* p, hip
     // instantiation: the caller passes a zero bias and an all-off grammar where it has none)
     if (p->harm != nullptr && (p->ld_harm < 12 || p->chord_tok == nullptr || p->bias == nullptr || p->gram == nullptr))
         return -22;
-    LoopStageArgsHarm a;
+    // (the kernel reads cls_ctl[b][0 .. 7] as 16-byte records; one instantiation, the harmony kernel's with the table)
+    if (p->cls_ctl != nullptr && (p->state == nullptr || p->seq == nullptr || p->bias == nullptr || p->gram == nullptr ||
+                                  p->harm == nullptr || p->chord_tok == nullptr ||
+                                  (reinterpret_cast<uintptr_t>(p->cls_ctl) & 15u) != 0))
+        return -22;
+    LoopStageArgsCls a;
     static_cast<LoopStageArgs&>(a) = LoopStageArgs{
         p->logits, p->ld, V, p->wrong, p->temperature, p->top_k, p->top_p,
         SamplingRows{p->temperature_rows, p->top_k_rows, p->top_p_rows}, p->token, p->probs_out, p->ldp, p->logp, p->seq_logp,
@@ -300,13 +315,17 @@ extern "C" int commu_decode_sample_post_pre(const commu_decode_loop_args* p, hip
         p->active, p->keep, p->draw, p->uni, p->trace, p->ld_trace, p->klen, p->lmax, g_loop_trace, p->bias, p->ld_bias};
     a.gram = p->gram; a.ld_gram = p->ld_gram; a.gram_on = p->gram_on;
     a.harm = p->harm; a.ld_harm = p->ld_harm; a.harm_on = p->harm_on;
+    a.cls_ctl = static_cast<const int4*>(p->cls_ctl);
+    const LoopStageArgsHarm& ah = a;
     const LoopStageArgsGram& ag = a;          // (each kernel gets the argument block of its own kind, by value)
     const LoopStageArgs& a0 = a;
     const dim3 grid(p->B), block(64);
     // five kernels: without a bias / a grammar / a harmony table the launch is the one it always was (no added load, no
-    // added register, no added argument)
-    if (p->harm != nullptr) {
-        COMMU_LAUNCH((sample_post_pre_kernel<true, true, true>), grid, block, 0, stream, a);
+    // added register, no added argument); a sixth for the class-keyed controls
+    if (p->cls_ctl != nullptr) {
+        COMMU_LAUNCH((sample_post_pre_kernel<true, true, true, true>), grid, block, 0, stream, a);
+    } else if (p->harm != nullptr) {
+        COMMU_LAUNCH((sample_post_pre_kernel<true, true, true>), grid, block, 0, stream, ah);
     } else if (p->gram != nullptr) {
         if (p->bias != nullptr) COMMU_LAUNCH((sample_post_pre_kernel<true, true>), grid, block, 0, stream, ag);
         else COMMU_LAUNCH((sample_post_pre_kernel<false, true>), grid, block, 0, stream, ag);

@@ -11,7 +11,8 @@
 // top-k: sample_topk_body<BIAS>); a table of such rows, picked by the class of the sequence's previous token, makes an event
 // grammar (<GRAM>, kernels of their own); a table of pitch-class rows, picked by the last chord the forcing rules placed, keeps
 // the drawn pitches in the sounding chord (<HARM>, one more kernel); without any of them the launch is the kernel that never
-// heard of them.
+// heard of them.  A table of control records per sequence, picked by the same class, gives each token family its own
+// temperature / top_k / top_p (<CLS>, a sixth kernel: the harmony kernel with the table).
 #include "decode_loop.h"
 #include "commu_hip.h"
 
@@ -89,6 +90,39 @@ __global__ __launch_bounds__(64) void sample_topk_harm_kernel(float* __restrict_
                                        probs_out, ldp, top_p, rows, logp_out != nullptr, logp_out, lp, bias, ld_bias, g, h);
 }
 
+// the same with class-keyed sampling controls (ClassControls): the harmony kernel's arguments plus the table of records,
+// once more a kernel of its own -- the triple of a draw is record token_class(previous token) of the sequence's table, the
+// scalars and the *_rows arrays are not looked at (they stay in the argument block so that the launch helper is shared)
+__global__ __launch_bounds__(64) void sample_topk_cls_kernel(float* __restrict__ logits, int ld, int V,
+                                                             const unsigned char* __restrict__ wrong, int ldw,
+                                                             const float* __restrict__ uni,
+                                                             const unsigned char* __restrict__ active,
+                                                             float temperature, int top_k,
+                                                             int* __restrict__ token, float* __restrict__ probs_out,
+                                                             int ldp, float top_p, SamplingRows rows,
+                                                             float* __restrict__ logp_out,
+                                                             const float* __restrict__ bias, int ld_bias,
+                                                             const float* __restrict__ gram, int ld_gram,
+                                                             const unsigned char* __restrict__ gram_on,
+                                                             const int* __restrict__ state, const int* __restrict__ seq,
+                                                             int ld_seq, const float* __restrict__ harm, int ld_harm,
+                                                             const unsigned char* __restrict__ harm_on,
+                                                             const int* __restrict__ chord_tok, int ld_chord,
+                                                             const int4* __restrict__ cls_ctl) {
+    TokenLogp lp;
+    const int b = blockIdx.x;
+    const unsigned char gon_b = *(gram_on != nullptr ? gram_on + b : reinterpret_cast<const unsigned char*>(token + b));
+    const unsigned char hon_b = *(harm_on != nullptr ? harm_on + b : reinterpret_cast<const unsigned char*>(token + b));
+    const Grammar g{gram, ld_gram, seq + (size_t)b * ld_seq, state[(size_t)b * F_COUNT + F_LEN], ld_seq,
+                    gram_on != nullptr ? (int)gon_b : 1};
+    const Harmony h{harm, ld_harm, chord_tok + (size_t)b * ld_chord, state[(size_t)b * F_COUNT + F_CUR], ld_chord,
+                    harm_on != nullptr ? (int)hon_b : 1};
+    const ClassControls cc{cls_ctl + (size_t)b * 8};
+    sample_topk_body<true, true, true, true>(b, threadIdx.x, logits, ld, V, wrong, ldw, uni, active, temperature, top_k,
+                                             token, probs_out, ldp, top_p, rows, logp_out != nullptr, logp_out, lp, bias,
+                                             ld_bias, g, h, cc);
+}
+
 }  // namespace
 
 extern "C" int commu_sample_args_bytes(void) { return (int)sizeof(commu_sample_args); }
@@ -99,8 +133,10 @@ extern "C" int commu_sample_topk(const commu_sample_args* a, hipStream_t stream)
     if (a->nseq <= 0) return 0;
     const int V = a->V;
     // (a scalar that an array replaces is not looked at; the kernel clamps what the arrays hold)
-    if (V > 64 * PER_LANE || V < 2 || (a->top_k_rows == nullptr && (a->top_k < 1 || a->top_k > V)) ||
-        (a->top_p_rows == nullptr && !(a->top_p > 0.f)))
+    // (with cls_ctl neither the scalars nor the arrays are looked at)
+    if (V > 64 * PER_LANE || V < 2 ||
+        (a->cls_ctl == nullptr && ((a->top_k_rows == nullptr && (a->top_k < 1 || a->top_k > V)) ||
+                                   (a->top_p_rows == nullptr && !(a->top_p > 0.f)))))
         return -22;
     if (a->bias != nullptr && a->ld_bias < V) return -22;    // (the kernel reads bias[b][0 .. V-1])
     // (the kernel reads gram[0 .. 7][0 .. V-1] and finds the previous token through the record)
@@ -109,6 +145,12 @@ extern "C" int commu_sample_topk(const commu_sample_args* a, hipStream_t stream)
     // instantiation: the caller passes a zero bias and an all-off grammar where it has none)
     if (a->harm != nullptr && (a->ld_harm < 12 || a->chord_tok == nullptr || a->ld_chord < 1 || a->bias == nullptr ||
                                a->gram == nullptr))
+        return -22;
+    // (the kernel reads cls_ctl[b][0 .. 7] as 16-byte records and finds the previous token through the record, as the
+    // grammar does; one instantiation: it is the harmony kernel's caller that passes the zero bias and the all-off tables)
+    if (a->cls_ctl != nullptr && (a->state == nullptr || a->seq == nullptr || a->bias == nullptr || a->gram == nullptr ||
+                                  a->harm == nullptr || a->chord_tok == nullptr || a->ld_seq < 1 ||
+                                  (reinterpret_cast<uintptr_t>(a->cls_ctl) & 15u) != 0))
         return -22;
     const SamplingRows rows{a->temperature_rows, a->top_k_rows, a->top_p_rows};
     const dim3 grid(a->nseq), block(64);
@@ -119,8 +161,11 @@ extern "C" int commu_sample_topk(const commu_sample_args* a, hipStream_t stream)
                      more...);
     };
     // five kernels: without a bias / a grammar / a harmony table the launch is the one it always was (no added load, no
-    // added register, no added argument)
-    if (a->harm != nullptr) {
+    // added register, no added argument); a sixth for the class-keyed controls
+    if (a->cls_ctl != nullptr) {
+        launch(sample_topk_cls_kernel, a->bias, a->ld_bias, a->gram, a->ld_gram, a->gram_on, a->state, a->seq, a->ld_seq,
+               a->harm, a->ld_harm, a->harm_on, a->chord_tok, a->ld_chord, static_cast<const int4*>(a->cls_ctl));
+    } else if (a->harm != nullptr) {
         launch(sample_topk_harm_kernel, a->bias, a->ld_bias, a->gram, a->ld_gram, a->gram_on, a->state, a->seq, a->ld_seq,
                a->harm, a->ld_harm, a->harm_on, a->chord_tok, a->ld_chord);
     } else if (a->gram != nullptr) {

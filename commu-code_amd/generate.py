@@ -63,6 +63,16 @@ def parse_args():
                                        "soft: by --harmony_penalty, or a JSON table of 110 rows of 12 numbers, null = banned)")
     model_arg_parser.add_argument("--harmony_penalty", type=float, default=4.0,
                                   help="what --harmony soft subtracts from the pitches outside the chord (default: %(default)s)")
+    # not in the reference (one temperature / top_k for every token of a request): a sampling triple per token family.
+    # {"pitch": {"temperature": 1.1, "top_k": 40}, "duration": {"temperature": 0}} names what is DRAWN -- velocity, pitch,
+    # duration, boundary (a position, a bar or EOS) -- which the default event grammar fixes from the previous token, so
+    # these names need --grammar; {"after": {"velocity": {...}}} names the class of the PREVIOUS token (other, bar, pitch,
+    # velocity, chord, duration, position: what the kernel keys on) and needs no grammar.  Controls a family does not
+    # name stay --temperature / --top_k / --top_p.  Forced tokens and --prompt_tokens are not affected.
+    model_arg_parser.add_argument("--class_sampling", type=str, default=None, metavar="JSON_OR_FILE",
+                                  help="sampling controls per token family: {\"pitch\": {\"temperature\": 1.1, \"top_k\": 40}, "
+                                       "\"duration\": {\"temperature\": 0}} (drawn names velocity, pitch, duration, boundary "
+                                       "need --grammar; {\"after\": {...}} is keyed by the previous token's class)")
     # not in the reference (which decodes one sequence at a time): how many attempts are decoded side by side.  1 .. 256;
     # up to 256 slots run the fused layer-tail launches ("Supported shapes").  The sequences returned do
     # not depend on it.  (checked by check_decode_slots: the range is named in its message)
@@ -193,6 +203,34 @@ def read_harmony(setting=None, penalty=4.0):
     return harmony_rows([[float("-inf") if v is None else float(v) for v in r] for r in doc])
 
 
+def read_class_sampling_arg(setting=None, grammar=False):
+    """--class_sampling as the JSON text of its validated document (None when the flag is not given): the value is the
+    document itself or the path of a file that holds it.  Host code only; raises (commu_amd.generate.CommuHipError,
+    ValueError) on an unreadable value, a malformed document, and on `drawn` names without --grammar."""
+    if setting is None:
+        return None
+    from commu_amd.generate import read_class_sampling
+    text = setting
+    if not setting.lstrip().startswith("{"):
+        try:
+            with open(setting) as f:
+                text = f.read()
+        except OSError as e:
+            raise ValueError(f"--class_sampling: a JSON object or a readable JSON file expected, got {setting!r} "
+                             f"({e.strerror})") from None
+    try:
+        doc = json.loads(text)
+    except json.JSONDecodeError as e:
+        raise ValueError(f"--class_sampling: not JSON ({e})") from None
+    _, uses_drawn = read_class_sampling(doc)
+    if uses_drawn and not grammar:
+        names = sorted(k for k in doc if k != "after")
+        raise ValueError(f"--class_sampling: {', '.join(names)} name what is drawn next, which only --grammar fixes from the "
+                         "previous token; give --grammar, or key the controls by the previous token's class with "
+                         "{\"after\": {...}}")
+    return json.dumps(doc)
+
+
 from commu_amd.midi_generator.replicas import generate_on_device, replica_worker, split_num_generate  # noqa: E402
 
 
@@ -215,6 +253,10 @@ def main(model_args, input_args, training_cfg=None, device_indices=None):
     logit_bias = read_constraints(in_args.pop("logit_bias", None), in_args.pop("pitch_min", None),
                                   in_args.pop("pitch_max", None))
     harmony = read_harmony(getattr(model_args, "harmony", None), getattr(model_args, "harmony_penalty", 4.0))      # (likewise)
+    # (likewise; the checked document travels to the replicas in model_args, ModelInitializeTask puts it into the
+    # inference configuration)
+    if getattr(model_args, "class_sampling", None) is not None:
+        model_args.class_sampling = read_class_sampling_arg(model_args.class_sampling, bool(getattr(model_args, "grammar", False)))
     if device_indices is None:
         n_vis = torch.cuda.device_count()
         device_indices = list(range(max(1, n_vis if gpus is None else min(gpus, n_vis))))

@@ -466,6 +466,21 @@ int commu_transpose_heads(const void* src, int ld, const float* bias, void* dst,
  *     chord_tok[b][state[b][F_CUR] - 1] (none while F_CUR is 0).  ONE kernel serves it, with a bias and a grammar: harm
  *     requires bias, gram, seq, state and chord_tok (ld_chord >= 1), else -22; a caller that has no bias or grammar
  *     passes a zero bias row and gram_on zeros (x + 0 is x and row 7 is zeros: bit for bit the draw without them).
+ * CLASS-KEYED CONTROLS (the reference samples every token of a request with one temperature / top_k)
+ *   cls_ctl: [nseq][8] records of 16 bytes, {float temperature; int top_k; float top_p; int reserved (0)}: sequence b's
+ *     table is one 128-byte line.  A draw of sequence b takes its triple from record cls_ctl[b][c], c the class (the
+ *     grammar's classes above, 0 .. 6) of the sequence's PREVIOUS token seq[b][min(max(F_LEN, 1), ld_seq) - 1] -- the
+ *     grammar's load with the grammar's clamp, whatever gram_on[b] says.  Record 7 is never selected; the host keeps the
+ *     sequence's base triple there.  With cls_ctl the triple comes from that record ONLY: temperature / top_k / top_p and
+ *     the three *_rows arrays are not looked at.  Everything after the selection is the step above: top_k clamped to
+ *     [1, V], temperature == 0 is greedy, the in-place division uses the selected temperature (a Q5 re-draw sees the same
+ *     previous token and compounds by the same temperature), then bias, grammar, harmony, top-k, wrong, top-p.  A draw
+ *     with record (t, k, p) is BIT FOR BIT the draw of the call with temperature_rows / top_k_rows / top_p_rows holding
+ *     (t, k, p) for that sequence: token, probs_out, the logits written back and the logp_out pair.  ONE kernel serves it,
+ *     the harmony kernel with the table: cls_ctl requires state, seq (ld_seq >= 1), bias, gram, harm and chord_tok (pass
+ *     the zero bias and all-off switch arrays where there is none) and a 16-byte aligned pointer, else -22.  Validating
+ *     the records is the caller's job (generate.class_sampling).  The same field, with the same meaning and the same
+ *     refusals, ends commu_decode_loop_args.
  * WHAT gram / harm READ
  *   state: the forcing records, int32 [nseq][commu_forcing_state_ints()]; seq int32 [nseq][ld_seq]; chord_tok int32
  *   [nseq][ld_chord].  Not looked at, and may be null, in a call without gram and harm.
@@ -505,6 +520,8 @@ typedef struct commu_sample_args {
     const int* seq;
     const int* chord_tok;
     int ld_seq, ld_chord;
+    /* class-keyed controls */
+    const void* cls_ctl;
 } commu_sample_args;
 int commu_sample_args_bytes(void);
 int commu_sample_topk(const commu_sample_args* a, hipStream_t stream);
@@ -722,6 +739,8 @@ typedef struct commu_decode_loop_args {
     const float* harm;
     const unsigned char* harm_on;
     int ld_bias, ld_gram, ld_harm;
+    /* class-keyed controls (commu_sample_args.cls_ctl) */
+    const void* cls_ctl;
 } commu_decode_loop_args;
 int commu_decode_loop_args_bytes(void);
 int commu_decode_sample_post_pre(const commu_decode_loop_args* a, hipStream_t stream);
