@@ -201,8 +201,8 @@ def event_grammar():
     """The default table, entries 0 or -inf: after OTHER, BAR, CHORD or DURATION a draw is a position, BAR or EOS (a group
     boundary); after a POSITION a velocity; after a VELOCITY a pitch; after a PITCH a duration.  Chord tokens are never
     drawn (the forcing rules place them).  With it every drawn token continues a group the reference's token-to-MIDI
-    step keeps (midi_inferrer.parse_events).  Not enforced: positions increasing inside a bar, duplicate notes, and the
-    contents of a prompt."""
+    step keeps (midi_inferrer.parse_events).  Not enforced by the grammar: positions increasing inside a bar and duplicate
+    notes (ForcedDecoder.set_note_order does that), and the contents of a prompt."""
     T = TOKEN_OFFSET
     g = np.full((8, VPAD), -np.inf, dtype=np.float32)
     g[7] = 0.0
@@ -464,6 +464,45 @@ def _class_request(cs):
             raise CommuHipError(f"class_sampling: a dict with the keys drawn / after expected, got {sorted(extra)!r}")
         return class_sampling(drawn=cs.get("drawn"), after=cs.get("after"))
     return class_sampling_table(cs)
+
+
+# ---- note order: one int32 control word per slot (commu_sample_args.order_ctl).  A slot that is on cannot draw a position
+# token before the position it is at, a pitch its current position already holds, or -- with a cap n -- the position itself
+# once it holds n notes.  The state is read off the slot's seq when the sampling stage runs; nothing else is kept.
+NOTE_ORDER_OFF = -1
+NOTE_ORDER_MAX = 128          # (a position cannot hold more notes than there are pitches)
+
+
+def note_order_ctl(x, B: int):
+    """A request's note_order= as the int32 control words of B slots: None / False (off, -1), True (on, 0), an integer
+    n in 1 .. 128 (on, at most n notes per position; 0 and -1 as the words themselves), or one such value per slot.
+    Pure host code; raises CommuHipError on anything else, with the numbers."""
+    B = int(B)
+
+    def word(v, where):
+        if v is None or v is False or (isinstance(v, np.bool_) and not v):
+            return NOTE_ORDER_OFF
+        if v is True or isinstance(v, np.bool_):
+            return 0
+        ok = isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v) and v == np.floor(v) \
+            and -1 <= v <= NOTE_ORDER_MAX
+        if not ok:
+            raise CommuHipError(f"note_order{where}: None / False (off), True (on) or an integer in [1, {NOTE_ORDER_MAX}] "
+                                f"(notes per position; -1 = off, 0 = no cap) expected, got {v!r}")
+        return int(v)
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    if x is None or np.ndim(x) == 0:
+        if isinstance(x, np.ndarray):
+            x = x.item()
+        return np.full(B, word(x, ""), dtype=np.int32)
+    x = list(x)
+    if len(x) != B:
+        raise CommuHipError(f"note_order: {B} values expected (one per sequence), got {len(x)}")
+    if any(np.ndim(v) != 0 for v in x):
+        raise CommuHipError(f"note_order: one value per sequence expected, got shape {np.shape(x)}")
+    return np.array([word(v.item() if isinstance(v, np.generic) and not isinstance(v, np.bool_) else v, f"[{b}]")
+                     for b, v in enumerate(x)], dtype=np.int32)
 
 
 class DecodeState:
@@ -1032,6 +1071,10 @@ class ForcedDecoder:
         # from; None: the launches a decoder without class controls always made
         self.cls_ctl = None
         self._cls_host = None
+        # note order (set_note_order): the slots' control words int32 [B], allocated by the first call that switches a
+        # slot on, and their host mirror; None: the launches a decoder without the feature always made
+        self.order_ctl = None
+        self._order_host = None
         # (the replay of a prompt token takes at most two iterations: the decision to force it, then its append)
         self.ld_trace = 2 * (self.generation_length + 2 + 2 * self.max_prompt) if record_trace else 0
         self.trace = torch.zeros(B, self.ld_trace, dtype=i32, device=dev) if record_trace else None
@@ -1060,11 +1103,12 @@ class ForcedDecoder:
             raise CommuHipError(f"rows: slot numbers in [0, {self.B}) expected, got {rows!r}")
         return idx
 
-    def _first_use(self, rows=False, bias=False, gram=False, harm=False, cls=False):
+    def _first_use(self, rows=False, bias=False, gram=False, harm=False, cls=False, order=False):
         """What the first use of a per-slot launch input does, for each one asked for that the decoder does not have yet:
         rows uploads the host mirror of the sampling controls (scalar mode kept the mirror only); bias / gram / harm
         allocate their zeroed device buffers (gram and harm: the table and the [B] switches); cls allocates the slots'
-        class-control records (set_class_sampling fills them).  When anything was missing the captured graphs are dropped,
+        class-control records (set_class_sampling fills them); order allocates the slots' note-order words, all off.
+        When anything was missing the captured graphs are dropped,
         once: they hold the launches without it."""
         new = False
         if rows and not self.rows_on:
@@ -1086,6 +1130,10 @@ class ForcedDecoder:
             new = True
             self.cls_ctl = torch.zeros(self.B, N_CLASSES + 1, 4, dtype=torch.int32, device=self.dev)
             self._cls_host = np.full((self.B, N_CLASSES + 1, 3), np.nan)
+        if order and self.order_ctl is None:
+            new = True
+            self.order_ctl = torch.full((self.B,), NOTE_ORDER_OFF, dtype=torch.int32, device=self.dev)
+            self._order_host = np.full(self.B, NOTE_ORDER_OFF, dtype=np.int32)
         if new:
             self.graph = self.graph_long = None
 
@@ -1264,6 +1312,38 @@ class ForcedDecoder:
     def _cls_args(self):
         return None if self.cls_ctl is None else (self.cls_ctl, self.fsm, self.seq)
 
+    def set_note_order(self, value=True, rows: Optional[Sequence[int]] = None):
+        """The note-order constraint for all slots (rows=None) or the listed ones: True (on), an integer n in 1 .. 128 (on,
+        at most n notes per position), None / False (off), or one such value per addressed slot (note_order_ctl).  A slot
+        that is on cannot DRAW a position token before the position its bar is at, a pitch that position already holds,
+        or -- with a cap -- the position itself once it holds n notes: inside a bar the drawn positions never go back and
+        no note is doubled; n = 1 gives one note per onset.  The state is read off the slot's seq when the sampling stage
+        runs (the prompt of a primed slot included), so a re-draw and a re-armed slot need nothing else.  Only DRAWS are
+        constrained: forced tokens are placed by the rules and a prompt is not checked.  The first call that switches a
+        slot on allocates the [B] control words -- and what the one kernel reads besides: the array launches, a zero bias,
+        an all-off grammar, an all-off harmony table and the class records holding every slot's base triple -- and drops
+        the captured graphs once; later calls rewrite the words IN PLACE, ordered on the current stream, and a captured
+        graph follows them.  A slot that is off bans nothing: it decodes bit for bit what it decoded without the feature.
+        A decoder that never switched a slot on allocates nothing.  Not enforced: overlapping durations (a cap of 1 is one
+        note per onset, not strict monophony); a bias, pitch range or strict harmony that leaves fewer pitches than notes
+        asked for at one position ends the slot by Q12."""
+        idx = self._slots(rows)
+        new = note_order_ctl(value, len(idx))                  # (validated before anything changes)
+        if self.order_ctl is None and not bool((new != NOTE_ORDER_OFF).any()):
+            return
+        fresh_cls = self.cls_ctl is None
+        self._first_use(rows=True, bias=True, gram=True, harm=True, cls=True, order=True)
+        if fresh_cls:          # (no class controls: every record of every slot holds the slot's base triple)
+            self._write_class_ctl(None, np.arange(self.B))
+        if np.array_equal(self._order_host[idx], new):
+            return
+        self._order_host[idx] = new
+        if rows is None and len(idx) > 4:
+            self.order_ctl.copy_(torch.from_numpy(self._order_host))
+        else:
+            for j in idx:
+                self.order_ctl[int(j)].fill_(int(self._order_host[j]))
+
     def pre(self):
         call("commu_forcing_pre", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_tok), _p(self.chord_pos),
              self.ld_chord, _p(self.wrong), _p(self.utable), self.ld_u, self.generation_length, _p(self.tok),
@@ -1281,7 +1361,8 @@ class ForcedDecoder:
                         probs_out=self.probs if want_probs else None, top_p=self.top_p if p_r is None else p_r,
                         logp_out=logp, bias=self.bias, **({} if self.gram is None else {"grammar": self._gram_args()}),
                         **({} if self.harm is None else {"harmony": self._harm_args()}),
-                        **({} if self.cls_ctl is None else {"class_ctl": self._cls_args()}))
+                        **({} if self.cls_ctl is None else {"class_ctl": self._cls_args()}),
+                        **({} if self.order_ctl is None else {"note_order": self.order_ctl}))
         call("commu_forcing_post", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_pos), self.ld_chord,
              _p(self.wrong), _p(self.draw), _p(self.token), None, _p(self.state.klen), _p(self.keep),
              self.state.klen_cap, _p(logp), _p(seq_logp), B, _s())
@@ -1304,7 +1385,8 @@ class ForcedDecoder:
             tok=_p(self.tok), active=_p(self.active), keep=_p(self.keep), draw=_p(self.draw), uni=_p(self.uni),
             trace=_p(self.trace), ld_trace=self.ld_trace, klen=_p(st.klen), lmax=st.klen_cap,
             bias=_p(self.bias), ld_bias=ld(self.bias), gram=_p(self.gram), ld_gram=ld(self.gram), gram_on=_p(self.gram_on),
-            harm=_p(self.harm), ld_harm=ld(self.harm), harm_on=_p(self.harm_on), cls_ctl=_p(self.cls_ctl))
+            harm=_p(self.harm), ld_harm=ld(self.harm), harm_on=_p(self.harm_on), cls_ctl=_p(self.cls_ctl),
+            order_ctl=_p(self.order_ctl))
         call("commu_decode_sample_post_pre", C.byref(a), _s())
 
     def iteration(self, want_probs: bool = False):
@@ -1562,8 +1644,11 @@ class ForcedDecoder:
     # logit_bias: a constraint row for the slot's next attempt (None: the slot keeps its row; set_logit_bias clears one).
     # grammar: True / False switches the slot's event grammar for its next attempt (None: the slot keeps its switch).
     # harmony: True / False switches the slot's harmony constraint for its next attempt (None: the slot keeps its switch).
+    # note_order: the slot's note-order control for its next attempt (set_note_order's values; None: the slot keeps its word).
     def rearm(self, b: int, uniforms_row: Optional[np.ndarray] = None, sampling=None, logit_bias=None, grammar=None,
-              harmony=None):
+              harmony=None, note_order=None):
+        if note_order is not None:
+            self.set_note_order(note_order, rows=[b])
         if sampling is not None:
             self.set_sampling(*sampling, rows=[b])
         if logit_bias is not None:
@@ -1757,7 +1842,8 @@ class BatchedGenerator:
         self._decoders = {}
 
     def decoder(self, B, temperature, top_k, max_chords, top_p=1.0, per_slot: bool = False, max_prompt: int = 0,
-                logit_bias=None, shared: bool = False, grammar=None, harmony=None, class_sampling=None):
+                logit_bias=None, shared: bool = False, grammar=None, harmony=None, class_sampling=None,
+                note_order=None):
         """The decoder for B slots, its slots set to the given controls (numbers or one value per slot).  per_slot: the
         caller will read log-probabilities or give slots their own controls later (rearm): the array launches from the
         start.  Otherwise one triple for all slots runs the scalar launches, until a second setting arrives for launches
@@ -1765,7 +1851,8 @@ class BatchedGenerator:
         or one per slot; None clears what an earlier request left on this decoder).  grammar / harmony: the request's event
         grammar and harmony table (None switches off what an earlier request left).  class_sampling: the request's
         class-control table (None resets every slot to its base triple where an earlier request left one; a decoder that
-        never had a table allocates nothing).  shared: the decoder that holds the
+        never had a table allocates nothing).  note_order: the request's note-order controls (note_order_ctl; None
+        switches off what an earlier request left, and allocates nothing on a decoder that never had one).  shared: the decoder that holds the
         request's common prompt once (its own cache layout: kept beside the unshared decoder of the same size)."""
         rows = sampling_rows(B, temperature, top_k, top_p)          # (validated before anything is built)
         if logit_bias is not None:
@@ -1773,6 +1860,7 @@ class BatchedGenerator:
         gram_table, gram_rows = _grammar_request(grammar, B)
         harm_table = _harmony_request(harmony)
         cls_table = _class_request(class_sampling)
+        order = note_order_ctl(note_order, B)
         key = (B, self.trace is not None, self.sliding) + (("shared",) if shared else ())
         dec = self._decoders.get(key)
         if dec is None or dec.ld_chord < max_chords or dec.max_prompt < max_prompt:
@@ -1795,6 +1883,8 @@ class BatchedGenerator:
         dec.set_harmony(harm_table)
         # (class-keyed controls: likewise, after set_sampling -- the inherited entries are the slots' base triples)
         dec.set_class_sampling(cls_table)
+        # (note order: likewise; its first use fills the class records with the base triples set above)
+        dec.set_note_order(order)
         return dec
 
     @staticmethod
@@ -1807,8 +1897,11 @@ class BatchedGenerator:
     @torch.no_grad()
     def generate(self, encoded_metas: Sequence[Sequence[int]], input_datas, temperature, top_k, top_p=1.0,
                  return_logprobs: bool = False, prompts: Optional[Sequence[Sequence[int]]] = None, logit_bias=None,
-                 grammar=None, harmony=None, class_sampling=None):
-        """temperature / top_k / top_p: a number for the batch or one value per sequence.  class_sampling: None, a table
+                 grammar=None, harmony=None, class_sampling=None, note_order=None):
+        """temperature / top_k / top_p: a number for the batch or one value per sequence.  note_order: None / False, True,
+        an integer cap in 1 .. 128 or one such value per sequence -- inside a bar the positions such a sequence DRAWS never
+        go back, no pitch is drawn twice at one position and, with a cap, a position gets at most that many notes
+        (ForcedDecoder.set_note_order).  class_sampling: None, a table
         (class_sampling()) or its arguments as a dict {"drawn": ..., "after": ...}, one setting for the request -- a triple
         per token class that replaces the sequence's own where the table says so (ForcedDecoder.set_class_sampling).  harmony: None, True (the strict
         default table: only chord tones) or a table (harmony_rows), one setting for the request -- every pitch a sequence
@@ -1828,7 +1921,7 @@ class BatchedGenerator:
         # (shared_prompt: requests with a prompt only -- without one there is nothing but the short context to share)
         dec = self.decoder(B, temperature, top_k, max_chords, top_p, per_slot=return_logprobs, max_prompt=max_prompt,
                            logit_bias=logit_bias, shared=self.shared_prompt and max_prompt > 0, grammar=grammar,
-                           harmony=self._one_harmony(harmony), class_sampling=class_sampling)
+                           harmony=self._one_harmony(harmony), class_sampling=class_sampling, note_order=note_order)
         uniforms = None
         if bool((dec._sampling[0] != 0).any()) or dec.class_samples():
             srcs = self.uniform_sources or [np.random.RandomState(1000 + b).random_sample for b in range(B)]
@@ -1852,7 +1945,7 @@ class BatchedGenerator:
     def generate_stream(self, encoded_meta: Sequence[int], input_data, temperature, top_k, need: int,
                         accept, top_p=1.0, slots: int = 64, seed: int = 0, max_attempts: Optional[int] = None,
                         return_logprobs: bool = False, prompt: Optional[Sequence[int]] = None, logit_bias=None,
-                        share_prompt: bool = False, grammar=None, harmony=None, class_sampling=None):
+                        share_prompt: bool = False, grammar=None, harmony=None, class_sampling=None, note_order=None):
         """Attempts of ONE request (the reference's `while idx != num_generate` loop, midi_inferrer.py:338-354, which tries
         one sequence after the other) decoded in up to `slots` parallel slots, CONTINUOUSLY: a slot whose sequence has
         ended is handed to `accept(sequence, report) -> bool` and re-armed with the next attempt while the other slots keep
@@ -1870,6 +1963,8 @@ class BatchedGenerator:
         harmony: None, True (harmony_table(), strict) or a table (harmony_rows): one setting for the request.
         class_sampling: None, a table (class_sampling()) or {"drawn": ..., "after": ...}: one setting for the request; the
         entries it leaves open inherit the ATTEMPT's own triple (a re-armed slot recomposes them).
+        note_order: None / False, True or an integer cap in 1 .. 128: one setting for every attempt of the request
+        (ForcedDecoder.set_note_order; the bans are read off a slot's seq, so a re-armed slot needs nothing).
         share_prompt (opt-in; also on with BatchedGenerator(shared_prompt=True) when a prompt is given): the K/V of the
         context and the prompt are computed and held once for all slots (ForcedDecoder(shared_prompt=True)); the attempts
         returned are the ones the unshared decoder defines, up to the summation order of the attention."""
@@ -1883,6 +1978,8 @@ class BatchedGenerator:
             raise CommuHipError(f"grammar: one setting for the request expected (True or a table), got shape "
                                 f"{np.shape(grammar)}")
         harmony = self._one_harmony(harmony)
+        if note_order is not None and np.ndim(note_order) != 0:
+            raise CommuHipError(f"note_order: one setting for the request expected, got shape {np.shape(note_order)}")
         max_chords = len(input_data.chord_token_components["chord_token"])
         # each control's schedule, validated on its own (the three may have different lengths)
         n_of = lambda x: 1 if np.ndim(x) == 0 else len(x)
@@ -1896,7 +1993,7 @@ class BatchedGenerator:
         dec = self.decoder(B, [t[0] for t in first], [t[1] for t in first], max_chords, [t[2] for t in first],
                            per_slot=return_logprobs or varying, max_prompt=0 if prompt is None else len(prompt),
                            logit_bias=logit_bias, shared=share, grammar=grammar, harmony=harmony,
-                           class_sampling=class_sampling)
+                           class_sampling=class_sampling, note_order=note_order)
         started = B
         sampled = bool((sched[0] != 0).any()) or dec.class_samples()          # (a greedy attempt reads no variate)
         uni = np.stack([self.attempt_uniforms(seed, a, dec.ld_u) for a in range(B)]) if sampled else None

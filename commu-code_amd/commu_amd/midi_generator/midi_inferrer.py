@@ -112,6 +112,35 @@ def parse_events(seq: List[int], start: int) -> Optional[int]:
     return None
 
 
+def note_order_bans(seq: List[int], max_notes: int = 0) -> set:
+    """The ids the note-order constraint (ForcedDecoder.set_note_order, csrc/decode_loop.h: NoteOrder) bans for the token
+    that follows seq.  With j the last BAR or POSITION token of seq: nothing when there is none or it is BAR; else, p that
+    position and the run everything since the last BAR or other position before j: the positions before p, the pitches in
+    the run and -- max_notes >= 1 -- p itself once the run holds max_notes pitches."""
+    pos_lo, pos_hi = TOKEN_OFFSET.POSITION, TOKEN_OFFSET.BPM
+    is_breaker = lambda t: t == TOKEN_OFFSET.BAR or pos_lo <= t < pos_hi
+    j = next((i for i in range(len(seq) - 1, -1, -1) if is_breaker(int(seq[i]))), None)
+    if j is None or int(seq[j]) == TOKEN_OFFSET.BAR:
+        return set()
+    p = int(seq[j])
+    s = next((i + 1 for i in range(j - 1, -1, -1) if is_breaker(int(seq[i])) and int(seq[i]) != p), 0)
+    pitches = [int(t) for t in seq[s:] if TOKEN_OFFSET.PITCH <= int(t) < TOKEN_OFFSET.NOTE_VELOCITY]
+    banned = set(range(pos_lo, p)) | set(pitches)
+    if max_notes >= 1 and len(pitches) >= max_notes:
+        banned.add(p)
+    return banned
+
+
+def note_order_violation(seq: List[int], start: int, max_notes: int = 0) -> Optional[int]:
+    """The index of the first token seq[i], i >= start, that the note-order constraint would have banned given seq[:i]
+    (note_order_bans): a position that steps back inside its bar, a pitch doubled at one position, or -- max_notes >= 1 --
+    a position repeated once it holds max_notes notes.  None when there is none."""
+    for i in range(max(int(start), 0), len(seq)):
+        if int(seq[i]) in note_order_bans(seq[:i], max_notes):
+            return i
+    return None
+
+
 class ForcingReport:
     """What the forcing state machine was asked to place in one sequence and how far it got."""
 
@@ -150,7 +179,7 @@ class InferenceTask:
 
     def execute(self, encoded_meta, max_rounds: Optional[int] = None, return_logprobs: bool = False,
                 prompt: Optional[List[int]] = None, logit_bias=None, grammar=None, harmony=None,
-                class_sampling=None):                                                                      # :338-354
+                class_sampling=None, note_order=None):                                                     # :338-354
         """return_logprobs (not in the reference): (sequences, their log-probability arrays -- ForcedDecoder.logprobs).
         prompt (not in the reference): token ids that follow the meta tokens; every attempt continues them (primed
         generation, BatchedGenerator.generate_stream) and every returned sequence starts with [0] + meta + prompt.
@@ -160,7 +189,9 @@ class InferenceTask:
         harmony (not in the reference): True (only chord tones) or a table (generate.harmony_rows) -- every drawn pitch is
         weighed by the chord that is sounding (generate.harmony_table, ForcedDecoder.set_harmony).
         class_sampling (not in the reference): a table (generate.class_sampling) or its arguments as a dict -- a
-        temperature / top_k / top_p per token class (ForcedDecoder.set_class_sampling)."""
+        temperature / top_k / top_p per token class (ForcedDecoder.set_class_sampling).
+        note_order (not in the reference): True or a cap of 1 .. 128 notes per position -- inside a bar the drawn
+        positions never go back and no pitch is drawn twice at one position (ForcedDecoder.set_note_order)."""
         from ..generate import BatchedGenerator
         data = self.input_data
         glen = self.inference_cfg.GENERATION.generation_length
@@ -182,6 +213,9 @@ class InferenceTask:
 
             from ..generate import read_class_sampling
             class_sampling = read_class_sampling(json.loads(self.inference_cfg.GENERATION.class_sampling))[0]
+        # (likewise: generate.py --note_order / --max_notes, the control word; an argument given here wins)
+        if note_order is None and getattr(self.inference_cfg.GENERATION, "note_order", None) is not None:
+            note_order = int(self.inference_cfg.GENERATION.note_order)
         gen = BatchedGenerator(self.model, self.device, glen, mlen, sliding=sliding, kv_dtype=kv_dtype,
                                **({"shared_prompt": True} if share else {}))
 
@@ -203,5 +237,6 @@ class InferenceTask:
                                   logit_bias=logit_bias, **({} if slots == 64 else {"slots": slots}),
                                   **({} if grammar is None else {"grammar": grammar}),
                                   **({} if harmony is None else {"harmony": harmony}),
-                                  **({} if class_sampling is None else {"class_sampling": class_sampling}))
+                                  **({} if class_sampling is None else {"class_sampling": class_sampling}),
+                                  **({} if note_order is None else {"note_order": note_order}))
         return (res[0], res[2]) if return_logprobs else res[0]

@@ -58,6 +58,15 @@ class ModelInitializeTask:
         # document (generate.read_class_sampling)
         if getattr(self.model_args, "class_sampling", None):
             cfg.GENERATION.class_sampling = str(self.model_args.class_sampling)
+        # generate.py --note_order / --max_notes (not in the reference): the note-order control word, 0 = on, N = on with
+        # at most N notes per position (generate.py check_note_order)
+        word = getattr(self.model_args, "note_order_word", None)
+        if word is None and getattr(self.model_args, "max_notes", None) is not None:      # (a caller that skipped the check)
+            word = int(self.model_args.max_notes)
+        elif word is None and getattr(self.model_args, "note_order", False):
+            word = 0
+        if word is not None:
+            cfg.GENERATION.note_order = int(word)
         # generate.py --decode_slots (not in the reference): attempts decoded side by side (64 unless the key is set)
         if getattr(self.model_args, "decode_slots", None) not in (None, 64):
             cfg.GENERATION.decode_slots = int(self.model_args.decode_slots)

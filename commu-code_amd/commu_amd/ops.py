@@ -933,7 +933,8 @@ def _check_draw_state(kind, device, specs):
 
 
 def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=None, token=None, probs_out=None,
-                top_p=1.0, logp_out=None, bias=None, V=729, grammar=None, harmony=None, class_ctl=None):
+                top_p=1.0, logp_out=None, bias=None, V=729, grammar=None, harmony=None, class_ctl=None,
+                note_order=None):
     """In-place temperature + softmax + top-k + wrong-token mask + inverse-CDF draw per sequence.
     logits: fp32 [nseq, >=V] (row stride = ld), modified in place (logits[:, 1:V] /= temperature).
     top_p < 1: nucleus filter after the top-k / rejected-token step (an extra mode; the reference has top-k only).
@@ -963,7 +964,13 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
     {float temperature; int top_k; float top_p; int 0} per class (generate.class_ctl_records), state and seq as the grammar's.
     Sequence b draws with the triple of record token_class(seq[b][state[b][0] - 1]); temperature / top_k / top_p given
     here are not looked at.  One kernel serves it, the harmony kernel's with the records: where the call has no bias,
-    grammar or harmony, a zero bias and all-off tables are made here (commu_sample_args.cls_ctl)."""
+    grammar or harmony, a zero bias and all-off tables are made here (commu_sample_args.cls_ctl).
+    note_order: int32 [nseq] on the device of the logits, one control word per sequence (generate.note_order_ctl): -1 off,
+    0 on, n >= 1 on with at most n notes per position.  A sequence that is on cannot draw a position before the one it
+    is at, a pitch its current position already holds, or (n >= 1) the position itself once it holds n notes; the bans
+    are read off seq[b][0 : state[b][0]] and replace y by -inf after the harmony term.  One kernel serves it, the class
+    kernel's with the scan: class_ctl= is required (a call without class controls passes records that all hold the
+    sequence's triple, generate.class_ctl_records) (commu_sample_args.order_ctl)."""
     nseq = logits.shape[0]
     V = int(V)
     assert logits.dtype == F32 and logits.stride(1) == 1
@@ -1013,6 +1020,13 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
                        torch.zeros(nseq, dtype=torch.uint8, device=logits.device), cstate,
                        torch.zeros(nseq, 1, dtype=torch.int32, device=logits.device))
         a.cls_ctl = _p(ctl)
+    if note_order is not None:
+        if class_ctl is None:
+            raise CommuHipError("note_order: class_ctl= expected as well (the one kernel reads the class records; pass the "
+                                "base-triple table where there are no class controls)")
+        _check_draw_state("note_order", logits.device, (
+            (note_order, "controls", torch.int32, "[%d]" % nseq, lambda t: tuple(t.shape) == (nseq,)),))
+        a.order_ctl = _p(note_order)
     if harmony is not None:
         htable, hon, hstate, chord_tok = harmony
         _check_draw_state("harmony", logits.device, (

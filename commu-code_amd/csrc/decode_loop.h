@@ -152,7 +152,33 @@ constexpr int TOK_PITCH_LO = 3, TOK_PITCH_HI = 130, HARM_NO_CHORD = 109, HARM_OF
 struct ClassControls {
     const int4* table;      // the sequence's 8 records
 };
-template <bool BIAS, bool GRAM = false, bool HARM = false, bool CLS = false>
+// ORD (NoteOrder: one int32 control per sequence, -1 off, 0 on, n in 1 .. 128 on with at most n notes per position): a ban
+//   chosen by what the sequence already holds at its current position, defined on seq alone when the stage runs (as the
+//   harmony row is: a Q5 re-draw, a re-armed and a primed sequence need no state of their own).  With L = min(max(F_LEN, 0),
+//   ld_seq) and S = seq[b][0:L]: j is the largest index with S[j] BAR or a POSITION token; none, or BAR: nothing is
+//   banned.  Else p = S[j], s is one past the largest i < j with S[i] BAR or a POSITION token != p (0: none), the RUN is
+//   S[s:L], D the PITCH tokens in it and n their number with multiplicity.  Banned: ids 432 .. p - 1 (the position never
+//   goes back), every id in D (no doubled note), and p itself when ctl >= 1 and n >= ctl (the cap).  A banned id's y is
+//   REPLACED by -inf after the harmony term -- a select, not an add: y = banned ? -inf : ((x + bias) + gram) + harm -- so
+//   all that is said of the bias holds (before top-k, never written back, probability exactly 0, `full` the log-softmax of
+//   y, a row with nothing left takes the Q12 exit), and a draw is bit for bit the CLS kernel's with bias[b] = -inf at the
+//   banned ids.  The bans apply whatever class is drawn and whatever the grammar's switch says.
+//   THE SCAN: lane l loads S[L - 1 - l - 64 c] for chunk c = 0, 1, .. (index clamped, lane carries a valid flag).  Chunk 0
+//   depends on F_LEN only and is issued beside the grammar's previous-token load, so it travels under the existing chain
+//   record -> previous token -> grammar row.  j and s are the lowest set lanes of two ballots ("BAR or POSITION", then "BAR
+//   or POSITION != p"; p by v_readlane); a chunk without the breaker looked for loops to the next one -- the trip count is
+//   wave-uniform (a scalar branch), bounded by ceil(L / 64), and a normal bar ends it in chunk 0.  p, n and the phase stay
+//   in scalar registers.  THE PITCH SET goes through LDS: the lanes of the run that hold a pitch write a flag at their id
+//   (192 ints, zeroed first), and the lanes that own the ids 0 .. 191 read their 12 flags back as three 16-byte reads -- one
+//   wave, LDS operations complete in order.  (The other design, four 32-bit words OR-reduced over the wave with the DPP
+//   helpers, was not built.)  The switch is one scalar: an off sequence runs the same scan and bans nothing, there is no
+//   branch on it.  Cost: +0.40 us on the kernel alone, +0.20 us more for a second chunk (docs/EXPERIMENTS.md 8v).
+//   ORD needs CLS (and so GRAM: the row of seq and its length are the grammar's).
+struct NoteOrder {
+    int ctl;                // the sequence's control as the caller loaded it
+};
+constexpr int ORD_FLAGS = 192;    // LDS flags by token id: 16 lanes * 12 ids >= TOK_PITCH_HI + 1
+template <bool BIAS, bool GRAM = false, bool HARM = false, bool CLS = false, bool ORD = false>
 __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restrict__ logits, int ld, int V,
                                                  const unsigned char* __restrict__ wrong, int ldw,
                                                  const float* __restrict__ uni,
@@ -163,8 +189,10 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
                                                  const float* __restrict__ bias = nullptr, int ld_bias = 0,
                                                  Grammar g = Grammar{nullptr, 0, nullptr, 0, 0, 0},
                                                  Harmony h = Harmony{nullptr, 0, nullptr, 0, 0, 0},
-                                                 ClassControls cc = ClassControls{nullptr}) {
+                                                 ClassControls cc = ClassControls{nullptr},
+                                                 NoteOrder no = NoteOrder{-1}) {
     static_assert(!CLS || GRAM, "the class key is the grammar's previous token");
+    static_assert(!ORD || CLS, "one note-order instantiation: the class kernel's with the scan");
     float* lg = logits + (size_t)b * ld;
     // The optional per-sequence inputs -- the active flag and this sequence's controls -- are loaded unconditionally: a null
     // array reads a valid word of this sequence instead (token[b], logits[b][0]), which is then ignored.  So they are in
@@ -185,6 +213,11 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
     for (int e = 0; e < PER_LANE; ++e) raw[e] = lg[min(base + e, V - 1)];
     int prev = 0;                 // (GRAM) the last token of seq: every lane loads the same word
     if constexpr (GRAM) prev = g.seq_row[min(max(g.len, 1), g.ld_seq) - 1];
+    int otok = 0, olen = 0;       // (ORD) chunk 0 of the backward scan: lane l holds seq[L - 1 - l] (clamped; valid: l < L)
+    if constexpr (ORD) {
+        olen = min(max(g.len, 0), g.ld_seq);
+        otok = g.seq_row[max(olen - 1 - lane, 0)];
+    }
     int chord = 0;                // (HARM) the last chord placed, chord_tok[b][F_CUR - 1]: likewise one word for all lanes
     if constexpr (HARM) chord = h.chord_row[min(max(h.cur, 1), h.ld_chord) - 1];
     float bv[PER_LANE];           // (BIAS) this lane's entries of the bias row, in the same batch of loads
@@ -237,6 +270,65 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
     // the radix select below needs 1 <= top_k <= V (exactly one lane owns the threshold bin); the host validates the
     // values, the clamp keeps the kernel in bounds whatever an array holds
     top_k = min(max(top_k, 1), V);
+    unsigned omask = 0u;          // (ORD) the ids of this lane that the note order bans
+    if constexpr (ORD) {
+        static_assert(PER_LANE == 12 && ORD_FLAGS % PER_LANE == 0 && ORD_FLAGS > TOK_PITCH_HI && ORD_FLAGS <= 3 * 64, "flag owners");
+        __shared__ __attribute__((aligned(16))) int oflag[ORD_FLAGS];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) oflag[lane + 64 * q] = 0;
+        int start = __builtin_amdgcn_readfirstlane(olen) - 1;         // seq index of lane 0 of the chunk
+        int pos = 0, n = 0, phase = 0;          // phase 0: looking for j; 1: p known, looking for s; 2: the run is complete
+        auto chunk = [&](int t) {
+            const bool valid = start - lane >= 0;
+            const bool brk = valid & ((t == TOK_BAR) | ((unsigned)(t - TOK_POS0) < (unsigned)POS_RES));
+            if (phase == 0) {
+                const unsigned long long m = __ballot(brk);
+                if (m != 0ull) {
+                    pos = __builtin_amdgcn_readlane(t, __builtin_ctzll(m));
+                    phase = 1;
+                }
+            }
+            unsigned long long take = ~0ull;    // the lanes of this chunk inside the run
+            if (phase == 1) {
+                // (a last breaker that is BAR differs from every POSITION token and from no BAR: the first ballot's lane
+                // itself answers, the run is empty below it and nothing of it is used)
+                const unsigned long long m = __ballot(brk & ((t != pos) | (pos == TOK_BAR)));
+                if (m != 0ull) {
+                    take = (1ull << __builtin_ctzll(m)) - 1ull;
+                    phase = 2;
+                }
+            }
+            const bool hit = valid & ((unsigned)(t - TOK_PITCH_LO) <= (unsigned)(TOK_PITCH_HI - TOK_PITCH_LO)) &
+                             (((take >> lane) & 1ull) != 0ull);
+            n += __popcll(__ballot(hit));
+            if (hit) oflag[t] = 1;
+            start -= 64;
+        };
+        // chunk 0 in straight-line code: its load went out beside the previous token's and has long arrived (as compiled
+        // the scan starts behind the rejected-token map's wait, which is for every load of the step: what the scan costs is
+        // its instructions, not a memory round trip)
+        chunk(otok);
+#pragma unroll 1
+        while (phase != 2 && start >= 0) chunk(g.seq_row[max(start - lane, 0)]);
+        __builtin_amdgcn_s_waitcnt(0xc07f);      // lgkmcnt(0): one wave, LDS operations complete in order
+        const int ctl = __builtin_amdgcn_readfirstlane(no.ctl);
+        const bool on = ctl >= 0 && phase != 0 && pos != TOK_BAR;
+        const int hi = on ? pos + ((ctl >= 1 && n >= ctl) ? 1 : 0) : TOK_POS0;         // positions [432, hi) are banned
+        // the lane's 12 flags as 16-byte LDS reads, unconditional (the lanes past the flags read the last owner's and
+        // drop them), packed into a bit mask without a branch: behind a branch per element they were 12 dependent LDS
+        // round trips and some 200 instructions
+        const int4* fq = reinterpret_cast<const int4*>(oflag + min(base, ORD_FLAGS - PER_LANE));
+        unsigned dm = 0u;
+#pragma unroll
+        for (int q = 0; q < PER_LANE / 4; ++q) {
+            const int4 f4 = fq[q];              // (a flag is 0 or 1)
+            dm |= ((unsigned)f4.x << (4 * q)) | ((unsigned)f4.y << (4 * q + 1)) | ((unsigned)f4.z << (4 * q + 2)) |
+                  ((unsigned)f4.w << (4 * q + 3));
+        }
+        const int lo_e = min(max(TOK_POS0 - base, 0), PER_LANE), hi_e = min(max(hi - base, 0), PER_LANE);
+        const unsigned pm = ((1u << hi_e) - 1u) & ~((1u << lo_e) - 1u);          // (empty while hi <= 432)
+        omask = pm | ((on && base < ORD_FLAGS) ? dm : 0u);
+    }
     if (active != nullptr && act_row == 0) return -2;
     // ---- calc_probs
     float lmx = 0.f, lsum = 1.f;          // (want_logp) max and sum of exp(x - max) over ids 1 .. V-1 of the row drawn from
@@ -249,6 +341,7 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
             if constexpr (BIAS) raw[e] += bv[e];               // greedy writes nothing back: the row drawn from is y
             if constexpr (GRAM) raw[e] += gv[e];
             if constexpr (HARM) raw[e] = (id >= TOK_PITCH_LO && id <= TOK_PITCH_HI) ? raw[e] + hv[e] : raw[e];
+            if constexpr (ORD) raw[e] = ((omask >> e) & 1u) ? -INFINITY : raw[e];
             if (id >= 1 && id < V && raw[e] > best) { best = raw[e]; bi = id; }
         }
         const float wbest = wmax_f(best);                      // ties: the lowest id
@@ -277,6 +370,7 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
             if constexpr (BIAS) y = in ? x + bv[e] : -INFINITY;          // (the bias is not written back)
             if constexpr (GRAM) y = in ? y + gv[e] : -INFINITY;          // (nor the grammar row)
             if constexpr (HARM) y = (id >= TOK_PITCH_LO && id <= TOK_PITCH_HI) ? y + hv[e] : y;      // (nor the chord's)
+            if constexpr (ORD) y = ((omask >> e) & 1u) ? -INFINITY : y;                                 // (nor the bans)
             p[e] = y;
             mx = fmaxf(mx, y);
         }

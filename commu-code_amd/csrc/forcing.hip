@@ -79,16 +79,22 @@ struct LoopStageArgsHarm : LoopStageArgsGram {
 struct LoopStageArgsCls : LoopStageArgsHarm {
     const int4* cls_ctl;
 };
-template <bool GRAM, bool HARM = false, bool CLS = false>
+// (ORD) the note-order control words [B] (decode_loop.h: NoteOrder): an argument of the note-order kernel only
+struct LoopStageArgsOrd : LoopStageArgsCls {
+    const int* order_ctl;
+};
+template <bool GRAM, bool HARM = false, bool CLS = false, bool ORD = false>
 struct LoopArgsOf { using type = LoopStageArgs; };
 template <>
-struct LoopArgsOf<true, false, false> { using type = LoopStageArgsGram; };
+struct LoopArgsOf<true, false, false, false> { using type = LoopStageArgsGram; };
 template <>
-struct LoopArgsOf<true, true, false> { using type = LoopStageArgsHarm; };
+struct LoopArgsOf<true, true, false, false> { using type = LoopStageArgsHarm; };
 template <>
-struct LoopArgsOf<true, true, true> { using type = LoopStageArgsCls; };
-template <bool BIAS, bool GRAM, bool HARM = false, bool CLS = false>
-__global__ __launch_bounds__(64) void sample_post_pre_kernel(typename LoopArgsOf<GRAM, HARM, CLS>::type a) {
+struct LoopArgsOf<true, true, true, false> { using type = LoopStageArgsCls; };
+template <>
+struct LoopArgsOf<true, true, true, true> { using type = LoopStageArgsOrd; };
+template <bool BIAS, bool GRAM, bool HARM = false, bool CLS = false, bool ORD = false>
+__global__ __launch_bounds__(64) void sample_post_pre_kernel(typename LoopArgsOf<GRAM, HARM, CLS, ORD>::type a) {
     const int b = blockIdx.x, lane = threadIdx.x;
     if (a.trace != nullptr && lane == 0) a.trace[b * 4 + 0] = wall_clock64();
     int rec[F_COUNT];                                  // the record travels through the three stages in lane 0's registers;
@@ -116,10 +122,13 @@ __global__ __launch_bounds__(64) void sample_post_pre_kernel(typename LoopArgsOf
     }
     ClassControls cc{nullptr};
     if constexpr (CLS) cc = ClassControls{a.cls_ctl + (size_t)b * 8};      // (the body loads the record it selects)
-    const int drawn = sample_topk_body<BIAS, GRAM, HARM, CLS>(b, lane, a.logits, a.ld, a.V, a.wrong, VOCAB, a.uni, a.draw,
-                                                              a.temperature, a.top_k, a.token, a.probs_out, a.ldp, a.top_p,
-                                                              a.rows, a.logp != nullptr || a.seq_logp != nullptr, a.logp,
-                                                              lp, a.bias, a.ld_bias, g, h, cc);
+    NoteOrder no{-1};
+    if constexpr (ORD) no = NoteOrder{a.order_ctl[b]};                      // (the control word with the flags above)
+    const int drawn = sample_topk_body<BIAS, GRAM, HARM, CLS, ORD>(b, lane, a.logits, a.ld, a.V, a.wrong, VOCAB, a.uni,
+                                                                   a.draw, a.temperature, a.top_k, a.token, a.probs_out,
+                                                                   a.ldp, a.top_p, a.rows,
+                                                                   a.logp != nullptr || a.seq_logp != nullptr, a.logp, lp,
+                                                                   a.bias, a.ld_bias, g, h, cc, no);
     __syncthreads();
     if (a.trace != nullptr && lane == 0) a.trace[b * 4 + 1] = wall_clock64();
     forcing_post_body(b, lane, rec, a.seq, a.ld_seq, a.chord_pos, a.ld_chord, a.wrong, a.draw, a.token, nullptr, a.klen,
@@ -307,7 +316,10 @@ extern "C" int commu_decode_sample_post_pre(const commu_decode_loop_args* p, hip
                                   p->harm == nullptr || p->chord_tok == nullptr ||
                                   (reinterpret_cast<uintptr_t>(p->cls_ctl) & 15u) != 0))
         return -22;
-    LoopStageArgsCls a;
+    // (the kernel reads order_ctl[b] and walks seq[b] backwards from the record's length; one instantiation, the class
+    // kernel's with the scan)
+    if (p->order_ctl != nullptr && p->cls_ctl == nullptr) return -22;
+    LoopStageArgsOrd a;
     static_cast<LoopStageArgs&>(a) = LoopStageArgs{
         p->logits, p->ld, V, p->wrong, p->temperature, p->top_k, p->top_p,
         SamplingRows{p->temperature_rows, p->top_k_rows, p->top_p_rows}, p->token, p->probs_out, p->ldp, p->logp, p->seq_logp,
@@ -316,14 +328,18 @@ extern "C" int commu_decode_sample_post_pre(const commu_decode_loop_args* p, hip
     a.gram = p->gram; a.ld_gram = p->ld_gram; a.gram_on = p->gram_on;
     a.harm = p->harm; a.ld_harm = p->ld_harm; a.harm_on = p->harm_on;
     a.cls_ctl = static_cast<const int4*>(p->cls_ctl);
+    a.order_ctl = p->order_ctl;
+    const LoopStageArgsCls& ac = a;
     const LoopStageArgsHarm& ah = a;
     const LoopStageArgsGram& ag = a;          // (each kernel gets the argument block of its own kind, by value)
     const LoopStageArgs& a0 = a;
     const dim3 grid(p->B), block(64);
     // five kernels: without a bias / a grammar / a harmony table the launch is the one it always was (no added load, no
-    // added register, no added argument); a sixth for the class-keyed controls
-    if (p->cls_ctl != nullptr) {
-        COMMU_LAUNCH((sample_post_pre_kernel<true, true, true, true>), grid, block, 0, stream, a);
+    // added register, no added argument); a sixth for the class-keyed controls, a seventh for the note order
+    if (p->order_ctl != nullptr) {
+        COMMU_LAUNCH((sample_post_pre_kernel<true, true, true, true, true>), grid, block, 0, stream, a);
+    } else if (p->cls_ctl != nullptr) {
+        COMMU_LAUNCH((sample_post_pre_kernel<true, true, true, true>), grid, block, 0, stream, ac);
     } else if (p->harm != nullptr) {
         COMMU_LAUNCH((sample_post_pre_kernel<true, true, true>), grid, block, 0, stream, ah);
     } else if (p->gram != nullptr) {

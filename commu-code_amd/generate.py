@@ -20,6 +20,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 DECODE_SLOTS_MIN, DECODE_SLOTS_MAX, DECODE_SLOTS_DEFAULT = 1, 256, 64          # --decode_slots
+MAX_NOTES_MIN, MAX_NOTES_MAX = 1, 128                                             # --max_notes
 
 
 def parse_args():
@@ -73,6 +74,16 @@ def parse_args():
                                   help="sampling controls per token family: {\"pitch\": {\"temperature\": 1.1, \"top_k\": 40}, "
                                        "\"duration\": {\"temperature\": 0}} (drawn names velocity, pitch, duration, boundary "
                                        "need --grammar; {\"after\": {...}} is keyed by the previous token's class)")
+    # not in the reference (whose sampler may step back inside a bar or put one pitch twice on one onset -- its training
+    # data, sorted by start time with one Position token per note, never does): inside a bar the DRAWN positions never go
+    # back and no pitch is drawn twice at one position; --max_notes N (1 .. 128, implies --note_order) also stops a position
+    # from being drawn again once it holds N notes (1: one note per onset).  Not enforced: overlapping durations, the order
+    # inside --prompt_tokens, forced tokens.  Combines with every other option, --parity included.
+    model_arg_parser.add_argument("--note_order", action="store_true",
+                                  help="note order: inside a bar drawn positions never go back and no note is doubled")
+    model_arg_parser.add_argument("--max_notes", default=None, metavar="N",
+                                  help=f"at most N notes per position, {MAX_NOTES_MIN} .. {MAX_NOTES_MAX} (implies --note_order; "
+                                       "1 = one note per onset)")
     # not in the reference (which decodes one sequence at a time): how many attempts are decoded side by side.  1 .. 256;
     # up to 256 slots run the fused layer-tail launches ("Supported shapes").  The sequences returned do
     # not depend on it.  (checked by check_decode_slots: the range is named in its message)
@@ -155,6 +166,23 @@ def check_decode_slots(model_args):
         raise ValueError(f"--decode_slots: an integer in [{DECODE_SLOTS_MIN}, {DECODE_SLOTS_MAX}] expected, got {v!r}")
     model_args.decode_slots = n
     return n
+
+
+def check_note_order(model_args):
+    """--note_order / --max_notes as the note-order control word (None: neither flag; 0: on; N: on with the cap); host
+    code only, ValueError that names the range.  Written back to model_args.note_order_word, which travels to the
+    replicas (ModelInitializeTask puts it into the inference configuration)."""
+    v = getattr(model_args, "max_notes", None)
+    word = 0 if getattr(model_args, "note_order", False) else None
+    if v is not None:
+        try:
+            word = int(v) if not isinstance(v, (bool, float)) else None
+        except (TypeError, ValueError):
+            word = None
+        if word is None or not MAX_NOTES_MIN <= word <= MAX_NOTES_MAX:
+            raise ValueError(f"--max_notes: an integer in [{MAX_NOTES_MIN}, {MAX_NOTES_MAX}] expected, got {v!r}")
+    model_args.note_order_word = word
+    return word
 
 
 def read_constraints(path=None, pitch_min=None, pitch_max=None):
@@ -243,6 +271,7 @@ def main(model_args, input_args, training_cfg=None, device_indices=None):
     import torch
     check_share_prompt(model_args, input_args)          # (refused before a model is loaded or a replica started)
     check_decode_slots(model_args)                      # (likewise)
+    check_note_order(model_args)                        # (likewise)
     in_args = dict(vars(input_args))
     max_rounds = in_args.pop("max_rounds", None)
     gpus = in_args.pop("gpus", None)

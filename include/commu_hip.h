@@ -481,6 +481,22 @@ int commu_transpose_heads(const void* src, int ld, const float* bias, void* dst,
  *     the zero bias and all-off switch arrays where there is none) and a 16-byte aligned pointer, else -22.  Validating
  *     the records is the caller's job (generate.class_sampling).  The same field, with the same meaning and the same
  *     refusals, ends commu_decode_loop_args.
+ * NOTE ORDER (the reference's encoder sorts a bar's notes by start time: training data never steps back inside a bar and
+ * never holds one pitch twice at one position; the reference's sampler does not enforce either)
+ *   order_ctl: int32 [nseq], one control word per sequence: -1 off, 0 on, n in 1 .. 128 on with at most n notes per
+ *     position.  Defined on seq alone when the stage runs: L = min(max(F_LEN, 0), ld_seq), S = seq[b][0:L]; j the largest
+ *     index with S[j] == BAR (2) or a POSITION token (432 .. 559) -- none, or BAR: nothing is banned; else p = S[j], s one
+ *     past the largest i < j with S[i] BAR or a POSITION token != p (0: none), the run is S[s:L], D the PITCH tokens
+ *     (3 .. 130) in it, n their number with multiplicity.  BANNED: ids 432 .. p - 1; every id in D; p itself when
+ *     order_ctl[b] >= 1 and n >= order_ctl[b].  A banned id's y is replaced by -inf after the harmony term (a select):
+ *     before top-k, never written back, probs_out exactly 0 there, the logp pair's `full` the log-softmax of y, a row
+ *     with nothing left gives token -1.  The bans apply whatever class is drawn and whatever gram_on[b] says.  A draw is
+ *     BIT FOR BIT the draw of the call without order_ctl and with bias[b] = -inf at the banned ids; an off sequence, or a
+ *     draw with nothing banned, is bit for bit the call without the field.  ONE kernel serves it, the class-control
+ *     kernel with the scan of seq: order_ctl requires cls_ctl and everything cls_ctl requires, else -22 (a caller
+ *     without class controls passes a table whose eight records all hold the sequence's triple).  Validating the words is
+ *     the caller's job (generate.note_order_ctl).  The same field, with the same meaning and the same refusal, ends
+ *     commu_decode_loop_args.  Null: the launch that never heard of it.
  * WHAT gram / harm READ
  *   state: the forcing records, int32 [nseq][commu_forcing_state_ints()]; seq int32 [nseq][ld_seq]; chord_tok int32
  *   [nseq][ld_chord].  Not looked at, and may be null, in a call without gram and harm.
@@ -520,6 +536,8 @@ typedef struct commu_sample_args {
     const int* seq;
     const int* chord_tok;
     int ld_seq, ld_chord;
+    /* note order (placed ahead of cls_ctl, which stays the struct's last field) */
+    const int* order_ctl;
     /* class-keyed controls */
     const void* cls_ctl;
 } commu_sample_args;
@@ -739,6 +757,8 @@ typedef struct commu_decode_loop_args {
     const float* harm;
     const unsigned char* harm_on;
     int ld_bias, ld_gram, ld_harm;
+    /* note order (commu_sample_args.order_ctl; likewise ahead of cls_ctl) */
+    const int* order_ctl;
     /* class-keyed controls (commu_sample_args.cls_ctl) */
     const void* cls_ctl;
 } commu_decode_loop_args;
