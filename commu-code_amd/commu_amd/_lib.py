@@ -64,7 +64,7 @@ class SampleArgs(C.Structure):
                 ("bias", c_p), ("gram", c_p), ("gram_on", c_p), ("harm", c_p), ("harm_on", c_p),
                 ("ld_bias", c_i), ("ld_gram", c_i), ("ld_harm", c_i),
                 ("state", c_p), ("seq", c_p), ("chord_tok", c_p), ("ld_seq", c_i), ("ld_chord", c_i),
-                ("order_ctl", c_p), ("cls_ctl", c_p)]
+                ("order_ctl", c_p), ("voice_ctl", c_p), ("cls_ctl", c_p)]
 
 
 class DecodeLoopArgs(C.Structure):
@@ -80,7 +80,7 @@ class DecodeLoopArgs(C.Structure):
                 ("klen", c_p), ("lmax", c_i),
                 ("bias", c_p), ("gram", c_p), ("gram_on", c_p), ("harm", c_p), ("harm_on", c_p),
                 ("ld_bias", c_i), ("ld_gram", c_i), ("ld_harm", c_i),
-                ("order_ctl", c_p), ("cls_ctl", c_p)]
+                ("order_ctl", c_p), ("voice_ctl", c_p), ("cls_ctl", c_p)]
 
 
 def struct_args(cls, **fields):

@@ -505,6 +505,53 @@ def note_order_ctl(x, B: int):
                      for b, v in enumerate(x)], dtype=np.int32)
 
 
+# ---- voice cap: one int32 control word per slot (commu_sample_args.voice_ctl).  A slot that is on cannot draw a position at
+# which N notes it already holds still sound, nor -- with the re-strike switch -- a pitch that still sounds at the onset it
+# is at.  Like the note order it is read off the slot's seq when the sampling stage runs; it relies on the note order (the
+# onsets never go back), which set_voices switches on.
+VOICES_OFF = -1
+VOICES_MAX = 128              # (no more notes can sound than there are pitches)
+VOICES_RESTRIKE = 256         # the word's re-strike bit
+
+
+def voices_word(max_voices: int = 0, no_restrike: bool = False) -> int:
+    """The control word N + 256 r of a cap (0: none) and the re-strike ban; voices_ctl validates it."""
+    return int(max_voices) + (VOICES_RESTRIKE if no_restrike else 0)
+
+
+def voices_ctl(x, B: int):
+    """A request's voices= as the int32 control words of B slots: None / False (off, -1) or an integer word N + 256 r with N
+    in 0 .. 128 (at most N notes sound at once; 0: no cap) and r in {0, 1} (1: a sounding pitch is not struck again) --
+    voices_word(N, r) -- or one such value per slot.  Pure host code; raises CommuHipError on anything else, with the
+    numbers."""
+    B = int(B)
+
+    def word(v, where):
+        if v is None or v is False or (isinstance(v, np.bool_) and not v):
+            return VOICES_OFF
+        ok = not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating)) \
+            and np.isfinite(v) and v == np.floor(v) and (v == VOICES_OFF or (0 <= v < 2 * VOICES_RESTRIKE and
+                                                                            (int(v) & 255) <= VOICES_MAX))
+        if not ok:
+            raise CommuHipError(f"voices{where}: None / False (off) or an integer word N + {VOICES_RESTRIKE} r with N in "
+                                f"[0, {VOICES_MAX}] (notes sounding at once; 0 = no cap) and r in {{0, 1}} (1 = no "
+                                f"re-striking; -1 = off) expected, got {v!r}")
+        return int(v)
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    if x is None or np.ndim(x) == 0:
+        if isinstance(x, np.ndarray):
+            x = x.item()
+        return np.full(B, word(x, ""), dtype=np.int32)
+    x = list(x)
+    if len(x) != B:
+        raise CommuHipError(f"voices: {B} values expected (one per sequence), got {len(x)}")
+    if any(np.ndim(v) != 0 for v in x):
+        raise CommuHipError(f"voices: one value per sequence expected, got shape {np.shape(x)}")
+    return np.array([word(v.item() if isinstance(v, np.generic) and not isinstance(v, np.bool_) else v, f"[{b}]")
+                     for b, v in enumerate(x)], dtype=np.int32)
+
+
 class DecodeState:
     """K/V caches + distance-indexed R tables for B sequences of up to Lmax positions.
 
@@ -1075,6 +1122,9 @@ class ForcedDecoder:
         # slot on, and their host mirror; None: the launches a decoder without the feature always made
         self.order_ctl = None
         self._order_host = None
+        # voice cap (set_voices): likewise the slots' voice words int32 [B] and their host mirror
+        self.voice_ctl = None
+        self._voice_host = None
         # (the replay of a prompt token takes at most two iterations: the decision to force it, then its append)
         self.ld_trace = 2 * (self.generation_length + 2 + 2 * self.max_prompt) if record_trace else 0
         self.trace = torch.zeros(B, self.ld_trace, dtype=i32, device=dev) if record_trace else None
@@ -1103,11 +1153,12 @@ class ForcedDecoder:
             raise CommuHipError(f"rows: slot numbers in [0, {self.B}) expected, got {rows!r}")
         return idx
 
-    def _first_use(self, rows=False, bias=False, gram=False, harm=False, cls=False, order=False):
+    def _first_use(self, rows=False, bias=False, gram=False, harm=False, cls=False, order=False, voices=False):
         """What the first use of a per-slot launch input does, for each one asked for that the decoder does not have yet:
         rows uploads the host mirror of the sampling controls (scalar mode kept the mirror only); bias / gram / harm
         allocate their zeroed device buffers (gram and harm: the table and the [B] switches); cls allocates the slots'
-        class-control records (set_class_sampling fills them); order allocates the slots' note-order words, all off.
+        class-control records (set_class_sampling fills them); order allocates the slots' note-order words, all off; voices
+        the slots' voice words, all off.
         When anything was missing the captured graphs are dropped,
         once: they hold the launches without it."""
         new = False
@@ -1134,6 +1185,10 @@ class ForcedDecoder:
             new = True
             self.order_ctl = torch.full((self.B,), NOTE_ORDER_OFF, dtype=torch.int32, device=self.dev)
             self._order_host = np.full(self.B, NOTE_ORDER_OFF, dtype=np.int32)
+        if voices and self.voice_ctl is None:
+            new = True
+            self.voice_ctl = torch.full((self.B,), VOICES_OFF, dtype=torch.int32, device=self.dev)
+            self._voice_host = np.full(self.B, VOICES_OFF, dtype=np.int32)
         if new:
             self.graph = self.graph_long = None
 
@@ -1324,9 +1379,9 @@ class ForcedDecoder:
         an all-off grammar, an all-off harmony table and the class records holding every slot's base triple -- and drops
         the captured graphs once; later calls rewrite the words IN PLACE, ordered on the current stream, and a captured
         graph follows them.  A slot that is off bans nothing: it decodes bit for bit what it decoded without the feature.
-        A decoder that never switched a slot on allocates nothing.  Not enforced: overlapping durations (a cap of 1 is one
-        note per onset, not strict monophony); a bias, pitch range or strict harmony that leaves fewer pitches than notes
-        asked for at one position ends the slot by Q12."""
+        A decoder that never switched a slot on allocates nothing.  Overlapping durations are not this rule's (a cap of 1 is
+        one note per onset, not strict monophony): set_voices bans them.  A bias, pitch range or strict harmony that
+        leaves fewer pitches than notes asked for at one position ends the slot by Q12."""
         idx = self._slots(rows)
         new = note_order_ctl(value, len(idx))                  # (validated before anything changes)
         if self.order_ctl is None and not bool((new != NOTE_ORDER_OFF).any()):
@@ -1343,6 +1398,39 @@ class ForcedDecoder:
         else:
             for j in idx:
                 self.order_ctl[int(j)].fill_(int(self._order_host[j]))
+
+    def set_voices(self, value, rows: Optional[Sequence[int]] = None):
+        """The voice cap for all slots (rows=None) or the listed ones: a word voices_word(N, r) -- at most N of the slot's
+        notes sound at once (N = 0: no cap; N = 1: a monophonic line) and, with r, no pitch is struck while it sounds --
+        None / False (off), or one such value per addressed slot (voices_ctl).  A note is a Position, Velocity, Pitch,
+        Duration group of the slot's seq, as the token-to-MIDI step reads it; a slot that is on cannot DRAW a position at
+        which N notes of the current or the previous bar still sound, nor a pitch that still sounds at the onset the bar is
+        at.  The rule relies on the note order (every known note then starts at or before any onset that can still be
+        drawn): a slot switched on here whose note order is off gets it switched on (word 0, no cap per position), and
+        switching the voices off leaves the note order as it is.  The state is read off seq when the sampling stage runs
+        (the prompt of a primed slot included).  Only DRAWS are constrained: notes inside a prompt are not checked against
+        each other and a forced token is placed by the rules.  The first call that switches a slot on allocates the [B]
+        words and drops the captured graphs once; later calls rewrite the words IN PLACE, ordered on the current stream,
+        and a captured graph follows them.  A slot that is off bans nothing.  A decoder that never switched a slot on
+        allocates nothing.  When a whole bar's rest is banned only Bar and EOS remain of the boundary family; a pitch range,
+        bias or strict harmony that leaves no pitch free ends the slot by Q12."""
+        idx = self._slots(rows)
+        new = voices_ctl(value, len(idx))                      # (validated before anything changes)
+        if self.voice_ctl is None and not bool((new != VOICES_OFF).any()):
+            return
+        need = [int(j) for j, w in zip(idx, new)
+                if w != VOICES_OFF and (self._order_host is None or self._order_host[j] == NOTE_ORDER_OFF)]
+        if need:
+            self.set_note_order(True, rows=need)               # (allocates what the note-order kernel reads)
+        self._first_use(voices=True)
+        if np.array_equal(self._voice_host[idx], new):
+            return
+        self._voice_host[idx] = new
+        if rows is None and len(idx) > 4:
+            self.voice_ctl.copy_(torch.from_numpy(self._voice_host))
+        else:
+            for j in idx:
+                self.voice_ctl[int(j)].fill_(int(self._voice_host[j]))
 
     def pre(self):
         call("commu_forcing_pre", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_tok), _p(self.chord_pos),
@@ -1362,7 +1450,8 @@ class ForcedDecoder:
                         logp_out=logp, bias=self.bias, **({} if self.gram is None else {"grammar": self._gram_args()}),
                         **({} if self.harm is None else {"harmony": self._harm_args()}),
                         **({} if self.cls_ctl is None else {"class_ctl": self._cls_args()}),
-                        **({} if self.order_ctl is None else {"note_order": self.order_ctl}))
+                        **({} if self.order_ctl is None else {"note_order": self.order_ctl}),
+                        **({} if self.voice_ctl is None else {"voices": self.voice_ctl}))
         call("commu_forcing_post", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_pos), self.ld_chord,
              _p(self.wrong), _p(self.draw), _p(self.token), None, _p(self.state.klen), _p(self.keep),
              self.state.klen_cap, _p(logp), _p(seq_logp), B, _s())
@@ -1386,7 +1475,7 @@ class ForcedDecoder:
             trace=_p(self.trace), ld_trace=self.ld_trace, klen=_p(st.klen), lmax=st.klen_cap,
             bias=_p(self.bias), ld_bias=ld(self.bias), gram=_p(self.gram), ld_gram=ld(self.gram), gram_on=_p(self.gram_on),
             harm=_p(self.harm), ld_harm=ld(self.harm), harm_on=_p(self.harm_on), cls_ctl=_p(self.cls_ctl),
-            order_ctl=_p(self.order_ctl))
+            order_ctl=_p(self.order_ctl), voice_ctl=_p(self.voice_ctl))
         call("commu_decode_sample_post_pre", C.byref(a), _s())
 
     def iteration(self, want_probs: bool = False):
@@ -1645,10 +1734,13 @@ class ForcedDecoder:
     # grammar: True / False switches the slot's event grammar for its next attempt (None: the slot keeps its switch).
     # harmony: True / False switches the slot's harmony constraint for its next attempt (None: the slot keeps its switch).
     # note_order: the slot's note-order control for its next attempt (set_note_order's values; None: the slot keeps its word).
+    # voices: the slot's voice word for its next attempt (set_voices' values, False: off; None: the slot keeps its word).
     def rearm(self, b: int, uniforms_row: Optional[np.ndarray] = None, sampling=None, logit_bias=None, grammar=None,
-              harmony=None, note_order=None):
+              harmony=None, note_order=None, voices=None):
         if note_order is not None:
             self.set_note_order(note_order, rows=[b])
+        if voices is not None:
+            self.set_voices(voices, rows=[b])
         if sampling is not None:
             self.set_sampling(*sampling, rows=[b])
         if logit_bias is not None:
@@ -1843,7 +1935,7 @@ class BatchedGenerator:
 
     def decoder(self, B, temperature, top_k, max_chords, top_p=1.0, per_slot: bool = False, max_prompt: int = 0,
                 logit_bias=None, shared: bool = False, grammar=None, harmony=None, class_sampling=None,
-                note_order=None):
+                note_order=None, voices=None):
         """The decoder for B slots, its slots set to the given controls (numbers or one value per slot).  per_slot: the
         caller will read log-probabilities or give slots their own controls later (rearm): the array launches from the
         start.  Otherwise one triple for all slots runs the scalar launches, until a second setting arrives for launches
@@ -1852,7 +1944,9 @@ class BatchedGenerator:
         grammar and harmony table (None switches off what an earlier request left).  class_sampling: the request's
         class-control table (None resets every slot to its base triple where an earlier request left one; a decoder that
         never had a table allocates nothing).  note_order: the request's note-order controls (note_order_ctl; None
-        switches off what an earlier request left, and allocates nothing on a decoder that never had one).  shared: the decoder that holds the
+        switches off what an earlier request left, and allocates nothing on a decoder that never had one).  voices: the
+        request's voice words (voices_ctl), likewise; a slot that gets one has its note order switched on.  shared: the
+        decoder that holds the
         request's common prompt once (its own cache layout: kept beside the unshared decoder of the same size)."""
         rows = sampling_rows(B, temperature, top_k, top_p)          # (validated before anything is built)
         if logit_bias is not None:
@@ -1861,6 +1955,7 @@ class BatchedGenerator:
         harm_table = _harmony_request(harmony)
         cls_table = _class_request(class_sampling)
         order = note_order_ctl(note_order, B)
+        vox = voices_ctl(voices, B)
         key = (B, self.trace is not None, self.sliding) + (("shared",) if shared else ())
         dec = self._decoders.get(key)
         if dec is None or dec.ld_chord < max_chords or dec.max_prompt < max_prompt:
@@ -1885,6 +1980,8 @@ class BatchedGenerator:
         dec.set_class_sampling(cls_table)
         # (note order: likewise; its first use fills the class records with the base triples set above)
         dec.set_note_order(order)
+        # (voice cap: likewise, after the note order -- it switches the note order on where the request left it off)
+        dec.set_voices(vox)
         return dec
 
     @staticmethod
@@ -1897,8 +1994,10 @@ class BatchedGenerator:
     @torch.no_grad()
     def generate(self, encoded_metas: Sequence[Sequence[int]], input_datas, temperature, top_k, top_p=1.0,
                  return_logprobs: bool = False, prompts: Optional[Sequence[Sequence[int]]] = None, logit_bias=None,
-                 grammar=None, harmony=None, class_sampling=None, note_order=None):
-        """temperature / top_k / top_p: a number for the batch or one value per sequence.  note_order: None / False, True,
+                 grammar=None, harmony=None, class_sampling=None, note_order=None, voices=None):
+        """temperature / top_k / top_p: a number for the batch or one value per sequence.  voices: None / False, a word
+        voices_word(N, r) or one per sequence -- at most N notes such a sequence DRAWS sound at once and (r) no pitch is
+        struck while it sounds; switches the sequence's note order on (ForcedDecoder.set_voices).  note_order: None / False, True,
         an integer cap in 1 .. 128 or one such value per sequence -- inside a bar the positions such a sequence DRAWS never
         go back, no pitch is drawn twice at one position and, with a cap, a position gets at most that many notes
         (ForcedDecoder.set_note_order).  class_sampling: None, a table
@@ -1921,7 +2020,8 @@ class BatchedGenerator:
         # (shared_prompt: requests with a prompt only -- without one there is nothing but the short context to share)
         dec = self.decoder(B, temperature, top_k, max_chords, top_p, per_slot=return_logprobs, max_prompt=max_prompt,
                            logit_bias=logit_bias, shared=self.shared_prompt and max_prompt > 0, grammar=grammar,
-                           harmony=self._one_harmony(harmony), class_sampling=class_sampling, note_order=note_order)
+                           harmony=self._one_harmony(harmony), class_sampling=class_sampling, note_order=note_order,
+                           voices=voices)
         uniforms = None
         if bool((dec._sampling[0] != 0).any()) or dec.class_samples():
             srcs = self.uniform_sources or [np.random.RandomState(1000 + b).random_sample for b in range(B)]
@@ -1945,7 +2045,8 @@ class BatchedGenerator:
     def generate_stream(self, encoded_meta: Sequence[int], input_data, temperature, top_k, need: int,
                         accept, top_p=1.0, slots: int = 64, seed: int = 0, max_attempts: Optional[int] = None,
                         return_logprobs: bool = False, prompt: Optional[Sequence[int]] = None, logit_bias=None,
-                        share_prompt: bool = False, grammar=None, harmony=None, class_sampling=None, note_order=None):
+                        share_prompt: bool = False, grammar=None, harmony=None, class_sampling=None, note_order=None,
+                        voices=None):
         """Attempts of ONE request (the reference's `while idx != num_generate` loop, midi_inferrer.py:338-354, which tries
         one sequence after the other) decoded in up to `slots` parallel slots, CONTINUOUSLY: a slot whose sequence has
         ended is handed to `accept(sequence, report) -> bool` and re-armed with the next attempt while the other slots keep
@@ -1965,6 +2066,8 @@ class BatchedGenerator:
         entries it leaves open inherit the ATTEMPT's own triple (a re-armed slot recomposes them).
         note_order: None / False, True or an integer cap in 1 .. 128: one setting for every attempt of the request
         (ForcedDecoder.set_note_order; the bans are read off a slot's seq, so a re-armed slot needs nothing).
+        voices: None / False or a word voices_word(N, r): one setting for every attempt of the request
+        (ForcedDecoder.set_voices; likewise read off seq).
         share_prompt (opt-in; also on with BatchedGenerator(shared_prompt=True) when a prompt is given): the K/V of the
         context and the prompt are computed and held once for all slots (ForcedDecoder(shared_prompt=True)); the attempts
         returned are the ones the unshared decoder defines, up to the summation order of the attention."""
@@ -1980,6 +2083,8 @@ class BatchedGenerator:
         harmony = self._one_harmony(harmony)
         if note_order is not None and np.ndim(note_order) != 0:
             raise CommuHipError(f"note_order: one setting for the request expected, got shape {np.shape(note_order)}")
+        if voices is not None and np.ndim(voices) != 0:
+            raise CommuHipError(f"voices: one setting for the request expected, got shape {np.shape(voices)}")
         max_chords = len(input_data.chord_token_components["chord_token"])
         # each control's schedule, validated on its own (the three may have different lengths)
         n_of = lambda x: 1 if np.ndim(x) == 0 else len(x)
@@ -1993,7 +2098,7 @@ class BatchedGenerator:
         dec = self.decoder(B, [t[0] for t in first], [t[1] for t in first], max_chords, [t[2] for t in first],
                            per_slot=return_logprobs or varying, max_prompt=0 if prompt is None else len(prompt),
                            logit_bias=logit_bias, shared=share, grammar=grammar, harmony=harmony,
-                           class_sampling=class_sampling, note_order=note_order)
+                           class_sampling=class_sampling, note_order=note_order, voices=voices)
         started = B
         sampled = bool((sched[0] != 0).any()) or dec.class_samples()          # (a greedy attempt reads no variate)
         uni = np.stack([self.attempt_uniforms(seed, a, dec.ld_u) for a in range(B)]) if sampled else None

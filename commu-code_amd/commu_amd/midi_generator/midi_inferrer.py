@@ -141,6 +141,86 @@ def note_order_violation(seq: List[int], start: int, max_notes: int = 0) -> Opti
     return None
 
 
+def _grid_notes(seq: List[int]):
+    """(start, length, pitch, bars after it) of every Position, Velocity, Pitch, Duration group of seq -- the groups the
+    reference's token-to-MIDI step turns into notes (encoder_utils.py:399-404) -- on the 128-step grid of their own bar."""
+    T = TOKEN_OFFSET
+    seq = [int(t) for t in seq]
+    bars_after = [0] * (len(seq) + 1)
+    for i in range(len(seq) - 1, -1, -1):
+        bars_after[i] = bars_after[i + 1] + (seq[i] == T.BAR)
+    out = []
+    for i in range(len(seq) - 3):
+        if T.POSITION <= seq[i] < T.BPM and T.NOTE_VELOCITY <= seq[i + 1] < T.CHORD_START \
+                and T.PITCH <= seq[i + 2] < T.NOTE_VELOCITY and T.NOTE_DURATION <= seq[i + 3] < T.POSITION:
+            out.append((seq[i] - T.POSITION, seq[i + 3] - T.NOTE_DURATION + 1, seq[i + 2], bars_after[i + 4]))
+    return out
+
+
+def voice_bans(seq: List[int], word: int) -> set:
+    """The ids the voice cap (ForcedDecoder.set_voices, csrc/decode_loop.h: Voices) bans for the token that follows seq.
+    word: -1 off, else N + 256 r.  A note of the current bar or the one before ends at e = min(start + length - 128 * (bars
+    after it), 128) on the current bar's grid.  N >= 1: the positions before the N-th largest end are banned (at every one
+    of them N notes still sound).  r = 1: the pitch of every note that ends past the onset seq is at (0 after a BAR)."""
+    word = int(word)
+    if word < 0:
+        return set()
+    cap, strike = word & 255, (word >> 8) & 1
+    ends = [(min(a + d - 128 * k, 128), p) for a, d, p, k in _grid_notes(seq) if k <= 1]
+    banned = set()
+    if cap >= 1 and len(ends) >= cap:
+        banned |= set(range(TOKEN_OFFSET.POSITION, TOKEN_OFFSET.POSITION + max(sorted(e for e, _ in ends)[-cap], 0)))
+    if strike:
+        at = next((int(t) for t in reversed(seq)
+                   if int(t) == TOKEN_OFFSET.BAR or TOKEN_OFFSET.POSITION <= int(t) < TOKEN_OFFSET.BPM), None)
+        if at is not None:
+            g0 = 0 if at == TOKEN_OFFSET.BAR else at - TOKEN_OFFSET.POSITION
+            banned |= {p for e, p in ends if e > g0}
+    return banned
+
+
+def voices_violation(seq: List[int], start: int, max_voices: int = 0, restrike: bool = True) -> Optional[int]:
+    """The index of the first token seq[i], i >= start, that the voice cap would have banned given seq[:i] (voice_bans with
+    N = max_voices, 0: no cap, and r = restrike): a position at which max_voices notes still sound, or a pitch struck while
+    it sounds.  A banned position that a chord token follows is none: a Position, Chord group starts no note (the rules
+    force `Position 432, Chord` behind a bar whatever still sounds).  None when there is none."""
+    word = int(max_voices) + 256 * int(bool(restrike))
+    for i in range(max(int(start), 0), len(seq)):
+        if int(seq[i]) in voice_bans(seq[:i], word):
+            chord_group = TOKEN_OFFSET.POSITION <= int(seq[i]) < TOKEN_OFFSET.BPM and i + 1 < len(seq) \
+                and TOKEN_OFFSET.CHORD_START <= int(seq[i + 1]) <= TOKEN_OFFSET.CHORD_END
+            if not chord_group:
+                return i
+    return None
+
+
+def max_sounding(seq: List[int], ticks_per_bar: int, start: int = 0):
+    """(most notes sounding at one tick, whether a pitch is struck while it sounds) for the notes of seq that begin at
+    index >= start, in TICKS as the reference's decoder places them (encoder_utils.py:433-442, encoder.py:79-88): onset q of
+    bar k at k * ticks_per_bar + floor(q * ticks_per_bar / 128), a length of d steps d * int(ticks_per_bar / 128) ticks.  A
+    note sounds on [on, off); notes that begin before `start` sound too but are not counted against each other."""
+    T = TOKEN_OFFSET
+    seq = [int(t) for t in seq]
+    unit = int(ticks_per_bar / 128)
+    notes, bar = [], 0          # (every Bar opens the next bar; only the notes' distances matter)
+    for i, t in enumerate(seq):
+        if t == T.BAR:
+            bar += 1
+        if i + 3 < len(seq) and T.POSITION <= t < T.BPM and T.NOTE_VELOCITY <= seq[i + 1] < T.CHORD_START \
+                and T.PITCH <= seq[i + 2] < T.NOTE_VELOCITY and T.NOTE_DURATION <= seq[i + 3] < T.POSITION:
+            on = bar * int(ticks_per_bar) + ((t - T.POSITION) * int(ticks_per_bar)) // 128
+            notes.append((on, on + (seq[i + 3] - T.NOTE_DURATION + 1) * unit, seq[i + 2], i >= start))
+    most, struck = 0, False
+    for k, (on, off, pitch, drawn) in enumerate(notes):
+        if not drawn:
+            continue
+        # (the note order makes onsets non-decreasing: every note that sounds when this one starts came before it)
+        live = [(o, f, p) for o, f, p, _ in notes[:k] if o <= on < f]
+        most = max(most, 1 + len(live))
+        struck = struck or any(p == pitch for _, _, p in live)
+    return most, struck
+
+
 class ForcingReport:
     """What the forcing state machine was asked to place in one sequence and how far it got."""
 
@@ -179,7 +259,7 @@ class InferenceTask:
 
     def execute(self, encoded_meta, max_rounds: Optional[int] = None, return_logprobs: bool = False,
                 prompt: Optional[List[int]] = None, logit_bias=None, grammar=None, harmony=None,
-                class_sampling=None, note_order=None):                                                     # :338-354
+                class_sampling=None, note_order=None, voices=None):                                        # :338-354
         """return_logprobs (not in the reference): (sequences, their log-probability arrays -- ForcedDecoder.logprobs).
         prompt (not in the reference): token ids that follow the meta tokens; every attempt continues them (primed
         generation, BatchedGenerator.generate_stream) and every returned sequence starts with [0] + meta + prompt.
@@ -191,7 +271,9 @@ class InferenceTask:
         class_sampling (not in the reference): a table (generate.class_sampling) or its arguments as a dict -- a
         temperature / top_k / top_p per token class (ForcedDecoder.set_class_sampling).
         note_order (not in the reference): True or a cap of 1 .. 128 notes per position -- inside a bar the drawn
-        positions never go back and no pitch is drawn twice at one position (ForcedDecoder.set_note_order)."""
+        positions never go back and no pitch is drawn twice at one position (ForcedDecoder.set_note_order).
+        voices (not in the reference): a word generate.voices_word(N, r) -- at most N drawn notes sound at once and (r) no
+        pitch is struck while it sounds; switches the note order on (ForcedDecoder.set_voices)."""
         from ..generate import BatchedGenerator
         data = self.input_data
         glen = self.inference_cfg.GENERATION.generation_length
@@ -216,6 +298,9 @@ class InferenceTask:
         # (likewise: generate.py --note_order / --max_notes, the control word; an argument given here wins)
         if note_order is None and getattr(self.inference_cfg.GENERATION, "note_order", None) is not None:
             note_order = int(self.inference_cfg.GENERATION.note_order)
+        # (likewise: generate.py --max_voices / --no_restrike, the voice word)
+        if voices is None and getattr(self.inference_cfg.GENERATION, "voices", None) is not None:
+            voices = int(self.inference_cfg.GENERATION.voices)
         gen = BatchedGenerator(self.model, self.device, glen, mlen, sliding=sliding, kv_dtype=kv_dtype,
                                **({"shared_prompt": True} if share else {}))
 
@@ -238,5 +323,6 @@ class InferenceTask:
                                   **({} if grammar is None else {"grammar": grammar}),
                                   **({} if harmony is None else {"harmony": harmony}),
                                   **({} if class_sampling is None else {"class_sampling": class_sampling}),
-                                  **({} if note_order is None else {"note_order": note_order}))
+                                  **({} if note_order is None else {"note_order": note_order}),
+                                  **({} if voices is None else {"voices": voices}))
         return (res[0], res[2]) if return_logprobs else res[0]

@@ -67,6 +67,14 @@ class ModelInitializeTask:
             word = 0
         if word is not None:
             cfg.GENERATION.note_order = int(word)
+        # generate.py --max_voices / --no_restrike (not in the reference): the voice word N + 256 r (generate.py check_voices)
+        vword = getattr(self.model_args, "voices_word", None)
+        if vword is None and (getattr(self.model_args, "max_voices", None) is not None
+                              or getattr(self.model_args, "no_restrike", False)):      # (a caller that skipped the check)
+            vword = int(getattr(self.model_args, "max_voices", None) or 0) \
+                + (256 if getattr(self.model_args, "no_restrike", False) else 0)
+        if vword is not None:
+            cfg.GENERATION.voices = int(vword)
         # generate.py --decode_slots (not in the reference): attempts decoded side by side (64 unless the key is set)
         if getattr(self.model_args, "decode_slots", None) not in (None, 64):
             cfg.GENERATION.decode_slots = int(self.model_args.decode_slots)

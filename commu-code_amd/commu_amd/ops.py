@@ -934,7 +934,7 @@ def _check_draw_state(kind, device, specs):
 
 def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=None, token=None, probs_out=None,
                 top_p=1.0, logp_out=None, bias=None, V=729, grammar=None, harmony=None, class_ctl=None,
-                note_order=None):
+                note_order=None, voices=None):
     """In-place temperature + softmax + top-k + wrong-token mask + inverse-CDF draw per sequence.
     logits: fp32 [nseq, >=V] (row stride = ld), modified in place (logits[:, 1:V] /= temperature).
     top_p < 1: nucleus filter after the top-k / rejected-token step (an extra mode; the reference has top-k only).
@@ -970,7 +970,12 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
     is at, a pitch its current position already holds, or (n >= 1) the position itself once it holds n notes; the bans
     are read off seq[b][0 : state[b][0]] and replace y by -inf after the harmony term.  One kernel serves it, the class
     kernel's with the scan: class_ctl= is required (a call without class controls passes records that all hold the
-    sequence's triple, generate.class_ctl_records) (commu_sample_args.order_ctl)."""
+    sequence's triple, generate.class_ctl_records) (commu_sample_args.order_ctl).
+    voices: int32 [nseq] on the device of the logits, one control word per sequence (generate.voices_ctl): -1 off, else
+    N + 256 r -- at most N notes of seq[b][0 : state[b][0]] may sound at the onset drawn next (N = 0: no cap), and with r = 1
+    no pitch that still sounds may be drawn.  The bans join the note order's in the same select.  One kernel serves it, the
+    note-order kernel's with the scan continued to the second BAR: note_order= is required
+    (commu_sample_args.voice_ctl)."""
     nseq = logits.shape[0]
     V = int(V)
     assert logits.dtype == F32 and logits.stride(1) == 1
@@ -1027,6 +1032,13 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
         _check_draw_state("note_order", logits.device, (
             (note_order, "controls", torch.int32, "[%d]" % nseq, lambda t: tuple(t.shape) == (nseq,)),))
         a.order_ctl = _p(note_order)
+    if voices is not None:
+        if note_order is None:
+            raise CommuHipError("voices: note_order= expected as well (the one kernel continues the note order's scan; pass "
+                                "words that are all -1 where the note order is off)")
+        _check_draw_state("voices", logits.device, (
+            (voices, "controls", torch.int32, "[%d]" % nseq, lambda t: tuple(t.shape) == (nseq,)),))
+        a.voice_ctl = _p(voices)
     if harmony is not None:
         htable, hon, hstate, chord_tok = harmony
         _check_draw_state("harmony", logits.device, (

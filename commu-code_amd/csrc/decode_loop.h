@@ -178,7 +178,31 @@ struct NoteOrder {
     int ctl;                // the sequence's control as the caller loaded it
 };
 constexpr int ORD_FLAGS = 192;    // LDS flags by token id: 16 lanes * 12 ids >= TOK_PITCH_HI + 1
-template <bool BIAS, bool GRAM = false, bool HARM = false, bool CLS = false, bool ORD = false>
+// VOX (Voices: one int32 control per sequence, -1 off, else N + 256 r with N in 0 .. 128 the voice cap (0: none) and r the
+//   re-strike switch): two more bans read off seq, so that at most N drawn notes sound at once and no pitch is struck while
+//   it sounds.  With S as above, a NOTE is an index i, i + 3 < L, with S[i .. i+3] = POSITION, VELOCITY, PITCH, DURATION; start
+//   a = S[i] - 432, length d = S[i+3] - 303, beta = the BAR tokens in S[i+4 : L], end on the current bar's grid
+//   e = min(a + d - 128 beta, 128); notes with beta >= 2 are ignored (a + d <= 255: they ended before this bar).  CAP (N >= 1):
+//   E = the N-th largest e with multiplicity (0: fewer than N notes, or the value is <= 0); banned: ids 432 .. 432 + E - 1.
+//   RE-STRIKE (r): with j the note order's last breaker and g0 = 0 for BAR, S[j] - 432 else: the pitch of every note with
+//   e > g0.  The bans join the note order's in the same select -- hi = max(hi_order, 432 + E), the pitch sets are united --
+//   so a draw is bit for bit the ORD kernel's with bias[b] = -inf at these ids.
+//   THE SCAN is the note order's, continued to the second BAR from the end (or index 0): the trip count stays wave-uniform.
+//   Lane l holds S[idx], idx = start - l, and with VOX also S[idx-1 .. idx-3] (three more clamped loads from the same lines;
+//   a note is seen by the lane that holds its DURATION, so a note that straddles a chunk seam needs nothing special).  beta
+//   is v_mbcnt of the chunk's BAR ballot (the BARs in lower lanes, i.e. at higher indices) plus a scalar carry from the
+//   chunks before.  E FOR EVERY N goes through a 128-bin LDS histogram of the ends 1 .. 128, highest end first: each lane reads
+//   two bins, one wscan_i gives #{e > g} for its two grid steps, and E is the smallest g with #{e > g} < N (a wmin_i).
+//   THE PITCH SET has flags of its own (the note order's are gated by the note order's switch, these by r).  A lane needs g0
+//   when it writes its flag: the first ballot of the chunk has run by then, and while it has found no breaker the lane's own
+//   POSITION (in the next chunk) is j, its note starts at g0 and sounds.  N, r, E and g0 stay in scalar registers; an off
+//   word runs the same scan and bans nothing.  VOX needs ORD.
+struct Voices {
+    int ctl;                // the sequence's control as the caller loaded it
+};
+constexpr int VOX_BINS = 128;     // LDS histogram of the note ends: slot 128 - e for e in 1 .. 128 (lane l reads slots 2l, 2l + 1)
+constexpr int TOK_VEL_LO = 131, TOK_VEL_HI = 194, TOK_DUR_LO = 304, TOK_DUR_HI = 431;
+template <bool BIAS, bool GRAM = false, bool HARM = false, bool CLS = false, bool ORD = false, bool VOX = false>
 __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restrict__ logits, int ld, int V,
                                                  const unsigned char* __restrict__ wrong, int ldw,
                                                  const float* __restrict__ uni,
@@ -190,9 +214,10 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
                                                  Grammar g = Grammar{nullptr, 0, nullptr, 0, 0, 0},
                                                  Harmony h = Harmony{nullptr, 0, nullptr, 0, 0, 0},
                                                  ClassControls cc = ClassControls{nullptr},
-                                                 NoteOrder no = NoteOrder{-1}) {
+                                                 NoteOrder no = NoteOrder{-1}, Voices vx = Voices{-1}) {
     static_assert(!CLS || GRAM, "the class key is the grammar's previous token");
     static_assert(!ORD || CLS, "one note-order instantiation: the class kernel's with the scan");
+    static_assert(!VOX || ORD, "one voices instantiation: the note-order kernel's with the longer scan");
     float* lg = logits + (size_t)b * ld;
     // The optional per-sequence inputs -- the active flag and this sequence's controls -- are loaded unconditionally: a null
     // array reads a valid word of this sequence instead (token[b], logits[b][0]), which is then ignored.  So they are in
@@ -217,6 +242,12 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
     if constexpr (ORD) {
         olen = min(max(g.len, 0), g.ld_seq);
         otok = g.seq_row[max(olen - 1 - lane, 0)];
+    }
+    int vt1 = 0, vt2 = 0, vt3 = 0;          // (VOX) the three tokens before the lane's: seq[L - 2 - l], [L - 3 - l], [L - 4 - l]
+    if constexpr (VOX) {
+        vt1 = g.seq_row[max(olen - 2 - lane, 0)];
+        vt2 = g.seq_row[max(olen - 3 - lane, 0)];
+        vt3 = g.seq_row[max(olen - 4 - lane, 0)];
     }
     int chord = 0;                // (HARM) the last chord placed, chord_tok[b][F_CUR - 1]: likewise one word for all lanes
     if constexpr (HARM) chord = h.chord_row[min(max(h.cur, 1), h.ld_chord) - 1];
@@ -278,9 +309,25 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
         for (int q = 0; q < 3; ++q) oflag[lane + 64 * q] = 0;
         int start = __builtin_amdgcn_readfirstlane(olen) - 1;         // seq index of lane 0 of the chunk
         int pos = 0, n = 0, phase = 0;          // phase 0: looking for j; 1: p known, looking for s; 2: the run is complete
-        auto chunk = [&](int t) {
+        // (VOX) the ends' histogram, the sounding pitches' flags and the BARs passed in the chunks so far
+        int *vflag = nullptr, *vhist = nullptr;
+        int nbar = 0;
+        if constexpr (VOX) {
+            static_assert(VOX_BINS == 2 * 64, "two bins per lane");
+            __shared__ __attribute__((aligned(16))) int vflag_lds[ORD_FLAGS];
+            __shared__ __attribute__((aligned(8))) int vhist_lds[VOX_BINS];
+            vflag = vflag_lds;
+            vhist = vhist_lds;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) vflag[lane + 64 * q] = 0;
+#pragma unroll
+            for (int q = 0; q < VOX_BINS / 64; ++q) vhist[lane + 64 * q] = 0;
+        }
+        auto chunk = [&](int t, int t1 = 0, int t2 = 0, int t3 = 0) {
             const bool valid = start - lane >= 0;
             const bool brk = valid & ((t == TOK_BAR) | ((unsigned)(t - TOK_POS0) < (unsigned)POS_RES));
+            bool ran = false;                   // (VOX) the run was complete before this chunk: none of its lanes is in it
+            if constexpr (VOX) ran = phase == 2;
             if (phase == 0) {
                 const unsigned long long m = __ballot(brk);
                 if (m != 0ull) {
@@ -298,22 +345,71 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
                     phase = 2;
                 }
             }
+            if constexpr (VOX) take = ran ? 0ull : take;
             const bool hit = valid & ((unsigned)(t - TOK_PITCH_LO) <= (unsigned)(TOK_PITCH_HI - TOK_PITCH_LO)) &
                              (((take >> lane) & 1ull) != 0ull);
             n += __popcll(__ballot(hit));
             if (hit) oflag[t] = 1;
+            if constexpr (VOX) {
+                // the lane that holds a note's DURATION sees the note (index start - lane - 3 >= 0: the clamped loads
+                // of the lanes below that are not looked at)
+                const unsigned long long bars = __ballot(valid & (t == TOK_BAR));
+                const int beta = nbar + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bars >> 32),
+                                                                       __builtin_amdgcn_mbcnt_lo((unsigned)bars, 0u));
+                const bool note = (start - lane - 3 >= 0) & ((unsigned)(t - TOK_DUR_LO) <= (unsigned)(TOK_DUR_HI - TOK_DUR_LO)) &
+                                  ((unsigned)(t1 - TOK_PITCH_LO) <= (unsigned)(TOK_PITCH_HI - TOK_PITCH_LO)) &
+                                  ((unsigned)(t2 - TOK_VEL_LO) <= (unsigned)(TOK_VEL_HI - TOK_VEL_LO)) &
+                                  ((unsigned)(t3 - TOK_POS0) < (unsigned)POS_RES) & (beta <= 1);
+                const int end = min((t3 - TOK_POS0) + (t - (TOK_DUR_LO - 1)) - POS_RES * beta, POS_RES);
+                if (note & (end >= 1)) atomicAdd(&vhist[VOX_BINS - end], 1);
+                // (phase 0 here: no breaker down to this chunk's last index, so this note's POSITION is j itself)
+                const int g0 = pos == TOK_BAR ? 0 : pos - TOK_POS0;
+                if (note & ((phase == 0) | (end > g0))) vflag[t1] = 1;
+                nbar += __popcll(bars);
+            }
             start -= 64;
         };
         // chunk 0 in straight-line code: its load went out beside the previous token's and has long arrived (as compiled
         // the scan starts behind the rejected-token map's wait, which is for every load of the step: what the scan costs is
         // its instructions, not a memory round trip)
-        chunk(otok);
+        if constexpr (VOX) {
+            __builtin_amdgcn_s_waitcnt(0xc07f);  // (the zeroes before the first atomic: one wave, LDS completes in order)
+            chunk(otok, vt1, vt2, vt3);
+            // (the run is complete at the first BAR from the end at the latest: the second BAR, or index 0, ends both)
 #pragma unroll 1
-        while (phase != 2 && start >= 0) chunk(g.seq_row[max(start - lane, 0)]);
+            while ((phase != 2 || nbar < 2) && start >= 0)
+                chunk(g.seq_row[max(start - lane, 0)], g.seq_row[max(start - lane - 1, 0)],
+                      g.seq_row[max(start - lane - 2, 0)], g.seq_row[max(start - lane - 3, 0)]);
+        } else {
+            chunk(otok);
+#pragma unroll 1
+            while (phase != 2 && start >= 0) chunk(g.seq_row[max(start - lane, 0)]);
+        }
         __builtin_amdgcn_s_waitcnt(0xc07f);      // lgkmcnt(0): one wave, LDS operations complete in order
         const int ctl = __builtin_amdgcn_readfirstlane(no.ctl);
         const bool on = ctl >= 0 && phase != 0 && pos != TOK_BAR;
-        const int hi = on ? pos + ((ctl >= 1 && n >= ctl) ? 1 : 0) : TOK_POS0;         // positions [432, hi) are banned
+        int hi = on ? pos + ((ctl >= 1 && n >= ctl) ? 1 : 0) : TOK_POS0;               // positions [432, hi) are banned
+        unsigned vdm = 0u;                       // (VOX) the lane's ids among the sounding pitches
+        if constexpr (VOX) {
+            const int vctl = __builtin_amdgcn_readfirstlane(vx.ctl);
+            const int cap = vctl >= 0 ? (vctl & 255) : 0, strike = vctl >= 0 ? ((vctl >> 8) & 1) : 0;
+            // lane l holds the bins of the ends 128 - 2l and 127 - 2l: `before` notes end past 128 - 2l, before + h.x past
+            // 127 - 2l, incl past 126 - 2l; the count falls with g, so the smallest g that leaves fewer than N is the
+            // lowest any lane can offer (none: 128, where the count is 0)
+            const int2 hb = *reinterpret_cast<const int2*>(vhist + 2 * lane);
+            const int incl = wscan_i(hb.x + hb.y, lane), before = incl - (hb.x + hb.y);
+            const int mine = incl < cap ? 126 - 2 * lane : (before + hb.x < cap ? 127 - 2 * lane : POS_RES);
+            const int E = cap >= 1 ? wmin_i(mine) : 0;
+            hi = max(hi, TOK_POS0 + E);
+            const int4* vq = reinterpret_cast<const int4*>(vflag + min(base, ORD_FLAGS - PER_LANE));
+#pragma unroll
+            for (int q = 0; q < PER_LANE / 4; ++q) {
+                const int4 f4 = vq[q];
+                vdm |= ((unsigned)f4.x << (4 * q)) | ((unsigned)f4.y << (4 * q + 1)) | ((unsigned)f4.z << (4 * q + 2)) |
+                       ((unsigned)f4.w << (4 * q + 3));
+            }
+            vdm = (strike != 0 && base < ORD_FLAGS) ? vdm : 0u;
+        }
         // the lane's 12 flags as 16-byte LDS reads, unconditional (the lanes past the flags read the last owner's and
         // drop them), packed into a bit mask without a branch: behind a branch per element they were 12 dependent LDS
         // round trips and some 200 instructions
@@ -328,6 +424,7 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
         const int lo_e = min(max(TOK_POS0 - base, 0), PER_LANE), hi_e = min(max(hi - base, 0), PER_LANE);
         const unsigned pm = ((1u << hi_e) - 1u) & ~((1u << lo_e) - 1u);          // (empty while hi <= 432)
         omask = pm | ((on && base < ORD_FLAGS) ? dm : 0u);
+        if constexpr (VOX) omask |= vdm;
     }
     if (active != nullptr && act_row == 0) return -2;
     // ---- calc_probs

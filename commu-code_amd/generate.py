@@ -21,6 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 DECODE_SLOTS_MIN, DECODE_SLOTS_MAX, DECODE_SLOTS_DEFAULT = 1, 256, 64          # --decode_slots
 MAX_NOTES_MIN, MAX_NOTES_MAX = 1, 128                                             # --max_notes
+MAX_VOICES_MIN, MAX_VOICES_MAX = 1, 128                                           # --max_voices
 
 
 def parse_args():
@@ -77,13 +78,27 @@ def parse_args():
     # not in the reference (whose sampler may step back inside a bar or put one pitch twice on one onset -- its training
     # data, sorted by start time with one Position token per note, never does): inside a bar the DRAWN positions never go
     # back and no pitch is drawn twice at one position; --max_notes N (1 .. 128, implies --note_order) also stops a position
-    # from being drawn again once it holds N notes (1: one note per onset).  Not enforced: overlapping durations, the order
+    # from being drawn again once it holds N notes (1: one note per onset).  Overlapping durations are --max_voices' business; not enforced: the order
     # inside --prompt_tokens, forced tokens.  Combines with every other option, --parity included.
     model_arg_parser.add_argument("--note_order", action="store_true",
                                   help="note order: inside a bar drawn positions never go back and no note is doubled")
     model_arg_parser.add_argument("--max_notes", default=None, metavar="N",
                                   help=f"at most N notes per position, {MAX_NOTES_MIN} .. {MAX_NOTES_MAX} (implies --note_order; "
                                        "1 = one note per onset)")
+    # not in the reference (whose token-to-MIDI step turns every Position, Velocity, Pitch, Duration group into a note
+    # [start, start + duration) and lets them overlap): --max_voices N (1 .. 128) -- among the DRAWN notes at most N sound at
+    # any tick (1: a monophonic line, for a bass or melody track); --no_restrike -- no drawn pitch is struck while the same
+    # pitch still sounds (the first note-off would silence the second note).  Both imply --note_order.  Not covered: notes
+    # inside --prompt_tokens against each other, anything a forced token starts; a strict --harmony or pitch range that
+    # leaves no pitch free ends that attempt (as with --max_notes).  When the rest of a bar is taken only Bar and EOS remain.
+    model_arg_parser.add_argument("--max_voices", default=None, metavar="N",
+                                  help=f"at most N drawn notes sound at once, {MAX_VOICES_MIN} .. {MAX_VOICES_MAX} (implies "
+                                       "--note_order; 1 = a monophonic line).  Not covered: notes inside --prompt_tokens "
+                                       "against each other, anything a forced token starts; a strict --harmony or pitch "
+                                       "range that leaves no pitch free ends that attempt")
+    model_arg_parser.add_argument("--no_restrike", action="store_true",
+                                  help="no drawn pitch is struck while it still sounds (implies --note_order; covers what "
+                                       "--max_voices covers)")
     # not in the reference (which decodes one sequence at a time): how many attempts are decoded side by side.  1 .. 256;
     # up to 256 slots run the fused layer-tail launches ("Supported shapes").  The sequences returned do
     # not depend on it.  (checked by check_decode_slots: the range is named in its message)
@@ -185,6 +200,27 @@ def check_note_order(model_args):
     return word
 
 
+def check_voices(model_args):
+    """--max_voices / --no_restrike as the voice control word N + 256 r (None: neither flag); host code only, ValueError
+    that names the range.  Written back to model_args.voices_word, which travels to the replicas (ModelInitializeTask puts
+    it into the inference configuration); either flag switches --note_order on."""
+    v = getattr(model_args, "max_voices", None)
+    n = 0
+    if v is not None:
+        try:
+            n = int(v) if not isinstance(v, (bool, float)) else None
+        except (TypeError, ValueError):
+            n = None
+        if n is None or not MAX_VOICES_MIN <= n <= MAX_VOICES_MAX:
+            raise ValueError(f"--max_voices: an integer in [{MAX_VOICES_MIN}, {MAX_VOICES_MAX}] expected, got {v!r}")
+    word = None
+    if v is not None or getattr(model_args, "no_restrike", False):
+        word = n + (256 if getattr(model_args, "no_restrike", False) else 0)
+        model_args.note_order = True
+    model_args.voices_word = word
+    return word
+
+
 def read_constraints(path=None, pitch_min=None, pitch_max=None):
     """The constraint row of --logit_bias / --pitch_min / --pitch_max (None when none of them is given); host code only,
     raises (commu_amd.generate.CommuHipError, ValueError) on a malformed file or an empty range."""
@@ -271,6 +307,7 @@ def main(model_args, input_args, training_cfg=None, device_indices=None):
     import torch
     check_share_prompt(model_args, input_args)          # (refused before a model is loaded or a replica started)
     check_decode_slots(model_args)                      # (likewise)
+    check_voices(model_args)                            # (likewise; ahead of the note order, which it switches on)
     check_note_order(model_args)                        # (likewise)
     in_args = dict(vars(input_args))
     max_rounds = in_args.pop("max_rounds", None)

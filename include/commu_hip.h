@@ -497,6 +497,25 @@ int commu_transpose_heads(const void* src, int ld, const float* bias, void* dst,
  *     without class controls passes a table whose eight records all hold the sequence's triple).  Validating the words is
  *     the caller's job (generate.note_order_ctl).  The same field, with the same meaning and the same refusal, ends
  *     commu_decode_loop_args.  Null: the launch that never heard of it.
+ * VOICE CAP (the reference's token-to-MIDI step turns every Position, Velocity, Pitch, Duration group into a note
+ * [start, start + duration); its sampler does not keep notes from overlapping, nor a pitch from being struck while it sounds)
+ *   voice_ctl: int32 [nseq], one control word per sequence: -1 off, else N + 256 r with N in 0 .. 128 the cap (0: none)
+ *     and r in {0, 1} (1: no re-striking).  Defined on seq alone when the stage runs, with L and S as for order_ctl.  A NOTE
+ *     is an index i, i + 3 < L, with S[i], S[i+1], S[i+2], S[i+3] = POSITION (432 .. 559), VELOCITY (131 .. 194), PITCH
+ *     (3 .. 130), DURATION (304 .. 431): start a = S[i] - 432, length d = S[i+3] - 303, pitch S[i+2], beta the number of BAR
+ *     tokens in S[i+4 : L], end on the current bar's grid e = min(a + d - 128 beta, 128).  Notes with beta >= 2 are ignored
+ *     (a + d <= 255: they end before the current bar), so the walk stops at the second BAR from the end.  CAP (N >= 1): E is
+ *     the N-th largest e over the notes with beta <= 1, with multiplicity, 0 when there are fewer than N or the value is
+ *     <= 0; BANNED: ids 432 .. 432 + E - 1.  RE-STRIKE (r = 1): with j as for order_ctl (none: nothing) and g0 = 0 for BAR,
+ *     S[j] - 432 else; BANNED: the pitch id of every note with beta <= 1 and e > g0.  The bans join order_ctl's in the same
+ *     select (positions [432, max of the two ends), the pitch sets united), so all that is said there holds: before top-k,
+ *     never written back, probs_out exactly 0, `full` the log-softmax of y, token -1 when nothing is left.  A draw is BIT
+ *     FOR BIT the draw of the call without voice_ctl and with bias[b] = -inf at these ids; an off word, or one that bans
+ *     nothing, is bit for bit the call without the field.  With order_ctl[b] >= 0 every known note starts at or before any
+ *     onset that can still be drawn, which is what makes one range enough; voice_ctl itself does not look at order_ctl[b].
+ *     ONE kernel serves it, the note-order kernel with the longer walk: voice_ctl requires order_ctl and everything
+ *     order_ctl requires, else -22.  Validating the words is the caller's job (generate.voices_ctl).  The same field, with
+ *     the same meaning and the same refusal, is in commu_decode_loop_args.  Null: the launch that never heard of it.
  * WHAT gram / harm READ
  *   state: the forcing records, int32 [nseq][commu_forcing_state_ints()]; seq int32 [nseq][ld_seq]; chord_tok int32
  *   [nseq][ld_chord].  Not looked at, and may be null, in a call without gram and harm.
@@ -538,6 +557,8 @@ typedef struct commu_sample_args {
     int ld_seq, ld_chord;
     /* note order (placed ahead of cls_ctl, which stays the struct's last field) */
     const int* order_ctl;
+    /* voice cap (likewise ahead of cls_ctl) */
+    const int* voice_ctl;
     /* class-keyed controls */
     const void* cls_ctl;
 } commu_sample_args;
@@ -759,6 +780,8 @@ typedef struct commu_decode_loop_args {
     int ld_bias, ld_gram, ld_harm;
     /* note order (commu_sample_args.order_ctl; likewise ahead of cls_ctl) */
     const int* order_ctl;
+    /* voice cap (commu_sample_args.voice_ctl; likewise ahead of cls_ctl) */
+    const int* voice_ctl;
     /* class-keyed controls (commu_sample_args.cls_ctl) */
     const void* cls_ctl;
 } commu_decode_loop_args;
