@@ -11,7 +11,9 @@ divided by the temperature when the previous draw was a rejected chord, quirk Q5
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
+import dataclasses
 import math
 from typing import List, Optional, Sequence
 
@@ -1792,6 +1794,219 @@ class ForcedDecoder:
             else:
                 self.trace[b].zero_()
 
+    # ---- request pool: a slot armed for ANY request.  What load() writes for all slots at once -- conditioning K/V
+    # rows, chord rows, state record, sequence head, per-slot controls -- is composed ONCE per request into an entry of
+    # a device-side request store (admit) and moved into the slots by ONE launch per poll window (arm,
+    # commu_decode_arm), between two graph replays.  A decoder that never calls pool_open() allocates none of this and
+    # launches what it always launched.
+    def pool_open(self, n_cond: int):
+        """Every slot idle (a finished record that decodes nothing), the store of Rcap = B entries allocated on first
+        use: the state a pool starts from instead of load().  n_cond: the number of conditioning tokens of every request
+        of the pool."""
+        if self.max_prompt > 0 or self.shared_prompt:
+            raise CommuHipError("request pool: primed and shared-prompt decoders are not served (a primed image needs a "
+                                "per-request replay)")
+        if self.state.parity:
+            raise CommuHipError("request pool: the fp32 parity mode (model.parity_fp32) has a third cache layout that the "
+                                "arm launch does not copy")
+        n_cond = int(n_cond)
+        if n_cond < 1 or n_cond + 1 > self.n_ctx_max:
+            raise CommuHipError(f"encoded_meta: 1 .. {self.n_ctx_max - 1} conditioning tokens expected, got {n_cond}")
+        if self.sliding and self.state.window < n_cond:
+            raise CommuHipError(f"request pool: a sliding window of {self.state.window} positions is shorter than the context "
+                                f"of {n_cond} tokens")
+        self._first_use(rows=True)          # (requests differ in their triples: the array launches from the start)
+        B, st, dev = self.B, self.state, self.dev
+        self.n_cond, self.klen0, self._primed, self._last_load = n_cond, n_cond, None, None
+        if getattr(st, "t_err", None) is not None:
+            st.t_err.zero_()
+        for t in st.cache_tensors():
+            t.zero_()
+        st.repack()
+        idle = np.zeros((B, self.NF), dtype=np.int32)
+        idle[:, 0], idle[:, 1], idle[:, 5] = 1, -1, 1          # len 1 (seq[0] = 0), nothing forced, done
+        self.fsm.copy_(torch.from_numpy(idle))
+        self.seq.zero_()
+        self.seq_logp.fill_(float("nan"))
+        self.logp.fill_(float("nan"))
+        self.wrong.zero_()
+        st.klen.zero_()
+        if self.trace is not None:
+            self.trace.zero_()
+        self.reports = [None] * B
+        if getattr(self, "_pool", None) is None:
+            R, i32, u8 = B, torch.int32, torch.uint8
+            z = lambda *shape, dtype=i32: torch.zeros(*shape, dtype=dtype, device=dev)
+            hdr = (2 * B + 3) // 4 * 4          # the jobs, padded so that the variates start at a 16-byte boundary
+            words = hdr + B * self.ld_u
+            self._pool = {
+                "image": tuple(z(t.shape[0], R, t.shape[2], self.n_ctx_max, t.shape[4], dtype=t.dtype)
+                               for t in st.cache_tensors()),
+                "e_klen0": z(R), "e_state": z(R, self.NF), "e_seq": z(R, self.n_ctx_max),
+                "e_chord_tok": z(R, self.ld_chord), "e_chord_pos": z(R, self.ld_chord),
+                "e_temperature": z(R, dtype=F32), "e_top_k": z(R), "e_top_p": z(R, dtype=F32),
+                "e_bias": z(R, VPAD, dtype=F32), "e_gram_on": z(R, dtype=u8), "e_harm_on": z(R, dtype=u8),
+                "e_order": torch.full((R,), NOTE_ORDER_OFF, dtype=i32, device=dev),
+                "e_voice": torch.full((R,), VOICES_OFF, dtype=i32, device=dev), "e_cls": z(R, N_CLASSES + 1, 4),
+                "hdr": hdr, "stage": z(words),
+                # two pinned staging buffers and an event each: the host never overwrites a buffer whose copy is in flight
+                "pin": [torch.zeros(words, dtype=i32).pin_memory() for _ in range(2)],
+                "ev": [None, None], "turn": 0, "args": None, "sig": None,
+                "one": torch.ones(1, dtype=i32, device=dev),
+                "meta": [None] * R,          # per entry: (n_chords, num_measures) for the slots' reports
+            }
+
+    def _pool_args(self):
+        """The arm launch's argument block, rebuilt when an optional array was allocated since (a null twin: not written)."""
+        P = self._pool
+        opt = (self.bias, self.gram_on, self.harm_on, self.order_ctl, self.voice_ctl, self.cls_ctl, self.trace)
+        sig = tuple(None if t is None else t.data_ptr() for t in opt)
+        if P["args"] is None or P["sig"] != sig:
+            st = self.state
+            on = lambda t, e: {} if t is None else e
+            P["args"] = ops.decode_arm_args(
+                st.cache_tensors(), P["image"], jobs=P["stage"], variates=P["stage"][P["hdr"]:].view(F32),
+                klen=st.klen, e_klen0=P["e_klen0"], state=self.fsm, e_state=P["e_state"], nf=self.NF,
+                seq=self.seq, e_seq=P["e_seq"], ld_seq=self.ld_seq, ld_head=self.n_ctx_max,
+                chord_tok=self.chord_tok, chord_pos=self.chord_pos, e_chord_tok=P["e_chord_tok"],
+                e_chord_pos=P["e_chord_pos"], ld_chord=self.ld_chord, wrong=self.wrong, ld_wrong=self.wrong.stride(0),
+                utable=self.utable, ld_u=self.ld_u, seq_logp=self.seq_logp, trace=self.trace, ld_trace=self.ld_trace,
+                temperature_rows=self.temperature_rows, top_k_rows=self.top_k_rows, top_p_rows=self.top_p_rows,
+                e_temperature=P["e_temperature"], e_top_k=P["e_top_k"], e_top_p=P["e_top_p"],
+                **on(self.bias, {"bias": self.bias, "e_bias": P["e_bias"], "ld_bias": VPAD}),
+                **on(self.gram_on, {"gram_on": self.gram_on, "e_gram_on": P["e_gram_on"]}),
+                **on(self.harm_on, {"harm_on": self.harm_on, "e_harm_on": P["e_harm_on"]}),
+                **on(self.order_ctl, {"order_ctl": self.order_ctl, "e_order": P["e_order"]}),
+                **on(self.voice_ctl, {"voice_ctl": self.voice_ctl, "e_voice": P["e_voice"]}),
+                **on(self.cls_ctl, {"cls_ctl": self.cls_ctl, "e_cls": P["e_cls"]}))
+            P["sig"] = sig
+        return P["args"]
+
+    def admit(self, entry: int, encoded_meta: Sequence[int], input_data, sampling=None, logit_bias=None, grammar=False,
+              harmony=False, note_order=None, voices=None, class_table=None):
+        """Compose store entry `entry` for a request and upload it with its K/V image: the state record, sequence head
+        and chord rows as load() builds them, klen0 = n_cond, the sampling triple (None: the decoder's), the bias row
+        (None: zeros), the grammar and harmony switches (they switch on what the decoder has a table for), the
+        note-order and voice words (None: off) and, where the decoder has class records, the request's record row
+        (class_table: its NaN-table, None: the base triple in every record).  The image is written by ONE memory-less
+        forward over this request's single column [n_cond, 1] and the prefill scatter of the cache's format into the
+        store: it does not depend on what else is admitted or decoding.  Everything is ordered on the current stream."""
+        P = getattr(self, "_pool", None)
+        if P is None:
+            raise CommuHipError("admit: pool_open() first")
+        entry, n_cond = int(entry), self.n_cond
+        if entry < 0 or entry >= self.B:
+            raise CommuHipError(f"admit: store entries are 0 .. {self.B - 1}, got {entry}")
+        if len(encoded_meta) != n_cond:
+            raise CommuHipError(f"encoded_meta: the pool was opened for {n_cond} conditioning tokens, got {len(encoded_meta)}")
+        t, k, p = sampling_rows(1, *((self.temperature, self.top_k, self.top_p) if sampling is None else sampling))
+        bias = None if logit_bias is None else logit_bias_rows(logit_bias, 1)[0]
+        order = note_order_ctl(note_order, 1)
+        vox = voices_ctl(voices, 1)
+        if grammar and (self.gram is None or self._gram_host is None):
+            raise CommuHipError("admit: grammar switched on, but the decoder has no grammar table (set_grammar)")
+        if harmony and (self.harm is None or self._harm_host is None):
+            raise CommuHipError("admit: harmony switched on, but the decoder has no harmony table (set_harmony)")
+        if bias is not None and self.bias is None:
+            raise CommuHipError("admit: a logit bias, but the decoder has no bias rows (set_logit_bias)")
+        if order[0] != NOTE_ORDER_OFF and self.order_ctl is None:
+            raise CommuHipError("admit: note order switched on, but the decoder has no note-order words (set_note_order)")
+        if vox[0] != VOICES_OFF and self.voice_ctl is None:
+            raise CommuHipError("admit: a voice cap, but the decoder has no voice words (set_voices)")
+        if vox[0] != VOICES_OFF and order[0] == NOTE_ORDER_OFF:
+            order[0] = 0                      # (set_voices: the voice cap relies on the note order, word 0 = no cap)
+        if class_table is not None and self.cls_ctl is None:
+            raise CommuHipError("admit: a class table, but the decoder has no class records (set_class_sampling)")
+        comps = input_data.chord_token_components
+        ct, cp = list(comps["chord_token"]), list(comps["chord_position"])
+        if len(ct) != len(cp):
+            raise AssertionError("Wrong Chord Length")                      # midi_inferrer.py:27
+        if len(ct) > self.ld_chord:
+            raise CommuHipError(f"{len(ct)} chords > max_chords={self.ld_chord}")
+        nm = float(input_data.num_measures)
+        rep = ForcingReport(len(ct), nm)
+        P["meta"][entry] = (len(ct), nm)
+        up = lambda dst, a: dst.copy_(torch.from_numpy(np.ascontiguousarray(a)))
+        up(P["e_state"][entry], np.array([1 + n_cond, -1, 0, 1, int(nm % 4 == 0), 0, 0, 0, 0, len(ct), 0,
+                                          int(rep.length_fit), 0, 0], dtype=np.int32))
+        head = np.zeros(self.n_ctx_max, dtype=np.int32)
+        head[1:1 + n_cond] = list(encoded_meta)
+        up(P["e_seq"][entry], head)
+        chords = np.zeros((2, self.ld_chord), dtype=np.int32)
+        chords[0, :len(ct)], chords[1, :len(cp)] = ct, cp
+        up(P["e_chord_tok"][entry], chords[0])
+        up(P["e_chord_pos"][entry], chords[1])
+        P["e_temperature"][entry].fill_(t[0].item())
+        P["e_top_k"][entry].fill_(int(k[0]))
+        P["e_top_p"][entry].fill_(p[0].item())
+        if self.bias is not None:
+            if bias is None:
+                P["e_bias"][entry].zero_()
+            else:
+                up(P["e_bias"][entry], bias)
+        P["e_gram_on"][entry].fill_(1 if grammar else 0)
+        P["e_harm_on"][entry].fill_(1 if harmony else 0)
+        P["e_order"][entry].fill_(int(order[0]))
+        P["e_voice"][entry].fill_(int(vox[0]))
+        if self.cls_ctl is not None:
+            tab = np.full((1, N_CLASSES + 1, 3), np.nan) if class_table is None else class_sampling_table(class_table)[None]
+            rec = class_ctl_records(tab, [t, k, p])
+            up(P["e_cls"][entry], rec.view(np.int32).reshape(N_CLASSES + 1, 4))
+        # the image: one forward over the request's own column, scattered into the store as into a cache of Rcap slots
+        # with n_ctx_max rows (rows = positions: the context is shorter than any ring)
+        ctx = torch.tensor([[0] + [int(x) for x in encoded_meta[:n_cond - 1]]], dtype=torch.long).t().contiguous().to(self.dev)
+        _, _, qkvs = self.model._run_forward(ctx, None, None, None, need_grad=False, want_logits=True, want_kv=True)
+        lens = P["one"] * n_cond
+        slot = P["one"] * entry
+        img = P["image"]
+        for i, qkv in enumerate(qkvs):
+            q2 = qkv.view(n_cond, -1)
+            if self.state.kv_dtype == "fp8":
+                ops.decode_prefill_scatter_kv8(q2, n_cond, img[0][i], img[1][i], img[2][i], img[3][i], P["e_klen0"], lens, slot)
+            else:
+                ops.decode_prefill_scatter(q2, n_cond, img[0][i], img[1][i], P["e_klen0"], lens, slot)
+
+    def arm(self, jobs):
+        """Arm slots for the window: jobs is a list of (slot, entry, variates row or None), distinct slots.  The jobs and
+        their variates are staged in pinned memory, copied to the device block by ONE non-blocking copy, and ONE
+        commu_decode_arm launch moves each entry into its slot -- K/V image, klen, record, sequence head, chords,
+        variates, controls; wrong zeroed, seq_logp NaN, trace zeroed.  self.reports[slot] becomes the new attempt's.  No
+        synchronisation: an armed slot sits out the iteration in flight and starts with the next one, as after rearm()."""
+        P = getattr(self, "_pool", None)
+        if P is None:
+            raise CommuHipError("arm: pool_open() first")
+        jobs = list(jobs)
+        if not jobs:
+            return
+        slots = [int(j[0]) for j in jobs]
+        if len(set(slots)) != len(slots) or min(slots) < 0 or max(slots) >= self.B:
+            raise CommuHipError(f"arm: distinct slots in [0, {self.B}) expected, got {slots}")
+        for _, e, _ in jobs:
+            if not 0 <= int(e) < self.B or P["meta"][int(e)] is None:
+                raise CommuHipError(f"arm: store entry {e} was not admitted")
+        args = self._pool_args()
+        turn = P["turn"]
+        P["turn"] = 1 - turn
+        if P["ev"][turn] is not None:
+            P["ev"][turn].synchronize()          # (the copy out of this buffer two arms ago: long done)
+        pin = P["pin"][turn].numpy()
+        n, hdr, ld_u = len(jobs), P["hdr"], self.ld_u
+        pin[:2 * n] = np.array([(int(s), int(e)) for s, e, _ in jobs], dtype=np.int32).reshape(-1)
+        uni = pin[hdr:hdr + n * ld_u].view(np.float32).reshape(n, ld_u)
+        for j, (_, _, u) in enumerate(jobs):
+            uni[j] = 0.5
+            if u is not None:
+                m = min(len(u), ld_u)
+                uni[j, :m] = u[:m]
+        words = hdr + n * ld_u
+        P["stage"][:words].copy_(P["pin"][turn][:words], non_blocking=True)
+        if P["ev"][turn] is None:
+            P["ev"][turn] = torch.cuda.Event()
+        P["ev"][turn].record()
+        ops.decode_arm(args, n)
+        for s, e, _ in jobs:
+            self.reports[int(s)] = ForcingReport(*P["meta"][int(e)])
+
     def harvest(self, b: int, fsm_row):
         """Token list of slot b (None where nothing could be drawn, Q12) from its downloaded state record."""
         self.reports[b].consumed = int(fsm_row[10])
@@ -1911,6 +2126,127 @@ class ForcedDecoder:
         fsm = self.fsm.cpu().numpy()
         lp = self.seq_logp.cpu().numpy()
         return [None if fsm[b, 6] else lp[b, :fsm[b, 0]].copy() for b in range(self.B)]
+
+
+@dataclasses.dataclass
+class PoolRequest:
+    """One request of BatchedGenerator.generate_pool: what generate_stream takes for it alone.  accept: a callable
+    (seq, report) -> bool, None accepts every sequence that is not None; logit_bias: one row; grammar / harmony: a
+    per-request bool (None: on where the pool has a table), they may only switch on what the pool has a table for;
+    note_order / voices: as generate_stream's."""
+    encoded_meta: Sequence[int]
+    input_data: object
+    need: int
+    temperature: float
+    top_k: int
+    top_p: float = 1.0
+    seed: int = 0
+    max_attempts: Optional[int] = None
+    accept: Optional[object] = None
+    logit_bias: Optional[object] = None
+    grammar: Optional[bool] = None
+    harmony: Optional[bool] = None
+    note_order: Optional[object] = None
+    voices: Optional[object] = None
+
+
+PoolResult = collections.namedtuple("PoolResult", ["sequences", "attempts_started", "logprobs"])
+PoolJob = collections.namedtuple("PoolJob", ["slot", "request", "attempt", "entry", "admit"])
+
+
+class PoolSchedule:
+    """Which attempt of which request a free decode slot takes: the policy of generate_pool, host only.
+
+    Requests are served in list order: a free slot takes the next attempt of the EARLIEST request that still wants one.
+    A request wants an attempt while in_flight + accepted < need and started < max_attempts; attempts are numbered
+    0, 1, 2, ... per request.  A request is decided when nothing of it is in flight and accepted == need or max_attempts
+    is exhausted; its answer is its accepted attempts in attempt order, and its store entry is freed.
+
+    Why that answer is generate_stream's "first `need` accepted attempts in attempt order".  Attempts start in number
+    order, so the started ones are 0 .. s - 1.  The cap gives in_flight + accepted <= need at all times, hence never
+    more than `need` accepted attempts, and a decision with accepted == need means the accepted attempts are ALL the
+    accepted ones among 0 .. s - 1, exactly `need` of them: the first `need`.  s is also the sequential loop's count:
+    attempt s - 1 was started while in_flight + accepted < need counted every attempt below it that was not yet
+    rejected, so fewer than `need` of 0 .. s - 2 are accepted in the end -- attempt s - 1 is the need-th accepted one,
+    where the one-at-a-time loop stops too.  With max_attempts exhausted the answer is every accepted attempt of
+    0 .. max_attempts - 1 (fewer than `need`, or the cap would have stopped earlier), as there.
+
+    The store has one entry per slot and that is enough: a rejection frees a slot in the same event that makes its
+    request want one, and earlier requests come first, so after every assignment each admitted, undecided request has
+    an attempt in flight -- at most `slots` entries are live."""
+
+    def __init__(self, needs: Sequence[int], max_attempts: Sequence[Optional[int]], slots: int):
+        self.need = [int(n) for n in needs]
+        self.cap = [None if m is None else int(m) for m in max_attempts]
+        n = len(self.need)
+        self.started, self.in_flight, self.accepted = [0] * n, [0] * n, [0] * n
+        self.results = [{} for _ in range(n)]          # attempt -> (accepted, payload)
+        self.entry = [None] * n                        # the store entry of an admitted, undecided request
+        self.decided = [False] * n
+        self.slot = [None] * int(slots)                # (request, attempt) decoding in the slot, None: free
+        self.free_entries = list(range(int(slots)))
+        self._head = 0                                 # requests below it want nothing any more
+
+    def wants(self, r: int) -> bool:
+        return (not self.decided[r] and self.in_flight[r] + self.accepted[r] < self.need[r]
+                and (self.cap[r] is None or self.started[r] < self.cap[r]))
+
+    def assign(self) -> List[PoolJob]:
+        """Hand every free slot the next attempt of the earliest request that wants one (admit: the request's first
+        attempt, its entry is taken here).  Returns the jobs in slot order."""
+        jobs = []
+        free = [b for b, occ in enumerate(self.slot) if occ is None]
+        r = self._head
+        for b in free:
+            while r < len(self.need) and not self.wants(r):
+                r += 1
+            if r >= len(self.need) or (self.entry[r] is None and not self.free_entries):
+                break                                  # (no entry free: cannot happen, see the class comment)
+            admit = self.entry[r] is None
+            if admit:
+                self.entry[r] = self.free_entries.pop(0)
+            a = self.started[r]
+            self.started[r] += 1
+            self.in_flight[r] += 1
+            self.slot[b] = (r, a)
+            jobs.append(PoolJob(b, r, a, self.entry[r], admit))
+        while self._head < len(self.need) and self.decided[self._head]:
+            self._head += 1
+        return jobs
+
+    def finish(self, slot: int, accepted: bool, payload=None):
+        """The attempt in `slot` has ended and was accepted or not; the slot is free."""
+        r, a = self.slot[slot]
+        self.slot[slot] = None
+        self.in_flight[r] -= 1
+        self.accepted[r] += bool(accepted)
+        self.results[r][a] = (bool(accepted), payload)
+
+    def collect(self) -> List[int]:
+        """The requests decided since the last call, in list order; their entries are freed (and reused)."""
+        out = []
+        for r in range(self._head, len(self.need)):
+            if self.decided[r] or self.in_flight[r]:
+                continue
+            if self.accepted[r] >= self.need[r] or (self.cap[r] is not None and self.started[r] >= self.cap[r]):
+                self.decided[r] = True
+                if self.entry[r] is not None:
+                    self.free_entries.append(self.entry[r])
+                    self.entry[r] = None
+                out.append(r)
+            elif self.started[r] == 0:
+                break                                  # (later requests have not been reached yet)
+        return out
+
+    def answer(self, r: int) -> list:
+        """The payloads of request r's accepted attempts in attempt order."""
+        return [p for _, (ok, p) in sorted(self.results[r].items()) if ok]
+
+    def busy(self) -> bool:
+        return any(occ is not None for occ in self.slot)
+
+    def done(self) -> bool:
+        return all(self.decided)
 
 
 class BatchedGenerator:
@@ -2158,3 +2494,181 @@ class BatchedGenerator:
         if return_logprobs:
             return out, started, out_lp
         return out, started
+
+    # ---- request pool: MANY requests decoded in one set of slots (generate_stream serves one; a request of a few
+    # sequences leaves most of the slots the machine would carry at the same iteration time empty)
+    def _check_pool(self, requests, slots, grammar, harmony):
+        """generate_pool's refusals, before anything is allocated; returns (slots, n_cond)."""
+        if isinstance(slots, bool) or not isinstance(slots, (int, np.integer)) or not 1 <= int(slots) <= 256:
+            raise CommuHipError(f"generate_pool: slots in 1 .. 256 expected, got {slots!r}")
+        requests = list(requests)
+        if not requests:
+            raise CommuHipError("generate_pool: an empty list of requests")
+        if self.shared_prompt:
+            raise CommuHipError("generate_pool: a generator built for prompts (shared_prompt) is not served: a primed "
+                                "image needs a per-request replay")
+        if bool(getattr(self.model, "parity_fp32", False)):
+            raise CommuHipError("generate_pool: the fp32 parity mode (model.parity_fp32) has a third cache layout that the "
+                                "arm launch does not copy")
+        n_cond = len(requests[0].encoded_meta)
+        for i, r in enumerate(requests):
+            if isinstance(r.need, bool) or not isinstance(r.need, (int, np.integer)) or r.need < 1:
+                raise CommuHipError(f"generate_pool: request {i}: need >= 1 expected, got {r.need!r}")
+            if len(r.encoded_meta) != n_cond:
+                raise CommuHipError(f"generate_pool: request {i} has {len(r.encoded_meta)} conditioning tokens, request 0 "
+                                    f"has {n_cond}: one length for the pool expected")
+            if r.grammar and grammar is None:
+                raise CommuHipError(f"generate_pool: request {i} switches the grammar on, but the pool has no grammar table "
+                                    "(generate_pool(grammar=))")
+            if r.harmony and harmony is None:
+                raise CommuHipError(f"generate_pool: request {i} switches the harmony on, but the pool has no harmony table "
+                                    "(generate_pool(harmony=))")
+            if r.max_attempts is not None and r.max_attempts < 0:
+                raise CommuHipError(f"generate_pool: request {i}: max_attempts >= 0 expected, got {r.max_attempts!r}")
+            if r.logit_bias is not None and np.ndim(r.logit_bias) != 1:
+                raise CommuHipError(f"generate_pool: request {i}: logit_bias: one row expected, got shape "
+                                    f"{np.shape(r.logit_bias)}")
+        if n_cond < 1 or n_cond > 15:
+            raise CommuHipError(f"generate_pool: 1 .. 15 conditioning tokens expected, got {n_cond}")
+        if self.sliding and int(self.memory_length) < n_cond:
+            raise CommuHipError(f"generate_pool: a sliding window of {self.memory_length} positions is shorter than the "
+                                f"context of {n_cond} tokens")
+        return int(slots), n_cond
+
+    @torch.no_grad()
+    def generate_pool(self, requests, slots: int = 64, grammar=None, harmony=None, class_sampling=None,
+                      return_logprobs: bool = False, on_result=None):
+        """MANY requests (PoolRequest) decoded in ONE decoder of B = min(slots, sum of need) slots: generate_stream's loop
+        -- the iteration graph built once, POLL iterations queued ahead, the records polled through the pinned copy,
+        finished slots harvested and handed to their request's accept -- in which a free slot takes the next attempt of
+        the earliest request that still wants one (PoolSchedule) and all slots that became free in a window are armed by
+        ONE launch (ForcedDecoder.arm).  Returns one PoolResult(sequences, attempts_started, logprobs) per request in
+        request order; on_result(index, result) is called as each request is decided.
+        CONTRACT: a request gets what generate_stream(..., slots=1) returns for it alone -- the same sequences, token for
+        token, and the same number of attempts started --, whatever else is in the pool and whichever slots decode it:
+        attempt a of a request draws from attempt_uniforms(request.seed, a, .), its conditioning K/V come from a forward
+        over its own single column (ForcedDecoder.admit), and the decode step computes every slot on its own.  (Beyond
+        512 keys per slot the split-key policy chooses the attention's summation order from the number of live rows, as
+        it does for generate_stream.)
+        grammar / harmony / class_sampling: ONE table each for the pool (generate_stream's values); a request switches
+        grammar and harmony per request, the class table applies to every request over its own base triple.
+        Refused, before anything is allocated: slots outside 1 .. 256, an empty list, need < 1, metas of different
+        lengths, a per-request switch without a pool table, a shared-prompt generator, model.parity_fp32, a sliding window
+        shorter than the context.
+        self.pool_stats holds the run's book-keeping: attempts rejected, the job count of every arm launch, how often a
+        slot was armed with another request than it held before, admissions."""
+        requests = list(requests)
+        slots, n_cond = self._check_pool(requests, slots, grammar, harmony)
+        if grammar is not None and not isinstance(grammar, (bool, np.bool_)) and np.ndim(grammar) != 2:
+            raise CommuHipError(f"grammar: one setting for the pool expected (True or a table), got shape {np.shape(grammar)}")
+        gram_table = None if grammar is None or grammar is False else (event_grammar() if grammar is True
+                                                                        else grammar_table(grammar))
+        harm_table = _harmony_request(self._one_harmony(harmony))
+        cls_table = _class_request(class_sampling)
+        # each request's controls, validated before anything is built
+        triples, biases, orders, voxes = [], [], [], []
+        for i, r in enumerate(requests):
+            t, k, p = sampling_rows(1, r.temperature, r.top_k, r.top_p)
+            triples.append((t[0].item(), int(k[0]), p[0].item()))
+            biases.append(None if r.logit_bias is None else logit_bias_rows(r.logit_bias, 1)[0])
+            orders.append(int(note_order_ctl(r.note_order, 1)[0]))
+            voxes.append(int(voices_ctl(r.voices, 1)[0]))
+        B = max(1, min(slots, sum(int(r.need) for r in requests)))
+        max_chords = max(len(r.input_data.chord_token_components["chord_token"]) for r in requests)
+        key = ("pool", B, self.trace is not None, self.sliding)          # (never shared with generate / generate_stream:
+        dec = self._decoders.get(key)                                     #  arm() writes the slots' controls on the device only)
+        if dec is None or dec.ld_chord < max_chords:
+            dec = ForcedDecoder(self.model, B, self.generation_length, self.memory_length, 1.0, 1,
+                                max_chords=max(64, max_chords), record_trace=self.trace is not None, sliding=self.sliding,
+                                kv_dtype=self.kv_dtype)
+            self._decoders[key] = dec
+        # the pool's tables and whatever per-slot arrays its requests need (first use allocates, later pools reuse)
+        dec.set_grammar(None)
+        if gram_table is not None:
+            dec.set_grammar(gram_table)
+        dec.set_harmony(harm_table)
+        use_order = any(o != NOTE_ORDER_OFF for o in orders) or any(v != VOICES_OFF for v in voxes)
+        if cls_table is not None or use_order:
+            dec._first_use(rows=True, bias=True, gram=True, harm=True, cls=True, order=use_order)
+        if any(v != VOICES_OFF for v in voxes):
+            dec._first_use(voices=True)
+        if any(b is not None for b in biases):
+            dec._first_use(bias=True)
+        dec.pool_open(n_cond)
+        cls_samples = cls_table is not None and bool((np.nan_to_num(cls_table[..., 0], nan=0.0) != 0).any())
+        sched = PoolSchedule([r.need for r in requests], [r.max_attempts for r in requests], B)
+        stats = {"rejected": 0, "arms": [], "rearmed_other_request": 0, "admissions": 0}
+        self.pool_stats = stats
+        held = [None] * B                                # the request each slot decoded last
+
+        def arm_free():
+            jobs = sched.assign()
+            staged = []
+            for j in jobs:
+                r = requests[j.request]
+                if j.admit:
+                    stats["admissions"] += 1
+                    dec.admit(j.entry, r.encoded_meta, r.input_data, sampling=triples[j.request],
+                              logit_bias=biases[j.request],
+                              grammar=(gram_table is not None) if r.grammar is None else bool(r.grammar),
+                              harmony=(harm_table is not None) if r.harmony is None else bool(r.harmony),
+                              note_order=orders[j.request], voices=voxes[j.request], class_table=cls_table)
+                sampled = triples[j.request][0] != 0 or cls_samples          # (a greedy attempt reads no variate)
+                staged.append((j.slot, j.entry, self.attempt_uniforms(r.seed, j.attempt, dec.ld_u) if sampled else None))
+                if held[j.slot] is not None and held[j.slot] != j.request:
+                    stats["rearmed_other_request"] += 1
+                held[j.slot] = j.request
+            if staged:
+                stats["arms"].append(len(staged))
+                dec.arm(staged)
+
+        results = [None] * len(requests)
+
+        def decide():
+            for r in sched.collect():
+                got = sched.answer(r)
+                results[r] = PoolResult([g[0] for g in got], sched.started[r],
+                                        [g[1] for g in got] if return_logprobs else None)
+                if on_result is not None:
+                    on_result(r, results[r])
+
+        decide()                                         # (requests with max_attempts = 0)
+        arm_free()
+        if self.use_graph and dec.graph is None:
+            dec.build_graph()
+        dec.pre()
+        dec.run_iterations(dec.POLL, self.use_graph)
+        kb, nlive = 0, None
+        while sched.busy():
+            dec.poll_submit()
+            dec.run_iterations(dec.POLL, self.use_graph, klen_bound=kb, live_rows=nlive)
+            fsm = dec.poll_result()
+            kb = int(fsm[:, 0].max()) + 3 * dec.POLL
+            nlive = sum(1 for b in range(B) if sched.slot[b] is not None and not fsm[b, 5]) + 1
+            fin = [b for b in range(B) if sched.slot[b] is not None and fsm[b, 5]]
+            if fin:
+                # the finished slots' rows in ONE download (a finished slot's rows no longer change)
+                idx = torch.tensor(fin, dtype=torch.long, device=dec.dev)
+                n = int(fsm[fin, 0].max())
+                rows = dec.seq.index_select(0, idx)[:, :n].cpu().numpy()
+                lps = dec.seq_logp.index_select(0, idx)[:, :n].cpu().numpy() if return_logprobs else None
+                for i, b in enumerate(fin):
+                    r, _ = sched.slot[b]
+                    dec.reports[b].consumed = int(fsm[b, 10])
+                    ln = int(fsm[b, 0])
+                    seq = None if fsm[b, 6] else rows[i, :ln].tolist()
+                    acc = requests[r].accept
+                    ok = (seq is not None) if acc is None else bool(acc(seq, dec.reports[b]))
+                    stats["rejected"] += not ok
+                    lp = lps[i, :ln].copy() if (ok and return_logprobs and seq is not None) else None
+                    sched.finish(b, ok, (seq, lp))
+                decide()
+                arm_free()
+        decide()
+        try:
+            dec.state.check()
+        except CommuHipError:
+            dec.state.tail_ok, dec.graph, dec.graph_long = False, None, None          # later pools on this decoder: per-Linear launches
+            dec.state.t_err.zero_()
+            raise
+        return results

@@ -326,3 +326,45 @@ class InferenceTask:
                                   **({} if note_order is None else {"note_order": note_order}),
                                   **({} if voices is None else {"voices": voices}))
         return (res[0], res[2]) if return_logprobs else res[0]
+
+    def execute_pool(self, items, return_logprobs: bool = False, harmony=None):
+        """generate.py --requests (not in the reference): MANY requests in one pool of decode slots
+        (BatchedGenerator.generate_pool).  items: one dict per request -- encoded_meta, input_data (its num_generate,
+        temperature, top_k, top_p), seed, max_rounds, logit_bias.  Every request is accepted by the two validators of
+        execute() and bounded by max_rounds x num_generate attempts, as there; the pool-wide options (grammar, harmony,
+        class_sampling, note_order, voices, decode_slots, kv_cache, sliding_memory) come from the inference configuration
+        as in execute().  Returns generate_pool's PoolResult list."""
+        from ..generate import BatchedGenerator, PoolRequest
+        G = self.inference_cfg.GENERATION
+        mlen = getattr(self.inference_cfg.MODEL, "memory_length", 4146) if hasattr(self.inference_cfg, "MODEL") else 4146
+        gen = BatchedGenerator(self.model, self.device, G.generation_length, mlen,
+                               sliding=bool(getattr(G, "sliding_memory", False)), kv_dtype=str(getattr(G, "kv_cache", "bf16")))
+        grammar = True if bool(getattr(G, "grammar", False)) else None
+        class_sampling = None
+        if getattr(G, "class_sampling", None):
+            import json
+
+            from ..generate import read_class_sampling
+            class_sampling = read_class_sampling(json.loads(G.class_sampling))[0]
+        note_order = None if getattr(G, "note_order", None) is None else int(G.note_order)
+        voices = None if getattr(G, "voices", None) is None else int(G.voices)
+
+        def accept(seq, rep) -> bool:
+            self.attempts += 1
+            if seq is None:
+                return False
+            try:
+                rep.validate_teacher_forced_sequence(seq)
+            except Exception:
+                return False
+            return self.validate_generated_sequence(seq)
+        reqs = []
+        for it in items:
+            d = it["input_data"]
+            mr = it.get("max_rounds")
+            reqs.append(PoolRequest(list(it["encoded_meta"]), d, int(d.num_generate), d.temperature, d.top_k,
+                                    top_p=getattr(d, "top_p", 1.0), seed=int(it.get("seed") or 0),
+                                    max_attempts=None if mr is None else int(mr) * int(d.num_generate), accept=accept,
+                                    logit_bias=it.get("logit_bias"), note_order=note_order, voices=voices))
+        return gen.generate_pool(reqs, slots=int(getattr(G, "decode_slots", 64)), grammar=grammar, harmony=harmony,
+                                 class_sampling=class_sampling, return_logprobs=return_logprobs)

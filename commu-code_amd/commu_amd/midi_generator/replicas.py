@@ -55,6 +55,38 @@ def generate_on_device(model_args, in_args, device_index, num_generate, uniform_
                                       harmony=harmony, class_sampling=class_sampling)
 
 
+def generate_requests_on_device(model_args, requests, device_index, training_cfg=None, logprobs=False, harmony=None):
+    """generate.py --requests: checkpoint -> model on cuda:<device_index>, then every request (a dict of one request's
+    input arguments plus seed, max_rounds and its constraint row logit_bias) through PreprocessTask and all of them in ONE
+    pool (InferenceTask.execute_pool).  Returns one dict per request in list order: encoded_meta, sequences, attempts
+    (and logprobs as logprobs_to_lists gives them)."""
+    import torch
+    from commu_amd.midi_generator.meta import PreprocessTask
+    from commu_amd.midi_generator.midi_inferrer import InferenceTask
+    from commu_amd.midi_generator.model_initializer import ModelInitializeTask
+    torch.cuda.set_device(device_index)
+    device = torch.device("cuda", device_index)
+    init = ModelInitializeTask(model_args, map_location="cpu", device=device, training_cfg=training_cfg)
+    model = init.execute()
+    items = []
+    for r in requests:
+        pre = PreprocessTask()
+        args = {k: v for k, v in r.items() if k not in ("seed", "max_rounds", "logit_bias")}
+        encoded_meta = pre.execute(args)
+        items.append({"encoded_meta": encoded_meta, "input_data": pre.input_data, "seed": int(r.get("seed") or 0),
+                      "max_rounds": r.get("max_rounds"), "logit_bias": r.get("logit_bias")})
+    task = InferenceTask(device)
+    task(model=model, input_data=None, inference_cfg=init.inference_cfg)
+    res = task.execute_pool(items, return_logprobs=logprobs, harmony=harmony)
+    out = []
+    for it, r in zip(items, res):
+        doc = {"encoded_meta": it["encoded_meta"], "sequences": r.sequences, "attempts": r.attempts_started}
+        if logprobs:
+            doc["logprobs"] = logprobs_to_lists(r.logprobs)
+        out.append(doc)
+    return out
+
+
 def replica_worker(rank, device_index, model_args, in_args, share, max_rounds, training_cfg, q, logprobs=False,
                    prompt=None, logit_bias=None, harmony=None, class_sampling=None):
     try:

@@ -1547,6 +1547,42 @@ def decode_prefill_scatter_kv8(qkv, T, kc8, vc8, ks, vs, klen, lens, slots=None,
          _p(lens), _p(slots), Bc, H, DH, Lmax, window, _s())
 
 
+# ---------------------------------------------------------------------------------------------- request pool (opt-in)
+def decode_arm_args(cache, image, **fields):
+    """The argument block of commu_decode_arm (include/commu_hip.h), built once per decoder: cache / image are the 2 or
+    4 cache tensors [L, B, H, Lmax, row] and the store's images [L, Rcap, H, ctx_rows, row] in the same order; every
+    other field by its name in the header, tensors (GPU, contiguous) for the pointers and None for an array the decoder
+    does not have.  The geometry (B, Rcap, L, H, Lmax, ctx_rows, row_bytes) is read off the tensors."""
+    if len(cache) != len(image) or len(cache) not in (2, 4):
+        raise CommuHipError(f"decode_arm: 2 or 4 cache tensors and as many images expected, got {len(cache)} / {len(image)}")
+    L, B, H, Lmax = cache[0].shape[:4]
+    Rcap, ctx_rows = image[0].shape[1], image[0].shape[3]
+    rb = []
+    for c, im in zip(cache, image):
+        if c.dim() != 5 or im.dim() != 5 or not c.is_contiguous() or not im.is_contiguous() or c.dtype != im.dtype:
+            raise CommuHipError("decode_arm: contiguous 5-D caches and images of one dtype expected")
+        if tuple(c.shape[:4]) != (L, B, H, Lmax) or tuple(im.shape) != (L, Rcap, H, ctx_rows, c.shape[4]):
+            raise CommuHipError(f"decode_arm: cache {tuple(c.shape)} and image {tuple(im.shape)} do not belong together")
+        rb.append(c.shape[4] * c.element_size())
+    a = _lib.struct_args(_lib.DecodeArmArgs, B=B, Rcap=Rcap, L=L, H=H, Lmax=Lmax, ctx_rows=ctx_rows, n_cache=len(cache))
+    for i, (c, im) in enumerate(zip(cache, image)):
+        a.row_bytes[i], a.cache[i], a.image[i] = rb[i], c.data_ptr(), im.data_ptr()
+    for name, v in fields.items():
+        if isinstance(v, torch.Tensor):
+            if not v.is_contiguous():
+                raise CommuHipError(f"decode_arm: {name} is not contiguous")
+            v = _p(v)
+        setattr(a, name, v)
+    return a
+
+
+def decode_arm(args, njobs: int):
+    """ONE launch that arms njobs (slot, entry) jobs staged at args.jobs / args.variates (commu_decode_arm); 0 jobs launch
+    nothing."""
+    args.njobs = int(njobs)
+    call("commu_decode_arm", C.byref(args), _s())
+
+
 # ---------------------------------------------------------------------------------------------- shared prompt prefix (opt-in)
 # (include/commu_hip.h, commu_decode_attn_prefix: the K/V of the positions all slots have in common, held once)
 def decode_prefix_chunk() -> int:

@@ -143,6 +143,17 @@ def parse_args():
     input_arg_parser.add_argument("--pitch_max", type=int, default=None)
     # not in the reference: replicas of the generator, one per GPU (default: every visible GPU, at most num_generate)
     input_arg_parser.add_argument("--gpus", type=int, default=None)
+    # not in the reference (one request per process and per model load): MANY requests decoded in one pool of decode slots
+    # (commu_amd.generate.BatchedGenerator.generate_pool).  FILE.json: a list of objects whose keys are the input arguments
+    # of one request -- bpm .. chord_progression, num_generate, top_k, temperature, top_p, optional seed, max_rounds,
+    # pitch_min, pitch_max, logit_bias -- each of which gets exactly the sequences a run of its own with --decode_slots 1 and
+    # the same seed writes.  The model arguments apply to the whole pool; sequences.json becomes {"requests": [...]}.
+    # Refused with any single-request input argument, --prompt_tokens, --share_prompt, --parity, and --gpus above 1.
+    input_arg_parser.add_argument("--requests", type=str, default=None, metavar="FILE.json",
+                                  help="a JSON list of requests (objects of input arguments: bpm .. chord_progression, "
+                                       "num_generate, top_k, temperature, top_p, optional seed, max_rounds, pitch_min, "
+                                       "pitch_max, logit_bias) decoded in ONE pool of --decode_slots slots; sequences.json "
+                                       "becomes {\"requests\": [...]}")
     return {"model_args": model_arg_parser, "input_args": input_arg_parser}
 
 
@@ -221,6 +232,65 @@ def check_voices(model_args):
     return word
 
 
+REQUEST_META_KEYS = ("bpm", "audio_key", "time_signature", "pitch_range", "num_measures", "inst", "genre", "track_role",
+                     "rhythm", "min_velocity", "max_velocity", "chord_progression")
+REQUEST_KEYS = REQUEST_META_KEYS + ("num_generate", "top_k", "temperature", "top_p", "seed", "max_rounds", "pitch_min",
+                                    "pitch_max", "logit_bias")
+# (single-request input arguments that --requests replaces, with the value the parser gives them when they are not named)
+SINGLE_REQUEST_ARGS = {**{k: None for k in REQUEST_META_KEYS}, "genre": "cinematic", "rhythm": "standard",
+                       "num_generate": None, "top_k": 32, "temperature": 0.95, "top_p": 1.0, "max_rounds": None,
+                       "logit_bias": None, "pitch_min": None, "pitch_max": None}
+
+
+def check_requests(model_args, input_args):
+    """--requests FILE.json as a list of per-request argument dicts (None without the flag): every key of REQUEST_KEYS,
+    the parser's defaults where an object does not name one (seed 0).  Host code only, run before a model is loaded;
+    ValueError that says what is wrong -- a single-request input argument, --prompt_tokens, --share_prompt or --parity
+    beside --requests, --gpus above 1, a file that is not a JSON list of objects, an unknown key or a missing
+    num_generate (with the index of the request)."""
+    path = getattr(input_args, "requests", None)
+    if path is None:
+        return None
+    given = [k for k, d in SINGLE_REQUEST_ARGS.items() if getattr(input_args, k, d) != d]
+    if given:
+        raise ValueError(f"--requests cannot be combined with the single-request input argument --{given[0]}: every "
+                         "request of the file carries its own")
+    for flag, on in (("--prompt_tokens", bool(getattr(input_args, "prompt_tokens", None))),
+                     ("--share_prompt", bool(getattr(model_args, "share_prompt", False))),
+                     ("--parity", bool(getattr(model_args, "parity", False)))):
+        if on:
+            raise ValueError(f"--requests cannot be combined with {flag}: the request pool serves unprimed requests on the "
+                             "bf16 and fp8 K/V caches")
+    gpus = getattr(input_args, "gpus", None)
+    if gpus is not None and gpus > 1:
+        raise ValueError(f"--requests with --gpus {gpus}: the request pool runs on one GPU (dealing requests to replicas "
+                         "is not built)")
+    try:
+        with open(path) as f:
+            doc = json.load(f)
+    except OSError as e:
+        raise ValueError(f"--requests: a readable JSON file expected, got {path!r} ({e.strerror})") from None
+    except json.JSONDecodeError as e:
+        raise ValueError(f"--requests: {path}: not JSON ({e})") from None
+    if not isinstance(doc, list) or not doc:
+        raise ValueError(f"--requests: {path}: a non-empty JSON list of request objects expected")
+    out = []
+    for i, r in enumerate(doc):
+        if not isinstance(r, dict):
+            raise ValueError(f"--requests: {path}: request {i}: an object of input arguments expected, got "
+                             f"{type(r).__name__}")
+        unknown = sorted(set(r) - set(REQUEST_KEYS))
+        if unknown:
+            raise ValueError(f"--requests: {path}: request {i}: unknown key {unknown[0]!r} (known: {', '.join(REQUEST_KEYS)})")
+        if "num_generate" not in r:
+            raise ValueError(f"--requests: {path}: request {i}: num_generate is missing")
+        n = r["num_generate"]
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError(f"--requests: {path}: request {i}: num_generate: an integer >= 1 expected, got {n!r}")
+        out.append({**SINGLE_REQUEST_ARGS, "seed": 0, **r})
+    return out
+
+
 def read_constraints(path=None, pitch_min=None, pitch_max=None):
     """The constraint row of --logit_bias / --pitch_min / --pitch_max (None when none of them is given); host code only,
     raises (commu_amd.generate.CommuHipError, ValueError) on a malformed file or an empty range."""
@@ -295,7 +365,20 @@ def read_class_sampling_arg(setting=None, grammar=False):
     return json.dumps(doc)
 
 
-from commu_amd.midi_generator.replicas import generate_on_device, replica_worker, split_num_generate  # noqa: E402
+from commu_amd.midi_generator.replicas import (generate_on_device, generate_requests_on_device, replica_worker,  # noqa: E402
+                                               split_num_generate)
+
+
+def main_requests(model_args, input_args, requests, harmony, want_lp, training_cfg=None, device_index=0):
+    """--requests: every request of the file through PreprocessTask, all of them decoded in one pool on one GPU, and
+    sequences.json = {"requests": [{"encoded_meta", "sequences", "attempts" (, "logprobs")}, ...]} in file order."""
+    for r in requests:          # (malformed constraints are refused before a model is loaded)
+        r["logit_bias"] = read_constraints(r.pop("logit_bias", None), r.pop("pitch_min", None), r.pop("pitch_max", None))
+    results = generate_requests_on_device(model_args, requests, device_index, training_cfg, want_lp, harmony)
+    os.makedirs(input_args.output_dir, exist_ok=True)
+    with open(os.path.join(input_args.output_dir, "sequences.json"), "w") as f:
+        json.dump({"requests": results}, f)
+    return [r["sequences"] for r in results]
 
 
 def main(model_args, input_args, training_cfg=None, device_indices=None):
@@ -305,11 +388,13 @@ def main(model_args, input_args, training_cfg=None, device_indices=None):
     device order.  --gpus 1 (or one visible device) keeps everything in this process.  `device_indices` (tests):
     explicit device of every replica, e.g. [0, 0] = two replica processes on the one GPU of a test box."""
     import torch
-    check_share_prompt(model_args, input_args)          # (refused before a model is loaded or a replica started)
+    requests = check_requests(model_args, input_args)   # (refused before a model is loaded or a replica started)
+    check_share_prompt(model_args, input_args)          # (likewise)
     check_decode_slots(model_args)                      # (likewise)
     check_voices(model_args)                            # (likewise; ahead of the note order, which it switches on)
     check_note_order(model_args)                        # (likewise)
     in_args = dict(vars(input_args))
+    in_args.pop("requests", None)
     max_rounds = in_args.pop("max_rounds", None)
     gpus = in_args.pop("gpus", None)
     want_lp = bool(in_args.pop("logprobs", False))
@@ -323,6 +408,9 @@ def main(model_args, input_args, training_cfg=None, device_indices=None):
     # inference configuration)
     if getattr(model_args, "class_sampling", None) is not None:
         model_args.class_sampling = read_class_sampling_arg(model_args.class_sampling, bool(getattr(model_args, "grammar", False)))
+    if requests is not None:
+        return main_requests(model_args, input_args, requests, harmony, want_lp, training_cfg,
+                             0 if device_indices is None else device_indices[0])
     if device_indices is None:
         n_vis = torch.cuda.device_count()
         device_indices = list(range(max(1, n_vis if gpus is None else min(gpus, n_vis))))

@@ -813,6 +813,90 @@ int commu_forcing_replay(int* state, int* seq, int ld_seq, const int* prompt, in
 int commu_decode_prefill_scatter(const void* qkv, int ld_qkv, int T, int B, void* kcache, void* vcache, int* klen,
                                  const int* len, const int* slot, int Bcache, int H, int DH, int Lmax, int window,
                                  hipStream_t stream);
+/* ---- request pool: arm decode slots for ANY request between two replays of the iteration graph (csrc/decode_arm.hip).
+ * A REQUEST STORE of Rcap entries holds, per entry, everything a slot needs at the start of an attempt; every e_* array
+ * below is the store's [Rcap][.] twin of the slot array [B][.] beside it, with the same row pitch.  The K/V image of an
+ * entry is rows 0 .. klen0 - 1 of every layer and head in the cache's own format: image[i] is laid out like cache[i]
+ * with Rcap for B and ctx_rows for Lmax ([L][Rcap][H][ctx_rows][row_bytes[i]] against [L][B][H][Lmax][row_bytes[i]]), so
+ * that commu_decode_prefill_scatter / _kv8 write an image as they write a cache.  n_cache tensors (2: bf16 K, V; 4: e4m3
+ * K, V and their scale bytes); row_bytes[i] is DH * 2, DH or DH / 32.
+ * ONE launch arms njobs jobs, 0 <= njobs <= B; job j is (slot, entry) = jobs[2 j], jobs[2 j + 1] (device int32) and its
+ * variates are variates[j][0 .. ld_u) (device fp32).  For each job with 0 <= slot < B and 0 <= entry < Rcap (others
+ * are skipped), with n = e_klen0[entry] clamped to [0, min(ctx_rows, Lmax)]:
+ *   cache[i][l][slot][h][0 .. n) = image[i][l][entry][h][0 .. n) for every i, l, h -- rows >= n and other slots are not
+ *     touched; 16-byte vector loads and stores wherever row_bytes[i] is a multiple of 16 (K and V), bytes for the scales;
+ *   klen[slot] = n;  state[slot][0 .. nf) = e_state[entry];  seq[slot][0 .. ld_head) = e_seq[entry] (pitch ld_head);
+ *   chord_tok / chord_pos [slot][0 .. ld_chord) = e_chord_tok / e_chord_pos [entry];  wrong[slot][0 .. ld_wrong) = 0;
+ *   utable[slot][0 .. ld_u) = variates[j];
+ *   and, each only where BOTH the slot array and its store twin are given (seq_logp, trace: the slot array), as the
+ *   loop's entry point treats a null array:  seq_logp[slot][0 .. 2 ld_seq) = NaN;  trace[slot][0 .. ld_trace) = 0;
+ *   temperature_rows / top_k_rows / top_p_rows [slot] = e_temperature / e_top_k / e_top_p [entry];
+ *   bias[slot][0 .. ld_bias) = e_bias[entry];  gram_on / harm_on [slot] = e_gram_on / e_harm_on [entry] (bytes);
+ *   order_ctl / voice_ctl [slot] = e_order / e_voice [entry];  cls_ctl[slot][0 .. 32) = e_cls[entry] (int32).
+ * tok / active / keep / draw are NOT written: an armed slot sits out the iteration whose decision was taken from its
+ * finished record and starts with the next one.  Two jobs of one launch must name different slots (the caller's duty).
+ * Nothing but njobs varies between launches; there is no host synchronisation.  Grid: one wave per (job, layer, head).
+ *   struct_bytes: sizeof(commu_decode_arm_args) as the caller compiled it; a value that differs from the library's
+ *     (commu_decode_arm_args_bytes()) is refused with -22 before anything else is looked at.
+ *   njobs == 0: nothing is launched, 0.  -22: njobs outside [0, B]; B, Rcap, L, H, Lmax, ctx_rows, nf, ld_head, ld_chord,
+ *     ld_wrong or ld_u < 1; ld_head > ld_seq; n_cache not 2 or 4; row_bytes[i] < 1; a null jobs, variates, klen, state,
+ *     seq, chord_tok, chord_pos, wrong, utable, cache[i], image[i] or store twin of those; a cache[i] / image[i] with
+ *     row_bytes[i] % 16 == 0 that is not 16-byte aligned; jobs / variates not 4-byte aligned. */
+typedef struct commu_decode_arm_args {
+    unsigned struct_bytes;
+    int njobs;
+    const int* jobs;
+    const float* variates;
+    int B, Rcap;
+    /* K/V caches and the store's images */
+    int L, H, Lmax, ctx_rows, n_cache;
+    int row_bytes[4];
+    void* cache[4];
+    const void* image[4];
+    /* required slot arrays and their store twins */
+    int* klen;
+    const int* e_klen0;
+    int* state;
+    const int* e_state;
+    int nf;
+    int* seq;
+    const int* e_seq;
+    int ld_seq, ld_head;
+    int* chord_tok;
+    int* chord_pos;
+    const int* e_chord_tok;
+    const int* e_chord_pos;
+    int ld_chord;
+    unsigned char* wrong;
+    int ld_wrong;
+    float* utable;
+    int ld_u;
+    /* optional */
+    float* seq_logp;
+    int* trace;
+    int ld_trace;
+    float* temperature_rows;
+    int* top_k_rows;
+    float* top_p_rows;
+    const float* e_temperature;
+    const int* e_top_k;
+    const float* e_top_p;
+    float* bias;
+    const float* e_bias;
+    int ld_bias;
+    unsigned char* gram_on;
+    const unsigned char* e_gram_on;
+    unsigned char* harm_on;
+    const unsigned char* e_harm_on;
+    int* order_ctl;
+    const int* e_order;
+    int* voice_ctl;
+    const int* e_voice;
+    int* cls_ctl;
+    const int* e_cls;
+} commu_decode_arm_args;
+int commu_decode_arm_args_bytes(void);
+int commu_decode_arm(const commu_decode_arm_args* a, hipStream_t stream);
 /* dst[b][0:n] = src[b][0:n] where mask[b] != 0 */
 int commu_copy_rows_masked_f32(float* dst, int ldd, const float* src, int lds, const unsigned char* mask, int rows,
                                int n, hipStream_t stream);
