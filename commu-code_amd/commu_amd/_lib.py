@@ -101,6 +101,24 @@ class DecodeArmArgs(C.Structure):
                 ("cls_ctl", c_p), ("e_cls", c_p)]
 
 
+class DecodeArmPrimedArgs(C.Structure):
+    """commu_decode_arm_primed_args (the header documents every field)."""
+    _fields_ = [("struct_bytes", C.c_uint), ("njobs", c_i), ("jobs", c_p), ("variates", c_p), ("B", c_i), ("Rcap", c_i),
+                ("L", c_i), ("H", c_i), ("Lmax", c_i), ("img_rows", c_i), ("n_cache", c_i),
+                ("row_bytes", c_i * 4), ("cache", c_p * 4), ("image", c_p * 4), ("ring", c_i), ("grid_rows", c_i),
+                ("klen", c_p), ("e_klen0", c_p), ("state", c_p), ("e_state", c_p), ("nf", c_i),
+                ("seq", c_p), ("e_seq", c_p), ("ld_seq", c_i), ("ld_head", c_i),
+                ("chord_tok", c_p), ("chord_pos", c_p), ("e_chord_tok", c_p), ("e_chord_pos", c_p), ("ld_chord", c_i),
+                ("wrong", c_p), ("ld_wrong", c_i), ("utable", c_p), ("ld_u", c_i),
+                ("seq_logp", c_p), ("trace", c_p), ("e_trace", c_p), ("ld_trace", c_i),
+                ("temperature_rows", c_p), ("top_k_rows", c_p), ("top_p_rows", c_p),
+                ("e_temperature", c_p), ("e_top_k", c_p), ("e_top_p", c_p),
+                ("bias", c_p), ("e_bias", c_p), ("ld_bias", c_i),
+                ("gram_on", c_p), ("e_gram_on", c_p), ("harm_on", c_p), ("e_harm_on", c_p),
+                ("order_ctl", c_p), ("e_order", c_p), ("voice_ctl", c_p), ("e_voice", c_p),
+                ("cls_ctl", c_p), ("e_cls", c_p)]
+
+
 def struct_args(cls, **fields):
     """An argument struct with struct_bytes set; fields not named stay zero / null."""
     return cls(struct_bytes=C.sizeof(cls), **fields)
@@ -212,6 +230,9 @@ PROTOTYPES = {
     "commu_decode_sample_post_pre": [C.POINTER(DecodeLoopArgs), c_p],
     "commu_decode_arm_args_bytes": [],
     "commu_decode_arm": [C.POINTER(DecodeArmArgs), c_p],
+    "commu_decode_arm_primed_args_bytes": [],
+    "commu_decode_arm_primed_chunk_rows": [],
+    "commu_decode_arm_primed": [C.POINTER(DecodeArmPrimedArgs), c_p],
     "commu_forcing_replay": [c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p,
                              c_p, c_p, c_i, c_p, c_i, c_p],
     "commu_decode_prefill_scatter": [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p],
@@ -244,7 +265,7 @@ _RESTYPE = {"commu_decode_tail_pack_bytes": C.c_longlong, "commu_attn_pf_bytes":
 _NOCHECK = {"commu_layernorm_bwd_nblocks", "commu_colsum_slabs", "commu_embed_bwd_ws_rows", "commu_hip_version", "commu_attn_bwd_qrows", "commu_attn_fwd_generation", "commu_attn_bwd_kv_generation", "commu_colsum_slab_pass", "commu_gemm_tn_grouped_slices", "commu_gemm_tn_grouped_slices_budget", "commu_attn_band_slabs", "commu_attn_band_pairs",
             "commu_forcing_state_ints", "commu_decode_tail_supported", "commu_decode_tail_sync_words", "commu_decode_tail_sync_words_for", "commu_decode_tail_pack_bytes", "commu_attn_p_scratch_elems", "commu_gemm_nt_signbits_words", "commu_pack_batch", "commu_attn_pf_bytes",
             "commu_decode_prefix_chunk", "commu_decode_prefix_group", "commu_sample_args_bytes", "commu_decode_loop_args_bytes",
-            "commu_decode_arm_args_bytes"}
+            "commu_decode_arm_args_bytes", "commu_decode_arm_primed_args_bytes", "commu_decode_arm_primed_chunk_rows"}
 
 _lib = None
 
@@ -273,7 +294,8 @@ def load():
         fn.restype = _RESTYPE.get(name, c_i)
     # the argument structs as this table lays them out against the library's own sizeof
     for cls, sizer in ((SampleArgs, lib.commu_sample_args_bytes), (DecodeLoopArgs, lib.commu_decode_loop_args_bytes),
-                       (DecodeArmArgs, lib.commu_decode_arm_args_bytes)):
+                       (DecodeArmArgs, lib.commu_decode_arm_args_bytes),
+                       (DecodeArmPrimedArgs, lib.commu_decode_arm_primed_args_bytes)):
         if C.sizeof(cls) != sizer():
             raise CommuHipError(f"{cls.__name__}: {C.sizeof(cls)} bytes here, {sizer()} in {LIB_PATH} (include/commu_hip.h "
                                 "and _lib.py disagree)")

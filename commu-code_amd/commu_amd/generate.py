@@ -14,6 +14,7 @@ from __future__ import annotations
 import collections
 import ctypes as C
 import dataclasses
+import functools
 import math
 from typing import List, Optional, Sequence
 
@@ -1799,13 +1800,105 @@ class ForcedDecoder:
     # a device-side request store (admit) and moved into the slots by ONE launch per poll window (arm,
     # commu_decode_arm), between two graph replays.  A decoder that never calls pool_open() allocates none of this and
     # launches what it always launched.
-    def pool_open(self, n_cond: int):
+    def pool_image_rows(self) -> int:
+        """K/V image rows of a store entry.  A decoder without prompts: the context, n_ctx_max.  A primed decoder
+        (max_prompt > 0): what a replay can leave, n_ctx_max + ld_fed, on a linear cache; on a ring of W = Lmax rows
+        min(W, n_ctx_max + ld_fed) -- either no prompt wraps (rows are positions), or the image is a ring with the
+        cache's own modulus and the prefill scatter's row rule is the cache's."""
+        if self.max_prompt == 0:
+            return self.n_ctx_max
+        rows = self.n_ctx_max + self.ld_fed
+        return min(self.state.Lmax, rows)          # (linear: a prompt that does not fit the cache is refused anyway)
+
+    def pool_replay(self, encoded_metas, input_datas, prompts):
+        """The primed half of a pool's admission, for ALL its requests before the pool is opened: every non-empty prompt
+        is replayed through the device state machine (commu_forcing_replay, no model step) in batches of up to B, the
+        slot arrays serving as scratch rows (pool_open resets every one of them afterwards), one download per batch.
+        Returns per request None (no prompt) or its replay result on the host -- record, seq[:len], the kept fed tokens,
+        klen0, the trace row -- from which admit(primed=) composes the store entry without a synchronisation.  Raises
+        CommuHipError naming the request for a prompt that leaves the rules, a replayed stream beyond the fed buffer,
+        and, on a linear cache, klen0 + generation_length + 1 > Lmax."""
+        if self.max_prompt < 1:
+            raise CommuHipError("pool_replay: a decoder built with max_prompt > 0 expected")
+        B, NF, st = self.B, self.NF, self.state
+        n_cond = len(encoded_metas[0])
+        out = [None] * len(prompts)
+        todo = [i for i, p in enumerate(prompts) if p]
+        for lo in range(0, len(todo), B):
+            batch = todo[lo:lo + B]
+            fsm = np.zeros((B, NF), dtype=np.int32)
+            fsm[:, 0], fsm[:, 1], fsm[:, 5] = 1, -1, 1          # rows beyond the batch: idle, no prompt
+            seq = np.zeros((B, self.ld_seq), dtype=np.int32)
+            chords = np.zeros((2, B, self.ld_chord), dtype=np.int32)
+            pr = np.zeros((B, self.max_prompt), dtype=np.int32)
+            plen = np.zeros(B, dtype=np.int32)
+            for b, i in enumerate(batch):
+                comps = input_datas[i].chord_token_components
+                ct, cp = list(comps["chord_token"]), list(comps["chord_position"])
+                if len(ct) != len(cp):
+                    raise AssertionError("Wrong Chord Length")                      # midi_inferrer.py:27
+                if len(ct) > self.ld_chord:
+                    raise CommuHipError(f"{len(ct)} chords > max_chords={self.ld_chord}")
+                nm = float(input_datas[i].num_measures)
+                rep = ForcingReport(len(ct), nm)
+                fsm[b] = [1 + n_cond, -1, 0, 1, int(nm % 4 == 0), 0, 0, 0, 0, len(ct), 0, int(rep.length_fit), 0, 0]
+                seq[b, 1:1 + n_cond] = list(encoded_metas[i])
+                chords[0, b, :len(ct)], chords[1, b, :len(cp)] = ct, cp
+                pr[b, :len(prompts[i])] = prompts[i]
+                plen[b] = len(prompts[i])
+            up = lambda dst, a: dst.copy_(torch.from_numpy(np.ascontiguousarray(a)))
+            up(self.fsm, fsm)
+            up(self.seq, seq)
+            up(self.chord_tok, chords[0])
+            up(self.chord_pos, chords[1])
+            up(self.prompt, pr)
+            up(self.prompt_len, plen)
+            self.wrong.zero_()
+            self.fed.zero_()
+            st.klen.fill_(n_cond)
+            if self.trace is not None:
+                self.trace.zero_()
+            call("commu_forcing_replay", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.prompt), self.max_prompt,
+                 _p(self.prompt_len), _p(self.chord_tok), _p(self.chord_pos), self.ld_chord, _p(self.wrong), _p(self.utable),
+                 self.ld_u, _p(self.tok), _p(self.active), _p(self.keep), _p(self.draw), _p(self.uni), _p(self.trace),
+                 self.ld_trace, _p(self.seq_logp), _p(st.klen), _p(self.fed), self.ld_fed, _p(self.diverged), B, _s())
+            parts = [self.fsm, st.klen[:, None], self.diverged, self.fed, self.seq[:, :self.n_ctx_max + self.max_prompt]]
+            if self.trace is not None:
+                parts.append(self.trace)
+            got = torch.cat(parts, 1).cpu().numpy()          # the batch's one download
+            o_fed = NF + 3
+            o_seq = o_fed + self.ld_fed
+            o_tr = o_seq + self.n_ctx_max + self.max_prompt
+            for b, i in enumerate(batch):
+                rec, klen0, div = got[b, :NF].copy(), int(got[b, NF]), got[b, NF + 1:NF + 3]
+                if div[0] >= 0:
+                    k, why = int(div[0]), int(div[1])
+                    raise CommuHipError(f"generate_pool: request {i}: the prompt cannot be continued: token {prompts[i][k]} at "
+                                        f"index {k} of {len(prompts[i])}: {self.REPLAY_REASONS.get(why, why)} (reason {why})")
+                if klen0 - n_cond > self.ld_fed:
+                    raise CommuHipError(f"generate_pool: request {i}: the replayed stream of {klen0 - n_cond} kept tokens "
+                                        f"exceeds the buffer of {self.ld_fed}")
+                if not self.sliding and klen0 + self.generation_length + 1 > st.Lmax:
+                    raise CommuHipError(
+                        f"generate_pool: request {i} starts with {klen0} cached positions (context {n_cond} + "
+                        f"{klen0 - n_cond} replayed model steps); with generation_length {self.generation_length} that needs "
+                        f"{klen0 + self.generation_length + 1} positions and the decode memory has {st.Lmax} (shorten the "
+                        "prompt or generation_length, or use sliding=True)")
+                out[i] = {"record": rec, "seq": got[b, o_seq:o_seq + int(rec[0])].copy(),
+                          "fed": got[b, o_fed:o_fed + klen0 - n_cond].copy(), "klen0": klen0,
+                          "trace": None if self.trace is None else got[b, o_tr:o_tr + self.ld_trace].copy()}
+        return out
+
+    def pool_open(self, n_cond: int, grid_rows: int = 0):
         """Every slot idle (a finished record that decodes nothing), the store of Rcap = B entries allocated on first
         use: the state a pool starts from instead of load().  n_cond: the number of conditioning tokens of every request
-        of the pool."""
-        if self.max_prompt > 0 or self.shared_prompt:
-            raise CommuHipError("request pool: primed and shared-prompt decoders are not served (a primed image needs a "
-                                "per-request replay)")
+        of the pool.  A decoder built with max_prompt > 0 serves primed entries (admit(primed=)): its store has
+        pool_image_rows() image rows and sequence heads of n_ctx_max + max_prompt words per entry, and its arm launch is
+        commu_decode_arm_primed; grid_rows: the pool's longest image (0: unknown, every chunk of the store is launched).
+        The store is Rcap = B entries of pool_image_rows() rows: B / Lmax * rows of the cache's own bytes (with 256 slots
+        and 1000-token prompts about what a 64-slot cache of 8192 positions holds)."""
+        if self.shared_prompt:
+            raise CommuHipError("request pool: shared-prompt decoders are not served (the prefix belongs to no slot)")
         if self.state.parity:
             raise CommuHipError("request pool: the fp32 parity mode (model.parity_fp32) has a third cache layout that the "
                                 "arm launch does not copy")
@@ -1839,10 +1932,13 @@ class ForcedDecoder:
             z = lambda *shape, dtype=i32: torch.zeros(*shape, dtype=dtype, device=dev)
             hdr = (2 * B + 3) // 4 * 4          # the jobs, padded so that the variates start at a 16-byte boundary
             words = hdr + B * self.ld_u
+            rows = self.pool_image_rows()
             self._pool = {
-                "image": tuple(z(t.shape[0], R, t.shape[2], self.n_ctx_max, t.shape[4], dtype=t.dtype)
+                "image": tuple(z(t.shape[0], R, t.shape[2], rows, t.shape[4], dtype=t.dtype)
                                for t in st.cache_tensors()),
-                "e_klen0": z(R), "e_state": z(R, self.NF), "e_seq": z(R, self.n_ctx_max),
+                "primed": self.max_prompt > 0, "rows": rows, "ld_head": self.n_ctx_max + self.max_prompt,
+                "e_trace": z(R, self.ld_trace) if (self.max_prompt > 0 and self.trace is not None) else None,
+                "e_klen0": z(R), "e_state": z(R, self.NF), "e_seq": z(R, self.n_ctx_max + self.max_prompt),
                 "e_chord_tok": z(R, self.ld_chord), "e_chord_pos": z(R, self.ld_chord),
                 "e_temperature": z(R, dtype=F32), "e_top_k": z(R), "e_top_p": z(R, dtype=F32),
                 "e_bias": z(R, VPAD, dtype=F32), "e_gram_on": z(R, dtype=u8), "e_harm_on": z(R, dtype=u8),
@@ -1855,6 +1951,18 @@ class ForcedDecoder:
                 "one": torch.ones(1, dtype=i32, device=dev),
                 "meta": [None] * R,          # per entry: (n_chords, num_measures) for the slots' reports
             }
+        P = self._pool
+        P["grid_rows"] = max(0, min(int(grid_rows), P["rows"]))
+        self.klen0 = max(n_cond, P["grid_rows"])
+
+    def pool_store_bytes(self) -> int:
+        """Bytes of the request store's K/V images: Rcap = B entries of pool_image_rows() rows in the cache's format."""
+        return sum(t.numel() * t.element_size() for t in self._pool["image"])
+
+    @property
+    def arm_kernel(self) -> str:
+        """The entry point arm() launches."""
+        return "commu_decode_arm_primed" if self.max_prompt > 0 else "commu_decode_arm"
 
     def _pool_args(self):
         """The arm launch's argument block, rebuilt when an optional array was allocated since (a null twin: not written)."""
@@ -1864,10 +1972,13 @@ class ForcedDecoder:
         if P["args"] is None or P["sig"] != sig:
             st = self.state
             on = lambda t, e: {} if t is None else e
-            P["args"] = ops.decode_arm_args(
+            # (a primed decoder: the block of commu_decode_arm_primed -- the same fields, the ring mode and the trace twin)
+            build = ops.decode_arm_args if not P["primed"] else functools.partial(
+                ops.decode_arm_primed_args, ring=self.sliding, **on(P["e_trace"], {"e_trace": P["e_trace"]}))
+            P["args"] = build(
                 st.cache_tensors(), P["image"], jobs=P["stage"], variates=P["stage"][P["hdr"]:].view(F32),
                 klen=st.klen, e_klen0=P["e_klen0"], state=self.fsm, e_state=P["e_state"], nf=self.NF,
-                seq=self.seq, e_seq=P["e_seq"], ld_seq=self.ld_seq, ld_head=self.n_ctx_max,
+                seq=self.seq, e_seq=P["e_seq"], ld_seq=self.ld_seq, ld_head=P["ld_head"],
                 chord_tok=self.chord_tok, chord_pos=self.chord_pos, e_chord_tok=P["e_chord_tok"],
                 e_chord_pos=P["e_chord_pos"], ld_chord=self.ld_chord, wrong=self.wrong, ld_wrong=self.wrong.stride(0),
                 utable=self.utable, ld_u=self.ld_u, seq_logp=self.seq_logp, trace=self.trace, ld_trace=self.ld_trace,
@@ -1880,20 +1991,28 @@ class ForcedDecoder:
                 **on(self.voice_ctl, {"voice_ctl": self.voice_ctl, "e_voice": P["e_voice"]}),
                 **on(self.cls_ctl, {"cls_ctl": self.cls_ctl, "e_cls": P["e_cls"]}))
             P["sig"] = sig
+        if P["primed"]:
+            P["args"].grid_rows = P["grid_rows"]          # (this pool's longest image: fewer chunk workgroups)
         return P["args"]
 
     def admit(self, entry: int, encoded_meta: Sequence[int], input_data, sampling=None, logit_bias=None, grammar=False,
-              harmony=False, note_order=None, voices=None, class_table=None):
+              harmony=False, note_order=None, voices=None, class_table=None, primed=None):
         """Compose store entry `entry` for a request and upload it with its K/V image: the state record, sequence head
         and chord rows as load() builds them, klen0 = n_cond, the sampling triple (None: the decoder's), the bias row
         (None: zeros), the grammar and harmony switches (they switch on what the decoder has a table for), the
         note-order and voice words (None: off) and, where the decoder has class records, the request's record row
         (class_table: its NaN-table, None: the base triple in every record).  The image is written by ONE memory-less
         forward over this request's single column [n_cond, 1] and the prefill scatter of the cache's format into the
-        store: it does not depend on what else is admitted or decoding.  Everything is ordered on the current stream."""
+        store: it does not depend on what else is admitted or decoding.  Everything is ordered on the current stream.
+        primed (a decoder built with max_prompt > 0): the request's replay result (pool_replay) -- the entry is then the
+        record as the replay left it, the sequence head [0] + meta + prompt, the replay's trace row, klen0 as replayed,
+        and the image comes from the forward over the single column [0] + meta[:n-1] + fed (T = klen0, B = 1): the forward
+        load(prompts=) runs at one slot."""
         P = getattr(self, "_pool", None)
         if P is None:
             raise CommuHipError("admit: pool_open() first")
+        if primed is not None and not P["primed"]:
+            raise CommuHipError("admit: a primed entry, but the decoder was built without prompts (max_prompt=)")
         entry, n_cond = int(entry), self.n_cond
         if entry < 0 or entry >= self.B:
             raise CommuHipError(f"admit: store entries are 0 .. {self.B - 1}, got {entry}")
@@ -1927,11 +2046,20 @@ class ForcedDecoder:
         rep = ForcingReport(len(ct), nm)
         P["meta"][entry] = (len(ct), nm)
         up = lambda dst, a: dst.copy_(torch.from_numpy(np.ascontiguousarray(a)))
-        up(P["e_state"][entry], np.array([1 + n_cond, -1, 0, 1, int(nm % 4 == 0), 0, 0, 0, 0, len(ct), 0,
-                                          int(rep.length_fit), 0, 0], dtype=np.int32))
-        head = np.zeros(self.n_ctx_max, dtype=np.int32)
-        head[1:1 + n_cond] = list(encoded_meta)
+        head = np.zeros(P["ld_head"], dtype=np.int32)
+        if primed is None:
+            up(P["e_state"][entry], np.array([1 + n_cond, -1, 0, 1, int(nm % 4 == 0), 0, 0, 0, 0, len(ct), 0,
+                                              int(rep.length_fit), 0, 0], dtype=np.int32))
+            head[1:1 + n_cond] = list(encoded_meta)
+        else:
+            up(P["e_state"][entry], primed["record"])
+            head[:len(primed["seq"])] = primed["seq"]
         up(P["e_seq"][entry], head)
+        if P["e_trace"] is not None:
+            if primed is None:
+                P["e_trace"][entry].zero_()
+            else:
+                up(P["e_trace"][entry], primed["trace"])
         chords = np.zeros((2, self.ld_chord), dtype=np.int32)
         chords[0, :len(ct)], chords[1, :len(cp)] = ct, cp
         up(P["e_chord_tok"][entry], chords[0])
@@ -1954,24 +2082,36 @@ class ForcedDecoder:
             up(P["e_cls"][entry], rec.view(np.int32).reshape(N_CLASSES + 1, 4))
         # the image: one forward over the request's own column, scattered into the store as into a cache of Rcap slots
         # with n_ctx_max rows (rows = positions: the context is shorter than any ring)
-        ctx = torch.tensor([[0] + [int(x) for x in encoded_meta[:n_cond - 1]]], dtype=torch.long).t().contiguous().to(self.dev)
+        # (a primed entry: the column goes on with the kept tokens of the replayed stream, T = klen0; where the store's
+        #  image is a ring -- a sliding decoder whose image has the cache's Lmax rows -- the scatter's row rule is the ring's)
+        col = [0] + [int(x) for x in encoded_meta[:n_cond - 1]] + ([] if primed is None else [int(x) for x in primed["fed"]])
+        T = len(col)
+        if primed is not None and T != primed["klen0"]:
+            raise CommuHipError(f"admit: internal error: a replayed column of {T} tokens for klen0 = {primed['klen0']}")
+        ctx = torch.tensor([col], dtype=torch.long).t().contiguous().to(self.dev)
         _, _, qkvs = self.model._run_forward(ctx, None, None, None, need_grad=False, want_logits=True, want_kv=True)
-        lens = P["one"] * n_cond
+        lens = P["one"] * T
         slot = P["one"] * entry
         img = P["image"]
+        ring = {"window": self.state.window} if (P["primed"] and self.sliding and P["rows"] == self.state.Lmax) else {}
+        if not ring and T > P["rows"]:
+            raise CommuHipError(f"admit: {T} cached positions for a store image of {P['rows']} rows")
         for i, qkv in enumerate(qkvs):
-            q2 = qkv.view(n_cond, -1)
+            q2 = qkv.view(T, -1)
             if self.state.kv_dtype == "fp8":
-                ops.decode_prefill_scatter_kv8(q2, n_cond, img[0][i], img[1][i], img[2][i], img[3][i], P["e_klen0"], lens, slot)
+                ops.decode_prefill_scatter_kv8(q2, T, img[0][i], img[1][i], img[2][i], img[3][i], P["e_klen0"], lens, slot,
+                                               **ring)
             else:
-                ops.decode_prefill_scatter(q2, n_cond, img[0][i], img[1][i], P["e_klen0"], lens, slot)
+                ops.decode_prefill_scatter(q2, T, img[0][i], img[1][i], P["e_klen0"], lens, slot, **ring)
 
     def arm(self, jobs):
         """Arm slots for the window: jobs is a list of (slot, entry, variates row or None), distinct slots.  The jobs and
         their variates are staged in pinned memory, copied to the device block by ONE non-blocking copy, and ONE
         commu_decode_arm launch moves each entry into its slot -- K/V image, klen, record, sequence head, chords,
-        variates, controls; wrong zeroed, seq_logp NaN, trace zeroed.  self.reports[slot] becomes the new attempt's.  No
-        synchronisation: an armed slot sits out the iteration in flight and starts with the next one, as after rearm()."""
+        variates, controls; wrong zeroed, seq_logp NaN, trace zeroed (a decoder built with max_prompt > 0:
+        commu_decode_arm_primed, which copies long images row-parallel and the entry's trace).  self.reports[slot] becomes
+        the new attempt's.  No synchronisation: an armed slot sits out the iteration in flight and starts with the next
+        one, as after rearm()."""
         P = getattr(self, "_pool", None)
         if P is None:
             raise CommuHipError("arm: pool_open() first")
@@ -2003,7 +2143,10 @@ class ForcedDecoder:
         if P["ev"][turn] is None:
             P["ev"][turn] = torch.cuda.Event()
         P["ev"][turn].record()
-        ops.decode_arm(args, n)
+        if P["primed"]:
+            ops.decode_arm_primed(args, n)
+        else:
+            ops.decode_arm(args, n)
         for s, e, _ in jobs:
             self.reports[int(s)] = ForcingReport(*P["meta"][int(e)])
 
@@ -2133,7 +2276,8 @@ class PoolRequest:
     """One request of BatchedGenerator.generate_pool: what generate_stream takes for it alone.  accept: a callable
     (seq, report) -> bool, None accepts every sequence that is not None; logit_bias: one row; grammar / harmony: a
     per-request bool (None: on where the pool has a table), they may only switch on what the pool has a table for;
-    note_order / voices: as generate_stream's."""
+    note_order / voices: as generate_stream's.  prompt: token ids that follow the conditioning tokens and that every
+    attempt of THIS request continues (generate_stream's prompt=); None or [] is an unprimed request."""
     encoded_meta: Sequence[int]
     input_data: object
     need: int
@@ -2148,6 +2292,7 @@ class PoolRequest:
     harmony: Optional[bool] = None
     note_order: Optional[object] = None
     voices: Optional[object] = None
+    prompt: Optional[Sequence[int]] = None
 
 
 PoolResult = collections.namedtuple("PoolResult", ["sequences", "attempts_started", "logprobs"])
@@ -2505,8 +2650,8 @@ class BatchedGenerator:
         if not requests:
             raise CommuHipError("generate_pool: an empty list of requests")
         if self.shared_prompt:
-            raise CommuHipError("generate_pool: a generator built for prompts (shared_prompt) is not served: a primed "
-                                "image needs a per-request replay")
+            raise CommuHipError("generate_pool: a generator built for ONE shared prompt (shared_prompt) is not served: the "
+                                "shared prefix belongs to no slot; give each request its own (PoolRequest(prompt=))")
         if bool(getattr(self.model, "parity_fp32", False)):
             raise CommuHipError("generate_pool: the fp32 parity mode (model.parity_fp32) has a third cache layout that the "
                                 "arm launch does not copy")
@@ -2535,6 +2680,24 @@ class BatchedGenerator:
                                 f"context of {n_cond} tokens")
         return int(slots), n_cond
 
+    @staticmethod
+    def _pool_prompts(requests):
+        """Every request's prompt as a list of ints (None / [] -> []), its tokens checked against the vocabulary, host only;
+        returns (prompts, the longest one's length)."""
+        V = TOKEN_OFFSET.VOCAB_SIZE
+        prompts = []
+        for i, r in enumerate(requests):
+            try:
+                p = [] if r.prompt is None else [int(t) for t in r.prompt]
+            except (TypeError, ValueError):
+                raise CommuHipError(f"generate_pool: request {i}: prompt: a list of token ids expected, got "
+                                    f"{r.prompt!r}") from None
+            bad = next((j for j, t in enumerate(p) if t < 0 or t >= V), None)
+            if bad is not None:
+                raise CommuHipError(f"generate_pool: request {i}: prompt token {p[bad]} at index {bad} is outside [0, {V})")
+            prompts.append(p)
+        return prompts, max(len(p) for p in prompts)
+
     @torch.no_grad()
     def generate_pool(self, requests, slots: int = 64, grammar=None, harmony=None, class_sampling=None,
                       return_logprobs: bool = False, on_result=None):
@@ -2554,11 +2717,20 @@ class BatchedGenerator:
         grammar and harmony per request, the class table applies to every request over its own base triple.
         Refused, before anything is allocated: slots outside 1 .. 256, an empty list, need < 1, metas of different
         lengths, a per-request switch without a pool table, a shared-prompt generator, model.parity_fp32, a sliding window
-        shorter than the context.
+        shorter than the context, a prompt token outside [0, 729).
+        PROMPTS: a request with prompt= continues its own prompt, as generate_stream(prompt=) does for it alone.  A pool
+        without prompts is the pool it always was (same decoder, same store of n_ctx_max image rows, commu_decode_arm).  A
+        pool with at least one prompt gets a decoder of its own built with max_prompt = the longest prompt; every prompt
+        is replayed (ForcedDecoder.pool_replay) and refused BEFORE the pool is opened -- a token outside [0, 729), a
+        prompt that leaves the rules (request index, token, index, reason), on a linear cache klen0 + generation_length
+        + 1 > Lmax --; its store holds pool_image_rows() rows per entry (pool_stats["store_bytes"]: B entries of that
+        many rows, all layers and heads, in the cache's format) and its slots are armed by commu_decode_arm_primed.
         self.pool_stats holds the run's book-keeping: attempts rejected, the job count of every arm launch, how often a
-        slot was armed with another request than it held before, admissions."""
+        slot was armed with another request than it held before, admissions, the arm launch's entry point ("kernel"), the
+        store's image rows and bytes, the longest memory a request starts with ("klen0_max")."""
         requests = list(requests)
         slots, n_cond = self._check_pool(requests, slots, grammar, harmony)
+        prompts, max_prompt = self._pool_prompts(requests)
         if grammar is not None and not isinstance(grammar, (bool, np.bool_)) and np.ndim(grammar) != 2:
             raise CommuHipError(f"grammar: one setting for the pool expected (True or a table), got shape {np.shape(grammar)}")
         gram_table = None if grammar is None or grammar is False else (event_grammar() if grammar is True
@@ -2576,12 +2748,21 @@ class BatchedGenerator:
         B = max(1, min(slots, sum(int(r.need) for r in requests)))
         max_chords = max(len(r.input_data.chord_token_components["chord_token"]) for r in requests)
         key = ("pool", B, self.trace is not None, self.sliding)          # (never shared with generate / generate_stream:
-        dec = self._decoders.get(key)                                     #  arm() writes the slots' controls on the device only)
-        if dec is None or dec.ld_chord < max_chords:
+        #                                                                    arm() writes the slots' controls on the device only)
+        if max_prompt > 0:
+            key += ("primed",)          # a pool with prompts: a decoder of its own (longer store images, the primed arm launch)
+        dec = self._decoders.get(key)
+        if dec is None or dec.ld_chord < max_chords or dec.max_prompt < max_prompt:
+            primed_kw = {} if max_prompt == 0 else {"max_prompt": max(max_prompt, 0 if dec is None else dec.max_prompt)}
             dec = ForcedDecoder(self.model, B, self.generation_length, self.memory_length, 1.0, 1,
                                 max_chords=max(64, max_chords), record_trace=self.trace is not None, sliding=self.sliding,
-                                kv_dtype=self.kv_dtype)
+                                kv_dtype=self.kv_dtype, **primed_kw)
             self._decoders[key] = dec
+        # every prompt replayed and checked before the pool is opened: no store is allocated and nothing is decoded for a
+        # list that holds a prompt the rules could not have produced or the cache cannot take
+        replays = [None] * len(requests)
+        if max_prompt > 0:
+            replays = dec.pool_replay([r.encoded_meta for r in requests], [r.input_data for r in requests], prompts)
         # the pool's tables and whatever per-slot arrays its requests need (first use allocates, later pools reuse)
         dec.set_grammar(None)
         if gram_table is not None:
@@ -2594,10 +2775,12 @@ class BatchedGenerator:
             dec._first_use(voices=True)
         if any(b is not None for b in biases):
             dec._first_use(bias=True)
-        dec.pool_open(n_cond)
+        klen0_max = max([n_cond] + [p["klen0"] for p in replays if p is not None])
+        dec.pool_open(n_cond, grid_rows=klen0_max)
         cls_samples = cls_table is not None and bool((np.nan_to_num(cls_table[..., 0], nan=0.0) != 0).any())
         sched = PoolSchedule([r.need for r in requests], [r.max_attempts for r in requests], B)
-        stats = {"rejected": 0, "arms": [], "rearmed_other_request": 0, "admissions": 0}
+        stats = {"rejected": 0, "arms": [], "rearmed_other_request": 0, "admissions": 0, "kernel": dec.arm_kernel,
+                 "image_rows": dec.pool_image_rows(), "store_bytes": dec.pool_store_bytes(), "klen0_max": klen0_max}
         self.pool_stats = stats
         held = [None] * B                                # the request each slot decoded last
 
@@ -2612,7 +2795,8 @@ class BatchedGenerator:
                               logit_bias=biases[j.request],
                               grammar=(gram_table is not None) if r.grammar is None else bool(r.grammar),
                               harmony=(harm_table is not None) if r.harmony is None else bool(r.harmony),
-                              note_order=orders[j.request], voices=voxes[j.request], class_table=cls_table)
+                              note_order=orders[j.request], voices=voxes[j.request], class_table=cls_table,
+                              primed=replays[j.request])
                 sampled = triples[j.request][0] != 0 or cls_samples          # (a greedy attempt reads no variate)
                 staged.append((j.slot, j.entry, self.attempt_uniforms(r.seed, j.attempt, dec.ld_u) if sampled else None))
                 if held[j.slot] is not None and held[j.slot] != j.request:

@@ -330,7 +330,8 @@ class InferenceTask:
     def execute_pool(self, items, return_logprobs: bool = False, harmony=None):
         """generate.py --requests (not in the reference): MANY requests in one pool of decode slots
         (BatchedGenerator.generate_pool).  items: one dict per request -- encoded_meta, input_data (its num_generate,
-        temperature, top_k, top_p), seed, max_rounds, logit_bias.  Every request is accepted by the two validators of
+        temperature, top_k, top_p), seed, max_rounds, logit_bias, prompt (token ids the request's sequences continue, None
+        or [] for none).  Every request is accepted by the two validators of
         execute() and bounded by max_rounds x num_generate attempts, as there; the pool-wide options (grammar, harmony,
         class_sampling, note_order, voices, decode_slots, kv_cache, sliding_memory) come from the inference configuration
         as in execute().  Returns generate_pool's PoolResult list."""
@@ -365,6 +366,7 @@ class InferenceTask:
             reqs.append(PoolRequest(list(it["encoded_meta"]), d, int(d.num_generate), d.temperature, d.top_k,
                                     top_p=getattr(d, "top_p", 1.0), seed=int(it.get("seed") or 0),
                                     max_attempts=None if mr is None else int(mr) * int(d.num_generate), accept=accept,
-                                    logit_bias=it.get("logit_bias"), note_order=note_order, voices=voices))
+                                    logit_bias=it.get("logit_bias"), note_order=note_order, voices=voices,
+                                    prompt=None if not it.get("prompt") else list(it["prompt"])))
         return gen.generate_pool(reqs, slots=int(getattr(G, "decode_slots", 64)), grammar=grammar, harmony=harmony,
                                  class_sampling=class_sampling, return_logprobs=return_logprobs)

@@ -1548,11 +1548,12 @@ def decode_prefill_scatter_kv8(qkv, T, kc8, vc8, ks, vs, klen, lens, slots=None,
 
 
 # ---------------------------------------------------------------------------------------------- request pool (opt-in)
-def decode_arm_args(cache, image, **fields):
+def decode_arm_args(cache, image, primed=False, **fields):
     """The argument block of commu_decode_arm (include/commu_hip.h), built once per decoder: cache / image are the 2 or
     4 cache tensors [L, B, H, Lmax, row] and the store's images [L, Rcap, H, ctx_rows, row] in the same order; every
     other field by its name in the header, tensors (GPU, contiguous) for the pointers and None for an array the decoder
-    does not have.  The geometry (B, Rcap, L, H, Lmax, ctx_rows, row_bytes) is read off the tensors."""
+    does not have.  The geometry (B, Rcap, L, H, Lmax, ctx_rows, row_bytes) is read off the tensors.
+    primed: the block of commu_decode_arm_primed instead (decode_arm_primed_args)."""
     if len(cache) != len(image) or len(cache) not in (2, 4):
         raise CommuHipError(f"decode_arm: 2 or 4 cache tensors and as many images expected, got {len(cache)} / {len(image)}")
     L, B, H, Lmax = cache[0].shape[:4]
@@ -1564,7 +1565,11 @@ def decode_arm_args(cache, image, **fields):
         if tuple(c.shape[:4]) != (L, B, H, Lmax) or tuple(im.shape) != (L, Rcap, H, ctx_rows, c.shape[4]):
             raise CommuHipError(f"decode_arm: cache {tuple(c.shape)} and image {tuple(im.shape)} do not belong together")
         rb.append(c.shape[4] * c.element_size())
-    a = _lib.struct_args(_lib.DecodeArmArgs, B=B, Rcap=Rcap, L=L, H=H, Lmax=Lmax, ctx_rows=ctx_rows, n_cache=len(cache))
+    if primed:
+        a = _lib.struct_args(_lib.DecodeArmPrimedArgs, B=B, Rcap=Rcap, L=L, H=H, Lmax=Lmax, img_rows=ctx_rows,
+                             n_cache=len(cache))
+    else:
+        a = _lib.struct_args(_lib.DecodeArmArgs, B=B, Rcap=Rcap, L=L, H=H, Lmax=Lmax, ctx_rows=ctx_rows, n_cache=len(cache))
     for i, (c, im) in enumerate(zip(cache, image)):
         a.row_bytes[i], a.cache[i], a.image[i] = rb[i], c.data_ptr(), im.data_ptr()
     for name, v in fields.items():
@@ -1581,6 +1586,25 @@ def decode_arm(args, njobs: int):
     nothing."""
     args.njobs = int(njobs)
     call("commu_decode_arm", C.byref(args), _s())
+
+
+def decode_arm_primed_args(cache, image, ring=False, grid_rows=0, **fields):
+    """The argument block of commu_decode_arm_primed (include/commu_hip.h): decode_arm_args with the store's images
+    [L, Rcap, H, img_rows, row] of a primed pool, ring (the caches are rings of Lmax rows: klen counts positions),
+    grid_rows (0, or the pool's longest image) and the optional e_trace beside trace."""
+    return decode_arm_args(cache, image, primed=True, ring=1 if ring else 0, grid_rows=int(grid_rows), **fields)
+
+
+def decode_arm_primed_chunk_rows() -> int:
+    """Image rows per chunk workgroup of commu_decode_arm_primed."""
+    return int(call("commu_decode_arm_primed_chunk_rows"))
+
+
+def decode_arm_primed(args, njobs: int):
+    """ONE launch that arms njobs (slot, entry) jobs of a primed pool (commu_decode_arm_primed): the image is copied by
+    one workgroup per (layer, head, job, chunk of rows); 0 jobs launch nothing."""
+    args.njobs = int(njobs)
+    call("commu_decode_arm_primed", C.byref(args), _s())
 
 
 # ---------------------------------------------------------------------------------------------- shared prompt prefix (opt-in)

@@ -146,13 +146,16 @@ def parse_args():
     # not in the reference (one request per process and per model load): MANY requests decoded in one pool of decode slots
     # (commu_amd.generate.BatchedGenerator.generate_pool).  FILE.json: a list of objects whose keys are the input arguments
     # of one request -- bpm .. chord_progression, num_generate, top_k, temperature, top_p, optional seed, max_rounds,
-    # pitch_min, pitch_max, logit_bias -- each of which gets exactly the sequences a run of its own with --decode_slots 1 and
-    # the same seed writes.  The model arguments apply to the whole pool; sequences.json becomes {"requests": [...]}.
+    # pitch_min, pitch_max, logit_bias, prompt_tokens -- each of which gets exactly the sequences a run of its own with
+    # --decode_slots 1 and the same seed writes.  prompt_tokens: a list of token ids the request's sequences continue (what
+    # --prompt_tokens FILE holds for a single request; every request may carry its own).  The model arguments apply to the
+    # whole pool; sequences.json becomes {"requests": [...]}.
     # Refused with any single-request input argument, --prompt_tokens, --share_prompt, --parity, and --gpus above 1.
     input_arg_parser.add_argument("--requests", type=str, default=None, metavar="FILE.json",
                                   help="a JSON list of requests (objects of input arguments: bpm .. chord_progression, "
                                        "num_generate, top_k, temperature, top_p, optional seed, max_rounds, pitch_min, "
-                                       "pitch_max, logit_bias) decoded in ONE pool of --decode_slots slots; sequences.json "
+                                       "pitch_max, logit_bias, prompt_tokens: a list of token ids the request "
+                                       "continues) decoded in ONE pool of --decode_slots slots; sequences.json "
                                        "becomes {\"requests\": [...]}")
     return {"model_args": model_arg_parser, "input_args": input_arg_parser}
 
@@ -236,6 +239,8 @@ REQUEST_META_KEYS = ("bpm", "audio_key", "time_signature", "pitch_range", "num_m
                      "rhythm", "min_velocity", "max_velocity", "chord_progression")
 REQUEST_KEYS = REQUEST_META_KEYS + ("num_generate", "top_k", "temperature", "top_p", "seed", "max_rounds", "pitch_min",
                                     "pitch_max", "logit_bias")
+# (keys a request object may carry and that its parsed dict holds only then: prompt_tokens, the token ids it continues)
+REQUEST_OPTIONAL_KEYS = ("prompt_tokens",)
 # (single-request input arguments that --requests replaces, with the value the parser gives them when they are not named)
 SINGLE_REQUEST_ARGS = {**{k: None for k in REQUEST_META_KEYS}, "genre": "cinematic", "rhythm": "standard",
                        "num_generate": None, "top_k": 32, "temperature": 0.95, "top_p": 1.0, "max_rounds": None,
@@ -246,8 +251,8 @@ def check_requests(model_args, input_args):
     """--requests FILE.json as a list of per-request argument dicts (None without the flag): every key of REQUEST_KEYS,
     the parser's defaults where an object does not name one (seed 0).  Host code only, run before a model is loaded;
     ValueError that says what is wrong -- a single-request input argument, --prompt_tokens, --share_prompt or --parity
-    beside --requests, --gpus above 1, a file that is not a JSON list of objects, an unknown key or a missing
-    num_generate (with the index of the request)."""
+    beside --requests, --gpus above 1, a file that is not a JSON list of objects, an unknown key, a missing
+    num_generate or a prompt_tokens value that is not a list of integers (with the index of the request)."""
     path = getattr(input_args, "requests", None)
     if path is None:
         return None
@@ -259,8 +264,8 @@ def check_requests(model_args, input_args):
                      ("--share_prompt", bool(getattr(model_args, "share_prompt", False))),
                      ("--parity", bool(getattr(model_args, "parity", False)))):
         if on:
-            raise ValueError(f"--requests cannot be combined with {flag}: the request pool serves unprimed requests on the "
-                             "bf16 and fp8 K/V caches")
+            raise ValueError(f"--requests cannot be combined with {flag}: a request of the pool carries its own prompt "
+                             "(\"prompt_tokens\" in its object); the pool runs on the bf16 and fp8 K/V caches")
     gpus = getattr(input_args, "gpus", None)
     if gpus is not None and gpus > 1:
         raise ValueError(f"--requests with --gpus {gpus}: the request pool runs on one GPU (dealing requests to replicas "
@@ -279,14 +284,18 @@ def check_requests(model_args, input_args):
         if not isinstance(r, dict):
             raise ValueError(f"--requests: {path}: request {i}: an object of input arguments expected, got "
                              f"{type(r).__name__}")
-        unknown = sorted(set(r) - set(REQUEST_KEYS))
+        unknown = sorted(set(r) - set(REQUEST_KEYS) - set(REQUEST_OPTIONAL_KEYS))
         if unknown:
-            raise ValueError(f"--requests: {path}: request {i}: unknown key {unknown[0]!r} (known: {', '.join(REQUEST_KEYS)})")
+            raise ValueError(f"--requests: {path}: request {i}: unknown key {unknown[0]!r} (known: "
+                             f"{', '.join(REQUEST_KEYS + REQUEST_OPTIONAL_KEYS)})")
         if "num_generate" not in r:
             raise ValueError(f"--requests: {path}: request {i}: num_generate is missing")
         n = r["num_generate"]
         if isinstance(n, bool) or not isinstance(n, int) or n < 1:
             raise ValueError(f"--requests: {path}: request {i}: num_generate: an integer >= 1 expected, got {n!r}")
+        pt = r.get("prompt_tokens", [])
+        if not isinstance(pt, list) or not all(isinstance(t, int) and not isinstance(t, bool) for t in pt):
+            raise ValueError(f"--requests: {path}: request {i}: prompt_tokens: a JSON list of token ids expected, got {pt!r}")
         out.append({**SINGLE_REQUEST_ARGS, "seed": 0, **r})
     return out
 

@@ -897,6 +897,91 @@ typedef struct commu_decode_arm_args {
 } commu_decode_arm_args;
 int commu_decode_arm_args_bytes(void);
 int commu_decode_arm(const commu_decode_arm_args* a, hipStream_t stream);
+/* ---- request pool, PRIMED entries: the arm launch of a pool whose requests continue a prompt of their own
+ * (csrc/decode_arm_primed.hip).  An entry's K/V image is then as long as its replayed prompt (img_rows: hundreds to
+ * thousands of rows, not 16), so the image is copied ROW-PARALLEL: grid (L H, njobs, ceil(R / C)) workgroups of 128
+ * threads, R = min(img_rows, Lmax) (min(.., grid_rows) where grid_rows > 0), C = commu_decode_arm_primed_chunk_rows();
+ * chunk workgroup z moves rows z C .. min(n, (z + 1) C) - 1 of its (layer, head) in every cache tensor with 16-byte
+ * vector loads and stores, four independent loads per thread issued before the first store; a chunk workgroup whose first
+ * row is >= n exits (chunk 0 stays: the L H workgroups of a job's chunk 0 share the slot arrays' rows as the waves of
+ * commu_decode_arm do).  Plain vector stores only; no atomics, no LDS, no synchronisation between workgroups.
+ * Every field that commu_decode_arm_args has means what it means there (img_rows is its ctx_rows).  What differs, per job
+ * (slot, entry) with 0 <= slot < B and 0 <= entry < Rcap (others are skipped):
+ *   rows: with R as above and k = max(e_klen0[entry], 0), n = min(k, R) rows are copied --
+ *     cache[i][l][slot][h][0 .. n) = image[i][l][entry][h][0 .. n) --, rows >= n and other slots are not touched;
+ *     ring == 0 (linear cache): klen[slot] = n;
+ *     ring != 0 (the cache is a ring of Lmax rows, klen counts POSITIONS and the attention takes the row modulo Lmax):
+ *       klen[slot] = k, unclamped; the image is then either no longer than any prompt needs (img_rows < Lmax, k <= img_rows
+ *       is the caller's duty) or a ring with the cache's modulus (img_rows == Lmax), so min(k, Lmax) physical rows are the
+ *       whole image of a wrapped prompt;
+ *   seq[slot][0 .. m) = e_seq[entry][0 .. m), m = e_state[entry][0] (the record's length word) clamped to [0, ld_head];
+ *     the words of seq[slot] from m on are not touched;
+ *   trace[slot][0 .. ld_trace) = e_trace[entry] where trace and e_trace are given (the replay's trace continues into the
+ *     decode), zeros where only trace is;
+ *   everything else as commu_decode_arm: klen, state, chords, wrong zeroed, utable, seq_logp NaN (prompt tokens carry no
+ *     pair), the sampling triple, bias row, grammar / harmony switches, note-order and voice words, class records.
+ *   grid_rows: 0, or an upper bound of every e_klen0 the launch will meet (the pool's longest image): fewer chunk
+ *     workgroups are launched; it is part of the clamp of n above, so a longer entry is truncated, never overrun.
+ * njobs == 0: nothing is launched, 0.  -22: a struct_bytes other than commu_decode_arm_primed_args_bytes(), and
+ * every condition commu_decode_arm refuses (img_rows for ctx_rows); grid_rows < 0; ring != 0 with img_rows > Lmax. */
+typedef struct commu_decode_arm_primed_args {
+    unsigned struct_bytes;
+    int njobs;
+    const int* jobs;
+    const float* variates;
+    int B, Rcap;
+    /* K/V caches and the store's images */
+    int L, H, Lmax, img_rows, n_cache;
+    int row_bytes[4];
+    void* cache[4];
+    const void* image[4];
+    int ring, grid_rows;
+    /* required slot arrays and their store twins */
+    int* klen;
+    const int* e_klen0;
+    int* state;
+    const int* e_state;
+    int nf;
+    int* seq;
+    const int* e_seq;
+    int ld_seq, ld_head;
+    int* chord_tok;
+    int* chord_pos;
+    const int* e_chord_tok;
+    const int* e_chord_pos;
+    int ld_chord;
+    unsigned char* wrong;
+    int ld_wrong;
+    float* utable;
+    int ld_u;
+    /* optional */
+    float* seq_logp;
+    int* trace;
+    const int* e_trace;
+    int ld_trace;
+    float* temperature_rows;
+    int* top_k_rows;
+    float* top_p_rows;
+    const float* e_temperature;
+    const int* e_top_k;
+    const float* e_top_p;
+    float* bias;
+    const float* e_bias;
+    int ld_bias;
+    unsigned char* gram_on;
+    const unsigned char* e_gram_on;
+    unsigned char* harm_on;
+    const unsigned char* e_harm_on;
+    int* order_ctl;
+    const int* e_order;
+    int* voice_ctl;
+    const int* e_voice;
+    int* cls_ctl;
+    const int* e_cls;
+} commu_decode_arm_primed_args;
+int commu_decode_arm_primed_args_bytes(void);
+int commu_decode_arm_primed_chunk_rows(void);
+int commu_decode_arm_primed(const commu_decode_arm_primed_args* a, hipStream_t stream);
 /* dst[b][0:n] = src[b][0:n] where mask[b] != 0 */
 int commu_copy_rows_masked_f32(float* dst, int ldd, const float* src, int lds, const unsigned char* mask, int rows,
                                int n, hipStream_t stream);
