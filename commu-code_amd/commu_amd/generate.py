@@ -555,6 +555,55 @@ def voices_ctl(x, B: int):
                      for b, v in enumerate(x)], dtype=np.int32)
 
 
+# ---- note density: one int32 control word per slot (commu_sample_args.density_ctl).  A slot that is on cannot draw Bar or
+# EOS while the bar it is writing holds fewer than `lo` notes (unless no position is left to draw), nor a position once the
+# bar holds `hi`.  Like the voice cap it is read off the slot's seq when the sampling stage runs, on the voice cap's walk:
+# set_density switches the voice words (and with them the note order) on.
+DENSITY_OFF = -1
+DENSITY_MAX = 255             # (each bound has one byte of the word)
+DENSITY_HI = 256              # the word is lo + DENSITY_HI * hi
+
+
+def density_word(min_notes: int = 0, max_notes: int = 0) -> int:
+    """The control word lo + 256 hi of a lower and an upper bound on a bar's notes (0: none); density_ctl validates it."""
+    return int(min_notes) + DENSITY_HI * int(max_notes)
+
+
+def density_ctl(x, B: int):
+    """A request's density= as the int32 control words of B slots: None / False (off, -1) or an integer word lo + 256 hi
+    with lo, hi in 0 .. 255 (a bar the slot DRAWS holds at least lo and at most hi notes; 0: that bound is not set; with
+    hi >= 1, hi >= max(lo, 1)) -- density_word(lo, hi) -- or one such value per slot.  Pure host code; raises CommuHipError
+    on anything else, with the numbers."""
+    B = int(B)
+
+    def word(v, where):
+        if v is None or v is False or (isinstance(v, np.bool_) and not v):
+            return DENSITY_OFF
+        ok = not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating)) \
+            and np.isfinite(v) and v == np.floor(v) and (v == DENSITY_OFF or 0 <= v < DENSITY_HI * (DENSITY_MAX + 1))
+        if ok and v >= 0:
+            lo, hi = int(v) & 255, int(v) >> 8
+            ok = hi == 0 or hi >= max(lo, 1)
+        if not ok:
+            raise CommuHipError(f"density{where}: None / False (off) or an integer word lo + {DENSITY_HI} hi with lo, hi in "
+                                f"[0, {DENSITY_MAX}] (notes per bar at least / at most; 0 = that bound is not set; hi >= lo "
+                                f"where both are set; -1 = off) expected, got {v!r}")
+        return int(v)
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    if x is None or np.ndim(x) == 0:
+        if isinstance(x, np.ndarray):
+            x = x.item()
+        return np.full(B, word(x, ""), dtype=np.int32)
+    x = list(x)
+    if len(x) != B:
+        raise CommuHipError(f"density: {B} values expected (one per sequence), got {len(x)}")
+    if any(np.ndim(v) != 0 for v in x):
+        raise CommuHipError(f"density: one value per sequence expected, got shape {np.shape(x)}")
+    return np.array([word(v.item() if isinstance(v, np.generic) and not isinstance(v, np.bool_) else v, f"[{b}]")
+                     for b, v in enumerate(x)], dtype=np.int32)
+
+
 class DecodeState:
     """K/V caches + distance-indexed R tables for B sequences of up to Lmax positions.
 
@@ -1128,6 +1177,9 @@ class ForcedDecoder:
         # voice cap (set_voices): likewise the slots' voice words int32 [B] and their host mirror
         self.voice_ctl = None
         self._voice_host = None
+        # note density (set_density): likewise the slots' density words int32 [B] and their host mirror
+        self.density_ctl = None
+        self._density_host = None
         # (the replay of a prompt token takes at most two iterations: the decision to force it, then its append)
         self.ld_trace = 2 * (self.generation_length + 2 + 2 * self.max_prompt) if record_trace else 0
         self.trace = torch.zeros(B, self.ld_trace, dtype=i32, device=dev) if record_trace else None
@@ -1156,12 +1208,13 @@ class ForcedDecoder:
             raise CommuHipError(f"rows: slot numbers in [0, {self.B}) expected, got {rows!r}")
         return idx
 
-    def _first_use(self, rows=False, bias=False, gram=False, harm=False, cls=False, order=False, voices=False):
+    def _first_use(self, rows=False, bias=False, gram=False, harm=False, cls=False, order=False, voices=False,
+                   density=False):
         """What the first use of a per-slot launch input does, for each one asked for that the decoder does not have yet:
         rows uploads the host mirror of the sampling controls (scalar mode kept the mirror only); bias / gram / harm
         allocate their zeroed device buffers (gram and harm: the table and the [B] switches); cls allocates the slots'
         class-control records (set_class_sampling fills them); order allocates the slots' note-order words, all off; voices
-        the slots' voice words, all off.
+        the slots' voice words, all off; density the slots' density words, all off.
         When anything was missing the captured graphs are dropped,
         once: they hold the launches without it."""
         new = False
@@ -1192,6 +1245,10 @@ class ForcedDecoder:
             new = True
             self.voice_ctl = torch.full((self.B,), VOICES_OFF, dtype=torch.int32, device=self.dev)
             self._voice_host = np.full(self.B, VOICES_OFF, dtype=np.int32)
+        if density and self.density_ctl is None:
+            new = True
+            self.density_ctl = torch.full((self.B,), DENSITY_OFF, dtype=torch.int32, device=self.dev)
+            self._density_host = np.full(self.B, DENSITY_OFF, dtype=np.int32)
         if new:
             self.graph = self.graph_long = None
 
@@ -1435,6 +1492,39 @@ class ForcedDecoder:
             for j in idx:
                 self.voice_ctl[int(j)].fill_(int(self._voice_host[j]))
 
+    def set_density(self, value, rows: Optional[Sequence[int]] = None):
+        """The note density for all slots (rows=None) or the listed ones: a word density_word(lo, hi) -- a bar the slot
+        DRAWS holds at least lo and at most hi notes (0: that bound is not set) -- None / False (off), or one such value
+        per addressed slot (density_ctl).  A note is a Position, Velocity, Pitch, Duration group of the slot's seq; the bar
+        being written is what follows the last Bar.  While it holds fewer than lo notes the slot cannot DRAW Bar or EOS --
+        unless the note order, the voice cap and the upper bound together leave no position to draw, in which case the bar
+        may end short -- and once it holds hi notes the slot cannot draw a position: only Bar and EOS remain of the
+        boundary family.  The count rides on the voice cap's walk over seq: a slot switched on here whose voice word is off
+        gets word 0 (no cap, re-striking allowed), and its note order is switched on where it was off (set_voices); switching
+        the density off leaves both as they are.  The state is read off seq when the sampling stage runs (the prompt of a
+        primed slot included: its notes count, and are never removed).  Only DRAWS are constrained: a forced Bar or EOS may
+        close a short bar, a note that starts on a forced position counts but is not prevented, and a bar that the
+        generation length cuts stays as it is.  The first call that switches a slot on allocates the [B] words and drops
+        the captured graphs once; later calls rewrite the words IN PLACE, ordered on the current stream, and a captured
+        graph follows them.  A slot that is off bans nothing.  A decoder that never switched a slot on allocates nothing."""
+        idx = self._slots(rows)
+        new = density_ctl(value, len(idx))                     # (validated before anything changes)
+        if self.density_ctl is None and not bool((new != DENSITY_OFF).any()):
+            return
+        need = [int(j) for j, w in zip(idx, new)
+                if w != DENSITY_OFF and (self._voice_host is None or self._voice_host[j] == VOICES_OFF)]
+        if need:
+            self.set_voices(0, rows=need)                      # (allocates what the voices kernel reads; the note order too)
+        self._first_use(density=True)
+        if np.array_equal(self._density_host[idx], new):
+            return
+        self._density_host[idx] = new
+        if rows is None and len(idx) > 4:
+            self.density_ctl.copy_(torch.from_numpy(self._density_host))
+        else:
+            for j in idx:
+                self.density_ctl[int(j)].fill_(int(self._density_host[j]))
+
     def pre(self):
         call("commu_forcing_pre", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_tok), _p(self.chord_pos),
              self.ld_chord, _p(self.wrong), _p(self.utable), self.ld_u, self.generation_length, _p(self.tok),
@@ -1454,7 +1544,8 @@ class ForcedDecoder:
                         **({} if self.harm is None else {"harmony": self._harm_args()}),
                         **({} if self.cls_ctl is None else {"class_ctl": self._cls_args()}),
                         **({} if self.order_ctl is None else {"note_order": self.order_ctl}),
-                        **({} if self.voice_ctl is None else {"voices": self.voice_ctl}))
+                        **({} if self.voice_ctl is None else {"voices": self.voice_ctl}),
+                        **({} if self.density_ctl is None else {"density": self.density_ctl}))
         call("commu_forcing_post", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_pos), self.ld_chord,
              _p(self.wrong), _p(self.draw), _p(self.token), None, _p(self.state.klen), _p(self.keep),
              self.state.klen_cap, _p(logp), _p(seq_logp), B, _s())
@@ -1478,7 +1569,7 @@ class ForcedDecoder:
             trace=_p(self.trace), ld_trace=self.ld_trace, klen=_p(st.klen), lmax=st.klen_cap,
             bias=_p(self.bias), ld_bias=ld(self.bias), gram=_p(self.gram), ld_gram=ld(self.gram), gram_on=_p(self.gram_on),
             harm=_p(self.harm), ld_harm=ld(self.harm), harm_on=_p(self.harm_on), cls_ctl=_p(self.cls_ctl),
-            order_ctl=_p(self.order_ctl), voice_ctl=_p(self.voice_ctl))
+            order_ctl=_p(self.order_ctl), voice_ctl=_p(self.voice_ctl), density_ctl=_p(self.density_ctl))
         call("commu_decode_sample_post_pre", C.byref(a), _s())
 
     def iteration(self, want_probs: bool = False):
@@ -1738,12 +1829,15 @@ class ForcedDecoder:
     # harmony: True / False switches the slot's harmony constraint for its next attempt (None: the slot keeps its switch).
     # note_order: the slot's note-order control for its next attempt (set_note_order's values; None: the slot keeps its word).
     # voices: the slot's voice word for its next attempt (set_voices' values, False: off; None: the slot keeps its word).
+    # density: the slot's density word for its next attempt (set_density's values, False: off; None: the slot keeps its word).
     def rearm(self, b: int, uniforms_row: Optional[np.ndarray] = None, sampling=None, logit_bias=None, grammar=None,
-              harmony=None, note_order=None, voices=None):
+              harmony=None, note_order=None, voices=None, density=None):
         if note_order is not None:
             self.set_note_order(note_order, rows=[b])
         if voices is not None:
             self.set_voices(voices, rows=[b])
+        if density is not None:
+            self.set_density(density, rows=[b])
         if sampling is not None:
             self.set_sampling(*sampling, rows=[b])
         if logit_bias is not None:
@@ -1943,7 +2037,8 @@ class ForcedDecoder:
                 "e_temperature": z(R, dtype=F32), "e_top_k": z(R), "e_top_p": z(R, dtype=F32),
                 "e_bias": z(R, VPAD, dtype=F32), "e_gram_on": z(R, dtype=u8), "e_harm_on": z(R, dtype=u8),
                 "e_order": torch.full((R,), NOTE_ORDER_OFF, dtype=i32, device=dev),
-                "e_voice": torch.full((R,), VOICES_OFF, dtype=i32, device=dev), "e_cls": z(R, N_CLASSES + 1, 4),
+                "e_voice": torch.full((R,), VOICES_OFF, dtype=i32, device=dev),
+                "e_density": torch.full((R,), DENSITY_OFF, dtype=i32, device=dev), "e_cls": z(R, N_CLASSES + 1, 4),
                 "hdr": hdr, "stage": z(words),
                 # two pinned staging buffers and an event each: the host never overwrites a buffer whose copy is in flight
                 "pin": [torch.zeros(words, dtype=i32).pin_memory() for _ in range(2)],
@@ -1967,7 +2062,8 @@ class ForcedDecoder:
     def _pool_args(self):
         """The arm launch's argument block, rebuilt when an optional array was allocated since (a null twin: not written)."""
         P = self._pool
-        opt = (self.bias, self.gram_on, self.harm_on, self.order_ctl, self.voice_ctl, self.cls_ctl, self.trace)
+        opt = (self.bias, self.gram_on, self.harm_on, self.order_ctl, self.voice_ctl, self.density_ctl, self.cls_ctl,
+               self.trace)
         sig = tuple(None if t is None else t.data_ptr() for t in opt)
         if P["args"] is None or P["sig"] != sig:
             st = self.state
@@ -1989,6 +2085,7 @@ class ForcedDecoder:
                 **on(self.harm_on, {"harm_on": self.harm_on, "e_harm_on": P["e_harm_on"]}),
                 **on(self.order_ctl, {"order_ctl": self.order_ctl, "e_order": P["e_order"]}),
                 **on(self.voice_ctl, {"voice_ctl": self.voice_ctl, "e_voice": P["e_voice"]}),
+                **on(self.density_ctl, {"density_ctl": self.density_ctl, "e_density": P["e_density"]}),
                 **on(self.cls_ctl, {"cls_ctl": self.cls_ctl, "e_cls": P["e_cls"]}))
             P["sig"] = sig
         if P["primed"]:
@@ -1996,11 +2093,11 @@ class ForcedDecoder:
         return P["args"]
 
     def admit(self, entry: int, encoded_meta: Sequence[int], input_data, sampling=None, logit_bias=None, grammar=False,
-              harmony=False, note_order=None, voices=None, class_table=None, primed=None):
+              harmony=False, note_order=None, voices=None, class_table=None, primed=None, density=None):
         """Compose store entry `entry` for a request and upload it with its K/V image: the state record, sequence head
         and chord rows as load() builds them, klen0 = n_cond, the sampling triple (None: the decoder's), the bias row
         (None: zeros), the grammar and harmony switches (they switch on what the decoder has a table for), the
-        note-order and voice words (None: off) and, where the decoder has class records, the request's record row
+        note-order, voice and density words (None: off) and, where the decoder has class records, the request's record row
         (class_table: its NaN-table, None: the base triple in every record).  The image is written by ONE memory-less
         forward over this request's single column [n_cond, 1] and the prefill scatter of the cache's format into the
         store: it does not depend on what else is admitted or decoding.  Everything is ordered on the current stream.
@@ -2022,6 +2119,7 @@ class ForcedDecoder:
         bias = None if logit_bias is None else logit_bias_rows(logit_bias, 1)[0]
         order = note_order_ctl(note_order, 1)
         vox = voices_ctl(voices, 1)
+        den = density_ctl(density, 1)
         if grammar and (self.gram is None or self._gram_host is None):
             raise CommuHipError("admit: grammar switched on, but the decoder has no grammar table (set_grammar)")
         if harmony and (self.harm is None or self._harm_host is None):
@@ -2030,6 +2128,10 @@ class ForcedDecoder:
             raise CommuHipError("admit: a logit bias, but the decoder has no bias rows (set_logit_bias)")
         if order[0] != NOTE_ORDER_OFF and self.order_ctl is None:
             raise CommuHipError("admit: note order switched on, but the decoder has no note-order words (set_note_order)")
+        if den[0] != DENSITY_OFF and self.density_ctl is None:
+            raise CommuHipError("admit: a note density, but the decoder has no density words (set_density)")
+        if den[0] != DENSITY_OFF and vox[0] == VOICES_OFF:
+            vox[0] = 0                        # (set_density: the count rides on the voice cap's walk, word 0 = no cap)
         if vox[0] != VOICES_OFF and self.voice_ctl is None:
             raise CommuHipError("admit: a voice cap, but the decoder has no voice words (set_voices)")
         if vox[0] != VOICES_OFF and order[0] == NOTE_ORDER_OFF:
@@ -2076,6 +2178,7 @@ class ForcedDecoder:
         P["e_harm_on"][entry].fill_(1 if harmony else 0)
         P["e_order"][entry].fill_(int(order[0]))
         P["e_voice"][entry].fill_(int(vox[0]))
+        P["e_density"][entry].fill_(int(den[0]))
         if self.cls_ctl is not None:
             tab = np.full((1, N_CLASSES + 1, 3), np.nan) if class_table is None else class_sampling_table(class_table)[None]
             rec = class_ctl_records(tab, [t, k, p])
@@ -2276,7 +2379,7 @@ class PoolRequest:
     """One request of BatchedGenerator.generate_pool: what generate_stream takes for it alone.  accept: a callable
     (seq, report) -> bool, None accepts every sequence that is not None; logit_bias: one row; grammar / harmony: a
     per-request bool (None: on where the pool has a table), they may only switch on what the pool has a table for;
-    note_order / voices: as generate_stream's.  prompt: token ids that follow the conditioning tokens and that every
+    note_order / voices / density: as generate_stream's.  prompt: token ids that follow the conditioning tokens and that every
     attempt of THIS request continues (generate_stream's prompt=); None or [] is an unprimed request."""
     encoded_meta: Sequence[int]
     input_data: object
@@ -2293,6 +2396,7 @@ class PoolRequest:
     note_order: Optional[object] = None
     voices: Optional[object] = None
     prompt: Optional[Sequence[int]] = None
+    density: Optional[object] = None
 
 
 PoolResult = collections.namedtuple("PoolResult", ["sequences", "attempts_started", "logprobs"])
@@ -2416,7 +2520,7 @@ class BatchedGenerator:
 
     def decoder(self, B, temperature, top_k, max_chords, top_p=1.0, per_slot: bool = False, max_prompt: int = 0,
                 logit_bias=None, shared: bool = False, grammar=None, harmony=None, class_sampling=None,
-                note_order=None, voices=None):
+                note_order=None, voices=None, density=None):
         """The decoder for B slots, its slots set to the given controls (numbers or one value per slot).  per_slot: the
         caller will read log-probabilities or give slots their own controls later (rearm): the array launches from the
         start.  Otherwise one triple for all slots runs the scalar launches, until a second setting arrives for launches
@@ -2426,7 +2530,9 @@ class BatchedGenerator:
         class-control table (None resets every slot to its base triple where an earlier request left one; a decoder that
         never had a table allocates nothing).  note_order: the request's note-order controls (note_order_ctl; None
         switches off what an earlier request left, and allocates nothing on a decoder that never had one).  voices: the
-        request's voice words (voices_ctl), likewise; a slot that gets one has its note order switched on.  shared: the
+        request's voice words (voices_ctl), likewise; a slot that gets one has its note order switched on.  density:
+        the request's density words (density_ctl), likewise; a slot that gets one has its voice word and note order switched
+        on.  shared: the
         decoder that holds the
         request's common prompt once (its own cache layout: kept beside the unshared decoder of the same size)."""
         rows = sampling_rows(B, temperature, top_k, top_p)          # (validated before anything is built)
@@ -2437,6 +2543,7 @@ class BatchedGenerator:
         cls_table = _class_request(class_sampling)
         order = note_order_ctl(note_order, B)
         vox = voices_ctl(voices, B)
+        den = density_ctl(density, B)
         key = (B, self.trace is not None, self.sliding) + (("shared",) if shared else ())
         dec = self._decoders.get(key)
         if dec is None or dec.ld_chord < max_chords or dec.max_prompt < max_prompt:
@@ -2463,6 +2570,8 @@ class BatchedGenerator:
         dec.set_note_order(order)
         # (voice cap: likewise, after the note order -- it switches the note order on where the request left it off)
         dec.set_voices(vox)
+        # (note density: likewise, after the voice cap -- it switches the voice words on where the request left them off)
+        dec.set_density(den)
         return dec
 
     @staticmethod
@@ -2475,8 +2584,10 @@ class BatchedGenerator:
     @torch.no_grad()
     def generate(self, encoded_metas: Sequence[Sequence[int]], input_datas, temperature, top_k, top_p=1.0,
                  return_logprobs: bool = False, prompts: Optional[Sequence[Sequence[int]]] = None, logit_bias=None,
-                 grammar=None, harmony=None, class_sampling=None, note_order=None, voices=None):
-        """temperature / top_k / top_p: a number for the batch or one value per sequence.  voices: None / False, a word
+                 grammar=None, harmony=None, class_sampling=None, note_order=None, voices=None, density=None):
+        """temperature / top_k / top_p: a number for the batch or one value per sequence.  density: None / False, a word
+        density_word(lo, hi) or one per sequence -- a bar such a sequence DRAWS holds at least lo and at most hi notes;
+        switches the sequence's voice word and note order on (ForcedDecoder.set_density).  voices: None / False, a word
         voices_word(N, r) or one per sequence -- at most N notes such a sequence DRAWS sound at once and (r) no pitch is
         struck while it sounds; switches the sequence's note order on (ForcedDecoder.set_voices).  note_order: None / False, True,
         an integer cap in 1 .. 128 or one such value per sequence -- inside a bar the positions such a sequence DRAWS never
@@ -2502,7 +2613,7 @@ class BatchedGenerator:
         dec = self.decoder(B, temperature, top_k, max_chords, top_p, per_slot=return_logprobs, max_prompt=max_prompt,
                            logit_bias=logit_bias, shared=self.shared_prompt and max_prompt > 0, grammar=grammar,
                            harmony=self._one_harmony(harmony), class_sampling=class_sampling, note_order=note_order,
-                           voices=voices)
+                           voices=voices, density=density)
         uniforms = None
         if bool((dec._sampling[0] != 0).any()) or dec.class_samples():
             srcs = self.uniform_sources or [np.random.RandomState(1000 + b).random_sample for b in range(B)]
@@ -2527,7 +2638,7 @@ class BatchedGenerator:
                         accept, top_p=1.0, slots: int = 64, seed: int = 0, max_attempts: Optional[int] = None,
                         return_logprobs: bool = False, prompt: Optional[Sequence[int]] = None, logit_bias=None,
                         share_prompt: bool = False, grammar=None, harmony=None, class_sampling=None, note_order=None,
-                        voices=None):
+                        voices=None, density=None):
         """Attempts of ONE request (the reference's `while idx != num_generate` loop, midi_inferrer.py:338-354, which tries
         one sequence after the other) decoded in up to `slots` parallel slots, CONTINUOUSLY: a slot whose sequence has
         ended is handed to `accept(sequence, report) -> bool` and re-armed with the next attempt while the other slots keep
@@ -2549,6 +2660,8 @@ class BatchedGenerator:
         (ForcedDecoder.set_note_order; the bans are read off a slot's seq, so a re-armed slot needs nothing).
         voices: None / False or a word voices_word(N, r): one setting for every attempt of the request
         (ForcedDecoder.set_voices; likewise read off seq).
+        density: None / False or a word density_word(lo, hi): one setting for every attempt of the request
+        (ForcedDecoder.set_density; likewise read off seq).
         share_prompt (opt-in; also on with BatchedGenerator(shared_prompt=True) when a prompt is given): the K/V of the
         context and the prompt are computed and held once for all slots (ForcedDecoder(shared_prompt=True)); the attempts
         returned are the ones the unshared decoder defines, up to the summation order of the attention."""
@@ -2566,6 +2679,8 @@ class BatchedGenerator:
             raise CommuHipError(f"note_order: one setting for the request expected, got shape {np.shape(note_order)}")
         if voices is not None and np.ndim(voices) != 0:
             raise CommuHipError(f"voices: one setting for the request expected, got shape {np.shape(voices)}")
+        if density is not None and np.ndim(density) != 0:
+            raise CommuHipError(f"density: one setting for the request expected, got shape {np.shape(density)}")
         max_chords = len(input_data.chord_token_components["chord_token"])
         # each control's schedule, validated on its own (the three may have different lengths)
         n_of = lambda x: 1 if np.ndim(x) == 0 else len(x)
@@ -2579,7 +2694,7 @@ class BatchedGenerator:
         dec = self.decoder(B, [t[0] for t in first], [t[1] for t in first], max_chords, [t[2] for t in first],
                            per_slot=return_logprobs or varying, max_prompt=0 if prompt is None else len(prompt),
                            logit_bias=logit_bias, shared=share, grammar=grammar, harmony=harmony,
-                           class_sampling=class_sampling, note_order=note_order, voices=voices)
+                           class_sampling=class_sampling, note_order=note_order, voices=voices, density=density)
         started = B
         sampled = bool((sched[0] != 0).any()) or dec.class_samples()          # (a greedy attempt reads no variate)
         uni = np.stack([self.attempt_uniforms(seed, a, dec.ld_u) for a in range(B)]) if sampled else None
@@ -2738,13 +2853,14 @@ class BatchedGenerator:
         harm_table = _harmony_request(self._one_harmony(harmony))
         cls_table = _class_request(class_sampling)
         # each request's controls, validated before anything is built
-        triples, biases, orders, voxes = [], [], [], []
+        triples, biases, orders, voxes, dens = [], [], [], [], []
         for i, r in enumerate(requests):
             t, k, p = sampling_rows(1, r.temperature, r.top_k, r.top_p)
             triples.append((t[0].item(), int(k[0]), p[0].item()))
             biases.append(None if r.logit_bias is None else logit_bias_rows(r.logit_bias, 1)[0])
             orders.append(int(note_order_ctl(r.note_order, 1)[0]))
             voxes.append(int(voices_ctl(r.voices, 1)[0]))
+            dens.append(int(density_ctl(r.density, 1)[0]))
         B = max(1, min(slots, sum(int(r.need) for r in requests)))
         max_chords = max(len(r.input_data.chord_token_components["chord_token"]) for r in requests)
         key = ("pool", B, self.trace is not None, self.sliding)          # (never shared with generate / generate_stream:
@@ -2768,11 +2884,14 @@ class BatchedGenerator:
         if gram_table is not None:
             dec.set_grammar(gram_table)
         dec.set_harmony(harm_table)
-        use_order = any(o != NOTE_ORDER_OFF for o in orders) or any(v != VOICES_OFF for v in voxes)
+        use_den = any(d != DENSITY_OFF for d in dens)          # (the density rides on the voice words and the note order)
+        use_order = any(o != NOTE_ORDER_OFF for o in orders) or any(v != VOICES_OFF for v in voxes) or use_den
         if cls_table is not None or use_order:
             dec._first_use(rows=True, bias=True, gram=True, harm=True, cls=True, order=use_order)
-        if any(v != VOICES_OFF for v in voxes):
+        if any(v != VOICES_OFF for v in voxes) or use_den:
             dec._first_use(voices=True)
+        if use_den:
+            dec._first_use(density=True)
         if any(b is not None for b in biases):
             dec._first_use(bias=True)
         klen0_max = max([n_cond] + [p["klen0"] for p in replays if p is not None])
@@ -2796,7 +2915,7 @@ class BatchedGenerator:
                               grammar=(gram_table is not None) if r.grammar is None else bool(r.grammar),
                               harmony=(harm_table is not None) if r.harmony is None else bool(r.harmony),
                               note_order=orders[j.request], voices=voxes[j.request], class_table=cls_table,
-                              primed=replays[j.request])
+                              primed=replays[j.request], density=dens[j.request])
                 sampled = triples[j.request][0] != 0 or cls_samples          # (a greedy attempt reads no variate)
                 staged.append((j.slot, j.entry, self.attempt_uniforms(r.seed, j.attempt, dec.ld_u) if sampled else None))
                 if held[j.slot] is not None and held[j.slot] != j.request:

@@ -259,7 +259,7 @@ class InferenceTask:
 
     def execute(self, encoded_meta, max_rounds: Optional[int] = None, return_logprobs: bool = False,
                 prompt: Optional[List[int]] = None, logit_bias=None, grammar=None, harmony=None,
-                class_sampling=None, note_order=None, voices=None):                                        # :338-354
+                class_sampling=None, note_order=None, voices=None, density=None):                          # :338-354
         """return_logprobs (not in the reference): (sequences, their log-probability arrays -- ForcedDecoder.logprobs).
         prompt (not in the reference): token ids that follow the meta tokens; every attempt continues them (primed
         generation, BatchedGenerator.generate_stream) and every returned sequence starts with [0] + meta + prompt.
@@ -273,7 +273,9 @@ class InferenceTask:
         note_order (not in the reference): True or a cap of 1 .. 128 notes per position -- inside a bar the drawn
         positions never go back and no pitch is drawn twice at one position (ForcedDecoder.set_note_order).
         voices (not in the reference): a word generate.voices_word(N, r) -- at most N drawn notes sound at once and (r) no
-        pitch is struck while it sounds; switches the note order on (ForcedDecoder.set_voices)."""
+        pitch is struck while it sounds; switches the note order on (ForcedDecoder.set_voices).
+        density (not in the reference): a word generate.density_word(lo, hi) -- a drawn bar holds at least lo and at most hi
+        notes; switches the voice word and the note order on (ForcedDecoder.set_density)."""
         from ..generate import BatchedGenerator
         data = self.input_data
         glen = self.inference_cfg.GENERATION.generation_length
@@ -301,6 +303,9 @@ class InferenceTask:
         # (likewise: generate.py --max_voices / --no_restrike, the voice word)
         if voices is None and getattr(self.inference_cfg.GENERATION, "voices", None) is not None:
             voices = int(self.inference_cfg.GENERATION.voices)
+        # (likewise: generate.py --min_notes_per_bar / --max_notes_per_bar, the density word)
+        if density is None and getattr(self.inference_cfg.GENERATION, "density", None) is not None:
+            density = int(self.inference_cfg.GENERATION.density)
         gen = BatchedGenerator(self.model, self.device, glen, mlen, sliding=sliding, kv_dtype=kv_dtype,
                                **({"shared_prompt": True} if share else {}))
 
@@ -324,7 +329,8 @@ class InferenceTask:
                                   **({} if harmony is None else {"harmony": harmony}),
                                   **({} if class_sampling is None else {"class_sampling": class_sampling}),
                                   **({} if note_order is None else {"note_order": note_order}),
-                                  **({} if voices is None else {"voices": voices}))
+                                  **({} if voices is None else {"voices": voices}),
+                                  **({} if density is None else {"density": density}))
         return (res[0], res[2]) if return_logprobs else res[0]
 
     def execute_pool(self, items, return_logprobs: bool = False, harmony=None):
@@ -333,7 +339,7 @@ class InferenceTask:
         temperature, top_k, top_p), seed, max_rounds, logit_bias, prompt (token ids the request's sequences continue, None
         or [] for none).  Every request is accepted by the two validators of
         execute() and bounded by max_rounds x num_generate attempts, as there; the pool-wide options (grammar, harmony,
-        class_sampling, note_order, voices, decode_slots, kv_cache, sliding_memory) come from the inference configuration
+        class_sampling, note_order, voices, density, decode_slots, kv_cache, sliding_memory) come from the inference configuration
         as in execute().  Returns generate_pool's PoolResult list."""
         from ..generate import BatchedGenerator, PoolRequest
         G = self.inference_cfg.GENERATION
@@ -349,6 +355,7 @@ class InferenceTask:
             class_sampling = read_class_sampling(json.loads(G.class_sampling))[0]
         note_order = None if getattr(G, "note_order", None) is None else int(G.note_order)
         voices = None if getattr(G, "voices", None) is None else int(G.voices)
+        density = None if getattr(G, "density", None) is None else int(G.density)
 
         def accept(seq, rep) -> bool:
             self.attempts += 1
@@ -367,6 +374,6 @@ class InferenceTask:
                                     top_p=getattr(d, "top_p", 1.0), seed=int(it.get("seed") or 0),
                                     max_attempts=None if mr is None else int(mr) * int(d.num_generate), accept=accept,
                                     logit_bias=it.get("logit_bias"), note_order=note_order, voices=voices,
-                                    prompt=None if not it.get("prompt") else list(it["prompt"])))
+                                    prompt=None if not it.get("prompt") else list(it["prompt"]), density=density))
         return gen.generate_pool(reqs, slots=int(getattr(G, "decode_slots", 64)), grammar=grammar, harmony=harmony,
                                  class_sampling=class_sampling, return_logprobs=return_logprobs)

@@ -75,6 +75,15 @@ class ModelInitializeTask:
                 + (256 if getattr(self.model_args, "no_restrike", False) else 0)
         if vword is not None:
             cfg.GENERATION.voices = int(vword)
+        # generate.py --min_notes_per_bar / --max_notes_per_bar (not in the reference): the density word lo + 256 hi
+        # (generate.py check_density)
+        dword = getattr(self.model_args, "density_word", None)
+        if dword is None and (getattr(self.model_args, "min_notes_per_bar", None) is not None
+                              or getattr(self.model_args, "max_notes_per_bar", None) is not None):   # (a caller that skipped the check)
+            dword = int(getattr(self.model_args, "min_notes_per_bar", None) or 0) \
+                + 256 * int(getattr(self.model_args, "max_notes_per_bar", None) or 0)
+        if dword is not None:
+            cfg.GENERATION.density = int(dword)
         # generate.py --decode_slots (not in the reference): attempts decoded side by side (64 unless the key is set)
         if getattr(self.model_args, "decode_slots", None) not in (None, 64):
             cfg.GENERATION.decode_slots = int(self.model_args.decode_slots)

@@ -934,7 +934,7 @@ def _check_draw_state(kind, device, specs):
 
 def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=None, token=None, probs_out=None,
                 top_p=1.0, logp_out=None, bias=None, V=729, grammar=None, harmony=None, class_ctl=None,
-                note_order=None, voices=None):
+                note_order=None, voices=None, density=None):
     """In-place temperature + softmax + top-k + wrong-token mask + inverse-CDF draw per sequence.
     logits: fp32 [nseq, >=V] (row stride = ld), modified in place (logits[:, 1:V] /= temperature).
     top_p < 1: nucleus filter after the top-k / rejected-token step (an extra mode; the reference has top-k only).
@@ -975,7 +975,12 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
     N + 256 r -- at most N notes of seq[b][0 : state[b][0]] may sound at the onset drawn next (N = 0: no cap), and with r = 1
     no pitch that still sounds may be drawn.  The bans join the note order's in the same select.  One kernel serves it, the
     note-order kernel's with the scan continued to the second BAR: note_order= is required
-    (commu_sample_args.voice_ctl)."""
+    (commu_sample_args.voice_ctl).
+    density: int32 [nseq] on the device of the logits, one control word per sequence (generate.density_ctl): -1 off, else
+    lo + 256 hi -- with C the complete notes of seq[b][0 : state[b][0]] behind its last BAR, every POSITION id is banned once
+    C >= hi >= 1, and BAR and EOS while C < lo unless no position is left to draw.  The bans join the note order's and the
+    voice cap's in the same select.  One kernel serves it, the voices kernel's with the count: voices= is required
+    (commu_sample_args.density_ctl)."""
     nseq = logits.shape[0]
     V = int(V)
     assert logits.dtype == F32 and logits.stride(1) == 1
@@ -1039,6 +1044,13 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
         _check_draw_state("voices", logits.device, (
             (voices, "controls", torch.int32, "[%d]" % nseq, lambda t: tuple(t.shape) == (nseq,)),))
         a.voice_ctl = _p(voices)
+    if density is not None:
+        if voices is None:
+            raise CommuHipError("density: voices= expected as well (the one kernel counts on the voice cap's walk; pass words "
+                                "that are all 0 where there is no cap)")
+        _check_draw_state("density", logits.device, (
+            (density, "controls", torch.int32, "[%d]" % nseq, lambda t: tuple(t.shape) == (nseq,)),))
+        a.density_ctl = _p(density)
     if harmony is not None:
         htable, hon, hstate, chord_tok = harmony
         _check_draw_state("harmony", logits.device, (

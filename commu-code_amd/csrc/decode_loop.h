@@ -202,7 +202,23 @@ struct Voices {
 };
 constexpr int VOX_BINS = 128;     // LDS histogram of the note ends: slot 128 - e for e in 1 .. 128 (lane l reads slots 2l, 2l + 1)
 constexpr int TOK_VEL_LO = 131, TOK_VEL_HI = 194, TOK_DUR_LO = 304, TOK_DUR_HI = 431;
-template <bool BIAS, bool GRAM = false, bool HARM = false, bool CLS = false, bool ORD = false, bool VOX = false>
+// DEN (Density: one int32 control per sequence, -1 off, else lo + 256 hi with lo, hi in 0 .. 255; 0: that bound is not set):
+//   bounds on the notes of the bar being written.  With NOTE and beta as for VOX, C = the number of notes with beta == 0 (the
+//   complete groups behind the last BAR of S, or anywhere in S when it holds none).  UPPER (hi >= 1 and C >= hi): every
+//   POSITION id 432 .. 559 is banned -- the end of the banned position range becomes 560, the maximum of the note order's, the
+//   voice cap's and this one.  LOWER (lo >= 1 and C < lo): BAR and EOS are banned, unless that merged end is 560 already: a
+//   bar that cannot take another onset can still end (without the waiver such a row would have nothing left of the boundary
+//   family and every attempt would end by Q12).  The bans join the select of ORD and VOX, so a draw is bit for bit the VOX
+//   kernel's with bias[b] = -inf at these ids.
+//   THE COUNT rides on the voice walk, which already visits every note back to the second BAR from the end: one more ballot
+//   of `note & beta == 0` per chunk, its popcount carried in a scalar.  No LDS, no load but the control word, the same trip
+//   count.  lo, hi, C and the waiver are scalars; BAR and EOS are ids 2 and 1 of lane 0.  An off word runs the same walk and
+//   bans nothing.  DEN needs VOX.
+struct Density {
+    int ctl;                // the sequence's control as the caller loaded it
+};
+template <bool BIAS, bool GRAM = false, bool HARM = false, bool CLS = false, bool ORD = false, bool VOX = false,
+          bool DEN = false>
 __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restrict__ logits, int ld, int V,
                                                  const unsigned char* __restrict__ wrong, int ldw,
                                                  const float* __restrict__ uni,
@@ -214,10 +230,12 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
                                                  Grammar g = Grammar{nullptr, 0, nullptr, 0, 0, 0},
                                                  Harmony h = Harmony{nullptr, 0, nullptr, 0, 0, 0},
                                                  ClassControls cc = ClassControls{nullptr},
-                                                 NoteOrder no = NoteOrder{-1}, Voices vx = Voices{-1}) {
+                                                 NoteOrder no = NoteOrder{-1}, Voices vx = Voices{-1},
+                                                 Density dn = Density{-1}) {
     static_assert(!CLS || GRAM, "the class key is the grammar's previous token");
     static_assert(!ORD || CLS, "one note-order instantiation: the class kernel's with the scan");
     static_assert(!VOX || ORD, "one voices instantiation: the note-order kernel's with the longer scan");
+    static_assert(!DEN || VOX, "one density instantiation: the voices kernel's with the count of the open bar's notes");
     float* lg = logits + (size_t)b * ld;
     // The optional per-sequence inputs -- the active flag and this sequence's controls -- are loaded unconditionally: a null
     // array reads a valid word of this sequence instead (token[b], logits[b][0]), which is then ignored.  So they are in
@@ -312,6 +330,7 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
         // (VOX) the ends' histogram, the sounding pitches' flags and the BARs passed in the chunks so far
         int *vflag = nullptr, *vhist = nullptr;
         int nbar = 0;
+        int dcount = 0;                         // (DEN) the notes with beta == 0 in the chunks so far
         if constexpr (VOX) {
             static_assert(VOX_BINS == 2 * 64, "two bins per lane");
             __shared__ __attribute__((aligned(16))) int vflag_lds[ORD_FLAGS];
@@ -365,6 +384,7 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
                 // (phase 0 here: no breaker down to this chunk's last index, so this note's POSITION is j itself)
                 const int g0 = pos == TOK_BAR ? 0 : pos - TOK_POS0;
                 if (note & ((phase == 0) | (end > g0))) vflag[t1] = 1;
+                if constexpr (DEN) dcount += __popcll(__ballot(note & (beta == 0)));
                 nbar += __popcll(bars);
             }
             start -= 64;
@@ -410,6 +430,15 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
             }
             vdm = (strike != 0 && base < ORD_FLAGS) ? vdm : 0u;
         }
+        bool dend = false;                       // (DEN) BAR and EOS are banned: the open bar holds fewer notes than asked for
+        if constexpr (DEN) {
+            static_assert(TOK_EOS < PER_LANE && TOK_BAR < PER_LANE, "lane 0 owns BAR and EOS");
+            const int dctl = __builtin_amdgcn_readfirstlane(dn.ctl);
+            const int dlo = dctl >= 0 ? (dctl & 255) : 0, dhi = dctl >= 0 ? ((dctl >> 8) & 255) : 0;
+            hi = (dhi >= 1 && dcount >= dhi) ? TOK_POS0 + POS_RES : hi;
+            // (the waiver: every position is banned already, by the three rules together -- the bar may end)
+            dend = dlo >= 1 && dcount < dlo && hi != TOK_POS0 + POS_RES;
+        }
         // the lane's 12 flags as 16-byte LDS reads, unconditional (the lanes past the flags read the last owner's and
         // drop them), packed into a bit mask without a branch: behind a branch per element they were 12 dependent LDS
         // round trips and some 200 instructions
@@ -425,6 +454,7 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
         const unsigned pm = ((1u << hi_e) - 1u) & ~((1u << lo_e) - 1u);          // (empty while hi <= 432)
         omask = pm | ((on && base < ORD_FLAGS) ? dm : 0u);
         if constexpr (VOX) omask |= vdm;
+        if constexpr (DEN) omask |= (dend && base == 0) ? ((1u << TOK_EOS) | (1u << TOK_BAR)) : 0u;
     }
     if (active != nullptr && act_row == 0) return -2;
     // ---- calc_probs

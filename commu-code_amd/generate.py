@@ -22,6 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 DECODE_SLOTS_MIN, DECODE_SLOTS_MAX, DECODE_SLOTS_DEFAULT = 1, 256, 64          # --decode_slots
 MAX_NOTES_MIN, MAX_NOTES_MAX = 1, 128                                             # --max_notes
 MAX_VOICES_MIN, MAX_VOICES_MAX = 1, 128                                           # --max_voices
+NOTES_PER_BAR_MIN, NOTES_PER_BAR_MAX = 1, 255                                     # --min_notes_per_bar / --max_notes_per_bar
 
 
 def parse_args():
@@ -99,6 +100,22 @@ def parse_args():
     model_arg_parser.add_argument("--no_restrike", action="store_true",
                                   help="no drawn pitch is struck while it still sounds (implies --note_order; covers what "
                                        "--max_voices covers)")
+    # not in the reference (whose conditioning has no token for how many notes a bar holds: with Bar allowed at every note
+    # boundary some bars close after one note or none, others run to dozens): --min_notes_per_bar N -- no Bar or EOS is
+    # DRAWN while the bar being written holds fewer than N notes, unless no position is left to draw; --max_notes_per_bar
+    # N -- no position is drawn once it holds N (only Bar and EOS remain).  Both imply --note_order.  Not covered: notes
+    # inside --prompt_tokens (they count, and are never removed); a note that starts on a forced position (a first chord
+    # inside its bar, two chords in one bar: it counts, and cannot be prevented); a bar cut by the generation length; forced
+    # tokens (a forced Bar or EOS may close a short bar); a strict --harmony, pitch range or --max_notes that leaves no
+    # pitch for a drawn position ends that attempt as before.  With --requests they hold for the whole pool.
+    model_arg_parser.add_argument("--min_notes_per_bar", default=None, metavar="N",
+                                  help=f"at least N notes in every bar that is drawn, {NOTES_PER_BAR_MIN} .. "
+                                       f"{NOTES_PER_BAR_MAX} (implies --note_order; waived when no position is left).  Not "
+                                       "covered: bars closed by a forced token or cut by the generation length")
+    model_arg_parser.add_argument("--max_notes_per_bar", default=None, metavar="N",
+                                  help=f"at most N notes in every bar that is drawn, {NOTES_PER_BAR_MIN} .. "
+                                       f"{NOTES_PER_BAR_MAX}, not below --min_notes_per_bar (implies --note_order).  Not "
+                                       "covered: notes inside --prompt_tokens, a note that starts on a forced position")
     # not in the reference (which decodes one sequence at a time): how many attempts are decoded side by side.  1 .. 256;
     # up to 256 slots run the fused layer-tail launches ("Supported shapes").  The sequences returned do
     # not depend on it.  (checked by check_decode_slots: the range is named in its message)
@@ -300,6 +317,33 @@ def check_requests(model_args, input_args):
     return out
 
 
+def check_density(model_args):
+    """--min_notes_per_bar / --max_notes_per_bar as the density control word lo + 256 hi (None: neither flag); host code
+    only, ValueError that names the range.  Written back to model_args.density_word, which travels to the replicas
+    (ModelInitializeTask puts it into the inference configuration); either flag switches --note_order on."""
+    got = {}
+    for flag in ("min_notes_per_bar", "max_notes_per_bar"):
+        v = getattr(model_args, flag, None)
+        if v is None:
+            continue
+        try:
+            n = int(v) if not isinstance(v, (bool, float)) else None
+        except (TypeError, ValueError):
+            n = None
+        if n is None or not NOTES_PER_BAR_MIN <= n <= NOTES_PER_BAR_MAX:
+            raise ValueError(f"--{flag}: an integer in [{NOTES_PER_BAR_MIN}, {NOTES_PER_BAR_MAX}] expected, got {v!r}")
+        got[flag] = n
+    lo, hi = got.get("min_notes_per_bar", 0), got.get("max_notes_per_bar", 0)
+    if lo and hi and hi < lo:
+        raise ValueError(f"--max_notes_per_bar: not below --min_notes_per_bar expected, got {hi} < {lo}")
+    word = None
+    if got:
+        word = lo + 256 * hi
+        model_args.note_order = True
+    model_args.density_word = word
+    return word
+
+
 def read_constraints(path=None, pitch_min=None, pitch_max=None):
     """The constraint row of --logit_bias / --pitch_min / --pitch_max (None when none of them is given); host code only,
     raises (commu_amd.generate.CommuHipError, ValueError) on a malformed file or an empty range."""
@@ -401,6 +445,7 @@ def main(model_args, input_args, training_cfg=None, device_indices=None):
     check_share_prompt(model_args, input_args)          # (likewise)
     check_decode_slots(model_args)                      # (likewise)
     check_voices(model_args)                            # (likewise; ahead of the note order, which it switches on)
+    check_density(model_args)                           # (likewise)
     check_note_order(model_args)                        # (likewise)
     in_args = dict(vars(input_args))
     in_args.pop("requests", None)

@@ -516,6 +516,26 @@ int commu_transpose_heads(const void* src, int ld, const float* bias, void* dst,
  *     ONE kernel serves it, the note-order kernel with the longer walk: voice_ctl requires order_ctl and everything
  *     order_ctl requires, else -22.  Validating the words is the caller's job (generate.voices_ctl).  The same field, with
  *     the same meaning and the same refusal, is in commu_decode_loop_args.  Null: the launch that never heard of it.
+ * NOTE DENSITY (the reference's conditioning has no token for how many notes a bar holds; with BAR allowed at every note
+ * boundary its sampler closes bars after one note or none and lets others run to dozens)
+ *   density_ctl: int32 [nseq], one control word per sequence: -1 off, else lo + 256 hi with lo, hi in 0 .. 255 (0: that
+ *     bound is not set; a word with hi >= 1 has hi >= max(lo, 1)).  Defined on seq alone when the stage runs, with L, S, NOTE
+ *     and beta as for voice_ctl.  C is the number of notes with beta == 0: the complete POSITION, VELOCITY, PITCH, DURATION
+ *     groups behind the last BAR of S, or anywhere in S when it holds no BAR.  UPPER (hi >= 1 and C >= hi); BANNED: every
+ *     POSITION id 432 .. 559 -- of the boundary family only BAR and EOS remain.  LOWER (lo >= 1 and C < lo); BANNED: BAR (2)
+ *     and EOS (1), UNLESS the position range that order_ctl, voice_ctl and the upper bound ban together already covers all
+ *     128 positions (its end is 560): a bar that cannot take another onset can still end.  The bans join order_ctl's and
+ *     voice_ctl's in the same select (positions [432, max of the three ends), the two ids selected to -inf likewise), so all
+ *     that is said for order_ctl holds: before top-k, never written back, probs_out exactly 0, `full` the log-softmax of y,
+ *     token -1 when nothing is left.  A draw is BIT FOR BIT the draw of the call without density_ctl and with bias[b] = -inf
+ *     at these ids; an off word, or one that bans nothing, is bit for bit the call without the field.
+ *     NOT COVERED: notes inside a prompt count toward C but are never removed; a note that starts on a FORCED position (a
+ *     first chord inside its bar, two chords in one bar) counts but cannot be prevented; a bar that ends because the
+ *     generation length ran out; forced tokens are never affected (a forced BAR or EOS closes a bar with C < lo).
+ *     ONE kernel serves it, the voices kernel with the count on the same walk: density_ctl requires voice_ctl and
+ *     everything voice_ctl requires, else -22.  Validating the words is the caller's job (generate.density_ctl).  The same
+ *     field, with the same meaning and the same refusal, is in commu_decode_loop_args.  Null: the launch that never heard of
+ *     it.
  * WHAT gram / harm READ
  *   state: the forcing records, int32 [nseq][commu_forcing_state_ints()]; seq int32 [nseq][ld_seq]; chord_tok int32
  *   [nseq][ld_chord].  Not looked at, and may be null, in a call without gram and harm.
@@ -555,6 +575,8 @@ typedef struct commu_sample_args {
     const int* seq;
     const int* chord_tok;
     int ld_seq, ld_chord;
+    /* note density (ahead of order_ctl: the three fields behind it keep their places at the struct's end) */
+    const int* density_ctl;
     /* note order (placed ahead of cls_ctl, which stays the struct's last field) */
     const int* order_ctl;
     /* voice cap (likewise ahead of cls_ctl) */
@@ -778,6 +800,8 @@ typedef struct commu_decode_loop_args {
     const float* harm;
     const unsigned char* harm_on;
     int ld_bias, ld_gram, ld_harm;
+    /* note density (commu_sample_args.density_ctl; likewise ahead of order_ctl) */
+    const int* density_ctl;
     /* note order (commu_sample_args.order_ctl; likewise ahead of cls_ctl) */
     const int* order_ctl;
     /* voice cap (commu_sample_args.voice_ctl; likewise ahead of cls_ctl) */
@@ -832,7 +856,7 @@ int commu_decode_prefill_scatter(const void* qkv, int ld_qkv, int T, int B, void
  *   loop's entry point treats a null array:  seq_logp[slot][0 .. 2 ld_seq) = NaN;  trace[slot][0 .. ld_trace) = 0;
  *   temperature_rows / top_k_rows / top_p_rows [slot] = e_temperature / e_top_k / e_top_p [entry];
  *   bias[slot][0 .. ld_bias) = e_bias[entry];  gram_on / harm_on [slot] = e_gram_on / e_harm_on [entry] (bytes);
- *   order_ctl / voice_ctl [slot] = e_order / e_voice [entry];  cls_ctl[slot][0 .. 32) = e_cls[entry] (int32).
+ *   order_ctl / voice_ctl / density_ctl [slot] = e_order / e_voice / e_density [entry];  cls_ctl[slot][0 .. 32) = e_cls[entry] (int32).
  * tok / active / keep / draw are NOT written: an armed slot sits out the iteration whose decision was taken from its
  * finished record and starts with the next one.  Two jobs of one launch must name different slots (the caller's duty).
  * Nothing but njobs varies between launches; there is no host synchronisation.  Grid: one wave per (job, layer, head).
@@ -888,6 +912,8 @@ typedef struct commu_decode_arm_args {
     const unsigned char* e_gram_on;
     unsigned char* harm_on;
     const unsigned char* e_harm_on;
+    int* density_ctl;
+    const int* e_density;
     int* order_ctl;
     const int* e_order;
     int* voice_ctl;
@@ -919,7 +945,8 @@ int commu_decode_arm(const commu_decode_arm_args* a, hipStream_t stream);
  *   trace[slot][0 .. ld_trace) = e_trace[entry] where trace and e_trace are given (the replay's trace continues into the
  *     decode), zeros where only trace is;
  *   everything else as commu_decode_arm: klen, state, chords, wrong zeroed, utable, seq_logp NaN (prompt tokens carry no
- *     pair), the sampling triple, bias row, grammar / harmony switches, note-order and voice words, class records.
+ *     pair), the sampling triple, bias row, grammar / harmony switches, note-order, voice and density words, class
+ *     records.
  *   grid_rows: 0, or an upper bound of every e_klen0 the launch will meet (the pool's longest image): fewer chunk
  *     workgroups are launched; it is part of the clamp of n above, so a longer entry is truncated, never overrun.
  * njobs == 0: nothing is launched, 0.  -22: a struct_bytes other than commu_decode_arm_primed_args_bytes(), and
@@ -972,6 +999,8 @@ typedef struct commu_decode_arm_primed_args {
     const unsigned char* e_gram_on;
     unsigned char* harm_on;
     const unsigned char* e_harm_on;
+    int* density_ctl;
+    const int* e_density;
     int* order_ctl;
     const int* e_order;
     int* voice_ctl;
