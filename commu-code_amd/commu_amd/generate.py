@@ -604,6 +604,59 @@ def density_ctl(x, B: int):
                      for b, v in enumerate(x)], dtype=np.int32)
 
 
+# ---- melodic interval: one int32 control word per slot (commu_sample_args.interval_ctl).  A slot that is on cannot draw a
+# pitch more than `up` semitones above or `down` below the pitch of its last note, nor (u) that pitch itself.  Like the
+# density it is read off the slot's seq when the sampling stage runs, on the voice cap's walk -- but it implies none of the
+# other words: set_interval allocates them all off and leaves them as the slot has them.
+INTERVAL_OFF = -1
+INTERVAL_MAX = 127            # (a leap inside the 128-pitch range)
+INTERVAL_DOWN = 256           # the word is up + INTERVAL_DOWN * down + INTERVAL_UNISON * u
+INTERVAL_UNISON = 65536
+
+
+def interval_word(up: int = 0, down: int = 0, no_repeat: bool = False) -> int:
+    """The control word up + 256 down + 65536 u of a cap on the leap upwards and downwards (semitones; 0: none) and the
+    ban on repeating the pitch; interval_ctl validates it."""
+    return int(up) + INTERVAL_DOWN * int(down) + (INTERVAL_UNISON if no_repeat else 0)
+
+
+def interval_ctl(x, B: int):
+    """A request's interval= as the int32 control words of B slots: None / False (off, -1) or an integer word
+    up + 256 down + 65536 u with up, down in 0 .. 127 (the pitch a slot DRAWS lies at most up semitones above and down below
+    the pitch of its last note; 0: that bound is not set) and u in {0, 1} (1: it is not that pitch) -- interval_word(up,
+    down, no_repeat) -- or one such value per slot.  Pure host code; raises CommuHipError on anything else, with the
+    numbers."""
+    B = int(B)
+
+    def word(v, where):
+        if v is None or v is False or (isinstance(v, np.bool_) and not v):
+            return INTERVAL_OFF
+        ok = not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating)) \
+            and np.isfinite(v) and v == np.floor(v) and (v == INTERVAL_OFF or 0 <= v < 2 * INTERVAL_UNISON)
+        if ok and v >= 0:
+            up, down = int(v) & 255, (int(v) >> 8) & 255
+            ok = up <= INTERVAL_MAX and down <= INTERVAL_MAX
+        if not ok:
+            raise CommuHipError(f"interval{where}: None / False (off) or an integer word up + {INTERVAL_DOWN} down + "
+                                f"{INTERVAL_UNISON} u with up, down in [0, {INTERVAL_MAX}] (semitones above / below the last "
+                                f"note; 0 = that bound is not set), u in [0, 1] (1 = no repeated pitch) and no higher bit "
+                                f"(-1 = off) expected, got {v!r}")
+        return int(v)
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    if x is None or np.ndim(x) == 0:
+        if isinstance(x, np.ndarray):
+            x = x.item()
+        return np.full(B, word(x, ""), dtype=np.int32)
+    x = list(x)
+    if len(x) != B:
+        raise CommuHipError(f"interval: {B} values expected (one per sequence), got {len(x)}")
+    if any(np.ndim(v) != 0 for v in x):
+        raise CommuHipError(f"interval: one value per sequence expected, got shape {np.shape(x)}")
+    return np.array([word(v.item() if isinstance(v, np.generic) and not isinstance(v, np.bool_) else v, f"[{b}]")
+                     for b, v in enumerate(x)], dtype=np.int32)
+
+
 class DecodeState:
     """K/V caches + distance-indexed R tables for B sequences of up to Lmax positions.
 
@@ -1180,6 +1233,9 @@ class ForcedDecoder:
         # note density (set_density): likewise the slots' density words int32 [B] and their host mirror
         self.density_ctl = None
         self._density_host = None
+        # melodic interval (set_interval): likewise the slots' interval words int32 [B] and their host mirror
+        self.interval_ctl = None
+        self._interval_host = None
         # (the replay of a prompt token takes at most two iterations: the decision to force it, then its append)
         self.ld_trace = 2 * (self.generation_length + 2 + 2 * self.max_prompt) if record_trace else 0
         self.trace = torch.zeros(B, self.ld_trace, dtype=i32, device=dev) if record_trace else None
@@ -1209,12 +1265,13 @@ class ForcedDecoder:
         return idx
 
     def _first_use(self, rows=False, bias=False, gram=False, harm=False, cls=False, order=False, voices=False,
-                   density=False):
+                   density=False, interval=False):
         """What the first use of a per-slot launch input does, for each one asked for that the decoder does not have yet:
         rows uploads the host mirror of the sampling controls (scalar mode kept the mirror only); bias / gram / harm
         allocate their zeroed device buffers (gram and harm: the table and the [B] switches); cls allocates the slots'
         class-control records (set_class_sampling fills them); order allocates the slots' note-order words, all off; voices
-        the slots' voice words, all off; density the slots' density words, all off.
+        the slots' voice words, all off; density the slots' density words, all off; interval the slots' interval words,
+        all off.
         When anything was missing the captured graphs are dropped,
         once: they hold the launches without it."""
         new = False
@@ -1249,6 +1306,10 @@ class ForcedDecoder:
             new = True
             self.density_ctl = torch.full((self.B,), DENSITY_OFF, dtype=torch.int32, device=self.dev)
             self._density_host = np.full(self.B, DENSITY_OFF, dtype=np.int32)
+        if interval and self.interval_ctl is None:
+            new = True
+            self.interval_ctl = torch.full((self.B,), INTERVAL_OFF, dtype=torch.int32, device=self.dev)
+            self._interval_host = np.full(self.B, INTERVAL_OFF, dtype=np.int32)
         if new:
             self.graph = self.graph_long = None
 
@@ -1525,6 +1586,41 @@ class ForcedDecoder:
             for j in idx:
                 self.density_ctl[int(j)].fill_(int(self._density_host[j]))
 
+    def set_interval(self, value, rows: Optional[Sequence[int]] = None):
+        """The melodic interval for all slots (rows=None) or the listed ones: a word interval_word(up, down, no_repeat) --
+        the pitch the slot DRAWS lies at most up semitones above and at most down below the pitch of its last note (0: that
+        bound is not set) and, with no_repeat, is not that pitch -- None / False (off), or one such value per addressed slot
+        (interval_ctl).  A note is a Position, Velocity, Pitch, Duration group of the slot's seq; the last note is the one
+        furthest back in seq that at most one Bar follows, so the first note of a sequence, and the first after a whole
+        bar's rest, is free.  The state is read off seq when the sampling stage runs (the prompt of a primed slot included:
+        its last note is the reference of the first draw, its notes are not checked against each other).  Only DRAWS are
+        constrained.  The word implies none of the others: the first call that switches a slot on allocates the [B] words
+        and, where the decoder lacks them, everything the one kernel reads besides -- the density, voice and note-order words
+        (all off), the array launches, a zero bias, an all-off grammar, an all-off harmony table and the class records
+        holding every slot's base triple -- and drops the captured graphs once; later calls rewrite the words IN PLACE,
+        ordered on the current stream, and a captured graph follows them.  A slot that is off bans nothing: it decodes bit
+        for bit what it decoded without the feature.  A decoder that never switched a slot on allocates nothing.  Several
+        notes at one position are compared in token order (the rule is meant for set_voices lines of one voice); a pitch
+        range, bias, strict harmony, note-order or re-strike ban that leaves no pitch inside the window ends the slot by
+        Q12."""
+        idx = self._slots(rows)
+        new = interval_ctl(value, len(idx))                    # (validated before anything changes)
+        if self.interval_ctl is None and not bool((new != INTERVAL_OFF).any()):
+            return
+        fresh_cls = self.cls_ctl is None
+        self._first_use(rows=True, bias=True, gram=True, harm=True, cls=True, order=True, voices=True, density=True,
+                        interval=True)
+        if fresh_cls:          # (no class controls: every record of every slot holds the slot's base triple)
+            self._write_class_ctl(None, np.arange(self.B))
+        if np.array_equal(self._interval_host[idx], new):
+            return
+        self._interval_host[idx] = new
+        if rows is None and len(idx) > 4:
+            self.interval_ctl.copy_(torch.from_numpy(self._interval_host))
+        else:
+            for j in idx:
+                self.interval_ctl[int(j)].fill_(int(self._interval_host[j]))
+
     def pre(self):
         call("commu_forcing_pre", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_tok), _p(self.chord_pos),
              self.ld_chord, _p(self.wrong), _p(self.utable), self.ld_u, self.generation_length, _p(self.tok),
@@ -1545,7 +1641,8 @@ class ForcedDecoder:
                         **({} if self.cls_ctl is None else {"class_ctl": self._cls_args()}),
                         **({} if self.order_ctl is None else {"note_order": self.order_ctl}),
                         **({} if self.voice_ctl is None else {"voices": self.voice_ctl}),
-                        **({} if self.density_ctl is None else {"density": self.density_ctl}))
+                        **({} if self.density_ctl is None else {"density": self.density_ctl}),
+                        **({} if self.interval_ctl is None else {"interval": self.interval_ctl}))
         call("commu_forcing_post", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_pos), self.ld_chord,
              _p(self.wrong), _p(self.draw), _p(self.token), None, _p(self.state.klen), _p(self.keep),
              self.state.klen_cap, _p(logp), _p(seq_logp), B, _s())
@@ -1569,7 +1666,8 @@ class ForcedDecoder:
             trace=_p(self.trace), ld_trace=self.ld_trace, klen=_p(st.klen), lmax=st.klen_cap,
             bias=_p(self.bias), ld_bias=ld(self.bias), gram=_p(self.gram), ld_gram=ld(self.gram), gram_on=_p(self.gram_on),
             harm=_p(self.harm), ld_harm=ld(self.harm), harm_on=_p(self.harm_on), cls_ctl=_p(self.cls_ctl),
-            order_ctl=_p(self.order_ctl), voice_ctl=_p(self.voice_ctl), density_ctl=_p(self.density_ctl))
+            order_ctl=_p(self.order_ctl), voice_ctl=_p(self.voice_ctl), density_ctl=_p(self.density_ctl),
+            interval_ctl=_p(self.interval_ctl))
         call("commu_decode_sample_post_pre", C.byref(a), _s())
 
     def iteration(self, want_probs: bool = False):
@@ -1830,14 +1928,17 @@ class ForcedDecoder:
     # note_order: the slot's note-order control for its next attempt (set_note_order's values; None: the slot keeps its word).
     # voices: the slot's voice word for its next attempt (set_voices' values, False: off; None: the slot keeps its word).
     # density: the slot's density word for its next attempt (set_density's values, False: off; None: the slot keeps its word).
+    # interval: the slot's interval word for its next attempt (set_interval's values, False: off; None: the slot keeps its word).
     def rearm(self, b: int, uniforms_row: Optional[np.ndarray] = None, sampling=None, logit_bias=None, grammar=None,
-              harmony=None, note_order=None, voices=None, density=None):
+              harmony=None, note_order=None, voices=None, density=None, interval=None):
         if note_order is not None:
             self.set_note_order(note_order, rows=[b])
         if voices is not None:
             self.set_voices(voices, rows=[b])
         if density is not None:
             self.set_density(density, rows=[b])
+        if interval is not None:
+            self.set_interval(interval, rows=[b])
         if sampling is not None:
             self.set_sampling(*sampling, rows=[b])
         if logit_bias is not None:
@@ -2038,7 +2139,8 @@ class ForcedDecoder:
                 "e_bias": z(R, VPAD, dtype=F32), "e_gram_on": z(R, dtype=u8), "e_harm_on": z(R, dtype=u8),
                 "e_order": torch.full((R,), NOTE_ORDER_OFF, dtype=i32, device=dev),
                 "e_voice": torch.full((R,), VOICES_OFF, dtype=i32, device=dev),
-                "e_density": torch.full((R,), DENSITY_OFF, dtype=i32, device=dev), "e_cls": z(R, N_CLASSES + 1, 4),
+                "e_density": torch.full((R,), DENSITY_OFF, dtype=i32, device=dev),
+                "e_interval": torch.full((R,), INTERVAL_OFF, dtype=i32, device=dev), "e_cls": z(R, N_CLASSES + 1, 4),
                 "hdr": hdr, "stage": z(words),
                 # two pinned staging buffers and an event each: the host never overwrites a buffer whose copy is in flight
                 "pin": [torch.zeros(words, dtype=i32).pin_memory() for _ in range(2)],
@@ -2062,8 +2164,8 @@ class ForcedDecoder:
     def _pool_args(self):
         """The arm launch's argument block, rebuilt when an optional array was allocated since (a null twin: not written)."""
         P = self._pool
-        opt = (self.bias, self.gram_on, self.harm_on, self.order_ctl, self.voice_ctl, self.density_ctl, self.cls_ctl,
-               self.trace)
+        opt = (self.bias, self.gram_on, self.harm_on, self.order_ctl, self.voice_ctl, self.density_ctl, self.interval_ctl,
+               self.cls_ctl, self.trace)
         sig = tuple(None if t is None else t.data_ptr() for t in opt)
         if P["args"] is None or P["sig"] != sig:
             st = self.state
@@ -2086,6 +2188,7 @@ class ForcedDecoder:
                 **on(self.order_ctl, {"order_ctl": self.order_ctl, "e_order": P["e_order"]}),
                 **on(self.voice_ctl, {"voice_ctl": self.voice_ctl, "e_voice": P["e_voice"]}),
                 **on(self.density_ctl, {"density_ctl": self.density_ctl, "e_density": P["e_density"]}),
+                **on(self.interval_ctl, {"interval_ctl": self.interval_ctl, "e_interval": P["e_interval"]}),
                 **on(self.cls_ctl, {"cls_ctl": self.cls_ctl, "e_cls": P["e_cls"]}))
             P["sig"] = sig
         if P["primed"]:
@@ -2093,11 +2196,11 @@ class ForcedDecoder:
         return P["args"]
 
     def admit(self, entry: int, encoded_meta: Sequence[int], input_data, sampling=None, logit_bias=None, grammar=False,
-              harmony=False, note_order=None, voices=None, class_table=None, primed=None, density=None):
+              harmony=False, note_order=None, voices=None, class_table=None, primed=None, density=None, interval=None):
         """Compose store entry `entry` for a request and upload it with its K/V image: the state record, sequence head
         and chord rows as load() builds them, klen0 = n_cond, the sampling triple (None: the decoder's), the bias row
         (None: zeros), the grammar and harmony switches (they switch on what the decoder has a table for), the
-        note-order, voice and density words (None: off) and, where the decoder has class records, the request's record row
+        note-order, voice, density and interval words (None: off) and, where the decoder has class records, the request's record row
         (class_table: its NaN-table, None: the base triple in every record).  The image is written by ONE memory-less
         forward over this request's single column [n_cond, 1] and the prefill scatter of the cache's format into the
         store: it does not depend on what else is admitted or decoding.  Everything is ordered on the current stream.
@@ -2120,6 +2223,7 @@ class ForcedDecoder:
         order = note_order_ctl(note_order, 1)
         vox = voices_ctl(voices, 1)
         den = density_ctl(density, 1)
+        mel = interval_ctl(interval, 1)
         if grammar and (self.gram is None or self._gram_host is None):
             raise CommuHipError("admit: grammar switched on, but the decoder has no grammar table (set_grammar)")
         if harmony and (self.harm is None or self._harm_host is None):
@@ -2128,6 +2232,8 @@ class ForcedDecoder:
             raise CommuHipError("admit: a logit bias, but the decoder has no bias rows (set_logit_bias)")
         if order[0] != NOTE_ORDER_OFF and self.order_ctl is None:
             raise CommuHipError("admit: note order switched on, but the decoder has no note-order words (set_note_order)")
+        if mel[0] != INTERVAL_OFF and self.interval_ctl is None:
+            raise CommuHipError("admit: a melodic interval, but the decoder has no interval words (set_interval)")
         if den[0] != DENSITY_OFF and self.density_ctl is None:
             raise CommuHipError("admit: a note density, but the decoder has no density words (set_density)")
         if den[0] != DENSITY_OFF and vox[0] == VOICES_OFF:
@@ -2179,6 +2285,7 @@ class ForcedDecoder:
         P["e_order"][entry].fill_(int(order[0]))
         P["e_voice"][entry].fill_(int(vox[0]))
         P["e_density"][entry].fill_(int(den[0]))
+        P["e_interval"][entry].fill_(int(mel[0]))
         if self.cls_ctl is not None:
             tab = np.full((1, N_CLASSES + 1, 3), np.nan) if class_table is None else class_sampling_table(class_table)[None]
             rec = class_ctl_records(tab, [t, k, p])
@@ -2379,7 +2486,7 @@ class PoolRequest:
     """One request of BatchedGenerator.generate_pool: what generate_stream takes for it alone.  accept: a callable
     (seq, report) -> bool, None accepts every sequence that is not None; logit_bias: one row; grammar / harmony: a
     per-request bool (None: on where the pool has a table), they may only switch on what the pool has a table for;
-    note_order / voices / density: as generate_stream's.  prompt: token ids that follow the conditioning tokens and that every
+    note_order / voices / density / interval: as generate_stream's.  prompt: token ids that follow the conditioning tokens and that every
     attempt of THIS request continues (generate_stream's prompt=); None or [] is an unprimed request."""
     encoded_meta: Sequence[int]
     input_data: object
@@ -2397,6 +2504,7 @@ class PoolRequest:
     voices: Optional[object] = None
     prompt: Optional[Sequence[int]] = None
     density: Optional[object] = None
+    interval: Optional[object] = None
 
 
 PoolResult = collections.namedtuple("PoolResult", ["sequences", "attempts_started", "logprobs"])
@@ -2520,7 +2628,7 @@ class BatchedGenerator:
 
     def decoder(self, B, temperature, top_k, max_chords, top_p=1.0, per_slot: bool = False, max_prompt: int = 0,
                 logit_bias=None, shared: bool = False, grammar=None, harmony=None, class_sampling=None,
-                note_order=None, voices=None, density=None):
+                note_order=None, voices=None, density=None, interval=None):
         """The decoder for B slots, its slots set to the given controls (numbers or one value per slot).  per_slot: the
         caller will read log-probabilities or give slots their own controls later (rearm): the array launches from the
         start.  Otherwise one triple for all slots runs the scalar launches, until a second setting arrives for launches
@@ -2532,7 +2640,7 @@ class BatchedGenerator:
         switches off what an earlier request left, and allocates nothing on a decoder that never had one).  voices: the
         request's voice words (voices_ctl), likewise; a slot that gets one has its note order switched on.  density:
         the request's density words (density_ctl), likewise; a slot that gets one has its voice word and note order switched
-        on.  shared: the
+        on.  interval: the request's interval words (interval_ctl), likewise; it switches nothing else on.  shared: the
         decoder that holds the
         request's common prompt once (its own cache layout: kept beside the unshared decoder of the same size)."""
         rows = sampling_rows(B, temperature, top_k, top_p)          # (validated before anything is built)
@@ -2544,6 +2652,7 @@ class BatchedGenerator:
         order = note_order_ctl(note_order, B)
         vox = voices_ctl(voices, B)
         den = density_ctl(density, B)
+        mel = interval_ctl(interval, B)
         key = (B, self.trace is not None, self.sliding) + (("shared",) if shared else ())
         dec = self._decoders.get(key)
         if dec is None or dec.ld_chord < max_chords or dec.max_prompt < max_prompt:
@@ -2572,6 +2681,8 @@ class BatchedGenerator:
         dec.set_voices(vox)
         # (note density: likewise, after the voice cap -- it switches the voice words on where the request left them off)
         dec.set_density(den)
+        # (melodic interval: likewise; it leaves the other words as they are)
+        dec.set_interval(mel)
         return dec
 
     @staticmethod
@@ -2584,8 +2695,12 @@ class BatchedGenerator:
     @torch.no_grad()
     def generate(self, encoded_metas: Sequence[Sequence[int]], input_datas, temperature, top_k, top_p=1.0,
                  return_logprobs: bool = False, prompts: Optional[Sequence[Sequence[int]]] = None, logit_bias=None,
-                 grammar=None, harmony=None, class_sampling=None, note_order=None, voices=None, density=None):
-        """temperature / top_k / top_p: a number for the batch or one value per sequence.  density: None / False, a word
+                 grammar=None, harmony=None, class_sampling=None, note_order=None, voices=None, density=None,
+                 interval=None):
+        """temperature / top_k / top_p: a number for the batch or one value per sequence.  interval: None / False, a word
+        interval_word(up, down, no_repeat) or one per sequence -- the pitch such a sequence DRAWS lies at most up semitones
+        above and down below the pitch of its last note, and (no_repeat) is not that pitch; implies none of the other
+        constraints (ForcedDecoder.set_interval).  density: None / False, a word
         density_word(lo, hi) or one per sequence -- a bar such a sequence DRAWS holds at least lo and at most hi notes;
         switches the sequence's voice word and note order on (ForcedDecoder.set_density).  voices: None / False, a word
         voices_word(N, r) or one per sequence -- at most N notes such a sequence DRAWS sound at once and (r) no pitch is
@@ -2613,7 +2728,7 @@ class BatchedGenerator:
         dec = self.decoder(B, temperature, top_k, max_chords, top_p, per_slot=return_logprobs, max_prompt=max_prompt,
                            logit_bias=logit_bias, shared=self.shared_prompt and max_prompt > 0, grammar=grammar,
                            harmony=self._one_harmony(harmony), class_sampling=class_sampling, note_order=note_order,
-                           voices=voices, density=density)
+                           voices=voices, density=density, interval=interval)
         uniforms = None
         if bool((dec._sampling[0] != 0).any()) or dec.class_samples():
             srcs = self.uniform_sources or [np.random.RandomState(1000 + b).random_sample for b in range(B)]
@@ -2638,7 +2753,7 @@ class BatchedGenerator:
                         accept, top_p=1.0, slots: int = 64, seed: int = 0, max_attempts: Optional[int] = None,
                         return_logprobs: bool = False, prompt: Optional[Sequence[int]] = None, logit_bias=None,
                         share_prompt: bool = False, grammar=None, harmony=None, class_sampling=None, note_order=None,
-                        voices=None, density=None):
+                        voices=None, density=None, interval=None):
         """Attempts of ONE request (the reference's `while idx != num_generate` loop, midi_inferrer.py:338-354, which tries
         one sequence after the other) decoded in up to `slots` parallel slots, CONTINUOUSLY: a slot whose sequence has
         ended is handed to `accept(sequence, report) -> bool` and re-armed with the next attempt while the other slots keep
@@ -2662,6 +2777,8 @@ class BatchedGenerator:
         (ForcedDecoder.set_voices; likewise read off seq).
         density: None / False or a word density_word(lo, hi): one setting for every attempt of the request
         (ForcedDecoder.set_density; likewise read off seq).
+        interval: None / False or a word interval_word(up, down, no_repeat): one setting for every attempt of the request
+        (ForcedDecoder.set_interval; likewise read off seq).
         share_prompt (opt-in; also on with BatchedGenerator(shared_prompt=True) when a prompt is given): the K/V of the
         context and the prompt are computed and held once for all slots (ForcedDecoder(shared_prompt=True)); the attempts
         returned are the ones the unshared decoder defines, up to the summation order of the attention."""
@@ -2681,6 +2798,8 @@ class BatchedGenerator:
             raise CommuHipError(f"voices: one setting for the request expected, got shape {np.shape(voices)}")
         if density is not None and np.ndim(density) != 0:
             raise CommuHipError(f"density: one setting for the request expected, got shape {np.shape(density)}")
+        if interval is not None and np.ndim(interval) != 0:
+            raise CommuHipError(f"interval: one setting for the request expected, got shape {np.shape(interval)}")
         max_chords = len(input_data.chord_token_components["chord_token"])
         # each control's schedule, validated on its own (the three may have different lengths)
         n_of = lambda x: 1 if np.ndim(x) == 0 else len(x)
@@ -2694,7 +2813,8 @@ class BatchedGenerator:
         dec = self.decoder(B, [t[0] for t in first], [t[1] for t in first], max_chords, [t[2] for t in first],
                            per_slot=return_logprobs or varying, max_prompt=0 if prompt is None else len(prompt),
                            logit_bias=logit_bias, shared=share, grammar=grammar, harmony=harmony,
-                           class_sampling=class_sampling, note_order=note_order, voices=voices, density=density)
+                           class_sampling=class_sampling, note_order=note_order, voices=voices, density=density,
+                           interval=interval)
         started = B
         sampled = bool((sched[0] != 0).any()) or dec.class_samples()          # (a greedy attempt reads no variate)
         uni = np.stack([self.attempt_uniforms(seed, a, dec.ld_u) for a in range(B)]) if sampled else None
@@ -2853,7 +2973,7 @@ class BatchedGenerator:
         harm_table = _harmony_request(self._one_harmony(harmony))
         cls_table = _class_request(class_sampling)
         # each request's controls, validated before anything is built
-        triples, biases, orders, voxes, dens = [], [], [], [], []
+        triples, biases, orders, voxes, dens, mels = [], [], [], [], [], []
         for i, r in enumerate(requests):
             t, k, p = sampling_rows(1, r.temperature, r.top_k, r.top_p)
             triples.append((t[0].item(), int(k[0]), p[0].item()))
@@ -2861,6 +2981,7 @@ class BatchedGenerator:
             orders.append(int(note_order_ctl(r.note_order, 1)[0]))
             voxes.append(int(voices_ctl(r.voices, 1)[0]))
             dens.append(int(density_ctl(r.density, 1)[0]))
+            mels.append(int(interval_ctl(r.interval, 1)[0]))
         B = max(1, min(slots, sum(int(r.need) for r in requests)))
         max_chords = max(len(r.input_data.chord_token_components["chord_token"]) for r in requests)
         key = ("pool", B, self.trace is not None, self.sliding)          # (never shared with generate / generate_stream:
@@ -2885,13 +3006,16 @@ class BatchedGenerator:
             dec.set_grammar(gram_table)
         dec.set_harmony(harm_table)
         use_den = any(d != DENSITY_OFF for d in dens)          # (the density rides on the voice words and the note order)
-        use_order = any(o != NOTE_ORDER_OFF for o in orders) or any(v != VOICES_OFF for v in voxes) or use_den
+        use_mel = any(m != INTERVAL_OFF for m in mels)         # (the interval kernel reads all three words, on or off)
+        use_order = any(o != NOTE_ORDER_OFF for o in orders) or any(v != VOICES_OFF for v in voxes) or use_den or use_mel
         if cls_table is not None or use_order:
             dec._first_use(rows=True, bias=True, gram=True, harm=True, cls=True, order=use_order)
-        if any(v != VOICES_OFF for v in voxes) or use_den:
+        if any(v != VOICES_OFF for v in voxes) or use_den or use_mel:
             dec._first_use(voices=True)
-        if use_den:
+        if use_den or use_mel:
             dec._first_use(density=True)
+        if use_mel:
+            dec._first_use(interval=True)
         if any(b is not None for b in biases):
             dec._first_use(bias=True)
         klen0_max = max([n_cond] + [p["klen0"] for p in replays if p is not None])
@@ -2915,7 +3039,7 @@ class BatchedGenerator:
                               grammar=(gram_table is not None) if r.grammar is None else bool(r.grammar),
                               harmony=(harm_table is not None) if r.harmony is None else bool(r.harmony),
                               note_order=orders[j.request], voices=voxes[j.request], class_table=cls_table,
-                              primed=replays[j.request], density=dens[j.request])
+                              primed=replays[j.request], density=dens[j.request], interval=mels[j.request])
                 sampled = triples[j.request][0] != 0 or cls_samples          # (a greedy attempt reads no variate)
                 staged.append((j.slot, j.entry, self.attempt_uniforms(r.seed, j.attempt, dec.ld_u) if sampled else None))
                 if held[j.slot] is not None and held[j.slot] != j.request:

@@ -194,6 +194,44 @@ def voices_violation(seq: List[int], start: int, max_voices: int = 0, restrike: 
     return None
 
 
+def interval_bans(seq: List[int], word: int) -> set:
+    """The ids the melodic interval (ForcedDecoder.set_interval, csrc/decode_loop.h: Interval) bans for the token that
+    follows seq.  word: -1 off, else up + 256 down + 65536 u.  The reference is the last note of seq that at most one BAR
+    follows, q its pitch token; none: nothing.  up >= 1: the pitches more than up semitones above q; down >= 1: those more
+    than down below it; u = 1: q itself."""
+    word = int(word)
+    if word < 0:
+        return set()
+    up, down, unison = word & 255, (word >> 8) & 255, (word >> 16) & 1
+    near = [p for _, _, p, k in _grid_notes(seq) if k <= 1]
+    if not near:
+        return set()
+    q = near[-1]
+    banned = set()
+    if up >= 1:
+        banned |= set(range(q + up + 1, TOKEN_OFFSET.NOTE_VELOCITY))
+    if down >= 1:
+        banned |= set(range(TOKEN_OFFSET.PITCH, q - down))
+    if unison:
+        banned.add(q)
+    return banned
+
+
+def interval_violation(seq: List[int], start: int, up: int = 0, down: int = 0, no_repeat: bool = False,
+                       drawn=None) -> Optional[int]:
+    """The index of the first token seq[i], i >= start, that the melodic interval would have banned given seq[:i]
+    (interval_bans with the word of up, down and no_repeat): a pitch more than up semitones above or down below the pitch of
+    the note before it, or -- no_repeat -- that pitch again.  drawn: a mask over seq; only the tokens it marks count (a
+    forced token and a prompt are not the rule's).  None when there is none."""
+    word = int(up) + 256 * int(down) + 65536 * int(bool(no_repeat))
+    for i in range(max(int(start), 0), len(seq)):
+        if drawn is not None and not drawn[i]:
+            continue
+        if TOKEN_OFFSET.PITCH <= int(seq[i]) < TOKEN_OFFSET.NOTE_VELOCITY and int(seq[i]) in interval_bans(seq[:i], word):
+            return i
+    return None
+
+
 def max_sounding(seq: List[int], ticks_per_bar: int, start: int = 0):
     """(most notes sounding at one tick, whether a pitch is struck while it sounds) for the notes of seq that begin at
     index >= start, in TICKS as the reference's decoder places them (encoder_utils.py:433-442, encoder.py:79-88): onset q of
@@ -259,7 +297,7 @@ class InferenceTask:
 
     def execute(self, encoded_meta, max_rounds: Optional[int] = None, return_logprobs: bool = False,
                 prompt: Optional[List[int]] = None, logit_bias=None, grammar=None, harmony=None,
-                class_sampling=None, note_order=None, voices=None, density=None):                          # :338-354
+                class_sampling=None, note_order=None, voices=None, density=None, interval=None):           # :338-354
         """return_logprobs (not in the reference): (sequences, their log-probability arrays -- ForcedDecoder.logprobs).
         prompt (not in the reference): token ids that follow the meta tokens; every attempt continues them (primed
         generation, BatchedGenerator.generate_stream) and every returned sequence starts with [0] + meta + prompt.
@@ -275,7 +313,10 @@ class InferenceTask:
         voices (not in the reference): a word generate.voices_word(N, r) -- at most N drawn notes sound at once and (r) no
         pitch is struck while it sounds; switches the note order on (ForcedDecoder.set_voices).
         density (not in the reference): a word generate.density_word(lo, hi) -- a drawn bar holds at least lo and at most hi
-        notes; switches the voice word and the note order on (ForcedDecoder.set_density)."""
+        notes; switches the voice word and the note order on (ForcedDecoder.set_density).
+        interval (not in the reference): a word generate.interval_word(up, down, no_repeat) -- a drawn pitch lies at most up
+        semitones above and down below the pitch of the note before it; switches nothing else on
+        (ForcedDecoder.set_interval)."""
         from ..generate import BatchedGenerator
         data = self.input_data
         glen = self.inference_cfg.GENERATION.generation_length
@@ -306,6 +347,9 @@ class InferenceTask:
         # (likewise: generate.py --min_notes_per_bar / --max_notes_per_bar, the density word)
         if density is None and getattr(self.inference_cfg.GENERATION, "density", None) is not None:
             density = int(self.inference_cfg.GENERATION.density)
+        # (likewise: generate.py --max_leap / --max_leap_up / --max_leap_down / --no_repeat_pitch, the interval word)
+        if interval is None and getattr(self.inference_cfg.GENERATION, "interval", None) is not None:
+            interval = int(self.inference_cfg.GENERATION.interval)
         gen = BatchedGenerator(self.model, self.device, glen, mlen, sliding=sliding, kv_dtype=kv_dtype,
                                **({"shared_prompt": True} if share else {}))
 
@@ -330,7 +374,8 @@ class InferenceTask:
                                   **({} if class_sampling is None else {"class_sampling": class_sampling}),
                                   **({} if note_order is None else {"note_order": note_order}),
                                   **({} if voices is None else {"voices": voices}),
-                                  **({} if density is None else {"density": density}))
+                                  **({} if density is None else {"density": density}),
+                                  **({} if interval is None else {"interval": interval}))
         return (res[0], res[2]) if return_logprobs else res[0]
 
     def execute_pool(self, items, return_logprobs: bool = False, harmony=None):
@@ -339,7 +384,7 @@ class InferenceTask:
         temperature, top_k, top_p), seed, max_rounds, logit_bias, prompt (token ids the request's sequences continue, None
         or [] for none).  Every request is accepted by the two validators of
         execute() and bounded by max_rounds x num_generate attempts, as there; the pool-wide options (grammar, harmony,
-        class_sampling, note_order, voices, density, decode_slots, kv_cache, sliding_memory) come from the inference configuration
+        class_sampling, note_order, voices, density, interval, decode_slots, kv_cache, sliding_memory) come from the inference configuration
         as in execute().  Returns generate_pool's PoolResult list."""
         from ..generate import BatchedGenerator, PoolRequest
         G = self.inference_cfg.GENERATION
@@ -356,6 +401,7 @@ class InferenceTask:
         note_order = None if getattr(G, "note_order", None) is None else int(G.note_order)
         voices = None if getattr(G, "voices", None) is None else int(G.voices)
         density = None if getattr(G, "density", None) is None else int(G.density)
+        interval = None if getattr(G, "interval", None) is None else int(G.interval)
 
         def accept(seq, rep) -> bool:
             self.attempts += 1
@@ -374,6 +420,7 @@ class InferenceTask:
                                     top_p=getattr(d, "top_p", 1.0), seed=int(it.get("seed") or 0),
                                     max_attempts=None if mr is None else int(mr) * int(d.num_generate), accept=accept,
                                     logit_bias=it.get("logit_bias"), note_order=note_order, voices=voices,
-                                    prompt=None if not it.get("prompt") else list(it["prompt"]), density=density))
+                                    prompt=None if not it.get("prompt") else list(it["prompt"]), density=density,
+                                    interval=interval))
         return gen.generate_pool(reqs, slots=int(getattr(G, "decode_slots", 64)), grammar=grammar, harmony=harmony,
                                  class_sampling=class_sampling, return_logprobs=return_logprobs)

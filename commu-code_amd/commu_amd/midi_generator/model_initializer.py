@@ -84,6 +84,11 @@ class ModelInitializeTask:
                 + 256 * int(getattr(self.model_args, "max_notes_per_bar", None) or 0)
         if dword is not None:
             cfg.GENERATION.density = int(dword)
+        # generate.py --max_leap / --max_leap_up / --max_leap_down / --no_repeat_pitch (not in the reference): the interval
+        # word up + 256 down + 65536 u (generate.py check_interval)
+        iword = getattr(self.model_args, "interval_word", None)
+        if iword is not None:
+            cfg.GENERATION.interval = int(iword)
         # generate.py --decode_slots (not in the reference): attempts decoded side by side (64 unless the key is set)
         if getattr(self.model_args, "decode_slots", None) not in (None, 64):
             cfg.GENERATION.decode_slots = int(self.model_args.decode_slots)

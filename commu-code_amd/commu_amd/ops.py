@@ -934,7 +934,7 @@ def _check_draw_state(kind, device, specs):
 
 def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=None, token=None, probs_out=None,
                 top_p=1.0, logp_out=None, bias=None, V=729, grammar=None, harmony=None, class_ctl=None,
-                note_order=None, voices=None, density=None):
+                note_order=None, voices=None, density=None, interval=None):
     """In-place temperature + softmax + top-k + wrong-token mask + inverse-CDF draw per sequence.
     logits: fp32 [nseq, >=V] (row stride = ld), modified in place (logits[:, 1:V] /= temperature).
     top_p < 1: nucleus filter after the top-k / rejected-token step (an extra mode; the reference has top-k only).
@@ -980,7 +980,12 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
     lo + 256 hi -- with C the complete notes of seq[b][0 : state[b][0]] behind its last BAR, every POSITION id is banned once
     C >= hi >= 1, and BAR and EOS while C < lo unless no position is left to draw.  The bans join the note order's and the
     voice cap's in the same select.  One kernel serves it, the voices kernel's with the count: voices= is required
-    (commu_sample_args.density_ctl)."""
+    (commu_sample_args.density_ctl).
+    interval: int32 [nseq] on the device of the logits, one control word per sequence (generate.interval_ctl): -1 off, else
+    up + 256 down + 65536 u -- with q the PITCH token of the last note of seq[b][0 : state[b][0]] that at most one BAR follows,
+    ids q + up + 1 .. 130 are banned (up >= 1), ids 3 .. q - down - 1 (down >= 1) and q itself (u = 1); no such note: nothing.
+    The bans join the note order's, the voice cap's and the density's in the same select.  One kernel serves it, the
+    density kernel's with the last note: density= is required (commu_sample_args.interval_ctl)."""
     nseq = logits.shape[0]
     V = int(V)
     assert logits.dtype == F32 and logits.stride(1) == 1
@@ -1051,6 +1056,13 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
         _check_draw_state("density", logits.device, (
             (density, "controls", torch.int32, "[%d]" % nseq, lambda t: tuple(t.shape) == (nseq,)),))
         a.density_ctl = _p(density)
+    if interval is not None:
+        if density is None:
+            raise CommuHipError("interval: density= expected as well (the one kernel finds the last note on the density "
+                                "kernel's walk; pass words that are all -1 where there is no density)")
+        _check_draw_state("interval", logits.device, (
+            (interval, "controls", torch.int32, "[%d]" % nseq, lambda t: tuple(t.shape) == (nseq,)),))
+        a.interval_ctl = _p(interval)
     if harmony is not None:
         htable, hon, hstate, chord_tok = harmony
         _check_draw_state("harmony", logits.device, (

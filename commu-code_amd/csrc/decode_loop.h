@@ -217,8 +217,23 @@ constexpr int TOK_VEL_LO = 131, TOK_VEL_HI = 194, TOK_DUR_LO = 304, TOK_DUR_HI =
 struct Density {
     int ctl;                // the sequence's control as the caller loaded it
 };
+// MEL (Interval: one int32 control per sequence, -1 off, else up + 256 down + 65536 u with up, down in 0 .. 127; 0: that
+//   bound is not set; u the unison switch): a cap on the leap from the last note to the pitch drawn next.  With NOTE and beta
+//   as for VOX, the REFERENCE NOTE is the note with beta <= 1 whose index is largest and q its PITCH token; none (the first
+//   note of a sequence, a line that rested for a whole bar or more): nothing is banned.  UP (up >= 1): ids q + up + 1 .. 130
+//   are banned.  DOWN (down >= 1): ids 3 .. q - down - 1.  UNISON (u): id q.  One id is one semitone.  The bans join the
+//   select of ORD, VOX and DEN, so a draw is bit for bit the DEN kernel's with bias[b] = -inf at these ids.
+//   THE REFERENCE NOTE rides on the voice walk: the lane that holds a note's DURATION has `note` (beta <= 1 is part of it)
+//   and the note's PITCH in t1, and lower lanes hold higher indices -- the first chunk from the end whose ballot of `note`
+//   is non-zero gives q = v_readlane(t1, lowest set lane).  One more ballot per chunk, no LDS, no load but the control
+//   word, the same trip count (the walk goes back to the second BAR from the end, so it passes every note with beta <= 1).
+//   q, the found flag, up, down and u are scalars; the bans are two bit ranges and one bit per lane, built like the position
+//   range.  An off word runs the same walk and bans nothing.  MEL needs DEN.
+struct Interval {
+    int ctl;                // the sequence's control as the caller loaded it
+};
 template <bool BIAS, bool GRAM = false, bool HARM = false, bool CLS = false, bool ORD = false, bool VOX = false,
-          bool DEN = false>
+          bool DEN = false, bool MEL = false>
 __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restrict__ logits, int ld, int V,
                                                  const unsigned char* __restrict__ wrong, int ldw,
                                                  const float* __restrict__ uni,
@@ -231,11 +246,12 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
                                                  Harmony h = Harmony{nullptr, 0, nullptr, 0, 0, 0},
                                                  ClassControls cc = ClassControls{nullptr},
                                                  NoteOrder no = NoteOrder{-1}, Voices vx = Voices{-1},
-                                                 Density dn = Density{-1}) {
+                                                 Density dn = Density{-1}, Interval ml = Interval{-1}) {
     static_assert(!CLS || GRAM, "the class key is the grammar's previous token");
     static_assert(!ORD || CLS, "one note-order instantiation: the class kernel's with the scan");
     static_assert(!VOX || ORD, "one voices instantiation: the note-order kernel's with the longer scan");
     static_assert(!DEN || VOX, "one density instantiation: the voices kernel's with the count of the open bar's notes");
+    static_assert(!MEL || DEN, "one interval instantiation: the density kernel's with the reference note");
     float* lg = logits + (size_t)b * ld;
     // The optional per-sequence inputs -- the active flag and this sequence's controls -- are loaded unconditionally: a null
     // array reads a valid word of this sequence instead (token[b], logits[b][0]), which is then ignored.  So they are in
@@ -331,6 +347,8 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
         int *vflag = nullptr, *vhist = nullptr;
         int nbar = 0;
         int dcount = 0;                         // (DEN) the notes with beta == 0 in the chunks so far
+        int mq = 0;                             // (MEL) the reference note's PITCH token, once found
+        bool mfound = false;
         if constexpr (VOX) {
             static_assert(VOX_BINS == 2 * 64, "two bins per lane");
             __shared__ __attribute__((aligned(16))) int vflag_lds[ORD_FLAGS];
@@ -385,6 +403,14 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
                 const int g0 = pos == TOK_BAR ? 0 : pos - TOK_POS0;
                 if (note & ((phase == 0) | (end > g0))) vflag[t1] = 1;
                 if constexpr (DEN) dcount += __popcll(__ballot(note & (beta == 0)));
+                if constexpr (MEL) {
+                    // (the lowest lane of the ballot is the highest index; a later chunk holds lower indices only)
+                    const unsigned long long nm = __ballot(note);
+                    if (!mfound && nm != 0ull) {
+                        mq = __builtin_amdgcn_readlane(t1, __builtin_ctzll(nm));
+                        mfound = true;
+                    }
+                }
                 nbar += __popcll(bars);
             }
             start -= 64;
@@ -455,6 +481,20 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
         omask = pm | ((on && base < ORD_FLAGS) ? dm : 0u);
         if constexpr (VOX) omask |= vdm;
         if constexpr (DEN) omask |= (dend && base == 0) ? ((1u << TOK_EOS) | (1u << TOK_BAR)) : 0u;
+        if constexpr (MEL) {
+            const int mctl = __builtin_amdgcn_readfirstlane(ml.ctl);
+            const bool mon = mctl >= 0 && mfound;
+            const int mup = mon ? (mctl & 255) : 0, mdown = mon ? ((mctl >> 8) & 255) : 0;
+            // ids [ulo, 131) and [3, dhi) are banned (empty where the bound is not set or reaches past the pitch range)
+            const int ulo = mup >= 1 ? min(mq + mup + 1, TOK_PITCH_HI + 1) : TOK_PITCH_HI + 1;
+            const int dhi = mdown >= 1 ? max(mq - mdown, TOK_PITCH_LO) : TOK_PITCH_LO;
+            const int same = (mon && ((mctl >> 16) & 1) != 0) ? mq : -1;          // (the one id of the unison ban)
+            const int u0 = min(max(ulo - base, 0), PER_LANE), u1 = min(max(TOK_PITCH_HI + 1 - base, 0), PER_LANE);
+            const int d0 = min(max(TOK_PITCH_LO - base, 0), PER_LANE), d1 = min(max(dhi - base, 0), PER_LANE);
+            omask |= ((1u << u1) - 1u) & ~((1u << u0) - 1u);
+            omask |= ((1u << d1) - 1u) & ~((1u << d0) - 1u);
+            omask |= (unsigned)(same - base) < (unsigned)PER_LANE ? 1u << (same - base) : 0u;
+        }
     }
     if (active != nullptr && act_row == 0) return -2;
     // ---- calc_probs

@@ -23,6 +23,7 @@ DECODE_SLOTS_MIN, DECODE_SLOTS_MAX, DECODE_SLOTS_DEFAULT = 1, 256, 64          #
 MAX_NOTES_MIN, MAX_NOTES_MAX = 1, 128                                             # --max_notes
 MAX_VOICES_MIN, MAX_VOICES_MAX = 1, 128                                           # --max_voices
 NOTES_PER_BAR_MIN, NOTES_PER_BAR_MAX = 1, 255                                     # --min_notes_per_bar / --max_notes_per_bar
+MAX_LEAP_MIN, MAX_LEAP_MAX = 1, 127                                               # --max_leap / --max_leap_up / --max_leap_down
 
 
 def parse_args():
@@ -116,6 +117,28 @@ def parse_args():
                                   help=f"at most N notes in every bar that is drawn, {NOTES_PER_BAR_MIN} .. "
                                        f"{NOTES_PER_BAR_MAX}, not below --min_notes_per_bar (implies --note_order).  Not "
                                        "covered: notes inside --prompt_tokens, a note that starts on a forced position")
+    # not in the reference (whose conditioning has no token for the melodic line: even a monophonic --max_voices 1 line
+    # jumps anywhere in the 128-pitch range from one note to the next): --max_leap N -- no pitch is DRAWN more than N
+    # semitones above or below the pitch of the note before it; --max_leap_up / --max_leap_down set one direction;
+    # --no_repeat_pitch bans that pitch itself.  They imply none of the other constraints and need no --grammar.  NOT
+    # covered: the first note, and a note after a full bar without one, have no reference; notes inside --prompt_tokens
+    # are not checked against each other (the prompt's last note is the reference of the first draw); several notes at
+    # one position are compared in token order, so the rule also limits the spread of a chord of notes (it is meant for
+    # --max_voices 1 lines); a pitch range, --logit_bias, strict --harmony, --note_order or --no_restrike ban that leaves
+    # no pitch inside the window ends that attempt as before (narrow windows with --no_repeat_pitch are the case); a
+    # prompt whose last note lies outside --pitch_min / --pitch_max by more than the cap does so at once.  With
+    # --requests they hold for the whole pool.
+    model_arg_parser.add_argument("--max_leap", default=None, metavar="N",
+                                  help=f"no drawn pitch more than N semitones above or below the note before it, "
+                                       f"{MAX_LEAP_MIN} .. {MAX_LEAP_MAX}.  Not covered: the first note and a note after a "
+                                       "full bar's rest; notes inside --prompt_tokens")
+    model_arg_parser.add_argument("--max_leap_up", default=None, metavar="N",
+                                  help=f"the same upwards only, {MAX_LEAP_MIN} .. {MAX_LEAP_MAX} (not beside --max_leap)")
+    model_arg_parser.add_argument("--max_leap_down", default=None, metavar="N",
+                                  help=f"the same downwards only, {MAX_LEAP_MIN} .. {MAX_LEAP_MAX} (not beside --max_leap)")
+    model_arg_parser.add_argument("--no_repeat_pitch", action="store_true",
+                                  help="no drawn pitch repeats the pitch of the note before it (same reference note as "
+                                       "--max_leap)")
     # not in the reference (which decodes one sequence at a time): how many attempts are decoded side by side.  1 .. 256;
     # up to 256 slots run the fused layer-tail launches ("Supported shapes").  The sequences returned do
     # not depend on it.  (checked by check_decode_slots: the range is named in its message)
@@ -344,6 +367,36 @@ def check_density(model_args):
     return word
 
 
+def check_interval(model_args):
+    """--max_leap / --max_leap_up / --max_leap_down / --no_repeat_pitch as the interval control word
+    up + 256 down + 65536 u (None: none of the flags); host code only, ValueError that names the flag and the value.
+    Written back to model_args.interval_word, which travels to the replicas (ModelInitializeTask puts it into the
+    inference configuration).  It switches nothing else on."""
+    got = {}
+    for flag in ("max_leap", "max_leap_up", "max_leap_down"):
+        v = getattr(model_args, flag, None)
+        if v is None:
+            continue
+        try:
+            n = int(v) if not isinstance(v, (bool, float)) else None
+        except (TypeError, ValueError):
+            n = None
+        if n is None or not MAX_LEAP_MIN <= n <= MAX_LEAP_MAX:
+            raise ValueError(f"--{flag}: an integer in [{MAX_LEAP_MIN}, {MAX_LEAP_MAX}] expected, got {v!r}")
+        got[flag] = n
+    for flag in ("max_leap_up", "max_leap_down"):
+        if flag in got and "max_leap" in got:
+            raise ValueError(f"--{flag} {got[flag]} cannot be combined with --max_leap {got['max_leap']}: --max_leap sets "
+                             "both directions")
+    unison = bool(getattr(model_args, "no_repeat_pitch", False))
+    word = None
+    if got or unison:
+        word = got.get("max_leap", got.get("max_leap_up", 0)) + 256 * got.get("max_leap", got.get("max_leap_down", 0)) \
+            + (65536 if unison else 0)
+    model_args.interval_word = word
+    return word
+
+
 def read_constraints(path=None, pitch_min=None, pitch_max=None):
     """The constraint row of --logit_bias / --pitch_min / --pitch_max (None when none of them is given); host code only,
     raises (commu_amd.generate.CommuHipError, ValueError) on a malformed file or an empty range."""
@@ -446,6 +499,7 @@ def main(model_args, input_args, training_cfg=None, device_indices=None):
     check_decode_slots(model_args)                      # (likewise)
     check_voices(model_args)                            # (likewise; ahead of the note order, which it switches on)
     check_density(model_args)                           # (likewise)
+    check_interval(model_args)                          # (likewise)
     check_note_order(model_args)                        # (likewise)
     in_args = dict(vars(input_args))
     in_args.pop("requests", None)

@@ -536,6 +536,28 @@ int commu_transpose_heads(const void* src, int ld, const float* bias, void* dst,
  *     everything voice_ctl requires, else -22.  Validating the words is the caller's job (generate.density_ctl).  The same
  *     field, with the same meaning and the same refusal, is in commu_decode_loop_args.  Null: the launch that never heard of
  *     it.
+ * MELODIC INTERVAL (the reference's conditioning has no token for the melodic line; even a monophonic line of its sampler
+ * jumps anywhere in the 128-pitch range from one note to the next)
+ *   interval_ctl: int32 [nseq], one control word per sequence: -1 off, else up + 256 down + 65536 u with up, down in
+ *     0 .. 127 (0: that bound is not set) and u in {0, 1} (1: the pitch may not repeat); word 0 is on and bans nothing.
+ *     Defined on seq alone when the stage runs, with L, S, NOTE and beta as for voice_ctl.  The REFERENCE NOTE is the note
+ *     with beta <= 1 whose index i is largest, q = S[i+2] its PITCH token; none (the first note of a sequence, a line that
+ *     rested for a whole bar or more): nothing is banned.  UP (up >= 1); BANNED: ids q + up + 1 .. 130.  DOWN (down >= 1);
+ *     BANNED: ids 3 .. q - down - 1.  UNISON (u = 1); BANNED: id q.  One id is one semitone.  The bans join order_ctl's,
+ *     voice_ctl's and density_ctl's in the same select, whatever class is drawn and whatever the grammar's switch says, so
+ *     all that is said for order_ctl holds: before top-k, never written back, probs_out exactly 0, `full` the log-softmax of
+ *     y, token -1 when nothing is left.  A draw is BIT FOR BIT the draw of the call without interval_ctl and with
+ *     bias[b] = -inf at these ids; an off word, word 0, or a word that bans nothing is bit for bit the call without the
+ *     field.  The word does not imply the note order, the voice cap or the density: those words stay as they are.
+ *     NOT COVERED: the first note, and a note after a full bar without one, have no reference; notes inside a prompt are
+ *     not checked against each other (the prompt's last note is the reference of the first draw); several notes at one
+ *     position are compared in token order, so the rule also limits the spread of a chord of notes; a bias, harmony,
+ *     note-order or re-strike ban that leaves no pitch inside the window ends the attempt by Q12, as before; forced tokens
+ *     are never affected.
+ *     ONE kernel serves it, the density kernel with one more ballot on the same walk: interval_ctl requires density_ctl
+ *     and everything density_ctl requires, else -22.  Validating the words is the caller's job (generate.interval_ctl).
+ *     The same field, with the same meaning and the same refusal, is in commu_decode_loop_args.  Null: the launch that
+ *     never heard of it.
  * WHAT gram / harm READ
  *   state: the forcing records, int32 [nseq][commu_forcing_state_ints()]; seq int32 [nseq][ld_seq]; chord_tok int32
  *   [nseq][ld_chord].  Not looked at, and may be null, in a call without gram and harm.
@@ -575,6 +597,8 @@ typedef struct commu_sample_args {
     const int* seq;
     const int* chord_tok;
     int ld_seq, ld_chord;
+    /* melodic interval (ahead of density_ctl: the four fields behind it keep their places at the struct's end) */
+    const int* interval_ctl;
     /* note density (ahead of order_ctl: the three fields behind it keep their places at the struct's end) */
     const int* density_ctl;
     /* note order (placed ahead of cls_ctl, which stays the struct's last field) */
@@ -800,6 +824,8 @@ typedef struct commu_decode_loop_args {
     const float* harm;
     const unsigned char* harm_on;
     int ld_bias, ld_gram, ld_harm;
+    /* melodic interval (commu_sample_args.interval_ctl; likewise ahead of density_ctl) */
+    const int* interval_ctl;
     /* note density (commu_sample_args.density_ctl; likewise ahead of order_ctl) */
     const int* density_ctl;
     /* note order (commu_sample_args.order_ctl; likewise ahead of cls_ctl) */
@@ -856,7 +882,8 @@ int commu_decode_prefill_scatter(const void* qkv, int ld_qkv, int T, int B, void
  *   loop's entry point treats a null array:  seq_logp[slot][0 .. 2 ld_seq) = NaN;  trace[slot][0 .. ld_trace) = 0;
  *   temperature_rows / top_k_rows / top_p_rows [slot] = e_temperature / e_top_k / e_top_p [entry];
  *   bias[slot][0 .. ld_bias) = e_bias[entry];  gram_on / harm_on [slot] = e_gram_on / e_harm_on [entry] (bytes);
- *   order_ctl / voice_ctl / density_ctl [slot] = e_order / e_voice / e_density [entry];  cls_ctl[slot][0 .. 32) = e_cls[entry] (int32).
+ *   order_ctl / voice_ctl / density_ctl / interval_ctl [slot] = e_order / e_voice / e_density / e_interval [entry];
+ *   cls_ctl[slot][0 .. 32) = e_cls[entry] (int32).
  * tok / active / keep / draw are NOT written: an armed slot sits out the iteration whose decision was taken from its
  * finished record and starts with the next one.  Two jobs of one launch must name different slots (the caller's duty).
  * Nothing but njobs varies between launches; there is no host synchronisation.  Grid: one wave per (job, layer, head).
@@ -912,6 +939,8 @@ typedef struct commu_decode_arm_args {
     const unsigned char* e_gram_on;
     unsigned char* harm_on;
     const unsigned char* e_harm_on;
+    int* interval_ctl;
+    const int* e_interval;
     int* density_ctl;
     const int* e_density;
     int* order_ctl;
@@ -945,8 +974,8 @@ int commu_decode_arm(const commu_decode_arm_args* a, hipStream_t stream);
  *   trace[slot][0 .. ld_trace) = e_trace[entry] where trace and e_trace are given (the replay's trace continues into the
  *     decode), zeros where only trace is;
  *   everything else as commu_decode_arm: klen, state, chords, wrong zeroed, utable, seq_logp NaN (prompt tokens carry no
- *     pair), the sampling triple, bias row, grammar / harmony switches, note-order, voice and density words, class
- *     records.
+ *     pair), the sampling triple, bias row, grammar / harmony switches, note-order, voice, density and interval words,
+ *     class records.
  *   grid_rows: 0, or an upper bound of every e_klen0 the launch will meet (the pool's longest image): fewer chunk
  *     workgroups are launched; it is part of the clamp of n above, so a longer entry is truncated, never overrun.
  * njobs == 0: nothing is launched, 0.  -22: a struct_bytes other than commu_decode_arm_primed_args_bytes(), and
@@ -999,6 +1028,8 @@ typedef struct commu_decode_arm_primed_args {
     const unsigned char* e_gram_on;
     unsigned char* harm_on;
     const unsigned char* e_harm_on;
+    int* interval_ctl;
+    const int* e_interval;
     int* density_ctl;
     const int* e_density;
     int* order_ctl;
