@@ -657,6 +657,97 @@ def interval_ctl(x, B: int):
                      for b, v in enumerate(x)], dtype=np.int32)
 
 
+# ---- onset templates: one int32 control word per slot (commu_sample_args.onset_ctl) and one device table of 128-bit rows
+# (onset_table).  A slot that is on can DRAW a position only where the row of the bar being written has a bit: the row is
+# base + (i mod R) for bar index i = max(seq.count(BAR) - 1, 0), the bars of a prompt included.  The kernel takes the count
+# from the forcing record.  Like the interval it implies none of the other words.
+ONSETS_OFF = -1
+ONSET_GRID = 128              # grid steps of a bar: position id 432 + g
+ONSET_ROWS_MAX = 4096         # rows of the device table; the word is base + ONSET_ROWS_MAX * R
+ONSET_CYCLE_MAX = 64          # bars of one template
+ONSET_POS0, ONSET_BAR = 432, 2
+
+
+def onset_word(base: int, cycle: int) -> int:
+    """The control word base + 4096 R of a template of R rows that starts at table row base."""
+    return int(base) + ONSET_ROWS_MAX * int(cycle)
+
+
+def onset_rows(x) -> np.ndarray:
+    """A template as uint32 [R][4], one 128-bit row per bar of its cycle (bit g % 32 of word g // 32: grid step g may hold an
+    onset).  x: a list of bars, each a list of positions 0 .. 127 (an empty bar rests); {"grid": n} with n a power of two
+    from 1 to 128 -- one bar, the positions that are multiples of 128 / n; {"bars": [...]} -- the list form; or a uint32 array
+    [R][4] that is one already.  1 <= R <= 64.  Pure host code; raises CommuHipError on anything else, with the value."""
+    if isinstance(x, np.ndarray) and x.dtype == np.uint32:
+        if x.ndim != 2 or x.shape[1] != 4 or not 1 <= x.shape[0] <= ONSET_CYCLE_MAX:
+            raise CommuHipError(f"onsets: a uint32 template is [1 .. {ONSET_CYCLE_MAX}][4], got shape {x.shape}")
+        return np.ascontiguousarray(x)
+    if isinstance(x, dict):
+        if set(x) == {"grid"}:
+            n = x["grid"]
+            if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= ONSET_GRID or n & (n - 1):
+                raise CommuHipError(f'onsets: {{"grid": n}} takes a power of two from 1 to {ONSET_GRID}, got {n!r}')
+            x = [list(range(0, ONSET_GRID, ONSET_GRID // int(n)))]
+        elif set(x) == {"bars"}:
+            x = x["bars"]
+        else:
+            raise CommuHipError(f'onsets: {{"grid": n}} or {{"bars": [...]}} expected, got the keys {sorted(map(str, x))}')
+    if not isinstance(x, (list, tuple)) or not all(isinstance(b, (list, tuple)) for b in x):
+        raise CommuHipError(f"onsets: a list of bars, each a list of positions 0 .. {ONSET_GRID - 1}, expected, got {x!r}")
+    if not 1 <= len(x) <= ONSET_CYCLE_MAX:
+        raise CommuHipError(f"onsets: a template holds 1 .. {ONSET_CYCLE_MAX} bars, got {len(x)}")
+    out = np.zeros((len(x), 4), dtype=np.uint32)
+    for i, bar in enumerate(x):
+        for g in bar:
+            if isinstance(g, (bool, np.bool_)) or not isinstance(g, (int, np.integer)) or not 0 <= g < ONSET_GRID:
+                raise CommuHipError(f"onsets: bar {i}: positions are integers 0 .. {ONSET_GRID - 1}, got {g!r}")
+            out[i, int(g) // 32] |= np.uint32(1 << (int(g) % 32))
+    return out
+
+
+def _is_note_at(seq, i) -> bool:
+    """seq[i : i + 4] is a Position, Velocity, Pitch, Duration group (voices_contract's NOTE)."""
+    return i + 3 < len(seq) and 432 <= seq[i] <= 559 and 131 <= seq[i + 1] <= 194 and 3 <= seq[i + 2] <= 130 \
+        and 304 <= seq[i + 3] <= 431
+
+
+def onsets_of(seq, start: int = 0, invert: bool = False) -> List[List[int]]:
+    """The onsets of a token sequence, bar by bar in the rule's bar index: element i lists the positions 0 .. 127 at which a
+    complete Position, Velocity, Pitch, Duration group of bar i starts, for the groups at index >= start (the stretch before
+    the first Bar belongs to bar 0, as the rule counts it).  invert: the positions of each bar that hold NO onset.  What it
+    returns is a template in onset_rows' list form: a request given it follows the track (or, inverted, leaves it room).
+    A sequence longer than 64 bars gives more bars than a template takes; cut it."""
+    seq = [int(t) for t in seq]
+    bars: List[set] = [set()]
+    nb = 0
+    for i, t in enumerate(seq):
+        if t == ONSET_BAR:
+            nb += 1
+            if nb >= 2:
+                bars.append(set())
+        elif i >= int(start) and _is_note_at(seq, i):
+            bars[max(nb - 1, 0)].add(t - ONSET_POS0)
+    if invert:
+        return [sorted(set(range(ONSET_GRID)) - b) for b in bars]
+    return [sorted(b) for b in bars]
+
+
+def _onsets_per_slot(x, B: int):
+    """A request's onsets= as B entries, each None (off) or a uint32 [R][4] template: None / False (all off), one template in
+    any form onset_rows takes (all slots), or a list of B entries each None / False or a template.  A list whose elements
+    are lists of integers is ONE template (its bars)."""
+    B = int(B)
+    if x is None or x is False:
+        return [None] * B
+    if isinstance(x, (list, tuple)) and len(x) and not all(
+            isinstance(b, (list, tuple)) and all(isinstance(g, (int, np.integer)) for g in b) for b in x):
+        if len(x) != B:
+            raise CommuHipError(f"onsets: {B} entries expected (one per sequence), got {len(x)}")
+        return [None if (v is None or v is False) else onset_rows(v) for v in x]
+    t = onset_rows(x)
+    return [t] * B
+
+
 class DecodeState:
     """K/V caches + distance-indexed R tables for B sequences of up to Lmax positions.
 
@@ -1117,6 +1208,17 @@ class ForcedDecoder:
 
     POLL = 16          # iterations between two looks at the `done` flags (one D2H of B ints)
 
+    # onset templates (set_onsets): the slots' control words int32 [B] with their host mirror, the device table of
+    # ONSET_ROWS_MAX rows (allocated once, so that its pointer stays fixed under graph capture) with its host mirror, the
+    # rows in use and the base row of every template packed so far, by its bytes.  Class-level: a decoder that never
+    # enables the rule has none of them.
+    onset_ctl = None
+    _onset_host = None
+    onset_table = None
+    _onset_table_host = None
+    _onset_used = 0
+    _onset_index = None
+
     def __init__(self, model, B: int, generation_length: int, memory_length: int, temperature: float, top_k: int,
                  max_chords: int = 64, record_trace: bool = False, top_p: float = 1.0, sliding: bool = False,
                  max_prompt: int = 0, kv_dtype: str = "bf16", shared_prompt: bool = False):
@@ -1265,13 +1367,13 @@ class ForcedDecoder:
         return idx
 
     def _first_use(self, rows=False, bias=False, gram=False, harm=False, cls=False, order=False, voices=False,
-                   density=False, interval=False):
+                   density=False, interval=False, onsets=False):
         """What the first use of a per-slot launch input does, for each one asked for that the decoder does not have yet:
         rows uploads the host mirror of the sampling controls (scalar mode kept the mirror only); bias / gram / harm
         allocate their zeroed device buffers (gram and harm: the table and the [B] switches); cls allocates the slots'
         class-control records (set_class_sampling fills them); order allocates the slots' note-order words, all off; voices
         the slots' voice words, all off; density the slots' density words, all off; interval the slots' interval words,
-        all off.
+        all off; onsets the slots' onset words, all off, and the template table of ONSET_ROWS_MAX all-ones rows.
         When anything was missing the captured graphs are dropped,
         once: they hold the launches without it."""
         new = False
@@ -1310,6 +1412,14 @@ class ForcedDecoder:
             new = True
             self.interval_ctl = torch.full((self.B,), INTERVAL_OFF, dtype=torch.int32, device=self.dev)
             self._interval_host = np.full(self.B, INTERVAL_OFF, dtype=np.int32)
+        if onsets and self.onset_ctl is None:
+            new = True
+            self.onset_ctl = torch.full((self.B,), ONSETS_OFF, dtype=torch.int32, device=self.dev)
+            self._onset_host = np.full(self.B, ONSETS_OFF, dtype=np.int32)
+            # (int32 on the device: the bit patterns of the uint32 rows)
+            self.onset_table = torch.full((ONSET_ROWS_MAX, 4), -1, dtype=torch.int32, device=self.dev)
+            self._onset_table_host = np.full((ONSET_ROWS_MAX, 4), 0xFFFFFFFF, dtype=np.uint32)
+            self._onset_used, self._onset_index = 0, {}
         if new:
             self.graph = self.graph_long = None
 
@@ -1621,6 +1731,82 @@ class ForcedDecoder:
             for j in idx:
                 self.interval_ctl[int(j)].fill_(int(self._interval_host[j]))
 
+    def _onsets_pack(self, templates, fresh: bool = False):
+        """The control words of the given templates (uint32 [R][4]; None: off) in the decoder's table.  Distinct templates,
+        told apart by their bytes, are packed one behind the other; a template packed before keeps its rows.  fresh: the
+        table is packed anew from these templates alone (every slot's word is about to be rewritten).  Refuses, before
+        anything changes, what does not fit.  New rows are written to the device table in place, ordered on the current
+        stream."""
+        index = {} if fresh else dict(self._onset_index)
+        used = 0 if fresh else self._onset_used
+        todo, words = [], []
+        for t in templates:
+            if t is None:
+                words.append(ONSETS_OFF)
+                continue
+            if t.shape[0] > ONSET_CYCLE_MAX:
+                raise CommuHipError(f"onsets: a template holds at most {ONSET_CYCLE_MAX} bars, got {t.shape[0]}")
+            key = t.tobytes()
+            if key not in index:
+                if used + t.shape[0] > ONSET_ROWS_MAX:
+                    raise CommuHipError(f"onsets: the distinct templates need more than the table's {ONSET_ROWS_MAX} rows "
+                                        f"({used} in use, {t.shape[0]} more asked for)")
+                index[key] = used
+                todo.append((used, t))
+                used += t.shape[0]
+            words.append(onset_word(index[key], t.shape[0]))
+        for base, t in todo:
+            self._onset_table_host[base:base + t.shape[0]] = t
+            self.onset_table[base:base + t.shape[0]].copy_(torch.from_numpy(t.view(np.int32)))
+        self._onset_index, self._onset_used = index, used
+        return np.array(words, dtype=np.int32)
+
+    def set_onsets(self, value, rows: Optional[Sequence[int]] = None):
+        """The onset template for all slots (rows=None) or the listed ones: a template in any form onset_rows takes -- a list
+        of bars, each a list of the positions 0 .. 127 at which a note may START, {"grid": n}, {"bars": [...]}, a uint32
+        [R][4] array -- None / False (off), or one such value per addressed slot.  A slot that is on DRAWS a position only
+        where the row of the bar being written has a bit; bar i of the sequence (its Bar tokens counted from the start,
+        the prompt's included, the stretch before the first Bar being bar 0) uses row i mod R of its template, so a primed
+        slot continues the cycle in phase.  An all-clear row is a bar of rest.  The kernel takes the bar count from the
+        slot's forcing record.  Only DRAWS are constrained: the position 0 forced after a Bar, a chord's forced position
+        and a prompt are not.  With set_density's lower bound a bar may end short once the template leaves it no onset.
+        The rule implies none of the others: the first call that switches a slot on allocates the [B] words, the table of
+        4096 rows -- ONCE, so that its address stays fixed under graph capture -- and, where the decoder lacks them,
+        everything the one kernel reads besides (the interval, density, voice and note-order words, all off, and what
+        set_interval allocates), and drops the captured graphs once; later calls pack new templates behind the ones in the
+        table (the same template, by its bytes, is stored once) and rewrite words and rows IN PLACE, ordered on the current
+        stream, and a captured graph follows them.  A call for all slots packs the table anew.  Refused with the numbers:
+        a template of more than 64 bars, distinct templates of more than 4096 rows together.  A slot that is off decodes
+        bit for bit what it decoded without the feature; a decoder that never switched a slot on allocates nothing."""
+        idx = self._slots(rows)
+        tmpl = _onsets_per_slot(value, len(idx))               # (validated before anything changes)
+        if self.onset_ctl is None and all(t is None for t in tmpl):
+            return
+        if self.onset_ctl is None:
+            # (the capacity check of _onsets_pack, before anything is allocated)
+            need, seen = 0, set()
+            for t in tmpl:
+                if t is not None and t.tobytes() not in seen:
+                    seen.add(t.tobytes())
+                    need += t.shape[0]
+            if need > ONSET_ROWS_MAX:
+                raise CommuHipError(f"onsets: the distinct templates need more than the table's {ONSET_ROWS_MAX} rows "
+                                    f"(0 in use, {need} asked for)")
+        fresh_cls = self.cls_ctl is None
+        self._first_use(rows=True, bias=True, gram=True, harm=True, cls=True, order=True, voices=True, density=True,
+                        interval=True, onsets=True)
+        if fresh_cls:          # (no class controls: every record of every slot holds the slot's base triple)
+            self._write_class_ctl(None, np.arange(self.B))
+        new = self._onsets_pack(tmpl, fresh=rows is None)
+        if np.array_equal(self._onset_host[idx], new):
+            return
+        self._onset_host[idx] = new
+        if rows is None and len(idx) > 4:
+            self.onset_ctl.copy_(torch.from_numpy(self._onset_host))
+        else:
+            for j in idx:
+                self.onset_ctl[int(j)].fill_(int(self._onset_host[j]))
+
     def pre(self):
         call("commu_forcing_pre", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_tok), _p(self.chord_pos),
              self.ld_chord, _p(self.wrong), _p(self.utable), self.ld_u, self.generation_length, _p(self.tok),
@@ -1642,7 +1828,8 @@ class ForcedDecoder:
                         **({} if self.order_ctl is None else {"note_order": self.order_ctl}),
                         **({} if self.voice_ctl is None else {"voices": self.voice_ctl}),
                         **({} if self.density_ctl is None else {"density": self.density_ctl}),
-                        **({} if self.interval_ctl is None else {"interval": self.interval_ctl}))
+                        **({} if self.interval_ctl is None else {"interval": self.interval_ctl}),
+                        **({} if self.onset_ctl is None else {"onsets": (self.onset_ctl, self.onset_table)}))
         call("commu_forcing_post", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_pos), self.ld_chord,
              _p(self.wrong), _p(self.draw), _p(self.token), None, _p(self.state.klen), _p(self.keep),
              self.state.klen_cap, _p(logp), _p(seq_logp), B, _s())
@@ -1667,7 +1854,9 @@ class ForcedDecoder:
             bias=_p(self.bias), ld_bias=ld(self.bias), gram=_p(self.gram), ld_gram=ld(self.gram), gram_on=_p(self.gram_on),
             harm=_p(self.harm), ld_harm=ld(self.harm), harm_on=_p(self.harm_on), cls_ctl=_p(self.cls_ctl),
             order_ctl=_p(self.order_ctl), voice_ctl=_p(self.voice_ctl), density_ctl=_p(self.density_ctl),
-            interval_ctl=_p(self.interval_ctl))
+            interval_ctl=_p(self.interval_ctl),
+            **({} if self.onset_ctl is None else {"onset_ctl": _p(self.onset_ctl), "onset_table": _p(self.onset_table),
+                                                  "onset_rows": ONSET_ROWS_MAX}))
         call("commu_decode_sample_post_pre", C.byref(a), _s())
 
     def iteration(self, want_probs: bool = False):
@@ -1929,8 +2118,9 @@ class ForcedDecoder:
     # voices: the slot's voice word for its next attempt (set_voices' values, False: off; None: the slot keeps its word).
     # density: the slot's density word for its next attempt (set_density's values, False: off; None: the slot keeps its word).
     # interval: the slot's interval word for its next attempt (set_interval's values, False: off; None: the slot keeps its word).
+    # onsets: the slot's onset template for its next attempt (set_onsets' values, False: off; None: the slot keeps its word).
     def rearm(self, b: int, uniforms_row: Optional[np.ndarray] = None, sampling=None, logit_bias=None, grammar=None,
-              harmony=None, note_order=None, voices=None, density=None, interval=None):
+              harmony=None, note_order=None, voices=None, density=None, interval=None, onsets=None):
         if note_order is not None:
             self.set_note_order(note_order, rows=[b])
         if voices is not None:
@@ -1939,6 +2129,8 @@ class ForcedDecoder:
             self.set_density(density, rows=[b])
         if interval is not None:
             self.set_interval(interval, rows=[b])
+        if onsets is not None:
+            self.set_onsets(onsets, rows=[b])
         if sampling is not None:
             self.set_sampling(*sampling, rows=[b])
         if logit_bias is not None:
@@ -2140,7 +2332,8 @@ class ForcedDecoder:
                 "e_order": torch.full((R,), NOTE_ORDER_OFF, dtype=i32, device=dev),
                 "e_voice": torch.full((R,), VOICES_OFF, dtype=i32, device=dev),
                 "e_density": torch.full((R,), DENSITY_OFF, dtype=i32, device=dev),
-                "e_interval": torch.full((R,), INTERVAL_OFF, dtype=i32, device=dev), "e_cls": z(R, N_CLASSES + 1, 4),
+                "e_interval": torch.full((R,), INTERVAL_OFF, dtype=i32, device=dev),
+                "e_onset": torch.full((R,), ONSETS_OFF, dtype=i32, device=dev), "e_cls": z(R, N_CLASSES + 1, 4),
                 "hdr": hdr, "stage": z(words),
                 # two pinned staging buffers and an event each: the host never overwrites a buffer whose copy is in flight
                 "pin": [torch.zeros(words, dtype=i32).pin_memory() for _ in range(2)],
@@ -2165,7 +2358,7 @@ class ForcedDecoder:
         """The arm launch's argument block, rebuilt when an optional array was allocated since (a null twin: not written)."""
         P = self._pool
         opt = (self.bias, self.gram_on, self.harm_on, self.order_ctl, self.voice_ctl, self.density_ctl, self.interval_ctl,
-               self.cls_ctl, self.trace)
+               self.onset_ctl, self.cls_ctl, self.trace)
         sig = tuple(None if t is None else t.data_ptr() for t in opt)
         if P["args"] is None or P["sig"] != sig:
             st = self.state
@@ -2189,6 +2382,7 @@ class ForcedDecoder:
                 **on(self.voice_ctl, {"voice_ctl": self.voice_ctl, "e_voice": P["e_voice"]}),
                 **on(self.density_ctl, {"density_ctl": self.density_ctl, "e_density": P["e_density"]}),
                 **on(self.interval_ctl, {"interval_ctl": self.interval_ctl, "e_interval": P["e_interval"]}),
+                **on(self.onset_ctl, {"onset_ctl": self.onset_ctl, "e_onset": P["e_onset"]}),
                 **on(self.cls_ctl, {"cls_ctl": self.cls_ctl, "e_cls": P["e_cls"]}))
             P["sig"] = sig
         if P["primed"]:
@@ -2196,11 +2390,13 @@ class ForcedDecoder:
         return P["args"]
 
     def admit(self, entry: int, encoded_meta: Sequence[int], input_data, sampling=None, logit_bias=None, grammar=False,
-              harmony=False, note_order=None, voices=None, class_table=None, primed=None, density=None, interval=None):
+              harmony=False, note_order=None, voices=None, class_table=None, primed=None, density=None, interval=None,
+              onsets=None):
         """Compose store entry `entry` for a request and upload it with its K/V image: the state record, sequence head
         and chord rows as load() builds them, klen0 = n_cond, the sampling triple (None: the decoder's), the bias row
         (None: zeros), the grammar and harmony switches (they switch on what the decoder has a table for), the
-        note-order, voice, density and interval words (None: off) and, where the decoder has class records, the request's record row
+        note-order, voice, density and interval words (None: off), the onset word of the template `onsets` (None: off; the
+        template's rows go to the decoder's own table, where the same template is stored once -- no table bytes move per arm) and, where the decoder has class records, the request's record row
         (class_table: its NaN-table, None: the base triple in every record).  The image is written by ONE memory-less
         forward over this request's single column [n_cond, 1] and the prefill scatter of the cache's format into the
         store: it does not depend on what else is admitted or decoding.  Everything is ordered on the current stream.
@@ -2224,6 +2420,9 @@ class ForcedDecoder:
         vox = voices_ctl(voices, 1)
         den = density_ctl(density, 1)
         mel = interval_ctl(interval, 1)
+        ons = _onsets_per_slot(onsets, 1)
+        if ons[0] is not None and self.onset_ctl is None:
+            raise CommuHipError("admit: an onset template, but the decoder has no onset words (set_onsets)")
         if grammar and (self.gram is None or self._gram_host is None):
             raise CommuHipError("admit: grammar switched on, but the decoder has no grammar table (set_grammar)")
         if harmony and (self.harm is None or self._harm_host is None):
@@ -2286,6 +2485,7 @@ class ForcedDecoder:
         P["e_voice"][entry].fill_(int(vox[0]))
         P["e_density"][entry].fill_(int(den[0]))
         P["e_interval"][entry].fill_(int(mel[0]))
+        P["e_onset"][entry].fill_(int(ONSETS_OFF if ons[0] is None else self._onsets_pack(ons)[0]))
         if self.cls_ctl is not None:
             tab = np.full((1, N_CLASSES + 1, 3), np.nan) if class_table is None else class_sampling_table(class_table)[None]
             rec = class_ctl_records(tab, [t, k, p])
@@ -2486,7 +2686,8 @@ class PoolRequest:
     """One request of BatchedGenerator.generate_pool: what generate_stream takes for it alone.  accept: a callable
     (seq, report) -> bool, None accepts every sequence that is not None; logit_bias: one row; grammar / harmony: a
     per-request bool (None: on where the pool has a table), they may only switch on what the pool has a table for;
-    note_order / voices / density / interval: as generate_stream's.  prompt: token ids that follow the conditioning tokens and that every
+    note_order / voices / density / interval / onsets: as generate_stream's (onsets: ONE template in any form onset_rows
+    takes; the pool packs its requests' templates into one table).  prompt: token ids that follow the conditioning tokens and that every
     attempt of THIS request continues (generate_stream's prompt=); None or [] is an unprimed request."""
     encoded_meta: Sequence[int]
     input_data: object
@@ -2505,6 +2706,7 @@ class PoolRequest:
     prompt: Optional[Sequence[int]] = None
     density: Optional[object] = None
     interval: Optional[object] = None
+    onsets: Optional[object] = None
 
 
 PoolResult = collections.namedtuple("PoolResult", ["sequences", "attempts_started", "logprobs"])
@@ -2628,7 +2830,7 @@ class BatchedGenerator:
 
     def decoder(self, B, temperature, top_k, max_chords, top_p=1.0, per_slot: bool = False, max_prompt: int = 0,
                 logit_bias=None, shared: bool = False, grammar=None, harmony=None, class_sampling=None,
-                note_order=None, voices=None, density=None, interval=None):
+                note_order=None, voices=None, density=None, interval=None, onsets=None):
         """The decoder for B slots, its slots set to the given controls (numbers or one value per slot).  per_slot: the
         caller will read log-probabilities or give slots their own controls later (rearm): the array launches from the
         start.  Otherwise one triple for all slots runs the scalar launches, until a second setting arrives for launches
@@ -2640,7 +2842,8 @@ class BatchedGenerator:
         switches off what an earlier request left, and allocates nothing on a decoder that never had one).  voices: the
         request's voice words (voices_ctl), likewise; a slot that gets one has its note order switched on.  density:
         the request's density words (density_ctl), likewise; a slot that gets one has its voice word and note order switched
-        on.  interval: the request's interval words (interval_ctl), likewise; it switches nothing else on.  shared: the
+        on.  interval: the request's interval words (interval_ctl), likewise; it switches nothing else on.  onsets: the request's onset templates (one for all
+        sequences or one per sequence, ForcedDecoder.set_onsets), likewise.  shared: the
         decoder that holds the
         request's common prompt once (its own cache layout: kept beside the unshared decoder of the same size)."""
         rows = sampling_rows(B, temperature, top_k, top_p)          # (validated before anything is built)
@@ -2653,6 +2856,7 @@ class BatchedGenerator:
         vox = voices_ctl(voices, B)
         den = density_ctl(density, B)
         mel = interval_ctl(interval, B)
+        ons = _onsets_per_slot(onsets, B)
         key = (B, self.trace is not None, self.sliding) + (("shared",) if shared else ())
         dec = self._decoders.get(key)
         if dec is None or dec.ld_chord < max_chords or dec.max_prompt < max_prompt:
@@ -2683,6 +2887,8 @@ class BatchedGenerator:
         dec.set_density(den)
         # (melodic interval: likewise; it leaves the other words as they are)
         dec.set_interval(mel)
+        # (onset templates: likewise; a request without them switches off what the one before left)
+        dec.set_onsets(ons)
         return dec
 
     @staticmethod
@@ -2696,8 +2902,11 @@ class BatchedGenerator:
     def generate(self, encoded_metas: Sequence[Sequence[int]], input_datas, temperature, top_k, top_p=1.0,
                  return_logprobs: bool = False, prompts: Optional[Sequence[Sequence[int]]] = None, logit_bias=None,
                  grammar=None, harmony=None, class_sampling=None, note_order=None, voices=None, density=None,
-                 interval=None):
-        """temperature / top_k / top_p: a number for the batch or one value per sequence.  interval: None / False, a word
+                 interval=None, onsets=None):
+        """temperature / top_k / top_p: a number for the batch or one value per sequence.  onsets: None / False, one
+        template in any form onset_rows takes, or a list with one entry (None / False / a template) per sequence -- such a
+        sequence DRAWS a position only where the row of its open bar has a bit; implies none of the other constraints
+        (ForcedDecoder.set_onsets).  interval: None / False, a word
         interval_word(up, down, no_repeat) or one per sequence -- the pitch such a sequence DRAWS lies at most up semitones
         above and down below the pitch of its last note, and (no_repeat) is not that pitch; implies none of the other
         constraints (ForcedDecoder.set_interval).  density: None / False, a word
@@ -2728,7 +2937,7 @@ class BatchedGenerator:
         dec = self.decoder(B, temperature, top_k, max_chords, top_p, per_slot=return_logprobs, max_prompt=max_prompt,
                            logit_bias=logit_bias, shared=self.shared_prompt and max_prompt > 0, grammar=grammar,
                            harmony=self._one_harmony(harmony), class_sampling=class_sampling, note_order=note_order,
-                           voices=voices, density=density, interval=interval)
+                           voices=voices, density=density, interval=interval, onsets=onsets)
         uniforms = None
         if bool((dec._sampling[0] != 0).any()) or dec.class_samples():
             srcs = self.uniform_sources or [np.random.RandomState(1000 + b).random_sample for b in range(B)]
@@ -2753,7 +2962,7 @@ class BatchedGenerator:
                         accept, top_p=1.0, slots: int = 64, seed: int = 0, max_attempts: Optional[int] = None,
                         return_logprobs: bool = False, prompt: Optional[Sequence[int]] = None, logit_bias=None,
                         share_prompt: bool = False, grammar=None, harmony=None, class_sampling=None, note_order=None,
-                        voices=None, density=None, interval=None):
+                        voices=None, density=None, interval=None, onsets=None):
         """Attempts of ONE request (the reference's `while idx != num_generate` loop, midi_inferrer.py:338-354, which tries
         one sequence after the other) decoded in up to `slots` parallel slots, CONTINUOUSLY: a slot whose sequence has
         ended is handed to `accept(sequence, report) -> bool` and re-armed with the next attempt while the other slots keep
@@ -2779,6 +2988,8 @@ class BatchedGenerator:
         (ForcedDecoder.set_density; likewise read off seq).
         interval: None / False or a word interval_word(up, down, no_repeat): one setting for every attempt of the request
         (ForcedDecoder.set_interval; likewise read off seq).
+        onsets: None / False or ONE template in any form onset_rows takes: one setting for every attempt of the request
+        (ForcedDecoder.set_onsets; the bar count is the forcing record's, the prompt's bars included).
         share_prompt (opt-in; also on with BatchedGenerator(shared_prompt=True) when a prompt is given): the K/V of the
         context and the prompt are computed and held once for all slots (ForcedDecoder(shared_prompt=True)); the attempts
         returned are the ones the unshared decoder defines, up to the summation order of the attention."""
@@ -2800,6 +3011,7 @@ class BatchedGenerator:
             raise CommuHipError(f"density: one setting for the request expected, got shape {np.shape(density)}")
         if interval is not None and np.ndim(interval) != 0:
             raise CommuHipError(f"interval: one setting for the request expected, got shape {np.shape(interval)}")
+        one_onsets = None if (onsets is None or onsets is False) else onset_rows(onsets)      # (ONE template, validated)
         max_chords = len(input_data.chord_token_components["chord_token"])
         # each control's schedule, validated on its own (the three may have different lengths)
         n_of = lambda x: 1 if np.ndim(x) == 0 else len(x)
@@ -2814,7 +3026,7 @@ class BatchedGenerator:
                            per_slot=return_logprobs or varying, max_prompt=0 if prompt is None else len(prompt),
                            logit_bias=logit_bias, shared=share, grammar=grammar, harmony=harmony,
                            class_sampling=class_sampling, note_order=note_order, voices=voices, density=density,
-                           interval=interval)
+                           interval=interval, onsets=one_onsets)
         started = B
         sampled = bool((sched[0] != 0).any()) or dec.class_samples()          # (a greedy attempt reads no variate)
         uni = np.stack([self.attempt_uniforms(seed, a, dec.ld_u) for a in range(B)]) if sampled else None
@@ -2973,7 +3185,7 @@ class BatchedGenerator:
         harm_table = _harmony_request(self._one_harmony(harmony))
         cls_table = _class_request(class_sampling)
         # each request's controls, validated before anything is built
-        triples, biases, orders, voxes, dens, mels = [], [], [], [], [], []
+        triples, biases, orders, voxes, dens, mels, onss = [], [], [], [], [], [], []
         for i, r in enumerate(requests):
             t, k, p = sampling_rows(1, r.temperature, r.top_k, r.top_p)
             triples.append((t[0].item(), int(k[0]), p[0].item()))
@@ -2982,6 +3194,7 @@ class BatchedGenerator:
             voxes.append(int(voices_ctl(r.voices, 1)[0]))
             dens.append(int(density_ctl(r.density, 1)[0]))
             mels.append(int(interval_ctl(r.interval, 1)[0]))
+            onss.append(None if (r.onsets is None or r.onsets is False) else onset_rows(r.onsets))
         B = max(1, min(slots, sum(int(r.need) for r in requests)))
         max_chords = max(len(r.input_data.chord_token_components["chord_token"]) for r in requests)
         key = ("pool", B, self.trace is not None, self.sliding)          # (never shared with generate / generate_stream:
@@ -3007,6 +3220,8 @@ class BatchedGenerator:
         dec.set_harmony(harm_table)
         use_den = any(d != DENSITY_OFF for d in dens)          # (the density rides on the voice words and the note order)
         use_mel = any(m != INTERVAL_OFF for m in mels)         # (the interval kernel reads all three words, on or off)
+        use_ons = any(t is not None for t in onss)             # (the onsets kernel reads all four words, on or off)
+        use_mel = use_mel or use_ons
         use_order = any(o != NOTE_ORDER_OFF for o in orders) or any(v != VOICES_OFF for v in voxes) or use_den or use_mel
         if cls_table is not None or use_order:
             dec._first_use(rows=True, bias=True, gram=True, harm=True, cls=True, order=use_order)
@@ -3016,6 +3231,10 @@ class BatchedGenerator:
             dec._first_use(density=True)
         if use_mel:
             dec._first_use(interval=True)
+        if use_ons:
+            # (the requests' templates go into the one table before the pool is opened; admit finds them by their bytes)
+            dec._first_use(onsets=True)
+            dec._onsets_pack(onss, fresh=True)
         if any(b is not None for b in biases):
             dec._first_use(bias=True)
         klen0_max = max([n_cond] + [p["klen0"] for p in replays if p is not None])
@@ -3039,7 +3258,8 @@ class BatchedGenerator:
                               grammar=(gram_table is not None) if r.grammar is None else bool(r.grammar),
                               harmony=(harm_table is not None) if r.harmony is None else bool(r.harmony),
                               note_order=orders[j.request], voices=voxes[j.request], class_table=cls_table,
-                              primed=replays[j.request], density=dens[j.request], interval=mels[j.request])
+                              primed=replays[j.request], density=dens[j.request], interval=mels[j.request],
+                              onsets=onss[j.request])
                 sampled = triples[j.request][0] != 0 or cls_samples          # (a greedy attempt reads no variate)
                 staged.append((j.slot, j.entry, self.attempt_uniforms(r.seed, j.attempt, dec.ld_u) if sampled else None))
                 if held[j.slot] is not None and held[j.slot] != j.request:

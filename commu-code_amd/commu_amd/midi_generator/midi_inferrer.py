@@ -14,6 +14,7 @@ callers of the reference touch:
 """
 from __future__ import annotations
 
+import json
 import math
 from typing import List, Optional
 
@@ -297,7 +298,8 @@ class InferenceTask:
 
     def execute(self, encoded_meta, max_rounds: Optional[int] = None, return_logprobs: bool = False,
                 prompt: Optional[List[int]] = None, logit_bias=None, grammar=None, harmony=None,
-                class_sampling=None, note_order=None, voices=None, density=None, interval=None):           # :338-354
+                class_sampling=None, note_order=None, voices=None, density=None, interval=None,
+                onsets=None):                                                                              # :338-354
         """return_logprobs (not in the reference): (sequences, their log-probability arrays -- ForcedDecoder.logprobs).
         prompt (not in the reference): token ids that follow the meta tokens; every attempt continues them (primed
         generation, BatchedGenerator.generate_stream) and every returned sequence starts with [0] + meta + prompt.
@@ -316,7 +318,9 @@ class InferenceTask:
         notes; switches the voice word and the note order on (ForcedDecoder.set_density).
         interval (not in the reference): a word generate.interval_word(up, down, no_repeat) -- a drawn pitch lies at most up
         semitones above and down below the pitch of the note before it; switches nothing else on
-        (ForcedDecoder.set_interval)."""
+        (ForcedDecoder.set_interval).
+        onsets (not in the reference): a template in any form generate.onset_rows takes -- a drawn position lies where the
+        row of its bar has a bit, bar i using row i mod R; switches nothing else on (ForcedDecoder.set_onsets)."""
         from ..generate import BatchedGenerator
         data = self.input_data
         glen = self.inference_cfg.GENERATION.generation_length
@@ -334,8 +338,6 @@ class InferenceTask:
             grammar = True
         # (likewise: generate.py --class_sampling, the JSON text of its document; an argument given here wins)
         if class_sampling is None and getattr(self.inference_cfg.GENERATION, "class_sampling", None):
-            import json
-
             from ..generate import read_class_sampling
             class_sampling = read_class_sampling(json.loads(self.inference_cfg.GENERATION.class_sampling))[0]
         # (likewise: generate.py --note_order / --max_notes, the control word; an argument given here wins)
@@ -350,6 +352,9 @@ class InferenceTask:
         # (likewise: generate.py --max_leap / --max_leap_up / --max_leap_down / --no_repeat_pitch, the interval word)
         if interval is None and getattr(self.inference_cfg.GENERATION, "interval", None) is not None:
             interval = int(self.inference_cfg.GENERATION.interval)
+        # (likewise: generate.py --onsets, the JSON text of the template's bars)
+        if onsets is None and getattr(self.inference_cfg.GENERATION, "onsets", None):
+            onsets = json.loads(self.inference_cfg.GENERATION.onsets)
         gen = BatchedGenerator(self.model, self.device, glen, mlen, sliding=sliding, kv_dtype=kv_dtype,
                                **({"shared_prompt": True} if share else {}))
 
@@ -375,14 +380,15 @@ class InferenceTask:
                                   **({} if note_order is None else {"note_order": note_order}),
                                   **({} if voices is None else {"voices": voices}),
                                   **({} if density is None else {"density": density}),
-                                  **({} if interval is None else {"interval": interval}))
+                                  **({} if interval is None else {"interval": interval}),
+                                  **({} if onsets is None else {"onsets": onsets}))
         return (res[0], res[2]) if return_logprobs else res[0]
 
     def execute_pool(self, items, return_logprobs: bool = False, harmony=None):
         """generate.py --requests (not in the reference): MANY requests in one pool of decode slots
         (BatchedGenerator.generate_pool).  items: one dict per request -- encoded_meta, input_data (its num_generate,
         temperature, top_k, top_p), seed, max_rounds, logit_bias, prompt (token ids the request's sequences continue, None
-        or [] for none).  Every request is accepted by the two validators of
+        or [] for none), onsets (the request's own onset template, None: the pool-wide one of --onsets, if any).  Every request is accepted by the two validators of
         execute() and bounded by max_rounds x num_generate attempts, as there; the pool-wide options (grammar, harmony,
         class_sampling, note_order, voices, density, interval, decode_slots, kv_cache, sliding_memory) come from the inference configuration
         as in execute().  Returns generate_pool's PoolResult list."""
@@ -394,14 +400,13 @@ class InferenceTask:
         grammar = True if bool(getattr(G, "grammar", False)) else None
         class_sampling = None
         if getattr(G, "class_sampling", None):
-            import json
-
             from ..generate import read_class_sampling
             class_sampling = read_class_sampling(json.loads(G.class_sampling))[0]
         note_order = None if getattr(G, "note_order", None) is None else int(G.note_order)
         voices = None if getattr(G, "voices", None) is None else int(G.voices)
         density = None if getattr(G, "density", None) is None else int(G.density)
         interval = None if getattr(G, "interval", None) is None else int(G.interval)
+        onsets = json.loads(G.onsets) if getattr(G, "onsets", None) else None
 
         def accept(seq, rep) -> bool:
             self.attempts += 1
@@ -421,6 +426,6 @@ class InferenceTask:
                                     max_attempts=None if mr is None else int(mr) * int(d.num_generate), accept=accept,
                                     logit_bias=it.get("logit_bias"), note_order=note_order, voices=voices,
                                     prompt=None if not it.get("prompt") else list(it["prompt"]), density=density,
-                                    interval=interval))
+                                    interval=interval, onsets=onsets if it.get("onsets") is None else it["onsets"]))
         return gen.generate_pool(reqs, slots=int(getattr(G, "decode_slots", 64)), grammar=grammar, harmony=harmony,
                                  class_sampling=class_sampling, return_logprobs=return_logprobs)

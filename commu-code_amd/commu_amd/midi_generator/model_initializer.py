@@ -89,6 +89,10 @@ class ModelInitializeTask:
         iword = getattr(self.model_args, "interval_word", None)
         if iword is not None:
             cfg.GENERATION.interval = int(iword)
+        # generate.py --onsets (not in the reference): the onset template as the JSON text of its list of bars
+        # (generate.py check_onsets)
+        if getattr(self.model_args, "onsets_bars", None) is not None:
+            cfg.GENERATION.onsets = str(self.model_args.onsets_bars)
         # generate.py --decode_slots (not in the reference): attempts decoded side by side (64 unless the key is set)
         if getattr(self.model_args, "decode_slots", None) not in (None, 64):
             cfg.GENERATION.decode_slots = int(self.model_args.decode_slots)

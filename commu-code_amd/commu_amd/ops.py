@@ -934,7 +934,7 @@ def _check_draw_state(kind, device, specs):
 
 def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=None, token=None, probs_out=None,
                 top_p=1.0, logp_out=None, bias=None, V=729, grammar=None, harmony=None, class_ctl=None,
-                note_order=None, voices=None, density=None, interval=None):
+                note_order=None, voices=None, density=None, interval=None, onsets=None):
     """In-place temperature + softmax + top-k + wrong-token mask + inverse-CDF draw per sequence.
     logits: fp32 [nseq, >=V] (row stride = ld), modified in place (logits[:, 1:V] /= temperature).
     top_p < 1: nucleus filter after the top-k / rejected-token step (an extra mode; the reference has top-k only).
@@ -985,7 +985,14 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
     up + 256 down + 65536 u -- with q the PITCH token of the last note of seq[b][0 : state[b][0]] that at most one BAR follows,
     ids q + up + 1 .. 130 are banned (up >= 1), ids 3 .. q - down - 1 (down >= 1) and q itself (u = 1); no such note: nothing.
     The bans join the note order's, the voice cap's and the density's in the same select.  One kernel serves it, the
-    density kernel's with the last note: density= is required (commu_sample_args.interval_ctl)."""
+    density kernel's with the last note: density= is required (commu_sample_args.interval_ctl).
+    onsets: (words, table) on the device of the logits -- words int32 [nseq], one control word per sequence
+    (generate.onset_ctl): -1 off, else base + 4096 R; table int32 [rows, 4] contiguous, 1 <= rows <= 4096, the bit patterns of
+    the uint32 template rows (generate.onset_rows): bit g % 32 of word g / 32 set means position id 432 + g may be drawn.  The
+    row of the open bar is base + (max(nb - 1, 0) mod R) with nb = state[b][8], the record's count of BAR tokens in seq; every
+    position id whose bit is clear is banned, in the same select as the four rules above, and the density's lower bound lets
+    a bar end once the position range together with the row leaves no position.  One kernel serves it, the interval kernel's
+    with the row: interval= is required (commu_sample_args.onset_ctl / onset_table / onset_rows)."""
     nseq = logits.shape[0]
     V = int(V)
     assert logits.dtype == F32 and logits.stride(1) == 1
@@ -1063,6 +1070,18 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
         _check_draw_state("interval", logits.device, (
             (interval, "controls", torch.int32, "[%d]" % nseq, lambda t: tuple(t.shape) == (nseq,)),))
         a.interval_ctl = _p(interval)
+    if onsets is not None:
+        if interval is None:
+            raise CommuHipError("onsets: interval= expected as well (the one kernel is the interval kernel's with the template "
+                                "row; pass words that are all -1 where there is no interval)")
+        if not isinstance(onsets, (tuple, list)) or len(onsets) != 2:
+            raise CommuHipError("onsets: a pair (control words int32 [nseq], table int32 [rows, 4]) expected")
+        owords, otable = onsets
+        _check_draw_state("onsets", logits.device, (
+            (owords, "controls", torch.int32, "[%d]" % nseq, lambda t: tuple(t.shape) == (nseq,)),
+            (otable, "table", torch.int32, "[1 .. 4096, 4]",
+             lambda t: t.dim() == 2 and 1 <= t.shape[0] <= 4096 and t.shape[1] == 4)))
+        a.onset_ctl, a.onset_table, a.onset_rows = _p(owords), _p(otable), int(otable.shape[0])
     if harmony is not None:
         htable, hon, hstate, chord_tok = harmony
         _check_draw_state("harmony", logits.device, (

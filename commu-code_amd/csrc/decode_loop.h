@@ -232,8 +232,34 @@ struct Density {
 struct Interval {
     int ctl;                // the sequence's control as the caller loaded it
 };
+// ONS (Onsets: one int32 control per sequence, -1 off, else base + 4096 R with R in 1 .. 64 the cycle length, base in
+//   0 .. 4095, base + R <= rows; table uint32 [rows][4], 1 <= rows <= 4096): WHEN a note may start.  A row is a 128-bit mask
+//   over the bar's grid: bit g % 32 of word g / 32 set means POSITION id 432 + g may be drawn.  With nb the BAR tokens in S,
+//   the open bar is i = max(nb - 1, 0) (the stretch before the first BAR uses bar 0's row, as DEN counts it), its row
+//   base + (i mod R), and every POSITION id whose bit is clear is banned.  The bans join the select of ORD, VOX, DEN and MEL,
+//   so a draw is bit for bit the MEL kernel's with bias[b] = -inf at these ids; an all-clear row is a bar of rest.
+//   nb IS NOT COUNTED: it is the record's F_NBAR, which forcing_pre_body / forcing_post_body keep equal to seq.count(BAR)
+//   on every path that appends a token (the forced append and the drawn append below; load() writes 0 beside a seq of
+//   conditioning tokens, none of which is BAR; the prompt replay runs the same two bodies; rearm / admit / the arm launches
+//   copy a record that one of these wrote).  The fused loop has it in registers, the stand-alone launch reads it beside F_LEN.
+//   THE ROW is wave-uniform: control word and nb are scalars, so the four words are one scalar load whose address needs the
+//   record only; it is issued beside the grammar row's loads and travels under the chain record -> previous token -> grammar
+//   row.  The row index is clamped to rows - 1, so the kernel stays in bounds whatever an array holds; an off word
+//   substitutes the all-ones row by a select, there is no branch on it.  A lane builds the bits of its 12 ids from the row
+//   with one 64-bit shift (ids 432 .. 559 are lanes 36 .. 46; 12 bits span at most two words).
+//   THE DENSITY WAIVER changes with ONS: DEN's lower bound bans BAR and EOS unless no position is left, and a position is
+//   left only where the merged banned range [432, hi) AND the row leave it -- row AND NOT range, four scalar words tested
+//   against zero.  With the all-ones row that is hi != 560, the parent's test.  No LDS, no load but the control word and the
+//   row.  ONS needs MEL.
+struct Onsets {
+    int ctl;                // the sequence's control as the caller loaded it
+    const unsigned* table;  // uint32 [rows][4]
+    int rows;               // 1 .. 4096 (the entry points refuse anything else)
+    int nbar;               // the record's F_NBAR
+};
+constexpr int ONS_ROWS_MAX = 4096, ONS_CYCLE_MAX = 64;
 template <bool BIAS, bool GRAM = false, bool HARM = false, bool CLS = false, bool ORD = false, bool VOX = false,
-          bool DEN = false, bool MEL = false>
+          bool DEN = false, bool MEL = false, bool ONS = false>
 __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restrict__ logits, int ld, int V,
                                                  const unsigned char* __restrict__ wrong, int ldw,
                                                  const float* __restrict__ uni,
@@ -246,12 +272,14 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
                                                  Harmony h = Harmony{nullptr, 0, nullptr, 0, 0, 0},
                                                  ClassControls cc = ClassControls{nullptr},
                                                  NoteOrder no = NoteOrder{-1}, Voices vx = Voices{-1},
-                                                 Density dn = Density{-1}, Interval ml = Interval{-1}) {
+                                                 Density dn = Density{-1}, Interval ml = Interval{-1},
+                                                 Onsets os = Onsets{-1, nullptr, 1, 0}) {
     static_assert(!CLS || GRAM, "the class key is the grammar's previous token");
     static_assert(!ORD || CLS, "one note-order instantiation: the class kernel's with the scan");
     static_assert(!VOX || ORD, "one voices instantiation: the note-order kernel's with the longer scan");
     static_assert(!DEN || VOX, "one density instantiation: the voices kernel's with the count of the open bar's notes");
     static_assert(!MEL || DEN, "one interval instantiation: the density kernel's with the reference note");
+    static_assert(!ONS || MEL, "one onsets instantiation: the interval kernel's with the template row");
     float* lg = logits + (size_t)b * ld;
     // The optional per-sequence inputs -- the active flag and this sequence's controls -- are loaded unconditionally: a null
     // array reads a valid word of this sequence instead (token[b], logits[b][0]), which is then ignored.  So they are in
@@ -297,6 +325,21 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
         const int row = __builtin_amdgcn_readfirstlane(g.on != 0 ? token_class(prev) : 7);
 #pragma unroll
         for (int e = 0; e < PER_LANE; ++e) gv[e] = g.table[(size_t)row * g.ld + min(base + e, V - 1)];
+    }
+    // (ONS) the open bar's template row, the same for every lane: its address needs the record and the control word only,
+    // so the one scalar load goes out beside the grammar row's; an off word reads row 0 and selects all ones
+    unsigned or0 = ~0u, or1 = ~0u, or2 = ~0u, or3 = ~0u;
+    if constexpr (ONS) {
+        const int octl = __builtin_amdgcn_readfirstlane(os.ctl);
+        const int obar = max(__builtin_amdgcn_readfirstlane(os.nbar) - 1, 0);
+        const int ocyc = min(max(octl >> 12, 1), ONS_CYCLE_MAX);
+        const int orow = min(max((octl & (ONS_ROWS_MAX - 1)) + obar % ocyc, 0), os.rows - 1);
+        const unsigned* ow = os.table + 4 * (size_t)__builtin_amdgcn_readfirstlane(octl >= 0 ? orow : 0);
+        const unsigned w0 = ow[0], w1 = ow[1], w2 = ow[2], w3 = ow[3];
+        or0 = octl >= 0 ? w0 : ~0u;
+        or1 = octl >= 0 ? w1 : ~0u;
+        or2 = octl >= 0 ? w2 : ~0u;
+        or3 = octl >= 0 ? w3 : ~0u;
     }
     // (HARM) the 12 pitch-class values of the chord's row, the same for every lane: element e of a lane is id 12 l + e,
     // MIDI pitch 12 l + e - 3, pitch class (e + 9) mod 12
@@ -464,6 +507,15 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
             hi = (dhi >= 1 && dcount >= dhi) ? TOK_POS0 + POS_RES : hi;
             // (the waiver: every position is banned already, by the three rules together -- the bar may end)
             dend = dlo >= 1 && dcount < dlo && hi != TOK_POS0 + POS_RES;
+            if constexpr (ONS) {
+                // (the waiver with a template: a position is left only where the merged range and the row both leave it)
+                const int ban = hi - TOK_POS0;                 // grid steps 0 .. ban - 1 are banned by the range
+                const auto left = [&](unsigned w, int k) {
+                    const int nlow = min(max(ban - 32 * k, 0), 32);
+                    return nlow >= 32 ? 0u : (w & ~((1u << nlow) - 1u));
+                };
+                dend = dlo >= 1 && dcount < dlo && (left(or0, 0) | left(or1, 1) | left(or2, 2) | left(or3, 3)) != 0u;
+            }
         }
         // the lane's 12 flags as 16-byte LDS reads, unconditional (the lanes past the flags read the last owner's and
         // drop them), packed into a bit mask without a branch: behind a branch per element they were 12 dependent LDS
@@ -494,6 +546,17 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
             omask |= ((1u << u1) - 1u) & ~((1u << u0) - 1u);
             omask |= ((1u << d1) - 1u) & ~((1u << d0) - 1u);
             omask |= (unsigned)(same - base) < (unsigned)PER_LANE ? 1u << (same - base) : 0u;
+        }
+        if constexpr (ONS) {
+            // the lane's 12 bits of the row start at grid step g0 = base - 432 (lanes 36 .. 46: 0, 12, .. 120) and span at most
+            // two words; lanes that own no position id have an empty range below and what they shift is dropped
+            const int g0 = base - TOK_POS0;
+            const int w = (g0 >> 5) & 3;
+            const unsigned wlo = w == 0 ? or0 : (w == 1 ? or1 : (w == 2 ? or2 : or3));
+            const unsigned whi = w == 0 ? or1 : (w == 1 ? or2 : (w == 2 ? or3 : 0u));
+            const unsigned may = (unsigned)(((((unsigned long long)whi) << 32) | wlo) >> (g0 & 31));
+            const int p0 = min(max(TOK_POS0 - base, 0), PER_LANE), p1 = min(max(TOK_POS0 + POS_RES - base, 0), PER_LANE);
+            omask |= ~may & (((1u << p1) - 1u) & ~((1u << p0) - 1u));
         }
     }
     if (active != nullptr && act_row == 0) return -2;

@@ -139,6 +139,21 @@ def parse_args():
     model_arg_parser.add_argument("--no_repeat_pitch", action="store_true",
                                   help="no drawn pitch repeats the pitch of the note before it (same reference note as "
                                        "--max_leap)")
+    # not in the reference (whose conditioning has one coarse rhythm token and nothing finer, so that two tracks generated
+    # from the same metadata share no groove): --onsets TEMPLATE -- a position is DRAWN only where the template's row for
+    # the bar being written allows an onset; bar i uses row i mod R, the bars of --prompt_tokens counted.  TEMPLATE is
+    # JSON text or a file holding it: a list of bars, each a list of positions 0 .. 127; {"grid": n}, n a power of two from
+    # 1 to 128 (the multiples of 128 / n); {"bars": [...]}; or {"from_tokens": [ids], "invert": bool} -- the onsets of a
+    # finished track bar by bar, or with invert the positions it leaves free.  It implies none of the other constraints
+    # and needs no --grammar.  NOT covered: forced tokens (the position 0 forced after a Bar, a chord's forced position,
+    # and so a note that starts on either), notes inside --prompt_tokens, a bar cut by --generation_length; a template,
+    # pitch range or strict --harmony that leaves nothing to draw in a family ends that attempt as before.  With
+    # --requests it holds for every request that does not carry an "onsets" of its own.
+    model_arg_parser.add_argument("--onsets", default=None, metavar="TEMPLATE",
+                                  help='a drawn note starts only where the bar\'s row of the template allows: JSON text or '
+                                       'file, [[positions 0 .. 127], ...] per bar (cycled), {"grid": n}, {"bars": [...]} or '
+                                       '{"from_tokens": [ids], "invert": bool}.  Not covered: forced positions, notes '
+                                       'inside --prompt_tokens')
     # not in the reference (which decodes one sequence at a time): how many attempts are decoded side by side.  1 .. 256;
     # up to 256 slots run the fused layer-tail launches ("Supported shapes").  The sequences returned do
     # not depend on it.  (checked by check_decode_slots: the range is named in its message)
@@ -280,7 +295,8 @@ REQUEST_META_KEYS = ("bpm", "audio_key", "time_signature", "pitch_range", "num_m
 REQUEST_KEYS = REQUEST_META_KEYS + ("num_generate", "top_k", "temperature", "top_p", "seed", "max_rounds", "pitch_min",
                                     "pitch_max", "logit_bias")
 # (keys a request object may carry and that its parsed dict holds only then: prompt_tokens, the token ids it continues)
-REQUEST_OPTIONAL_KEYS = ("prompt_tokens",)
+# and onsets, its own onset template (--onsets' forms, as JSON values)
+REQUEST_OPTIONAL_KEYS = ("prompt_tokens", "onsets")
 # (single-request input arguments that --requests replaces, with the value the parser gives them when they are not named)
 SINGLE_REQUEST_ARGS = {**{k: None for k in REQUEST_META_KEYS}, "genre": "cinematic", "rhythm": "standard",
                        "num_generate": None, "top_k": 32, "temperature": 0.95, "top_p": 1.0, "max_rounds": None,
@@ -292,7 +308,8 @@ def check_requests(model_args, input_args):
     the parser's defaults where an object does not name one (seed 0).  Host code only, run before a model is loaded;
     ValueError that says what is wrong -- a single-request input argument, --prompt_tokens, --share_prompt or --parity
     beside --requests, --gpus above 1, a file that is not a JSON list of objects, an unknown key, a missing
-    num_generate or a prompt_tokens value that is not a list of integers (with the index of the request)."""
+    num_generate, a prompt_tokens value that is not a list of integers or an onsets value that is no template (with the
+    index of the request)."""
     path = getattr(input_args, "requests", None)
     if path is None:
         return None
@@ -336,8 +353,61 @@ def check_requests(model_args, input_args):
         pt = r.get("prompt_tokens", [])
         if not isinstance(pt, list) or not all(isinstance(t, int) and not isinstance(t, bool) for t in pt):
             raise ValueError(f"--requests: {path}: request {i}: prompt_tokens: a JSON list of token ids expected, got {pt!r}")
+        if r.get("onsets") is not None:
+            try:
+                r = {**r, "onsets": onsets_bars(r["onsets"], "onsets")}
+            except ValueError as e:
+                raise ValueError(f"--requests: {path}: request {i}: {e}") from None
         out.append({**SINGLE_REQUEST_ARGS, "seed": 0, **r})
     return out
+
+
+def onsets_bars(doc, what="--onsets"):
+    """An onset template given as a JSON value -- a list of bars, {"grid": n}, {"bars": [...]} or {"from_tokens": [ids],
+    "invert": bool} -- as its list of bars, each the sorted list of positions 0 .. 127 that may hold an onset; host code
+    only, ValueError that says what is wrong."""
+    from commu_amd.generate import CommuHipError, onset_rows, onsets_of
+    if isinstance(doc, dict) and "from_tokens" in doc:
+        extra = sorted(set(doc) - {"from_tokens", "invert"})
+        toks, inv = doc["from_tokens"], doc.get("invert", False)
+        if extra:
+            raise ValueError(f'{what}: {{"from_tokens": [ids], "invert": bool}} expected, got the key {extra[0]!r} as well')
+        if not isinstance(toks, list) or not all(isinstance(t, int) and not isinstance(t, bool) and 0 <= t < 729 for t in toks):
+            raise ValueError(f"{what}: from_tokens: a JSON list of token ids in [0, 729) expected")
+        if not isinstance(inv, bool):
+            raise ValueError(f"{what}: invert: true or false expected, got {inv!r}")
+        doc = onsets_of(toks, invert=inv)
+    try:
+        rows = onset_rows(doc)
+    except CommuHipError as e:
+        raise ValueError(f"{what}: {str(e).removeprefix('onsets: ')}") from None
+    return [[g for g in range(128) if (int(row[g // 32]) >> (g % 32)) & 1] for row in rows]
+
+
+def check_onsets(model_args):
+    """--onsets as the JSON text of the template's list of bars (None without the flag): the value is the JSON document
+    itself or the path of a file that holds it.  Host code only, run before a model is loaded; ValueError that says what is
+    wrong.  Written back to model_args.onsets_bars, which travels to the replicas (ModelInitializeTask puts it into the
+    inference configuration).  It switches nothing else on."""
+    setting = getattr(model_args, "onsets", None)
+    model_args.onsets_bars = None
+    if setting is None:
+        return None
+    text = setting
+    if not isinstance(setting, str):
+        raise ValueError(f"--onsets: JSON text or a readable JSON file expected, got {setting!r}")
+    if not setting.lstrip().startswith(("{", "[")):
+        try:
+            with open(setting) as f:
+                text = f.read()
+        except OSError as e:
+            raise ValueError(f"--onsets: JSON text or a readable JSON file expected, got {setting!r} ({e.strerror})") from None
+    try:
+        doc = json.loads(text)
+    except json.JSONDecodeError as e:
+        raise ValueError(f"--onsets: not JSON ({e})") from None
+    model_args.onsets_bars = json.dumps(onsets_bars(doc))
+    return model_args.onsets_bars
 
 
 def check_density(model_args):
@@ -500,6 +570,7 @@ def main(model_args, input_args, training_cfg=None, device_indices=None):
     check_voices(model_args)                            # (likewise; ahead of the note order, which it switches on)
     check_density(model_args)                           # (likewise)
     check_interval(model_args)                          # (likewise)
+    check_onsets(model_args)                            # (likewise)
     check_note_order(model_args)                        # (likewise)
     in_args = dict(vars(input_args))
     in_args.pop("requests", None)

@@ -558,6 +558,28 @@ int commu_transpose_heads(const void* src, int ld, const float* bias, void* dst,
  *     and everything density_ctl requires, else -22.  Validating the words is the caller's job (generate.interval_ctl).
  *     The same field, with the same meaning and the same refusal, is in commu_decode_loop_args.  Null: the launch that
  *     never heard of it.
+ * ONSET TEMPLATES (the reference's conditioning has one coarse rhythm token; nothing says WHEN a note may start, so two
+ * tracks generated from the same metadata share no groove)
+ *   onset_ctl: int32 [nseq], one control word per sequence: -1 off, else base + 4096 R with R in 1 .. 64 the cycle length,
+ *     base in 0 .. 4095 and base + R <= onset_rows.  onset_table: uint32 [onset_rows][4], 1 <= onset_rows <= 4096; a row is a
+ *     128-bit mask over the bar's 128-step grid: bit g % 32 of word g / 32 set means POSITION id 432 + g may be drawn.  With
+ *     nb the BAR tokens in S (taken from the forcing record: state[b][8], which the forcing stage keeps equal to that
+ *     count), the OPEN BAR is i = max(nb - 1, 0) -- the stretch before the first BAR uses bar 0's row, as density_ctl counts
+ *     it -- and its row is base + (i mod R), clamped to onset_rows - 1 whatever the arrays hold.  BANNED: every POSITION id
+ *     whose bit is clear.  i counts a prompt's bars too: a primed sequence continues the cycle in phase.  The bans join
+ *     order_ctl's, voice_ctl's, density_ctl's and interval_ctl's in the same select, so all that is said for order_ctl
+ *     holds; an all-clear row is a bar of rest.  A draw is BIT FOR BIT the draw of the call without onset_ctl and with
+ *     bias[b] = -inf at these ids; an off word, or a word over an all-ones row, is bit for bit the call without the field.
+ *     DENSITY WAIVER: with onset_ctl given, density_ctl's LOWER bound bans BAR and EOS unless NO position id is left
+ *     unbanned by the merged position range TOGETHER WITH the template row (an off word: the all-ones row, i.e. exactly the
+ *     rule above).  It is the one place where the template is more than a bias.
+ *     NOT COVERED: forced tokens (the position 0 forced after a BAR, a chord's forced position, and so a note that starts
+ *     on either); notes inside a prompt; a bar cut by the generation length; a template, bias or harmony that leaves
+ *     nothing to draw in a family ends the attempt by Q12, as before.
+ *     ONE kernel serves it, the interval kernel with the row's four words loaded beside the grammar row: onset_ctl
+ *     requires interval_ctl and everything interval_ctl requires, a non-null onset_table and 1 <= onset_rows <= 4096,
+ *     else -22.  Validating the words is the caller's job (generate.onset_ctl).  The same three fields, with the same
+ *     meaning and the same refusals, are in commu_decode_loop_args.  Null onset_ctl: the launch that never heard of it.
  * WHAT gram / harm READ
  *   state: the forcing records, int32 [nseq][commu_forcing_state_ints()]; seq int32 [nseq][ld_seq]; chord_tok int32
  *   [nseq][ld_chord].  Not looked at, and may be null, in a call without gram and harm.
@@ -597,6 +619,10 @@ typedef struct commu_sample_args {
     const int* seq;
     const int* chord_tok;
     int ld_seq, ld_chord;
+    /* onset templates (ahead of interval_ctl: the five fields behind them keep their places at the struct's end) */
+    const int* onset_ctl;
+    const unsigned* onset_table;
+    int onset_rows;
     /* melodic interval (ahead of density_ctl: the four fields behind it keep their places at the struct's end) */
     const int* interval_ctl;
     /* note density (ahead of order_ctl: the three fields behind it keep their places at the struct's end) */
@@ -824,6 +850,10 @@ typedef struct commu_decode_loop_args {
     const float* harm;
     const unsigned char* harm_on;
     int ld_bias, ld_gram, ld_harm;
+    /* onset templates (commu_sample_args.onset_ctl / onset_table / onset_rows; likewise ahead of interval_ctl) */
+    const int* onset_ctl;
+    const unsigned* onset_table;
+    int onset_rows;
     /* melodic interval (commu_sample_args.interval_ctl; likewise ahead of density_ctl) */
     const int* interval_ctl;
     /* note density (commu_sample_args.density_ctl; likewise ahead of order_ctl) */
@@ -882,7 +912,8 @@ int commu_decode_prefill_scatter(const void* qkv, int ld_qkv, int T, int B, void
  *   loop's entry point treats a null array:  seq_logp[slot][0 .. 2 ld_seq) = NaN;  trace[slot][0 .. ld_trace) = 0;
  *   temperature_rows / top_k_rows / top_p_rows [slot] = e_temperature / e_top_k / e_top_p [entry];
  *   bias[slot][0 .. ld_bias) = e_bias[entry];  gram_on / harm_on [slot] = e_gram_on / e_harm_on [entry] (bytes);
- *   order_ctl / voice_ctl / density_ctl / interval_ctl [slot] = e_order / e_voice / e_density / e_interval [entry];
+ *   order_ctl / voice_ctl / density_ctl / interval_ctl / onset_ctl [slot] = e_order / e_voice / e_density / e_interval /
+ *   e_onset [entry] (the onset table is the pool's own: no table bytes move per arm);
  *   cls_ctl[slot][0 .. 32) = e_cls[entry] (int32).
  * tok / active / keep / draw are NOT written: an armed slot sits out the iteration whose decision was taken from its
  * finished record and starts with the next one.  Two jobs of one launch must name different slots (the caller's duty).
@@ -939,6 +970,8 @@ typedef struct commu_decode_arm_args {
     const unsigned char* e_gram_on;
     unsigned char* harm_on;
     const unsigned char* e_harm_on;
+    int* onset_ctl;
+    const int* e_onset;
     int* interval_ctl;
     const int* e_interval;
     int* density_ctl;
@@ -1028,6 +1061,8 @@ typedef struct commu_decode_arm_primed_args {
     const unsigned char* e_gram_on;
     unsigned char* harm_on;
     const unsigned char* e_harm_on;
+    int* onset_ctl;
+    const int* e_onset;
     int* interval_ctl;
     const int* e_interval;
     int* density_ctl;
