@@ -748,6 +748,214 @@ def _onsets_per_slot(x, B: int):
     return [t] * B
 
 
+# ---- guide track: one int32 control word per slot (commu_sample_args.guide_ctl) and one device table of 128-bit rows
+# (guide_table).  A template has R bars of C = 128 >> s cells; a bar is a block of 1 + C rows: the LIVE ROW (a mask over
+# positions, the onset table's format) and C CELL ROWS (masks over pitches: bit k is pitch id 3 + k, MIDI pitch k).  A slot
+# that is on DRAWS a pitch only where the cell row of the position its bar is at has a bit, and a position only where the
+# live row has one.  The block of the open bar is base + (i mod R) (1 + C), i as for the onsets.  It implies none of the
+# other words.
+GUIDE_OFF = -1
+GUIDE_ROWS_MAX = 65536         # rows of the device table (1 MB); the word is base + 65536 R + 2^23 s
+GUIDE_CYCLE_MAX = 64           # bars of one template
+GUIDE_KEYS_RAW = {"cells", "bars", "pitch_range"}
+GUIDE_KEYS_DERIVED = {"from_tokens", "cells", "avoid_intervals", "no_unison", "below", "above", "pitch_range"}
+
+
+def guide_word(base: int, bars: int, cells: int) -> int:
+    """The control word base + 65536 R + 2^23 s of a template of R bars of `cells` = 128 >> s cells at table row base."""
+    return int(base) + 65536 * int(bars) + (1 << 23) * _guide_shift(cells)
+
+
+def _guide_shift(cells) -> int:
+    if isinstance(cells, bool) or not isinstance(cells, (int, np.integer)) or not 1 <= cells <= ONSET_GRID or cells & (cells - 1):
+        raise CommuHipError(f"guide: cells is a power of two from 1 to {ONSET_GRID}, got {cells!r}")
+    return 7 - (int(cells).bit_length() - 1)
+
+
+def _guide_range(pitch_range):
+    if pitch_range is None:
+        return 0, 127
+    try:
+        lo, hi = pitch_range
+        ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (lo, hi)) and 0 <= lo <= hi <= 127
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise CommuHipError(f"guide: pitch_range is a pair of MIDI pitches 0 <= lo <= hi <= 127, got {pitch_range!r}")
+    return int(lo), int(hi)
+
+
+def sounding_of(seq, start: int = 0):
+    """The notes of a token sequence on the absolute grid, with its bars counted as the rule counts them: a list
+    (bars, notes), bars the number of bars (the stretch before the first Bar is bar 0) and notes a list of (first step,
+    one past the last step, MIDI pitch) for every complete Position, Velocity, Pitch, Duration group at index >= start:
+    first step 128 bar + position, length in steps the duration id - 303."""
+    seq = [int(t) for t in seq]
+    nb, notes = 0, []
+    for i, t in enumerate(seq):
+        if t == ONSET_BAR:
+            nb += 1
+        elif i >= int(start) and _is_note_at(seq, i):
+            a = ONSET_GRID * max(nb - 1, 0) + (t - ONSET_POS0)
+            notes.append((a, a + seq[i + 3] - 303, seq[i + 2] - 3))
+    return max(nb, 1), notes
+
+
+def _guide_cells_of(doc):
+    """The derived form as a list of bars of C cells, each cell a 128-bit Python int over MIDI pitches."""
+    extra = sorted(set(doc) - GUIDE_KEYS_DERIVED)
+    if extra:
+        raise CommuHipError(f"guide: unknown key {extra[0]!r} beside from_tokens (known: {sorted(GUIDE_KEYS_DERIVED)})")
+    toks = doc["from_tokens"]
+    if not isinstance(toks, (list, tuple, np.ndarray)) or not all(
+            isinstance(t, (int, np.integer)) and not isinstance(t, bool) and 0 <= t < 729 for t in toks):
+        raise CommuHipError("guide: from_tokens: a list of token ids in [0, 729) expected")
+    cells = doc.get("cells", 16)
+    s = _guide_shift(cells)
+    avoid = doc.get("avoid_intervals", [1, 11])
+    if not isinstance(avoid, (list, tuple)) or not all(
+            isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 0 <= v <= 11 for v in avoid):
+        raise CommuHipError(f"guide: avoid_intervals: interval classes 0 .. 11 expected, got {avoid!r}")
+    uni = doc.get("no_unison", False)
+    if not isinstance(uni, (bool, np.bool_)):
+        raise CommuHipError(f"guide: no_unison: true or false expected, got {uni!r}")
+    if "below" in doc and "above" in doc:
+        raise CommuHipError(f"guide: below ({doc['below']!r}) beside above ({doc['above']!r}): one of them expected")
+    for k in ("below", "above"):
+        if k in doc and (isinstance(doc[k], bool) or not isinstance(doc[k], (int, np.integer)) or not 0 <= doc[k] <= 127):
+            raise CommuHipError(f"guide: {k}: a number of semitones 0 .. 127 expected, got {doc[k]!r}")
+    nbars, notes = sounding_of(toks)
+    if nbars > GUIDE_CYCLE_MAX:
+        raise CommuHipError(f"guide: a template holds 1 .. {GUIDE_CYCLE_MAX} bars, the track has {nbars}")
+    full = (1 << 128) - 1
+    steps = [full] * (nbars * ONSET_GRID)
+    sound = [[] for _ in steps]
+    for a, e, y in notes:
+        for t in range(a, min(e, len(steps))):
+            sound[t].append(y)
+    memo = {}
+    for t, ys in enumerate(sound):
+        if not ys:
+            continue          # (a silent step allows everything)
+        key = tuple(sorted(set(ys)))
+        if key not in memo:
+            m = 0
+            for x in range(128):
+                ok = all((x - y) % 12 not in avoid for y in key)
+                ok = ok and not (uni and x in key)
+                ok = ok and not ("below" in doc and x > key[0] - int(doc["below"]))
+                ok = ok and not ("above" in doc and x < key[-1] + int(doc["above"]))
+                m |= int(ok) << x
+            memo[key] = m
+        steps[t] = memo[key]
+    per = 1 << s
+    out = []
+    for b in range(nbars):
+        bar = []
+        for c in range(int(cells)):
+            m = full
+            for t in range(b * ONSET_GRID + c * per, b * ONSET_GRID + (c + 1) * per):
+                m &= steps[t]
+            bar.append(m)
+        out.append(bar)
+    return out, s
+
+
+def _guide_cells_raw(doc):
+    extra = sorted(set(doc) - GUIDE_KEYS_RAW)
+    if extra:
+        raise CommuHipError(f"guide: unknown key {extra[0]!r} (known: {sorted(GUIDE_KEYS_RAW)}, or the from_tokens form)")
+    if "cells" not in doc or "bars" not in doc:
+        raise CommuHipError(f'guide: {{"cells": C, "bars": [...]}} or {{"from_tokens": [...], ...}} expected, got the keys '
+                            f'{sorted(map(str, doc))}')
+    cells = doc["cells"]
+    s = _guide_shift(cells)
+    bars = doc["bars"]
+    if not isinstance(bars, (list, tuple)) or not 1 <= len(bars) <= GUIDE_CYCLE_MAX:
+        raise CommuHipError(f"guide: a template holds 1 .. {GUIDE_CYCLE_MAX} bars, got "
+                            f"{len(bars) if isinstance(bars, (list, tuple)) else bars!r}")
+    full = (1 << 128) - 1
+    out = []
+    for i, bar in enumerate(bars):
+        if not isinstance(bar, (list, tuple)) or len(bar) != cells:
+            raise CommuHipError(f"guide: bar {i}: {cells} cells expected, got "
+                                f"{len(bar) if isinstance(bar, (list, tuple)) else bar!r}")
+        row = []
+        for c, cell in enumerate(bar):
+            if cell is None:
+                row.append(full)
+                continue
+            if not isinstance(cell, (list, tuple)) or not all(
+                    isinstance(x, (int, np.integer)) and not isinstance(x, bool) and 0 <= x <= 127 for x in cell):
+                raise CommuHipError(f"guide: bar {i}, cell {c}: null or a list of MIDI pitches 0 .. 127 expected, got {cell!r}")
+            m = 0
+            for x in cell:
+                m |= 1 << int(x)
+            row.append(m)
+        out.append(row)
+    return out, s
+
+
+def _guide_words4(m: int) -> List[int]:
+    return [(m >> (32 * k)) & 0xFFFFFFFF for k in range(4)]
+
+
+def guide_template(x, pitch_range=None):
+    """A guide as (rows, cells): rows uint32 [R (1 + C)][4], per bar the live row and the C cell rows (guide_rows), and C.
+    x: the raw form {"cells": C, "bars": [[null | [MIDI pitches], .. C entries], ..]} (null: every pitch); the derived form
+    {"from_tokens": [ids], "cells": C = 16, "avoid_intervals": [1, 11], "no_unison": false, "below": m | "above": m}; either
+    may carry "pitch_range": [lo, hi], used where the argument is None; or a pair (uint32 [R (1 + C)][4], C) that is one
+    already.  Pure host code; raises CommuHipError on anything else, with the value."""
+    if isinstance(x, tuple) and len(x) == 2 and isinstance(x[0], np.ndarray) and x[0].dtype == np.uint32:
+        rows, cells = x
+        per = 1 + (ONSET_GRID >> _guide_shift(cells))
+        if rows.ndim != 2 or rows.shape[1] != 4 or rows.shape[0] % per or not 1 <= rows.shape[0] // per <= GUIDE_CYCLE_MAX:
+            raise CommuHipError(f"guide: a uint32 template of {cells} cells is [R * {per}][4] with R in 1 .. "
+                                f"{GUIDE_CYCLE_MAX}, got shape {rows.shape}")
+        return np.ascontiguousarray(rows), int(cells)
+    if not isinstance(x, dict):
+        raise CommuHipError(f'guide: {{"cells": C, "bars": [...]}} or {{"from_tokens": [...], ...}} expected, got {x!r}')
+    if pitch_range is None:
+        pitch_range = x.get("pitch_range")
+    lo, hi = _guide_range(pitch_range)
+    bars, s = _guide_cells_of(x) if "from_tokens" in x else _guide_cells_raw(x)
+    cells = ONSET_GRID >> s
+    inside = ((1 << (hi + 1)) - 1) & ~((1 << lo) - 1)
+    out = np.zeros((len(bars) * (1 + cells), 4), dtype=np.uint32)
+    for b, bar in enumerate(bars):
+        live = 0
+        for c, m in enumerate(bar):
+            out[b * (1 + cells) + 1 + c] = _guide_words4(m)
+            if m & inside:          # (the live bits of the cell's steps: the cell leaves a pitch of the range)
+                live |= ((1 << (1 << s)) - 1) << (c << s)
+        out[b * (1 + cells)] = _guide_words4(live)
+    return out, cells
+
+
+def guide_rows(x, pitch_range=None) -> np.ndarray:
+    """A guide's table rows, uint32 [R (1 + C)][4]: per bar one LIVE ROW (bit g % 32 of word g // 32: a note may start at
+    step g -- set iff the step's cell, intersected with pitch_range = (lo, hi) MIDI when given, leaves a pitch) and C CELL
+    ROWS (bit k % 32 of word k // 32: MIDI pitch k, token id 3 + k, may be drawn).  x as for guide_template.  In the derived
+    form the notes of the finished track are its Position, Velocity, Pitch, Duration groups, a note's length in steps its
+    duration id - 303, on the absolute grid 128 bar + position with the bars counted as the rule counts them; at a step
+    where pitches Y sound, x is allowed iff (x - y) mod 12 is in avoid_intervals for no y, x is not in Y (no_unison),
+    x <= min Y - m (below) and x >= max Y + m (above); a silent step allows everything, a cell is the AND over its steps."""
+    return guide_template(x, pitch_range)[0]
+
+
+def _guide_per_slot(x, B: int):
+    """A request's guide= as B entries, each None (off) or a template (rows, cells): None / False (all off), one guide in
+    any form guide_template takes (all slots), or a list of B entries each None / False or a guide."""
+    B = int(B)
+    if x is None or x is False:
+        return [None] * B
+    if isinstance(x, list):
+        if len(x) != B:
+            raise CommuHipError(f"guide: {B} entries expected (one per sequence), got {len(x)}")
+        return [None if (v is None or v is False) else guide_template(v) for v in x]
+    return [guide_template(x)] * B
+
+
 class DecodeState:
     """K/V caches + distance-indexed R tables for B sequences of up to Lmax positions.
 
@@ -1219,6 +1427,14 @@ class ForcedDecoder:
     _onset_used = 0
     _onset_index = None
 
+    # guide track (set_guide): the same six for the guide's control words and its table of GUIDE_ROWS_MAX rows (1 MB)
+    guide_ctl = None
+    _guide_host = None
+    guide_table = None
+    _guide_table_host = None
+    _guide_used = 0
+    _guide_index = None
+
     def __init__(self, model, B: int, generation_length: int, memory_length: int, temperature: float, top_k: int,
                  max_chords: int = 64, record_trace: bool = False, top_p: float = 1.0, sliding: bool = False,
                  max_prompt: int = 0, kv_dtype: str = "bf16", shared_prompt: bool = False):
@@ -1367,13 +1583,14 @@ class ForcedDecoder:
         return idx
 
     def _first_use(self, rows=False, bias=False, gram=False, harm=False, cls=False, order=False, voices=False,
-                   density=False, interval=False, onsets=False):
+                   density=False, interval=False, onsets=False, guide=False):
         """What the first use of a per-slot launch input does, for each one asked for that the decoder does not have yet:
         rows uploads the host mirror of the sampling controls (scalar mode kept the mirror only); bias / gram / harm
         allocate their zeroed device buffers (gram and harm: the table and the [B] switches); cls allocates the slots'
         class-control records (set_class_sampling fills them); order allocates the slots' note-order words, all off; voices
         the slots' voice words, all off; density the slots' density words, all off; interval the slots' interval words,
-        all off; onsets the slots' onset words, all off, and the template table of ONSET_ROWS_MAX all-ones rows.
+        all off; onsets the slots' onset words, all off, and the template table of ONSET_ROWS_MAX all-ones rows; guide the
+        slots' guide words, all off, and the guide table of GUIDE_ROWS_MAX all-ones rows.
         When anything was missing the captured graphs are dropped,
         once: they hold the launches without it."""
         new = False
@@ -1420,6 +1637,13 @@ class ForcedDecoder:
             self.onset_table = torch.full((ONSET_ROWS_MAX, 4), -1, dtype=torch.int32, device=self.dev)
             self._onset_table_host = np.full((ONSET_ROWS_MAX, 4), 0xFFFFFFFF, dtype=np.uint32)
             self._onset_used, self._onset_index = 0, {}
+        if guide and self.guide_ctl is None:
+            new = True
+            self.guide_ctl = torch.full((self.B,), GUIDE_OFF, dtype=torch.int32, device=self.dev)
+            self._guide_host = np.full(self.B, GUIDE_OFF, dtype=np.int32)
+            self.guide_table = torch.full((GUIDE_ROWS_MAX, 4), -1, dtype=torch.int32, device=self.dev)
+            self._guide_table_host = np.full((GUIDE_ROWS_MAX, 4), 0xFFFFFFFF, dtype=np.uint32)
+            self._guide_used, self._guide_index = 0, {}
         if new:
             self.graph = self.graph_long = None
 
@@ -1807,6 +2031,82 @@ class ForcedDecoder:
             for j in idx:
                 self.onset_ctl[int(j)].fill_(int(self._onset_host[j]))
 
+    def _guide_pack(self, templates, fresh: bool = False):
+        """The control words of the given guides ((rows uint32 [R (1 + C)][4], C); None: off) in the decoder's table: as
+        _onsets_pack -- distinct templates, told apart by their cells and bytes, one behind the other; fresh packs the table
+        anew from these alone; what does not fit is refused before anything changes; new rows are written in place, ordered
+        on the current stream."""
+        index = {} if fresh else dict(self._guide_index)
+        used = 0 if fresh else self._guide_used
+        todo, words = [], []
+        for t in templates:
+            if t is None:
+                words.append(GUIDE_OFF)
+                continue
+            rows, cells = t
+            bars = rows.shape[0] // (1 + cells)
+            if bars > GUIDE_CYCLE_MAX:
+                raise CommuHipError(f"guide: a template holds at most {GUIDE_CYCLE_MAX} bars, got {bars}")
+            key = (cells, rows.tobytes())
+            if key not in index:
+                if used + rows.shape[0] > GUIDE_ROWS_MAX:
+                    raise CommuHipError(f"guide: the distinct templates need more than the table's {GUIDE_ROWS_MAX} rows "
+                                        f"({used} in use, {rows.shape[0]} more asked for)")
+                index[key] = used
+                todo.append((used, rows))
+                used += rows.shape[0]
+            words.append(guide_word(index[key], bars, cells))
+        for base, rows in todo:
+            self._guide_table_host[base:base + rows.shape[0]] = rows
+            self.guide_table[base:base + rows.shape[0]].copy_(torch.from_numpy(rows.view(np.int32)))
+        self._guide_index, self._guide_used = index, used
+        return np.array(words, dtype=np.int32)
+
+    def set_guide(self, value, rows: Optional[Sequence[int]] = None):
+        """The guide track for all slots (rows=None) or the listed ones: a guide in any form guide_template takes -- the raw
+        form {"cells": C, "bars": [...]}, the derived form {"from_tokens": [ids], ...}, a pair (uint32 rows, C) -- None /
+        False (off), or a list with one such value per addressed slot.  A slot that is on DRAWS a pitch only where the cell
+        row of the position its bar is at has a bit, and a position only where the bar's live row has one; bar i of the
+        sequence (counted as set_onsets counts it, the prompt's bars included) uses block i mod R.  Only a note's START is
+        tested: a drawn note held across a later change of the guide is not checked; nor are forced tokens (the position 0
+        after a Bar, a chord's position) or a prompt; a pitch range, strict harmony or interval window that together with
+        the cell row leaves no pitch ends the attempt by Q12 as before.
+        Exactly like set_onsets: the first call that switches a slot on allocates the [B] words, the table of 65536 rows
+        (1 MB) -- ONCE, so that its address stays fixed under graph capture -- and, where the decoder lacks them, the
+        off-words of everything the one kernel reads besides (set_onsets' words and table included), and drops the
+        captured graphs once; later calls pack new templates behind the ones in the table and rewrite words and rows IN
+        PLACE, ordered on the current stream.  A call for all slots packs the table anew.  Refused with the numbers: a
+        template of more than 64 bars, distinct templates of more than 65536 rows together.  A slot that is off decodes
+        bit for bit what it decoded without the feature; a decoder that never switched a slot on allocates nothing."""
+        idx = self._slots(rows)
+        tmpl = _guide_per_slot(value, len(idx))                # (validated before anything changes)
+        if self.guide_ctl is None and all(t is None for t in tmpl):
+            return
+        if self.guide_ctl is None:
+            # (the capacity check of _guide_pack, before anything is allocated)
+            need, seen = 0, set()
+            for t in tmpl:
+                if t is not None and (t[1], t[0].tobytes()) not in seen:
+                    seen.add((t[1], t[0].tobytes()))
+                    need += t[0].shape[0]
+            if need > GUIDE_ROWS_MAX:
+                raise CommuHipError(f"guide: the distinct templates need more than the table's {GUIDE_ROWS_MAX} rows "
+                                    f"(0 in use, {need} asked for)")
+        fresh_cls = self.cls_ctl is None
+        self._first_use(rows=True, bias=True, gram=True, harm=True, cls=True, order=True, voices=True, density=True,
+                        interval=True, onsets=True, guide=True)
+        if fresh_cls:          # (no class controls: every record of every slot holds the slot's base triple)
+            self._write_class_ctl(None, np.arange(self.B))
+        new = self._guide_pack(tmpl, fresh=rows is None)
+        if np.array_equal(self._guide_host[idx], new):
+            return
+        self._guide_host[idx] = new
+        if rows is None and len(idx) > 4:
+            self.guide_ctl.copy_(torch.from_numpy(self._guide_host))
+        else:
+            for j in idx:
+                self.guide_ctl[int(j)].fill_(int(self._guide_host[j]))
+
     def pre(self):
         call("commu_forcing_pre", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_tok), _p(self.chord_pos),
              self.ld_chord, _p(self.wrong), _p(self.utable), self.ld_u, self.generation_length, _p(self.tok),
@@ -1829,7 +2129,8 @@ class ForcedDecoder:
                         **({} if self.voice_ctl is None else {"voices": self.voice_ctl}),
                         **({} if self.density_ctl is None else {"density": self.density_ctl}),
                         **({} if self.interval_ctl is None else {"interval": self.interval_ctl}),
-                        **({} if self.onset_ctl is None else {"onsets": (self.onset_ctl, self.onset_table)}))
+                        **({} if self.onset_ctl is None else {"onsets": (self.onset_ctl, self.onset_table)}),
+                        **({} if self.guide_ctl is None else {"guide": (self.guide_ctl, self.guide_table)}))
         call("commu_forcing_post", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_pos), self.ld_chord,
              _p(self.wrong), _p(self.draw), _p(self.token), None, _p(self.state.klen), _p(self.keep),
              self.state.klen_cap, _p(logp), _p(seq_logp), B, _s())
@@ -1856,7 +2157,9 @@ class ForcedDecoder:
             order_ctl=_p(self.order_ctl), voice_ctl=_p(self.voice_ctl), density_ctl=_p(self.density_ctl),
             interval_ctl=_p(self.interval_ctl),
             **({} if self.onset_ctl is None else {"onset_ctl": _p(self.onset_ctl), "onset_table": _p(self.onset_table),
-                                                  "onset_rows": ONSET_ROWS_MAX}))
+                                                  "onset_rows": ONSET_ROWS_MAX}),
+            **({} if self.guide_ctl is None else {"guide_ctl": _p(self.guide_ctl), "guide_table": _p(self.guide_table),
+                                                  "guide_rows": GUIDE_ROWS_MAX}))
         call("commu_decode_sample_post_pre", C.byref(a), _s())
 
     def iteration(self, want_probs: bool = False):
@@ -2119,8 +2422,9 @@ class ForcedDecoder:
     # density: the slot's density word for its next attempt (set_density's values, False: off; None: the slot keeps its word).
     # interval: the slot's interval word for its next attempt (set_interval's values, False: off; None: the slot keeps its word).
     # onsets: the slot's onset template for its next attempt (set_onsets' values, False: off; None: the slot keeps its word).
+    # guide: the slot's guide track for its next attempt (set_guide's values, False: off; None: the slot keeps its word).
     def rearm(self, b: int, uniforms_row: Optional[np.ndarray] = None, sampling=None, logit_bias=None, grammar=None,
-              harmony=None, note_order=None, voices=None, density=None, interval=None, onsets=None):
+              harmony=None, note_order=None, voices=None, density=None, interval=None, onsets=None, guide=None):
         if note_order is not None:
             self.set_note_order(note_order, rows=[b])
         if voices is not None:
@@ -2131,6 +2435,8 @@ class ForcedDecoder:
             self.set_interval(interval, rows=[b])
         if onsets is not None:
             self.set_onsets(onsets, rows=[b])
+        if guide is not None:
+            self.set_guide(guide, rows=[b])
         if sampling is not None:
             self.set_sampling(*sampling, rows=[b])
         if logit_bias is not None:
@@ -2333,7 +2639,8 @@ class ForcedDecoder:
                 "e_voice": torch.full((R,), VOICES_OFF, dtype=i32, device=dev),
                 "e_density": torch.full((R,), DENSITY_OFF, dtype=i32, device=dev),
                 "e_interval": torch.full((R,), INTERVAL_OFF, dtype=i32, device=dev),
-                "e_onset": torch.full((R,), ONSETS_OFF, dtype=i32, device=dev), "e_cls": z(R, N_CLASSES + 1, 4),
+                "e_onset": torch.full((R,), ONSETS_OFF, dtype=i32, device=dev),
+                "e_guide": torch.full((R,), GUIDE_OFF, dtype=i32, device=dev), "e_cls": z(R, N_CLASSES + 1, 4),
                 "hdr": hdr, "stage": z(words),
                 # two pinned staging buffers and an event each: the host never overwrites a buffer whose copy is in flight
                 "pin": [torch.zeros(words, dtype=i32).pin_memory() for _ in range(2)],
@@ -2358,7 +2665,7 @@ class ForcedDecoder:
         """The arm launch's argument block, rebuilt when an optional array was allocated since (a null twin: not written)."""
         P = self._pool
         opt = (self.bias, self.gram_on, self.harm_on, self.order_ctl, self.voice_ctl, self.density_ctl, self.interval_ctl,
-               self.onset_ctl, self.cls_ctl, self.trace)
+               self.onset_ctl, self.guide_ctl, self.cls_ctl, self.trace)
         sig = tuple(None if t is None else t.data_ptr() for t in opt)
         if P["args"] is None or P["sig"] != sig:
             st = self.state
@@ -2383,6 +2690,7 @@ class ForcedDecoder:
                 **on(self.density_ctl, {"density_ctl": self.density_ctl, "e_density": P["e_density"]}),
                 **on(self.interval_ctl, {"interval_ctl": self.interval_ctl, "e_interval": P["e_interval"]}),
                 **on(self.onset_ctl, {"onset_ctl": self.onset_ctl, "e_onset": P["e_onset"]}),
+                **on(self.guide_ctl, {"guide_ctl": self.guide_ctl, "e_guide": P["e_guide"]}),
                 **on(self.cls_ctl, {"cls_ctl": self.cls_ctl, "e_cls": P["e_cls"]}))
             P["sig"] = sig
         if P["primed"]:
@@ -2391,12 +2699,13 @@ class ForcedDecoder:
 
     def admit(self, entry: int, encoded_meta: Sequence[int], input_data, sampling=None, logit_bias=None, grammar=False,
               harmony=False, note_order=None, voices=None, class_table=None, primed=None, density=None, interval=None,
-              onsets=None):
+              onsets=None, guide=None):
         """Compose store entry `entry` for a request and upload it with its K/V image: the state record, sequence head
         and chord rows as load() builds them, klen0 = n_cond, the sampling triple (None: the decoder's), the bias row
         (None: zeros), the grammar and harmony switches (they switch on what the decoder has a table for), the
         note-order, voice, density and interval words (None: off), the onset word of the template `onsets` (None: off; the
-        template's rows go to the decoder's own table, where the same template is stored once -- no table bytes move per arm) and, where the decoder has class records, the request's record row
+        template's rows go to the decoder's own table, where the same template is stored once -- no table bytes move per arm),
+        the guide word of the guide track `guide` (likewise) and, where the decoder has class records, the request's record row
         (class_table: its NaN-table, None: the base triple in every record).  The image is written by ONE memory-less
         forward over this request's single column [n_cond, 1] and the prefill scatter of the cache's format into the
         store: it does not depend on what else is admitted or decoding.  Everything is ordered on the current stream.
@@ -2423,6 +2732,9 @@ class ForcedDecoder:
         ons = _onsets_per_slot(onsets, 1)
         if ons[0] is not None and self.onset_ctl is None:
             raise CommuHipError("admit: an onset template, but the decoder has no onset words (set_onsets)")
+        gde = _guide_per_slot(guide, 1)
+        if gde[0] is not None and self.guide_ctl is None:
+            raise CommuHipError("admit: a guide track, but the decoder has no guide words (set_guide)")
         if grammar and (self.gram is None or self._gram_host is None):
             raise CommuHipError("admit: grammar switched on, but the decoder has no grammar table (set_grammar)")
         if harmony and (self.harm is None or self._harm_host is None):
@@ -2486,6 +2798,7 @@ class ForcedDecoder:
         P["e_density"][entry].fill_(int(den[0]))
         P["e_interval"][entry].fill_(int(mel[0]))
         P["e_onset"][entry].fill_(int(ONSETS_OFF if ons[0] is None else self._onsets_pack(ons)[0]))
+        P["e_guide"][entry].fill_(int(GUIDE_OFF if gde[0] is None else self._guide_pack(gde)[0]))
         if self.cls_ctl is not None:
             tab = np.full((1, N_CLASSES + 1, 3), np.nan) if class_table is None else class_sampling_table(class_table)[None]
             rec = class_ctl_records(tab, [t, k, p])
@@ -2687,7 +3000,8 @@ class PoolRequest:
     (seq, report) -> bool, None accepts every sequence that is not None; logit_bias: one row; grammar / harmony: a
     per-request bool (None: on where the pool has a table), they may only switch on what the pool has a table for;
     note_order / voices / density / interval / onsets: as generate_stream's (onsets: ONE template in any form onset_rows
-    takes; the pool packs its requests' templates into one table).  prompt: token ids that follow the conditioning tokens and that every
+    takes; the pool packs its requests' templates into one table); guide: ONE guide track in any form guide_template takes,
+    likewise.  prompt: token ids that follow the conditioning tokens and that every
     attempt of THIS request continues (generate_stream's prompt=); None or [] is an unprimed request."""
     encoded_meta: Sequence[int]
     input_data: object
@@ -2707,6 +3021,7 @@ class PoolRequest:
     density: Optional[object] = None
     interval: Optional[object] = None
     onsets: Optional[object] = None
+    guide: Optional[object] = None
 
 
 PoolResult = collections.namedtuple("PoolResult", ["sequences", "attempts_started", "logprobs"])
@@ -2830,7 +3145,7 @@ class BatchedGenerator:
 
     def decoder(self, B, temperature, top_k, max_chords, top_p=1.0, per_slot: bool = False, max_prompt: int = 0,
                 logit_bias=None, shared: bool = False, grammar=None, harmony=None, class_sampling=None,
-                note_order=None, voices=None, density=None, interval=None, onsets=None):
+                note_order=None, voices=None, density=None, interval=None, onsets=None, guide=None):
         """The decoder for B slots, its slots set to the given controls (numbers or one value per slot).  per_slot: the
         caller will read log-probabilities or give slots their own controls later (rearm): the array launches from the
         start.  Otherwise one triple for all slots runs the scalar launches, until a second setting arrives for launches
@@ -2843,7 +3158,8 @@ class BatchedGenerator:
         request's voice words (voices_ctl), likewise; a slot that gets one has its note order switched on.  density:
         the request's density words (density_ctl), likewise; a slot that gets one has its voice word and note order switched
         on.  interval: the request's interval words (interval_ctl), likewise; it switches nothing else on.  onsets: the request's onset templates (one for all
-        sequences or one per sequence, ForcedDecoder.set_onsets), likewise.  shared: the
+        sequences or one per sequence, ForcedDecoder.set_onsets), likewise.  guide: the request's guide tracks (one for
+        all sequences or one per sequence, ForcedDecoder.set_guide), likewise.  shared: the
         decoder that holds the
         request's common prompt once (its own cache layout: kept beside the unshared decoder of the same size)."""
         rows = sampling_rows(B, temperature, top_k, top_p)          # (validated before anything is built)
@@ -2857,6 +3173,7 @@ class BatchedGenerator:
         den = density_ctl(density, B)
         mel = interval_ctl(interval, B)
         ons = _onsets_per_slot(onsets, B)
+        gde = _guide_per_slot(guide, B)
         key = (B, self.trace is not None, self.sliding) + (("shared",) if shared else ())
         dec = self._decoders.get(key)
         if dec is None or dec.ld_chord < max_chords or dec.max_prompt < max_prompt:
@@ -2889,6 +3206,8 @@ class BatchedGenerator:
         dec.set_interval(mel)
         # (onset templates: likewise; a request without them switches off what the one before left)
         dec.set_onsets(ons)
+        # (guide track: likewise)
+        dec.set_guide(gde)
         return dec
 
     @staticmethod
@@ -2902,8 +3221,11 @@ class BatchedGenerator:
     def generate(self, encoded_metas: Sequence[Sequence[int]], input_datas, temperature, top_k, top_p=1.0,
                  return_logprobs: bool = False, prompts: Optional[Sequence[Sequence[int]]] = None, logit_bias=None,
                  grammar=None, harmony=None, class_sampling=None, note_order=None, voices=None, density=None,
-                 interval=None, onsets=None):
-        """temperature / top_k / top_p: a number for the batch or one value per sequence.  onsets: None / False, one
+                 interval=None, onsets=None, guide=None):
+        """temperature / top_k / top_p: a number for the batch or one value per sequence.  guide: None / False, one guide
+        track in any form guide_template takes, or a list with one entry (None / False / a guide) per sequence -- such a
+        sequence DRAWS a pitch only where the cell row of the position its bar is at has a bit, and a position only where
+        the live row has one; implies none of the other constraints (ForcedDecoder.set_guide).  onsets: None / False, one
         template in any form onset_rows takes, or a list with one entry (None / False / a template) per sequence -- such a
         sequence DRAWS a position only where the row of its open bar has a bit; implies none of the other constraints
         (ForcedDecoder.set_onsets).  interval: None / False, a word
@@ -2937,7 +3259,7 @@ class BatchedGenerator:
         dec = self.decoder(B, temperature, top_k, max_chords, top_p, per_slot=return_logprobs, max_prompt=max_prompt,
                            logit_bias=logit_bias, shared=self.shared_prompt and max_prompt > 0, grammar=grammar,
                            harmony=self._one_harmony(harmony), class_sampling=class_sampling, note_order=note_order,
-                           voices=voices, density=density, interval=interval, onsets=onsets)
+                           voices=voices, density=density, interval=interval, onsets=onsets, guide=guide)
         uniforms = None
         if bool((dec._sampling[0] != 0).any()) or dec.class_samples():
             srcs = self.uniform_sources or [np.random.RandomState(1000 + b).random_sample for b in range(B)]
@@ -2962,7 +3284,7 @@ class BatchedGenerator:
                         accept, top_p=1.0, slots: int = 64, seed: int = 0, max_attempts: Optional[int] = None,
                         return_logprobs: bool = False, prompt: Optional[Sequence[int]] = None, logit_bias=None,
                         share_prompt: bool = False, grammar=None, harmony=None, class_sampling=None, note_order=None,
-                        voices=None, density=None, interval=None, onsets=None):
+                        voices=None, density=None, interval=None, onsets=None, guide=None):
         """Attempts of ONE request (the reference's `while idx != num_generate` loop, midi_inferrer.py:338-354, which tries
         one sequence after the other) decoded in up to `slots` parallel slots, CONTINUOUSLY: a slot whose sequence has
         ended is handed to `accept(sequence, report) -> bool` and re-armed with the next attempt while the other slots keep
@@ -2990,6 +3312,8 @@ class BatchedGenerator:
         (ForcedDecoder.set_interval; likewise read off seq).
         onsets: None / False or ONE template in any form onset_rows takes: one setting for every attempt of the request
         (ForcedDecoder.set_onsets; the bar count is the forcing record's, the prompt's bars included).
+        guide: None / False or ONE guide track in any form guide_template takes: one setting for every attempt of the request
+        (ForcedDecoder.set_guide; likewise).
         share_prompt (opt-in; also on with BatchedGenerator(shared_prompt=True) when a prompt is given): the K/V of the
         context and the prompt are computed and held once for all slots (ForcedDecoder(shared_prompt=True)); the attempts
         returned are the ones the unshared decoder defines, up to the summation order of the attention."""
@@ -3012,6 +3336,9 @@ class BatchedGenerator:
         if interval is not None and np.ndim(interval) != 0:
             raise CommuHipError(f"interval: one setting for the request expected, got shape {np.shape(interval)}")
         one_onsets = None if (onsets is None or onsets is False) else onset_rows(onsets)      # (ONE template, validated)
+        if isinstance(guide, list):
+            raise CommuHipError(f"guide: one setting for the request expected, got a list of {len(guide)}")
+        one_guide = None if (guide is None or guide is False) else guide_template(guide)      # (likewise)
         max_chords = len(input_data.chord_token_components["chord_token"])
         # each control's schedule, validated on its own (the three may have different lengths)
         n_of = lambda x: 1 if np.ndim(x) == 0 else len(x)
@@ -3026,7 +3353,7 @@ class BatchedGenerator:
                            per_slot=return_logprobs or varying, max_prompt=0 if prompt is None else len(prompt),
                            logit_bias=logit_bias, shared=share, grammar=grammar, harmony=harmony,
                            class_sampling=class_sampling, note_order=note_order, voices=voices, density=density,
-                           interval=interval, onsets=one_onsets)
+                           interval=interval, onsets=one_onsets, guide=one_guide)
         started = B
         sampled = bool((sched[0] != 0).any()) or dec.class_samples()          # (a greedy attempt reads no variate)
         uni = np.stack([self.attempt_uniforms(seed, a, dec.ld_u) for a in range(B)]) if sampled else None
@@ -3185,7 +3512,7 @@ class BatchedGenerator:
         harm_table = _harmony_request(self._one_harmony(harmony))
         cls_table = _class_request(class_sampling)
         # each request's controls, validated before anything is built
-        triples, biases, orders, voxes, dens, mels, onss = [], [], [], [], [], [], []
+        triples, biases, orders, voxes, dens, mels, onss, gdes = [], [], [], [], [], [], [], []
         for i, r in enumerate(requests):
             t, k, p = sampling_rows(1, r.temperature, r.top_k, r.top_p)
             triples.append((t[0].item(), int(k[0]), p[0].item()))
@@ -3195,6 +3522,10 @@ class BatchedGenerator:
             dens.append(int(density_ctl(r.density, 1)[0]))
             mels.append(int(interval_ctl(r.interval, 1)[0]))
             onss.append(None if (r.onsets is None or r.onsets is False) else onset_rows(r.onsets))
+            try:
+                gdes.append(None if (r.guide is None or r.guide is False) else guide_template(r.guide))
+            except CommuHipError as e:
+                raise CommuHipError(f"request {i}: {e}") from None
         B = max(1, min(slots, sum(int(r.need) for r in requests)))
         max_chords = max(len(r.input_data.chord_token_components["chord_token"]) for r in requests)
         key = ("pool", B, self.trace is not None, self.sliding)          # (never shared with generate / generate_stream:
@@ -3221,6 +3552,8 @@ class BatchedGenerator:
         use_den = any(d != DENSITY_OFF for d in dens)          # (the density rides on the voice words and the note order)
         use_mel = any(m != INTERVAL_OFF for m in mels)         # (the interval kernel reads all three words, on or off)
         use_ons = any(t is not None for t in onss)             # (the onsets kernel reads all four words, on or off)
+        use_gde = any(t is not None for t in gdes)             # (the guide kernel reads all five, on or off)
+        use_ons = use_ons or use_gde
         use_mel = use_mel or use_ons
         use_order = any(o != NOTE_ORDER_OFF for o in orders) or any(v != VOICES_OFF for v in voxes) or use_den or use_mel
         if cls_table is not None or use_order:
@@ -3235,6 +3568,9 @@ class BatchedGenerator:
             # (the requests' templates go into the one table before the pool is opened; admit finds them by their bytes)
             dec._first_use(onsets=True)
             dec._onsets_pack(onss, fresh=True)
+        if use_gde:
+            dec._first_use(guide=True)
+            dec._guide_pack(gdes, fresh=True)
         if any(b is not None for b in biases):
             dec._first_use(bias=True)
         klen0_max = max([n_cond] + [p["klen0"] for p in replays if p is not None])
@@ -3259,7 +3595,7 @@ class BatchedGenerator:
                               harmony=(harm_table is not None) if r.harmony is None else bool(r.harmony),
                               note_order=orders[j.request], voices=voxes[j.request], class_table=cls_table,
                               primed=replays[j.request], density=dens[j.request], interval=mels[j.request],
-                              onsets=onss[j.request])
+                              onsets=onss[j.request], guide=gdes[j.request])
                 sampled = triples[j.request][0] != 0 or cls_samples          # (a greedy attempt reads no variate)
                 staged.append((j.slot, j.entry, self.attempt_uniforms(r.seed, j.attempt, dec.ld_u) if sampled else None))
                 if held[j.slot] is not None and held[j.slot] != j.request:

@@ -299,7 +299,7 @@ class InferenceTask:
     def execute(self, encoded_meta, max_rounds: Optional[int] = None, return_logprobs: bool = False,
                 prompt: Optional[List[int]] = None, logit_bias=None, grammar=None, harmony=None,
                 class_sampling=None, note_order=None, voices=None, density=None, interval=None,
-                onsets=None):                                                                              # :338-354
+                onsets=None, guide=None):                                                                  # :338-354
         """return_logprobs (not in the reference): (sequences, their log-probability arrays -- ForcedDecoder.logprobs).
         prompt (not in the reference): token ids that follow the meta tokens; every attempt continues them (primed
         generation, BatchedGenerator.generate_stream) and every returned sequence starts with [0] + meta + prompt.
@@ -320,7 +320,9 @@ class InferenceTask:
         semitones above and down below the pitch of the note before it; switches nothing else on
         (ForcedDecoder.set_interval).
         onsets (not in the reference): a template in any form generate.onset_rows takes -- a drawn position lies where the
-        row of its bar has a bit, bar i using row i mod R; switches nothing else on (ForcedDecoder.set_onsets)."""
+        row of its bar has a bit, bar i using row i mod R; switches nothing else on (ForcedDecoder.set_onsets).
+        guide (not in the reference): a guide track in any form generate.guide_template takes -- a drawn pitch lies where the
+        guide's cell for the position its bar is at has a bit; switches nothing else on (ForcedDecoder.set_guide)."""
         from ..generate import BatchedGenerator
         data = self.input_data
         glen = self.inference_cfg.GENERATION.generation_length
@@ -355,6 +357,9 @@ class InferenceTask:
         # (likewise: generate.py --onsets, the JSON text of the template's bars)
         if onsets is None and getattr(self.inference_cfg.GENERATION, "onsets", None):
             onsets = json.loads(self.inference_cfg.GENERATION.onsets)
+        # (likewise: generate.py --guide, the JSON text of the guide's raw form)
+        if guide is None and getattr(self.inference_cfg.GENERATION, "guide", None):
+            guide = json.loads(self.inference_cfg.GENERATION.guide)
         gen = BatchedGenerator(self.model, self.device, glen, mlen, sliding=sliding, kv_dtype=kv_dtype,
                                **({"shared_prompt": True} if share else {}))
 
@@ -381,14 +386,15 @@ class InferenceTask:
                                   **({} if voices is None else {"voices": voices}),
                                   **({} if density is None else {"density": density}),
                                   **({} if interval is None else {"interval": interval}),
-                                  **({} if onsets is None else {"onsets": onsets}))
+                                  **({} if onsets is None else {"onsets": onsets}),
+                                  **({} if guide is None else {"guide": guide}))
         return (res[0], res[2]) if return_logprobs else res[0]
 
     def execute_pool(self, items, return_logprobs: bool = False, harmony=None):
         """generate.py --requests (not in the reference): MANY requests in one pool of decode slots
         (BatchedGenerator.generate_pool).  items: one dict per request -- encoded_meta, input_data (its num_generate,
         temperature, top_k, top_p), seed, max_rounds, logit_bias, prompt (token ids the request's sequences continue, None
-        or [] for none), onsets (the request's own onset template, None: the pool-wide one of --onsets, if any).  Every request is accepted by the two validators of
+        or [] for none), onsets (the request's own onset template, None: the pool-wide one of --onsets, if any), guide (likewise: --guide).  Every request is accepted by the two validators of
         execute() and bounded by max_rounds x num_generate attempts, as there; the pool-wide options (grammar, harmony,
         class_sampling, note_order, voices, density, interval, decode_slots, kv_cache, sliding_memory) come from the inference configuration
         as in execute().  Returns generate_pool's PoolResult list."""
@@ -407,6 +413,7 @@ class InferenceTask:
         density = None if getattr(G, "density", None) is None else int(G.density)
         interval = None if getattr(G, "interval", None) is None else int(G.interval)
         onsets = json.loads(G.onsets) if getattr(G, "onsets", None) else None
+        guide = json.loads(G.guide) if getattr(G, "guide", None) else None
 
         def accept(seq, rep) -> bool:
             self.attempts += 1
@@ -426,6 +433,7 @@ class InferenceTask:
                                     max_attempts=None if mr is None else int(mr) * int(d.num_generate), accept=accept,
                                     logit_bias=it.get("logit_bias"), note_order=note_order, voices=voices,
                                     prompt=None if not it.get("prompt") else list(it["prompt"]), density=density,
-                                    interval=interval, onsets=onsets if it.get("onsets") is None else it["onsets"]))
+                                    interval=interval, onsets=onsets if it.get("onsets") is None else it["onsets"],
+                                    guide=guide if it.get("guide") is None else it["guide"]))
         return gen.generate_pool(reqs, slots=int(getattr(G, "decode_slots", 64)), grammar=grammar, harmony=harmony,
                                  class_sampling=class_sampling, return_logprobs=return_logprobs)

@@ -93,6 +93,10 @@ class ModelInitializeTask:
         # (generate.py check_onsets)
         if getattr(self.model_args, "onsets_bars", None) is not None:
             cfg.GENERATION.onsets = str(self.model_args.onsets_bars)
+        # generate.py --guide (not in the reference): the guide track as the JSON text of its raw form (generate.py
+        # check_guide)
+        if getattr(self.model_args, "guide_doc", None) is not None:
+            cfg.GENERATION.guide = str(self.model_args.guide_doc)
         # generate.py --decode_slots (not in the reference): attempts decoded side by side (64 unless the key is set)
         if getattr(self.model_args, "decode_slots", None) not in (None, 64):
             cfg.GENERATION.decode_slots = int(self.model_args.decode_slots)

@@ -934,7 +934,7 @@ def _check_draw_state(kind, device, specs):
 
 def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=None, token=None, probs_out=None,
                 top_p=1.0, logp_out=None, bias=None, V=729, grammar=None, harmony=None, class_ctl=None,
-                note_order=None, voices=None, density=None, interval=None, onsets=None):
+                note_order=None, voices=None, density=None, interval=None, onsets=None, guide=None):
     """In-place temperature + softmax + top-k + wrong-token mask + inverse-CDF draw per sequence.
     logits: fp32 [nseq, >=V] (row stride = ld), modified in place (logits[:, 1:V] /= temperature).
     top_p < 1: nucleus filter after the top-k / rejected-token step (an extra mode; the reference has top-k only).
@@ -992,7 +992,16 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
     row of the open bar is base + (max(nb - 1, 0) mod R) with nb = state[b][8], the record's count of BAR tokens in seq; every
     position id whose bit is clear is banned, in the same select as the four rules above, and the density's lower bound lets
     a bar end once the position range together with the row leaves no position.  One kernel serves it, the interval kernel's
-    with the row: interval= is required (commu_sample_args.onset_ctl / onset_table / onset_rows)."""
+    with the row: interval= is required (commu_sample_args.onset_ctl / onset_table / onset_rows).
+    guide: (words, table) on the device of the logits -- words int32 [nseq], one control word per sequence: -1 off, else
+    base + 65536 R + 2^23 s (generate.guide_word); table int32 [rows, 4] contiguous, 1 <= rows <= 65536, the bit patterns of
+    the uint32 guide rows (generate.guide_rows): per bar a block of 1 + C rows, C = 128 >> s -- the live row over positions
+    and C cell rows over pitches (bit k: id 3 + k).  The block of the open bar is base + (max(nb - 1, 0) mod R) (1 + C); with p
+    the last BAR-or-POSITION token of seq, a POSITION, the cell row is block + 1 + ((p - 432) >> s) and every pitch id whose
+    bit is clear is banned; every position id whose bit in the live row is clear is banned, and the density waiver sees the
+    onset row ANDed with the live row.  Row indices are clamped into the table.  One kernel serves it, the onsets kernel's
+    with the two rows: onsets= is required -- pass all -1 onset words over a one-row all-ones table where there is no
+    template (commu_sample_args.guide_ctl / guide_table / guide_rows)."""
     nseq = logits.shape[0]
     V = int(V)
     assert logits.dtype == F32 and logits.stride(1) == 1
@@ -1082,6 +1091,18 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
             (otable, "table", torch.int32, "[1 .. 4096, 4]",
              lambda t: t.dim() == 2 and 1 <= t.shape[0] <= 4096 and t.shape[1] == 4)))
         a.onset_ctl, a.onset_table, a.onset_rows = _p(owords), _p(otable), int(otable.shape[0])
+    if guide is not None:
+        if onsets is None:
+            raise CommuHipError("guide: onsets= expected as well (the one kernel is the onsets kernel's with the guide's two "
+                                "rows; pass words that are all -1 over a one-row all-ones table where there is no template)")
+        if not isinstance(guide, (tuple, list)) or len(guide) != 2:
+            raise CommuHipError("guide: a pair (control words int32 [nseq], table int32 [rows, 4]) expected")
+        gwords, gtable = guide
+        _check_draw_state("guide", logits.device, (
+            (gwords, "controls", torch.int32, "[%d]" % nseq, lambda t: tuple(t.shape) == (nseq,)),
+            (gtable, "table", torch.int32, "[1 .. 65536, 4]",
+             lambda t: t.dim() == 2 and 1 <= t.shape[0] <= 65536 and t.shape[1] == 4)))
+        a.guide_ctl, a.guide_table, a.guide_rows = _p(gwords), _p(gtable), int(gtable.shape[0])
     if harmony is not None:
         htable, hon, hstate, chord_tok = harmony
         _check_draw_state("harmony", logits.device, (

@@ -119,6 +119,7 @@ __global__ __launch_bounds__(ARM_THREADS) void decode_arm_primed_kernel(const co
         if (a.density_ctl != nullptr && a.e_density != nullptr) a.density_ctl[slot] = a.e_density[entry];
         if (a.interval_ctl != nullptr && a.e_interval != nullptr) a.interval_ctl[slot] = a.e_interval[entry];
         if (a.onset_ctl != nullptr && a.e_onset != nullptr) a.onset_ctl[slot] = a.e_onset[entry];
+        if (a.guide_ctl != nullptr && a.e_guide != nullptr) a.guide_ctl[slot] = a.e_guide[entry];
     }
 }
 

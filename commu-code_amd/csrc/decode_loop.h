@@ -258,8 +258,44 @@ struct Onsets {
     int nbar;               // the record's F_NBAR
 };
 constexpr int ONS_ROWS_MAX = 4096, ONS_CYCLE_MAX = 64;
+// GDE (Guide: one int32 control per sequence, -1 off, else base + 65536 R + 2^23 s with R in 1 .. 64 the cycle length in
+//   bars, s in 0 .. 7 and C = 128 >> s the cells of a bar, base in 0 .. 65535, base + R (1 + C) <= rows; table uint32
+//   [rows][4], 1 <= rows <= 65536): WHICH PITCH a note may take, by the time it starts -- a mask over pitches indexed by time,
+//   derived on the host from a finished track or given raw.  A bar of the template is a BLOCK of 1 + C consecutive rows: row 0
+//   the bar's LIVE ROW, a 128-bit mask over POSITIONS in the onset table's format (bit g: a note may start at step g); rows
+//   1 .. C the CELL ROWS, 128-bit masks over PITCHES (bit k % 32 of word k / 32 set: PITCH id 3 + k may be drawn).
+//   THE BLOCK OF THE OPEN BAR mirrors ONS: i = max(nb - 1, 0) with nb the record's F_NBAR (never counted on a draw, a
+//   prompt's bars included), block = base + (i mod R) (1 + C).
+//   PITCH BAN: j and p are ORD's (j the largest index with S[j] BAR or a POSITION).  No such j, or S[j] BAR: no pitch is
+//   banned.  Else g = p - 432, the cell row is block + 1 + (g >> s), and every PITCH id 3 .. 130 whose bit is clear is banned;
+//   ids outside 3 .. 130 are never touched (lane 10 owns ids 120 .. 131, and id 131 is a velocity).
+//   POSITION BAN: every POSITION id whose bit in the live row is clear is banned -- the live row is ANDed into the four onset
+//   words before they are used, so the ONS position ban AND ITS DENSITY WAIVER apply to the intersection with no new code:
+//   the waiver lets a bar end once range, onset row and live row together leave no position.
+//   The bans join the one select of ORD, VOX, DEN, MEL and ONS, so a draw is bit for bit the ONS kernel's with bias[b] = -inf
+//   at these ids (and DEN's BAR / EOS ban taken under the waiver on the ANDed row); an off word, or a word over an all-ones
+//   live row with all-ones cell rows, is bit for bit the ONS kernel.  Every row index is clamped to rows - 1, whatever the
+//   arrays hold.
+//   THE LOADS: the live row is one scalar 16-byte load whose address needs the record and the control word only; it goes out
+//   beside the onset row's, ahead of the chain.  The cell row is one scalar 16-byte load whose address needs p: it is issued
+//   as soon as the first ballot of the scan has produced j -- behind chunk 0 for a normal bar, behind the chunk loop
+//   otherwise (the trip count is wave-uniform already, so is this branch).  Off words select all ones, no branch on the
+//   switch.  A lane builds its 12 pitch bits with the 64-bit shift ONS uses; the start bit is base - 3, negative for lane 0,
+//   which shifts from bit 0 and moves the result up by 3 instead (ids 0 .. 2 are outside the pitch range and masked out).
+//   No LDS, no load but the word and the two rows.  (As compiled the three row loads are s_load_dwordx4 in the stand-alone
+//   kernel; in the fused loop kernel, which stores to global memory ahead of them, they come out as uniform-address vector
+//   loads, as the onset row's does there: docs/EXPERIMENTS.md 9c.)
+//   NOT COVERED: only a note's START is tested (a drawn note held across a later change of the guide is not checked); forced
+//   tokens (the position 0 after a BAR, a chord's position); notes inside a prompt; a pitch range, strict harmony or interval
+//   window that together with the cell row leaves no pitch ends the attempt by Q12, as before.  GDE needs ONS.
+struct Guide {
+    int ctl;                // the sequence's control as the caller loaded it
+    const unsigned* table;  // uint32 [rows][4]
+    int rows;               // 1 .. 65536 (the entry points refuse anything else)
+};
+constexpr int GDE_ROWS_MAX = 65536, GDE_CYCLE_MAX = 64;
 template <bool BIAS, bool GRAM = false, bool HARM = false, bool CLS = false, bool ORD = false, bool VOX = false,
-          bool DEN = false, bool MEL = false, bool ONS = false>
+          bool DEN = false, bool MEL = false, bool ONS = false, bool GDE = false>
 __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restrict__ logits, int ld, int V,
                                                  const unsigned char* __restrict__ wrong, int ldw,
                                                  const float* __restrict__ uni,
@@ -273,13 +309,15 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
                                                  ClassControls cc = ClassControls{nullptr},
                                                  NoteOrder no = NoteOrder{-1}, Voices vx = Voices{-1},
                                                  Density dn = Density{-1}, Interval ml = Interval{-1},
-                                                 Onsets os = Onsets{-1, nullptr, 1, 0}) {
+                                                 Onsets os = Onsets{-1, nullptr, 1, 0},
+                                                 Guide gd = Guide{-1, nullptr, 1}) {
     static_assert(!CLS || GRAM, "the class key is the grammar's previous token");
     static_assert(!ORD || CLS, "one note-order instantiation: the class kernel's with the scan");
     static_assert(!VOX || ORD, "one voices instantiation: the note-order kernel's with the longer scan");
     static_assert(!DEN || VOX, "one density instantiation: the voices kernel's with the count of the open bar's notes");
     static_assert(!MEL || DEN, "one interval instantiation: the density kernel's with the reference note");
     static_assert(!ONS || MEL, "one onsets instantiation: the interval kernel's with the template row");
+    static_assert(!GDE || ONS, "one guide instantiation: the onsets kernel's with the live row and the cell row");
     float* lg = logits + (size_t)b * ld;
     // The optional per-sequence inputs -- the active flag and this sequence's controls -- are loaded unconditionally: a null
     // array reads a valid word of this sequence instead (token[b], logits[b][0]), which is then ignored.  So they are in
@@ -341,6 +379,24 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
         or2 = octl >= 0 ? w2 : ~0u;
         or3 = octl >= 0 ? w3 : ~0u;
     }
+    // (GDE) the open bar's block and its live row: like the onset row's, the address needs the record and the control word
+    // only, so this scalar load goes out beside it; the live row is ANDed into the onset words here, ahead of every use (the
+    // position ban and the density waiver below see the intersection).  An off word reads row 0 and selects all ones.
+    int gctl = -1, gshift = 0, gblock = 0;
+    if constexpr (GDE) {
+        gctl = __builtin_amdgcn_readfirstlane(gd.ctl);
+        const int gbar = max(__builtin_amdgcn_readfirstlane(os.nbar) - 1, 0);
+        const int gcyc = min(max((gctl >> 16) & 127, 1), GDE_CYCLE_MAX);
+        gshift = (gctl >> 23) & 7;
+        gblock = (gctl & (GDE_ROWS_MAX - 1)) + (gbar % gcyc) * (1 + (POS_RES >> gshift));
+        const int grow = min(max(gblock, 0), gd.rows - 1);
+        const unsigned* gw = gd.table + 4 * (size_t)__builtin_amdgcn_readfirstlane(gctl >= 0 ? grow : 0);
+        const unsigned w0 = gw[0], w1 = gw[1], w2 = gw[2], w3 = gw[3];
+        or0 &= gctl >= 0 ? w0 : ~0u;
+        or1 &= gctl >= 0 ? w1 : ~0u;
+        or2 &= gctl >= 0 ? w2 : ~0u;
+        or3 &= gctl >= 0 ? w3 : ~0u;
+    }
     // (HARM) the 12 pitch-class values of the chord's row, the same for every lane: element e of a lane is id 12 l + e,
     // MIDI pitch 12 l + e - 3, pitch class (e + 9) mod 12
     float hv[PER_LANE];
@@ -392,6 +448,7 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
         int dcount = 0;                         // (DEN) the notes with beta == 0 in the chunks so far
         int mq = 0;                             // (MEL) the reference note's PITCH token, once found
         bool mfound = false;
+        unsigned gc0 = ~0u, gc1 = ~0u, gc2 = ~0u, gc3 = ~0u;          // (GDE) the cell row's four words, once loaded
         if constexpr (VOX) {
             static_assert(VOX_BINS == 2 * 64, "two bins per lane");
             __shared__ __attribute__((aligned(16))) int vflag_lds[ORD_FLAGS];
@@ -464,11 +521,34 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
         if constexpr (VOX) {
             __builtin_amdgcn_s_waitcnt(0xc07f);  // (the zeroes before the first atomic: one wave, LDS completes in order)
             chunk(otok, vt1, vt2, vt3);
+            // (GDE) the cell row of the position the bar is at: its address needs p, which the first ballot of the scan
+            // gives -- in chunk 0 for a normal bar, so the scalar load goes out here and travels under the rest of the
+            // walk; a row whose last breaker lies further back loads behind the loop (a wave-uniform branch like the
+            // loop's own).  No breaker, BAR, or an off word: row 0 is read and all ones selected.
+            const auto gcell = [&]() {
+                const bool gon = gctl >= 0 && phase != 0 && pos != TOK_BAR;
+                const int gstep = min(max(pos - TOK_POS0, 0), POS_RES - 1);
+                const int grow = min(max(gblock + 1 + (gstep >> gshift), 0), gd.rows - 1);
+                const unsigned* gw = gd.table + 4 * (size_t)__builtin_amdgcn_readfirstlane(gon ? grow : 0);
+                const unsigned w0 = gw[0], w1 = gw[1], w2 = gw[2], w3 = gw[3];
+                gc0 = gon ? w0 : ~0u;
+                gc1 = gon ? w1 : ~0u;
+                gc2 = gon ? w2 : ~0u;
+                gc3 = gon ? w3 : ~0u;
+            };
+            bool gearly = false;
+            if constexpr (GDE) {
+                gearly = phase != 0;
+                if (gearly) gcell();
+            }
             // (the run is complete at the first BAR from the end at the latest: the second BAR, or index 0, ends both)
 #pragma unroll 1
             while ((phase != 2 || nbar < 2) && start >= 0)
                 chunk(g.seq_row[max(start - lane, 0)], g.seq_row[max(start - lane - 1, 0)],
                       g.seq_row[max(start - lane - 2, 0)], g.seq_row[max(start - lane - 3, 0)]);
+            if constexpr (GDE) {
+                if (!gearly) gcell();
+            }
         } else {
             chunk(otok);
 #pragma unroll 1
@@ -556,6 +636,18 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
             const unsigned whi = w == 0 ? or1 : (w == 1 ? or2 : (w == 2 ? or3 : 0u));
             const unsigned may = (unsigned)(((((unsigned long long)whi) << 32) | wlo) >> (g0 & 31));
             const int p0 = min(max(TOK_POS0 - base, 0), PER_LANE), p1 = min(max(TOK_POS0 + POS_RES - base, 0), PER_LANE);
+            omask |= ~may & (((1u << p1) - 1u) & ~((1u << p0) - 1u));
+        }
+        if constexpr (GDE) {
+            // the lane's 12 bits of the cell row start at pitch bit k0 = base - 3 (lanes 0 .. 10: -3, 9, .. 117) and span at
+            // most two words; lane 0 shifts from bit 0 and moves the result up by 3 -- ids 0 .. 2 are outside the range
+            // below -- and lane 10's bit 11 (id 131, a velocity) is outside it too; lanes past 10 have an empty range
+            const int k0 = base - TOK_PITCH_LO, kk = max(k0, 0);
+            const int w = (kk >> 5) & 3;
+            const unsigned wlo = w == 0 ? gc0 : (w == 1 ? gc1 : (w == 2 ? gc2 : gc3));
+            const unsigned whi = w == 0 ? gc1 : (w == 1 ? gc2 : (w == 2 ? gc3 : 0u));
+            const unsigned may = (unsigned)(((((unsigned long long)whi) << 32) | wlo) >> (kk & 31)) << (kk - k0);
+            const int p0 = min(max(TOK_PITCH_LO - base, 0), PER_LANE), p1 = min(max(TOK_PITCH_HI + 1 - base, 0), PER_LANE);
             omask |= ~may & (((1u << p1) - 1u) & ~((1u << p0) - 1u));
         }
     }

@@ -102,29 +102,38 @@ struct LoopStageArgsOns : LoopStageArgsMel {
     const unsigned* onset_table;
     int onset_rows;
 };
+// (GDE) the guide control words [B], the guide table [guide_rows][4] and its row count (decode_loop.h: Guide): arguments of
+// the guide kernel only
+struct LoopStageArgsGde : LoopStageArgsOns {
+    const int* guide_ctl;
+    const unsigned* guide_table;
+    int guide_rows;
+};
 template <bool GRAM, bool HARM = false, bool CLS = false, bool ORD = false, bool VOX = false, bool DEN = false,
-          bool MEL = false, bool ONS = false>
+          bool MEL = false, bool ONS = false, bool GDE = false>
 struct LoopArgsOf { using type = LoopStageArgs; };
 template <>
-struct LoopArgsOf<true, false, false, false, false, false, false, false> { using type = LoopStageArgsGram; };
+struct LoopArgsOf<true, false, false, false, false, false, false, false, false> { using type = LoopStageArgsGram; };
 template <>
-struct LoopArgsOf<true, true, false, false, false, false, false, false> { using type = LoopStageArgsHarm; };
+struct LoopArgsOf<true, true, false, false, false, false, false, false, false> { using type = LoopStageArgsHarm; };
 template <>
-struct LoopArgsOf<true, true, true, false, false, false, false, false> { using type = LoopStageArgsCls; };
+struct LoopArgsOf<true, true, true, false, false, false, false, false, false> { using type = LoopStageArgsCls; };
 template <>
-struct LoopArgsOf<true, true, true, true, false, false, false, false> { using type = LoopStageArgsOrd; };
+struct LoopArgsOf<true, true, true, true, false, false, false, false, false> { using type = LoopStageArgsOrd; };
 template <>
-struct LoopArgsOf<true, true, true, true, true, false, false, false> { using type = LoopStageArgsVox; };
+struct LoopArgsOf<true, true, true, true, true, false, false, false, false> { using type = LoopStageArgsVox; };
 template <>
-struct LoopArgsOf<true, true, true, true, true, true, false, false> { using type = LoopStageArgsDen; };
+struct LoopArgsOf<true, true, true, true, true, true, false, false, false> { using type = LoopStageArgsDen; };
 template <>
-struct LoopArgsOf<true, true, true, true, true, true, true, false> { using type = LoopStageArgsMel; };
+struct LoopArgsOf<true, true, true, true, true, true, true, false, false> { using type = LoopStageArgsMel; };
 template <>
-struct LoopArgsOf<true, true, true, true, true, true, true, true> { using type = LoopStageArgsOns; };
+struct LoopArgsOf<true, true, true, true, true, true, true, true, false> { using type = LoopStageArgsOns; };
+template <>
+struct LoopArgsOf<true, true, true, true, true, true, true, true, true> { using type = LoopStageArgsGde; };
 template <bool BIAS, bool GRAM, bool HARM = false, bool CLS = false, bool ORD = false, bool VOX = false, bool DEN = false,
-          bool MEL = false, bool ONS = false>
+          bool MEL = false, bool ONS = false, bool GDE = false>
 __global__ __launch_bounds__(64) void sample_post_pre_kernel(
-    typename LoopArgsOf<GRAM, HARM, CLS, ORD, VOX, DEN, MEL, ONS>::type a) {
+    typename LoopArgsOf<GRAM, HARM, CLS, ORD, VOX, DEN, MEL, ONS, GDE>::type a) {
     const int b = blockIdx.x, lane = threadIdx.x;
     if (a.trace != nullptr && lane == 0) a.trace[b * 4 + 0] = wall_clock64();
     int rec[F_COUNT];                                  // the record travels through the three stages in lane 0's registers;
@@ -163,10 +172,12 @@ __global__ __launch_bounds__(64) void sample_post_pre_kernel(
     Onsets os{-1, nullptr, 1, 0};
     if constexpr (ONS) os = Onsets{a.onset_ctl[b], a.onset_table, a.onset_rows, rec[F_NBAR]};      // (likewise; the bar count
                                                                                                    // is the record's)
-    const int drawn = sample_topk_body<BIAS, GRAM, HARM, CLS, ORD, VOX, DEN, MEL, ONS>(
+    Guide gd{-1, nullptr, 1};
+    if constexpr (GDE) gd = Guide{a.guide_ctl[b], a.guide_table, a.guide_rows};                    // (likewise)
+    const int drawn = sample_topk_body<BIAS, GRAM, HARM, CLS, ORD, VOX, DEN, MEL, ONS, GDE>(
         b, lane, a.logits, a.ld, a.V, a.wrong, VOCAB, a.uni, a.draw, a.temperature, a.top_k, a.token, a.probs_out, a.ldp,
         a.top_p, a.rows, a.logp != nullptr || a.seq_logp != nullptr, a.logp, lp, a.bias, a.ld_bias, g, h, cc, no, vx, dn, ml,
-        os);
+        os, gd);
     __syncthreads();
     if (a.trace != nullptr && lane == 0) a.trace[b * 4 + 1] = wall_clock64();
     forcing_post_body(b, lane, rec, a.seq, a.ld_seq, a.chord_pos, a.ld_chord, a.wrong, a.draw, a.token, nullptr, a.klen,
@@ -367,7 +378,11 @@ extern "C" int commu_decode_sample_post_pre(const commu_decode_loop_args* p, hip
     if (p->onset_ctl != nullptr && (p->interval_ctl == nullptr || p->onset_table == nullptr || p->onset_rows < 1 ||
                                     p->onset_rows > ONS_ROWS_MAX))
         return -22;
-    LoopStageArgsOns a;
+    // (the kernel reads guide_ctl[b] and two rows of guide_table, their indices clamped into the table; one instantiation)
+    if (p->guide_ctl != nullptr && (p->onset_ctl == nullptr || p->guide_table == nullptr || p->guide_rows < 1 ||
+                                    p->guide_rows > GDE_ROWS_MAX))
+        return -22;
+    LoopStageArgsGde a;
     static_cast<LoopStageArgs&>(a) = LoopStageArgs{
         p->logits, p->ld, V, p->wrong, p->temperature, p->top_k, p->top_p,
         SamplingRows{p->temperature_rows, p->top_k_rows, p->top_p_rows}, p->token, p->probs_out, p->ldp, p->logp, p->seq_logp,
@@ -383,6 +398,10 @@ extern "C" int commu_decode_sample_post_pre(const commu_decode_loop_args* p, hip
     a.onset_ctl = p->onset_ctl;
     a.onset_table = p->onset_table;
     a.onset_rows = p->onset_rows;
+    a.guide_ctl = p->guide_ctl;
+    a.guide_table = p->guide_table;
+    a.guide_rows = p->guide_rows;
+    const LoopStageArgsOns& an = a;
     const LoopStageArgsMel& am = a;
     const LoopStageArgsDen& ad = a;
     const LoopStageArgsVox& av = a;
@@ -394,10 +413,14 @@ extern "C" int commu_decode_sample_post_pre(const commu_decode_loop_args* p, hip
     const dim3 grid(p->B), block(64);
     // five kernels: without a bias / a grammar / a harmony table the launch is the one it always was (no added load, no
     // added register, no added argument); a sixth for the class-keyed controls, a seventh for the note order, an eighth
-    // for the voice cap, a ninth for the note density, a tenth for the melodic interval, an eleventh for the onset templates
-    if (p->onset_ctl != nullptr) {
+    // for the voice cap, a ninth for the note density, a tenth for the melodic interval, an eleventh for the onset templates,
+    // a twelfth for the guide track
+    if (p->guide_ctl != nullptr) {
+        COMMU_LAUNCH((sample_post_pre_kernel<true, true, true, true, true, true, true, true, true, true>), grid, block, 0,
+                     stream, a);
+    } else if (p->onset_ctl != nullptr) {
         COMMU_LAUNCH((sample_post_pre_kernel<true, true, true, true, true, true, true, true, true>), grid, block, 0, stream,
-                     a);
+                     an);
     } else if (p->interval_ctl != nullptr) {
         COMMU_LAUNCH((sample_post_pre_kernel<true, true, true, true, true, true, true, true>), grid, block, 0, stream, am);
     } else if (p->density_ctl != nullptr) {

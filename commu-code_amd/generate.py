@@ -154,6 +154,24 @@ def parse_args():
                                        'file, [[positions 0 .. 127], ...] per bar (cycled), {"grid": n}, {"bars": [...]} or '
                                        '{"from_tokens": [ids], "invert": bool}.  Not covered: forced positions, notes '
                                        'inside --prompt_tokens')
+    # not in the reference (which builds an arrangement by combining tracks generated separately, none of which reads another
+    # track's notes): --guide SPEC -- a pitch is DRAWN only where the guide's cell for the position the bar is at allows it,
+    # and a position only where its cell leaves a pitch (of --pitch_min .. --pitch_max).  SPEC is JSON text or a file
+    # holding it: the raw form {"cells": C, "bars": [[null | [MIDI pitches], .. C entries], ..]} (null: every pitch; C a
+    # power of two from 1 to 128; at most 64 bars, cycled), or the derived form {"from_tokens": [ids], "cells": 16,
+    # "avoid_intervals": [1, 11], "no_unison": false, "below": m | "above": m} -- the notes of a finished track: where
+    # pitches Y sound, x is allowed iff (x - y) mod 12 is in avoid_intervals for no y, x is not in Y (no_unison),
+    # x <= min Y - m (below), x >= max Y + m (above); a silent step allows everything; a cell is the AND over its steps.
+    # It implies none of the other constraints and needs no --grammar.  NOT covered: only a note's START is tested (a drawn
+    # note held across a later change of the guide is not checked), forced tokens (the position 0 after a Bar, a chord's
+    # position), notes inside --prompt_tokens; a pitch range, strict --harmony or --max_leap window that together with the
+    # cell leaves no pitch ends that attempt as before.  With --requests it holds for every request that does not carry a
+    # "guide" of its own.
+    model_arg_parser.add_argument("--guide", default=None, metavar="SPEC",
+                                  help='a drawn pitch fits a mask over pitches indexed by time: JSON text or file, '
+                                       '{"cells": C, "bars": [[null | [pitches], ...], ...]} or {"from_tokens": [ids], '
+                                       '"cells": 16, "avoid_intervals": [1, 11], "no_unison": false, "below": m | "above": m}'
+                                       '.  Not covered: held notes, forced positions, notes inside --prompt_tokens')
     # not in the reference (which decodes one sequence at a time): how many attempts are decoded side by side.  1 .. 256;
     # up to 256 slots run the fused layer-tail launches ("Supported shapes").  The sequences returned do
     # not depend on it.  (checked by check_decode_slots: the range is named in its message)
@@ -296,7 +314,8 @@ REQUEST_KEYS = REQUEST_META_KEYS + ("num_generate", "top_k", "temperature", "top
                                     "pitch_max", "logit_bias")
 # (keys a request object may carry and that its parsed dict holds only then: prompt_tokens, the token ids it continues)
 # and onsets, its own onset template (--onsets' forms, as JSON values)
-REQUEST_OPTIONAL_KEYS = ("prompt_tokens", "onsets")
+# and guide, its own guide track (--guide's forms, as JSON values)
+REQUEST_OPTIONAL_KEYS = ("prompt_tokens", "onsets", "guide")
 # (single-request input arguments that --requests replaces, with the value the parser gives them when they are not named)
 SINGLE_REQUEST_ARGS = {**{k: None for k in REQUEST_META_KEYS}, "genre": "cinematic", "rhythm": "standard",
                        "num_generate": None, "top_k": 32, "temperature": 0.95, "top_p": 1.0, "max_rounds": None,
@@ -358,8 +377,67 @@ def check_requests(model_args, input_args):
                 r = {**r, "onsets": onsets_bars(r["onsets"], "onsets")}
             except ValueError as e:
                 raise ValueError(f"--requests: {path}: request {i}: {e}") from None
+        if r.get("guide") is not None:
+            try:
+                r = {**r, "guide": guide_doc(r["guide"], "guide", r.get("pitch_min"), r.get("pitch_max"))}
+            except ValueError as e:
+                raise ValueError(f"--requests: {path}: request {i}: {e}") from None
         out.append({**SINGLE_REQUEST_ARGS, "seed": 0, **r})
     return out
+
+
+def guide_doc(doc, what="--guide", pitch_min=None, pitch_max=None):
+    """A guide track given as a JSON value -- the raw form or the from_tokens form -- validated and returned as the raw form
+    {"cells": C, "bars": [...], "pitch_range": [lo, hi]} (the derived form is worked out here, once); pitch_min / pitch_max
+    (None: 0 / 127) feed the pitch range of the live bits unless the value names one.  Host code only, ValueError that says
+    what is wrong."""
+    from commu_amd.generate import CommuHipError, guide_template
+    try:
+        if not isinstance(doc, dict):
+            raise CommuHipError(f'guide: {{"cells": C, "bars": [...]}} or {{"from_tokens": [...], ...}} expected, got {doc!r}')
+        rng = doc.get("pitch_range")
+        if rng is None:
+            rng = [0 if pitch_min is None else int(pitch_min), 127 if pitch_max is None else int(pitch_max)]
+        rows, cells = guide_template(doc, tuple(rng) if isinstance(rng, list) else rng)
+    except CommuHipError as e:
+        raise ValueError(f"{what}: {str(e).removeprefix('guide: ')}") from None
+    bars = []
+    for b in range(rows.shape[0] // (1 + cells)):
+        bar = []
+        for c in range(cells):
+            w = rows[b * (1 + cells) + 1 + c]
+            ps = [k for k in range(128) if (int(w[k // 32]) >> (k % 32)) & 1]
+            bar.append(None if len(ps) == 128 else ps)
+        bars.append(bar)
+    return {"cells": cells, "bars": bars, "pitch_range": [int(rng[0]), int(rng[1])]}
+
+
+def check_guide(model_args, input_args=None):
+    """--guide as the JSON text of the guide's raw form (None without the flag): the value is the JSON document itself or
+    the path of a file that holds it.  Host code only, run before a model is loaded; ValueError that says what is wrong.
+    --pitch_min / --pitch_max feed the pitch range of the live bits.  Written back to model_args.guide_doc, which travels
+    to the replicas (ModelInitializeTask puts it into the inference configuration).  It switches nothing else on."""
+    setting = getattr(model_args, "guide", None)
+    model_args.guide_doc = None
+    if setting is None:
+        return None
+    text = setting
+    if not isinstance(setting, str):
+        raise ValueError(f"--guide: JSON text or a readable JSON file expected, got {setting!r}")
+    if not setting.lstrip().startswith(("{", "[")):
+        try:
+            with open(setting) as f:
+                text = f.read()
+        except OSError as e:
+            raise ValueError(f"--guide: JSON text or a readable JSON file expected, got {setting!r} ({e.strerror})") from None
+    try:
+        doc = json.loads(text)
+    except json.JSONDecodeError as e:
+        raise ValueError(f"--guide: not JSON ({e})") from None
+    src = input_args if input_args is not None else model_args
+    model_args.guide_doc = json.dumps(guide_doc(doc, "--guide", getattr(src, "pitch_min", None),
+                                                getattr(src, "pitch_max", None)))
+    return model_args.guide_doc
 
 
 def onsets_bars(doc, what="--onsets"):
@@ -571,6 +649,7 @@ def main(model_args, input_args, training_cfg=None, device_indices=None):
     check_density(model_args)                           # (likewise)
     check_interval(model_args)                          # (likewise)
     check_onsets(model_args)                            # (likewise)
+    check_guide(model_args, input_args)                 # (likewise)
     check_note_order(model_args)                        # (likewise)
     in_args = dict(vars(input_args))
     in_args.pop("requests", None)

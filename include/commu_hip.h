@@ -580,6 +580,34 @@ int commu_transpose_heads(const void* src, int ld, const float* bias, void* dst,
  *     requires interval_ctl and everything interval_ctl requires, a non-null onset_table and 1 <= onset_rows <= 4096,
  *     else -22.  Validating the words is the caller's job (generate.onset_ctl).  The same three fields, with the same
  *     meaning and the same refusals, are in commu_decode_loop_args.  Null onset_ctl: the launch that never heard of it.
+ * GUIDE TRACK (an arrangement is built by combining tracks generated separately from shared metadata, and no other rule
+ * reads another track's notes: harmony knows the chord symbol, an onset template from a track shares its rhythm, and for
+ * PITCH there was nothing)
+ *   guide_ctl: int32 [nseq], one control word per sequence: -1 off, else base + 65536 R + 2^23 s with R in 1 .. 64 the
+ *     template's bars, s in 0 .. 7 and C = 128 >> s the cells per bar, base in 0 .. 65535, base + R (1 + C) <= guide_rows.
+ *     guide_table: uint32 [guide_rows][4], 1 <= guide_rows <= 65536.  Each bar of a template is a block of 1 + C consecutive
+ *     rows: row 0 the bar's LIVE ROW, a 128-bit mask over POSITIONS in onset_table's format (bit g set: a note may start at
+ *     step g); rows 1 .. C the CELL ROWS, 128-bit masks over PITCHES (bit k % 32 of word k / 32 set: PITCH id 3 + k may be
+ *     drawn).  BLOCK OF THE OPEN BAR, as for onset_ctl: i = max(nb - 1, 0) with nb = state[b][8], never counted on a draw,
+ *     a prompt's bars included; the block starts at base + (i mod R) (1 + C).
+ *     PITCH BAN: j and p are order_ctl's (j the largest index with S[j] BAR or a POSITION).  No such j, or S[j] BAR: no
+ *     pitch is banned.  Else g = p - 432, the cell row is block + 1 + (g >> s), and every PITCH id whose bit is clear is
+ *     banned.  Ids outside 3 .. 130 are never touched.
+ *     POSITION BAN: every POSITION id whose bit in the live row is clear is banned.  The live row is ANDed into the onset
+ *     row before that is used, so onset_ctl's position ban AND ITS DENSITY WAIVER apply to the intersection: the waiver lets
+ *     a bar end once position range, onset row and live row together leave no position.
+ *     The bans join the one select of order_ctl, voice_ctl, density_ctl, interval_ctl and onset_ctl.  A draw is BIT FOR BIT
+ *     the draw of the call without guide_ctl and with bias[b] = -inf at these ids (density_ctl's BAR / EOS ban taken under the
+ *     waiver on the ANDed row); an off word, or a word over an all-ones live row with all-ones cell rows, is bit for bit the
+ *     call without the fields.  Every row index is clamped to guide_rows - 1, whatever the arrays hold.
+ *     NOT COVERED: only a note's START is tested -- a drawn note held across a later change of the guide is not checked;
+ *     forced tokens (the position 0 forced after a BAR, a chord's forced position); notes inside a prompt; a pitch range,
+ *     strict harmony or interval window that together with the cell row leaves no pitch ends the attempt by Q12, as before.
+ *     ONE kernel serves it, the onsets kernel with two more scalar 16-byte loads (the live row beside the onset row, the
+ *     cell row once the scan has found p): guide_ctl requires onset_ctl and everything onset_ctl requires, a non-null
+ *     guide_table and 1 <= guide_rows <= 65536, else -22.  Validating the words is the caller's job (generate.guide_rows /
+ *     ForcedDecoder.set_guide).  The same three fields, with the same meaning and the same refusals, are in
+ *     commu_decode_loop_args.  Null guide_ctl: the launch that never heard of it.
  * WHAT gram / harm READ
  *   state: the forcing records, int32 [nseq][commu_forcing_state_ints()]; seq int32 [nseq][ld_seq]; chord_tok int32
  *   [nseq][ld_chord].  Not looked at, and may be null, in a call without gram and harm.
@@ -619,6 +647,10 @@ typedef struct commu_sample_args {
     const int* seq;
     const int* chord_tok;
     int ld_seq, ld_chord;
+    /* guide track (ahead of onset_ctl: the eight fields behind them keep their places at the struct's end) */
+    const int* guide_ctl;
+    const unsigned* guide_table;
+    int guide_rows;
     /* onset templates (ahead of interval_ctl: the five fields behind them keep their places at the struct's end) */
     const int* onset_ctl;
     const unsigned* onset_table;
@@ -850,6 +882,10 @@ typedef struct commu_decode_loop_args {
     const float* harm;
     const unsigned char* harm_on;
     int ld_bias, ld_gram, ld_harm;
+    /* guide track (commu_sample_args.guide_ctl / guide_table / guide_rows; likewise ahead of onset_ctl) */
+    const int* guide_ctl;
+    const unsigned* guide_table;
+    int guide_rows;
     /* onset templates (commu_sample_args.onset_ctl / onset_table / onset_rows; likewise ahead of interval_ctl) */
     const int* onset_ctl;
     const unsigned* onset_table;
@@ -913,7 +949,8 @@ int commu_decode_prefill_scatter(const void* qkv, int ld_qkv, int T, int B, void
  *   temperature_rows / top_k_rows / top_p_rows [slot] = e_temperature / e_top_k / e_top_p [entry];
  *   bias[slot][0 .. ld_bias) = e_bias[entry];  gram_on / harm_on [slot] = e_gram_on / e_harm_on [entry] (bytes);
  *   order_ctl / voice_ctl / density_ctl / interval_ctl / onset_ctl [slot] = e_order / e_voice / e_density / e_interval /
- *   e_onset [entry] (the onset table is the pool's own: no table bytes move per arm);
+ *   e_onset [entry] (the onset table is the pool's own: no table bytes move per arm);  guide_ctl[slot] = e_guide[entry]
+ *   (likewise: the guide table is the pool's own);
  *   cls_ctl[slot][0 .. 32) = e_cls[entry] (int32).
  * tok / active / keep / draw are NOT written: an armed slot sits out the iteration whose decision was taken from its
  * finished record and starts with the next one.  Two jobs of one launch must name different slots (the caller's duty).
@@ -970,6 +1007,8 @@ typedef struct commu_decode_arm_args {
     const unsigned char* e_gram_on;
     unsigned char* harm_on;
     const unsigned char* e_harm_on;
+    int* guide_ctl;
+    const int* e_guide;
     int* onset_ctl;
     const int* e_onset;
     int* interval_ctl;
@@ -1061,6 +1100,8 @@ typedef struct commu_decode_arm_primed_args {
     const unsigned char* e_gram_on;
     unsigned char* harm_on;
     const unsigned char* e_harm_on;
+    int* guide_ctl;
+    const int* e_guide;
     int* onset_ctl;
     const int* e_onset;
     int* interval_ctl;
