@@ -64,6 +64,7 @@ class SampleArgs(C.Structure):
                 ("bias", c_p), ("gram", c_p), ("gram_on", c_p), ("harm", c_p), ("harm_on", c_p),
                 ("ld_bias", c_i), ("ld_gram", c_i), ("ld_harm", c_i),
                 ("state", c_p), ("seq", c_p), ("chord_tok", c_p), ("ld_seq", c_i), ("ld_chord", c_i),
+                ("art_ctl", c_p), ("art_table", c_p), ("art_rows", c_i),
                 ("guide_ctl", c_p), ("guide_table", c_p), ("guide_rows", c_i),
                 ("onset_ctl", c_p), ("onset_table", c_p), ("onset_rows", c_i),
                 ("interval_ctl", c_p), ("density_ctl", c_p), ("order_ctl", c_p), ("voice_ctl", c_p), ("cls_ctl", c_p)]
@@ -82,6 +83,7 @@ class DecodeLoopArgs(C.Structure):
                 ("klen", c_p), ("lmax", c_i),
                 ("bias", c_p), ("gram", c_p), ("gram_on", c_p), ("harm", c_p), ("harm_on", c_p),
                 ("ld_bias", c_i), ("ld_gram", c_i), ("ld_harm", c_i),
+                ("art_ctl", c_p), ("art_table", c_p), ("art_rows", c_i),
                 ("guide_ctl", c_p), ("guide_table", c_p), ("guide_rows", c_i),
                 ("onset_ctl", c_p), ("onset_table", c_p), ("onset_rows", c_i),
                 ("interval_ctl", c_p), ("density_ctl", c_p), ("order_ctl", c_p), ("voice_ctl", c_p), ("cls_ctl", c_p)]
@@ -101,6 +103,7 @@ class DecodeArmArgs(C.Structure):
                 ("e_temperature", c_p), ("e_top_k", c_p), ("e_top_p", c_p),
                 ("bias", c_p), ("e_bias", c_p), ("ld_bias", c_i),
                 ("gram_on", c_p), ("e_gram_on", c_p), ("harm_on", c_p), ("e_harm_on", c_p),
+                ("art_ctl", c_p), ("e_art", c_p),
                 ("guide_ctl", c_p), ("e_guide", c_p),
                 ("onset_ctl", c_p), ("e_onset", c_p),
                 ("interval_ctl", c_p), ("e_interval", c_p), ("density_ctl", c_p), ("e_density", c_p),
@@ -122,6 +125,7 @@ class DecodeArmPrimedArgs(C.Structure):
                 ("e_temperature", c_p), ("e_top_k", c_p), ("e_top_p", c_p),
                 ("bias", c_p), ("e_bias", c_p), ("ld_bias", c_i),
                 ("gram_on", c_p), ("e_gram_on", c_p), ("harm_on", c_p), ("e_harm_on", c_p),
+                ("art_ctl", c_p), ("e_art", c_p),
                 ("guide_ctl", c_p), ("e_guide", c_p),
                 ("onset_ctl", c_p), ("e_onset", c_p),
                 ("interval_ctl", c_p), ("e_interval", c_p), ("density_ctl", c_p), ("e_density", c_p),

@@ -956,6 +956,126 @@ def _guide_per_slot(x, B: int):
     return [guide_template(x)] * B
 
 
+# ---- articulation: one int32 control word per slot (commu_sample_args.art_ctl) and one device table of 128-bit rows
+# (art_table).  A row is one bar of a template: word 0 dlo | dhi << 8 (steps, 0: not set), words 1 and 2 the 64-bit mask of
+# the velocity bins that may be drawn, word 3 reserved (0).  A slot that is on DRAWS a duration only inside the window of
+# its open bar's row -- capped at the bar line (within_bar) and at the first step where the slot's guide bans the pitch just
+# drawn (hold_guide) -- and a velocity only where the row has a bit.  The row of the open bar is base + (i mod R), i as for
+# the onsets.  It implies none of the other words.
+ARTICULATION_OFF = -1
+ARTICULATION_ROWS_MAX = 4096   # rows of the device table (64 KB); the word is base + 4096 R + 2^19 w + 2^20 h
+ARTICULATION_CYCLE_MAX = 64    # bars of one template
+ARTICULATION_KEYS = {"bars", "within_bar", "hold_guide"}
+ARTICULATION_BAR_KEYS = {"duration", "velocity"}
+
+
+def articulation_word(base: int, bars: int, within_bar: bool = False, hold_guide: bool = False) -> int:
+    """The control word base + 4096 R + 2^19 w + 2^20 h of a template of R bars at table row base."""
+    return int(base) + 4096 * int(bars) + (1 << 19) * int(bool(within_bar)) + (1 << 20) * int(bool(hold_guide))
+
+
+def _articulation_bar(bar, where: str) -> List[int]:
+    """One bar {"duration": [lo, hi], "velocity": [lo, hi]} | None as its four words."""
+    if bar is None:
+        return [0, 0xFFFFFFFF, 0xFFFFFFFF, 0]
+    if not isinstance(bar, dict):
+        raise CommuHipError(f'articulation: {where}null or {{"duration": [lo, hi], "velocity": [lo, hi]}} expected, got {bar!r}')
+    extra = sorted(set(bar) - ARTICULATION_BAR_KEYS)
+    if extra:
+        raise CommuHipError(f"articulation: {where}unknown key {extra[0]!r} (known: {sorted(ARTICULATION_BAR_KEYS)})")
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+    dlo = dhi = 0
+    if bar.get("duration") is not None:
+        d = bar["duration"]
+        if not isinstance(d, (list, tuple)) or len(d) != 2 or not all(v is None or (is_int(v) and 1 <= v <= 128) for v in d):
+            raise CommuHipError(f"articulation: {where}duration: a pair [lo, hi] of steps 1 .. 128 (either may be null) "
+                                f"expected, got {d!r}")
+        if d[0] is not None and d[1] is not None and d[0] > d[1]:
+            raise CommuHipError(f"articulation: {where}duration: lo <= hi expected, got {list(d)!r}")
+        dlo, dhi = int(d[0] or 0), int(d[1] or 0)
+    mask = (1 << 64) - 1
+    if bar.get("velocity") is not None:
+        v = bar["velocity"]
+        if not isinstance(v, (list, tuple)) or len(v) != 2 or not all(is_int(x) and 0 <= x <= 127 for x in v):
+            raise CommuHipError(f"articulation: {where}velocity: a pair [lo, hi] of MIDI velocities 0 .. 127 expected, got {v!r}")
+        if v[0] > v[1]:
+            raise CommuHipError(f"articulation: {where}velocity: lo <= hi expected, got {list(v)!r}")
+        # (bins floor(lo / 2) .. ceil(hi / 2), capped at 63: token_constraints(velocity_range=...) maps them the same way)
+        b0, b1 = int(v[0]) // 2, min((int(v[1]) + 1) // 2, 63)
+        if b0 > b1:
+            raise CommuHipError(f"articulation: {where}velocity: the range {list(v)!r} holds no velocity bin")
+        mask = ((1 << (b1 + 1)) - 1) & ~((1 << b0) - 1)
+    return [dlo | dhi << 8, mask & 0xFFFFFFFF, mask >> 32, 0]
+
+
+def articulation_template(x):
+    """An articulation as (rows, within_bar, hold_guide): rows uint32 [R][4] (articulation_rows) and the two switches.  x: the
+    full form {"bars": [{"duration": [lo, hi], "velocity": [lo, hi]} | null, ..], "within_bar": bool, "hold_guide": bool} (at
+    most 64 bars, cycled bar by bar; a null bar constrains nothing); the short form, the single bar's keys at top level, e.g.
+    {"duration": [2, 16], "hold_guide": true}; or a triple (uint32 [R][4], within_bar, hold_guide) that is one already.
+    duration is in steps 1 .. 128, either end may be null; velocity is in MIDI 0 .. 127 and maps to the bins floor(lo / 2) ..
+    ceil(hi / 2), capped at 63.  Pure host code; raises CommuHipError on anything else, with the bar index and the value."""
+    if isinstance(x, tuple) and len(x) == 3 and isinstance(x[0], np.ndarray) and x[0].dtype == np.uint32:
+        rows, w, h = x
+        if rows.ndim != 2 or rows.shape[1] != 4 or not 1 <= rows.shape[0] <= ARTICULATION_CYCLE_MAX:
+            raise CommuHipError(f"articulation: a uint32 template is [R][4] with R in 1 .. {ARTICULATION_CYCLE_MAX}, got "
+                                f"shape {rows.shape}")
+        if ((rows[:, 1] | rows[:, 2]) == 0).any():
+            raise CommuHipError(f"articulation: bar {int(np.argmax((rows[:, 1] | rows[:, 2]) == 0))}: an empty velocity mask")
+        return np.ascontiguousarray(rows), bool(w), bool(h)
+    if not isinstance(x, dict):
+        raise CommuHipError(f'articulation: {{"bars": [...], "within_bar": bool, "hold_guide": bool}} or {{"duration": '
+                            f'[lo, hi], "velocity": [lo, hi], ...}} expected, got {x!r}')
+    if "bars" in x:
+        extra = sorted(set(x) - ARTICULATION_KEYS)
+        if extra:
+            raise CommuHipError(f"articulation: unknown key {extra[0]!r} beside bars (known: {sorted(ARTICULATION_KEYS)})")
+        bars = x["bars"]
+        if not isinstance(bars, (list, tuple)) or not 1 <= len(bars) <= ARTICULATION_CYCLE_MAX:
+            raise CommuHipError(f"articulation: a template holds 1 .. {ARTICULATION_CYCLE_MAX} bars, got "
+                                f"{len(bars) if isinstance(bars, (list, tuple)) else bars!r}")
+        words = [_articulation_bar(b, f"bar {i}: ") for i, b in enumerate(bars)]
+    else:
+        extra = sorted(set(x) - ARTICULATION_BAR_KEYS - {"within_bar", "hold_guide"})
+        if extra:
+            raise CommuHipError(f"articulation: unknown key {extra[0]!r} (known: "
+                                f"{sorted(ARTICULATION_BAR_KEYS | ARTICULATION_KEYS)})")
+        words = [_articulation_bar({k: x[k] for k in ARTICULATION_BAR_KEYS if k in x}, "")]
+    for k in ("within_bar", "hold_guide"):
+        if not isinstance(x.get(k, False), (bool, np.bool_)):
+            raise CommuHipError(f"articulation: {k}: true or false expected, got {x[k]!r}")
+    return np.array(words, dtype=np.uint32), bool(x.get("within_bar", False)), bool(x.get("hold_guide", False))
+
+
+def articulation_rows(x) -> np.ndarray:
+    """An articulation's table rows, uint32 [R][4]: per bar word 0 = dlo | dhi << 8 (steps; 0: not set), words 1 and 2 the
+    64-bit mask of the velocity bins that may be drawn (bit k % 32 of word 1 + k // 32: id 131 + k, MIDI velocity 2 k),
+    word 3 = 0.  x as for articulation_template."""
+    return articulation_template(x)[0]
+
+
+def _articulation_needs_guide(arts, guides):
+    """hold_guide reads the sequence's own guide: refused where a sequence asks for it and has none."""
+    for i, (a, g) in enumerate(zip(arts, guides)):
+        if a is not None and a[2] and g is None:
+            raise CommuHipError("articulation: hold_guide without a guide" +
+                                (f" (sequence {i})" if len(arts) > 1 else "") + ": it reads the sequence's own guide track")
+
+
+def _articulation_per_slot(x, B: int):
+    """A request's articulation= as B entries, each None (off) or a template (rows, within_bar, hold_guide): None / False
+    (all off), one articulation in any form articulation_template takes (all slots), or a list of B entries each None /
+    False or an articulation."""
+    B = int(B)
+    if x is None or x is False:
+        return [None] * B
+    if isinstance(x, list):
+        if len(x) != B:
+            raise CommuHipError(f"articulation: {B} entries expected (one per sequence), got {len(x)}")
+        return [None if (v is None or v is False) else articulation_template(v) for v in x]
+    return [articulation_template(x)] * B
+
+
 class DecodeState:
     """K/V caches + distance-indexed R tables for B sequences of up to Lmax positions.
 
@@ -1435,6 +1555,15 @@ class ForcedDecoder:
     _guide_used = 0
     _guide_index = None
 
+    # articulation (set_articulation): the same six for the articulation's control words and its table of
+    # ARTICULATION_ROWS_MAX rows (64 KB)
+    art_ctl = None
+    _art_host = None
+    art_table = None
+    _art_table_host = None
+    _art_used = 0
+    _art_index = None
+
     def __init__(self, model, B: int, generation_length: int, memory_length: int, temperature: float, top_k: int,
                  max_chords: int = 64, record_trace: bool = False, top_p: float = 1.0, sliding: bool = False,
                  max_prompt: int = 0, kv_dtype: str = "bf16", shared_prompt: bool = False):
@@ -1583,14 +1712,15 @@ class ForcedDecoder:
         return idx
 
     def _first_use(self, rows=False, bias=False, gram=False, harm=False, cls=False, order=False, voices=False,
-                   density=False, interval=False, onsets=False, guide=False):
+                   density=False, interval=False, onsets=False, guide=False, articulation=False):
         """What the first use of a per-slot launch input does, for each one asked for that the decoder does not have yet:
         rows uploads the host mirror of the sampling controls (scalar mode kept the mirror only); bias / gram / harm
         allocate their zeroed device buffers (gram and harm: the table and the [B] switches); cls allocates the slots'
         class-control records (set_class_sampling fills them); order allocates the slots' note-order words, all off; voices
         the slots' voice words, all off; density the slots' density words, all off; interval the slots' interval words,
         all off; onsets the slots' onset words, all off, and the template table of ONSET_ROWS_MAX all-ones rows; guide the
-        slots' guide words, all off, and the guide table of GUIDE_ROWS_MAX all-ones rows.
+        slots' guide words, all off, and the guide table of GUIDE_ROWS_MAX all-ones rows; articulation the slots'
+        articulation words, all off, and the articulation table of ARTICULATION_ROWS_MAX rows that constrain nothing.
         When anything was missing the captured graphs are dropped,
         once: they hold the launches without it."""
         new = False
@@ -1644,6 +1774,15 @@ class ForcedDecoder:
             self.guide_table = torch.full((GUIDE_ROWS_MAX, 4), -1, dtype=torch.int32, device=self.dev)
             self._guide_table_host = np.full((GUIDE_ROWS_MAX, 4), 0xFFFFFFFF, dtype=np.uint32)
             self._guide_used, self._guide_index = 0, {}
+        if articulation and self.art_ctl is None:
+            new = True
+            self.art_ctl = torch.full((self.B,), ARTICULATION_OFF, dtype=torch.int32, device=self.dev)
+            self._art_host = np.full(self.B, ARTICULATION_OFF, dtype=np.int32)
+            # (a row that constrains nothing: no bounds, every velocity bin, the reserved word 0)
+            free = np.array([0, 0xFFFFFFFF, 0xFFFFFFFF, 0], dtype=np.uint32)
+            self._art_table_host = np.tile(free, (ARTICULATION_ROWS_MAX, 1))
+            self.art_table = torch.from_numpy(self._art_table_host.view(np.int32).copy()).to(self.dev)
+            self._art_used, self._art_index = 0, {}
         if new:
             self.graph = self.graph_long = None
 
@@ -2107,6 +2246,79 @@ class ForcedDecoder:
             for j in idx:
                 self.guide_ctl[int(j)].fill_(int(self._guide_host[j]))
 
+    def _art_pack(self, templates, fresh: bool = False):
+        """The control words of the given articulations ((rows uint32 [R][4], within_bar, hold_guide); None: off) in the
+        decoder's table: as _guide_pack -- distinct templates, told apart by their bytes (the switches live in the word, so
+        two settings over the same rows share them), one behind the other; fresh packs the table anew from these alone; what
+        does not fit is refused before anything changes; new rows are written in place, ordered on the current stream."""
+        index = {} if fresh else dict(self._art_index)
+        used = 0 if fresh else self._art_used
+        todo, words = [], []
+        for t in templates:
+            if t is None:
+                words.append(ARTICULATION_OFF)
+                continue
+            rows, w, h = t
+            if rows.shape[0] > ARTICULATION_CYCLE_MAX:
+                raise CommuHipError(f"articulation: a template holds at most {ARTICULATION_CYCLE_MAX} bars, got {rows.shape[0]}")
+            key = rows.tobytes()
+            if key not in index:
+                if used + rows.shape[0] > ARTICULATION_ROWS_MAX:
+                    raise CommuHipError(f"articulation: the distinct templates need more than the table's "
+                                        f"{ARTICULATION_ROWS_MAX} rows ({used} in use, {rows.shape[0]} more asked for)")
+                index[key] = used
+                todo.append((used, rows))
+                used += rows.shape[0]
+            words.append(articulation_word(index[key], rows.shape[0], w, h))
+        for base, rows in todo:
+            self._art_table_host[base:base + rows.shape[0]] = rows
+            self.art_table[base:base + rows.shape[0]].copy_(torch.from_numpy(rows.view(np.int32)))
+        self._art_index, self._art_used = index, used
+        return np.array(words, dtype=np.int32)
+
+    def set_articulation(self, value, rows: Optional[Sequence[int]] = None):
+        """The articulation for all slots (rows=None) or the listed ones: an articulation in any form articulation_template
+        takes -- the full form {"bars": [...], "within_bar": bool, "hold_guide": bool}, the short form {"duration": [lo, hi],
+        "velocity": [lo, hi], ...}, a triple (uint32 rows, within_bar, hold_guide) -- None / False (off), or a list with one
+        such value per addressed slot.  A slot that is on DRAWS a velocity only where the row of its open bar has a bit and
+        a duration only inside the row's window, capped at the bar line (within_bar) and at the first step where the slot's
+        guide (set_guide) bans the pitch just drawn (hold_guide; with the slot's guide off the term does not apply); bar i
+        of the sequence (counted as set_onsets counts it, the prompt's bars included) uses row i mod R.  Where the bar line
+        or the guide leaves less room than the lower bound, the lower bound gives way.  Not covered: forced tokens and
+        anything a forced position starts; a prompt; the hold term reads the guide only, and reads the next bar's block
+        even where the generation length would cut the sequence first.
+        Exactly like set_guide: the first call that switches a slot on allocates the [B] words, the table of 4096 rows
+        (64 KB) -- ONCE, so that its address stays fixed under graph capture -- and, where the decoder lacks them, the
+        off-words of everything the one kernel reads besides (set_guide's words and table included), and drops the
+        captured graphs once; later calls pack new templates behind the ones in the table and rewrite words and rows IN
+        PLACE, ordered on the current stream.  A call for all slots packs the table anew.  Refused with the numbers: a
+        template of more than 64 bars, distinct templates of more than 4096 rows together.  A slot that is off decodes
+        bit for bit what it decoded without the feature; a decoder that never switched a slot on allocates nothing."""
+        idx = self._slots(rows)
+        tmpl = _articulation_per_slot(value, len(idx))         # (validated before anything changes)
+        if self.art_ctl is None and all(t is None for t in tmpl):
+            return
+        if self.art_ctl is None:
+            # (the capacity check of _art_pack, before anything is allocated)
+            need = sum(len(k) // 16 for k in {t[0].tobytes() for t in tmpl if t is not None})
+            if need > ARTICULATION_ROWS_MAX:
+                raise CommuHipError(f"articulation: the distinct templates need more than the table's "
+                                    f"{ARTICULATION_ROWS_MAX} rows (0 in use, {need} asked for)")
+        fresh_cls = self.cls_ctl is None
+        self._first_use(rows=True, bias=True, gram=True, harm=True, cls=True, order=True, voices=True, density=True,
+                        interval=True, onsets=True, guide=True, articulation=True)
+        if fresh_cls:          # (no class controls: every record of every slot holds the slot's base triple)
+            self._write_class_ctl(None, np.arange(self.B))
+        new = self._art_pack(tmpl, fresh=rows is None)
+        if np.array_equal(self._art_host[idx], new):
+            return
+        self._art_host[idx] = new
+        if rows is None and len(idx) > 4:
+            self.art_ctl.copy_(torch.from_numpy(self._art_host))
+        else:
+            for j in idx:
+                self.art_ctl[int(j)].fill_(int(self._art_host[j]))
+
     def pre(self):
         call("commu_forcing_pre", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_tok), _p(self.chord_pos),
              self.ld_chord, _p(self.wrong), _p(self.utable), self.ld_u, self.generation_length, _p(self.tok),
@@ -2130,7 +2342,8 @@ class ForcedDecoder:
                         **({} if self.density_ctl is None else {"density": self.density_ctl}),
                         **({} if self.interval_ctl is None else {"interval": self.interval_ctl}),
                         **({} if self.onset_ctl is None else {"onsets": (self.onset_ctl, self.onset_table)}),
-                        **({} if self.guide_ctl is None else {"guide": (self.guide_ctl, self.guide_table)}))
+                        **({} if self.guide_ctl is None else {"guide": (self.guide_ctl, self.guide_table)}),
+                        **({} if self.art_ctl is None else {"articulation": (self.art_ctl, self.art_table)}))
         call("commu_forcing_post", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_pos), self.ld_chord,
              _p(self.wrong), _p(self.draw), _p(self.token), None, _p(self.state.klen), _p(self.keep),
              self.state.klen_cap, _p(logp), _p(seq_logp), B, _s())
@@ -2159,7 +2372,9 @@ class ForcedDecoder:
             **({} if self.onset_ctl is None else {"onset_ctl": _p(self.onset_ctl), "onset_table": _p(self.onset_table),
                                                   "onset_rows": ONSET_ROWS_MAX}),
             **({} if self.guide_ctl is None else {"guide_ctl": _p(self.guide_ctl), "guide_table": _p(self.guide_table),
-                                                  "guide_rows": GUIDE_ROWS_MAX}))
+                                                  "guide_rows": GUIDE_ROWS_MAX}),
+            **({} if self.art_ctl is None else {"art_ctl": _p(self.art_ctl), "art_table": _p(self.art_table),
+                                                "art_rows": ARTICULATION_ROWS_MAX}))
         call("commu_decode_sample_post_pre", C.byref(a), _s())
 
     def iteration(self, want_probs: bool = False):
@@ -2423,8 +2638,11 @@ class ForcedDecoder:
     # interval: the slot's interval word for its next attempt (set_interval's values, False: off; None: the slot keeps its word).
     # onsets: the slot's onset template for its next attempt (set_onsets' values, False: off; None: the slot keeps its word).
     # guide: the slot's guide track for its next attempt (set_guide's values, False: off; None: the slot keeps its word).
+    # articulation: the slot's articulation for its next attempt (set_articulation's values, False: off; None: the slot keeps
+    # its word).
     def rearm(self, b: int, uniforms_row: Optional[np.ndarray] = None, sampling=None, logit_bias=None, grammar=None,
-              harmony=None, note_order=None, voices=None, density=None, interval=None, onsets=None, guide=None):
+              harmony=None, note_order=None, voices=None, density=None, interval=None, onsets=None, guide=None,
+              articulation=None):
         if note_order is not None:
             self.set_note_order(note_order, rows=[b])
         if voices is not None:
@@ -2437,6 +2655,8 @@ class ForcedDecoder:
             self.set_onsets(onsets, rows=[b])
         if guide is not None:
             self.set_guide(guide, rows=[b])
+        if articulation is not None:
+            self.set_articulation(articulation, rows=[b])
         if sampling is not None:
             self.set_sampling(*sampling, rows=[b])
         if logit_bias is not None:
@@ -2640,7 +2860,8 @@ class ForcedDecoder:
                 "e_density": torch.full((R,), DENSITY_OFF, dtype=i32, device=dev),
                 "e_interval": torch.full((R,), INTERVAL_OFF, dtype=i32, device=dev),
                 "e_onset": torch.full((R,), ONSETS_OFF, dtype=i32, device=dev),
-                "e_guide": torch.full((R,), GUIDE_OFF, dtype=i32, device=dev), "e_cls": z(R, N_CLASSES + 1, 4),
+                "e_guide": torch.full((R,), GUIDE_OFF, dtype=i32, device=dev),
+                "e_art": torch.full((R,), ARTICULATION_OFF, dtype=i32, device=dev), "e_cls": z(R, N_CLASSES + 1, 4),
                 "hdr": hdr, "stage": z(words),
                 # two pinned staging buffers and an event each: the host never overwrites a buffer whose copy is in flight
                 "pin": [torch.zeros(words, dtype=i32).pin_memory() for _ in range(2)],
@@ -2665,7 +2886,7 @@ class ForcedDecoder:
         """The arm launch's argument block, rebuilt when an optional array was allocated since (a null twin: not written)."""
         P = self._pool
         opt = (self.bias, self.gram_on, self.harm_on, self.order_ctl, self.voice_ctl, self.density_ctl, self.interval_ctl,
-               self.onset_ctl, self.guide_ctl, self.cls_ctl, self.trace)
+               self.onset_ctl, self.guide_ctl, self.art_ctl, self.cls_ctl, self.trace)
         sig = tuple(None if t is None else t.data_ptr() for t in opt)
         if P["args"] is None or P["sig"] != sig:
             st = self.state
@@ -2691,6 +2912,7 @@ class ForcedDecoder:
                 **on(self.interval_ctl, {"interval_ctl": self.interval_ctl, "e_interval": P["e_interval"]}),
                 **on(self.onset_ctl, {"onset_ctl": self.onset_ctl, "e_onset": P["e_onset"]}),
                 **on(self.guide_ctl, {"guide_ctl": self.guide_ctl, "e_guide": P["e_guide"]}),
+                **on(self.art_ctl, {"art_ctl": self.art_ctl, "e_art": P["e_art"]}),
                 **on(self.cls_ctl, {"cls_ctl": self.cls_ctl, "e_cls": P["e_cls"]}))
             P["sig"] = sig
         if P["primed"]:
@@ -2699,13 +2921,13 @@ class ForcedDecoder:
 
     def admit(self, entry: int, encoded_meta: Sequence[int], input_data, sampling=None, logit_bias=None, grammar=False,
               harmony=False, note_order=None, voices=None, class_table=None, primed=None, density=None, interval=None,
-              onsets=None, guide=None):
+              onsets=None, guide=None, articulation=None):
         """Compose store entry `entry` for a request and upload it with its K/V image: the state record, sequence head
         and chord rows as load() builds them, klen0 = n_cond, the sampling triple (None: the decoder's), the bias row
         (None: zeros), the grammar and harmony switches (they switch on what the decoder has a table for), the
         note-order, voice, density and interval words (None: off), the onset word of the template `onsets` (None: off; the
         template's rows go to the decoder's own table, where the same template is stored once -- no table bytes move per arm),
-        the guide word of the guide track `guide` (likewise) and, where the decoder has class records, the request's record row
+        the guide word of the guide track `guide` (likewise), the articulation word of `articulation` (likewise) and, where the decoder has class records, the request's record row
         (class_table: its NaN-table, None: the base triple in every record).  The image is written by ONE memory-less
         forward over this request's single column [n_cond, 1] and the prefill scatter of the cache's format into the
         store: it does not depend on what else is admitted or decoding.  Everything is ordered on the current stream.
@@ -2735,6 +2957,9 @@ class ForcedDecoder:
         gde = _guide_per_slot(guide, 1)
         if gde[0] is not None and self.guide_ctl is None:
             raise CommuHipError("admit: a guide track, but the decoder has no guide words (set_guide)")
+        art = _articulation_per_slot(articulation, 1)
+        if art[0] is not None and self.art_ctl is None:
+            raise CommuHipError("admit: an articulation, but the decoder has no articulation words (set_articulation)")
         if grammar and (self.gram is None or self._gram_host is None):
             raise CommuHipError("admit: grammar switched on, but the decoder has no grammar table (set_grammar)")
         if harmony and (self.harm is None or self._harm_host is None):
@@ -2799,6 +3024,7 @@ class ForcedDecoder:
         P["e_interval"][entry].fill_(int(mel[0]))
         P["e_onset"][entry].fill_(int(ONSETS_OFF if ons[0] is None else self._onsets_pack(ons)[0]))
         P["e_guide"][entry].fill_(int(GUIDE_OFF if gde[0] is None else self._guide_pack(gde)[0]))
+        P["e_art"][entry].fill_(int(ARTICULATION_OFF if art[0] is None else self._art_pack(art)[0]))
         if self.cls_ctl is not None:
             tab = np.full((1, N_CLASSES + 1, 3), np.nan) if class_table is None else class_sampling_table(class_table)[None]
             rec = class_ctl_records(tab, [t, k, p])
@@ -3001,7 +3227,8 @@ class PoolRequest:
     per-request bool (None: on where the pool has a table), they may only switch on what the pool has a table for;
     note_order / voices / density / interval / onsets: as generate_stream's (onsets: ONE template in any form onset_rows
     takes; the pool packs its requests' templates into one table); guide: ONE guide track in any form guide_template takes,
-    likewise.  prompt: token ids that follow the conditioning tokens and that every
+    likewise; articulation: ONE articulation in any form articulation_template takes, likewise (hold_guide needs the request's
+    own guide).  prompt: token ids that follow the conditioning tokens and that every
     attempt of THIS request continues (generate_stream's prompt=); None or [] is an unprimed request."""
     encoded_meta: Sequence[int]
     input_data: object
@@ -3022,6 +3249,7 @@ class PoolRequest:
     interval: Optional[object] = None
     onsets: Optional[object] = None
     guide: Optional[object] = None
+    articulation: Optional[object] = None
 
 
 PoolResult = collections.namedtuple("PoolResult", ["sequences", "attempts_started", "logprobs"])
@@ -3145,7 +3373,7 @@ class BatchedGenerator:
 
     def decoder(self, B, temperature, top_k, max_chords, top_p=1.0, per_slot: bool = False, max_prompt: int = 0,
                 logit_bias=None, shared: bool = False, grammar=None, harmony=None, class_sampling=None,
-                note_order=None, voices=None, density=None, interval=None, onsets=None, guide=None):
+                note_order=None, voices=None, density=None, interval=None, onsets=None, guide=None, articulation=None):
         """The decoder for B slots, its slots set to the given controls (numbers or one value per slot).  per_slot: the
         caller will read log-probabilities or give slots their own controls later (rearm): the array launches from the
         start.  Otherwise one triple for all slots runs the scalar launches, until a second setting arrives for launches
@@ -3159,7 +3387,8 @@ class BatchedGenerator:
         the request's density words (density_ctl), likewise; a slot that gets one has its voice word and note order switched
         on.  interval: the request's interval words (interval_ctl), likewise; it switches nothing else on.  onsets: the request's onset templates (one for all
         sequences or one per sequence, ForcedDecoder.set_onsets), likewise.  guide: the request's guide tracks (one for
-        all sequences or one per sequence, ForcedDecoder.set_guide), likewise.  shared: the
+        all sequences or one per sequence, ForcedDecoder.set_guide), likewise.  articulation: the request's articulations
+        (one for all sequences or one per sequence, ForcedDecoder.set_articulation), likewise.  shared: the
         decoder that holds the
         request's common prompt once (its own cache layout: kept beside the unshared decoder of the same size)."""
         rows = sampling_rows(B, temperature, top_k, top_p)          # (validated before anything is built)
@@ -3174,6 +3403,8 @@ class BatchedGenerator:
         mel = interval_ctl(interval, B)
         ons = _onsets_per_slot(onsets, B)
         gde = _guide_per_slot(guide, B)
+        art = _articulation_per_slot(articulation, B)
+        _articulation_needs_guide(art, gde)
         key = (B, self.trace is not None, self.sliding) + (("shared",) if shared else ())
         dec = self._decoders.get(key)
         if dec is None or dec.ld_chord < max_chords or dec.max_prompt < max_prompt:
@@ -3208,6 +3439,8 @@ class BatchedGenerator:
         dec.set_onsets(ons)
         # (guide track: likewise)
         dec.set_guide(gde)
+        # (articulation: likewise)
+        dec.set_articulation(art)
         return dec
 
     @staticmethod
@@ -3221,8 +3454,12 @@ class BatchedGenerator:
     def generate(self, encoded_metas: Sequence[Sequence[int]], input_datas, temperature, top_k, top_p=1.0,
                  return_logprobs: bool = False, prompts: Optional[Sequence[Sequence[int]]] = None, logit_bias=None,
                  grammar=None, harmony=None, class_sampling=None, note_order=None, voices=None, density=None,
-                 interval=None, onsets=None, guide=None):
-        """temperature / top_k / top_p: a number for the batch or one value per sequence.  guide: None / False, one guide
+                 interval=None, onsets=None, guide=None, articulation=None):
+        """temperature / top_k / top_p: a number for the batch or one value per sequence.  articulation: None / False, one
+        articulation in any form articulation_template takes, or a list with one entry (None / False / an articulation) per
+        sequence -- such a sequence DRAWS a duration only inside the window of its open bar's row, capped at the bar line
+        (within_bar) and at the first step where its guide bans the pitch just drawn (hold_guide: guide= is required), and a
+        velocity only where the row has a bit; implies none of the other constraints (ForcedDecoder.set_articulation).  guide: None / False, one guide
         track in any form guide_template takes, or a list with one entry (None / False / a guide) per sequence -- such a
         sequence DRAWS a pitch only where the cell row of the position its bar is at has a bit, and a position only where
         the live row has one; implies none of the other constraints (ForcedDecoder.set_guide).  onsets: None / False, one
@@ -3259,7 +3496,8 @@ class BatchedGenerator:
         dec = self.decoder(B, temperature, top_k, max_chords, top_p, per_slot=return_logprobs, max_prompt=max_prompt,
                            logit_bias=logit_bias, shared=self.shared_prompt and max_prompt > 0, grammar=grammar,
                            harmony=self._one_harmony(harmony), class_sampling=class_sampling, note_order=note_order,
-                           voices=voices, density=density, interval=interval, onsets=onsets, guide=guide)
+                           voices=voices, density=density, interval=interval, onsets=onsets, guide=guide,
+                           articulation=articulation)
         uniforms = None
         if bool((dec._sampling[0] != 0).any()) or dec.class_samples():
             srcs = self.uniform_sources or [np.random.RandomState(1000 + b).random_sample for b in range(B)]
@@ -3284,7 +3522,7 @@ class BatchedGenerator:
                         accept, top_p=1.0, slots: int = 64, seed: int = 0, max_attempts: Optional[int] = None,
                         return_logprobs: bool = False, prompt: Optional[Sequence[int]] = None, logit_bias=None,
                         share_prompt: bool = False, grammar=None, harmony=None, class_sampling=None, note_order=None,
-                        voices=None, density=None, interval=None, onsets=None, guide=None):
+                        voices=None, density=None, interval=None, onsets=None, guide=None, articulation=None):
         """Attempts of ONE request (the reference's `while idx != num_generate` loop, midi_inferrer.py:338-354, which tries
         one sequence after the other) decoded in up to `slots` parallel slots, CONTINUOUSLY: a slot whose sequence has
         ended is handed to `accept(sequence, report) -> bool` and re-armed with the next attempt while the other slots keep
@@ -3314,6 +3552,8 @@ class BatchedGenerator:
         (ForcedDecoder.set_onsets; the bar count is the forcing record's, the prompt's bars included).
         guide: None / False or ONE guide track in any form guide_template takes: one setting for every attempt of the request
         (ForcedDecoder.set_guide; likewise).
+        articulation: None / False or ONE articulation in any form articulation_template takes: one setting for every attempt
+        of the request (ForcedDecoder.set_articulation; likewise; hold_guide needs guide=).
         share_prompt (opt-in; also on with BatchedGenerator(shared_prompt=True) when a prompt is given): the K/V of the
         context and the prompt are computed and held once for all slots (ForcedDecoder(shared_prompt=True)); the attempts
         returned are the ones the unshared decoder defines, up to the summation order of the attention."""
@@ -3339,6 +3579,9 @@ class BatchedGenerator:
         if isinstance(guide, list):
             raise CommuHipError(f"guide: one setting for the request expected, got a list of {len(guide)}")
         one_guide = None if (guide is None or guide is False) else guide_template(guide)      # (likewise)
+        if isinstance(articulation, list):
+            raise CommuHipError(f"articulation: one setting for the request expected, got a list of {len(articulation)}")
+        one_art = None if (articulation is None or articulation is False) else articulation_template(articulation)
         max_chords = len(input_data.chord_token_components["chord_token"])
         # each control's schedule, validated on its own (the three may have different lengths)
         n_of = lambda x: 1 if np.ndim(x) == 0 else len(x)
@@ -3353,7 +3596,7 @@ class BatchedGenerator:
                            per_slot=return_logprobs or varying, max_prompt=0 if prompt is None else len(prompt),
                            logit_bias=logit_bias, shared=share, grammar=grammar, harmony=harmony,
                            class_sampling=class_sampling, note_order=note_order, voices=voices, density=density,
-                           interval=interval, onsets=one_onsets, guide=one_guide)
+                           interval=interval, onsets=one_onsets, guide=one_guide, articulation=one_art)
         started = B
         sampled = bool((sched[0] != 0).any()) or dec.class_samples()          # (a greedy attempt reads no variate)
         uni = np.stack([self.attempt_uniforms(seed, a, dec.ld_u) for a in range(B)]) if sampled else None
@@ -3512,7 +3755,7 @@ class BatchedGenerator:
         harm_table = _harmony_request(self._one_harmony(harmony))
         cls_table = _class_request(class_sampling)
         # each request's controls, validated before anything is built
-        triples, biases, orders, voxes, dens, mels, onss, gdes = [], [], [], [], [], [], [], []
+        triples, biases, orders, voxes, dens, mels, onss, gdes, arts = [], [], [], [], [], [], [], [], []
         for i, r in enumerate(requests):
             t, k, p = sampling_rows(1, r.temperature, r.top_k, r.top_p)
             triples.append((t[0].item(), int(k[0]), p[0].item()))
@@ -3524,6 +3767,9 @@ class BatchedGenerator:
             onss.append(None if (r.onsets is None or r.onsets is False) else onset_rows(r.onsets))
             try:
                 gdes.append(None if (r.guide is None or r.guide is False) else guide_template(r.guide))
+                arts.append(None if (r.articulation is None or r.articulation is False)
+                            else articulation_template(r.articulation))
+                _articulation_needs_guide(arts[-1:], gdes[-1:])
             except CommuHipError as e:
                 raise CommuHipError(f"request {i}: {e}") from None
         B = max(1, min(slots, sum(int(r.need) for r in requests)))
@@ -3552,7 +3798,8 @@ class BatchedGenerator:
         use_den = any(d != DENSITY_OFF for d in dens)          # (the density rides on the voice words and the note order)
         use_mel = any(m != INTERVAL_OFF for m in mels)         # (the interval kernel reads all three words, on or off)
         use_ons = any(t is not None for t in onss)             # (the onsets kernel reads all four words, on or off)
-        use_gde = any(t is not None for t in gdes)             # (the guide kernel reads all five, on or off)
+        use_art = any(t is not None for t in arts)             # (the articulation kernel reads all six, on or off)
+        use_gde = any(t is not None for t in gdes) or use_art  # (the guide kernel reads all five, on or off)
         use_ons = use_ons or use_gde
         use_mel = use_mel or use_ons
         use_order = any(o != NOTE_ORDER_OFF for o in orders) or any(v != VOICES_OFF for v in voxes) or use_den or use_mel
@@ -3571,6 +3818,9 @@ class BatchedGenerator:
         if use_gde:
             dec._first_use(guide=True)
             dec._guide_pack(gdes, fresh=True)
+        if use_art:
+            dec._first_use(articulation=True)
+            dec._art_pack(arts, fresh=True)
         if any(b is not None for b in biases):
             dec._first_use(bias=True)
         klen0_max = max([n_cond] + [p["klen0"] for p in replays if p is not None])
@@ -3595,7 +3845,7 @@ class BatchedGenerator:
                               harmony=(harm_table is not None) if r.harmony is None else bool(r.harmony),
                               note_order=orders[j.request], voices=voxes[j.request], class_table=cls_table,
                               primed=replays[j.request], density=dens[j.request], interval=mels[j.request],
-                              onsets=onss[j.request], guide=gdes[j.request])
+                              onsets=onss[j.request], guide=gdes[j.request], articulation=arts[j.request])
                 sampled = triples[j.request][0] != 0 or cls_samples          # (a greedy attempt reads no variate)
                 staged.append((j.slot, j.entry, self.attempt_uniforms(r.seed, j.attempt, dec.ld_u) if sampled else None))
                 if held[j.slot] is not None and held[j.slot] != j.request:

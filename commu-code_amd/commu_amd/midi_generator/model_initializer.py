@@ -97,6 +97,10 @@ class ModelInitializeTask:
         # check_guide)
         if getattr(self.model_args, "guide_doc", None) is not None:
             cfg.GENERATION.guide = str(self.model_args.guide_doc)
+        # generate.py --articulation (not in the reference): the articulation as the JSON text of its full form (generate.py
+        # check_articulation)
+        if getattr(self.model_args, "articulation_doc", None) is not None:
+            cfg.GENERATION.articulation = str(self.model_args.articulation_doc)
         # generate.py --decode_slots (not in the reference): attempts decoded side by side (64 unless the key is set)
         if getattr(self.model_args, "decode_slots", None) not in (None, 64):
             cfg.GENERATION.decode_slots = int(self.model_args.decode_slots)

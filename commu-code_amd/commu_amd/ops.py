@@ -934,7 +934,7 @@ def _check_draw_state(kind, device, specs):
 
 def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=None, token=None, probs_out=None,
                 top_p=1.0, logp_out=None, bias=None, V=729, grammar=None, harmony=None, class_ctl=None,
-                note_order=None, voices=None, density=None, interval=None, onsets=None, guide=None):
+                note_order=None, voices=None, density=None, interval=None, onsets=None, guide=None, articulation=None):
     """In-place temperature + softmax + top-k + wrong-token mask + inverse-CDF draw per sequence.
     logits: fp32 [nseq, >=V] (row stride = ld), modified in place (logits[:, 1:V] /= temperature).
     top_p < 1: nucleus filter after the top-k / rejected-token step (an extra mode; the reference has top-k only).
@@ -1001,7 +1001,17 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
     bit is clear is banned; every position id whose bit in the live row is clear is banned, and the density waiver sees the
     onset row ANDed with the live row.  Row indices are clamped into the table.  One kernel serves it, the onsets kernel's
     with the two rows: onsets= is required -- pass all -1 onset words over a one-row all-ones table where there is no
-    template (commu_sample_args.guide_ctl / guide_table / guide_rows)."""
+    template (commu_sample_args.guide_ctl / guide_table / guide_rows).
+    articulation: (words, table) on the device of the logits -- words int32 [nseq], one control word per sequence: -1 off,
+    else base + 4096 R + 2^19 w + 2^20 h (generate.articulation_word); table int32 [rows, 4] contiguous, 1 <= rows <= 4096,
+    the bit patterns of the uint32 articulation rows (generate.articulation_rows): word 0 dlo | dhi << 8, words 1 and 2 the
+    64-bit velocity mask (bit k: id 131 + k), word 3 reserved.  The row of the open bar is base + (max(nb - 1, 0) mod R);
+    every velocity id whose bit is clear is banned, and of the duration ids 304 .. 431 those outside the window lo .. cap
+    steps: cap is 128, dhi where set, 128 - a under w (a the step of the last BAR-or-POSITION token of seq, a POSITION) and,
+    under h with the sequence's guide word on and the previous token a pitch, the first step ahead whose guide cell bans
+    that pitch; lo = min(max(dlo, 1), cap).  Row indices are clamped into the tables.  One kernel serves it, the guide
+    kernel's with the row and the hold term: guide= is required -- pass all -1 guide words over a one-row table where
+    there is no guide (commu_sample_args.art_ctl / art_table / art_rows)."""
     nseq = logits.shape[0]
     V = int(V)
     assert logits.dtype == F32 and logits.stride(1) == 1
@@ -1103,6 +1113,18 @@ def sample_topk(logits, temperature, top_k, wrong=None, uniforms=None, active=No
             (gtable, "table", torch.int32, "[1 .. 65536, 4]",
              lambda t: t.dim() == 2 and 1 <= t.shape[0] <= 65536 and t.shape[1] == 4)))
         a.guide_ctl, a.guide_table, a.guide_rows = _p(gwords), _p(gtable), int(gtable.shape[0])
+    if articulation is not None:
+        if guide is None:
+            raise CommuHipError("articulation: guide= expected as well (the one kernel is the guide kernel's with the row and "
+                                "the hold term; pass words that are all -1 over a one-row table where there is no guide)")
+        if not isinstance(articulation, (tuple, list)) or len(articulation) != 2:
+            raise CommuHipError("articulation: a pair (control words int32 [nseq], table int32 [rows, 4]) expected")
+        awords, atable = articulation
+        _check_draw_state("articulation", logits.device, (
+            (awords, "controls", torch.int32, "[%d]" % nseq, lambda t: tuple(t.shape) == (nseq,)),
+            (atable, "table", torch.int32, "[1 .. 4096, 4]",
+             lambda t: t.dim() == 2 and 1 <= t.shape[0] <= 4096 and t.shape[1] == 4)))
+        a.art_ctl, a.art_table, a.art_rows = _p(awords), _p(atable), int(atable.shape[0])
     if harmony is not None:
         htable, hon, hstate, chord_tok = harmony
         _check_draw_state("harmony", logits.device, (

@@ -79,6 +79,7 @@ __global__ __launch_bounds__(64) void decode_arm_kernel(const commu_decode_arm_a
         if (a.interval_ctl != nullptr && a.e_interval != nullptr) a.interval_ctl[slot] = a.e_interval[entry];
         if (a.onset_ctl != nullptr && a.e_onset != nullptr) a.onset_ctl[slot] = a.e_onset[entry];
         if (a.guide_ctl != nullptr && a.e_guide != nullptr) a.guide_ctl[slot] = a.e_guide[entry];
+        if (a.art_ctl != nullptr && a.e_art != nullptr) a.art_ctl[slot] = a.e_art[entry];
     }
 }
 

@@ -294,8 +294,54 @@ struct Guide {
     int rows;               // 1 .. 65536 (the entry points refuse anything else)
 };
 constexpr int GDE_ROWS_MAX = 65536, GDE_CYCLE_MAX = 64;
+// ART (Articulation: one int32 control per sequence, -1 off, else base + 4096 R + 2^19 w + 2^20 h with R in 1 .. 64 the
+//   cycle length in bars, base in 0 .. 4095, base + R <= rows, w the bar-line switch and h the guide-hold switch; table
+//   uint32 [rows][4], 1 <= rows <= 4096): HOW LONG a note lasts and HOW LOUD it is.  A row is one bar of a template: word 0
+//   is dlo | dhi << 8, each 0 .. 128 (0: that bound is not set); words 1 and 2 a 64-bit mask over velocities (bit k % 32 of
+//   word 1 + k / 32 set: VELOCITY id 131 + k may be drawn); word 3 is reserved, written 0 by the host and never read.
+//   THE ROW OF THE OPEN BAR mirrors ONS: i = max(nb - 1, 0) with nb the record's F_NBAR (never counted on a draw, a prompt's
+//   bars included), row = base + (i mod R), clamped to rows - 1 whatever the arrays hold.
+//   VELOCITY BAN: every VELOCITY id 131 .. 194 whose bit is clear is banned; ids 130 and 195 are never touched.
+//   DURATION WINDOW: j and p are ORD's; a = p - 432 exists when S[j] is a POSITION; k = q - 3 exists when q, the grammar's
+//   previous token, is a PITCH.  cap = 128, lowered to dhi when dhi >= 1, to 128 - a when w is set and a exists (the note
+//   ends by the bar line), and to f when h is set, the sequence's GUIDE word is on and a and k exist: f the smallest m in
+//   1 .. 127 such that bit k of the guide's cell row for step a + m is clear (none: the term does not apply).  The cell row
+//   of step a + m < 128 is block_i + 1 + ((a + m) >> s), of a later step block_{i+1} + 1 + ((a + m - 128) >> s), with
+//   block_x = base_g + (x mod R_g) (1 + C) read off the guide word and every row index clamped to the guide's rows - 1.
+//   lo = min(max(dlo, 1), cap); banned are DURATION ids 304 .. 303 + lo - 1 and 304 + cap .. 431.  The window is never empty
+//   (a <= 127, f >= 1): where the bar line or the guide leaves less room than dlo the lower bound gives way.  Ids 303 and
+//   432 are never touched; step a itself is not tested (that is GDE's pitch ban).
+//   The bans apply whatever class is drawn and join the one select of ORD .. GDE, so a draw is bit for bit the GDE kernel's
+//   with bias[b] = -inf at these ids; an off word, or a word over a row with dlo = dhi = 0, an all-ones velocity mask and
+//   w = h = 0, is bit for bit the GDE kernel.
+//   THE LOADS: the row is one wave-uniform 16-byte load whose address needs the record and the control word only; it goes
+//   out beside the onset row's and the guide's live row, ahead of the chain.  THE HOLD TERM is the new work: lane l tests
+//   m = 1 + l and m = 65 + l (m = 128 is masked out); for each it computes the clamped cell-row index and loads the ONE word
+//   table[4 row + (k >> 5)] -- two per-lane vector loads, not a row: the 127 steps ahead touch up to 127 rows of 16 bytes,
+//   and a lane needs one bit of each.  The addresses need p (the first ballot of the scan) and the previous token, so the
+//   loads go out where the guide's cell row does: behind chunk 0 for a normal bar, behind the chunk loop otherwise (that
+//   branch is wave-uniform already).  Two ballots of "clear" give f: the lowest set lane of the first, else 64 + that of the
+//   second.  An off word, an off guide word, no a or no k reads row 0 and selects "none clear": no branch on the switches.
+//   dlo, dhi, w, h, a, k, f, cap and lo stay in scalar registers; the velocity bits of a lane come from the 64-bit shift ONS
+//   and GDE use (ids 131 .. 194 are lanes 10 .. 16, 12 bits span at most two words; lane 10's start bit is negative and it
+//   shifts from bit 0 and moves the result up, as GDE's lane 0 does); the duration window is two bit ranges per lane, built
+//   like the position range.  No LDS, no scratch.  (As compiled the row is scalar loads in the stand-alone kernel and one
+//   uniform-address global_load_dwordx3 in the fused loop kernel, as the onset and guide rows are there; the hold term is
+//   four global_load_dword, two at each of its two places: docs/EXPERIMENTS.md 9d.)
+//   THE OTHER DESIGN -- a run-length table precomputed on the host, indexed by bar, cell and pitch, so that f is one load --
+//   costs 1 MB per 64-bar template and a repack on every change of the guide; it was not built.
+//   NOT COVERED: forced tokens and anything a forced position starts; notes inside a prompt; a note forced shorter than dlo
+//   (above); an empty velocity mask ends the attempt by Q12, as before (the host refuses to build one); the hold term reads
+//   the next bar's block even where the generation length would cut the sequence first; the hold term tests the guide only
+//   (harmony across a chord change is not tested).  ART needs GDE.
+struct Articulation {
+    int ctl;                // the sequence's control as the caller loaded it
+    const unsigned* table;  // uint32 [rows][4]
+    int rows;               // 1 .. 4096 (the entry points refuse anything else)
+};
+constexpr int ART_ROWS_MAX = 4096, ART_CYCLE_MAX = 64;
 template <bool BIAS, bool GRAM = false, bool HARM = false, bool CLS = false, bool ORD = false, bool VOX = false,
-          bool DEN = false, bool MEL = false, bool ONS = false, bool GDE = false>
+          bool DEN = false, bool MEL = false, bool ONS = false, bool GDE = false, bool ART = false>
 __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restrict__ logits, int ld, int V,
                                                  const unsigned char* __restrict__ wrong, int ldw,
                                                  const float* __restrict__ uni,
@@ -310,7 +356,8 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
                                                  NoteOrder no = NoteOrder{-1}, Voices vx = Voices{-1},
                                                  Density dn = Density{-1}, Interval ml = Interval{-1},
                                                  Onsets os = Onsets{-1, nullptr, 1, 0},
-                                                 Guide gd = Guide{-1, nullptr, 1}) {
+                                                 Guide gd = Guide{-1, nullptr, 1},
+                                                 Articulation ar = Articulation{-1, nullptr, 1}) {
     static_assert(!CLS || GRAM, "the class key is the grammar's previous token");
     static_assert(!ORD || CLS, "one note-order instantiation: the class kernel's with the scan");
     static_assert(!VOX || ORD, "one voices instantiation: the note-order kernel's with the longer scan");
@@ -318,6 +365,7 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
     static_assert(!MEL || DEN, "one interval instantiation: the density kernel's with the reference note");
     static_assert(!ONS || MEL, "one onsets instantiation: the interval kernel's with the template row");
     static_assert(!GDE || ONS, "one guide instantiation: the onsets kernel's with the live row and the cell row");
+    static_assert(!ART || GDE, "one articulation instantiation: the guide kernel's with the row and the hold term");
     float* lg = logits + (size_t)b * ld;
     // The optional per-sequence inputs -- the active flag and this sequence's controls -- are loaded unconditionally: a null
     // array reads a valid word of this sequence instead (token[b], logits[b][0]), which is then ignored.  So they are in
@@ -397,6 +445,28 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
         or2 &= gctl >= 0 ? w2 : ~0u;
         or3 &= gctl >= 0 ? w3 : ~0u;
     }
+    // (ART) the open bar's articulation row: once more the address needs the record and the control word only, so the one
+    // uniform 16-byte load goes out beside the two above (word 3 is reserved and not looked at); an off word reads row 0 and
+    // selects no bounds, the all-ones velocity mask and both switches off.  The guide's block of the NEXT bar, which the hold
+    // term looks into, is worked out here from the guide word as well.
+    int adlo = 0, adhi = 0, abarline = 0, ahold = 0, gblock1 = 0;
+    unsigned av0 = ~0u, av1 = ~0u;
+    if constexpr (ART) {
+        const int actl = __builtin_amdgcn_readfirstlane(ar.ctl);
+        const int abar = max(__builtin_amdgcn_readfirstlane(os.nbar) - 1, 0);
+        const int acyc = min(max((actl >> 12) & 127, 1), ART_CYCLE_MAX);
+        const int arow = min(max((actl & (ART_ROWS_MAX - 1)) + abar % acyc, 0), ar.rows - 1);
+        const unsigned* aw = ar.table + 4 * (size_t)__builtin_amdgcn_readfirstlane(actl >= 0 ? arow : 0);
+        const unsigned w0 = aw[0], w1 = aw[1], w2 = aw[2];
+        adlo = actl >= 0 ? (int)(w0 & 255u) : 0;
+        adhi = actl >= 0 ? (int)((w0 >> 8) & 255u) : 0;
+        av0 = actl >= 0 ? w1 : ~0u;
+        av1 = actl >= 0 ? w2 : ~0u;
+        abarline = actl >= 0 ? ((actl >> 19) & 1) : 0;
+        ahold = (actl >= 0 && gctl >= 0) ? ((actl >> 20) & 1) : 0;
+        const int gcyc = min(max((gctl >> 16) & 127, 1), GDE_CYCLE_MAX);
+        gblock1 = (gctl & (GDE_ROWS_MAX - 1)) + ((abar + 1) % gcyc) * (1 + (POS_RES >> gshift));
+    }
     // (HARM) the 12 pitch-class values of the chord's row, the same for every lane: element e of a lane is id 12 l + e,
     // MIDI pitch 12 l + e - 3, pitch class (e + 9) mod 12
     float hv[PER_LANE];
@@ -449,6 +519,8 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
         int mq = 0;                             // (MEL) the reference note's PITCH token, once found
         bool mfound = false;
         unsigned gc0 = ~0u, gc1 = ~0u, gc2 = ~0u, gc3 = ~0u;          // (GDE) the cell row's four words, once loaded
+        unsigned hw0 = ~0u, hw1 = ~0u;          // (ART) the lane's two words of the hold term, once loaded
+        bool hon = false;                       // (ART) the hold term applies: h, the guide word on, a and k exist
         if constexpr (VOX) {
             static_assert(VOX_BINS == 2 * 64, "two bins per lane");
             __shared__ __attribute__((aligned(16))) int vflag_lds[ORD_FLAGS];
@@ -536,10 +608,28 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
                 gc2 = gon ? w2 : ~0u;
                 gc3 = gon ? w3 : ~0u;
             };
+            // (ART) the hold term's two words per lane: bit k of the guide's cell rows for the steps a + 1 + l and
+            // a + 65 + l, the second bar's block past step 127.  The addresses need p and the previous token, so the two
+            // vector loads go out with the cell row's.  Off, no a or no k: row 0, word 0, and "none clear" is selected below.
+            const auto ghold = [&]() {
+                const int hstep = min(max(pos - TOK_POS0, 0), POS_RES - 1), hk = min(max(prev - TOK_PITCH_LO, 0), 127);
+                hon = ahold != 0 && phase != 0 && pos != TOK_BAR &&
+                      (unsigned)(prev - TOK_PITCH_LO) <= (unsigned)(TOK_PITCH_HI - TOK_PITCH_LO);
+                const auto word_of = [&](int m) {
+                    const int t = hstep + m;          // (1 .. 254)
+                    const int r = t < POS_RES ? gblock + 1 + (t >> gshift) : gblock1 + 1 + ((t - POS_RES) >> gshift);
+                    return gd.table[hon ? 4 * (size_t)min(max(r, 0), gd.rows - 1) + (hk >> 5) : 0];
+                };
+                hw0 = word_of(1 + lane);
+                hw1 = word_of(65 + lane);
+            };
             bool gearly = false;
             if constexpr (GDE) {
                 gearly = phase != 0;
-                if (gearly) gcell();
+                if (gearly) {
+                    gcell();
+                    if constexpr (ART) ghold();
+                }
             }
             // (the run is complete at the first BAR from the end at the latest: the second BAR, or index 0, ends both)
 #pragma unroll 1
@@ -547,7 +637,10 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
                 chunk(g.seq_row[max(start - lane, 0)], g.seq_row[max(start - lane - 1, 0)],
                       g.seq_row[max(start - lane - 2, 0)], g.seq_row[max(start - lane - 3, 0)]);
             if constexpr (GDE) {
-                if (!gearly) gcell();
+                if (!gearly) {
+                    gcell();
+                    if constexpr (ART) ghold();
+                }
             }
         } else {
             chunk(otok);
@@ -649,6 +742,33 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
             const unsigned may = (unsigned)(((((unsigned long long)whi) << 32) | wlo) >> (kk & 31)) << (kk - k0);
             const int p0 = min(max(TOK_PITCH_LO - base, 0), PER_LANE), p1 = min(max(TOK_PITCH_HI + 1 - base, 0), PER_LANE);
             omask |= ~may & (((1u << p1) - 1u) & ~((1u << p0) - 1u));
+        }
+        if constexpr (ART) {
+            // the hold term: lane l holds the steps m = 1 + l and m = 65 + l (lane 63's second is m = 128, masked out); f is
+            // the lowest clear one, 128 where none is -- which lowers no cap
+            const int hb = min(max(prev - TOK_PITCH_LO, 0), 127) & 31;
+            const unsigned long long c0 = __ballot(hon & (((hw0 >> hb) & 1u) == 0u));
+            const unsigned long long c1 = __ballot(hon & (((hw1 >> hb) & 1u) == 0u)) & ~(1ull << 63);
+            const int f = c0 != 0ull ? 1 + __builtin_ctzll(c0) : (c1 != 0ull ? 65 + __builtin_ctzll(c1) : POS_RES);
+            const bool aex = phase != 0 && pos != TOK_BAR;
+            int cap = adhi >= 1 ? min(adhi, POS_RES) : POS_RES;
+            cap = (abarline != 0 && aex) ? min(cap, POS_RES - min(max(pos - TOK_POS0, 0), POS_RES - 1)) : cap;
+            cap = min(cap, f);
+            const int dlo1 = min(max(adlo, 1), cap);
+            // DURATION ids [304, 303 + lo) and [304 + cap, 432) are banned: two bit ranges per lane
+            const int s0 = min(max(TOK_DUR_LO - base, 0), PER_LANE), s1 = min(max(TOK_DUR_LO - 1 + dlo1 - base, 0), PER_LANE);
+            const int l0 = min(max(TOK_DUR_LO + cap - base, 0), PER_LANE), l1 = min(max(TOK_DUR_HI + 1 - base, 0), PER_LANE);
+            omask |= ((1u << s1) - 1u) & ~((1u << s0) - 1u);
+            omask |= ((1u << l1) - 1u) & ~((1u << l0) - 1u);
+            // the lane's 12 bits of the velocity mask start at bit k0 = base - 131 (lanes 10 .. 16: -11, 1, .. 61) and span at
+            // most two words; lane 10 shifts from bit 0 and moves the result up by 11 -- ids 120 .. 130 are outside the range
+            // below -- and lane 16's bits past 63 (ids 195 ..) are outside it too
+            const int k0 = base - TOK_VEL_LO, kk = min(max(k0, 0), 63);
+            const unsigned wlo = (kk >> 5) == 0 ? av0 : av1;
+            const unsigned whi = (kk >> 5) == 0 ? av1 : 0u;
+            const unsigned may = (unsigned)(((((unsigned long long)whi) << 32) | wlo) >> (kk & 31)) << min(max(kk - k0, 0), 31);
+            const int v0 = min(max(TOK_VEL_LO - base, 0), PER_LANE), v1 = min(max(TOK_VEL_HI + 1 - base, 0), PER_LANE);
+            omask |= ~may & (((1u << v1) - 1u) & ~((1u << v0) - 1u));
         }
     }
     if (active != nullptr && act_row == 0) return -2;

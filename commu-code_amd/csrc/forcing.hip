@@ -109,31 +109,40 @@ struct LoopStageArgsGde : LoopStageArgsOns {
     const unsigned* guide_table;
     int guide_rows;
 };
+// (ART) the articulation control words [B], the articulation table [art_rows][4] and its row count (decode_loop.h:
+// Articulation): arguments of the articulation kernel only
+struct LoopStageArgsArt : LoopStageArgsGde {
+    const int* art_ctl;
+    const unsigned* art_table;
+    int art_rows;
+};
 template <bool GRAM, bool HARM = false, bool CLS = false, bool ORD = false, bool VOX = false, bool DEN = false,
-          bool MEL = false, bool ONS = false, bool GDE = false>
+          bool MEL = false, bool ONS = false, bool GDE = false, bool ART = false>
 struct LoopArgsOf { using type = LoopStageArgs; };
 template <>
-struct LoopArgsOf<true, false, false, false, false, false, false, false, false> { using type = LoopStageArgsGram; };
+struct LoopArgsOf<true, false, false, false, false, false, false, false, false, false> { using type = LoopStageArgsGram; };
 template <>
-struct LoopArgsOf<true, true, false, false, false, false, false, false, false> { using type = LoopStageArgsHarm; };
+struct LoopArgsOf<true, true, false, false, false, false, false, false, false, false> { using type = LoopStageArgsHarm; };
 template <>
-struct LoopArgsOf<true, true, true, false, false, false, false, false, false> { using type = LoopStageArgsCls; };
+struct LoopArgsOf<true, true, true, false, false, false, false, false, false, false> { using type = LoopStageArgsCls; };
 template <>
-struct LoopArgsOf<true, true, true, true, false, false, false, false, false> { using type = LoopStageArgsOrd; };
+struct LoopArgsOf<true, true, true, true, false, false, false, false, false, false> { using type = LoopStageArgsOrd; };
 template <>
-struct LoopArgsOf<true, true, true, true, true, false, false, false, false> { using type = LoopStageArgsVox; };
+struct LoopArgsOf<true, true, true, true, true, false, false, false, false, false> { using type = LoopStageArgsVox; };
 template <>
-struct LoopArgsOf<true, true, true, true, true, true, false, false, false> { using type = LoopStageArgsDen; };
+struct LoopArgsOf<true, true, true, true, true, true, false, false, false, false> { using type = LoopStageArgsDen; };
 template <>
-struct LoopArgsOf<true, true, true, true, true, true, true, false, false> { using type = LoopStageArgsMel; };
+struct LoopArgsOf<true, true, true, true, true, true, true, false, false, false> { using type = LoopStageArgsMel; };
 template <>
-struct LoopArgsOf<true, true, true, true, true, true, true, true, false> { using type = LoopStageArgsOns; };
+struct LoopArgsOf<true, true, true, true, true, true, true, true, false, false> { using type = LoopStageArgsOns; };
 template <>
-struct LoopArgsOf<true, true, true, true, true, true, true, true, true> { using type = LoopStageArgsGde; };
+struct LoopArgsOf<true, true, true, true, true, true, true, true, true, false> { using type = LoopStageArgsGde; };
+template <>
+struct LoopArgsOf<true, true, true, true, true, true, true, true, true, true> { using type = LoopStageArgsArt; };
 template <bool BIAS, bool GRAM, bool HARM = false, bool CLS = false, bool ORD = false, bool VOX = false, bool DEN = false,
-          bool MEL = false, bool ONS = false, bool GDE = false>
+          bool MEL = false, bool ONS = false, bool GDE = false, bool ART = false>
 __global__ __launch_bounds__(64) void sample_post_pre_kernel(
-    typename LoopArgsOf<GRAM, HARM, CLS, ORD, VOX, DEN, MEL, ONS, GDE>::type a) {
+    typename LoopArgsOf<GRAM, HARM, CLS, ORD, VOX, DEN, MEL, ONS, GDE, ART>::type a) {
     const int b = blockIdx.x, lane = threadIdx.x;
     if (a.trace != nullptr && lane == 0) a.trace[b * 4 + 0] = wall_clock64();
     int rec[F_COUNT];                                  // the record travels through the three stages in lane 0's registers;
@@ -174,10 +183,12 @@ __global__ __launch_bounds__(64) void sample_post_pre_kernel(
                                                                                                    // is the record's)
     Guide gd{-1, nullptr, 1};
     if constexpr (GDE) gd = Guide{a.guide_ctl[b], a.guide_table, a.guide_rows};                    // (likewise)
-    const int drawn = sample_topk_body<BIAS, GRAM, HARM, CLS, ORD, VOX, DEN, MEL, ONS, GDE>(
+    Articulation ar{-1, nullptr, 1};
+    if constexpr (ART) ar = Articulation{a.art_ctl[b], a.art_table, a.art_rows};                   // (likewise)
+    const int drawn = sample_topk_body<BIAS, GRAM, HARM, CLS, ORD, VOX, DEN, MEL, ONS, GDE, ART>(
         b, lane, a.logits, a.ld, a.V, a.wrong, VOCAB, a.uni, a.draw, a.temperature, a.top_k, a.token, a.probs_out, a.ldp,
         a.top_p, a.rows, a.logp != nullptr || a.seq_logp != nullptr, a.logp, lp, a.bias, a.ld_bias, g, h, cc, no, vx, dn, ml,
-        os, gd);
+        os, gd, ar);
     __syncthreads();
     if (a.trace != nullptr && lane == 0) a.trace[b * 4 + 1] = wall_clock64();
     forcing_post_body(b, lane, rec, a.seq, a.ld_seq, a.chord_pos, a.ld_chord, a.wrong, a.draw, a.token, nullptr, a.klen,
@@ -382,7 +393,12 @@ extern "C" int commu_decode_sample_post_pre(const commu_decode_loop_args* p, hip
     if (p->guide_ctl != nullptr && (p->onset_ctl == nullptr || p->guide_table == nullptr || p->guide_rows < 1 ||
                                     p->guide_rows > GDE_ROWS_MAX))
         return -22;
-    LoopStageArgsGde a;
+    // (the kernel reads art_ctl[b], one row of art_table, its index clamped into the table, and up to two words per lane of
+    // guide_table, their row indices clamped likewise; one instantiation)
+    if (p->art_ctl != nullptr && (p->guide_ctl == nullptr || p->art_table == nullptr || p->art_rows < 1 ||
+                                  p->art_rows > ART_ROWS_MAX))
+        return -22;
+    LoopStageArgsArt a;
     static_cast<LoopStageArgs&>(a) = LoopStageArgs{
         p->logits, p->ld, V, p->wrong, p->temperature, p->top_k, p->top_p,
         SamplingRows{p->temperature_rows, p->top_k_rows, p->top_p_rows}, p->token, p->probs_out, p->ldp, p->logp, p->seq_logp,
@@ -401,6 +417,10 @@ extern "C" int commu_decode_sample_post_pre(const commu_decode_loop_args* p, hip
     a.guide_ctl = p->guide_ctl;
     a.guide_table = p->guide_table;
     a.guide_rows = p->guide_rows;
+    a.art_ctl = p->art_ctl;
+    a.art_table = p->art_table;
+    a.art_rows = p->art_rows;
+    const LoopStageArgsGde& agd = a;
     const LoopStageArgsOns& an = a;
     const LoopStageArgsMel& am = a;
     const LoopStageArgsDen& ad = a;
@@ -414,10 +434,13 @@ extern "C" int commu_decode_sample_post_pre(const commu_decode_loop_args* p, hip
     // five kernels: without a bias / a grammar / a harmony table the launch is the one it always was (no added load, no
     // added register, no added argument); a sixth for the class-keyed controls, a seventh for the note order, an eighth
     // for the voice cap, a ninth for the note density, a tenth for the melodic interval, an eleventh for the onset templates,
-    // a twelfth for the guide track
-    if (p->guide_ctl != nullptr) {
+    // a twelfth for the guide track, a thirteenth for the articulation
+    if (p->art_ctl != nullptr) {
+        COMMU_LAUNCH((sample_post_pre_kernel<true, true, true, true, true, true, true, true, true, true, true>), grid, block,
+                     0, stream, a);
+    } else if (p->guide_ctl != nullptr) {
         COMMU_LAUNCH((sample_post_pre_kernel<true, true, true, true, true, true, true, true, true, true>), grid, block, 0,
-                     stream, a);
+                     stream, agd);
     } else if (p->onset_ctl != nullptr) {
         COMMU_LAUNCH((sample_post_pre_kernel<true, true, true, true, true, true, true, true, true>), grid, block, 0, stream,
                      an);

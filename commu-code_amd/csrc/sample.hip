@@ -368,6 +368,55 @@ __global__ __launch_bounds__(64) void sample_topk_gde_kernel(float* __restrict__
         logp_out != nullptr, logp_out, lp, bias, ld_bias, g, h, cc, no, vx, dn, ml, os, gd);
 }
 
+// the same with the articulation (Articulation): the guide kernel's arguments plus the articulation's control words, its
+// table and row count, a kernel of its own once more; the open bar's index is the record's F_NBAR, as for the onset row
+__global__ __launch_bounds__(64) void sample_topk_art_kernel(float* __restrict__ logits, int ld, int V,
+                                                             const unsigned char* __restrict__ wrong, int ldw,
+                                                             const float* __restrict__ uni,
+                                                             const unsigned char* __restrict__ active,
+                                                             float temperature, int top_k,
+                                                             int* __restrict__ token, float* __restrict__ probs_out,
+                                                             int ldp, float top_p, SamplingRows rows,
+                                                             float* __restrict__ logp_out,
+                                                             const float* __restrict__ bias, int ld_bias,
+                                                             const float* __restrict__ gram, int ld_gram,
+                                                             const unsigned char* __restrict__ gram_on,
+                                                             const int* __restrict__ state, const int* __restrict__ seq,
+                                                             int ld_seq, const float* __restrict__ harm, int ld_harm,
+                                                             const unsigned char* __restrict__ harm_on,
+                                                             const int* __restrict__ chord_tok, int ld_chord,
+                                                             const int4* __restrict__ cls_ctl,
+                                                             const int* __restrict__ order_ctl,
+                                                             const int* __restrict__ voice_ctl,
+                                                             const int* __restrict__ density_ctl,
+                                                             const int* __restrict__ interval_ctl,
+                                                             const int* __restrict__ onset_ctl,
+                                                             const unsigned* __restrict__ onset_table, int onset_rows,
+                                                             const int* __restrict__ guide_ctl,
+                                                             const unsigned* __restrict__ guide_table, int guide_rows,
+                                                             const int* __restrict__ art_ctl,
+                                                             const unsigned* __restrict__ art_table, int art_rows) {
+    TokenLogp lp;
+    const int b = blockIdx.x;
+    const unsigned char gon_b = *(gram_on != nullptr ? gram_on + b : reinterpret_cast<const unsigned char*>(token + b));
+    const unsigned char hon_b = *(harm_on != nullptr ? harm_on + b : reinterpret_cast<const unsigned char*>(token + b));
+    const Grammar g{gram, ld_gram, seq + (size_t)b * ld_seq, state[(size_t)b * F_COUNT + F_LEN], ld_seq,
+                    gram_on != nullptr ? (int)gon_b : 1};
+    const Harmony h{harm, ld_harm, chord_tok + (size_t)b * ld_chord, state[(size_t)b * F_COUNT + F_CUR], ld_chord,
+                    harm_on != nullptr ? (int)hon_b : 1};
+    const ClassControls cc{cls_ctl + (size_t)b * 8};
+    const NoteOrder no{order_ctl[b]};
+    const Voices vx{voice_ctl[b]};
+    const Density dn{density_ctl[b]};
+    const Interval ml{interval_ctl[b]};
+    const Onsets os{onset_ctl[b], onset_table, onset_rows, state[(size_t)b * F_COUNT + F_NBAR]};
+    const Guide gd{guide_ctl[b], guide_table, guide_rows};
+    const Articulation ar{art_ctl[b], art_table, art_rows};
+    sample_topk_body<true, true, true, true, true, true, true, true, true, true, true>(
+        b, threadIdx.x, logits, ld, V, wrong, ldw, uni, active, temperature, top_k, token, probs_out, ldp, top_p, rows,
+        logp_out != nullptr, logp_out, lp, bias, ld_bias, g, h, cc, no, vx, dn, ml, os, gd, ar);
+}
+
 }  // namespace
 
 extern "C" int commu_sample_args_bytes(void) { return (int)sizeof(commu_sample_args); }
@@ -419,6 +468,12 @@ extern "C" int commu_sample_topk(const commu_sample_args* a, hipStream_t stream)
     if (a->guide_ctl != nullptr && (a->onset_ctl == nullptr || a->guide_table == nullptr || a->guide_rows < 1 ||
                                     a->guide_rows > GDE_ROWS_MAX))
         return -22;
+    // (the kernel reads art_ctl[b], one row of art_table[0 .. art_rows - 1][0 .. 2], its index clamped into the table, and up
+    // to two words per lane of guide_table, their row indices clamped likewise; one instantiation, the guide kernel's with
+    // the row and the hold term)
+    if (a->art_ctl != nullptr && (a->guide_ctl == nullptr || a->art_table == nullptr || a->art_rows < 1 ||
+                                  a->art_rows > ART_ROWS_MAX))
+        return -22;
     const SamplingRows rows{a->temperature_rows, a->top_k_rows, a->top_p_rows};
     const dim3 grid(a->nseq), block(64);
     // every kernel's parameters begin with the same fifteen, then (bias, ld_bias), then what its constraints add
@@ -430,8 +485,13 @@ extern "C" int commu_sample_topk(const commu_sample_args* a, hipStream_t stream)
     // five kernels: without a bias / a grammar / a harmony table the launch is the one it always was (no added load, no
     // added register, no added argument); a sixth for the class-keyed controls, a seventh for the note order, an eighth
     // for the voice cap, a ninth for the note density, a tenth for the melodic interval, an eleventh for the onset templates,
-    // a twelfth for the guide track
-    if (a->guide_ctl != nullptr) {
+    // a twelfth for the guide track, a thirteenth for the articulation
+    if (a->art_ctl != nullptr) {
+        launch(sample_topk_art_kernel, a->bias, a->ld_bias, a->gram, a->ld_gram, a->gram_on, a->state, a->seq, a->ld_seq,
+               a->harm, a->ld_harm, a->harm_on, a->chord_tok, a->ld_chord, static_cast<const int4*>(a->cls_ctl),
+               a->order_ctl, a->voice_ctl, a->density_ctl, a->interval_ctl, a->onset_ctl, a->onset_table, a->onset_rows,
+               a->guide_ctl, a->guide_table, a->guide_rows, a->art_ctl, a->art_table, a->art_rows);
+    } else if (a->guide_ctl != nullptr) {
         launch(sample_topk_gde_kernel, a->bias, a->ld_bias, a->gram, a->ld_gram, a->gram_on, a->state, a->seq, a->ld_seq,
                a->harm, a->ld_harm, a->harm_on, a->chord_tok, a->ld_chord, static_cast<const int4*>(a->cls_ctl),
                a->order_ctl, a->voice_ctl, a->density_ctl, a->interval_ctl, a->onset_ctl, a->onset_table, a->onset_rows,

@@ -163,7 +163,7 @@ def parse_args():
     # pitches Y sound, x is allowed iff (x - y) mod 12 is in avoid_intervals for no y, x is not in Y (no_unison),
     # x <= min Y - m (below), x >= max Y + m (above); a silent step allows everything; a cell is the AND over its steps.
     # It implies none of the other constraints and needs no --grammar.  NOT covered: only a note's START is tested (a drawn
-    # note held across a later change of the guide is not checked), forced tokens (the position 0 after a Bar, a chord's
+    # note held across a later change of the guide is not checked; --articulation's hold_guide covers it), forced tokens (the position 0 after a Bar, a chord's
     # position), notes inside --prompt_tokens; a pitch range, strict --harmony or --max_leap window that together with the
     # cell leaves no pitch ends that attempt as before.  With --requests it holds for every request that does not carry a
     # "guide" of its own.
@@ -172,6 +172,24 @@ def parse_args():
                                        '{"cells": C, "bars": [[null | [pitches], ...], ...]} or {"from_tokens": [ids], '
                                        '"cells": 16, "avoid_intervals": [1, 11], "no_unison": false, "below": m | "above": m}'
                                        '.  Not covered: held notes, forced positions, notes inside --prompt_tokens')
+    # not in the reference (whose notes take whatever duration and velocity the model draws): --articulation SPEC -- a
+    # duration is DRAWN only inside a window of steps and a velocity only inside a range, per bar of a template.  SPEC is
+    # JSON text or a file holding it: the full form {"bars": [{"duration": [lo, hi], "velocity": [lo, hi]} | null, ...],
+    # "within_bar": bool, "hold_guide": bool} (at most 64 bars, cycled bar by bar; a null bar constrains nothing), or the short
+    # form with the single bar's keys at top level, e.g. {"duration": [2, 16], "hold_guide": true}.  duration is in steps
+    # 1 .. 128 and either end may be null; velocity is in MIDI 0 .. 127 and maps to the bins floor(lo / 2) .. ceil(hi / 2),
+    # capped at 63, as --min_velocity / --max_velocity do.  within_bar: a drawn note ends by the bar line.  hold_guide (needs
+    # --guide): a drawn note ends before the first step where the guide bans its pitch -- the guide's own rule tests a
+    # note's start only.  Where the bar line or the guide leaves less room than the lower bound, the lower bound gives way.
+    # It implies none of the other constraints and needs no --grammar.  NOT covered: forced tokens and anything a forced
+    # position starts, notes inside --prompt_tokens; hold_guide reads the next bar's cells even where --generation_length
+    # would cut the sequence first, and tests the guide only (--harmony across a chord change is not tested).  With
+    # --requests it holds for every request that does not carry an "articulation" of its own.
+    model_arg_parser.add_argument("--articulation", default=None, metavar="SPEC",
+                                  help='drawn durations and velocities follow a per-bar template: JSON text or file, '
+                                       '{"bars": [{"duration": [lo, hi], "velocity": [lo, hi]} | null, ...], "within_bar": '
+                                       'bool, "hold_guide": bool} or one bar\'s keys at top level.  Not covered: forced '
+                                       'tokens, notes inside --prompt_tokens')
     # not in the reference (which decodes one sequence at a time): how many attempts are decoded side by side.  1 .. 256;
     # up to 256 slots run the fused layer-tail launches ("Supported shapes").  The sequences returned do
     # not depend on it.  (checked by check_decode_slots: the range is named in its message)
@@ -315,7 +333,8 @@ REQUEST_KEYS = REQUEST_META_KEYS + ("num_generate", "top_k", "temperature", "top
 # (keys a request object may carry and that its parsed dict holds only then: prompt_tokens, the token ids it continues)
 # and onsets, its own onset template (--onsets' forms, as JSON values)
 # and guide, its own guide track (--guide's forms, as JSON values)
-REQUEST_OPTIONAL_KEYS = ("prompt_tokens", "onsets", "guide")
+# and articulation, its own articulation (--articulation's forms, as JSON values)
+REQUEST_OPTIONAL_KEYS = ("prompt_tokens", "onsets", "guide", "articulation")
 # (single-request input arguments that --requests replaces, with the value the parser gives them when they are not named)
 SINGLE_REQUEST_ARGS = {**{k: None for k in REQUEST_META_KEYS}, "genre": "cinematic", "rhythm": "standard",
                        "num_generate": None, "top_k": 32, "temperature": 0.95, "top_p": 1.0, "max_rounds": None,
@@ -382,8 +401,74 @@ def check_requests(model_args, input_args):
                 r = {**r, "guide": guide_doc(r["guide"], "guide", r.get("pitch_min"), r.get("pitch_max"))}
             except ValueError as e:
                 raise ValueError(f"--requests: {path}: request {i}: {e}") from None
+        if r.get("articulation") is not None:
+            try:
+                r = {**r, "articulation": articulation_doc(r["articulation"], "articulation")}
+            except ValueError as e:
+                raise ValueError(f"--requests: {path}: request {i}: {e}") from None
         out.append({**SINGLE_REQUEST_ARGS, "seed": 0, **r})
+    # (hold_guide reads the request's guide: its own, or the pool-wide one of --guide)
+    pool_art = check_articulation(model_args, needs_guide=False)
+    pool_art = None if pool_art is None else json.loads(pool_art)
+    for i, r in enumerate(out):
+        art = r.get("articulation") if r.get("articulation") is not None else pool_art
+        if art is not None and art["hold_guide"] and r.get("guide") is None and getattr(model_args, "guide", None) is None:
+            raise ValueError(f"--requests: {path}: request {i}: articulation: hold_guide without a guide (neither the "
+                             "request's own \"guide\" nor --guide)")
     return out
+
+
+def articulation_doc(doc, what="--articulation"):
+    """An articulation given as a JSON value -- the full form or the short form -- validated and returned as the full form
+    {"bars": [...], "within_bar": bool, "hold_guide": bool} with every bar written out ({"duration": [lo | null, hi | null],
+    "velocity": [lo, hi]} in MIDI velocities that map back to the same bins, null for a bar that constrains nothing).  Host
+    code only, ValueError that says what is wrong."""
+    from commu_amd.generate import CommuHipError, articulation_template
+    try:
+        rows, w, h = articulation_template(doc)
+    except CommuHipError as e:
+        raise ValueError(f"{what}: {str(e).removeprefix('articulation: ')}") from None
+    bars = []
+    for r in rows:
+        dlo, dhi = int(r[0]) & 255, (int(r[0]) >> 8) & 255
+        mask = int(r[1]) | int(r[2]) << 32
+        if dlo == 0 and dhi == 0 and mask == (1 << 64) - 1:
+            bars.append(None)
+            continue
+        b0, b1 = (mask & -mask).bit_length() - 1, mask.bit_length() - 1
+        bars.append({"duration": [dlo or None, dhi or None], "velocity": [2 * b0, min(2 * b1, 127)]})
+    return {"bars": bars, "within_bar": w, "hold_guide": h}
+
+
+def check_articulation(model_args, needs_guide=True):
+    """--articulation as the JSON text of the articulation's full form (None without the flag): the value is the JSON
+    document itself or the path of a file that holds it.  Host code only, run before a model is loaded; ValueError that says
+    what is wrong -- hold_guide without --guide among it (needs_guide; with --requests a request's own guide will do, and
+    check_requests tests it).  Written back to model_args.articulation_doc, which travels to the replicas
+    (ModelInitializeTask puts it into the inference configuration).  It switches nothing else on."""
+    setting = getattr(model_args, "articulation", None)
+    model_args.articulation_doc = None
+    if setting is None:
+        return None
+    text = setting
+    if not isinstance(setting, str):
+        raise ValueError(f"--articulation: JSON text or a readable JSON file expected, got {setting!r}")
+    if not setting.lstrip().startswith(("{", "[")):
+        try:
+            with open(setting) as f:
+                text = f.read()
+        except OSError as e:
+            raise ValueError(f"--articulation: JSON text or a readable JSON file expected, got {setting!r} "
+                             f"({e.strerror})") from None
+    try:
+        doc = json.loads(text)
+    except json.JSONDecodeError as e:
+        raise ValueError(f"--articulation: not JSON ({e})") from None
+    out = articulation_doc(doc, "--articulation")
+    if needs_guide and out["hold_guide"] and getattr(model_args, "guide", None) is None:
+        raise ValueError("--articulation: hold_guide without --guide: it ends a note where the guide bans its pitch")
+    model_args.articulation_doc = json.dumps(out)
+    return model_args.articulation_doc
 
 
 def guide_doc(doc, what="--guide", pitch_min=None, pitch_max=None):
@@ -650,6 +735,7 @@ def main(model_args, input_args, training_cfg=None, device_indices=None):
     check_interval(model_args)                          # (likewise)
     check_onsets(model_args)                            # (likewise)
     check_guide(model_args, input_args)                 # (likewise)
+    check_articulation(model_args, needs_guide=requests is None)      # (likewise)
     check_note_order(model_args)                        # (likewise)
     in_args = dict(vars(input_args))
     in_args.pop("requests", None)

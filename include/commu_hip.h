@@ -608,6 +608,42 @@ int commu_transpose_heads(const void* src, int ld, const float* bias, void* dst,
  *     guide_table and 1 <= guide_rows <= 65536, else -22.  Validating the words is the caller's job (generate.guide_rows /
  *     ForcedDecoder.set_guide).  The same three fields, with the same meaning and the same refusals, are in
  *     commu_decode_loop_args.  Null guide_ctl: the launch that never heard of it.
+ *     With art_ctl's h switch (below) a note's held steps are tested against the guide as well.
+ * ARTICULATION (a note is the group Position, Velocity, Pitch, Duration; the rules above decide when it starts and which
+ * pitch it takes, this one how long it lasts and how loud it is)
+ *   art_ctl: int32 [nseq], one control word per sequence: -1 off, else base + 4096 R + 2^19 w + 2^20 h with R in 1 .. 64
+ *     the template's bars, base in 0 .. 4095, base + R <= art_rows, w the bar-line switch, h the guide-hold switch.
+ *     art_table: uint32 [art_rows][4], 1 <= art_rows <= 4096.  One row is one bar of a template: word 0 is dlo | dhi << 8,
+ *     each 0 .. 128 (0: that bound is not set); words 1 and 2 are a 64-bit velocity mask (bit k % 32 of word 1 + k / 32
+ *     set: VELOCITY id 131 + k, MIDI velocity 2 k, may be drawn); word 3 is reserved: write 0, it is never read.
+ *     ROW OF THE OPEN BAR, as for onset_ctl: i = max(nb - 1, 0) with nb = state[b][8], never counted on a draw, a prompt's
+ *     bars included; the row is base + (i mod R), clamped to art_rows - 1 whatever the arrays hold.
+ *     VELOCITY BAN: every VELOCITY id 131 .. 194 whose bit is clear is banned.  Ids 130 and 195 are never touched.
+ *     DURATION WINDOW (DURATION id 303 + d lasts d steps, 1 .. 128): j and p are order_ctl's; a = p - 432 exists when S[j]
+ *     is a POSITION; q = S[L - 1] is the grammar's previous token and k = q - 3 exists when q is a PITCH.  cap = 128,
+ *     lowered by each that applies: dhi >= 1: min(cap, dhi); w set and a exists: min(cap, 128 - a), the note ends by the bar
+ *     line; h set, guide_ctl[b] on, a and k exist: min(cap, f), f the smallest m in 1 .. 127 such that bit k of the guide's
+ *     cell row for step a + m is clear (none: the term does not apply).  The cell row of step a + m < 128 is
+ *     block_i + 1 + ((a + m) >> s), of a later step block_{i+1} + 1 + ((a + m - 128) >> s), block_x = base_g +
+ *     (x mod R_g) (1 + C) with guide_ctl[b]'s own base_g, R_g, s and C; every row index is clamped to guide_rows - 1.
+ *     lo = min(max(dlo, 1), cap); banned are DURATION ids 304 .. 303 + lo - 1 and 304 + cap .. 431.  The window is never
+ *     empty (a <= 127, f >= 1): where the bar line or the guide leaves less room than dlo the lower bound gives way.  Ids
+ *     303 and 432 are never touched; step a itself is not tested (that is guide_ctl's pitch ban).
+ *     The bans apply whatever class is drawn and join the one select of order_ctl .. guide_ctl.  A draw is BIT FOR BIT the
+ *     draw of the call without art_ctl and with bias[b] = -inf at these ids; an off word, or a word over a row with
+ *     dlo = dhi = 0, an all-ones velocity mask and w = h = 0, is bit for bit the call without the fields.
+ *     NOT COVERED: forced tokens, and anything a forced position starts; notes inside a prompt; a note forced shorter than
+ *     dlo (above); an empty velocity mask ends the attempt by Q12 as before (the host refuses to build one); the hold term
+ *     reads the next bar's block even where the generation length would cut the sequence first; the hold term tests the
+ *     guide only (harmony across a chord change is not tested).
+ *     ONE kernel serves it, the guide kernel with one more uniform 16-byte load (the row, beside the onset row) and two
+ *     one-word loads per lane for the hold term (lane l tests steps a + 1 + l and a + 65 + l; issued with the guide's cell
+ *     row, once the scan has found p; two ballots give f).  A host-precomputed run-length table by bar, cell and pitch
+ *     would make f one load; it costs 1 MB per 64-bar template and a repack on every change of the guide, and was not
+ *     built.  art_ctl requires guide_ctl and everything guide_ctl requires -- callers without a guide pass all -1 guide
+ *     words over a one-row table -- a non-null art_table and 1 <= art_rows <= 4096, else -22.  Validating the words is the
+ *     caller's job (generate.articulation_rows / ForcedDecoder.set_articulation).  The same three fields, with the same
+ *     meaning and the same refusals, are in commu_decode_loop_args.  Null art_ctl: the launch that never heard of it.
  * WHAT gram / harm READ
  *   state: the forcing records, int32 [nseq][commu_forcing_state_ints()]; seq int32 [nseq][ld_seq]; chord_tok int32
  *   [nseq][ld_chord].  Not looked at, and may be null, in a call without gram and harm.
@@ -647,6 +683,10 @@ typedef struct commu_sample_args {
     const int* seq;
     const int* chord_tok;
     int ld_seq, ld_chord;
+    /* articulation (ahead of guide_ctl: the eleven fields behind them keep their places at the struct's end) */
+    const int* art_ctl;
+    const unsigned* art_table;
+    int art_rows;
     /* guide track (ahead of onset_ctl: the eight fields behind them keep their places at the struct's end) */
     const int* guide_ctl;
     const unsigned* guide_table;
@@ -882,6 +922,10 @@ typedef struct commu_decode_loop_args {
     const float* harm;
     const unsigned char* harm_on;
     int ld_bias, ld_gram, ld_harm;
+    /* articulation (commu_sample_args.art_ctl / art_table / art_rows; likewise ahead of guide_ctl) */
+    const int* art_ctl;
+    const unsigned* art_table;
+    int art_rows;
     /* guide track (commu_sample_args.guide_ctl / guide_table / guide_rows; likewise ahead of onset_ctl) */
     const int* guide_ctl;
     const unsigned* guide_table;
@@ -950,7 +994,7 @@ int commu_decode_prefill_scatter(const void* qkv, int ld_qkv, int T, int B, void
  *   bias[slot][0 .. ld_bias) = e_bias[entry];  gram_on / harm_on [slot] = e_gram_on / e_harm_on [entry] (bytes);
  *   order_ctl / voice_ctl / density_ctl / interval_ctl / onset_ctl [slot] = e_order / e_voice / e_density / e_interval /
  *   e_onset [entry] (the onset table is the pool's own: no table bytes move per arm);  guide_ctl[slot] = e_guide[entry]
- *   (likewise: the guide table is the pool's own);
+ *   (likewise: the guide table is the pool's own);  art_ctl[slot] = e_art[entry] (likewise);
  *   cls_ctl[slot][0 .. 32) = e_cls[entry] (int32).
  * tok / active / keep / draw are NOT written: an armed slot sits out the iteration whose decision was taken from its
  * finished record and starts with the next one.  Two jobs of one launch must name different slots (the caller's duty).
@@ -1007,6 +1051,8 @@ typedef struct commu_decode_arm_args {
     const unsigned char* e_gram_on;
     unsigned char* harm_on;
     const unsigned char* e_harm_on;
+    int* art_ctl;
+    const int* e_art;
     int* guide_ctl;
     const int* e_guide;
     int* onset_ctl;
@@ -1100,6 +1146,8 @@ typedef struct commu_decode_arm_primed_args {
     const unsigned char* e_gram_on;
     unsigned char* harm_on;
     const unsigned char* e_harm_on;
+    int* art_ctl;
+    const int* e_art;
     int* guide_ctl;
     const int* e_guide;
     int* onset_ctl;
