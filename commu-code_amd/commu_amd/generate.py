@@ -16,7 +16,7 @@ import ctypes as C
 import dataclasses
 import functools
 import math
-from typing import List, Optional, Sequence
+from typing import Callable, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -1528,6 +1528,59 @@ class DecodeState:
                                 "invalid")
 
 
+# The constraint tiers of the sampling step, as the kernels order them (csrc/decode_loop.h: Tier): a launch of a tier reads what
+# every tier below it reads, so a decoder that enables one allocates, switched off, whatever it lacks below it.
+T_NONE, T_GRAM, T_HARM, T_CLS, T_ORD, T_VOX, T_DEN, T_MEL, T_ONS, T_GDE, T_ART = range(11)
+
+
+class SlotRule(NamedTuple):
+    """One per-slot constraint of ForcedDecoder: control words int32 [B] on the device with a host mirror, and for the
+    rules that own a template table the table's shape and how a template becomes rows and a word.  The decoder's attributes
+    are named after `stem`: <stem>_ctl and _<stem>_host, <stem>_table, _<stem>_table_host, _<stem>_used and _<stem>_index;
+    the fields of the argument structs are <stem>_ctl, <stem>_table and <stem>_rows."""
+    tier: int
+    stem: str
+    kw: str                          # the keyword of ops.sample_topk
+    off: int                         # the word of a slot that is off
+    label: str = ""                  # (table) what refusals call it
+    rows_max: int = 0                # (table) rows of the device table, allocated once; 0: the rule has no table
+    cycle_max: int = 0               # (table) bars of one template
+    fill: tuple = ()                 # (table) a row that constrains nothing
+    rows_of: Callable = None         # (table) template -> its uint32 [n][4] rows
+    key: Callable = None             # (table) template -> what tells distinct templates apart
+    bars: Callable = None            # (table) template -> its bars
+    word: Callable = None            # (table) (base row, bars, template) -> control word
+
+    ctl = property(lambda r: r.stem + "_ctl")
+    host = property(lambda r: "_" + r.stem + "_host")
+    table = property(lambda r: r.stem + "_table")
+    table_host = property(lambda r: "_" + r.stem + "_table_host")
+    used = property(lambda r: "_" + r.stem + "_used")
+    index = property(lambda r: "_" + r.stem + "_index")
+
+
+_ONES = (0xFFFFFFFF,) * 4
+ORDER = SlotRule(T_ORD, "order", "note_order", NOTE_ORDER_OFF)
+VOICES = SlotRule(T_VOX, "voice", "voices", VOICES_OFF)
+DENSITY = SlotRule(T_DEN, "density", "density", DENSITY_OFF)
+INTERVAL = SlotRule(T_MEL, "interval", "interval", INTERVAL_OFF)
+# (a template is the uint32 rows)
+ONSETS = SlotRule(T_ONS, "onset", "onsets", ONSETS_OFF, "onsets", ONSET_ROWS_MAX, ONSET_CYCLE_MAX, _ONES,
+                  rows_of=lambda t: t, key=lambda t: t.tobytes(), bars=lambda t: t.shape[0],
+                  word=lambda base, bars, t: onset_word(base, bars))
+# (a template is (rows, cells): a bar is a block of 1 + cells rows, and the same bytes under other cells are another guide)
+GUIDE = SlotRule(T_GDE, "guide", "guide", GUIDE_OFF, "guide", GUIDE_ROWS_MAX, GUIDE_CYCLE_MAX, _ONES,
+                 rows_of=lambda t: t[0], key=lambda t: (t[1], t[0].tobytes()), bars=lambda t: t[0].shape[0] // (1 + t[1]),
+                 word=lambda base, bars, t: guide_word(base, bars, t[1]))
+# (a template is (rows, within_bar, hold_guide): the switches live in the word, so two settings over the same rows share
+# them; a free row: no bounds, every velocity bin, the reserved word 0)
+ARTICULATION = SlotRule(T_ART, "art", "articulation", ARTICULATION_OFF, "articulation", ARTICULATION_ROWS_MAX,
+                        ARTICULATION_CYCLE_MAX, (0, 0xFFFFFFFF, 0xFFFFFFFF, 0),
+                        rows_of=lambda t: t[0], key=lambda t: t[0].tobytes(), bars=lambda t: t[0].shape[0],
+                        word=lambda base, bars, t: articulation_word(base, bars, t[1], t[2]))
+SLOT_RULES = (ORDER, VOICES, DENSITY, INTERVAL, ONSETS, GUIDE, ARTICULATION)
+
+
 class ForcedDecoder:
     """The device-resident decode loop for B sequences: state records + token buffers + one hipGraph per iteration.
 
@@ -1711,19 +1764,17 @@ class ForcedDecoder:
             raise CommuHipError(f"rows: slot numbers in [0, {self.B}) expected, got {rows!r}")
         return idx
 
-    def _first_use(self, rows=False, bias=False, gram=False, harm=False, cls=False, order=False, voices=False,
-                   density=False, interval=False, onsets=False, guide=False, articulation=False):
-        """What the first use of a per-slot launch input does, for each one asked for that the decoder does not have yet:
-        rows uploads the host mirror of the sampling controls (scalar mode kept the mirror only); bias / gram / harm
-        allocate their zeroed device buffers (gram and harm: the table and the [B] switches); cls allocates the slots'
-        class-control records (set_class_sampling fills them); order allocates the slots' note-order words, all off; voices
-        the slots' voice words, all off; density the slots' density words, all off; interval the slots' interval words,
-        all off; onsets the slots' onset words, all off, and the template table of ONSET_ROWS_MAX all-ones rows; guide the
-        slots' guide words, all off, and the guide table of GUIDE_ROWS_MAX all-ones rows; articulation the slots'
-        articulation words, all off, and the articulation table of ARTICULATION_ROWS_MAX rows that constrain nothing.
-        When anything was missing the captured graphs are dropped,
+    def _first_use(self, tier=T_NONE, rows=False, bias=False, gram=False):
+        """What the first use of a per-slot launch input does, for each one asked for that the decoder does not have yet.
+        tier: everything the launch of that tier reads (T_* above) -- from T_HARM up the bias and the grammar, from T_CLS up
+        the array launches; below T_HARM the three are independent of each other and asked for by name.  rows uploads the
+        host mirror of the sampling controls (scalar mode kept the mirror only); bias / gram / harmony allocate their
+        zeroed device buffers (gram and harmony: the table and the [B] switches); the class tier allocates the slots'
+        class-control records (set_class_sampling fills them); every rule of SLOT_RULES its words, all off, and -- where it
+        owns one -- its table of rows that constrain nothing.  When anything was missing the captured graphs are dropped,
         once: they hold the launches without it."""
         new = False
+        rows, bias, gram = rows or tier >= T_CLS, bias or tier >= T_HARM, gram or tier >= T_HARM
         if rows and not self.rows_on:
             new = self.rows_on = True
             for dst, src in zip((self.temperature_rows, self.top_k_rows, self.top_p_rows), self._sampling):
@@ -1735,56 +1786,95 @@ class ForcedDecoder:
             new = True
             self.gram = torch.zeros(N_CLASSES + 1, VPAD, dtype=F32, device=self.dev)
             self.gram_on = torch.zeros(self.B, dtype=torch.uint8, device=self.dev)
-        if harm and self.harm is None:
+        if tier >= T_HARM and self.harm is None:
             new = True
             self.harm = torch.zeros(HARM_ROWS, HARM_COLS, dtype=F32, device=self.dev)
             self.harm_on = torch.zeros(self.B, dtype=torch.uint8, device=self.dev)
-        if cls and self.cls_ctl is None:
+        if tier >= T_CLS and self.cls_ctl is None:
             new = True
             self.cls_ctl = torch.zeros(self.B, N_CLASSES + 1, 4, dtype=torch.int32, device=self.dev)
             self._cls_host = np.full((self.B, N_CLASSES + 1, 3), np.nan)
-        if order and self.order_ctl is None:
+        for r in SLOT_RULES:
+            if tier < r.tier or getattr(self, r.ctl) is not None:
+                continue
             new = True
-            self.order_ctl = torch.full((self.B,), NOTE_ORDER_OFF, dtype=torch.int32, device=self.dev)
-            self._order_host = np.full(self.B, NOTE_ORDER_OFF, dtype=np.int32)
-        if voices and self.voice_ctl is None:
-            new = True
-            self.voice_ctl = torch.full((self.B,), VOICES_OFF, dtype=torch.int32, device=self.dev)
-            self._voice_host = np.full(self.B, VOICES_OFF, dtype=np.int32)
-        if density and self.density_ctl is None:
-            new = True
-            self.density_ctl = torch.full((self.B,), DENSITY_OFF, dtype=torch.int32, device=self.dev)
-            self._density_host = np.full(self.B, DENSITY_OFF, dtype=np.int32)
-        if interval and self.interval_ctl is None:
-            new = True
-            self.interval_ctl = torch.full((self.B,), INTERVAL_OFF, dtype=torch.int32, device=self.dev)
-            self._interval_host = np.full(self.B, INTERVAL_OFF, dtype=np.int32)
-        if onsets and self.onset_ctl is None:
-            new = True
-            self.onset_ctl = torch.full((self.B,), ONSETS_OFF, dtype=torch.int32, device=self.dev)
-            self._onset_host = np.full(self.B, ONSETS_OFF, dtype=np.int32)
-            # (int32 on the device: the bit patterns of the uint32 rows)
-            self.onset_table = torch.full((ONSET_ROWS_MAX, 4), -1, dtype=torch.int32, device=self.dev)
-            self._onset_table_host = np.full((ONSET_ROWS_MAX, 4), 0xFFFFFFFF, dtype=np.uint32)
-            self._onset_used, self._onset_index = 0, {}
-        if guide and self.guide_ctl is None:
-            new = True
-            self.guide_ctl = torch.full((self.B,), GUIDE_OFF, dtype=torch.int32, device=self.dev)
-            self._guide_host = np.full(self.B, GUIDE_OFF, dtype=np.int32)
-            self.guide_table = torch.full((GUIDE_ROWS_MAX, 4), -1, dtype=torch.int32, device=self.dev)
-            self._guide_table_host = np.full((GUIDE_ROWS_MAX, 4), 0xFFFFFFFF, dtype=np.uint32)
-            self._guide_used, self._guide_index = 0, {}
-        if articulation and self.art_ctl is None:
-            new = True
-            self.art_ctl = torch.full((self.B,), ARTICULATION_OFF, dtype=torch.int32, device=self.dev)
-            self._art_host = np.full(self.B, ARTICULATION_OFF, dtype=np.int32)
-            # (a row that constrains nothing: no bounds, every velocity bin, the reserved word 0)
-            free = np.array([0, 0xFFFFFFFF, 0xFFFFFFFF, 0], dtype=np.uint32)
-            self._art_table_host = np.tile(free, (ARTICULATION_ROWS_MAX, 1))
-            self.art_table = torch.from_numpy(self._art_table_host.view(np.int32).copy()).to(self.dev)
-            self._art_used, self._art_index = 0, {}
+            setattr(self, r.ctl, torch.full((self.B,), r.off, dtype=torch.int32, device=self.dev))
+            setattr(self, r.host, np.full(self.B, r.off, dtype=np.int32))
+            if r.rows_max:
+                host = np.tile(np.array(r.fill, dtype=np.uint32), (r.rows_max, 1))
+                setattr(self, r.table_host, host)
+                # (int32 on the device: the bit patterns of the uint32 rows)
+                setattr(self, r.table, torch.from_numpy(host.view(np.int32).copy()).to(self.dev))
+                setattr(self, r.used, 0)
+                setattr(self, r.index, {})
         if new:
             self.graph = self.graph_long = None
+
+    def _first_use_words(self, r):
+        """_first_use of a word setter: what rule r's kernel reads; class records that no table ever filled hold every
+        slot's base triple in every record."""
+        fresh_cls = self.cls_ctl is None
+        self._first_use(r.tier)
+        if fresh_cls:
+            self._write_class_ctl(None, np.arange(self.B))
+
+    def _write_words(self, r, idx, new, rows):
+        """The tail of a word setter: the words `new` of the slots idx, where they differ from the mirror, written in
+        place -- the whole array by one copy, or a few slots by device-side fills."""
+        host, ctl = getattr(self, r.host), getattr(self, r.ctl)
+        if np.array_equal(host[idx], new):
+            return
+        host[idx] = new
+        if rows is None and len(idx) > 4:
+            ctl.copy_(torch.from_numpy(host))
+        else:
+            for j in idx:
+                ctl[int(j)].fill_(int(host[j]))
+
+    def _pack(self, r, templates, fresh: bool = False):
+        """The control words of the given templates (None: off) in the table of rule r.  Distinct templates, told apart by
+        r.key, are packed one behind the other; a template packed before keeps its rows.  fresh: the table is packed anew
+        from these templates alone (every slot's word is about to be rewritten).  Refuses, before anything changes, what
+        does not fit.  New rows are written to the device table in place, ordered on the current stream."""
+        index = {} if fresh else dict(getattr(self, r.index))
+        used = 0 if fresh else getattr(self, r.used)
+        todo, words = [], []
+        for t in templates:
+            if t is None:
+                words.append(r.off)
+                continue
+            rows, bars = r.rows_of(t), r.bars(t)
+            if bars > r.cycle_max:
+                raise CommuHipError(f"{r.label}: a template holds at most {r.cycle_max} bars, got {bars}")
+            key = r.key(t)
+            if key not in index:
+                if used + rows.shape[0] > r.rows_max:
+                    raise CommuHipError(f"{r.label}: the distinct templates need more than the table's {r.rows_max} rows "
+                                        f"({used} in use, {rows.shape[0]} more asked for)")
+                index[key] = used
+                todo.append((used, rows))
+                used += rows.shape[0]
+            words.append(r.word(index[key], bars, t))
+        host, table = getattr(self, r.table_host), getattr(self, r.table)
+        for base, rows in todo:
+            host[base:base + rows.shape[0]] = rows
+            table[base:base + rows.shape[0]].copy_(torch.from_numpy(rows.view(np.int32)))
+        setattr(self, r.index, index)
+        setattr(self, r.used, used)
+        return np.array(words, dtype=np.int32)
+
+    def _set_templates(self, r, tmpl, idx, rows):
+        """The body of a template setter, after its values were validated: nothing for a decoder without the rule that
+        is given no template; the capacity check of _pack before anything is allocated; first use; pack; words."""
+        if getattr(self, r.ctl) is None:
+            if all(t is None for t in tmpl):
+                return
+            need = sum(r.rows_of(t).shape[0] for t in {r.key(t): t for t in tmpl if t is not None}.values())
+            if need > r.rows_max:
+                raise CommuHipError(f"{r.label}: the distinct templates need more than the table's {r.rows_max} rows "
+                                    f"(0 in use, {need} asked for)")
+        self._first_use_words(r)
+        self._write_words(r, idx, self._pack(r, tmpl, fresh=rows is None), rows)
 
     @staticmethod
     def _switch(on, val, rows, idx):
@@ -1911,7 +2001,7 @@ class ForcedDecoder:
         new = None if table is None else (harmony_table() if table is True else harmony_rows(table))
         if self.harm is None and new is None:
             return
-        self._first_use(harm=True, bias=True, gram=True)      # (the one harmony kernel reads a bias and a grammar)
+        self._first_use(T_HARM)                               # (the one harmony kernel reads a bias and a grammar)
         if new is not None and (self._harm_host is None or not np.array_equal(new, self._harm_host)):
             self.harm.copy_(torch.from_numpy(new))
             self._harm_host = new
@@ -1938,7 +2028,7 @@ class ForcedDecoder:
         if self.cls_ctl is None and new is None:
             return
         fresh = self.cls_ctl is None
-        self._first_use(rows=True, bias=True, gram=True, harm=True, cls=True)
+        self._first_use(T_CLS)
         self._cls_host[idx] = np.nan if new is None else new
         if fresh:          # (the slots not addressed get their base triple in every record)
             rows, idx = None, np.arange(self.B)
@@ -1961,6 +2051,10 @@ class ForcedDecoder:
     def _cls_args(self):
         return None if self.cls_ctl is None else (self.cls_ctl, self.fsm, self.seq)
 
+    def _slot_words(self):
+        """(rule, control words) for every rule of SLOT_RULES the decoder has words for."""
+        return [(r, getattr(self, r.ctl)) for r in SLOT_RULES if getattr(self, r.ctl) is not None]
+
     def set_note_order(self, value=True, rows: Optional[Sequence[int]] = None):
         """The note-order constraint for all slots (rows=None) or the listed ones: True (on), an integer n in 1 .. 128 (on,
         at most n notes per position), None / False (off), or one such value per addressed slot (note_order_ctl).  A slot
@@ -1980,18 +2074,8 @@ class ForcedDecoder:
         new = note_order_ctl(value, len(idx))                  # (validated before anything changes)
         if self.order_ctl is None and not bool((new != NOTE_ORDER_OFF).any()):
             return
-        fresh_cls = self.cls_ctl is None
-        self._first_use(rows=True, bias=True, gram=True, harm=True, cls=True, order=True)
-        if fresh_cls:          # (no class controls: every record of every slot holds the slot's base triple)
-            self._write_class_ctl(None, np.arange(self.B))
-        if np.array_equal(self._order_host[idx], new):
-            return
-        self._order_host[idx] = new
-        if rows is None and len(idx) > 4:
-            self.order_ctl.copy_(torch.from_numpy(self._order_host))
-        else:
-            for j in idx:
-                self.order_ctl[int(j)].fill_(int(self._order_host[j]))
+        self._first_use_words(ORDER)
+        self._write_words(ORDER, idx, new, rows)
 
     def set_voices(self, value, rows: Optional[Sequence[int]] = None):
         """The voice cap for all slots (rows=None) or the listed ones: a word voices_word(N, r) -- at most N of the slot's
@@ -2016,15 +2100,8 @@ class ForcedDecoder:
                 if w != VOICES_OFF and (self._order_host is None or self._order_host[j] == NOTE_ORDER_OFF)]
         if need:
             self.set_note_order(True, rows=need)               # (allocates what the note-order kernel reads)
-        self._first_use(voices=True)
-        if np.array_equal(self._voice_host[idx], new):
-            return
-        self._voice_host[idx] = new
-        if rows is None and len(idx) > 4:
-            self.voice_ctl.copy_(torch.from_numpy(self._voice_host))
-        else:
-            for j in idx:
-                self.voice_ctl[int(j)].fill_(int(self._voice_host[j]))
+        self._first_use_words(VOICES)
+        self._write_words(VOICES, idx, new, rows)
 
     def set_density(self, value, rows: Optional[Sequence[int]] = None):
         """The note density for all slots (rows=None) or the listed ones: a word density_word(lo, hi) -- a bar the slot
@@ -2049,15 +2126,8 @@ class ForcedDecoder:
                 if w != DENSITY_OFF and (self._voice_host is None or self._voice_host[j] == VOICES_OFF)]
         if need:
             self.set_voices(0, rows=need)                      # (allocates what the voices kernel reads; the note order too)
-        self._first_use(density=True)
-        if np.array_equal(self._density_host[idx], new):
-            return
-        self._density_host[idx] = new
-        if rows is None and len(idx) > 4:
-            self.density_ctl.copy_(torch.from_numpy(self._density_host))
-        else:
-            for j in idx:
-                self.density_ctl[int(j)].fill_(int(self._density_host[j]))
+        self._first_use_words(DENSITY)
+        self._write_words(DENSITY, idx, new, rows)
 
     def set_interval(self, value, rows: Optional[Sequence[int]] = None):
         """The melodic interval for all slots (rows=None) or the listed ones: a word interval_word(up, down, no_repeat) --
@@ -2080,49 +2150,8 @@ class ForcedDecoder:
         new = interval_ctl(value, len(idx))                    # (validated before anything changes)
         if self.interval_ctl is None and not bool((new != INTERVAL_OFF).any()):
             return
-        fresh_cls = self.cls_ctl is None
-        self._first_use(rows=True, bias=True, gram=True, harm=True, cls=True, order=True, voices=True, density=True,
-                        interval=True)
-        if fresh_cls:          # (no class controls: every record of every slot holds the slot's base triple)
-            self._write_class_ctl(None, np.arange(self.B))
-        if np.array_equal(self._interval_host[idx], new):
-            return
-        self._interval_host[idx] = new
-        if rows is None and len(idx) > 4:
-            self.interval_ctl.copy_(torch.from_numpy(self._interval_host))
-        else:
-            for j in idx:
-                self.interval_ctl[int(j)].fill_(int(self._interval_host[j]))
-
-    def _onsets_pack(self, templates, fresh: bool = False):
-        """The control words of the given templates (uint32 [R][4]; None: off) in the decoder's table.  Distinct templates,
-        told apart by their bytes, are packed one behind the other; a template packed before keeps its rows.  fresh: the
-        table is packed anew from these templates alone (every slot's word is about to be rewritten).  Refuses, before
-        anything changes, what does not fit.  New rows are written to the device table in place, ordered on the current
-        stream."""
-        index = {} if fresh else dict(self._onset_index)
-        used = 0 if fresh else self._onset_used
-        todo, words = [], []
-        for t in templates:
-            if t is None:
-                words.append(ONSETS_OFF)
-                continue
-            if t.shape[0] > ONSET_CYCLE_MAX:
-                raise CommuHipError(f"onsets: a template holds at most {ONSET_CYCLE_MAX} bars, got {t.shape[0]}")
-            key = t.tobytes()
-            if key not in index:
-                if used + t.shape[0] > ONSET_ROWS_MAX:
-                    raise CommuHipError(f"onsets: the distinct templates need more than the table's {ONSET_ROWS_MAX} rows "
-                                        f"({used} in use, {t.shape[0]} more asked for)")
-                index[key] = used
-                todo.append((used, t))
-                used += t.shape[0]
-            words.append(onset_word(index[key], t.shape[0]))
-        for base, t in todo:
-            self._onset_table_host[base:base + t.shape[0]] = t
-            self.onset_table[base:base + t.shape[0]].copy_(torch.from_numpy(t.view(np.int32)))
-        self._onset_index, self._onset_used = index, used
-        return np.array(words, dtype=np.int32)
+        self._first_use_words(INTERVAL)
+        self._write_words(INTERVAL, idx, new, rows)
 
     def set_onsets(self, value, rows: Optional[Sequence[int]] = None):
         """The onset template for all slots (rows=None) or the listed ones: a template in any form onset_rows takes -- a list
@@ -2143,63 +2172,7 @@ class ForcedDecoder:
         bit for bit what it decoded without the feature; a decoder that never switched a slot on allocates nothing."""
         idx = self._slots(rows)
         tmpl = _onsets_per_slot(value, len(idx))               # (validated before anything changes)
-        if self.onset_ctl is None and all(t is None for t in tmpl):
-            return
-        if self.onset_ctl is None:
-            # (the capacity check of _onsets_pack, before anything is allocated)
-            need, seen = 0, set()
-            for t in tmpl:
-                if t is not None and t.tobytes() not in seen:
-                    seen.add(t.tobytes())
-                    need += t.shape[0]
-            if need > ONSET_ROWS_MAX:
-                raise CommuHipError(f"onsets: the distinct templates need more than the table's {ONSET_ROWS_MAX} rows "
-                                    f"(0 in use, {need} asked for)")
-        fresh_cls = self.cls_ctl is None
-        self._first_use(rows=True, bias=True, gram=True, harm=True, cls=True, order=True, voices=True, density=True,
-                        interval=True, onsets=True)
-        if fresh_cls:          # (no class controls: every record of every slot holds the slot's base triple)
-            self._write_class_ctl(None, np.arange(self.B))
-        new = self._onsets_pack(tmpl, fresh=rows is None)
-        if np.array_equal(self._onset_host[idx], new):
-            return
-        self._onset_host[idx] = new
-        if rows is None and len(idx) > 4:
-            self.onset_ctl.copy_(torch.from_numpy(self._onset_host))
-        else:
-            for j in idx:
-                self.onset_ctl[int(j)].fill_(int(self._onset_host[j]))
-
-    def _guide_pack(self, templates, fresh: bool = False):
-        """The control words of the given guides ((rows uint32 [R (1 + C)][4], C); None: off) in the decoder's table: as
-        _onsets_pack -- distinct templates, told apart by their cells and bytes, one behind the other; fresh packs the table
-        anew from these alone; what does not fit is refused before anything changes; new rows are written in place, ordered
-        on the current stream."""
-        index = {} if fresh else dict(self._guide_index)
-        used = 0 if fresh else self._guide_used
-        todo, words = [], []
-        for t in templates:
-            if t is None:
-                words.append(GUIDE_OFF)
-                continue
-            rows, cells = t
-            bars = rows.shape[0] // (1 + cells)
-            if bars > GUIDE_CYCLE_MAX:
-                raise CommuHipError(f"guide: a template holds at most {GUIDE_CYCLE_MAX} bars, got {bars}")
-            key = (cells, rows.tobytes())
-            if key not in index:
-                if used + rows.shape[0] > GUIDE_ROWS_MAX:
-                    raise CommuHipError(f"guide: the distinct templates need more than the table's {GUIDE_ROWS_MAX} rows "
-                                        f"({used} in use, {rows.shape[0]} more asked for)")
-                index[key] = used
-                todo.append((used, rows))
-                used += rows.shape[0]
-            words.append(guide_word(index[key], bars, cells))
-        for base, rows in todo:
-            self._guide_table_host[base:base + rows.shape[0]] = rows
-            self.guide_table[base:base + rows.shape[0]].copy_(torch.from_numpy(rows.view(np.int32)))
-        self._guide_index, self._guide_used = index, used
-        return np.array(words, dtype=np.int32)
+        self._set_templates(ONSETS, tmpl, idx, rows)
 
     def set_guide(self, value, rows: Optional[Sequence[int]] = None):
         """The guide track for all slots (rows=None) or the listed ones: a guide in any form guide_template takes -- the raw
@@ -2219,62 +2192,7 @@ class ForcedDecoder:
         bit for bit what it decoded without the feature; a decoder that never switched a slot on allocates nothing."""
         idx = self._slots(rows)
         tmpl = _guide_per_slot(value, len(idx))                # (validated before anything changes)
-        if self.guide_ctl is None and all(t is None for t in tmpl):
-            return
-        if self.guide_ctl is None:
-            # (the capacity check of _guide_pack, before anything is allocated)
-            need, seen = 0, set()
-            for t in tmpl:
-                if t is not None and (t[1], t[0].tobytes()) not in seen:
-                    seen.add((t[1], t[0].tobytes()))
-                    need += t[0].shape[0]
-            if need > GUIDE_ROWS_MAX:
-                raise CommuHipError(f"guide: the distinct templates need more than the table's {GUIDE_ROWS_MAX} rows "
-                                    f"(0 in use, {need} asked for)")
-        fresh_cls = self.cls_ctl is None
-        self._first_use(rows=True, bias=True, gram=True, harm=True, cls=True, order=True, voices=True, density=True,
-                        interval=True, onsets=True, guide=True)
-        if fresh_cls:          # (no class controls: every record of every slot holds the slot's base triple)
-            self._write_class_ctl(None, np.arange(self.B))
-        new = self._guide_pack(tmpl, fresh=rows is None)
-        if np.array_equal(self._guide_host[idx], new):
-            return
-        self._guide_host[idx] = new
-        if rows is None and len(idx) > 4:
-            self.guide_ctl.copy_(torch.from_numpy(self._guide_host))
-        else:
-            for j in idx:
-                self.guide_ctl[int(j)].fill_(int(self._guide_host[j]))
-
-    def _art_pack(self, templates, fresh: bool = False):
-        """The control words of the given articulations ((rows uint32 [R][4], within_bar, hold_guide); None: off) in the
-        decoder's table: as _guide_pack -- distinct templates, told apart by their bytes (the switches live in the word, so
-        two settings over the same rows share them), one behind the other; fresh packs the table anew from these alone; what
-        does not fit is refused before anything changes; new rows are written in place, ordered on the current stream."""
-        index = {} if fresh else dict(self._art_index)
-        used = 0 if fresh else self._art_used
-        todo, words = [], []
-        for t in templates:
-            if t is None:
-                words.append(ARTICULATION_OFF)
-                continue
-            rows, w, h = t
-            if rows.shape[0] > ARTICULATION_CYCLE_MAX:
-                raise CommuHipError(f"articulation: a template holds at most {ARTICULATION_CYCLE_MAX} bars, got {rows.shape[0]}")
-            key = rows.tobytes()
-            if key not in index:
-                if used + rows.shape[0] > ARTICULATION_ROWS_MAX:
-                    raise CommuHipError(f"articulation: the distinct templates need more than the table's "
-                                        f"{ARTICULATION_ROWS_MAX} rows ({used} in use, {rows.shape[0]} more asked for)")
-                index[key] = used
-                todo.append((used, rows))
-                used += rows.shape[0]
-            words.append(articulation_word(index[key], rows.shape[0], w, h))
-        for base, rows in todo:
-            self._art_table_host[base:base + rows.shape[0]] = rows
-            self.art_table[base:base + rows.shape[0]].copy_(torch.from_numpy(rows.view(np.int32)))
-        self._art_index, self._art_used = index, used
-        return np.array(words, dtype=np.int32)
+        self._set_templates(GUIDE, tmpl, idx, rows)
 
     def set_articulation(self, value, rows: Optional[Sequence[int]] = None):
         """The articulation for all slots (rows=None) or the listed ones: an articulation in any form articulation_template
@@ -2296,28 +2214,7 @@ class ForcedDecoder:
         bit for bit what it decoded without the feature; a decoder that never switched a slot on allocates nothing."""
         idx = self._slots(rows)
         tmpl = _articulation_per_slot(value, len(idx))         # (validated before anything changes)
-        if self.art_ctl is None and all(t is None for t in tmpl):
-            return
-        if self.art_ctl is None:
-            # (the capacity check of _art_pack, before anything is allocated)
-            need = sum(len(k) // 16 for k in {t[0].tobytes() for t in tmpl if t is not None})
-            if need > ARTICULATION_ROWS_MAX:
-                raise CommuHipError(f"articulation: the distinct templates need more than the table's "
-                                    f"{ARTICULATION_ROWS_MAX} rows (0 in use, {need} asked for)")
-        fresh_cls = self.cls_ctl is None
-        self._first_use(rows=True, bias=True, gram=True, harm=True, cls=True, order=True, voices=True, density=True,
-                        interval=True, onsets=True, guide=True, articulation=True)
-        if fresh_cls:          # (no class controls: every record of every slot holds the slot's base triple)
-            self._write_class_ctl(None, np.arange(self.B))
-        new = self._art_pack(tmpl, fresh=rows is None)
-        if np.array_equal(self._art_host[idx], new):
-            return
-        self._art_host[idx] = new
-        if rows is None and len(idx) > 4:
-            self.art_ctl.copy_(torch.from_numpy(self._art_host))
-        else:
-            for j in idx:
-                self.art_ctl[int(j)].fill_(int(self._art_host[j]))
+        self._set_templates(ARTICULATION, tmpl, idx, rows)
 
     def pre(self):
         call("commu_forcing_pre", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_tok), _p(self.chord_pos),
@@ -2337,13 +2234,7 @@ class ForcedDecoder:
                         logp_out=logp, bias=self.bias, **({} if self.gram is None else {"grammar": self._gram_args()}),
                         **({} if self.harm is None else {"harmony": self._harm_args()}),
                         **({} if self.cls_ctl is None else {"class_ctl": self._cls_args()}),
-                        **({} if self.order_ctl is None else {"note_order": self.order_ctl}),
-                        **({} if self.voice_ctl is None else {"voices": self.voice_ctl}),
-                        **({} if self.density_ctl is None else {"density": self.density_ctl}),
-                        **({} if self.interval_ctl is None else {"interval": self.interval_ctl}),
-                        **({} if self.onset_ctl is None else {"onsets": (self.onset_ctl, self.onset_table)}),
-                        **({} if self.guide_ctl is None else {"guide": (self.guide_ctl, self.guide_table)}),
-                        **({} if self.art_ctl is None else {"articulation": (self.art_ctl, self.art_table)}))
+                        **{r.kw: (w, getattr(self, r.table)) if r.rows_max else w for r, w in self._slot_words()})
         call("commu_forcing_post", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_pos), self.ld_chord,
              _p(self.wrong), _p(self.draw), _p(self.token), None, _p(self.state.klen), _p(self.keep),
              self.state.klen_cap, _p(logp), _p(seq_logp), B, _s())
@@ -2357,6 +2248,11 @@ class ForcedDecoder:
         ld = lambda t: 0 if t is None else t.stride(0)
         # (a constraint the decoder never got is a null pointer: the launch that never heard of it; set_harmony allocated
         # the bias and the grammar its kernel reads)
+        cons = {}
+        for r, w in self._slot_words():
+            cons[r.ctl] = _p(w)
+            if r.rows_max:
+                cons.update({r.table: _p(getattr(self, r.table)), r.stem + "_rows": r.rows_max})
         a = struct_args(
             DecodeLoopArgs, logits=_p(st.logits), ld=st.logits.stride(0), V=TOKEN_OFFSET.VOCAB_SIZE, B=self.B,
             wrong=_p(self.wrong), temperature=self.temperature, top_k=self.top_k, top_p=self.top_p, temperature_rows=_p(t_r),
@@ -2367,14 +2263,7 @@ class ForcedDecoder:
             trace=_p(self.trace), ld_trace=self.ld_trace, klen=_p(st.klen), lmax=st.klen_cap,
             bias=_p(self.bias), ld_bias=ld(self.bias), gram=_p(self.gram), ld_gram=ld(self.gram), gram_on=_p(self.gram_on),
             harm=_p(self.harm), ld_harm=ld(self.harm), harm_on=_p(self.harm_on), cls_ctl=_p(self.cls_ctl),
-            order_ctl=_p(self.order_ctl), voice_ctl=_p(self.voice_ctl), density_ctl=_p(self.density_ctl),
-            interval_ctl=_p(self.interval_ctl),
-            **({} if self.onset_ctl is None else {"onset_ctl": _p(self.onset_ctl), "onset_table": _p(self.onset_table),
-                                                  "onset_rows": ONSET_ROWS_MAX}),
-            **({} if self.guide_ctl is None else {"guide_ctl": _p(self.guide_ctl), "guide_table": _p(self.guide_table),
-                                                  "guide_rows": GUIDE_ROWS_MAX}),
-            **({} if self.art_ctl is None else {"art_ctl": _p(self.art_ctl), "art_table": _p(self.art_table),
-                                                "art_rows": ARTICULATION_ROWS_MAX}))
+            **cons)
         call("commu_decode_sample_post_pre", C.byref(a), _s())
 
     def iteration(self, want_probs: bool = False):
@@ -3022,9 +2911,9 @@ class ForcedDecoder:
         P["e_voice"][entry].fill_(int(vox[0]))
         P["e_density"][entry].fill_(int(den[0]))
         P["e_interval"][entry].fill_(int(mel[0]))
-        P["e_onset"][entry].fill_(int(ONSETS_OFF if ons[0] is None else self._onsets_pack(ons)[0]))
-        P["e_guide"][entry].fill_(int(GUIDE_OFF if gde[0] is None else self._guide_pack(gde)[0]))
-        P["e_art"][entry].fill_(int(ARTICULATION_OFF if art[0] is None else self._art_pack(art)[0]))
+        P["e_onset"][entry].fill_(int(ONSETS_OFF if ons[0] is None else self._pack(ONSETS, ons)[0]))
+        P["e_guide"][entry].fill_(int(GUIDE_OFF if gde[0] is None else self._pack(GUIDE, gde)[0]))
+        P["e_art"][entry].fill_(int(ARTICULATION_OFF if art[0] is None else self._pack(ARTICULATION, art)[0]))
         if self.cls_ctl is not None:
             tab = np.full((1, N_CLASSES + 1, 3), np.nan) if class_table is None else class_sampling_table(class_table)[None]
             rec = class_ctl_records(tab, [t, k, p])
@@ -3803,24 +3692,14 @@ class BatchedGenerator:
         use_ons = use_ons or use_gde
         use_mel = use_mel or use_ons
         use_order = any(o != NOTE_ORDER_OFF for o in orders) or any(v != VOICES_OFF for v in voxes) or use_den or use_mel
-        if cls_table is not None or use_order:
-            dec._first_use(rows=True, bias=True, gram=True, harm=True, cls=True, order=use_order)
-        if any(v != VOICES_OFF for v in voxes) or use_den or use_mel:
-            dec._first_use(voices=True)
-        if use_den or use_mel:
-            dec._first_use(density=True)
-        if use_mel:
-            dec._first_use(interval=True)
-        if use_ons:
-            # (the requests' templates go into the one table before the pool is opened; admit finds them by their bytes)
-            dec._first_use(onsets=True)
-            dec._onsets_pack(onss, fresh=True)
-        if use_gde:
-            dec._first_use(guide=True)
-            dec._guide_pack(gdes, fresh=True)
-        if use_art:
-            dec._first_use(articulation=True)
-            dec._art_pack(arts, fresh=True)
+        # (one first use, of the highest tier any request needs; the requests' templates go into the tables before the pool
+        # is opened: admit finds them by their bytes)
+        dec._first_use(T_ART if use_art else T_GDE if use_gde else T_ONS if use_ons else T_MEL if use_mel
+                       else T_DEN if use_den else T_VOX if any(v != VOICES_OFF for v in voxes)
+                       else T_ORD if use_order else T_CLS if cls_table is not None else T_NONE)
+        for r, tmpls, use in ((ONSETS, onss, use_ons), (GUIDE, gdes, use_gde), (ARTICULATION, arts, use_art)):
+            if use:
+                dec._pack(r, tmpls, fresh=True)
         if any(b is not None for b in biases):
             dec._first_use(bias=True)
         klen0_max = max([n_cond] + [p["klen0"] for p in replays if p is not None])

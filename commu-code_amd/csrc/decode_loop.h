@@ -340,8 +340,15 @@ struct Articulation {
     int rows;               // 1 .. 4096 (the entry points refuse anything else)
 };
 constexpr int ART_ROWS_MAX = 4096, ART_CYCLE_MAX = 64;
-template <bool BIAS, bool GRAM = false, bool HARM = false, bool CLS = false, bool ORD = false, bool VOX = false,
-          bool DEN = false, bool MEL = false, bool ONS = false, bool GDE = false, bool ART = false>
+// THE TIER.  The constraints above are strictly nested: each one's kernel is the kernel of the one before it with one more
+// input, so a launch is described by how far up this list it goes -- grammar, harmony, class controls, note order, voices,
+// density, interval, onsets, guide, articulation, in the order of the enum -- and a tier includes every tier below it.  The
+// optional bias is the one free switch: tiers T_NONE and T_GRAM exist with and without it, from T_HARM up there is one
+// instantiation and it reads a bias (callers without one pass a zero row, and all-off switches / words for the tiers they
+// do not use).  A launch of tier T compiles to the code that never heard of the tiers above T: nothing of their arguments
+// is looked at.
+enum Tier { T_NONE, T_GRAM, T_HARM, T_CLS, T_ORD, T_VOX, T_DEN, T_MEL, T_ONS, T_GDE, T_ART };
+template <bool BIAS, int TIER = T_NONE>
 __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restrict__ logits, int ld, int V,
                                                  const unsigned char* __restrict__ wrong, int ldw,
                                                  const float* __restrict__ uni,
@@ -358,14 +365,8 @@ __device__ __forceinline__ int sample_topk_body(int b, int lane, float* __restri
                                                  Onsets os = Onsets{-1, nullptr, 1, 0},
                                                  Guide gd = Guide{-1, nullptr, 1},
                                                  Articulation ar = Articulation{-1, nullptr, 1}) {
-    static_assert(!CLS || GRAM, "the class key is the grammar's previous token");
-    static_assert(!ORD || CLS, "one note-order instantiation: the class kernel's with the scan");
-    static_assert(!VOX || ORD, "one voices instantiation: the note-order kernel's with the longer scan");
-    static_assert(!DEN || VOX, "one density instantiation: the voices kernel's with the count of the open bar's notes");
-    static_assert(!MEL || DEN, "one interval instantiation: the density kernel's with the reference note");
-    static_assert(!ONS || MEL, "one onsets instantiation: the interval kernel's with the template row");
-    static_assert(!GDE || ONS, "one guide instantiation: the onsets kernel's with the live row and the cell row");
-    static_assert(!ART || GDE, "one articulation instantiation: the guide kernel's with the row and the hold term");
+    constexpr bool GRAM = TIER >= T_GRAM, HARM = TIER >= T_HARM, CLS = TIER >= T_CLS, ORD = TIER >= T_ORD, VOX = TIER >= T_VOX,
+                   DEN = TIER >= T_DEN, MEL = TIER >= T_MEL, ONS = TIER >= T_ONS, GDE = TIER >= T_GDE, ART = TIER >= T_ART;
     float* lg = logits + (size_t)b * ld;
     // The optional per-sequence inputs -- the active flag and this sequence's controls -- are loaded unconditionally: a null
     // array reads a valid word of this sequence instead (token[b], logits[b][0]), which is then ignored.  So they are in

@@ -13,7 +13,7 @@
 //                        drawn -> reject, remember it, redo | EOS with chords left -> force position / bar | bar
 //                        with no chords left -> force EOS | else append.
 // One 64-lane wave per sequence: lane 0 runs the transition, the wave clears the 729-entry rejected-token bitmap.
-#include "decode_loop.h"
+#include "sample_tier.h"
 #include "commu_hip.h"
 
 namespace {
@@ -45,7 +45,14 @@ __global__ __launch_bounds__(64) void forcing_post_kernel(int* st, int* seq, int
 // One launch for the three per-sequence stages that follow the model step: sampling step -> book-keeping (post) -> the
 // decision of the NEXT iteration (pre).  A sequence's stages only exchange data of that sequence, and one wave runs
 // them in order; the workgroup barriers order the wave's own global stores and loads between stages.
-struct LoopStageArgs {
+// The argument block is a ladder of structs keyed by the tier (decode_loop.h: Tier): LoopArgs<T> is LoopArgs<T - 1> plus what
+// tier T reads, and the kernel of tier T takes LoopArgs<T> by value -- so the launch without a constraint keeps its
+// instructions AND its argument block (the kernel body is written on its parameter: moved into a device function that takes
+// the arguments by reference, the kernels without a grammar came out different).
+template <int TIER>
+struct LoopArgs;
+template <>
+struct LoopArgs<T_NONE> {
     float* logits; int ld, V;
     unsigned char* wrong;
     float temperature; int top_k; float top_p;
@@ -63,86 +70,63 @@ struct LoopStageArgs {
     unsigned long long* trace;      // (diagnostics) [sequence][4] 100 MHz timestamps: start, sampled, post done, pre done
     const float* bias; int ld_bias; // (BIAS) the caller's constraint rows for the sampling step (sample_topk_body)
 };
-// (GRAM) the grammar table [8][ld_gram] and the slots' switches [B]: arguments of the grammar kernels only, so that the
-// launch without a grammar keeps its instructions AND its argument block (the kernel body is written on its parameter: moved
-// into a device function that takes the arguments by reference, the kernels without a grammar came out different)
-struct LoopStageArgsGram : LoopStageArgs {
+// the grammar table [8][ld_gram] and the slots' switches [B]
+template <>
+struct LoopArgs<T_GRAM> : LoopArgs<T_NONE> {
     const float* gram; int ld_gram;
     const unsigned char* gram_on;
 };
-// (HARM) the harmony table [111][ld_harm] and the slots' switches [B]: likewise arguments of the harmony kernel only
-struct LoopStageArgsHarm : LoopStageArgsGram {
+// the harmony table [111][ld_harm] and the slots' switches [B]
+template <>
+struct LoopArgs<T_HARM> : LoopArgs<T_GRAM> {
     const float* harm; int ld_harm;
     const unsigned char* harm_on;
 };
-// (CLS) the class-control records [B][8] (decode_loop.h: ClassControls): an argument of the class kernel only
-struct LoopStageArgsCls : LoopStageArgsHarm {
+// the class-control records [B][8] (decode_loop.h: ClassControls)
+template <>
+struct LoopArgs<T_CLS> : LoopArgs<T_HARM> {
     const int4* cls_ctl;
 };
-// (ORD) the note-order control words [B] (decode_loop.h: NoteOrder): an argument of the note-order kernel only
-struct LoopStageArgsOrd : LoopStageArgsCls {
+// the control words [B] of the note order, the voice cap, the note density and the melodic interval (decode_loop.h:
+// NoteOrder, Voices, Density, Interval)
+template <>
+struct LoopArgs<T_ORD> : LoopArgs<T_CLS> {
     const int* order_ctl;
 };
-// (VOX) the voice control words [B] (decode_loop.h: Voices): an argument of the voices kernel only
-struct LoopStageArgsVox : LoopStageArgsOrd {
+template <>
+struct LoopArgs<T_VOX> : LoopArgs<T_ORD> {
     const int* voice_ctl;
 };
-// (DEN) the density control words [B] (decode_loop.h: Density): an argument of the density kernel only
-struct LoopStageArgsDen : LoopStageArgsVox {
+template <>
+struct LoopArgs<T_DEN> : LoopArgs<T_VOX> {
     const int* density_ctl;
 };
-// (MEL) the interval control words [B] (decode_loop.h: Interval): an argument of the interval kernel only
-struct LoopStageArgsMel : LoopStageArgsDen {
+template <>
+struct LoopArgs<T_MEL> : LoopArgs<T_DEN> {
     const int* interval_ctl;
 };
-// (ONS) the onset control words [B], the template table [onset_rows][4] and its row count (decode_loop.h: Onsets):
-// arguments of the onsets kernel only
-struct LoopStageArgsOns : LoopStageArgsMel {
+// the control words [B], the table [rows][4] and its row count of the onset templates, the guide track and the
+// articulation (decode_loop.h: Onsets, Guide, Articulation)
+template <>
+struct LoopArgs<T_ONS> : LoopArgs<T_MEL> {
     const int* onset_ctl;
     const unsigned* onset_table;
     int onset_rows;
 };
-// (GDE) the guide control words [B], the guide table [guide_rows][4] and its row count (decode_loop.h: Guide): arguments of
-// the guide kernel only
-struct LoopStageArgsGde : LoopStageArgsOns {
+template <>
+struct LoopArgs<T_GDE> : LoopArgs<T_ONS> {
     const int* guide_ctl;
     const unsigned* guide_table;
     int guide_rows;
 };
-// (ART) the articulation control words [B], the articulation table [art_rows][4] and its row count (decode_loop.h:
-// Articulation): arguments of the articulation kernel only
-struct LoopStageArgsArt : LoopStageArgsGde {
+template <>
+struct LoopArgs<T_ART> : LoopArgs<T_GDE> {
     const int* art_ctl;
     const unsigned* art_table;
     int art_rows;
 };
-template <bool GRAM, bool HARM = false, bool CLS = false, bool ORD = false, bool VOX = false, bool DEN = false,
-          bool MEL = false, bool ONS = false, bool GDE = false, bool ART = false>
-struct LoopArgsOf { using type = LoopStageArgs; };
-template <>
-struct LoopArgsOf<true, false, false, false, false, false, false, false, false, false> { using type = LoopStageArgsGram; };
-template <>
-struct LoopArgsOf<true, true, false, false, false, false, false, false, false, false> { using type = LoopStageArgsHarm; };
-template <>
-struct LoopArgsOf<true, true, true, false, false, false, false, false, false, false> { using type = LoopStageArgsCls; };
-template <>
-struct LoopArgsOf<true, true, true, true, false, false, false, false, false, false> { using type = LoopStageArgsOrd; };
-template <>
-struct LoopArgsOf<true, true, true, true, true, false, false, false, false, false> { using type = LoopStageArgsVox; };
-template <>
-struct LoopArgsOf<true, true, true, true, true, true, false, false, false, false> { using type = LoopStageArgsDen; };
-template <>
-struct LoopArgsOf<true, true, true, true, true, true, true, false, false, false> { using type = LoopStageArgsMel; };
-template <>
-struct LoopArgsOf<true, true, true, true, true, true, true, true, false, false> { using type = LoopStageArgsOns; };
-template <>
-struct LoopArgsOf<true, true, true, true, true, true, true, true, true, false> { using type = LoopStageArgsGde; };
-template <>
-struct LoopArgsOf<true, true, true, true, true, true, true, true, true, true> { using type = LoopStageArgsArt; };
-template <bool BIAS, bool GRAM, bool HARM = false, bool CLS = false, bool ORD = false, bool VOX = false, bool DEN = false,
-          bool MEL = false, bool ONS = false, bool GDE = false, bool ART = false>
-__global__ __launch_bounds__(64) void sample_post_pre_kernel(
-    typename LoopArgsOf<GRAM, HARM, CLS, ORD, VOX, DEN, MEL, ONS, GDE, ART>::type a) {
+template <bool BIAS, int TIER>
+__global__ __launch_bounds__(64) void sample_post_pre_kernel(LoopArgs<TIER> a) {
     const int b = blockIdx.x, lane = threadIdx.x;
     if (a.trace != nullptr && lane == 0) a.trace[b * 4 + 0] = wall_clock64();
     int rec[F_COUNT];                                  // the record travels through the three stages in lane 0's registers;
@@ -152,7 +136,7 @@ __global__ __launch_bounds__(64) void sample_post_pre_kernel(
     const StepFlags flags{a.draw[b], a.keep[b], *(a.klen != nullptr ? a.klen + b : a.token + b)};
     TokenLogp lp{NAN, NAN};                            // like `drawn`, the pair reaches post in registers
     Grammar g{nullptr, 0, nullptr, 0, 0, 0};
-    if constexpr (GRAM) {
+    if constexpr (TIER >= T_GRAM) {
         // the slot's switch is loaded with the flags above (a null gram_on reads draw[b], which is then ignored).  The
         // previous token is one dependent load behind the record: the sampling body issues it right behind its logits
         // loads -- issued here, the wait for the record came BEFORE the logits loads and they sat behind it
@@ -161,7 +145,7 @@ __global__ __launch_bounds__(64) void sample_post_pre_kernel(
                     a.gram_on != nullptr ? (int)on_b : 1};
     }
     Harmony h{nullptr, 0, nullptr, 0, 0, 0};
-    if constexpr (HARM) {
+    if constexpr (TIER >= T_HARM) {
         // the same for the chord: the switch with the flags, the record's chord count as it was loaded; the chord token
         // chord_tok[b][F_CUR - 1] is the body's load, beside the previous token
         const unsigned char on_b = *(a.harm_on != nullptr ? a.harm_on + b : a.draw + b);
@@ -169,23 +153,23 @@ __global__ __launch_bounds__(64) void sample_post_pre_kernel(
                     a.harm_on != nullptr ? (int)on_b : 1};
     }
     ClassControls cc{nullptr};
-    if constexpr (CLS) cc = ClassControls{a.cls_ctl + (size_t)b * 8};      // (the body loads the record it selects)
+    if constexpr (TIER >= T_CLS) cc = ClassControls{a.cls_ctl + (size_t)b * 8};      // (the body loads the record it selects)
+    // the control words are loaded with the flags above; the bar count of the onset row is the record's
     NoteOrder no{-1};
-    if constexpr (ORD) no = NoteOrder{a.order_ctl[b]};                      // (the control word with the flags above)
+    if constexpr (TIER >= T_ORD) no = NoteOrder{a.order_ctl[b]};
     Voices vx{-1};
-    if constexpr (VOX) vx = Voices{a.voice_ctl[b]};                         // (likewise)
+    if constexpr (TIER >= T_VOX) vx = Voices{a.voice_ctl[b]};
     Density dn{-1};
-    if constexpr (DEN) dn = Density{a.density_ctl[b]};                      // (likewise)
+    if constexpr (TIER >= T_DEN) dn = Density{a.density_ctl[b]};
     Interval ml{-1};
-    if constexpr (MEL) ml = Interval{a.interval_ctl[b]};                    // (likewise)
+    if constexpr (TIER >= T_MEL) ml = Interval{a.interval_ctl[b]};
     Onsets os{-1, nullptr, 1, 0};
-    if constexpr (ONS) os = Onsets{a.onset_ctl[b], a.onset_table, a.onset_rows, rec[F_NBAR]};      // (likewise; the bar count
-                                                                                                   // is the record's)
+    if constexpr (TIER >= T_ONS) os = Onsets{a.onset_ctl[b], a.onset_table, a.onset_rows, rec[F_NBAR]};
     Guide gd{-1, nullptr, 1};
-    if constexpr (GDE) gd = Guide{a.guide_ctl[b], a.guide_table, a.guide_rows};                    // (likewise)
+    if constexpr (TIER >= T_GDE) gd = Guide{a.guide_ctl[b], a.guide_table, a.guide_rows};
     Articulation ar{-1, nullptr, 1};
-    if constexpr (ART) ar = Articulation{a.art_ctl[b], a.art_table, a.art_rows};                   // (likewise)
-    const int drawn = sample_topk_body<BIAS, GRAM, HARM, CLS, ORD, VOX, DEN, MEL, ONS, GDE, ART>(
+    if constexpr (TIER >= T_ART) ar = Articulation{a.art_ctl[b], a.art_table, a.art_rows};
+    const int drawn = sample_topk_body<BIAS, TIER>(
         b, lane, a.logits, a.ld, a.V, a.wrong, VOCAB, a.uni, a.draw, a.temperature, a.top_k, a.token, a.probs_out, a.ldp,
         a.top_p, a.rows, a.logp != nullptr || a.seq_logp != nullptr, a.logp, lp, a.bias, a.ld_bias, g, h, cc, no, vx, dn, ml,
         os, gd, ar);
@@ -364,42 +348,9 @@ extern "C" int commu_decode_sample_post_pre(const commu_decode_loop_args* p, hip
     if (p->cls_ctl == nullptr &&
         ((p->top_k_rows == nullptr && (p->top_k < 1 || p->top_k > V)) || (p->top_p_rows == nullptr && !(p->top_p > 0.f))))
         return -22;
-    if (p->bias != nullptr && p->ld_bias < V) return -22;    // (the kernel reads bias[b][0 .. V-1])
-    // (the kernel reads gram[0 .. 7][0 .. V-1] and finds the previous token through the record)
-    if (p->gram != nullptr && (p->ld_gram < V || p->state == nullptr || p->seq == nullptr)) return -22;
-    // (the kernel reads harm[0 .. 110][0 .. 11] and finds the chord through the record: chord_tok[b][F_CUR - 1]; one
-    // instantiation: the caller passes a zero bias and an all-off grammar where it has none)
-    if (p->harm != nullptr && (p->ld_harm < 12 || p->chord_tok == nullptr || p->bias == nullptr || p->gram == nullptr))
-        return -22;
-    // (the kernel reads cls_ctl[b][0 .. 7] as 16-byte records; one instantiation, the harmony kernel's with the table)
-    if (p->cls_ctl != nullptr && (p->state == nullptr || p->seq == nullptr || p->bias == nullptr || p->gram == nullptr ||
-                                  p->harm == nullptr || p->chord_tok == nullptr ||
-                                  (reinterpret_cast<uintptr_t>(p->cls_ctl) & 15u) != 0))
-        return -22;
-    // (the kernel reads order_ctl[b] and walks seq[b] backwards from the record's length; one instantiation, the class
-    // kernel's with the scan)
-    if (p->order_ctl != nullptr && p->cls_ctl == nullptr) return -22;
-    // (the kernel reads voice_ctl[b] and continues the note order's walk to the second BAR; one instantiation)
-    if (p->voice_ctl != nullptr && p->order_ctl == nullptr) return -22;
-    // (the kernel reads density_ctl[b] and counts the open bar's notes on the voice cap's walk; one instantiation)
-    if (p->density_ctl != nullptr && p->voice_ctl == nullptr) return -22;
-    // (the kernel reads interval_ctl[b] and finds the reference note on the voice cap's walk; one instantiation)
-    if (p->interval_ctl != nullptr && p->density_ctl == nullptr) return -22;
-    // (the kernel reads onset_ctl[b] and one row of onset_table, its index clamped into the table; one instantiation)
-    if (p->onset_ctl != nullptr && (p->interval_ctl == nullptr || p->onset_table == nullptr || p->onset_rows < 1 ||
-                                    p->onset_rows > ONS_ROWS_MAX))
-        return -22;
-    // (the kernel reads guide_ctl[b] and two rows of guide_table, their indices clamped into the table; one instantiation)
-    if (p->guide_ctl != nullptr && (p->onset_ctl == nullptr || p->guide_table == nullptr || p->guide_rows < 1 ||
-                                    p->guide_rows > GDE_ROWS_MAX))
-        return -22;
-    // (the kernel reads art_ctl[b], one row of art_table, its index clamped into the table, and up to two words per lane of
-    // guide_table, their row indices clamped likewise; one instantiation)
-    if (p->art_ctl != nullptr && (p->guide_ctl == nullptr || p->art_table == nullptr || p->art_rows < 1 ||
-                                  p->art_rows > ART_ROWS_MAX))
-        return -22;
-    LoopStageArgsArt a;
-    static_cast<LoopStageArgs&>(a) = LoopStageArgs{
+    if (!check_constraints(*p, V)) return -22;
+    LoopArgs<T_ART> a;
+    static_cast<LoopArgs<T_NONE>&>(a) = LoopArgs<T_NONE>{
         p->logits, p->ld, V, p->wrong, p->temperature, p->top_k, p->top_p,
         SamplingRows{p->temperature_rows, p->top_k_rows, p->top_p_rows}, p->token, p->probs_out, p->ldp, p->logp, p->seq_logp,
         p->state, p->seq, p->ld_seq, p->chord_tok, p->chord_pos, p->ld_chord, p->utable, p->ld_u, p->max_iters, p->tok,
@@ -411,59 +362,24 @@ extern "C" int commu_decode_sample_post_pre(const commu_decode_loop_args* p, hip
     a.voice_ctl = p->voice_ctl;
     a.density_ctl = p->density_ctl;
     a.interval_ctl = p->interval_ctl;
-    a.onset_ctl = p->onset_ctl;
-    a.onset_table = p->onset_table;
-    a.onset_rows = p->onset_rows;
-    a.guide_ctl = p->guide_ctl;
-    a.guide_table = p->guide_table;
-    a.guide_rows = p->guide_rows;
-    a.art_ctl = p->art_ctl;
-    a.art_table = p->art_table;
-    a.art_rows = p->art_rows;
-    const LoopStageArgsGde& agd = a;
-    const LoopStageArgsOns& an = a;
-    const LoopStageArgsMel& am = a;
-    const LoopStageArgsDen& ad = a;
-    const LoopStageArgsVox& av = a;
-    const LoopStageArgsOrd& ao = a;
-    const LoopStageArgsCls& ac = a;
-    const LoopStageArgsHarm& ah = a;
-    const LoopStageArgsGram& ag = a;          // (each kernel gets the argument block of its own kind, by value)
-    const LoopStageArgs& a0 = a;
+    a.onset_ctl = p->onset_ctl; a.onset_table = p->onset_table; a.onset_rows = p->onset_rows;
+    a.guide_ctl = p->guide_ctl; a.guide_table = p->guide_table; a.guide_rows = p->guide_rows;
+    a.art_ctl = p->art_ctl; a.art_table = p->art_table; a.art_rows = p->art_rows;
     const dim3 grid(p->B), block(64);
-    // five kernels: without a bias / a grammar / a harmony table the launch is the one it always was (no added load, no
-    // added register, no added argument); a sixth for the class-keyed controls, a seventh for the note order, an eighth
-    // for the voice cap, a ninth for the note density, a tenth for the melodic interval, an eleventh for the onset templates,
-    // a twelfth for the guide track, a thirteenth for the articulation
-    if (p->art_ctl != nullptr) {
-        COMMU_LAUNCH((sample_post_pre_kernel<true, true, true, true, true, true, true, true, true, true, true>), grid, block,
-                     0, stream, a);
-    } else if (p->guide_ctl != nullptr) {
-        COMMU_LAUNCH((sample_post_pre_kernel<true, true, true, true, true, true, true, true, true, true>), grid, block, 0,
-                     stream, agd);
-    } else if (p->onset_ctl != nullptr) {
-        COMMU_LAUNCH((sample_post_pre_kernel<true, true, true, true, true, true, true, true, true>), grid, block, 0, stream,
-                     an);
-    } else if (p->interval_ctl != nullptr) {
-        COMMU_LAUNCH((sample_post_pre_kernel<true, true, true, true, true, true, true, true>), grid, block, 0, stream, am);
-    } else if (p->density_ctl != nullptr) {
-        COMMU_LAUNCH((sample_post_pre_kernel<true, true, true, true, true, true, true>), grid, block, 0, stream, ad);
-    } else if (p->voice_ctl != nullptr) {
-        COMMU_LAUNCH((sample_post_pre_kernel<true, true, true, true, true, true>), grid, block, 0, stream, av);
-    } else if (p->order_ctl != nullptr) {
-        COMMU_LAUNCH((sample_post_pre_kernel<true, true, true, true, true>), grid, block, 0, stream, ao);
-    } else if (p->cls_ctl != nullptr) {
-        COMMU_LAUNCH((sample_post_pre_kernel<true, true, true, true>), grid, block, 0, stream, ac);
-    } else if (p->harm != nullptr) {
-        COMMU_LAUNCH((sample_post_pre_kernel<true, true, true>), grid, block, 0, stream, ah);
-    } else if (p->gram != nullptr) {
-        if (p->bias != nullptr) COMMU_LAUNCH((sample_post_pre_kernel<true, true>), grid, block, 0, stream, ag);
-        else COMMU_LAUNCH((sample_post_pre_kernel<false, true>), grid, block, 0, stream, ag);
-    } else if (p->bias != nullptr) {
-        COMMU_LAUNCH((sample_post_pre_kernel<true, false>), grid, block, 0, stream, a0);
-    } else {
-        COMMU_LAUNCH((sample_post_pre_kernel<false, false>), grid, block, 0, stream, a0);
-    }
+    // one kernel per tier, each with the argument block of its own tier (by value), so that a launch below a tier is the one
+    // it always was: no added load, no added register, no added argument.  Below the harmony tier a bias is optional and
+    // the launch without one is a kernel of its own.
+    with_tier(tier_of(*p), [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        const auto& at = static_cast<const LoopArgs<T>&>(a);      // (each kernel gets the block of its own tier)
+        if constexpr (T < T_HARM) {
+            if (p->bias == nullptr) {
+                COMMU_LAUNCH((sample_post_pre_kernel<false, T>), grid, block, 0, stream, at);
+                return;
+            }
+        }
+        COMMU_LAUNCH((sample_post_pre_kernel<true, T>), grid, block, 0, stream, at);
+    });
     COMMU_LAUNCH_CHECK();
     return 0;
 }

@@ -22,7 +22,7 @@ def per_launch(db, counter):
     for name, cname, val, did in con.execute("select kernel_name, counter_name, value, dispatch_id from counters_collection"):
         if cname != counter:
             continue
-        m = re.search(r"(decode_attn_kernel|decode_tail_kernel<[^>]*>|sample_post_pre_kernel)", name)
+        m = re.search(r"(decode_attn_kernel|decode_tail_kernel<[^>]*>|sample_post_pre_kernel<[^>]*>)", name)      # (<BIAS, TIER>)
         if m:
             acc[m.group(1)] += val
             ids[m.group(1)].add(did)
