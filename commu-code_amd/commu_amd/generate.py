@@ -15,6 +15,7 @@ import collections
 import ctypes as C
 import dataclasses
 import functools
+import json
 import math
 from typing import Callable, List, NamedTuple, Optional, Sequence
 
@@ -1076,6 +1077,203 @@ def _articulation_per_slot(x, B: int):
     return [articulation_template(x)] * B
 
 
+# ---- form templates: one int32 control word per slot (commu_decode_loop_args.form_ctl) and one device table of 128-bit rows
+# (form_table).  Row base + i is bar i of the form: free, or a REPLAY of an earlier bar of the slot's own sequence.  The rule
+# lives in the forcing stage (csrc/decode_loop.h: Form): inside a replay bar the tokens of the source bar's note groups are
+# handed to the book-keeping as if drawn.  A form is not cycled: bars past its end are free.
+FORM_OFF = -1
+FORM_ROWS_MAX = 4096           # rows of the device table (64 KB); the word is base + 4096 R
+FORM_BARS_MAX = 64             # bars of one form
+FORM_TRANSPOSE_MAX = 48
+FORM_COPIES = ("all", "rhythm")
+FORM_BAR_KEYS = {"of", "copy", "transpose"}
+
+
+def form_word(base: int, bars: int) -> int:
+    """The control word base + 4096 R of a form of R bars that starts at table row base."""
+    return int(base) + FORM_ROWS_MAX * int(bars)
+
+
+def form_row_word(src: int, copy: str = "all", transpose: int = 0) -> int:
+    """Word 0 of a replay row: src | copy << 6 | (transpose + 64) << 8 (a free bar's word is 0)."""
+    return int(src) | (FORM_COPIES.index(copy) << 6) | ((int(transpose) + 64) << 8)
+
+
+def form_row_fields(word: int):
+    """(src, copy, transpose) of a row's word 0, None for a free bar."""
+    word = int(word)
+    if (word >> 8) & 127 == 0:
+        return None
+    return word & 63, FORM_COPIES[(word >> 6) & 1], ((word >> 8) & 127) - 64
+
+
+def _form_bar(i: int, bar) -> int:
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if bar is None:
+        return 0
+    if is_int(bar):
+        bar = {"of": bar}
+    if not isinstance(bar, dict):
+        raise CommuHipError(f'form: bar {i}: null, a bar index or {{"of": j, "copy": "all" | "rhythm", "transpose": s}} '
+                            f"expected, got {bar!r}")
+    extra = sorted(set(map(str, bar)) - FORM_BAR_KEYS)
+    if extra:
+        raise CommuHipError(f"form: bar {i}: unknown key {extra[0]!r} (known: {sorted(FORM_BAR_KEYS)})")
+    if "of" not in bar or not is_int(bar["of"]) or bar["of"] < 0:
+        raise CommuHipError(f'form: bar {i}: "of": the index of an earlier bar expected, got {bar.get("of")!r}')
+    if bar["of"] >= i:
+        raise CommuHipError(f'form: bar {i}: "of": {bar["of"]} is not an earlier bar (a bar replays one below its own index'
+                            + ("; bar 0 is always free)" if i == 0 else ")"))
+    copy = bar.get("copy", "all")
+    if copy not in FORM_COPIES:
+        raise CommuHipError(f'form: bar {i}: "copy": "all" or "rhythm" expected, got {copy!r}')
+    s = bar.get("transpose", 0)
+    if not is_int(s) or not -FORM_TRANSPOSE_MAX <= s <= FORM_TRANSPOSE_MAX:
+        raise CommuHipError(f'form: bar {i}: "transpose": semitones in -{FORM_TRANSPOSE_MAX} .. {FORM_TRANSPOSE_MAX} '
+                            f"expected, got {s!r}")
+    if s != 0 and copy == "rhythm":
+        raise CommuHipError(f'form: bar {i}: "transpose": {s} beside "copy": "rhythm" (the pitches of such a bar are drawn)')
+    return form_row_word(bar["of"], copy, s)
+
+
+def form_template(x) -> np.ndarray:
+    """A form as uint32 [R][4], one row per bar (word 0: form_row_word, 0 for a free bar; words 1 .. 3 are 0).  x: a letter
+    string such as "AABA" -- the first bar with a letter is free, later ones replay it in full; {"bars": [null | j |
+    {"of": j, "copy": "all" | "rhythm", "transpose": s}, ...]} -- bar i is free or replays bar j < i, everything or the
+    rhythm only (the pitches are then drawn), transposed by s semitones (all only, -48 .. 48); JSON text or the path of a
+    file holding either; or a uint32 array [R][4] that is one already.  1 <= R <= 64, bar 0 is always free.  Pure host code;
+    raises CommuHipError that names the bar."""
+    if isinstance(x, np.ndarray) and x.dtype == np.uint32:
+        if x.ndim != 2 or x.shape[1] != 4 or not 1 <= x.shape[0] <= FORM_BARS_MAX:
+            raise CommuHipError(f"form: a uint32 form is [1 .. {FORM_BARS_MAX}][4], got shape {x.shape}")
+        for i, w in enumerate(x[:, 0].tolist()):
+            f = form_row_fields(w)
+            ok = f is None and w == 0 or f is not None and w >> 15 == 0 and f[0] < i and abs(f[2]) <= FORM_TRANSPOSE_MAX \
+                and not (f[1] == "rhythm" and f[2] != 0)
+            if not ok or x[i, 1:].any():
+                raise CommuHipError(f"form: bar {i}: not a row of a form: {x[i].tolist()}")
+        return np.ascontiguousarray(x)
+    if isinstance(x, str):
+        text = x.strip()
+        if not text.isalpha() and not text.startswith(("{", "[", '"')):
+            try:
+                with open(x) as f:
+                    text = f.read().strip()
+            except OSError as e:
+                raise CommuHipError(f"form: letters, JSON text or a readable file expected, got {x!r} ({e.strerror})") from None
+        if text.isalpha():
+            first = {}
+            x = {"bars": [None if first.setdefault(c, i) == i else first[c] for i, c in enumerate(text)]}
+        else:
+            try:
+                doc = json.loads(text)
+            except json.JSONDecodeError as e:
+                raise CommuHipError(f"form: not JSON ({e})") from None
+            if isinstance(doc, str) and not doc.isalpha():
+                raise CommuHipError(f"form: a letter string such as \"AABA\" expected, got {doc!r}")
+            return form_template(doc)
+    if not isinstance(x, dict) or set(x) != {"bars"} or not isinstance(x["bars"], (list, tuple)):
+        raise CommuHipError('form: a letter string or {"bars": [null | j | {"of": j, "copy": ..., "transpose": s}, ...]} '
+                            f"expected, got {x!r}")
+    bars = x["bars"]
+    if not 1 <= len(bars) <= FORM_BARS_MAX:
+        raise CommuHipError(f"form: a form holds 1 .. {FORM_BARS_MAX} bars, got {len(bars)}" +
+                            (f" (bar {FORM_BARS_MAX} is one too many)" if bars else ""))
+    out = np.zeros((len(bars), 4), dtype=np.uint32)
+    for i, bar in enumerate(bars):
+        out[i, 0] = _form_bar(i, bar)
+    return out
+
+
+def form_is_rhythm(rows) -> bool:
+    """Does a form (uint32 rows) hold a bar in rhythm mode?"""
+    return any(f is not None and f[1] == "rhythm" for f in map(form_row_fields, rows[:, 0].tolist()))
+
+
+def _form_needs_grammar(forms, gram_on):
+    """A rhythm bar draws its pitches: without the event grammar the draw at that place need not be a pitch.  Refused where
+    a sequence asks for one and its grammar is off.  gram_on: the sequences whose grammar is on."""
+    on = set(int(b) for b in gram_on)
+    for i, f in enumerate(forms):
+        if f is not None and form_is_rhythm(f) and i not in on:
+            raise CommuHipError('form: "copy": "rhythm" without the event grammar' +
+                                (f" (sequence {i})" if len(forms) > 1 else "") +
+                                ": the pitch of such a bar is drawn, and only the grammar makes that draw a pitch")
+
+
+def _form_per_slot(x, B: int):
+    """A request's form= as B entries, each None (off) or a form's uint32 rows: None / False (all off), one form in any form
+    form_template takes (all slots), or a list of B entries each None / False or a form."""
+    B = int(B)
+    if x is None or x is False:
+        return [None] * B
+    if isinstance(x, list):
+        if len(x) != B:
+            raise CommuHipError(f"form: {B} entries expected (one per sequence), got {len(x)}")
+        return [None if (v is None or v is False) else form_template(v) for v in x]
+    return [form_template(x)] * B
+
+
+def _form_fold(pitch_token: int, s: int) -> int:
+    m = int(pitch_token) - 3 + int(s)
+    while m < 0:
+        m += 12
+    while m > 127:
+        m -= 12
+    return m + 3
+
+
+def form_violation(seq, start: int, template, drawn=None):
+    """The checker of the form rule, shared by the tests and by users: the first CLOSED replay bar of seq whose note groups
+    do not match its source bar under the row's mode, as (bar, source bar, reason), else None.  Bar i is the stretch between
+    the (i+1)-th Bar token and the next Bar (or the Eos that replaced it); it is closed when that token exists.  A bar is a
+    replay bar when the form's row says so AND the loop opened it itself: its Bar token lies at index >= start (the bar a
+    prompt leaves open is free).  Its note groups (Position, Velocity, Pitch, Duration, found one behind the other as the
+    rule finds them) must equal the source's one for one -- the pitch transposed and folded into 0 .. 127 (all), or any
+    pitch (rhythm).  template: anything form_template takes.  drawn (optional, parallel to seq): True where a token was drawn
+    by the sampling step (it has a log-probability); then the replayed tokens must not be, and the pitches of a rhythm bar
+    must be."""
+    rows = form_template(template)
+    seq = [int(t) for t in seq]
+    bar_at = [i for i, t in enumerate(seq) if t == ONSET_BAR]
+
+    def close_of(i):
+        nxt = bar_at[i + 1] if i + 1 < len(bar_at) else None
+        if nxt is None and seq and seq[-1] == 1 and bar_at:            # (the Eos that replaced the last Bar)
+            nxt = len(seq) - 1
+        return nxt
+
+    def groups(i):
+        out, g, end = [], bar_at[i] + 1, close_of(i)
+        while g + 3 < end:
+            if _is_note_at(seq, g) and g + 3 < end:
+                out.append(g)
+                g += 4
+            else:
+                g += 1
+        return out
+    for i in range(min(len(bar_at), len(rows), FORM_BARS_MAX)):
+        f = form_row_fields(rows[i, 0])
+        if f is None or bar_at[i] < int(start) or close_of(i) is None or close_of(i) <= bar_at[i]:
+            continue
+        j, copy, s = f
+        src, dst = groups(j), groups(i)
+        if len(src) != len(dst):
+            return i, j, f"{len(dst)} note groups, the source has {len(src)}"
+        for a, b in zip(src, dst):
+            want = [seq[a], seq[a + 1], _form_fold(seq[a + 2], s), seq[a + 3]]
+            got = seq[b:b + 4]
+            if copy == "rhythm":
+                want[2] = got[2]
+            if want != got:
+                return i, j, f"group at index {b} is {got}, the source's at {a} gives {want}"
+            if drawn is not None:
+                d = [bool(drawn[b + k]) for k in range(4)]
+                if d != [False, False, copy == "rhythm", False]:
+                    return i, j, f"group at index {b}: drawn flags {d}"
+    return None
+
+
 class DecodeState:
     """K/V caches + distance-indexed R tables for B sequences of up to Lmax positions.
 
@@ -1579,6 +1777,11 @@ ARTICULATION = SlotRule(T_ART, "art", "articulation", ARTICULATION_OFF, "articul
                         rows_of=lambda t: t[0], key=lambda t: t[0].tobytes(), bars=lambda t: t[0].shape[0],
                         word=lambda base, bars, t: articulation_word(base, bars, t[1], t[2]))
 SLOT_RULES = (ORDER, VOICES, DENSITY, INTERVAL, ONSETS, GUIDE, ARTICULATION)
+# (the form rule is no tier of the sampling step: it lives in the forcing stage and its switch is its own, so it is not in
+# SLOT_RULES; the one template packer serves it.  A template is the uint32 rows; a free row is all zeros.)
+FORM = SlotRule(-1, "form", "form", FORM_OFF, "form", FORM_ROWS_MAX, FORM_BARS_MAX, (0, 0, 0, 0),
+                rows_of=lambda t: t, key=lambda t: t.tobytes(), bars=lambda t: t.shape[0],
+                word=lambda base, bars, t: form_word(base, bars))
 
 
 class ForcedDecoder:
@@ -1616,6 +1819,17 @@ class ForcedDecoder:
     _art_table_host = None
     _art_used = 0
     _art_index = None
+
+    # form templates (set_form): the same six for the form's control words and its table of FORM_ROWS_MAX rows (64 KB), and
+    # the two arrays the rule keeps per slot: the replay state int32 [B][commu_form_state_ints()] and the replay token [B]
+    form_ctl = None
+    _form_host = None
+    form_table = None
+    _form_table_host = None
+    _form_used = 0
+    _form_index = None
+    form_state = None
+    form_tok = None
 
     def __init__(self, model, B: int, generation_length: int, memory_length: int, temperature: float, top_k: int,
                  max_chords: int = 64, record_trace: bool = False, top_p: float = 1.0, sliding: bool = False,
@@ -2216,7 +2430,72 @@ class ForcedDecoder:
         tmpl = _articulation_per_slot(value, len(idx))         # (validated before anything changes)
         self._set_templates(ARTICULATION, tmpl, idx, rows)
 
+    def set_form(self, value, rows: Optional[Sequence[int]] = None):
+        """The form for all slots (rows=None) or the listed ones: a form in any form form_template takes -- a letter string
+        "AABA", {"bars": [null | j | {"of": j, "copy": "all" | "rhythm", "transpose": s}, ...]}, uint32 rows -- None / False
+        (off), or a list with one such value per addressed slot.  A bar that the loop of a slot that is on OPENS ITSELF and
+        whose row names an earlier bar REPLAYS that bar's note groups (Position, Velocity, Pitch, Duration) through the
+        forcing stage: the tokens are handed to the book-keeping as if drawn, so every forcing rule applies to them -- the
+        bar gets the chords of its own place in the progression --, no variate is consumed, and their log-probability pairs
+        are NaN.  "rhythm": the pitches are drawn, under every constraint the slot has (the slot's grammar must be on: the
+        generator refuses the request otherwise).  A prompt's bars are valid sources; the bar a prompt leaves open is free.
+        A form is not cycled: bars past its end (and past the 64th) are free.  Not covered: replayed tokens are not checked
+        against any constraint (forced tokens are not either); a replay bar cut by the generation length is not completed; a
+        source note the bar line cut does not appear; chord tokens are never copied.
+        Like set_articulation: the first call that switches a slot on allocates the [B] words, the table of 4096 rows
+        (64 KB) -- ONCE, so that its address stays fixed under graph capture --, the slots' replay state and replay tokens,
+        and drops the captured graphs once (the loop launches the form kernels from then on); it allocates nothing of the
+        sampling tiers.  Later calls pack new forms behind the ones in the table and rewrite words and rows IN PLACE, ordered
+        on the current stream: no re-capture.  A word takes effect at the next Bar the slot appends; load() and rearm()
+        reset the slot's replay state.  A call for all slots packs the table anew.  A slot that is off decodes bit for bit
+        what it decoded without the feature; a decoder that never switched a slot on allocates nothing and launches the
+        kernels it always launched."""
+        idx = self._slots(rows)
+        tmpl = _form_per_slot(value, len(idx))                 # (validated before anything changes)
+        r = FORM
+        if self.form_ctl is None:
+            if all(t is None for t in tmpl):
+                return
+            need = sum(t.shape[0] for t in {t.tobytes(): t for t in tmpl if t is not None}.values())
+            if need > r.rows_max:
+                raise CommuHipError(f"{r.label}: the distinct templates need more than the table's {r.rows_max} rows "
+                                    f"(0 in use, {need} asked for)")
+        self._first_use_form()
+        self._write_words(r, idx, self._pack(r, tmpl, fresh=rows is None), rows)
+
+    def _first_use_form(self):
+        """What the first form allocates: the words (all off), the table (all free), the slots' replay state and replay
+        tokens; the captured graphs are dropped, once: they hold the launches without the rule."""
+        if self.form_ctl is not None:
+            return
+        B, i32 = self.B, torch.int32
+        self.form_ctl = torch.full((B,), FORM_OFF, dtype=i32, device=self.dev)
+        self._form_host = np.full(B, FORM_OFF, dtype=np.int32)
+        self._form_table_host = np.zeros((FORM.rows_max, 4), dtype=np.uint32)
+        self.form_table = torch.zeros(FORM.rows_max, 4, dtype=i32, device=self.dev)
+        self._form_used, self._form_index = 0, {}
+        self.form_state = torch.zeros(B, call("commu_form_state_ints"), dtype=i32, device=self.dev)
+        self.form_tok = torch.full((B,), -1, dtype=i32, device=self.dev)
+        self._form_reset(0, B)
+        self.graph = self.graph_long = None
+
+    def _form_reset(self, first: int, n: int):
+        """The replay state of slots first .. first + n - 1 as a load leaves it: nothing replayed, the Bars of seq recorded."""
+        if self.form_ctl is not None:
+            call("commu_form_reset", _p(self.form_state), _p(self.form_tok), _p(self.fsm), _p(self.seq), self.ld_seq,
+                 int(first), int(n), _s())
+
+    def _form_args(self):
+        """The five form arguments of the stand-alone stages, in order."""
+        return _p(self.form_ctl), _p(self.form_table), FORM.rows_max, _p(self.form_state), _p(self.form_tok)
+
     def pre(self):
+        if self.form_ctl is not None:
+            call("commu_forcing_pre_form", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_tok), _p(self.chord_pos),
+                 self.ld_chord, _p(self.wrong), _p(self.utable), self.ld_u, self.generation_length, _p(self.tok),
+                 _p(self.active), _p(self.keep), _p(self.draw), _p(self.uni), _p(self.trace), self.ld_trace,
+                 _p(self._rows_args()[4]), *self._form_args(), self.B, _s())
+            return
         call("commu_forcing_pre", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_tok), _p(self.chord_pos),
              self.ld_chord, _p(self.wrong), _p(self.utable), self.ld_u, self.generation_length, _p(self.tok),
              _p(self.active), _p(self.keep), _p(self.draw), _p(self.uni), _p(self.trace), self.ld_trace,
@@ -2235,6 +2514,11 @@ class ForcedDecoder:
                         **({} if self.harm is None else {"harmony": self._harm_args()}),
                         **({} if self.cls_ctl is None else {"class_ctl": self._cls_args()}),
                         **{r.kw: (w, getattr(self, r.table)) if r.rows_max else w for r, w in self._slot_words()})
+        if self.form_ctl is not None:
+            call("commu_forcing_post_form", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_pos), self.ld_chord,
+                 _p(self.wrong), _p(self.draw), _p(self.token), None, _p(self.state.klen), _p(self.keep),
+                 self.state.klen_cap, _p(logp), _p(seq_logp), *self._form_args(), B, _s())
+            return
         call("commu_forcing_post", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_pos), self.ld_chord,
              _p(self.wrong), _p(self.draw), _p(self.token), None, _p(self.state.klen), _p(self.keep),
              self.state.klen_cap, _p(logp), _p(seq_logp), B, _s())
@@ -2253,6 +2537,9 @@ class ForcedDecoder:
             cons[r.ctl] = _p(w)
             if r.rows_max:
                 cons.update({r.table: _p(getattr(self, r.table)), r.stem + "_rows": r.rows_max})
+        if self.form_ctl is not None:          # (the form kernels; a decoder that never had a form: the launch it always made)
+            cons.update(form_ctl=_p(self.form_ctl), form_table=_p(self.form_table), form_rows=FORM.rows_max,
+                        form_state=_p(self.form_state), form_tok=_p(self.form_tok))
         a = struct_args(
             DecodeLoopArgs, logits=_p(st.logits), ld=st.logits.stride(0), V=TOKEN_OFFSET.VOCAB_SIZE, B=self.B,
             wrong=_p(self.wrong), temperature=self.temperature, top_k=self.top_k, top_p=self.top_p, temperature_rows=_p(t_r),
@@ -2288,6 +2575,8 @@ class ForcedDecoder:
         # (the K/V rows the warm-up appends at klen are rewritten by the real run: the caches need no copy)
         bufs = (self.fsm, self.seq, self.wrong, st.klen, st.logits, self.tok, self.active, self.keep, self.draw, self.uni,
                 self.seq_logp, self.logp)
+        if self.form_ctl is not None:
+            bufs += (self.form_state, self.form_tok)
         saved = [t.clone() for t in bufs]
         tr = None if self.trace is None else self.trace.clone()
         keep_splits, st.attn_splits = st.attn_splits, (self.LONG_SPLITS if long else 1)
@@ -2505,6 +2794,7 @@ class ForcedDecoder:
             self._prime(ctx, prompts)
             if self.sliding:
                 self._keep_ring_rows(self.klen0)
+        self._form_reset(0, B)          # (after the replay: a prompt's bars are valid sources, the bar it leaves open is free)
 
     # ---- slots: a finished sequence's slot can be re-armed for another attempt of the SAME request (same conditioning
     # tokens and chords) without touching the other slots: the context rows of its K/V cache are what they were, so only
@@ -2529,9 +2819,13 @@ class ForcedDecoder:
     # guide: the slot's guide track for its next attempt (set_guide's values, False: off; None: the slot keeps its word).
     # articulation: the slot's articulation for its next attempt (set_articulation's values, False: off; None: the slot keeps
     # its word).
+    # form: the slot's form for its next attempt (set_form's values, False: off; None: the slot keeps its word); the slot's
+    # replay state is reset with its record whatever the form.
     def rearm(self, b: int, uniforms_row: Optional[np.ndarray] = None, sampling=None, logit_bias=None, grammar=None,
               harmony=None, note_order=None, voices=None, density=None, interval=None, onsets=None, guide=None,
-              articulation=None):
+              articulation=None, form=None):
+        if form is not None:
+            self.set_form(form, rows=[b])
         if note_order is not None:
             self.set_note_order(note_order, rows=[b])
         if voices is not None:
@@ -2569,6 +2863,7 @@ class ForcedDecoder:
             rec = [1 + self.n_cond, -1, 0, 1, int(rep.num_measures % 4 == 0), 0, 0, 0, 0, rep.n_chords, 0,
                    int(rep.length_fit), 0, 0]
             self.fsm[b].copy_(torch.tensor(rec, dtype=torch.int32))
+        self._form_reset(b, 1)                # (seq[b] up to the record's length is the context and the prompt)
         self.wrong[b].zero_()
         self.seq_logp[b].fill_(float("nan"))
         if self.sliding:
@@ -2722,6 +3017,7 @@ class ForcedDecoder:
         idle[:, 0], idle[:, 1], idle[:, 5] = 1, -1, 1          # len 1 (seq[0] = 0), nothing forced, done
         self.fsm.copy_(torch.from_numpy(idle))
         self.seq.zero_()
+        self._form_reset(0, B)
         self.seq_logp.fill_(float("nan"))
         self.logp.fill_(float("nan"))
         self.wrong.zero_()
@@ -2751,6 +3047,7 @@ class ForcedDecoder:
                 "e_onset": torch.full((R,), ONSETS_OFF, dtype=i32, device=dev),
                 "e_guide": torch.full((R,), GUIDE_OFF, dtype=i32, device=dev),
                 "e_art": torch.full((R,), ARTICULATION_OFF, dtype=i32, device=dev), "e_cls": z(R, N_CLASSES + 1, 4),
+                "e_form": torch.full((R,), FORM_OFF, dtype=i32, device=dev),
                 "hdr": hdr, "stage": z(words),
                 # two pinned staging buffers and an event each: the host never overwrites a buffer whose copy is in flight
                 "pin": [torch.zeros(words, dtype=i32).pin_memory() for _ in range(2)],
@@ -2775,7 +3072,7 @@ class ForcedDecoder:
         """The arm launch's argument block, rebuilt when an optional array was allocated since (a null twin: not written)."""
         P = self._pool
         opt = (self.bias, self.gram_on, self.harm_on, self.order_ctl, self.voice_ctl, self.density_ctl, self.interval_ctl,
-               self.onset_ctl, self.guide_ctl, self.art_ctl, self.cls_ctl, self.trace)
+               self.onset_ctl, self.guide_ctl, self.art_ctl, self.cls_ctl, self.trace, self.form_ctl)
         sig = tuple(None if t is None else t.data_ptr() for t in opt)
         if P["args"] is None or P["sig"] != sig:
             st = self.state
@@ -2802,6 +3099,8 @@ class ForcedDecoder:
                 **on(self.onset_ctl, {"onset_ctl": self.onset_ctl, "e_onset": P["e_onset"]}),
                 **on(self.guide_ctl, {"guide_ctl": self.guide_ctl, "e_guide": P["e_guide"]}),
                 **on(self.art_ctl, {"art_ctl": self.art_ctl, "e_art": P["e_art"]}),
+                **on(self.form_ctl, {"form_ctl": self.form_ctl, "e_form": P["e_form"], "form_state": self.form_state,
+                                     "form_tok": self.form_tok}),
                 **on(self.cls_ctl, {"cls_ctl": self.cls_ctl, "e_cls": P["e_cls"]}))
             P["sig"] = sig
         if P["primed"]:
@@ -2810,13 +3109,14 @@ class ForcedDecoder:
 
     def admit(self, entry: int, encoded_meta: Sequence[int], input_data, sampling=None, logit_bias=None, grammar=False,
               harmony=False, note_order=None, voices=None, class_table=None, primed=None, density=None, interval=None,
-              onsets=None, guide=None, articulation=None):
+              onsets=None, guide=None, articulation=None, form=None):
         """Compose store entry `entry` for a request and upload it with its K/V image: the state record, sequence head
         and chord rows as load() builds them, klen0 = n_cond, the sampling triple (None: the decoder's), the bias row
         (None: zeros), the grammar and harmony switches (they switch on what the decoder has a table for), the
         note-order, voice, density and interval words (None: off), the onset word of the template `onsets` (None: off; the
         template's rows go to the decoder's own table, where the same template is stored once -- no table bytes move per arm),
-        the guide word of the guide track `guide` (likewise), the articulation word of `articulation` (likewise) and, where the decoder has class records, the request's record row
+        the guide word of the guide track `guide` (likewise), the articulation word of `articulation` (likewise), the form word of `form` (likewise; the arm launch resets the slot's
+        replay state and records the Bars of the entry's sequence head) and, where the decoder has class records, the request's record row
         (class_table: its NaN-table, None: the base triple in every record).  The image is written by ONE memory-less
         forward over this request's single column [n_cond, 1] and the prefill scatter of the cache's format into the
         store: it does not depend on what else is admitted or decoding.  Everything is ordered on the current stream.
@@ -2849,6 +3149,11 @@ class ForcedDecoder:
         art = _articulation_per_slot(articulation, 1)
         if art[0] is not None and self.art_ctl is None:
             raise CommuHipError("admit: an articulation, but the decoder has no articulation words (set_articulation)")
+        frm = _form_per_slot(form, 1)
+        if frm[0] is not None and self.form_ctl is None:
+            raise CommuHipError("admit: a form, but the decoder has no form words (set_form)")
+        if frm[0] is not None:
+            _form_needs_grammar(frm, [0] if grammar else [])
         if grammar and (self.gram is None or self._gram_host is None):
             raise CommuHipError("admit: grammar switched on, but the decoder has no grammar table (set_grammar)")
         if harmony and (self.harm is None or self._harm_host is None):
@@ -2914,6 +3219,7 @@ class ForcedDecoder:
         P["e_onset"][entry].fill_(int(ONSETS_OFF if ons[0] is None else self._pack(ONSETS, ons)[0]))
         P["e_guide"][entry].fill_(int(GUIDE_OFF if gde[0] is None else self._pack(GUIDE, gde)[0]))
         P["e_art"][entry].fill_(int(ARTICULATION_OFF if art[0] is None else self._pack(ARTICULATION, art)[0]))
+        P["e_form"][entry].fill_(int(FORM_OFF if frm[0] is None else self._pack(FORM, frm)[0]))
         if self.cls_ctl is not None:
             tab = np.full((1, N_CLASSES + 1, 3), np.nan) if class_table is None else class_sampling_table(class_table)[None]
             rec = class_ctl_records(tab, [t, k, p])
@@ -3139,6 +3445,7 @@ class PoolRequest:
     onsets: Optional[object] = None
     guide: Optional[object] = None
     articulation: Optional[object] = None
+    form: Optional[object] = None          # ONE form in any form form_template takes ("copy": "rhythm" needs the grammar on)
 
 
 PoolResult = collections.namedtuple("PoolResult", ["sequences", "attempts_started", "logprobs"])
@@ -3262,7 +3569,8 @@ class BatchedGenerator:
 
     def decoder(self, B, temperature, top_k, max_chords, top_p=1.0, per_slot: bool = False, max_prompt: int = 0,
                 logit_bias=None, shared: bool = False, grammar=None, harmony=None, class_sampling=None,
-                note_order=None, voices=None, density=None, interval=None, onsets=None, guide=None, articulation=None):
+                note_order=None, voices=None, density=None, interval=None, onsets=None, guide=None, articulation=None,
+                form=None):
         """The decoder for B slots, its slots set to the given controls (numbers or one value per slot).  per_slot: the
         caller will read log-probabilities or give slots their own controls later (rearm): the array launches from the
         start.  Otherwise one triple for all slots runs the scalar launches, until a second setting arrives for launches
@@ -3277,7 +3585,9 @@ class BatchedGenerator:
         on.  interval: the request's interval words (interval_ctl), likewise; it switches nothing else on.  onsets: the request's onset templates (one for all
         sequences or one per sequence, ForcedDecoder.set_onsets), likewise.  guide: the request's guide tracks (one for
         all sequences or one per sequence, ForcedDecoder.set_guide), likewise.  articulation: the request's articulations
-        (one for all sequences or one per sequence, ForcedDecoder.set_articulation), likewise.  shared: the
+        (one for all sequences or one per sequence, ForcedDecoder.set_articulation), likewise.  form: the request's forms
+        (one for all sequences or one per sequence, ForcedDecoder.set_form), likewise; a rhythm bar needs the sequence's
+        grammar on.  shared: the
         decoder that holds the
         request's common prompt once (its own cache layout: kept beside the unshared decoder of the same size)."""
         rows = sampling_rows(B, temperature, top_k, top_p)          # (validated before anything is built)
@@ -3294,6 +3604,8 @@ class BatchedGenerator:
         gde = _guide_per_slot(guide, B)
         art = _articulation_per_slot(articulation, B)
         _articulation_needs_guide(art, gde)
+        frm = _form_per_slot(form, B)
+        _form_needs_grammar(frm, gram_rows)
         key = (B, self.trace is not None, self.sliding) + (("shared",) if shared else ())
         dec = self._decoders.get(key)
         if dec is None or dec.ld_chord < max_chords or dec.max_prompt < max_prompt:
@@ -3330,6 +3642,8 @@ class BatchedGenerator:
         dec.set_guide(gde)
         # (articulation: likewise)
         dec.set_articulation(art)
+        # (form: likewise)
+        dec.set_form(frm)
         return dec
 
     @staticmethod
@@ -3343,8 +3657,11 @@ class BatchedGenerator:
     def generate(self, encoded_metas: Sequence[Sequence[int]], input_datas, temperature, top_k, top_p=1.0,
                  return_logprobs: bool = False, prompts: Optional[Sequence[Sequence[int]]] = None, logit_bias=None,
                  grammar=None, harmony=None, class_sampling=None, note_order=None, voices=None, density=None,
-                 interval=None, onsets=None, guide=None, articulation=None):
-        """temperature / top_k / top_p: a number for the batch or one value per sequence.  articulation: None / False, one
+                 interval=None, onsets=None, guide=None, articulation=None, form=None):
+        """temperature / top_k / top_p: a number for the batch or one value per sequence.  form: None / False, one form in
+        any form form_template takes, or a list with one entry (None / False / a form) per sequence -- a bar such a sequence
+        opens itself replays the earlier bar its row names (ForcedDecoder.set_form; "copy": "rhythm" needs grammar=).
+        articulation: None / False, one
         articulation in any form articulation_template takes, or a list with one entry (None / False / an articulation) per
         sequence -- such a sequence DRAWS a duration only inside the window of its open bar's row, capped at the bar line
         (within_bar) and at the first step where its guide bans the pitch just drawn (hold_guide: guide= is required), and a
@@ -3386,7 +3703,7 @@ class BatchedGenerator:
                            logit_bias=logit_bias, shared=self.shared_prompt and max_prompt > 0, grammar=grammar,
                            harmony=self._one_harmony(harmony), class_sampling=class_sampling, note_order=note_order,
                            voices=voices, density=density, interval=interval, onsets=onsets, guide=guide,
-                           articulation=articulation)
+                           articulation=articulation, form=form)
         uniforms = None
         if bool((dec._sampling[0] != 0).any()) or dec.class_samples():
             srcs = self.uniform_sources or [np.random.RandomState(1000 + b).random_sample for b in range(B)]
@@ -3411,7 +3728,8 @@ class BatchedGenerator:
                         accept, top_p=1.0, slots: int = 64, seed: int = 0, max_attempts: Optional[int] = None,
                         return_logprobs: bool = False, prompt: Optional[Sequence[int]] = None, logit_bias=None,
                         share_prompt: bool = False, grammar=None, harmony=None, class_sampling=None, note_order=None,
-                        voices=None, density=None, interval=None, onsets=None, guide=None, articulation=None):
+                        voices=None, density=None, interval=None, onsets=None, guide=None, articulation=None,
+                        form=None):
         """Attempts of ONE request (the reference's `while idx != num_generate` loop, midi_inferrer.py:338-354, which tries
         one sequence after the other) decoded in up to `slots` parallel slots, CONTINUOUSLY: a slot whose sequence has
         ended is handed to `accept(sequence, report) -> bool` and re-armed with the next attempt while the other slots keep
@@ -3443,6 +3761,8 @@ class BatchedGenerator:
         (ForcedDecoder.set_guide; likewise).
         articulation: None / False or ONE articulation in any form articulation_template takes: one setting for every attempt
         of the request (ForcedDecoder.set_articulation; likewise; hold_guide needs guide=).
+        form: None / False or ONE form in any form form_template takes: one setting for every attempt of the request
+        (ForcedDecoder.set_form; a re-armed slot's replay state is reset with its record; "copy": "rhythm" needs grammar=).
         share_prompt (opt-in; also on with BatchedGenerator(shared_prompt=True) when a prompt is given): the K/V of the
         context and the prompt are computed and held once for all slots (ForcedDecoder(shared_prompt=True)); the attempts
         returned are the ones the unshared decoder defines, up to the summation order of the attention."""
@@ -3471,6 +3791,9 @@ class BatchedGenerator:
         if isinstance(articulation, list):
             raise CommuHipError(f"articulation: one setting for the request expected, got a list of {len(articulation)}")
         one_art = None if (articulation is None or articulation is False) else articulation_template(articulation)
+        if isinstance(form, list):
+            raise CommuHipError(f"form: one setting for the request expected, got a list of {len(form)}")
+        one_form = None if (form is None or form is False) else form_template(form)
         max_chords = len(input_data.chord_token_components["chord_token"])
         # each control's schedule, validated on its own (the three may have different lengths)
         n_of = lambda x: 1 if np.ndim(x) == 0 else len(x)
@@ -3485,7 +3808,8 @@ class BatchedGenerator:
                            per_slot=return_logprobs or varying, max_prompt=0 if prompt is None else len(prompt),
                            logit_bias=logit_bias, shared=share, grammar=grammar, harmony=harmony,
                            class_sampling=class_sampling, note_order=note_order, voices=voices, density=density,
-                           interval=interval, onsets=one_onsets, guide=one_guide, articulation=one_art)
+                           interval=interval, onsets=one_onsets, guide=one_guide, articulation=one_art,
+                           form=one_form)
         started = B
         sampled = bool((sched[0] != 0).any()) or dec.class_samples()          # (a greedy attempt reads no variate)
         uni = np.stack([self.attempt_uniforms(seed, a, dec.ld_u) for a in range(B)]) if sampled else None
@@ -3644,7 +3968,7 @@ class BatchedGenerator:
         harm_table = _harmony_request(self._one_harmony(harmony))
         cls_table = _class_request(class_sampling)
         # each request's controls, validated before anything is built
-        triples, biases, orders, voxes, dens, mels, onss, gdes, arts = [], [], [], [], [], [], [], [], []
+        triples, biases, orders, voxes, dens, mels, onss, gdes, arts, frms = [], [], [], [], [], [], [], [], [], []
         for i, r in enumerate(requests):
             t, k, p = sampling_rows(1, r.temperature, r.top_k, r.top_p)
             triples.append((t[0].item(), int(k[0]), p[0].item()))
@@ -3659,6 +3983,11 @@ class BatchedGenerator:
                 arts.append(None if (r.articulation is None or r.articulation is False)
                             else articulation_template(r.articulation))
                 _articulation_needs_guide(arts[-1:], gdes[-1:])
+                if isinstance(r.form, list):
+                    raise CommuHipError(f"form: one setting for the request expected, got a list of {len(r.form)}")
+                frms.append(None if (r.form is None or r.form is False) else form_template(r.form))
+                _form_needs_grammar(frms[-1:], [0] if ((gram_table is not None) if r.grammar is None else bool(r.grammar))
+                                    else [])
             except CommuHipError as e:
                 raise CommuHipError(f"request {i}: {e}") from None
         B = max(1, min(slots, sum(int(r.need) for r in requests)))
@@ -3702,6 +4031,12 @@ class BatchedGenerator:
                 dec._pack(r, tmpls, fresh=True)
         if any(b is not None for b in biases):
             dec._first_use(bias=True)
+        # (the form rule: the requests' forms go into its table before the pool is opened; a later pool without one switches
+        # every slot off, and a decoder that never had one allocates nothing)
+        dec.set_form(None)
+        if any(t is not None for t in frms):
+            dec._first_use_form()
+            dec._pack(FORM, frms, fresh=True)
         klen0_max = max([n_cond] + [p["klen0"] for p in replays if p is not None])
         dec.pool_open(n_cond, grid_rows=klen0_max)
         cls_samples = cls_table is not None and bool((np.nan_to_num(cls_table[..., 0], nan=0.0) != 0).any())
@@ -3724,7 +4059,8 @@ class BatchedGenerator:
                               harmony=(harm_table is not None) if r.harmony is None else bool(r.harmony),
                               note_order=orders[j.request], voices=voxes[j.request], class_table=cls_table,
                               primed=replays[j.request], density=dens[j.request], interval=mels[j.request],
-                              onsets=onss[j.request], guide=gdes[j.request], articulation=arts[j.request])
+                              onsets=onss[j.request], guide=gdes[j.request], articulation=arts[j.request],
+                              form=frms[j.request])
                 sampled = triples[j.request][0] != 0 or cls_samples          # (a greedy attempt reads no variate)
                 staged.append((j.slot, j.entry, self.attempt_uniforms(r.seed, j.attempt, dec.ld_u) if sampled else None))
                 if held[j.slot] is not None and held[j.slot] != j.request:

@@ -299,7 +299,7 @@ class InferenceTask:
     def execute(self, encoded_meta, max_rounds: Optional[int] = None, return_logprobs: bool = False,
                 prompt: Optional[List[int]] = None, logit_bias=None, grammar=None, harmony=None,
                 class_sampling=None, note_order=None, voices=None, density=None, interval=None,
-                onsets=None, guide=None, articulation=None):                                               # :338-354
+                onsets=None, guide=None, articulation=None, form=None):                                    # :338-354
         """return_logprobs (not in the reference): (sequences, their log-probability arrays -- ForcedDecoder.logprobs).
         prompt (not in the reference): token ids that follow the meta tokens; every attempt continues them (primed
         generation, BatchedGenerator.generate_stream) and every returned sequence starts with [0] + meta + prompt.
@@ -326,7 +326,10 @@ class InferenceTask:
         articulation (not in the reference): an articulation in any form generate.articulation_template takes -- a drawn
         duration lies in the window of its bar's row, capped at the bar line (within_bar) and where the guide bans the held
         pitch (hold_guide), a drawn velocity where the row has a bit; switches nothing else on
-        (ForcedDecoder.set_articulation)."""
+        (ForcedDecoder.set_articulation).
+        form (not in the reference): a form in any form generate.form_template takes -- a bar the loop opens itself replays
+        the earlier bar its row names, in full (optionally transposed) or its rhythm only; "copy": "rhythm" needs the
+        grammar (ForcedDecoder.set_form)."""
         from ..generate import BatchedGenerator
         data = self.input_data
         glen = self.inference_cfg.GENERATION.generation_length
@@ -367,6 +370,9 @@ class InferenceTask:
         # (likewise: generate.py --articulation, the JSON text of the articulation's full form)
         if articulation is None and getattr(self.inference_cfg.GENERATION, "articulation", None):
             articulation = json.loads(self.inference_cfg.GENERATION.articulation)
+        # (likewise: generate.py --form, the JSON text of the form's bars)
+        if form is None and getattr(self.inference_cfg.GENERATION, "form", None):
+            form = json.loads(self.inference_cfg.GENERATION.form)
         gen = BatchedGenerator(self.model, self.device, glen, mlen, sliding=sliding, kv_dtype=kv_dtype,
                                **({"shared_prompt": True} if share else {}))
 
@@ -395,14 +401,15 @@ class InferenceTask:
                                   **({} if interval is None else {"interval": interval}),
                                   **({} if onsets is None else {"onsets": onsets}),
                                   **({} if guide is None else {"guide": guide}),
-                                  **({} if articulation is None else {"articulation": articulation}))
+                                  **({} if articulation is None else {"articulation": articulation}),
+                                  **({} if form is None else {"form": form}))
         return (res[0], res[2]) if return_logprobs else res[0]
 
     def execute_pool(self, items, return_logprobs: bool = False, harmony=None):
         """generate.py --requests (not in the reference): MANY requests in one pool of decode slots
         (BatchedGenerator.generate_pool).  items: one dict per request -- encoded_meta, input_data (its num_generate,
         temperature, top_k, top_p), seed, max_rounds, logit_bias, prompt (token ids the request's sequences continue, None
-        or [] for none), onsets (the request's own onset template, None: the pool-wide one of --onsets, if any), guide (likewise: --guide), articulation (likewise: --articulation).  Every request is accepted by the two validators of
+        or [] for none), onsets (the request's own onset template, None: the pool-wide one of --onsets, if any), guide (likewise: --guide), articulation (likewise: --articulation), form (likewise: --form).  Every request is accepted by the two validators of
         execute() and bounded by max_rounds x num_generate attempts, as there; the pool-wide options (grammar, harmony,
         class_sampling, note_order, voices, density, interval, decode_slots, kv_cache, sliding_memory) come from the inference configuration
         as in execute().  Returns generate_pool's PoolResult list."""
@@ -423,6 +430,7 @@ class InferenceTask:
         onsets = json.loads(G.onsets) if getattr(G, "onsets", None) else None
         guide = json.loads(G.guide) if getattr(G, "guide", None) else None
         articulation = json.loads(G.articulation) if getattr(G, "articulation", None) else None
+        form = json.loads(G.form) if getattr(G, "form", None) else None
 
         def accept(seq, rep) -> bool:
             self.attempts += 1
@@ -444,6 +452,7 @@ class InferenceTask:
                                     prompt=None if not it.get("prompt") else list(it["prompt"]), density=density,
                                     interval=interval, onsets=onsets if it.get("onsets") is None else it["onsets"],
                                     guide=guide if it.get("guide") is None else it["guide"],
-                                    articulation=articulation if it.get("articulation") is None else it["articulation"]))
+                                    articulation=articulation if it.get("articulation") is None else it["articulation"],
+                                    form=form if it.get("form") is None else it["form"]))
         return gen.generate_pool(reqs, slots=int(getattr(G, "decode_slots", 64)), grammar=grammar, harmony=harmony,
                                  class_sampling=class_sampling, return_logprobs=return_logprobs)

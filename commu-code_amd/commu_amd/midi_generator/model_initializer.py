@@ -101,6 +101,9 @@ class ModelInitializeTask:
         # check_articulation)
         if getattr(self.model_args, "articulation_doc", None) is not None:
             cfg.GENERATION.articulation = str(self.model_args.articulation_doc)
+        # generate.py --form (not in the reference): the form as the JSON text of its bars (generate.py check_form)
+        if getattr(self.model_args, "form_doc", None) is not None:
+            cfg.GENERATION.form = str(self.model_args.form_doc)
         # generate.py --decode_slots (not in the reference): attempts decoded side by side (64 unless the key is set)
         if getattr(self.model_args, "decode_slots", None) not in (None, 64):
             cfg.GENERATION.decode_slots = int(self.model_args.decode_slots)

@@ -57,7 +57,7 @@ def generate_on_device(model_args, in_args, device_index, num_generate, uniform_
 
 def generate_requests_on_device(model_args, requests, device_index, training_cfg=None, logprobs=False, harmony=None):
     """generate.py --requests: checkpoint -> model on cuda:<device_index>, then every request (a dict of one request's
-    input arguments plus seed, max_rounds, its constraint row logit_bias, its prompt_tokens, its onsets template, its guide track and its articulation) through PreprocessTask and all of them in ONE
+    input arguments plus seed, max_rounds, its constraint row logit_bias, its prompt_tokens, its onsets template, its guide track, its articulation and its form) through PreprocessTask and all of them in ONE
     pool (InferenceTask.execute_pool).  Returns one dict per request in list order: encoded_meta, sequences, attempts
     (and logprobs as logprobs_to_lists gives them)."""
     import torch
@@ -72,12 +72,12 @@ def generate_requests_on_device(model_args, requests, device_index, training_cfg
     for r in requests:
         pre = PreprocessTask()
         args = {k: v for k, v in r.items() if k not in ("seed", "max_rounds", "logit_bias", "prompt_tokens", "onsets", "guide",
-                                                       "articulation")}
+                                                       "articulation", "form")}
         encoded_meta = pre.execute(args)
         items.append({"encoded_meta": encoded_meta, "input_data": pre.input_data, "seed": int(r.get("seed") or 0),
                       "max_rounds": r.get("max_rounds"), "logit_bias": r.get("logit_bias"),
                       "prompt": r.get("prompt_tokens"), "onsets": r.get("onsets"), "guide": r.get("guide"),
-                      "articulation": r.get("articulation")})
+                      "articulation": r.get("articulation"), "form": r.get("form")})
     task = InferenceTask(device)
     task(model=model, input_data=None, inference_cfg=init.inference_cfg)
     res = task.execute_pool(items, return_logprobs=logprobs, harmony=harmony)

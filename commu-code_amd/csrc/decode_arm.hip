@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "form.h"
 #include "commu_hip.h"
 
 namespace {
@@ -26,6 +27,8 @@ __device__ __forceinline__ void arm_fill(T* __restrict__ dst, T v, int n, ArmRan
     for (int i = r.first; i < n; i += r.stride) dst[i] = v;
 }
 
+// FORM: the launch that also arms the form rule (form.h); without it the kernel is the one it always was
+template <bool FORM>
 __global__ __launch_bounds__(64) void decode_arm_kernel(const commu_decode_arm_args a) {
     const int j = blockIdx.y;
     const int slot = a.jobs[2 * j], entry = a.jobs[2 * j + 1];
@@ -81,6 +84,17 @@ __global__ __launch_bounds__(64) void decode_arm_kernel(const commu_decode_arm_a
         if (a.guide_ctl != nullptr && a.e_guide != nullptr) a.guide_ctl[slot] = a.e_guide[entry];
         if (a.art_ctl != nullptr && a.e_art != nullptr) a.art_ctl[slot] = a.e_art[entry];
     }
+    // (FORM) the slot's form word, and its form state as a load leaves it: nothing replayed, the BARs of the entry's sequence
+    // head recorded (one wave)
+    if constexpr (FORM) {
+        if (lh == 0 && lane == 0) {
+            if (a.form_ctl != nullptr && a.e_form != nullptr) a.form_ctl[slot] = a.e_form[entry];
+            if (a.form_tok != nullptr) a.form_tok[slot] = -1;
+        }
+        if (a.form_state != nullptr && lh == 0 && lane < 64)
+            form_reset_row(a.form_state + s * FS_COUNT, a.e_seq + e * a.ld_head, min(max(a.e_state[e * a.nf], 0), a.ld_head),
+                           lane);
+    }
 }
 
 }  // namespace
@@ -108,7 +122,10 @@ extern "C" int commu_decode_arm(const commu_decode_arm_args* p, hipStream_t stre
             return -22;
     }
     if ((long long)p->L * p->H > 2147483647LL) return -22;
-    COMMU_LAUNCH(decode_arm_kernel, dim3(p->L * p->H, p->njobs), dim3(64), 0, stream, *p);
+    if (p->form_ctl != nullptr || p->form_state != nullptr)
+        COMMU_LAUNCH(decode_arm_kernel<true>, dim3(p->L * p->H, p->njobs), dim3(64), 0, stream, *p);
+    else
+        COMMU_LAUNCH(decode_arm_kernel<false>, dim3(p->L * p->H, p->njobs), dim3(64), 0, stream, *p);
     COMMU_LAUNCH_CHECK();
     return 0;
 }

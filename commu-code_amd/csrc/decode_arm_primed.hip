@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "form.h"
 #include "commu_hip.h"
 
 namespace {
@@ -63,6 +64,8 @@ __host__ __device__ __forceinline__ int arm_rows_cap(int img_rows, int Lmax, int
     return (grid_rows > 0 && grid_rows < r) ? grid_rows : r;
 }
 
+// FORM: the launch that also arms the form rule (form.h); without it the kernel is the one it always was
+template <bool FORM>
 __global__ __launch_bounds__(ARM_THREADS) void decode_arm_primed_kernel(const commu_decode_arm_primed_args a) {
     const int j = blockIdx.y;
     const int slot = a.jobs[2 * j], entry = a.jobs[2 * j + 1];
@@ -122,6 +125,17 @@ __global__ __launch_bounds__(ARM_THREADS) void decode_arm_primed_kernel(const co
         if (a.guide_ctl != nullptr && a.e_guide != nullptr) a.guide_ctl[slot] = a.e_guide[entry];
         if (a.art_ctl != nullptr && a.e_art != nullptr) a.art_ctl[slot] = a.e_art[entry];
     }
+    // (FORM) the slot's form word, and its form state as a load leaves it: nothing replayed, the BARs of the entry's sequence
+    // head recorded (one wave)
+    if constexpr (FORM) {
+        if (lh == 0 && tid == 0) {
+            if (a.form_ctl != nullptr && a.e_form != nullptr) a.form_ctl[slot] = a.e_form[entry];
+            if (a.form_tok != nullptr) a.form_tok[slot] = -1;
+        }
+        if (a.form_state != nullptr && lh == 0 && tid < 64)
+            form_reset_row(a.form_state + s * FS_COUNT, a.e_seq + e * a.ld_head, min(max(a.e_state[e * a.nf], 0), a.ld_head),
+                           tid);
+    }
 }
 
 }  // namespace
@@ -154,7 +168,10 @@ extern "C" int commu_decode_arm_primed(const commu_decode_arm_primed_args* p, hi
     if ((long long)p->L * p->H > 2147483647LL) return -22;
     const int chunks = (arm_rows_cap(p->img_rows, p->Lmax, p->grid_rows) + ARM_CHUNK - 1) / ARM_CHUNK;
     if (chunks > 65535) return -22;
-    COMMU_LAUNCH(decode_arm_primed_kernel, dim3(p->L * p->H, p->njobs, chunks), dim3(ARM_THREADS), 0, stream, *p);
+    if (p->form_ctl != nullptr || p->form_state != nullptr)
+        COMMU_LAUNCH(decode_arm_primed_kernel<true>, dim3(p->L * p->H, p->njobs, chunks), dim3(ARM_THREADS), 0, stream, *p);
+    else
+        COMMU_LAUNCH(decode_arm_primed_kernel<false>, dim3(p->L * p->H, p->njobs, chunks), dim3(ARM_THREADS), 0, stream, *p);
     COMMU_LAUNCH_CHECK();
     return 0;
 }

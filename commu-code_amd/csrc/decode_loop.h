@@ -2,6 +2,7 @@
 // stand-alone kernels (sample.hip, forcing.hip) and the fused sample -> post -> pre launch (forcing.hip).
 #pragma once
 #include "common.h"
+#include "form.h"
 
 namespace {
 
@@ -1057,16 +1058,125 @@ __device__ __forceinline__ void record_store(const int (&r)[F_COUNT], int* st, i
     for (int f = 0; f < F_COUNT; ++f) st[(size_t)b * F_COUNT + f] = r[f];
 }
 
+// FORM (Form: one int32 control per sequence, -1 off, else base + 4096 R with R in 1 .. 64 the form's bars and base in
+//   0 .. 4095, base + R <= rows; table uint32 [rows][4], 1 <= rows <= 4096; the slot's state row of FS_COUNT ints, form.h):
+//   a bar the loop opens may REPLAY an earlier bar of its own sequence.  Row base + i is bar i of the form, bars from R on
+//   (and from the 64th on) are free: the form is not cycled.  Word 0 is src | copy << 6 | (transpose + 64) << 8 with src in
+//   0 .. 63, copy 0 (all) or 1 (rhythm) and transpose in -48 .. 48; 0 is a free bar (a replay row's bits 8 .. 14 are never
+//   0).  Words 1 .. 3 are reserved, written 0 by the host and never read.  A row whose src is not below its own bar is
+//   treated as free, whatever the table holds; the row index is clamped to rows - 1.
+//   The rule lives in the forcing stage, not in the sampler: where `pre` would draw and the slot is inside a replay bar, the
+//   next token of the source bar's next complete note group (POSITION, VELOCITY, PITCH, DURATION) is handed to `post` through
+//   form_tok[b] as if it had been drawn -- draw[b] stays 0, so the sampling stage skips the slot, no variate is consumed and
+//   the logits are not divided -- and `post` runs every rule it has on it (a position past a pending chord forces the chord's
+//   position and the token is offered again, BAR with chords left inside the bar forces the next chord's position, BAR with
+//   none left forces EOS).  When the source bar has no group left the replay token is BAR.  In rhythm mode the PITCH is a
+//   normal draw under every constraint the slot has.  Chord tokens are never copied.
+//   THE SEARCH is the wave's work: lane l looks at seq[cursor + l + 64 c .. + 3] with clamped, unconditional loads, one
+//   ballot per chunk gives g, and chunk c is taken only while cursor + 64 c + 3 < end: the trip count is wave-uniform.  The
+//   token at g + k comes from the finding lane by v_readlane.  No LDS.  Lane 0 keeps the header in registers (FormRegs)
+//   through post and pre, as it keeps the record; bar_at is read and written in memory, by lane 0 only.
+//   NOT COVERED: replayed tokens are not checked against any constraint, as forced tokens are not; a replay bar cut by the
+//   iteration cap or ld_seq is not completed; bars past the 64th are free; a source note that the bar line cut does not
+//   appear (g + 3 < end).
+struct Form {
+    int ctl;                // the sequence's control as the caller loaded it
+    const unsigned* table;  // uint32 [rows][4]
+    int rows;               // 1 .. 4096 (the entry points refuse anything else)
+    int* state;             // the sequence's row of form_state
+    int* tok;               // form_tok + b: `pre` writes the replay token (-1: none) ...
+    int tokv;               // ... and `post` gets the value the caller loaded
+};
+struct FormRegs {
+    int active, cursor, end, k, row, g;
+};
+__device__ __forceinline__ void form_regs_load(FormRegs& f, const int* fs) {
+    f.active = fs[FS_ACTIVE]; f.cursor = fs[FS_CURSOR]; f.end = fs[FS_END]; f.k = fs[FS_K]; f.row = fs[FS_ROW]; f.g = fs[FS_G];
+}
+__device__ __forceinline__ void form_regs_store(const FormRegs& f, int* fs) {
+    fs[FS_ACTIVE] = f.active; fs[FS_CURSOR] = f.cursor; fs[FS_END] = f.end; fs[FS_K] = f.k; fs[FS_ROW] = f.row; fs[FS_G] = f.g;
+}
+// (lane 0) a BAR was appended at `index` as the (nb + 1)-th of the sequence: record it, and open bar nb under its row
+__device__ __forceinline__ void form_bar(const Form& fm, FormRegs& f, int nb, int index) {
+    if (nb >= 0 && nb < FORM_BARS) fm.state[FS_BAR_AT + nb] = index;
+    const int bars = min((fm.ctl >> 12) & 127, FORM_BARS);
+    const bool on = fm.ctl >= 0 && nb >= 0 && nb < bars;
+    const int r = min(max((fm.ctl & (FORM_ROWS_MAX - 1)) + (on ? nb : 0), 0), fm.rows - 1);
+    const unsigned w = fm.table[4 * (size_t)(on ? r : 0)];
+    const int src = (int)(w & 63u);
+    const bool rep = on && ((w >> 8) & 127u) != 0u && src < nb;
+    // (field by field, selects: an aggregate assignment behind the branch left two of the fields in scratch)
+    const int from = fm.state[FS_BAR_AT + (rep ? src : 0)], to = fm.state[FS_BAR_AT + (rep ? src + 1 : 0)];
+    f.active = rep ? 1 : 0;
+    f.cursor = rep ? from + 1 : 0;
+    f.end = rep ? (src + 1 == nb ? index : to) : 0;
+    f.k = 0;
+    f.row = rep ? (int)(w & 0x7fffu) : 0;
+    f.g = -1;
+}
+__device__ __forceinline__ bool form_is_group(int t0, int t1, int t2, int t3) {
+    return ((unsigned)(t0 - TOK_POS0) < (unsigned)POS_RES) & ((unsigned)(t1 - TOK_VEL_LO) <= (unsigned)(TOK_VEL_HI - TOK_VEL_LO)) &
+           ((unsigned)(t2 - TOK_PITCH_LO) <= (unsigned)(TOK_PITCH_HI - TOK_PITCH_LO)) &
+           ((unsigned)(t3 - TOK_DUR_LO) <= (unsigned)(TOK_DUR_HI - TOK_DUR_LO));
+}
+// (the wave) the smallest g >= cursor with g + 3 < end whose four tokens are a note group, -1: none; tk: seq[g + k].
+// cursor, end and k are wave-uniform.
+__device__ __forceinline__ int form_search(const int* __restrict__ sq, int ld_seq, int cursor, int end, int k, int lane, int& tk) {
+    int g = -1;
+    tk = -1;
+    cursor = max(cursor, 0);
+    end = min(end, ld_seq);
+#pragma unroll 1
+    for (int base = cursor; base + 3 < end; base += 64) {
+        const int i = base + lane;
+        const int t0 = sq[min(i, ld_seq - 1)], t1 = sq[min(i + 1, ld_seq - 1)], t2 = sq[min(i + 2, ld_seq - 1)],
+                  t3 = sq[min(i + 3, ld_seq - 1)];
+        const unsigned long long m = __ballot((i + 3 < end) & form_is_group(t0, t1, t2, t3));
+        if (m != 0ull) {
+            const int l = __builtin_ctzll(m);
+            g = base + l;
+            tk = __builtin_amdgcn_readlane(k == 0 ? t0 : (k == 1 ? t1 : (k == 2 ? t2 : t3)), l);
+            break;
+        }
+    }
+    return g;
+}
+// (lane 0) the replay token of a slot inside a replay bar, -1: a normal draw is made (rhythm mode at the pitch)
+__device__ __forceinline__ int form_token(const FormRegs& f, int g, int tk) {
+    if (g < 0) return TOK_BAR;
+    const bool rhythm = ((f.row >> 6) & 1) != 0;
+    if (f.k != 2) return tk;
+    if (rhythm) return -1;
+    const int s = ((f.row >> 8) & 127) - 64;
+    int m = tk - TOK_PITCH_LO + s;
+    while (m < 0) m += 12;
+    while (m > 127) m -= 12;
+    return m + TOK_PITCH_LO;
+}
+
+template <bool FORM = false>
 __device__ __forceinline__ void forcing_pre_body(int b, int lane, int (&s)[F_COUNT], int* seq, int ld_seq,
                                                  const int* __restrict__ chord_tok, const int* __restrict__ chord_pos,
                                                  int ld_chord, unsigned char* wrong, const float* __restrict__ utable,
                                                  int ld_u, int max_iters, long long* tok, unsigned char* active,
                                                  unsigned char* keep, unsigned char* draw, float* uni, int* trace,
-                                                 int ld_trace, float* seq_logp) {
+                                                 int ld_trace, float* seq_logp,
+                                                 Form fm = Form{-1, nullptr, 1, nullptr, nullptr, -1},
+                                                 FormRegs* fr = nullptr) {
     int* sq = seq + (size_t)b * ld_seq;
     int clear = 0;
+    int fg = -1, ftk = -1;        // (FORM) the source bar's next group and its token of the current phase
+    if constexpr (FORM) {
+        // the search runs ahead of the decision, for a slot inside a replay bar that has no token to feed: what it reads
+        // (cursor, end, k) changes in this stage only where nothing is drawn afterwards
+        const bool look = fr->active != 0 && s[F_FORCED] < 0 && !s[F_DONE];
+        if (__builtin_amdgcn_readfirstlane((int)look))
+            fg = form_search(sq, ld_seq, __builtin_amdgcn_readfirstlane(fr->cursor), __builtin_amdgcn_readfirstlane(fr->end),
+                             __builtin_amdgcn_readfirstlane(fr->k), lane, ftk);
+    }
     if (lane == 0) {
         int act = 0, kp = 0, dr = 0;
+        int ft = -1;              // (FORM) the replay token handed to post
         long long t = 0;
         const int len = s[F_LEN];
         const int last = sq[len - 1], prev = len >= 2 ? sq[len - 2] : -1;
@@ -1082,6 +1192,9 @@ __device__ __forceinline__ void forcing_pre_body(int b, int lane, int (&s)[F_COU
                     q[0] = q[1] = NAN;
                 }
                 s[F_LEN] = len + 1;
+                if constexpr (FORM) {
+                    if (f == TOK_BAR) form_bar(fm, *fr, s[F_NBAR], len);
+                }
                 if (f == TOK_BAR) s[F_NBAR] += 1;
                 t = f; act = 1; kp = 1;
             } else {
@@ -1109,6 +1222,16 @@ __device__ __forceinline__ void forcing_pre_body(int b, int lane, int (&s)[F_COU
                         s[F_CUR] = cur + 1;
                         clear = 1;
                         decided = true;
+                        if constexpr (FORM) {                           // the chord took the replayed position: the group starts over
+                            if (fr->active && fr->k == 1) fr->k = 0;
+                        }
+                    }
+                }
+                if constexpr (FORM) {
+                    if (!decided && fr->active) {
+                        fr->g = fg;
+                        ft = form_token(*fr, fg, ftk);
+                        decided = ft >= 0;                              // (no variate, draw[b] stays 0)
                     }
                 }
                 if (!decided) {
@@ -1131,6 +1254,7 @@ __device__ __forceinline__ void forcing_pre_body(int b, int lane, int (&s)[F_COU
         active[b] = (unsigned char)act;
         keep[b] = (unsigned char)kp;
         draw[b] = (unsigned char)dr;
+        if constexpr (FORM) *fm.tok = ft;
     }
     clear = __builtin_amdgcn_readfirstlane(clear);
     if (clear)
@@ -1145,11 +1269,14 @@ __device__ __forceinline__ void forcing_pre_body(int b, int lane, int (&s)[F_COU
 struct StepFlags {
     int draw, keep, klen;
 };
+template <bool FORM = false>
 __device__ __forceinline__ void forcing_post_body(int b, int lane, int (&s)[F_COUNT], int* seq, int ld_seq,
                                                   const int* __restrict__ chord_pos, int ld_chord, unsigned char* wrong,
                                                   const unsigned char* draw, const int* token, int* live, int* klen,
                                                   const unsigned char* keep, int lmax, int token_val, TokenLogp lp,
-                                                  const float* logp, float* seq_logp, const StepFlags* flags = nullptr) {
+                                                  const float* logp, float* seq_logp, const StepFlags* flags = nullptr,
+                                                  Form fm = Form{-1, nullptr, 1, nullptr, nullptr, -1},
+                                                  FormRegs* fr = nullptr) {
     int clear = 0;
     if (lane == 0) {
         // memory length of the step that just ran: it grows unless the step's memory is discarded (quirk Q3)
@@ -1160,8 +1287,11 @@ __device__ __forceinline__ void forcing_post_body(int b, int lane, int (&s)[F_CO
                 if (kl < lmax - 1) klen[b] = kl + 1;
             }
         }
-        if (flags != nullptr ? flags->draw : (int)draw[b]) {
-            const int t = token_val >= -1 ? token_val : token[b];
+        bool drew = flags != nullptr ? flags->draw : (int)draw[b];
+        if constexpr (FORM) drew = drew || fm.tokv >= 0;                 // (a replay token is treated exactly as a drawn one)
+        if (drew) {
+            int t = token_val >= -1 ? token_val : token[b];
+            if constexpr (FORM) t = fm.tokv >= 0 ? fm.tokv : t;
             const int cur = s[F_CUR];
             const bool remnant = cur < s[F_NCHORD];
             const int cp = remnant ? chord_pos[(size_t)b * ld_chord + cur] : -1;
@@ -1188,8 +1318,15 @@ __device__ __forceinline__ void forcing_post_body(int b, int lane, int (&s)[F_CO
                         if (token_val >= -1) { q[0] = lp.full; q[1] = lp.kept; }
                         else if (logp != nullptr) { q[0] = logp[2 * b]; q[1] = logp[2 * b + 1]; }
                         else q[0] = q[1] = NAN;
+                        if constexpr (FORM) {
+                            if (fm.tokv >= 0) q[0] = q[1] = NAN;          // (it was not drawn)
+                        }
                     }
                     s[F_LEN] = len + 1;
+                    if constexpr (FORM) {
+                        if (t == TOK_BAR) form_bar(fm, *fr, s[F_NBAR], len);
+                        else if (fr->active && ++fr->k == 4) { fr->cursor = fr->g + 4; fr->k = 0; }
+                    }
                 }
                 if (t == TOK_BAR) s[F_NBAR] += 1;
             }

@@ -42,6 +42,67 @@ __global__ __launch_bounds__(64) void forcing_post_kernel(int* st, int* seq, int
     if (threadIdx.x == 0) record_store(rec, st, blockIdx.x);
 }
 
+// The two stages with the form rule (decode_loop.h: Form): the header of the slot's form state travels through the stage in
+// lane 0's registers beside the record.
+__global__ __launch_bounds__(64) void forcing_pre_form_kernel(int* st, int* seq, int ld_seq, const int* __restrict__ chord_tok,
+                                                              const int* __restrict__ chord_pos, int ld_chord,
+                                                              unsigned char* wrong, const float* __restrict__ utable,
+                                                              int ld_u, int max_iters, long long* tok, unsigned char* active,
+                                                              unsigned char* keep, unsigned char* draw, float* uni,
+                                                              int* trace, int ld_trace, float* seq_logp, const int* form_ctl,
+                                                              const unsigned* form_table, int form_rows, int* form_state,
+                                                              int* form_tok) {
+    const int b = blockIdx.x;
+    int rec[F_COUNT] = {};
+    FormRegs fr{0, 0, 0, 0, 0, -1};
+    int* fs = form_state + (size_t)b * FS_COUNT;
+    if (threadIdx.x == 0) {
+        record_load(rec, st, b);
+        form_regs_load(fr, fs);
+    }
+    forcing_pre_body<true>(b, threadIdx.x, rec, seq, ld_seq, chord_tok, chord_pos, ld_chord, wrong, utable, ld_u, max_iters,
+                           tok, active, keep, draw, uni, trace, ld_trace, seq_logp,
+                           Form{form_ctl[b], form_table, form_rows, fs, form_tok + b, -1}, &fr);
+    if (threadIdx.x == 0) {
+        record_store(rec, st, b);
+        form_regs_store(fr, fs);
+    }
+}
+
+__global__ __launch_bounds__(64) void forcing_post_form_kernel(int* st, int* seq, int ld_seq, const int* __restrict__ chord_pos,
+                                                               int ld_chord, unsigned char* wrong, const unsigned char* draw,
+                                                               const int* token, int* live, int* klen,
+                                                               const unsigned char* keep, int lmax, const float* logp,
+                                                               float* seq_logp, const int* form_ctl,
+                                                               const unsigned* form_table, int form_rows, int* form_state,
+                                                               int* form_tok) {
+    const int b = blockIdx.x;
+    int rec[F_COUNT] = {};
+    FormRegs fr{0, 0, 0, 0, 0, -1};
+    int* fs = form_state + (size_t)b * FS_COUNT;
+    if (threadIdx.x == 0) {
+        record_load(rec, st, b);
+        form_regs_load(fr, fs);
+    }
+    forcing_post_body<true>(b, threadIdx.x, rec, seq, ld_seq, chord_pos, ld_chord, wrong, draw, token, live, klen, keep, lmax,
+                            -3, TokenLogp{NAN, NAN}, logp, seq_logp, nullptr,
+                            Form{form_ctl[b], form_table, form_rows, fs, form_tok + b, form_tok[b]}, &fr);
+    if (threadIdx.x == 0) {
+        record_store(rec, st, b);
+        form_regs_store(fr, fs);
+    }
+}
+
+// form_state and form_tok of the slots first .. first + n - 1 as a load leaves them (form.h: form_reset_row): the BARs of
+// seq[b][0 .. F_LEN) recorded, nothing replayed
+__global__ __launch_bounds__(64) void form_reset_kernel(int* form_state, int* form_tok, const int* __restrict__ st,
+                                                        const int* __restrict__ seq, int ld_seq, int first) {
+    const int b = first + blockIdx.x;
+    const int len = min(max(st[(size_t)b * F_COUNT + F_LEN], 0), ld_seq);
+    form_reset_row(form_state + (size_t)b * FS_COUNT, seq + (size_t)b * ld_seq, len, threadIdx.x);
+    if (threadIdx.x == 0) form_tok[b] = -1;
+}
+
 // One launch for the three per-sequence stages that follow the model step: sampling step -> book-keeping (post) -> the
 // decision of the NEXT iteration (pre).  A sequence's stages only exchange data of that sequence, and one wave runs
 // them in order; the workgroup barriers order the wave's own global stores and loads between stages.
@@ -125,8 +186,18 @@ struct LoopArgs<T_ART> : LoopArgs<T_GDE> {
     const unsigned* art_table;
     int art_rows;
 };
-template <bool BIAS, int TIER>
-__global__ __launch_bounds__(64) void sample_post_pre_kernel(LoopArgs<TIER> a) {
+// the form rule (decode_loop.h: Form) is a switch of its own beside the tier: the kernel with it takes the block of its tier
+// plus these five, the kernel without it the block it always took
+template <int TIER>
+struct LoopArgsForm : LoopArgs<TIER> {
+    const int* form_ctl;
+    const unsigned* form_table;
+    int form_rows;
+    int* form_state;
+    int* form_tok;
+};
+template <bool BIAS, int TIER, bool FORM = false>
+__global__ __launch_bounds__(64) void sample_post_pre_kernel(std::conditional_t<FORM, LoopArgsForm<TIER>, LoopArgs<TIER>> a) {
     const int b = blockIdx.x, lane = threadIdx.x;
     if (a.trace != nullptr && lane == 0) a.trace[b * 4 + 0] = wall_clock64();
     int rec[F_COUNT];                                  // the record travels through the three stages in lane 0's registers;
@@ -135,6 +206,15 @@ __global__ __launch_bounds__(64) void sample_post_pre_kernel(LoopArgs<TIER> a) {
     // what post reads of this iteration's decision, loaded here for the same reason (a null klen reads token[b] instead)
     const StepFlags flags{a.draw[b], a.keep[b], *(a.klen != nullptr ? a.klen + b : a.token + b)};
     TokenLogp lp{NAN, NAN};                            // like `drawn`, the pair reaches post in registers
+    // (FORM) the header of the slot's form state, the control word and the replay token of this iteration's decision,
+    // loaded with the record: every lane loads the same words
+    Form fm{-1, nullptr, 1, nullptr, nullptr, -1};
+    FormRegs fr{0, 0, 0, 0, 0, -1};
+    if constexpr (FORM) {
+        int* fs = a.form_state + (size_t)b * FS_COUNT;
+        form_regs_load(fr, fs);
+        fm = Form{a.form_ctl[b], a.form_table, a.form_rows, fs, a.form_tok + b, a.form_tok[b]};
+    }
     Grammar g{nullptr, 0, nullptr, 0, 0, 0};
     if constexpr (TIER >= T_GRAM) {
         // the slot's switch is loaded with the flags above (a null gram_on reads draw[b], which is then ignored).  The
@@ -175,13 +255,16 @@ __global__ __launch_bounds__(64) void sample_post_pre_kernel(LoopArgs<TIER> a) {
         os, gd, ar);
     __syncthreads();
     if (a.trace != nullptr && lane == 0) a.trace[b * 4 + 1] = wall_clock64();
-    forcing_post_body(b, lane, rec, a.seq, a.ld_seq, a.chord_pos, a.ld_chord, a.wrong, a.draw, a.token, nullptr, a.klen,
-                      a.keep, a.lmax, drawn >= -1 ? drawn : -3, lp, a.logp, a.seq_logp, &flags);
+    forcing_post_body<FORM>(b, lane, rec, a.seq, a.ld_seq, a.chord_pos, a.ld_chord, a.wrong, a.draw, a.token, nullptr, a.klen,
+                            a.keep, a.lmax, drawn >= -1 ? drawn : -3, lp, a.logp, a.seq_logp, &flags, fm, &fr);
     __syncthreads();
     if (a.trace != nullptr && lane == 0) a.trace[b * 4 + 2] = wall_clock64();
-    forcing_pre_body(b, lane, rec, a.seq, a.ld_seq, a.chord_tok, a.chord_pos, a.ld_chord, a.wrong, a.utable, a.ld_u,
-                     a.max_iters, a.tok, a.active, a.keep, a.draw, a.uni, a.step_trace, a.ld_trace, a.seq_logp);
+    forcing_pre_body<FORM>(b, lane, rec, a.seq, a.ld_seq, a.chord_tok, a.chord_pos, a.ld_chord, a.wrong, a.utable, a.ld_u,
+                           a.max_iters, a.tok, a.active, a.keep, a.draw, a.uni, a.step_trace, a.ld_trace, a.seq_logp, fm, &fr);
     if (lane == 0) record_store(rec, a.st, b);
+    if constexpr (FORM) {
+        if (lane == 0) form_regs_store(fr, fm.state);
+    }
     if (a.trace != nullptr && lane == 0) a.trace[b * 4 + 3] = wall_clock64();
 }
 
@@ -301,6 +384,54 @@ extern "C" int commu_forcing_post(int* state, int* seq, int ld_seq, const int* c
     return 0;
 }
 
+extern "C" int commu_form_state_ints(void) { return FS_COUNT; }
+
+static bool form_args_ok(const int* form_ctl, const unsigned* form_table, int form_rows, const int* form_state,
+                         const int* form_tok) {
+    return form_ctl != nullptr && form_table != nullptr && form_state != nullptr && form_tok != nullptr && form_rows >= 1 &&
+           form_rows <= FORM_ROWS_MAX;
+}
+
+extern "C" int commu_forcing_pre_form(int* state, int* seq, int ld_seq, const int* chord_tok, const int* chord_pos,
+                                      int ld_chord, unsigned char* wrong, const float* utable, int ld_u, int max_iters,
+                                      long long* tok, unsigned char* active, unsigned char* keep, unsigned char* draw,
+                                      float* uni, int* trace, int ld_trace, float* seq_logp, const int* form_ctl,
+                                      const unsigned* form_table, int form_rows, int* form_state, int* form_tok, int B,
+                                      hipStream_t stream) {
+    if (B <= 0) return 0;
+    if (ld_seq < 2 || ld_chord < 1 || ld_u < 1) return -22;
+    if (!form_args_ok(form_ctl, form_table, form_rows, form_state, form_tok)) return -22;
+    COMMU_LAUNCH(forcing_pre_form_kernel, dim3(B), dim3(64), 0, stream, state, seq, ld_seq, chord_tok, chord_pos, ld_chord,
+                 wrong, utable, ld_u, max_iters, tok, active, keep, draw, uni, trace, ld_trace, seq_logp, form_ctl, form_table,
+                 form_rows, form_state, form_tok);
+    COMMU_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int commu_forcing_post_form(int* state, int* seq, int ld_seq, const int* chord_pos, int ld_chord,
+                                       unsigned char* wrong, const unsigned char* draw, const int* token, int* live,
+                                       int* klen, const unsigned char* keep, int lmax, const float* logp, float* seq_logp,
+                                       const int* form_ctl, const unsigned* form_table, int form_rows, int* form_state,
+                                       int* form_tok, int B, hipStream_t stream) {
+    if (B <= 0) return 0;
+    if (ld_seq < 2 || ld_chord < 1) return -22;
+    if (!form_args_ok(form_ctl, form_table, form_rows, form_state, form_tok)) return -22;
+    COMMU_LAUNCH(forcing_post_form_kernel, dim3(B), dim3(64), 0, stream, state, seq, ld_seq, chord_pos, ld_chord, wrong,
+                 draw, token, live, klen, keep, lmax, logp, seq_logp, form_ctl, form_table, form_rows, form_state, form_tok);
+    COMMU_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int commu_form_reset(int* form_state, int* form_tok, const int* state, const int* seq, int ld_seq, int first,
+                                int n, hipStream_t stream) {
+    if (n <= 0) return 0;
+    if (form_state == nullptr || form_tok == nullptr || state == nullptr || seq == nullptr || ld_seq < 1 || first < 0)
+        return -22;
+    COMMU_LAUNCH(form_reset_kernel, dim3(n), dim3(64), 0, stream, form_state, form_tok, state, seq, ld_seq, first);
+    COMMU_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int commu_forcing_replay(int* state, int* seq, int ld_seq, const int* prompt, int ld_prompt,
                                     const int* prompt_len, const int* chord_tok, const int* chord_pos, int ld_chord,
                                     unsigned char* wrong, const float* utable, int ld_u, long long* tok,
@@ -349,7 +480,10 @@ extern "C" int commu_decode_sample_post_pre(const commu_decode_loop_args* p, hip
         ((p->top_k_rows == nullptr && (p->top_k < 1 || p->top_k > V)) || (p->top_p_rows == nullptr && !(p->top_p > 0.f))))
         return -22;
     if (!check_constraints(*p, V)) return -22;
-    LoopArgs<T_ART> a;
+    // (the form rule: every one of its arrays or none)
+    if (p->form_ctl != nullptr && !form_args_ok(p->form_ctl, p->form_table, p->form_rows, p->form_state, p->form_tok))
+        return -22;
+    LoopArgsForm<T_ART> a;
     static_cast<LoopArgs<T_NONE>&>(a) = LoopArgs<T_NONE>{
         p->logits, p->ld, V, p->wrong, p->temperature, p->top_k, p->top_p,
         SamplingRows{p->temperature_rows, p->top_k_rows, p->top_p_rows}, p->token, p->probs_out, p->ldp, p->logp, p->seq_logp,
@@ -365,6 +499,8 @@ extern "C" int commu_decode_sample_post_pre(const commu_decode_loop_args* p, hip
     a.onset_ctl = p->onset_ctl; a.onset_table = p->onset_table; a.onset_rows = p->onset_rows;
     a.guide_ctl = p->guide_ctl; a.guide_table = p->guide_table; a.guide_rows = p->guide_rows;
     a.art_ctl = p->art_ctl; a.art_table = p->art_table; a.art_rows = p->art_rows;
+    a.form_ctl = p->form_ctl; a.form_table = p->form_table; a.form_rows = p->form_rows;
+    a.form_state = p->form_state; a.form_tok = p->form_tok;
     const dim3 grid(p->B), block(64);
     // one kernel per tier, each with the argument block of its own tier (by value), so that a launch below a tier is the one
     // it always was: no added load, no added register, no added argument.  Below the harmony tier a bias is optional and
@@ -372,6 +508,20 @@ extern "C" int commu_decode_sample_post_pre(const commu_decode_loop_args* p, hip
     with_tier(tier_of(*p), [&](auto t) {
         constexpr int T = decltype(t)::value;
         const auto& at = static_cast<const LoopArgs<T>&>(a);      // (each kernel gets the block of its own tier)
+        if (p->form_ctl != nullptr) {                             // (the form kernels: that block and the form's five)
+            LoopArgsForm<T> af;
+            static_cast<LoopArgs<T>&>(af) = at;
+            af.form_ctl = a.form_ctl; af.form_table = a.form_table; af.form_rows = a.form_rows;
+            af.form_state = a.form_state; af.form_tok = a.form_tok;
+            if constexpr (T < T_HARM) {
+                if (p->bias == nullptr) {
+                    COMMU_LAUNCH((sample_post_pre_kernel<false, T, true>), grid, block, 0, stream, af);
+                    return;
+                }
+            }
+            COMMU_LAUNCH((sample_post_pre_kernel<true, T, true>), grid, block, 0, stream, af);
+            return;
+        }
         if constexpr (T < T_HARM) {
             if (p->bias == nullptr) {
                 COMMU_LAUNCH((sample_post_pre_kernel<false, T>), grid, block, 0, stream, at);

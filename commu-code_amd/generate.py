@@ -190,6 +190,25 @@ def parse_args():
                                        '{"bars": [{"duration": [lo, hi], "velocity": [lo, hi]} | null, ...], "within_bar": '
                                        'bool, "hold_guide": bool} or one bar\'s keys at top level.  Not covered: forced '
                                        'tokens, notes inside --prompt_tokens')
+    # not in the reference (whose bars are unrelated draws): --form SPEC -- a bar of the sequence REPLAYS an earlier bar of the
+    # same sequence.  SPEC is a letter string such as AABA (the first bar with a letter is free, later ones replay it in
+    # full), JSON text {"bars": [null | j | {"of": j, "copy": "all" | "rhythm", "transpose": s}, ...]} (bar i is free or
+    # replays bar j < i: every token of its notes, transposed by s semitones in -48 .. 48 and folded into the MIDI range, or
+    # its rhythm only -- positions, velocities and durations, the pitches drawn under every constraint in force), or a file
+    # holding either.  At most 64 bars, not cycled: bars past the form's end are free; bar 0 is always free.  The replayed
+    # tokens go through the chord / bar rules like drawn ones, so the bar gets the chords of its own place in the
+    # progression; they consume no random number and carry no log-probability.  "copy": "rhythm" needs --grammar.  The bars
+    # of --prompt_tokens are valid sources; the bar a prompt leaves open is free.  It runs under --parity as well (the
+    # parity mode decodes through the same loop).  NOT covered: replayed tokens are not checked against any constraint, as
+    # forced tokens are not (a strict --harmony under another chord is the user's business: "copy": "rhythm" is the answer);
+    # a replay bar cut by --generation_length is not completed; bars past the 64th are free; a note of the source bar that
+    # the bar line cut does not appear; chord tokens are never copied.  With --requests it holds for every request that
+    # does not carry a "form" of its own.
+    model_arg_parser.add_argument("--form", default=None, metavar="SPEC",
+                                  help='a bar replays an earlier bar of its own sequence: letters (AABA), JSON text or file, '
+                                       '{"bars": [null | j | {"of": j, "copy": "all" | "rhythm", "transpose": s}, ...]}.  '
+                                       'Not covered: constraints on replayed tokens, bars past the 64th, a bar cut by '
+                                       '--generation_length')
     # not in the reference (which decodes one sequence at a time): how many attempts are decoded side by side.  1 .. 256;
     # up to 256 slots run the fused layer-tail launches ("Supported shapes").  The sequences returned do
     # not depend on it.  (checked by check_decode_slots: the range is named in its message)
@@ -334,7 +353,8 @@ REQUEST_KEYS = REQUEST_META_KEYS + ("num_generate", "top_k", "temperature", "top
 # and onsets, its own onset template (--onsets' forms, as JSON values)
 # and guide, its own guide track (--guide's forms, as JSON values)
 # and articulation, its own articulation (--articulation's forms, as JSON values)
-REQUEST_OPTIONAL_KEYS = ("prompt_tokens", "onsets", "guide", "articulation")
+# and form, its own form (--form's forms, as JSON values)
+REQUEST_OPTIONAL_KEYS = ("prompt_tokens", "onsets", "guide", "articulation", "form")
 # (single-request input arguments that --requests replaces, with the value the parser gives them when they are not named)
 SINGLE_REQUEST_ARGS = {**{k: None for k in REQUEST_META_KEYS}, "genre": "cinematic", "rhythm": "standard",
                        "num_generate": None, "top_k": 32, "temperature": 0.95, "top_p": 1.0, "max_rounds": None,
@@ -406,6 +426,11 @@ def check_requests(model_args, input_args):
                 r = {**r, "articulation": articulation_doc(r["articulation"], "articulation")}
             except ValueError as e:
                 raise ValueError(f"--requests: {path}: request {i}: {e}") from None
+        if r.get("form") is not None:
+            try:
+                r = {**r, "form": form_doc(r["form"], "form", bool(getattr(model_args, "grammar", False)))}
+            except ValueError as e:
+                raise ValueError(f"--requests: {path}: request {i}: {e}") from None
         out.append({**SINGLE_REQUEST_ARGS, "seed": 0, **r})
     # (hold_guide reads the request's guide: its own, or the pool-wide one of --guide)
     pool_art = check_articulation(model_args, needs_guide=False)
@@ -416,6 +441,42 @@ def check_requests(model_args, input_args):
             raise ValueError(f"--requests: {path}: request {i}: articulation: hold_guide without a guide (neither the "
                              "request's own \"guide\" nor --guide)")
     return out
+
+
+def form_doc(doc, what="--form", grammar=True):
+    """A form given as a letter string or a JSON value, validated and returned written out: {"bars": [null | {"of": j,
+    "copy": "all" | "rhythm", "transpose": s}, ...]}.  Host code only, ValueError that says what is wrong -- a rhythm bar
+    without --grammar among it."""
+    from commu_amd.generate import CommuHipError, form_is_rhythm, form_row_fields, form_template
+    try:
+        rows = form_template(doc)
+    except CommuHipError as e:
+        raise ValueError(f"{what}: {str(e).removeprefix('form: ')}") from None
+    if form_is_rhythm(rows) and not grammar:
+        raise ValueError(f'{what}: "copy": "rhythm" without --grammar: the pitches of such a bar are drawn, and only the '
+                         "grammar makes that draw a pitch")
+    bars = []
+    for w in rows[:, 0].tolist():
+        f = form_row_fields(w)
+        bars.append(None if f is None else {"of": f[0], "copy": f[1], "transpose": f[2]})
+    if all(b is None or (b["copy"] == "all" and b["transpose"] == 0) for b in bars):
+        bars = [None if b is None else b["of"] for b in bars]
+    return {"bars": bars}
+
+
+def check_form(model_args):
+    """--form as the JSON text of the form written out (None without the flag): the value is a letter string, the JSON
+    document itself or the path of a file that holds either.  Host code only, run before a model is loaded; ValueError that
+    says what is wrong.  Written back to model_args.form_doc, which travels to the replicas (ModelInitializeTask puts it into
+    the inference configuration).  It switches nothing else on."""
+    setting = getattr(model_args, "form", None)
+    model_args.form_doc = None
+    if setting is None:
+        return None
+    if not isinstance(setting, str):
+        raise ValueError(f"--form: letters, JSON text or a readable file expected, got {setting!r}")
+    model_args.form_doc = json.dumps(form_doc(setting, "--form", bool(getattr(model_args, "grammar", False))))
+    return model_args.form_doc
 
 
 def articulation_doc(doc, what="--articulation"):
@@ -736,6 +797,7 @@ def main(model_args, input_args, training_cfg=None, device_indices=None):
     check_onsets(model_args)                            # (likewise)
     check_guide(model_args, input_args)                 # (likewise)
     check_articulation(model_args, needs_guide=requests is None)      # (likewise)
+    check_form(model_args)                              # (likewise)
     check_note_order(model_args)                        # (likewise)
     in_args = dict(vars(input_args))
     in_args.pop("requests", None)

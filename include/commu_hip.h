@@ -853,6 +853,53 @@ int commu_forcing_pre(int* state, int* seq, int ld_seq, const int* chord_tok, co
 int commu_forcing_post(int* state, int* seq, int ld_seq, const int* chord_pos, int ld_chord, unsigned char* wrong,
                        const unsigned char* draw, const int* token, int* live, int* klen, const unsigned char* keep,
                        int lmax, const float* logp, float* seq_logp, int B, hipStream_t stream);
+/* ---- FORM templates: a bar the loop opens may replay an earlier bar of its own sequence (csrc/decode_loop.h: Form).
+ *   form_ctl: int32 [B], one control word per sequence: -1 off, else base + 4096 R with R in 1 .. 64 the form's bars and
+ *     base in 0 .. 4095, base + R <= form_rows.  form_table: uint32 [form_rows][4], 1 <= form_rows <= 4096; row base + i is
+ *     bar i of the form (bars from R on, and from the 64th on, are free: a form is not cycled).  Word 0 is
+ *     src | copy << 6 | (transpose + 64) << 8 with src in 0 .. 63 the bar replayed (src < i, else the row is free), copy 0
+ *     (all four tokens of a note) or 1 (rhythm: the pitch is drawn), transpose in -48 .. 48 semitones (0 with rhythm); the
+ *     word 0 is a free bar.  Words 1 .. 3 are reserved, written 0 and never read.
+ *   form_state: int32 [B][commu_form_state_ints()]: active, cursor, end, k (the phase 0 .. 3 inside the current note group),
+ *     the open bar's row word, g (the group the last search found, -1: none), two reserved ints, then bar_at[0 .. 63], the
+ *     index in seq of the (i+1)-th BAR token (context and prompt included).  commu_form_reset writes the state a load leaves;
+ *     the arm launches write it for the slots they arm.
+ *   form_tok: int32 [B]: the replay token commu_forcing_pre_form decided on (-1: none), read by commu_forcing_post_form.
+ * THE RULE, on a note group = four consecutive tokens POSITION (432 .. 559), VELOCITY (131 .. 194), PITCH (3 .. 130),
+ * DURATION (304 .. 431), with bar i the stretch bar_at[i] < index < bar_at[i + 1]:
+ *   a BAR is appended (forced in pre or drawn in post): bar_at takes its index while fewer than 64 are recorded; the new
+ *     open bar i = F_NBAR - 1 with a replay row of src j gets active = 1, cursor = bar_at[j] + 1, end = bar_at[j + 1], k = 0,
+ *     any other bar active = 0;
+ *   pre reaches its "draw" decision with active set: g is the smallest index >= cursor with g + 3 < end whose four tokens
+ *     are a note group (none: the replay token is BAR); in rhythm mode at k = 2 a normal draw is made; otherwise the replay
+ *     token is seq[g + k], at k = 2 transposed (the MIDI pitch folded by 12 into 0 .. 127).  A replay token consumes no
+ *     variate (F_NDRAW does not move) and leaves draw[b] = 0, so the sampling stage skips the slot and its logits are not
+ *     divided; the model step runs as for a draw;
+ *   post with form_tok[b] >= 0 treats it exactly as a drawn token (every branch applies); appended and not BAR: k += 1, and
+ *     at k = 4 cursor = g + 4, k = 0; not appended: nothing moves and it is offered again; its log-probability pair is NaN;
+ *   pre forces a chord while k = 1 (the replayed position was the pending chord's): k = 0, the group starts over;
+ *   a pitch drawn in rhythm mode goes through post as any draw; appended: k += 1.
+ * Not covered: replayed tokens are not checked against any constraint (forced tokens are not either); a replay bar cut by
+ * max_iters or ld_seq is not completed; bars past the 64th are free; a source note the bar line cut does not appear; chord
+ * tokens are never copied.
+ * commu_forcing_pre_form / commu_forcing_post_form: commu_forcing_pre / commu_forcing_post (same leading arguments, same
+ * refusals) with the rule; -22 for a null form_ctl, form_table, form_state or form_tok and for form_rows outside 1 .. 4096.
+ * In commu_decode_loop_args a null form_ctl launches the kernels that never heard of the rule; a form_ctl without table,
+ * state or form_tok, or with form_rows outside 1 .. 4096, is refused with -22. */
+int commu_form_state_ints(void);
+int commu_forcing_pre_form(int* state, int* seq, int ld_seq, const int* chord_tok, const int* chord_pos, int ld_chord,
+                           unsigned char* wrong, const float* utable, int ld_u, int max_iters, long long* tok,
+                           unsigned char* active, unsigned char* keep, unsigned char* draw, float* uni, int* trace,
+                           int ld_trace, float* seq_logp, const int* form_ctl, const unsigned* form_table, int form_rows,
+                           int* form_state, int* form_tok, int B, hipStream_t stream);
+int commu_forcing_post_form(int* state, int* seq, int ld_seq, const int* chord_pos, int ld_chord, unsigned char* wrong,
+                            const unsigned char* draw, const int* token, int* live, int* klen, const unsigned char* keep,
+                            int lmax, const float* logp, float* seq_logp, const int* form_ctl, const unsigned* form_table,
+                            int form_rows, int* form_state, int* form_tok, int B, hipStream_t stream);
+/* form_state[b] and form_tok[b] of the slots first .. first + n - 1 as a load leaves them: nothing replayed, form_tok -1,
+ * bar_at over seq[b][0 .. state[b][0]) (the record's length word, clamped to ld_seq).  One wave per slot. */
+int commu_form_reset(int* form_state, int* form_tok, const int* state, const int* seq, int ld_seq, int first, int n,
+                     hipStream_t stream);
 /* diagnostics: following commu_decode_sample_post_pre launches write 100 MHz timestamps buf[sequence][4] = kernel start,
  * after the sampling step, after post, after pre (device memory; null: off) */
 int commu_decode_loop_trace(unsigned long long* buf);
@@ -922,6 +969,12 @@ typedef struct commu_decode_loop_args {
     const float* harm;
     const unsigned char* harm_on;
     int ld_bias, ld_gram, ld_harm;
+    /* form templates (below: FORM; likewise ahead of art_ctl) */
+    const int* form_ctl;
+    const unsigned* form_table;
+    int form_rows;
+    int* form_state;
+    int* form_tok;
     /* articulation (commu_sample_args.art_ctl / art_table / art_rows; likewise ahead of guide_ctl) */
     const int* art_ctl;
     const unsigned* art_table;
@@ -995,6 +1048,9 @@ int commu_decode_prefill_scatter(const void* qkv, int ld_qkv, int T, int B, void
  *   order_ctl / voice_ctl / density_ctl / interval_ctl / onset_ctl [slot] = e_order / e_voice / e_density / e_interval /
  *   e_onset [entry] (the onset table is the pool's own: no table bytes move per arm);  guide_ctl[slot] = e_guide[entry]
  *   (likewise: the guide table is the pool's own);  art_ctl[slot] = e_art[entry] (likewise);
+ *   form_ctl[slot] = e_form[entry] (likewise), and where form_state and form_tok are given the slot's form state as
+ *   commu_form_reset leaves it, over the entry's sequence head (bar_at of e_seq[entry][0 .. e_state[entry][0]), so a
+ *   prompt's bars are valid sources) and form_tok[slot] = -1;
  *   cls_ctl[slot][0 .. 32) = e_cls[entry] (int32).
  * tok / active / keep / draw are NOT written: an armed slot sits out the iteration whose decision was taken from its
  * finished record and starts with the next one.  Two jobs of one launch must name different slots (the caller's duty).
@@ -1067,6 +1123,12 @@ typedef struct commu_decode_arm_args {
     const int* e_voice;
     int* cls_ctl;
     const int* e_cls;
+    /* form templates: the slots' control words and their store twin, the state rows and the replay tokens
+     * (at the struct's end: every other field keeps its place) */
+    int* form_ctl;
+    const int* e_form;
+    int* form_state;
+    int* form_tok;
 } commu_decode_arm_args;
 int commu_decode_arm_args_bytes(void);
 int commu_decode_arm(const commu_decode_arm_args* a, hipStream_t stream);
@@ -1162,6 +1224,12 @@ typedef struct commu_decode_arm_primed_args {
     const int* e_voice;
     int* cls_ctl;
     const int* e_cls;
+    /* form templates: the slots' control words and their store twin, the state rows and the replay tokens
+     * (at the struct's end: every other field keeps its place) */
+    int* form_ctl;
+    const int* e_form;
+    int* form_state;
+    int* form_tok;
 } commu_decode_arm_primed_args;
 int commu_decode_arm_primed_args_bytes(void);
 int commu_decode_arm_primed_chunk_rows(void);
