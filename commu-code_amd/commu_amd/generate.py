@@ -470,6 +470,25 @@ def _class_request(cs):
     return class_sampling_table(cs)
 
 
+def _words_per_slot(name: str, word, x, B: int):
+    """What the word normalisers share: x as the int32 words of B slots -- one value for all of them or one per slot, each
+    through word(value, where), the rule's own check."""
+    B = int(B)
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    if x is None or np.ndim(x) == 0:
+        if isinstance(x, np.ndarray):
+            x = x.item()
+        return np.full(B, word(x, ""), dtype=np.int32)
+    x = list(x)
+    if len(x) != B:
+        raise CommuHipError(f"{name}: {B} values expected (one per sequence), got {len(x)}")
+    if any(np.ndim(v) != 0 for v in x):
+        raise CommuHipError(f"{name}: one value per sequence expected, got shape {np.shape(x)}")
+    return np.array([word(v.item() if isinstance(v, np.generic) and not isinstance(v, np.bool_) else v, f"[{b}]")
+                     for b, v in enumerate(x)], dtype=np.int32)
+
+
 # ---- note order: one int32 control word per slot (commu_sample_args.order_ctl).  A slot that is on cannot draw a position
 # token before the position it is at, a pitch its current position already holds, or -- with a cap n -- the position itself
 # once it holds n notes.  The state is read off the slot's seq when the sampling stage runs; nothing else is kept.
@@ -481,8 +500,6 @@ def note_order_ctl(x, B: int):
     """A request's note_order= as the int32 control words of B slots: None / False (off, -1), True (on, 0), an integer
     n in 1 .. 128 (on, at most n notes per position; 0 and -1 as the words themselves), or one such value per slot.
     Pure host code; raises CommuHipError on anything else, with the numbers."""
-    B = int(B)
-
     def word(v, where):
         if v is None or v is False or (isinstance(v, np.bool_) and not v):
             return NOTE_ORDER_OFF
@@ -494,19 +511,7 @@ def note_order_ctl(x, B: int):
             raise CommuHipError(f"note_order{where}: None / False (off), True (on) or an integer in [1, {NOTE_ORDER_MAX}] "
                                 f"(notes per position; -1 = off, 0 = no cap) expected, got {v!r}")
         return int(v)
-    if isinstance(x, torch.Tensor):
-        x = x.detach().cpu().numpy()
-    if x is None or np.ndim(x) == 0:
-        if isinstance(x, np.ndarray):
-            x = x.item()
-        return np.full(B, word(x, ""), dtype=np.int32)
-    x = list(x)
-    if len(x) != B:
-        raise CommuHipError(f"note_order: {B} values expected (one per sequence), got {len(x)}")
-    if any(np.ndim(v) != 0 for v in x):
-        raise CommuHipError(f"note_order: one value per sequence expected, got shape {np.shape(x)}")
-    return np.array([word(v.item() if isinstance(v, np.generic) and not isinstance(v, np.bool_) else v, f"[{b}]")
-                     for b, v in enumerate(x)], dtype=np.int32)
+    return _words_per_slot("note_order", word, x, B)
 
 
 # ---- voice cap: one int32 control word per slot (commu_sample_args.voice_ctl).  A slot that is on cannot draw a position at
@@ -528,8 +533,6 @@ def voices_ctl(x, B: int):
     in 0 .. 128 (at most N notes sound at once; 0: no cap) and r in {0, 1} (1: a sounding pitch is not struck again) --
     voices_word(N, r) -- or one such value per slot.  Pure host code; raises CommuHipError on anything else, with the
     numbers."""
-    B = int(B)
-
     def word(v, where):
         if v is None or v is False or (isinstance(v, np.bool_) and not v):
             return VOICES_OFF
@@ -541,19 +544,7 @@ def voices_ctl(x, B: int):
                                 f"[0, {VOICES_MAX}] (notes sounding at once; 0 = no cap) and r in {{0, 1}} (1 = no "
                                 f"re-striking; -1 = off) expected, got {v!r}")
         return int(v)
-    if isinstance(x, torch.Tensor):
-        x = x.detach().cpu().numpy()
-    if x is None or np.ndim(x) == 0:
-        if isinstance(x, np.ndarray):
-            x = x.item()
-        return np.full(B, word(x, ""), dtype=np.int32)
-    x = list(x)
-    if len(x) != B:
-        raise CommuHipError(f"voices: {B} values expected (one per sequence), got {len(x)}")
-    if any(np.ndim(v) != 0 for v in x):
-        raise CommuHipError(f"voices: one value per sequence expected, got shape {np.shape(x)}")
-    return np.array([word(v.item() if isinstance(v, np.generic) and not isinstance(v, np.bool_) else v, f"[{b}]")
-                     for b, v in enumerate(x)], dtype=np.int32)
+    return _words_per_slot("voices", word, x, B)
 
 
 # ---- note density: one int32 control word per slot (commu_sample_args.density_ctl).  A slot that is on cannot draw Bar or
@@ -575,8 +566,6 @@ def density_ctl(x, B: int):
     with lo, hi in 0 .. 255 (a bar the slot DRAWS holds at least lo and at most hi notes; 0: that bound is not set; with
     hi >= 1, hi >= max(lo, 1)) -- density_word(lo, hi) -- or one such value per slot.  Pure host code; raises CommuHipError
     on anything else, with the numbers."""
-    B = int(B)
-
     def word(v, where):
         if v is None or v is False or (isinstance(v, np.bool_) and not v):
             return DENSITY_OFF
@@ -590,19 +579,7 @@ def density_ctl(x, B: int):
                                 f"[0, {DENSITY_MAX}] (notes per bar at least / at most; 0 = that bound is not set; hi >= lo "
                                 f"where both are set; -1 = off) expected, got {v!r}")
         return int(v)
-    if isinstance(x, torch.Tensor):
-        x = x.detach().cpu().numpy()
-    if x is None or np.ndim(x) == 0:
-        if isinstance(x, np.ndarray):
-            x = x.item()
-        return np.full(B, word(x, ""), dtype=np.int32)
-    x = list(x)
-    if len(x) != B:
-        raise CommuHipError(f"density: {B} values expected (one per sequence), got {len(x)}")
-    if any(np.ndim(v) != 0 for v in x):
-        raise CommuHipError(f"density: one value per sequence expected, got shape {np.shape(x)}")
-    return np.array([word(v.item() if isinstance(v, np.generic) and not isinstance(v, np.bool_) else v, f"[{b}]")
-                     for b, v in enumerate(x)], dtype=np.int32)
+    return _words_per_slot("density", word, x, B)
 
 
 # ---- melodic interval: one int32 control word per slot (commu_sample_args.interval_ctl).  A slot that is on cannot draw a
@@ -627,8 +604,6 @@ def interval_ctl(x, B: int):
     the pitch of its last note; 0: that bound is not set) and u in {0, 1} (1: it is not that pitch) -- interval_word(up,
     down, no_repeat) -- or one such value per slot.  Pure host code; raises CommuHipError on anything else, with the
     numbers."""
-    B = int(B)
-
     def word(v, where):
         if v is None or v is False or (isinstance(v, np.bool_) and not v):
             return INTERVAL_OFF
@@ -643,19 +618,7 @@ def interval_ctl(x, B: int):
                                 f"note; 0 = that bound is not set), u in [0, 1] (1 = no repeated pitch) and no higher bit "
                                 f"(-1 = off) expected, got {v!r}")
         return int(v)
-    if isinstance(x, torch.Tensor):
-        x = x.detach().cpu().numpy()
-    if x is None or np.ndim(x) == 0:
-        if isinstance(x, np.ndarray):
-            x = x.item()
-        return np.full(B, word(x, ""), dtype=np.int32)
-    x = list(x)
-    if len(x) != B:
-        raise CommuHipError(f"interval: {B} values expected (one per sequence), got {len(x)}")
-    if any(np.ndim(v) != 0 for v in x):
-        raise CommuHipError(f"interval: one value per sequence expected, got shape {np.shape(x)}")
-    return np.array([word(v.item() if isinstance(v, np.generic) and not isinstance(v, np.bool_) else v, f"[{b}]")
-                     for b, v in enumerate(x)], dtype=np.int32)
+    return _words_per_slot("interval", word, x, B)
 
 
 # ---- onset templates: one int32 control word per slot (commu_sample_args.onset_ctl) and one device table of 128-bit rows
@@ -747,6 +710,19 @@ def _onsets_per_slot(x, B: int):
         return [None if (v is None or v is False) else onset_rows(v) for v in x]
     t = onset_rows(x)
     return [t] * B
+
+
+def _templates_per_slot(name: str, template, x, B: int):
+    """What the guide's, the articulation's and the form's normalisers share: None / False (all off), one value in any form
+    `template` takes (all slots), or a list of B entries each None / False or such a value."""
+    B = int(B)
+    if x is None or x is False:
+        return [None] * B
+    if isinstance(x, list):
+        if len(x) != B:
+            raise CommuHipError(f"{name}: {B} entries expected (one per sequence), got {len(x)}")
+        return [None if (v is None or v is False) else template(v) for v in x]
+    return [template(x)] * B
 
 
 # ---- guide track: one int32 control word per slot (commu_sample_args.guide_ctl) and one device table of 128-bit rows
@@ -947,14 +923,7 @@ def guide_rows(x, pitch_range=None) -> np.ndarray:
 def _guide_per_slot(x, B: int):
     """A request's guide= as B entries, each None (off) or a template (rows, cells): None / False (all off), one guide in
     any form guide_template takes (all slots), or a list of B entries each None / False or a guide."""
-    B = int(B)
-    if x is None or x is False:
-        return [None] * B
-    if isinstance(x, list):
-        if len(x) != B:
-            raise CommuHipError(f"guide: {B} entries expected (one per sequence), got {len(x)}")
-        return [None if (v is None or v is False) else guide_template(v) for v in x]
-    return [guide_template(x)] * B
+    return _templates_per_slot("guide", guide_template, x, B)
 
 
 # ---- articulation: one int32 control word per slot (commu_sample_args.art_ctl) and one device table of 128-bit rows
@@ -1067,14 +1036,7 @@ def _articulation_per_slot(x, B: int):
     """A request's articulation= as B entries, each None (off) or a template (rows, within_bar, hold_guide): None / False
     (all off), one articulation in any form articulation_template takes (all slots), or a list of B entries each None /
     False or an articulation."""
-    B = int(B)
-    if x is None or x is False:
-        return [None] * B
-    if isinstance(x, list):
-        if len(x) != B:
-            raise CommuHipError(f"articulation: {B} entries expected (one per sequence), got {len(x)}")
-        return [None if (v is None or v is False) else articulation_template(v) for v in x]
-    return [articulation_template(x)] * B
+    return _templates_per_slot("articulation", articulation_template, x, B)
 
 
 # ---- form templates: one int32 control word per slot (commu_decode_loop_args.form_ctl) and one device table of 128-bit rows
@@ -1204,14 +1166,7 @@ def _form_needs_grammar(forms, gram_on):
 def _form_per_slot(x, B: int):
     """A request's form= as B entries, each None (off) or a form's uint32 rows: None / False (all off), one form in any form
     form_template takes (all slots), or a list of B entries each None / False or a form."""
-    B = int(B)
-    if x is None or x is False:
-        return [None] * B
-    if isinstance(x, list):
-        if len(x) != B:
-            raise CommuHipError(f"form: {B} entries expected (one per sequence), got {len(x)}")
-        return [None if (v is None or v is False) else form_template(v) for v in x]
-    return [form_template(x)] * B
+    return _templates_per_slot("form", form_template, x, B)
 
 
 def _form_fold(pitch_token: int, s: int) -> int:
@@ -1733,14 +1688,20 @@ T_NONE, T_GRAM, T_HARM, T_CLS, T_ORD, T_VOX, T_DEN, T_MEL, T_ONS, T_GDE, T_ART =
 
 class SlotRule(NamedTuple):
     """One per-slot constraint of ForcedDecoder: control words int32 [B] on the device with a host mirror, and for the
-    rules that own a template table the table's shape and how a template becomes rows and a word.  The decoder's attributes
-    are named after `stem`: <stem>_ctl and _<stem>_host, <stem>_table, _<stem>_table_host, _<stem>_used and _<stem>_index;
-    the fields of the argument structs are <stem>_ctl, <stem>_table and <stem>_rows."""
-    tier: int
+    rules that own a template table the table's shape and how a template becomes rows and a word.  Every name follows from
+    `stem` and `kw`: the decoder's attributes are <stem>_ctl and _<stem>_host, <stem>_table, _<stem>_table_host,
+    _<stem>_used and _<stem>_index (class-level None / 0: a decoder that never enables the rule has none of them); the
+    fields of the argument structs are <stem>_ctl, <stem>_table and <stem>_rows; the request store's words are e_<stem>;
+    the keyword of every entry point and of ops.sample_topk is `kw`, the setter that holds the contract set_<kw>."""
+    tier: int                        # the sampling tier whose launch reads the words; -1: none (the form: forcing stage)
     stem: str
-    kw: str                          # the keyword of ops.sample_topk
+    kw: str
     off: int                         # the word of a slot that is off
-    label: str = ""                  # (table) what refusals call it
+    normalize: Callable              # (value, n) -> the words (no table) or templates (None: off) of n slots
+    asks: str                        # admit's refusal: what the request asks for that the decoder has no words of
+    implies: str = ""                # the kw of the rule a slot that is on needs on too: where that is off it gets word 0
+    template: Callable = None        # (table) value -> template
+    lists: bool = False              # (table) a Python list is one value per slot, never one template
     rows_max: int = 0                # (table) rows of the device table, allocated once; 0: the rule has no table
     cycle_max: int = 0               # (table) bars of one template
     fill: tuple = ()                 # (table) a row that constrains nothing
@@ -1755,33 +1716,93 @@ class SlotRule(NamedTuple):
     table_host = property(lambda r: "_" + r.stem + "_table_host")
     used = property(lambda r: "_" + r.stem + "_used")
     index = property(lambda r: "_" + r.stem + "_index")
+    entry = property(lambda r: "e_" + r.stem)
+    setter = property(lambda r: "set_" + r.kw)
+
+    def one(r, value):
+        """A request's single setting, validated: the value itself (no table) or its template, None where it is off.
+        Refuses one value per slot."""
+        if not r.rows_max:
+            if value is not None and np.ndim(value) != 0:
+                raise CommuHipError(f"{r.kw}: one setting for the request expected, got shape {np.shape(value)}")
+            return value
+        if r.lists and isinstance(value, list):
+            raise CommuHipError(f"{r.kw}: one setting for the request expected, got a list of {len(value)}")
+        return None if (value is None or value is False) else r.template(value)
+
+    def is_on(r, v) -> bool:
+        """Is a normalised value (a word, or a template / None) a slot that is on?"""
+        return v is not None if r.rows_max else v != r.off
 
 
 _ONES = (0xFFFFFFFF,) * 4
-ORDER = SlotRule(T_ORD, "order", "note_order", NOTE_ORDER_OFF)
-VOICES = SlotRule(T_VOX, "voice", "voices", VOICES_OFF)
-DENSITY = SlotRule(T_DEN, "density", "density", DENSITY_OFF)
-INTERVAL = SlotRule(T_MEL, "interval", "interval", INTERVAL_OFF)
-# (a template is the uint32 rows)
-ONSETS = SlotRule(T_ONS, "onset", "onsets", ONSETS_OFF, "onsets", ONSET_ROWS_MAX, ONSET_CYCLE_MAX, _ONES,
+ORDER = SlotRule(T_ORD, "order", "note_order", NOTE_ORDER_OFF, note_order_ctl,
+                 "note order switched on, but the decoder has no note-order words")
+VOICES = SlotRule(T_VOX, "voice", "voices", VOICES_OFF, voices_ctl, "a voice cap, but the decoder has no voice words",
+                  implies="note_order")
+DENSITY = SlotRule(T_DEN, "density", "density", DENSITY_OFF, density_ctl,
+                   "a note density, but the decoder has no density words", implies="voices")
+INTERVAL = SlotRule(T_MEL, "interval", "interval", INTERVAL_OFF, interval_ctl,
+                    "a melodic interval, but the decoder has no interval words")
+# (a template is the uint32 rows; a list is a template's bars)
+ONSETS = SlotRule(T_ONS, "onset", "onsets", ONSETS_OFF, _onsets_per_slot,
+                  "an onset template, but the decoder has no onset words", "", onset_rows, False,
+                  ONSET_ROWS_MAX, ONSET_CYCLE_MAX, _ONES,
                   rows_of=lambda t: t, key=lambda t: t.tobytes(), bars=lambda t: t.shape[0],
                   word=lambda base, bars, t: onset_word(base, bars))
 # (a template is (rows, cells): a bar is a block of 1 + cells rows, and the same bytes under other cells are another guide)
-GUIDE = SlotRule(T_GDE, "guide", "guide", GUIDE_OFF, "guide", GUIDE_ROWS_MAX, GUIDE_CYCLE_MAX, _ONES,
+GUIDE = SlotRule(T_GDE, "guide", "guide", GUIDE_OFF, _guide_per_slot,
+                 "a guide track, but the decoder has no guide words", "", guide_template, True,
+                 GUIDE_ROWS_MAX, GUIDE_CYCLE_MAX, _ONES,
                  rows_of=lambda t: t[0], key=lambda t: (t[1], t[0].tobytes()), bars=lambda t: t[0].shape[0] // (1 + t[1]),
                  word=lambda base, bars, t: guide_word(base, bars, t[1]))
 # (a template is (rows, within_bar, hold_guide): the switches live in the word, so two settings over the same rows share
 # them; a free row: no bounds, every velocity bin, the reserved word 0)
-ARTICULATION = SlotRule(T_ART, "art", "articulation", ARTICULATION_OFF, "articulation", ARTICULATION_ROWS_MAX,
-                        ARTICULATION_CYCLE_MAX, (0, 0xFFFFFFFF, 0xFFFFFFFF, 0),
+ARTICULATION = SlotRule(T_ART, "art", "articulation", ARTICULATION_OFF, _articulation_per_slot,
+                        "an articulation, but the decoder has no articulation words", "", articulation_template, True,
+                        ARTICULATION_ROWS_MAX, ARTICULATION_CYCLE_MAX, (0, 0xFFFFFFFF, 0xFFFFFFFF, 0),
                         rows_of=lambda t: t[0], key=lambda t: t[0].tobytes(), bars=lambda t: t[0].shape[0],
                         word=lambda base, bars, t: articulation_word(base, bars, t[1], t[2]))
-SLOT_RULES = (ORDER, VOICES, DENSITY, INTERVAL, ONSETS, GUIDE, ARTICULATION)
-# (the form rule is no tier of the sampling step: it lives in the forcing stage and its switch is its own, so it is not in
-# SLOT_RULES; the one template packer serves it.  A template is the uint32 rows; a free row is all zeros.)
-FORM = SlotRule(-1, "form", "form", FORM_OFF, "form", FORM_ROWS_MAX, FORM_BARS_MAX, (0, 0, 0, 0),
+# (the form rule is no tier of the sampling step: it lives in the forcing stage, its switch is its own and its first use
+# allocates nothing of the tiers -- the last of the table, tier -1.  A template is the uint32 rows; a free row is all zeros.)
+FORM = SlotRule(-1, "form", "form", FORM_OFF, _form_per_slot, "a form, but the decoder has no form words", "",
+                form_template, True, FORM_ROWS_MAX, FORM_BARS_MAX, (0, 0, 0, 0),
                 rows_of=lambda t: t, key=lambda t: t.tobytes(), bars=lambda t: t.shape[0],
                 word=lambda base, bars, t: form_word(base, bars))
+SLOT_RULES = (ORDER, VOICES, DENSITY, INTERVAL, ONSETS, GUIDE, ARTICULATION, FORM)          # (in tier order, the form last)
+SAMPLING_RULES = SLOT_RULES[:-1]                                                            # (the tiers of the sampling step)
+RULE_OF = {r.kw: r for r in SLOT_RULES}
+
+
+def rule_closure(kws):
+    """The rules that are on once the rules named kws are: themselves and, transitively, what they imply."""
+    out = set()
+    for kw in kws:
+        while kw and kw not in out:
+            out.add(kw)
+            kw = RULE_OF[kw].implies
+    return out
+
+
+def pool_tier(kws, class_table: bool = False) -> int:
+    """The tier a pool's one first use asks for: the highest any rule its requests switch on needs (a launch of a tier
+    reads every word below it, so the implied rules -- all of a lower tier -- come with it), else the class tier where
+    the pool has a class table, else none."""
+    return max([RULE_OF[kw].tier for kw in rule_closure(kws)] + [T_CLS if class_table else T_NONE])
+
+
+def _rule_values(rules: dict, default=None) -> dict:
+    """The keyword arguments **rules of an entry point that takes one value per rule of SLOT_RULES, checked against the
+    table and completed with the default, in the table's order."""
+    extra = sorted(set(rules) - set(RULE_OF))
+    if extra:
+        raise TypeError(f"got an unexpected keyword argument {extra[0]!r}")
+    return {r.kw: rules.get(r.kw, default) for r in SLOT_RULES}
+
+
+def _rules_of(scope: dict) -> dict:
+    """The rule keywords of an entry point that spells them out, picked from its locals()."""
+    return {r.kw: scope[r.kw] for r in SLOT_RULES}
 
 
 class ForcedDecoder:
@@ -1792,42 +1813,14 @@ class ForcedDecoder:
 
     POLL = 16          # iterations between two looks at the `done` flags (one D2H of B ints)
 
-    # onset templates (set_onsets): the slots' control words int32 [B] with their host mirror, the device table of
-    # ONSET_ROWS_MAX rows (allocated once, so that its pointer stays fixed under graph capture) with its host mirror, the
-    # rows in use and the base row of every template packed so far, by its bytes.  Class-level: a decoder that never
-    # enables the rule has none of them.
-    onset_ctl = None
-    _onset_host = None
-    onset_table = None
-    _onset_table_host = None
-    _onset_used = 0
-    _onset_index = None
-
-    # guide track (set_guide): the same six for the guide's control words and its table of GUIDE_ROWS_MAX rows (1 MB)
-    guide_ctl = None
-    _guide_host = None
-    guide_table = None
-    _guide_table_host = None
-    _guide_used = 0
-    _guide_index = None
-
-    # articulation (set_articulation): the same six for the articulation's control words and its table of
-    # ARTICULATION_ROWS_MAX rows (64 KB)
-    art_ctl = None
-    _art_host = None
-    art_table = None
-    _art_table_host = None
-    _art_used = 0
-    _art_index = None
-
-    # form templates (set_form): the same six for the form's control words and its table of FORM_ROWS_MAX rows (64 KB), and
-    # the two arrays the rule keeps per slot: the replay state int32 [B][commu_form_state_ints()] and the replay token [B]
-    form_ctl = None
-    _form_host = None
-    form_table = None
-    _form_table_host = None
-    _form_used = 0
-    _form_index = None
+    # every rule of SLOT_RULES: the slots' control words int32 [B] with their host mirror and, where the rule owns one, the
+    # device table of rows_max rows (allocated once, so that its pointer stays fixed under graph capture) with its host
+    # mirror, the rows in use and the base row of every template packed so far, by its key.  Class-level: a decoder that
+    # never enables a rule has none of them.
+    for _r in SLOT_RULES:
+        locals().update({_r.ctl: None, _r.host: None, _r.table: None, _r.table_host: None, _r.used: 0, _r.index: None})
+    del _r
+    # the form keeps two arrays more per slot: the replay state int32 [B][commu_form_state_ints()] and the replay token [B]
     form_state = None
     form_tok = None
 
@@ -1937,19 +1930,7 @@ class ForcedDecoder:
         # from; None: the launches a decoder without class controls always made
         self.cls_ctl = None
         self._cls_host = None
-        # note order (set_note_order): the slots' control words int32 [B], allocated by the first call that switches a
-        # slot on, and their host mirror; None: the launches a decoder without the feature always made
-        self.order_ctl = None
-        self._order_host = None
-        # voice cap (set_voices): likewise the slots' voice words int32 [B] and their host mirror
-        self.voice_ctl = None
-        self._voice_host = None
-        # note density (set_density): likewise the slots' density words int32 [B] and their host mirror
-        self.density_ctl = None
-        self._density_host = None
-        # melodic interval (set_interval): likewise the slots' interval words int32 [B] and their host mirror
-        self.interval_ctl = None
-        self._interval_host = None
+        # (the words and tables of SLOT_RULES: class-level None until the first call that switches a slot on)
         # (the replay of a prompt token takes at most two iterations: the decision to force it, then its append)
         self.ld_trace = 2 * (self.generation_length + 2 + 2 * self.max_prompt) if record_trace else 0
         self.trace = torch.zeros(B, self.ld_trace, dtype=i32, device=dev) if record_trace else None
@@ -1984,7 +1965,7 @@ class ForcedDecoder:
         the array launches; below T_HARM the three are independent of each other and asked for by name.  rows uploads the
         host mirror of the sampling controls (scalar mode kept the mirror only); bias / gram / harmony allocate their
         zeroed device buffers (gram and harmony: the table and the [B] switches); the class tier allocates the slots'
-        class-control records (set_class_sampling fills them); every rule of SLOT_RULES its words, all off, and -- where it
+        class-control records (set_class_sampling fills them); every rule of SAMPLING_RULES its words, all off, and -- where it
         owns one -- its table of rows that constrain nothing.  When anything was missing the captured graphs are dropped,
         once: they hold the launches without it."""
         new = False
@@ -2008,25 +1989,33 @@ class ForcedDecoder:
             new = True
             self.cls_ctl = torch.zeros(self.B, N_CLASSES + 1, 4, dtype=torch.int32, device=self.dev)
             self._cls_host = np.full((self.B, N_CLASSES + 1, 3), np.nan)
-        for r in SLOT_RULES:
-            if tier < r.tier or getattr(self, r.ctl) is not None:
-                continue
-            new = True
-            setattr(self, r.ctl, torch.full((self.B,), r.off, dtype=torch.int32, device=self.dev))
-            setattr(self, r.host, np.full(self.B, r.off, dtype=np.int32))
-            if r.rows_max:
-                host = np.tile(np.array(r.fill, dtype=np.uint32), (r.rows_max, 1))
-                setattr(self, r.table_host, host)
-                # (int32 on the device: the bit patterns of the uint32 rows)
-                setattr(self, r.table, torch.from_numpy(host.view(np.int32).copy()).to(self.dev))
-                setattr(self, r.used, 0)
-                setattr(self, r.index, {})
+        for r in SAMPLING_RULES:
+            if tier >= r.tier:
+                new = self._alloc_rule(r) or new
         if new:
             self.graph = self.graph_long = None
 
+    def _alloc_rule(self, r) -> bool:
+        """Rule r's words, all off, with their mirror and -- where it owns one -- its table of rows that constrain nothing,
+        unless the decoder has them; returns whether it had not."""
+        if getattr(self, r.ctl) is not None:
+            return False
+        setattr(self, r.ctl, torch.full((self.B,), r.off, dtype=torch.int32, device=self.dev))
+        setattr(self, r.host, np.full(self.B, r.off, dtype=np.int32))
+        if r.rows_max:
+            host = np.tile(np.array(r.fill, dtype=np.uint32), (r.rows_max, 1))
+            setattr(self, r.table_host, host)
+            # (int32 on the device: the bit patterns of the uint32 rows)
+            setattr(self, r.table, torch.from_numpy(host.view(np.int32).copy()).to(self.dev))
+            setattr(self, r.used, 0)
+            setattr(self, r.index, {})
+        return True
+
     def _first_use_words(self, r):
         """_first_use of a word setter: what rule r's kernel reads; class records that no table ever filled hold every
-        slot's base triple in every record."""
+        slot's base triple in every record.  The form has a first use of its own."""
+        if r is FORM:
+            return self._first_use_form()
         fresh_cls = self.cls_ctl is None
         self._first_use(r.tier)
         if fresh_cls:
@@ -2059,11 +2048,11 @@ class ForcedDecoder:
                 continue
             rows, bars = r.rows_of(t), r.bars(t)
             if bars > r.cycle_max:
-                raise CommuHipError(f"{r.label}: a template holds at most {r.cycle_max} bars, got {bars}")
+                raise CommuHipError(f"{r.kw}: a template holds at most {r.cycle_max} bars, got {bars}")
             key = r.key(t)
             if key not in index:
                 if used + rows.shape[0] > r.rows_max:
-                    raise CommuHipError(f"{r.label}: the distinct templates need more than the table's {r.rows_max} rows "
+                    raise CommuHipError(f"{r.kw}: the distinct templates need more than the table's {r.rows_max} rows "
                                         f"({used} in use, {rows.shape[0]} more asked for)")
                 index[key] = used
                 todo.append((used, rows))
@@ -2077,15 +2066,34 @@ class ForcedDecoder:
         setattr(self, r.used, used)
         return np.array(words, dtype=np.int32)
 
-    def _set_templates(self, r, tmpl, idx, rows):
-        """The body of a template setter, after its values were validated: nothing for a decoder without the rule that
-        is given no template; the capacity check of _pack before anything is allocated; first use; pack; words."""
+    def _set_words(self, r, value, rows):
+        """The body of a word setter: the values validated before anything changes; nothing for a decoder without the
+        rule that switches no slot on; the rule r implies switched on (word 0) where a slot that is switched on has it off
+        -- through its setter, which allocates what its kernel reads --; first use; words."""
+        idx = self._slots(rows)
+        new = r.normalize(value, len(idx))
+        if getattr(self, r.ctl) is None and not bool((new != r.off).any()):
+            return
+        if r.implies:
+            dep = RULE_OF[r.implies]
+            host = getattr(self, dep.host)
+            need = [int(j) for j, w in zip(idx, new) if w != r.off and (host is None or host[j] == dep.off)]
+            if need:
+                getattr(self, dep.setter)(0, rows=need)
+        self._first_use_words(r)
+        self._write_words(r, idx, new, rows)
+
+    def _set_templates(self, r, value, rows):
+        """The body of a template setter: the values validated before anything changes; nothing for a decoder without the
+        rule that is given no template; the capacity check of _pack before anything is allocated; first use; pack; words."""
+        idx = self._slots(rows)
+        tmpl = r.normalize(value, len(idx))
         if getattr(self, r.ctl) is None:
             if all(t is None for t in tmpl):
                 return
             need = sum(r.rows_of(t).shape[0] for t in {r.key(t): t for t in tmpl if t is not None}.values())
             if need > r.rows_max:
-                raise CommuHipError(f"{r.label}: the distinct templates need more than the table's {r.rows_max} rows "
+                raise CommuHipError(f"{r.kw}: the distinct templates need more than the table's {r.rows_max} rows "
                                     f"(0 in use, {need} asked for)")
         self._first_use_words(r)
         self._write_words(r, idx, self._pack(r, tmpl, fresh=rows is None), rows)
@@ -2266,8 +2274,8 @@ class ForcedDecoder:
         return None if self.cls_ctl is None else (self.cls_ctl, self.fsm, self.seq)
 
     def _slot_words(self):
-        """(rule, control words) for every rule of SLOT_RULES the decoder has words for."""
-        return [(r, getattr(self, r.ctl)) for r in SLOT_RULES if getattr(self, r.ctl) is not None]
+        """(rule, control words) for every rule of SAMPLING_RULES the decoder has words for."""
+        return [(r, getattr(self, r.ctl)) for r in SAMPLING_RULES if getattr(self, r.ctl) is not None]
 
     def set_note_order(self, value=True, rows: Optional[Sequence[int]] = None):
         """The note-order constraint for all slots (rows=None) or the listed ones: True (on), an integer n in 1 .. 128 (on,
@@ -2284,12 +2292,7 @@ class ForcedDecoder:
         A decoder that never switched a slot on allocates nothing.  Overlapping durations are not this rule's (a cap of 1 is
         one note per onset, not strict monophony): set_voices bans them.  A bias, pitch range or strict harmony that
         leaves fewer pitches than notes asked for at one position ends the slot by Q12."""
-        idx = self._slots(rows)
-        new = note_order_ctl(value, len(idx))                  # (validated before anything changes)
-        if self.order_ctl is None and not bool((new != NOTE_ORDER_OFF).any()):
-            return
-        self._first_use_words(ORDER)
-        self._write_words(ORDER, idx, new, rows)
+        self._set_words(ORDER, value, rows)
 
     def set_voices(self, value, rows: Optional[Sequence[int]] = None):
         """The voice cap for all slots (rows=None) or the listed ones: a word voices_word(N, r) -- at most N of the slot's
@@ -2306,16 +2309,7 @@ class ForcedDecoder:
         and a captured graph follows them.  A slot that is off bans nothing.  A decoder that never switched a slot on
         allocates nothing.  When a whole bar's rest is banned only Bar and EOS remain of the boundary family; a pitch range,
         bias or strict harmony that leaves no pitch free ends the slot by Q12."""
-        idx = self._slots(rows)
-        new = voices_ctl(value, len(idx))                      # (validated before anything changes)
-        if self.voice_ctl is None and not bool((new != VOICES_OFF).any()):
-            return
-        need = [int(j) for j, w in zip(idx, new)
-                if w != VOICES_OFF and (self._order_host is None or self._order_host[j] == NOTE_ORDER_OFF)]
-        if need:
-            self.set_note_order(True, rows=need)               # (allocates what the note-order kernel reads)
-        self._first_use_words(VOICES)
-        self._write_words(VOICES, idx, new, rows)
+        self._set_words(VOICES, value, rows)
 
     def set_density(self, value, rows: Optional[Sequence[int]] = None):
         """The note density for all slots (rows=None) or the listed ones: a word density_word(lo, hi) -- a bar the slot
@@ -2332,16 +2326,7 @@ class ForcedDecoder:
         generation length cuts stays as it is.  The first call that switches a slot on allocates the [B] words and drops
         the captured graphs once; later calls rewrite the words IN PLACE, ordered on the current stream, and a captured
         graph follows them.  A slot that is off bans nothing.  A decoder that never switched a slot on allocates nothing."""
-        idx = self._slots(rows)
-        new = density_ctl(value, len(idx))                     # (validated before anything changes)
-        if self.density_ctl is None and not bool((new != DENSITY_OFF).any()):
-            return
-        need = [int(j) for j, w in zip(idx, new)
-                if w != DENSITY_OFF and (self._voice_host is None or self._voice_host[j] == VOICES_OFF)]
-        if need:
-            self.set_voices(0, rows=need)                      # (allocates what the voices kernel reads; the note order too)
-        self._first_use_words(DENSITY)
-        self._write_words(DENSITY, idx, new, rows)
+        self._set_words(DENSITY, value, rows)
 
     def set_interval(self, value, rows: Optional[Sequence[int]] = None):
         """The melodic interval for all slots (rows=None) or the listed ones: a word interval_word(up, down, no_repeat) --
@@ -2360,12 +2345,7 @@ class ForcedDecoder:
         notes at one position are compared in token order (the rule is meant for set_voices lines of one voice); a pitch
         range, bias, strict harmony, note-order or re-strike ban that leaves no pitch inside the window ends the slot by
         Q12."""
-        idx = self._slots(rows)
-        new = interval_ctl(value, len(idx))                    # (validated before anything changes)
-        if self.interval_ctl is None and not bool((new != INTERVAL_OFF).any()):
-            return
-        self._first_use_words(INTERVAL)
-        self._write_words(INTERVAL, idx, new, rows)
+        self._set_words(INTERVAL, value, rows)
 
     def set_onsets(self, value, rows: Optional[Sequence[int]] = None):
         """The onset template for all slots (rows=None) or the listed ones: a template in any form onset_rows takes -- a list
@@ -2384,9 +2364,7 @@ class ForcedDecoder:
         stream, and a captured graph follows them.  A call for all slots packs the table anew.  Refused with the numbers:
         a template of more than 64 bars, distinct templates of more than 4096 rows together.  A slot that is off decodes
         bit for bit what it decoded without the feature; a decoder that never switched a slot on allocates nothing."""
-        idx = self._slots(rows)
-        tmpl = _onsets_per_slot(value, len(idx))               # (validated before anything changes)
-        self._set_templates(ONSETS, tmpl, idx, rows)
+        self._set_templates(ONSETS, value, rows)
 
     def set_guide(self, value, rows: Optional[Sequence[int]] = None):
         """The guide track for all slots (rows=None) or the listed ones: a guide in any form guide_template takes -- the raw
@@ -2404,9 +2382,7 @@ class ForcedDecoder:
         PLACE, ordered on the current stream.  A call for all slots packs the table anew.  Refused with the numbers: a
         template of more than 64 bars, distinct templates of more than 65536 rows together.  A slot that is off decodes
         bit for bit what it decoded without the feature; a decoder that never switched a slot on allocates nothing."""
-        idx = self._slots(rows)
-        tmpl = _guide_per_slot(value, len(idx))                # (validated before anything changes)
-        self._set_templates(GUIDE, tmpl, idx, rows)
+        self._set_templates(GUIDE, value, rows)
 
     def set_articulation(self, value, rows: Optional[Sequence[int]] = None):
         """The articulation for all slots (rows=None) or the listed ones: an articulation in any form articulation_template
@@ -2426,9 +2402,7 @@ class ForcedDecoder:
         PLACE, ordered on the current stream.  A call for all slots packs the table anew.  Refused with the numbers: a
         template of more than 64 bars, distinct templates of more than 4096 rows together.  A slot that is off decodes
         bit for bit what it decoded without the feature; a decoder that never switched a slot on allocates nothing."""
-        idx = self._slots(rows)
-        tmpl = _articulation_per_slot(value, len(idx))         # (validated before anything changes)
-        self._set_templates(ARTICULATION, tmpl, idx, rows)
+        self._set_templates(ARTICULATION, value, rows)
 
     def set_form(self, value, rows: Optional[Sequence[int]] = None):
         """The form for all slots (rows=None) or the listed ones: a form in any form form_template takes -- a letter string
@@ -2450,33 +2424,16 @@ class ForcedDecoder:
         reset the slot's replay state.  A call for all slots packs the table anew.  A slot that is off decodes bit for bit
         what it decoded without the feature; a decoder that never switched a slot on allocates nothing and launches the
         kernels it always launched."""
-        idx = self._slots(rows)
-        tmpl = _form_per_slot(value, len(idx))                 # (validated before anything changes)
-        r = FORM
-        if self.form_ctl is None:
-            if all(t is None for t in tmpl):
-                return
-            need = sum(t.shape[0] for t in {t.tobytes(): t for t in tmpl if t is not None}.values())
-            if need > r.rows_max:
-                raise CommuHipError(f"{r.label}: the distinct templates need more than the table's {r.rows_max} rows "
-                                    f"(0 in use, {need} asked for)")
-        self._first_use_form()
-        self._write_words(r, idx, self._pack(r, tmpl, fresh=rows is None), rows)
+        self._set_templates(FORM, value, rows)
 
     def _first_use_form(self):
         """What the first form allocates: the words (all off), the table (all free), the slots' replay state and replay
         tokens; the captured graphs are dropped, once: they hold the launches without the rule."""
-        if self.form_ctl is not None:
+        if not self._alloc_rule(FORM):
             return
-        B, i32 = self.B, torch.int32
-        self.form_ctl = torch.full((B,), FORM_OFF, dtype=i32, device=self.dev)
-        self._form_host = np.full(B, FORM_OFF, dtype=np.int32)
-        self._form_table_host = np.zeros((FORM.rows_max, 4), dtype=np.uint32)
-        self.form_table = torch.zeros(FORM.rows_max, 4, dtype=i32, device=self.dev)
-        self._form_used, self._form_index = 0, {}
-        self.form_state = torch.zeros(B, call("commu_form_state_ints"), dtype=i32, device=self.dev)
-        self.form_tok = torch.full((B,), -1, dtype=i32, device=self.dev)
-        self._form_reset(0, B)
+        self.form_state = torch.zeros(self.B, call("commu_form_state_ints"), dtype=torch.int32, device=self.dev)
+        self.form_tok = torch.full((self.B,), -1, dtype=torch.int32, device=self.dev)
+        self._form_reset(0, self.B)
         self.graph = self.graph_long = None
 
     def _form_reset(self, first: int, n: int):
@@ -2811,35 +2768,15 @@ class ForcedDecoder:
     # logit_bias: a constraint row for the slot's next attempt (None: the slot keeps its row; set_logit_bias clears one).
     # grammar: True / False switches the slot's event grammar for its next attempt (None: the slot keeps its switch).
     # harmony: True / False switches the slot's harmony constraint for its next attempt (None: the slot keeps its switch).
-    # note_order: the slot's note-order control for its next attempt (set_note_order's values; None: the slot keeps its word).
-    # voices: the slot's voice word for its next attempt (set_voices' values, False: off; None: the slot keeps its word).
-    # density: the slot's density word for its next attempt (set_density's values, False: off; None: the slot keeps its word).
-    # interval: the slot's interval word for its next attempt (set_interval's values, False: off; None: the slot keeps its word).
-    # onsets: the slot's onset template for its next attempt (set_onsets' values, False: off; None: the slot keeps its word).
-    # guide: the slot's guide track for its next attempt (set_guide's values, False: off; None: the slot keeps its word).
-    # articulation: the slot's articulation for its next attempt (set_articulation's values, False: off; None: the slot keeps
-    # its word).
-    # form: the slot's form for its next attempt (set_form's values, False: off; None: the slot keeps its word); the slot's
-    # replay state is reset with its record whatever the form.
+    # **rules: one keyword per rule of SLOT_RULES (note_order, voices, density, interval, onsets, guide, articulation, form):
+    # the slot's setting for its next attempt, the values of the rule's setter with False for off (None: the slot keeps its
+    # word).  They are set in the table's order, so what a rule implies is in place before it; the slot's replay state is
+    # reset with its record whatever the form.
     def rearm(self, b: int, uniforms_row: Optional[np.ndarray] = None, sampling=None, logit_bias=None, grammar=None,
-              harmony=None, note_order=None, voices=None, density=None, interval=None, onsets=None, guide=None,
-              articulation=None, form=None):
-        if form is not None:
-            self.set_form(form, rows=[b])
-        if note_order is not None:
-            self.set_note_order(note_order, rows=[b])
-        if voices is not None:
-            self.set_voices(voices, rows=[b])
-        if density is not None:
-            self.set_density(density, rows=[b])
-        if interval is not None:
-            self.set_interval(interval, rows=[b])
-        if onsets is not None:
-            self.set_onsets(onsets, rows=[b])
-        if guide is not None:
-            self.set_guide(guide, rows=[b])
-        if articulation is not None:
-            self.set_articulation(articulation, rows=[b])
+              harmony=None, **rules):
+        for kw, value in _rule_values(rules).items():
+            if value is not None:
+                getattr(self, RULE_OF[kw].setter)(value, rows=[b])
         if sampling is not None:
             self.set_sampling(*sampling, rows=[b])
         if logit_bias is not None:
@@ -3040,14 +2977,8 @@ class ForcedDecoder:
                 "e_chord_tok": z(R, self.ld_chord), "e_chord_pos": z(R, self.ld_chord),
                 "e_temperature": z(R, dtype=F32), "e_top_k": z(R), "e_top_p": z(R, dtype=F32),
                 "e_bias": z(R, VPAD, dtype=F32), "e_gram_on": z(R, dtype=u8), "e_harm_on": z(R, dtype=u8),
-                "e_order": torch.full((R,), NOTE_ORDER_OFF, dtype=i32, device=dev),
-                "e_voice": torch.full((R,), VOICES_OFF, dtype=i32, device=dev),
-                "e_density": torch.full((R,), DENSITY_OFF, dtype=i32, device=dev),
-                "e_interval": torch.full((R,), INTERVAL_OFF, dtype=i32, device=dev),
-                "e_onset": torch.full((R,), ONSETS_OFF, dtype=i32, device=dev),
-                "e_guide": torch.full((R,), GUIDE_OFF, dtype=i32, device=dev),
-                "e_art": torch.full((R,), ARTICULATION_OFF, dtype=i32, device=dev), "e_cls": z(R, N_CLASSES + 1, 4),
-                "e_form": torch.full((R,), FORM_OFF, dtype=i32, device=dev),
+                **{r.entry: torch.full((R,), r.off, dtype=i32, device=dev) for r in SLOT_RULES},
+                "e_cls": z(R, N_CLASSES + 1, 4),
                 "hdr": hdr, "stage": z(words),
                 # two pinned staging buffers and an event each: the host never overwrites a buffer whose copy is in flight
                 "pin": [torch.zeros(words, dtype=i32).pin_memory() for _ in range(2)],
@@ -3071,8 +3002,8 @@ class ForcedDecoder:
     def _pool_args(self):
         """The arm launch's argument block, rebuilt when an optional array was allocated since (a null twin: not written)."""
         P = self._pool
-        opt = (self.bias, self.gram_on, self.harm_on, self.order_ctl, self.voice_ctl, self.density_ctl, self.interval_ctl,
-               self.onset_ctl, self.guide_ctl, self.art_ctl, self.cls_ctl, self.trace, self.form_ctl)
+        words = {r: getattr(self, r.ctl) for r in SLOT_RULES}
+        opt = (self.bias, self.gram_on, self.harm_on, self.cls_ctl, self.trace) + tuple(words.values())
         sig = tuple(None if t is None else t.data_ptr() for t in opt)
         if P["args"] is None or P["sig"] != sig:
             st = self.state
@@ -3092,15 +3023,8 @@ class ForcedDecoder:
                 **on(self.bias, {"bias": self.bias, "e_bias": P["e_bias"], "ld_bias": VPAD}),
                 **on(self.gram_on, {"gram_on": self.gram_on, "e_gram_on": P["e_gram_on"]}),
                 **on(self.harm_on, {"harm_on": self.harm_on, "e_harm_on": P["e_harm_on"]}),
-                **on(self.order_ctl, {"order_ctl": self.order_ctl, "e_order": P["e_order"]}),
-                **on(self.voice_ctl, {"voice_ctl": self.voice_ctl, "e_voice": P["e_voice"]}),
-                **on(self.density_ctl, {"density_ctl": self.density_ctl, "e_density": P["e_density"]}),
-                **on(self.interval_ctl, {"interval_ctl": self.interval_ctl, "e_interval": P["e_interval"]}),
-                **on(self.onset_ctl, {"onset_ctl": self.onset_ctl, "e_onset": P["e_onset"]}),
-                **on(self.guide_ctl, {"guide_ctl": self.guide_ctl, "e_guide": P["e_guide"]}),
-                **on(self.art_ctl, {"art_ctl": self.art_ctl, "e_art": P["e_art"]}),
-                **on(self.form_ctl, {"form_ctl": self.form_ctl, "e_form": P["e_form"], "form_state": self.form_state,
-                                     "form_tok": self.form_tok}),
+                **{k: v for r, w in words.items() if w is not None for k, v in ((r.ctl, w), (r.entry, P[r.entry]))},
+                **on(self.form_ctl, {"form_state": self.form_state, "form_tok": self.form_tok}),
                 **on(self.cls_ctl, {"cls_ctl": self.cls_ctl, "e_cls": P["e_cls"]}))
             P["sig"] = sig
         if P["primed"]:
@@ -3108,15 +3032,14 @@ class ForcedDecoder:
         return P["args"]
 
     def admit(self, entry: int, encoded_meta: Sequence[int], input_data, sampling=None, logit_bias=None, grammar=False,
-              harmony=False, note_order=None, voices=None, class_table=None, primed=None, density=None, interval=None,
-              onsets=None, guide=None, articulation=None, form=None):
+              harmony=False, class_table=None, primed=None, **rules):
         """Compose store entry `entry` for a request and upload it with its K/V image: the state record, sequence head
         and chord rows as load() builds them, klen0 = n_cond, the sampling triple (None: the decoder's), the bias row
-        (None: zeros), the grammar and harmony switches (they switch on what the decoder has a table for), the
-        note-order, voice, density and interval words (None: off), the onset word of the template `onsets` (None: off; the
-        template's rows go to the decoder's own table, where the same template is stored once -- no table bytes move per arm),
-        the guide word of the guide track `guide` (likewise), the articulation word of `articulation` (likewise), the form word of `form` (likewise; the arm launch resets the slot's
-        replay state and records the Bars of the entry's sequence head) and, where the decoder has class records, the request's record row
+        (None: zeros), the grammar and harmony switches (they switch on what the decoder has a table for), the word of
+        every rule of SLOT_RULES (**rules: one setting for the request by the rule's keyword, None: off; what a rule
+        implies is switched on as its setter does; a template's rows go to the decoder's own table, where the same template
+        is stored once -- no table bytes move per arm; the arm launch resets the slot's replay state and records the Bars
+        of the entry's sequence head) and, where the decoder has class records, the request's record row
         (class_table: its NaN-table, None: the base triple in every record).  The image is written by ONE memory-less
         forward over this request's single column [n_cond, 1] and the prefill scatter of the cache's format into the
         store: it does not depend on what else is admitted or decoding.  Everything is ordered on the current stream.
@@ -3124,6 +3047,7 @@ class ForcedDecoder:
         record as the replay left it, the sequence head [0] + meta + prompt, the replay's trace row, klen0 as replayed,
         and the image comes from the forward over the single column [0] + meta[:n-1] + fed (T = klen0, B = 1): the forward
         load(prompts=) runs at one slot."""
+        rules = _rule_values(rules)
         P = getattr(self, "_pool", None)
         if P is None:
             raise CommuHipError("admit: pool_open() first")
@@ -3136,42 +3060,21 @@ class ForcedDecoder:
             raise CommuHipError(f"encoded_meta: the pool was opened for {n_cond} conditioning tokens, got {len(encoded_meta)}")
         t, k, p = sampling_rows(1, *((self.temperature, self.top_k, self.top_p) if sampling is None else sampling))
         bias = None if logit_bias is None else logit_bias_rows(logit_bias, 1)[0]
-        order = note_order_ctl(note_order, 1)
-        vox = voices_ctl(voices, 1)
-        den = density_ctl(density, 1)
-        mel = interval_ctl(interval, 1)
-        ons = _onsets_per_slot(onsets, 1)
-        if ons[0] is not None and self.onset_ctl is None:
-            raise CommuHipError("admit: an onset template, but the decoder has no onset words (set_onsets)")
-        gde = _guide_per_slot(guide, 1)
-        if gde[0] is not None and self.guide_ctl is None:
-            raise CommuHipError("admit: a guide track, but the decoder has no guide words (set_guide)")
-        art = _articulation_per_slot(articulation, 1)
-        if art[0] is not None and self.art_ctl is None:
-            raise CommuHipError("admit: an articulation, but the decoder has no articulation words (set_articulation)")
-        frm = _form_per_slot(form, 1)
-        if frm[0] is not None and self.form_ctl is None:
-            raise CommuHipError("admit: a form, but the decoder has no form words (set_form)")
-        if frm[0] is not None:
-            _form_needs_grammar(frm, [0] if grammar else [])
+        vals = {RULE_OF[kw]: RULE_OF[kw].normalize(v, 1) for kw, v in rules.items()}
+        for r, v in vals.items():
+            if r.is_on(v[0]) and getattr(self, r.ctl) is None:
+                raise CommuHipError(f"admit: {r.asks} ({r.setter})")
+        _form_needs_grammar(vals[FORM], [0] if grammar else [])
         if grammar and (self.gram is None or self._gram_host is None):
             raise CommuHipError("admit: grammar switched on, but the decoder has no grammar table (set_grammar)")
         if harmony and (self.harm is None or self._harm_host is None):
             raise CommuHipError("admit: harmony switched on, but the decoder has no harmony table (set_harmony)")
         if bias is not None and self.bias is None:
             raise CommuHipError("admit: a logit bias, but the decoder has no bias rows (set_logit_bias)")
-        if order[0] != NOTE_ORDER_OFF and self.order_ctl is None:
-            raise CommuHipError("admit: note order switched on, but the decoder has no note-order words (set_note_order)")
-        if mel[0] != INTERVAL_OFF and self.interval_ctl is None:
-            raise CommuHipError("admit: a melodic interval, but the decoder has no interval words (set_interval)")
-        if den[0] != DENSITY_OFF and self.density_ctl is None:
-            raise CommuHipError("admit: a note density, but the decoder has no density words (set_density)")
-        if den[0] != DENSITY_OFF and vox[0] == VOICES_OFF:
-            vox[0] = 0                        # (set_density: the count rides on the voice cap's walk, word 0 = no cap)
-        if vox[0] != VOICES_OFF and self.voice_ctl is None:
-            raise CommuHipError("admit: a voice cap, but the decoder has no voice words (set_voices)")
-        if vox[0] != VOICES_OFF and order[0] == NOTE_ORDER_OFF:
-            order[0] = 0                      # (set_voices: the voice cap relies on the note order, word 0 = no cap)
+        for r in reversed(SAMPLING_RULES):          # (from the top: the density reaches the note order through the voices)
+            dep = RULE_OF.get(r.implies)
+            if dep is not None and r.is_on(vals[r][0]) and not dep.is_on(vals[dep][0]):
+                vals[dep][0] = 0                  # (as the rule's setter: word 0, no cap, where the request leaves it off)
         if class_table is not None and self.cls_ctl is None:
             raise CommuHipError("admit: a class table, but the decoder has no class records (set_class_sampling)")
         comps = input_data.chord_token_components
@@ -3212,14 +3115,9 @@ class ForcedDecoder:
                 up(P["e_bias"][entry], bias)
         P["e_gram_on"][entry].fill_(1 if grammar else 0)
         P["e_harm_on"][entry].fill_(1 if harmony else 0)
-        P["e_order"][entry].fill_(int(order[0]))
-        P["e_voice"][entry].fill_(int(vox[0]))
-        P["e_density"][entry].fill_(int(den[0]))
-        P["e_interval"][entry].fill_(int(mel[0]))
-        P["e_onset"][entry].fill_(int(ONSETS_OFF if ons[0] is None else self._pack(ONSETS, ons)[0]))
-        P["e_guide"][entry].fill_(int(GUIDE_OFF if gde[0] is None else self._pack(GUIDE, gde)[0]))
-        P["e_art"][entry].fill_(int(ARTICULATION_OFF if art[0] is None else self._pack(ARTICULATION, art)[0]))
-        P["e_form"][entry].fill_(int(FORM_OFF if frm[0] is None else self._pack(FORM, frm)[0]))
+        for r, v in vals.items():
+            word = r.off if not r.is_on(v[0]) else self._pack(r, v)[0] if r.rows_max else v[0]
+            P[r.entry][entry].fill_(int(word))
         if self.cls_ctl is not None:
             tab = np.full((1, N_CLASSES + 1, 3), np.nan) if class_table is None else class_sampling_table(class_table)[None]
             rec = class_ctl_records(tab, [t, k, p])
@@ -3420,11 +3318,10 @@ class PoolRequest:
     """One request of BatchedGenerator.generate_pool: what generate_stream takes for it alone.  accept: a callable
     (seq, report) -> bool, None accepts every sequence that is not None; logit_bias: one row; grammar / harmony: a
     per-request bool (None: on where the pool has a table), they may only switch on what the pool has a table for;
-    note_order / voices / density / interval / onsets: as generate_stream's (onsets: ONE template in any form onset_rows
-    takes; the pool packs its requests' templates into one table); guide: ONE guide track in any form guide_template takes,
-    likewise; articulation: ONE articulation in any form articulation_template takes, likewise (hold_guide needs the request's
-    own guide).  prompt: token ids that follow the conditioning tokens and that every
-    attempt of THIS request continues (generate_stream's prompt=); None or [] is an unprimed request."""
+    note_order / voices / density / interval / onsets / guide / articulation / form: the rules of SLOT_RULES, ONE setting
+    each as generate_stream takes it (the pool packs its requests' templates into one table per rule; hold_guide needs the
+    request's own guide, "copy": "rhythm" its grammar on).  prompt: token ids that follow the conditioning tokens and that
+    every attempt of THIS request continues (generate_stream's prompt=); None or [] is an unprimed request."""
     encoded_meta: Sequence[int]
     input_data: object
     need: int
@@ -3445,7 +3342,7 @@ class PoolRequest:
     onsets: Optional[object] = None
     guide: Optional[object] = None
     articulation: Optional[object] = None
-    form: Optional[object] = None          # ONE form in any form form_template takes ("copy": "rhythm" needs the grammar on)
+    form: Optional[object] = None
 
 
 PoolResult = collections.namedtuple("PoolResult", ["sequences", "attempts_started", "logprobs"])
@@ -3568,9 +3465,7 @@ class BatchedGenerator:
         self._decoders = {}
 
     def decoder(self, B, temperature, top_k, max_chords, top_p=1.0, per_slot: bool = False, max_prompt: int = 0,
-                logit_bias=None, shared: bool = False, grammar=None, harmony=None, class_sampling=None,
-                note_order=None, voices=None, density=None, interval=None, onsets=None, guide=None, articulation=None,
-                form=None):
+                logit_bias=None, shared: bool = False, grammar=None, harmony=None, class_sampling=None, **rules):
         """The decoder for B slots, its slots set to the given controls (numbers or one value per slot).  per_slot: the
         caller will read log-probabilities or give slots their own controls later (rearm): the array launches from the
         start.  Otherwise one triple for all slots runs the scalar launches, until a second setting arrives for launches
@@ -3578,34 +3473,21 @@ class BatchedGenerator:
         or one per slot; None clears what an earlier request left on this decoder).  grammar / harmony: the request's event
         grammar and harmony table (None switches off what an earlier request left).  class_sampling: the request's
         class-control table (None resets every slot to its base triple where an earlier request left one; a decoder that
-        never had a table allocates nothing).  note_order: the request's note-order controls (note_order_ctl; None
-        switches off what an earlier request left, and allocates nothing on a decoder that never had one).  voices: the
-        request's voice words (voices_ctl), likewise; a slot that gets one has its note order switched on.  density:
-        the request's density words (density_ctl), likewise; a slot that gets one has its voice word and note order switched
-        on.  interval: the request's interval words (interval_ctl), likewise; it switches nothing else on.  onsets: the request's onset templates (one for all
-        sequences or one per sequence, ForcedDecoder.set_onsets), likewise.  guide: the request's guide tracks (one for
-        all sequences or one per sequence, ForcedDecoder.set_guide), likewise.  articulation: the request's articulations
-        (one for all sequences or one per sequence, ForcedDecoder.set_articulation), likewise.  form: the request's forms
-        (one for all sequences or one per sequence, ForcedDecoder.set_form), likewise; a rhythm bar needs the sequence's
-        grammar on.  shared: the
-        decoder that holds the
-        request's common prompt once (its own cache layout: kept beside the unshared decoder of the same size)."""
+        never had a table allocates nothing).  **rules: one keyword per rule of SLOT_RULES (note_order, voices, density,
+        interval, onsets, guide, articulation, form) -- one value for all sequences or one per sequence, as the rule's
+        setter ForcedDecoder.set_<keyword> takes them; None switches off what an earlier request left, and allocates nothing
+        on a decoder that never had the rule.  shared: the decoder that holds the request's common prompt once (its own
+        cache layout: kept beside the unshared decoder of the same size)."""
+        rules = _rule_values(rules)
         rows = sampling_rows(B, temperature, top_k, top_p)          # (validated before anything is built)
         if logit_bias is not None:
             logit_bias = logit_bias_rows(logit_bias, B)
         gram_table, gram_rows = _grammar_request(grammar, B)
         harm_table = _harmony_request(harmony)
         cls_table = _class_request(class_sampling)
-        order = note_order_ctl(note_order, B)
-        vox = voices_ctl(voices, B)
-        den = density_ctl(density, B)
-        mel = interval_ctl(interval, B)
-        ons = _onsets_per_slot(onsets, B)
-        gde = _guide_per_slot(guide, B)
-        art = _articulation_per_slot(articulation, B)
-        _articulation_needs_guide(art, gde)
-        frm = _form_per_slot(form, B)
-        _form_needs_grammar(frm, gram_rows)
+        vals = {RULE_OF[kw]: RULE_OF[kw].normalize(v, B) for kw, v in rules.items()}
+        _articulation_needs_guide(vals[ARTICULATION], vals[GUIDE])
+        _form_needs_grammar(vals[FORM], gram_rows)
         key = (B, self.trace is not None, self.sliding) + (("shared",) if shared else ())
         dec = self._decoders.get(key)
         if dec is None or dec.ld_chord < max_chords or dec.max_prompt < max_prompt:
@@ -3628,22 +3510,10 @@ class BatchedGenerator:
         dec.set_harmony(harm_table)
         # (class-keyed controls: likewise, after set_sampling -- the inherited entries are the slots' base triples)
         dec.set_class_sampling(cls_table)
-        # (note order: likewise; its first use fills the class records with the base triples set above)
-        dec.set_note_order(order)
-        # (voice cap: likewise, after the note order -- it switches the note order on where the request left it off)
-        dec.set_voices(vox)
-        # (note density: likewise, after the voice cap -- it switches the voice words on where the request left them off)
-        dec.set_density(den)
-        # (melodic interval: likewise; it leaves the other words as they are)
-        dec.set_interval(mel)
-        # (onset templates: likewise; a request without them switches off what the one before left)
-        dec.set_onsets(ons)
-        # (guide track: likewise)
-        dec.set_guide(gde)
-        # (articulation: likewise)
-        dec.set_articulation(art)
-        # (form: likewise)
-        dec.set_form(frm)
+        # (the rules of SLOT_RULES: likewise, in the table's order -- a first use fills the class records with the base
+        # triples set above, and a rule comes after the one it implies, which it switches on where the request left it off)
+        for r, v in vals.items():
+            getattr(dec, r.setter)(v)
         return dec
 
     @staticmethod
@@ -3658,30 +3528,13 @@ class BatchedGenerator:
                  return_logprobs: bool = False, prompts: Optional[Sequence[Sequence[int]]] = None, logit_bias=None,
                  grammar=None, harmony=None, class_sampling=None, note_order=None, voices=None, density=None,
                  interval=None, onsets=None, guide=None, articulation=None, form=None):
-        """temperature / top_k / top_p: a number for the batch or one value per sequence.  form: None / False, one form in
-        any form form_template takes, or a list with one entry (None / False / a form) per sequence -- a bar such a sequence
-        opens itself replays the earlier bar its row names (ForcedDecoder.set_form; "copy": "rhythm" needs grammar=).
-        articulation: None / False, one
-        articulation in any form articulation_template takes, or a list with one entry (None / False / an articulation) per
-        sequence -- such a sequence DRAWS a duration only inside the window of its open bar's row, capped at the bar line
-        (within_bar) and at the first step where its guide bans the pitch just drawn (hold_guide: guide= is required), and a
-        velocity only where the row has a bit; implies none of the other constraints (ForcedDecoder.set_articulation).  guide: None / False, one guide
-        track in any form guide_template takes, or a list with one entry (None / False / a guide) per sequence -- such a
-        sequence DRAWS a pitch only where the cell row of the position its bar is at has a bit, and a position only where
-        the live row has one; implies none of the other constraints (ForcedDecoder.set_guide).  onsets: None / False, one
-        template in any form onset_rows takes, or a list with one entry (None / False / a template) per sequence -- such a
-        sequence DRAWS a position only where the row of its open bar has a bit; implies none of the other constraints
-        (ForcedDecoder.set_onsets).  interval: None / False, a word
-        interval_word(up, down, no_repeat) or one per sequence -- the pitch such a sequence DRAWS lies at most up semitones
-        above and down below the pitch of its last note, and (no_repeat) is not that pitch; implies none of the other
-        constraints (ForcedDecoder.set_interval).  density: None / False, a word
-        density_word(lo, hi) or one per sequence -- a bar such a sequence DRAWS holds at least lo and at most hi notes;
-        switches the sequence's voice word and note order on (ForcedDecoder.set_density).  voices: None / False, a word
-        voices_word(N, r) or one per sequence -- at most N notes such a sequence DRAWS sound at once and (r) no pitch is
-        struck while it sounds; switches the sequence's note order on (ForcedDecoder.set_voices).  note_order: None / False, True,
-        an integer cap in 1 .. 128 or one such value per sequence -- inside a bar the positions such a sequence DRAWS never
-        go back, no pitch is drawn twice at one position and, with a cap, a position gets at most that many notes
-        (ForcedDecoder.set_note_order).  class_sampling: None, a table
+        """temperature / top_k / top_p: a number for the batch or one value per sequence.
+        note_order / voices / density / interval / onsets / guide / articulation / form: the rules of SLOT_RULES, each None /
+        False (off), one value for the batch or one per sequence (a list with one entry per sequence for guide,
+        articulation and form) -- what such a sequence may DRAW, in full at the rule's setter ForcedDecoder.set_<keyword>;
+        voices switches the sequence's note order on, density its voice word and note order, the others imply nothing;
+        articulation's hold_guide needs the sequence's guide=, a form's "copy": "rhythm" its grammar=.
+        class_sampling: None, a table
         (class_sampling()) or its arguments as a dict {"drawn": ..., "after": ...}, one setting for the request -- a triple
         per token class that replaces the sequence's own where the table says so (ForcedDecoder.set_class_sampling).  harmony: None, True (the strict
         default table: only chord tones) or a table (harmony_rows), one setting for the request -- every pitch a sequence
@@ -3693,6 +3546,7 @@ class BatchedGenerator:
         value, ForcedDecoder.logprobs() of the batch.  prompts: one token list per sequence (may be empty) that the
         sequence continues (ForcedDecoder.load): every returned sequence is [0] + meta + prompt + what was generated, and
         generation_length counts the iterations after the prompt."""
+        rules = _rules_of(locals())
         B = len(input_datas)
         max_chords = max(len(d.chord_token_components["chord_token"]) for d in input_datas)
         if prompts is not None and len(prompts) != B:
@@ -3701,9 +3555,7 @@ class BatchedGenerator:
         # (shared_prompt: requests with a prompt only -- without one there is nothing but the short context to share)
         dec = self.decoder(B, temperature, top_k, max_chords, top_p, per_slot=return_logprobs, max_prompt=max_prompt,
                            logit_bias=logit_bias, shared=self.shared_prompt and max_prompt > 0, grammar=grammar,
-                           harmony=self._one_harmony(harmony), class_sampling=class_sampling, note_order=note_order,
-                           voices=voices, density=density, interval=interval, onsets=onsets, guide=guide,
-                           articulation=articulation, form=form)
+                           harmony=self._one_harmony(harmony), class_sampling=class_sampling, **rules)
         uniforms = None
         if bool((dec._sampling[0] != 0).any()) or dec.class_samples():
             srcs = self.uniform_sources or [np.random.RandomState(1000 + b).random_sample for b in range(B)]
@@ -3747,25 +3599,14 @@ class BatchedGenerator:
         harmony: None, True (harmony_table(), strict) or a table (harmony_rows): one setting for the request.
         class_sampling: None, a table (class_sampling()) or {"drawn": ..., "after": ...}: one setting for the request; the
         entries it leaves open inherit the ATTEMPT's own triple (a re-armed slot recomposes them).
-        note_order: None / False, True or an integer cap in 1 .. 128: one setting for every attempt of the request
-        (ForcedDecoder.set_note_order; the bans are read off a slot's seq, so a re-armed slot needs nothing).
-        voices: None / False or a word voices_word(N, r): one setting for every attempt of the request
-        (ForcedDecoder.set_voices; likewise read off seq).
-        density: None / False or a word density_word(lo, hi): one setting for every attempt of the request
-        (ForcedDecoder.set_density; likewise read off seq).
-        interval: None / False or a word interval_word(up, down, no_repeat): one setting for every attempt of the request
-        (ForcedDecoder.set_interval; likewise read off seq).
-        onsets: None / False or ONE template in any form onset_rows takes: one setting for every attempt of the request
-        (ForcedDecoder.set_onsets; the bar count is the forcing record's, the prompt's bars included).
-        guide: None / False or ONE guide track in any form guide_template takes: one setting for every attempt of the request
-        (ForcedDecoder.set_guide; likewise).
-        articulation: None / False or ONE articulation in any form articulation_template takes: one setting for every attempt
-        of the request (ForcedDecoder.set_articulation; likewise; hold_guide needs guide=).
-        form: None / False or ONE form in any form form_template takes: one setting for every attempt of the request
-        (ForcedDecoder.set_form; a re-armed slot's replay state is reset with its record; "copy": "rhythm" needs grammar=).
+        note_order / voices / density / interval / onsets / guide / articulation / form: the rules of SLOT_RULES, each None /
+        False or ONE setting for every attempt of the request, in the form the rule's setter ForcedDecoder.set_<keyword>
+        takes for one slot (the state is read off a slot's seq and its forcing record, so a re-armed slot needs nothing; its
+        replay state is reset with its record); articulation's hold_guide needs guide=, a form's "copy": "rhythm" grammar=.
         share_prompt (opt-in; also on with BatchedGenerator(shared_prompt=True) when a prompt is given): the K/V of the
         context and the prompt are computed and held once for all slots (ForcedDecoder(shared_prompt=True)); the attempts
         returned are the ones the unshared decoder defines, up to the summation order of the attention."""
+        rules = _rules_of(locals())
         B = max(1, min(int(slots), int(need)))
         if share_prompt and not prompt:
             raise CommuHipError("share_prompt: there is no prompt to share (prompt= is empty)")
@@ -3776,24 +3617,7 @@ class BatchedGenerator:
             raise CommuHipError(f"grammar: one setting for the request expected (True or a table), got shape "
                                 f"{np.shape(grammar)}")
         harmony = self._one_harmony(harmony)
-        if note_order is not None and np.ndim(note_order) != 0:
-            raise CommuHipError(f"note_order: one setting for the request expected, got shape {np.shape(note_order)}")
-        if voices is not None and np.ndim(voices) != 0:
-            raise CommuHipError(f"voices: one setting for the request expected, got shape {np.shape(voices)}")
-        if density is not None and np.ndim(density) != 0:
-            raise CommuHipError(f"density: one setting for the request expected, got shape {np.shape(density)}")
-        if interval is not None and np.ndim(interval) != 0:
-            raise CommuHipError(f"interval: one setting for the request expected, got shape {np.shape(interval)}")
-        one_onsets = None if (onsets is None or onsets is False) else onset_rows(onsets)      # (ONE template, validated)
-        if isinstance(guide, list):
-            raise CommuHipError(f"guide: one setting for the request expected, got a list of {len(guide)}")
-        one_guide = None if (guide is None or guide is False) else guide_template(guide)      # (likewise)
-        if isinstance(articulation, list):
-            raise CommuHipError(f"articulation: one setting for the request expected, got a list of {len(articulation)}")
-        one_art = None if (articulation is None or articulation is False) else articulation_template(articulation)
-        if isinstance(form, list):
-            raise CommuHipError(f"form: one setting for the request expected, got a list of {len(form)}")
-        one_form = None if (form is None or form is False) else form_template(form)
+        rules = {kw: RULE_OF[kw].one(v) for kw, v in rules.items()}          # (ONE setting each, templates validated)
         max_chords = len(input_data.chord_token_components["chord_token"])
         # each control's schedule, validated on its own (the three may have different lengths)
         n_of = lambda x: 1 if np.ndim(x) == 0 else len(x)
@@ -3807,9 +3631,7 @@ class BatchedGenerator:
         dec = self.decoder(B, [t[0] for t in first], [t[1] for t in first], max_chords, [t[2] for t in first],
                            per_slot=return_logprobs or varying, max_prompt=0 if prompt is None else len(prompt),
                            logit_bias=logit_bias, shared=share, grammar=grammar, harmony=harmony,
-                           class_sampling=class_sampling, note_order=note_order, voices=voices, density=density,
-                           interval=interval, onsets=one_onsets, guide=one_guide, articulation=one_art,
-                           form=one_form)
+                           class_sampling=class_sampling, **rules)
         started = B
         sampled = bool((sched[0] != 0).any()) or dec.class_samples()          # (a greedy attempt reads no variate)
         uni = np.stack([self.attempt_uniforms(seed, a, dec.ld_u) for a in range(B)]) if sampled else None
@@ -3968,26 +3790,25 @@ class BatchedGenerator:
         harm_table = _harmony_request(self._one_harmony(harmony))
         cls_table = _class_request(class_sampling)
         # each request's controls, validated before anything is built
-        triples, biases, orders, voxes, dens, mels, onss, gdes, arts, frms = [], [], [], [], [], [], [], [], [], []
-        for i, r in enumerate(requests):
-            t, k, p = sampling_rows(1, r.temperature, r.top_k, r.top_p)
+        # (a rule's value per request: the word of a rule without a table, else the template or None; the refusals of the
+        # rules whose value may be a list name the request)
+        triples, biases, vals = [], [], {rule: [] for rule in SLOT_RULES}
+        for i, q in enumerate(requests):
+            t, k, p = sampling_rows(1, q.temperature, q.top_k, q.top_p)
             triples.append((t[0].item(), int(k[0]), p[0].item()))
-            biases.append(None if r.logit_bias is None else logit_bias_rows(r.logit_bias, 1)[0])
-            orders.append(int(note_order_ctl(r.note_order, 1)[0]))
-            voxes.append(int(voices_ctl(r.voices, 1)[0]))
-            dens.append(int(density_ctl(r.density, 1)[0]))
-            mels.append(int(interval_ctl(r.interval, 1)[0]))
-            onss.append(None if (r.onsets is None or r.onsets is False) else onset_rows(r.onsets))
+            biases.append(None if q.logit_bias is None else logit_bias_rows(q.logit_bias, 1)[0])
+            gram_on = (gram_table is not None) if q.grammar is None else bool(q.grammar)
+            for rule in SLOT_RULES:
+                try:
+                    v = getattr(q, rule.kw)
+                    vals[rule].append(rule.one(v) if rule.rows_max else int(rule.normalize(v, 1)[0]))
+                except CommuHipError as e:
+                    if not rule.lists:
+                        raise
+                    raise CommuHipError(f"request {i}: {e}") from None
             try:
-                gdes.append(None if (r.guide is None or r.guide is False) else guide_template(r.guide))
-                arts.append(None if (r.articulation is None or r.articulation is False)
-                            else articulation_template(r.articulation))
-                _articulation_needs_guide(arts[-1:], gdes[-1:])
-                if isinstance(r.form, list):
-                    raise CommuHipError(f"form: one setting for the request expected, got a list of {len(r.form)}")
-                frms.append(None if (r.form is None or r.form is False) else form_template(r.form))
-                _form_needs_grammar(frms[-1:], [0] if ((gram_table is not None) if r.grammar is None else bool(r.grammar))
-                                    else [])
+                _articulation_needs_guide(vals[ARTICULATION][-1:], vals[GUIDE][-1:])
+                _form_needs_grammar(vals[FORM][-1:], [0] if gram_on else [])
             except CommuHipError as e:
                 raise CommuHipError(f"request {i}: {e}") from None
         B = max(1, min(slots, sum(int(r.need) for r in requests)))
@@ -4013,30 +3834,23 @@ class BatchedGenerator:
         if gram_table is not None:
             dec.set_grammar(gram_table)
         dec.set_harmony(harm_table)
-        use_den = any(d != DENSITY_OFF for d in dens)          # (the density rides on the voice words and the note order)
-        use_mel = any(m != INTERVAL_OFF for m in mels)         # (the interval kernel reads all three words, on or off)
-        use_ons = any(t is not None for t in onss)             # (the onsets kernel reads all four words, on or off)
-        use_art = any(t is not None for t in arts)             # (the articulation kernel reads all six, on or off)
-        use_gde = any(t is not None for t in gdes) or use_art  # (the guide kernel reads all five, on or off)
-        use_ons = use_ons or use_gde
-        use_mel = use_mel or use_ons
-        use_order = any(o != NOTE_ORDER_OFF for o in orders) or any(v != VOICES_OFF for v in voxes) or use_den or use_mel
         # (one first use, of the highest tier any request needs; the requests' templates go into the tables before the pool
-        # is opened: admit finds them by their bytes)
-        dec._first_use(T_ART if use_art else T_GDE if use_gde else T_ONS if use_ons else T_MEL if use_mel
-                       else T_DEN if use_den else T_VOX if any(v != VOICES_OFF for v in voxes)
-                       else T_ORD if use_order else T_CLS if cls_table is not None else T_NONE)
-        for r, tmpls, use in ((ONSETS, onss, use_ons), (GUIDE, gdes, use_gde), (ARTICULATION, arts, use_art)):
-            if use:
-                dec._pack(r, tmpls, fresh=True)
+        # is opened: admit finds them by their bytes.  A table rule's kernel reads the tables below it, so every table up
+        # to the highest one in use is packed anew -- articulation makes the guide's and the onsets' exist)
+        used = {rule for rule in SLOT_RULES if any(rule.is_on(v) for v in vals[rule])}
+        dec._first_use(pool_tier({rule.kw for rule in used}, cls_table is not None))
+        top = max([rule.tier for rule in used if rule.rows_max] + [T_NONE])
+        for rule in SAMPLING_RULES:
+            if rule.rows_max and rule.tier <= top:
+                dec._pack(rule, vals[rule], fresh=True)
         if any(b is not None for b in biases):
             dec._first_use(bias=True)
         # (the form rule: the requests' forms go into its table before the pool is opened; a later pool without one switches
         # every slot off, and a decoder that never had one allocates nothing)
         dec.set_form(None)
-        if any(t is not None for t in frms):
+        if FORM in used:
             dec._first_use_form()
-            dec._pack(FORM, frms, fresh=True)
+            dec._pack(FORM, vals[FORM], fresh=True)
         klen0_max = max([n_cond] + [p["klen0"] for p in replays if p is not None])
         dec.pool_open(n_cond, grid_rows=klen0_max)
         cls_samples = cls_table is not None and bool((np.nan_to_num(cls_table[..., 0], nan=0.0) != 0).any())
@@ -4057,10 +3871,8 @@ class BatchedGenerator:
                               logit_bias=biases[j.request],
                               grammar=(gram_table is not None) if r.grammar is None else bool(r.grammar),
                               harmony=(harm_table is not None) if r.harmony is None else bool(r.harmony),
-                              note_order=orders[j.request], voices=voxes[j.request], class_table=cls_table,
-                              primed=replays[j.request], density=dens[j.request], interval=mels[j.request],
-                              onsets=onss[j.request], guide=gdes[j.request], articulation=arts[j.request],
-                              form=frms[j.request])
+                              class_table=cls_table, primed=replays[j.request],
+                              **{rule.kw: v[j.request] for rule, v in vals.items()})
                 sampled = triples[j.request][0] != 0 or cls_samples          # (a greedy attempt reads no variate)
                 staged.append((j.slot, j.entry, self.attempt_uniforms(r.seed, j.attempt, dec.ld_u) if sampled else None))
                 if held[j.slot] is not None and held[j.slot] != j.request:
