@@ -83,6 +83,7 @@ class DecodeLoopArgs(C.Structure):
                 ("klen", c_p), ("lmax", c_i),
                 ("bias", c_p), ("gram", c_p), ("gram_on", c_p), ("harm", c_p), ("harm_on", c_p),
                 ("ld_bias", c_i), ("ld_gram", c_i), ("ld_harm", c_i),
+                ("form_src", c_p), ("form_src_len", c_i),
                 ("form_ctl", c_p), ("form_table", c_p), ("form_rows", c_i), ("form_state", c_p), ("form_tok", c_p),
                 ("art_ctl", c_p), ("art_table", c_p), ("art_rows", c_i),
                 ("guide_ctl", c_p), ("guide_table", c_p), ("guide_rows", c_i),
@@ -248,6 +249,11 @@ PROTOTYPES = {
                                c_p, c_p, c_i, c_p, c_p, c_i, c_p],
     "commu_forcing_post_form": [c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p,
                                 c_p, c_p, c_i, c_p, c_p, c_i, c_p],
+    "commu_form_src_max": [],
+    "commu_forcing_pre_form_src": [c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p,
+                                   c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_p],
+    "commu_forcing_post_form_src": [c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p,
+                                    c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_p],
     "commu_form_reset": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p],
     "commu_decode_loop_args_bytes": [],
     "commu_decode_sample_post_pre": [C.POINTER(DecodeLoopArgs), c_p],
@@ -286,7 +292,7 @@ PROTOTYPES = {
 _RESTYPE = {"commu_decode_tail_pack_bytes": C.c_longlong, "commu_attn_pf_bytes": C.c_longlong, "commu_hip_version": C.c_char_p, "commu_attn_p_scratch_elems": C.c_longlong,
             "commu_gemm_nt_signbits_words": C.c_longlong, "commu_pack_batch": C.c_longlong}
 _NOCHECK = {"commu_layernorm_bwd_nblocks", "commu_colsum_slabs", "commu_embed_bwd_ws_rows", "commu_hip_version", "commu_attn_bwd_qrows", "commu_attn_fwd_generation", "commu_attn_bwd_kv_generation", "commu_colsum_slab_pass", "commu_gemm_tn_grouped_slices", "commu_gemm_tn_grouped_slices_budget", "commu_attn_band_slabs", "commu_attn_band_pairs",
-            "commu_forcing_state_ints", "commu_form_state_ints", "commu_decode_tail_supported", "commu_decode_tail_sync_words", "commu_decode_tail_sync_words_for", "commu_decode_tail_pack_bytes", "commu_attn_p_scratch_elems", "commu_gemm_nt_signbits_words", "commu_pack_batch", "commu_attn_pf_bytes",
+            "commu_forcing_state_ints", "commu_form_state_ints", "commu_form_src_max", "commu_decode_tail_supported", "commu_decode_tail_sync_words", "commu_decode_tail_sync_words_for", "commu_decode_tail_pack_bytes", "commu_attn_p_scratch_elems", "commu_gemm_nt_signbits_words", "commu_pack_batch", "commu_attn_pf_bytes",
             "commu_decode_prefix_chunk", "commu_decode_prefix_group", "commu_sample_args_bytes", "commu_decode_loop_args_bytes",
             "commu_decode_arm_args_bytes", "commu_decode_arm_primed_args_bytes", "commu_decode_arm_primed_chunk_rows"}
 

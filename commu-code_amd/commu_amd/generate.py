@@ -1049,6 +1049,24 @@ FORM_BARS_MAX = 64             # bars of one form
 FORM_TRANSPOSE_MAX = 48
 FORM_COPIES = ("all", "rhythm")
 FORM_BAR_KEYS = {"of", "copy", "transpose"}
+# ---- takes: a bar may also replay a bar of a finished sequence the user already has.  A TAKE ROW has bit 7 of word 0 set,
+# word 1 `begin` and word 2 `end`: the source bar is form_src[begin .. end) of the decoder's take buffer.  In a template the
+# two are counted from the take's own start; the decoder rebases them to where it placed the take (ForcedDecoder._pack).
+FORM_TAKE_BIT = 1 << 7
+FORM_SRC_MAX = 1 << 18         # ints of the decoder's take buffer (1 MiB): 64 takes of 4096 tokens
+FORM_TAKE_KEYS = {"take", "of", "copy", "transpose"}
+FORM_KEEP_KEYS = {"keep", "redo", "repitch"}
+
+
+class FormTakes(np.ndarray):
+    """A form that names takes: its uint32 [R][4] rows (take rows carry begin / end counted from their take's start) with
+    .takes, the takes' tokens as int32 arrays, and .take_of, per bar the index of the take its row reads (-1: none)."""
+    takes: tuple = ()
+    take_of: tuple = ()
+
+    def __array_finalize__(self, obj):
+        self.takes = getattr(obj, "takes", ())
+        self.take_of = getattr(obj, "take_of", ())
 
 
 def form_word(base: int, bars: int) -> int:
@@ -1086,6 +1104,12 @@ def _form_bar(i: int, bar) -> int:
     if bar["of"] >= i:
         raise CommuHipError(f'form: bar {i}: "of": {bar["of"]} is not an earlier bar (a bar replays one below its own index'
                             + ("; bar 0 is always free)" if i == 0 else ")"))
+    return form_row_word(bar["of"], *_form_mode(i, bar))
+
+
+def _form_mode(i: int, bar: dict):
+    """("all" | "rhythm", transpose) of a replay bar's document."""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
     copy = bar.get("copy", "all")
     if copy not in FORM_COPIES:
         raise CommuHipError(f'form: bar {i}: "copy": "all" or "rhythm" expected, got {copy!r}')
@@ -1095,7 +1119,137 @@ def _form_bar(i: int, bar) -> int:
                             f"expected, got {s!r}")
     if s != 0 and copy == "rhythm":
         raise CommuHipError(f'form: bar {i}: "transpose": {s} beside "copy": "rhythm" (the pitches of such a bar are drawn)')
-    return form_row_word(bar["of"], copy, s)
+    return copy, s
+
+
+def form_take_bars(tokens) -> List[tuple]:
+    """The bars of a take as (begin, end) index pairs: bar j is the stretch behind the take's (j+1)-th Bar token up to its
+    next Bar, the last bar up to the list's end.  An EMPTY bar is given as the one-token stretch of its own Bar token (no
+    note group lies in it, so its replay is an empty bar; begin == end would be a free row)."""
+    at = [i for i, t in enumerate(tokens) if int(t) == ONSET_BAR]
+    ends = at[1:] + [len(tokens)]
+    return [(a + 1, e) if a + 1 < e else (a, a + 1) for a, e in zip(at, ends)]
+
+
+def _form_take_tokens(t: int, ids) -> np.ndarray:
+    if isinstance(ids, dict) and set(ids) == {"from_tokens"}:
+        ids = ids["from_tokens"]
+    try:
+        arr = np.asarray(ids)
+    except ValueError:
+        arr = None
+    if arr is None or arr.ndim != 1 or arr.size == 0 or arr.dtype.kind not in "iu":
+        raise CommuHipError(f"form: take {t}: a list of token ids expected, got {ids!r:.80}")
+    if arr.size > FORM_SRC_MAX:
+        raise CommuHipError(f"form: take {t}: {arr.size} tokens, the take buffer holds {FORM_SRC_MAX}")
+    bad = np.flatnonzero((arr < 0) | (arr >= TOKEN_OFFSET.VOCAB_SIZE))
+    if bad.size:
+        raise CommuHipError(f"form: take {t}: token {int(arr[bad[0]])} at index {int(bad[0])} is outside "
+                            f"[0, {TOKEN_OFFSET.VOCAB_SIZE})")
+    if not (arr == ONSET_BAR).any():
+        raise CommuHipError(f"form: take {t}: no Bar token: a take without a bar line has no bar to replay")
+    return np.ascontiguousarray(arr, dtype=np.int32)
+
+
+def _form_with_takes(x) -> "FormTakes":
+    """The {"takes": ..., "bars": ...} document as a FormTakes."""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    takes, bars = x["takes"], x["bars"]
+    if isinstance(takes, dict) or (isinstance(takes, (list, tuple, np.ndarray)) and len(takes) and is_int(takes[0])):
+        takes = [takes]                                        # (one take, given bare)
+    if not isinstance(takes, (list, tuple)) or not takes or not isinstance(bars, (list, tuple)):
+        raise CommuHipError('form: {"takes": [[ids], ...] | {"from_tokens": [ids]}, "bars": [...]} expected, got '
+                            f"{x!r:.120}")
+    takes = [_form_take_tokens(t, ids) for t, ids in enumerate(takes)]
+    if not 1 <= len(bars) <= FORM_BARS_MAX:
+        raise CommuHipError(f"form: a form holds 1 .. {FORM_BARS_MAX} bars, got {len(bars)}" +
+                            (f" (bar {FORM_BARS_MAX} is one too many)" if bars else ""))
+    spans = [form_take_bars(tk) for tk in takes]
+    out = np.zeros((len(bars), 4), dtype=np.uint32)
+    take_of = [-1] * len(bars)
+    for i, bar in enumerate(bars):
+        if not isinstance(bar, dict) or "take" not in bar:
+            out[i, 0] = _form_bar(i, bar)
+            continue
+        extra = sorted(set(map(str, bar)) - FORM_TAKE_KEYS)
+        if extra:
+            raise CommuHipError(f"form: bar {i}: unknown key {extra[0]!r} (known: {sorted(FORM_TAKE_KEYS)})")
+        t = bar["take"]
+        if t is None and len(takes) == 1:
+            t = 0
+        if not is_int(t) or not 0 <= t < len(takes):
+            raise CommuHipError(f'form: bar {i}: "take": {t!r} is not one of the {len(takes)} takes')
+        j = bar.get("of")
+        if not is_int(j) or not 0 <= j < len(spans[t]):
+            raise CommuHipError(f'form: bar {i}: "of": {j!r} is not a bar of take {t} (it has {len(spans[t])})')
+        if j >= FORM_BARS_MAX:
+            raise CommuHipError(f'form: bar {i}: "of": {j}: a row names one of a take\'s first {FORM_BARS_MAX} bars')
+        out[i] = (form_row_word(j, *_form_mode(i, bar)) | FORM_TAKE_BIT, spans[t][j][0], spans[t][j][1], 0)
+        take_of[i] = int(t)
+    res = out.view(FormTakes)
+    res.takes, res.take_of = tuple(takes), tuple(take_of)
+    return res
+
+
+def _form_keep(x) -> dict:
+    """The short form {"keep": take, "redo": [bars], "repitch": [bars]} written out in full."""
+    is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    take = _form_take_tokens(0, x["keep"])
+    n = len(form_take_bars(take))
+    lists = {}
+    for k in ("redo", "repitch"):
+        v = x.get(k, [])
+        if not isinstance(v, (list, tuple)) or not all(is_int(b) for b in v):
+            raise CommuHipError(f'form: "{k}": a list of bar indices expected, got {v!r}')
+        for b in v:
+            if not 0 <= b < n:
+                raise CommuHipError(f'form: bar {b}: "{k}" names a bar the take does not have (it has {n})')
+        lists[k] = set(int(b) for b in v)
+    both = sorted(lists["redo"] & lists["repitch"])
+    if both:
+        raise CommuHipError(f'form: bar {both[0]}: listed in "redo" and in "repitch"')
+    bars = [None if i in lists["redo"] else
+            {"take": 0, "of": i, "copy": "rhythm"} if i in lists["repitch"] else {"take": 0, "of": i}
+            for i in range(min(n, FORM_BARS_MAX))]
+    return {"takes": [take], "bars": bars}
+
+
+def form_document(template) -> dict:
+    """A form as a document form_template reads, in the full form: {"bars": [...]} and, where it names takes, "takes"."""
+    rows = form_template(template)
+    take_of = getattr(rows, "take_of", ())
+    bars = []
+    for i, w in enumerate(rows[:, 0].tolist()):
+        f = form_row_fields(w)
+        if f is None:
+            bars.append(None)
+            continue
+        bar = {"of": f[0], "copy": f[1], "transpose": f[2]}
+        if w & FORM_TAKE_BIT:
+            bar = {"take": int(take_of[i]), **bar}
+        bars.append(bar)
+    if getattr(rows, "takes", ()):
+        return {"takes": [tk.tolist() for tk in rows.takes], "bars": bars}
+    return {"bars": bars}
+
+
+def _form_takes_checked(x: "FormTakes") -> "FormTakes":
+    """A FormTakes handed back in: the rows must still be the rows of its takes."""
+    if x.ndim != 2 or x.shape[1] != 4 or not 1 <= x.shape[0] <= FORM_BARS_MAX or x.dtype != np.uint32:
+        raise CommuHipError(f"form: a uint32 form is [1 .. {FORM_BARS_MAX}][4], got {x.dtype} {x.shape}")
+    if len(x.take_of) != x.shape[0]:
+        raise CommuHipError(f"form: {x.shape[0]} rows beside take_of for {len(x.take_of)} bars (a slice of a form with "
+                            "takes is not one)")
+    for i, (w, begin, end, w3) in enumerate(np.asarray(x).tolist()):
+        f, k = form_row_fields(w), x.take_of[i]
+        ok = w >> 15 == 0 and w3 == 0 and (f is None or abs(f[2]) <= FORM_TRANSPOSE_MAX and not (f[1] == "rhythm" and f[2]))
+        if f is not None and w & FORM_TAKE_BIT:
+            ok = ok and 0 <= k < len(x.takes) and 0 <= begin < end <= x.takes[k].size
+        else:
+            ok = ok and k < 0 and begin == 0 and end == 0 and (w == 0 if f is None else f[0] < i)
+        if not ok:
+            raise CommuHipError(f"form: bar {i}: not a row of a form over its takes: {[w, begin, end, w3]}, take_of {k}")
+    return x
 
 
 def form_template(x) -> np.ndarray:
@@ -1104,14 +1258,28 @@ def form_template(x) -> np.ndarray:
     {"of": j, "copy": "all" | "rhythm", "transpose": s}, ...]} -- bar i is free or replays bar j < i, everything or the
     rhythm only (the pitches are then drawn), transposed by s semitones (all only, -48 .. 48); JSON text or the path of a
     file holding either; or a uint32 array [R][4] that is one already.  1 <= R <= 64, bar 0 is always free.  Pure host code;
-    raises CommuHipError that names the bar."""
+    raises CommuHipError that names the bar.
+    TAKES: {"takes": [[ids], ...] | {"from_tokens": [ids]}, "bars": [null | j | {"of": j, ...} | {"take": t, "of": j,
+    "copy": ..., "transpose": s}, ...]} -- a bar with "take" replays bar j of take t (null: the only take), a finished token
+    sequence of the user's, whose bars are the stretches behind its Bar tokens (form_take_bars); any bar of the form, bar 0
+    included, may name one.  The short form {"keep": {"from_tokens": [ids]}, "redo": [bars], "repitch": [bars]} keeps every
+    bar of the take (up to 64) except those listed: a bar in redo is free, a bar in repitch takes the take's rhythm and draws
+    its pitches; an entry of redo or repitch from 64 on names a bar the take has and the form does not reach -- no row is
+    made for it, bars past the 64th are free.  Such a form comes back as a FormTakes: the rows with the takes' tokens beside
+    them; given one, its rows are checked against its takes (a slice or an edited copy whose take_of no longer lines up with
+    its rows, or whose begin / end leave the take, is refused).
+    ONE INPUT accepted before the takes is refused now: a plain uint32 array whose word 0 has bit 7 set.  The kernels
+    ignored the bit then and read it as "a take row" now, so such a row would silently become a free bar."""
+    if isinstance(x, FormTakes) and x.takes:
+        return _form_takes_checked(x)
     if isinstance(x, np.ndarray) and x.dtype == np.uint32:
         if x.ndim != 2 or x.shape[1] != 4 or not 1 <= x.shape[0] <= FORM_BARS_MAX:
             raise CommuHipError(f"form: a uint32 form is [1 .. {FORM_BARS_MAX}][4], got shape {x.shape}")
         for i, w in enumerate(x[:, 0].tolist()):
             f = form_row_fields(w)
+            # (a take row cannot stand without its take: bit 7 belongs to a FormTakes)
             ok = f is None and w == 0 or f is not None and w >> 15 == 0 and f[0] < i and abs(f[2]) <= FORM_TRANSPOSE_MAX \
-                and not (f[1] == "rhythm" and f[2] != 0)
+                and not (f[1] == "rhythm" and f[2] != 0) and not w & FORM_TAKE_BIT
             if not ok or x[i, 1:].any():
                 raise CommuHipError(f"form: bar {i}: not a row of a form: {x[i].tolist()}")
         return np.ascontiguousarray(x)
@@ -1134,6 +1302,10 @@ def form_template(x) -> np.ndarray:
             if isinstance(doc, str) and not doc.isalpha():
                 raise CommuHipError(f"form: a letter string such as \"AABA\" expected, got {doc!r}")
             return form_template(doc)
+    if isinstance(x, dict) and "keep" in x and set(x) <= FORM_KEEP_KEYS:
+        x = _form_keep(x)
+    if isinstance(x, dict) and set(x) == {"takes", "bars"}:
+        return _form_with_takes(x)
     if not isinstance(x, dict) or set(x) != {"bars"} or not isinstance(x["bars"], (list, tuple)):
         raise CommuHipError('form: a letter string or {"bars": [null | j | {"of": j, "copy": ..., "transpose": s}, ...]} '
                             f"expected, got {x!r}")
@@ -1169,6 +1341,15 @@ def _form_per_slot(x, B: int):
     return _templates_per_slot("form", form_template, x, B)
 
 
+def _form_key(t):
+    """What tells two forms apart: the rows' bytes and, where they name takes, which take each row reads and its tokens
+    (equal rows over different takes are different forms)."""
+    takes = getattr(t, "takes", ())
+    if not takes:
+        return t.tobytes()
+    return t.tobytes(), tuple(t.take_of), tuple(tk.tobytes() for tk in takes)
+
+
 def _form_fold(pitch_token: int, s: int) -> int:
     m = int(pitch_token) - 3 + int(s)
     while m < 0:
@@ -1187,7 +1368,8 @@ def form_violation(seq, start: int, template, drawn=None):
     rule finds them) must equal the source's one for one -- the pitch transposed and folded into 0 .. 127 (all), or any
     pitch (rhythm).  template: anything form_template takes.  drawn (optional, parallel to seq): True where a token was drawn
     by the sampling step (it has a log-probability); then the replayed tokens must not be, and the pitches of a rhythm bar
-    must be."""
+    must be.  A take row's source bar is the bar of its take (the returned source bar is the take's), and a take row's bar is
+    a replay bar whatever its index."""
     rows = form_template(template)
     seq = [int(t) for t in seq]
     bar_at = [i for i, t in enumerate(seq) if t == ONSET_BAR]
@@ -1198,25 +1380,34 @@ def form_violation(seq, start: int, template, drawn=None):
             nxt = len(seq) - 1
         return nxt
 
-    def groups(i):
-        out, g, end = [], bar_at[i] + 1, close_of(i)
+    def groups_in(buf, g, end):
+        out = []
         while g + 3 < end:
-            if _is_note_at(seq, g) and g + 3 < end:
+            if _is_note_at(buf, g) and g + 3 < end:
                 out.append(g)
                 g += 4
             else:
                 g += 1
         return out
+
+    def groups(i):
+        return groups_in(seq, bar_at[i] + 1, close_of(i))
     for i in range(min(len(bar_at), len(rows), FORM_BARS_MAX)):
         f = form_row_fields(rows[i, 0])
         if f is None or bar_at[i] < int(start) or close_of(i) is None or close_of(i) <= bar_at[i]:
             continue
         j, copy, s = f
-        src, dst = groups(j), groups(i)
+        from_seq = seq
+        if int(rows[i, 0]) & FORM_TAKE_BIT:                    # (a take row: the source bar lies in its take)
+            from_seq = [int(t) for t in rows.takes[rows.take_of[i]]]
+            src = groups_in(from_seq, int(rows[i, 1]), min(int(rows[i, 2]), len(from_seq)))
+        else:
+            src = groups(j)
+        dst = groups(i)
         if len(src) != len(dst):
             return i, j, f"{len(dst)} note groups, the source has {len(src)}"
         for a, b in zip(src, dst):
-            want = [seq[a], seq[a + 1], _form_fold(seq[a + 2], s), seq[a + 3]]
+            want = [from_seq[a], from_seq[a + 1], _form_fold(from_seq[a + 2], s), from_seq[a + 3]]
             got = seq[b:b + 4]
             if copy == "rhythm":
                 want[2] = got[2]
@@ -1767,7 +1958,7 @@ ARTICULATION = SlotRule(T_ART, "art", "articulation", ARTICULATION_OFF, _articul
 # allocates nothing of the tiers -- the last of the table, tier -1.  A template is the uint32 rows; a free row is all zeros.)
 FORM = SlotRule(-1, "form", "form", FORM_OFF, _form_per_slot, "a form, but the decoder has no form words", "",
                 form_template, True, FORM_ROWS_MAX, FORM_BARS_MAX, (0, 0, 0, 0),
-                rows_of=lambda t: t, key=lambda t: t.tobytes(), bars=lambda t: t.shape[0],
+                rows_of=lambda t: t, key=lambda t: _form_key(t), bars=lambda t: t.shape[0],
                 word=lambda base, bars, t: form_word(base, bars))
 SLOT_RULES = (ORDER, VOICES, DENSITY, INTERVAL, ONSETS, GUIDE, ARTICULATION, FORM)          # (in tier order, the form last)
 SAMPLING_RULES = SLOT_RULES[:-1]                                                            # (the tiers of the sampling step)
@@ -1823,6 +2014,11 @@ class ForcedDecoder:
     # the form keeps two arrays more per slot: the replay state int32 [B][commu_form_state_ints()] and the replay token [B]
     form_state = None
     form_tok = None
+    # ... and, from the first form that names a take on, the take buffer int32 [FORM_SRC_MAX] with its mirror and its index
+    form_src = None
+    _form_src_host = None
+    _form_src_index: dict = {}
+    _form_src_used = 0
 
     def __init__(self, model, B: int, generation_length: int, memory_length: int, temperature: float, top_k: int,
                  max_chords: int = 64, record_trace: bool = False, top_p: float = 1.0, sliding: bool = False,
@@ -2034,7 +2230,7 @@ class ForcedDecoder:
             for j in idx:
                 ctl[int(j)].fill_(int(host[j]))
 
-    def _pack(self, r, templates, fresh: bool = False):
+    def _pack(self, r, templates, fresh: bool = False, label: str = ""):
         """The control words of the given templates (None: off) in the table of rule r.  Distinct templates, told apart by
         r.key, are packed one behind the other; a template packed before keeps its rows.  fresh: the table is packed anew
         from these templates alone (every slot's word is about to be rewritten).  Refuses, before anything changes, what
@@ -2042,6 +2238,9 @@ class ForcedDecoder:
         index = {} if fresh else dict(getattr(self, r.index))
         used = 0 if fresh else getattr(self, r.used)
         todo, words = [], []
+        # (the form's takes: each distinct take is placed once in the take buffer, and the rows that read it are rebased to
+        # its place; a fresh pack reclaims the takes of forms no longer referenced)
+        place = self._form_src_plan(templates, fresh, label) if r is FORM else None
         for t in templates:
             if t is None:
                 words.append(r.off)
@@ -2054,10 +2253,17 @@ class ForcedDecoder:
                 if used + rows.shape[0] > r.rows_max:
                     raise CommuHipError(f"{r.kw}: the distinct templates need more than the table's {r.rows_max} rows "
                                         f"({used} in use, {rows.shape[0]} more asked for)")
+                if place is not None and getattr(t, "takes", ()):
+                    rows = np.array(rows, dtype=np.uint32)
+                    for i, k in enumerate(t.take_of):
+                        if k >= 0:
+                            rows[i, 1:3] += np.uint32(place[0][t.takes[k].tobytes()])
                 index[key] = used
                 todo.append((used, rows))
                 used += rows.shape[0]
             words.append(r.word(index[key], bars, t))
+        if place is not None:
+            self._form_src_write(*place)
         host, table = getattr(self, r.table_host), getattr(self, r.table)
         for base, rows in todo:
             host[base:base + rows.shape[0]] = rows
@@ -2095,6 +2301,8 @@ class ForcedDecoder:
             if need > r.rows_max:
                 raise CommuHipError(f"{r.kw}: the distinct templates need more than the table's {r.rows_max} rows "
                                     f"(0 in use, {need} asked for)")
+            if r is FORM:
+                self._form_src_plan(tmpl, True)          # (the takes' capacity too, before the first use allocates)
         self._first_use_words(r)
         self._write_words(r, idx, self._pack(r, tmpl, fresh=rows is None), rows)
 
@@ -2423,12 +2631,62 @@ class ForcedDecoder:
         on the current stream: no re-capture.  A word takes effect at the next Bar the slot appends; load() and rearm()
         reset the slot's replay state.  A call for all slots packs the table anew.  A slot that is off decodes bit for bit
         what it decoded without the feature; a decoder that never switched a slot on allocates nothing and launches the
-        kernels it always launched."""
+        kernels it always launched.
+        TAKES: a form may name bars of finished sequences of the user's ({"takes": ..., "bars": [... {"take": t, "of": j}]}
+        or {"keep": ..., "redo": [...], "repitch": [...]}, form_template): such a bar -- any bar, bar 0 included -- replays
+        the take's bar exactly as an own-past row replays its source.  The first form with a take allocates the take buffer
+        (FORM_SRC_MAX ints, once, at a fixed address) and drops the graphs once more; each distinct take is placed once,
+        de-duplicated by bytes, its rows rebased to its place; a call for all slots reclaims the takes no form names any
+        more; what does not fit is refused before anything changes, with the tokens needed against the capacity.
+        Unlike a word, which takes effect at the slot's next Bar, a reclaim takes effect AT ONCE: a call for all slots
+        rewrites the buffer from its start, and a slot that is inside a take's replay bar at that moment goes on reading
+        its old indices -- clamped, so safe, but other tokens -- until its next Bar (an own-past bar has no such hazard, its
+        source is its own sequence).  Switch a form with takes for all slots between runs, before load() or rearm(); a call
+        for listed slots only appends and disturbs nothing.  Not
+        covered beside the above: generation is left to right, so a bar drawn between kept bars knows only those before it;
+        a kept bar gets the chords of its own place in this sequence's progression."""
         self._set_templates(FORM, value, rows)
 
-    def _first_use_form(self):
+    def _form_src_plan(self, templates, fresh: bool, label: str = ""):
+        """Where the takes of the given forms go in the take buffer: (index: a take's bytes -> its first int, ints in use,
+        [(first int, tokens)] still to be written).  Nothing changes; refuses what the buffer does not hold."""
+        index = {} if fresh else dict(self._form_src_index)
+        used = 0 if fresh else self._form_src_used
+        todo, over = [], None
+        for i, t in enumerate(templates):
+            for tk in (getattr(t, "takes", ()) if t is not None else ()):
+                key = tk.tobytes()
+                if key not in index:
+                    index[key] = used
+                    todo.append((used, tk))
+                    used += int(tk.size)
+            if over is None and used > FORM_SRC_MAX:
+                over = i
+        if over is not None:
+            raise CommuHipError((f"{label} {over}: " if label else "") + f"form: the distinct takes need {used} tokens, "
+                                f"the take buffer holds {FORM_SRC_MAX}")
+        return index, used, todo
+
+    def _form_src_write(self, index, used, todo):
+        """The planned takes written to the buffer in place, ordered on the current stream."""
+        if todo:
+            self._first_use_form(takes=True)
+            for first, tk in todo:
+                self._form_src_host[first:first + tk.size] = tk
+                self.form_src[first:first + tk.size].copy_(torch.from_numpy(tk))
+        self._form_src_index, self._form_src_used = index, used
+
+    def _first_use_form(self, takes: bool = False):
         """What the first form allocates: the words (all off), the table (all free), the slots' replay state and replay
-        tokens; the captured graphs are dropped, once: they hold the launches without the rule."""
+        tokens; the captured graphs are dropped, once: they hold the launches without the rule.  takes: the first form that
+        names a take allocates the take buffer as well, at full capacity (FORM_SRC_MAX ints, 1 MiB) so that its address
+        stays fixed, and drops the graphs once more: they hold the launches without the buffer."""
+        if takes and self.form_src is None:
+            self._first_use_form()
+            self._form_src_host = np.zeros(FORM_SRC_MAX, dtype=np.int32)
+            self.form_src = torch.zeros(FORM_SRC_MAX, dtype=torch.int32, device=self.dev)
+            self.graph = self.graph_long = None
+            return
         if not self._alloc_rule(FORM):
             return
         self.form_state = torch.zeros(self.B, call("commu_form_state_ints"), dtype=torch.int32, device=self.dev)
@@ -2443,12 +2701,14 @@ class ForcedDecoder:
                  int(first), int(n), _s())
 
     def _form_args(self):
-        """The five form arguments of the stand-alone stages, in order."""
-        return _p(self.form_ctl), _p(self.form_table), FORM.rows_max, _p(self.form_state), _p(self.form_tok)
+        """The form arguments of the stand-alone stages, in order: five, and the take buffer's two where the decoder has
+        one (the _src entry points)."""
+        five = _p(self.form_ctl), _p(self.form_table), FORM.rows_max, _p(self.form_state), _p(self.form_tok)
+        return five if self.form_src is None else five + (_p(self.form_src), FORM_SRC_MAX)
 
     def pre(self):
         if self.form_ctl is not None:
-            call("commu_forcing_pre_form", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_tok), _p(self.chord_pos),
+            call("commu_forcing_pre_form" if self.form_src is None else "commu_forcing_pre_form_src", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_tok), _p(self.chord_pos),
                  self.ld_chord, _p(self.wrong), _p(self.utable), self.ld_u, self.generation_length, _p(self.tok),
                  _p(self.active), _p(self.keep), _p(self.draw), _p(self.uni), _p(self.trace), self.ld_trace,
                  _p(self._rows_args()[4]), *self._form_args(), self.B, _s())
@@ -2472,8 +2732,8 @@ class ForcedDecoder:
                         **({} if self.cls_ctl is None else {"class_ctl": self._cls_args()}),
                         **{r.kw: (w, getattr(self, r.table)) if r.rows_max else w for r, w in self._slot_words()})
         if self.form_ctl is not None:
-            call("commu_forcing_post_form", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_pos), self.ld_chord,
-                 _p(self.wrong), _p(self.draw), _p(self.token), None, _p(self.state.klen), _p(self.keep),
+            call("commu_forcing_post_form" if self.form_src is None else "commu_forcing_post_form_src", _p(self.fsm),
+                 _p(self.seq), self.ld_seq, _p(self.chord_pos), self.ld_chord, _p(self.wrong), _p(self.draw), _p(self.token), None, _p(self.state.klen), _p(self.keep),
                  self.state.klen_cap, _p(logp), _p(seq_logp), *self._form_args(), B, _s())
             return
         call("commu_forcing_post", _p(self.fsm), _p(self.seq), self.ld_seq, _p(self.chord_pos), self.ld_chord,
@@ -2497,6 +2757,8 @@ class ForcedDecoder:
         if self.form_ctl is not None:          # (the form kernels; a decoder that never had a form: the launch it always made)
             cons.update(form_ctl=_p(self.form_ctl), form_table=_p(self.form_table), form_rows=FORM.rows_max,
                         form_state=_p(self.form_state), form_tok=_p(self.form_tok))
+            if self.form_src is not None:      # (the take buffer, whole: its rows hold indices the decoder placed)
+                cons.update(form_src=_p(self.form_src), form_src_len=FORM_SRC_MAX)
         a = struct_args(
             DecodeLoopArgs, logits=_p(st.logits), ld=st.logits.stride(0), V=TOKEN_OFFSET.VOCAB_SIZE, B=self.B,
             wrong=_p(self.wrong), temperature=self.temperature, top_k=self.top_k, top_p=self.top_p, temperature_rows=_p(t_r),
@@ -3850,13 +4112,14 @@ class BatchedGenerator:
         dec.set_form(None)
         if FORM in used:
             dec._first_use_form()
-            dec._pack(FORM, vals[FORM], fresh=True)
+            dec._pack(FORM, vals[FORM], fresh=True, label="request")
         klen0_max = max([n_cond] + [p["klen0"] for p in replays if p is not None])
         dec.pool_open(n_cond, grid_rows=klen0_max)
         cls_samples = cls_table is not None and bool((np.nan_to_num(cls_table[..., 0], nan=0.0) != 0).any())
         sched = PoolSchedule([r.need for r in requests], [r.max_attempts for r in requests], B)
         stats = {"rejected": 0, "arms": [], "rearmed_other_request": 0, "admissions": 0, "kernel": dec.arm_kernel,
-                 "image_rows": dec.pool_image_rows(), "store_bytes": dec.pool_store_bytes(), "klen0_max": klen0_max}
+                 "image_rows": dec.pool_image_rows(), "store_bytes": dec.pool_store_bytes(), "klen0_max": klen0_max,
+                 "form_src_tokens": dec._form_src_used}         # (ints of the take buffer in use: shared takes count once)
         self.pool_stats = stats
         held = [None] * B                                # the request each slot decoded last
 

@@ -1076,6 +1076,12 @@ __device__ __forceinline__ void record_store(const int (&r)[F_COUNT], int* st, i
 //   ballot per chunk gives g, and chunk c is taken only while cursor + 64 c + 3 < end: the trip count is wave-uniform.  The
 //   token at g + k comes from the finding lane by v_readlane.  No LDS.  Lane 0 keeps the header in registers (FormRegs)
 //   through post and pre, as it keeps the record; bar_at is read and written in memory, by lane 0 only.
+//   A TAKE ROW (bit 7 of word 0 set: src | copy << 6 | 1 << 7 | (transpose + 64) << 8) replays a bar of a finished sequence
+//   the caller supplied: its source is form_src[begin .. end) (words 1 and 2: the first index behind the source bar's BAR and
+//   the index of the take's next BAR or end; src is kept for the checker, word 3 stays reserved) instead of a stretch of
+//   seq[b].  Such a bar is a replay bar whatever its index, bar 0 included; cursor = clamp(begin, 0, form_src_len), end =
+//   clamp(end, cursor, form_src_len); without a buffer, with form_src_len < 4 or with begin >= end the row is free.  The
+//   search reads form_src clamped to form_src_len - 1; everything behind the four tokens is the same code.
 //   NOT COVERED: replayed tokens are not checked against any constraint, as forced tokens are not; a replay bar cut by the
 //   iteration cap or ld_seq is not completed; bars past the 64th are free; a source note that the bar line cut does not
 //   appear (g + 3 < end).
@@ -1086,6 +1092,8 @@ struct Form {
     int* state;             // the sequence's row of form_state
     int* tok;               // form_tok + b: `pre` writes the replay token (-1: none) ...
     int tokv;               // ... and `post` gets the value the caller loaded
+    const int* src;         // (optional) the take buffer int32 [src_len]: the tokens of every take, one behind the other
+    int src_len;
 };
 struct FormRegs {
     int active, cursor, end, k, row, g;
@@ -1104,12 +1112,25 @@ __device__ __forceinline__ void form_bar(const Form& fm, FormRegs& f, int nb, in
     const int r = min(max((fm.ctl & (FORM_ROWS_MAX - 1)) + (on ? nb : 0), 0), fm.rows - 1);
     const unsigned w = fm.table[4 * (size_t)(on ? r : 0)];
     const int src = (int)(w & 63u);
-    const bool rep = on && ((w >> 8) & 127u) != 0u && src < nb;
+    const bool row = on && ((w >> 8) & 127u) != 0u;
+    // a TAKE row (bit 7): the source bar is form_src[begin .. end), words 1 and 2, whatever nb is; free without a buffer, with
+    // one too short for a group or with begin >= end.  Words 1 .. 3 of any other row are not read.
+    const bool take = row && (w & 128u) != 0u;
+    const int n = fm.src != nullptr ? fm.src_len : 0;
+    int tb = 0, te = 0;
+    if (take) {
+        tb = (int)fm.table[4 * (size_t)r + 1];
+        te = (int)fm.table[4 * (size_t)r + 2];
+    }
+    const bool tak = take && n >= 4 && tb < te;
+    const int tc = min(max(tb, 0), n);
+    const bool own = row && !take && src < nb;
+    const bool rep = own || tak;
     // (field by field, selects: an aggregate assignment behind the branch left two of the fields in scratch)
-    const int from = fm.state[FS_BAR_AT + (rep ? src : 0)], to = fm.state[FS_BAR_AT + (rep ? src + 1 : 0)];
+    const int from = fm.state[FS_BAR_AT + (own ? src : 0)], to = fm.state[FS_BAR_AT + (own ? src + 1 : 0)];
     f.active = rep ? 1 : 0;
-    f.cursor = rep ? from + 1 : 0;
-    f.end = rep ? (src + 1 == nb ? index : to) : 0;
+    f.cursor = own ? from + 1 : (tak ? tc : 0);
+    f.end = own ? (src + 1 == nb ? index : to) : (tak ? min(max(te, tc), n) : 0);
     f.k = 0;
     f.row = rep ? (int)(w & 0x7fffu) : 0;
     f.g = -1;
@@ -1120,7 +1141,7 @@ __device__ __forceinline__ bool form_is_group(int t0, int t1, int t2, int t3) {
            ((unsigned)(t3 - TOK_DUR_LO) <= (unsigned)(TOK_DUR_HI - TOK_DUR_LO));
 }
 // (the wave) the smallest g >= cursor with g + 3 < end whose four tokens are a note group, -1: none; tk: seq[g + k].
-// cursor, end and k are wave-uniform.
+// cursor, end and k are wave-uniform; so are sq and ld_seq, which are the take buffer and its length inside a take's bar.
 __device__ __forceinline__ int form_search(const int* __restrict__ sq, int ld_seq, int cursor, int end, int k, int lane, int& tk) {
     int g = -1;
     tk = -1;
@@ -1170,9 +1191,12 @@ __device__ __forceinline__ void forcing_pre_body(int b, int lane, int (&s)[F_COU
         // the search runs ahead of the decision, for a slot inside a replay bar that has no token to feed: what it reads
         // (cursor, end, k) changes in this stage only where nothing is drawn afterwards
         const bool look = fr->active != 0 && s[F_FORCED] < 0 && !s[F_DONE];
-        if (__builtin_amdgcn_readfirstlane((int)look))
-            fg = form_search(sq, ld_seq, __builtin_amdgcn_readfirstlane(fr->cursor), __builtin_amdgcn_readfirstlane(fr->end),
-                             __builtin_amdgcn_readfirstlane(fr->k), lane, ftk);
+        if (__builtin_amdgcn_readfirstlane((int)look)) {
+            // (the open bar's row says where its source lies: lane 0's word, so pointer, bound and trip count stay uniform)
+            const bool take = (__builtin_amdgcn_readfirstlane(fr->row) & 128) != 0 && fm.src != nullptr && fm.src_len >= 1;
+            fg = form_search(take ? fm.src : sq, take ? fm.src_len : ld_seq, __builtin_amdgcn_readfirstlane(fr->cursor),
+                             __builtin_amdgcn_readfirstlane(fr->end), __builtin_amdgcn_readfirstlane(fr->k), lane, ftk);
+        }
     }
     if (lane == 0) {
         int act = 0, kp = 0, dr = 0;

@@ -51,7 +51,7 @@ __global__ __launch_bounds__(64) void forcing_pre_form_kernel(int* st, int* seq,
                                                               unsigned char* keep, unsigned char* draw, float* uni,
                                                               int* trace, int ld_trace, float* seq_logp, const int* form_ctl,
                                                               const unsigned* form_table, int form_rows, int* form_state,
-                                                              int* form_tok) {
+                                                              int* form_tok, const int* form_src, int form_src_len) {
     const int b = blockIdx.x;
     int rec[F_COUNT] = {};
     FormRegs fr{0, 0, 0, 0, 0, -1};
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(64) void forcing_pre_form_kernel(int* st, int* seq,
     }
     forcing_pre_body<true>(b, threadIdx.x, rec, seq, ld_seq, chord_tok, chord_pos, ld_chord, wrong, utable, ld_u, max_iters,
                            tok, active, keep, draw, uni, trace, ld_trace, seq_logp,
-                           Form{form_ctl[b], form_table, form_rows, fs, form_tok + b, -1}, &fr);
+                           Form{form_ctl[b], form_table, form_rows, fs, form_tok + b, -1, form_src, form_src_len}, &fr);
     if (threadIdx.x == 0) {
         record_store(rec, st, b);
         form_regs_store(fr, fs);
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(64) void forcing_post_form_kernel(int* st, int* seq
                                                                const unsigned char* keep, int lmax, const float* logp,
                                                                float* seq_logp, const int* form_ctl,
                                                                const unsigned* form_table, int form_rows, int* form_state,
-                                                               int* form_tok) {
+                                                               int* form_tok, const int* form_src, int form_src_len) {
     const int b = blockIdx.x;
     int rec[F_COUNT] = {};
     FormRegs fr{0, 0, 0, 0, 0, -1};
@@ -86,7 +86,8 @@ __global__ __launch_bounds__(64) void forcing_post_form_kernel(int* st, int* seq
     }
     forcing_post_body<true>(b, threadIdx.x, rec, seq, ld_seq, chord_pos, ld_chord, wrong, draw, token, live, klen, keep, lmax,
                             -3, TokenLogp{NAN, NAN}, logp, seq_logp, nullptr,
-                            Form{form_ctl[b], form_table, form_rows, fs, form_tok + b, form_tok[b]}, &fr);
+                            Form{form_ctl[b], form_table, form_rows, fs, form_tok + b, form_tok[b], form_src, form_src_len},
+                            &fr);
     if (threadIdx.x == 0) {
         record_store(rec, st, b);
         form_regs_store(fr, fs);
@@ -187,7 +188,7 @@ struct LoopArgs<T_ART> : LoopArgs<T_GDE> {
     int art_rows;
 };
 // the form rule (decode_loop.h: Form) is a switch of its own beside the tier: the kernel with it takes the block of its tier
-// plus these five, the kernel without it the block it always took
+// plus these seven (the take buffer is optional: null, 0), the kernel without it the block it always took
 template <int TIER>
 struct LoopArgsForm : LoopArgs<TIER> {
     const int* form_ctl;
@@ -195,6 +196,8 @@ struct LoopArgsForm : LoopArgs<TIER> {
     int form_rows;
     int* form_state;
     int* form_tok;
+    const int* form_src;
+    int form_src_len;
 };
 template <bool BIAS, int TIER, bool FORM = false>
 __global__ __launch_bounds__(64) void sample_post_pre_kernel(std::conditional_t<FORM, LoopArgsForm<TIER>, LoopArgs<TIER>> a) {
@@ -213,7 +216,7 @@ __global__ __launch_bounds__(64) void sample_post_pre_kernel(std::conditional_t<
     if constexpr (FORM) {
         int* fs = a.form_state + (size_t)b * FS_COUNT;
         form_regs_load(fr, fs);
-        fm = Form{a.form_ctl[b], a.form_table, a.form_rows, fs, a.form_tok + b, a.form_tok[b]};
+        fm = Form{a.form_ctl[b], a.form_table, a.form_rows, fs, a.form_tok + b, a.form_tok[b], a.form_src, a.form_src_len};
     }
     Grammar g{nullptr, 0, nullptr, 0, 0, 0};
     if constexpr (TIER >= T_GRAM) {
@@ -391,6 +394,27 @@ static bool form_args_ok(const int* form_ctl, const unsigned* form_table, int fo
     return form_ctl != nullptr && form_table != nullptr && form_state != nullptr && form_tok != nullptr && form_rows >= 1 &&
            form_rows <= FORM_ROWS_MAX;
 }
+// (the take buffer is optional; given, it holds at least one token)
+static bool form_src_ok(const int* form_src, int form_src_len) { return form_src == nullptr || form_src_len >= 1; }
+constexpr int FORM_SRC_MAX = 1 << 18;      // ints the decoder's take buffer holds: 64 takes of 4096 tokens
+
+extern "C" int commu_form_src_max(void) { return FORM_SRC_MAX; }
+
+extern "C" int commu_forcing_pre_form_src(int* state, int* seq, int ld_seq, const int* chord_tok, const int* chord_pos,
+                                          int ld_chord, unsigned char* wrong, const float* utable, int ld_u, int max_iters,
+                                          long long* tok, unsigned char* active, unsigned char* keep, unsigned char* draw,
+                                          float* uni, int* trace, int ld_trace, float* seq_logp, const int* form_ctl,
+                                          const unsigned* form_table, int form_rows, int* form_state, int* form_tok,
+                                          const int* form_src, int form_src_len, int B, hipStream_t stream) {
+    if (B <= 0) return 0;
+    if (ld_seq < 2 || ld_chord < 1 || ld_u < 1) return -22;
+    if (!form_args_ok(form_ctl, form_table, form_rows, form_state, form_tok) || !form_src_ok(form_src, form_src_len)) return -22;
+    COMMU_LAUNCH(forcing_pre_form_kernel, dim3(B), dim3(64), 0, stream, state, seq, ld_seq, chord_tok, chord_pos, ld_chord,
+                 wrong, utable, ld_u, max_iters, tok, active, keep, draw, uni, trace, ld_trace, seq_logp, form_ctl, form_table,
+                 form_rows, form_state, form_tok, form_src, form_src_len);
+    COMMU_LAUNCH_CHECK();
+    return 0;
+}
 
 extern "C" int commu_forcing_pre_form(int* state, int* seq, int ld_seq, const int* chord_tok, const int* chord_pos,
                                       int ld_chord, unsigned char* wrong, const float* utable, int ld_u, int max_iters,
@@ -398,12 +422,23 @@ extern "C" int commu_forcing_pre_form(int* state, int* seq, int ld_seq, const in
                                       float* uni, int* trace, int ld_trace, float* seq_logp, const int* form_ctl,
                                       const unsigned* form_table, int form_rows, int* form_state, int* form_tok, int B,
                                       hipStream_t stream) {
+    return commu_forcing_pre_form_src(state, seq, ld_seq, chord_tok, chord_pos, ld_chord, wrong, utable, ld_u, max_iters, tok,
+                                      active, keep, draw, uni, trace, ld_trace, seq_logp, form_ctl, form_table, form_rows,
+                                      form_state, form_tok, nullptr, 0, B, stream);
+}
+
+extern "C" int commu_forcing_post_form_src(int* state, int* seq, int ld_seq, const int* chord_pos, int ld_chord,
+                                           unsigned char* wrong, const unsigned char* draw, const int* token, int* live,
+                                           int* klen, const unsigned char* keep, int lmax, const float* logp,
+                                           float* seq_logp, const int* form_ctl, const unsigned* form_table, int form_rows,
+                                           int* form_state, int* form_tok, const int* form_src, int form_src_len, int B,
+                                           hipStream_t stream) {
     if (B <= 0) return 0;
-    if (ld_seq < 2 || ld_chord < 1 || ld_u < 1) return -22;
-    if (!form_args_ok(form_ctl, form_table, form_rows, form_state, form_tok)) return -22;
-    COMMU_LAUNCH(forcing_pre_form_kernel, dim3(B), dim3(64), 0, stream, state, seq, ld_seq, chord_tok, chord_pos, ld_chord,
-                 wrong, utable, ld_u, max_iters, tok, active, keep, draw, uni, trace, ld_trace, seq_logp, form_ctl, form_table,
-                 form_rows, form_state, form_tok);
+    if (ld_seq < 2 || ld_chord < 1) return -22;
+    if (!form_args_ok(form_ctl, form_table, form_rows, form_state, form_tok) || !form_src_ok(form_src, form_src_len)) return -22;
+    COMMU_LAUNCH(forcing_post_form_kernel, dim3(B), dim3(64), 0, stream, state, seq, ld_seq, chord_pos, ld_chord, wrong,
+                 draw, token, live, klen, keep, lmax, logp, seq_logp, form_ctl, form_table, form_rows, form_state, form_tok,
+                 form_src, form_src_len);
     COMMU_LAUNCH_CHECK();
     return 0;
 }
@@ -413,13 +448,9 @@ extern "C" int commu_forcing_post_form(int* state, int* seq, int ld_seq, const i
                                        int* klen, const unsigned char* keep, int lmax, const float* logp, float* seq_logp,
                                        const int* form_ctl, const unsigned* form_table, int form_rows, int* form_state,
                                        int* form_tok, int B, hipStream_t stream) {
-    if (B <= 0) return 0;
-    if (ld_seq < 2 || ld_chord < 1) return -22;
-    if (!form_args_ok(form_ctl, form_table, form_rows, form_state, form_tok)) return -22;
-    COMMU_LAUNCH(forcing_post_form_kernel, dim3(B), dim3(64), 0, stream, state, seq, ld_seq, chord_pos, ld_chord, wrong,
-                 draw, token, live, klen, keep, lmax, logp, seq_logp, form_ctl, form_table, form_rows, form_state, form_tok);
-    COMMU_LAUNCH_CHECK();
-    return 0;
+    return commu_forcing_post_form_src(state, seq, ld_seq, chord_pos, ld_chord, wrong, draw, token, live, klen, keep, lmax,
+                                       logp, seq_logp, form_ctl, form_table, form_rows, form_state, form_tok, nullptr, 0, B,
+                                       stream);
 }
 
 extern "C" int commu_form_reset(int* form_state, int* form_tok, const int* state, const int* seq, int ld_seq, int first,
@@ -483,6 +514,8 @@ extern "C" int commu_decode_sample_post_pre(const commu_decode_loop_args* p, hip
     // (the form rule: every one of its arrays or none)
     if (p->form_ctl != nullptr && !form_args_ok(p->form_ctl, p->form_table, p->form_rows, p->form_state, p->form_tok))
         return -22;
+    // (the take buffer: optional, never without the rule, never empty)
+    if (p->form_src != nullptr && (p->form_ctl == nullptr || p->form_src_len < 1)) return -22;
     LoopArgsForm<T_ART> a;
     static_cast<LoopArgs<T_NONE>&>(a) = LoopArgs<T_NONE>{
         p->logits, p->ld, V, p->wrong, p->temperature, p->top_k, p->top_p,
@@ -501,6 +534,7 @@ extern "C" int commu_decode_sample_post_pre(const commu_decode_loop_args* p, hip
     a.art_ctl = p->art_ctl; a.art_table = p->art_table; a.art_rows = p->art_rows;
     a.form_ctl = p->form_ctl; a.form_table = p->form_table; a.form_rows = p->form_rows;
     a.form_state = p->form_state; a.form_tok = p->form_tok;
+    a.form_src = p->form_src; a.form_src_len = p->form_src_len;
     const dim3 grid(p->B), block(64);
     // one kernel per tier, each with the argument block of its own tier (by value), so that a launch below a tier is the one
     // it always was: no added load, no added register, no added argument.  Below the harmony tier a bias is optional and
@@ -508,11 +542,12 @@ extern "C" int commu_decode_sample_post_pre(const commu_decode_loop_args* p, hip
     with_tier(tier_of(*p), [&](auto t) {
         constexpr int T = decltype(t)::value;
         const auto& at = static_cast<const LoopArgs<T>&>(a);      // (each kernel gets the block of its own tier)
-        if (p->form_ctl != nullptr) {                             // (the form kernels: that block and the form's five)
+        if (p->form_ctl != nullptr) {                             // (the form kernels: that block and the form's seven)
             LoopArgsForm<T> af;
             static_cast<LoopArgs<T>&>(af) = at;
             af.form_ctl = a.form_ctl; af.form_table = a.form_table; af.form_rows = a.form_rows;
             af.form_state = a.form_state; af.form_tok = a.form_tok;
+            af.form_src = a.form_src; af.form_src_len = a.form_src_len;
             if constexpr (T < T_HARM) {
                 if (p->bias == nullptr) {
                     COMMU_LAUNCH((sample_post_pre_kernel<false, T, true>), grid, block, 0, stream, af);

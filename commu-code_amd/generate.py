@@ -206,8 +206,11 @@ def parse_args():
     # does not carry a "form" of its own.
     model_arg_parser.add_argument("--form", default=None, metavar="SPEC",
                                   help='a bar replays an earlier bar of its own sequence: letters (AABA), JSON text or file, '
-                                       '{"bars": [null | j | {"of": j, "copy": "all" | "rhythm", "transpose": s}, ...]}.  '
-                                       'Not covered: constraints on replayed tokens, bars past the 64th, a bar cut by '
+                                       '{"bars": [null | j | {"of": j, "copy": "all" | "rhythm", "transpose": s}, ...]}; or a '
+                                       'bar of a finished sequence you have: {"keep": {"from_tokens": [ids]}, "redo": [bars], '
+                                       '"repitch": [bars]} or {"takes": [[ids], ...], "bars": [... {"take": t, "of": j}]}.  '
+                                       'Not covered: a redone bar knows only the bars before it, constraints on replayed '
+                                       'tokens, bars past the 64th, a bar cut by '
                                        '--generation_length')
     # not in the reference (which decodes one sequence at a time): how many attempts are decoded side by side.  1 .. 256;
     # up to 256 slots run the fused layer-tail launches ("Supported shapes").  The sequences returned do
@@ -445,9 +448,11 @@ def check_requests(model_args, input_args):
 
 def form_doc(doc, what="--form", grammar=True):
     """A form given as a letter string or a JSON value, validated and returned written out: {"bars": [null | {"of": j,
-    "copy": "all" | "rhythm", "transpose": s}, ...]}.  Host code only, ValueError that says what is wrong -- a rhythm bar
-    without --grammar among it."""
-    from commu_amd.generate import CommuHipError, form_is_rhythm, form_row_fields, form_template
+    "copy": "all" | "rhythm", "transpose": s}, ...]}.  A form that names takes -- {"takes": ..., "bars": ...} or the short
+    form {"keep": ..., "redo": [...], "repitch": [...]} -- is written out in the full form {"takes": [[ids], ...], "bars":
+    [...]}, so that whoever gets the document gets the tokens.  Host code only, ValueError that says what is wrong -- a
+    rhythm bar without --grammar among it."""
+    from commu_amd.generate import CommuHipError, form_document, form_is_rhythm, form_row_fields, form_template
     try:
         rows = form_template(doc)
     except CommuHipError as e:
@@ -455,6 +460,8 @@ def form_doc(doc, what="--form", grammar=True):
     if form_is_rhythm(rows) and not grammar:
         raise ValueError(f'{what}: "copy": "rhythm" without --grammar: the pitches of such a bar are drawn, and only the '
                          "grammar makes that draw a pitch")
+    if getattr(rows, "takes", ()):
+        return form_document(rows)
     bars = []
     for w in rows[:, 0].tolist():
         f = form_row_fields(w)

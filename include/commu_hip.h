@@ -885,8 +885,38 @@ int commu_forcing_post(int* state, int* seq, int ld_seq, const int* chord_pos, i
  * commu_forcing_pre_form / commu_forcing_post_form: commu_forcing_pre / commu_forcing_post (same leading arguments, same
  * refusals) with the rule; -22 for a null form_ctl, form_table, form_state or form_tok and for form_rows outside 1 .. 4096.
  * In commu_decode_loop_args a null form_ctl launches the kernels that never heard of the rule; a form_ctl without table,
- * state or form_tok, or with form_rows outside 1 .. 4096, is refused with -22. */
+ * state or form_tok, or with form_rows outside 1 .. 4096, is refused with -22.
+ * TAKES: a bar may also replay a bar of a finished sequence the caller supplies.  form_src: const int32 [form_src_len], the
+ *   tokens of every take the caller knows, one behind the other.  A row with bit 7 of word 0 set is a TAKE ROW: word 0 is
+ *   src | copy << 6 | 1 << 7 | (transpose + 64) << 8 (src: the take's bar, kept for the checker, not used by the kernels),
+ *   word 1 `begin`, the index in form_src of the first token behind the source bar's BAR, word 2 `end` (exclusive), the index
+ *   of the take's next BAR or of the take's end; word 3 stays reserved and is never read.  Rows without bit 7 mean what they
+ *   always meant and their words 1 .. 3 are still never read.  When a BAR opens a take row's bar it is a replay bar whatever
+ *   its index (bar 0 included: src < i belongs to own-past rows) with cursor = clamp(begin, 0, form_src_len), end =
+ *   clamp(end, cursor, form_src_len); the search and the replay token read form_src (indices clamped to form_src_len - 1)
+ *   instead of seq, and nothing else differs: k, g, cursor = g + 4, the chord hand-over, rhythm mode, the transposition.
+ *   A take row is FREE where form_src is null, form_src_len < 4 or begin >= end -- so through commu_forcing_pre_form /
+ *   commu_forcing_post_form, which pass no buffer, every take row is free.
+ *   commu_forcing_pre_form_src / commu_forcing_post_form_src: the two stages with the buffer (post opens bars too); a null
+ *   form_src is legal, a form_src with form_src_len < 1 is refused with -22.  In commu_decode_loop_args form_src with
+ *   form_src_len < 1, or without form_ctl, is refused with -22 before anything is launched.  The arm launches do not know the
+ *   buffer: they reset the slot's state, and a take's tokens are the caller's to place before the rows that name them.
+ *   commu_form_src_max(): the ints the decoder's buffer holds, 1 << 18 (64 takes of 4096 tokens).
+ *   Not covered, beside the above: a take made under another chord progression still gets this sequence's chords (chord
+ *   tokens are never copied); generation is left to right, so a bar drawn between kept bars knows only those before it. */
 int commu_form_state_ints(void);
+int commu_form_src_max(void);
+int commu_forcing_pre_form_src(int* state, int* seq, int ld_seq, const int* chord_tok, const int* chord_pos, int ld_chord,
+                               unsigned char* wrong, const float* utable, int ld_u, int max_iters, long long* tok,
+                               unsigned char* active, unsigned char* keep, unsigned char* draw, float* uni, int* trace,
+                               int ld_trace, float* seq_logp, const int* form_ctl, const unsigned* form_table, int form_rows,
+                               int* form_state, int* form_tok, const int* form_src, int form_src_len, int B,
+                               hipStream_t stream);
+int commu_forcing_post_form_src(int* state, int* seq, int ld_seq, const int* chord_pos, int ld_chord, unsigned char* wrong,
+                                const unsigned char* draw, const int* token, int* live, int* klen,
+                                const unsigned char* keep, int lmax, const float* logp, float* seq_logp, const int* form_ctl,
+                                const unsigned* form_table, int form_rows, int* form_state, int* form_tok,
+                                const int* form_src, int form_src_len, int B, hipStream_t stream);
 int commu_forcing_pre_form(int* state, int* seq, int ld_seq, const int* chord_tok, const int* chord_pos, int ld_chord,
                            unsigned char* wrong, const float* utable, int ld_u, int max_iters, long long* tok,
                            unsigned char* active, unsigned char* keep, unsigned char* draw, float* uni, int* trace,
@@ -969,6 +999,9 @@ typedef struct commu_decode_loop_args {
     const float* harm;
     const unsigned char* harm_on;
     int ld_bias, ld_gram, ld_harm;
+    /* the form's take buffer (below: FORM, take rows; optional; likewise ahead of form_ctl) */
+    const int* form_src;
+    int form_src_len;
     /* form templates (below: FORM; likewise ahead of art_ctl) */
     const int* form_ctl;
     const unsigned* form_table;
