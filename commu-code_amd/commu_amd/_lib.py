@@ -185,6 +185,10 @@ PROTOTYPES = {
     "commu_adam_step": [c_p, c_p, c_p, c_p, c_p, c_z, c_f, c_f, c_f, c_f, c_i, c_p, c_f, c_p],
     "commu_adam_step_dev": [c_p, c_p, c_p, c_p, c_p, c_z, c_p, c_f, c_f, c_f, c_p, c_f, c_p],
     "commu_adam_bias_corrections": [c_f, c_f, c_i, c_p],
+    "commu_adam_step_groups": [c_p, c_p, c_p, c_p, c_p, c_z, c_p, c_i, c_p, c_p, C.c_uint, c_i, c_f, c_f, c_f, c_i, c_p,
+                               c_f, c_p],
+    "commu_adam_step_groups_dev": [c_p, c_p, c_p, c_p, c_p, c_z, c_p, c_p, c_i, c_f, c_f, c_f, c_p, c_f, c_p],
+    "commu_grad_norm_groups": [c_p, c_z, c_p, C.c_uint, c_p, c_i, c_p, c_p],
     "commu_set_seed_salt": [c_p, c_p],
     "commu_scale_clip_f32": [c_p, c_z, c_p, c_f, c_p],
     "commu_cast_f32_bf16": [c_p, c_p, c_z, c_p],

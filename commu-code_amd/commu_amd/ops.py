@@ -632,6 +632,53 @@ def adam_bias_corrections(beta1, beta2, step):
     return float(out[0]), float(out[1])
 
 
+OPTIM_MAX_GROUPS = 16          # COMMU_OPTIM_MAX_GROUPS
+
+
+def _group_args(lrs, wds, frozen):
+    k = len(lrs)
+    if not (1 <= k <= OPTIM_MAX_GROUPS and len(wds) == k and len(frozen) == k):
+        raise CommuHipError(f"1 .. {OPTIM_MAX_GROUPS} optimiser groups, got {k}")
+    mask = sum(1 << i for i, f in enumerate(frozen) if f)
+    return (C.c_float * k)(*[float(x) for x in lrs]), (C.c_float * k)(*[float(x) for x in wds]), mask
+
+
+def adam_step_groups(p, g, m, v, p_bf16, block_group, lrs, wds, frozen, step, decoupled=False, gnorm=None, clip=0.0,
+                     beta1=0.9, beta2=0.999, eps=1e-8):
+    """adam_step over WHOLE flat buffers (every tensor at a multiple of 64 elements) with per-group lr / weight decay /
+    frozen flag; block_group: uint8 device tensor, one group number per 64-element block.  decoupled: AdamW's decay."""
+    assert block_group.dtype == torch.uint8 and block_group.numel() * 64 == p.numel()
+    lr_a, wd_a, mask = _group_args(lrs, wds, frozen)
+    call("commu_adam_step_groups", _p(p), _p(g), _p(m), _p(v), _p(p_bf16), p.numel(), _p(block_group), len(lrs), lr_a, wd_a,
+         mask, int(bool(decoupled)), beta1, beta2, eps, step, _p(gnorm), clip, _s())
+
+
+def group_table(lrs, wds, frozen, bc1, bc2):
+    """The 2 + 3 * 16 floats commu_adam_step_groups_dev reads (host tensor): entries past the groups in use are frozen."""
+    _group_args(lrs, wds, frozen)
+    k, G = len(lrs), OPTIM_MAX_GROUPS
+    pad = [0.0] * (G - k)
+    return torch.tensor([bc1, bc2] + [float(x) for x in lrs] + pad + [float(x) for x in wds] + pad
+                        + [1.0 if f else 0.0 for f in frozen] + [1.0] * (G - k), dtype=F32)
+
+
+def adam_step_groups_dev(p, g, m, v, p_bf16, block_group, table, decoupled=False, gnorm=None, clip=0.0, beta1=0.9, beta2=0.999,
+                         eps=1e-8):
+    """adam_step_groups with the bias corrections and the group table read from the device tensor `table` (group_table)."""
+    assert block_group.dtype == torch.uint8 and block_group.numel() * 64 == p.numel()
+    assert table.dtype == F32 and table.numel() >= 2 + 3 * OPTIM_MAX_GROUPS
+    call("commu_adam_step_groups_dev", _p(p), _p(g), _p(m), _p(v), _p(p_bf16), p.numel(), _p(block_group), _p(table),
+         int(bool(decoupled)), beta1, beta2, eps, _p(gnorm), clip, _s())
+
+
+def grad_norm_groups(g, block_group, frozen, part, out):
+    """grad_norm over the blocks whose group is not frozen (the frozen ones are not read)."""
+    assert block_group.dtype == torch.uint8 and block_group.numel() * 64 == g.numel()
+    mask = sum(1 << i for i, f in enumerate(frozen) if f)
+    call("commu_grad_norm_groups", _p(g), g.numel(), _p(block_group), mask, _p(part), part.numel(), _p(out), _s())
+    return out
+
+
 def set_seed_salt(src):
     """Every dropout site adds the uint32 at device tensor `src` (int32 [1]) to its seed from now on (None: back to 0)."""
     call("commu_set_seed_salt", _p(src), _s())

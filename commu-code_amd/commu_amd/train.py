@@ -64,8 +64,11 @@ class Trainer:
 
     MERGE_MAX_ROWS = 65536          # tokens (T x B) up to which the micro-batches of a step are run as ONE pass
 
-    def __init__(self, model, cfg, num_gpus=1, reducer=None, pad_id=0, graph=False, merge_chunks=None, settle_heap=False):
-        """merge_chunks: the reference splits a batch into `batch_chunk` micro-batches to fit its GPU's memory
+    def __init__(self, model, cfg, num_gpus=1, reducer=None, pad_id=0, graph=False, merge_chunks=None, settle_heap=False,
+                 param_groups=None, decoupled=False):
+        """param_groups / decoupled (not in the reference): FusedAdam's `groups` and AdamW's form of
+        cfg.TRAIN.weight_decay; every group's lr is its multiplier times cfg.TRAIN.lr / num_gpus.
+        merge_chunks: the reference splits a batch into `batch_chunk` micro-batches to fit its GPU's memory
         (train.py:113-155); each contributes mean(loss over ITS non-pad targets) / batch_chunk.  With 288 GB of HBM the
         columns of all micro-batches go through ONE forward / backward whose loss weights every token by
         1 / (batch_chunk x non-pad count of its micro-batch) -- the same loss and gradients (tested), 1.5x the throughput
@@ -93,7 +96,8 @@ class Trainer:
         # dropout salt of a replayed step (the seed arguments are frozen in the graph): torch's CPU generator, no device sync
         self.salt_source = lambda: int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
         local_lr = cfg.TRAIN.lr / num_gpus                                  # train.py:441
-        self.optimizer = FusedAdam(model, lr=local_lr, weight_decay=cfg.TRAIN.weight_decay)
+        self.optimizer = FusedAdam(model, lr=local_lr, weight_decay=cfg.TRAIN.weight_decay, decoupled=decoupled,
+                                   groups=param_groups)
         self.scheduler = torch.optim.lr_scheduler.LambdaLR(
             self.optimizer, lr_lambda=lr_lambda_factory(cfg.TRAIN.warmup_step, cfg.TRAIN.lr, cfg.TRAIN.lr_min))
         self.train_step = 0
@@ -250,9 +254,12 @@ class Trainer:
         cfg, model = self.cfg, self.model
         dev = data.device
         fl = model._ensure_flat()
+        if self.optimizer.kernel_name() != "commu_adam_step":
+            self.optimizer._block_map(fl)                     # (a resumed run captures before any eager step built it)
         st = {"data": data.clone(), "target": target.clone(), "reset": reset_mems.clone(),
               "salt": torch.zeros(1, device=dev, dtype=torch.int32),
               "scal": torch.zeros(4, device=dev, dtype=torch.float32),
+              "table": self.optimizer.group_table(1.0, 1.0).to(dev),          # the grouped step's form of `scal`
               "mems": [None if m is None else m.detach().clone() for m in self.mems]}
         cur = torch.cuda.current_stream(dev)
         if fl.get("shadow_ready") is not None:                # recorded by the last eager optimiser step: join it here,
@@ -271,7 +278,7 @@ class Trainer:
             for s_ in nll_sums:
                 self.log_train_loss += s_[0]
             ops.set_seed_salt(None)
-        self.optimizer.dev_scalars = st["scal"]
+        self.optimizer.dev_scalars, self.optimizer.dev_table = st["scal"], st["table"]
         try:
             with torch.cuda.graph(g_opt, pool=pool, capture_error_mode="thread_local"):
                 gn = clip_grad_norm_(model, cfg.TRAIN.clip, self.optimizer)
@@ -282,7 +289,7 @@ class Trainer:
                     model._flat["shadow_ready"] = None
                 self.log_grad_norm += gn
         finally:
-            self.optimizer.dev_scalars = None
+            self.optimizer.dev_scalars, self.optimizer.dev_table = None, None
         st["total"] = total
         self._graphs, self._graph_state = (g_fb, g_opt), st
         self._graph_key = (tuple(data.shape), data.device, cfg.TRAIN.batch_chunk, bool(model.training), float(model.drop.p))
@@ -328,7 +335,10 @@ class Trainer:
         grp = opt.param_groups[0]
         opt.step_count += 1
         bc1, bc2 = ops.adam_bias_corrections(grp["betas"][0], grp["betas"][1], opt.step_count)
-        st["scal"].copy_(torch.tensor([float(grp["lr"]), bc1, bc2, 0.0], dtype=torch.float32), non_blocking=True)
+        if opt.kernel_name() == "commu_adam_step":
+            st["scal"].copy_(torch.tensor([float(grp["lr"]), bc1, bc2, 0.0], dtype=torch.float32), non_blocking=True)
+        else:                                                 # every group's lr of this step, beside the bias corrections
+            st["table"].copy_(opt.group_table(bc1, bc2), non_blocking=True)
         self._graphs[0].replay()
         if self.reducer is not None:
             self.reducer.allreduce_mean(model)

@@ -12,7 +12,9 @@ gradient all-reduce per optimiser step overlapped with backward), the logging wi
 evaluation every `eval_interval` steps with the same_length / long-memory setting (C6) and checkpoint_last /
 checkpoint_best written by rank 0 between barriers (C7).  The reference's hyper-parameters are hard-coded defaults
 (config_helper.py:4-49); the extra flags below only exist so that small runs and the benchmark shapes can be driven
-from the same entry point.
+from the same entry point.  Fine-tuning flags (not in the reference either): --init_checkpoint / --resume, --lr,
+--warmup_step, --weight_decay, --adamw and --param_groups (per-tensor lr multiplier / weight decay / frozen, see
+commu_amd.optim.resolve_groups); what can be refused without a dataset or a model is refused first (check_fine_tune_args).
 """
 import argparse
 import math
@@ -49,21 +51,66 @@ def parse_args(argv=None):
     for name in ("num_layers", "num_heads", "units", "inner_size", "tgt_length", "mem_length", "batch_size",
                  "batch_chunk"):
         p.add_argument("--" + name, type=int, default=None)
+    # -- not in the reference: fine-tuning (start from a checkpoint, weight decay, per-tensor optimiser groups)
+    p.add_argument("--init_checkpoint", type=str, default=None, metavar="FILE",
+                   help="(not in the reference) start from the MODEL WEIGHTS of a checkpoint (strict=False, as the "
+                        "generation loader reads it); the optimiser is fresh and the step starts at 0")
+    p.add_argument("--resume", type=str, default=None, metavar="FILE",
+                   help="(not in the reference) continue a run: model, optimiser, scheduler, train_step and best_val_loss of "
+                        "a checkpoint.  The batch stream is not part of a checkpoint: the resumed run draws its shuffle from "
+                        "seed + 1000 * rank + train_step")
+    p.add_argument("--lr", type=float, default=None, help="(not in the reference) overrides TRAIN.lr")
+    p.add_argument("--warmup_step", type=int, default=None, help="(not in the reference) overrides TRAIN.warmup_step")
+    p.add_argument("--weight_decay", type=float, default=None,
+                   help="(not in the reference) overrides TRAIN.weight_decay (torch.optim.Adam's coupled decay)")
+    p.add_argument("--adamw", action="store_true",
+                   help="(not in the reference) decoupled weight decay as in torch.optim.AdamW")
+    p.add_argument("--param_groups", type=str, default=None, metavar="SPEC",
+                   help="(not in the reference) JSON text or a JSON file: a list of {\"match\": glob or list of globs over the "
+                        "state-dict names, \"lr_mult\": 1, \"weight_decay\": the default, \"frozen\": false}; the first "
+                        "match wins, unmatched tensors keep the defaults")
     return p.parse_args(argv)
+
+
+def check_fine_tune_args(args):
+    """The refusals that need neither a dataset nor a model; returns the parsed --param_groups (or None)."""
+    from commu_amd.optim import GroupSpecError, load_group_spec
+    if args.init_checkpoint is not None and args.resume is not None:
+        raise ValueError("--init_checkpoint and --resume exclude each other: the first starts a new run from a "
+                         "checkpoint's weights, the second continues the checkpoint's own run")
+    for flag in ("init_checkpoint", "resume"):
+        path = getattr(args, flag)
+        if path is not None and not os.path.isfile(path):
+            raise ValueError(f"--{flag}: no such file: {path}")
+    for flag in ("lr", "weight_decay"):
+        x = getattr(args, flag)
+        if x is not None and not (0.0 <= x < float("inf")):
+            raise ValueError(f"--{flag} {x} must be a finite number >= 0")
+    if args.param_groups is None:
+        return None
+    try:
+        return load_group_spec(args.param_groups)
+    except GroupSpecError as exc:
+        raise ValueError(f"--param_groups: {exc}") from None
 
 
 def main(argv=None):
     from commu_amd.ddp import GradReducer
     from commu_amd.model.config_helper import get_default_cfg_training
     from commu_amd.model.dataset import ComMUDataset
-    from commu_amd.train import Trainer, build_model, evaluate_best_checkpoint, save_checkpoint
+    from commu_amd.train import (Trainer, build_model, evaluate_best_checkpoint, load_checkpoint, read_checkpoint,
+                                 save_checkpoint)
     args = parse_args(argv)
+    group_spec = check_fine_tune_args(args)
     cfg = get_default_cfg_training()
     cfg.defrost()
     for name in ("num_layers", "num_heads", "units", "inner_size"):
         if getattr(args, name) is not None:
             cfg.MODEL[name] = getattr(args, name)
     for name in ("tgt_length", "mem_length", "batch_size", "batch_chunk", "max_step", "log_interval", "eval_interval"):
+        if getattr(args, name) is not None:
+            cfg.TRAIN[name] = getattr(args, name)
+    for name in ("lr", "warmup_step", "weight_decay"):
         if getattr(args, name) is not None:
             cfg.TRAIN[name] = getattr(args, name)
     cfg.freeze()
@@ -106,16 +153,34 @@ def main(argv=None):
                                       local_rank=rank, world_size=num_gpus)
     assert cfg.MODEL.units % cfg.MODEL.num_heads == 0
     model = build_model(cfg, dataset.vocab, device)
+    if args.init_checkpoint is not None:
+        missing, unexpected = model.load_state_dict(read_checkpoint(args.init_checkpoint)["model"], strict=False)
     if getattr(args, "parity", False):
         model.fp32_training = True
         model.parity_fp32 = True
     log(f"#total params = {sum(p.nelement() for p in model.parameters())}")
+    if args.init_checkpoint is not None:
+        log(f"weights of {args.init_checkpoint} (missing: {list(missing)}, unexpected: {list(unexpected)})")
     reducer = GradReducer() if world > 1 else None
     if reducer is not None:
         reducer.broadcast_params(model)                                         # DDP constructor semantics (C3)
     trainer = Trainer(model, cfg, num_gpus=num_gpus, reducer=reducer, graph=bool(getattr(args, "graph", False)),
-                      merge_chunks=getattr(args, "merge_chunks", None), settle_heap=True)
+                      merge_chunks=getattr(args, "merge_chunks", None), settle_heap=True, param_groups=group_spec,
+                      decoupled=bool(args.adamw))
     best_val_nll = float("inf")
+    if args.resume is not None:
+        # (a checkpoint whose optimiser grouping differs from these flags is refused by FusedAdam.load_state_dict)
+        trainer.train_step, best = load_checkpoint(args.resume, model, trainer.optimizer, trainer.scheduler)
+        best_val_nll = float("inf") if best is None else float(best)
+        trainer._log_step0 = trainer.train_step                                 # the logging window starts here
+        if reducer is not None:
+            reducer.broadcast_params(model)
+        log(f"resumed {args.resume} at step {trainer.train_step}")
+        if trainer.train_step >= cfg.TRAIN.max_step:
+            raise ValueError(f"--resume: the checkpoint is at step {trainer.train_step}, max_step is {cfg.TRAIN.max_step}")
+        # the batch stream is not part of a checkpoint: a fresh shuffle, not the one the run started with
+        train_iter = dataset.get_iterator(batch_size, cfg.TRAIN.tgt_length, device, "train", True,
+                                          seed=seed + 1000 * rank + trainer.train_step)
 
     def checkpoint(name, val_nll):                                              # train.py:29-54 (C7)
         if reducer is not None:

@@ -262,6 +262,32 @@ int commu_adam_step(float* p, const float* g, float* m, float* v, void* p_bf16, 
 int commu_adam_step_dev(float* p, const float* g, float* m, float* v, void* p_bf16, size_t n, const float* scal,
                         float beta1, float beta2, float eps, const float* gnorm, float clip, hipStream_t stream);
 int commu_adam_bias_corrections(float beta1, float beta2, int step, float* out2);
+/* ---- the same step with per-tensor GROUPS (optim.Adam's `weight_decay`, train.py:442-443, which the step above lacks;
+ * torch.optim param_groups with their own lr / weight_decay; tensors with requires_grad = False).  The buffers are WHOLE
+ * flat buffers in which every tensor starts at a multiple of 64 elements and the gaps are zero: block_group (device,
+ * n / 64 bytes) holds the group number of every 64-element block.  Per element of group k, coef the clip coefficient:
+ *   decoupled == 0 (optim.Adam):  gr = coef g + wd_k p, then the step above with lr_k;
+ *   decoupled != 0 (optim.AdamW): p *= 1 - lr_k wd_k,   then the step above with lr_k and gr = coef g;
+ *   frozen (bit k of frozen_mask): p, m, v and p_bf16 are neither read nor written.
+ * lr, weight_decay: HOST arrays of ngroups (<= COMMU_OPTIM_MAX_GROUPS) floats, passed on as kernel arguments (no copy to
+ * the device).  With one group, decay 0 and nothing frozen the results are commu_adam_step's bit for bit.
+ * -22: n is not a multiple of 64, a buffer is not 16-byte aligned, ngroups out of range; nothing is launched then. */
+#define COMMU_OPTIM_MAX_GROUPS 16
+int commu_adam_step_groups(float* p, const float* g, float* m, float* v, void* p_bf16, size_t n,
+                           const unsigned char* block_group, int ngroups, const float* lr, const float* weight_decay,
+                           unsigned frozen_mask, int decoupled, float beta1, float beta2, float eps, int step,
+                           const float* gnorm, float clip, hipStream_t stream);
+/* ... with the bias corrections and the group table read from DEVICE memory, 2 + 3 * 16 floats:
+ * table = {1 - beta1^t, 1 - beta2^t, lr[16], weight_decay[16], frozen[16] (non-zero: frozen)}; entries past the groups in
+ * use must be marked frozen.  Bit-identical to commu_adam_step_groups; what a captured optimiser graph replays. */
+int commu_adam_step_groups_dev(float* p, const float* g, float* m, float* v, void* p_bf16, size_t n,
+                               const unsigned char* block_group, const float* table, int decoupled, float beta1,
+                               float beta2, float eps, const float* gnorm, float clip, hipStream_t stream);
+/* commu_grad_norm over the blocks of the groups that are not frozen (clip_grad_norm_, train.py:159-161, when frozen
+ * parameters carry no gradient): frozen blocks are not read; deterministic; with frozen_mask == 0 it is commu_grad_norm bit
+ * for bit.  -22 as above. */
+int commu_grad_norm_groups(const float* g, size_t n, const unsigned char* block_group, unsigned frozen_mask, float* part,
+                           int npart, float* out_norm, hipStream_t stream);
 /* Dropout seed salt: every dropout site of every kernel uses (its seed argument + salt); the salt is 0 until this call
  * loads it from device memory (src == NULL: back to 0).  Kernel arguments of a captured hipGraph are frozen, the salt
  * is not: a captured training step starts with this call and draws fresh masks on every replay. */
