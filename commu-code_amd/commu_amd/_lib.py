@@ -95,29 +95,6 @@ class DecodeArmArgs(C.Structure):
     """commu_decode_arm_args (the header documents every field)."""
     _fields_ = [("struct_bytes", C.c_uint), ("njobs", c_i), ("jobs", c_p), ("variates", c_p), ("B", c_i), ("Rcap", c_i),
                 ("L", c_i), ("H", c_i), ("Lmax", c_i), ("ctx_rows", c_i), ("n_cache", c_i),
-                ("row_bytes", c_i * 4), ("cache", c_p * 4), ("image", c_p * 4),
-                ("klen", c_p), ("e_klen0", c_p), ("state", c_p), ("e_state", c_p), ("nf", c_i),
-                ("seq", c_p), ("e_seq", c_p), ("ld_seq", c_i), ("ld_head", c_i),
-                ("chord_tok", c_p), ("chord_pos", c_p), ("e_chord_tok", c_p), ("e_chord_pos", c_p), ("ld_chord", c_i),
-                ("wrong", c_p), ("ld_wrong", c_i), ("utable", c_p), ("ld_u", c_i),
-                ("seq_logp", c_p), ("trace", c_p), ("ld_trace", c_i),
-                ("temperature_rows", c_p), ("top_k_rows", c_p), ("top_p_rows", c_p),
-                ("e_temperature", c_p), ("e_top_k", c_p), ("e_top_p", c_p),
-                ("bias", c_p), ("e_bias", c_p), ("ld_bias", c_i),
-                ("gram_on", c_p), ("e_gram_on", c_p), ("harm_on", c_p), ("e_harm_on", c_p),
-                ("art_ctl", c_p), ("e_art", c_p),
-                ("guide_ctl", c_p), ("e_guide", c_p),
-                ("onset_ctl", c_p), ("e_onset", c_p),
-                ("interval_ctl", c_p), ("e_interval", c_p), ("density_ctl", c_p), ("e_density", c_p),
-                ("order_ctl", c_p), ("e_order", c_p), ("voice_ctl", c_p), ("e_voice", c_p),
-                ("cls_ctl", c_p), ("e_cls", c_p),
-                ("form_ctl", c_p), ("e_form", c_p), ("form_state", c_p), ("form_tok", c_p)]
-
-
-class DecodeArmPrimedArgs(C.Structure):
-    """commu_decode_arm_primed_args (the header documents every field)."""
-    _fields_ = [("struct_bytes", C.c_uint), ("njobs", c_i), ("jobs", c_p), ("variates", c_p), ("B", c_i), ("Rcap", c_i),
-                ("L", c_i), ("H", c_i), ("Lmax", c_i), ("img_rows", c_i), ("n_cache", c_i),
                 ("row_bytes", c_i * 4), ("cache", c_p * 4), ("image", c_p * 4), ("ring", c_i), ("grid_rows", c_i),
                 ("klen", c_p), ("e_klen0", c_p), ("state", c_p), ("e_state", c_p), ("nf", c_i),
                 ("seq", c_p), ("e_seq", c_p), ("ld_seq", c_i), ("ld_head", c_i),
@@ -135,6 +112,10 @@ class DecodeArmPrimedArgs(C.Structure):
                 ("order_ctl", c_p), ("e_order", c_p), ("voice_ctl", c_p), ("e_voice", c_p),
                 ("cls_ctl", c_p), ("e_cls", c_p),
                 ("form_ctl", c_p), ("e_form", c_p), ("form_state", c_p), ("form_tok", c_p)]
+
+
+class DecodeArmPrimedArgs(DecodeArmArgs):
+    """commu_decode_arm_primed_args: the same block (its _fields_ are inherited), under the name its callers build it by."""
 
 
 def struct_args(cls, **fields):
@@ -265,7 +246,7 @@ PROTOTYPES = {
     "commu_decode_arm": [C.POINTER(DecodeArmArgs), c_p],
     "commu_decode_arm_primed_args_bytes": [],
     "commu_decode_arm_primed_chunk_rows": [],
-    "commu_decode_arm_primed": [C.POINTER(DecodeArmPrimedArgs), c_p],
+    "commu_decode_arm_primed": [C.POINTER(DecodeArmArgs), c_p],
     "commu_forcing_replay": [c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p,
                              c_p, c_p, c_i, c_p, c_i, c_p],
     "commu_decode_prefill_scatter": [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p],

@@ -14,7 +14,6 @@ from __future__ import annotations
 import collections
 import ctypes as C
 import dataclasses
-import functools
 import json
 import math
 from typing import Callable, List, NamedTuple, Optional, Sequence
@@ -2944,6 +2943,29 @@ class ForcedDecoder:
         else:
             self._ctx_kv = tuple(t[:, :, :, :n].clone() for t in self.state.cache_tensors())
 
+    # ---- the start state of a request, the one statement load(), rearm(), pool_replay() and admit() share
+    @staticmethod
+    def _start_record(n_cond, rep):
+        """The state record a request's attempt starts from, for its report `rep`."""
+        # record: len, forced, redo, first, filled, done, failed, iters, nbar, nchord, cur, length_fit, ndraw, ntrace
+        return [1 + n_cond, -1, 0, 1, int(rep.num_measures % 4 == 0), 0, 0, 0, 0, rep.n_chords, 0, int(rep.length_fit), 0, 0]
+
+    def _idle_records(self):
+        """[B, NF] records of idle slots: len 1 (seq[0] = 0), nothing forced, done -- they decode nothing."""
+        idle = np.zeros((self.B, self.NF), dtype=np.int32)
+        idle[:, 0], idle[:, 1], idle[:, 5] = 1, -1, 1
+        return idle
+
+    def _chord_rows(self, input_data):
+        """(chord tokens, chord positions, a fresh ForcingReport) of a request, checked as the reference checks them."""
+        comps = input_data.chord_token_components
+        ct, cp = list(comps["chord_token"]), list(comps["chord_position"])
+        if len(ct) != len(cp):
+            raise AssertionError("Wrong Chord Length")                      # midi_inferrer.py:27
+        if len(ct) > self.ld_chord:
+            raise CommuHipError(f"{len(ct)} chords > max_chords={self.ld_chord}")
+        return ct, cp, ForcingReport(len(ct), float(input_data.num_measures))
+
     def load(self, encoded_metas: Sequence[Sequence[int]], input_datas, uniforms: Optional[np.ndarray] = None,
              prompts: Optional[Sequence[Sequence[int]]] = None):
         """Conditioning of all B sequences: context [0] + meta[:n-1] into the caches (the n-th meta token is fed by
@@ -2981,20 +3003,12 @@ class ForcedDecoder:
         cpos = np.zeros((B, self.ld_chord), dtype=np.int32)
         self.reports: List[ForcingReport] = []
         for b, (meta, data) in enumerate(zip(encoded_metas, input_datas)):
-            comps = data.chord_token_components
-            ct, cp = list(comps["chord_token"]), list(comps["chord_position"])
-            if len(ct) != len(cp):
-                raise AssertionError("Wrong Chord Length")                      # midi_inferrer.py:27
-            if len(ct) > self.ld_chord:
-                raise CommuHipError(f"{len(ct)} chords > max_chords={self.ld_chord}")
+            ct, cp, rep = self._chord_rows(data)
             seq[b, 0] = 0
             seq[b, 1:1 + n_cond] = meta[:n_cond]
             ctok[b, :len(ct)], cpos[b, :len(cp)] = ct, cp
-            nm = float(data.num_measures)
-            rep = ForcingReport(len(ct), nm)
             self.reports.append(rep)
-            # record: len, forced, redo, first, filled, done, failed, iters, nbar, nchord, cur, length_fit, ndraw, ntrace
-            fsm[b] = [1 + n_cond, -1, 0, 1, int(nm % 4 == 0), 0, 0, 0, 0, len(ct), 0, int(rep.length_fit), 0, 0]
+            fsm[b] = self._start_record(n_cond, rep)
         self.fsm.copy_(torch.from_numpy(fsm))
         self.seq.copy_(torch.from_numpy(seq))
         self.seq_logp.fill_(float("nan"))          # (the context was not drawn)
@@ -3059,9 +3073,7 @@ class ForcedDecoder:
         if self._primed is not None:          # back to the primed state: the record as the replay left it (device copy)
             self.fsm[b].copy_(self._primed[0][b])
         else:
-            rec = [1 + self.n_cond, -1, 0, 1, int(rep.num_measures % 4 == 0), 0, 0, 0, 0, rep.n_chords, 0,
-                   int(rep.length_fit), 0, 0]
-            self.fsm[b].copy_(torch.tensor(rec, dtype=torch.int32))
+            self.fsm[b].copy_(torch.tensor(self._start_record(self.n_cond, rep), dtype=torch.int32))
         self._form_reset(b, 1)                # (seq[b] up to the record's length is the context and the prompt)
         self.wrong[b].zero_()
         self.seq_logp[b].fill_(float("nan"))
@@ -3122,22 +3134,14 @@ class ForcedDecoder:
         todo = [i for i, p in enumerate(prompts) if p]
         for lo in range(0, len(todo), B):
             batch = todo[lo:lo + B]
-            fsm = np.zeros((B, NF), dtype=np.int32)
-            fsm[:, 0], fsm[:, 1], fsm[:, 5] = 1, -1, 1          # rows beyond the batch: idle, no prompt
+            fsm = self._idle_records()          # rows beyond the batch: idle, no prompt
             seq = np.zeros((B, self.ld_seq), dtype=np.int32)
             chords = np.zeros((2, B, self.ld_chord), dtype=np.int32)
             pr = np.zeros((B, self.max_prompt), dtype=np.int32)
             plen = np.zeros(B, dtype=np.int32)
             for b, i in enumerate(batch):
-                comps = input_datas[i].chord_token_components
-                ct, cp = list(comps["chord_token"]), list(comps["chord_position"])
-                if len(ct) != len(cp):
-                    raise AssertionError("Wrong Chord Length")                      # midi_inferrer.py:27
-                if len(ct) > self.ld_chord:
-                    raise CommuHipError(f"{len(ct)} chords > max_chords={self.ld_chord}")
-                nm = float(input_datas[i].num_measures)
-                rep = ForcingReport(len(ct), nm)
-                fsm[b] = [1 + n_cond, -1, 0, 1, int(nm % 4 == 0), 0, 0, 0, 0, len(ct), 0, int(rep.length_fit), 0, 0]
+                ct, cp, rep = self._chord_rows(input_datas[i])
+                fsm[b] = self._start_record(n_cond, rep)
                 seq[b, 1:1 + n_cond] = list(encoded_metas[i])
                 chords[0, b, :len(ct)], chords[1, b, :len(cp)] = ct, cp
                 pr[b, :len(prompts[i])] = prompts[i]
@@ -3212,9 +3216,7 @@ class ForcedDecoder:
         for t in st.cache_tensors():
             t.zero_()
         st.repack()
-        idle = np.zeros((B, self.NF), dtype=np.int32)
-        idle[:, 0], idle[:, 1], idle[:, 5] = 1, -1, 1          # len 1 (seq[0] = 0), nothing forced, done
-        self.fsm.copy_(torch.from_numpy(idle))
+        self.fsm.copy_(torch.from_numpy(self._idle_records()))
         self.seq.zero_()
         self._form_reset(0, B)
         self.seq_logp.fill_(float("nan"))
@@ -3270,10 +3272,9 @@ class ForcedDecoder:
         if P["args"] is None or P["sig"] != sig:
             st = self.state
             on = lambda t, e: {} if t is None else e
-            # (a primed decoder: the block of commu_decode_arm_primed -- the same fields, the ring mode and the trace twin)
-            build = ops.decode_arm_args if not P["primed"] else functools.partial(
-                ops.decode_arm_primed_args, ring=self.sliding, **on(P["e_trace"], {"e_trace": P["e_trace"]}))
-            P["args"] = build(
+            # (the one block of both launches; only a primed pool names the ring mode, the trace twin and grid_rows below)
+            primed = {"ring": int(self.sliding), **on(P["e_trace"], {"e_trace": P["e_trace"]})} if P["primed"] else {}
+            P["args"] = ops.decode_arm_args(
                 st.cache_tensors(), P["image"], jobs=P["stage"], variates=P["stage"][P["hdr"]:].view(F32),
                 klen=st.klen, e_klen0=P["e_klen0"], state=self.fsm, e_state=P["e_state"], nf=self.NF,
                 seq=self.seq, e_seq=P["e_seq"], ld_seq=self.ld_seq, ld_head=P["ld_head"],
@@ -3287,7 +3288,7 @@ class ForcedDecoder:
                 **on(self.harm_on, {"harm_on": self.harm_on, "e_harm_on": P["e_harm_on"]}),
                 **{k: v for r, w in words.items() if w is not None for k, v in ((r.ctl, w), (r.entry, P[r.entry]))},
                 **on(self.form_ctl, {"form_state": self.form_state, "form_tok": self.form_tok}),
-                **on(self.cls_ctl, {"cls_ctl": self.cls_ctl, "e_cls": P["e_cls"]}))
+                **on(self.cls_ctl, {"cls_ctl": self.cls_ctl, "e_cls": P["e_cls"]}), **primed)
             P["sig"] = sig
         if P["primed"]:
             P["args"].grid_rows = P["grid_rows"]          # (this pool's longest image: fewer chunk workgroups)
@@ -3339,20 +3340,12 @@ class ForcedDecoder:
                 vals[dep][0] = 0                  # (as the rule's setter: word 0, no cap, where the request leaves it off)
         if class_table is not None and self.cls_ctl is None:
             raise CommuHipError("admit: a class table, but the decoder has no class records (set_class_sampling)")
-        comps = input_data.chord_token_components
-        ct, cp = list(comps["chord_token"]), list(comps["chord_position"])
-        if len(ct) != len(cp):
-            raise AssertionError("Wrong Chord Length")                      # midi_inferrer.py:27
-        if len(ct) > self.ld_chord:
-            raise CommuHipError(f"{len(ct)} chords > max_chords={self.ld_chord}")
-        nm = float(input_data.num_measures)
-        rep = ForcingReport(len(ct), nm)
-        P["meta"][entry] = (len(ct), nm)
+        ct, cp, rep = self._chord_rows(input_data)
+        P["meta"][entry] = (rep.n_chords, rep.num_measures)
         up = lambda dst, a: dst.copy_(torch.from_numpy(np.ascontiguousarray(a)))
         head = np.zeros(P["ld_head"], dtype=np.int32)
         if primed is None:
-            up(P["e_state"][entry], np.array([1 + n_cond, -1, 0, 1, int(nm % 4 == 0), 0, 0, 0, 0, len(ct), 0,
-                                              int(rep.length_fit), 0, 0], dtype=np.int32))
+            up(P["e_state"][entry], np.array(self._start_record(n_cond, rep), dtype=np.int32))
             head[1:1 + n_cond] = list(encoded_meta)
         else:
             up(P["e_state"][entry], primed["record"])

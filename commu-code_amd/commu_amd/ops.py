@@ -1681,12 +1681,11 @@ def decode_prefill_scatter_kv8(qkv, T, kc8, vc8, ks, vs, klen, lens, slots=None,
 
 
 # ---------------------------------------------------------------------------------------------- request pool (opt-in)
-def decode_arm_args(cache, image, primed=False, **fields):
+def decode_arm_args(cache, image, **fields):
     """The argument block of commu_decode_arm (include/commu_hip.h), built once per decoder: cache / image are the 2 or
     4 cache tensors [L, B, H, Lmax, row] and the store's images [L, Rcap, H, ctx_rows, row] in the same order; every
     other field by its name in the header, tensors (GPU, contiguous) for the pointers and None for an array the decoder
-    does not have.  The geometry (B, Rcap, L, H, Lmax, ctx_rows, row_bytes) is read off the tensors.
-    primed: the block of commu_decode_arm_primed instead (decode_arm_primed_args)."""
+    does not have.  The geometry (B, Rcap, L, H, Lmax, ctx_rows, row_bytes) is read off the tensors."""
     if len(cache) != len(image) or len(cache) not in (2, 4):
         raise CommuHipError(f"decode_arm: 2 or 4 cache tensors and as many images expected, got {len(cache)} / {len(image)}")
     L, B, H, Lmax = cache[0].shape[:4]
@@ -1698,11 +1697,7 @@ def decode_arm_args(cache, image, primed=False, **fields):
         if tuple(c.shape[:4]) != (L, B, H, Lmax) or tuple(im.shape) != (L, Rcap, H, ctx_rows, c.shape[4]):
             raise CommuHipError(f"decode_arm: cache {tuple(c.shape)} and image {tuple(im.shape)} do not belong together")
         rb.append(c.shape[4] * c.element_size())
-    if primed:
-        a = _lib.struct_args(_lib.DecodeArmPrimedArgs, B=B, Rcap=Rcap, L=L, H=H, Lmax=Lmax, img_rows=ctx_rows,
-                             n_cache=len(cache))
-    else:
-        a = _lib.struct_args(_lib.DecodeArmArgs, B=B, Rcap=Rcap, L=L, H=H, Lmax=Lmax, ctx_rows=ctx_rows, n_cache=len(cache))
+    a = _lib.struct_args(_lib.DecodeArmArgs, B=B, Rcap=Rcap, L=L, H=H, Lmax=Lmax, ctx_rows=ctx_rows, n_cache=len(cache))
     for i, (c, im) in enumerate(zip(cache, image)):
         a.row_bytes[i], a.cache[i], a.image[i] = rb[i], c.data_ptr(), im.data_ptr()
     for name, v in fields.items():
@@ -1722,10 +1717,11 @@ def decode_arm(args, njobs: int):
 
 
 def decode_arm_primed_args(cache, image, ring=False, grid_rows=0, **fields):
-    """The argument block of commu_decode_arm_primed (include/commu_hip.h): decode_arm_args with the store's images
-    [L, Rcap, H, img_rows, row] of a primed pool, ring (the caches are rings of Lmax rows: klen counts positions),
-    grid_rows (0, or the pool's longest image) and the optional e_trace beside trace."""
-    return decode_arm_args(cache, image, primed=True, ring=1 if ring else 0, grid_rows=int(grid_rows), **fields)
+    """The argument block of commu_decode_arm_primed (include/commu_hip.h), the same block: decode_arm_args with the
+    store's images [L, Rcap, H, ctx_rows, row] of a primed pool, ring (the caches are rings of Lmax rows: klen counts
+    positions), grid_rows (0, or the pool's longest image) and the optional e_trace beside trace."""
+    a = decode_arm_args(cache, image, ring=1 if ring else 0, grid_rows=int(grid_rows), **fields)
+    return _lib.DecodeArmPrimedArgs.from_buffer_copy(a)
 
 
 def decode_arm_primed_chunk_rows() -> int:

@@ -1,5 +1,5 @@
 // Form templates (gfx950): the per-slot replay state of the forcing stage and what resets it, shared by the forcing kernels
-// (decode_loop.h, forcing.hip) and the two arm launches (decode_arm.hip, decode_arm_primed.hip).
+// (decode_loop.h, forcing.hip) and the slot-array routine of the two arm launches (decode_arm.hip).
 //
 // form_state is int32 [B][FS_COUNT]: a header of FS_BAR_AT ints -- active, cursor, end, k (the phase inside the current note
 // group), the open bar's row word, g (the group the last search found, -1: none), two reserved ints written 0 -- and

@@ -1101,7 +1101,8 @@ int commu_decode_prefill_scatter(const void* qkv, int ld_qkv, int T, int B, void
  *   chord_tok / chord_pos [slot][0 .. ld_chord) = e_chord_tok / e_chord_pos [entry];  wrong[slot][0 .. ld_wrong) = 0;
  *   utable[slot][0 .. ld_u) = variates[j];
  *   and, each only where BOTH the slot array and its store twin are given (seq_logp, trace: the slot array), as the
- *   loop's entry point treats a null array:  seq_logp[slot][0 .. 2 ld_seq) = NaN;  trace[slot][0 .. ld_trace) = 0;
+ *   loop's entry point treats a null array:  seq_logp[slot][0 .. 2 ld_seq) = NaN;  trace[slot][0 .. ld_trace) =
+ *   e_trace[entry] where e_trace is given (a replay's trace continues into the decode), zeros where only trace is;
  *   temperature_rows / top_k_rows / top_p_rows [slot] = e_temperature / e_top_k / e_top_p [entry];
  *   bias[slot][0 .. ld_bias) = e_bias[entry];  gram_on / harm_on [slot] = e_gram_on / e_harm_on [entry] (bytes);
  *   order_ctl / voice_ctl / density_ctl / interval_ctl / onset_ctl [slot] = e_order / e_voice / e_density / e_interval /
@@ -1119,7 +1120,8 @@ int commu_decode_prefill_scatter(const void* qkv, int ld_qkv, int T, int B, void
  *   njobs == 0: nothing is launched, 0.  -22: njobs outside [0, B]; B, Rcap, L, H, Lmax, ctx_rows, nf, ld_head, ld_chord,
  *     ld_wrong or ld_u < 1; ld_head > ld_seq; n_cache not 2 or 4; row_bytes[i] < 1; a null jobs, variates, klen, state,
  *     seq, chord_tok, chord_pos, wrong, utable, cache[i], image[i] or store twin of those; a cache[i] / image[i] with
- *     row_bytes[i] % 16 == 0 that is not 16-byte aligned; jobs / variates not 4-byte aligned. */
+ *     row_bytes[i] % 16 == 0 that is not 16-byte aligned; jobs / variates not 4-byte aligned; ring != 0 or
+ *     grid_rows != 0 (the geometry of commu_decode_arm_primed below, which this launch does not have). */
 typedef struct commu_decode_arm_args {
     unsigned struct_bytes;
     int njobs;
@@ -1131,106 +1133,7 @@ typedef struct commu_decode_arm_args {
     int row_bytes[4];
     void* cache[4];
     const void* image[4];
-    /* required slot arrays and their store twins */
-    int* klen;
-    const int* e_klen0;
-    int* state;
-    const int* e_state;
-    int nf;
-    int* seq;
-    const int* e_seq;
-    int ld_seq, ld_head;
-    int* chord_tok;
-    int* chord_pos;
-    const int* e_chord_tok;
-    const int* e_chord_pos;
-    int ld_chord;
-    unsigned char* wrong;
-    int ld_wrong;
-    float* utable;
-    int ld_u;
-    /* optional */
-    float* seq_logp;
-    int* trace;
-    int ld_trace;
-    float* temperature_rows;
-    int* top_k_rows;
-    float* top_p_rows;
-    const float* e_temperature;
-    const int* e_top_k;
-    const float* e_top_p;
-    float* bias;
-    const float* e_bias;
-    int ld_bias;
-    unsigned char* gram_on;
-    const unsigned char* e_gram_on;
-    unsigned char* harm_on;
-    const unsigned char* e_harm_on;
-    int* art_ctl;
-    const int* e_art;
-    int* guide_ctl;
-    const int* e_guide;
-    int* onset_ctl;
-    const int* e_onset;
-    int* interval_ctl;
-    const int* e_interval;
-    int* density_ctl;
-    const int* e_density;
-    int* order_ctl;
-    const int* e_order;
-    int* voice_ctl;
-    const int* e_voice;
-    int* cls_ctl;
-    const int* e_cls;
-    /* form templates: the slots' control words and their store twin, the state rows and the replay tokens
-     * (at the struct's end: every other field keeps its place) */
-    int* form_ctl;
-    const int* e_form;
-    int* form_state;
-    int* form_tok;
-} commu_decode_arm_args;
-int commu_decode_arm_args_bytes(void);
-int commu_decode_arm(const commu_decode_arm_args* a, hipStream_t stream);
-/* ---- request pool, PRIMED entries: the arm launch of a pool whose requests continue a prompt of their own
- * (csrc/decode_arm_primed.hip).  An entry's K/V image is then as long as its replayed prompt (img_rows: hundreds to
- * thousands of rows, not 16), so the image is copied ROW-PARALLEL: grid (L H, njobs, ceil(R / C)) workgroups of 128
- * threads, R = min(img_rows, Lmax) (min(.., grid_rows) where grid_rows > 0), C = commu_decode_arm_primed_chunk_rows();
- * chunk workgroup z moves rows z C .. min(n, (z + 1) C) - 1 of its (layer, head) in every cache tensor with 16-byte
- * vector loads and stores, four independent loads per thread issued before the first store; a chunk workgroup whose first
- * row is >= n exits (chunk 0 stays: the L H workgroups of a job's chunk 0 share the slot arrays' rows as the waves of
- * commu_decode_arm do).  Plain vector stores only; no atomics, no LDS, no synchronisation between workgroups.
- * Every field that commu_decode_arm_args has means what it means there (img_rows is its ctx_rows).  What differs, per job
- * (slot, entry) with 0 <= slot < B and 0 <= entry < Rcap (others are skipped):
- *   rows: with R as above and k = max(e_klen0[entry], 0), n = min(k, R) rows are copied --
- *     cache[i][l][slot][h][0 .. n) = image[i][l][entry][h][0 .. n) --, rows >= n and other slots are not touched;
- *     ring == 0 (linear cache): klen[slot] = n;
- *     ring != 0 (the cache is a ring of Lmax rows, klen counts POSITIONS and the attention takes the row modulo Lmax):
- *       klen[slot] = k, unclamped; the image is then either no longer than any prompt needs (img_rows < Lmax, k <= img_rows
- *       is the caller's duty) or a ring with the cache's modulus (img_rows == Lmax), so min(k, Lmax) physical rows are the
- *       whole image of a wrapped prompt;
- *   seq[slot][0 .. m) = e_seq[entry][0 .. m), m = e_state[entry][0] (the record's length word) clamped to [0, ld_head];
- *     the words of seq[slot] from m on are not touched;
- *   trace[slot][0 .. ld_trace) = e_trace[entry] where trace and e_trace are given (the replay's trace continues into the
- *     decode), zeros where only trace is;
- *   everything else as commu_decode_arm: klen, state, chords, wrong zeroed, utable, seq_logp NaN (prompt tokens carry no
- *     pair), the sampling triple, bias row, grammar / harmony switches, note-order, voice, density and interval words,
- *     class records.
- *   grid_rows: 0, or an upper bound of every e_klen0 the launch will meet (the pool's longest image): fewer chunk
- *     workgroups are launched; it is part of the clamp of n above, so a longer entry is truncated, never overrun.
- * njobs == 0: nothing is launched, 0.  -22: a struct_bytes other than commu_decode_arm_primed_args_bytes(), and
- * every condition commu_decode_arm refuses (img_rows for ctx_rows); grid_rows < 0; ring != 0 with img_rows > Lmax. */
-typedef struct commu_decode_arm_primed_args {
-    unsigned struct_bytes;
-    int njobs;
-    const int* jobs;
-    const float* variates;
-    int B, Rcap;
-    /* K/V caches and the store's images */
-    int L, H, Lmax, img_rows, n_cache;
-    int row_bytes[4];
-    void* cache[4];
-    const void* image[4];
-    int ring, grid_rows;
+    int ring, grid_rows;          /* commu_decode_arm_primed only: commu_decode_arm takes 0, 0 */
     /* required slot arrays and their store twins */
     int* klen;
     const int* e_klen0;
@@ -1289,7 +1192,35 @@ typedef struct commu_decode_arm_primed_args {
     const int* e_form;
     int* form_state;
     int* form_tok;
-} commu_decode_arm_primed_args;
+} commu_decode_arm_args;
+int commu_decode_arm_args_bytes(void);
+int commu_decode_arm(const commu_decode_arm_args* a, hipStream_t stream);
+/* ---- request pool, PRIMED entries: the arm launch of a pool whose requests continue a prompt of their own
+ * (csrc/decode_arm.hip, the same file).  It takes the SAME argument block, and every field means what it means above.
+ * An entry's K/V image is then as long as its replayed prompt (ctx_rows: hundreds to thousands of rows, not 16), so the
+ * image is copied ROW-PARALLEL: grid (L H, njobs, ceil(R / C)) workgroups of 128 threads, R = min(ctx_rows, Lmax)
+ * (min(.., grid_rows) where grid_rows > 0), C = commu_decode_arm_primed_chunk_rows(); chunk workgroup z moves rows
+ * z C .. min(n, (z + 1) C) - 1 of its (layer, head) in every cache tensor with 16-byte vector loads and stores, four
+ * independent loads per thread issued before the first store; a chunk workgroup whose first row is >= n exits (chunk 0
+ * stays: the L H workgroups of a job's chunk 0 share the slot arrays' rows as the waves of commu_decode_arm do).  Plain
+ * vector stores only; no atomics, no LDS, no synchronisation between workgroups.
+ * What differs from commu_decode_arm, per job (slot, entry) with 0 <= slot < B and 0 <= entry < Rcap (others are skipped):
+ *   rows: with R as above and k = max(e_klen0[entry], 0), n = min(k, R) rows are copied --
+ *     cache[i][l][slot][h][0 .. n) = image[i][l][entry][h][0 .. n) --, rows >= n and other slots are not touched;
+ *     ring == 0 (linear cache): klen[slot] = n;
+ *     ring != 0 (the cache is a ring of Lmax rows, klen counts POSITIONS and the attention takes the row modulo Lmax):
+ *       klen[slot] = k, unclamped; the image is then either no longer than any prompt needs (ctx_rows < Lmax, k <= ctx_rows
+ *       is the caller's duty) or a ring with the cache's modulus (ctx_rows == Lmax), so min(k, Lmax) physical rows are the
+ *       whole image of a wrapped prompt;
+ *   seq[slot][0 .. m) = e_seq[entry][0 .. m), m = e_state[entry][0] (the record's length word) clamped to [0, ld_head];
+ *     the words of seq[slot] from m on are not touched;
+ *   grid_rows: 0, or an upper bound of every e_klen0 the launch will meet (the pool's longest image): fewer chunk
+ *     workgroups are launched; it is part of the clamp of n above, so a longer entry is truncated, never overrun.
+ *   Everything else is written as commu_decode_arm writes it (seq_logp NaN: prompt tokens carry no pair).
+ * njobs == 0: nothing is launched, 0.  -22: a struct_bytes other than commu_decode_arm_primed_args_bytes() (the same
+ * value), and every condition commu_decode_arm refuses but its last (ring, grid_rows); grid_rows < 0; ring != 0 with
+ * ctx_rows > Lmax. */
+typedef commu_decode_arm_args commu_decode_arm_primed_args;
 int commu_decode_arm_primed_args_bytes(void);
 int commu_decode_arm_primed_chunk_rows(void);
 int commu_decode_arm_primed(const commu_decode_arm_primed_args* a, hipStream_t stream);

@@ -1,26 +1,83 @@
-"""Shared builders of the request-pool tests (tests/test_pool_host.py, tests/test_pool_gpu.py): the arm launch's
-operands with sentinels in every byte, its expected result in numpy, and the requests of the end-to-end tests."""
+"""Shared builders of the request-pool tests (tests/test_pool_host.py, tests/test_pool_gpu.py and their primed twins over
+tests/pool_prime_contract.py): the ONE numpy restatement of both arm launches (commu_decode_arm, commu_decode_arm_primed,
+include/commu_hip.h) -- the state of every cache tensor and slot array after a launch, given the state before --, the
+launches' operands with sentinels in every byte, and the requests of the end-to-end tests."""
 import types
 
 import numpy as np
 
+import form_contract as FC
+
 NAN_BYTE = 0x7F          # (kv8_contract.NAN_BYTE: what rows that must never be read hold)
 NF = 14                  # commu_forcing_state_ints()
 CTX_ROWS = 16
-# slot array -> (store twin, row shape, dtype, sentinel); None twin: written without one
+BAR = 2                  # (prime_contract.BAR)
+# slot array -> (store twin, row shape, dtype); a None shape: the widths of the case
 REQUIRED = {"state": ("e_state", (NF,), np.int32), "seq": ("e_seq", None, np.int32),
             "chord_tok": ("e_chord_tok", None, np.int32), "chord_pos": ("e_chord_pos", None, np.int32)}
+# every optional per-slot array the launches move from a store twin
 OPTIONAL = {"temperature_rows": ("e_temperature", (), np.float32), "top_k_rows": ("e_top_k", (), np.int32),
             "top_p_rows": ("e_top_p", (), np.float32), "bias": ("e_bias", (768,), np.float32),
             "gram_on": ("e_gram_on", (), np.uint8), "harm_on": ("e_harm_on", (), np.uint8),
             "order_ctl": ("e_order", (), np.int32), "voice_ctl": ("e_voice", (), np.int32),
+            "density_ctl": ("e_density", (), np.int32), "interval_ctl": ("e_interval", (), np.int32),
+            "onset_ctl": ("e_onset", (), np.int32), "guide_ctl": ("e_guide", (), np.int32),
+            "art_ctl": ("e_art", (), np.int32), "form_ctl": ("e_form", (), np.int32),
             "cls_ctl": ("e_cls", (32,), np.int32)}
 
 
-def arm_case(torch, kv, DH, B=5, Lmax=24, R=3, klen0=(1, 11, 16), L=2, H=3, ld_u=9, ld_seq=40, ld_chord=6, ld_trace=8,
-             optional=True, seed=0, dev="cuda"):
-    """Slot arrays and caches full of sentinels, a store of R random entries, the staging block and the launch's
-    argument block.  kv: "bf16" (K, V) or "fp8" (K, V bytes and their scale bytes)."""
+def arm_restated(before, store, images, jobs, variates, B, R, Lmax, img_rows, ld_head, ring=False, grid_rows=0,
+                 whole_head=False):
+    """What either launch must leave.  before: {name: array} of the slot arrays ("klen", "state", "seq", "chord_tok",
+    "chord_pos", "wrong", "utable", optional "seq_logp", "trace", "form_state", "form_tok" and the controls of OPTIONAL) and
+    "cache<i>" byte arrays [L, B, H, Lmax, row]; store: the e_* twins [R, .] (an optional "e_trace"); images: byte arrays
+    [L, R, H, img_rows, row]; jobs [(slot, entry)], skipped outside [0, B) x [0, R); variates [njobs, ld_u].
+    Rows: k = max(e_klen0, 0), n = min(k, img_rows, Lmax (, grid_rows)) rows of the image go to the slot's rows 0 .. n - 1,
+    nothing else of a cache changes; klen = n on a linear cache and k, unclamped, on a ring.  The sequence head is ld_head
+    words (whole_head: the unprimed launch) or the record's length word, clamped to [0, ld_head], many (the primed one);
+    the trace is the entry's where the store has one, zeros where not.  The form state is form_contract.initial_state over
+    the entry's head up to the clamped length word -- in both launches --, and form_tok -1."""
+    exp = {k: v.copy() for k, v in before.items()}
+    cap = min(img_rows, Lmax)
+    if grid_rows > 0:
+        cap = min(cap, grid_rows)
+    for j, (s, e) in enumerate(jobs):
+        if not (0 <= s < B and 0 <= e < R):
+            continue
+        k = max(int(store["e_klen0"][e]), 0)
+        n = min(k, cap)
+        for i, im in enumerate(images):
+            exp[f"cache{i}"][:, s, :, :n] = im[:, e, :, :n]
+        exp["klen"][s] = k if ring else n
+        exp["state"][s] = store["e_state"][e]
+        length = min(max(int(store["e_state"][e][0]), 0), ld_head)
+        m = ld_head if whole_head else length
+        exp["seq"][s, :m] = store["e_seq"][e, :m]
+        exp["chord_tok"][s] = store["e_chord_tok"][e]
+        exp["chord_pos"][s] = store["e_chord_pos"][e]
+        exp["wrong"][s] = 0
+        exp["utable"][s] = np.asarray(variates, dtype=np.float32)[j]
+        if "seq_logp" in exp:
+            exp["seq_logp"][s] = np.nan
+        if "trace" in exp:
+            exp["trace"][s] = store["e_trace"][e] if "e_trace" in store else 0
+        for name, (twin, _, _) in OPTIONAL.items():
+            if name in exp:
+                exp[name][s] = store[twin][e]
+        if "form_tok" in exp:
+            exp["form_tok"][s] = -1
+        if "form_state" in exp:
+            exp["form_state"][s] = FC.initial_state([int(x) for x in store["e_seq"][e]], length)
+    return exp
+
+
+def case(torch, kv, DH, klen0, lens, primed, B=5, Lmax=24, R=3, img_rows=CTX_ROWS, L=2, H=3, ld_u=9, ld_seq=40,
+         ld_head=CTX_ROWS, ld_chord=6, ld_trace=8, optional=True, e_trace=False, ring=False, grid_rows=0, seed=0, dev="cuda"):
+    """Slot arrays full of sentinels and caches full of NAN_BYTE, a store of R random entries with images of img_rows rows,
+    e_klen0 = klen0 and the records' length words = lens, the staging block and the argument block of the launch (primed:
+    commu_decode_arm_primed's).  kv: "bf16" (K, V) or "fp8" (K, V bytes and their scale bytes).  Every entry's sequence
+    head gets Bar tokens planted: two below its length word (clamped to [0, ld_head]) and one at or beyond it, wherever the
+    length leaves such positions, so that the form state's bar_at is neither empty nor every Bar of the row."""
     from commu_amd import ops
     rng = np.random.RandomState(seed)
     rows = [DH * 2, DH * 2] if kv == "bf16" else [DH, DH, DH // 32, DH // 32]
@@ -33,44 +90,56 @@ def arm_case(torch, kv, DH, B=5, Lmax=24, R=3, klen0=(1, 11, 16), L=2, H=3, ld_u
         for rb in rows:
             a = np.full((L, n_slots, H, n_rows, rb), fill, dtype=np.uint8) if fill is not None else \
                 rng.randint(0, 256, (L, n_slots, H, n_rows, rb)).astype(np.uint8)
-            if kv == "bf16":
-                out.append(t(a).view(torch.bfloat16))
-            else:
-                out.append(t(a))
+            out.append(t(a).view(torch.bfloat16) if kv == "bf16" else t(a))
         return tuple(out)
-    c = types.SimpleNamespace(B=B, R=R, L=L, H=H, Lmax=Lmax, ld_u=ld_u, ld_seq=ld_seq, ld_chord=ld_chord, ld_trace=ld_trace,
-                              kv=kv, rows=rows, klen0=list(klen0))
+    c = types.SimpleNamespace(B=B, R=R, L=L, H=H, Lmax=Lmax, img_rows=img_rows, ld_u=ld_u, ld_seq=ld_seq, ld_head=ld_head,
+                              ld_chord=ld_chord, ld_trace=ld_trace, kv=kv, rows=rows, klen0=list(klen0), lens=list(lens),
+                              primed=primed, ring=ring, grid_rows=grid_rows)
     c.cache = cache_like(B, Lmax, NAN_BYTE)
-    c.image = cache_like(R, CTX_ROWS, None)
-    sent_i, sent_f, sent_b = -777, 123.0, 0xAB
-    sent = {np.int32: sent_i, np.float32: sent_f, np.uint8: sent_b}
-    widths = {"seq": (ld_seq, CTX_ROWS), "chord_tok": (ld_chord, ld_chord), "chord_pos": (ld_chord, ld_chord)}
-    c.slot, c.store = {}, {}
+    c.image = cache_like(R, img_rows, None)
+    sent = {np.int32: -777, np.float32: 123.0, np.uint8: 0xAB}
+    widths = {"seq": (ld_seq, ld_head), "chord_tok": (ld_chord, ld_chord), "chord_pos": (ld_chord, ld_chord)}
+    c.slot, store = {}, {}
     for name, (twin, shape, dt) in list(REQUIRED.items()) + (list(OPTIONAL.items()) if optional else []):
-        if shape is not None:
-            s_shape = e_shape = shape
-        else:
-            s_shape, e_shape = (widths[name][0],), (widths[name][1],)
+        s_shape, e_shape = (shape, shape) if shape is not None else ((widths[name][0],), (widths[name][1],))
         c.slot[name] = t(np.full((B,) + s_shape, sent[dt], dtype=dt))
         if dt == np.float32:
-            c.store[twin] = t(rng.random_sample((R,) + e_shape).astype(dt))
+            store[twin] = rng.random_sample((R,) + e_shape).astype(dt)
         else:
-            c.store[twin] = t(rng.randint(0, 200, (R,) + e_shape).astype(dt))
-    c.store["e_klen0"] = t(np.array(klen0, dtype=np.int32))
-    c.slot["klen"] = t(np.full(B, sent_i, dtype=np.int32))
-    c.slot["wrong"] = t(np.full((B, 729), sent_b, dtype=np.uint8))
-    c.slot["utable"] = t(np.full((B, ld_u), sent_f, dtype=np.float32))
+            store[twin] = rng.randint(0, 200, (R,) + e_shape).astype(dt)
+    store["e_state"][:, 0] = np.array(lens, dtype=np.int32)
+    for e in range(R):
+        m = min(max(int(lens[e]), 0), ld_head)
+        if m > 0:
+            store["e_seq"][e, rng.choice(m, size=min(2, m), replace=False)] = BAR
+        if m < ld_head:
+            store["e_seq"][e, rng.randint(m, ld_head)] = BAR
+    store["e_klen0"] = np.array(klen0, dtype=np.int32)
+    c.slot["klen"] = t(np.full(B, sent[np.int32], dtype=np.int32))
+    c.slot["wrong"] = t(np.full((B, 729), sent[np.uint8], dtype=np.uint8))
+    c.slot["utable"] = t(np.full((B, ld_u), sent[np.float32], dtype=np.float32))
     if optional:
-        c.slot["seq_logp"] = t(np.full((B, ld_seq, 2), sent_f, dtype=np.float32))
-        c.slot["trace"] = t(np.full((B, ld_trace), sent_i, dtype=np.int32))
+        c.slot["seq_logp"] = t(np.full((B, ld_seq, 2), sent[np.float32], dtype=np.float32))
+        c.slot["trace"] = t(np.full((B, ld_trace), sent[np.int32], dtype=np.int32))
+        c.slot["form_state"] = t(np.full((B, FC.NS), sent[np.int32], dtype=np.int32))
+        c.slot["form_tok"] = t(np.full(B, sent[np.int32], dtype=np.int32))
+        if e_trace:
+            store["e_trace"] = rng.randint(0, 700, (R, ld_trace)).astype(np.int32)
+    c.store = {k: t(v) for k, v in store.items()}
     c.hdr = (2 * B + 3) // 4 * 4
     c.stage = t(np.zeros(c.hdr + B * ld_u, dtype=np.int32))
-    fields = dict(c.slot)
-    fields.update(c.store)
-    c.args = ops.decode_arm_args(c.cache, c.image, jobs=c.stage, variates=c.stage[c.hdr:].view(torch.float32), nf=NF,
-                                 ld_seq=ld_seq, ld_head=CTX_ROWS, ld_chord=ld_chord, ld_wrong=729, ld_u=ld_u,
-                                 ld_trace=ld_trace if optional else 0, ld_bias=768 if optional else 0, **fields)
+    build = ops.decode_arm_args if not primed else (
+        lambda *a, **kw: ops.decode_arm_primed_args(*a, ring=ring, grid_rows=grid_rows, **kw))
+    c.args = build(c.cache, c.image, jobs=c.stage, variates=c.stage[c.hdr:].view(torch.float32), nf=NF, ld_seq=ld_seq,
+                   ld_head=ld_head, ld_chord=ld_chord, ld_wrong=729, ld_u=ld_u, ld_trace=ld_trace if optional else 0,
+                   ld_bias=768 if optional else 0, **c.slot, **c.store)
     return c
+
+
+def arm_case(torch, kv, DH, B=5, Lmax=24, R=3, klen0=(1, 11, 16), lens=(9, 16, 12), **kw):
+    """case() for commu_decode_arm: images of CTX_ROWS rows, sequence heads of CTX_ROWS words.  lens: the records' length
+    words; the default leaves two entries room for Bars on both sides of it and gives one the whole head."""
+    return case(torch, kv, DH, klen0, lens, False, B=B, Lmax=Lmax, R=R, **kw)
 
 
 def snapshot(c):
@@ -92,31 +161,12 @@ def stage_jobs(c, jobs, variates):
 
 
 def arm_expected(c, before, jobs, variates):
-    """What the launch must leave, from the snapshot before it: jobs outside the ranges are skipped."""
+    """What the launch of a case (either launch's) must leave, from the snapshot before it: arm_restated on its operands."""
     import torch
-    exp = {k: v.copy() for k, v in before.items()}
     store = {k: v.cpu().numpy() for k, v in c.store.items()}
     images = [t.view(torch.uint8).cpu().numpy() for t in c.image]
-    for j, (s, e) in enumerate(jobs):
-        if not (0 <= s < c.B and 0 <= e < c.R):
-            continue
-        n = min(max(int(store["e_klen0"][e]), 0), min(CTX_ROWS, c.Lmax))
-        for i, im in enumerate(images):
-            exp[f"cache{i}"][:, s, :, :n] = im[:, e, :, :n]
-        exp["klen"][s] = n
-        exp["state"][s] = store["e_state"][e]
-        exp["seq"][s, :CTX_ROWS] = store["e_seq"][e]
-        exp["chord_tok"][s] = store["e_chord_tok"][e]
-        exp["chord_pos"][s] = store["e_chord_pos"][e]
-        exp["wrong"][s] = 0
-        exp["utable"][s] = np.asarray(variates, dtype=np.float32)[j]
-        if "seq_logp" in exp:
-            exp["seq_logp"][s] = np.nan
-            exp["trace"][s] = 0
-        for name, (twin, _, _) in OPTIONAL.items():
-            if name in exp:
-                exp[name][s] = store[twin][e]
-    return exp
+    return arm_restated(before, store, images, jobs, variates, c.B, c.R, c.Lmax, c.img_rows, c.ld_head, ring=c.ring,
+                        grid_rows=c.grid_rows, whole_head=not c.primed)
 
 
 def same_bits(a, b):

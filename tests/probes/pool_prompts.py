@@ -1,5 +1,5 @@
 """What per-request prompts cost and buy in the request pool (BatchedGenerator.generate_pool with PoolRequest(prompt=),
-csrc/decode_arm_primed.hip): the bench model's geometry (L6 D512 H8, d_head 64), everything INTERLEAVED in one process.
+csrc/decode_arm.hip): the bench model's geometry (L6 D512 H8, d_head 64), everything INTERLEAVED in one process.
 
   arm       the arm launch alone on synthetic operands: 1, 16 and 64 jobs with images of 16, 256 and 1000 rows, bf16 and
             fp8 -- commu_decode_arm_primed (one workgroup per (layer, head, job, chunk of rows)) against commu_decode_arm (one

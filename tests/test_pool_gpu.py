@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+import form_contract as FC
 import pool_contract as PC
 
 pytestmark = pytest.mark.gpu
@@ -35,12 +36,20 @@ def test_arm_launch_alone(kv, DH):
     (skipped, the third job done); every optional pointer null."""
     c = PC.arm_case(torch, kv, DH)
     before, after = _launch_and_compare(c, JOBS, 1)
+    e_seq = c.store["e_seq"].cpu().numpy()
     for s, e in JOBS:          # (what arm_expected states, spelled out for the caches once more)
         n = c.klen0[e]
         for i in range(len(c.cache)):
             assert (after[f"cache{i}"][:, s, :, n:] == PC.NAN_BYTE).all()
             assert not (after[f"cache{i}"][:, s, :, :n] == PC.NAN_BYTE).all()
         assert after["klen"][s] == n and not after["wrong"][s].any() and np.isnan(after["seq_logp"][s]).all()
+        # the form state: the case plants Bars on both sides of the entry's length word (9 and 12 of 16 head words), so
+        # bar_at holds at least two Bars and fewer than the head has; the whole head is copied all the same
+        bars = [i for i in range(PC.CTX_ROWS) if e_seq[e, i] == PC.BAR]
+        below = [i for i in bars if i < c.lens[e]]
+        assert 2 <= len(below) < len(bars)
+        assert after["form_state"][s, FC.BAR_AT:FC.BAR_AT + len(bars)].tolist() == below + [0] * (len(bars) - len(below))
+        assert after["form_tok"][s] == -1 and PC.same_bits(after["seq"][s, :PC.CTX_ROWS], e_seq[e])
     for s in (1, 2):
         for k in after:
             assert PC.same_bits(after[k][:, s] if k.startswith("cache") else after[k][s],
@@ -63,6 +72,47 @@ def test_arm_launch_on_a_wrapped_ring(kv):
     img = c.image[0].view(torch.uint8).cpu().numpy()
     assert PC.same_bits(after["cache0"][:, 3, :, :11], img[:, 1, :, :11])
     assert (after["cache0"][:, 3, :, 11:] == PC.NAN_BYTE).all()
+
+
+@pytest.mark.parametrize("kv", ["bf16", "fp8"])
+def test_arm_launch_with_a_trace_twin(kv):
+    """commu_decode_arm honours e_trace as the primed launch does: with the twin the armed slots' trace rows are the
+    entries', without it they are zero; the idle slots keep their sentinel."""
+    c = PC.arm_case(torch, kv, 32, e_trace=True, seed=3)
+    before, after = _launch_and_compare(c, JOBS, 5)
+    e_trace = c.store["e_trace"].cpu().numpy()
+    for s, e in JOBS:
+        assert e_trace[e].any() and PC.same_bits(after["trace"][s], e_trace[e])
+    assert PC.same_bits(after["trace"][[1, 2]], before["trace"][[1, 2]])
+    zeroed = PC.arm_case(torch, kv, 32, seed=3)
+    assert "e_trace" not in zeroed.store and zeroed.args.e_trace is None
+    before, after = _launch_and_compare(zeroed, JOBS, 5)
+    assert not after["trace"][[0, 3, 4]].any() and PC.same_bits(after["trace"][[1, 2]], before["trace"][[1, 2]])
+
+
+def test_arm_refuses_the_primed_geometry():
+    """On a good block of commu_decode_arm, ring = 1 and grid_rows = 3 each return -22 and launch nothing: every slot array
+    and cache byte is what it was; afterwards the good block returns 0."""
+    from commu_amd import _lib
+    from commu_amd.ops import _s
+    import ctypes as C
+    lib = _lib.load()
+    c = PC.arm_case(torch, "bf16", 32)
+    PC.stage_jobs(c, JOBS, np.zeros((len(JOBS), c.ld_u), dtype=np.float32))
+    before = PC.snapshot(c)
+    c.args.njobs = len(JOBS)
+    assert c.args.ring == 0 and c.args.grid_rows == 0
+    c.args.ring = 1
+    assert lib.commu_decode_arm(C.byref(c.args), _s()) == -22
+    c.args.ring, c.args.grid_rows = 0, 3
+    assert lib.commu_decode_arm(C.byref(c.args), _s()) == -22
+    c.args.grid_rows = 0
+    torch.cuda.synchronize()
+    after = PC.snapshot(c)
+    assert all(PC.same_bits(before[k], after[k]) for k in before)
+    assert lib.commu_decode_arm(C.byref(c.args), _s()) == 0          # (the block itself was good)
+    torch.cuda.synchronize()
+    assert not PC.same_bits(PC.snapshot(c)["klen"], before["klen"])
 
 
 # ---------------------------------------------------------------------------------------------- end to end

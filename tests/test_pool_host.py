@@ -139,6 +139,35 @@ def test_arm_args_abi():
     assert lib.commu_decode_arm(C.byref(a), None) == -22
 
 
+def test_both_arm_launches_take_one_argument_block():
+    """DecodeArmPrimedArgs is DecodeArmArgs under its own name: the same _fields_ and size, the library's two *_args_bytes()
+    agree; ring and grid_rows sit directly behind image[4] and e_trace directly behind trace (offsets and names), the
+    image's row count is ctx_rows, the form's four fields stay last; an instance of either class passes for either entry
+    point, and 0 jobs return 0 before the geometry -- ring, grid_rows -- is looked at."""
+    from commu_amd import _lib
+    lib = _lib.load()
+    A, P = _lib.DecodeArmArgs, _lib.DecodeArmPrimedArgs
+    assert issubclass(P, A) and P.__name__ == "DecodeArmPrimedArgs"
+    assert list(P._fields_) == list(A._fields_) and C.sizeof(P) == C.sizeof(A)
+    assert lib.commu_decode_arm_args_bytes() == lib.commu_decode_arm_primed_args_bytes() == C.sizeof(A)
+    names = [n for n, _ in A._fields_]
+    i, t = names.index("image"), names.index("trace")
+    assert names[i - 2:i + 4] == ["row_bytes", "cache", "image", "ring", "grid_rows", "klen"]
+    assert names[t - 1:t + 3] == ["seq_logp", "trace", "e_trace", "ld_trace"]
+    assert names[-4:] == ["form_ctl", "e_form", "form_state", "form_tok"]
+    assert "ctx_rows" in names and "img_rows" not in names and len(names) == len(set(names))
+    ptr = C.sizeof(C.c_void_p)
+    assert A.ring.offset == A.image.offset + 4 * ptr and A.grid_rows.offset == A.ring.offset + 4
+    assert A.klen.offset == A.ring.offset + 8 and A.e_trace.offset == A.trace.offset + ptr
+    assert A.ld_trace.offset == A.e_trace.offset + ptr and C.sizeof(A) == A.form_tok.offset + ptr
+    for cls in (A, P):
+        a = _lib.struct_args(cls, njobs=0, B=2, Rcap=2, ring=1, grid_rows=3)
+        assert a.e_trace is None and a.struct_bytes == C.sizeof(A)
+        assert lib.commu_decode_arm(C.byref(a), None) == 0 and lib.commu_decode_arm_primed(C.byref(a), None) == 0
+        a.struct_bytes += 8
+        assert lib.commu_decode_arm(C.byref(a), None) == -22 and lib.commu_decode_arm_primed(C.byref(a), None) == -22
+
+
 # ---------------------------------------------------------------------------------------------- command line
 def _cli():
     import importlib.util

@@ -80,6 +80,55 @@ def test_restatement_on_a_ring_by_hand():
     assert exp["klen"][1] == 2 and exp["cache1"][0, 1, 0].tolist() == [[101, 102], [103, 104], [0x7F, 0x7F]]
 
 
+WORDS = ["order_ctl", "voice_ctl", "density_ctl", "interval_ctl", "onset_ctl", "guide_ctl", "art_ctl", "form_ctl"]
+
+
+def _tiny_form(length):
+    """_tiny with a sequence head of 8 words that holds Bars (token 2) at 1, 3, 6 and 7, the eight per-slot rule words with
+    their twins (entry values 31 .. 38), the form state rows and the replay tokens."""
+    import form_contract as FC
+    before, store, images = _tiny(2, length)
+    before["seq"] = np.full((2, 10), -7, dtype=np.int32)
+    store["e_seq"] = np.array([[0, 2, 11, 2, 12, 13, 2, 2]], dtype=np.int32)
+    for i, name in enumerate(WORDS):
+        before[name] = np.full(2, -7, dtype=np.int32)
+        store[PC.OPTIONAL[name][0]] = np.array([31 + i], dtype=np.int32)
+    before["form_state"] = np.full((2, FC.NS), -7, dtype=np.int32)
+    before["form_tok"] = np.full(2, -7, dtype=np.int32)
+    return before, store, images
+
+
+def _form_row(bars):
+    """A form state row by hand: active, cursor, end, k, row 0, g -1, two reserved 0, then bar_at zero-padded to 64."""
+    return [0, 0, 0, 0, 0, -1, 0, 0] + list(bars) + [0] * (64 - len(bars))
+
+
+def test_restatement_of_the_rule_words_and_the_form_state_by_hand():
+    """Length word 5 of a head with Bars at 1, 3, 6, 7: bar_at is [1, 3] in BOTH launches -- the primed one copies 5 words
+    of the head and leaves the rest, the unprimed one all 8 --; every rule word is the entry's, form_tok -1, the idle slot
+    keeps every sentinel.  A length word beyond ld_head records all four Bars, 0 and a negative one none; a length word
+    of 2 stops before the Bar at 3."""
+    for whole_head, seq in ((False, [0, 2, 11, 2, 12, -7, -7, -7, -7, -7]), (True, [0, 2, 11, 2, 12, 13, 2, 2, -7, -7])):
+        before, store, images = _tiny_form(5)
+        exp = PC.arm_restated(before, store, images, [(1, 0)], [[0.1, 0.2, 0.3]], 2, 1, 4, 3, 8, whole_head=whole_head)
+        assert exp["seq"].tolist() == [[-7] * 10, seq]
+        assert exp["form_state"][1].tolist() == _form_row([1, 3]) and (exp["form_state"][0] == -7).all()
+        assert exp["form_tok"].tolist() == [-7, -1]
+        assert [exp[name].tolist() for name in WORDS] == [[-7, 31 + i] for i in range(8)]
+        assert exp["klen"].tolist() == [-7, 2] and exp["trace"].tolist() == [[-7, -7], [41, 42]]
+    assert PC.same_bits(PP.arm_primed_expected(before, store, images, [(1, 0)], [[0.1, 0.2, 0.3]], 2, 1, 4, 3, 8)["seq"],
+                        np.array([[-7] * 10, [0, 2, 11, 2, 12, -7, -7, -7, -7, -7]], dtype=np.int32))
+    for length, bars in ((50, [1, 3, 6, 7]), (8, [1, 3, 6, 7]), (7, [1, 3, 6]), (2, [1]), (1, []), (0, []), (-3, [])):
+        before, store, images = _tiny_form(length)
+        for whole_head in (False, True):
+            exp = PC.arm_restated(before, store, images, [(0, 0)], [[0, 0, 0]], 2, 1, 4, 3, 8, whole_head=whole_head)
+            assert exp["form_state"][0].tolist() == _form_row(bars), (length, whole_head)
+            assert exp["form_tok"].tolist() == [-1, -7] and (exp["form_state"][1] == -7).all()
+    before, store, images = _tiny_form(5)
+    exp = PC.arm_restated(before, store, images, [(2, 0), (0, 1)], [[0] * 3] * 2, 2, 1, 4, 3, 8, whole_head=True)
+    assert all(PC.same_bits(exp[k], before[k]) for k in before)
+
+
 def test_pool_request_prompt_defaults():
     import commu_amd.generate as G
     r = G.PoolRequest(PC.META, PC.data(), 1, 0.9, 8)
