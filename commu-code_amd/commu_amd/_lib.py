@@ -158,6 +158,10 @@ PROTOTYPES = {
     "commu_layernorm_bwd_reduce": [c_p, c_i, c_i, c_p, c_p, c_p, c_p],
     "commu_ce_fwd": [c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_p],
     "commu_ce_bwd": [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p],
+    "commu_ce_fwd_opts": [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_f, c_p],
+    "commu_ce_bwd_opts": [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p],
+    "commu_nll_by_class_blocks": [c_i],
+    "commu_nll_by_class": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p],
     "commu_masked_mean": [c_p, c_p, c_i, c_i, c_f, c_p, c_p, c_p, c_p],
     "commu_loss_grad": [c_p, c_i, c_i, c_p, c_f, c_p, c_p],
     "commu_masked_mean_groups": [c_p, c_p, c_i, c_i, c_f, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
@@ -270,13 +274,15 @@ PROTOTYPES = {
     "commu_layernorm_fwd_f32": [c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_f, c_p],
     "commu_layernorm_bwd_f32": [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_i, c_p],
     "commu_ce_bwd_f32": [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p],
+    "commu_ce_fwd_opts_f32": [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_f, c_p],
+    "commu_ce_bwd_opts_f32": [c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p],
     "commu_embed_bwd_f32": [c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_f, c_f, C.c_uint, c_p],
     "commu_dropout_f32": [c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_f, C.c_uint, c_p],
     "commu_hip_version": [],
 }
 _RESTYPE = {"commu_decode_tail_pack_bytes": C.c_longlong, "commu_attn_pf_bytes": C.c_longlong, "commu_hip_version": C.c_char_p, "commu_attn_p_scratch_elems": C.c_longlong,
             "commu_gemm_nt_signbits_words": C.c_longlong, "commu_pack_batch": C.c_longlong}
-_NOCHECK = {"commu_layernorm_bwd_nblocks", "commu_colsum_slabs", "commu_embed_bwd_ws_rows", "commu_hip_version", "commu_attn_bwd_qrows", "commu_attn_fwd_generation", "commu_attn_bwd_kv_generation", "commu_colsum_slab_pass", "commu_gemm_tn_grouped_slices", "commu_gemm_tn_grouped_slices_budget", "commu_attn_band_slabs", "commu_attn_band_pairs",
+_NOCHECK = {"commu_layernorm_bwd_nblocks", "commu_nll_by_class_blocks", "commu_colsum_slabs", "commu_embed_bwd_ws_rows", "commu_hip_version", "commu_attn_bwd_qrows", "commu_attn_fwd_generation", "commu_attn_bwd_kv_generation", "commu_colsum_slab_pass", "commu_gemm_tn_grouped_slices", "commu_gemm_tn_grouped_slices_budget", "commu_attn_band_slabs", "commu_attn_band_pairs",
             "commu_forcing_state_ints", "commu_form_state_ints", "commu_form_src_max", "commu_decode_tail_supported", "commu_decode_tail_sync_words", "commu_decode_tail_sync_words_for", "commu_decode_tail_pack_bytes", "commu_attn_p_scratch_elems", "commu_gemm_nt_signbits_words", "commu_pack_batch", "commu_attn_pf_bytes",
             "commu_decode_prefix_chunk", "commu_decode_prefix_group", "commu_sample_args_bytes", "commu_decode_loop_args_bytes",
             "commu_decode_arm_args_bytes", "commu_decode_arm_primed_args_bytes", "commu_decode_arm_primed_chunk_rows"}

@@ -148,6 +148,37 @@ def chord_pitch_classes(token: int) -> frozenset:
     return frozenset((root + i) % 12 for i in _QUAL_INTERVALS[_QUALS[(int(token) - 195) % len(_QUALS)]])
 
 
+# ---- token families of the training-side reports (per-family validation NLL): family id -> name
+TOKEN_FAMILIES = ("pad_eos_bar", "position", "chord", "velocity", "pitch", "duration", "meta", "other")
+
+
+def token_family_ranges() -> Dict[str, range]:
+    """Half-open id range of every family but "other", from the offsets of this package: the chord vocabulary and the
+    position / meta bases above, the note ranges of midi_inferrer.TOKEN_OFFSET."""
+    from .midi_inferrer import TOKEN_OFFSET as T
+    chord_lo, chord_hi = min(CHORD_VOCAB.values()), max(CHORD_VOCAB.values()) + 1
+    return {"pad_eos_bar": range(0, T.PITCH), "pitch": range(T.PITCH, T.NOTE_VELOCITY),
+            "velocity": range(T.NOTE_VELOCITY, chord_lo), "chord": range(chord_lo, chord_hi),
+            "duration": range(T.NOTE_DURATION, POSITION_BASE),
+            "position": range(POSITION_BASE, POSITION_BASE + POSITION_RESOLUTION),
+            # (the last meta field: its "unknown" token, then one token per value)
+            "meta": range(min(_BASE.values()), _BASE[META_FIELDS[-1]] + 1 + len(_MAPS[META_FIELDS[-1]]))}
+
+
+def class_of_token(vocab_size: int = 729) -> List[int]:
+    """Family id (index into TOKEN_FAMILIES) of every token id below vocab_size; ids no range holds are "other"."""
+    table = [TOKEN_FAMILIES.index("other")] * vocab_size
+    seen = [0] * vocab_size
+    for name, ids in token_family_ranges().items():
+        for t in ids:
+            if t < vocab_size:
+                table[t] = TOKEN_FAMILIES.index(name)
+                seen[t] += 1
+    if max(seen, default=0) > 1:
+        raise ValueError("token family ranges overlap")
+    return table
+
+
 def chord_token_components(chord_progression: Sequence[str], time_signature: str) -> Dict[str, List[int]]:
     """container.py:37-61: one (token, position) per chord CHANGE (and per bar start).  The position of a change
     inside a bar reproduces the reference's decimal-string arithmetic (e.g. 1/6 of a bar -> 432 + 21)."""

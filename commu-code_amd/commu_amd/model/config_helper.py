@@ -87,6 +87,10 @@ def train(cfg):            # commu/model/config_helper.py:18-34
     cfg.TRAIN.log_interval = 100
     cfg.TRAIN.eval_interval = 1000
     cfg.TRAIN.weight_decay = 0.0
+    # (not in the reference) loss options of the training step and the per-family validation report; defaults: off
+    cfg.TRAIN.label_smoothing = 0.0
+    cfg.TRAIN.z_loss = 0.0
+    cfg.TRAIN.report_families = False
     return cfg
 
 

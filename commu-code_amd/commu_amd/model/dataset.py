@@ -252,18 +252,35 @@ class ComMUDataset:
     valid_data = property(lambda self: self._as_list("valid"))
     test_data = property(lambda self: self._as_list("test"))
 
-    def get_iterator(self, batch_size, bptt, device, split="train", do_shuffle=True, seed=None):
+    def get_iterator(self, batch_size, bptt, device, split="train", do_shuffle=True, seed=None, start=None):
         """Returns a callable that starts the (endless, when shuffling) batch stream:
-        (data [T,B] int64, target [T,B] int64, reset_mem [B] bool, number of non-pad targets)."""
+        (data [T,B] int64, target [T,B] int64, reset_mem [B] bool, number of non-pad targets).
+        The callable's `position` = {"epoch", "index"} names the batch that follows the last one handed out (the prefetched
+        ones do not count): what a checkpoint stores.  start=(epoch, index), with shuffling: the stream begins there -- the
+        shuffles of the epochs before it are replayed from `seed` (each permutes the order the last one left), the epoch is
+        scheduled again and the batches before `index` are skipped; from there on it is the stream an uninterrupted run
+        hands out."""
         if split not in self._corpus:
             raise NotImplementedError
         corpus = self._corpus[split]
         pad = self._vocab.pad_id
+        if start is not None:
+            start = (int(start[0]), int(start[1]))
+            if not do_shuffle or start[0] < 0 or start[1] < 0:
+                raise ValueError(f"start={start}: (epoch >= 0, index >= 0) of a shuffled stream expected")
+        position = {"epoch": start[0] if start else 0, "index": start[1] if start else 0}
 
         def iterator():
             rng = np.random.RandomState(seed) if do_shuffle else None
             order = np.arange(len(corpus))
-            state = {"t": 0, "plan": None}
+            state = {"t": 0, "plan": None, "epoch": -1}
+            if start is not None:
+                for _ in range(start[0] + 1):
+                    rng.shuffle(order)
+                plan = schedule_epoch(corpus.lens, order, batch_size, bptt)
+                if start[1] > plan[0].shape[0]:
+                    raise ValueError(f"start={start}: epoch {start[0]} of this corpus and seed has {plan[0].shape[0]} batches")
+                state.update(plan=plan, t=start[1], epoch=start[0])
 
             def produce(bufs):
                 while state["plan"] is None or state["t"] >= state["plan"][0].shape[0]:
@@ -272,20 +289,23 @@ class ComMUDataset:
                     if do_shuffle:
                         rng.shuffle(order)                        # in place, epoch after epoch (dataset.py:142,175)
                     state["plan"], state["t"] = schedule_epoch(corpus.lens, order, batch_size, bptt), 0
+                    state["epoch"] += 1
                 seq, pos, cnt, reset = state["plan"]
                 t = state["t"]
                 ntok = gather_batch(corpus, seq[t], pos[t], cnt[t], bptt, bufs[0].numpy(), bufs[1].numpy(), pad)
                 bufs[2].numpy()[:] = reset[t]
                 state["t"] = t + 1
-                return ntok
+                return ntok, state["epoch"], t + 1
             shapes = [((bptt, batch_size), torch.long), ((bptt, batch_size), torch.long), ((batch_size,), torch.bool)]
             pf = _Prefetcher(produce, shapes, device)
             try:
-                for (data, target, reset), ntok in pf:
+                for (data, target, reset), (ntok, epoch, index) in pf:
+                    position["epoch"], position["index"] = epoch, index
                     yield data, target, reset, ntok
             finally:
                 pf.close()
 
+        iterator.position = position
         return iterator
 
     def eval_iterator(self, batch_size, bptt, device, split="valid", local_rank=0, world_size=0):

@@ -119,7 +119,17 @@ class _Saved:
     """Activations of one forward call kept for its backward (the fp32 training mode leaves qs / hbits / zff unset)."""
     __slots__ = ("T", "M", "B", "tokens", "target", "reset", "h", "cat", "qkv", "rd", "vec", "lse", "qs", "z1", "mu1",
                  "rs1", "a", "hid", "hbits", "zff", "z2", "mu2", "rs2", "pd", "hL", "logits", "ce_lse", "same_length", "mem_len",
-                 "p", "patt", "seed")
+                 "p", "patt", "seed", "loss_opts")
+
+
+def check_loss_options(label_smoothing=0.0, z_loss=0.0):
+    """(eps, zeta) as floats; ValueError unless 0 <= eps < 1 and 0 <= zeta < inf."""
+    eps, zeta = float(label_smoothing), float(z_loss)
+    if not 0.0 <= eps < 1.0:
+        raise ValueError(f"label_smoothing {label_smoothing} must be in [0, 1)")
+    if not 0.0 <= zeta < float("inf"):
+        raise ValueError(f"z_loss {z_loss} must be a finite number >= 0")
+    return eps, zeta
 
 
 class _XLLoss(torch.autograd.Function):
@@ -207,6 +217,23 @@ class MemTransformerLM(nn.Module):
         # fp32 training (opt-in): a gradient-enabled forward and its backward in the reference's arithmetic -- fp32 master
         # weights (no shadows, no padding), activations, memory and every backward contraction (csrc/train_f32.hip)
         self.fp32_training = False
+        # loss options (opt-in, not in the reference): label smoothing eps in [0, 1) and z-loss zeta >= 0 of a gradient-enabled
+        # forward -- loss = (1 - eps) nll + eps (lse - mean of the V logits) + zeta lse^2, in the fused loss kernels
+        # (commu_ce_fwd_opts / commu_ce_bwd_opts).  At the defaults the step launches commu_ce_fwd / commu_ce_bwd; a no-grad
+        # forward (evaluate) returns the plain nll whatever the options.
+        self.loss_options = {"label_smoothing": 0.0, "z_loss": 0.0}
+
+    def _loss_opts(self):
+        """(eps, zeta) of a gradient pass, None at the defaults (the plain kernels)."""
+        eps, zeta = check_loss_options(**getattr(self, "loss_options", {}))
+        return None if eps == 0.0 and zeta == 0.0 else (eps, zeta)
+
+    def loss_kernel_names(self):
+        """The loss entry points (forward, backward) a gradient-enabled forward of this model launches now."""
+        tail = "_f32" if getattr(self, "fp32_training", False) else ""
+        if self._loss_opts() is None:
+            return "commu_ce_fwd", "commu_ce_bwd" + tail
+        return "commu_ce_fwd_opts" + tail, "commu_ce_bwd_opts" + tail
 
     # ------------------------------------------------------------------ reference API
     def reset_length(self, tgt_len, mem_len):                            # model.py:494-496
@@ -351,9 +378,14 @@ class MemTransformerLM(nn.Module):
         if target is None:
             return logits.view(T, B, V), new_mems, extra
         tgt = target.contiguous().view(-1).to(dev)
-        nll, ce_lse = ops.ce_fwd(logits, tgt, V)                                           # :689-691 (fp32 log-softmax + gather)
+        opts = self._loss_opts() if save else None
+        if opts is None:
+            nll, ce_lse = ops.ce_fwd(logits, tgt, V)                                       # :689-691 (fp32 log-softmax + gather)
+        else:          # the loss with options is what the gradient pass returns; the plain nll stays readable for the logs
+            nll, plain, ce_lse = ops.ce_fwd_opts_f32(logits, tgt, V, *opts)
+            self.__dict__["last_nll"] = plain.view(T, B)
         if save:
-            sv.hL, sv.logits, sv.ce_lse, sv.target = h_out, logits, ce_lse, tgt
+            sv.hL, sv.logits, sv.ce_lse, sv.target, sv.loss_opts = h_out, logits, ce_lse, tgt, opts
         return nll.view(T, B), new_mems, extra
 
     def _update_mems_f32(self, hids, mems, M, T, B):
@@ -404,7 +436,11 @@ class MemTransformerLM(nn.Module):
             ones = fl["ones_f32"] = torch.ones(max(TB, K * B), device=dev, dtype=F32)
         E = self.word_emb.emb_layers[0].weight
         gE = gv("word_emb.emb_layers.0.weight", (V, D))
-        dlogits = ops.ce_bwd_f32(sv.logits, sv.target, sv.ce_lse, dloss.reshape(-1).to(F32).contiguous(), V)
+        g = dloss.reshape(-1).to(F32).contiguous()
+        if sv.loss_opts is None:
+            dlogits = ops.ce_bwd_f32(sv.logits, sv.target, sv.ce_lse, g, V)
+        else:
+            dlogits = ops.ce_bwd_opts_f32(sv.logits, sv.target, sv.ce_lse, g, V, *sv.loss_opts)
         ops.gemm_f32(dlogits, sv.hL, out=gE, ta=True, tb=False, accumulate=True)           # output layer (tied weight)
         ops.colsum_f32(dlogits, gv("crit.out_layers.0.bias", (V,)), ones)
         dy = ops.gemm_f32(dlogits, E, tb=False)
@@ -839,9 +875,14 @@ class MemTransformerLM(nn.Module):
         if want_logits:
             return logits.view(T, B, VPAD)[:, :, :V], new_mems, (kv_out if want_kv else None)
         tgt = target.contiguous().view(-1)
-        nll, ce_lse = ops.ce_fwd(logits, tgt, V)
+        opts = self._loss_opts() if need_grad else None
+        if opts is None:
+            nll, ce_lse = ops.ce_fwd(logits, tgt, V)
+        else:          # the loss with options is what the gradient pass returns; the plain nll stays readable for the logs
+            nll, plain, ce_lse = ops.ce_fwd_opts(logits, tgt, V, *opts)
+            self.__dict__["last_nll"] = plain.view(T, B)
         if need_grad:
-            sv.hL, sv.logits, sv.ce_lse, sv.target = h_out, logits, ce_lse, tgt
+            sv.hL, sv.logits, sv.ce_lse, sv.target, sv.loss_opts = h_out, logits, ce_lse, tgt, opts
             if getattr(self, "keep_saved", False):       # tests read the saved activations (e.g. the ReLU gates) of the last call
                 self.__dict__["last_saved"] = sv
         return nll.view(T, B), new_mems, sv
@@ -973,7 +1014,10 @@ class MemTransformerLM(nn.Module):
         spec = self._spec if pad else (lambda kind: None)
         sh = fl["shadow"]
         g = dloss.reshape(-1).to(F32)
-        dlogits = ops.ce_bwd(sv.logits, sv.target, sv.ce_lse, g, V)             # [TB, 768] bf16, pad cols 0
+        if sv.loss_opts is None:
+            dlogits = ops.ce_bwd(sv.logits, sv.target, sv.ce_lse, g, V)         # [TB, 768] bf16, pad cols 0
+        else:
+            dlogits = ops.ce_bwd_opts(sv.logits, sv.target, sv.ce_lse, g, V, *sv.loss_opts)
         keep.append(dlogits)
         # every final column-sum pass of the step (bias, LayerNorm-parameter, r_w_bias / r_r_bias gradients) runs as ONE
         # launch at the end of the pass; only the slab passes over the large bf16 operands are issued where they arise

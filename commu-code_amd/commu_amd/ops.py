@@ -573,6 +573,43 @@ def ce_bwd(logits, target, lse, g, V, dlogits=None):
     return dlogits
 
 
+def ce_fwd_opts(logits, target, V, label_smoothing=0.0, z_loss=0.0, entry="commu_ce_fwd_opts"):
+    """(loss, nll, lse) [rows] of the loss with options: loss = (1 - eps) nll + eps (lse - mean_j l_j) + zeta lse^2 over the V
+    real tokens; nll and lse are ce_fwd's."""
+    rows = logits.shape[0]
+    loss, nll, lse = (torch.empty(rows, device=logits.device, dtype=F32) for _ in range(3))
+    call(entry, _p(logits), logits.stride(0), _p(target), _p(loss), _p(nll), _p(lse), rows, V,
+         float(label_smoothing), float(z_loss), _s())
+    return loss, nll, lse
+
+
+def ce_bwd_opts(logits, target, lse, g, V, label_smoothing=0.0, z_loss=0.0, dlogits=None):
+    """bf16 dlogits [rows, ld] of ce_fwd_opts' loss weighted by g [rows] (lse: the forward's); pad columns zero."""
+    rows = logits.shape[0]
+    if dlogits is None:
+        dlogits = torch.empty(rows, logits.stride(0), device=logits.device, dtype=BF16)
+    call("commu_ce_bwd_opts", _p(logits), logits.stride(0), _p(target), _p(lse), _p(g), _p(dlogits), dlogits.stride(0),
+         rows, V, float(label_smoothing), float(z_loss), _s())
+    return dlogits
+
+
+def nll_by_class(nll, target, class_of_token, n_classes, pad=-1):
+    """(sum fp32 [n_classes], count int32 [n_classes]) of nll over the rows by the class of their target token
+    (class_of_token: int32 [V] on the device); rows whose target is `pad` are left out.  Deterministic (two passes)."""
+    rows = nll.numel()
+    dev = nll.device
+    assert nll.dtype == F32 and nll.is_contiguous() and target.dtype == torch.int64 and target.is_contiguous()
+    assert target.numel() == rows and class_of_token.dtype == torch.int32 and class_of_token.is_contiguous()
+    nblk = call("commu_nll_by_class_blocks", rows)
+    part_sum = torch.empty(nblk, n_classes, device=dev, dtype=F32)
+    part_cnt = torch.empty(nblk, n_classes, device=dev, dtype=torch.int32)
+    out_sum = torch.empty(n_classes, device=dev, dtype=F32)
+    out_cnt = torch.empty(n_classes, device=dev, dtype=torch.int32)
+    call("commu_nll_by_class", _p(nll), _p(target), _p(class_of_token), class_of_token.numel(), n_classes, int(pad), rows,
+         _p(part_sum), _p(part_cnt), nblk, _p(out_sum), _p(out_cnt), _s())
+    return out_sum, out_cnt
+
+
 def mems_update(hids, mems, out, beg):
     """K9: out[l] = cat(mems[l], hids[l])[beg:]  with hids [L+1, T*B, Dp], mems [L+1, M, B, Dp] (layer stride free),
     out [L+1, n, B, Dp] contiguous, 0 <= beg < M."""
@@ -589,6 +626,14 @@ def mems_update(hids, mems, out, beg):
 def masked_mean(nll, target, pad, scale, ws_sum, ws_cnt, out):
     call("commu_masked_mean", _p(nll), _p(target), nll.numel(), pad, scale, _p(ws_sum), _p(ws_cnt), _p(out), _s())
     return out
+
+
+def masked_sum(nll, target, pad):
+    """fp32 [1]: the sum of nll over the targets that are not `pad` (commu_masked_mean's sum workspace; its mean and count
+    go to scratch) -- the plain-NLL sum of the logging window when the step trains on a loss with options."""
+    ws = torch.empty(3, device=nll.device, dtype=F32)
+    call("commu_masked_mean", _p(nll), _p(target), nll.numel(), int(pad), 1.0, _p(ws), ws.data_ptr() + 4, ws.data_ptr() + 8, _s())
+    return ws[:1]
 
 
 def loss_grad(target, pad, ws_cnt, scale, g):
@@ -1512,6 +1557,21 @@ def ce_bwd_f32(logits, target, lse, g, V):
     dl = torch.empty(rows, V, device=logits.device, dtype=F32)
     call("commu_ce_bwd_f32", _p(logits), _f32_2d(logits, "logits"), _p(target), _p(lse), _p(g), _p(dl), V, rows, V, _s())
     return dl
+
+
+def ce_bwd_opts_f32(logits, target, lse, g, V, label_smoothing=0.0, z_loss=0.0, dlogits=None):
+    """fp32 dlogits [rows, V] of ce_fwd_opts' loss, weighted by g [rows] (dlogits given: columns [V, stride) are zeroed)."""
+    rows = logits.shape[0]
+    if dlogits is None:
+        dlogits = torch.empty(rows, V, device=logits.device, dtype=F32)
+    call("commu_ce_bwd_opts_f32", _p(logits), _f32_2d(logits, "logits"), _p(target), _p(lse), _p(g), _p(dlogits),
+         _f32_2d(dlogits, "dlogits"), rows, V, float(label_smoothing), float(z_loss), _s())
+    return dlogits
+
+
+def ce_fwd_opts_f32(logits, target, V, label_smoothing=0.0, z_loss=0.0):
+    """ce_fwd_opts under the fp32 schedule's entry point (its logits are fp32 like the bf16 schedule's: the same kernels)."""
+    return ce_fwd_opts(logits, target, V, label_smoothing, z_loss, entry="commu_ce_fwd_opts_f32")
 
 
 def embed_bwd_f32(tok, dx, gE, scale, drop_p=0.0, drop_seed=0, order=None):

@@ -110,6 +110,9 @@ class Trainer:
 
     def step(self, data, target, reset_mems, batch_token_num):
         """train.py:131-169 for one batch; returns the summed micro-batch loss (device tensor)."""
+        if self._graphs is not None and self.model._loss_opts() != self._graph_state["loss_opts"]:
+            raise ValueError("model.loss_options changed after the step was captured: they are constants of the hipGraph "
+                             f"(captured {self._graph_state['loss_opts']}, now {self.model._loss_opts()}); build a new Trainer")
         if self.graph_mode and self.graph_failed is None and self._graph_ready(data, reset_mems):
             return self._graph_step(data, target, reset_mems, batch_token_num)
         cfg, model = self.cfg, self.model
@@ -136,6 +139,9 @@ class Trainer:
                 loss, nll_sum = masked_mean_groups(loss, t, self.pad_id, groups)
             else:
                 loss, nll_sum = masked_mean(loss, t, self.pad_id, 1.0 / chunk, with_sum=True)
+            if model._loss_opts() is not None:          # the window logs the plain NLL, not the regularised loss
+                from . import ops
+                nll_sum = ops.masked_sum(model.last_nll.reshape(-1), t.view(-1), self.pad_id)
             if overlap and i == chunk - 1:
                 # gradients are complete once the LAST micro-batch's backward has passed a layer: exchange that
                 # layer's slice while the layers below are still being differentiated
@@ -244,6 +250,8 @@ class Trainer:
                 ops.masked_mean(nll.view(-1), tt, int(self.pad_id), 1.0 / chunk, ws_sum, ws_cnt, out)
                 ops.loss_grad(tt, int(self.pad_id), ws_cnt, 1.0 / chunk, g)
             model._run_backward(sv, g.view(nll.shape))
+            if sv.loss_opts is not None:          # the window logs the plain NLL, not the regularised loss (`nll` here)
+                ws_sum = ops.masked_sum(model.last_nll.reshape(-1), tt, self.pad_id)
             total = out[0] if total is None else total + out[0]
             nll_sums.append(ws_sum)
             mems_out.append(new_mems if mems_in[i] is not None or cfg.TRAIN.mem_length > 0 else None)
@@ -260,7 +268,8 @@ class Trainer:
               "salt": torch.zeros(1, device=dev, dtype=torch.int32),
               "scal": torch.zeros(4, device=dev, dtype=torch.float32),
               "table": self.optimizer.group_table(1.0, 1.0).to(dev),          # the grouped step's form of `scal`
-              "mems": [None if m is None else m.detach().clone() for m in self.mems]}
+              "mems": [None if m is None else m.detach().clone() for m in self.mems],
+              "loss_opts": model._loss_opts()}          # constants of the captured launches (step() refuses a change)
         cur = torch.cuda.current_stream(dev)
         if fl.get("shadow_ready") is not None:                # recorded by the last eager optimiser step: join it here,
             cur.wait_event(fl["shadow_ready"])                # a captured stream must not wait for an outside event
@@ -367,33 +376,65 @@ class Trainer:
         nll = loss_sum / max(tokens, 1.0)
         return nll, gnorm_sum / (steps * self.num_gpus), tokens
 
-    def evaluate_reduced(self, eval_iter):
+    def evaluate_reduced(self, eval_iter, families=None):
         """evaluate() + the token-count / NLL all-reduce of train.py:209-210,264-265 (one packed collective);
-        returns (tokens of all ranks, NLL per token)."""
-        tok, nll = self.evaluate(eval_iter)
-        tok_all, nll_all = self._sum_over_ranks([tok, nll / 10000.0])
+        returns (tokens of all ranks, NLL per token).  families: a dict that receives the per-family report of all ranks
+        ({family: {"nll": per token, "tokens": count}}, see evaluate) from the same collective."""
+        own = {} if families is not None else None
+        tok, nll = self.evaluate(eval_iter, families=own)
+        vals = [tok, nll / 10000.0]
+        if own is not None:
+            vals += [own[k]["nll_sum"] / 10000.0 for k in own] + [own[k]["tokens"] for k in own]
+        red = self._sum_over_ranks(vals)
+        tok_all, nll_all = red[0], red[1]
+        if own is not None:
+            n = len(own)
+            for i, k in enumerate(own):
+                cnt = int(red[2 + n + i])
+                families[k] = {"nll": red[2 + i] * 10000.0 / cnt if cnt else float("nan"), "tokens": cnt}
         return int(tok_all), nll_all / (max(tok_all, 1.0) / 10000.0)
 
-    def evaluate(self, eval_iter):
+    def evaluate(self, eval_iter, families=None):
         """train.py:74-110: same_length evaluation with the longer EVALUATE memory."""
-        return evaluate(self.model, self.cfg, eval_iter, self.pad_id)
+        return evaluate(self.model, self.cfg, eval_iter, self.pad_id, families=families)
 
 
 @torch.no_grad()
-def evaluate(model, cfg, eval_iter, pad_id=0):
+def evaluate(model, cfg, eval_iter, pad_id=0, families=None):
     """train.py:74-110 for any model: eval mode, EVALUATE lengths, same_length on; the TRAIN settings restored after.
-    Returns (non-pad target tokens, summed NLL) of this rank's share of the split."""
+    Returns (non-pad target tokens, summed NLL) of this rank's share of the split.
+    families (not in the reference): a dict that receives {family: {"nll_sum", "tokens"}} over the non-pad targets, by the
+    token family of the target (midi_generator.meta.TOKEN_FAMILIES; one commu_nll_by_class launch pair per batch, summed
+    on the device in float64, read once at the end)."""
     model.eval()
     model.reset_length(tgt_len=cfg.EVALUATE.tgt_length, mem_len=cfg.EVALUATE.mem_length)
     model.same_length = True
     total_tok, total_nll = 0, 0.0
     mems = None
+    fam_table = fam_sum = fam_cnt = None
     for data, target, all_reset, ntok in eval_iter():
         if all_reset:
             mems = None
         loss, mems = model(data, target, None, mems)
         total_nll += ntok * float(masked_mean(loss, target, pad_id, 1.0))
         total_tok += ntok
+        if families is not None:
+            from . import ops
+            from .midi_generator.meta import TOKEN_FAMILIES, class_of_token
+            if fam_table is None:
+                fam_table = torch.tensor(class_of_token(model.n_token), dtype=torch.int32, device=loss.device)
+                fam_sum = torch.zeros(len(TOKEN_FAMILIES), dtype=torch.float64, device=loss.device)
+                fam_cnt = torch.zeros(len(TOKEN_FAMILIES), dtype=torch.int64, device=loss.device)
+            s_, c_ = ops.nll_by_class(loss.float().contiguous().view(-1), target.contiguous().view(-1), fam_table,
+                                      len(TOKEN_FAMILIES), pad=pad_id)
+            fam_sum += s_
+            fam_cnt += c_
+    if families is not None:
+        from .midi_generator.meta import TOKEN_FAMILIES
+        sums = [0.0] * len(TOKEN_FAMILIES) if fam_sum is None else fam_sum.tolist()
+        cnts = [0] * len(TOKEN_FAMILIES) if fam_cnt is None else fam_cnt.tolist()
+        for name, s_, c_ in zip(TOKEN_FAMILIES, sums, cnts):
+            families[name] = {"nll_sum": float(s_), "tokens": int(c_)}
     model.reset_length(cfg.TRAIN.tgt_length, cfg.TRAIN.mem_length)
     model.same_length = cfg.MODEL.same_length
     model.train()
@@ -420,13 +461,46 @@ def evaluate_best_checkpoint(path, cfg, vocab, device, eval_iter, reducer=None, 
     return nll / (max(tok, 1.0) / 10000.0), int(tok)
 
 
-def save_checkpoint(path, model, optimizer, vocab, train_step, best_val_loss, scheduler):
+def save_checkpoint(path, model, optimizer, vocab, train_step, best_val_loss, scheduler, data_position=None,
+                    val_families=None):
     """train.py:29-54: same dictionary layout (model = unwrapped state_dict, optimizer in torch.optim.Adam's
-    layout, amp = None) -- loadable by the reference and vice versa."""
-    torch.save({"model": {k: v.detach().float().cpu() for k, v in model.state_dict().items()},
-                "optimizer": optimizer.state_dict() if optimizer is not None else None,
-                "train_step": train_step, "scheduler": scheduler.state_dict(),
-                "best_val_loss": best_val_loss, "vocab": vocab, "amp": None}, path)
+    layout, amp = None) -- loadable by the reference and vice versa.  Two optional keys (not in the reference; absent
+    unless given, ignored by readers that do not know them): "data_position" = stream_key(...) + {"streams": one
+    [seed, epoch, index] per rank} of the training batch stream (the seed its get_iterator was given and its `position`),
+    and "val_families" =
+    the per-family validation report of Trainer.evaluate_reduced."""
+    ck = {"model": {k: v.detach().float().cpu() for k, v in model.state_dict().items()},
+          "optimizer": optimizer.state_dict() if optimizer is not None else None,
+          "train_step": train_step, "scheduler": scheduler.state_dict(),
+          "best_val_loss": best_val_loss, "vocab": vocab, "amp": None}
+    if data_position is not None:
+        ck["data_position"] = data_position
+    if val_families is not None:
+        ck["val_families"] = val_families
+    torch.save(ck, path)
+
+
+def stream_key(world, batch_size, bptt, lens):
+    """What an (epoch, index) of the training batch stream is relative to, beside the stream's seed: the number of ranks,
+    the per-rank batch size, the segment length and the corpus (its sequence lengths, as a count and a CRC)."""
+    import zlib
+    import numpy as np
+    lens = np.ascontiguousarray(lens, dtype=np.int64)
+    return {"world": int(world), "batch_size": int(batch_size), "bptt": int(bptt),
+            "corpus": [int(lens.shape[0]), int(zlib.crc32(lens.tobytes()))]}
+
+
+def resume_position(ck, rank, key):
+    """(stream seed, (epoch, index)) of this rank for get_iterator(seed=, start=) from a checkpoint dictionary, or None: the
+    checkpoint has no "data_position" (written before the key existed), or its stream was scheduled for another number of
+    ranks, batch size, segment length or corpus (`key`: stream_key of this run) -- then the resumed run draws a fresh
+    shuffle from seed + 1000 * rank + train_step, as it always did.  The seed returned is the one the checkpoint's stream
+    was REALLY drawn from, which after such a fresh shuffle is not the run's base seed."""
+    pos = ck.get("data_position")
+    if not pos or any(pos.get(k) != v for k, v in key.items()):
+        return None
+    seed, epoch, index = pos["streams"][rank]
+    return int(seed), (int(epoch), int(index))
 
 
 class _ReferencePickle:
@@ -454,10 +528,11 @@ def read_checkpoint(path, map_location="cpu"):
     return torch.load(path, map_location=map_location, weights_only=False, pickle_module=_ReferencePickle)
 
 
-def load_checkpoint(path, model, optimizer=None, scheduler=None):
+def load_checkpoint(path, model, optimizer=None, scheduler=None, ck=None):
     """Resume from a checkpoint written by save_checkpoint or by the reference (train.py:493-495 reads
-    checkpoint["model"]).  Returns (train_step, best_val_loss)."""
-    ck = read_checkpoint(path)
+    checkpoint["model"]).  Returns (train_step, best_val_loss).  ck: the dictionary, when the caller has read it already."""
+    if ck is None:
+        ck = read_checkpoint(path)
     model.load_state_dict(ck["model"])
     if optimizer is not None and ck.get("optimizer") is not None:
         optimizer.load_state_dict(ck["optimizer"])

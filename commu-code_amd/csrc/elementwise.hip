@@ -692,6 +692,177 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
 }
 
 // ---------------------------------------------------------------------------------------------
+// The loss with options (not in the reference): label smoothing eps in [0, 1) and z-loss zeta >= 0.  Per row, V real tokens,
+//   nll    = lse - l_t                         (written whatever the options: what evaluation and the logs report)
+//   smooth = lse - sum_{j<V} l_j / V           (the cross entropy against the uniform distribution over the V tokens)
+//   loss   = (1 - eps) nll + eps smooth + zeta lse^2
+//   dl_j   = g [(1 + 2 zeta lse) softmax_j - (1 - eps) [j == t] - eps / V],  j < V;  0 in the pad columns
+// The kernels are ce_fwd* / ce_bwd* with one more accumulator (sum l_j, from the sweep that feeds the exponentials) and one
+// more multiply-add per element; max, sum and lse are computed by the same operations in the same order, so eps = zeta = 0
+// gives the plain kernels' bits.
+__device__ __forceinline__ void ce_opts_row_out(const float* __restrict__ p, const int64_t* __restrict__ target,
+                                                float* __restrict__ loss, float* __restrict__ nll,
+                                                float* __restrict__ lse, int row, int V, float l, float sl, float eps,
+                                                float zeta) {
+    lse[row] = l;
+    const long long tg = target[row];          // (outside [0, V): NaN, as ce_fwd)
+    const float n = (tg >= 0 && tg < V) ? l - p[tg] : __builtin_nanf("");
+    nll[row] = n;
+    const float sm = l - sl / (float)V;
+    loss[row] = ((1.f - eps) * n + eps * sm) + zeta * (l * l);
+}
+
+__global__ __launch_bounds__(256) void ce_fwd_opts_kernel(const float* __restrict__ logits, int ldl,
+                                                          const int64_t* __restrict__ target, float* __restrict__ loss,
+                                                          float* __restrict__ nll, float* __restrict__ lse, int rows, int V,
+                                                          float eps, float zeta) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const float* p = logits + (size_t)row * ldl;
+    float mx = -3.0e38f;
+    for (int c = lane; c < V; c += 64) mx = fmaxf(mx, p[c]);
+    mx = wave_max(mx);
+    float s = 0.f, sl = 0.f;
+    for (int c = lane; c < V; c += 64) {
+        const float x = p[c];
+        s += expf(x - mx);
+        sl += x;
+    }
+    s = wave_sum(s);
+    sl = wave_sum(sl);
+    if (lane == 0) ce_opts_row_out(p, target, loss, nll, lse, row, V, mx + logf(s), sl, eps, zeta);
+}
+
+// rows of at most 768 logits with a 16-byte aligned stride: read ONCE into registers (as ce_fwd_vec_kernel)
+__global__ __launch_bounds__(256) void ce_fwd_opts_vec_kernel(const float* __restrict__ logits, int ldl,
+                                                              const int64_t* __restrict__ target, float* __restrict__ loss,
+                                                              float* __restrict__ nll, float* __restrict__ lse, int rows,
+                                                              int V, float eps, float zeta) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const float* p = logits + (size_t)row * ldl;
+    f32x4 x[3];
+    float mx = -3.0e38f, sl = 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int c = 4 * lane + 256 * k;
+        x[k] = c < ldl ? *(const f32x4*)(p + c) : (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (c + e >= V) x[k][e] = -3.0e38f;
+            else sl += x[k][e];
+            mx = fmaxf(mx, x[k][e]);
+        }
+    }
+    mx = wave_max(mx);
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s += (4 * lane + 256 * k + e < V) ? expf(x[k][e] - mx) : 0.f;
+    s = wave_sum(s);
+    sl = wave_sum(sl);
+    if (lane == 0) ce_opts_row_out(p, target, loss, nll, lse, row, V, mx + logf(s), sl, eps, zeta);
+}
+
+// per row: a = 1 + 2 zeta lse scales the softmax; the target column loses (1 - eps) + eps / V, every other one eps / V
+__global__ __launch_bounds__(256) void ce_bwd_opts_vec_kernel(const float* __restrict__ logits, int ldl,
+                                                              const int64_t* __restrict__ target,
+                                                              const float* __restrict__ lse, const float* __restrict__ g,
+                                                              bf16* __restrict__ dlogits, int ldd, int rows, int V, float eps,
+                                                              float zeta) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const float* p = logits + (size_t)row * ldl;
+    bf16* o = dlogits + (size_t)row * ldd;
+    const float l = lse[row], gr = g[row];
+    const int t = (int)target[row];
+    const float a = 1.f + 2.f * zeta * l, u = eps / (float)V, ut = (1.f - eps) + u;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int c = 4 * lane + 256 * k;
+        if (c >= ldd) break;
+        const f32x4 x = c < ldl ? *(const f32x4*)(p + c) : (f32x4){0.f, 0.f, 0.f, 0.f};
+        bf16x4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            v[e] = f2bf(c + e < V ? gr * (a * expf(x[e] - l) - (c + e == t ? ut : u)) : 0.f);
+        *(bf16x4*)(o + c) = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void ce_bwd_opts_kernel(const float* __restrict__ logits, int ldl,
+                                                          const int64_t* __restrict__ target, const float* __restrict__ lse,
+                                                          const float* __restrict__ g, bf16* __restrict__ dlogits, int ldd,
+                                                          int rows, int V, float eps, float zeta) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const float* p = logits + (size_t)row * ldl;
+    bf16* o = dlogits + (size_t)row * ldd;
+    const float l = lse[row], gr = g[row];
+    const int t = (int)target[row];
+    const float a = 1.f + 2.f * zeta * l, u = eps / (float)V, ut = (1.f - eps) + u;
+    for (int c = lane; c < ldd; c += 64) {
+        float v = 0.f;
+        if (c < V) v = gr * (a * expf(p[c] - l) - (c == t ? ut : u));
+        o[c] = f2bf(v);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Per-family NLL: sum[k] / count[k] over the rows whose target is of class k (class_of_token[target]) and is not the pad id.
+// Deterministic: block b takes rows b * 256 + tid, + nblk * 256, ... one after the other, a butterfly joins the lanes, the
+// four waves add in order, and one final workgroup adds the blocks' partials in order.  No atomics.
+#define NLL_CLASSES_MAX 8
+__global__ __launch_bounds__(256) void nll_by_class_partial_kernel(const float* __restrict__ nll, const int64_t* __restrict__ target,
+                                                                   const int* __restrict__ class_of_token, int V, int C, int pad,
+                                                                   int rows, float* __restrict__ part_sum,
+                                                                   int* __restrict__ part_cnt) {
+    __shared__ float rs[4][NLL_CLASSES_MAX];
+    __shared__ int rc[4][NLL_CLASSES_MAX];
+    float acc[NLL_CLASSES_MAX];
+    int cnt[NLL_CLASSES_MAX];
+#pragma unroll
+    for (int k = 0; k < NLL_CLASSES_MAX; ++k) acc[k] = 0.f, cnt[k] = 0;
+    for (long long r = (long long)blockIdx.x * 256 + threadIdx.x; r < rows; r += (long long)gridDim.x * 256) {
+        const long long t = target[r];
+        if (t < 0 || t >= V || t == pad) continue;
+        const int cls = class_of_token[t];
+        const float v = nll[r];
+#pragma unroll
+        for (int k = 0; k < NLL_CLASSES_MAX; ++k)
+            if (cls == k) acc[k] += v, cnt[k] += 1;
+    }
+#pragma unroll
+    for (int k = 0; k < NLL_CLASSES_MAX; ++k) {
+        acc[k] = wave_sum(acc[k]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) cnt[k] += __shfl_xor(cnt[k], o, 64);
+        if ((threadIdx.x & 63) == 0) rs[threadIdx.x >> 6][k] = acc[k], rc[threadIdx.x >> 6][k] = cnt[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < C) {
+        const int k = threadIdx.x;
+        part_sum[(size_t)blockIdx.x * C + k] = ((rs[0][k] + rs[1][k]) + rs[2][k]) + rs[3][k];
+        part_cnt[(size_t)blockIdx.x * C + k] = rc[0][k] + rc[1][k] + rc[2][k] + rc[3][k];
+    }
+}
+__global__ void nll_by_class_final_kernel(const float* __restrict__ part_sum, const int* __restrict__ part_cnt, int nblk, int C,
+                                          float* __restrict__ sum, int* __restrict__ count) {
+    const int k = threadIdx.x;
+    if (k >= C) return;
+    float s = 0.f;
+    int n = 0;
+    for (int b = 0; b < nblk; ++b) s += part_sum[(size_t)b * C + k], n += part_cnt[(size_t)b * C + k];
+    sum[k] = s;
+    count[k] = n;
+}
+
+// ---------------------------------------------------------------------------------------------
 // K12/K13: global grad norm (deterministic two-stage) and clipped Adam on the flat buffers
 // (train.py:159-169; torch.optim.Adam defaults; clip_grad_norm_ coefficient = min(1, c/(n+1e-6)))
 __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restrict__ g, size_t n,
@@ -1302,6 +1473,53 @@ extern "C" int commu_ce_bwd(const float* logits, int ldl, const int64_t* target,
     else
         COMMU_LAUNCH(ce_bwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, logits, ldl, target, lse,
                        g, (bf16*)dlogits, ldd, rows, V);
+    COMMU_LAUNCH_CHECK();
+    return 0;
+}
+
+// (the same layout conditions as commu_ce_fwd / commu_ce_bwd pick the register kernels)
+extern "C" int commu_ce_fwd_opts(const float* logits, int ldl, const int64_t* target, float* loss, float* nll, float* lse,
+                                 int rows, int V, float label_smoothing, float z_loss, hipStream_t stream) {
+    if (!(label_smoothing >= 0.f && label_smoothing < 1.f) || !(z_loss >= 0.f && z_loss < INFINITY) || V <= 0) return -22;
+    if (rows <= 0) return 0;
+    if (V <= 768 && ldl <= 768 && (ldl % 4) == 0 && (((size_t)logits) & 15) == 0)
+        COMMU_LAUNCH(ce_fwd_opts_vec_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, logits, ldl, target, loss, nll, lse,
+                     rows, V, label_smoothing, z_loss);
+    else
+        COMMU_LAUNCH(ce_fwd_opts_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, logits, ldl, target, loss, nll, lse, rows,
+                     V, label_smoothing, z_loss);
+    COMMU_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int commu_ce_bwd_opts(const float* logits, int ldl, const int64_t* target, const float* lse, const float* g,
+                                 void* dlogits, int ldd, int rows, int V, float label_smoothing, float z_loss,
+                                 hipStream_t stream) {
+    if (!(label_smoothing >= 0.f && label_smoothing < 1.f) || !(z_loss >= 0.f && z_loss < INFINITY) || V <= 0) return -22;
+    if (rows <= 0) return 0;
+    if (V <= 768 && ldl <= 768 && ldd <= 768 && (ldl % 4) == 0 && (ldd % 4) == 0 && ldd <= ldl + 3 && (((size_t)logits) & 15) == 0 &&
+        (((size_t)dlogits) & 7) == 0)
+        COMMU_LAUNCH(ce_bwd_opts_vec_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, logits, ldl, target, lse, g,
+                     (bf16*)dlogits, ldd, rows, V, label_smoothing, z_loss);
+    else
+        COMMU_LAUNCH(ce_bwd_opts_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, logits, ldl, target, lse, g,
+                     (bf16*)dlogits, ldd, rows, V, label_smoothing, z_loss);
+    COMMU_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int commu_nll_by_class_blocks(int rows) {
+    const int n = (rows + 1023) / 1024;          // at least four rows per thread before a second workgroup starts
+    return n < 1 ? 1 : (n > 256 ? 256 : n);
+}
+
+extern "C" int commu_nll_by_class(const float* nll, const int64_t* target, const int* class_of_token, int V, int C, int pad,
+                                  int rows, float* part_sum, int* part_cnt, int nblk, float* sum, int* count,
+                                  hipStream_t stream) {
+    if (C < 1 || C > NLL_CLASSES_MAX || V <= 0 || rows < 0 || nblk < 1 || nblk > 1024) return -22;
+    COMMU_LAUNCH(nll_by_class_partial_kernel, dim3(nblk), dim3(256), 0, stream, nll, target, class_of_token, V, C, pad, rows,
+                 part_sum, part_cnt);
+    COMMU_LAUNCH(nll_by_class_final_kernel, dim3(1), dim3(64), 0, stream, part_sum, part_cnt, nblk, C, sum, count);
     COMMU_LAUNCH_CHECK();
     return 0;
 }

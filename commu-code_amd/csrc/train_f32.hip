@@ -450,6 +450,21 @@ __global__ __launch_bounds__(256) void ce_bwd_f32_kernel(const float* __restrict
         dl[(size_t)row * ldd + c] = gr * (expf(logits[(size_t)row * ldl + c] - l) - (c == t ? 1.f : 0.f));
 }
 
+// the same with loss options (label smoothing eps, z-loss zeta; csrc/elementwise.hip states the formulas):
+// dlogits[r, c] = g[r] ((1 + 2 zeta lse[r]) softmax(logits[r])[c] - (1 - eps) [c == target[r]] - eps / V), 0 in [V, ldd)
+__global__ __launch_bounds__(256) void ce_bwd_opts_f32_kernel(const float* __restrict__ logits, int ldl,
+                                                              const long long* __restrict__ target, const float* __restrict__ lse,
+                                                              const float* __restrict__ g, float* __restrict__ dl, int ldd, int rows,
+                                                              int V, float eps, float zeta) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const float l = lse[row], gr = g[row];
+    const long long t = target[row];
+    const float a = 1.f + 2.f * zeta * l, u = eps / (float)V, ut = (1.f - eps) + u;
+    for (int c = lane; c < ldd; c += 64)
+        dl[(size_t)row * ldd + c] = c < V ? gr * (a * expf(logits[(size_t)row * ldl + c] - l) - (c == t ? ut : u)) : 0.f;
+}
+
 // gE[v] += scale * sum over the rows of token v (sorted order: perm / offs of commu_token_order) of drop(dX[row]); the
 // dropout is the embedding site's (element index row * D + c).  One workgroup per vocabulary row.
 __global__ __launch_bounds__(256) void embed_bwd_f32_kernel(const long long* __restrict__ perm, const long long* __restrict__ offs,
@@ -633,6 +648,23 @@ extern "C" int commu_ce_bwd_f32(const float* logits, int ldl, const long long* t
                                 float* dlogits, int ldd, int rows, int V, hipStream_t stream) {
     if (rows <= 0 || V <= 0) return -22;
     COMMU_LAUNCH(ce_bwd_f32_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, logits, ldl, target, lse, g, dlogits, ldd, rows, V);
+    COMMU_LAUNCH_CHECK();
+    return 0;
+}
+
+// (the fp32 schedule's logits are fp32 like the bf16 one's: the forward with options is commu_ce_fwd_opts under this name)
+extern "C" int commu_ce_fwd_opts_f32(const float* logits, int ldl, const long long* target, float* loss, float* nll, float* lse,
+                                     int rows, int V, float label_smoothing, float z_loss, hipStream_t stream) {
+    return commu_ce_fwd_opts(logits, ldl, (const int64_t*)target, loss, nll, lse, rows, V, label_smoothing, z_loss, stream);
+}
+
+extern "C" int commu_ce_bwd_opts_f32(const float* logits, int ldl, const long long* target, const float* lse, const float* g,
+                                     float* dlogits, int ldd, int rows, int V, float label_smoothing, float z_loss,
+                                     hipStream_t stream) {
+    if (rows <= 0 || V <= 0 || ldd < V) return -22;
+    if (!(label_smoothing >= 0.f && label_smoothing < 1.f) || !(z_loss >= 0.f && z_loss < INFINITY)) return -22;
+    COMMU_LAUNCH(ce_bwd_opts_f32_kernel, dim3((rows + 3) / 4), dim3(256), 0, stream, logits, ldl, target, lse, g, dlogits, ldd,
+                 rows, V, label_smoothing, z_loss);
     COMMU_LAUNCH_CHECK();
     return 0;
 }

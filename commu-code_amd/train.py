@@ -15,6 +15,9 @@ checkpoint_best written by rank 0 between barriers (C7).  The reference's hyper-
 from the same entry point.  Fine-tuning flags (not in the reference either): --init_checkpoint / --resume, --lr,
 --warmup_step, --weight_decay, --adamw and --param_groups (per-tensor lr multiplier / weight decay / frozen, see
 commu_amd.optim.resolve_groups); what can be refused without a dataset or a model is refused first (check_fine_tune_args).
+Loss options (not in the reference): --label_smoothing, --z_loss (the fused loss kernels of the training step; evaluation and
+the logs keep reporting the plain NLL) and --report_families (per-family validation NLL); refused first likewise
+(check_loss_args).  A checkpoint stores the position of the training batch stream, and --resume continues from it.
 """
 import argparse
 import math
@@ -44,7 +47,8 @@ def parse_args(argv=None):
                         "when a micro-batch is small enough for the host's launch rate to bound the step)")
     p.add_argument("--parity", action="store_true",
                    help="(not in the reference) train in the reference's fp32 arithmetic: fp32 forward with dropout, fp32 "
-                        "backward, eager steps (model.fp32_training + model.parity_fp32; evaluation in fp32 too)")
+                        "backward, eager steps (model.fp32_training + model.parity_fp32; evaluation in fp32 too); "
+                        "--label_smoothing and --z_loss apply to it as well (the fp32 loss kernels)")
     p.add_argument("--max_step", type=int, default=None)
     p.add_argument("--log_interval", type=int, default=None)
     p.add_argument("--eval_interval", type=int, default=None)
@@ -57,7 +61,9 @@ def parse_args(argv=None):
                         "generation loader reads it); the optimiser is fresh and the step starts at 0")
     p.add_argument("--resume", type=str, default=None, metavar="FILE",
                    help="(not in the reference) continue a run: model, optimiser, scheduler, train_step and best_val_loss of "
-                        "a checkpoint.  The batch stream is not part of a checkpoint: the resumed run draws its shuffle from "
+                        "a checkpoint, and the batch stream from the stored seed, epoch and batch index (same number of ranks, "
+                        "batch size, tgt_length and corpus).  Otherwise, and for a checkpoint without a stored position, the "
+                        "resumed run draws a fresh shuffle from "
                         "seed + 1000 * rank + train_step")
     p.add_argument("--lr", type=float, default=None, help="(not in the reference) overrides TRAIN.lr")
     p.add_argument("--warmup_step", type=int, default=None, help="(not in the reference) overrides TRAIN.warmup_step")
@@ -69,6 +75,18 @@ def parse_args(argv=None):
                    help="(not in the reference) JSON text or a JSON file: a list of {\"match\": glob or list of globs over the "
                         "state-dict names, \"lr_mult\": 1, \"weight_decay\": the default, \"frozen\": false}; the first "
                         "match wins, unmatched tensors keep the defaults")
+    # -- not in the reference: loss options of the training step, per-family validation report
+    p.add_argument("--label_smoothing", type=float, default=None, metavar="EPS",
+                   help="(not in the reference) overrides TRAIN.label_smoothing: train on (1 - EPS) nll + EPS * cross entropy "
+                        "against the uniform distribution over the vocabulary, 0 <= EPS < 1 (evaluation and the logs report "
+                        "the plain nll)")
+    p.add_argument("--z_loss", type=float, default=None, metavar="ZETA",
+                   help="(not in the reference) overrides TRAIN.z_loss: adds ZETA * logsumexp(logits)^2 per token to the "
+                        "training loss, ZETA >= 0")
+    p.add_argument("--report_families", action="store_true", default=None,
+                   help="(not in the reference) overrides TRAIN.report_families: every evaluation also logs the nll and the "
+                        "token count per token family (pad/EOS/Bar, position, chord, velocity, pitch, duration, meta, "
+                        "other); checkpoint_best.pt keeps the report under \"val_families\"")
     return p.parse_args(argv)
 
 
@@ -94,14 +112,25 @@ def check_fine_tune_args(args):
         raise ValueError(f"--param_groups: {exc}") from None
 
 
+def check_loss_args(args):
+    """The refusals of the loss options that need neither a dataset nor a model."""
+    from commu_amd.model.model import check_loss_options
+    eps, zeta = getattr(args, "label_smoothing", None), getattr(args, "z_loss", None)
+    try:
+        check_loss_options(0.0 if eps is None else eps, 0.0 if zeta is None else zeta)
+    except ValueError as exc:
+        raise ValueError(f"--label_smoothing / --z_loss: {exc}") from None
+
+
 def main(argv=None):
     from commu_amd.ddp import GradReducer
     from commu_amd.model.config_helper import get_default_cfg_training
     from commu_amd.model.dataset import ComMUDataset
     from commu_amd.train import (Trainer, build_model, evaluate_best_checkpoint, load_checkpoint, read_checkpoint,
-                                 save_checkpoint)
+                                 resume_position, save_checkpoint, stream_key)
     args = parse_args(argv)
     group_spec = check_fine_tune_args(args)
+    check_loss_args(args)
     cfg = get_default_cfg_training()
     cfg.defrost()
     for name in ("num_layers", "num_heads", "units", "inner_size"):
@@ -110,7 +139,7 @@ def main(argv=None):
     for name in ("tgt_length", "mem_length", "batch_size", "batch_chunk", "max_step", "log_interval", "eval_interval"):
         if getattr(args, name) is not None:
             cfg.TRAIN[name] = getattr(args, name)
-    for name in ("lr", "warmup_step", "weight_decay"):
+    for name in ("lr", "warmup_step", "weight_decay", "label_smoothing", "z_loss", "report_families"):
         if getattr(args, name) is not None:
             cfg.TRAIN[name] = getattr(args, name)
     cfg.freeze()
@@ -145,8 +174,9 @@ def main(argv=None):
     assert cfg.TRAIN.batch_size % num_gpus == 0
     batch_size = cfg.TRAIN.batch_size // num_gpus
     assert batch_size % cfg.TRAIN.batch_chunk == 0
-    train_iter = dataset.get_iterator(batch_size, cfg.TRAIN.tgt_length, device, "train", True,
-                                      seed=seed + 1000 * rank)                  # Q9
+    stream_seed = seed + 1000 * rank                                            # Q9
+    train_iter = dataset.get_iterator(batch_size, cfg.TRAIN.tgt_length, device, "train", True, seed=stream_seed)
+    key = stream_key(num_gpus, batch_size, cfg.TRAIN.tgt_length, dataset.train_seq_length)
     val_iter = dataset.eval_iterator(cfg.EVALUATE.batch_size, cfg.EVALUATE.tgt_length, device, "valid",
                                      local_rank=rank, world_size=num_gpus)
     test_iter = dataset.eval_iterator(cfg.EVALUATE.batch_size, cfg.EVALUATE.tgt_length, device, "test",
@@ -158,6 +188,7 @@ def main(argv=None):
     if getattr(args, "parity", False):
         model.fp32_training = True
         model.parity_fp32 = True
+    model.loss_options = {"label_smoothing": cfg.TRAIN.label_smoothing, "z_loss": cfg.TRAIN.z_loss}
     log(f"#total params = {sum(p.nelement() for p in model.parameters())}")
     if args.init_checkpoint is not None:
         log(f"weights of {args.init_checkpoint} (missing: {list(missing)}, unexpected: {list(unexpected)})")
@@ -170,7 +201,8 @@ def main(argv=None):
     best_val_nll = float("inf")
     if args.resume is not None:
         # (a checkpoint whose optimiser grouping differs from these flags is refused by FusedAdam.load_state_dict)
-        trainer.train_step, best = load_checkpoint(args.resume, model, trainer.optimizer, trainer.scheduler)
+        ck = read_checkpoint(args.resume)
+        trainer.train_step, best = load_checkpoint(args.resume, model, trainer.optimizer, trainer.scheduler, ck=ck)
         best_val_nll = float("inf") if best is None else float(best)
         trainer._log_step0 = trainer.train_step                                 # the logging window starts here
         if reducer is not None:
@@ -178,16 +210,34 @@ def main(argv=None):
         log(f"resumed {args.resume} at step {trainer.train_step}")
         if trainer.train_step >= cfg.TRAIN.max_step:
             raise ValueError(f"--resume: the checkpoint is at step {trainer.train_step}, max_step is {cfg.TRAIN.max_step}")
-        # the batch stream is not part of a checkpoint: a fresh shuffle, not the one the run started with
-        train_iter = dataset.get_iterator(batch_size, cfg.TRAIN.tgt_length, device, "train", True,
-                                          seed=seed + 1000 * rank + trainer.train_step)
+        found = resume_position(ck, rank, key)
+        if found is not None:          # the stream of the checkpoint's run, from the batch after its last step
+            stream_seed, start = found
+            train_iter = dataset.get_iterator(batch_size, cfg.TRAIN.tgt_length, device, "train", True, seed=stream_seed,
+                                              start=start)
+            log(f"batch stream resumed at epoch {start[0]}, batch {start[1]} (stream seed {stream_seed})")
+        else:          # no position in the checkpoint, or one of another stream layout: a fresh shuffle
+            stream_seed = seed + 1000 * rank + trainer.train_step
+            train_iter = dataset.get_iterator(batch_size, cfg.TRAIN.tgt_length, device, "train", True, seed=stream_seed)
+        del ck
 
-    def checkpoint(name, val_nll):                                              # train.py:29-54 (C7)
+    def data_position():
+        """stream_key + {"streams": [seed, epoch, index] of every rank}: the seed each rank's stream was really drawn from
+        (after a fresh shuffle on resume that is not seed + 1000 * rank) -- one packed all-reduce, each rank fills its slots"""
+        own = train_iter.position
+        slots = [0.0] * (3 * num_gpus)
+        slots[3 * rank:3 * rank + 3] = float(stream_seed), float(own["epoch"]), float(own["index"])
+        if reducer is not None:
+            slots = reducer.sum_scalars(slots, device=device)
+        return dict(key, streams=[[int(x) for x in slots[3 * r:3 * r + 3]] for r in range(num_gpus)])
+
+    def checkpoint(name, val_nll, val_families=None):                           # train.py:29-54 (C7)
+        position = data_position()
         if reducer is not None:
             reducer.barrier()
         if rank == 0:
             save_checkpoint(os.path.join(work_dir, name), model, trainer.optimizer, dataset.vocab, trainer.train_step,
-                            val_nll, trainer.scheduler)
+                            val_nll, trainer.scheduler, data_position=position, val_families=val_families)
         if reducer is not None:
             reducer.barrier()
 
@@ -205,13 +255,17 @@ def main(argv=None):
             t_log = time.time()
         if step % cfg.TRAIN.eval_interval == 0:
             t0 = time.time()
-            val_tok, val_nll = trainer.evaluate_reduced(val_iter)
-            log("Eval step {}, time={}s, val nll={}, val ppl={},".format(step, time.time() - t0, val_nll,
-                                                                        math.exp(min(val_nll, 50.0))))
+            fam = {} if cfg.TRAIN.report_families else None
+            val_tok, val_nll = trainer.evaluate_reduced(val_iter, families=fam)
+            msg = "Eval step {}, time={}s, val nll={}, val ppl={},".format(step, time.time() - t0, val_nll,
+                                                                          math.exp(min(val_nll, 50.0)))
+            if fam is not None:
+                msg += " families: " + ", ".join(f"{k} nll={v['nll']:.4f} tokens={v['tokens']}" for k, v in fam.items())
+            log(msg)
             checkpoint("checkpoint_last.pt", val_nll)
             if val_nll < best_val_nll:
                 best_val_nll = val_nll
-                checkpoint("checkpoint_best.pt", best_val_nll)
+                checkpoint("checkpoint_best.pt", best_val_nll, val_families=fam)
                 t0 = time.time()
                 test_tok, test_nll = trainer.evaluate_reduced(test_iter)
                 log("Test step {}, time={}s, test nll={}, test ppl={}, #evaluated tokens={}".format(

@@ -234,6 +234,22 @@ int commu_ce_fwd(const float* logits, int ldl, const int64_t* target, float* nll
                  int V, hipStream_t stream);
 int commu_ce_bwd(const float* logits, int ldl, const int64_t* target, const float* lse, const float* g,
                  void* dlogits_bf16, int ldd, int rows, int V, hipStream_t stream);
+/* The loss with options (not in the reference): label_smoothing eps in [0, 1), z_loss zeta >= 0 (else -22).  Per row, over
+ * the V real tokens (pad columns [V, ld) never enter a sum; the backward writes them as zero):
+ *   nll = lse - l_t,  smooth = lse - sum_j l_j / V,  loss = (1 - eps) nll + eps smooth + zeta lse^2
+ *   dlogits_j = g ((1 + 2 zeta lse) softmax_j - (1 - eps) [j == t] - eps / V)
+ * The forward writes loss, nll and lse; the backward reads that lse.  eps = zeta = 0: the bits of commu_ce_fwd / commu_ce_bwd. */
+int commu_ce_fwd_opts(const float* logits, int ldl, const int64_t* target, float* loss, float* nll, float* lse, int rows,
+                      int V, float label_smoothing, float z_loss, hipStream_t stream);
+int commu_ce_bwd_opts(const float* logits, int ldl, const int64_t* target, const float* lse, const float* g,
+                      void* dlogits_bf16, int ldd, int rows, int V, float label_smoothing, float z_loss, hipStream_t stream);
+/* Per-class NLL: sum[k] = sum of nll[r], count[k] = number of rows r < rows with class_of_token[target[r]] == k, over the
+ * rows whose target is in [0, V) and is not `pad` (the rows of loss weight 0; pad < 0: none).  C <= 8 classes.  Two passes
+ * in a fixed order, no atomics: part_sum / part_cnt hold nblk x C partials (nblk <= 1024; commu_nll_by_class_blocks(rows)
+ * is the count the host wrappers use), then one workgroup adds them block after block.  Two runs give the same bits. */
+int commu_nll_by_class_blocks(int rows);
+int commu_nll_by_class(const float* nll, const int64_t* target, const int* class_of_token, int V, int C, int pad, int rows,
+                       float* part_sum, int* part_cnt, int nblk, float* sum, int* count, hipStream_t stream);
 /* out[0] = scale * mean(nll[target != pad])   (train.py:148-149); keeps the count in cnt_ws; NaN when every
  * target is the pad id (mean of an empty selection, as in the reference) */
 int commu_masked_mean(const float* nll, const int64_t* target, int n, int pad, float scale, float* sum_ws,
@@ -1321,6 +1337,12 @@ int commu_layernorm_bwd_f32(const float* dy, int lddy, const float* add, int lda
 /* model.py:64-73 backward in fp32: dlogits[r][c] = g[r] (exp(logits[r][c] - lse[r]) - [c == target[r]]), c < V */
 int commu_ce_bwd_f32(const float* logits, int ldl, const long long* target, const float* lse, const float* g,
                      float* dlogits, int ldd, int rows, int V, hipStream_t stream);
+/* the fp32 forms of commu_ce_fwd_opts / commu_ce_bwd_opts.  The fp32 schedule's logits are fp32 like the bf16 one's, so the
+ * forward is commu_ce_fwd_opts under the name of its schedule; the backward writes fp32 dlogits, columns [V, ldd) as zero */
+int commu_ce_fwd_opts_f32(const float* logits, int ldl, const long long* target, float* loss, float* nll, float* lse, int rows,
+                          int V, float label_smoothing, float z_loss, hipStream_t stream);
+int commu_ce_bwd_opts_f32(const float* logits, int ldl, const long long* target, const float* lse, const float* g,
+                          float* dlogits, int ldd, int rows, int V, float label_smoothing, float z_loss, hipStream_t stream);
 /* model.py:409-420 + 585-586 backward: gE[v] += scale * sum over the rows of token v, in the order perm / offs of
  * commu_token_order, of dropout(dx[row]) (the embedding site: element index row * D + c) */
 int commu_embed_bwd_f32(const long long* perm, const long long* offs, const float* dx, int ldx, float* gE, int V, int D,
